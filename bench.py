@@ -1,20 +1,27 @@
 #!/usr/bin/env python3
 """bench.py -- headline benchmark of the MyZKP MSM / NTT prover path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--log2n 20] [--skip-cpu]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--log2n 20] [--dump-outputs DIR] [--full [--skip-cpu] ...]
 
-ONE JSON line on stdout (rank 0), under 8 KB: the contract's keys, `roofline`, `cpu_baseline`, the four numbers of
-BASELINE.json's metric as top-level scalars (MSM pairs/s and NTT elems/s at 2^20 and 2^24), the GPU's clock and power cap,
-and one time per sub-leg (`legs_ms`).  Everything else every leg measures -- phases, parity flags, notes -- goes to
-`bench_detail.json` beside this file (`--detail-file`; `detail_file` in the line names it).
+A plain run does only what the headline needs: set-up, the W warm-up and K timed steps of the KZG commit, and ONE JSON line on
+stdout (rank 0) with the contract's keys (`metric`, `value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step`, ...).
+`--dump-outputs DIR` writes what the last timed step computed (the commitment) as DIR/kzg_commitment.npy; the inputs are
+seeded, so two builds can be compared output for output.
+
+`--full` adds everything else, checked and measured as before: parity against the CPU oracle before timing, `roofline`,
+`cpu_baseline`, the four numbers of BASELINE.json's metric as top-level scalars (MSM pairs/s and NTT elems/s at 2^20 and 2^24),
+the GPU's clock and power cap, and one time per sub-leg (`legs_ms`), in a line under 8 KB.  Everything else every leg
+measures -- phases, parity flags, notes -- goes to `bench_detail.json` beside this file (`--detail-file`; `detail_file` in the
+line names it).  `--skip-cpu`, `--e2e-log2n`, `--strong-log2n`, `--strong-ntt-log2n`, `--extra-sizes`, `--no-two-in-flight`,
+`--sharded-legs-only`, `--detail-file` and `--inproc-devices` shape those further legs and act only with `--full`.
 
 A "step" is one pass of the hot path over one batch of synthetic input already resident in HBM:
   * primary (`value`): one KZG commit = BN254 G1 MSM of 2^log2n (scalar, point) pairs PER GPU against a device-resident SRS
     (BASELINE.json configs[2]; weak scaling: the N-GPU job is one MSM of N * 2^log2n pairs, contiguous shards, one
     all-gather of N 128-byte partials over RCCL, local fold -- configs[3] shape);
-  * `ntt`: one forward radix-2 NTT of 2^log2n BN254-Fr elements per GPU (configs[1]; N GPUs run N independent transforms;
-    ONE transform sharded over the ranks is the strong_scaling_ntt leg).
-Both are checked bit-for-bit against the CPU oracle before timing.  `roofline` prices the dominant kernel against HBM
+  * `ntt` (--full): one forward radix-2 NTT of 2^log2n BN254-Fr elements per GPU (configs[1]; N GPUs run N independent
+    transforms; ONE transform sharded over the ranks is the strong_scaling_ntt leg).
+With --full both are checked bit-for-bit against the CPU oracle before timing.  `roofline` prices the dominant kernel against HBM
 bandwidth as BASELINE.md section 4 defines it (MSM: 96 B per pair, NTT: 2*32 B per element); `alu_roofline` adds the
 integer-multiply roofline that actually binds.  One function per leg; main() only orders them.
 """
@@ -269,6 +276,11 @@ def parse_args(argv=None):
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--log2n", type=int, default=20)
+    ap.add_argument("--dump-outputs", type=str, default="", metavar="DIR",
+                    help="after the timed steps write the commitment of the last one to DIR/kzg_commitment.npy: float64 (2, 8), the affine "
+                         "x and y as eight little-endian 32-bit words each (exact in float64)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: parity vs the CPU oracle, the sub-legs, rooflines, extra sizes, the CPU baseline and the detail file")
     ap.add_argument("--skip-cpu", action="store_true", help="skip the cpu_baseline leg")
     ap.add_argument("--settle-s", type=float, default=0.5, help="untimed settle time per leg before the W warm-up steps")
     ap.add_argument("--e2e-log2n", type=int, default=22, help="degree of the end-to-end KZG run (0 = skip)")
@@ -569,9 +581,10 @@ def read_phases(B):
     return out
 
 
-def timed(B, step, K, W, price_mask=0, priced_in_timed_region=True):
+def timed(B, step, K, W, price_mask=0, priced_in_timed_region=True, capture=None):
     """The contract's timed region: W warm-up steps, then EXACTLY K steps between barrier + synchronize; returns its wall time
-    (max over ranks) and the kernel-phase averages of two further, untimed passes.
+    (max over ranks) and, with --full, the kernel-phase averages of two further, untimed passes (a plain run returns no phases).
+    capture(): called right after the timed region, its result kept as B.captured (what the last timed step computed).
     priced_in_timed_region (the headline and the generic MSM): the one priced kernel (price_mask) carries its HIP-event pair INSIDE the
     timed region, as the roofline contract asks (0.1 % of a 1.4-ms step).  False (the short sub-legs: transforms, LDE, Merkle): the
     timed region carries NO event -- the pair's two marker packets are ~5-8 us, 7-14 % of such a step -- so `ms_per_step` and
@@ -602,6 +615,11 @@ def timed(B, step, K, W, price_mask=0, priced_in_timed_region=True):
     barrier_sync(B)
     dt = time.perf_counter() - t0
     L.mzk_prof_enable(0)
+    if capture is not None:
+        B.captured = capture()
+    if not B.args.full:
+        L.mzk_prof_reset()
+        return max_over_ranks(B, dt), {}
     priced = read_phases(B)
     priced_tag, priced_step_ms = "_in_timed_region", None
     if not priced_in_timed_region:
@@ -1627,16 +1645,61 @@ def compact_line(line):
     return line
 
 
+def headline_line(B, srs_dt):
+    """The keys every run prints: the contract's, measured over the K timed KZG commits (srs_dt seconds), and what they ran on."""
+    n, K, world, lg, dist = B.n, B.K, B.world, B.args.log2n, B.dist
+    return {
+        "metric": METRIC,
+        "value": world * n / (srs_dt / K), "unit": "pairs/s", "n_gpus": world, "steps": K, "warmup": B.W, "ms_per_step": srs_dt / K * 1e3,
+        "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "u32x9 (29-bit limbs, 254-bit Montgomery)", "data": "synthetic",
+        # `value` is measured at the library's default window width for this SRS size (17 bits at 2^20 since round 3; BASELINE
+        # configs[2] names 16 bits: legs_ms.kzg_commit_16_bit_windows) -- stated at top level so that a change of the default shows
+        "value_window_bits": B.srs_window_bits,
+        "config": {"workload": "KZG commit = BN254 G1 Pippenger MSM of 2^%d (scalar, point) pairs per GPU against a device-resident SRS (commit_kzg, kzg.rs:57-59); "
+                               "%d-bit signed windows (library default at this size), %d window tables built once at upload; N GPUs = one MSM of N*2^%d pairs "
+                               "(BASELINE configs[2]/[3])" % (lg, B.srs_window_bits, B.srs_table_windows, lg),
+                   "pairs_per_gpu": n, "seed": SEED, "window_bits": B.srs_window_bits, "sharding": "contiguous shards + all_gather of 128 B partials (RCCL) + local fold"},
+        "process_group": {"world_size": dist.get_world_size() if dist.is_initialized() else 1, "backend": dist.get_backend() if dist.is_initialized() else None,
+                          "forced_collectives": bool(B.forced),
+                          "launched_by": os.environ.get("MZK_BENCH_LAUNCHED_BY", "external launcher" if world > 1 else "single process")},
+        **({"REHEARSAL_NOT_A_MEASUREMENT": "ranks share one GPU, exchange over gloo via host (MZK_BENCH_SHARED_GPU_TEST=1)"} if B.shared_gpu_test else {}),
+    }
+
+
+def dump_outputs(B, out_dir):
+    """--dump-outputs: the affine commitment the last timed step returned (B.captured, 8 x 64-bit canonical limbs: x then y) as
+    out_dir/kzg_commitment.npy, float64 of shape (2, 8) -- each coordinate in eight little-endian 32-bit words, exact in float64."""
+    np = B.np
+    words = np.ascontiguousarray(B.captured.cpu().numpy().view(np.uint64).astype("<u8")).view("<u4").reshape(2, 8)
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "kzg_commitment.npy"), words.astype(np.float64))
+
+
+def teardown(B):
+    if B.dist.is_initialized():
+        B.dist.barrier()
+        B.dist.destroy_process_group()
+
+
 def main():
     T_START = time.perf_counter()
     args = parse_args()
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python bench.py --gpus N` by itself: become the launcher BEFORE anything touches the GPU
         sys.exit(launch_ranks(args.gpus, sys.argv[1:]))
-    sysfs = gpu_sysfs_snapshot()           # clock range and power cap of the cards, read before the HIP runtime starts
+    sysfs = gpu_sysfs_snapshot() if args.full else {}    # clock range and power cap of the cards, read before the HIP runtime starts
     B = setup(args, T_START)
     torch, L, mz, n, K, W, world, rank = B.torch, B.L, B.mz, B.n, B.K, B.W, B.world, B.rank
     make_inputs(B)
+    if not args.full:
+        # a plain run: the headline's timed region, its outputs and its line, nothing else
+        srs_dt, _ = timed(B, lambda: srs_step(B), K, W, 1 << PH_ACC, capture=lambda: B.result_srs.clone())
+        if rank == 0:
+            if args.dump_outputs:
+                dump_outputs(B, args.dump_outputs)
+            print(json.dumps(headline_line(B, srs_dt)))
+        teardown(B)
+        return
     props = torch.cuda.get_device_properties(B.dev)
     try:
         pci = "%04x:%02x:%02x.0" % (props.pci_domain_id, props.pci_bus_id, props.pci_device_id)
@@ -1650,7 +1713,9 @@ def main():
     # kernel inside the region (0.1 % of the step); the short sub-legs carry none and price their kernels in a pass of their own.
     T = {}
     T["msm"] = timed(B, lambda: msm_step(B), K, W, 1 << PH_ACC)
-    T["srs"] = timed(B, lambda: srs_step(B), K, W, 1 << PH_ACC)
+    T["srs"] = timed(B, lambda: srs_step(B), K, W, 1 << PH_ACC, capture=lambda: B.result_srs.clone())
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(B, args.dump_outputs)
     clock_under_load = leg_clock_under_load(B, lambda: srs_step(B), card)       # (every rank: the step holds the gather)
     if B.all_legs:
         T["ntt"] = timed(B, lambda: ntt_step(B), K, W, 1 << PH_NTT_TOTAL, priced_in_timed_region=False)
@@ -1698,29 +1763,16 @@ def main():
            "how": "sysfs (pp_dpm_sclk, hwmon power1_cap) read before the HIP runtime starts; the clock under load from hwmon freq1_input during a further, "
                   "untimed pass of the headline step"}
     lg = args.log2n
-    out = {
-        "metric": METRIC,
-        "value": srs_rate, "unit": "pairs/s", "n_gpus": world, "steps": K, "warmup": W, "ms_per_step": srs_ms,
-        "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "u32x9 (29-bit limbs, 254-bit Montgomery)", "data": "synthetic",
-        # `value` is measured at the library's default window width for this SRS size (17 bits at 2^20 since round 3; BASELINE
-        # configs[2] names 16 bits: legs_ms.kzg_commit_16_bit_windows) -- stated at top level so that a change of the default shows
-        "value_window_bits": B.srs_window_bits,
-        "config": {"workload": "KZG commit = BN254 G1 Pippenger MSM of 2^%d (scalar, point) pairs per GPU against a device-resident SRS (commit_kzg, kzg.rs:57-59); "
-                               "%d-bit signed windows (library default at this size), %d window tables built once at upload; N GPUs = one MSM of N*2^%d pairs "
-                               "(BASELINE configs[2]/[3])" % (lg, B.srs_window_bits, B.srs_table_windows, lg),
-                   "pairs_per_gpu": n, "seed": SEED, "window_bits": B.srs_window_bits, "sharding": "contiguous shards + all_gather of 128 B partials (RCCL) + local fold"},
+    out = headline_line(B, srs_dt)
+    out.update({
         "roofline": R["srs"],
         "gpu_clock_mhz_max": clk_max, "power_cap_w": cap_w, "gpu_clock_mhz_under_load": (clock_under_load or {}).get("median_mhz"),
         # two boxes compared kernel for kernel: chip-wide time per mixed addition of the priced kernel, and the same in SIMD cycles per
         # wave-level addition (64 lanes) at the clock this line reports: t x f x SIMDs / (additions / 64)
         "accumulate_ns_per_madd": None if _nan(srs_acc_ms) else srs_acc_ms * 1e6 / madds,
         "accumulate_cycles_per_madd_at_reported_clock": None if _nan(srs_acc_ms) or not clk_rep else srs_acc_ms * 1e-3 * clk_rep * 1e6 * simds / (madds / 64.0),
-        "process_group": {"world_size": B.dist.get_world_size() if B.dist.is_initialized() else 1, "backend": B.dist.get_backend() if B.dist.is_initialized() else None,
-                          "forced_collectives": bool(B.forced),
-                          "launched_by": os.environ.get("MZK_BENCH_LAUNCHED_BY", "external launcher" if world > 1 else "single process")},
-        **({"REHEARSAL_NOT_A_MEASUREMENT": "ranks share one GPU, exchange over gloo via host (MZK_BENCH_SHARED_GPU_TEST=1)"} if B.shared_gpu_test else {}),
         "parity": parity,
-    }
+    })
     # ---- BASELINE.json's metric as top-level scalars: MSM pairs/s and NTT elems/s at 2^20 and 2^24 (the literal "G1 MSM" on
     # arbitrary points beside the KZG-commit special case `value` measures)
     out["msm_2p%d_pairs_per_s" % lg], out["msm_2p%d_ms" % lg] = srs_rate, srs_ms
@@ -1834,9 +1886,7 @@ def main():
             except OSError as ex:
                 out["detail_file"] = "not written: %s" % str(ex)[:80]
         print(json.dumps(out))
-    if B.dist.is_initialized():
-        B.dist.barrier()
-        B.dist.destroy_process_group()
+    teardown(B)
 
 
 if __name__ == "__main__":

@@ -31,9 +31,9 @@ def test_one_rank_nccl_group_runs_every_collective_of_the_sharded_path():
 
 
 def test_bench_sharded_legs_through_the_nccl_branch_on_one_gpu():
-    """`bench.py --gpus 1 --force-process-group`: the weak-scaling headline (partial -> gather -> fold every step), the
+    """`bench.py --full --gpus 1 --force-process-group`: the weak-scaling headline (partial -> gather -> fold every step), the
     fixed-size MSM, the end-to-end KZG and the sharded transform all run their exchange steps over a one-rank nccl group."""
-    r = _run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--force-process-group", "--steps", "3", "--warmup", "1", "--log2n", "16",
+    r = _run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "1", "--force-process-group", "--steps", "3", "--warmup", "1", "--log2n", "16",
               "--e2e-log2n", "16", "--strong-log2n", "16", "--strong-ntt-log2n", "16", "--extra-sizes", "", "--skip-cpu", "--sharded-legs-only"], 1200)
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert r.returncode == 0 and lines, "bench failed (rc %d):\n%s\n%s" % (r.returncode, r.stdout[-2000:], r.stderr[-4000:])

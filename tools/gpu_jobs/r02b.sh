@@ -6,12 +6,12 @@ mkdir -p $O
 cd $R
 ( time timeout 2400 python -m pytest tests -m gpu -x -q --durations=8 ) > $O/r02b_pytest.log 2>&1
 echo "pytest rc=$?" >> $O/r02b_pytest.log
-timeout 1200 python bench.py > $O/r02b_bench.json 2> $O/r02b_bench.err
+timeout 1200 python bench.py --full > $O/r02b_bench.json 2> $O/r02b_bench.err
 cd /tmp && export TMPDIR=/tmp
-BENCH="$R/bench.py --steps 10 --warmup 2 --skip-cpu --extra-sizes= --e2e-log2n 0 --strong-log2n 0"
+BENCH="$R/bench.py --full --steps 10 --warmup 2 --skip-cpu --extra-sizes= --e2e-log2n 0 --strong-log2n 0"
 timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $O/r02b_prof -- python3 $BENCH > $O/r02b_bench_under_rocprof.json 2> $O/r02b_prof.err
 for c in FETCH_SIZE WRITE_SIZE; do
-  timeout 900 rocprofv3 --kernel-trace --pmc $c --output-format csv -d $O/r02b_pmc_$c -- python3 $R/bench.py --steps 3 --warmup 1 --skip-cpu --extra-sizes= --e2e-log2n 0 --strong-log2n 0 > /dev/null 2> $O/r02b_pmc_$c.err
+  timeout 900 rocprofv3 --kernel-trace --pmc $c --output-format csv -d $O/r02b_pmc_$c -- python3 $R/bench.py --full --steps 3 --warmup 1 --skip-cpu --extra-sizes= --e2e-log2n 0 --strong-log2n 0 > /dev/null 2> $O/r02b_pmc_$c.err
 done
 python3 $R/tools/timing/pmc_summary.py $O/r02b_pmc_FETCH_SIZE $O/r02b_pmc_WRITE_SIZE > $O/r02b_hbm_traffic_pmc.txt 2>&1
 find $O/r02b_prof -name "*kernel_stats.csv" -exec cp {} $O/r02b_bench_kernel_stats.csv \;

@@ -6,10 +6,10 @@ mkdir -p $O
 cd $R
 ( time timeout 2400 python -m pytest tests -m gpu -x -q --durations=8 ) > $O/r02m_pytest.log 2>&1
 echo "pytest rc=$?" >> $O/r02m_pytest.log
-timeout 1200 python bench.py > $O/r02m_bench.json 2> $O/r02m_bench.err
+timeout 1200 python bench.py --full > $O/r02m_bench.json 2> $O/r02m_bench.err
 python tools/timing/small_latency.py > $O/r02m_small_latency.txt 2>&1
 cd /tmp && export TMPDIR=/tmp
-BENCH="$R/bench.py --steps 10 --warmup 2 --skip-cpu --extra-sizes= --e2e-log2n 0 --strong-log2n 0 --no-two-in-flight"
+BENCH="$R/bench.py --full --steps 10 --warmup 2 --skip-cpu --extra-sizes= --e2e-log2n 0 --strong-log2n 0 --no-two-in-flight"
 timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $O/r02m_prof -- python3 $BENCH > $O/r02m_bench_under_rocprof.json 2> $O/r02m_prof.err
 find $O/r02m_prof -name "*kernel_stats.csv" -exec cp {} $O/r02m_bench_kernel_stats.csv \;
 python3 $R/tools/timing/prof_split.py $(find $O/r02m_prof -name "*kernel_trace.csv" | head -1) > $O/r02m_per_msm_kernel_budget.txt 2>&1

@@ -13,5 +13,5 @@ grep -v amdgpu.ids $O/r03h_pcie.txt
 ( time timeout 2400 python -m pytest tests -m gpu -x -q --durations=6 ) > $O/r03h_pytest.log 2>&1
 echo "pytest rc=$?" >> $O/r03h_pytest.log
 tail -12 $O/r03h_pytest.log
-timeout 1200 python bench.py > $O/r03h_bench.json 2> $O/r03h_bench.err
+timeout 1200 python bench.py --full > $O/r03h_bench.json 2> $O/r03h_bench.err
 echo "bench rc=$?"; head -c 400 $O/r03h_bench.json; echo

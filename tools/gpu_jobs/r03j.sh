@@ -11,5 +11,5 @@ timeout 600 python tools/timing/window_sweep.py 20,22,24 17 > $O/r03j_commit.txt
 timeout 600 python tools/timing/small_latency.py 4,10,12,14,16,18,20 >> $O/r03j_commit.txt 2>&1
 timeout 600 python tools/timing/pcie_incl.py >> $O/r03j_commit.txt 2>&1
 grep -v amdgpu.ids $O/r03j_commit.txt
-timeout 1200 python bench.py > $O/r03j_bench.json 2> $O/r03j_bench.err
+timeout 1200 python bench.py --full > $O/r03j_bench.json 2> $O/r03j_bench.err
 echo "bench rc=$?"; head -c 300 $O/r03j_bench.json; echo

@@ -10,13 +10,13 @@ mkdir -p $O
 cd $R
 ( time timeout 2400 python -m pytest tests -m gpu -x -q --durations=8 ) > $O/${T}_pytest.log 2>&1
 echo "pytest rc=$?" >> $O/${T}_pytest.log
-timeout 1200 python bench.py > $O/${T}_bench.json 2> $O/${T}_bench.err
+timeout 1200 python bench.py --full > $O/${T}_bench.json 2> $O/${T}_bench.err
 echo "bench rc=$?" >> $O/${T}_pytest.log
 python tools/timing/small_latency.py > $O/${T}_small_latency.txt 2>&1
 python tools/timing/many_commit.py 10:256,10:256:1:10,10:256:1:12,12:64,12:64:1:10,8:1024,8:1024:1:10,14:16 > $O/${T}_many_commit.txt 2>&1
 bash tools/gpu_jobs/r04_many_trace.sh > $O/${T}_many_commit_kernel_trace.txt 2>&1
 cd /tmp && export TMPDIR=/tmp
-BENCH="$R/bench.py --steps 10 --warmup 2 --skip-cpu --extra-sizes= --e2e-log2n 0 --strong-log2n 0 --strong-ntt-log2n 0 --no-two-in-flight"
+BENCH="$R/bench.py --full --steps 10 --warmup 2 --skip-cpu --extra-sizes= --e2e-log2n 0 --strong-log2n 0 --strong-ntt-log2n 0 --no-two-in-flight"
 timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $O/${T}_prof -- python3 $BENCH > $O/${T}_bench_under_rocprof.json 2> $O/${T}_prof.err
 find $O/${T}_prof -name "*kernel_stats.csv" -exec cp {} $O/${T}_bench_kernel_stats.csv \;
 python3 $R/tools/timing/prof_split.py $(find $O/${T}_prof -name "*kernel_trace.csv" | head -1) > $O/${T}_per_msm_kernel_budget.txt 2>&1

@@ -4,7 +4,7 @@ R=${GRAFT_REPO_ROOT:-/root/repo}
 O=$R/gpurun_out
 mkdir -p $O
 cd $R
-timeout 1200 python bench.py > $O/r04b_bench.json 2> $O/r04b_bench.err
+timeout 1200 python bench.py --full > $O/r04b_bench.json 2> $O/r04b_bench.err
 echo "bench rc=$?"
 python - <<'PY'
 import json

@@ -15,7 +15,7 @@ find $O/${T}_interp -name "*kernel_stats.csv" -exec cp {} $O/${T}_interp_kernel_
 cd $R
 find $O -name "*.csv" -size +4M -delete
 tail -4 $O/${T}_pytest.log; cat $O/${T}_pipeline.txt; grep "interp rep" $O/${T}_interp.log; head -8 $O/${T}_interp_kernel_stats.csv | cut -c1-60,150-230
-timeout 600 python bench.py --steps 5 --warmup 1 --skip-cpu --extra-sizes= --e2e-log2n 0 --strong-log2n 0 --strong-ntt-log2n 0 > $O/${T}_bench.json 2> $O/${T}_bench.err
+timeout 600 python bench.py --full --steps 5 --warmup 1 --skip-cpu --extra-sizes= --e2e-log2n 0 --strong-log2n 0 --strong-ntt-log2n 0 > $O/${T}_bench.json 2> $O/${T}_bench.err
 python3 -c "
 import json
 d=json.loads(open('$O/${T}_bench.json').read().strip().split('\n')[-1])

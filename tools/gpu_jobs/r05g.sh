@@ -7,7 +7,7 @@ mkdir -p $O
 cd $R
 ( time timeout 900 python -m pytest tests/test_gpu_dev_api.py -m gpu -x -q ) > $O/${T}_pytest.log 2>&1
 echo "pytest rc=$?" >> $O/${T}_pytest.log
-timeout 1200 python bench.py > $O/${T}_bench.json 2> $O/${T}_bench.err
+timeout 1200 python bench.py --full > $O/${T}_bench.json 2> $O/${T}_bench.err
 echo "bench rc=$?" >> $O/${T}_pytest.log
 python tools/timing/fri_round_cost.py > $O/${T}_fri_round_cost.txt 2>&1
 python tools/timing/stark_commit_pipeline.py 12 16 > $O/${T}_stark_pipeline_2pow12.txt 2>&1

@@ -11,7 +11,7 @@ mkdir -p $O
 cd $R
 ( time timeout 2400 python -m pytest tests -m gpu -x -q --durations=8 ) > $O/${T}_pytest.log 2>&1
 echo "pytest rc=$?" >> $O/${T}_pytest.log
-timeout 1200 python bench.py --detail-file $O/${T}_bench_default_detail.json > $O/${T}_bench_default.json 2> $O/${T}_bench.err
+timeout 1200 python bench.py --full --detail-file $O/${T}_bench_default_detail.json > $O/${T}_bench_default.json 2> $O/${T}_bench.err
 echo "bench rc=$?" >> $O/${T}_pytest.log
 python tools/timing/small_latency.py > $O/${T}_small_latency.txt 2>&1
 python tools/timing/pcie_incl.py > $O/${T}_pcie_inclusive.txt 2>&1
@@ -24,7 +24,7 @@ python tools/timing/time_ntt.py 10,14,16,18,20,21,22,24 > $O/${T}_time_ntt.txt 2
 python tools/timing/generic_phases.py 20 22 23 24 > $O/${T}_generic_phases.txt 2>&1
 python tools/timing/window_sweep.py 16,18,20,22,24 1 2>&1 | cut -c1-230 > $O/${T}_commit_phases.txt
 cd /tmp && export TMPDIR=/tmp
-BENCH="$R/bench.py --steps 10 --warmup 2 --skip-cpu --extra-sizes= --e2e-log2n 0 --strong-log2n 0 --strong-ntt-log2n 0 --no-two-in-flight --detail-file $O/${T}_bench_under_rocprof_detail.json"
+BENCH="$R/bench.py --full --steps 10 --warmup 2 --skip-cpu --extra-sizes= --e2e-log2n 0 --strong-log2n 0 --strong-ntt-log2n 0 --no-two-in-flight --detail-file $O/${T}_bench_under_rocprof_detail.json"
 timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $O/${T}_prof -- python3 $BENCH > $O/${T}_bench_under_rocprof.json 2> $O/${T}_prof.err
 find $O/${T}_prof -name "*kernel_stats.csv" -exec cp {} $O/${T}_bench_kernel_stats.csv \;
 python3 $R/tools/timing/prof_split.py $(find $O/${T}_prof -name "*kernel_trace.csv" | head -1) > $O/${T}_per_msm_kernel_budget.txt 2>&1

@@ -22,7 +22,7 @@ for v in 0 3; do
 done
 cat $O/r06c_ab.txt
 unset MZK_HIP_LIB
-MZK_BENCH_VERBOSE=1 timeout 900 python bench.py --log2n 16 --e2e-log2n 16 --strong-log2n 16 --strong-ntt-log2n 16 --extra-sizes 18 --steps 3 --detail-file $O/r06c_bench_detail_small.json > $O/r06c_bench_small.json 2> $O/r06c_bench_small.err; echo "bench rc=$?"
+MZK_BENCH_VERBOSE=1 timeout 900 python bench.py --full --log2n 16 --e2e-log2n 16 --strong-log2n 16 --strong-ntt-log2n 16 --extra-sizes 18 --steps 3 --detail-file $O/r06c_bench_detail_small.json > $O/r06c_bench_small.json 2> $O/r06c_bench_small.err; echo "bench rc=$?"
 tail -c 3000 $O/r06c_bench_small.err | grep -v amdgpu.ids | tail -15
 wc -c $O/r06c_bench_small.json
 timeout 1500 python -m pytest tests/test_gpu_rccl_world1.py -m gpu -x -q 2>&1 | tail -15 | tee $O/r06c_pytest_rccl.txt

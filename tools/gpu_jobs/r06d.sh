@@ -27,5 +27,5 @@ done
 done
 cat $O/r06d_sort_ab.txt
 unset MZK_HIP_LIB
-timeout 900 python bench.py --detail-file $O/r06d_bench_detail.json > $O/r06d_bench.json 2> $O/r06d_bench.err; echo "bench rc=$?"
+timeout 900 python bench.py --full --detail-file $O/r06d_bench_detail.json > $O/r06d_bench.json 2> $O/r06d_bench.err; echo "bench rc=$?"
 wc -c $O/r06d_bench.json

@@ -6,7 +6,7 @@ O=$R/gpurun_out
 mkdir -p $O
 cd $R
 timeout 900 python -m pytest tests/test_gpu_e2e_kzg.py tests/test_gpu_rccl_world1.py -m gpu -x -q 2>&1 | tail -4 | tee $O/r06j_pytest.txt
-timeout 1200 python bench.py --detail-file $O/r06j_bench_default_detail.json > $O/r06j_bench_default.json 2> $O/r06j_bench.err; echo "bench rc=$?"
-timeout 900 python bench.py --gpus 1 --force-process-group --sharded-legs-only --steps 5 --warmup 2 --skip-cpu --extra-sizes= \
+timeout 1200 python bench.py --full --detail-file $O/r06j_bench_default_detail.json > $O/r06j_bench_default.json 2> $O/r06j_bench.err; echo "bench rc=$?"
+timeout 900 python bench.py --full --gpus 1 --force-process-group --sharded-legs-only --steps 5 --warmup 2 --skip-cpu --extra-sizes= \
   --detail-file $O/r06j_bench_forced_nccl_world1_detail.json > $O/r06j_bench_forced_nccl_world1.json 2> $O/r06j_forced.err; echo "forced rc=$?"
 bash tools/gpu_jobs/r06_fuzz.sh 6101 6102 6103 6104
