@@ -659,7 +659,9 @@ static int msm_host_chunked(const uint64_t* scalars, const uint64_t* points, voi
   for (int k = 0; k < K; k++) { ch[k].d_scalars = (const uint8_t*)d_s + ch[k].i0 * 32; ch[k].ready = es.ev[k]; }
   const HostChunkUpload up{scalars, points, d_s, d_p, ch, es.ev, side};
   const std::function<int(int)> before = [&](int k) -> int { return up(k); };
-  return msm_chunked_impl(ch, K, d_points_for_msm, n, point_kind, table_stride, d_o, false, s, nullptr, &before);
+  const int rc = msm_chunked_impl(ch, K, d_points_for_msm, n, point_kind, table_stride, d_o, false, s, &before);
+  if (rc != MZK_OK) (void)hipStreamSynchronize(side);      // no piece may still be reading the caller's host buffers on return
+  return rc;
 }
 
 int mzk_ntt(int field_id, const uint64_t* root, const uint64_t* in, uint64_t* out, size_t n, int inverse) {
@@ -987,7 +989,7 @@ int mzk_msm_g1_bn254(const uint64_t* scalars, const uint64_t* points_xy, size_t 
   MZK_TRY(side_stream(&side, &fork, &join));
   MZK_TRY(ws_get(WS_MISC_A, n ? n * 64 : 16, &d_p));
   MZK_TRY(ws_get(WS_MISC_B, 256, &d_o));
-  if (msm_chunkable(n, MSM_PTS_PLAIN) && host_chunks_enabled()) {
+  if (msm_chunkable(n, MSM_PTS_PLAIN, 0) && host_chunks_enabled()) {
     // four equal pieces of scalars + points: the transfers (96 bytes per pair: 1.7 ms at 2^20) run under the pieces' kernels but for
     // the first piece's (profiles/round6_host_buffer_chunks.txt)
     static const int quarters[4] = {64, 128, 192, 256};
@@ -1159,7 +1161,7 @@ int mzk_kzg_commit_srs(const mzk_srs* srs, const uint64_t* coef, size_t n, uint6
   WsGuard wsg(s);
   void *d_s, *d_o;
   MZK_TRY(ws_get(WS_MISC_B, 256, &d_o));
-  if (msm_chunkable(n, srs->kind()) && host_chunks_enabled()) {
+  if (msm_chunkable(n, srs->kind(), srs->n) && host_chunks_enabled()) {
     // a quarter of the coefficients first, the rest under its kernels (two pieces: every piece costs a segment combine of its own)
     static const int quarter_then_rest[2] = {64, 256};
     MsmChunk ch[8];
@@ -1181,26 +1183,7 @@ int mzk_kzg_commit_srs_dev(const mzk_srs* srs, const void* d_coef, size_t n, voi
   if (!srs || !d_out || (!d_coef && n)) { set_error("commit_srs_dev: null pointer"); return MZK_E_ARG; }
   MZK_TRY(srs_check_ctx(srs));
   if (n > srs->n) { set_error("index out of bounds: the len is %zu but the index is %zu", srs->n, srs->n); return MZK_E_LENGTH; }
-#ifdef MZK_TUNING
-  // what-if of the verdict's two-half pipeline (VERDICT r05 #1a): MZK_DEV_CHUNKS pieces of resident coefficients, piece k + 1's sort on a
-  // side stream (MZK_DEV_SORT_STREAM=1) under piece k's accumulate -- measured and not adopted (profiles/round6_two_half_pipeline.txt)
-  static const int dev_chunks = mzk::tune_int("MZK_DEV_CHUNKS", 0), dev_sort_stream = mzk::tune_int("MZK_DEV_SORT_STREAM", 0);
-  if (dev_chunks >= 2 && dev_chunks <= 8 && msm_chunkable(n, srs->kind())) {
-    MsmChunk ch[8];
-    size_t prev = 0;
-    for (int k = 0; k < dev_chunks; k++) {
-      const size_t end = (k + 1 == dev_chunks) ? n : ((n * (size_t)(k + 1) / (size_t)dev_chunks) & ~(size_t)4095);
-      ch[k] = MsmChunk{(const uint8_t*)d_coef + prev * 32, prev, end - prev, nullptr};
-      prev = end;
-    }
-    hipStream_t side = nullptr;
-    hipEvent_t fork, join;
-    if (dev_sort_stream) MZK_TRY(side_stream(&side, &fork, &join));
-    return msm_chunked_impl(ch, dev_chunks, srs->d_points_mont, n, srs->kind(), srs->n, d_out, out_partial != 0, (hipStream_t)stream, side);
-  }
-#endif
-  return msm_dev_impl(d_coef, srs->d_points_mont, n, srs->kind(), srs->n, d_out, out_partial != 0,
-                      (hipStream_t)stream);
+  return msm_dev_impl(d_coef, srs->d_points_mont, n, srs->kind(), srs->n, d_out, out_partial != 0, (hipStream_t)stream);
 }
 
 }  // extern "C" (the lane scheduler is a template)

@@ -11,6 +11,7 @@
 #include <vector>
 #include "../../include/mzk.h"
 #include "mzk_field.h"
+#include "mzk_msm_plan.h"
 
 namespace mzk {
 
@@ -184,9 +185,7 @@ int fri_fold_dev_consts(int fid, const void* d_cw, size_t n, const uint64_t* alp
 int kzg_batch_open_dev(const void* d_coef, size_t n, const uint64_t* us_host, size_t k, const void* d_points, int point_kind,
                        size_t table_stride, void* d_ys, void* d_w_xy, hipStream_t s);
 
-enum { MSM_PTS_PLAIN = 0, MSM_PTS_MONT = 1, MSM_PTS_TABLES = 2 };
-// Fixed-base window tables: c-bit signed windows, 254 / c + 1 of them.  point_kind carries c in bits 8..15
-// (MSM_PTS_TABLES alone = 16).  Width by SRS size, from the sweep of round 3 (tools/timing/window_sweep.py,
+// point_kind, window tables: mzk_msm_plan.h.  Width by SRS size, from the sweep of round 3 (tools/timing/window_sweep.py,
 // profiles/r03b_window_sweep.txt; one box, ms per commit at c = 16 / 17 / 19 / 20):
 //   2^17  0.54 / 0.57 / 0.89 / 0.80      2^20  1.67 / 1.63 / 2.24 / 1.78      2^22   6.46 /  6.12 /  6.98 / 5.85
 //   2^18  0.73 / 0.74 / 1.00 / 0.93      2^21  3.28 / 2.94 / 3.83 / 3.20      2^24  24.38 / 23.00 / 25.01 /  --
@@ -198,9 +197,6 @@ enum { MSM_PTS_PLAIN = 0, MSM_PTS_MONT = 1, MSM_PTS_TABLES = 2 };
 // four buckets, 4096 segment partials apiece at 2^20 -- 0.45 ms of heavy-bucket combine at every size.
 // Other widths stay selectable through mzk_srs_from_device_ex for tuning and tests (BASELINE configs[2] names 16 bits:
 // bench.py reports that width as its own leg).
-static inline int msm_table_windows(int c) { return 254 / c + 1; }
-// tables a handle with `sets` bucket sets holds: every sets-th window, ceil(windows / sets) = 254 / (c sets) + 1
-static inline int msm_table_rows(int c, int sets) { return 254 / (c * sets) + 1; }
 // Small SRS (the reference's actual sizes: a few thousand powers at most) take the short paths of mzk_msm.hip (two launches:
 // k_small_accumulate_scan + the tail); with tables there is no window Horner either (its ~120 serial doublings are the latency
 // floor of a small generic MSM), so they get narrow windows: 8 bits = 32 tables x 128 buckets up to 1024 points, 10 bits =
@@ -215,7 +211,6 @@ static inline int msm_srs_window_bits(size_t n) {
   return n <= 1024 ? 8 : (n <= ((size_t)1 << 14) ? 10 : (n < ((size_t)1 << 19) ? 16 : (n < ((size_t)1 << 22) ? 17 : 20)));
 }
 static inline bool msm_srs_default_tables(size_t n) { return n > 0; }
-#define MSM_PTS_TABLES_C(c) (MSM_PTS_TABLES | ((c) << 8))      // bits 16..23: bucket sets (0 or 1 = one)
 // One MSM computed in CHUNKS of consecutive pairs (msm_chunked_impl): every chunk is sorted and accumulated on its own -- as soon as
 // ITS scalars (and points) are on the device -- into its own bucket array, the chunks' bucket arrays are summed and reduced once.
 // msm_dev_impl in chunk mode (cc != null) takes the chunk's scalars, the WHOLE point array, and stops after the segment combine.
@@ -224,12 +219,11 @@ struct MsmChunkCtx {
   size_t i0;             // index of the chunk's first pair in the whole problem
   size_t n_total;        // pairs of the whole problem: decides the window width / bucket layout of every chunk
   size_t n_alloc;        // the largest chunk: size of the per-chunk buffers (the same in every call, so that no workspace slot is regrown)
-  hipStream_t sort_stream;   // where the digit sort runs (null: the main stream): a chunk's sort may run under the previous chunk's accumulate
 };
 struct MsmChunk { const void* d_scalars; size_t i0, n; hipEvent_t ready; };    // ready (or null): recorded when the chunk's inputs are on the device
 int msm_chunked_impl(const MsmChunk* chunks, int K, const void* d_points, size_t n_total, int point_kind, size_t table_stride, void* d_out,
-                     bool out_partial_xyzz, hipStream_t s, hipStream_t sort_stream, const std::function<int(int)>* before_chunk = nullptr);
-bool msm_chunkable(size_t n_total, int point_kind);      // large enough, and a layout the chunk mode covers
+                     bool out_partial_xyzz, hipStream_t s, const std::function<int(int)>* before_chunk = nullptr);
+bool msm_chunkable(size_t n_total, int point_kind, size_t table_stride);      // mzk_msm_plan.h, with the library's MsmKnobs
 int msm_dev_impl(const void* d_scalars, const void* d_points, size_t n, int point_kind, size_t table_stride, void* d_out,
                  bool out_partial_xyzz, hipStream_t s, const std::function<int()>* points_ready = nullptr, const MsmChunkCtx* cc = nullptr);
 

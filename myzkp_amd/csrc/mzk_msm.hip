@@ -29,65 +29,19 @@
 
 namespace mzk {
 
-constexpr int SCALAR_BITS = 254;
-constexpr int MAX_WINDOWS = 32;
-
-struct MsmShape {
-  int c;          // window bits
-  int nwin;       // windows
-  int lgB;        // log2 buckets per window = c - 1
-  size_t nbuckets;
-};
-
-static MsmShape choose_shape(size_t n) {
-  int lg = 0;
-  while (((size_t)1 << lg) < n) lg++;
-  int c = lg - 3;
-  if (c < 8) c = 8;
-  if (c > 16) c = 16;
-  MsmShape s;
-  s.c = c;
-  s.nwin = SCALAR_BITS / c + 1;
-  s.lgB = c - 1;
-  s.nbuckets = (size_t)s.nwin << s.lgB;
-  return s;
+// the MSM's tuning switches: read once; in the shipped library tune_int is the constant default
+static const MsmKnobs& msm_knobs() {
+  static const MsmKnobs k = [] {
+    const MsmKnobs d;
+    return MsmKnobs{tune_int("MZK_GLV_C", d.glv_c), tune_int("MZK_SMALL_SCAN", d.small_scan), tune_int("MZK_SCAN_MAX_LOG", d.scan_max_log),
+                    tune_int("MZK_ACC_PREFETCH", d.acc_prefetch), tune_int("MZK_ACC_SEG", d.acc_seg), tune_int("MZK_COARSE_LOG_20", d.coarse_log_20),
+                    tune_int("MZK_COARSE_LOG_17", d.coarse_log_17), tune_int("MZK_PER_FINE", d.per_fine), tune_int("MZK_SORT_SCAN_FREE", d.sort_scan_free),
+                    tune_int("MZK_COARSE_STAGED", d.coarse_staged), tune_int("MZK_COMBINE_WIDE_MIN_LOG", d.combine_wide_min_log)};
+  }();
+  return k;
 }
 
-// Generic layout after the GLV split: 2n points with scalars below 2^126.  Windows must cover 127 bits plus the
-// signed-digit carry; at c = 16 that is exactly 8 windows (2^18 buckets: the two-level sort's power of two).
-constexpr int GLV_MAG_BITS = 126;      // |k1|, |k2| < 2^126 (mzk_glv.h)
-static MsmShape choose_shape_glv(size_t n) {
-  int lg = 0;
-  while (((size_t)1 << lg) < 2 * n) lg++;
-  int c = lg - 3;
-  if (c < 8) c = 8;
-  if (c > 16) c = 16;
-  if (c == 15) c = 16;     // 2^17 pairs: 8 full windows + the two-level sort beat 9 windows with a 6-bit top window
-  // From 3 x 2^21 pairs on: 19 bits -- SEVEN windows per half instead of eight (14 mixed additions per pair, not 16: the accumulate is
-  // 80 % of the call), 7 x 2^18 buckets.  17 and 18 bits still need eight windows (7 x 18 = 126 leaves the top window nothing but
-  // carries), 20 bits also seven but twice the buckets, 22 bits six windows over 6 x 2^21 buckets whose reduction and one-pass sort cost
-  // more than the windows save.  The larger bucket set costs ~0.7 ms more to sort, combine and reduce whatever n is, the saved additions
-  // 0.145 ms per 2^20 pairs: 2^22 +3.6 %, 2^23 -2 %, 2^24 -6.5 %, 2^26 -7.5 % (profiles/round6_generic_window_sweep.txt).
-  static const int env_glv_c = tune_int("MZK_GLV_C", 0);         // tuning build: force a width (the sweep)
-  if (n >= ((size_t)3 << 21)) c = 19;
-  if (env_glv_c > 0) c = env_glv_c;
-  // nwin windows must cover the 126 magnitude bits plus the signed-digit carry.  The top window only holds
-  // 126 - c (nwin - 1) real bits; if that is (almost) nothing, every scalar whose carry runs into it lands in the
-  // same few buckets (c = 14: ONE bucket receives a third of all entries) -- step c down until the top window is
-  // reasonably populated.
-  for (; c > 8; c--) {
-    const int nw = GLV_MAG_BITS / c + 1;
-    if (GLV_MAG_BITS - c * (nw - 1) >= 5) break;
-  }
-  MsmShape s;
-  s.c = c;
-  s.nwin = GLV_MAG_BITS / c + 1;
-  s.lgB = c - 1;
-  s.nbuckets = (size_t)s.nwin << s.lgB;
-  return s;
-}
-
-int msm_generic_window_bits(size_t n) { return choose_shape_glv(n ? n : 1).c; }
+int msm_generic_window_bits(size_t n) { return choose_shape_glv(n ? n : 1, msm_knobs().glv_c).c; }
 
 // ---- global loads of packed 256-bit values -----------------------------------------------------------
 __device__ __forceinline__ void load_words8(const u32* __restrict__ g, u32* w) {
@@ -118,7 +72,7 @@ __device__ __forceinline__ void xyzz_gstore(u32* __restrict__ g, size_t idx, con
 // addition).  That matters because a wave pays for a flush whenever ANY of its lanes crosses a bucket boundary -- nearly
 // every iteration in the generic layout (64-entry buckets, 64-entry segments).  Limbs are whatever the accumulator held:
 // normalised, value < 2.5 p, exactly what xyzz_add accepts; infinity is all-zero.
-constexpr int SLOT_WORDS = 4 * FqParams::L;      // 36
+static_assert(SLOT_WORDS == 4 * FqParams::L, "a slot is the four raw coordinates");
 __device__ __forceinline__ void xyzz_gstore_raw(u32* __restrict__ g, size_t idx, const Xyzz& p) {
   u32 w[SLOT_WORDS];
   const bool inf = xyzz_is_inf(p);
@@ -231,16 +185,6 @@ __device__ __forceinline__ u32 raw_window(const u32* w, int win, int c) {
   if (k + 1 < 8) v |= (u64)w[k + 1] << 32;
   return (u32)(v >> s) & ((1u << c) - 1u);
 }
-// Bucket layout.  Generic MSM: bucket = window * 2^(c-1) + |digit| - 1, entry = point index.
-// Fixed-base MSM over precomputed tables T[w][i] = 2^(c w) P_i: every window shares ONE bucket set,
-// bucket = |digit| - 1, entry = w * table_stride + i.
-struct DigitLayout {
-  int c, nwin, merged;
-  int sets;              // merged layout: bucket sets (mzk_srs::sets); window w goes to set w % sets and reads table row w / sets
-  size_t table_stride;
-  int glv;               // generic layout only: scalars are GLV-split, the phi images of the points start at phi_offset
-  size_t phi_offset;
-};
 // Calls emit(slot, key, payload) for every non-zero signed digit of scalar i (canonical words w).  `slot` numbers
 // the (half, window) positions of a scalar: 0 .. slots_per_scalar-1.  key = bucket index; payload = point reference
 // with the sign in bit 31.
@@ -484,12 +428,6 @@ __global__ __launch_bounds__(LDS_SORT_THREADS) void k_digits_scatter_lds(const u
 //           and k_fine_scatter writes the final 4-byte entries -- all inside one bin's region (256 KiB at 2^20),
 //           which stays in L2 while it fills.
 // key = bucket index: |digit| - 1 (merged layout) or window * 2^(c-1) + |digit| - 1.
-#ifndef MZK_COARSE_LOG
-#define MZK_COARSE_LOG 8
-#endif
-constexpr int COARSE_LOG = MZK_COARSE_LOG;      // 9: A/B build (one more bit for the point reference in the 4-byte sort records)
-constexpr int COARSE_BINS = 1 << COARSE_LOG;
-constexpr int COARSE_PER_WG = 4096;
 constexpr int SORT2_THREADS = 1024;
 // C: compile-time window width of the merged layout (walk_digits_merged), 0 = any layout by walk_digits
 // CL: log2 of the coarse bins.  256 everywhere but at 20-bit windows (2^19 buckets, the default from 2^22 points on): there 1024, so
@@ -628,14 +566,13 @@ constexpr int stage_records(int C, int CL) { return (CL > 8 ? (254 / C + 1) : 16
 constexpr size_t stage_lds_bytes(int C, int CL, size_t rec_bytes) {
   return (size_t)stage_records(C, CL) * (rec_bytes + (CL > 8 ? 2 : 1)) + (size_t)(4 * (1 << CL) + 1) * 4;
 }
-constexpr int STAGE_RECORDS = 16 * SORT2_THREADS;
 template <class REC, int C, int CL = COARSE_LOG>
 __global__ __launch_bounds__(SORT2_THREADS) void k_coarse_scatter_staged(const u32* __restrict__ scalars, size_t n, size_t table_stride, int key_shift,
                                                                           u32 fine_mask, int fb, const u32* __restrict__ binbase, int nwg,
                                                                           typename REC::T* __restrict__ tmp, const u32* __restrict__ bin_tot,
                                                                           u32* __restrict__ bin_cur, u32* __restrict__ bin_start_out) {
   typedef typename REC::T R;
-  constexpr int COARSE_BINS = 1 << CL;           // (shadows the 256 of the other kernels)
+  constexpr int COARSE_BINS = 1 << CL;
   constexpr int STAGE_RECORDS = stage_records(C, CL);
   constexpr int PER_LANE = COARSE_BINS / 64;     // bins per lane in the one-wave scan
   typedef typename std::conditional<(CL > 8), unsigned short, unsigned char>::type BinTag;
@@ -757,7 +694,6 @@ __device__ __forceinline__ FineSlice fine_plan(const u32* __restrict__ binbase, 
   return r;
 }
 constexpr int FINE_UNROLL = 8;
-constexpr int FINE_MAX = 8192;     // buckets per bin: NB / 256 (128 merged c = 16, 2048 generic c = 16, 8192 merged c = 22)
 template <class REC>
 __global__ __launch_bounds__(SORT2_THREADS) void k_fine_count(const typename REC::T* __restrict__ tmp, const u32* __restrict__ binbase, int nwg, int F,
                                                                int S, int fb, u32* __restrict__ finehist, int bins, u32 cap, u32* __restrict__ bucket_tot) {
@@ -834,7 +770,6 @@ __global__ __launch_bounds__(SORT2_THREADS) void k_fine_scatter_direct(const typ
 // one workgroup per CU: sort 0.170 -> 0.163 ms at 2^20, 0.726 -> 0.668 at 2^22; 4096 loses on the generic layout: profiles/r04l_*)
 constexpr int STAGE_CAP = MZK_STAGE_CAP;
 constexpr int STAGE_PER_LANE = STAGE_CAP / SORT2_THREADS;     // records per lane per round
-constexpr int STAGE_F_MAX = 2048;
 template <class REC>
 __global__ __launch_bounds__(SORT2_THREADS) void k_fine_scatter(const typename REC::T* __restrict__ tmp, const u32* __restrict__ binbase, int nwg, int F,
                                                                  int S, int fb, const u32* __restrict__ finebase, u32* __restrict__ offsets,
@@ -925,8 +860,6 @@ __global__ __launch_bounds__(SORT2_THREADS) void k_fine_scatter(const typename R
 }
 
 // ---- 2. exclusive scan (three small kernels) -----------------------------------------------------------
-constexpr int SCAN_ITEMS = 8;                      // per thread
-constexpr int SCAN_BLOCK = 256 * SCAN_ITEMS;       // 2048 per block
 __global__ __launch_bounds__(256) void k_scan_local(const u32* __restrict__ in, u32* __restrict__ out, u32* __restrict__ block_sums, size_t n) {
   __shared__ u32 sh[256];
   const size_t base = (size_t)blockIdx.x * SCAN_BLOCK + (size_t)threadIdx.x * SCAN_ITEMS;
@@ -977,11 +910,6 @@ __global__ __launch_bounds__(256) void k_scan_add(u32* __restrict__ offsets, con
 // scan than the launches -- one CU cannot stream and shuffle-scan 256 KiB as fast as 32 workgroups do, launch latency included.)
 // Above SCAN_DIRECT_BLOCKS block totals that re-summing would be quadratic (the generic layout at 2^24 has 16384 of them, 22-bit
 // windows 65536: ~10^9 .. 10^10 redundant loads), so the totals are scanned by a recursive call and added (four or five launches).
-constexpr size_t SCAN_DIRECT_BLOCKS = 2048;
-static size_t scan_scratch_words(size_t n) {
-  const size_t sb = (n + SCAN_BLOCK - 1) / SCAN_BLOCK;
-  return sb + 2 + (sb > SCAN_DIRECT_BLOCKS ? scan_scratch_words(sb) : 0);
-}
 static int launch_exclusive_scan(const u32* in, u32* out, size_t n, u32* scratch, hipStream_t s) {
   const size_t sb = (n + SCAN_BLOCK - 1) / SCAN_BLOCK;
   hipLaunchKernelGGL(k_scan_local, dim3((unsigned)sb), dim3(256), 0, s, in, out, scratch, n);
@@ -1087,12 +1015,11 @@ __global__ __launch_bounds__(256) void k_seg_accumulate(const u32* __restrict__ 
 // Buckets with more than HEAVY_SLOTS partials (skewed scalars: bit vectors, repeated values) would be one long
 // serial chain; they are queued in `heavy` (count at heavy[0], then (bucket id, end of entries) pairs) and summed by a whole
 // workgroup each (k_seg_combine_heavy).
-// The threshold is 32 partials; 16 for the one-kernel sort of the grid-batched pass (HEAVY_SLOTS_SORT1): there a bucket has 8 - 9
+// The threshold is 32 partials (HEAVY_SLOTS, mzk_msm_plan.h); 16 for the one-kernel sort of the grid-batched pass (HEAVY_SLOTS_SORT1): there a bucket has 8 - 9
 // partials and the signed digits of SHORT coefficients (31-byte chunks) put the carry out of their last non-zero window into bucket 0
 // of the window above -- ONE bucket per polynomial with three times the entries of the others, a chain of ~30 in a kernel that is as
 // long as its longest chain (256 x 2^10: segment combine 0.149 -> 0.105 ms).  Elsewhere 16 loses: 64 x 2^12 full-width coefficients have
 // ~12 such buckets per polynomial (the 4-bit top window), 768 deferred buckets are two rounds of the workgroup kernel: 0.114 -> 0.168.
-constexpr u32 HEAVY_SLOTS = 32;
 constexpr u32 HEAVY_SLOTS_SORT1 = 16;
 // end of bucket b's entries.  The one-kernel sort of the grid-batched commitments (k_many_sort1) leaves a tail of sentinels behind the
 // LAST bucket of every polynomial's fixed-capacity region; `tails` (one word per polynomial, or null) is where the real entries end,
@@ -1103,19 +1030,6 @@ __device__ __forceinline__ u32 bucket_end(const u32* __restrict__ offsets, const
   if (tails && (b & (((size_t)1 << lg_nb) - 1)) == (((size_t)1 << lg_nb) - 1)) return tails[b >> lg_nb];
   return offsets[b + 1];
 }
-// Layout of `heavy`: [0] count, [1] the segment length in force (written by the combine kernel), [2, 2 + HEAVY_GRID) arrival counters of k_seg_combine_heavy's shared buckets (zeroed with
-// the count, one memset), then (bucket id, end of its entries as the deferring kernel saw it -- bucket_end) pairs, then HEAVY_GRID
-// XYZZ records of scratch for the workgroups that share a bucket.
-// Behind the arrival counters, inside the same cleared header: the scan-free sort's per-bin totals and cursors (k_coarse_count /
-// k_coarse_scatter*: SORT_CTR_BINS words each) -- one memset per call clears everything that has to start at zero.
-constexpr int HEAVY_GRID = 512;
-constexpr int SORT_CTR_BINS = 1024;               // the most coarse bins any layout uses (20-bit merged windows)
-constexpr int SORT_CTR_AT = 2 + HEAVY_GRID;       // bin totals at heavy[SORT_CTR_AT ..), bin cursors SORT_CTR_BINS words further
-constexpr int HEAVY_HDR = SORT_CTR_AT + 2 * SORT_CTR_BINS;
-constexpr size_t HEAVY_CLEAR_BYTES = (size_t)HEAVY_HDR * 4;
-// (a multiple of four words: the scratch records behind the list are read and written as uint4)
-__host__ __device__ constexpr size_t heavy_list_words(size_t max_heavy) { return (HEAVY_HDR + 2 * max_heavy + 2 + 3) & ~(size_t)3; }
-__host__ __device__ constexpr size_t heavy_total_words(size_t max_heavy) { return heavy_list_words(max_heavy) + (size_t)HEAVY_GRID * 32 + 8; }
 __device__ __forceinline__ bool defer_heavy(size_t b, size_t s0, size_t s1, u32 o1, u32* __restrict__ heavy, bool leader, u32 threshold = HEAVY_SLOTS) {
   if (s1 - s0 + 1 <= threshold) return false;
   if (leader) { const u32 i = atomicAdd(&heavy[0], 1u); heavy[HEAVY_HDR + 2 * i] = (u32)b; heavy[HEAVY_HDR + 2 * i + 1] = o1; }
@@ -1389,8 +1303,6 @@ __global__ __launch_bounds__(TAIL_THREADS) void k_reduce_tail(u32* __restrict__ 
 //                       summed by a quad-cooperative tree through LDS (seven rounds of ~2 us instead of a serial chain)
 //   k_reduce_tail       all halving steps of a bucket set inside one workgroup (t_start = 0), then k_window_combine.
 constexpr int SMALL_SORT_THREADS = 1024;
-constexpr size_t SMALL_MAX_N = 4097;          // exclusive: 4096 (a blob of das/avail.rs) still takes the three-launch path
-constexpr size_t SMALL_MAX_BUCKETS = 8192;
 __global__ __launch_bounds__(SMALL_SORT_THREADS) void k_small_sort(const u32* __restrict__ scalars, size_t n, DigitLayout L, int NB,
                                                                     u32* __restrict__ offsets, u32* __restrict__ entries) {
   extern __shared__ u32 sh_small[];
@@ -1700,28 +1612,22 @@ int msm_build_tables(const void* d_points_mont, size_t n, void* d_tables, int wi
 }
 
 // record-format dependent half of the two-level sort (coarse scatter, fine count, scan, fine scatter)
-struct SortArgs {
-  const u32* scalars; size_t n; DigitLayout L; int key_shift; u32 fine_mask; int fb; u32* binhist; int nwg; void* tmp; int F; int S;
-  u32* finehist; u32* scan3; size_t sb_f; size_t n_fine; u32* offsets; u32* entries; size_t NBtot;
-  unsigned fine_wgs; u32 fine_cap;       // grid of the fine kernels (slices of all bins + the extra slices of over-full ones) and the slice capacity (fine_plan)
-  int cl;           // log2 of the coarse bins: COARSE_LOG, or 10 for the 20-bit merged layout
+struct SortBufs {
+  const u32* scalars; u32* binhist; void* tmp; u32* finehist; u32* scan3; u32* offsets; u32* entries;
   // scan-free forms (null: the global scans of rounds 3-5): per-bin totals / cursors (in the call's cleared header), the bins + 1 bin starts the
   // coarse scatter publishes, per-bucket totals / cursors (zeroed by k_coarse_count)
   u32 *bin_tot, *bin_cur, *bin_start, *bucket_tot, *bucket_cur;
 };
 template <class REC>
-static int sort_records(const SortArgs& a, hipStream_t s) {
+static int sort_records(const MsmPlan& P, const SortBufs& a, hipStream_t s) {
   typedef typename REC::T R;
-  const int cw = (a.L.merged && !a.L.glv && a.L.sets == 1 && (a.L.c == 16 || a.L.c == 17 || a.L.c == 20)) ? a.L.c : 0;     // the default widths by SRS size
-  static const int env_staged = tune_int("MZK_COARSE_STAGED", 1);      // 0: A/B against the direct stores
-  const unsigned bins = 1u << a.cl;
-  // scan-free forms: a.bin_tot / a.bucket_tot non-null (see k_coarse_count, k_fine_scatter)
-#define MZK_STAGED(C, CLOG) hipLaunchKernelGGL((k_coarse_scatter_staged<REC, C, CLOG>), dim3(a.nwg), dim3(SORT2_THREADS), lds, s, a.scalars, a.n, a.L.table_stride, \
-                                               a.key_shift, a.fine_mask, a.fb, (const u32*)a.binhist, a.nwg, (R*)a.tmp, (const u32*)a.bin_tot, a.bin_cur, a.bin_start)
-#define MZK_DIRECT(C) hipLaunchKernelGGL((k_coarse_scatter<REC, C>), dim3(a.nwg), dim3(SORT2_THREADS), 0, s, a.scalars, a.n, a.L, a.key_shift, a.fine_mask, a.fb, \
-                                         (const u32*)a.binhist, a.nwg, (R*)a.tmp, (const u32*)a.bin_tot, a.bin_cur, a.bin_start)
-  if (cw != 0 && (env_staged != 0 || a.cl != COARSE_LOG)) {
-    const size_t lds = stage_lds_bytes(cw, a.cl, sizeof(R));
+  const unsigned bins = 1u << P.cl;
+#define MZK_STAGED(C, CLOG) hipLaunchKernelGGL((k_coarse_scatter_staged<REC, C, CLOG>), dim3(P.nwg), dim3(SORT2_THREADS), lds, s, a.scalars, P.n, P.L.table_stride, \
+                                               P.key_shift, P.fine_mask, P.fb, (const u32*)a.binhist, P.nwg, (R*)a.tmp, (const u32*)a.bin_tot, a.bin_cur, a.bin_start)
+#define MZK_DIRECT(C, CLOG) hipLaunchKernelGGL((k_coarse_scatter<REC, C, CLOG>), dim3(P.nwg), dim3(SORT2_THREADS), 0, s, a.scalars, P.n, P.L, P.key_shift, P.fine_mask, \
+                                               P.fb, (const u32*)a.binhist, P.nwg, (R*)a.tmp, (const u32*)a.bin_tot, a.bin_cur, a.bin_start)
+  if (P.scatter_staged) {
+    const size_t lds = stage_lds_bytes(P.coarse_c, P.cl, sizeof(R));
     bool& attr = ctx().attr_done[sizeof(R) == 4 ? ATTR_COARSE_STAGED4 : ATTR_COARSE_STAGED8];
     if (!attr) {
       MZK_HIP(hipFuncSetAttribute((const void*)k_coarse_scatter_staged<REC, 16>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
@@ -1731,351 +1637,170 @@ static int sort_records(const SortArgs& a, hipStream_t s) {
       MZK_HIP(hipFuncSetAttribute((const void*)k_coarse_scatter_staged<REC, 17, 9>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
       attr = true;
     }
-    if (cw == 17 && a.cl == 9) MZK_STAGED(17, 9);
-    else if (cw == 20 && a.cl == 10) MZK_STAGED(20, 10);
-    else if (cw == 20) MZK_STAGED(20, COARSE_LOG);
-    else if (cw == 17) MZK_STAGED(17, COARSE_LOG);
+    if (P.coarse_c == 17 && P.cl == 9) MZK_STAGED(17, 9);
+    else if (P.coarse_c == 20 && P.cl == 10) MZK_STAGED(20, 10);
+    else if (P.coarse_c == 20) MZK_STAGED(20, COARSE_LOG);
+    else if (P.coarse_c == 17) MZK_STAGED(17, COARSE_LOG);
     else MZK_STAGED(16, COARSE_LOG);
   }
 #ifdef MZK_TUNING
-  else if (cw == 20) MZK_DIRECT(20);
-  else if (cw == 17) MZK_DIRECT(17);
-  else if (cw == 16) MZK_DIRECT(16);
+  else if (P.coarse_c == 20) MZK_DIRECT(20, COARSE_LOG);
+  else if (P.coarse_c == 17) MZK_DIRECT(17, COARSE_LOG);
+  else if (P.coarse_c == 16) MZK_DIRECT(16, COARSE_LOG);
 #endif
-  else if (a.cl == 10) hipLaunchKernelGGL((k_coarse_scatter<REC, 0, 10>), dim3(a.nwg), dim3(SORT2_THREADS), 0, s, a.scalars, a.n, a.L, a.key_shift, a.fine_mask, a.fb,
-                                          (const u32*)a.binhist, a.nwg, (R*)a.tmp, (const u32*)a.bin_tot, a.bin_cur, a.bin_start);
-  else MZK_DIRECT(0);
+  else if (P.cl == 10) MZK_DIRECT(0, 10);
+  else MZK_DIRECT(0, COARSE_LOG);
 #undef MZK_STAGED
 #undef MZK_DIRECT
   // bin boundaries as the fine kernels index them: the coarse scan's [bin][workgroup] prefix, or the scan-free form's bins + 1 starts
   const u32* bounds = a.bin_tot ? (const u32*)a.bin_start : (const u32*)a.binhist;
-  const int bstride = a.bin_tot ? 1 : a.nwg;
-  const bool fine_free = a.bucket_tot != nullptr && a.F <= STAGE_F_MAX;
-  hipLaunchKernelGGL((k_fine_count<REC>), dim3(a.fine_wgs), dim3(SORT2_THREADS), 0, s, (const R*)a.tmp, bounds, bstride, a.F, a.S,
-                     a.fb, a.finehist, (int)bins, a.fine_cap, fine_free ? a.bucket_tot : (u32*)nullptr);
-  if (!fine_free) MZK_TRY(launch_exclusive_scan((const u32*)a.finehist, a.finehist, a.n_fine, a.scan3, s));
-  if (a.F <= STAGE_F_MAX) {
-    const size_t lds = ((size_t)3 * a.F + SORT2_THREADS + STAGE_CAP) * 4 + (size_t)STAGE_CAP * 2;
+  const int bstride = a.bin_tot ? 1 : P.nwg;
+  hipLaunchKernelGGL((k_fine_count<REC>), dim3(P.fine_wgs), dim3(SORT2_THREADS), 0, s, (const R*)a.tmp, bounds, bstride, P.F, P.S,
+                     P.fb, a.finehist, (int)bins, P.slice_cap, a.bucket_tot);
+  if (!P.fine_free) MZK_TRY(launch_exclusive_scan((const u32*)a.finehist, a.finehist, P.own.n_fine, a.scan3, s));
+  if (P.F <= STAGE_F_MAX) {
+    const size_t lds = ((size_t)3 * P.F + SORT2_THREADS + STAGE_CAP) * 4 + (size_t)STAGE_CAP * 2;
     bool& staged_attr = ctx().attr_done[sizeof(R) == 4 ? ATTR_FINE_SCATTER4 : ATTR_FINE_SCATTER8];     // per instantiation and context
     if (!staged_attr) {
       MZK_HIP(hipFuncSetAttribute((const void*)k_fine_scatter<REC>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
       staged_attr = true;
     }
-    hipLaunchKernelGGL((k_fine_scatter<REC>), dim3(a.fine_wgs), dim3(SORT2_THREADS), lds, s, (const R*)a.tmp, bounds, bstride, a.F,
-                       a.S, a.fb, (const u32*)a.finehist, a.offsets, a.entries, a.NBtot, (int)bins, a.fine_cap,
-                       fine_free ? (const u32*)a.bucket_tot : (const u32*)nullptr, fine_free ? a.bucket_cur : (u32*)nullptr);
+    hipLaunchKernelGGL((k_fine_scatter<REC>), dim3(P.fine_wgs), dim3(SORT2_THREADS), lds, s, (const R*)a.tmp, bounds, bstride, P.F,
+                       P.S, P.fb, (const u32*)a.finehist, a.offsets, a.entries, P.NBtot, (int)bins, P.slice_cap, (const u32*)a.bucket_tot, a.bucket_cur);
   } else {
-    hipLaunchKernelGGL((k_fine_scatter_direct<REC>), dim3(a.fine_wgs), dim3(SORT2_THREADS), 0, s, (const R*)a.tmp, bounds, bstride,
-                       a.F, a.S, a.fb, (const u32*)a.finehist, a.offsets, a.entries, a.NBtot, (int)bins, a.fine_cap);
+    hipLaunchKernelGGL((k_fine_scatter_direct<REC>), dim3(P.fine_wgs), dim3(SORT2_THREADS), 0, s, (const R*)a.tmp, bounds, bstride,
+                       P.F, P.S, P.fb, (const u32*)a.finehist, a.offsets, a.entries, P.NBtot, (int)bins, P.slice_cap);
   }
   MZK_HIP(hipGetLastError());
   return MZK_OK;
 }
 
-// point_kind: 0 = affine canonical (ABI form), 1 = affine Montgomery (prepared), 2 = SRS window tables
-// (SRS_WINDOWS x table_stride affine Montgomery points: all windows share one bucket set, no Horner).
+// Executes msm_plan (mzk_msm_plan.h: point_kind, layout, path, workspace).
 // points_ready (optional, plain points only): called once, after the digit sort has been enqueued and before the first kernel
 // that reads the points -- the host-buffer entry point stages the points onto the device there, so that the transfer of the
 // 64 n bytes of points runs under the sort of the scalars instead of in front of it.
 int msm_dev_impl(const void* d_scalars, const void* d_points, size_t n, int point_kind, size_t table_stride, void* d_out,
                  bool out_partial_xyzz, hipStream_t s, const std::function<int()>* points_ready, const MsmChunkCtx* cc) {
   if (!d_out || ((!d_scalars || !d_points) && n)) { set_error("msm: null pointer"); return MZK_E_ARG; }
-  if (n > ((size_t)1 << 27)) { set_error("msm: n > 2^27 not supported"); return MZK_E_ARG; }
-  // chunk mode (msm_chunked_impl): the pairs [i0, i0 + n) of a problem of n_shape pairs; layout by the whole problem, per-chunk buffers
+  // chunk mode (msm_chunked_impl): the pairs [i0, i0 + n) of a problem of n_total pairs; layout by the whole problem, per-chunk buffers
   // sized for the largest chunk, returns with the chunk's buckets summed (no reduction)
-  const size_t n_shape = cc ? cc->n_total : n, n_alloc = cc ? cc->n_alloc : n, i0 = cc ? cc->i0 : 0;
-  const int ck = cc ? cc->k : 0, cK = cc ? cc->K : 1;
-  hipStream_t ss = (cc && cc->sort_stream) ? cc->sort_stream : s;      // the stream of the digit sort
-  if (cc && (n < SMALL_MAX_N || n > n_alloc)) { set_error("msm: chunk of %zu pairs (chunks hold 4097 .. %zu)", n, n_alloc); return MZK_E_ARG; }
+  if (cc && (n < SMALL_MAX_N || n > cc->n_alloc)) { set_error("msm: chunk of %zu pairs (chunks hold 4097 .. %zu)", n, cc->n_alloc); return MZK_E_ARG; }
   if (n == 0) {  // empty polynomial -> point at infinity (polynomial.rs:160)
     if (points_ready) MZK_TRY((*points_ready)());
     MZK_HIP(hipMemsetAsync(d_out, 0, out_partial_xyzz ? 128 : 64, s));
     return MZK_OK;
   }
-  DigitLayout L;
-  const int table_c = ((point_kind >> 8) & 0xff) ? ((point_kind >> 8) & 0xff) : 16;
-  const int table_sets = ((point_kind >> 16) & 0xff) ? ((point_kind >> 16) & 0xff) : 1;
-  point_kind &= 0xff;
-  L.merged = (point_kind == 2) ? 1 : 0;
-  L.sets = L.merged ? table_sets : 1;
-  L.table_stride = table_stride;
-  // generic layout: GLV split (mzk_glv.h) -- 2n points (P_i and phi(P_i) at phi_offset + i), half-length scalars
-  L.glv = L.merged ? 0 : 1;
-  L.phi_offset = (point_kind == 0) ? n_shape : table_stride;   // prepared below / laid out by the SRS handle
-  MsmShape sh = L.merged ? choose_shape(n_shape) : choose_shape_glv(n_shape);
-  if (L.merged) {
-    sh.c = table_c; sh.nwin = msm_table_windows(table_c); sh.lgB = sh.c - 1; sh.nbuckets = (size_t)L.sets << sh.lgB;
-  }
-  L.c = sh.c; L.nwin = sh.nwin;
-  const size_t NB = sh.nbuckets;
-  const bool one_set = L.merged && L.sets == 1;     // the tail writes the result itself: no Horner over bucket sets
-  const int red_windows = L.merged ? L.sets : sh.nwin;   // bucket sets to reduce
-  const int horner_c = one_set ? 0 : sh.c;
+  const size_t n_shape = cc ? cc->n_total : n, i0 = cc ? cc->i0 : 0;
+  const MsmPlan P = msm_plan(n, n_shape, cc ? cc->n_alloc : n, point_kind, table_stride, ctx().num_cu, cc ? cc->K : 0, msm_knobs());
+  if (P.err != MZK_OK) { set_error("%s", P.msg); return P.err; }
+  u32 *pm = nullptr, *counts = nullptr, *offsets = nullptr, *ranks = nullptr, *entries = nullptr, *scan = nullptr, *buckets = nullptr,
+      *slots = nullptr, *wghist = nullptr, *wsum = nullptr;
+  // one request per slot; in chunk mode the per-chunk slots hold one region (of `words`) per chunk, this chunk's is the k-th
+  const struct { WsSlot slot; size_t bytes; u32** p; size_t words; } req[] = {
+      {WS_MSM_POINTS, P.ws.points, &pm, 0}, {WS_MSM_COUNTS, P.ws.counts, &counts, 0}, {WS_MSM_OFFSETS, P.ws.offsets, &offsets, P.NBtot + 1},
+      {WS_MSM_CURSOR, P.ws.cursor, &ranks, 0}, {WS_MSM_ENTRIES, P.ws.entries, &entries, P.alloc.E}, {WS_MSM_SCAN, P.ws.scan, &scan, 0},
+      {WS_MSM_BUCKETS, P.ws.buckets, &buckets, P.NB * 32}, {WS_MSM_SLOTS, P.ws.slots, &slots, P.slot_region_words},
+      {WS_MSM_WGHIST, P.ws.wghist, &wghist, 0}, {WS_MSM_OUT, P.ws.out, &wsum, 0}};
+  for (const auto& r : req)
+    if (r.bytes) { MZK_TRY(ws_get(r.slot, r.bytes, (void**)r.p)); *r.p += (cc ? cc->k : 0) * r.words; }
   // (a chunk's entries count from its first pair: every table row / the endomorphism images sit at the same distance behind it)
-  const u32* pts = (const u32*)d_points + i0 * 16;
-  void* pm = nullptr;
-  if (point_kind == 0) {
-    MZK_TRY(ws_get(WS_MSM_POINTS, 2 * n_shape * 64, &pm));
-    pts = (const u32*)pm + i0 * 16;
-  }
+  const u32* pts = (pm ? pm : (const u32*)d_points) + i0 * 16;
   bool prepared = false;
   auto prepare = [&]() -> int {          // Montgomery form + endomorphism images of plain points; once, before their first reader
     if (prepared) return MZK_OK;
     prepared = true;
     if (points_ready) MZK_TRY((*points_ready)());
-    if (point_kind != 0) return MZK_OK;
+    if (!pm) return MZK_OK;
     prof_begin(s, MZK_PH_MSM_PREPARE);
-    MZK_TRY(msm_prepare_points((const u32*)d_points + i0 * 16, n, (u32*)pm + i0 * 16, (u32*)pm + (n_shape + i0) * 16, s));
+    MZK_TRY(msm_prepare_points((const u32*)d_points + i0 * 16, n, pm + i0 * 16, pm + (n_shape + i0) * 16, s));
     prof_end(s, MZK_PH_MSM_PREPARE);
     return MZK_OK;
   };
-  const size_t windows_per_pair = (size_t)(L.glv ? 2 * sh.nwin : sh.nwin);
-  const size_t E_max = n * windows_per_pair, E_alloc = n_alloc * windows_per_pair;
-  // (the generic layout has twice the entries per pair: measured at 4096 pairs it is 5 % slower on this path, the commit 14 % faster)
-  static const int env_scan = tune_int("MZK_SMALL_SCAN", 1);     // 0: A/B against the sorted path
-  static const int env_scan_log = tune_int("MZK_SCAN_MAX_LOG", 14);
-  const bool scan_ok = one_set && env_scan != 0 && n <= ((size_t)1 << env_scan_log) && (L.c == 8 || (L.c >= 10 && L.c <= 13));
-  if (!cc && (scan_ok || n < (L.merged ? SMALL_MAX_N : SMALL_MAX_N - 1)) && NB <= SMALL_MAX_BUCKETS) {
-    u32 *offsets, *entries, *buckets, *wsum;
-    MZK_TRY(ws_get(WS_MSM_OFFSETS, (NB + 1) * 4, (void**)&offsets));
-    MZK_TRY(ws_get(WS_MSM_ENTRIES, E_max * 4, (void**)&entries));
-    MZK_TRY(ws_get(WS_MSM_BUCKETS, NB * 128, (void**)&buckets));
-    MZK_TRY(ws_get(WS_MSM_OUT, (size_t)MAX_WINDOWS * 128, (void**)&wsum));
+  if (P.path == MsmPath::SmallScan) {      // two launches: every bucket's workgroup finds its own entries
     MZK_TRY(prepare());
-    if (scan_ok) {      // two launches: every bucket's workgroup finds its own entries
-      prof_begin(s, MZK_PH_MSM_ACCUMULATE);
-#define MZK_SCAN_CASE(C) case C: hipLaunchKernelGGL((k_small_accumulate_scan<256, C>), dim3((unsigned)NB), dim3(256), 0, s, (const u32*)d_scalars, n, L.table_stride, pts, buckets); break;
-      switch (L.c) { MZK_SCAN_CASE(8) MZK_SCAN_CASE(10) MZK_SCAN_CASE(11) MZK_SCAN_CASE(12) MZK_SCAN_CASE(13) }
+    prof_begin(s, MZK_PH_MSM_ACCUMULATE);
+#define MZK_SCAN_CASE(C) case C: hipLaunchKernelGGL((k_small_accumulate_scan<256, C>), dim3((unsigned)P.NB), dim3(256), 0, s, (const u32*)d_scalars, n, P.L.table_stride, pts, buckets); break;
+    switch (P.L.c) { MZK_SCAN_CASE(8) MZK_SCAN_CASE(10) MZK_SCAN_CASE(11) MZK_SCAN_CASE(12) MZK_SCAN_CASE(13) }
 #undef MZK_SCAN_CASE
-      prof_end(s, MZK_PH_MSM_ACCUMULATE);
-      MZK_TRY(reduce_bucket_sets(buckets, sh.lgB, red_windows, true, horner_c, wsum, (u32*)d_out, out_partial_xyzz, s));
-      MZK_HIP(hipGetLastError());
-      return MZK_OK;
-    }
+    prof_end(s, MZK_PH_MSM_ACCUMULATE);
+  } else if (P.path == MsmPath::SmallSort) {
+    MZK_TRY(prepare());
     prof_begin(s, MZK_PH_MSM_SORT);
-    hipLaunchKernelGGL(k_small_sort, dim3(1), dim3(SMALL_SORT_THREADS), (NB + SMALL_SORT_THREADS) * 4, s, (const u32*)d_scalars, n, L, (int)NB, offsets, entries);
+    hipLaunchKernelGGL(k_small_sort, dim3(1), dim3(SMALL_SORT_THREADS), (P.NB + SMALL_SORT_THREADS) * 4, s, (const u32*)d_scalars, n, P.L, (int)P.NB, offsets, entries);
     prof_end(s, MZK_PH_MSM_SORT);
     prof_begin(s, MZK_PH_MSM_ACCUMULATE);
-    if (E_max / NB > 64)      // ~256 entries per bucket (commits against narrow tables): a lane per entry
-      hipLaunchKernelGGL(k_small_accumulate<256>, dim3((unsigned)NB), dim3(256), 0, s, pts, (const u32*)offsets, (const u32*)entries, buckets);
+    if (P.small_wide)
+      hipLaunchKernelGGL(k_small_accumulate<256>, dim3((unsigned)P.NB), dim3(256), 0, s, pts, (const u32*)offsets, (const u32*)entries, buckets);
     else
-      hipLaunchKernelGGL(k_small_accumulate<64>, dim3((unsigned)NB), dim3(64), 0, s, pts, (const u32*)offsets, (const u32*)entries, buckets);
+      hipLaunchKernelGGL(k_small_accumulate<64>, dim3((unsigned)P.NB), dim3(64), 0, s, pts, (const u32*)offsets, (const u32*)entries, buckets);
     prof_end(s, MZK_PH_MSM_ACCUMULATE);
-    MZK_TRY(reduce_bucket_sets(buckets, sh.lgB, red_windows, one_set, horner_c, wsum, (u32*)d_out, out_partial_xyzz, s));
-    MZK_HIP(hipGetLastError());
-    return MZK_OK;
-  }
-  // entries pack the point reference into 31 bits (+ sign) and entry positions into 32: reject shapes that overflow
-  // (window widths below 16 on a > 2^26-point SRS) instead of gathering a wrong table row
-  {
-    const size_t ref_limit = L.merged ? (size_t)msm_table_rows(sh.c, L.sets) * table_stride : L.phi_offset + n;
-    if (ref_limit > ((size_t)1 << 31) || E_max >= ((size_t)1 << 32)) {
-      set_error("msm: %zu pairs x %d windows (table stride %zu) exceed the 31-bit point references / 32-bit entry offsets", n, sh.nwin, table_stride);
-      return MZK_E_ARG;
-    }
-  }
-  // Segment length: one lane per segment, sized as if four waves per SIMD were resident (E / (CUs * 4 * 4 * 64), >= 16).  Round 2's
-  // kernel had 123 VGPRs and the grid was exactly one round of resident waves; with the signed mixed addition of round 3 the
-  // compiler takes 140 VGPRs (three waves per SIMD), and the same segment length is still the fastest of the variants measured
-  // (profiles/r03o_accumulate_occupancy_ab.txt: shipped 1.05-1.06 ms at 2^20; __launch_bounds__(256, 4) = 128 VGPRs + 64 B of
-  // scratch 1.07-1.10; segments sized for three waves 1.07 with a cheaper segment combine: equal in total).
-  // (tools/timing/acc_sweep.py sweeps MZK_ACC_PREFETCH / MZK_ACC_SEG.)
-  static const int env_prefetch = tune_int("MZK_ACC_PREFETCH", -1);
-  static const int env_seg = tune_int("MZK_ACC_SEG", 0);
-  const bool acc_prefetch = env_prefetch >= 0 ? env_prefetch != 0 : false;
-  const size_t resident_lanes = (size_t)ctx().num_cu * 4 * (acc_prefetch ? 3 : 4) * 64;
-  size_t seg_sz = (E_max + resident_lanes - 1) / resident_lanes;
-  if (seg_sz < 16) seg_sz = 16;
-  if (env_seg > 0) seg_sz = (size_t)env_seg;
-  const u32 seg = (u32)seg_sz;
-  const size_t T = (E_max + seg_sz - 1) / seg_sz;
-  const u32 t_max = env_seg > 0 ? 0u : (u32)T;            // the kernels shorten the segments when the scalars emit fewer entries (segment_length)
-  const size_t nslots = T + NB + 1;
-  const size_t max_heavy = (T + NB) / HEAVY_SLOTS + 1;             // at most (T + NB) / 33 buckets hold more than 32 partials
-  const size_t heavy_words = heavy_total_words(max_heavy);
-  u32 *counts, *offsets, *ranks, *entries, *scan_tmp, *buckets, *slots;
-  // two-level sort when the bucket space is a power of two >= 2^12 (merged layout always; generic at c = 16)
-  // The two-level sort wants a power of two: the generic layout's 7 x 2^18 buckets (19-bit windows) sort as if there were an eighth,
-  // empty window -- the sort's arrays are sized by NBtot, its offsets beyond NB all equal the entry count, everything after the sort
-  // works on the NB real buckets.
-  size_t NBtot = NB;
-  if (L.glv && (NB & (NB - 1)) != 0 && sh.c >= 17) { NBtot = 1; while (NBtot < NB) NBtot <<= 1; }
-  MZK_TRY(ws_get(WS_MSM_COUNTS, 2 * NBtot * 4, (void**)&counts));      // (two-level sort, scan-free form: per-bucket totals + cursors)
-  // per-chunk buffers (chunk mode: cK of each, one behind the other; the sort's scratch is shared -- the chunks' sorts run one after
-  // the other on one stream, and nothing after a chunk's sort reads it)
-  MZK_TRY(ws_get(WS_MSM_OFFSETS, (size_t)cK * (NBtot + 1) * 4, (void**)&offsets));
-  offsets += (size_t)ck * (NBtot + 1);
-  // (small inputs keep the one-pass kernels, except that the merged one-pass histogram must fit the LDS: 2^15 buckets)
-  // coarse bins: 256, or 1024 for the 20-bit merged layout (2^19 buckets: 512 per bin instead of 2048; k_coarse_count)
-  static const int env_cl20 = tune_int("MZK_COARSE_LOG_20", 10);      // tuning build: 8 = the 256-bin form at 20 bits too
-  // (the generic GLV layout stays at 256 bins: its coarse scatter stores records one by one -- the walk is the GLV split, no staging --
-  // and 512 bins measured slower at 2^22 and 2^24: sort 3.77 -> 3.91 ms, profiles/round5_sort_1024_bins.txt)
-  int cl = (L.merged && !L.glv && L.sets == 1 && L.c == 20 && env_cl20 == 10) ? 10 : COARSE_LOG;
-  // 17-bit merged layout: 512 bins when that one bit is what lets the sort's intermediate records shrink from 8 to 4 bytes (reference
-  // 15 n < 2^24, 7-bit fine key, sign: 2^20 pairs exactly) -- the coarse scatter writes and both fine passes read half the bytes
-  // (profiles/round6_halving_multi_and_rec4_ab.txt; without that gain 512 bins lost to 256 in round 3: HISTORY)
-  static const int env_cl17 = tune_int("MZK_COARSE_LOG_17", 9);       // tuning build: 8 = the 256-bin form with 8-byte records
-  if (L.merged && !L.glv && L.sets == 1 && L.c == 17 && env_cl17 == 9 && cl == COARSE_LOG && COARSE_LOG == 8) {
-    const size_t ref_max17 = (size_t)msm_table_rows(sh.c, L.sets) * table_stride;
-    if (ref_max17 > ((size_t)1 << (31 - 8)) && ref_max17 <= ((size_t)1 << (31 - 7))) cl = 9;
-  }
-  if (L.glv && NBtot > ((size_t)STAGE_F_MAX << COARSE_LOG)) cl = 10;      // generic layout at 19 bits: 2^21 sorted buckets, 2048 per bin
-  const size_t cbins = (size_t)1 << cl;
-  const bool two_level = (NBtot & (NBtot - 1)) == 0 && NBtot >= 4096 && (NBtot / cbins) <= (size_t)FINE_MAX &&
-                         (n >= 4096 || ((point_kind & 0xff) == 2 && NBtot > ((size_t)1 << 15)));
-  if (cc && !two_level) { set_error("msm: chunk mode needs the two-level sort (layout %d bits, %zu buckets)", sh.c, NB); return MZK_E_ARG; }
-  MZK_TRY(ws_get(WS_MSM_CURSOR, E_alloc * (two_level ? 8 : 4), (void**)&ranks));
-  MZK_TRY(ws_get(WS_MSM_ENTRIES, (size_t)cK * E_alloc * 4, (void**)&entries));
-  entries += (size_t)ck * E_alloc;
-  MZK_TRY(ws_get(WS_MSM_SCAN, scan_scratch_words(NB) * 4, (void**)&scan_tmp));
-  MZK_TRY(ws_get(WS_MSM_BUCKETS, (size_t)cK * NB * 128, (void**)&buckets));
-  buckets += (size_t)ck * NB * 32;
-  // (a chunk never has more segments than resident lanes, nor than entries / 16: the slot region of every chunk is sized for that)
-  const size_t T_cap = cc ? ((resident_lanes + 1 < E_alloc / 16 + 1) ? resident_lanes + 1 : E_alloc / 16 + 1) : T;
-  const size_t nslots_cap = T_cap + NB + 1, heavy_words_cap = heavy_total_words((T_cap + NB) / HEAVY_SLOTS + 1);
-  const size_t slot_region_words = (nslots_cap * SLOT_WORDS + heavy_words_cap + 3) & ~(size_t)3;
-  MZK_TRY(ws_get(WS_MSM_SLOTS, (size_t)cK * slot_region_words * 4, (void**)&slots));
-  slots += (size_t)ck * slot_region_words;
-  u32* heavy = slots + nslots * SLOT_WORDS;
-  // the digit sort runs on `ss`: behind everything the main stream has enqueued so far (the workspace's previous users), and the
-  // accumulate on the main stream behind it
-  if (ss != s) {
-    hipEvent_t ev;
-    MZK_HIP(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-    const hipError_t e1 = hipEventRecord(ev, s), e2 = (e1 == hipSuccess) ? hipStreamWaitEvent(ss, ev, 0) : e1;
-    (void)hipEventDestroy(ev);
-    MZK_HIP(e2);
-  }
-  hipStream_t s_main = s;
-  s = ss;              // (the sort phase below is written against `s`)
-  prof_begin(s, MZK_PH_MSM_SORT);
-  // every slot k_seg_combine reads is written by k_seg_accumulate first (slot t + b exists exactly when segment t
-  // overlaps bucket b; checked by poisoning the array under the whole GPU suite), so only the heavy-bucket counter
-  // needs clearing
-  MZK_HIP(hipMemsetAsync(heavy, 0, HEAVY_CLEAR_BYTES, s));
-  const unsigned nblk = (unsigned)((n + 255) / 256);
-  if (two_level) {
-    int kb = 0;
-    while (((size_t)1 << kb) < NBtot) kb++;
-    const int key_shift = kb - cl;
-    const int F = (int)(NBtot / cbins);
-    const u32 fine_mask = (u32)F - 1u;
-    const int nwg = (int)((n + COARSE_PER_WG - 1) / COARSE_PER_WG);
-    // records per fine workgroup: 32 Ki for the merged layout, 16 Ki for the generic one (measured: generic sort 0.250 -> 0.230 ms
-    // at 2^20, merged equal within noise from 16 Ki to 64 Ki: profiles/r04m_*), 128 Ki when a bin has thousands of buckets
-    // (the [bucket][sub] histogram that is scanned afterwards has NB * S entries)
-    static const int env_per_fine = tune_int("MZK_PER_FINE", 0);      // tuning: tools/timing/window_sweep.py
-    const size_t per_fine = env_per_fine > 0 ? (size_t)env_per_fine : ((NBtot / cbins >= 4096) ? 131072 : (NBtot / cbins >= 2048) ? 65536 : (L.glv ? 16384 : 32768));
-    int S = (int)((E_max / cbins + per_fine - 1) / per_fine);
-    if (S < 2) S = 2;
-    if (S > 64) S = 64;
-    // fine workgroups: S slices for every bin + the extra slices of over-full bins (fine_plan: a slice holds at most 1.5 nominal ones)
-    const size_t slice_nom = (E_max + cbins * (size_t)S - 1) / (cbins * (size_t)S);
-    const size_t slice_cap = slice_nom + slice_nom / 2 + 1;
-    const size_t fine_wgs = cbins * (size_t)S + (E_max + slice_cap - 1) / slice_cap + 1;
-    const size_t n_coarse = cbins * nwg, n_fine = (size_t)F * fine_wgs;
-    u32 *binhist, *finehist;
-    // (chunk mode: sized for the largest chunk, the same request in every chunk's call)
-    const size_t nwg_a = (n_alloc + COARSE_PER_WG - 1) / COARSE_PER_WG, n_coarse_a = cbins * nwg_a;
-    const size_t slice_nom_a = (E_alloc + cbins * (size_t)64 - 1) / (cbins * (size_t)64);      // (S <= 64: the smallest nominal slice)
-    const size_t fine_wgs_a = cc ? cbins * 64 + (E_alloc + slice_nom_a) / (slice_nom_a + slice_nom_a / 2 + 1) + 2 : fine_wgs;
-    const size_t n_fine_a = cc ? (size_t)F * fine_wgs_a : n_fine;
-    MZK_TRY(ws_get(WS_MSM_WGHIST, ((cc ? n_coarse_a : n_coarse) + 1 + n_fine_a + 1 + cbins + 1) * 4, (void**)&binhist));
-    finehist = binhist + (cc ? n_coarse_a : n_coarse) + 1;
-    const size_t sb_f = (n_fine + SCAN_BLOCK - 1) / SCAN_BLOCK;
-    u32* scan2;
-    MZK_TRY(ws_get(WS_MSM_SCAN, (scan_scratch_words(cc ? n_coarse_a : n_coarse) + scan_scratch_words(n_fine_a) + 4) * 4, (void**)&scan2));
-    // scan-free sort (k_coarse_count, k_fine_scatter): no global scan at either level, nine launches -> five
-    static const int env_scan_free = tune_int("MZK_SORT_SCAN_FREE", 3);       // tuning build: bit 0 = coarse level, bit 1 = fine level
-    const bool coarse_free = (env_scan_free & 1) != 0 && cbins <= (size_t)SORT_CTR_BINS;
-    const bool fine_free = (env_scan_free & 2) != 0 && F <= STAGE_F_MAX;
-    u32* bin_tot = coarse_free ? heavy + SORT_CTR_AT : nullptr;
-    u32* bin_cur = coarse_free ? heavy + SORT_CTR_AT + SORT_CTR_BINS : nullptr;
-    u32* bin_start = coarse_free ? finehist + n_fine_a + 1 : nullptr;
-    u32* bucket_tot = fine_free ? counts : nullptr;                          // (counts: 2 NB words, see above)
-    u32* bucket_cur = fine_free ? counts + NBtot : nullptr;
-    u32* zero_ptr = fine_free ? counts : nullptr;
-    const size_t zero_words = fine_free ? 2 * NBtot : 0;
-#define MZK_CCOUNT(C, CLOG) hipLaunchKernelGGL((k_coarse_count<C, CLOG>), dim3(nwg), dim3(SORT2_THREADS), 0, s, (const u32*)d_scalars, n, L, key_shift, binhist, nwg, \
-                                               bin_tot, zero_ptr, zero_words)
-    const bool plain_merged = L.merged && !L.glv && L.sets == 1;
-    if (cl == 10 && L.glv) MZK_CCOUNT(0, 10);
-    else if (cl == 10) MZK_CCOUNT(20, 10);
-    else if (cl == 9) MZK_CCOUNT(17, 9);
-    else if (plain_merged && L.c == 20) MZK_CCOUNT(20, COARSE_LOG);
-    else if (plain_merged && L.c == 17) MZK_CCOUNT(17, COARSE_LOG);
-    else if (plain_merged && L.c == 16) MZK_CCOUNT(16, COARSE_LOG);
-    else MZK_CCOUNT(0, COARSE_LOG);
-#undef MZK_CCOUNT
-    if (!coarse_free) MZK_TRY(launch_exclusive_scan((const u32*)binhist, binhist, n_coarse, scan2, s));
-    int fb = 0;
-    while ((1 << fb) < F) fb++;
-    // largest point reference: merged nwin * stride, generic phi_offset + n
-    const size_t ref_max = L.merged ? (size_t)msm_table_rows(sh.c, L.sets) * table_stride : L.phi_offset + n;
-    const bool compact = ref_max <= ((size_t)1 << (31 - fb));      // references are < ref_max
-    SortArgs sa{(const u32*)d_scalars, n, L, key_shift, fine_mask, fb, binhist, nwg, (void*)ranks, F, S, finehist, scan2 + scan_scratch_words(cc ? n_coarse_a : n_coarse) + 2, sb_f, n_fine,
-                offsets, entries, NBtot, (unsigned)fine_wgs, (u32)slice_cap, cl, bin_tot, bin_cur, bin_start, bucket_tot, bucket_cur};
-    MZK_TRY(compact ? sort_records<Rec4>(sa, s) : sort_records<Rec8>(sa, s));
-  } else if (L.merged) {
-    // LDS histogram path (no global atomics)
-    int nwg = (int)((n + 4095) / 4096);
-    if (nwg > ctx().num_cu) nwg = ctx().num_cu;
-    if (nwg < 1) nwg = 1;
-    const size_t per_wg = (n + nwg - 1) / nwg;
-    u32* wg_hist;
-    MZK_TRY(ws_get(WS_MSM_WGHIST, (size_t)nwg * NB * 4, (void**)&wg_hist));
-    const size_t lds = NB * 4;
-    bool& lds_attr_set = ctx().attr_done[ATTR_DIGITS_LDS];
-    if (!lds_attr_set) {
-      MZK_HIP(hipFuncSetAttribute((const void*)k_digits_count_lds, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-      MZK_HIP(hipFuncSetAttribute((const void*)k_digits_scatter_lds, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-      lds_attr_set = true;
-    }
-    hipLaunchKernelGGL(k_digits_count_lds, dim3(nwg), dim3(LDS_SORT_THREADS), lds, s, (const u32*)d_scalars, n, per_wg, L, wg_hist, ranks);
-    hipLaunchKernelGGL(k_wg_hist_prefix, dim3((unsigned)((NB + 255) / 256)), dim3(256), 0, s, wg_hist, nwg, (int)NB, counts);
-    MZK_TRY(launch_exclusive_scan((const u32*)counts, offsets, NB, scan_tmp, s));
-    hipLaunchKernelGGL(k_digits_scatter_lds, dim3(nwg), dim3(LDS_SORT_THREADS), lds, s, (const u32*)d_scalars, n, per_wg, L, (const u32*)offsets,
-                       (const u32*)wg_hist, (const u32*)ranks, entries);
   } else {
-    MZK_HIP(hipMemsetAsync(counts, 0, NB * 4, s));
-    hipLaunchKernelGGL(k_digits_count, dim3(nblk), dim3(256), 0, s, (const u32*)d_scalars, n, L, counts, ranks);
-    MZK_TRY(launch_exclusive_scan((const u32*)counts, offsets, NB, scan_tmp, s));
-    hipLaunchKernelGGL(k_digits_scatter, dim3(nblk), dim3(256), 0, s, (const u32*)d_scalars, n, L, offsets, ranks, entries);
-  }
-  MZK_HIP(hipGetLastError());
-  prof_end(s, MZK_PH_MSM_SORT);
-  if (s != s_main) {       // the accumulate (main stream) behind this chunk's sort
-    hipEvent_t ev;
-    MZK_HIP(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-    const hipError_t e1 = hipEventRecord(ev, s), e2 = (e1 == hipSuccess) ? hipStreamWaitEvent(s_main, ev, 0) : e1;
-    (void)hipEventDestroy(ev);
-    MZK_HIP(e2);
-  }
-  s = s_main;
-  MZK_TRY(prepare());
-  prof_begin(s, MZK_PH_MSM_ACCUMULATE);
-  // the true entry count lives in offsets[NB] on the device; lanes past it exit (E_max bounds it)
+    u32* heavy = slots + P.nslots * SLOT_WORDS;
+    prof_begin(s, MZK_PH_MSM_SORT);
+    // every slot k_seg_combine reads is written by k_seg_accumulate first (slot t + b exists exactly when segment t
+    // overlaps bucket b; checked by poisoning the array under the whole GPU suite), so only the heavy-bucket counter
+    // needs clearing
+    MZK_HIP(hipMemsetAsync(heavy, 0, (size_t)HEAVY_HDR * 4, s));
+    if (P.path == MsmPath::TwoLevel) {
+      u32* finehist = wghist + P.alloc.n_coarse + 1;
+      const SortBufs sb{(const u32*)d_scalars, wghist, ranks, finehist, scan + scan_scratch_words(P.alloc.n_coarse) + 2, offsets, entries,
+                        P.coarse_free ? heavy + SORT_CTR_AT : nullptr, P.coarse_free ? heavy + SORT_CTR_AT + SORT_CTR_BINS : nullptr,
+                        P.coarse_free ? finehist + P.alloc.n_fine + 1 : nullptr, P.fine_free ? counts : nullptr, P.fine_free ? counts + P.NBtot : nullptr};
+#define MZK_CCOUNT(C, CLOG) hipLaunchKernelGGL((k_coarse_count<C, CLOG>), dim3(P.nwg), dim3(SORT2_THREADS), 0, s, (const u32*)d_scalars, n, P.L, P.key_shift, wghist, \
+                                               P.nwg, sb.bin_tot, sb.bucket_tot, P.fine_free ? 2 * P.NBtot : (size_t)0)
+      if (P.coarse_c == 20 && P.cl == 10) MZK_CCOUNT(20, 10);
+      else if (P.coarse_c == 17 && P.cl == 9) MZK_CCOUNT(17, 9);
+      else if (P.cl == 10) MZK_CCOUNT(0, 10);
+      else if (P.coarse_c == 20) MZK_CCOUNT(20, COARSE_LOG);
+      else if (P.coarse_c == 17) MZK_CCOUNT(17, COARSE_LOG);
+      else if (P.coarse_c == 16) MZK_CCOUNT(16, COARSE_LOG);
+      else MZK_CCOUNT(0, COARSE_LOG);
+#undef MZK_CCOUNT
+      if (!P.coarse_free) MZK_TRY(launch_exclusive_scan((const u32*)wghist, wghist, P.own.n_coarse, scan, s));
+      MZK_TRY(P.compact ? sort_records<Rec4>(P, sb, s) : sort_records<Rec8>(P, sb, s));
+    } else if (P.path == MsmPath::LdsOnePass) {      // LDS histogram path (no global atomics)
+      const size_t lds = P.NB * 4;
+      bool& lds_attr_set = ctx().attr_done[ATTR_DIGITS_LDS];
+      if (!lds_attr_set) {
+        MZK_HIP(hipFuncSetAttribute((const void*)k_digits_count_lds, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+        MZK_HIP(hipFuncSetAttribute((const void*)k_digits_scatter_lds, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+        lds_attr_set = true;
+      }
+      hipLaunchKernelGGL(k_digits_count_lds, dim3(P.nwg), dim3(LDS_SORT_THREADS), lds, s, (const u32*)d_scalars, n, P.per_wg, P.L, wghist, ranks);
+      hipLaunchKernelGGL(k_wg_hist_prefix, dim3((unsigned)((P.NB + 255) / 256)), dim3(256), 0, s, wghist, P.nwg, (int)P.NB, counts);
+      MZK_TRY(launch_exclusive_scan((const u32*)counts, offsets, P.NB, scan, s));
+      hipLaunchKernelGGL(k_digits_scatter_lds, dim3(P.nwg), dim3(LDS_SORT_THREADS), lds, s, (const u32*)d_scalars, n, P.per_wg, P.L, (const u32*)offsets,
+                         (const u32*)wghist, (const u32*)ranks, entries);
+    } else {
+      const unsigned nblk = (unsigned)((n + 255) / 256);
+      MZK_HIP(hipMemsetAsync(counts, 0, P.NB * 4, s));
+      hipLaunchKernelGGL(k_digits_count, dim3(nblk), dim3(256), 0, s, (const u32*)d_scalars, n, P.L, counts, ranks);
+      MZK_TRY(launch_exclusive_scan((const u32*)counts, offsets, P.NB, scan, s));
+      hipLaunchKernelGGL(k_digits_scatter, dim3(nblk), dim3(256), 0, s, (const u32*)d_scalars, n, P.L, offsets, ranks, entries);
+    }
+    MZK_HIP(hipGetLastError());
+    prof_end(s, MZK_PH_MSM_SORT);
+    MZK_TRY(prepare());
+    prof_begin(s, MZK_PH_MSM_ACCUMULATE);
+    // the true entry count lives in offsets[NB] on the device; lanes past it exit (E_max bounds it)
 #ifdef MZK_TUNING
-  if (acc_prefetch)
-    hipLaunchKernelGGL(k_seg_accumulate<true>, dim3((unsigned)((T + 255) / 256)), dim3(256), 0, s, pts, offsets, entries, slots, NB, seg, t_max);
-  else
+    if (P.prefetch)
+      hipLaunchKernelGGL(k_seg_accumulate<true>, dim3((unsigned)((P.T + 255) / 256)), dim3(256), 0, s, pts, offsets, entries, slots, P.NB, P.seg, P.t_max);
+    else
 #endif
-    hipLaunchKernelGGL(k_seg_accumulate<false>, dim3((unsigned)((T + 255) / 256)), dim3(256), 0, s, pts, offsets, entries, slots, NB, seg, t_max);
-  prof_end(s, MZK_PH_MSM_ACCUMULATE);
-  prof_begin(s, MZK_PH_MSM_SEG_COMBINE);
-  static const int wide_min_log = tune_int("MZK_COMBINE_WIDE_MIN_LOG", 17);
-  if (NB >= ((size_t)1 << wide_min_log))
-    hipLaunchKernelGGL(k_seg_combine_wide, dim3((unsigned)((NB + 127) / 128)), dim3(128), 0, s, slots, offsets, buckets, NB, seg, heavy, t_max);
-  else
-    hipLaunchKernelGGL(k_seg_combine<1>, dim3((unsigned)((4 * NB + 127) / 128)), dim3(128), 0, s, slots, offsets, buckets, NB, seg, heavy, (const u32*)nullptr, 0, t_max);
-  hipLaunchKernelGGL(k_seg_combine_heavy, dim3(HEAVY_GRID), dim3(HEAVY_THREADS), 0, s, (const u32*)slots, (const u32*)offsets, buckets, heavy, max_heavy);
-  MZK_HIP(hipGetLastError());
-  prof_end(s, MZK_PH_MSM_SEG_COMBINE);
-  if (cc) return MZK_OK;        // chunk mode: msm_chunked_impl sums the chunks' bucket arrays and reduces once
-
-  u32* wsum;
-  MZK_TRY(ws_get(WS_MSM_OUT, (size_t)MAX_WINDOWS * 128, (void**)&wsum));
-  MZK_TRY(reduce_bucket_sets(buckets, sh.lgB, red_windows, one_set, horner_c, wsum, (u32*)d_out, out_partial_xyzz, s));
+      hipLaunchKernelGGL(k_seg_accumulate<false>, dim3((unsigned)((P.T + 255) / 256)), dim3(256), 0, s, pts, offsets, entries, slots, P.NB, P.seg, P.t_max);
+    prof_end(s, MZK_PH_MSM_ACCUMULATE);
+    prof_begin(s, MZK_PH_MSM_SEG_COMBINE);
+    if (P.combine_wide)
+      hipLaunchKernelGGL(k_seg_combine_wide, dim3((unsigned)((P.NB + 127) / 128)), dim3(128), 0, s, slots, offsets, buckets, P.NB, P.seg, heavy, P.t_max);
+    else
+      hipLaunchKernelGGL(k_seg_combine<1>, dim3((unsigned)((4 * P.NB + 127) / 128)), dim3(128), 0, s, slots, offsets, buckets, P.NB, P.seg, heavy, (const u32*)nullptr, 0, P.t_max);
+    hipLaunchKernelGGL(k_seg_combine_heavy, dim3(HEAVY_GRID), dim3(HEAVY_THREADS), 0, s, (const u32*)slots, (const u32*)offsets, buckets, heavy, P.max_heavy);
+    MZK_HIP(hipGetLastError());
+    prof_end(s, MZK_PH_MSM_SEG_COMBINE);
+    if (cc) return MZK_OK;        // chunk mode: msm_chunked_impl sums the chunks' bucket arrays and reduces once
+  }
+  MZK_TRY(reduce_bucket_sets(buckets, P.lgB, P.red_windows, P.one_set, P.horner_c, wsum, (u32*)d_out, out_partial_xyzz, s));
   MZK_HIP(hipGetLastError());
   return MZK_OK;
 }
@@ -2089,18 +1814,13 @@ __global__ __launch_bounds__(128) void k_fold_bucket_sets(u32* __restrict__ buck
   for (int k = 1; k < K; k++) acc = xyzz_add_with<FeAsm>(acc, xyzz_gload(buckets, (size_t)k * NB + b));
   xyzz_gstore(buckets, b, acc);
 }
-// Chunk mode covers the layouts of the large calls: window tables with one bucket set, and the generic GLV layout -- from 2^18 pairs on
-// (every chunk must take the two-level sort and keep the accumulate's lanes busy).
-bool msm_chunkable(size_t n_total, int point_kind) {
-  const int kind = point_kind & 0xff, sets = ((point_kind >> 16) & 0xff) ? ((point_kind >> 16) & 0xff) : 1;
-  return n_total >= ((size_t)1 << 18) && (kind != MSM_PTS_TABLES || sets == 1);
-}
+bool msm_chunkable(size_t n_total, int point_kind, size_t table_stride) { return msm_chunkable(n_total, point_kind, table_stride, msm_knobs()); }
 // Sum over the chunks' pairs = the MSM of all n_total pairs (polynomial.rs:156-165 is a sum over independent pairs; the bucket sums
 // are too).  chunks[k].d_scalars: that chunk's scalars on the device; d_points: the WHOLE point array / table set.  A chunk is sorted
-// (on sort_stream if given -- then chunk k + 1's sort may run under chunk k's accumulate) and accumulated as soon as its `ready`
-// event has fired: the host-buffer entry points upload chunk k + 1 meanwhile.  Same canonical affine point as the one-piece call.
+// and accumulated as soon as its `ready` event has fired: the host-buffer entry points upload chunk k + 1 meanwhile.  Same canonical
+// affine point as the one-piece call.
 int msm_chunked_impl(const MsmChunk* chunks, int K, const void* d_points, size_t n_total, int point_kind, size_t table_stride, void* d_out,
-                     bool out_partial_xyzz, hipStream_t s, hipStream_t sort_stream, const std::function<int(int)>* before_chunk) {
+                     bool out_partial_xyzz, hipStream_t s, const std::function<int(int)>* before_chunk) {
   if (!chunks || K < 1 || K > 8 || !d_out || !d_points) { set_error("msm_chunked: bad argument"); return MZK_E_ARG; }
   size_t n_alloc = 0, covered = 0;
   for (int k = 0; k < K; k++) {
@@ -2108,33 +1828,27 @@ int msm_chunked_impl(const MsmChunk* chunks, int K, const void* d_points, size_t
     covered += chunks[k].n;
     n_alloc = chunks[k].n > n_alloc ? chunks[k].n : n_alloc;
   }
-  if (covered != n_total || !msm_chunkable(n_total, point_kind)) { set_error("msm_chunked: chunks do not cover a chunkable problem"); return MZK_E_ARG; }
+  if (covered != n_total || !msm_chunkable(n_total, point_kind, table_stride)) { set_error("msm_chunked: chunks do not cover a chunkable problem"); return MZK_E_ARG; }
   for (int k = 0; k < K; k++) {
     // before_chunk(k): the caller brings chunk k's inputs onto the device (a host-buffer entry point copies them here, blocking the
     // host while the GPU works on chunk k - 1) and records chunks[k].ready
     if (before_chunk) MZK_TRY((*before_chunk)(k));
-    if (chunks[k].ready) MZK_HIP(hipStreamWaitEvent(sort_stream ? sort_stream : s, chunks[k].ready, 0));
-    if (chunks[k].ready && sort_stream && (point_kind & 0xff) == MSM_PTS_PLAIN) MZK_HIP(hipStreamWaitEvent(s, chunks[k].ready, 0));     // the points are read on the main stream
-    const MsmChunkCtx cc{k, K, chunks[k].i0, n_total, n_alloc, sort_stream};
+    if (chunks[k].ready) MZK_HIP(hipStreamWaitEvent(s, chunks[k].ready, 0));
+    const MsmChunkCtx cc{k, K, chunks[k].i0, n_total, n_alloc};
     MZK_TRY(msm_dev_impl(chunks[k].d_scalars, d_points, chunks[k].n, point_kind, table_stride, d_out, out_partial_xyzz, s, nullptr, &cc));
   }
-  // the layout every chunk used (msm_dev_impl derives the same from n_total)
-  const int kind = point_kind & 0xff;
-  const int table_c = ((point_kind >> 8) & 0xff) ? ((point_kind >> 8) & 0xff) : 16;
-  const bool merged = kind == MSM_PTS_TABLES;
-  MsmShape sh = merged ? choose_shape(n_total) : choose_shape_glv(n_total);
-  if (merged) { sh.c = table_c; sh.nwin = msm_table_windows(table_c); sh.lgB = sh.c - 1; sh.nbuckets = (size_t)1 << sh.lgB; }
-  const size_t NB = sh.nbuckets;
+  // the plan every chunk followed (its largest chunk's): layout, bucket array
+  const MsmPlan P = msm_plan(n_alloc, n_total, n_alloc, point_kind, table_stride, ctx().num_cu, K, msm_knobs());
   u32 *buckets, *wsum;
-  MZK_TRY(ws_get(WS_MSM_BUCKETS, (size_t)K * NB * 128, (void**)&buckets));       // (the chunks' request: same size, same buffer)
+  MZK_TRY(ws_get(WS_MSM_BUCKETS, P.ws.buckets, (void**)&buckets));       // (the chunks' request: same size, same buffer)
   MZK_TRY(ws_get(WS_MSM_OUT, (size_t)MAX_WINDOWS * 128, (void**)&wsum));
   if (K > 1) {
     prof_begin(s, MZK_PH_MSM_SEG_COMBINE);
-    hipLaunchKernelGGL(k_fold_bucket_sets, dim3((unsigned)((NB + 127) / 128)), dim3(128), 0, s, buckets, NB, K);
+    hipLaunchKernelGGL(k_fold_bucket_sets, dim3((unsigned)((P.NB + 127) / 128)), dim3(128), 0, s, buckets, P.NB, K);
     MZK_HIP(hipGetLastError());
     prof_end(s, MZK_PH_MSM_SEG_COMBINE);
   }
-  MZK_TRY(reduce_bucket_sets(buckets, sh.lgB, merged ? 1 : sh.nwin, merged, merged ? 0 : sh.c, wsum, (u32*)d_out, out_partial_xyzz, s));
+  MZK_TRY(reduce_bucket_sets(buckets, P.lgB, P.red_windows, P.one_set, P.horner_c, wsum, (u32*)d_out, out_partial_xyzz, s));
   MZK_HIP(hipGetLastError());
   return MZK_OK;
 }
@@ -2323,7 +2037,7 @@ int msm_many_dev_impl(const void* d_scalars, size_t n, size_t stride_elems, size
     else MZK_TRY(ws_get(WS_MSM_OFFSETS, cnt * 4, (void**)&tails));
     u32* heavy = slots + nslots * SLOT_WORDS;
     prof_begin(s, MZK_PH_MSM_SORT);
-    MZK_HIP(hipMemsetAsync(heavy, 0, HEAVY_CLEAR_BYTES, s));
+    MZK_HIP(hipMemsetAsync(heavy, 0, (size_t)HEAVY_HDR * 4, s));
     const unsigned nwg = (unsigned)(cnt * (size_t)nch);
     const bool one_kernel_sort = nch == 1;      // polynomials of <= 1024 coefficients: fixed-capacity regions, k_many_sort1
     if (one_kernel_sort) {                      // its staged region is up to 128 KiB of LDS: the attribute, once per context

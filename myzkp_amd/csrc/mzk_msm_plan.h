@@ -1,0 +1,303 @@
+// mzk_msm_plan.h -- what one Pippenger MSM call (msm_dev_impl, mzk_msm.hip) does, decided on the host before anything is launched:
+// the bucket layout, the sort form, the accumulate's segments and the bytes of every workspace slot.  Host-only C++17 with no HIP
+// include, so that the decision can be compiled and checked on its own (tests/test_msm_plan.py).
+#pragma once
+#include <stddef.h>
+#include <stdint.h>
+#include <stdio.h>
+#include "../../include/mzk.h"
+
+namespace mzk {
+
+// point_kind: 0 = affine canonical (ABI form), 1 = affine Montgomery (prepared), 2 = SRS window tables (msm_table_rows(c, sets) x table_stride
+// affine Montgomery points: c-bit signed windows, 254 / c + 1 of them), with c in bits 8..15 (0 = 16) and the bucket sets in bits 16..23
+// (0 = one).  msm_plan decodes it; nothing else does.
+enum { MSM_PTS_PLAIN = 0, MSM_PTS_MONT = 1, MSM_PTS_TABLES = 2 };
+static inline int msm_table_windows(int c) { return 254 / c + 1; }
+// tables a handle with `sets` bucket sets holds: every sets-th window, ceil(windows / sets) = 254 / (c sets) + 1
+static inline int msm_table_rows(int c, int sets) { return 254 / (c * sets) + 1; }
+
+constexpr int SCALAR_BITS = 254;
+constexpr int MAX_WINDOWS = 32;
+constexpr int GLV_MAG_BITS = 126;      // |k1|, |k2| < 2^126 (mzk_glv.h)
+constexpr int SLOT_WORDS = 36;         // a segment partial: 4 x 9 raw limbs (mzk_msm.hip)
+
+// Bucket layout.  Generic MSM: bucket = window * 2^(c-1) + |digit| - 1, entry = point index.
+// Fixed-base MSM over precomputed tables T[w][i] = 2^(c w) P_i: every window shares ONE bucket set,
+// bucket = |digit| - 1, entry = w * table_stride + i.
+struct DigitLayout {
+  int c, nwin, merged;
+  int sets;              // merged layout: bucket sets (mzk_srs::sets); window w goes to set w % sets and reads table row w / sets
+  size_t table_stride;
+  int glv;               // generic layout only: scalars are GLV-split, the phi images of the points start at phi_offset
+  size_t phi_offset;
+};
+
+struct MsmShape { int c, nwin, lgB; size_t nbuckets; };     // window bits, windows, log2 buckets per window = c - 1, buckets
+// Generic layout after the GLV split: 2n points with scalars below 2^126.  Windows must cover 127 bits plus the
+// signed-digit carry; at c = 16 that is exactly 8 windows (2^18 buckets: the two-level sort's power of two).
+// force_c (MZK_GLV_C, tuning build): force a width (the sweep).
+static MsmShape choose_shape_glv(size_t n, int force_c = 0) {
+  int lg = 0;
+  while (((size_t)1 << lg) < 2 * n) lg++;
+  int c = lg - 3;
+  if (c < 8) c = 8;
+  if (c > 16) c = 16;
+  if (c == 15) c = 16;     // 2^17 pairs: 8 full windows + the two-level sort beat 9 windows with a 6-bit top window
+  // From 3 x 2^21 pairs on: 19 bits -- SEVEN windows per half instead of eight (14 mixed additions per pair, not 16: the accumulate is
+  // 80 % of the call), 7 x 2^18 buckets.  17 and 18 bits still need eight windows (7 x 18 = 126 leaves the top window nothing but
+  // carries), 20 bits also seven but twice the buckets, 22 bits six windows over 6 x 2^21 buckets whose reduction and one-pass sort cost
+  // more than the windows save.  The larger bucket set costs ~0.7 ms more to sort, combine and reduce whatever n is, the saved additions
+  // 0.145 ms per 2^20 pairs: 2^22 +3.6 %, 2^23 -2 %, 2^24 -6.5 %, 2^26 -7.5 % (profiles/round6_generic_window_sweep.txt).
+  if (n >= ((size_t)3 << 21)) c = 19;
+  if (force_c > 0) c = force_c;
+  // nwin windows must cover the 126 magnitude bits plus the signed-digit carry.  The top window only holds
+  // 126 - c (nwin - 1) real bits; if that is (almost) nothing, every scalar whose carry runs into it lands in the
+  // same few buckets (c = 14: ONE bucket receives a third of all entries) -- step c down until the top window is
+  // reasonably populated.
+  for (; c > 8; c--) {
+    const int nw = GLV_MAG_BITS / c + 1;
+    if (GLV_MAG_BITS - c * (nw - 1) >= 5) break;
+  }
+  MsmShape s;
+  s.c = c;
+  s.nwin = GLV_MAG_BITS / c + 1;
+  s.lgB = c - 1;
+  s.nbuckets = (size_t)s.nwin << s.lgB;
+  return s;
+}
+
+// ---- the sort's constants --------------------------------------------------------------------------------------------------------
+#ifndef MZK_COARSE_LOG
+#define MZK_COARSE_LOG 8
+#endif
+constexpr int COARSE_LOG = MZK_COARSE_LOG;      // 9: A/B build (one more bit for the point reference in the 4-byte sort records)
+constexpr int COARSE_PER_WG = 4096;
+constexpr int FINE_MAX = 8192;     // buckets per bin: NB / 256 (128 merged c = 16, 2048 generic c = 16, 8192 merged c = 22)
+constexpr int STAGE_F_MAX = 2048;  // the most buckets per bin k_fine_scatter stages in LDS
+constexpr size_t SMALL_MAX_N = 4097;          // exclusive: 4096 (a blob of das/avail.rs) still takes the three-launch path
+constexpr size_t SMALL_MAX_BUCKETS = 8192;
+// launch_exclusive_scan (mzk_msm.hip): blocks of SCAN_BLOCK; above SCAN_DIRECT_BLOCKS of them their totals are scanned recursively
+constexpr int SCAN_ITEMS = 8;                      // per thread
+constexpr int SCAN_BLOCK = 256 * SCAN_ITEMS;       // 2048 per block
+constexpr size_t SCAN_DIRECT_BLOCKS = 2048;
+static inline size_t scan_scratch_words(size_t n) {
+  const size_t sb = (n + SCAN_BLOCK - 1) / SCAN_BLOCK;
+  return sb + 2 + (sb > SCAN_DIRECT_BLOCKS ? scan_scratch_words(sb) : 0);
+}
+// Buckets with more than HEAVY_SLOTS segment partials are summed by a whole workgroup each (k_seg_combine_heavy, mzk_msm.hip).
+constexpr uint32_t HEAVY_SLOTS = 32;
+// Layout of `heavy`: [0] count, [1] the segment length in force (written by the combine kernel), [2, 2 + HEAVY_GRID) arrival counters of k_seg_combine_heavy's shared buckets (zeroed with
+// the count, one memset), then (bucket id, end of its entries as the deferring kernel saw it -- bucket_end) pairs, then HEAVY_GRID
+// XYZZ records of scratch for the workgroups that share a bucket.
+// Behind the arrival counters, inside the same cleared header: the scan-free sort's per-bin totals and cursors (k_coarse_count /
+// k_coarse_scatter*: SORT_CTR_BINS words each) -- one memset per call clears everything that has to start at zero.
+constexpr int HEAVY_GRID = 512;
+constexpr int SORT_CTR_BINS = 1024;               // the most coarse bins any layout uses (20-bit merged windows)
+constexpr int SORT_CTR_AT = 2 + HEAVY_GRID;       // bin totals at heavy[SORT_CTR_AT ..), bin cursors SORT_CTR_BINS words further
+constexpr int HEAVY_HDR = SORT_CTR_AT + 2 * SORT_CTR_BINS;
+// (a multiple of four words: the scratch records behind the list are read and written as uint4)
+constexpr size_t heavy_list_words(size_t max_heavy) { return (HEAVY_HDR + 2 * max_heavy + 2 + 3) & ~(size_t)3; }
+constexpr size_t heavy_total_words(size_t max_heavy) { return heavy_list_words(max_heavy) + (size_t)HEAVY_GRID * 32 + 8; }
+
+// ---- the plan ----------------------------------------------------------------------------------------------------------------------
+// The MSM's tuning switches: the shipped values here; the tuning build reads MZK_<NAME> over them, in this order (mzk_msm.hip).
+struct MsmKnobs {
+  int glv_c = 0;                  // MZK_GLV_C: force the generic layout's width
+  int small_scan = 1;             // MZK_SMALL_SCAN: 0 = A/B against the sorted path
+  int scan_max_log = 14;          // MZK_SCAN_MAX_LOG
+  int acc_prefetch = -1;          // MZK_ACC_PREFETCH (tools/timing/acc_sweep.py sweeps it and MZK_ACC_SEG)
+  int acc_seg = 0;                // MZK_ACC_SEG: a fixed segment length
+  int coarse_log_20 = 10;         // MZK_COARSE_LOG_20: 8 = the 256-bin form at 20 bits too
+  int coarse_log_17 = 9;          // MZK_COARSE_LOG_17: 8 = the 256-bin form with 8-byte records
+  int per_fine = 0;               // MZK_PER_FINE: records per fine workgroup (tools/timing/window_sweep.py)
+  int sort_scan_free = 3;         // MZK_SORT_SCAN_FREE: bit 0 = coarse level, bit 1 = fine level
+  int coarse_staged = 1;          // MZK_COARSE_STAGED: 0 = A/B against the direct stores
+  int combine_wide_min_log = 17;  // MZK_COMBINE_WIDE_MIN_LOG
+};
+
+enum class MsmPath { SmallScan, SmallSort, TwoLevel, LdsOnePass, Atomic };
+// Bytes per workspace slot (0: not asked for).  offsets, entries, buckets and slots hold one region per chunk in chunk mode.
+struct MsmWsBytes { size_t points, counts, offsets, cursor, entries, buckets, scan, slots, wghist, out; };
+struct MsmSizing { size_t E, T, n_coarse, n_fine; };     // what the sized buffers hold: entries, segments, coarse / fine histogram words
+
+struct MsmPlan {
+  int err = MZK_OK;
+  char msg[192] = {};
+  size_t n = 0;                                // pairs of this call
+  DigitLayout L{};
+  int lgB = 0, red_windows = 0, horner_c = 0;  // log2 buckets per set, bucket sets to reduce, Horner width over them (0: none)
+  size_t NB = 0, NBtot = 0;                    // buckets; the two-level sort's power of two >= NB
+  bool one_set = false, small_wide = false;    // the tail writes the result itself (no Horner over bucket sets); small sort: a lane per entry
+  MsmPath path = MsmPath::SmallSort;
+  // two-level sort (log2 coarse bins, buckets per bin, fine key bits, slices per bin); sort workgroups (two-level: coarse, LDS path: one-pass)
+  int cl = 0, F = 0, fb = 0, key_shift = 0, S = 0, nwg = 0;
+  uint32_t fine_mask = 0, slice_cap = 0;
+  unsigned fine_wgs = 0;
+  size_t per_wg = 0;                           // LDS path: pairs per workgroup
+  bool compact = false, coarse_free = false, fine_free = false, scatter_staged = false;   // 4-byte records, scan-free levels, staged scatter
+  int coarse_c = 0;                            // the compile-time merged width of the coarse count / scatter kernels (0: any layout)
+  // accumulate
+  uint32_t seg = 0, t_max = 0;
+  size_t T = 0, nslots = 0, max_heavy = 0, slot_region_words = 0;    // (one chunk's slots + heavy list)
+  bool prefetch = false, combine_wide = false;
+  MsmSizing own{}, alloc{};                    // what this call touches; what its buffers are sized for (the largest chunk in chunk mode)
+  MsmWsBytes ws{}, ws_used{};                  // requests; the same formula over `own` (no chunk outgrows its region)
+  MsmPlan& fail(const char* fmt, size_t a = 0, size_t b = 0, size_t c = 0) { err = MZK_E_ARG; snprintf(msg, sizeof msg, fmt, a, b, c); return *this; }
+};
+
+// one chunk's segment partials (T + NB + 1 slots) and heavy-bucket list, rounded to four words
+static inline size_t msm_slot_region_words(size_t T, size_t NB) {
+  return ((T + NB + 1) * SLOT_WORDS + heavy_total_words((T + NB) / HEAVY_SLOTS + 1) + 3) & ~(size_t)3;
+}
+// the bytes of the slots that grow with the problem (ws over `alloc`, ws_used over `own`); `regions` copies of the per-chunk ones
+static inline MsmPlan& msm_sized(MsmPlan& P, size_t regions) {
+  for (int u = 0; u < 2; u++) {
+    const MsmSizing& z = u ? P.own : P.alloc;
+    MsmWsBytes& w = u ? P.ws_used : P.ws;
+    w.points = P.ws.points, w.out = P.ws.out;
+    w.offsets = regions * (P.NBtot + 1) * 4;
+    w.entries = regions * z.E * 4;
+    w.buckets = regions * P.NB * 128;
+    if (P.path == MsmPath::SmallScan || P.path == MsmPath::SmallSort) continue;
+    const bool two = P.path == MsmPath::TwoLevel;
+    w.counts = 2 * P.NBtot * 4;      // (two-level sort, scan-free form: per-bucket totals + cursors)
+    w.cursor = z.E * (two ? 8 : 4);
+    w.slots = regions * msm_slot_region_words(z.T, P.NB) * 4;
+    w.wghist = two ? (z.n_coarse + 1 + z.n_fine + 1 + ((size_t)1 << P.cl) + 1) * 4 : P.path == MsmPath::LdsOnePass ? (size_t)P.nwg * P.NB * 4 : 0;
+    w.scan = two ? (scan_scratch_words(z.n_coarse) + scan_scratch_words(z.n_fine) + 4) * 4 : scan_scratch_words(P.NB) * 4;
+  }
+  return P;
+}
+
+// n pairs of a problem of n_shape pairs (the layout follows n_shape), buffers sized for n_alloc pairs.  chunks = 0: one whole call;
+// K >= 1: one chunk of an MSM in K chunks (msm_chunked_impl: every chunk's call asks for the same bytes, K regions of the per-chunk
+// slots, and stops before the reduction).
+static inline MsmPlan msm_plan(size_t n, size_t n_shape, size_t n_alloc, int point_kind, size_t table_stride, int num_cu, int chunks,
+                               const MsmKnobs& kn) {
+  MsmPlan P;
+  P.n = n;
+  if (n > ((size_t)1 << 27)) return P.fail("msm: n > 2^27 not supported");
+  const int kind = point_kind & 0xff, table_c = (point_kind >> 8) & 0xff, table_sets = (point_kind >> 16) & 0xff;
+  DigitLayout& L = P.L;
+  L.merged = kind == MSM_PTS_TABLES;
+  L.sets = (L.merged && table_sets) ? table_sets : 1;
+  L.table_stride = table_stride;
+  // generic layout: GLV split (mzk_glv.h) -- 2n points (P_i and phi(P_i) at phi_offset + i), half-length scalars
+  L.glv = !L.merged;
+  L.phi_offset = kind == MSM_PTS_PLAIN ? n_shape : table_stride;   // prepared by msm_dev_impl / laid out by the SRS handle
+  const MsmShape sh = choose_shape_glv(n_shape, kn.glv_c);
+  L.c = L.merged ? (table_c ? table_c : 16) : sh.c;
+  L.nwin = L.merged ? msm_table_windows(L.c) : sh.nwin;
+  P.NB = L.merged ? (size_t)L.sets << (L.c - 1) : sh.nbuckets;
+  P.lgB = L.c - 1, P.red_windows = L.merged ? L.sets : L.nwin;
+  P.one_set = L.merged && L.sets == 1, P.horner_c = P.one_set ? 0 : L.c;
+  const size_t windows_per_pair = L.glv ? 2 * L.nwin : L.nwin, regions = chunks ? chunks : 1;
+  const size_t E_max = P.own.E = n * windows_per_pair, E_alloc = P.alloc.E = n_alloc * windows_per_pair;
+  P.ws.points = kind == MSM_PTS_PLAIN ? 2 * n_shape * 64 : 0;
+  P.ws.out = chunks ? 0 : (size_t)MAX_WINDOWS * 128;
+  // The two-level sort wants a power of two: the generic layout's 7 x 2^18 buckets (19-bit windows) sort as if there were an eighth,
+  // empty window -- the sort's arrays are sized by NBtot, its offsets beyond NB all equal the entry count, everything after the sort
+  // works on the NB real buckets.
+  P.NBtot = P.NB;
+  if (L.glv && (P.NB & (P.NB - 1)) != 0 && L.c >= 17) { P.NBtot = 1; while (P.NBtot < P.NB) P.NBtot <<= 1; }
+
+  // (the generic layout has twice the entries per pair: measured at 4096 pairs it is 5 % slower on this path, the commit 14 % faster)
+  const bool scan_ok = P.one_set && kn.small_scan != 0 && n <= ((size_t)1 << kn.scan_max_log) && (L.c == 8 || (L.c >= 10 && L.c <= 13));
+  if (!chunks && (scan_ok || n < (L.merged ? SMALL_MAX_N : SMALL_MAX_N - 1)) && P.NB <= SMALL_MAX_BUCKETS) {
+    P.path = scan_ok ? MsmPath::SmallScan : MsmPath::SmallSort;
+    P.small_wide = E_max / P.NB > 64;     // ~256 entries per bucket (commits against narrow tables): a lane per entry
+    return msm_sized(P, 1);
+  }
+  // entries pack the point reference into 31 bits (+ sign) and entry positions into 32: reject shapes that overflow
+  // (window widths below 16 on a > 2^26-point SRS) instead of gathering a wrong table row
+  const size_t ref_max = L.merged ? (size_t)msm_table_rows(L.c, L.sets) * table_stride : L.phi_offset + n;
+  if (ref_max > ((size_t)1 << 31) || E_max >= ((size_t)1 << 32))
+    return P.fail("msm: %zu pairs x %zu windows (table stride %zu) exceed the 31-bit point references / 32-bit entry offsets", n, (size_t)L.nwin, table_stride);
+
+  // Segment length: one lane per segment, sized as if four waves per SIMD were resident (E / (CUs * 4 * 4 * 64), >= 16).  Round 2's
+  // kernel had 123 VGPRs and the grid was exactly one round of resident waves; with the signed mixed addition of round 3 the
+  // compiler takes 140 VGPRs (three waves per SIMD), and the same segment length is still the fastest of the variants measured
+  // (profiles/r03o_accumulate_occupancy_ab.txt: shipped 1.05-1.06 ms at 2^20; __launch_bounds__(256, 4) = 128 VGPRs + 64 B of
+  // scratch 1.07-1.10; segments sized for three waves 1.07 with a cheaper segment combine: equal in total).
+  P.prefetch = kn.acc_prefetch > 0;
+  const size_t resident_lanes = (size_t)num_cu * 4 * (P.prefetch ? 3 : 4) * 64;
+  size_t seg = (E_max + resident_lanes - 1) / resident_lanes;
+  seg = kn.acc_seg > 0 ? (size_t)kn.acc_seg : seg < 16 ? 16 : seg;
+  P.seg = (uint32_t)seg;
+  P.T = P.own.T = (E_max + seg - 1) / seg;
+  P.t_max = kn.acc_seg > 0 ? 0u : (uint32_t)P.T;       // the kernels shorten the segments when the scalars emit fewer entries (segment_length)
+  P.nslots = P.T + P.NB + 1;
+  P.max_heavy = (P.T + P.NB) / HEAVY_SLOTS + 1;        // at most (T + NB) / 33 buckets hold more than 32 partials
+  P.combine_wide = P.NB >= ((size_t)1 << kn.combine_wide_min_log);
+  // (a chunk never has more segments than resident lanes, nor than entries / 16 -- entries / MZK_ACC_SEG with a fixed length: the
+  // slot region of every chunk is sized for that)
+  const size_t T_seg = E_alloc / (kn.acc_seg > 0 ? (size_t)kn.acc_seg : 16) + 1;
+  P.alloc.T = !chunks ? P.T : kn.acc_seg > 0 ? T_seg : (resident_lanes + 1 < T_seg ? resident_lanes + 1 : T_seg);
+  P.slot_region_words = msm_slot_region_words(P.alloc.T, P.NB);
+
+  // two-level sort when the bucket space is a power of two >= 2^12 (merged layout always; generic at c = 16)
+  const bool plain_merged = L.merged && L.sets == 1;
+  // (small inputs keep the one-pass kernels, except that the merged one-pass histogram must fit the LDS: 2^15 buckets)
+  // coarse bins: 256, or 1024 for the 20-bit merged layout (2^19 buckets: 512 per bin instead of 2048; k_coarse_count)
+  // (the generic GLV layout stays at 256 bins: its coarse scatter stores records one by one -- the walk is the GLV split, no staging --
+  // and 512 bins measured slower at 2^22 and 2^24: sort 3.77 -> 3.91 ms, profiles/round5_sort_1024_bins.txt)
+  P.cl = (plain_merged && L.c == 20 && kn.coarse_log_20 == 10) ? 10 : COARSE_LOG;
+  // 17-bit merged layout: 512 bins when that one bit is what lets the sort's intermediate records shrink from 8 to 4 bytes (reference
+  // 15 n < 2^24, 7-bit fine key, sign: 2^20 pairs exactly) -- the coarse scatter writes and both fine passes read half the bytes
+  // (profiles/round6_halving_multi_and_rec4_ab.txt; without that gain 512 bins lost to 256 in round 3: HISTORY)
+  if (plain_merged && L.c == 17 && kn.coarse_log_17 == 9 && COARSE_LOG == 8 && ref_max > ((size_t)1 << (31 - 8)) && ref_max <= ((size_t)1 << (31 - 7)))
+    P.cl = 9;
+  if (L.glv && P.NBtot > ((size_t)STAGE_F_MAX << COARSE_LOG)) P.cl = 10;      // generic layout at 19 bits: 2^21 sorted buckets, 2048 per bin
+  const size_t cbins = (size_t)1 << P.cl;
+  const bool two_level = (P.NBtot & (P.NBtot - 1)) == 0 && P.NBtot >= 4096 && (P.NBtot / cbins) <= (size_t)FINE_MAX &&
+                         (n >= 4096 || (L.merged && P.NBtot > ((size_t)1 << 15)));
+  if (chunks && !two_level) return P.fail("msm: chunk mode needs the two-level sort (layout %zu bits, %zu buckets)", (size_t)L.c, P.NB);
+  P.path = two_level ? MsmPath::TwoLevel : L.merged ? MsmPath::LdsOnePass : MsmPath::Atomic;
+  if (P.path == MsmPath::LdsOnePass) {       // one-pass workgroups: one per 4096 pairs, at most one per CU
+    const size_t nwg = (n + 4095) / 4096;
+    P.nwg = nwg < 1 ? 1 : nwg > (size_t)num_cu ? num_cu : (int)nwg;
+    P.per_wg = (n + P.nwg - 1) / P.nwg;
+  }
+  if (!two_level) return msm_sized(P, regions);
+  while (((size_t)1 << P.key_shift) < P.NBtot) P.key_shift++;
+  P.key_shift -= P.cl;
+  P.F = (int)(P.NBtot / cbins);
+  P.fine_mask = (uint32_t)P.F - 1u;
+  while ((1 << P.fb) < P.F) P.fb++;
+  P.nwg = (int)((n + COARSE_PER_WG - 1) / COARSE_PER_WG);
+  // records per fine workgroup: 32 Ki for the merged layout, 16 Ki for the generic one (measured: generic sort 0.250 -> 0.230 ms
+  // at 2^20, merged equal within noise from 16 Ki to 64 Ki: profiles/r04m_*), 128 Ki when a bin has thousands of buckets
+  // (the [bucket][sub] histogram that is scanned afterwards has NB * S entries)
+  const size_t per_fine = kn.per_fine > 0 ? (size_t)kn.per_fine : (P.F >= 4096 ? 131072 : P.F >= 2048 ? 65536 : (L.glv ? 16384 : 32768));
+  const size_t S = (E_max / cbins + per_fine - 1) / per_fine;
+  P.S = S < 2 ? 2 : S > 64 ? 64 : (int)S;
+  // fine workgroups: S slices for every bin + the extra slices of over-full bins (fine_plan: a slice holds at most 1.5 nominal ones)
+  const size_t slice_nom = (E_max + cbins * (size_t)P.S - 1) / (cbins * (size_t)P.S);
+  P.slice_cap = (uint32_t)(slice_nom + slice_nom / 2 + 1);
+  P.fine_wgs = (unsigned)(cbins * (size_t)P.S + (E_max + P.slice_cap - 1) / P.slice_cap + 1);
+  P.own.n_coarse = cbins * P.nwg;
+  P.own.n_fine = (size_t)P.F * P.fine_wgs;
+  // (chunk mode: sized for the largest chunk, the same request in every chunk's call)
+  const size_t slice_nom_a = (E_alloc + cbins * (size_t)64 - 1) / (cbins * (size_t)64);      // (S <= 64: the smallest nominal slice)
+  P.alloc.n_coarse = chunks ? cbins * ((n_alloc + COARSE_PER_WG - 1) / COARSE_PER_WG) : P.own.n_coarse;
+  P.alloc.n_fine = chunks ? (size_t)P.F * (cbins * 64 + (E_alloc + slice_nom_a) / (slice_nom_a + slice_nom_a / 2 + 1) + 2) : P.own.n_fine;
+  P.compact = ref_max <= ((size_t)1 << (31 - P.fb));      // references are < ref_max
+  // scan-free sort (k_coarse_count, k_fine_scatter): no global scan at either level, nine launches -> five
+  P.coarse_free = (kn.sort_scan_free & 1) != 0 && cbins <= (size_t)SORT_CTR_BINS;
+  P.fine_free = (kn.sort_scan_free & 2) != 0 && P.F <= STAGE_F_MAX;
+  P.coarse_c = (plain_merged && (L.c == 16 || L.c == 17 || L.c == 20)) ? L.c : 0;     // the default widths by SRS size
+  P.scatter_staged = P.coarse_c != 0 && (kn.coarse_staged != 0 || P.cl != COARSE_LOG);
+  return msm_sized(P, regions);
+}
+
+// Chunk mode (msm_chunked_impl) covers the problems whose every chunk takes the two-level sort with one bucket set: the generic layout
+// and window tables of 13 bits and more, from 2^18 pairs on (every chunk must keep the accumulate's lanes busy).  The path does not
+// depend on the CU count.
+static inline bool msm_chunkable(size_t n_total, int point_kind, size_t table_stride, const MsmKnobs& kn) {
+  if (n_total < ((size_t)1 << 18)) return false;
+  const MsmPlan P = msm_plan(n_total, n_total, n_total, point_kind, table_stride, 256, 1, kn);
+  return P.err == MZK_OK && P.L.sets == 1 && P.path == MsmPath::TwoLevel;
+}
+
+}  // namespace mzk

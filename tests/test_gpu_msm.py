@@ -288,3 +288,32 @@ def test_host_buffer_calls_in_pieces_equal_the_resident_calls(mz, n):
     assert L.mzk_kzg_commit_srs(h, hs.ctypes.data_as(ctypes.c_void_p), ctypes.c_size_t(m), got.ctypes.data_as(ctypes.c_void_p)) == 0
     assert mz.array_to_points(got)[0] == orc.msm_fast(hs[:m], hp[:m])
     L.mzk_srs_free(h)
+
+
+@pytest.mark.parametrize("with_tables", [8, 10, 12, 13])
+def test_host_commit_on_narrow_tables_at_the_piece_threshold(mz, with_tables):
+    """Pieces need the two-level sort: narrow window tables (2^(c-1) <= 2048 buckets) sort in one pass, so a host-buffer commit
+    of >= 2^18 coefficients on such a handle takes the one-piece path (msm_chunkable asks the plan); 13 bits is chunked"""
+    import ctypes
+    import torch
+    n = 1 << 18
+    L, dev = mz.lib(), torch.device("cuda", 0)
+    L.mzk_last_error.restype = ctypes.c_char_p
+    st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+    sc = torch.empty(n * 4, dtype=torch.int64, device=dev)
+    pt = torch.empty(n * 8, dtype=torch.int64, device=dev)
+    assert L.mzk_synth_field_dev(0, ctypes.c_uint64(7300 + with_tables), ctypes.c_size_t(n), ctypes.c_void_p(sc.data_ptr()), st) == 0
+    assert L.mzk_synth_g1_points_dev(ctypes.c_uint64(7400 + with_tables), ctypes.c_size_t(n), ctypes.c_void_p(pt.data_ptr()), st) == 0
+    h = ctypes.c_void_p()
+    assert L.mzk_srs_from_device_ex(ctypes.c_void_p(pt.data_ptr()), ctypes.c_size_t(n), ctypes.c_int(with_tables), ctypes.byref(h), st) == 0, L.mzk_last_error()
+    out = torch.zeros(8, dtype=torch.int64, device=dev)
+    assert L.mzk_kzg_commit_srs_dev(h, ctypes.c_void_p(sc.data_ptr()), ctypes.c_size_t(n), ctypes.c_void_p(out.data_ptr()), 0, st) == 0, L.mzk_last_error()
+    torch.cuda.synchronize()
+    hs = sc.cpu().numpy().view(np.uint64).reshape(n, 4).copy()
+    hp = pt.cpu().numpy().view(np.uint64).reshape(n, 8).copy()
+    want = orc.msm_fast(hs, hp)
+    assert mz.array_to_points(out.cpu().numpy().view(np.uint64).reshape(1, 8))[0] == want, "device-resident commit"
+    got = np.zeros((1, 8), dtype=np.uint64)
+    assert L.mzk_kzg_commit_srs(h, hs.ctypes.data_as(ctypes.c_void_p), ctypes.c_size_t(n), got.ctypes.data_as(ctypes.c_void_p)) == 0, L.mzk_last_error()
+    assert mz.array_to_points(got)[0] == want, "host-scalar commit"
+    L.mzk_srs_free(h)
