@@ -278,6 +278,45 @@ int mzk_fri_commit_keep_trees_dev(int field_id, const void* d_magnitudes, const 
  * their Sign::Minus flags (all 0 unless the tree was built from signed leaves). */
 int mzk_merkle_leaves(const mzk_merkle* tree, const uint64_t* indices, size_t count, uint64_t* magnitudes, uint8_t* negative);
 
+/* FRI::prove (zkstark/fri.rs:99-143) in one call: commit, the proof stream, sample_indices and reveal all run on the device; the
+ * result is the reference's FriProof, packed.  The proof stream is the reference's FiatShamirTransformer started empty: bincode 1.x
+ * (u64 LE lengths) of Vec<Vec<Vec<u8>>>; round r pushes vec![root_r] and, unless it is the last round, takes
+ * alpha = F::sample(SHAKE256(stream)[0..32]) (the last 8 bytes big-endian); after the last root the last codeword is pushed as one
+ * object of bincode(FiniteFieldElement) leaves and seed = SHAKE256(stream)[0..32]; top-level indices: Blake2b-256(seed || counter
+ * as u64 LE), sample_index % (n/2), kept when their residue mod the last codeword's length is new (fri.rs:19-62).  The leaf bytes
+ * are the library's restatement of bincode(FiniteFieldElement) (see the Merkle section), not pinned against a Rust vector.
+ *
+ * num_rounds = FRI::num_rounds(n, expansion_factor, num_colinearity_tests) (fri.rs:86-97).  Errors, before anything is enqueued:
+ * bad field id, null pointer (MZK_E_ARG); n == 0 or num_rounds < 2 (MZK_E_LENGTH: the reference indexes codewords[1]);
+ * n not a power of two (MZK_E_NOT_POW2); num_colinearity_tests > the last codeword's length (MZK_E_ARG, the reference's
+ * "cannot sample more indices than available in last codeword" assertion); omega / offset not canonical (MZK_E_RANGE);
+ * proof_cap below the layout's total (MZK_E_LENGTH).  negative (optional): Sign::Minus flags of the initial codeword, which is
+ * then given as magnitudes (mzk_fri_commit_signed semantics: round 0 commits to and reveals the elements as given).
+ *
+ * Packed proof (mzk_fri_proof_layout gives num_rounds R and every section's byte offset and size; offsets are 8-byte aligned;
+ * T = num_colinearity_tests, m = n >> (R-1), L = R-1 layers, NL = limbs per element, d_r = log2(n >> r)):
+ *   MZK_FRI_STATUS         u64: 0, or 1 when sample_indices found no T distinct residues in 2^20 counters (the reference loops
+ *                          forever; mzk_fri_prove then returns MZK_E_RANGE)
+ *   MZK_FRI_TOP_INDICES    T x u64: top_level_indices
+ *   MZK_FRI_ROOTS          R x 32 bytes: merkle_roots
+ *   MZK_FRI_LAST_CODEWORD  m x NL u64: last_codeword (canonical)
+ *   MZK_FRI_VALUES         for layer i, for a, b, c: T x NL u64 -- revealed_layers[i].{a,b,c}.0 (magnitudes)
+ *   MZK_FRI_SIGNS          the same order, one byte per value: 1 = Sign::Minus (only round-0 values of a signed codeword)
+ *   MZK_FRI_PATHS          for layer i: T paths of d_i entries for a, T of d_i for b, T of d_(i+1) for c; MZK_FRI_PATH_STRIDE
+ *                          bytes per entry, zero-padded: entry 0 the sibling leaf's bytes, then 32-byte digests (Merkle::open)
+ *   MZK_FRI_PATH_LENS      one u64 per path entry: its length in bytes */
+enum { MZK_FRI_STATUS = 0, MZK_FRI_TOP_INDICES = 1, MZK_FRI_ROOTS = 2, MZK_FRI_LAST_CODEWORD = 3, MZK_FRI_VALUES = 4, MZK_FRI_SIGNS = 5,
+       MZK_FRI_PATHS = 6, MZK_FRI_PATH_LENS = 7, MZK_FRI_SECTIONS = 8, MZK_FRI_PATH_STRIDE = 48 };
+/* host only, no device work: offsets / sizes have MZK_FRI_SECTIONS entries (each may be NULL) */
+int mzk_fri_proof_layout(int field_id, size_t n, size_t expansion_factor, size_t num_colinearity_tests, int* num_rounds, uint64_t* offsets,
+                         uint64_t* sizes, uint64_t* total_bytes);
+/* host memory in and out; returns when proof_out is complete */
+int mzk_fri_prove(int field_id, const uint64_t* magnitudes, const uint8_t* negative, size_t n, const uint64_t* omega, const uint64_t* offset,
+                  size_t expansion_factor, size_t num_colinearity_tests, uint8_t* proof_out, size_t proof_cap);
+/* device memory in and out (d_negative: device flags or NULL); only enqueues on `stream`: read MZK_FRI_STATUS after synchronizing */
+int mzk_fri_prove_dev(int field_id, const void* d_magnitudes, const void* d_negative, size_t n, const uint64_t* omega, const uint64_t* offset,
+                      size_t expansion_factor, size_t num_colinearity_tests, void* d_proof, size_t proof_cap, void* stream);
+
 /* ---- G2 (BN254 twist over Fq2 = Fq[u]/(u^2+1); bn128.rs:33-49) ------------------------------------------------
  * A G2 point is 16 limbs: x.c0 | x.c1 | y.c0 | y.c1 (4 limbs each, canonical); all-zero = infinity.
  * mzk_msm_g2_bn254: Polynomial::eval_with_powers_on_curve over pk.powers_2 (polynomial.rs:156-165 as called from

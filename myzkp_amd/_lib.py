@@ -669,6 +669,85 @@ def fri_commit(fid, codeword, omega, offset, num_rounds, challenge, negative=Non
     return cws, rts
 
 
+FRI_SECTIONS = ("status", "top_indices", "roots", "last_codeword", "values", "signs", "paths", "path_lens")
+FRI_PATH_STRIDE = 48
+
+
+def fri_proof_layout(fid, n, expansion_factor, num_colinearity_tests):
+    """mzk_fri_proof_layout: (num_rounds, {section: (byte offset, byte size)}, total bytes) of the packed proof (host only)."""
+    rounds = ctypes.c_int()
+    off = (ctypes.c_uint64 * len(FRI_SECTIONS))()
+    size = (ctypes.c_uint64 * len(FRI_SECTIONS))()
+    total = ctypes.c_uint64()
+    _check(lib().mzk_fri_proof_layout(int(fid), ctypes.c_size_t(n), ctypes.c_size_t(expansion_factor), ctypes.c_size_t(num_colinearity_tests),
+                                      ctypes.byref(rounds), off, size, ctypes.byref(total)))
+    return rounds.value, {k: (off[i], size[i]) for i, k in enumerate(FRI_SECTIONS)}, total.value
+
+
+def fri_unpack_proof(fid, n, expansion_factor, num_colinearity_tests, raw):
+    """The packed proof of mzk_fri_prove as the reference's FriProof (fri.rs:71-82): top_level_indices, last_codeword ((m, limbs)
+    array), merkle_roots (bytes), revealed_layers ([{"a": (values, paths), "b": ..., "c": ...}]).  A value with Sign::Minus is the
+    negative int -magnitude.  Raises MzkError when the status word is set."""
+    raw = bytes(raw)
+    nl = LIMBS[fid]
+    R, sec, _ = fri_proof_layout(fid, n, expansion_factor, num_colinearity_tests)
+    T = num_colinearity_tests
+
+    def part(k):
+        o, s = sec[k]
+        return raw[o:o + s]
+    status = int.from_bytes(part("status"), "little")
+    if status != 0:
+        raise MzkError(-6, "fri_prove: sample_indices gave up (status %d)" % status)
+    top = [int(x) for x in np.frombuffer(part("top_indices"), dtype=np.uint64)]
+    roots = [part("roots")[32 * r:32 * r + 32] for r in range(R)]
+    last = np.frombuffer(part("last_codeword"), dtype=np.uint64).reshape(-1, nl).copy()
+    vals = from_limbs(np.frombuffer(part("values"), dtype=np.uint64).reshape(-1, nl)) if T else []
+    signs = part("signs")
+    paths, lens = part("paths"), np.frombuffer(part("path_lens"), dtype=np.uint64)
+    layers, q, e = [], 0, 0
+    for i in range(R - 1):
+        layer = {}
+        for kind in "abc":
+            d = (n >> (i + (kind == "c"))).bit_length() - 1
+            v, ps = [], []
+            for _ in range(T):
+                v.append(-vals[q] if signs[q] else vals[q])
+                ps.append([paths[(e + k) * FRI_PATH_STRIDE:(e + k) * FRI_PATH_STRIDE + int(lens[e + k])] for k in range(d)])
+                q += 1
+                e += d
+            layer[kind] = (v, ps)
+        layers.append(layer)
+    return {"top_level_indices": top, "last_codeword": last, "merkle_roots": roots, "revealed_layers": layers}
+
+
+def fri_prove(fid, codeword, omega, offset, expansion_factor, num_colinearity_tests, negative=None, device_ptr=None, n=None):
+    """FRI::prove (zkstark/fri.rs:99-143) in one call (mzk_fri_prove): the reference's transcript, index sampling and query phase on
+    the device.  Returns fri_unpack_proof's dict.  negative: Sign::Minus flags of the initial codeword, then given as magnitudes.
+    device_ptr / n: the codeword is already in HBM (mzk_fri_prove_dev on torch's current stream; negative then a device pointer or
+    None); `codeword` is ignored."""
+    _, _, total = fri_proof_layout(fid, n if device_ptr is not None else _arr(fid, codeword).shape[0], expansion_factor, num_colinearity_tests)
+    w, o = _one(fid, omega), _one(fid, offset)
+    if device_ptr is None:
+        c = _arr(fid, codeword)
+        n = c.shape[0]
+        ng = None if negative is None else np.ascontiguousarray(negative, dtype=np.uint8)
+        buf = (ctypes.c_uint8 * total)()
+        _check(lib().mzk_fri_prove(int(fid), _p(c), None if ng is None else _p(ng), ctypes.c_size_t(n), _p(w), _p(o), ctypes.c_size_t(expansion_factor),
+                                   ctypes.c_size_t(num_colinearity_tests), buf, ctypes.c_size_t(total)))
+        raw = bytes(buf)
+    else:
+        import torch
+        proof = torch.empty(total, dtype=torch.uint8, device="cuda")
+        stream = torch.cuda.current_stream()
+        _check(lib().mzk_fri_prove_dev(int(fid), ctypes.c_void_p(int(device_ptr)), None if negative is None else ctypes.c_void_p(int(negative)),
+                                       ctypes.c_size_t(n), _p(w), _p(o), ctypes.c_size_t(expansion_factor), ctypes.c_size_t(num_colinearity_tests),
+                                       ctypes.c_void_p(proof.data_ptr()), ctypes.c_size_t(total), ctypes.c_void_p(stream.cuda_stream)))
+        stream.synchronize()
+        raw = proof.cpu().numpy().tobytes()
+    return fri_unpack_proof(fid, n, expansion_factor, num_colinearity_tests, raw)
+
+
 def fast_coset_divide(fid, lhs, rhs, offset, root, root_order):
     """ntt::fast_coset_divide (algebra/ntt.rs:271-330)."""
     a, b = _arr(fid, lhs), _arr(fid, rhs)

@@ -1423,3 +1423,342 @@ int mzk_merkle_leaves(const mzk_merkle* t, const uint64_t* indices, size_t count
 }
 
 }  // extern "C"
+
+// ================================================================================================================================
+// FRI::prove (zkstark/fri.rs:99-143) in one enqueue: commit (:144-209) with the proof stream on the device, sample_indices
+// (:19-62) and reveal (:211-260).  Per round r the Merkle tree is hashed as in mzk_fri_commit; then k_fri_tx_round appends
+// vec![root_r] to the device transcript, rehashes the whole serialization with SHAKE256 and writes alpha_r; the fold reads it
+// from there.  After the last root k_fri_tx_last pushes the last codeword, squeezes the index seed and samples the top-level
+// indices; k_fri_query gathers every layer's values and paths into the packed proof.  No host round trip inside.
+#include "mzk_transcript.h"
+namespace mzk {
+
+// SHAKE256(msg[0 .. len))[0 .. 32) by the lane pair (lane & 1 = parity) of the calling lanes 0 / 1; out_w32[2 i + parity] = the
+// parity half of digest word i.  msg: 8-byte aligned, readable to the next multiple of 8.
+__device__ void fri_shake256_pair(const u8* msg, size_t len, int parity, u32* out_w32) {
+  u32 a[25];
+#pragma unroll
+  for (int i = 0; i < 25; i++) a[i] = 0;
+  const size_t blocks = mzk_tx::shake_blocks(len);
+  for (size_t b = 0; b < blocks; b++) {
+#pragma unroll
+    for (int w = 0; w < SHA3_RATE / 8; w++) {
+      const u64 v = mzk_tx::shake_word(msg, len, b, w);
+      a[w] ^= parity ? (u32)(v >> 32) : (u32)v;
+    }
+    keccak_f_pair(a, parity);
+  }
+#pragma unroll
+  for (int i = 0; i < 4; i++) out_w32[2 * i + parity] = a[i];
+}
+
+// Round r of the proof stream: push vec![root_r] (u64 1 | u64 32 | root), the object count becomes r + 1; unless this is the
+// last round, alpha_r = F::sample(SHAKE256(stream)[0 .. 32)) (fri.rs:168-176) into `alpha` (4 limbs, canonical: < 2^64).
+__global__ __launch_bounds__(64) void k_fri_tx_round(u64* __restrict__ tx, int r, const u64* __restrict__ root, u64* __restrict__ proof_root,
+                                                     u64* __restrict__ alpha, int squeeze) {
+  __shared__ u32 dig[8];
+  const int tid = threadIdx.x;
+  if (tid < 6) {
+    const u64 v = tid == 0 ? 1 : (tid == 1 ? 32 : root[tid - 2]);
+    tx[1 + 6 * (size_t)r + tid] = v;
+    if (tid >= 2) proof_root[tid - 2] = v;
+  }
+  if (tid == 0) tx[0] = (u64)r + 1;
+  __syncthreads();
+  if (!squeeze) return;
+  if (tid < 2) fri_shake256_pair(reinterpret_cast<const u8*>(tx), 8 + 48 * ((size_t)r + 1), tid, dig);
+  __syncthreads();
+  if (tid < 4) alpha[tid] = tid == 0 ? mzk_tx::sample_digest_word3(((u64)dig[7] << 32) | dig[6]) : 0;
+}
+
+// After the last root: push the last codeword (one object of m leaves, each u64 length + bincode(FiniteFieldElement)), squeeze the
+// seed (fri.rs:114-123), sample the top-level indices (fri.rs:40-62) and write status / indices / last codeword into the proof.
+// size = n / 2, reduced = m (powers of two: the reductions are masks).  One workgroup; `seen` holds m bits (global scratch).
+constexpr int TX_LAST_THREADS = 256;
+template <int NW>
+__global__ __launch_bounds__(TX_LAST_THREADS) void k_fri_tx_last(u8* __restrict__ tx, int rounds, const u32* __restrict__ cw, size_t m, size_t size,
+                                                                  size_t number, u32* __restrict__ seen, u64* __restrict__ p_status,
+                                                                  u64* __restrict__ p_top, u32* __restrict__ p_last) {
+  __shared__ u64 scan[TX_LAST_THREADS];
+  __shared__ u64 cand[TX_LAST_THREADS];
+  __shared__ u32 seed32[8];
+  __shared__ u64 s_count, s_done;
+  const int tid = threadIdx.x;
+  u64* tw = reinterpret_cast<u64*>(tx);
+  const size_t obj = 8 + 48 * (size_t)rounds;      // the object's u64 string count, then the strings
+  if (tid == 0) { tw[0] = (u64)rounds + 1; tw[obj / 8] = (u64)m; }
+  size_t at = obj + 8;
+  for (size_t base = 0; base < m; base += TX_LAST_THREADS) {
+    const size_t j = base + tid;
+    u32 w[NW];
+    int k = 0;
+    if (j < m) {
+#pragma unroll
+      for (int q = 0; q < NW; q++) { w[q] = cw[j * NW + q]; p_last[j * NW + q] = w[q]; if (w[q]) k = q + 1; }
+    }
+    const u64 rec = j < m ? 8 + 9 + 4 * (u64)k : 0;
+    scan[tid] = rec;
+    __syncthreads();
+    for (int d = 1; d < TX_LAST_THREADS; d <<= 1) {          // inclusive scan of the record lengths
+      const u64 add = tid >= d ? scan[tid - d] : 0;
+      __syncthreads();
+      scan[tid] += add;
+      __syncthreads();
+    }
+    if (j < m) {
+      u8* p = tx + at + scan[tid] - rec;
+      const u64 len = 9 + 4 * (u64)k;
+      for (int b = 0; b < 8; b++) p[b] = (u8)(len >> (8 * b));
+      p[8] = k ? 1 : 0;                                       // Sign::Plus / NoSign (the fold sanitized the codeword)
+      for (int b = 0; b < 8; b++) p[9 + b] = b == 0 ? (u8)k : 0;
+      for (int q = 0; q < k; q++)
+        for (int b = 0; b < 4; b++) p[17 + 4 * q + b] = (u8)(w[q] >> (8 * b));
+    }
+    at += scan[TX_LAST_THREADS - 1];
+    __syncthreads();
+  }
+  if (tid < 2) fri_shake256_pair(tx, at, tid, seed32);
+  for (size_t i = tid; i < (m + 31) / 32; i += TX_LAST_THREADS) seen[i] = 0;
+  if (tid == 0) { s_count = 0; s_done = 0; }
+  __syncthreads();
+  u64 seed[4];
+#pragma unroll
+  for (int i = 0; i < 4; i++) seed[i] = ((u64)seed32[2 * i + 1] << 32) | seed32[2 * i];
+  // counters in batches of 256, hashed side by side and accepted in counter order (the reference's loop, bounded)
+  for (u64 c0 = 0; c0 < mzk_tx::SAMPLE_COUNTER_LIMIT && !s_done; c0 += TX_LAST_THREADS) {
+    u64 h[4];
+    mzk_tx::blake2b256_seed_counter(seed, c0 + tid, h);
+    cand[tid] = mzk_tx::sample_digest_word3(h[3]) & (u64)(size - 1);
+    __syncthreads();
+    if (tid == 0) {
+      u64 cnt = s_count;
+      for (int t = 0; t < TX_LAST_THREADS && cnt < number; t++) {
+        const u64 idx = cand[t], red = idx & (u64)(m - 1);
+        const u32 bit = 1u << (red & 31);
+        if (!(seen[red >> 5] & bit)) {
+          seen[red >> 5] |= bit;
+          p_top[cnt++] = idx;
+        }
+      }
+      s_count = cnt;
+      s_done = cnt >= number;
+    }
+    __syncthreads();
+  }
+  if (tid == 0) {
+    for (u64 q = s_count; q < number; q++) p_top[q] = 0;
+    *p_status = s_count >= number ? 0 : 1;
+  }
+}
+
+// The query phase: block q = (layer i, kind a / b / c, test s).  a = top % (len_i / 2), b = a + len_i / 2 in round i's tree, c = a in
+// round i + 1's.  Writes the value (limbs and Sign::Minus flag) and the path exactly as mzk_merkle_open_batch returns it: entry 0 the
+// sibling leaf's bincode bytes, entries 1 .. depth-1 the digests; PATH_STRIDE bytes per entry, zero-padded, lengths beside.
+struct FriQueryArgs {
+  const u8* cw;          // all rounds' codewords back to back
+  const u8* nodes;       // all rounds' digests back to back
+  const u32* mag0;       // round 0's leaves as committed (the magnitudes, when signed; else the codeword itself)
+  const u8* neg0;        // round 0's Sign::Minus flags or null
+  const u64* top;
+  u8* values; u8* signs; u8* paths; u64* lens;
+  u64 n, tests;
+  u64 cw_off[64], node_off[64];     // byte offsets of round r's codeword / digests
+};
+template <int NW>
+__global__ __launch_bounds__(64) void k_fri_query(FriQueryArgs A) {
+  const u64 T = A.tests, q = blockIdx.x;
+  const int layer = (int)(q / (3 * T)), kind = (int)((q / T) % 3);
+  const u64 s = q % T;
+  const u64 half = (A.n >> layer) / 2;
+  const u64 a = A.top[s] & (half - 1);
+  const u64 idx = kind == 1 ? a + half : a;
+  const int rnd = layer + (kind == 2);
+  const u64 len = A.n >> rnd;
+  const int depth = mzk_tx::log2_pow2(len);
+  const u32* leaves = rnd == 0 ? A.mag0 : reinterpret_cast<const u32*>(A.cw + A.cw_off[rnd]);
+  const u8* neg = rnd == 0 ? A.neg0 : nullptr;
+  const u64* nodes = reinterpret_cast<const u64*>(A.nodes + A.node_off[rnd]);
+  const int tid = threadIdx.x;
+  if (tid < NW) reinterpret_cast<u32*>(A.values)[q * NW + tid] = leaves[idx * NW + tid];
+  if (tid == 0) A.signs[q] = neg ? neg[idx] : 0;
+  const u64 e0 = mzk_tx::fri_entry_base(A.n, T, layer, kind) + s * (u64)depth;
+  const int l = tid;
+  if (l >= 1 && l < depth) {
+    const u64 start = len - (len >> (l - 1));
+    const u64* src = nodes + 4 * (start + ((idx >> l) ^ 1));
+    u64* dst = reinterpret_cast<u64*>(A.paths + (e0 + l) * mzk_tx::PATH_STRIDE);
+#pragma unroll
+    for (int k = 0; k < 4; k++) dst[k] = src[k];
+    dst[4] = 0; dst[5] = 0;
+    A.lens[e0 + l] = 32;
+  }
+  if (tid == 0) {
+    const u64 sib = idx ^ 1;
+    u32 w[NW];
+    int k = 0;
+#pragma unroll
+    for (int j = 0; j < NW; j++) { w[j] = leaves[sib * NW + j]; if (w[j]) k = j + 1; }
+    u8 buf[mzk_tx::PATH_STRIDE];
+#pragma unroll
+    for (int b = 0; b < mzk_tx::PATH_STRIDE; b++) buf[b] = 0;
+    buf[0] = k ? ((neg && neg[sib]) ? 0xff : 1) : 0;
+    buf[1] = (u8)k;
+#pragma unroll
+    for (int j = 0; j < NW; j++)
+      if (j < k)
+        for (int b = 0; b < 4; b++) buf[9 + 4 * j + b] = (u8)(w[j] >> (8 * b));
+    u64* dst = reinterpret_cast<u64*>(A.paths + e0 * mzk_tx::PATH_STRIDE);
+#pragma unroll
+    for (int b = 0; b < mzk_tx::PATH_STRIDE / 8; b++) {
+      u64 v = 0;
+      for (int t = 0; t < 8; t++) v |= (u64)buf[8 * b + t] << (8 * t);
+      dst[b] = v;
+    }
+    A.lens[e0] = 9 + 4 * (u64)k;
+  }
+}
+
+// Validation shared by the three entry points; fills the layout.  Nothing is enqueued.
+static int fri_prove_check(int field_id, size_t n, size_t expansion_factor, size_t tests, mzk_tx::FriLayout* L) {
+  if (field_id != MZK_FIELD_FR && field_id != MZK_FIELD_M128) { set_error("fri_prove: bad field id %d", field_id); return MZK_E_ARG; }
+  if (n == 0) { set_error("fri_prove: empty codeword"); return MZK_E_LENGTH; }
+  if (!is_pow2(n)) { set_error("fri_prove: codeword length must be a power of two"); return MZK_E_NOT_POW2; }
+  mzk_tx::fri_layout(n, expansion_factor, tests, field_limbs64(field_id), L);
+  if (L->rounds < 2) {
+    set_error("fri_prove: num_rounds = %d for domain length %zu, expansion factor %zu, %zu colinearity tests; FRI::prove reads codewords[1] (fri.rs:117-121)",
+              L->rounds, n, expansion_factor, tests);
+    return MZK_E_LENGTH;
+  }
+  if (tests > L->last_len) {
+    set_error("cannot sample more indices than available in last codeword; requested: %zu, available: %llu", tests, (unsigned long long)L->last_len);
+    return MZK_E_ARG;
+  }
+  if (L->rounds > 63) { set_error("fri_prove: too many rounds"); return MZK_E_LENGTH; }
+  return MZK_OK;
+}
+
+static int fri_prove_impl(int field_id, const void* src, const void* negative, bool on_device, size_t n, const uint64_t* omega, const uint64_t* offset,
+                          size_t expansion_factor, size_t tests, void* proof_out, size_t proof_cap, hipStream_t s_in) {
+  mzk_tx::FriLayout L;
+  MZK_TRY(fri_prove_check(field_id, n, expansion_factor, tests, &L));
+  if (!src || !omega || !offset || !proof_out) { set_error("fri_prove: null pointer"); return MZK_E_ARG; }
+  if (proof_cap < L.total) { set_error("fri_prove: proof buffer of %zu bytes, the layout needs %llu", proof_cap, (unsigned long long)L.total); return MZK_E_LENGTH; }
+  const HostField* hf = host_field(field_id);
+  if (!h_is_canonical(hf, omega) || !h_is_canonical(hf, offset)) { set_error("fri_prove: parameter not canonical"); return MZK_E_RANGE; }
+  MZK_ENTER();
+  hipStream_t s = on_device ? s_in : ctx().stream;
+  WsGuard wsg(s);
+  const int R = L.rounds, nl = hf->nl;
+  const size_t esz = field_bytes(field_id);
+  auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
+  // one workspace block: codewords of all rounds | digests of all rounds | round-0 magnitudes and signs | transcript | alphas | seen
+  // bits | the proof (host form).  Every tree lives here until the query kernel is done.
+  size_t cw_total = 0, node_total = 0;
+  uint64_t cw_off[64], node_off[64];
+  for (int r = 0; r < R; r++) { cw_off[r] = cw_total; node_off[r] = node_total; cw_total += (n >> r) * esz; node_total += ((n >> r) - 1) * 32; }
+  const size_t o_nodes = al(cw_total), o_mag = o_nodes + al(node_total), o_neg = o_mag + (negative ? al(n * esz) : 0);
+  const size_t o_tx = o_neg + (negative && !on_device ? al(n) : 0);
+  const size_t o_alpha = o_tx + al(mzk_tx::fri_transcript_cap(L, nl) + 16), o_seen = o_alpha + al(32 * (size_t)R);
+  const size_t o_proof = o_seen + al((L.last_len + 31) / 32 * 4), total = o_proof + (on_device ? 0 : al(L.total));
+  uint8_t* blk;
+  MZK_TRY(ws_get(WS_MISC_F, total, (void**)&blk));
+  uint8_t* cw = blk;
+  uint8_t* nodes = blk + o_nodes;
+  uint8_t* proof = on_device ? (uint8_t*)proof_out : blk + o_proof;
+  u64* tx = (u64*)(blk + o_tx);
+  u64* alphas = (u64*)(blk + o_alpha);
+  const hipMemcpyKind kind = on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
+  MZK_HIP(hipMemcpyAsync(cw, src, n * esz, kind, s));
+  const u8* d_neg = nullptr;
+  const u32* mag0 = (const u32*)cw;
+  if (negative) {      // round 0 commits to the magnitudes with their signs (fri.rs:160-166); the fold reads the canonical values
+    MZK_HIP(hipMemcpyAsync(blk + o_mag, src, n * esz, kind, s));
+    mag0 = (const u32*)(blk + o_mag);
+    if (on_device) d_neg = (const u8*)negative;
+    else {
+      MZK_HIP(hipMemcpyAsync(blk + o_neg, negative, n, hipMemcpyHostToDevice, s));
+      d_neg = blk + o_neg;
+    }
+  }
+  uint64_t om[4] = {0, 0, 0, 0}, of[4] = {0, 0, 0, 0};
+  memcpy(om, omega, 8 * nl);
+  memcpy(of, offset, 8 * nl);
+  FriFoldConsts fc;
+  MZK_TRY(fri_fold_consts(field_id, of, om, &fc));
+  const mzk_tx::FriLayout& P = L;
+  for (int r = 0; r < R; r++) {
+    const size_t len = n >> r;
+    const void* leaves = r == 0 ? (const void*)mag0 : (const void*)(cw + cw_off[r]);
+    u64* nd = (u64*)(nodes + node_off[r]);
+    MZK_TRY(merkle_hash_levels(0, field_id, leaves, nullptr, len, nd, s, r == 0 ? d_neg : nullptr));
+    const bool last = r == R - 1;
+    hipLaunchKernelGGL(k_fri_tx_round, dim3(1), dim3(64), 0, s, tx, r, (const u64*)(nd + 4 * (len - 2)), (u64*)(proof + P.off[mzk_tx::SEC_ROOTS] + 32 * (size_t)r),
+                       alphas + 4 * r, last ? 0 : 1);
+    MZK_HIP(hipGetLastError());
+    if (r == 0 && negative) {
+      if (field_id == MZK_FIELD_M128) hipLaunchKernelGGL((k_canonicalize_signed<4>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, (u32*)cw, d_neg, n, field_id);
+      else hipLaunchKernelGGL((k_canonicalize_signed<8>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, (u32*)cw, d_neg, n, field_id);
+      MZK_HIP(hipGetLastError());
+    }
+    if (last) break;
+    MZK_TRY(fri_fold_dev_alpha(field_id, cw + cw_off[r], len, alphas + 4 * r, fc, cw + cw_off[r + 1], s));
+    fri_fold_consts_square(field_id, &fc);
+  }
+  const u32* last_cw = (const u32*)(cw + cw_off[R - 1]);
+  auto sec = [&](int k) { return proof + P.off[k]; };
+  if (field_id == MZK_FIELD_M128)
+    hipLaunchKernelGGL((k_fri_tx_last<4>), dim3(1), dim3(TX_LAST_THREADS), 0, s, (u8*)tx, R, last_cw, (size_t)L.last_len, n / 2, tests,
+                       (u32*)(blk + o_seen), (u64*)sec(mzk_tx::SEC_STATUS), (u64*)sec(mzk_tx::SEC_TOP_INDICES), (u32*)sec(mzk_tx::SEC_LAST_CODEWORD));
+  else
+    hipLaunchKernelGGL((k_fri_tx_last<8>), dim3(1), dim3(TX_LAST_THREADS), 0, s, (u8*)tx, R, last_cw, (size_t)L.last_len, n / 2, tests,
+                       (u32*)(blk + o_seen), (u64*)sec(mzk_tx::SEC_STATUS), (u64*)sec(mzk_tx::SEC_TOP_INDICES), (u32*)sec(mzk_tx::SEC_LAST_CODEWORD));
+  MZK_HIP(hipGetLastError());
+  const size_t queries = 3 * tests * (size_t)(R - 1);
+  if (queries) {
+    FriQueryArgs A;
+    A.cw = cw; A.nodes = nodes; A.mag0 = mag0; A.neg0 = d_neg; A.top = (const u64*)sec(mzk_tx::SEC_TOP_INDICES);
+    A.values = sec(mzk_tx::SEC_VALUES); A.signs = sec(mzk_tx::SEC_SIGNS); A.paths = sec(mzk_tx::SEC_PATHS); A.lens = (u64*)sec(mzk_tx::SEC_PATH_LENS);
+    A.n = n; A.tests = tests;
+    for (int r = 0; r < 64; r++) { A.cw_off[r] = r < R ? cw_off[r] : 0; A.node_off[r] = r < R ? node_off[r] : 0; }
+    if (field_id == MZK_FIELD_M128) hipLaunchKernelGGL((k_fri_query<4>), dim3((unsigned)queries), dim3(64), 0, s, A);
+    else hipLaunchKernelGGL((k_fri_query<8>), dim3((unsigned)queries), dim3(64), 0, s, A);
+    MZK_HIP(hipGetLastError());
+  }
+  if (on_device) return MZK_OK;
+  MZK_TRY(d2h_sync(proof_out, proof, L.total, s));
+  uint64_t status;
+  memcpy(&status, proof_out, 8);
+  if (status != 0) {
+    set_error("fri_prove: sample_indices found %zu distinct reduced indices in %llu counters", tests, (unsigned long long)mzk_tx::SAMPLE_COUNTER_LIMIT);
+    return MZK_E_RANGE;
+  }
+  return MZK_OK;
+}
+
+}  // namespace mzk
+
+extern "C" {
+
+int mzk_fri_proof_layout(int field_id, size_t n, size_t expansion_factor, size_t num_colinearity_tests, int* num_rounds, uint64_t* offsets,
+                         uint64_t* sizes, uint64_t* total_bytes) {
+  mzk_tx::FriLayout L;
+  MZK_TRY(fri_prove_check(field_id, n, expansion_factor, num_colinearity_tests, &L));
+  if (num_rounds) *num_rounds = L.rounds;
+  for (int k = 0; k < mzk_tx::SEC_COUNT; k++) {
+    if (offsets) offsets[k] = L.off[k];
+    if (sizes) sizes[k] = L.size[k];
+  }
+  if (total_bytes) *total_bytes = L.total;
+  return MZK_OK;
+}
+int mzk_fri_prove(int field_id, const uint64_t* magnitudes, const uint8_t* negative, size_t n, const uint64_t* omega, const uint64_t* offset,
+                  size_t expansion_factor, size_t num_colinearity_tests, uint8_t* proof_out, size_t proof_cap) {
+  return fri_prove_impl(field_id, magnitudes, negative, false, n, omega, offset, expansion_factor, num_colinearity_tests, proof_out, proof_cap, nullptr);
+}
+int mzk_fri_prove_dev(int field_id, const void* d_magnitudes, const void* d_negative, size_t n, const uint64_t* omega, const uint64_t* offset,
+                      size_t expansion_factor, size_t num_colinearity_tests, void* d_proof, size_t proof_cap, void* stream) {
+  return fri_prove_impl(field_id, d_magnitudes, d_negative, true, n, omega, offset, expansion_factor, num_colinearity_tests, d_proof, proof_cap,
+                        (hipStream_t)stream);
+}
+
+}  // extern "C"

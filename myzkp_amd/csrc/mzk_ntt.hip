@@ -1383,6 +1383,46 @@ int fri_fold_dev_consts(int fid, const void* d_cw, size_t n, const uint64_t* alp
   MZK_HIP(hipGetLastError());
   return MZK_OK;
 }
+// The same fold with alpha in device memory (mzk_fri_prove: the transcript kernel of the round wrote it there; alpha < 2^64, canonical
+// limbs).  k_mont = 2^-1 offset^-1 R^2: one product with the plain alpha gives r_0 in Montgomery form, as the host forms it above.
+template <class P>
+__global__ void k_fri_fold_dev_alpha(const u32* __restrict__ cw, size_t h, const u32* __restrict__ alpha, Words8 k_mont, Words8 winv_mont,
+                                     Words8 half_mont, u32* __restrict__ out, int per_lane) {
+  const size_t chunk = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const size_t i0 = chunk * (size_t)per_lane;
+  if (i0 >= h) return;
+  const Fe<P> winv = fe_unpack<P>(winv_mont.w), half = fe_unpack<P>(half_mont.w);
+  const Fe<P> r0 = FeAsm<P>::mul(gload<P>(alpha, 0), fe_unpack<P>(k_mont.w));
+  Fe<P> r = FeAsm<P>::mul(r0, fe_pow_u64<P>(winv, i0));
+  for (int t = 0; t < per_lane && i0 + t < h; t++) {
+    const Fe<P> a = gload<P>(cw, i0 + t), b = gload<P>(cw, h + i0 + t);
+    const Fe<P> sum = fe_add<P>(a, b);
+    const Fe<P> dif = fe_carry<P>(fe_sub<P, 4>(a, b));
+    const Fe<P> o = fe_add<P>(FeAsm<P>::mul(sum, half), FeAsm<P>::mul(dif, r));
+    gstore<P>(out, i0 + t, fe_reduce<P>(o));
+    r = FeAsm<P>::mul(r, winv);
+  }
+}
+int fri_fold_dev_alpha(int fid, const void* d_cw, size_t n, const uint64_t* d_alpha, const FriFoldConsts& fc, void* d_out, hipStream_t s) {
+  const size_t h = n / 2;
+  if (h == 0) return MZK_OK;
+  const HostField* hf = host_field(fid);
+  uint64_t kv[4], winv[4], halfv[4];
+  h_mulmod(hf, kv, fc.half, fc.oinv);
+  h_mulmod(hf, kv, kv, fc.rmod); h_mulmod(hf, kv, kv, fc.rmod);
+  h_mulmod(hf, winv, fc.winv, fc.rmod); h_mulmod(hf, halfv, fc.half, fc.rmod);
+  Words8 kw, winvw, halfw;
+  to_words(kv, hf->nl, &kw); to_words(winv, hf->nl, &winvw); to_words(halfv, hf->nl, &halfw);
+  const int per_lane = h >= ((size_t)1 << 20) ? GEN_CHUNK : (h >= ((size_t)1 << 16) ? 4 : 1);
+  const size_t chunks = (h + (size_t)per_lane - 1) / (size_t)per_lane;
+  const unsigned blocks = (unsigned)((chunks + 127) / 128);
+  if (fid == MZK_FIELD_M128)
+    hipLaunchKernelGGL((k_fri_fold_dev_alpha<M128Params>), dim3(blocks), dim3(128), 0, s, (const u32*)d_cw, h, (const u32*)d_alpha, kw, winvw, halfw, (u32*)d_out, per_lane);
+  else
+    hipLaunchKernelGGL((k_fri_fold_dev_alpha<FrParams>), dim3(blocks), dim3(128), 0, s, (const u32*)d_cw, h, (const u32*)d_alpha, kw, winvw, halfw, (u32*)d_out, per_lane);
+  MZK_HIP(hipGetLastError());
+  return MZK_OK;
+}
 int fri_fold_dev_impl(int fid, const void* d_cw, size_t n, const uint64_t* alpha, const uint64_t* offset, const uint64_t* omega,
                       void* d_out, hipStream_t s) {
   if (fid != MZK_FIELD_FR && fid != MZK_FIELD_M128) { set_error("fri_fold: bad field id %d", fid); return MZK_E_ARG; }

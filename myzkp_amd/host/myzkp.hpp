@@ -18,6 +18,7 @@
 //   accumulate_curve_points (G1 and G2)     zksnark/utils.rs:83-92
 //   Merkle::commit / open, commit_codeword   algebra/merkle.rs:15-46, zkstark/fri.rs:160-166
 //   fri_split_and_fold, fri_commit           zkstark/fri.rs:144-209
+//   FriProof, fri_prove                      zkstark/fri.rs:71-143      -> mzk_fri_prove
 //
 // Values are held canonical (u64 limbs) -- the ABI wire format; arithmetic on single elements that the
 // reference does on the host (a handful of scalar ops in tests) is not offered here: this header only
@@ -29,6 +30,7 @@
 #include <stdexcept>
 #include <string>
 #include <type_traits>
+#include <utility>
 #include <vector>
 #include <exception>
 #include "../../include/mzk.h"
@@ -415,6 +417,59 @@ FriCommitment<F> fri_commit(const std::vector<F>& initial_codeword, const F& ome
     at += n >> r;
   }
   return out;
+}
+// FRI::prove (fri.rs:99-143) in one call (mzk_fri_prove): commit, the proof stream (started empty, as FRI::prove starts it),
+// sample_indices and reveal on the device.  FriProof / FriQueryLayer as fri.rs:71-82; the codeword's elements are canonical here.
+template <class F> struct FriQueryLayer {
+  std::pair<std::vector<F>, std::vector<MerklePath>> a, b, c;
+};
+template <class F> struct FriProof {
+  std::vector<size_t> top_level_indices;
+  std::vector<F> last_codeword;
+  std::vector<MerkleRoot> merkle_roots;
+  std::vector<FriQueryLayer<F>> revealed_layers;
+};
+template <class F>
+FriProof<F> fri_prove(const std::vector<F>& initial_codeword, const F& omega, const F& offset, size_t expansion_factor, size_t num_colinearity_tests) {
+  const int fid = Polynomial<F>::field_id();
+  const size_t n = initial_codeword.size(), nl = F().value.size(), T = num_colinearity_tests;
+  int rounds = 0;
+  uint64_t off[MZK_FRI_SECTIONS], size[MZK_FRI_SECTIONS], total = 0;
+  expect(mzk_fri_proof_layout(fid, n, expansion_factor, T, &rounds, off, size, &total));
+  std::vector<uint8_t> buf(total);
+  auto c = to_wire(initial_codeword);
+  expect(mzk_fri_prove(fid, c.data(), nullptr, n, omega.value.data(), offset.value.data(), expansion_factor, T, buf.data(), buf.size()));
+  auto u64_at = [&](uint64_t byte) { uint64_t v; std::memcpy(&v, buf.data() + byte, 8); return v; };
+  auto elems = [&](uint64_t byte, size_t count) {
+    std::vector<uint64_t> w(count * nl);
+    if (count) std::memcpy(w.data(), buf.data() + byte, 8 * w.size());
+    return from_wire<F>(w, count);
+  };
+  FriProof<F> p;
+  for (size_t s = 0; s < T; s++) p.top_level_indices.push_back((size_t)u64_at(off[MZK_FRI_TOP_INDICES] + 8 * s));
+  for (int r = 0; r < rounds; r++) p.merkle_roots.emplace_back(buf.begin() + off[MZK_FRI_ROOTS] + 32 * r, buf.begin() + off[MZK_FRI_ROOTS] + 32 * r + 32);
+  p.last_codeword = elems(off[MZK_FRI_LAST_CODEWORD], n >> (rounds - 1));
+  size_t q = 0, e = 0;
+  for (int i = 0; i + 1 < rounds; i++) {
+    FriQueryLayer<F> L;
+    std::pair<std::vector<F>, std::vector<MerklePath>>* parts[3] = {&L.a, &L.b, &L.c};
+    for (int k = 0; k < 3; k++) {
+      size_t depth = 0;
+      while (((size_t)1 << depth) < (n >> (i + (k == 2)))) depth++;
+      parts[k]->first = elems(off[MZK_FRI_VALUES] + 8 * nl * q, T);
+      for (size_t s = 0; s < T; s++, e += depth) {
+        MerklePath path;
+        for (size_t l = 0; l < depth; l++) {
+          const uint64_t at = off[MZK_FRI_PATHS] + (uint64_t)MZK_FRI_PATH_STRIDE * (e + l);
+          path.emplace_back(buf.begin() + at, buf.begin() + at + u64_at(off[MZK_FRI_PATH_LENS] + 8 * (e + l)));
+        }
+        parts[k]->second.push_back(std::move(path));
+      }
+      q += T;
+    }
+    p.revealed_layers.push_back(std::move(L));
+  }
+  return p;
 }
 
 // ---- extensions: the reference's per-item loops as one call ------------------------------------------------------
