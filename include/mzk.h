@@ -494,6 +494,51 @@ int mzk_kzg_open_quotient_dev(const void* d_coef, size_t n, const uint64_t u_hos
 int mzk_kzg_open_slice_value_dev(const void* d_coef_slice, size_t len, const uint64_t u_host[4], void* d_value, void* stream);
 int mzk_kzg_open_slice_quotient_dev(const void* d_coef_slice, size_t len, const uint64_t u_host[4], const uint64_t carry_in[4], void* d_q_slice,
                                     void* stream);
+/* ---- Gemini multilinear commitments and the sum-check prover (algebra/gemini.rs, algebra/sumcheck.rs) ------------------
+ * A multilinear g over el variables is given by its n = 2^el coefficients in the order of get_coefs_in_order
+ * (sumcheck.rs:97-108): bit i of the index t is the exponent of variable i.  Every value is Fr, standard form, canonical.
+ *
+ * split_and_fold (gemini.rs:51-100): out = the el + 1 levels f_0 = coef, f_{i+1}[k] = f_i[2k] + rhos[i] f_i[2k+1], back to back
+ * (2n - 1 elements; level i starts at 2n - 2n/2^i and holds n/2^i elements; level el is mu).  n not a power of two (0 included):
+ * MZK_E_NOT_POW2 (CoefsNotPowerOfTwo); n_rhos != el: MZK_E_LENGTH (PointsLenMismatch); a rho not canonical: MZK_E_RANGE.
+ * n <= 2^30.  The _dev form enqueues on `stream`; d_out may equal d_coef (level 0 is then already in place). */
+int mzk_gemini_split_fold(const uint64_t* coef, size_t n, const uint64_t* rhos, size_t n_rhos, uint64_t* out);
+int mzk_gemini_split_fold_dev(const void* d_coef, size_t n, const uint64_t* rhos, size_t n_rhos, void* d_out, void* stream);
+/* commit_gemini (gemini.rs:112-114) of the packed levels of split_fold: out_xy = el + 1 affine points, commit_kzg of each level.
+ * n > SRS length: MZK_E_LENGTH (the index panic of eval_with_powers_on_curve). */
+int mzk_gemini_commit_srs(const mzk_srs* srs, const uint64_t* levels, size_t n, uint64_t* out_xy);
+int mzk_gemini_commit_srs_dev(const mzk_srs* srs, const void* d_levels, size_t n, void* d_out_xy, void* stream);
+/* open_gemini (gemini.rs:116-144) of the packed levels at beta:
+ *   i < el:  batch_open_kzg(f_i, [beta, -beta, beta^2]) -- ys[12 i .. 12 i + 12) = f_i(beta), f_i(-beta), f_i(beta^2) (-beta =
+ *            (0 - beta).sanitize()), ws_xy[8 i ..] = MSM of the quotient by (X - beta)(X + beta)(X - beta^2) (level el - 1 has two
+ *            coefficients: empty quotient, w = infinity);
+ *   i <= el: deg_xy[8 i ..] = prove_degree_bound(f_i, pk, 2^(el - i)) = MSM(f_i, powers[max_d - 2^(el-i), max_d)), max_d = SRS length - 1.
+ * Every value and point is bit-identical to the reference's.  The SRS must hold n + 1 powers (max_d < n: the reference's usize
+ * underflow, MZK_E_LENGTH).  beta not canonical: MZK_E_RANGE; beta in {0, 1, -1} (the three points are not distinct and the
+ * reference's interpolation divides by zero): MZK_E_ARG.  ys / ws_xy may be NULL when n == 1. */
+int mzk_gemini_open_srs(const mzk_srs* srs, const uint64_t* levels, size_t n, const uint64_t beta[4], uint64_t* ys, uint64_t* ws_xy, uint64_t* deg_xy);
+int mzk_gemini_open_srs_dev(const mzk_srs* srs, const void* d_levels, size_t n, const uint64_t beta[4], void* d_ys, void* d_ws_xy, void* d_deg_xy,
+                            void* stream);
+/* sum_over_boolean_hypercube (sumcheck.rs:57-66) of a multilinear g: h = sum_t coef[t] 2^(el - popcount(t)). */
+int mzk_sumcheck_sum(const uint64_t* coef, size_t n, uint64_t h[4]);
+/* prove_sumcheck (sumcheck.rs:128-167) for a multilinear g.  Round j < el: the device computes g_j(X) = A_j + B_j X of
+ * build_gj_from_prefix(g, r_0..r_{j-1}) from the current fold level f_j (m = el - 1 - j):
+ *   A_j = sum over even t of f_j[t] 2^(m - popcount(t >> 1)),   B_j = the same over odd t,
+ * writes them to gs[8 j .. 8 j + 8) (A_j then B_j), and calls challenge(user, j, g = gs + 8 j, r_out) for r_j (canonical;
+ * MZK_E_RANGE otherwise), which it folds into f_{j+1} in the same pass that sums g_{j+1}.  Then challenge(user, el, NULL, r_out)
+ * returns beta, and the kept fold levels (they are split_and_fold(coefs, rs)) are committed and opened exactly as
+ * mzk_gemini_commit_srs (commits_xy: el + 1 points) and mzk_gemini_open_srs (ys, ws_xy, deg_xy) do.  rs: el values out.
+ * Why a callback: the reference's transcript pushes bincode(MPolynomial g_j), a HashMap whose iteration order is random per
+ * process, so those bytes cannot be reproduced on any device.  The caller owns the FiatShamirTransformer, builds g_j from
+ * (A_j, B_j) (the constant term A_j, X_j's coefficient B_j), pushes it and samples r_j.  The reference samples beta from the
+ * unchanged stream right after r_{el-1} (no push in between), so a faithful shim returns beta == r_{el-1}.
+ * A non-zero return of the callback stops the prover with MZK_E_CALLBACK.  The callback must not call into this library (the
+ * fold levels live in the context's workspace).  el = 0: MZK_E_LENGTH (the assert of build_gj_from_prefix); SRS shorter than
+ * n + 1: MZK_E_LENGTH.  Every error returns with nothing left enqueued. */
+typedef int (*mzk_sumcheck_challenge_fn)(void* user, int round, const uint64_t g[8], uint64_t r_out[4]);
+int mzk_sumcheck_prove_srs(const mzk_srs* srs, const uint64_t* coef, size_t n, mzk_sumcheck_challenge_fn challenge, void* user, uint64_t* gs,
+                           uint64_t* rs, uint64_t beta[4], uint64_t* commits_xy, uint64_t* ys, uint64_t* ws_xy, uint64_t* deg_xy);
+
 /* Build an SRS handle from points already in HBM (affine canonical, n * 8 limbs).  The _ex form chooses
  * whether the window tables are built (worth it from ~30 commits per SRS on at 2^20 points; a one-shot pipeline keeps
  * the plain prepared points and pays the window Horner instead).  Default widths by size: 8 bits up to 1024 points,

@@ -433,6 +433,20 @@ class Srs:
         torch.cuda.synchronize()
         return array_to_points(d_o.cpu().numpy().view(np.uint64).reshape(count, 8))
 
+    def gemini_commit(self, levels):
+        """commit_gemini (algebra/gemini.rs:112-114) of the fold levels (gemini_split_fold's list, or the packed 2n - 1 rows)."""
+        return _gemini_commit(self._h, levels)
+
+    def gemini_open(self, levels, beta):
+        """open_gemini (algebra/gemini.rs:116-144) -> (ys, ws, deg): ys[i] = (f_i(beta), f_i(-beta), f_i(beta^2)) and ws[i] for
+        i < el, deg[i] = prove_degree_bound(f_i, pk, 2^(el - i)) for i <= el."""
+        return _gemini_open(self._h, levels, beta)
+
+    def sumcheck_prove(self, coef, challenge):
+        """prove_sumcheck (algebra/sumcheck.rs:128-167) of a multilinear g.  challenge(round, g) -> int, with g = (A_j, B_j) of
+        g_j(X) = A_j + B_j X for round j < el and None for round el (beta).  Returns a dict: gs, rs, beta, commits, ys, ws, deg."""
+        return _sumcheck_prove(self._h, coef, challenge)
+
     def build_direct(self, window_bits=0, max_bytes=0):
         """Direct tables for batches of short polynomials (mzk_srs_build_direct); returns the width built."""
         _check(lib().mzk_srs_build_direct(self._h, int(window_bits), ctypes.c_size_t(max_bytes), None))
@@ -582,6 +596,113 @@ def merkle_commit_field(fid, elems):
     _check(lib().mzk_merkle_commit_field(fid, _p(e), ctypes.c_size_t(e.shape[0]), buf, ctypes.c_size_t(48), ctypes.byref(ln)))
     return bytes(buf[:ln.value])
 
+
+# ---- Gemini / sum-check (algebra/gemini.rs, algebra/sumcheck.rs) ----------------------------------------------------
+def _levels_split(packed, n):
+    out, at = [], 0
+    while n >= 1:
+        out.append(packed[at:at + n].copy())
+        at += n
+        n //= 2
+    return out
+
+
+def _levels_packed(levels):
+    """a list of fold levels (as gemini_split_fold returns) or the packed (2n - 1, 4) array -> (packed array, n)"""
+    if isinstance(levels, (list, tuple)):
+        arr = np.ascontiguousarray(np.concatenate([np.asarray(l, dtype=np.uint64).reshape(-1, 4) for l in levels]), dtype=np.uint64)
+        return arr, np.asarray(levels[0]).reshape(-1, 4).shape[0]
+    arr = np.ascontiguousarray(levels, dtype=np.uint64).reshape(-1, 4)
+    return arr, (arr.shape[0] + 1) // 2
+
+
+def gemini_split_fold(coef, rhos):
+    """split_and_fold (algebra/gemini.rs:51-100): the el + 1 fold levels f_0 = coef .. f_el = [mu], as (len, 4) limb arrays."""
+    c = np.ascontiguousarray(coef, dtype=np.uint64).reshape(-1, 4)
+    n = c.shape[0]
+    r = to_limbs(list(rhos), 4) if len(rhos) else np.zeros((1, 4), dtype=np.uint64)
+    out = np.zeros((max(2 * n - 1, 1), 4), dtype=np.uint64)
+    _check(lib().mzk_gemini_split_fold(_p(c) if n else None, ctypes.c_size_t(n), _p(r), ctypes.c_size_t(len(rhos)), _p(out)))
+    return _levels_split(out, n)
+
+
+def gemini_split_fold_dev(d_coef, n, rhos, d_out, stream=None):
+    """mzk_gemini_split_fold_dev: device pointers (ints), the 2n - 1 packed levels written at d_out; only enqueues."""
+    r = to_limbs(list(rhos), 4) if len(rhos) else np.zeros((1, 4), dtype=np.uint64)
+    _check(lib().mzk_gemini_split_fold_dev(ctypes.c_void_p(int(d_coef)), ctypes.c_size_t(n), _p(r), ctypes.c_size_t(len(rhos)),
+                                           ctypes.c_void_p(int(d_out)), ctypes.c_void_p(stream)))
+
+
+def sumcheck_sum(coef):
+    """sum_over_boolean_hypercube (algebra/sumcheck.rs:57-66) of the multilinear g with these coefficients (get_coefs_in_order)."""
+    c = np.ascontiguousarray(coef, dtype=np.uint64).reshape(-1, 4)
+    h = np.zeros((1, 4), dtype=np.uint64)
+    _check(lib().mzk_sumcheck_sum(_p(c) if c.shape[0] else None, ctypes.c_size_t(c.shape[0]), _p(h)))
+    return from_limbs(h)[0]
+
+
+_SUMCHECK_CB = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64))
+
+
+def _gemini_commit(h, levels):
+    arr, n = _levels_packed(levels)
+    el = max(n.bit_length() - 1, 0)
+    out = np.zeros((el + 1, 8), dtype=np.uint64)
+    _check(lib().mzk_gemini_commit_srs(h, _p(arr), ctypes.c_size_t(n), _p(out)))
+    return array_to_points(out)
+
+
+def _gemini_open(h, levels, beta):
+    arr, n = _levels_packed(levels)
+    el = max(n.bit_length() - 1, 0)
+    ys = np.zeros((max(3 * el, 1), 4), dtype=np.uint64)
+    ws = np.zeros((max(el, 1), 8), dtype=np.uint64)
+    deg = np.zeros((el + 1, 8), dtype=np.uint64)
+    b = to_limbs([beta], 4)
+    _check(lib().mzk_gemini_open_srs(h, _p(arr), ctypes.c_size_t(n), _p(b), _p(ys), _p(ws), _p(deg)))
+    y = from_limbs(ys[:3 * el]) if el else []
+    return [tuple(y[3 * i:3 * i + 3]) for i in range(el)], (array_to_points(ws[:el]) if el else []), array_to_points(deg)
+
+
+def _sumcheck_prove(h, coef, challenge):
+    c = np.ascontiguousarray(coef, dtype=np.uint64).reshape(-1, 4)
+    n = c.shape[0]
+    el = max(n.bit_length() - 1, 0)
+    failure = []
+
+    def cb(user, rnd, g, r_out):
+        # An exception must not escape into C: keep it, stop the prover (non-zero status -> MZK_E_CALLBACK), re-raise below.
+        try:
+            gg = None
+            if g:
+                v = [int(g[k]) for k in range(8)]
+                gg = (sum(v[k] << (64 * k) for k in range(4)), sum(v[4 + k] << (64 * k) for k in range(4)))
+            r = challenge(rnd, gg)
+            if r is None:
+                raise ValueError("challenge(%d) returned no value" % rnd)
+            r = int(r)
+            for j in range(4):
+                r_out[j] = (r >> (64 * j)) & 0xFFFFFFFFFFFFFFFF
+            return 0
+        except BaseException as ex:      # noqa: BLE001 -- re-raised by sumcheck_prove
+            failure.append(ex)
+            return 1
+
+    k = max(el, 1)
+    gs, rs = np.zeros((k, 8), dtype=np.uint64), np.zeros((k, 4), dtype=np.uint64)
+    beta = np.zeros((1, 4), dtype=np.uint64)
+    commits, deg = np.zeros((el + 1, 8), dtype=np.uint64), np.zeros((el + 1, 8), dtype=np.uint64)
+    ys, ws = np.zeros((3 * k, 4), dtype=np.uint64), np.zeros((k, 8), dtype=np.uint64)
+    fn = _SUMCHECK_CB(cb)
+    rc = lib().mzk_sumcheck_prove_srs(h, _p(c) if n else None, ctypes.c_size_t(n), fn, None, _p(gs), _p(rs), _p(beta), _p(commits), _p(ys), _p(ws),
+                                      _p(deg))
+    if failure:
+        raise failure[0]
+    _check(rc)
+    y = from_limbs(ys[:3 * el])
+    return {"gs": list(zip(from_limbs(gs[:el, :4]), from_limbs(gs[:el, 4:]))), "rs": from_limbs(rs[:el]), "beta": from_limbs(beta)[0],
+            "commits": array_to_points(commits), "ys": [tuple(y[3 * i:3 * i + 3]) for i in range(el)], "ws": array_to_points(ws[:el]),
+            "deg": array_to_points(deg)}
 
 _FRI_CB = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_uint8), ctypes.c_size_t,
                            ctypes.POINTER(ctypes.c_uint64))

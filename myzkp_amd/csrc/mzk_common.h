@@ -286,9 +286,12 @@ struct mzk_srs {
 
 namespace mzk {
 // `count` commitments of n coefficients each (polynomial j at d_scalars + j * stride_elems * 32 bytes) against one handle, as ONE
-// pass: over the direct tables when the handle has them, over its narrow window tables otherwise (srs_many_capable)
+// pass: over the direct tables when the handle has them, over its narrow window tables otherwise (srs_many_capable).
+// shift != 0: against the points [shift, shift + n) of the handle (every layout keeps point i of a table at row offset i, so the
+// tables are entered `shift` rows further on with the row stride unchanged); shift + n <= srs->n.
 bool srs_many_capable(const mzk_srs* srs);
-int msm_many_srs(const mzk_srs* srs, const void* d_scalars, size_t n, size_t stride_elems, size_t count, void* d_out, hipStream_t s);
+int msm_many_srs(const mzk_srs* srs, const void* d_scalars, size_t n, size_t stride_elems, size_t count, void* d_out, hipStream_t s,
+                 size_t shift = 0);
 bool kzg_open_many_supported(const mzk_srs* srs, size_t n);
 int kzg_open_many_dev(const mzk_srs* srs, const void* d_coefs, size_t n, size_t count, const uint64_t* us_host, void* d_ys, void* d_ws_xy, hipStream_t s);
 }  // namespace mzk

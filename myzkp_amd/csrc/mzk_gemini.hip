@@ -1,0 +1,704 @@
+// mzk_gemini.hip -- the multilinear half of the prover path on gfx950: Gemini split-and-fold, commit and open
+// (myzkp/src/modules/algebra/gemini.rs:51-144) and the sum-check prover (algebra/sumcheck.rs:57-166).
+//
+// All values are BN254 Fr in standard form.  A multilinear g with coefficient c[t] at index t (bit i of t = exponent of
+// variable i, get_coefs_in_order, sumcheck.rs:97-108) folds as f_{i+1}[k] = f_i[2k] + rho_i f_i[2k+1]; level el is the
+// constant mu.  rho is turned into Montgomery form (rho R) once on the host, so one Montgomery product c * (rho R) / R
+// returns c rho in standard form.
+//
+// Kernels:
+//   k_gm_fold        one memory-bound pass per large level;
+//   k_gm_fold_lds    every level from FOLD_LDS_IN elements down, in LDS, in one launch;
+//   k_gm_sums        weighted sums over a level (sum_over_boolean_hypercube, and the sum-check round messages A_j / B_j),
+//                    optionally fused with the fold that produces the level (one pass over the data per round);
+//   k_sh_eval / k_sh_scan / k_sh_fill
+//                    suffix Horner b_t = c_t + u b_{t+1} for a TABLE of (polynomial, point) jobs at once: chunk values, one
+//                    workgroup per job scans the chunk values, chunk fill.  b_0 = f(u), b_1.. = the quotient by (X - u).
+//                    Gemini's evaluations at beta, -beta, beta^2 and its quotients by (X - beta)(X + beta)(X - beta^2) of
+//                    every level are three such rounds (nine launches whatever el is).
+// The MSMs run on the SRS handle's tables (mzk_msm.hip); the degree-bound MSMs of prove_degree_bound (kzg.rs:121-134) on the
+// handle entered max_d - d rows further on (see gemini_open_impl).
+#include "mzk_common.h"
+
+namespace mzk {
+
+typedef FrParams GP;
+typedef Fe<GP> GE;
+struct GmW8 { u32 w[8]; };
+
+__device__ __forceinline__ GE gm_load(const u32* __restrict__ g, size_t i) {
+  const uint4* p = reinterpret_cast<const uint4*>(g + 8 * i);
+  const uint4 a = p[0], b = p[1];
+  const u32 w[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
+  return fe_unpack<GP>(w);
+}
+// v canonical
+__device__ __forceinline__ void gm_store(u32* __restrict__ g, size_t i, const GE& v) {
+  u32 w[8];
+  fe_pack<GP>(v, w);
+  uint4* p = reinterpret_cast<uint4*>(g + 8 * i);
+  p[0] = make_uint4(w[0], w[1], w[2], w[3]);
+  p[1] = make_uint4(w[4], w[5], w[6], w[7]);
+}
+// canonical a + b * (r R) / R = a + b r
+__device__ __forceinline__ GE gm_fold1(const GE& a, const GE& b, const GE& r_mont) {
+  return fe_reduce<GP>(fe_add<GP>(a, fe_mul<GP>(b, r_mont)));
+}
+
+// ---- host parameter math ------------------------------------------------------------------------------------------
+static void gm_words(const uint64_t* v, GmW8* out) {
+  for (int i = 0; i < 4; i++) { out->w[2 * i] = (u32)v[i]; out->w[2 * i + 1] = (u32)(v[i] >> 32); }
+}
+// v R mod r (R = 2^(29 L) = 2^261), as 8 words
+static void gm_mont(const uint64_t* v, GmW8* out) {
+  const HostField* fr = host_field(MZK_FIELD_FR);
+  uint64_t two[4] = {2, 0, 0, 0}, rmod[4], t[4];
+  h_powmod_u64(fr, rmod, two, 29 * GP::L);
+  h_mulmod(fr, t, v, rmod);
+  gm_words(t, out);
+}
+static bool gm_log2(size_t n, int* el) {
+  if (n == 0 || (n & (n - 1))) return false;
+  int e = 0;
+  while (((size_t)1 << e) < n) e++;
+  *el = e;
+  return true;
+}
+constexpr int GM_MAX_LOG = 30;
+static int gm_check_n(size_t n, int* el, const char* who) {
+  if (!gm_log2(n, el)) { set_error("%s: coefs.len() must be a power of two, but got %zu", who, n); return MZK_E_NOT_POW2; }
+  if (*el > GM_MAX_LOG) { set_error("%s: 2^%d coefficients (at most 2^%d)", who, *el, GM_MAX_LOG); return MZK_E_ARG; }
+  return MZK_OK;
+}
+// 2^k R for k = 0..31: the weights of the hypercube sums
+struct GmPow2 { u32 w[32][8]; };
+static GmPow2 gm_pow2() {
+  GmPow2 p;
+  for (int k = 0; k < 32; k++) {
+    uint64_t v[4] = {(uint64_t)1 << k, 0, 0, 0};
+    GmW8 m;
+    gm_mont(v, &m);
+    memcpy(p.w[k], m.w, 32);
+  }
+  return p;
+}
+
+// ---- split-and-fold (gemini.rs:51-100) ----------------------------------------------------------------------------
+constexpr size_t FOLD_LDS_IN = 2048;       // levels of at most this many elements fold in LDS, all in one launch
+constexpr int FOLD_THREADS = 256;
+struct GmRho16 { u32 w[16][8]; };
+
+__global__ __launch_bounds__(FOLD_THREADS) void k_gm_fold(const u32* __restrict__ in, size_t n_out, GmW8 rho, u32* __restrict__ out) {
+  const size_t k = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (k >= n_out) return;
+  gm_store(out, k, gm_fold1(gm_load(in, 2 * k), gm_load(in, 2 * k + 1), fe_unpack<GP>(rho.w)));
+}
+// in: one level of len0 <= FOLD_LDS_IN elements (global); writes the nfold levels below it back to back from `out`
+__global__ __launch_bounds__(FOLD_THREADS) void k_gm_fold_lds(const u32* __restrict__ in, int len0, GmRho16 rho, int nfold, u32* __restrict__ out) {
+  __shared__ u32 A[FOLD_LDS_IN / 2][8];
+  __shared__ u32 B[FOLD_LDS_IN / 4][8];
+  const int tid = threadIdx.x;
+  int len = len0 >> 1;
+  {
+    const GE r = fe_unpack<GP>(rho.w[0]);
+    for (int k = tid; k < len; k += FOLD_THREADS) {
+      const GE v = gm_fold1(gm_load(in, 2 * k), gm_load(in, 2 * k + 1), r);
+      fe_pack<GP>(v, A[k]);
+      gm_store(out, k, v);
+    }
+  }
+  u32* o = out + 8 * (size_t)len;
+  for (int f = 1; f < nfold; f++) {
+    __syncthreads();
+    u32 (*src)[8] = (f & 1) ? A : B;
+    u32 (*dst)[8] = (f & 1) ? B : A;
+    const GE r = fe_unpack<GP>(rho.w[f]);
+    const int nl = len >> 1;
+    for (int k = tid; k < nl; k += FOLD_THREADS) {
+      const GE v = gm_fold1(fe_unpack<GP>(src[2 * k]), fe_unpack<GP>(src[2 * k + 1]), r);
+      fe_pack<GP>(v, dst[k]);
+      gm_store(o, k, v);
+    }
+    o += 8 * (size_t)nl;
+    len = nl;
+  }
+}
+
+// levels: 2n - 1 elements, level 0 first.  rhos: el host values (canonical).  d_levels may hold level 0 already.
+static int split_fold_impl(const void* d_coef, size_t n, const uint64_t* rhos, size_t n_rhos, void* d_levels, hipStream_t s) {
+  if (!d_levels || (!d_coef && n)) { set_error("split_fold: null pointer"); return MZK_E_ARG; }
+  int el;
+  MZK_TRY(gm_check_n(n, &el, "split_fold"));
+  if (n_rhos != (size_t)el) { set_error("points.len() must be %d, but got %zu", el, n_rhos); return MZK_E_LENGTH; }
+  if (el && !rhos) { set_error("split_fold: null pointer"); return MZK_E_ARG; }
+  const HostField* fr = host_field(MZK_FIELD_FR);
+  for (int i = 0; i < el; i++) if (!h_is_canonical(fr, rhos + 4 * i)) { set_error("split_fold: rho_%d not canonical", i); return MZK_E_RANGE; }
+  if (d_coef != d_levels) MZK_HIP(hipMemcpyAsync(d_levels, d_coef, n * 32, hipMemcpyDeviceToDevice, s));
+  const u32* cur = (const u32*)d_levels;
+  size_t len = n;
+  int i = 0;
+  while (len > FOLD_LDS_IN) {
+    GmW8 r;
+    gm_mont(rhos + 4 * i, &r);
+    u32* next = (u32*)cur + 8 * len;
+    const size_t nout = len / 2;
+    hipLaunchKernelGGL(k_gm_fold, dim3((unsigned)((nout + FOLD_THREADS - 1) / FOLD_THREADS)), dim3(FOLD_THREADS), 0, s, cur, nout, r, next);
+    cur = next; len = nout; i++;
+  }
+  if (len > 1) {
+    GmRho16 rr;
+    for (int f = 0; f < el - i; f++) { GmW8 r; gm_mont(rhos + 4 * (i + f), &r); memcpy(rr.w[f], r.w, 32); }
+    hipLaunchKernelGGL(k_gm_fold_lds, dim3(1), dim3(FOLD_THREADS), 0, s, cur, (int)len, rr, el - i, (u32*)cur + 8 * len);
+  }
+  MZK_HIP(hipGetLastError());
+  return MZK_OK;
+}
+
+// ---- hypercube sums ------------------------------------------------------------------------------------------------
+// Element t of the visited level (FOLD: t of the level being produced, v_t = f[2t] + r f[2t+1], stored to out) enters slot
+// (split ? t & 1 : 0) with weight 2^(base - popcount(t >> shift)); base < 0: no sums.  One partial per (workgroup, slot).
+constexpr int SUM_THREADS = 256;
+constexpr int SUM_MAX_WG = 1024;
+template <bool FOLD>
+__global__ __launch_bounds__(SUM_THREADS) void k_gm_sums(const u32* __restrict__ f, size_t count, GmW8 r, u32* __restrict__ out, int base, int shift,
+                                                          int split, GmPow2 pw, u32* __restrict__ partials) {
+  __shared__ u32 S[2][SUM_THREADS][GP::L];
+  const int tid = threadIdx.x;
+  GE acc[2] = {fe_zero<GP>(), fe_zero<GP>()};
+  const GE rm = fe_unpack<GP>(r.w);
+  for (size_t t = (size_t)blockIdx.x * SUM_THREADS + tid; t < count; t += (size_t)gridDim.x * SUM_THREADS) {
+    GE v;
+    if (FOLD) {
+      v = gm_fold1(gm_load(f, 2 * t), gm_load(f, 2 * t + 1), rm);
+      gm_store(out, t, v);
+    } else {
+      v = gm_load(f, t);
+    }
+    if (base < 0) continue;
+    const int e = base - __popcll((unsigned long long)(t >> shift));
+    const GE term = fe_mul<GP>(v, fe_unpack<GP>(pw.w[e]));
+    const int slot = split ? (int)(t & 1) : 0;
+    acc[slot] = fe_reduce<GP>(fe_add<GP>(acc[slot], term));
+  }
+  if (base < 0) return;
+#pragma unroll
+  for (int q = 0; q < 2; q++)
+#pragma unroll
+    for (int i = 0; i < GP::L; i++) S[q][tid][i] = acc[q].l[i];
+  for (int d = SUM_THREADS / 2; d > 0; d >>= 1) {
+    __syncthreads();
+    if (tid < d) {
+#pragma unroll
+      for (int q = 0; q < 2; q++) {
+        GE a, b;
+#pragma unroll
+        for (int i = 0; i < GP::L; i++) { a.l[i] = S[q][tid][i]; b.l[i] = S[q][tid + d][i]; }
+        a = fe_reduce<GP>(fe_add<GP>(a, b));
+#pragma unroll
+        for (int i = 0; i < GP::L; i++) S[q][tid][i] = a.l[i];
+      }
+    }
+  }
+  __syncthreads();                 // lane 1 reads S[1][0], which lane 0 wrote in the last step
+  if (tid < 2) {
+    GE a;
+#pragma unroll
+    for (int i = 0; i < GP::L; i++) a.l[i] = S[tid][0][i];
+    gm_store(partials, 2 * (size_t)blockIdx.x + tid, a);
+  }
+}
+// out[0..2) = the two slots summed over nparts workgroups
+__global__ __launch_bounds__(SUM_THREADS) void k_gm_sums_final(const u32* __restrict__ partials, int nparts, u32* __restrict__ out) {
+  __shared__ u32 S[2][SUM_THREADS][GP::L];
+  const int tid = threadIdx.x;
+  GE acc[2] = {fe_zero<GP>(), fe_zero<GP>()};
+  for (int p = tid; p < nparts; p += SUM_THREADS)
+#pragma unroll
+    for (int q = 0; q < 2; q++) acc[q] = fe_reduce<GP>(fe_add<GP>(acc[q], gm_load(partials, 2 * (size_t)p + q)));
+#pragma unroll
+  for (int q = 0; q < 2; q++)
+#pragma unroll
+    for (int i = 0; i < GP::L; i++) S[q][tid][i] = acc[q].l[i];
+  for (int d = SUM_THREADS / 2; d > 0; d >>= 1) {
+    __syncthreads();
+    if (tid < d) {
+#pragma unroll
+      for (int q = 0; q < 2; q++) {
+        GE a, b;
+#pragma unroll
+        for (int i = 0; i < GP::L; i++) { a.l[i] = S[q][tid][i]; b.l[i] = S[q][tid + d][i]; }
+        a = fe_reduce<GP>(fe_add<GP>(a, b));
+#pragma unroll
+        for (int i = 0; i < GP::L; i++) S[q][tid][i] = a.l[i];
+      }
+    }
+  }
+  __syncthreads();                 // lane 1 reads S[1][0], which lane 0 wrote in the last step
+  if (tid < 2) {
+    GE a;
+#pragma unroll
+    for (int i = 0; i < GP::L; i++) a.l[i] = S[tid][0][i];
+    gm_store(out, tid, a);
+  }
+}
+// d_out2: 2 elements (slot 0, slot 1).  Workspace: WS_NTT_IO_A (partials).
+static int gm_sums(const void* d_f, size_t count, const uint64_t* r_host, void* d_fold_out, int base, int shift, int split, void* d_out2, hipStream_t s) {
+  static const GmPow2 pw = gm_pow2();
+  GmW8 r = {};
+  if (r_host) gm_mont(r_host, &r);
+  const size_t wg_need = (count + SUM_THREADS - 1) / SUM_THREADS;
+  const int nwg = (int)(wg_need < (size_t)SUM_MAX_WG ? (wg_need ? wg_need : 1) : SUM_MAX_WG);
+  u32* partials = nullptr;
+  MZK_TRY(ws_get(WS_NTT_IO_A, (size_t)nwg * 64, (void**)&partials));
+  if (d_fold_out)
+    hipLaunchKernelGGL(k_gm_sums<true>, dim3(nwg), dim3(SUM_THREADS), 0, s, (const u32*)d_f, count, r, (u32*)d_fold_out, base, shift, split, pw, partials);
+  else
+    hipLaunchKernelGGL(k_gm_sums<false>, dim3(nwg), dim3(SUM_THREADS), 0, s, (const u32*)d_f, count, r, (u32*)nullptr, base, shift, split, pw, partials);
+  if (base >= 0) hipLaunchKernelGGL(k_gm_sums_final, dim3(1), dim3(SUM_THREADS), 0, s, (const u32*)partials, nwg, (u32*)d_out2);
+  MZK_HIP(hipGetLastError());
+  return MZK_OK;
+}
+
+// ---- batched suffix Horner ------------------------------------------------------------------------------------------
+constexpr int SH_K_LOG = 5;
+constexpr size_t SH_K = (size_t)1 << SH_K_LOG;   // elements per chunk (one lane's serial Horner)
+constexpr int SH_SCAN_THREADS = 256;
+struct ShJob {
+  const u32* src;   // len coefficients
+  u32* dst;         // the quotient b_1 .. b_{len-1} (len - 1 elements), or null
+  u32* y;           // b_0 = src(u), or null
+  u64 len;
+  u64 chunk0;       // first chunk of this job in the flat chunk arrays
+  u32 u[8];         // u R
+  u32 uk[8];        // u^K R
+};
+__device__ __forceinline__ int sh_job_of(const ShJob* __restrict__ jobs, int njobs, u64 g) {
+  int lo = 0, hi = njobs - 1;     // last job with chunk0 <= g
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (jobs[mid].chunk0 <= g) lo = mid; else hi = mid - 1;
+  }
+  return lo;
+}
+// h[chunk] = sum_{t in chunk} c[t] u^(t - lo)
+__global__ __launch_bounds__(64) void k_sh_eval(const ShJob* __restrict__ jobs, int njobs, u64 nchunks, u32* __restrict__ h) {
+  const u64 g = (u64)blockIdx.x * blockDim.x + threadIdx.x;
+  if (g >= nchunks) return;
+  const ShJob& J = jobs[sh_job_of(jobs, njobs, g)];
+  const u64 lo = (g - J.chunk0) << SH_K_LOG;
+  const u64 hi = (lo + SH_K < J.len) ? lo + SH_K : J.len;
+  const GE u = fe_unpack<GP>(J.u);
+  GE acc = gm_load(J.src, hi - 1);
+  for (u64 t = hi - 1; t-- > lo;) acc = fe_add<GP>(fe_mul<GP>(acc, u), gm_load(J.src, t));
+  gm_store(h, g, fe_reduce<GP>(acc));
+}
+// one workgroup per job: carry[m] = sum_{m' >= m} h[m'] (u^K)^(m' - m) = b_{m K}; y = carry[0]
+__global__ __launch_bounds__(SH_SCAN_THREADS) void k_sh_scan(const ShJob* __restrict__ jobs, const u32* __restrict__ h, u32* __restrict__ carry) {
+  __shared__ u32 S[SH_SCAN_THREADS][GP::L];
+  const ShJob& J = jobs[blockIdx.x];
+  const int L = threadIdx.x;
+  const u64 nh = (J.len + SH_K - 1) >> SH_K_LOG;
+  const u32* hj = h + 8 * J.chunk0;
+  u32* cj = carry + 8 * J.chunk0;
+  const GE uk = fe_unpack<GP>(J.uk);
+  const u64 K2 = (nh + SH_SCAN_THREADS - 1) / SH_SCAN_THREADS;
+  const u64 lo = (u64)L * K2;
+  const u64 hi = (lo + K2 < nh) ? lo + K2 : nh;
+  GE mine = fe_zero<GP>();
+  if (lo < nh) {
+    mine = gm_load(hj, hi - 1);
+    for (u64 t = hi - 1; t-- > lo;) mine = fe_add<GP>(fe_mul<GP>(mine, uk), gm_load(hj, t));
+    mine = fe_reduce<GP>(mine);
+  }
+  GE pw = fe_one<GP>(), b = uk;                              // (u^K)^K2 R
+  for (u64 k = K2; k; k >>= 1) {
+    if (k & 1) pw = fe_mul<GP>(pw, b);
+    b = fe_sqr<GP>(b);
+  }
+#pragma unroll
+  for (int i = 0; i < GP::L; i++) S[L][i] = mine.l[i];
+  for (int d = 1; d < SH_SCAN_THREADS; d <<= 1) {
+    __syncthreads();
+    GE other = fe_zero<GP>();
+    if (L + d < SH_SCAN_THREADS) {
+#pragma unroll
+      for (int i = 0; i < GP::L; i++) other.l[i] = S[L + d][i];
+    }
+    __syncthreads();
+    mine = fe_reduce<GP>(fe_add<GP>(mine, fe_mul<GP>(other, pw)));
+#pragma unroll
+    for (int i = 0; i < GP::L; i++) S[L][i] = mine.l[i];
+    pw = fe_sqr<GP>(pw);
+  }
+  __syncthreads();
+  if (lo >= nh) return;
+  GE acc = fe_zero<GP>();
+  if (L + 1 < SH_SCAN_THREADS) {
+#pragma unroll
+    for (int i = 0; i < GP::L; i++) acc.l[i] = S[L + 1][i];
+  }
+  for (u64 t = hi; t-- > lo;) {
+    acc = fe_reduce<GP>(fe_add<GP>(fe_mul<GP>(acc, uk), gm_load(hj, t)));
+    gm_store(cj, t, acc);
+  }
+  if (L == 0 && J.y) gm_store(J.y, 0, acc);
+}
+// b[t] = c[t] + u b[t+1] inside each chunk from the carry of the next chunk; the quotient is b[1..len)
+__global__ __launch_bounds__(64) void k_sh_fill(const ShJob* __restrict__ jobs, int njobs, u64 nchunks, const u32* __restrict__ carry) {
+  const u64 g = (u64)blockIdx.x * blockDim.x + threadIdx.x;
+  if (g >= nchunks) return;
+  const ShJob& J = jobs[sh_job_of(jobs, njobs, g)];
+  if (!J.dst) return;
+  const u64 m = g - J.chunk0;
+  const u64 lo = m << SH_K_LOG;
+  const u64 hi = (lo + SH_K < J.len) ? lo + SH_K : J.len;
+  const GE u = fe_unpack<GP>(J.u);
+  GE acc = (hi < J.len) ? gm_load(carry, g + 1) : fe_zero<GP>();
+  for (u64 t = hi; t-- > lo;) {
+    acc = fe_reduce<GP>(fe_add<GP>(fe_mul<GP>(acc, u), gm_load(J.src, t)));
+    if (t > 0) gm_store(J.dst, t - 1, acc);
+  }
+}
+struct ShRound {
+  std::vector<ShJob> jobs;
+  u64 nchunks = 0;
+  void add(const void* src, size_t len, const GmW8& u, const GmW8& uk, void* dst, void* y) {
+    if (len == 0) return;
+    ShJob j;
+    j.src = (const u32*)src; j.dst = (u32*)dst; j.y = (u32*)y; j.len = len; j.chunk0 = nchunks;
+    memcpy(j.u, u.w, 32); memcpy(j.uk, uk.w, 32);
+    jobs.push_back(j);
+    nchunks += (len + SH_K - 1) >> SH_K_LOG;
+  }
+};
+// d_jobs: room for the table; h, carry: nchunks elements each
+static int sh_run(const ShRound& R, ShJob* d_jobs, u32* h, u32* carry, hipStream_t s) {
+  if (R.jobs.empty()) return MZK_OK;
+  MZK_HIP(hipMemcpyAsync(d_jobs, R.jobs.data(), R.jobs.size() * sizeof(ShJob), hipMemcpyHostToDevice, s));
+  const int nj = (int)R.jobs.size();
+  const unsigned grid = (unsigned)((R.nchunks + 63) / 64);
+  hipLaunchKernelGGL(k_sh_eval, dim3(grid), dim3(64), 0, s, (const ShJob*)d_jobs, nj, R.nchunks, h);
+  hipLaunchKernelGGL(k_sh_scan, dim3(nj), dim3(SH_SCAN_THREADS), 0, s, (const ShJob*)d_jobs, (const u32*)h, carry);
+  bool fill = false;
+  for (const ShJob& j : R.jobs) fill |= j.dst != nullptr;
+  if (fill) hipLaunchKernelGGL(k_sh_fill, dim3(grid), dim3(64), 0, s, (const ShJob*)d_jobs, nj, R.nchunks, (const u32*)carry);
+  MZK_HIP(hipGetLastError());
+  return MZK_OK;
+}
+
+// ---- MSM schedule ---------------------------------------------------------------------------------------------------
+// Levels of at most GM_SMALL coefficients go through ONE grid-batched pass per kind (commitments, quotients, degree bounds)
+// when the handle has a grid-batched path (srs_many_capable: direct tables, or narrow 8 / 10..13-bit tables with one bucket
+// set); rows are zero-padded to the longest small level (zero coefficients add nothing).  Larger levels -- and every level on
+// handles without that path (wide default tables of large SRS, degraded bucket sets, the no-table layout) -- take one MSM each.
+constexpr size_t GM_SMALL = (size_t)1 << 12;
+constexpr int GM_ROWS_MAX = 32;
+struct GmRows { const u32* src[GM_ROWS_MAX]; u32 len[GM_ROWS_MAX]; u32 pad[GM_ROWS_MAX]; };
+// row r of dst (width w): pad[r] zeros, src[r][0 .. len[r]), zeros
+__global__ __launch_bounds__(256) void k_gm_pack(GmRows R, u32 w, u32* __restrict__ dst) {
+  const u32 t = blockIdx.x * blockDim.x + threadIdx.x;
+  const int r = blockIdx.y;
+  if (t >= w) return;
+  uint4* p = reinterpret_cast<uint4*>(dst + 8 * ((size_t)r * w + t));
+  if (t >= R.pad[r] && t - R.pad[r] < R.len[r]) {
+    const uint4* q = reinterpret_cast<const uint4*>(R.src[r] + 8 * (size_t)(t - R.pad[r]));
+    p[0] = q[0]; p[1] = q[1];
+  } else {
+    p[0] = make_uint4(0, 0, 0, 0); p[1] = p[0];
+  }
+}
+int msm_points_to_plain(const void* d_points_mont, size_t n, void* d_points_plain, hipStream_t s);   // mzk_msm.hip
+// On handles without that path a table MSM pays its bucket pass whatever n is (about 0.9 ms at 17-bit windows, also for 16
+// coefficients), so levels of at most GM_PLAIN_MAX coefficients run as generic MSMs over a plain copy of the points they use:
+// row 0 of every layout holds the prepared points P_i themselves.
+constexpr size_t GM_PLAIN_MAX = (size_t)1 << 16;
+struct GmMsm { const void* src; size_t len; size_t shift; };
+// out[k] (64 bytes each) = MSM(items[k].src, points [shift_k, shift_k + len_k)).  Items i0.. (the small ones) may go as one pass:
+// then `front` pads at the front (all windows end at the same point, base = that end - width) instead of at the back.
+static int gm_msms(const mzk_srs* srs, const GmMsm* items, int count, int i0, bool front, u32* d_out, hipStream_t s) {
+  const bool capable = srs_many_capable(srs);
+  const bool many = capable && count - i0 >= 2;
+  const int single_to = many ? i0 : count;
+  size_t plain_max = 0;
+  for (int k = 0; k < single_to && !capable; k++)
+    if (items[k].len <= GM_PLAIN_MAX && items[k].len > plain_max) plain_max = items[k].len;
+  u32* plain = nullptr;
+  if (plain_max) MZK_TRY(ws_get(WS_NTT_TMP, plain_max * 64, (void**)&plain));
+  for (int k = 0; k < single_to; k++) {
+    const char* pts = (const char*)srs->d_points_mont + items[k].shift * 64;
+    if (plain && items[k].len <= plain_max && items[k].len > 0) {
+      MZK_TRY(msm_points_to_plain(pts, items[k].len, plain, s));
+      MZK_TRY(msm_dev_impl(items[k].src, plain, items[k].len, MSM_PTS_PLAIN, 0, d_out + 16 * k, false, s));
+    } else {
+      MZK_TRY(msm_dev_impl(items[k].src, pts, items[k].len, srs->kind(), srs->n, d_out + 16 * k, false, s));
+    }
+  }
+  if (!many) return MZK_OK;
+  GmRows R;
+  size_t w = 0;
+  const int rows = count - i0;
+  for (int k = i0; k < count; k++) w = items[k].len > w ? items[k].len : w;
+  if (w == 0) { MZK_HIP(hipMemsetAsync(d_out + 16 * i0, 0, (size_t)rows * 64, s)); return MZK_OK; }
+  for (int r = 0; r < rows; r++) {
+    R.src[r] = (const u32*)items[i0 + r].src;
+    R.len[r] = (u32)items[i0 + r].len;
+    R.pad[r] = front ? (u32)(w - items[i0 + r].len) : 0;
+  }
+  u32* mat;
+  MZK_TRY(ws_get(WS_MISC_F, (size_t)rows * w * 32, (void**)&mat));
+  hipLaunchKernelGGL(k_gm_pack, dim3((unsigned)((w + 255) / 256), (unsigned)rows), dim3(256), 0, s, R, (u32)w, mat);
+  MZK_HIP(hipGetLastError());
+  // front-padded rows: every window ends at shift_k + len_k = the same point; the padded row starts w earlier
+  const size_t shift = front ? items[i0].shift + items[i0].len - w : 0;
+  return msm_many_srs(srs, mat, w, w, (size_t)rows, d_out + 16 * i0, s, shift);
+}
+
+static int gm_srs_ok(const mzk_srs* srs, size_t n, int* el, const char* who) {
+  MZK_TRY(gm_check_n(n, el, who));
+  if (srs->ctx_index != ctx().index && mzk_ctx_device(srs->ctx_index) != ctx().device) {
+    set_error("SRS handle lives on context %d, the current context %d drives device %d (mzk_ctx_select)", srs->ctx_index, ctx().index, ctx().device);
+    return MZK_E_ARG;
+  }
+  return MZK_OK;
+}
+static inline size_t gm_level_off(size_t n, int i) { return 2 * n - (n >> i) * 2; }     // sum_{j < i} n / 2^j
+
+// commit_gemini (gemini.rs:112-114): el + 1 commitments of the packed levels.  d_out: (el + 1) * 16 words.
+static int gemini_commit_impl(const mzk_srs* srs, const void* d_levels, size_t n, void* d_out, hipStream_t s) {
+  if (!srs || !d_levels || !d_out) { set_error("gemini_commit: null pointer"); return MZK_E_ARG; }
+  int el;
+  MZK_TRY(gm_srs_ok(srs, n, &el, "gemini_commit"));
+  if (n > srs->n) { set_error("index out of bounds: the len is %zu but the index is %zu", srs->n, srs->n); return MZK_E_LENGTH; }
+  GmMsm it[GM_MAX_LOG + 1];
+  int i0 = el + 1;
+  for (int i = 0; i <= el; i++) {
+    it[i] = {(const char*)d_levels + gm_level_off(n, i) * 32, n >> i, 0};
+    if ((n >> i) <= GM_SMALL && i0 > i) i0 = i;
+  }
+  return gm_msms(srs, it, el + 1, i0, false, (u32*)d_out, s);
+}
+
+// open_gemini (gemini.rs:116-144).  d_ys: el * 3 values (f_i(beta), f_i(-beta), f_i(beta^2)); d_ws: el points; d_deg: el + 1 points.
+static int gemini_open_impl(const mzk_srs* srs, const void* d_levels, size_t n, const uint64_t* beta, void* d_ys, void* d_ws, void* d_deg, hipStream_t s) {
+  if (!srs || !d_levels || !beta || !d_deg || ((!d_ys || !d_ws) && n > 1)) { set_error("gemini_open: null pointer"); return MZK_E_ARG; }
+  int el;
+  MZK_TRY(gm_srs_ok(srs, n, &el, "gemini_open"));
+  const HostField* fr = host_field(MZK_FIELD_FR);
+  if (!h_is_canonical(fr, beta)) { set_error("gemini_open: beta not canonical"); return MZK_E_RANGE; }
+  // prove_degree_bound(f_0, pk, n): max_d - n underflows when max_d < n (kzg.rs:126)
+  const size_t max_d = srs->n - 1;
+  if (srs->n == 0 || max_d < n) { set_error("attempt to subtract with overflow (max_d %zu - d %zu): the SRS needs n + 1 powers", srs->n ? max_d : 0, n); return MZK_E_LENGTH; }
+  uint64_t nb[4] = {0, 0, 0, 0}, b2[4];
+  if (beta[0] | beta[1] | beta[2] | beta[3]) {            // (0 - beta).sanitize()
+    unsigned __int128 br = 0;
+    for (int i = 0; i < 4; i++) {
+      const unsigned __int128 d = (unsigned __int128)fr->p[i] - beta[i] - (uint64_t)br;
+      nb[i] = (uint64_t)d;
+      br = (d >> 64) ? 1 : 0;
+    }
+  }
+  h_mulmod(fr, b2, beta, beta);
+  if (el > 0 && (!memcmp(beta, nb, 32) || !memcmp(beta, b2, 32) || !memcmp(nb, b2, 32))) {
+    set_error("gemini_open: beta, -beta and beta^2 must be distinct (beta in {0, 1, -1}: interpolate divides by zero)");
+    return MZK_E_ARG;
+  }
+  // evaluations and quotients: three rounds of suffix Horner over every level i < el
+  size_t qtot = 0;
+  for (int i = 0; i < el; i++) qtot += n >> i;
+  u32 *qa = nullptr, *qb = nullptr, *hc = nullptr;
+  ShJob* d_jobs = nullptr;
+  if (el > 0) {
+    GmW8 ub, ubk, un, unk, u2, u2k;
+    uint64_t t[4];
+    gm_mont(beta, &ub); h_powmod_u64(fr, t, beta, SH_K); gm_mont(t, &ubk);
+    gm_mont(nb, &un); h_powmod_u64(fr, t, nb, SH_K); gm_mont(t, &unk);
+    gm_mont(b2, &u2); h_powmod_u64(fr, t, b2, SH_K); gm_mont(t, &u2k);
+    ShRound A, B, C;
+    size_t qoff = 0;
+    MZK_TRY(ws_get(WS_MISC_A, qtot * 32, (void**)&qa));
+    MZK_TRY(ws_get(WS_MISC_B, qtot * 32, (void**)&qb));
+    for (int i = 0; i < el; i++) {
+      const size_t len = n >> i;
+      const char* f = (const char*)d_levels + gm_level_off(n, i) * 32;
+      char* y = (char*)d_ys + (size_t)i * 96;
+      A.add(f, len, ub, ubk, qa + 8 * qoff, y);              // q1 = f / (X - beta), f(beta)
+      A.add(f, len, un, unk, nullptr, y + 32);                // f(-beta)
+      A.add(f, len, u2, u2k, nullptr, y + 64);                // f(beta^2)
+      B.add(qa + 8 * qoff, len - 1, un, unk, qb + 8 * qoff, nullptr);              // q2 = q1 / (X + beta)
+      if (len >= 2) C.add(qb + 8 * qoff, len - 2, u2, u2k, qa + 8 * qoff, nullptr);  // q3 = q2 / (X - beta^2): len - 3 elements
+      qoff += len;
+    }
+    MZK_TRY(ws_get(WS_MISC_C, A.jobs.size() * sizeof(ShJob) * 3, (void**)&d_jobs));
+    MZK_TRY(ws_get(WS_MISC_D, A.nchunks * 64, (void**)&hc));
+    // three tables side by side: a later round's upload must not overwrite a table an earlier round's kernels still read
+    MZK_TRY(sh_run(A, d_jobs, hc, hc + 8 * A.nchunks, s));
+    MZK_TRY(sh_run(B, d_jobs + A.jobs.size(), hc, hc + 8 * B.nchunks, s));
+    MZK_TRY(sh_run(C, d_jobs + 2 * A.jobs.size(), hc, hc + 8 * C.nchunks, s));
+  }
+  // w_i = MSM(q3_i, powers[0, len - 3))
+  GmMsm it[GM_MAX_LOG + 1];
+  int i0 = el;
+  size_t qoff = 0;
+  for (int i = 0; i < el; i++) {
+    const size_t len = n >> i;
+    it[i] = {qa + 8 * qoff, len >= 3 ? len - 3 : 0, 0};
+    if (len <= GM_SMALL && i0 > i) i0 = i;
+    qoff += len;
+  }
+  if (el > 0) MZK_TRY(gm_msms(srs, it, el, i0, false, (u32*)d_ws, s));
+  // deg_i = MSM(f_i * X^(max_d - d_i), powers) = MSM(f_i, powers[max_d - d_i, max_d)), d_i = len(f_i) = 2^(el - i)
+  i0 = el + 1;
+  for (int i = 0; i <= el; i++) {
+    const size_t len = n >> i;
+    it[i] = {(const char*)d_levels + gm_level_off(n, i) * 32, len, max_d - len};
+    if (len <= GM_SMALL && i0 > i) i0 = i;
+  }
+  return gm_msms(srs, it, el + 1, i0, true, (u32*)d_deg, s);
+}
+
+}  // namespace mzk
+
+using namespace mzk;
+
+extern "C" {
+
+int mzk_gemini_split_fold_dev(const void* d_coef, size_t n, const uint64_t* rhos, size_t n_rhos, void* d_out, void* stream) {
+  MZK_ENTER();
+  WsGuard wsg((hipStream_t)stream);
+  return split_fold_impl(d_coef, n, rhos, n_rhos, d_out, (hipStream_t)stream);
+}
+
+int mzk_gemini_split_fold(const uint64_t* coef, size_t n, const uint64_t* rhos, size_t n_rhos, uint64_t* out) {
+  MZK_ENTER();
+  if (!out || (!coef && n)) { set_error("split_fold: null pointer"); return MZK_E_ARG; }
+  int el;
+  MZK_TRY(gm_check_n(n, &el, "split_fold"));
+  if (n_rhos != (size_t)el) { set_error("points.len() must be %d, but got %zu", el, n_rhos); return MZK_E_LENGTH; }
+  if (el && !rhos) { set_error("split_fold: null pointer"); return MZK_E_ARG; }
+  for (int i = 0; i < el; i++)
+    if (!h_is_canonical(host_field(MZK_FIELD_FR), rhos + 4 * i)) { set_error("split_fold: rho_%d not canonical", i); return MZK_E_RANGE; }
+  hipStream_t s = ctx().stream;
+  WsGuard wsg(s);
+  void* d;
+  MZK_TRY(ws_get(WS_MISC_E, (2 * n - 1) * 32, &d));
+  MZK_HIP(hipMemcpyAsync(d, coef, n * 32, hipMemcpyHostToDevice, s));
+  MZK_TRY(split_fold_impl(d, n, rhos, n_rhos, d, s));
+  return d2h_sync(out, d, (2 * n - 1) * 32, s);
+}
+
+int mzk_gemini_commit_srs_dev(const mzk_srs* srs, const void* d_levels, size_t n, void* d_out_xy, void* stream) {
+  MZK_ENTER();
+  WsGuard wsg((hipStream_t)stream);
+  return gemini_commit_impl(srs, d_levels, n, d_out_xy, (hipStream_t)stream);
+}
+
+int mzk_gemini_commit_srs(const mzk_srs* srs, const uint64_t* levels, size_t n, uint64_t* out_xy) {
+  MZK_ENTER();
+  if (!srs || !levels || !out_xy) { set_error("gemini_commit: null pointer"); return MZK_E_ARG; }
+  int el;
+  MZK_TRY(gm_srs_ok(srs, n, &el, "gemini_commit"));
+  hipStream_t s = ctx().stream;
+  WsGuard wsg(s);
+  void *d, *d_o;
+  MZK_TRY(ws_get(WS_MISC_E, (2 * n - 1) * 32, &d));
+  MZK_TRY(ws_get(WS_NTT_IO_B, (size_t)(el + 1) * 64, &d_o));
+  MZK_HIP(hipMemcpyAsync(d, levels, (2 * n - 1) * 32, hipMemcpyHostToDevice, s));
+  const int rc = gemini_commit_impl(srs, d, n, d_o, s);
+  if (rc != MZK_OK) { (void)hipStreamSynchronize(s); return rc; }
+  return d2h_sync(out_xy, d_o, (size_t)(el + 1) * 64, s);
+}
+
+int mzk_gemini_open_srs_dev(const mzk_srs* srs, const void* d_levels, size_t n, const uint64_t beta[4], void* d_ys, void* d_ws_xy, void* d_deg_xy,
+                            void* stream) {
+  MZK_ENTER();
+  WsGuard wsg((hipStream_t)stream);
+  return gemini_open_impl(srs, d_levels, n, beta, d_ys, d_ws_xy, d_deg_xy, (hipStream_t)stream);
+}
+
+// results of the host forms in one device block: ys (el * 3 * 32 B), ws (el * 64 B), deg ((el + 1) * 64 B)
+static int gm_open_host(const mzk_srs* srs, const void* d_levels, size_t n, int el, const uint64_t* beta, uint64_t* ys, uint64_t* ws_xy, uint64_t* deg_xy,
+                        hipStream_t s) {
+  const size_t by = (size_t)el * 96, bw = (size_t)el * 64, bd = (size_t)(el + 1) * 64;
+  char* d_o;
+  MZK_TRY(ws_get(WS_NTT_IO_B, by + bw + bd, (void**)&d_o));
+  const int rc = gemini_open_impl(srs, d_levels, n, beta, d_o, d_o + by, d_o + by + bw, s);
+  if (rc != MZK_OK) { (void)hipStreamSynchronize(s); return rc; }
+  std::vector<uint64_t> tmp((by + bw + bd) / 8);
+  MZK_TRY(d2h_sync(tmp.data(), d_o, by + bw + bd, s));
+  if (el) { memcpy(ys, tmp.data(), by); memcpy(ws_xy, (char*)tmp.data() + by, bw); }
+  memcpy(deg_xy, (char*)tmp.data() + by + bw, bd);
+  return MZK_OK;
+}
+
+int mzk_gemini_open_srs(const mzk_srs* srs, const uint64_t* levels, size_t n, const uint64_t beta[4], uint64_t* ys, uint64_t* ws_xy, uint64_t* deg_xy) {
+  MZK_ENTER();
+  if (!srs || !levels || !beta || !deg_xy || ((!ys || !ws_xy) && n > 1)) { set_error("gemini_open: null pointer"); return MZK_E_ARG; }
+  int el;
+  MZK_TRY(gm_srs_ok(srs, n, &el, "gemini_open"));
+  hipStream_t s = ctx().stream;
+  WsGuard wsg(s);
+  void* d;
+  MZK_TRY(ws_get(WS_MISC_E, (2 * n - 1) * 32, &d));
+  MZK_HIP(hipMemcpyAsync(d, levels, (2 * n - 1) * 32, hipMemcpyHostToDevice, s));
+  return gm_open_host(srs, d, n, el, beta, ys, ws_xy, deg_xy, s);
+}
+
+int mzk_sumcheck_sum(const uint64_t* coef, size_t n, uint64_t h[4]) {
+  MZK_ENTER();
+  if (!h || (!coef && n)) { set_error("sumcheck_sum: null pointer"); return MZK_E_ARG; }
+  int el;
+  MZK_TRY(gm_check_n(n, &el, "sumcheck_sum"));
+  hipStream_t s = ctx().stream;
+  WsGuard wsg(s);
+  void *d, *d_o;
+  MZK_TRY(ws_get(WS_MISC_E, n * 32, &d));
+  MZK_TRY(ws_get(WS_NTT_IO_B, 64, &d_o));
+  MZK_HIP(hipMemcpyAsync(d, coef, n * 32, hipMemcpyHostToDevice, s));
+  // h = sum_t c[t] 2^(el - popcount t): variable i contributes g(..0..) + g(..1..), a factor 2 where its exponent is 0
+  MZK_TRY(gm_sums(d, n, nullptr, nullptr, el, 0, 0, d_o, s));
+  uint64_t out[8];
+  MZK_TRY(d2h_sync(out, d_o, 64, s));
+  memcpy(h, out, 32);
+  return MZK_OK;
+}
+
+int mzk_sumcheck_prove_srs(const mzk_srs* srs, const uint64_t* coef, size_t n, mzk_sumcheck_challenge_fn cb, void* user, uint64_t* gs, uint64_t* rs,
+                           uint64_t beta[4], uint64_t* commits_xy, uint64_t* ys, uint64_t* ws_xy, uint64_t* deg_xy) {
+  MZK_ENTER();
+  if (!srs || !coef || !cb || !gs || !rs || !beta || !commits_xy || !ys || !ws_xy || !deg_xy) { set_error("sumcheck_prove: null pointer"); return MZK_E_ARG; }
+  int el;
+  MZK_TRY(gm_srs_ok(srs, n, &el, "sumcheck_prove"));
+  if (el == 0) { set_error("invalid sizes for sum-check round (el = 0)"); return MZK_E_LENGTH; }
+  if (srs->n < n + 1) { set_error("attempt to subtract with overflow (max_d %zu - d %zu): the SRS needs n + 1 powers", srs->n - 1, n); return MZK_E_LENGTH; }
+  const HostField* fr = host_field(MZK_FIELD_FR);
+  hipStream_t s = ctx().stream;
+  WsGuard wsg(s);
+  char *d, *d_g;
+  MZK_TRY(ws_get(WS_MISC_E, (2 * n - 1) * 32, (void**)&d));
+  MZK_TRY(ws_get(WS_NTT_IO_B, 64, (void**)&d_g));
+  MZK_HIP(hipMemcpyAsync(d, coef, n * 32, hipMemcpyHostToDevice, s));
+  // round 0: g_0 = A_0 + B_0 X from f_0 (m = el - 1)
+  MZK_TRY(gm_sums(d, n, nullptr, nullptr, el - 1, 1, 1, d_g, s));
+  for (int j = 0; j < el; j++) {
+    MZK_TRY(d2h_sync(gs + 8 * j, d_g, 64, s));
+    uint64_t r[4] = {0, 0, 0, 0};
+    if (cb(user, j, gs + 8 * j, r) != 0) { set_error("sumcheck_prove: the challenge callback failed in round %d", j); return MZK_E_CALLBACK; }
+    if (!h_is_canonical(fr, r)) { set_error("sumcheck_prove: r_%d not canonical", j); return MZK_E_RANGE; }
+    memcpy(rs + 4 * j, r, 32);
+    // f_{j+1} = fold(f_j, r_j), and in the same pass g_{j+1}'s sums (m = el - 2 - j; none after the last round)
+    const size_t len = n >> j;
+    MZK_TRY(gm_sums(d + gm_level_off(n, j) * 32, len / 2, r, d + gm_level_off(n, j + 1) * 32, el - 2 - j, 1, 1, d_g, s));
+  }
+  uint64_t b[4] = {0, 0, 0, 0};
+  if (cb(user, el, nullptr, b) != 0) { (void)hipStreamSynchronize(s); set_error("sumcheck_prove: the challenge callback failed for beta"); return MZK_E_CALLBACK; }
+  if (!h_is_canonical(fr, b)) { (void)hipStreamSynchronize(s); set_error("sumcheck_prove: beta not canonical"); return MZK_E_RANGE; }
+  memcpy(beta, b, 32);
+  char* d_c;
+  MZK_TRY(ws_get(WS_NTT_IO_A, (size_t)(el + 1) * 64, (void**)&d_c));
+  int rc = gemini_commit_impl(srs, d, n, d_c, s);
+  if (rc == MZK_OK) rc = d2h_sync(commits_xy, d_c, (size_t)(el + 1) * 64, s);
+  if (rc != MZK_OK) { (void)hipStreamSynchronize(s); return rc; }
+  return gm_open_host(srs, d, n, el, b, ys, ws_xy, deg_xy, s);
+}
+
+}  // extern "C"

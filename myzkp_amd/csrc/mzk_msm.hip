@@ -2286,8 +2286,12 @@ bool srs_many_capable(const mzk_srs* srs) { return srs->d_direct != nullptr || (
 // 10 bits, 0.707 at 12; 32 x 2^13 0.842 / 0.713; 64 x 2^12 0.730 / 0.752; 128 x 2^11 0.755 / 1.236): 12 bits from 2^13 coefficients on.
 constexpr size_t MANY_WIDE_FROM = (size_t)1 << 13;
 constexpr int MANY_WIDE_BITS = 12;
-int msm_many_srs(const mzk_srs* srs, const void* d_scalars, size_t n, size_t stride_elems, size_t count, void* d_out, hipStream_t s) {
-  if (srs->d_direct) return msm_direct_many_dev_impl(d_scalars, n, stride_elems, count, srs->d_direct, srs->direct_bits, srs->n, d_out, s);
+int msm_many_srs(const mzk_srs* srs, const void* d_scalars, size_t n, size_t stride_elems, size_t count, void* d_out, hipStream_t s,
+                 size_t shift) {
+  if (shift && shift + n > srs->n) { set_error("msm_many: points [%zu, %zu) past the handle's %zu", shift, shift + n, srs->n); return MZK_E_LENGTH; }
+  if (srs->d_direct)      // D[(w n + i) 2^(c-1) + m]: point i's multiples are 2^(c-1) records of 64 bytes
+    return msm_direct_many_dev_impl(d_scalars, n, stride_elems, count, (const char*)srs->d_direct + shift * ((size_t)1 << (srs->direct_bits - 1)) * 64,
+                                    srs->direct_bits, srs->n, d_out, s);
   if (n >= MANY_WIDE_FROM && srs->has_tables && srs->sets == 1 && srs->window_bits < MANY_WIDE_BITS) {
     if (!srs->d_tables_wide && srs->wide_bits == 0) {       // once per handle: row 0 of its own tables are the prepared points
       const size_t bytes = (size_t)msm_table_windows(MANY_WIDE_BITS) * srs->n * 64;
@@ -2306,9 +2310,10 @@ int msm_many_srs(const mzk_srs* srs, const void* d_scalars, size_t n, size_t str
         if (within_budget) clear_error();
       }
     }
-    if (srs->d_tables_wide) return msm_many_dev_impl(d_scalars, n, stride_elems, count, srs->d_tables_wide, srs->wide_bits, srs->n, d_out, s);
+    if (srs->d_tables_wide)
+      return msm_many_dev_impl(d_scalars, n, stride_elems, count, (const char*)srs->d_tables_wide + shift * 64, srs->wide_bits, srs->n, d_out, s);
   }
-  return msm_many_dev_impl(d_scalars, n, stride_elems, count, srs->d_points_mont, srs->window_bits, srs->n, d_out, s);
+  return msm_many_dev_impl(d_scalars, n, stride_elems, count, (const char*)srs->d_points_mont + shift * 64, srs->window_bits, srs->n, d_out, s);
 }
 
 int msm_fold_partials_impl(const void* d_partials, int count, void* d_out_xy, hipStream_t s) {

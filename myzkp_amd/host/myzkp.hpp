@@ -19,6 +19,7 @@
 //   Merkle::commit / open, commit_codeword   algebra/merkle.rs:15-46, zkstark/fri.rs:160-166
 //   fri_split_and_fold, fri_commit           zkstark/fri.rs:144-209
 //   FriProof, fri_prove                      zkstark/fri.rs:71-143      -> mzk_fri_prove
+//   batch::split_and_fold / commit_gemini / open_gemini / prove_sumcheck   algebra/gemini.rs:51-144, algebra/sumcheck.rs:128-167
 //
 // Values are held canonical (u64 limbs) -- the ABI wire format; arithmetic on single elements that the
 // reference does on the host (a handful of scalar ops in tests) is not offered here: this header only
@@ -626,6 +627,117 @@ template <class F> std::vector<F> ntt_multi(const F& primitive_root, const std::
   std::vector<uint64_t> out(in.size());
   expect(mzk_ntt_multi(Polynomial<F>::field_id(), primitive_root.value.data(), in.data(), out.data(), values.size(), inverse ? 1 : 0));
   return from_wire<F>(out, values.size());
+}
+
+// ---- Gemini and sum-check (algebra/gemini.rs, algebra/sumcheck.rs) over a device-resident SRS -----------------------------
+// split_and_fold (gemini.rs:51-100) -> mzk_gemini_split_fold: the el + 1 fold levels, f_0 = coef, last = [mu]
+inline std::vector<Polynomial<FqOrder>> split_and_fold(const std::vector<FqOrder>& coef, const std::vector<FqOrder>& rhos) {
+  const size_t n = coef.size();
+  auto c = to_wire(coef), r = to_wire(rhos);
+  std::vector<uint64_t> out((2 * n + 1) * 4);
+  expect(mzk_gemini_split_fold(c.data(), n, r.data(), rhos.size(), out.data()));
+  std::vector<Polynomial<FqOrder>> fs;
+  for (size_t len = n, at = 0; len >= 1; at += len, len /= 2) {
+    std::vector<uint64_t> w(out.begin() + 4 * at, out.begin() + 4 * (at + len));
+    fs.push_back(Polynomial<FqOrder>{from_wire<FqOrder>(w, len)});
+  }
+  return fs;
+}
+static inline std::vector<uint64_t> levels_to_wire(const std::vector<Polynomial<FqOrder>>& polys, size_t* n) {
+  *n = polys.empty() ? 0 : polys[0].coef.size();
+  std::vector<uint64_t> w;
+  size_t len = *n;
+  for (auto& p : polys) {             // every level at its full length 2^(el - i) (trailing zeros included)
+    if (p.coef.size() > len) throw Panic(MZK_E_ARG, "gemini: the levels of split_and_fold are expected");
+    auto c = to_wire(p.coef);
+    c.resize(len * 4, 0);
+    w.insert(w.end(), c.begin(), c.end());
+    len /= 2;
+  }
+  return w;
+}
+// commit_gemini (gemini.rs:112-114) -> mzk_gemini_commit_srs
+inline std::vector<CommitmentKZG> commit_gemini(const std::vector<Polynomial<FqOrder>>& polys, const SrsHandle& srs) {
+  size_t n;
+  auto w = levels_to_wire(polys, &n);
+  std::vector<uint64_t> xy(8 * polys.size());
+  expect(mzk_gemini_commit_srs(srs.h, w.data(), n, xy.data()));
+  std::vector<CommitmentKZG> out(polys.size());
+  for (size_t i = 0; i < polys.size(); i++) out[i] = G1Point::from_wire(&xy[8 * i]);
+  return out;
+}
+struct ProofGemini { std::vector<BatchProofKZG> es; std::vector<G1Point> degree_proofs; };   // gemini.rs:107-110
+static inline ProofGemini gemini_from_wire(size_t el, const std::vector<uint64_t>& ys, const std::vector<uint64_t>& ws, const std::vector<uint64_t>& deg) {
+  ProofGemini pr;
+  for (size_t i = 0; i < el; i++) {
+    BatchProofKZG b;
+    for (int k = 0; k < 3; k++) { FqOrder y; std::memcpy(y.value.data(), &ys[12 * i + 4 * k], 32); b.ys.push_back(y); }
+    b.w = G1Point::from_wire(&ws[8 * i]);
+    pr.es.push_back(b);
+  }
+  for (size_t i = 0; i <= el; i++) pr.degree_proofs.push_back(G1Point::from_wire(&deg[8 * i]));
+  return pr;
+}
+// open_gemini (gemini.rs:116-144) -> mzk_gemini_open_srs
+inline ProofGemini open_gemini(const std::vector<Polynomial<FqOrder>>& polys, const FqOrder& beta, const SrsHandle& srs) {
+  size_t n;
+  auto w = levels_to_wire(polys, &n);
+  const size_t el = polys.empty() ? 0 : polys.size() - 1;
+  std::vector<uint64_t> ys(12 * el + 4), ws(8 * el + 8), deg(8 * (el + 1));
+  expect(mzk_gemini_open_srs(srs.h, w.data(), n, beta.value.data(), ys.data(), ws.data(), deg.data()));
+  return gemini_from_wire(el, ys, ws, deg);
+}
+// prove_sumcheck (sumcheck.rs:128-167) for a multilinear g given by get_coefs_in_order (sumcheck.rs:97-108) -> mzk_sumcheck_prove_srs.
+// challenge(round, g): g = {A_j, B_j} of g_j(X) = A_j + B_j X for round j < el (the caller pushes the MPolynomial it builds from them to
+// its FiatShamirTransformer and samples r_j), g = nullptr for round el (beta: the reference samples it right after r_{el-1}).
+struct SumCheckProof {                     // sumcheck.rs:110-116, g_j as (A_j, B_j), plus the challenges
+  FqOrder h;
+  size_t el = 0;
+  std::vector<std::pair<FqOrder, FqOrder>> gs;
+  std::vector<FqOrder> rs;
+  FqOrder beta;
+  std::vector<CommitmentKZG> c_g;
+  ProofGemini pi;
+};
+template <class Challenge>
+SumCheckProof prove_sumcheck(const std::vector<FqOrder>& coefs, const FqOrder& h, Challenge challenge, const SrsHandle& srs) {
+  struct Ctx { Challenge* f; std::exception_ptr err; } cx{&challenge, nullptr};
+  auto tramp = [](void* user, int round, const uint64_t* g, uint64_t* r_out) -> int {
+    auto* c = static_cast<Ctx*>(user);
+    try {
+      FqOrder gg[2];
+      if (g) { std::memcpy(gg[0].value.data(), g, 32); std::memcpy(gg[1].value.data(), g + 4, 32); }
+      const FqOrder r = (*c->f)(round, g ? gg : nullptr);
+      std::memcpy(r_out, r.value.data(), 32);
+      return 0;
+    } catch (...) {
+      c->err = std::current_exception();
+      return 1;
+    }
+  };
+  const size_t n = coefs.size();
+  size_t el = 0;
+  while (((size_t)1 << el) < n) el++;
+  const size_t k = el ? el : 1;
+  auto c = to_wire(coefs);
+  std::vector<uint64_t> gs(8 * k), rs(4 * k), beta(4), commits(8 * (el + 1)), ys(12 * k), ws(8 * k), deg(8 * (el + 1));
+  const int rc = mzk_sumcheck_prove_srs(srs.h, c.data(), n, +tramp, &cx, gs.data(), rs.data(), beta.data(), commits.data(), ys.data(), ws.data(),
+                                        deg.data());
+  if (cx.err) std::rethrow_exception(cx.err);
+  expect(rc);
+  SumCheckProof pr;
+  pr.h = h;
+  pr.el = el;
+  for (size_t j = 0; j < el; j++) {
+    FqOrder a, b, r;
+    std::memcpy(a.value.data(), &gs[8 * j], 32); std::memcpy(b.value.data(), &gs[8 * j + 4], 32); std::memcpy(r.value.data(), &rs[4 * j], 32);
+    pr.gs.emplace_back(a, b);
+    pr.rs.push_back(r);
+  }
+  std::memcpy(pr.beta.value.data(), beta.data(), 32);
+  for (size_t i = 0; i <= el; i++) pr.c_g.push_back(G1Point::from_wire(&commits[8 * i]));
+  pr.pi = gemini_from_wire(el, ys, ws, deg);
+  return pr;
 }
 
 }  // namespace batch
