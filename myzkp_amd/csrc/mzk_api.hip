@@ -1397,6 +1397,7 @@ int mzk_kzg_open_srs_dev(const mzk_srs* srs, const void* d_coef, size_t n, const
   if (!srs) { set_error("open_srs_dev: null srs"); return MZK_E_ARG; }
   MZK_TRY(srs_check_ctx(srs));
   if (n > 1 && n - 1 > srs->n) { set_error("index out of bounds: the len is %zu but the index is %zu", srs->n, srs->n); return MZK_E_LENGTH; }
+  if (!d_w_xy) { set_error("kzg_open: null pointer"); return MZK_E_ARG; }
   return kzg_open_dev(d_coef, n, u_host, srs->d_points_mont, srs->kind(), srs->n, d_y, d_w_xy, nullptr, (hipStream_t)stream);
 }
 int mzk_kzg_setup_g1_dev(const uint64_t alpha_host[4], const uint64_t g1_xy_host[8], size_t max_d, void* d_powers_xy, void* stream) {
@@ -1414,15 +1415,14 @@ int mzk_kzg_open_quotient_dev(const void* d_coef, size_t n, const uint64_t u_hos
   MZK_ENTER();
   WsGuard wsg((hipStream_t)stream);
   if (!d_q && n > 1) { set_error("open_quotient: null pointer"); return MZK_E_ARG; }
-  int dummy;
-  return kzg_open_dev(d_coef, n, u_host, nullptr, MSM_PTS_PLAIN, 0, d_y, nullptr, d_q ? d_q : (void*)&dummy, (hipStream_t)stream);
+  return kzg_open_dev(d_coef, n, u_host, nullptr, MSM_PTS_PLAIN, 0, d_y, nullptr, d_q, (hipStream_t)stream);
 }
 int mzk_kzg_open_slice_value_dev(const void* d_coef_slice, size_t len, const uint64_t u_host[4], void* d_value, void* stream) {
   MZK_ENTER();
   WsGuard wsg((hipStream_t)stream);
   if (!d_value || !u_host || (!d_coef_slice && len)) { set_error("open_slice_value: null pointer"); return MZK_E_ARG; }
   // the slice's own recurrence with nothing behind it: b_lo = the slice as a polynomial, evaluated at u (kzg_open_dev's y)
-  return kzg_open_dev(d_coef_slice, len, u_host, nullptr, MSM_PTS_PLAIN, 0, d_value, nullptr, nullptr, (hipStream_t)stream, true);
+  return kzg_open_dev(d_coef_slice, len, u_host, nullptr, MSM_PTS_PLAIN, 0, d_value, nullptr, nullptr, (hipStream_t)stream);
 }
 int mzk_kzg_open_slice_quotient_dev(const void* d_coef_slice, size_t len, const uint64_t u_host[4], const uint64_t carry_in[4], void* d_q_slice,
                                     void* stream) {
@@ -1432,17 +1432,12 @@ int mzk_kzg_open_slice_quotient_dev(const void* d_coef_slice, size_t len, const 
   if (!u_host || !carry_in || ((!d_coef_slice || !d_q_slice) && len)) { set_error("open_slice_quotient: null pointer"); return MZK_E_ARG; }
   if (!h_is_canonical(host_field(MZK_FIELD_FR), carry_in)) { set_error("open_slice_quotient: carry not canonical"); return MZK_E_RANGE; }
   if (len == 0) return MZK_OK;
-  // b over the slice with b_hi = carry is the plain recurrence over the len + 1 coefficients (slice, carry): the copy's last element
-  // b_len = carry, b_{len-1} = c_{len-1} + u carry, ...; its quotient output b_1 .. b_len is the slice of q
-  void* ext;
-  MZK_TRY(ws_get(WS_MISC_E, (len + 1) * 32, &ext));
-  MZK_HIP(hipMemcpyAsync(ext, d_coef_slice, len * 32, hipMemcpyDeviceToDevice, s));
-  MZK_HIP(hipMemcpyAsync((uint8_t*)ext + len * 32, carry_in, 32, hipMemcpyHostToDevice, s));
-  void* d_y;
-  MZK_TRY(ws_get(WS_MISC_F, 64, &d_y));
-  MZK_TRY(kzg_open_dev(ext, len + 1, u_host, nullptr, MSM_PTS_PLAIN, 0, d_y, nullptr, d_q_slice, s));
-  MZK_HIP(hipStreamSynchronize(s));           // carry_in is the caller's host memory: read until here
-  return MZK_OK;
+  if (!h_is_canonical(host_field(MZK_FIELD_FR), u_host)) { set_error("kzg_open: u not canonical"); return MZK_E_RANGE; }
+  // b over the slice from b_len = carry: one division whose end is the carry (read into the job table here); its quotient
+  // b_1 .. b_len is the slice of q
+  const SdJob job = {d_coef_slice, len, u_host, carry_in, nullptr, d_q_slice};
+  const size_t one = 1;
+  return synth_div_dev(&job, &one, 1, s);
 }
 int mzk_srs_from_device(const void* d_powers_xy, size_t n, mzk_srs** out, void* stream) {
   return mzk_srs_from_device_ex(d_powers_xy, n, 1, out, stream);

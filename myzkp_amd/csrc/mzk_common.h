@@ -252,7 +252,14 @@ int selftest_field_asm_impl(int fid, uint64_t seed, size_t n, uint64_t* mismatch
 int selftest_copy_impl(const void* d_src, void* d_dst, size_t bytes, hipStream_t s);
 int kzg_setup_g1_dev(const uint64_t* alpha_host, const uint64_t* g1_host, size_t first, size_t count, void* d_powers_xy, hipStream_t s);
 int kzg_open_dev(const void* d_coef, size_t n, const uint64_t* u_host, const void* d_points, int point_kind, size_t table_stride,
-                 void* d_y, void* d_w_xy, void* d_q_out, hipStream_t s, bool value_only = false);
+                 void* d_y, void* d_w_xy, void* d_q, hipStream_t s);
+// Synthetic division by (X - u) over BN254 Fr (mzk_kzg.hip): b_len = *end (0 when end is null),
+// b_t = src[t] + u b_{t+1}; y = b_0, q = b_1 .. b_{len-1}, or b_1 .. b_len with an end.  u and end are canonical host values;
+// y and q are device outputs or null; a job of length 0 writes nothing.
+struct SdJob { const void* src; size_t len; const uint64_t* u; const uint64_t* end; void* y; void* q; };
+// rounds[r] consecutive jobs form round r; the jobs of a round are independent, a later round may read what an earlier one wrote.
+// Workspace: WS_MISC_C (the job table) and WS_MISC_D (chunk values and carries).
+int synth_div_dev(const SdJob* jobs, const size_t* rounds, int nrounds, hipStream_t s);
 
 }  // namespace mzk
 

@@ -11,11 +11,8 @@
 //   k_gm_fold_lds    every level from FOLD_LDS_IN elements down, in LDS, in one launch;
 //   k_gm_sums        weighted sums over a level (sum_over_boolean_hypercube, and the sum-check round messages A_j / B_j),
 //                    optionally fused with the fold that produces the level (one pass over the data per round);
-//   k_sh_eval / k_sh_scan / k_sh_fill
-//                    suffix Horner b_t = c_t + u b_{t+1} for a TABLE of (polynomial, point) jobs at once: chunk values, one
-//                    workgroup per job scans the chunk values, chunk fill.  b_0 = f(u), b_1.. = the quotient by (X - u).
-//                    Gemini's evaluations at beta, -beta, beta^2 and its quotients by (X - beta)(X + beta)(X - beta^2) of
-//                    every level are three such rounds (nine launches whatever el is).
+// Gemini's evaluations at beta, -beta, beta^2 and its quotients by (X - beta)(X + beta)(X - beta^2) of every level are three rounds
+// of the library's synthetic division (synth_div_dev, mzk_kzg.hip).
 // The MSMs run on the SRS handle's tables (mzk_msm.hip); the degree-bound MSMs of prove_degree_bound (kzg.rs:121-134) on the
 // handle entered max_d - d rows further on (see gemini_open_impl).
 #include "mzk_common.h"
@@ -259,133 +256,6 @@ static int gm_sums(const void* d_f, size_t count, const uint64_t* r_host, void* 
   return MZK_OK;
 }
 
-// ---- batched suffix Horner ------------------------------------------------------------------------------------------
-constexpr int SH_K_LOG = 5;
-constexpr size_t SH_K = (size_t)1 << SH_K_LOG;   // elements per chunk (one lane's serial Horner)
-constexpr int SH_SCAN_THREADS = 256;
-struct ShJob {
-  const u32* src;   // len coefficients
-  u32* dst;         // the quotient b_1 .. b_{len-1} (len - 1 elements), or null
-  u32* y;           // b_0 = src(u), or null
-  u64 len;
-  u64 chunk0;       // first chunk of this job in the flat chunk arrays
-  u32 u[8];         // u R
-  u32 uk[8];        // u^K R
-};
-__device__ __forceinline__ int sh_job_of(const ShJob* __restrict__ jobs, int njobs, u64 g) {
-  int lo = 0, hi = njobs - 1;     // last job with chunk0 <= g
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) >> 1;
-    if (jobs[mid].chunk0 <= g) lo = mid; else hi = mid - 1;
-  }
-  return lo;
-}
-// h[chunk] = sum_{t in chunk} c[t] u^(t - lo)
-__global__ __launch_bounds__(64) void k_sh_eval(const ShJob* __restrict__ jobs, int njobs, u64 nchunks, u32* __restrict__ h) {
-  const u64 g = (u64)blockIdx.x * blockDim.x + threadIdx.x;
-  if (g >= nchunks) return;
-  const ShJob& J = jobs[sh_job_of(jobs, njobs, g)];
-  const u64 lo = (g - J.chunk0) << SH_K_LOG;
-  const u64 hi = (lo + SH_K < J.len) ? lo + SH_K : J.len;
-  const GE u = fe_unpack<GP>(J.u);
-  GE acc = gm_load(J.src, hi - 1);
-  for (u64 t = hi - 1; t-- > lo;) acc = fe_add<GP>(fe_mul<GP>(acc, u), gm_load(J.src, t));
-  gm_store(h, g, fe_reduce<GP>(acc));
-}
-// one workgroup per job: carry[m] = sum_{m' >= m} h[m'] (u^K)^(m' - m) = b_{m K}; y = carry[0]
-__global__ __launch_bounds__(SH_SCAN_THREADS) void k_sh_scan(const ShJob* __restrict__ jobs, const u32* __restrict__ h, u32* __restrict__ carry) {
-  __shared__ u32 S[SH_SCAN_THREADS][GP::L];
-  const ShJob& J = jobs[blockIdx.x];
-  const int L = threadIdx.x;
-  const u64 nh = (J.len + SH_K - 1) >> SH_K_LOG;
-  const u32* hj = h + 8 * J.chunk0;
-  u32* cj = carry + 8 * J.chunk0;
-  const GE uk = fe_unpack<GP>(J.uk);
-  const u64 K2 = (nh + SH_SCAN_THREADS - 1) / SH_SCAN_THREADS;
-  const u64 lo = (u64)L * K2;
-  const u64 hi = (lo + K2 < nh) ? lo + K2 : nh;
-  GE mine = fe_zero<GP>();
-  if (lo < nh) {
-    mine = gm_load(hj, hi - 1);
-    for (u64 t = hi - 1; t-- > lo;) mine = fe_add<GP>(fe_mul<GP>(mine, uk), gm_load(hj, t));
-    mine = fe_reduce<GP>(mine);
-  }
-  GE pw = fe_one<GP>(), b = uk;                              // (u^K)^K2 R
-  for (u64 k = K2; k; k >>= 1) {
-    if (k & 1) pw = fe_mul<GP>(pw, b);
-    b = fe_sqr<GP>(b);
-  }
-#pragma unroll
-  for (int i = 0; i < GP::L; i++) S[L][i] = mine.l[i];
-  for (int d = 1; d < SH_SCAN_THREADS; d <<= 1) {
-    __syncthreads();
-    GE other = fe_zero<GP>();
-    if (L + d < SH_SCAN_THREADS) {
-#pragma unroll
-      for (int i = 0; i < GP::L; i++) other.l[i] = S[L + d][i];
-    }
-    __syncthreads();
-    mine = fe_reduce<GP>(fe_add<GP>(mine, fe_mul<GP>(other, pw)));
-#pragma unroll
-    for (int i = 0; i < GP::L; i++) S[L][i] = mine.l[i];
-    pw = fe_sqr<GP>(pw);
-  }
-  __syncthreads();
-  if (lo >= nh) return;
-  GE acc = fe_zero<GP>();
-  if (L + 1 < SH_SCAN_THREADS) {
-#pragma unroll
-    for (int i = 0; i < GP::L; i++) acc.l[i] = S[L + 1][i];
-  }
-  for (u64 t = hi; t-- > lo;) {
-    acc = fe_reduce<GP>(fe_add<GP>(fe_mul<GP>(acc, uk), gm_load(hj, t)));
-    gm_store(cj, t, acc);
-  }
-  if (L == 0 && J.y) gm_store(J.y, 0, acc);
-}
-// b[t] = c[t] + u b[t+1] inside each chunk from the carry of the next chunk; the quotient is b[1..len)
-__global__ __launch_bounds__(64) void k_sh_fill(const ShJob* __restrict__ jobs, int njobs, u64 nchunks, const u32* __restrict__ carry) {
-  const u64 g = (u64)blockIdx.x * blockDim.x + threadIdx.x;
-  if (g >= nchunks) return;
-  const ShJob& J = jobs[sh_job_of(jobs, njobs, g)];
-  if (!J.dst) return;
-  const u64 m = g - J.chunk0;
-  const u64 lo = m << SH_K_LOG;
-  const u64 hi = (lo + SH_K < J.len) ? lo + SH_K : J.len;
-  const GE u = fe_unpack<GP>(J.u);
-  GE acc = (hi < J.len) ? gm_load(carry, g + 1) : fe_zero<GP>();
-  for (u64 t = hi; t-- > lo;) {
-    acc = fe_reduce<GP>(fe_add<GP>(fe_mul<GP>(acc, u), gm_load(J.src, t)));
-    if (t > 0) gm_store(J.dst, t - 1, acc);
-  }
-}
-struct ShRound {
-  std::vector<ShJob> jobs;
-  u64 nchunks = 0;
-  void add(const void* src, size_t len, const GmW8& u, const GmW8& uk, void* dst, void* y) {
-    if (len == 0) return;
-    ShJob j;
-    j.src = (const u32*)src; j.dst = (u32*)dst; j.y = (u32*)y; j.len = len; j.chunk0 = nchunks;
-    memcpy(j.u, u.w, 32); memcpy(j.uk, uk.w, 32);
-    jobs.push_back(j);
-    nchunks += (len + SH_K - 1) >> SH_K_LOG;
-  }
-};
-// d_jobs: room for the table; h, carry: nchunks elements each
-static int sh_run(const ShRound& R, ShJob* d_jobs, u32* h, u32* carry, hipStream_t s) {
-  if (R.jobs.empty()) return MZK_OK;
-  MZK_HIP(hipMemcpyAsync(d_jobs, R.jobs.data(), R.jobs.size() * sizeof(ShJob), hipMemcpyHostToDevice, s));
-  const int nj = (int)R.jobs.size();
-  const unsigned grid = (unsigned)((R.nchunks + 63) / 64);
-  hipLaunchKernelGGL(k_sh_eval, dim3(grid), dim3(64), 0, s, (const ShJob*)d_jobs, nj, R.nchunks, h);
-  hipLaunchKernelGGL(k_sh_scan, dim3(nj), dim3(SH_SCAN_THREADS), 0, s, (const ShJob*)d_jobs, (const u32*)h, carry);
-  bool fill = false;
-  for (const ShJob& j : R.jobs) fill |= j.dst != nullptr;
-  if (fill) hipLaunchKernelGGL(k_sh_fill, dim3(grid), dim3(64), 0, s, (const ShJob*)d_jobs, nj, R.nchunks, (const u32*)carry);
-  MZK_HIP(hipGetLastError());
-  return MZK_OK;
-}
-
 // ---- MSM schedule ---------------------------------------------------------------------------------------------------
 // Levels of at most GM_SMALL coefficients go through ONE grid-batched pass per kind (commitments, quotients, degree bounds)
 // when the handle has a grid-batched path (srs_many_capable: direct tables, or narrow 8 / 10..13-bit tables with one bucket
@@ -502,38 +372,35 @@ static int gemini_open_impl(const mzk_srs* srs, const void* d_levels, size_t n, 
     set_error("gemini_open: beta, -beta and beta^2 must be distinct (beta in {0, 1, -1}: interpolate divides by zero)");
     return MZK_E_ARG;
   }
-  // evaluations and quotients: three rounds of suffix Horner over every level i < el
+  // evaluations and quotients: three rounds of synthetic division over every level i < el
   size_t qtot = 0;
   for (int i = 0; i < el; i++) qtot += n >> i;
-  u32 *qa = nullptr, *qb = nullptr, *hc = nullptr;
-  ShJob* d_jobs = nullptr;
+  u32 *qa = nullptr, *qb = nullptr;
   if (el > 0) {
-    GmW8 ub, ubk, un, unk, u2, u2k;
-    uint64_t t[4];
-    gm_mont(beta, &ub); h_powmod_u64(fr, t, beta, SH_K); gm_mont(t, &ubk);
-    gm_mont(nb, &un); h_powmod_u64(fr, t, nb, SH_K); gm_mont(t, &unk);
-    gm_mont(b2, &u2); h_powmod_u64(fr, t, b2, SH_K); gm_mont(t, &u2k);
-    ShRound A, B, C;
-    size_t qoff = 0;
     MZK_TRY(ws_get(WS_MISC_A, qtot * 32, (void**)&qa));
     MZK_TRY(ws_get(WS_MISC_B, qtot * 32, (void**)&qb));
-    for (int i = 0; i < el; i++) {
-      const size_t len = n >> i;
-      const char* f = (const char*)d_levels + gm_level_off(n, i) * 32;
-      char* y = (char*)d_ys + (size_t)i * 96;
-      A.add(f, len, ub, ubk, qa + 8 * qoff, y);              // q1 = f / (X - beta), f(beta)
-      A.add(f, len, un, unk, nullptr, y + 32);                // f(-beta)
-      A.add(f, len, u2, u2k, nullptr, y + 64);                // f(beta^2)
-      B.add(qa + 8 * qoff, len - 1, un, unk, qb + 8 * qoff, nullptr);              // q2 = q1 / (X + beta)
-      if (len >= 2) C.add(qb + 8 * qoff, len - 2, u2, u2k, qa + 8 * qoff, nullptr);  // q3 = q2 / (X - beta^2): len - 3 elements
-      qoff += len;
+    // round A: every level at beta (quotient q1 kept), at -beta and at beta^2 (values); round B: q2 = q1 / (X + beta); round C:
+    // q3 = q2 / (X - beta^2), len - 3 elements.  Grouped by point: the engine's host powers of u are per run of equal points.
+    std::vector<SdJob> jobs;
+    for (int p = 0; p < 5; p++) {
+      size_t qoff = 0;
+      for (int i = 0; i < el; i++) {
+        const size_t len = n >> i;
+        const char* f = (const char*)d_levels + gm_level_off(n, i) * 32;
+        char* y = (char*)d_ys + (size_t)i * 96;
+        u32 *q1 = qa + 8 * qoff, *q2 = qb + 8 * qoff;
+        switch (p) {
+          case 0: jobs.push_back({f, len, beta, nullptr, y, q1}); break;
+          case 1: jobs.push_back({f, len, nb, nullptr, y + 32, nullptr}); break;
+          case 2: jobs.push_back({f, len, b2, nullptr, y + 64, nullptr}); break;
+          case 3: jobs.push_back({q1, len - 1, nb, nullptr, nullptr, q2}); break;
+          default: jobs.push_back({q2, len - 2, b2, nullptr, nullptr, q1}); break;
+        }
+        qoff += len;
+      }
     }
-    MZK_TRY(ws_get(WS_MISC_C, A.jobs.size() * sizeof(ShJob) * 3, (void**)&d_jobs));
-    MZK_TRY(ws_get(WS_MISC_D, A.nchunks * 64, (void**)&hc));
-    // three tables side by side: a later round's upload must not overwrite a table an earlier round's kernels still read
-    MZK_TRY(sh_run(A, d_jobs, hc, hc + 8 * A.nchunks, s));
-    MZK_TRY(sh_run(B, d_jobs + A.jobs.size(), hc, hc + 8 * B.nchunks, s));
-    MZK_TRY(sh_run(C, d_jobs + 2 * A.jobs.size(), hc, hc + 8 * C.nchunks, s));
+    const size_t rounds[3] = {3 * (size_t)el, (size_t)el, (size_t)el};
+    MZK_TRY(synth_div_dev(jobs.data(), rounds, 3, s));
   }
   // w_i = MSM(q3_i, powers[0, len - 3))
   GmMsm it[GM_MAX_LOG + 1];

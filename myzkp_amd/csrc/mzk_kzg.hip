@@ -266,10 +266,29 @@ int kzg_setup_g1_dev(const uint64_t* alpha_host, const uint64_t* g1_host, size_t
   return xyzz_batch_to_affine(acc, count, d_powers_xy, false, s);
 }
 
-// ---- open: suffix Horner b_i = c_i + u b_{i+1} -----------------------------------------------------------
-constexpr int OPEN_K_LOG = 5;   // chunk = 32: the per-lane recurrence is a serial chain, so short chunks (more levels, all tiny) win
-constexpr size_t OPEN_K = (size_t)1 << OPEN_K_LOG;
+// ---- synthetic division by (X - u): the one engine behind every opening --------------------------------------------------
+// b_len = end (0 without one), b_t = c_t + u b_{t+1}; y = b_0, q = b_1 .. b_{len-1}, or b_1 .. b_len with an end.
+// A round whose longest job has at most SD_BLOCK_MAX coefficients is one launch of k_sd_block, one workgroup per job.  Otherwise
+// every job is cut into chunks of SD_K: k_sd_eval gives each chunk's value at u (the end folded into the last chunk), the same
+// division one level up on those values at u^SD_K yields b at every chunk start, and k_sd_fill rebuilds each chunk from b at the
+// start of the next.  b_0 is the same value at every level, so y comes from the top level; a job without q needs no fill.
+constexpr int SD_K_LOG = 5;                       // chunk of 32: the per-lane recurrence is a serial chain, short chunks win
+constexpr size_t SD_K = (size_t)1 << SD_K_LOG;
+// one workgroup per job up to 2^13: every doubling doubles each lane's serial chain (a single opening of 2^12: 0.042 ms, 2^13: 0.064),
+// while 2^14 through one chunk level takes 0.074
+constexpr size_t SD_BLOCK_MAX = (size_t)1 << 13;
+constexpr int SD_THREADS = 256;
 typedef Fe<FrParams> FrE;
+struct SdRec {          // one job of one level, as the kernels read it
+  const u32* src;       // len coefficients
+  u32* q;               // b_1 .., or null
+  u32* y;               // b_0, or null
+  u64 len;
+  u64 chunk0;           // first chunk of this job in its level's chunk arrays
+  u32 u[8];             // canonical
+  u32 end[8];           // b_len, canonical
+  u32 has_end;          // q also gets b_len
+};
 __device__ __forceinline__ FrE fr_gload(const u32* __restrict__ g, size_t i) {
   u32 w[8];
   ld8(g + 8 * i, w);
@@ -280,78 +299,191 @@ __device__ __forceinline__ void fr_gstore(u32* __restrict__ g, size_t i, const F
   fe_pack<FrParams>(v, w);
   st8(g + 8 * i, w);
 }
-// h[m] = sum_{t in chunk m} c[t] u^(t - m K)
-__global__ __launch_bounds__(64) void k_open_chunk_eval(const u32* __restrict__ c, size_t n, Words8k u_mont, u32* __restrict__ h) {
-  const size_t m = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const size_t lo = m << OPEN_K_LOG;
-  if (lo >= n) return;
-  const size_t hi = (lo + OPEN_K < n) ? lo + OPEN_K : n;
-  const FrE u = fe_unpack<FrParams>(u_mont.w);
-  FrE acc = fr_gload(c, hi - 1);
-  for (size_t t = hi - 1; t-- > lo;) acc = fe_add<FrParams>(fe_mul<FrParams>(acc, u), fr_gload(c, t));
-  fr_gstore(h, m, fe_reduce<FrParams>(acc));
+// b_lo from b_hi = acc over the coefficients [lo, hi); u in Montgomery form (fe_mul(x, u R) = x u)
+__device__ __forceinline__ FrE sd_horner(const u32* __restrict__ c, u64 lo, u64 hi, const FrE& u, FrE acc) {
+  for (u64 t = hi; t-- > lo;) acc = fe_add<FrParams>(fe_mul<FrParams>(acc, u), fr_gload(c, t));
+  return fe_reduce<FrParams>(acc);
 }
-// b[t] = c[t] + u b[t+1] inside chunk m, with b[(m+1) K] = carry[m+1] (0 past the end)
-__global__ __launch_bounds__(64) void k_open_chunk_fill(const u32* __restrict__ c, size_t n, Words8k u_mont, const u32* __restrict__ carry,
-                                                         size_t ncarry, u32* __restrict__ b) {
-  const size_t m = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const size_t lo = m << OPEN_K_LOG;
-  if (lo >= n) return;
-  const size_t hi = (lo + OPEN_K < n) ? lo + OPEN_K : n;
-  const FrE u = fe_unpack<FrParams>(u_mont.w);
-  FrE acc = (carry != nullptr && m + 1 < ncarry) ? fr_gload(carry, m + 1) : fe_zero<FrParams>();
-  for (size_t t = hi; t-- > lo;) {
-    acc = fe_reduce<FrParams>(fe_add<FrParams>(fe_mul<FrParams>(acc, u), fr_gload(c, t)));
-    fr_gstore(b, t, acc);
+// b_hi-1 .. b_lo from b_hi = acc into q (b_t at q[t - 1]; b_0 is y's)
+__device__ __forceinline__ void sd_fill(const SdRec& J, u64 lo, u64 hi, const FrE& u, FrE acc) {
+  if (hi == J.len && J.has_end) fr_gstore(J.q, hi - 1, acc);
+  for (u64 t = hi; t-- > lo;) {
+    acc = fe_reduce<FrParams>(fe_add<FrParams>(fe_mul<FrParams>(acc, u), fr_gload(J.src, t)));
+    if (t > 0) fr_gstore(J.q, t - 1, acc);
   }
+}
+// a job's values are wave-uniform: held in VGPRs, the powers of u of the scan below do not overflow the scalar registers
+__device__ __forceinline__ FrE sd_vgpr(FrE x) {
+#pragma unroll
+  for (int i = 0; i < FrParams::L; i++) asm volatile("" : "+v"(x.l[i]));
+  return x;
+}
+// one workgroup per job: lane L owns the K = ceil(len / 256) coefficients [L K, (L + 1) K); the lanes' chunk values are scanned
+// with u^K, u^2K, ... through LDS, so S[L] = b_{L K}; then every lane fills its chunk from S[L + 1]
+__global__ __launch_bounds__(SD_THREADS) void k_sd_block(const SdRec* __restrict__ jobs) {
+  typedef FrParams P;
+  __shared__ u32 S[SD_THREADS][P::L];
+  const SdRec& J = jobs[blockIdx.x];
+  const int L = threadIdx.x;
+  const u64 n = J.len;
+  const FrE u = sd_vgpr(fe_to_mont<P>(fe_unpack<P>(J.u))), end = sd_vgpr(fe_unpack<P>(J.end));
+  const u64 K = (n + SD_THREADS - 1) / SD_THREADS;
+  const u64 lo = (u64)L * K;
+  const u64 hi = (lo + K < n) ? lo + K : n;
+  FrE mine = fe_zero<P>();
+  if (lo < n) mine = sd_horner(J.src, lo, hi, u, hi == n ? end : fe_zero<P>());
+  FrE pw = fe_one<P>(), base = u;                           // u^K in Montgomery form
+  for (u64 k = K; k; k >>= 1) {
+    if (k & 1) pw = fe_mul<P>(pw, base);
+    base = fe_sqr<P>(base);
+  }
+#pragma unroll
+  for (int i = 0; i < P::L; i++) S[L][i] = mine.l[i];
+  for (int d = 1; d < SD_THREADS; d <<= 1) {
+    __syncthreads();
+    FrE other = fe_zero<P>();
+    if (L + d < SD_THREADS) {
+#pragma unroll
+      for (int i = 0; i < P::L; i++) other.l[i] = S[L + d][i];
+    }
+    __syncthreads();
+    mine = fe_reduce<P>(fe_add<P>(mine, fe_mul<P>(other, pw)));
+#pragma unroll
+    for (int i = 0; i < P::L; i++) S[L][i] = mine.l[i];
+    pw = fe_sqr<P>(pw);
+  }
+  if (L == 0 && J.y) fr_gstore(J.y, 0, mine);
+  __syncthreads();
+  if (!J.q || lo >= n) return;
+  FrE acc = end;                                            // b_hi
+  if (hi < n) {
+#pragma unroll
+    for (int i = 0; i < P::L; i++) acc.l[i] = S[L + 1][i];
+  }
+  sd_fill(J, lo, hi, u, acc);
+}
+__device__ __forceinline__ int sd_job_of(const SdRec* __restrict__ jobs, int njobs, u64 g) {
+  int lo = 0, hi = njobs - 1;     // last job with chunk0 <= g
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (jobs[mid].chunk0 <= g) lo = mid; else hi = mid - 1;
+  }
+  return lo;
+}
+// h[g] = the value of chunk g at u, from b = end behind the job's last chunk
+__global__ __launch_bounds__(64) void k_sd_eval(const SdRec* __restrict__ jobs, int njobs, u64 nchunks, u32* __restrict__ h) {
+  const u64 g = (u64)blockIdx.x * blockDim.x + threadIdx.x;
+  if (g >= nchunks) return;
+  const SdRec& J = jobs[sd_job_of(jobs, njobs, g)];
+  const u64 lo = (g - J.chunk0) << SD_K_LOG;
+  const u64 hi = (lo + SD_K < J.len) ? lo + SD_K : J.len;
+  const FrE u = fe_to_mont<FrParams>(fe_unpack<FrParams>(J.u));
+  fr_gstore(h, g, sd_horner(J.src, lo, hi, u, hi == J.len ? fe_unpack<FrParams>(J.end) : fe_zero<FrParams>()));
+}
+// chunk g from b at the start of the next chunk, carry[g] (the level above wrote it as its quotient), or from the end
+__global__ __launch_bounds__(64) void k_sd_fill(const SdRec* __restrict__ jobs, int njobs, u64 nchunks, const u32* __restrict__ carry) {
+  const u64 g = (u64)blockIdx.x * blockDim.x + threadIdx.x;
+  if (g >= nchunks) return;
+  const SdRec& J = jobs[sd_job_of(jobs, njobs, g)];
+  if (!J.q) return;
+  const u64 lo = (g - J.chunk0) << SD_K_LOG;
+  const u64 hi = (lo + SD_K < J.len) ? lo + SD_K : J.len;
+  const FrE u = fe_to_mont<FrParams>(fe_unpack<FrParams>(J.u));
+  sd_fill(J, lo, hi, u, hi == J.len ? fe_unpack<FrParams>(J.end) : fr_gload(carry, g));
 }
 
-// One synthetic division of the level-0 array `c` (n elements) by (X - u): fills b (n elements) with
-// b_i = c_i + u b_{i+1}.  Scratch: hbuf / bup hold the upper levels.
-static int suffix_horner(const u32* c, size_t n, const uint64_t* u_host, u32* b, u32* hbuf, u32* bup, hipStream_t s) {
+static void sd_words(const uint64_t* v, u32* w) {
+  for (int i = 0; i < 4; i++) { w[2 * i] = (u32)v[i]; w[2 * i + 1] = (u32)(v[i] >> 32); }
+}
+int synth_div_dev(const SdJob* jobs, const size_t* rounds, int nrounds, hipStream_t s) {
   const HostField* fr = host_field(MZK_FIELD_FR);
-  size_t lens[8];
-  int nlev = 0;
-  lens[0] = n;
-  while (lens[nlev] > OPEN_K) { lens[nlev + 1] = (lens[nlev] + OPEN_K - 1) >> OPEN_K_LOG; nlev++; }
-  Words8k um[8];
-  {
-    uint64_t ul[4] = {u_host[0], u_host[1], u_host[2], u_host[3]};
-    uint64_t two[4] = {2, 0, 0, 0}, rmod[4], t[4];
-    h_powmod_u64(fr, rmod, two, 261);
-    for (int l = 0; l <= nlev; l++) {
-      h_mulmod(fr, t, ul, rmod);
-      for (int i = 0; i < 4; i++) { um[l].w[2 * i] = (u32)t[i]; um[l].w[2 * i + 1] = (u32)(t[i] >> 32); }
-      h_powmod_u64(fr, ul, ul, OPEN_K);
+  enum { BLOCK, EVAL, FILL };
+  struct Step { int kind; size_t first, count; u64 nchunks; size_t arr; };   // arr: the level's chunk values / carries in WS_MISC_D
+  std::vector<SdRec> tab;
+  std::vector<Step> steps;
+  // The table of every round and level is built here and uploaded once: a round's kernels then never wait for a host copy, and no
+  // upload can overwrite a table that earlier kernels still read.  walk(nullptr) only measures WS_MISC_D (its records are dropped).
+  auto walk = [&](u32* D) -> size_t {
+    tab.clear();
+    steps.clear();
+    size_t need = 0, j0 = 0;
+    for (int r = 0; r < nrounds; j0 += rounds[r], r++) {
+      size_t first = tab.size();
+      std::vector<uint64_t> us;                             // plain u of the current level's records
+      bool fill = false;
+      for (size_t i = j0; i < j0 + rounds[r]; i++) {
+        const SdJob& J = jobs[i];
+        if (J.len == 0) continue;
+        SdRec x = {};
+        x.src = (const u32*)J.src; x.q = (u32*)J.q; x.y = (u32*)J.y; x.len = J.len;
+        sd_words(J.u, x.u);
+        if (J.end) { sd_words(J.end, x.end); x.has_end = 1; }
+        tab.push_back(x);
+        us.insert(us.end(), J.u, J.u + 4);
+        fill |= J.q != nullptr;                            // every level above has q where level 0 has
+      }
+      std::vector<Step> fills;
+      size_t off = 0;                                       // a round's levels reuse WS_MISC_D from 0: the rounds run in order
+      while (tab.size() > first) {
+        const size_t count = tab.size() - first;
+        u64 longest = 0, nch = 0;
+        for (size_t k = first; k < tab.size(); k++) {
+          longest = tab[k].len > longest ? tab[k].len : longest;
+          tab[k].chunk0 = nch;
+          nch += (tab[k].len + SD_K - 1) >> SD_K_LOG;
+        }
+        if (longest <= SD_BLOCK_MAX) { steps.push_back({BLOCK, first, count, 0, 0}); break; }
+        steps.push_back({EVAL, first, count, nch, off});
+        if (fill) fills.push_back({FILL, first, count, nch, off + nch});
+        // one level up: each job's chunk values at u^SD_K; its quotient (b at chunks 1, 2, ..) is this level's carries
+        std::vector<uint64_t> uk(4 * count);
+        for (size_t k = 0; k < count; k++) {
+          const SdRec b = tab[first + k];
+          SdRec x = {};
+          x.src = D ? D + 8 * (off + b.chunk0) : nullptr;
+          x.q = (D && b.q) ? D + 8 * (off + nch + b.chunk0) : nullptr;
+          x.y = b.y;
+          x.len = (b.len + SD_K - 1) >> SD_K_LOG;
+          if (D) {                                          // host powers are the call's set-up latency: once per run of equal points
+            if (k > 0 && !memcmp(&us[4 * k], &us[4 * k - 4], 32)) memcpy(&uk[4 * k], &uk[4 * k - 4], 32);
+            else h_powmod_u64(fr, &uk[4 * k], &us[4 * k], SD_K);
+            sd_words(&uk[4 * k], x.u);
+          }
+          tab.push_back(x);
+        }
+        us.swap(uk);
+        off += 2 * nch;
+        first += count;
+      }
+      need = off > need ? off : need;
+      steps.insert(steps.end(), fills.rbegin(), fills.rend());   // fills from the top level down
     }
+    return need;
+  };
+  u32* D = nullptr;
+  const size_t need = walk(nullptr);
+  if (need) {
+    MZK_TRY(ws_get(WS_MISC_D, need * 32, (void**)&D));
+    walk(D);
   }
-  const u32* level_in[8];
-  u32* level_b[8];
-  level_in[0] = c;
-  level_b[0] = b;
-  size_t off = 0;
-  for (int l = 1; l <= nlev; l++) {
-    level_in[l] = hbuf + off * 8;
-    level_b[l] = bup + off * 8;
-    off += lens[l];
-  }
-  for (int l = 0; l < nlev; l++) {
-    const size_t chunks = lens[l + 1];
-    hipLaunchKernelGGL(k_open_chunk_eval, dim3((unsigned)((chunks + 63) / 64)), dim3(64), 0, s, level_in[l], lens[l], um[l], (u32*)level_in[l + 1]);
-  }
-  for (int l = nlev; l >= 0; l--) {
-    const size_t chunks = (lens[l] + OPEN_K - 1) >> OPEN_K_LOG;
-    const u32* carry = (l == nlev) ? nullptr : level_b[l + 1];
-    hipLaunchKernelGGL(k_open_chunk_fill, dim3((unsigned)((chunks + 63) / 64)), dim3(64), 0, s, level_in[l], lens[l], um[l], carry,
-                       (l == nlev) ? (size_t)0 : lens[l + 1], level_b[l]);
+  if (tab.empty()) return MZK_OK;
+  SdRec* d_tab;
+  MZK_TRY(ws_get(WS_MISC_C, tab.size() * sizeof(SdRec), (void**)&d_tab));
+  MZK_HIP(hipMemcpyAsync(d_tab, tab.data(), tab.size() * sizeof(SdRec), hipMemcpyHostToDevice, s));
+  for (const Step& st : steps) {
+    const SdRec* jt = d_tab + st.first;
+    const unsigned grid = (unsigned)((st.nchunks + 63) / 64);
+    if (st.kind == BLOCK) hipLaunchKernelGGL(k_sd_block, dim3((unsigned)st.count), dim3(SD_THREADS), 0, s, jt);
+    else if (st.kind == EVAL) hipLaunchKernelGGL(k_sd_eval, dim3(grid), dim3(64), 0, s, jt, (int)st.count, st.nchunks, D + 8 * st.arr);
+    else hipLaunchKernelGGL(k_sd_fill, dim3(grid), dim3(64), 0, s, jt, (int)st.count, st.nchunks, (const u32*)D + 8 * st.arr);
   }
   MZK_HIP(hipGetLastError());
   return MZK_OK;
 }
 
-// batch_open_kzg (kzg.rs:74-88).  y_i = f(u_i) is b_0 of the synthetic division of f by (X - u_i).  The
-// quotient of f by prod (X - u_i) -- which equals (f - I)/Z because I = f mod Z -- is k successive synthetic
-// divisions (each drops the remainder b_0).  d_ys: k * 8 words, d_w_xy: 16 words.
+// batch_open_kzg (kzg.rs:74-88).  y_i = f(u_i) is b_0 of the division of f by (X - u_i).  The quotient of f by prod (X - u_i) --
+// which equals (f - I)/Z because I = f mod Z -- is k successive divisions (each drops the remainder b_0): one round of k
+// evaluations, then one round per quotient.  d_ys: k * 8 words, d_w_xy: 16 words.
 int kzg_batch_open_dev(const void* d_coef, size_t n, const uint64_t* us_host, size_t k, const void* d_points, int point_kind,
                        size_t table_stride, void* d_ys, void* d_w_xy, hipStream_t s) {
   if (!d_w_xy || (!d_coef && n) || ((!us_host || !d_ys) && k)) { set_error("batch_open: null pointer"); return MZK_E_ARG; }
@@ -362,167 +494,49 @@ int kzg_batch_open_dev(const void* d_coef, size_t n, const uint64_t* us_host, si
     MZK_HIP(hipMemsetAsync(d_w_xy, 0, 64, s));
     return MZK_OK;
   }
-  size_t total_up = 0;
-  for (size_t l = (n + OPEN_K - 1) >> OPEN_K_LOG; ; l = (l + OPEN_K - 1) >> OPEN_K_LOG) { total_up += l; if (l <= 1) break; }
-  u32 *bA, *bB, *hbuf, *bup;
+  u32 *bA, *bB;
   MZK_TRY(ws_get(WS_MISC_A, n * 32, (void**)&bA));
-  MZK_TRY(ws_get(WS_MISC_D, n * 32, (void**)&bB));
-  MZK_TRY(ws_get(WS_MISC_B, (total_up + 2) * 32, (void**)&hbuf));
-  MZK_TRY(ws_get(WS_MISC_C, (total_up + 2) * 32, (void**)&bup));
-  // evaluations of the ORIGINAL f
-  for (size_t i = 0; i < k; i++) {
-    MZK_TRY(suffix_horner((const u32*)d_coef, n, us_host + 4 * i, bA, hbuf, bup, s));
-    MZK_HIP(hipMemcpyAsync((char*)d_ys + 32 * i, bA, 32, hipMemcpyDeviceToDevice, s));
-  }
-  // successive quotients
-  const u32* cur = (const u32*)d_coef;
+  MZK_TRY(ws_get(WS_MISC_B, n * 32, (void**)&bB));
+  std::vector<SdJob> jobs;
+  std::vector<size_t> rounds;
+  for (size_t i = 0; i < k; i++) jobs.push_back({d_coef, n, us_host + 4 * i, nullptr, (char*)d_ys + 32 * i, nullptr});
+  rounds.push_back(k);
+  const void* cur = d_coef;
   size_t len = n;
-  u32* dst = bA;
-  for (size_t i = 0; i < k && len > 0; i++) {
-    MZK_TRY(suffix_horner(cur, len, us_host + 4 * i, dst, hbuf, bup, s));
-    cur = dst + 8;          // q_j = b_{j+1}
-    len -= 1;
-    dst = (dst == bA) ? bB : bA;
+  for (size_t i = 0; i < k && len > 0; i++, len--) {
+    u32* dst = (i & 1) ? bB : bA;
+    jobs.push_back({cur, len, us_host + 4 * i, nullptr, nullptr, dst});
+    rounds.push_back(1);
+    cur = dst;
   }
-  if (k > n) len = 0;
+  MZK_TRY(synth_div_dev(jobs.data(), rounds.data(), (int)rounds.size(), s));
   return msm_dev_impl(cur, d_points, len, point_kind, table_stride, d_w_xy, false, s);
 }
 
-// d_y: 8 words; d_w_xy: 16 words.
+// open_kzg (kzg.rs:61-72) as one division: y = f(u) into d_y (8 words); the quotient q = b_1 .. b_{n-1} into d_q when given; the
+// witness w = MSM(q, points) into d_w_xy (16 words) when given, q then in workspace unless d_q holds it.
 int kzg_open_dev(const void* d_coef, size_t n, const uint64_t* u_host, const void* d_points, int point_kind, size_t table_stride,
-                 void* d_y, void* d_w_xy, void* d_q_out, hipStream_t s, bool value_only) {
-  if (!u_host || !d_y || (!d_w_xy && !d_q_out && !value_only) || (!d_coef && n) || (!d_points && n > 1 && !d_q_out && !value_only)) { set_error("kzg_open: null pointer"); return MZK_E_ARG; }
-  const HostField* fr = host_field(MZK_FIELD_FR);
-  if (!h_is_canonical(fr, u_host)) { set_error("kzg_open: u not canonical"); return MZK_E_RANGE; }
+                 void* d_y, void* d_w_xy, void* d_q, hipStream_t s) {
+  if (!u_host || !d_y || (!d_coef && n) || (d_w_xy && !d_points && n > 1)) { set_error("kzg_open: null pointer"); return MZK_E_ARG; }
+  if (!h_is_canonical(host_field(MZK_FIELD_FR), u_host)) { set_error("kzg_open: u not canonical"); return MZK_E_RANGE; }
   if (n == 0) {  // empty polynomial: y = 0, quotient empty -> infinity
     MZK_HIP(hipMemsetAsync(d_y, 0, 32, s));
     if (d_w_xy) MZK_HIP(hipMemsetAsync(d_w_xy, 0, 64, s));
     return MZK_OK;
   }
-  // level arrays: L0 = coef (n), L1 = chunk values (ceil(n/K)), ...
-  size_t lens[8];
-  int nlev = 0;
-  lens[0] = n;
-  while (lens[nlev] > OPEN_K) { lens[nlev + 1] = (lens[nlev] + OPEN_K - 1) >> OPEN_K_LOG; nlev++; }
-  size_t total_up = 0;
-  for (int l = 1; l <= nlev; l++) total_up += lens[l];
-  u32 *bbuf, *hbuf, *bup;
-  MZK_TRY(ws_get(WS_MISC_A, n * 32, (void**)&bbuf));                  // b of level 0
-  MZK_TRY(ws_get(WS_MISC_B, (total_up + 1) * 32, (void**)&hbuf));     // h of levels 1..nlev
-  MZK_TRY(ws_get(WS_MISC_C, (total_up + 1) * 32, (void**)&bup));      // b of levels 1..nlev
-  // u^(K^l) in Montgomery form, on the host (parameter math)
-  Words8k um[8];
-  {
-    uint64_t ul[4] = {u_host[0], u_host[1], u_host[2], u_host[3]};
-    uint64_t two[4] = {2, 0, 0, 0}, rmod[4], t[4];
-    h_powmod_u64(fr, rmod, two, 261);
-    for (int l = 0; l <= nlev; l++) {
-      h_mulmod(fr, t, ul, rmod);
-      for (int i = 0; i < 4; i++) { um[l].w[2 * i] = (u32)t[i]; um[l].w[2 * i + 1] = (u32)(t[i] >> 32); }
-      h_powmod_u64(fr, ul, ul, OPEN_K);
-    }
-  }
-  const u32* level_in[8];
-  u32* level_b[8];
-  level_in[0] = (const u32*)d_coef;
-  level_b[0] = bbuf;
-  size_t off = 0;
-  for (int l = 1; l <= nlev; l++) {
-    level_in[l] = hbuf + off * 8;
-    level_b[l] = bup + off * 8;
-    off += lens[l];
-  }
-  for (int l = 0; l < nlev; l++) {
-    const size_t chunks = lens[l + 1];
-    hipLaunchKernelGGL(k_open_chunk_eval, dim3((unsigned)((chunks + 63) / 64)), dim3(64), 0, s, level_in[l], lens[l], um[l],
-                       (u32*)level_in[l + 1]);
-  }
-  for (int l = nlev; l >= 0; l--) {
-    const size_t chunks = (lens[l] + OPEN_K - 1) >> OPEN_K_LOG;
-    const u32* carry = (l == nlev) ? nullptr : level_b[l + 1];
-    hipLaunchKernelGGL(k_open_chunk_fill, dim3((unsigned)((chunks + 63) / 64)), dim3(64), 0, s, level_in[l], lens[l], um[l], carry,
-                       (l == nlev) ? (size_t)0 : lens[l + 1], level_b[l]);
-  }
-  MZK_HIP(hipGetLastError());
-  MZK_HIP(hipMemcpyAsync(d_y, bbuf, 32, hipMemcpyDeviceToDevice, s));   // y = b_0
-  if (value_only) return MZK_OK;          // f(u) alone (the sharded opening's first pass: the slice's value)
-  if (d_q_out) {   // quotient only (sharded opening: every rank MSMs its own slice of q)
-    if (n > 1) MZK_HIP(hipMemcpyAsync(d_q_out, bbuf + 8, (n - 1) * 32, hipMemcpyDeviceToDevice, s));
-    return MZK_OK;
-  }
-  // w = MSM(q, powers), q_j = b_{j+1}, j < n - 1     (kzg.rs:70)
-  return msm_dev_impl(bbuf + 8, d_points, n - 1, point_kind, table_stride, d_w_xy, false, s);
+  if (d_w_xy && !d_q) MZK_TRY(ws_get(WS_MISC_A, n * 32, &d_q));
+  const SdJob job = {d_coef, n, u_host, nullptr, d_y, d_q};
+  const size_t one = 1;
+  MZK_TRY(synth_div_dev(&job, &one, 1, s));
+  if (!d_w_xy) return MZK_OK;
+  return msm_dev_impl(d_q, d_points, n - 1, point_kind, table_stride, d_w_xy, false, s);   // w = MSM(q, powers)  (kzg.rs:70)
 }
 
-// ---- open_kzg of MANY short polynomials, polynomial j at its own point u_j (kzg.rs:61-72 once per polynomial, as
-// das/avail.rs:132 does per cell): ONE workgroup per polynomial solves the suffix recurrence b_i = c_i + u b_{i+1} --
-// lane L owns the K = ceil(n / 256) coefficients [L K, (L + 1) K): chunk value at u by Horner, a log-step suffix scan of
-// the 256 chunk values with u^K, u^2K, ... through LDS, then the chunk is filled from its successor's carry.  y_j = b_0,
-// q_j = b_1 .. b_{n-1} (row j of `q`, rows q_stride_words apart); the witness MSMs then run as one grid-batched pass
-// (msm_many_dev_impl).  Field arithmetic is exact, so the canonical outputs equal the chunked single-opening path bit for bit.
-constexpr int OPENM_THREADS = 256;
-constexpr size_t OPENM_MAX_N = (size_t)1 << 14;
-constexpr int PUT_WORDS_MAX = 112;                 // 32-byte values per launch through the kernel-argument buffer (3.5 KiB)
-struct PutBatch { u32 w[PUT_WORDS_MAX][8]; };
-__global__ void k_put_words8(PutBatch b, int count, u32* __restrict__ dst) {
-  const int i = threadIdx.x;
-  if (i < count) st8(dst + 8 * i, b.w[i]);
-}
-__global__ __launch_bounds__(OPENM_THREADS) void k_open_many(const u32* __restrict__ coefs, size_t n, size_t stride_words, const u32* __restrict__ us,
-                                                              u32* __restrict__ q, size_t q_stride_words, u32* __restrict__ ys) {
-  typedef FrParams P;
-  __shared__ u32 S[OPENM_THREADS][P::L];
-  const size_t j = blockIdx.x;
-  const int L = threadIdx.x;
-  const u32* c = coefs + j * stride_words;
-  u32 uw[8];
-  ld8(us + 8 * j, uw);
-  const FrE u = fe_to_mont<P>(fe_unpack<P>(uw));            // u R: fe_mul(x, u) = x u for plain x
-  const size_t K = (n + OPENM_THREADS - 1) / OPENM_THREADS;
-  const size_t lo = (size_t)L * K;
-  const size_t hi = (lo + K < n) ? lo + K : n;
-  FrE mine = fe_zero<P>();
-  if (lo < n) {
-    mine = fr_gload(c, hi - 1);
-    for (size_t t = hi - 1; t-- > lo;) mine = fe_add<P>(fe_mul<P>(mine, u), fr_gload(c, t));
-    mine = fe_reduce<P>(mine);
-  }
-  FrE pw = fe_one<P>(), base = u;                           // u^K in Montgomery form
-  for (size_t k = K; k; k >>= 1) {
-    if (k & 1) pw = fe_mul<P>(pw, base);
-    base = fe_sqr<P>(base);
-  }
-#pragma unroll
-  for (int i = 0; i < P::L; i++) S[L][i] = mine.l[i];
-  for (int d = 1; d < OPENM_THREADS; d <<= 1) {
-    __syncthreads();
-    FrE other = fe_zero<P>();
-    if (L + d < OPENM_THREADS) {
-#pragma unroll
-      for (int i = 0; i < P::L; i++) other.l[i] = S[L + d][i];
-    }
-    __syncthreads();
-    mine = fe_reduce<P>(fe_add<P>(mine, fe_mul<P>(other, pw)));
-#pragma unroll
-    for (int i = 0; i < P::L; i++) S[L][i] = mine.l[i];
-    pw = fe_sqr<P>(pw);
-  }
-  __syncthreads();
-  if (lo >= n) return;
-  FrE acc = fe_zero<P>();                                   // b at index (L + 1) K
-  if (L + 1 < OPENM_THREADS) {
-#pragma unroll
-    for (int i = 0; i < P::L; i++) acc.l[i] = S[L + 1][i];
-  }
-  u32* qj = q + j * q_stride_words;
-  for (size_t t = hi; t-- > lo;) {
-    acc = fe_reduce<P>(fe_add<P>(fe_mul<P>(acc, u), fr_gload(c, t)));
-    if (t > 0) fr_gstore(qj, t - 1, acc);
-    else fr_gstore(ys, j, acc);
-  }
-}
-
-bool kzg_open_many_supported(const mzk_srs* srs, size_t n) { return n <= OPENM_MAX_N && srs_many_capable(srs); }
+// ---- open_kzg of MANY short polynomials, polynomial j at its own point u_j (kzg.rs:61-72 once per polynomial, as das/avail.rs:132
+// does per cell): one round of divisions, y_j = b_0, q_j = b_1 .. b_{n-1} (row j of q, n elements apart); the witness MSMs then run
+// as one grid-batched pass (msm_many_srs).  Field arithmetic is exact, so the outputs equal the single openings bit for bit.
+constexpr size_t OPEN_MANY_MAX_N = (size_t)1 << 14;      // the witness pass's range; the division takes any n
+bool kzg_open_many_supported(const mzk_srs* srs, size_t n) { return n <= OPEN_MANY_MAX_N && srs_many_capable(srs); }
 // d_ys: count * 8 words, d_ws_xy: count * 16 words.
 int kzg_open_many_dev(const mzk_srs* srs, const void* d_coefs, size_t n, size_t count, const uint64_t* us_host, void* d_ys, void* d_ws_xy, hipStream_t s) {
   if (count == 0) return MZK_OK;
@@ -534,26 +548,16 @@ int kzg_open_many_dev(const mzk_srs* srs, const void* d_coefs, size_t n, size_t 
     MZK_HIP(hipMemsetAsync(d_ws_xy, 0, count * 64, s));
     return MZK_OK;
   }
-  size_t per_pass = (((size_t)1 << 22) + n - 1) / n;
-  u32 *d_us, *d_q;
-  const size_t first_cnt = count < per_pass ? count : per_pass;
-  MZK_TRY(ws_get(WS_MISC_B, first_cnt * 32, (void**)&d_us));
-  MZK_TRY(ws_get(WS_MISC_A, first_cnt * n * 32, (void**)&d_q));
+  const size_t per_pass = (((size_t)1 << 22) + n - 1) / n;
+  char* d_q;
+  MZK_TRY(ws_get(WS_MISC_A, (count < per_pass ? count : per_pass) * n * 32, (void**)&d_q));
+  std::vector<SdJob> jobs;
   for (size_t first = 0; first < count; first += per_pass) {
     const size_t cnt = (count - first < per_pass) ? count - first : per_pass;
-    for (size_t k = 0; k < cnt; k += PUT_WORDS_MAX) {
-      PutBatch b;
-      const int m = (int)((cnt - k < (size_t)PUT_WORDS_MAX) ? cnt - k : (size_t)PUT_WORDS_MAX);
-      for (int i = 0; i < m; i++)
-        for (int l = 0; l < 4; l++) {
-          const uint64_t v = us_host[4 * (first + k + i) + l];
-          b.w[i][2 * l] = (u32)v; b.w[i][2 * l + 1] = (u32)(v >> 32);
-        }
-      hipLaunchKernelGGL(k_put_words8, dim3(1), dim3(128), 0, s, b, m, d_us + 8 * k);
-    }
-    hipLaunchKernelGGL(k_open_many, dim3((unsigned)cnt), dim3(OPENM_THREADS), 0, s, (const u32*)d_coefs + first * n * 8, n, n * 8, (const u32*)d_us, d_q, n * 8,
-                       (u32*)d_ys + first * 8);
-    MZK_HIP(hipGetLastError());
+    jobs.clear();
+    for (size_t j = first; j < first + cnt; j++)
+      jobs.push_back({(const char*)d_coefs + j * n * 32, n, us_host + 4 * j, nullptr, (char*)d_ys + j * 32, d_q + (j - first) * n * 32});
+    MZK_TRY(synth_div_dev(jobs.data(), &cnt, 1, s));
     // w_j = MSM(q_j, powers), q_j of n - 1 coefficients     (kzg.rs:70)
     MZK_TRY(msm_many_srs(srs, d_q, n - 1, n, cnt, (u32*)d_ws_xy + first * 16, s));
   }

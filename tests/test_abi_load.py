@@ -123,7 +123,6 @@ def test_no_hot_kernel_spills_registers():
         "k_ntt_strided<mzk::FrParams": (24, "three wave-uniform Shoup twiddles are 2 x 9 scalar registers each, next to 102 usable SGPRs"),
         "k_ntt_last<mzk::FrParams": (24, "same"),
         "k_many_sort1": (64, "per-window histogram bases kept in scalar registers across the walk"),
-        "k_open_many": (16, "chunk bookkeeping of the suffix scan"),
         "k_seg_combine_heavy": (8, "skewed inputs only (returns at once when no bucket was deferred, i.e. on every uniform input); two forms in one kernel -- a workgroup per bucket / several per bucket -- rather than a launch more on the path of every MSM"),
         "k_reduce_tail_row": (128, "single-workgroup latency tail: non-inlined one-shot operations, constants of four Horner chains"),
         "k_direct_finish": (96, "one workgroup per polynomial, latency tail: the non-inlined row operations of the tail"),

@@ -123,7 +123,10 @@ def test_sharded_end_to_end_on_one_gpu(world):
     assert w == orc.ec_mul(0, (1, 2), (fa - y) * pow(alpha - u, -1, P_FR) % P_FR)
 
 
-@pytest.mark.parametrize("n,world", [(1000, 3), (1 << 16, 8), (33, 2), (5, 4)])
+# slices below, at and above the one-workgroup limit of the division (2^13) and 2^14, and (2^20 + 66, 2) past two chunk levels
+@pytest.mark.parametrize("n,world", [(1000, 3), (1 << 16, 8), (33, 2), (5, 4), ((1 << 13) - 1, 1), (1 << 13, 1), ((1 << 13) + 1, 1),
+                                     (3 << 13, 3), ((1 << 14) + 7, 2), (1 << 14, 1), ((1 << 14) + 1, 1), (3 << 14, 3), ((1 << 15) + 7, 2),
+                                     ((1 << 20) + 66, 2)])
 def test_sharded_open_quotient_equals_the_whole_quotient(n, world):
     """the quotient of open_kzg (kzg.rs:61-72) computed slice by slice -- mzk_kzg_open_slice_value_dev, the top-down
     carries (sharded.open_carries), mzk_kzg_open_slice_quotient_dev -- with all `world` ranks inside one process: the concatenated

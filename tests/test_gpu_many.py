@@ -231,7 +231,7 @@ def test_batch_entry_points_route_to_the_same_pass(mz):
     h.close()
 
 
-@pytest.mark.parametrize("n,count", [(1, 3), (2, 2), (257, 5), (1024, 9), (1025, 4), (4097, 3), (16384, 2)])
+@pytest.mark.parametrize("n,count", [(1, 3), (2, 2), (257, 5), (1024, 9), (1025, 4), (4097, 3), (8193, 3), (16384, 2)])
 def test_many_openings_equal_definition_and_single_calls(mz, n, count):
     """open_kzg (kzg.rs:61-72) per polynomial at its own point: y = f(u) by the oracle's Horner, w = the oracle's witness
     (literal kzg_open_ref for the small cases), and both equal to mzk_kzg_open_srs_dev"""
