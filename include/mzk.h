@@ -539,6 +539,49 @@ typedef int (*mzk_sumcheck_challenge_fn)(void* user, int round, const uint64_t g
 int mzk_sumcheck_prove_srs(const mzk_srs* srs, const uint64_t* coef, size_t n, mzk_sumcheck_challenge_fn challenge, void* user, uint64_t* gs,
                            uint64_t* rs, uint64_t beta[4], uint64_t* commits_xy, uint64_t* ys, uint64_t* ws_xy, uint64_t* deg_xy);
 
+/* ---- symbolic evaluation of multivariate constraints and the combination of the quotients (FastStark::prove) ----------
+ * MPolynomial::evaluate_symbolic (algebra/mpolynomials.rs:125-141; zkstark/fast_stark.rs:246-259 composes every transition
+ * constraint with the trace polynomials, zkstark/stark.rs:214 does the same) for n_constraints sparse multivariate polynomials over
+ * ONE point of n_vars univariate polynomials:  out_a = sum_t c_t * prod_i point[i]^k[t][i], trimmed of trailing zeros as every
+ * `+` and `*` of polynomial.rs:214-228, 302-316 trims (the zero polynomial is empty; pow(0) is one even for the zero polynomial,
+ * polynomial.rs:338-348).  Computed in evaluation form -- one batched forward transform of the point, one kernel over (domain point,
+ * constraint), one batched inverse transform -- and bit-identical to the reference's term-by-term products (exact arithmetic).
+ *   flat term table: constraint a = terms [term_offsets[a], term_offsets[a+1]) (n_constraints + 1 offsets); term t has the coefficient
+ *     term_coefs[t] (one element) and the exponents term_exps[t * n_vars .. (t+1) * n_vars).  Duplicate exponent rows are allowed and
+ *     add up (a HashMap cannot hold them, a flat table can); zero coefficients are allowed.  The reference indexes point[i] for every
+ *     i < k.len(), so one n_vars serves the exponent rows and the point.
+ *   point[i] = elements [point_offsets[i], point_offsets[i+1]) of `point`, ascending degree (n_vars + 1 offsets).  Lengths need not be
+ *     trimmed: trailing zeros enlarge the bound below and give the same result.
+ *   degree bound of constraint a: D_a = max over its terms of sum_i k[t][i] * (len_i - 1); a term with a positive exponent on an empty
+ *     point[i] vanishes and does not count.  Transform size N = next_pow2(max_a D_a + 1).
+ *   out: row a = out[a * out_stride ..], out_lens[a] coefficients and zeros behind them up to out_stride.
+ * mzk_mpoly_compose_plan (host only, needs no device): *n_transform = N, *out_stride_min = max_a (D_a + 1), bounds[a] = D_a + 1
+ * (bounds may be NULL; 0 for a constraint without a non-vanishing term; all three 0 when n_constraints == 0).
+ * Errors, with nothing left enqueued: a field other than MZK_FIELD_FR / MZK_FIELD_M128, a null pointer, n_vars >
+ * MZK_MPOLY_MAX_VARS: MZK_E_ARG; a coefficient of a term or (host form) of a point polynomial not canonical: MZK_E_RANGE;
+ * out_stride < out_stride_min, N above the size limit of transforms, a degree bound that overflows 64 bits, an offset array that
+ * decreases, 2^28 terms or more: MZK_E_LENGTH.  n_constraints == 0: MZK_OK, nothing written.  A constraint without terms: length 0.  Constants only: N = 1.
+ * The _dev form: point and out in HBM (canonical, not checked), complete on `stream` before the call; the term table, the offsets and
+ * out_lens are host memory; returns when d_out is complete (as mzk_fast_interpolate_batch_dev does). */
+enum { MZK_MPOLY_MAX_VARS = 8 };
+int mzk_mpoly_compose_plan(int field_id, const uint32_t* term_exps, const size_t* term_offsets, size_t n_constraints, size_t n_vars,
+                           const size_t* point_offsets, size_t* n_transform, size_t* out_stride_min, size_t* bounds);
+int mzk_mpoly_compose(int field_id, const uint64_t* term_coefs, const uint32_t* term_exps, const size_t* term_offsets, size_t n_constraints,
+                      size_t n_vars, const uint64_t* point, const size_t* point_offsets, uint64_t* out, size_t out_stride, size_t* out_lens);
+int mzk_mpoly_compose_dev(int field_id, const uint64_t* term_coefs, const uint32_t* term_exps, const size_t* term_offsets, size_t n_constraints,
+                          size_t n_vars, const void* d_point, const size_t* point_offsets, void* d_out, size_t out_stride, size_t* out_lens,
+                          void* stream);
+/* The weighted combination of the quotients (fast_stark.rs:301-326: sum_i w_i * X^(s_i) * p_i, each quotient once plain and once
+ * shifted):  out[j] = sum_i weights[i] * p_i[j - shifts[i]],  p_i = elements [offsets[i], offsets[i+1]) of polys (count + 1 offsets).
+ * One launch; out is written (zero-filled) up to out_cap, *out_len = the length after the reference's trim.  Bit-identical to the
+ * reference's sequence of Polynomial products and sums.  weights (canonical, MZK_E_RANGE otherwise), shifts, offsets and out_len are
+ * host memory in both forms.  out_cap < max_i (len_i + shifts[i]) or decreasing offsets: MZK_E_LENGTH; bad field, null pointer:
+ * MZK_E_ARG; (host form) a coefficient not canonical: MZK_E_RANGE.  count == 0: the zero polynomial. */
+int mzk_poly_lincomb(int field_id, const uint64_t* polys, const size_t* offsets, size_t count, const uint64_t* weights, const size_t* shifts,
+                     uint64_t* out, size_t out_cap, size_t* out_len);
+int mzk_poly_lincomb_dev(int field_id, const void* d_polys, const size_t* offsets, size_t count, const uint64_t* weights, const size_t* shifts,
+                         void* d_out, size_t out_cap, size_t* out_len, void* stream);
+
 /* Build an SRS handle from points already in HBM (affine canonical, n * 8 limbs).  The _ex form chooses
  * whether the window tables are built (worth it from ~30 commits per SRS on at 2^20 points; a one-shot pipeline keeps
  * the plain prepared points and pays the window Horner instead).  Default widths by size: 8 bits up to 1024 points,

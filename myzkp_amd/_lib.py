@@ -949,6 +949,96 @@ def fast_interpolate_batch_dev(fid, domain, d_values_ptr, batch, root, root_orde
     return [int(lens[k]) for k in range(batch)]
 
 
+def mpoly_term_table(fid, constraints, n_vars):
+    """[[(coef, exps), ...], ...] (one list of terms per constraint; an MPolynomial.dictionary is `[(c, k) for k, c in d.items()]`) ->
+    the flat term table of mzk_mpoly_compose: coefficients (terms x limbs), exponents (terms x n_vars, uint32), offsets (size_t)."""
+    coefs, exps, offs = [], [], [0]
+    for terms in constraints:
+        for c, k in terms:
+            if len(k) != n_vars:
+                raise MzkError(-5, "index out of bounds: a term has %d exponents, the point %d polynomials" % (len(k), n_vars))
+            coefs.append(int(c))
+            exps.append([int(e) for e in k])
+        offs.append(len(coefs))
+    tc = to_limbs(coefs, LIMBS[fid]) if coefs else np.zeros((0, LIMBS[fid]), dtype=np.uint64)
+    te = np.ascontiguousarray(np.array(exps, dtype=np.uint32).reshape(len(coefs), n_vars))
+    return tc, te, (ctypes.c_size_t * len(offs))(*offs)
+
+
+def _offsets_of(lens):
+    offs = [0]
+    for n in lens:
+        offs.append(offs[-1] + int(n))
+    return (ctypes.c_size_t * len(offs))(*offs)
+
+
+def mpoly_compose_plan(fid, constraints, point_lens):
+    """mzk_mpoly_compose_plan (host only): (N, out_stride_min, [D_a + 1]) for constraints as in mpoly_term_table over point
+    polynomials of the given lengths."""
+    nv, nc = len(point_lens), len(constraints)
+    _, te, toff = mpoly_term_table(fid, constraints, nv)
+    n, smin = ctypes.c_size_t(0), ctypes.c_size_t(0)
+    bounds = (ctypes.c_size_t * max(nc, 1))()
+    _check(lib().mzk_mpoly_compose_plan(int(fid), _p(te), toff, ctypes.c_size_t(nc), ctypes.c_size_t(nv), _offsets_of(point_lens),
+                                        ctypes.byref(n), ctypes.byref(smin), bounds))
+    return n.value, smin.value, [int(bounds[a]) for a in range(nc)]
+
+
+def mpoly_compose(fid, constraints, point, out_stride=None):
+    """MPolynomial::evaluate_symbolic (algebra/mpolynomials.rs:125-141) of every constraint over one point: `point` is a list of
+    coefficient arrays (n_i x limbs, ascending degree); returns one trimmed coefficient array per constraint."""
+    pts = [_arr(fid, q) for q in point]
+    nv, nc = len(pts), len(constraints)
+    tc, te, toff = mpoly_term_table(fid, constraints, nv)
+    poff = _offsets_of([q.shape[0] for q in pts])
+    flat = np.ascontiguousarray(np.concatenate(pts)) if nv else np.zeros((0, LIMBS[fid]), dtype=np.uint64)
+    if out_stride is None:
+        out_stride = mpoly_compose_plan(fid, constraints, [q.shape[0] for q in pts])[1]
+    out = np.zeros((max(nc, 1), max(out_stride, 1), LIMBS[fid]), dtype=np.uint64)
+    lens = (ctypes.c_size_t * max(nc, 1))()
+    _check(lib().mzk_mpoly_compose(int(fid), _p(tc), _p(te), toff, ctypes.c_size_t(nc), ctypes.c_size_t(nv), _p(flat), poff, _p(out),
+                                   ctypes.c_size_t(out_stride), lens))
+    return [out[a, :lens[a]].copy() for a in range(nc)]
+
+
+def mpoly_compose_dev(fid, constraints, d_point_ptr, point_lens, d_out_ptr, out_stride, stream=0):
+    """mzk_mpoly_compose_dev: the point polynomials back to back in HBM (raw device pointer), rows of out_stride elements written at
+    d_out_ptr; returns the trimmed lengths."""
+    nv, nc = len(point_lens), len(constraints)
+    tc, te, toff = mpoly_term_table(fid, constraints, nv)
+    lens = (ctypes.c_size_t * max(nc, 1))()
+    _check(lib().mzk_mpoly_compose_dev(int(fid), _p(tc), _p(te), toff, ctypes.c_size_t(nc), ctypes.c_size_t(nv), ctypes.c_void_p(d_point_ptr),
+                                       _offsets_of(point_lens), ctypes.c_void_p(d_out_ptr), ctypes.c_size_t(out_stride), lens, ctypes.c_void_p(stream)))
+    return [int(lens[a]) for a in range(nc)]
+
+
+def poly_lincomb(fid, polys, weights, shifts, out_cap=None):
+    """sum_i weights[i] * X^shifts[i] * polys[i] (fast_stark.rs:301-326), trimmed: mzk_poly_lincomb."""
+    ps = [_arr(fid, q) for q in polys]
+    count = len(ps)
+    flat = np.ascontiguousarray(np.concatenate(ps)) if count else np.zeros((0, LIMBS[fid]), dtype=np.uint64)
+    if out_cap is None:
+        out_cap = max([q.shape[0] + int(sh) for q, sh in zip(ps, shifts)] + [0])
+    w = to_limbs([int(x) for x in weights], LIMBS[fid]) if count else np.zeros((0, LIMBS[fid]), dtype=np.uint64)
+    sh = (ctypes.c_size_t * max(count, 1))(*[int(x) for x in shifts])
+    out = np.zeros((max(out_cap, 1), LIMBS[fid]), dtype=np.uint64)
+    n = ctypes.c_size_t(0)
+    _check(lib().mzk_poly_lincomb(int(fid), _p(flat), _offsets_of([q.shape[0] for q in ps]), ctypes.c_size_t(count), _p(w), sh, _p(out),
+                                  ctypes.c_size_t(out_cap), ctypes.byref(n)))
+    return out[:n.value].copy()
+
+
+def poly_lincomb_dev(fid, d_polys_ptr, lens, weights, shifts, d_out_ptr, out_cap, stream=0):
+    """mzk_poly_lincomb_dev: polynomials back to back in HBM, out_cap elements written at d_out_ptr; returns the trimmed length."""
+    count = len(lens)
+    w = to_limbs([int(x) for x in weights], LIMBS[fid]) if count else np.zeros((0, LIMBS[fid]), dtype=np.uint64)
+    sh = (ctypes.c_size_t * max(count, 1))(*[int(x) for x in shifts])
+    n = ctypes.c_size_t(0)
+    _check(lib().mzk_poly_lincomb_dev(int(fid), ctypes.c_void_p(d_polys_ptr), _offsets_of(lens), ctypes.c_size_t(count), _p(w), sh,
+                                      ctypes.c_void_p(d_out_ptr), ctypes.c_size_t(out_cap), ctypes.byref(n), ctypes.c_void_p(stream)))
+    return n.value
+
+
 def g2_points_to_array(pts):
     """[((x0, x1), (y0, y1)), ...] -> (n, 16) limbs; infinity = ((0, 0), (0, 0))."""
     a = np.zeros((len(pts), 16), dtype=np.uint64)

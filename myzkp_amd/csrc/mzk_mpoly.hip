@@ -1,0 +1,546 @@
+// mzk_mpoly.hip -- the polynomial algebra between the transforms of FastStark::prove (zkstark/fast_stark.rs:177-396) on gfx950:
+//   * MPolynomial::evaluate_symbolic (algebra/mpolynomials.rs:125-141; fast_stark.rs:246-259, stark.rs:214): univariate polynomials
+//     substituted for the variables of sparse multivariate constraints, several constraints over one point in one call;
+//   * the weighted, shifted combination of the quotients (fast_stark.rs:301-326).
+//
+// evaluate_symbolic is a polynomial identity, out_a = sum_t c_t prod_i point[i]^k[t][i], and field arithmetic is exact: computed in
+// EVALUATION form over a subgroup of N > deg(out_a) points it gives the canonical coefficients the reference's term-by-term schoolbook
+// products give.  A call is
+//   k_mp_pad      the n_vars point polynomials, zero-padded to N, as rows of one matrix;
+//   ONE batched forward transform of n_vars rows (mzk_ntt.hip);
+//   k_mp_terms    V[a][j] = sum_t c_t prod_i E[i][j]^k[t][i] for every domain point j and constraint a (below);
+//   ONE batched inverse transform of n_constraints rows;
+//   k_mp_rows     rows copied to the caller's stride (zeros behind them) and every row's trimmed length (polynomial.rs:214-228 trims
+//                 after every + and *), so that only the lengths travel to the host.
+//
+// k_mp_terms runs a TERM PROGRAM the host compiles per constraint (mp_compile).  The terms are sorted so that those sharing the monomial of
+// every variable but one (the Horner variable h: the one with the largest exponent in the constraint) form a run -- the shape
+// MPolynomial::lift produces (rescueprime.rs:454-484: a univariate in the cycle variable times a monomial of the state variables) -- and a
+// run sum_j c_j x_h^(d_j) m, d_0 > d_1 > ..., is evaluated as (((c_0 x_h^(d_0-d_1) + c_1) x_h^(d_1-d_2) + ...) x_h^(d_k)) m: about one
+// product per term.  Exponents of at most MP_TABLE come from per-variable power tables, 4 .. 2 MP_TABLE from two table products, larger
+// ones from square-and-multiply (uniform over the wave: the exponent is part of the program).
+//
+// Launch shape: one wave per workgroup, one domain point per lane, grid = (N / 64, n_constraints).  The program and the coefficients are
+// the same for every lane and are read with wave-uniform loads; a lane's state is the Horner accumulator, the constraint's sum and the
+// operand of the running product.  The power tables x_i, x_i^2, x_i^3 (Montgomery form) live in LDS as [slot][limb][lane] -- the slot is a
+// run-time value of the program, and a register array indexed by it would go to scratch memory; lane-minor order makes every read
+// conflict-free.  Variables that never need a power above 1 or 2 get fewer slots (mp_compile: depth), unused ones none.
+// Values: E and the coefficients are plain (canonical), the tables are Montgomery form, and plain * Montgomery / R = plain: the
+// accumulator never changes form and the sum is reduced and stored as it stands.
+#include <algorithm>
+#include <vector>
+#include "mzk_common.h"
+#include "mzk_field_asm.h"
+
+namespace mzk {
+
+constexpr int MP_MAX_VARS = MZK_MPOLY_MAX_VARS;
+constexpr int MP_TABLE = 3;              // deepest power kept per variable
+constexpr int MP_LANES = 64;
+enum { MP_LOADC = 1, MP_ADDC = 2, MP_MULT = 3, MP_HORNER = 4, MP_POW = 5 };
+constexpr u32 MP_FLUSH = 1u << 31;       // after the op: sum += acc
+// op word: op | slot << 8 | flush; arg word: coefficient index (LOADC, ADDC, HORNER) or exponent (POW; slot = the variable's first slot)
+struct MpOp { u32 op, arg; };
+struct MpVars { u32 first_slot[MP_MAX_VARS]; u32 depth[MP_MAX_VARS]; };
+struct MpRows { size_t off[MP_MAX_VARS + 1]; };
+
+template <class P> __device__ __forceinline__ Fe<P> mp_gload(const u32* __restrict__ g, size_t idx) {
+  u32 w[P::NW];
+  const uint4* p4 = reinterpret_cast<const uint4*>(g + idx * P::NW);
+#pragma unroll
+  for (int q = 0; q < P::NW / 4; q++) { const uint4 v = p4[q]; w[4 * q] = v.x; w[4 * q + 1] = v.y; w[4 * q + 2] = v.z; w[4 * q + 3] = v.w; }
+  return fe_unpack<P>(w);
+}
+template <class P> __device__ __forceinline__ void mp_gstore(u32* __restrict__ g, size_t idx, const Fe<P>& v) {   // v canonical
+  u32 w[P::NW];
+  fe_pack<P>(v, w);
+  uint4* p4 = reinterpret_cast<uint4*>(g + idx * P::NW);
+#pragma unroll
+  for (int q = 0; q < P::NW / 4; q++) p4[q] = make_uint4(w[4 * q], w[4 * q + 1], w[4 * q + 2], w[4 * q + 3]);
+}
+// the same element for every lane: word loads at a wave-uniform address
+template <class P> __device__ __forceinline__ Fe<P> mp_uload(const u32* __restrict__ g, u32 idx) {
+  u32 w[P::NW];
+#pragma unroll
+  for (int k = 0; k < P::NW; k++) w[k] = g[(size_t)idx * P::NW + k];
+  return fe_unpack<P>(w);
+}
+template <class P> __device__ __forceinline__ Fe<P> mp_lds_load(const u32* lds, u32 slot, int lane) {
+  Fe<P> r;
+#pragma unroll
+  for (int i = 0; i < P::L; i++) r.l[i] = lds[(slot * P::L + i) * MP_LANES + lane];
+  return r;
+}
+template <class P> __device__ __forceinline__ void mp_lds_store(u32* lds, u32 slot, int lane, const Fe<P>& v) {
+#pragma unroll
+  for (int i = 0; i < P::L; i++) lds[(slot * P::L + i) * MP_LANES + lane] = v.l[i];
+}
+
+// row i of dst (n elements) = point i, zero-padded
+template <class P>
+__global__ __launch_bounds__(256) void k_mp_pad(const u32* __restrict__ point, MpRows R, size_t n, u32* __restrict__ dst) {
+  const size_t j = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (j >= n) return;
+  const int i = blockIdx.y;
+  const size_t len = R.off[i + 1] - R.off[i];
+  uint4* o = reinterpret_cast<uint4*>(dst + ((size_t)i * n + j) * P::NW);
+  const uint4* s = reinterpret_cast<const uint4*>(point + (R.off[i] + j) * P::NW);
+#pragma unroll
+  for (int q = 0; q < P::NW / 4; q++) o[q] = j < len ? s[q] : make_uint4(0, 0, 0, 0);
+}
+
+// E: n_vars rows of n evaluations (canonical).  prog_off[a] .. prog_off[a + 1]: the ops of constraint a = blockIdx.y.  V: row a.
+template <class P>
+__global__ __launch_bounds__(MP_LANES) void k_mp_terms(const u32* __restrict__ E, size_t n, int n_vars, MpVars vars, const MpOp* __restrict__ prog,
+                                                       const u32* __restrict__ prog_off, const u32* __restrict__ coefs, u32* __restrict__ V) {
+  extern __shared__ u32 mp_lds[];
+  const int lane = threadIdx.x;
+  const size_t j = (size_t)blockIdx.x * MP_LANES + lane;
+  const size_t jj = j < n ? j : n - 1;             // lanes past the end compute point n - 1 again and store nothing
+  for (int i = 0; i < n_vars; i++) {
+    const u32 depth = vars.depth[i], s0 = vars.first_slot[i];
+    if (depth == 0) continue;
+    const Fe<P> x = FeAsm<P>::mul(mp_gload<P>(E, (size_t)i * n + jj), fe_r2<P>());
+    mp_lds_store<P>(mp_lds, s0, lane, x);
+    if (depth > 1) {
+      const Fe<P> x2 = FeAsm<P>::sqr(x);
+      mp_lds_store<P>(mp_lds, s0 + 1, lane, x2);
+      if (depth > 2) mp_lds_store<P>(mp_lds, s0 + 2, lane, FeAsm<P>::mul(x2, x));
+    }
+  }
+  // a lane reads back only what it wrote itself: no barrier
+  const int a = blockIdx.y;
+  const u32 pc0 = prog_off[a], pc1 = prog_off[a + 1];
+  Fe<P> acc = fe_zero<P>(), sum = fe_zero<P>();
+  for (u32 pc = pc0; pc < pc1; pc++) {
+    const u32 w = __builtin_amdgcn_readfirstlane(prog[pc].op), arg = __builtin_amdgcn_readfirstlane(prog[pc].arg);
+    const u32 op = w & 0xffu, slot = (w >> 8) & 0xffffu;
+    if (op == MP_LOADC) {
+      acc = mp_uload<P>(coefs, arg);
+    } else if (op == MP_ADDC) {
+      acc = fe_reduce<P>(fe_add<P>(acc, mp_uload<P>(coefs, arg)));
+    } else if (op == MP_POW) {
+      // acc *= x^arg, arg > 2 MP_TABLE: square-and-multiply from the top bit down
+      const Fe<P> x = mp_lds_load<P>(mp_lds, slot, lane);
+      Fe<P> y = x;
+      for (int bit = 30 - __builtin_clz(arg); bit >= 0; bit--) {
+        y = FeAsm<P>::sqr(y);
+        if ((arg >> bit) & 1u) y = FeAsm<P>::mul(y, x);
+      }
+      acc = FeAsm<P>::mul(acc, y);
+    } else {
+      // MULT / HORNER: acc < 3p with limbs below 2^30 times a normalised table entry; the sum of a product (< p + 1) and a canonical
+      // coefficient needs no reduction before the next product
+      acc = FeAsm<P>::mul(acc, mp_lds_load<P>(mp_lds, slot, lane));
+      if (op == MP_HORNER) acc = fe_add<P>(acc, mp_uload<P>(coefs, arg));
+    }
+    if (w & MP_FLUSH) sum = fe_reduce<P>(fe_add<P>(sum, acc));
+  }
+  if (j < n) mp_gstore<P>(V, (size_t)a * n + j, sum);
+}
+
+// out row a (stride elements) = the first min(n, stride) elements of V's row a, zeros behind them; lens[a] = max(lens[a], 1 + index of the
+// last non-zero element) -- lens zeroed before the launch
+template <class P>
+__global__ __launch_bounds__(256) void k_mp_rows(const u32* __restrict__ V, size_t n, u32* __restrict__ out, size_t stride, unsigned long long* __restrict__ lens) {
+  __shared__ unsigned long long sh[256];
+  const size_t j = (size_t)blockIdx.x * 256 + threadIdx.x;
+  const int a = blockIdx.y;
+  unsigned long long best = 0;
+  if (j < stride) {
+    uint4 v[P::NW / 4];
+    u32 nz = 0;
+#pragma unroll
+    for (int q = 0; q < P::NW / 4; q++) {
+      v[q] = j < n ? reinterpret_cast<const uint4*>(V + ((size_t)a * n + j) * P::NW)[q] : make_uint4(0, 0, 0, 0);
+      nz |= v[q].x | v[q].y | v[q].z | v[q].w;
+      reinterpret_cast<uint4*>(out + ((size_t)a * stride + j) * P::NW)[q] = v[q];
+    }
+    if (nz) best = j + 1;
+  }
+  sh[threadIdx.x] = best;
+  __syncthreads();
+  for (int off = 128; off >= 1; off >>= 1) {
+    if ((int)threadIdx.x < off && sh[threadIdx.x + off] > sh[threadIdx.x]) sh[threadIdx.x] = sh[threadIdx.x + off];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0 && sh[0]) atomicMax(&lens[a], sh[0]);
+}
+
+// ---- the weighted combination (fast_stark.rs:301-326) ------------------------------------------------------------------------------
+// out[j] = sum_i w_i p_i[j - s_i]: one output coefficient per lane, the table (offset, length, shift, weight in Montgomery form) wave-uniform
+struct MpLcItem { unsigned long long off, len, shift; u32 w[8]; u32 pad[2]; };
+template <class P>
+__global__ __launch_bounds__(256) void k_mp_lincomb(const u32* __restrict__ polys, const MpLcItem* __restrict__ items, u32 count, u32* __restrict__ out,
+                                                    size_t cap, unsigned long long* __restrict__ len) {
+  __shared__ unsigned long long sh[256];
+  const size_t j = (size_t)blockIdx.x * 256 + threadIdx.x;
+  Fe<P> acc = fe_zero<P>();
+  for (u32 i = 0; i < count; i++) {
+    const unsigned long long off = items[i].off, ln = items[i].len, sft = items[i].shift;
+    if (j < sft || j - sft >= ln || j >= cap) continue;
+    u32 w[P::NW];
+#pragma unroll
+    for (int k = 0; k < P::NW; k++) w[k] = items[i].w[k];
+    acc = fe_reduce<P>(fe_add<P>(acc, FeAsm<P>::mul(mp_gload<P>(polys, off + (j - sft)), fe_unpack<P>(w))));
+  }
+  unsigned long long best = 0;
+  if (j < cap) {
+    mp_gstore<P>(out, j, acc);
+    if (!fe_is_zero_canon<P>(acc)) best = j + 1;
+  }
+  sh[threadIdx.x] = best;
+  __syncthreads();
+  for (int off = 128; off >= 1; off >>= 1) {
+    if ((int)threadIdx.x < off && sh[threadIdx.x + off] > sh[threadIdx.x]) sh[threadIdx.x] = sh[threadIdx.x + off];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0 && sh[0]) atomicMax(len, sh[0]);
+}
+
+// ---- host plan -----------------------------------------------------------------------------------------------------------------------
+static bool mp_field_ok(int fid) { return fid == MZK_FIELD_FR || fid == MZK_FIELD_M128; }
+static unsigned mp_max_log(int fid) { return fid == MZK_FIELD_FR ? 28 : 32; }       // mzk.h "Size limits"
+struct MpPlan { size_t n = 0, stride_min = 0; std::vector<size_t> bounds; };
+
+static int mp_monotone(const size_t* off, size_t count, const char* what) {
+  for (size_t i = 0; i < count; i++) if (off[i + 1] < off[i]) { set_error("mpoly_compose: %s[%zu] = %zu is below %s[%zu] = %zu", what, i + 1, off[i + 1], what, i, off[i]); return MZK_E_LENGTH; }
+  return MZK_OK;
+}
+// term t vanishes (a positive exponent on an empty polynomial) ?  *deg = sum_i k_i (len_i - 1)
+static int mp_term_degree(const uint32_t* k, size_t nv, const size_t* point_offsets, bool* vanishes, size_t* deg) {
+  size_t d = 0;
+  *vanishes = false;
+  for (size_t i = 0; i < nv; i++) {
+    if (k[i] == 0) continue;
+    const size_t len = point_offsets[i + 1] - point_offsets[i];
+    if (len == 0) { *vanishes = true; return MZK_OK; }
+    size_t m;
+    if (__builtin_mul_overflow((size_t)k[i], len - 1, &m) || __builtin_add_overflow(d, m, &d)) {
+      set_error("mpoly_compose: the degree bound of a term overflows 64 bits");
+      return MZK_E_LENGTH;
+    }
+  }
+  *deg = d;
+  return MZK_OK;
+}
+static int mp_plan(int fid, const uint32_t* term_exps, const size_t* term_offsets, size_t nc, size_t nv, const size_t* point_offsets, MpPlan* pl) {
+  if (!mp_field_ok(fid)) { set_error("mpoly_compose: bad field id %d", fid); return MZK_E_ARG; }
+  if (nv > (size_t)MP_MAX_VARS) { set_error("mpoly_compose: %zu variables (at most %d)", nv, MP_MAX_VARS); return MZK_E_ARG; }
+  if (nc == 0) return MZK_OK;
+  if (!term_offsets || (nv && !point_offsets)) { set_error("mpoly_compose: null pointer"); return MZK_E_ARG; }
+  MZK_TRY(mp_monotone(term_offsets, nc, "term_offsets"));
+  if (nv) MZK_TRY(mp_monotone(point_offsets, nv, "point_offsets"));
+  if (term_offsets[nc] > term_offsets[0] && nv && !term_exps) { set_error("mpoly_compose: null pointer"); return MZK_E_ARG; }
+  pl->bounds.assign(nc, 0);
+  for (size_t a = 0; a < nc; a++)
+    for (size_t t = term_offsets[a]; t < term_offsets[a + 1]; t++) {
+      bool vanishes;
+      size_t d = 0;
+      MZK_TRY(mp_term_degree(nv ? term_exps + t * nv : nullptr, nv, point_offsets, &vanishes, &d));
+      if (vanishes) continue;
+      if (d == SIZE_MAX) { set_error("mpoly_compose: the degree bound of a term overflows 64 bits"); return MZK_E_LENGTH; }
+      pl->bounds[a] = std::max(pl->bounds[a], d + 1);
+    }
+  pl->stride_min = *std::max_element(pl->bounds.begin(), pl->bounds.end());
+  unsigned lg = 0;
+  while (lg < 64 && ((size_t)1 << lg) < pl->stride_min) lg++;
+  if (lg > mp_max_log(fid)) {
+    set_error("mpoly_compose: degree bound %zu needs a transform of 2^%u points (at most 2^%u over this field)", pl->stride_min - 1, lg, mp_max_log(fid));
+    return MZK_E_LENGTH;
+  }
+  pl->n = (size_t)1 << lg;
+  return MZK_OK;
+}
+
+// ---- term programs -------------------------------------------------------------------------------------------------------------------
+struct MpProgram { std::vector<MpOp> ops; std::vector<u32> off; MpVars vars; u32 slots = 0; };
+
+static void mp_emit_pow(std::vector<MpOp>& ops, const MpVars& v, u32 var, u32 e) {
+  const u32 s0 = v.first_slot[var];
+  if (e == 0) return;
+  if (e <= (u32)MP_TABLE) ops.push_back({MP_MULT | (s0 + e - 1) << 8, 0});
+  else if (e <= 2u * MP_TABLE) { ops.push_back({MP_MULT | (s0 + MP_TABLE - 1) << 8, 0}); ops.push_back({MP_MULT | (s0 + e - MP_TABLE - 1) << 8, 0}); }
+  else ops.push_back({MP_POW | s0 << 8, e});
+}
+// term_exps / term_offsets as at the ABI; coefficient index = term index - term_offsets[0]
+static void mp_compile(const uint32_t* term_exps, const size_t* term_offsets, size_t nc, size_t nv, const size_t* point_offsets, MpProgram* pg) {
+  // table depth per variable: the largest exponent any term asks for, at most MP_TABLE (gaps and tails of a Horner run are no larger)
+  u32 maxe[MP_MAX_VARS] = {};
+  for (size_t t = term_offsets[0]; t < term_offsets[nc]; t++)
+    for (size_t i = 0; i < nv; i++) maxe[i] = std::max(maxe[i], term_exps[t * nv + i]);
+  pg->slots = 0;
+  for (size_t i = 0; i < (size_t)MP_MAX_VARS; i++) {
+    const u32 e = i < nv ? maxe[i] : 0;
+    pg->vars.depth[i] = e > (u32)MP_TABLE ? (u32)MP_TABLE : e;
+    pg->vars.first_slot[i] = pg->slots;
+    pg->slots += pg->vars.depth[i];
+  }
+  pg->off.assign(1, 0);
+  for (size_t a = 0; a < nc; a++) {
+    std::vector<size_t> terms;
+    u32 cmax[MP_MAX_VARS] = {};
+    for (size_t t = term_offsets[a]; t < term_offsets[a + 1]; t++) {
+      bool vanishes = false;
+      for (size_t i = 0; i < nv; i++) {
+        const u32 e = term_exps[t * nv + i];
+        if (e && point_offsets[i + 1] == point_offsets[i]) vanishes = true;
+        cmax[i] = std::max(cmax[i], e);
+      }
+      if (!vanishes) terms.push_back(t);
+    }
+    size_t h = 0;                                        // the Horner variable
+    for (size_t i = 1; i < nv; i++) if (cmax[i] > cmax[h]) h = i;
+    auto rest_less = [&](size_t x, size_t y) {           // by the monomial of the other variables, then by falling exponent of h
+      for (size_t i = 0; i < nv; i++) {
+        if (i == h) continue;
+        const u32 ex = term_exps[x * nv + i], ey = term_exps[y * nv + i];
+        if (ex != ey) return ex < ey;
+      }
+      if (nv && term_exps[x * nv + h] != term_exps[y * nv + h]) return term_exps[x * nv + h] > term_exps[y * nv + h];
+      return x < y;
+    };
+    std::sort(terms.begin(), terms.end(), rest_less);
+    auto same_rest = [&](size_t x, size_t y) {
+      for (size_t i = 0; i < nv; i++) if (i != h && term_exps[x * nv + i] != term_exps[y * nv + i]) return false;
+      return true;
+    };
+    for (size_t r0 = 0; r0 < terms.size();) {
+      size_t r1 = r0 + 1;
+      while (r1 < terms.size() && same_rest(terms[r0], terms[r1])) r1++;
+      pg->ops.push_back({MP_LOADC, (u32)(terms[r0] - term_offsets[0])});
+      for (size_t q = r0 + 1; q < r1; q++) {
+        const u32 gap = nv ? term_exps[terms[q - 1] * nv + h] - term_exps[terms[q] * nv + h] : 0u;
+        const u32 ci = (u32)(terms[q] - term_offsets[0]);
+        if (gap == 0) pg->ops.push_back({MP_ADDC, ci});
+        else if (gap <= (u32)MP_TABLE) pg->ops.push_back({MP_HORNER | (pg->vars.first_slot[h] + gap - 1) << 8, ci});
+        else {
+          mp_emit_pow(pg->ops, pg->vars, (u32)h, gap);
+          // the product is below p + 1: the sum with a canonical coefficient is what HORNER leaves, one reduction more is harmless
+          pg->ops.push_back({MP_ADDC, ci});
+        }
+      }
+      if (nv) mp_emit_pow(pg->ops, pg->vars, (u32)h, term_exps[terms[r1 - 1] * nv + h]);
+      for (size_t i = 0; i < nv; i++) if (i != h) mp_emit_pow(pg->ops, pg->vars, (u32)i, term_exps[terms[r0] * nv + i]);
+      pg->ops.back().op |= MP_FLUSH;
+      r0 = r1;
+    }
+    pg->off.push_back((u32)pg->ops.size());
+  }
+}
+
+static inline unsigned mp_grid(size_t n, unsigned per) { return (unsigned)((n + per - 1) / per); }
+
+template <class P>
+static int mp_compose_dev(int fid, const uint64_t* term_coefs, const uint32_t* term_exps, const size_t* term_offsets, size_t nc, size_t nv,
+                          const void* d_point, const size_t* point_offsets, void* d_out, size_t out_stride, size_t* out_lens, hipStream_t s) {
+  MpPlan pl;
+  MZK_TRY(mp_plan(fid, term_exps, term_offsets, nc, nv, point_offsets, &pl));
+  if (nc == 0) return MZK_OK;
+  if (!out_lens || (out_stride && !d_out)) { set_error("mpoly_compose: null pointer"); return MZK_E_ARG; }
+  const size_t t0 = term_offsets[0], nt = term_offsets[nc] - t0;
+  if (nt && !term_coefs) { set_error("mpoly_compose: null pointer"); return MZK_E_ARG; }
+  if (nv && point_offsets[nv] > point_offsets[0] && !d_point) { set_error("mpoly_compose: null pointer"); return MZK_E_ARG; }
+  if (nt >= ((size_t)1 << 28)) { set_error("mpoly_compose: %zu terms (at most 2^28 - 1)", nt); return MZK_E_LENGTH; }     // op counters are 32 bits
+  const HostField* hf = host_field(fid);
+  const int nl = hf->nl;
+  for (size_t t = 0; t < nt; t++)
+    if (!h_is_canonical(hf, term_coefs + (t0 + t) * nl)) { set_error("mpoly_compose: term_coefs[%zu] not canonical", t0 + t); return MZK_E_RANGE; }
+  if (out_stride < pl.stride_min) { set_error("mpoly_compose: out_stride %zu is below the degree bound + 1 = %zu", out_stride, pl.stride_min); return MZK_E_LENGTH; }
+  if (out_stride == 0) { for (size_t a = 0; a < nc; a++) out_lens[a] = 0; return MZK_OK; }      // every constraint is empty or vanishes
+  MpProgram pg;
+  mp_compile(term_exps, term_offsets, nc, nv, point_offsets, &pg);
+  const size_t N = pl.n, esz = field_bytes(fid);
+  uint64_t root[4] = {0, 0, 0, 0};
+  unsigned lg = 0;
+  while (((size_t)1 << lg) < N) lg++;
+  MZK_TRY(mzk_root_of_unity(fid, lg, root));
+  // one blob: ops | offsets | coefficients | lengths
+  const size_t b_ops = (pg.ops.size() * sizeof(MpOp) + 15) & ~(size_t)15, b_off = (pg.off.size() * 4 + 15) & ~(size_t)15, b_coef = (nt * esz + 15) & ~(size_t)15;
+  const size_t b_tab = b_ops + b_off + b_coef;
+  char *d_tab, *d_E, *d_V;
+  unsigned long long* d_lens;
+  MZK_TRY(ws_get(WS_MISC_C, b_tab ? b_tab : 16, (void**)&d_tab));
+  MZK_TRY(ws_get(WS_MISC_D, nc * 8, (void**)&d_lens));
+  MZK_TRY(ws_get(WS_MISC_A, (nv ? nv : 1) * N * esz, (void**)&d_E));
+  MZK_TRY(ws_get(WS_MISC_B, nc * N * esz, (void**)&d_V));
+  std::vector<char> tab(b_tab);
+  if (!pg.ops.empty()) memcpy(tab.data(), pg.ops.data(), pg.ops.size() * sizeof(MpOp));
+  memcpy(tab.data() + b_ops, pg.off.data(), pg.off.size() * 4);
+  if (nt) memcpy(tab.data() + b_ops + b_off, term_coefs + t0 * nl, nt * esz);
+  auto fail = [&](int rc) { (void)hipStreamSynchronize(s); return rc; };       // nothing stays enqueued behind an error
+  // the blob is host memory of this call: every path below waits for the stream before it returns
+  MZK_HIP(hipMemcpyAsync(d_tab, tab.data(), b_tab, hipMemcpyHostToDevice, s));
+  if (hipMemsetAsync(d_lens, 0, nc * 8, s) != hipSuccess) return fail(MZK_E_HIP);
+  if (nv) {
+    MpRows R;
+    for (size_t i = 0; i <= (size_t)MP_MAX_VARS; i++) R.off[i] = point_offsets[i < nv ? i : nv] - point_offsets[0];
+    const char* pt = (const char*)d_point + point_offsets[0] * esz;
+    hipLaunchKernelGGL((k_mp_pad<P>), dim3(mp_grid(N, 256), (unsigned)nv), dim3(256), 0, s, (const u32*)pt, R, N, (u32*)d_E);
+    int rc = ntt_batch_dev_impl(fid, root, d_E, d_E, N, nv, 0, s);
+    if (rc != MZK_OK) return fail(rc);
+  }
+  hipLaunchKernelGGL((k_mp_terms<P>), dim3(mp_grid(N, MP_LANES), (unsigned)nc), dim3(MP_LANES), (size_t)pg.slots * P::L * MP_LANES * 4, s, (const u32*)d_E, N,
+                     (int)nv, pg.vars, (const MpOp*)d_tab, (const u32*)(d_tab + b_ops), (const u32*)(d_tab + b_ops + b_off), (u32*)d_V);
+  if (hipGetLastError() != hipSuccess) { set_error("mpoly_compose: launch failed"); return fail(MZK_E_HIP); }
+  int rc = ntt_batch_dev_impl(fid, root, d_V, d_V, N, nc, 1, s);
+  if (rc != MZK_OK) return fail(rc);
+  hipLaunchKernelGGL((k_mp_rows<P>), dim3(mp_grid(out_stride, 256), (unsigned)nc), dim3(256), 0, s, (const u32*)d_V, N, (u32*)d_out, out_stride, d_lens);
+  if (hipGetLastError() != hipSuccess) { set_error("mpoly_compose: launch failed"); return fail(MZK_E_HIP); }
+  std::vector<unsigned long long> lens(nc);
+  rc = d2h_sync(lens.data(), d_lens, nc * 8, s);
+  if (rc != MZK_OK) return fail(rc);
+  for (size_t a = 0; a < nc; a++) out_lens[a] = (size_t)lens[a];
+  return MZK_OK;
+}
+
+// v R mod p, R = 2^(29 L), as 32-bit words
+static void mp_mont_words(int fid, const uint64_t* v, u32* out8) {
+  const HostField* hf = host_field(fid);
+  uint64_t two[4] = {2, 0, 0, 0}, r[4] = {0, 0, 0, 0}, t[4] = {0, 0, 0, 0};
+  h_powmod_u64(hf, r, two, 29 * (fid == MZK_FIELD_M128 ? M128Params::L : FrParams::L));
+  h_mulmod(hf, t, v, r);
+  for (int i = 0; i < 8; i++) out8[i] = i < 2 * hf->nl ? (u32)(t[i / 2] >> (32 * (i & 1))) : 0u;
+}
+
+static int mp_lincomb_check(int fid, const size_t* offsets, size_t count, const uint64_t* weights, const size_t* shifts, size_t out_cap, const void* out,
+                            const size_t* out_len) {
+  if (!mp_field_ok(fid)) { set_error("poly_lincomb: bad field id %d", fid); return MZK_E_ARG; }
+  if (!out_len || (out_cap && !out) || (count && (!offsets || !weights || !shifts))) { set_error("poly_lincomb: null pointer"); return MZK_E_ARG; }
+  if (count >= ((size_t)1 << 31)) { set_error("poly_lincomb: %zu polynomials (at most 2^31 - 1)", count); return MZK_E_LENGTH; }
+  const HostField* hf = host_field(fid);
+  for (size_t i = 0; i < count; i++) {
+    if (offsets[i + 1] < offsets[i]) { set_error("poly_lincomb: offsets[%zu] = %zu is below offsets[%zu] = %zu", i + 1, offsets[i + 1], i, offsets[i]); return MZK_E_LENGTH; }
+    if (!h_is_canonical(hf, weights + i * hf->nl)) { set_error("poly_lincomb: weights[%zu] not canonical", i); return MZK_E_RANGE; }
+    size_t end;
+    if (__builtin_add_overflow(offsets[i + 1] - offsets[i], shifts[i], &end) || end > out_cap) {
+      set_error("poly_lincomb: polynomial %zu (%zu coefficients, shift %zu) does not fit out_cap = %zu", i, offsets[i + 1] - offsets[i], shifts[i], out_cap);
+      return MZK_E_LENGTH;
+    }
+  }
+  return MZK_OK;
+}
+// validated arguments
+template <class P>
+static int mp_lincomb_dev(int fid, const void* d_polys, const size_t* offsets, size_t count, const uint64_t* weights, const size_t* shifts, void* d_out,
+                          size_t out_cap, size_t* out_len, hipStream_t s) {
+  *out_len = 0;
+  if (out_cap == 0) return MZK_OK;
+  std::vector<MpLcItem> items(count);
+  const int nl = host_field(fid)->nl;
+  for (size_t i = 0; i < count; i++) {
+    items[i].off = offsets[i] - offsets[0]; items[i].len = offsets[i + 1] - offsets[i]; items[i].shift = shifts[i];
+    mp_mont_words(fid, weights + i * nl, items[i].w);
+    items[i].pad[0] = items[i].pad[1] = 0;
+  }
+  char* d_tab;
+  MZK_TRY(ws_get(WS_MISC_C, (count ? count : 1) * sizeof(MpLcItem) + 16, (void**)&d_tab));
+  unsigned long long* d_len = (unsigned long long*)d_tab;
+  MpLcItem* d_items = (MpLcItem*)(d_tab + 16);
+  auto fail = [&](int rc) { (void)hipStreamSynchronize(s); return rc; };
+  MZK_HIP(hipMemsetAsync(d_len, 0, 16, s));
+  if (count && hipMemcpyAsync(d_items, items.data(), count * sizeof(MpLcItem), hipMemcpyHostToDevice, s) != hipSuccess) return fail(MZK_E_HIP);
+  const char* base = (const char*)d_polys + (count ? offsets[0] : 0) * field_bytes(fid);
+  hipLaunchKernelGGL((k_mp_lincomb<P>), dim3(mp_grid(out_cap, 256)), dim3(256), 0, s, (const u32*)base, (const MpLcItem*)d_items, (u32)count, (u32*)d_out, out_cap,
+                     d_len);
+  if (hipGetLastError() != hipSuccess) { set_error("poly_lincomb: launch failed"); return fail(MZK_E_HIP); }
+  unsigned long long len = 0;
+  const int rc = d2h_sync(&len, d_len, 8, s);
+  if (rc != MZK_OK) return fail(rc);
+  *out_len = (size_t)len;
+  return MZK_OK;
+}
+
+}  // namespace mzk
+
+using namespace mzk;
+
+extern "C" {
+
+int mzk_mpoly_compose_plan(int field_id, const uint32_t* term_exps, const size_t* term_offsets, size_t n_constraints, size_t n_vars,
+                           const size_t* point_offsets, size_t* n_transform, size_t* out_stride_min, size_t* bounds) {
+  if (!n_transform || !out_stride_min) { set_error("mpoly_compose_plan: null pointer"); return MZK_E_ARG; }
+  MpPlan pl;
+  MZK_TRY(mp_plan(field_id, term_exps, term_offsets, n_constraints, n_vars, point_offsets, &pl));
+  *n_transform = pl.n;
+  *out_stride_min = pl.stride_min;
+  if (bounds) for (size_t a = 0; a < n_constraints; a++) bounds[a] = pl.bounds[a];
+  return MZK_OK;
+}
+
+int mzk_mpoly_compose_dev(int field_id, const uint64_t* term_coefs, const uint32_t* term_exps, const size_t* term_offsets, size_t n_constraints,
+                          size_t n_vars, const void* d_point, const size_t* point_offsets, void* d_out, size_t out_stride, size_t* out_lens,
+                          void* stream) {
+  MZK_ENTER();
+  if (!mp_field_ok(field_id)) { set_error("mpoly_compose: bad field id %d", field_id); return MZK_E_ARG; }
+  WsGuard wsg((hipStream_t)stream);
+  return field_id == MZK_FIELD_M128
+             ? mp_compose_dev<M128Params>(field_id, term_coefs, term_exps, term_offsets, n_constraints, n_vars, d_point, point_offsets, d_out, out_stride, out_lens, (hipStream_t)stream)
+             : mp_compose_dev<FrParams>(field_id, term_coefs, term_exps, term_offsets, n_constraints, n_vars, d_point, point_offsets, d_out, out_stride, out_lens, (hipStream_t)stream);
+}
+
+int mzk_mpoly_compose(int field_id, const uint64_t* term_coefs, const uint32_t* term_exps, const size_t* term_offsets, size_t n_constraints,
+                      size_t n_vars, const uint64_t* point, const size_t* point_offsets, uint64_t* out, size_t out_stride, size_t* out_lens) {
+  MZK_ENTER();
+  MpPlan pl;
+  MZK_TRY(mp_plan(field_id, term_exps, term_offsets, n_constraints, n_vars, point_offsets, &pl));
+  if (n_constraints == 0) return MZK_OK;
+  if (!out_lens || (out_stride && !out)) { set_error("mpoly_compose: null pointer"); return MZK_E_ARG; }
+  const HostField* hf = host_field(field_id);
+  const size_t esz = field_bytes(field_id), p0 = n_vars ? point_offsets[0] : 0, np = n_vars ? point_offsets[n_vars] - p0 : 0;
+  if (np && !point) { set_error("mpoly_compose: null pointer"); return MZK_E_ARG; }
+  for (size_t i = 0; i < np; i++)
+    if (!h_is_canonical(hf, point + (p0 + i) * hf->nl)) { set_error("mpoly_compose: point[%zu] not canonical", p0 + i); return MZK_E_RANGE; }
+  if (out_stride > ((size_t)1 << 40) / n_constraints) { set_error("mpoly_compose: out_stride too large"); return MZK_E_LENGTH; }
+  hipStream_t s = ctx().stream;
+  WsGuard wsg(s);
+  char *d_p, *d_o;
+  MZK_TRY(ws_get(WS_MISC_E, (np ? np : 1) * esz, (void**)&d_p));
+  MZK_TRY(ws_get(WS_MISC_F, (n_constraints * out_stride + 1) * esz, (void**)&d_o));
+  // offsets relative to the staged copy
+  std::vector<size_t> rel(n_vars + 1, 0);
+  for (size_t i = 0; i <= n_vars && n_vars; i++) rel[i] = point_offsets[i] - p0;
+  if (np) MZK_HIP(hipMemcpyAsync(d_p, point + p0 * hf->nl, np * esz, hipMemcpyHostToDevice, s));
+  const int rc = field_id == MZK_FIELD_M128
+                     ? mp_compose_dev<M128Params>(field_id, term_coefs, term_exps, term_offsets, n_constraints, n_vars, d_p, rel.data(), d_o, out_stride, out_lens, s)
+                     : mp_compose_dev<FrParams>(field_id, term_coefs, term_exps, term_offsets, n_constraints, n_vars, d_p, rel.data(), d_o, out_stride, out_lens, s);
+  if (rc != MZK_OK) { (void)hipStreamSynchronize(s); return rc; }
+  if (out_stride == 0) return MZK_OK;
+  return d2h_sync(out, d_o, n_constraints * out_stride * esz, s);
+}
+
+int mzk_poly_lincomb_dev(int field_id, const void* d_polys, const size_t* offsets, size_t count, const uint64_t* weights, const size_t* shifts,
+                         void* d_out, size_t out_cap, size_t* out_len, void* stream) {
+  MZK_ENTER();
+  MZK_TRY(mp_lincomb_check(field_id, offsets, count, weights, shifts, out_cap, d_out, out_len));
+  if (count && offsets[count] > offsets[0] && !d_polys) { set_error("poly_lincomb: null pointer"); return MZK_E_ARG; }
+  WsGuard wsg((hipStream_t)stream);
+  return field_id == MZK_FIELD_M128 ? mp_lincomb_dev<M128Params>(field_id, d_polys, offsets, count, weights, shifts, d_out, out_cap, out_len, (hipStream_t)stream)
+                                    : mp_lincomb_dev<FrParams>(field_id, d_polys, offsets, count, weights, shifts, d_out, out_cap, out_len, (hipStream_t)stream);
+}
+
+int mzk_poly_lincomb(int field_id, const uint64_t* polys, const size_t* offsets, size_t count, const uint64_t* weights, const size_t* shifts,
+                     uint64_t* out, size_t out_cap, size_t* out_len) {
+  MZK_ENTER();
+  MZK_TRY(mp_lincomb_check(field_id, offsets, count, weights, shifts, out_cap, out, out_len));
+  const HostField* hf = host_field(field_id);
+  const size_t esz = field_bytes(field_id), p0 = count ? offsets[0] : 0, np = count ? offsets[count] - p0 : 0;
+  if (np && !polys) { set_error("poly_lincomb: null pointer"); return MZK_E_ARG; }
+  for (size_t i = 0; i < np; i++)
+    if (!h_is_canonical(hf, polys + (p0 + i) * hf->nl)) { set_error("poly_lincomb: polys[%zu] not canonical", p0 + i); return MZK_E_RANGE; }
+  hipStream_t s = ctx().stream;
+  WsGuard wsg(s);
+  char *d_p, *d_o;
+  MZK_TRY(ws_get(WS_MISC_E, (np ? np : 1) * esz, (void**)&d_p));
+  MZK_TRY(ws_get(WS_MISC_F, (out_cap ? out_cap : 1) * esz, (void**)&d_o));
+  std::vector<size_t> rel(count + 1, 0);
+  for (size_t i = 0; i <= count; i++) rel[i] = count ? offsets[i] - p0 : 0;
+  if (np) MZK_HIP(hipMemcpyAsync(d_p, polys + p0 * hf->nl, np * esz, hipMemcpyHostToDevice, s));
+  const int rc = field_id == MZK_FIELD_M128 ? mp_lincomb_dev<M128Params>(field_id, d_p, rel.data(), count, weights, shifts, d_o, out_cap, out_len, s)
+                                            : mp_lincomb_dev<FrParams>(field_id, d_p, rel.data(), count, weights, shifts, d_o, out_cap, out_len, s);
+  if (rc != MZK_OK) { (void)hipStreamSynchronize(s); return rc; }
+  if (out_cap == 0) return MZK_OK;
+  return d2h_sync(out, d_o, out_cap * esz, s);
+}
+
+}  // extern "C"

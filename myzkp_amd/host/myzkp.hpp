@@ -32,6 +32,7 @@
 #include <string>
 #include <type_traits>
 #include <utility>
+#include <map>
 #include <vector>
 #include <exception>
 #include "../../include/mzk.h"
@@ -273,6 +274,77 @@ std::vector<F> fri_split_and_fold(const std::vector<F>& codeword, const F& alpha
   std::vector<uint64_t> out((codeword.size() / 2 + 1) * F().value.size());
   expect(mzk_fri_fold(Polynomial<F>::field_id(), c.data(), codeword.size(), alpha.value.data(), offset.value.data(), omega.value.data(), out.data()));
   return from_wire<F>(out, codeword.size() / 2);
+}
+
+// ---- MPolynomial<F> (algebra/mpolynomials.rs:9-12): exponent vector -> coefficient --------------------------
+// An ordered map stands in for the HashMap (the iteration order of evaluate_symbolic's sum does not matter in a field).
+template <class F> struct MPolynomial {
+  std::map<std::vector<size_t>, F> dictionary;
+
+  // the flat term table of mzk_mpoly_compose for a set of polynomials over n_vars variables (shorter keys are padded with zeros,
+  // as Add / Mul pad them, mpolynomials.rs:219-230)
+  static void term_table(const std::vector<MPolynomial>& ms, size_t n_vars, std::vector<uint64_t>& coefs, std::vector<uint32_t>& exps, std::vector<size_t>& offsets) {
+    offsets.assign(1, 0);
+    for (const MPolynomial& m : ms) {
+      for (const auto& kv : m.dictionary) {
+        if (kv.first.size() > n_vars) throw Panic(MZK_E_LENGTH, "index out of bounds: the len is " + std::to_string(n_vars) + " but the index is " + std::to_string(n_vars));
+        for (size_t i = 0; i < n_vars; i++) {
+          const size_t e = i < kv.first.size() ? kv.first[i] : 0;
+          if (e > 0xffffffffu) throw Panic(MZK_E_LENGTH, "exponent above 2^32 - 1");
+          exps.push_back((uint32_t)e);
+        }
+        coefs.insert(coefs.end(), kv.second.value.begin(), kv.second.value.end());
+      }
+      offsets.push_back(coefs.size() / F().value.size());
+    }
+  }
+  // mpolynomials.rs:125-141
+  Polynomial<F> evaluate_symbolic(const std::vector<Polynomial<F>>& point) const { return evaluate_symbolic_many({*this}, point)[0]; }
+  // every constraint of an AIR over one point in one call (fast_stark.rs:246-259 loops over them)
+  static std::vector<Polynomial<F>> evaluate_symbolic_many(const std::vector<MPolynomial>& ms, const std::vector<Polynomial<F>>& point) {
+    const size_t nl = F().value.size(), nv = point.size();
+    std::vector<uint64_t> coefs, pt;
+    std::vector<uint32_t> exps;
+    std::vector<size_t> toff, poff(1, 0);
+    term_table(ms, nv, coefs, exps, toff);
+    for (const Polynomial<F>& q : point) {
+      auto w = to_wire(q.coef);
+      pt.insert(pt.end(), w.begin(), w.end());
+      poff.push_back(pt.size() / nl);
+    }
+    size_t n = 0, stride = 0;
+    expect(mzk_mpoly_compose_plan(Polynomial<F>::field_id(), exps.data(), toff.data(), ms.size(), nv, poff.data(), &n, &stride, nullptr));
+    std::vector<uint64_t> out((ms.size() * stride + 1) * nl);
+    std::vector<size_t> lens(ms.size() + 1);
+    expect(mzk_mpoly_compose(Polynomial<F>::field_id(), coefs.data(), exps.data(), toff.data(), ms.size(), nv, pt.data(), poff.data(), out.data(), stride,
+                             lens.data()));
+    std::vector<Polynomial<F>> res(ms.size());
+    for (size_t a = 0; a < ms.size(); a++) {
+      res[a].coef.resize(lens[a]);
+      for (size_t i = 0; i < lens[a]; i++) std::memcpy(res[a].coef[i].value.data(), &out[(a * stride + i) * nl], 8 * nl);
+    }
+    return res;
+  }
+};
+// the weighted sum of FastStark::prove (fast_stark.rs:301-326): sum_i weights[i] * X^shifts[i] * terms[i]
+template <class F>
+Polynomial<F> weighted_combination(const std::vector<Polynomial<F>>& terms, const std::vector<F>& weights, const std::vector<size_t>& shifts) {
+  if (weights.size() != terms.size() || shifts.size() != terms.size()) throw Panic(MZK_E_LENGTH, "index out of bounds: weights / shifts / terms differ in length");
+  const size_t nl = F().value.size();
+  std::vector<uint64_t> flat;
+  std::vector<size_t> off(1, 0);
+  size_t cap = 0;
+  for (size_t i = 0; i < terms.size(); i++) {
+    auto w = to_wire(terms[i].coef);
+    flat.insert(flat.end(), w.begin(), w.end());
+    off.push_back(flat.size() / nl);
+    cap = std::max(cap, terms[i].coef.size() + shifts[i]);
+  }
+  auto w = to_wire(weights);
+  std::vector<uint64_t> out((cap + 1) * nl);
+  size_t len = 0;
+  expect(mzk_poly_lincomb(Polynomial<F>::field_id(), flat.data(), off.data(), terms.size(), w.data(), shifts.data(), out.data(), cap, &len));
+  return Polynomial<F>{from_wire<F>(out, len)};
 }
 
 
