@@ -144,6 +144,20 @@ int mzk_kzg_prove_degree_bound(const uint64_t* coef, size_t n, const uint64_t* p
  * lhs.degree(), :285 -- a zero lhs included).  out must hold ll coefficients; *out_len receives the count. */
 int mzk_fast_coset_divide(int field_id, const uint64_t* lhs, size_t ll, const uint64_t* rhs, size_t lr, const uint64_t* offset,
                           const uint64_t* root, size_t root_order, uint64_t* out, size_t* out_len);
+/* The same division for `count` numerators in HBM over ONE denominator in HBM (FastStark::prove divides every transition polynomial by
+ * the one transition zerofier, fast_stark.rs:261-273).  Numerator i = d_lhs[i * lhs_stride ..], lhs_lens[i] coefficients (need not be
+ * trimmed: the trimmed lengths of the numerators and of the denominator are found on the device first, one wait); quotient i =
+ * d_out[i * out_stride ..], out_lens[i] coefficients and zeros behind them up to out_stride.  Every row is bit-identical to
+ * mzk_fast_coset_divide of that row, with the same error mapping (the first offending row decides) and the same degree < 8 branch (at
+ * most 8 coefficients of such a row visit the host).  Rows whose squared-down order (ntt.rs:298-302) agrees share one batched forward
+ * transform, one denominator transform, one division launch whose inversion chain serves all of them, one batched inverse transform and
+ * one scale-back launch.  Also MZK_E_LENGTH: lhs_lens[i] > lhs_stride, a quotient longer than out_stride.  lhs_lens, offset, root and
+ * out_lens are host memory; d_lhs and d_rhs complete on `stream` before the call (canonical, not checked); d_out must not overlap them;
+ * returns when d_out is complete.  On an error d_out and out_lens are undefined (every assertion is checked before any quotient is
+ * enqueued).  Rows of degree < 8 cost two more waits for all of them together.  count == 0: MZK_OK. */
+int mzk_fast_coset_divide_batch_dev(int field_id, const void* d_lhs, size_t lhs_stride, const size_t* lhs_lens, size_t count, const void* d_rhs,
+                                    size_t rhs_len, const uint64_t* offset, const uint64_t* root, size_t root_order, void* d_out, size_t out_stride,
+                                    size_t* out_lens, void* stream);
 
 /* ntt::fast_zerofier / fast_evaluate / fast_interpolate (algebra/ntt.rs:118-252; FastStark::prove interpolates every
  * trace register with fast_interpolate, zkstark/fast_stark.rs:209, and builds its transition zerofier with
@@ -581,6 +595,107 @@ int mzk_poly_lincomb(int field_id, const uint64_t* polys, const size_t* offsets,
                      uint64_t* out, size_t out_cap, size_t* out_len);
 int mzk_poly_lincomb_dev(int field_id, const void* d_polys, const size_t* offsets, size_t count, const uint64_t* weights, const size_t* shifts,
                          void* d_out, size_t out_cap, size_t* out_len, void* stream);
+/* Division by a product of linear factors, many rows at once (the boundary quotients of fast_stark.rs:217-224,
+ * (tp - interpolant) / zerofier with zerofier = prod_j (X - r_j)).  Row i = polys[i * stride ..], lens[i] coefficients in ascending
+ * degree, is divided by prod (X - roots[j]), j in [root_offsets[i], root_offsets[i+1]) (count + 1 offsets, in elements of `roots`):
+ * the quotient of Polynomial long division (polynomial.rs:371-405), remainder dropped, trimmed.  Because the interpolant has a lower
+ * degree than the zerofier, that quotient is floor(tp / zerofier) whatever the interpolant is, so it is neither an argument nor
+ * computed; the division need not be exact.  One synthetic division per root (the engine of the KZG openings, over either field);
+ * rows are independent jobs, round r handles every row with more than r roots.
+ *   lens need NOT be trimmed: the division runs over the coefficients as given and the trimmed length is found on the device at the
+ *     end, so an input with leading zeros gives the reference's result for its trimmed form.
+ *   out row i = out[i * stride ..] (the same stride): out_lens[i] coefficients, zeros behind them up to stride.  No roots: the row,
+ *     trimmed.  Trimmed length <= number of roots: the zero polynomial, out_lens[i] = 0 (polynomial.rs:372).  Repeated roots are legal.
+ *     out must not overlap polys.  polys and out each hold count * stride elements: the last row, too, is a full stride (the host form
+ *     copies the block whole; only the lens[i] coefficients of a row are read as values or range-checked).
+ * lens, roots (canonical), root_offsets and out_lens are host memory in both forms; the _dev form takes rows in HBM (canonical, not
+ * checked), complete on `stream` before the call, and returns when d_out and out_lens are complete.
+ * Errors, with nothing left enqueued: bad field, null pointer: MZK_E_ARG; a root or (host form) a coefficient not canonical:
+ * MZK_E_RANGE; decreasing root_offsets, lens[i] > stride, more than 2^40 elements in all: MZK_E_LENGTH.  count == 0: MZK_OK. */
+int mzk_poly_div_roots(int field_id, const uint64_t* polys, size_t stride, const size_t* lens, size_t count, const uint64_t* roots,
+                       const size_t* root_offsets, uint64_t* out, size_t* out_lens);
+int mzk_poly_div_roots_dev(int field_id, const void* d_polys, size_t stride, const size_t* lens, size_t count, const uint64_t* roots,
+                           const size_t* root_offsets, void* d_out, size_t* out_lens, void* stream);
+/* ---- FastStark: the sizes of a proof before there is a trace (host only, needs no device) ---------------------------------------
+ * Everything initialize_fast_stark_m128 (zkstark/fast_stark.rs:573-616), the degree helpers (:77-111, :150-160) and FRI::num_rounds
+ * (fri.rs:86-97) derive from the parameters, the AIR and the boundary -- the lengths, strides and shifts a caller needs to run
+ * FastStark::prove stage by stage over the *_dev entry points:
+ *   num_randomizers = 4 * num_colinearity_checks; randomized_trace_length = num_cycles + num_randomizers;
+ *   omicron_domain_length = 1 << bit_length(randomized_trace_length * transition_constraints_degree); fri_domain_length = that * expansion_factor;
+ *   transition_degree_bounds[a] = max over the terms of constraint a of k[0] + (randomized_trace_length - 1) * (k[1] + .. + k[2 m])
+ *     (0 without terms); transition_quotient_degree_bounds[a] = that - (num_cycles - 1);
+ *   max_degree = (1 << bits(max_a quotient bound)) - 1, bits(0) = 1 as format!("{:b}", 0) has one digit; randomizer_length = max_degree + 1;
+ *   boundary_counts[s] = boundary entries of register s (the degree of its zerofier; a cell listed twice counts twice; an entry whose
+ *     register is >= num_registers is ignored, as the reference's `if *r == s` ignores it); boundary_quotient_degree_bounds[s] =
+ *     randomized_trace_length - 1 - boundary_counts[s];
+ *   transition_shifts[a] / boundary_shifts[s] = max_degree - the quotient's degree bound (the X^shift terms of fast_stark.rs:301-326);
+ *   n_weights = 1 + 2 * n_constraints + 2 * num_registers; fri_num_rounds, fri_last_length = fri_domain_length >> (rounds - 1);
+ *   num_indices = 4 * num_colinearity_checks, the duplicated indices at which every codeword is opened (fast_stark.rs:338-346).
+ * The AIR is the flat term table of mzk_mpoly_compose with n_vars = 1 + 2 * num_registers (X, the registers, the registers one cycle on),
+ * so num_registers <= MZK_STARK_MAX_REGISTERS = (MZK_MPOLY_MAX_VARS - 1) / 2 = 3 today; the coefficients are not needed.
+ * Errors: bad field, null pointer, more registers or constraints than the limits, no constraint at all (the reference unwraps the maximum of an
+ * empty list): MZK_E_ARG; expansion_factor not a power of two: MZK_E_NOT_POW2; every usize subtraction that would underflow in Rust
+ * (num_cycles - 1, bound - (num_cycles - 1), randomized degree - boundary count, max_degree - boundary bound), an overflowing product,
+ * a FRI domain beyond the transform size limit of the field, decreasing term_offsets, fewer than two FRI rounds: MZK_E_LENGTH; more
+ * colinearity checks than the last FRI codeword has elements: MZK_E_ARG (as mzk_fri_prove). */
+enum { MZK_STARK_MAX_REGISTERS = 3, MZK_STARK_MAX_CONSTRAINTS = 16 };
+typedef struct mzk_stark_dims {
+  uint64_t num_randomizers, randomized_trace_length, omicron_domain_length, fri_domain_length;
+  uint64_t num_registers, n_vars, n_constraints;
+  uint64_t max_degree, randomizer_length, n_weights, fri_num_rounds, fri_last_length, num_indices;
+  uint64_t transition_degree_bounds[MZK_STARK_MAX_CONSTRAINTS], transition_quotient_degree_bounds[MZK_STARK_MAX_CONSTRAINTS],
+      transition_shifts[MZK_STARK_MAX_CONSTRAINTS];
+  uint64_t boundary_counts[MZK_STARK_MAX_REGISTERS], boundary_quotient_degree_bounds[MZK_STARK_MAX_REGISTERS], boundary_shifts[MZK_STARK_MAX_REGISTERS];
+} mzk_stark_dims;
+int mzk_stark_plan(int field_id, size_t expansion_factor, size_t num_colinearity_checks, size_t num_registers, size_t num_cycles,
+                   size_t transition_constraints_degree, const uint32_t* term_exps, const size_t* term_offsets, size_t n_constraints,
+                   const size_t* boundary_cycles, const size_t* boundary_registers, size_t n_boundary, mzk_stark_dims* out);
+/* ---- FastStark::prove in one call (zkstark/fast_stark.rs:177-396) -------------------------------------------------------------------
+ * mzk_stark_new is FastStark + preprocess (fast_stark.rs:52-75, :573-616): omega / omicron from mzk_root_of_unity, `generator` the
+ * caller's coset offset (M128: 85408008396924667383611388730472331217), the AIR as the flat term table of mzk_mpoly_compose over
+ * 1 + 2 * num_registers variables; it builds fast_zerofier over omicron^0 .. omicron^(T-2), its coset codeword and its Merkle tree (kept
+ * for the openings), and allocates every buffer a prove needs (MZK_E_NOMEM).  Errors of mzk_stark_plan apply; num_cycles < 2: MZK_E_LENGTH.
+ * mzk_stark_transition_zerofier_root: the 32-byte root the verifier is given.  mzk_stark_dims_of: the plan without a boundary (the
+ * boundary_* fields are zero; mzk_stark_plan with the boundary gives the dims of a proof).
+ *
+ * mzk_stark_prove: trace = num_cycles + num_randomizers rows of num_registers elements, row-major as Trace<F> is -- THE CALLER appends
+ * the random rows and supplies the max_degree + 1 random coefficients of the randomizer polynomial; the library draws no randomness, so
+ * the call is a pure function of its arguments.  boundary entry j = (boundary_cycles[j], boundary_registers[j], boundary_values[j]); the
+ * values do not enter the proof (the boundary quotient is floor(tp / zerofier) whatever the interpolant is) and are only range-checked.
+ * Stages and pushes in the reference's order: bqc_root[0..m), rdc_root, weights = sample_weights(1 + 2 n_constraints + 2 m,
+ * SHAKE256(stream)[0..32]) hashed on the host from the roots; FRI::prove on its own empty stream (mzk_fri_prove); the top-level indices
+ * sorted, duplicated (+ expansion_factor, then + fri_domain_length / 2, mod the length, sorted), and all m + 2 trees opened there.
+ * The packed proof (mzk_stark_proof_layout; sections 8-byte aligned, path entries MZK_FRI_PATH_STRIDE bytes, zero padded):
+ *   MZK_STARK_STATUS      u64: the FRI sampler's status word (non-zero: MZK_E_RANGE, as mzk_fri_prove)
+ *   MZK_STARK_FRI         the packed proof of mzk_fri_proof_layout verbatim, except that MZK_FRI_TOP_INDICES holds the SORTED indices
+ *                         (fast_stark.rs:338); the revealed layers stay in sampling order
+ *   MZK_STARK_INDICES     4 * checks x u64: the duplicated indices, sorted
+ *   MZK_STARK_BQC_ROOTS   m x 32 bytes;  MZK_STARK_RDC_ROOT  32 bytes
+ *   MZK_STARK_BQC_POINTS  m x 4 * checks elements (register-major);  MZK_STARK_RDC_POINTS, MZK_STARK_TZC_POINTS  4 * checks elements
+ *   MZK_STARK_BQC_PATHS, _RDC_PATHS, _TZC_PATHS   per opened index log2(fri_domain_length) entries: the sibling leaf's bytes, then digests
+ *   MZK_STARK_PATH_LENS   one u64 per path entry, in the order bqc, rdc, tzc
+ * Errors before anything is enqueued: null pointer MZK_E_ARG; n_rows != num_cycles + num_randomizers, proof_cap below the layout's total,
+ * the plan's errors for this boundary: MZK_E_LENGTH; (host form) a trace element, randomizer coefficient or boundary value not canonical:
+ * MZK_E_RANGE.  Errors of a stage map as the stage maps them (a transition polynomial that is zero or of lower degree than the zerofier:
+ * MZK_E_LENGTH, ntt.rs:285).  The _dev form takes trace, randomizer and proof in HBM, complete on `stream` before the call, and returns
+ * when the proof is complete.  One prove at a time per handle.  Not kept between calls yet: the inverse of the zerofier's coset
+ * transform (mzk_fast_coset_divide_batch_dev recomputes it). */
+typedef struct mzk_stark mzk_stark;
+enum { MZK_STARK_STATUS = 0, MZK_STARK_FRI = 1, MZK_STARK_INDICES = 2, MZK_STARK_BQC_ROOTS = 3, MZK_STARK_RDC_ROOT = 4, MZK_STARK_BQC_POINTS = 5,
+       MZK_STARK_RDC_POINTS = 6, MZK_STARK_TZC_POINTS = 7, MZK_STARK_BQC_PATHS = 8, MZK_STARK_RDC_PATHS = 9, MZK_STARK_TZC_PATHS = 10,
+       MZK_STARK_PATH_LENS = 11, MZK_STARK_SECTIONS = 12 };
+/* host only: offsets / sizes have MZK_STARK_SECTIONS entries (each may be NULL); dims as mzk_stark_plan filled them (MZK_E_LENGTH otherwise) */
+int mzk_stark_proof_layout(const mzk_stark_dims* dims, int field_id, uint64_t* offsets, uint64_t* sizes, uint64_t* total_bytes);
+int mzk_stark_new(int field_id, size_t expansion_factor, size_t num_colinearity_checks, size_t num_registers, size_t num_cycles,
+                  size_t transition_constraints_degree, const uint64_t* generator, const uint64_t* term_coefs, const uint32_t* term_exps,
+                  const size_t* term_offsets, size_t n_constraints, mzk_stark** out);
+void mzk_stark_free(mzk_stark* h);
+int mzk_stark_transition_zerofier_root(const mzk_stark* h, uint8_t root[32]);
+int mzk_stark_dims_of(const mzk_stark* h, mzk_stark_dims* out);
+int mzk_stark_prove(mzk_stark* h, const uint64_t* trace, size_t n_rows, const size_t* boundary_cycles, const size_t* boundary_registers,
+                    const uint64_t* boundary_values, size_t n_boundary, const uint64_t* randomizer, uint8_t* proof_out, size_t proof_cap);
+int mzk_stark_prove_dev(mzk_stark* h, const void* d_trace, size_t n_rows, const size_t* boundary_cycles, const size_t* boundary_registers,
+                        const uint64_t* boundary_values, size_t n_boundary, const void* d_randomizer, void* d_proof, size_t proof_cap, void* stream);
 
 /* Build an SRS handle from points already in HBM (affine canonical, n * 8 limbs).  The _ex form chooses
  * whether the window tables are built (worth it from ~30 commits per SRS on at 2^20 points; a one-shot pipeline keeps

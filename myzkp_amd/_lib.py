@@ -887,6 +887,19 @@ def _np2(x):
     return p
 
 
+def fast_coset_divide_batch_dev(fid, d_lhs_ptr, lhs_stride, lhs_lens, d_rhs_ptr, rhs_len, offset, root, root_order, d_out_ptr, out_stride, stream=0):
+    """mzk_fast_coset_divide_batch_dev: numerators (rows of lhs_stride elements) and one denominator in HBM (raw device pointers), quotient
+    rows of out_stride elements written at d_out_ptr; returns the quotient lengths."""
+    count = len(lhs_lens)
+    ln = (ctypes.c_size_t * max(count, 1))(*[int(x) for x in lhs_lens])
+    out_lens = (ctypes.c_size_t * max(count, 1))()
+    o, r = _one(fid, offset), _one(fid, root)
+    _check(lib().mzk_fast_coset_divide_batch_dev(int(fid), ctypes.c_void_p(d_lhs_ptr), ctypes.c_size_t(lhs_stride), ln, ctypes.c_size_t(count),
+                                                 ctypes.c_void_p(d_rhs_ptr), ctypes.c_size_t(rhs_len), _p(o), _p(r), ctypes.c_size_t(root_order),
+                                                 ctypes.c_void_p(d_out_ptr), ctypes.c_size_t(out_stride), out_lens, ctypes.c_void_p(stream)))
+    return [int(out_lens[i]) for i in range(count)]
+
+
 def fast_zerofier(fid, domain, root, root_order):
     """ntt::fast_zerofier (algebra/ntt.rs:118-144)."""
     d = _arr(fid, domain)
@@ -1037,6 +1050,194 @@ def poly_lincomb_dev(fid, d_polys_ptr, lens, weights, shifts, d_out_ptr, out_cap
     _check(lib().mzk_poly_lincomb_dev(int(fid), ctypes.c_void_p(d_polys_ptr), _offsets_of(lens), ctypes.c_size_t(count), _p(w), sh,
                                       ctypes.c_void_p(d_out_ptr), ctypes.c_size_t(out_cap), ctypes.byref(n), ctypes.c_void_p(stream)))
     return n.value
+
+
+def poly_div_roots(fid, polys, roots, stride=None):
+    """Row i of `polys` (a list of (n_i, limbs) arrays, need not be trimmed) divided by prod (X - r) over roots[i] (a list of integers,
+    may be empty or repeat): the trimmed quotients of Polynomial long division (polynomial.rs:371-405), remainder dropped --
+    the boundary quotients of fast_stark.rs:217-224.  mzk_poly_div_roots."""
+    ps = [_arr(fid, q) for q in polys]
+    count, nl = len(ps), LIMBS[fid]
+    if len(roots) != count:
+        raise MzkError(-5, "poly_div_roots: %d rows, %d root lists" % (count, len(roots)))
+    if stride is None:
+        stride = max([q.shape[0] for q in ps] + [0])
+    flat = np.zeros((max(count * stride, 1), nl), dtype=np.uint64)
+    for i, q in enumerate(ps):
+        flat[i * stride:i * stride + min(q.shape[0], stride)] = q[:stride]
+    lens = (ctypes.c_size_t * max(count, 1))(*[q.shape[0] for q in ps])
+    rs = [int(r) for row in roots for r in row]
+    r = to_limbs(rs, nl) if rs else np.zeros((1, nl), dtype=np.uint64)
+    out = np.zeros_like(flat)
+    out_lens = (ctypes.c_size_t * max(count, 1))()
+    _check(lib().mzk_poly_div_roots(int(fid), _p(flat), ctypes.c_size_t(stride), lens, ctypes.c_size_t(count), _p(r),
+                                    _offsets_of([len(row) for row in roots]), _p(out), out_lens))
+    return [out[i * stride:i * stride + int(out_lens[i])].copy() for i in range(count)]
+
+
+def poly_div_roots_dev(fid, d_polys_ptr, stride, lens, roots, d_out_ptr, stream=0):
+    """mzk_poly_div_roots_dev: rows of `stride` elements in HBM (raw device pointers, out rows at the same stride, not overlapping the
+    input); roots[i] as in poly_div_roots; returns the trimmed quotient lengths."""
+    count, nl = len(lens), LIMBS[fid]
+    if len(roots) != count:
+        raise MzkError(-5, "poly_div_roots: %d rows, %d root lists" % (count, len(roots)))
+    rs = [int(r) for row in roots for r in row]
+    r = to_limbs(rs, nl) if rs else np.zeros((1, nl), dtype=np.uint64)
+    ln = (ctypes.c_size_t * max(count, 1))(*[int(x) for x in lens])
+    out_lens = (ctypes.c_size_t * max(count, 1))()
+    _check(lib().mzk_poly_div_roots_dev(int(fid), ctypes.c_void_p(d_polys_ptr), ctypes.c_size_t(stride), ln, ctypes.c_size_t(count), _p(r),
+                                        _offsets_of([len(row) for row in roots]), ctypes.c_void_p(d_out_ptr), out_lens, ctypes.c_void_p(stream)))
+    return [int(out_lens[i]) for i in range(count)]
+
+
+STARK_MAX_REGISTERS, STARK_MAX_CONSTRAINTS = 3, 16
+
+
+class StarkDims(ctypes.Structure):
+    """mzk_stark_dims (include/mzk.h)"""
+    _scalars = ("num_randomizers", "randomized_trace_length", "omicron_domain_length", "fri_domain_length", "num_registers", "n_vars",
+                "n_constraints", "max_degree", "randomizer_length", "n_weights", "fri_num_rounds", "fri_last_length", "num_indices")
+    _per_constraint = ("transition_degree_bounds", "transition_quotient_degree_bounds", "transition_shifts")
+    _per_register = ("boundary_counts", "boundary_quotient_degree_bounds", "boundary_shifts")
+    _fields_ = ([(k, ctypes.c_uint64) for k in _scalars] + [(k, ctypes.c_uint64 * STARK_MAX_CONSTRAINTS) for k in _per_constraint] +
+                [(k, ctypes.c_uint64 * STARK_MAX_REGISTERS) for k in _per_register])
+
+
+def stark_plan(fid, expansion_factor, num_colinearity_checks, num_registers, num_cycles, transition_constraints_degree, constraints, boundary):
+    """mzk_stark_plan (host only): the sizes FastStark derives from its parameters (fast_stark.rs:573-616, :77-111, :150-160) as a dict.
+    constraints as in mpoly_term_table over 1 + 2 * num_registers variables (the coefficients are not used); boundary: (cycle, register[, value])."""
+    nv = 1 + 2 * int(num_registers)
+    _, te, toff = mpoly_term_table(fid, constraints, nv)
+    nb = len(boundary)
+    bc = (ctypes.c_size_t * max(nb, 1))(*[int(b[0]) for b in boundary])
+    br = (ctypes.c_size_t * max(nb, 1))(*[int(b[1]) for b in boundary])
+    d = StarkDims()
+    sz = ctypes.c_size_t
+    _check(lib().mzk_stark_plan(int(fid), sz(expansion_factor), sz(num_colinearity_checks), sz(num_registers), sz(num_cycles),
+                                sz(transition_constraints_degree), _p(te), toff, sz(len(constraints)), bc, br, sz(nb), ctypes.byref(d)))
+    out = {k: int(getattr(d, k)) for k in StarkDims._scalars}
+    out.update({k: [int(v) for v in getattr(d, k)][:len(constraints)] for k in StarkDims._per_constraint})
+    out.update({k: [int(v) for v in getattr(d, k)][:int(num_registers)] for k in StarkDims._per_register})
+    return out
+
+
+STARK_SECTIONS = ("status", "fri", "indices", "bqc_roots", "rdc_root", "bqc_points", "rdc_points", "tzc_points", "bqc_paths", "rdc_paths",
+                  "tzc_paths", "path_lens")
+
+
+def _stark_dims_struct(dims):
+    d = StarkDims()
+    for k in StarkDims._scalars:
+        setattr(d, k, int(dims[k]))
+    for k in StarkDims._per_constraint + StarkDims._per_register:
+        for i, v in enumerate(dims[k]):
+            getattr(d, k)[i] = int(v)
+    return d
+
+
+def stark_proof_layout(fid, dims):
+    """mzk_stark_proof_layout (host only): ({section: (offset, size)}, total bytes) for the dims dict of stark_plan."""
+    off, size = (ctypes.c_uint64 * len(STARK_SECTIONS))(), (ctypes.c_uint64 * len(STARK_SECTIONS))()
+    total = ctypes.c_uint64()
+    d = _stark_dims_struct(dims)
+    _check(lib().mzk_stark_proof_layout(ctypes.byref(d), int(fid), off, size, ctypes.byref(total)))
+    return {k: (int(off[i]), int(size[i])) for i, k in enumerate(STARK_SECTIONS)}, int(total.value)
+
+
+def stark_unpack_proof(fid, dims, raw):
+    """The packed proof of mzk_stark_prove as the reference's FastStarkProof (fast_stark.rs:22-32), a dict: fri (fri_unpack_proof's dict
+    with last_codeword as integers and the SORTED top_level_indices), bqc_roots, bqc_points, bqc_paths, rdc_root, rdc_points, rdc_paths,
+    tzc_points, tzc_paths, and `indices` (the duplicated indices the openings are at).  Raises MzkError when the status word is set."""
+    raw = bytes(raw)
+    nl = LIMBS[fid]
+    sec, _ = stark_proof_layout(fid, dims)
+    part = lambda k: raw[sec[k][0]:sec[k][0] + sec[k][1]]
+    if int.from_bytes(part("status"), "little") != 0:
+        raise MzkError(-6, "stark_prove: sample_indices gave up")
+    flen, e, t, m = dims["fri_domain_length"], dims["fri_domain_length"] // dims["omicron_domain_length"], dims["num_randomizers"] // 4, dims["num_registers"]
+    fri = fri_unpack_proof(fid, flen, e, t, part("fri"))
+    fri["last_codeword"] = from_limbs(fri["last_codeword"])
+    k, depth = dims["num_indices"], flen.bit_length() - 1
+    lens = np.frombuffer(part("path_lens"), dtype=np.uint64)
+    out = {"fri": fri, "indices": [int(x) for x in np.frombuffer(part("indices"), dtype=np.uint64)],
+           "bqc_roots": [part("bqc_roots")[32 * r:32 * r + 32] for r in range(m)], "rdc_root": part("rdc_root")}
+    at = 0
+    for name, count in (("bqc", m * k), ("rdc", k), ("tzc", k)):
+        out[name + "_points"] = from_limbs(np.frombuffer(part(name + "_points"), dtype=np.uint64).reshape(-1, nl)) if count else []
+        blob, paths = part(name + "_paths"), []
+        for q in range(count):
+            paths.append([blob[(q * depth + j) * 48:(q * depth + j) * 48 + int(lens[at + j])] for j in range(depth)])
+            at += depth
+        out[name + "_paths"] = paths
+    return out
+
+
+class Stark:
+    """FastStark with what preprocess makes (mzk_stark_new) and prove in one call.  constraints as in mpoly_term_table over
+    1 + 2 * num_registers variables; boundary: (cycle, register, value) triples."""
+
+    def __init__(self, fid, expansion_factor, num_colinearity_checks, num_registers, num_cycles, transition_constraints_degree, generator, constraints):
+        self._h = ctypes.c_void_p()
+        self.fid, self.constraints = int(fid), constraints
+        self.params = (int(expansion_factor), int(num_colinearity_checks), int(num_registers), int(num_cycles), int(transition_constraints_degree))
+        tc, te, toff = mpoly_term_table(fid, constraints, 1 + 2 * int(num_registers))
+        sz = ctypes.c_size_t
+        _check(lib().mzk_stark_new(self.fid, *[sz(v) for v in self.params], _p(_one(fid, generator)), _p(tc), _p(te), toff, sz(len(constraints)),
+                                   ctypes.byref(self._h)))
+
+    def dims(self, boundary):
+        """the sizes of a proof for this boundary (stark_plan)"""
+        return stark_plan(self.fid, *self.params, self.constraints, boundary)
+
+    def transition_zerofier_root(self):
+        buf = (ctypes.c_uint8 * 32)()
+        _check(lib().mzk_stark_transition_zerofier_root(self._h, buf))
+        return bytes(buf)
+
+    def _boundary(self, boundary):
+        nb = len(boundary)
+        sz = ctypes.c_size_t
+        bc = (sz * max(nb, 1))(*[int(b[0]) for b in boundary])
+        br = (sz * max(nb, 1))(*[int(b[1]) for b in boundary])
+        bv = to_limbs([int(b[2]) for b in boundary], LIMBS[self.fid]) if nb else np.zeros((1, LIMBS[self.fid]), dtype=np.uint64)
+        return bc, br, bv, sz(nb)
+
+    def prove_raw(self, trace, boundary, randomizer):
+        """mzk_stark_prove: trace (rows x registers x limbs, the random rows appended), randomizer (max_degree + 1 coefficients) -> packed bytes"""
+        d = self.dims(boundary)
+        _, total = stark_proof_layout(self.fid, d)
+        t = np.ascontiguousarray(trace, dtype=np.uint64).reshape(-1, self.params[2], LIMBS[self.fid])
+        r = _arr(self.fid, randomizer)
+        bc, br, bv, nb = self._boundary(boundary)
+        buf = (ctypes.c_uint8 * total)()
+        _check(lib().mzk_stark_prove(self._h, _p(t), ctypes.c_size_t(t.shape[0]), bc, br, _p(bv), nb, _p(r), buf, ctypes.c_size_t(total)))
+        return bytes(buf)
+
+    def prove(self, trace, boundary, randomizer):
+        return stark_unpack_proof(self.fid, self.dims(boundary), self.prove_raw(trace, boundary, randomizer))
+
+    def prove_dev(self, d_trace_ptr, n_rows, boundary, d_randomizer_ptr, d_proof_ptr, proof_cap, stream=0):
+        """mzk_stark_prove_dev: raw device pointers; returns when the proof at d_proof_ptr is complete"""
+        bc, br, bv, nb = self._boundary(boundary)
+        _check(lib().mzk_stark_prove_dev(self._h, ctypes.c_void_p(d_trace_ptr), ctypes.c_size_t(n_rows), bc, br, _p(bv), nb, ctypes.c_void_p(d_randomizer_ptr),
+                                         ctypes.c_void_p(d_proof_ptr), ctypes.c_size_t(proof_cap), ctypes.c_void_p(stream)))
+
+    def close(self):
+        if self._h:
+            lib().mzk_stark_free(self._h)
+            self._h = ctypes.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 def g2_points_to_array(pts):

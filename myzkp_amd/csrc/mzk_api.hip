@@ -891,6 +891,37 @@ int mzk_fast_multiply(int field_id, const uint64_t* a, size_t la, const uint64_t
   return MZK_OK;
 }
 
+// lhs / rhs of at most 8 coefficients (trimmed lengths tl <= 8, 0 < tr <= tl): the trimmed quotient into out, its length returned
+static size_t small_poly_div(const HostField* hf, const uint64_t* lhs, size_t tl, const uint64_t* rhs, size_t tr, uint64_t* out) {
+  const int nl = hf->nl;
+  const size_t ql = tl - tr + 1;
+  // ntt.rs:295-297 `return lhs / rhs`: true long division (polynomial.rs:371-405) of at most 8 coefficients --
+  // parameter-sized work, done with the host parameter arithmetic
+  uint64_t rem[8][4], quo[8][4], linv[4], lead[4], prod[4];
+  memset(rem, 0, sizeof rem); memset(quo, 0, sizeof quo);
+  for (size_t i = 0; i < tl; i++) memcpy(rem[i], lhs + i * nl, 8 * nl);
+  h_invmod(hf, linv, rhs + (tr - 1) * nl);
+  size_t rl = tl;
+  while (rl >= tr) {
+    h_mulmod(hf, lead, rem[rl - 1], linv);
+    const size_t dd = rl - tr;
+    memcpy(quo[dd], lead, 8 * nl);
+    for (size_t i = 0; i < tr; i++) {
+      h_mulmod(hf, prod, lead, rhs + i * nl);
+      // rem - prod mod p = rem + (p - prod)
+      uint64_t neg[4] = {0, 0, 0, 0};
+      bool z = true;
+      for (int k = 0; k < nl; k++) z = z && prod[k] == 0;
+      if (!z) { unsigned __int128 br = 0; for (int k = 0; k < nl; k++) { unsigned __int128 d = (unsigned __int128)hf->p[k] - prod[k] - br; neg[k] = (uint64_t)d; br = (d >> 64) & 1; } }
+      h_addmod(hf, rem[dd + i], rem[dd + i], neg);
+    }
+    while (rl > 0) { bool z = true; for (int k = 0; k < nl; k++) z = z && rem[rl - 1][k] == 0; if (!z) break; rl--; }
+  }
+  size_t qt = ql;
+  while (qt > 0) { bool z = true; for (int k = 0; k < nl; k++) z = z && quo[qt - 1][k] == 0; if (!z) break; qt--; }
+  for (size_t i = 0; i < qt; i++) memcpy(out + i * nl, quo[i], 8 * nl);
+  return qt;
+}
 // ntt::fast_coset_divide (ntt.rs:271-330): the quotient step of FastStark::prove (fast_stark.rs:265).
 int mzk_fast_coset_divide(int field_id, const uint64_t* lhs, size_t ll, const uint64_t* rhs, size_t lr, const uint64_t* offset,
                           const uint64_t* root, size_t root_order, uint64_t* out, size_t* out_len) {
@@ -912,32 +943,7 @@ int mzk_fast_coset_divide(int field_id, const uint64_t* lhs, size_t ll, const ui
   if (!(tr < tl)) { set_error("assertion failed: rhs.degree() < lhs.degree()"); return MZK_E_LENGTH; }      // ntt.rs:285 (a zero lhs has degree -1)
   const size_t degree = tl - 1, ql = tl - tr + 1;
   if (degree < 8) {
-    // ntt.rs:295-297 `return lhs / rhs`: true long division (polynomial.rs:371-405) of at most 8 coefficients --
-    // parameter-sized work, done with the host parameter arithmetic
-    uint64_t rem[8][4], quo[8][4], linv[4], lead[4], prod[4];
-    memset(rem, 0, sizeof rem); memset(quo, 0, sizeof quo);
-    for (size_t i = 0; i < tl; i++) memcpy(rem[i], lhs + i * nl, 8 * nl);
-    h_invmod(hf, linv, rhs + (tr - 1) * nl);
-    size_t rl = tl;
-    while (rl >= tr) {
-      h_mulmod(hf, lead, rem[rl - 1], linv);
-      const size_t dd = rl - tr;
-      memcpy(quo[dd], lead, 8 * nl);
-      for (size_t i = 0; i < tr; i++) {
-        h_mulmod(hf, prod, lead, rhs + i * nl);
-        // rem - prod mod p = rem + (p - prod)
-        uint64_t neg[4] = {0, 0, 0, 0};
-        bool z = true;
-        for (int k = 0; k < nl; k++) z = z && prod[k] == 0;
-        if (!z) { unsigned __int128 br = 0; for (int k = 0; k < nl; k++) { unsigned __int128 d = (unsigned __int128)hf->p[k] - prod[k] - br; neg[k] = (uint64_t)d; br = (d >> 64) & 1; } }
-        h_addmod(hf, rem[dd + i], rem[dd + i], neg);
-      }
-      while (rl > 0) { bool z = true; for (int k = 0; k < nl; k++) z = z && rem[rl - 1][k] == 0; if (!z) break; rl--; }
-    }
-    size_t qt = ql;
-    while (qt > 0) { bool z = true; for (int k = 0; k < nl; k++) z = z && quo[qt - 1][k] == 0; if (!z) break; qt--; }
-    for (size_t i = 0; i < qt; i++) memcpy(out + i * nl, quo[i], 8 * nl);
-    *out_len = qt;
+    *out_len = small_poly_div(hf, lhs, tl, rhs, tr, out);
     return MZK_OK;
   }
   uint64_t r[4] = {0, 0, 0, 0};
@@ -958,6 +964,96 @@ int mzk_fast_coset_divide(int field_id, const uint64_t* lhs, size_t ll, const ui
   MZK_TRY(coset_divide_dev_impl(field_id, d_l, tl, d_r, tr, offset, r, order, d_o, s));
   MZK_TRY(stage_out(out, d_o, ql * esz, s));
   *out_len = ql;
+  return MZK_OK;
+}
+
+// fast_coset_divide of `count` numerators in HBM over ONE denominator (the transition quotients of fast_stark.rs:261-273), each row
+// bit-identical to mzk_fast_coset_divide.  The trimmed lengths -- which decide the error checks, the degree < 8 branch and the
+// squared-down order of ntt.rs:298-302 -- are found on the device first (one wait); rows of one order then share one batched forward
+// transform, one denominator transform, one division launch, one batched inverse transform and one scale-back launch.
+int mzk_fast_coset_divide_batch_dev(int field_id, const void* d_lhs, size_t lhs_stride, const size_t* lhs_lens, size_t count, const void* d_rhs,
+                                    size_t rhs_len, const uint64_t* offset, const uint64_t* root, size_t root_order, void* d_out, size_t out_stride,
+                                    size_t* out_lens, void* stream) {
+  MZK_ENTER();
+  if (field_id != MZK_FIELD_FR && field_id != MZK_FIELD_M128) { set_error("fast_coset_divide: bad field id %d", field_id); return MZK_E_ARG; }
+  if (!root || !offset || (!d_rhs && rhs_len) || (count && (!lhs_lens || !out_lens || (!d_lhs && lhs_stride) || (!d_out && out_stride)))) {
+    set_error("fast_coset_divide: null pointer");
+    return MZK_E_ARG;
+  }
+  const HostField* hf = host_field(field_id);
+  const int nl = hf->nl;
+  if (!h_is_canonical(hf, root) || !h_is_canonical(hf, offset)) { set_error("fast_coset_divide: parameter not canonical"); return MZK_E_RANGE; }
+  uint64_t t[4];
+  h_powmod_u64(hf, t, root, root_order);       // ntt.rs:282-283
+  if (!h_is_one(hf, t)) { set_error("assertion failed: primitive_root.pow(root_order).is_one()"); return MZK_E_ROOT_ORDER; }
+  h_powmod_u64(hf, t, root, root_order / 2);
+  if (h_is_one(hf, t)) { set_error("assertion failed: !primitive_root.pow(root_order / 2).is_one()"); return MZK_E_ROOT_PRIM; }
+  for (size_t i = 0; i < count; i++)
+    if (lhs_lens[i] > lhs_stride) { set_error("fast_coset_divide: row %zu has %zu coefficients, lhs_stride is %zu", i, lhs_lens[i], lhs_stride); return MZK_E_LENGTH; }
+  if (count > ((size_t)1 << 20) || (lhs_stride && count > ((size_t)1 << 40) / lhs_stride) || (out_stride && count > ((size_t)1 << 40) / out_stride)) {
+    set_error("fast_coset_divide: %zu rows are too many", count);
+    return MZK_E_LENGTH;
+  }
+  if (count == 0) return MZK_OK;
+  hipStream_t s = (hipStream_t)stream;
+  WsGuard wsg(s);
+  const size_t esz = field_bytes(field_id);
+  if (rhs_len == 0) { set_error("assertion failed: !rhs.is_zero()"); return MZK_E_ARG; }                    // ntt.rs:284: no launch for an empty denominator
+  std::vector<size_t> tl(count + 1);
+  MZK_TRY(rows_trimmed_len_dev(field_id, const_cast<void*>(d_lhs), lhs_stride, lhs_lens, count, 0, d_rhs, rhs_len, WS_MISC_F, tl.data(), s));
+  const size_t tr = tl[count];
+  if (tr == 0) { set_error("assertion failed: !rhs.is_zero()"); return MZK_E_ARG; }                           // ntt.rs:284
+  struct Group { size_t order; uint64_t root[4]; std::vector<CdRow> rows; };
+  std::vector<Group> groups;
+  std::vector<size_t> small;
+  for (size_t i = 0; i < count; i++) {
+    if (!(tr < tl[i])) { set_error("assertion failed: rhs.degree() < lhs.degree() (row %zu)", i); return MZK_E_LENGTH; }   // ntt.rs:285
+    const size_t degree = tl[i] - 1, ql = tl[i] - tr + 1;
+    if (ql > out_stride) { set_error("fast_coset_divide: row %zu has a quotient of %zu coefficients, out_stride is %zu", i, ql, out_stride); return MZK_E_LENGTH; }
+    if (degree < 8) { small.push_back(i); continue; }
+    size_t order = root_order;
+    while (degree < order / 2) order /= 2;       // ntt.rs:299-302
+    if (tl[i] > order) {   // the inner ntt call's own assertions (ntt.rs:8-18)
+      if (tl[i] & (tl[i] - 1)) { set_error("cannot compute ntt of non-power-of-two sequence"); return MZK_E_NOT_POW2; }
+      set_error("primitive root must be nth root of unity, where n is len(values)"); return MZK_E_ROOT_ORDER;
+    }
+    size_t g = 0;
+    while (g < groups.size() && groups[g].order != order) g++;
+    if (g == groups.size()) {
+      groups.push_back(Group());
+      groups[g].order = order;
+      memset(groups[g].root, 0, sizeof groups[g].root);
+      memcpy(groups[g].root, root, 8 * nl);
+      for (size_t o = root_order; o > order; o /= 2) h_mulmod(hf, groups[g].root, groups[g].root, groups[g].root);
+    }
+    groups[g].rows.push_back({i, tl[i]});
+    out_lens[i] = ql;
+  }
+  auto fail = [&](int rc) { (void)hipStreamSynchronize(s); return rc; };
+  if (!small.empty()) {      // ntt.rs:295-297 `return lhs / rhs`: at most 8 coefficients of a row visit the host; one wait in, one out for all
+    const size_t ns = small.size();
+    std::vector<uint64_t> hl(ns * 32, 0), hq(ns * 32, 0);
+    uint64_t hr[8][4];
+    for (size_t j = 0; j < ns; j++)
+      if (hipMemcpyAsync(&hl[j * 32], (const char*)d_lhs + small[j] * lhs_stride * esz, tl[small[j]] * esz, hipMemcpyDeviceToHost, s) != hipSuccess) return fail(MZK_E_HIP);
+    int rc = d2h_sync(hr, d_rhs, tr * esz, s);                // the stream is idle afterwards: the rows above have arrived too
+    if (rc != MZK_OK) return fail(rc);
+    for (size_t j = 0; j < ns; j++) {
+      const size_t i = small[j];
+      // the copies pack elements of nl limbs back to back: view the arrays that way
+      const size_t qt = small_poly_div(hf, &hl[j * 32], tl[i], (const uint64_t*)hr, tr, &hq[j * 32]);
+      char* row = (char*)d_out + i * out_stride * esz;
+      if (hipMemsetAsync(row, 0, out_stride * esz, s) != hipSuccess) return fail(MZK_E_HIP);
+      if (qt && hipMemcpyAsync(row, &hq[j * 32], qt * esz, hipMemcpyHostToDevice, s) != hipSuccess) return fail(MZK_E_HIP);
+      out_lens[i] = qt;
+    }
+    if (hipStreamSynchronize(s) != hipSuccess) return fail(MZK_E_HIP);          // hq leaves scope
+  }
+  for (const Group& g : groups) {
+    const int rc = coset_divide_rows_dev_impl(field_id, d_lhs, lhs_stride, g.rows.data(), g.rows.size(), d_rhs, tr, offset, g.root, g.order, d_out, out_stride, s);
+    if (rc != MZK_OK) return fail(rc);
+  }
+  MZK_HIP(hipStreamSynchronize(s));
   return MZK_OK;
 }
 

@@ -169,6 +169,18 @@ int transpose_elems_dev_impl(int fid, const void* d_in, void* d_out, size_t rows
 int poly_scale_dev_impl(int fid, const void* d_in, size_t n, const uint64_t* ratio_host, const uint64_t* lead_host, void* d_out, hipStream_t s);
 int coset_divide_dev_impl(int fid, const void* d_lhs, size_t tl, const void* d_rhs, size_t tr, const uint64_t* offset_host,
                           const uint64_t* root_host, size_t order, void* d_out, hipStream_t s);
+// Trimmed length (1 + index of the last non-zero coefficient among the lens[i] given) of `count` rows `stride` elements apart, plus --
+// when d_extra is not null -- of one more vector of extra_len elements elsewhere (out_lens[count]), into host memory, in ONE launch and
+// one wait.  clear_to != 0: elements [lens[i], clear_to) of every row are zeroed in the same pass (d_rows is written only then).
+// Workspace: `slot` alone.
+int rows_trimmed_len_dev(int fid, void* d_rows, size_t stride, const size_t* lens, size_t count, size_t clear_to, const void* d_extra, size_t extra_len,
+                         WsSlot slot, size_t* out_lens, hipStream_t s);
+// coset_divide_dev_impl for several numerators of ONE squared-down order over one denominator: rows[k] = (row index in d_lhs / d_out,
+// trimmed length); quotient row = tl - tr + 1 coefficients, zeros behind them up to out_stride.  Workspace: WS_MISC_A, B, F and the
+// transform slots.
+struct CdRow { size_t row, tl; };
+int coset_divide_rows_dev_impl(int fid, const void* d_lhs, size_t lhs_stride, const CdRow* rows, size_t nrows, const void* d_rhs, size_t tr,
+                               const uint64_t* offset_host, const uint64_t* root_host, size_t order, void* d_out, size_t out_stride, hipStream_t s);
 int pointwise_div_dev(int fid, const void* d_a, const void* d_b, void* d_out, size_t n, hipStream_t s);
 int pointwise_div_shared_dev(int fid, const void* d_a, size_t a_stride, const void* d_b, void* d_out, size_t out_stride, size_t n, size_t regs, hipStream_t s);
 int pointwise_mul_shared_dev(int fid, const void* d_a, size_t a_stride, const void* d_b, void* d_out, size_t out_stride, size_t n, size_t regs, hipStream_t s);
@@ -253,13 +265,22 @@ int selftest_copy_impl(const void* d_src, void* d_dst, size_t bytes, hipStream_t
 int kzg_setup_g1_dev(const uint64_t* alpha_host, const uint64_t* g1_host, size_t first, size_t count, void* d_powers_xy, hipStream_t s);
 int kzg_open_dev(const void* d_coef, size_t n, const uint64_t* u_host, const void* d_points, int point_kind, size_t table_stride,
                  void* d_y, void* d_w_xy, void* d_q, hipStream_t s);
-// Synthetic division by (X - u) over BN254 Fr (mzk_kzg.hip): b_len = *end (0 when end is null),
+// Synthetic division by (X - u) (mzk_kzg.hip): b_len = *end (0 when end is null),
 // b_t = src[t] + u b_{t+1}; y = b_0, q = b_1 .. b_{len-1}, or b_1 .. b_len with an end.  u and end are canonical host values;
 // y and q are device outputs or null; a job of length 0 writes nothing.
 struct SdJob { const void* src; size_t len; const uint64_t* u; const uint64_t* end; void* y; void* q; };
 // rounds[r] consecutive jobs form round r; the jobs of a round are independent, a later round may read what an earlier one wrote.
 // Workspace: WS_MISC_C (the job table) and WS_MISC_D (chunk values and carries).
 int synth_div_dev(const SdJob* jobs, const size_t* rounds, int nrounds, hipStream_t s);
+// The same engine over Fr or M128 (u and end then hold 2 limbs).
+int synth_div_field_dev(int fid, const SdJob* jobs, const size_t* rounds, int nrounds, hipStream_t s);
+// Row i of d_polys (lens[i] coefficients, rows `stride` elements apart) divided by prod_j (X - roots[j]), j in [root_offsets[i],
+// root_offsets[i+1]): quotient rows into d_out (same stride, zero behind the quotient), trimmed lengths into out_lens (mzk.h:
+// mzk_poly_div_roots).  _check validates, _dev_impl enqueues and returns when d_out is complete.  Workspace: WS_MISC_A .. E.
+int poly_div_roots_check(int fid, const void* polys, size_t stride, const size_t* lens, size_t count, const uint64_t* roots, const size_t* root_offsets,
+                         const void* out, const size_t* out_lens);
+int poly_div_roots_dev_impl(int fid, const void* d_polys, size_t stride, const size_t* lens, size_t count, const uint64_t* roots, const size_t* root_offsets,
+                            void* d_out, size_t* out_lens, hipStream_t s);
 
 }  // namespace mzk
 

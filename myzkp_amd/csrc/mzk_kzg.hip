@@ -278,8 +278,8 @@ constexpr size_t SD_K = (size_t)1 << SD_K_LOG;
 // while 2^14 through one chunk level takes 0.074
 constexpr size_t SD_BLOCK_MAX = (size_t)1 << 13;
 constexpr int SD_THREADS = 256;
-typedef Fe<FrParams> FrE;
-struct SdRec {          // one job of one level, as the kernels read it
+// SD_K_LOG and SD_BLOCK_MAX were measured for Fr; not measured for M128.
+struct SdRec {          // one job of one level, as the kernels read it; u / end hold P::NW words (8 for Fr, 4 for M128)
   const u32* src;       // len coefficients
   u32* q;               // b_1 .., or null
   u32* y;               // b_0, or null
@@ -289,50 +289,55 @@ struct SdRec {          // one job of one level, as the kernels read it
   u32 end[8];           // b_len, canonical
   u32 has_end;          // q also gets b_len
 };
-__device__ __forceinline__ FrE fr_gload(const u32* __restrict__ g, size_t i) {
-  u32 w[8];
-  ld8(g + 8 * i, w);
-  return fe_unpack<FrParams>(w);
+template <class P> __device__ __forceinline__ Fe<P> sd_gload(const u32* __restrict__ g, size_t i) {
+  u32 w[P::NW];
+  const uint4* p4 = reinterpret_cast<const uint4*>(g + i * P::NW);
+#pragma unroll
+  for (int k = 0; k < P::NW / 4; k++) { const uint4 v = p4[k]; w[4 * k] = v.x; w[4 * k + 1] = v.y; w[4 * k + 2] = v.z; w[4 * k + 3] = v.w; }
+  return fe_unpack<P>(w);
 }
-__device__ __forceinline__ void fr_gstore(u32* __restrict__ g, size_t i, const FrE& v) {
-  u32 w[8];
-  fe_pack<FrParams>(v, w);
-  st8(g + 8 * i, w);
+template <class P> __device__ __forceinline__ void sd_gstore(u32* __restrict__ g, size_t i, const Fe<P>& v) {   // v canonical
+  u32 w[P::NW];
+  fe_pack<P>(v, w);
+  uint4* p4 = reinterpret_cast<uint4*>(g + i * P::NW);
+#pragma unroll
+  for (int k = 0; k < P::NW / 4; k++) p4[k] = make_uint4(w[4 * k], w[4 * k + 1], w[4 * k + 2], w[4 * k + 3]);
 }
 // b_lo from b_hi = acc over the coefficients [lo, hi); u in Montgomery form (fe_mul(x, u R) = x u)
-__device__ __forceinline__ FrE sd_horner(const u32* __restrict__ c, u64 lo, u64 hi, const FrE& u, FrE acc) {
-  for (u64 t = hi; t-- > lo;) acc = fe_add<FrParams>(fe_mul<FrParams>(acc, u), fr_gload(c, t));
-  return fe_reduce<FrParams>(acc);
+template <class P> __device__ __forceinline__ Fe<P> sd_horner(const u32* __restrict__ c, u64 lo, u64 hi, const Fe<P>& u, Fe<P> acc) {
+  for (u64 t = hi; t-- > lo;) acc = fe_add<P>(fe_mul<P>(acc, u), sd_gload<P>(c, t));
+  return fe_reduce<P>(acc);
 }
 // b_hi-1 .. b_lo from b_hi = acc into q (b_t at q[t - 1]; b_0 is y's)
-__device__ __forceinline__ void sd_fill(const SdRec& J, u64 lo, u64 hi, const FrE& u, FrE acc) {
-  if (hi == J.len && J.has_end) fr_gstore(J.q, hi - 1, acc);
+template <class P> __device__ __forceinline__ void sd_fill(const SdRec& J, u64 lo, u64 hi, const Fe<P>& u, Fe<P> acc) {
+  if (hi == J.len && J.has_end) sd_gstore<P>(J.q, hi - 1, acc);
   for (u64 t = hi; t-- > lo;) {
-    acc = fe_reduce<FrParams>(fe_add<FrParams>(fe_mul<FrParams>(acc, u), fr_gload(J.src, t)));
-    if (t > 0) fr_gstore(J.q, t - 1, acc);
+    acc = fe_reduce<P>(fe_add<P>(fe_mul<P>(acc, u), sd_gload<P>(J.src, t)));
+    if (t > 0) sd_gstore<P>(J.q, t - 1, acc);
   }
 }
 // a job's values are wave-uniform: held in VGPRs, the powers of u of the scan below do not overflow the scalar registers
-__device__ __forceinline__ FrE sd_vgpr(FrE x) {
+template <class P> __device__ __forceinline__ Fe<P> sd_vgpr(Fe<P> x) {
 #pragma unroll
-  for (int i = 0; i < FrParams::L; i++) asm volatile("" : "+v"(x.l[i]));
+  for (int i = 0; i < P::L; i++) asm volatile("" : "+v"(x.l[i]));
   return x;
 }
 // one workgroup per job: lane L owns the K = ceil(len / 256) coefficients [L K, (L + 1) K); the lanes' chunk values are scanned
 // with u^K, u^2K, ... through LDS, so S[L] = b_{L K}; then every lane fills its chunk from S[L + 1]
+template <class P>
 __global__ __launch_bounds__(SD_THREADS) void k_sd_block(const SdRec* __restrict__ jobs) {
-  typedef FrParams P;
+  typedef Fe<P> E;
   __shared__ u32 S[SD_THREADS][P::L];
   const SdRec& J = jobs[blockIdx.x];
   const int L = threadIdx.x;
   const u64 n = J.len;
-  const FrE u = sd_vgpr(fe_to_mont<P>(fe_unpack<P>(J.u))), end = sd_vgpr(fe_unpack<P>(J.end));
+  const E u = sd_vgpr<P>(fe_to_mont<P>(fe_unpack<P>(J.u))), end = sd_vgpr<P>(fe_unpack<P>(J.end));
   const u64 K = (n + SD_THREADS - 1) / SD_THREADS;
   const u64 lo = (u64)L * K;
   const u64 hi = (lo + K < n) ? lo + K : n;
-  FrE mine = fe_zero<P>();
-  if (lo < n) mine = sd_horner(J.src, lo, hi, u, hi == n ? end : fe_zero<P>());
-  FrE pw = fe_one<P>(), base = u;                           // u^K in Montgomery form
+  E mine = fe_zero<P>();
+  if (lo < n) mine = sd_horner<P>(J.src, lo, hi, u, hi == n ? end : fe_zero<P>());
+  E pw = fe_one<P>(), base = u;                             // u^K in Montgomery form
   for (u64 k = K; k; k >>= 1) {
     if (k & 1) pw = fe_mul<P>(pw, base);
     base = fe_sqr<P>(base);
@@ -341,7 +346,7 @@ __global__ __launch_bounds__(SD_THREADS) void k_sd_block(const SdRec* __restrict
   for (int i = 0; i < P::L; i++) S[L][i] = mine.l[i];
   for (int d = 1; d < SD_THREADS; d <<= 1) {
     __syncthreads();
-    FrE other = fe_zero<P>();
+    E other = fe_zero<P>();
     if (L + d < SD_THREADS) {
 #pragma unroll
       for (int i = 0; i < P::L; i++) other.l[i] = S[L + d][i];
@@ -352,15 +357,15 @@ __global__ __launch_bounds__(SD_THREADS) void k_sd_block(const SdRec* __restrict
     for (int i = 0; i < P::L; i++) S[L][i] = mine.l[i];
     pw = fe_sqr<P>(pw);
   }
-  if (L == 0 && J.y) fr_gstore(J.y, 0, mine);
+  if (L == 0 && J.y) sd_gstore<P>(J.y, 0, mine);
   __syncthreads();
   if (!J.q || lo >= n) return;
-  FrE acc = end;                                            // b_hi
+  E acc = end;                                              // b_hi
   if (hi < n) {
 #pragma unroll
     for (int i = 0; i < P::L; i++) acc.l[i] = S[L + 1][i];
   }
-  sd_fill(J, lo, hi, u, acc);
+  sd_fill<P>(J, lo, hi, u, acc);
 }
 __device__ __forceinline__ int sd_job_of(const SdRec* __restrict__ jobs, int njobs, u64 g) {
   int lo = 0, hi = njobs - 1;     // last job with chunk0 <= g
@@ -371,16 +376,18 @@ __device__ __forceinline__ int sd_job_of(const SdRec* __restrict__ jobs, int njo
   return lo;
 }
 // h[g] = the value of chunk g at u, from b = end behind the job's last chunk
+template <class P>
 __global__ __launch_bounds__(64) void k_sd_eval(const SdRec* __restrict__ jobs, int njobs, u64 nchunks, u32* __restrict__ h) {
   const u64 g = (u64)blockIdx.x * blockDim.x + threadIdx.x;
   if (g >= nchunks) return;
   const SdRec& J = jobs[sd_job_of(jobs, njobs, g)];
   const u64 lo = (g - J.chunk0) << SD_K_LOG;
   const u64 hi = (lo + SD_K < J.len) ? lo + SD_K : J.len;
-  const FrE u = fe_to_mont<FrParams>(fe_unpack<FrParams>(J.u));
-  fr_gstore(h, g, sd_horner(J.src, lo, hi, u, hi == J.len ? fe_unpack<FrParams>(J.end) : fe_zero<FrParams>()));
+  const Fe<P> u = fe_to_mont<P>(fe_unpack<P>(J.u));
+  sd_gstore<P>(h, g, sd_horner<P>(J.src, lo, hi, u, hi == J.len ? fe_unpack<P>(J.end) : fe_zero<P>()));
 }
 // chunk g from b at the start of the next chunk, carry[g] (the level above wrote it as its quotient), or from the end
+template <class P>
 __global__ __launch_bounds__(64) void k_sd_fill(const SdRec* __restrict__ jobs, int njobs, u64 nchunks, const u32* __restrict__ carry) {
   const u64 g = (u64)blockIdx.x * blockDim.x + threadIdx.x;
   if (g >= nchunks) return;
@@ -388,15 +395,19 @@ __global__ __launch_bounds__(64) void k_sd_fill(const SdRec* __restrict__ jobs, 
   if (!J.q) return;
   const u64 lo = (g - J.chunk0) << SD_K_LOG;
   const u64 hi = (lo + SD_K < J.len) ? lo + SD_K : J.len;
-  const FrE u = fe_to_mont<FrParams>(fe_unpack<FrParams>(J.u));
-  sd_fill(J, lo, hi, u, hi == J.len ? fe_unpack<FrParams>(J.end) : fr_gload(carry, g));
+  const Fe<P> u = fe_to_mont<P>(fe_unpack<P>(J.u));
+  sd_fill<P>(J, lo, hi, u, hi == J.len ? fe_unpack<P>(J.end) : sd_gload<P>(carry, g));
 }
 
-static void sd_words(const uint64_t* v, u32* w) {
-  for (int i = 0; i < 4; i++) { w[2 * i] = (u32)v[i]; w[2 * i + 1] = (u32)(v[i] >> 32); }
+// nl 64-bit limbs -> 2 nl words
+static void sd_words(const uint64_t* v, int nl, u32* w) {
+  for (int i = 0; i < nl; i++) { w[2 * i] = (u32)v[i]; w[2 * i + 1] = (u32)(v[i] >> 32); }
 }
-int synth_div_dev(const SdJob* jobs, const size_t* rounds, int nrounds, hipStream_t s) {
-  const HostField* fr = host_field(MZK_FIELD_FR);
+template <class P>
+static int synth_div_impl(int fid, const SdJob* jobs, const size_t* rounds, int nrounds, hipStream_t s) {
+  const HostField* hf = host_field(fid);
+  const int nl = hf->nl;
+  const size_t ub = 8 * (size_t)nl;                        // bytes of one host element
   enum { BLOCK, EVAL, FILL };
   struct Step { int kind; size_t first, count; u64 nchunks; size_t arr; };   // arr: the level's chunk values / carries in WS_MISC_D
   std::vector<SdRec> tab;
@@ -416,10 +427,10 @@ int synth_div_dev(const SdJob* jobs, const size_t* rounds, int nrounds, hipStrea
         if (J.len == 0) continue;
         SdRec x = {};
         x.src = (const u32*)J.src; x.q = (u32*)J.q; x.y = (u32*)J.y; x.len = J.len;
-        sd_words(J.u, x.u);
-        if (J.end) { sd_words(J.end, x.end); x.has_end = 1; }
+        sd_words(J.u, nl, x.u);
+        if (J.end) { sd_words(J.end, nl, x.end); x.has_end = 1; }
         tab.push_back(x);
-        us.insert(us.end(), J.u, J.u + 4);
+        us.insert(us.end(), J.u, J.u + nl);
         fill |= J.q != nullptr;                            // every level above has q where level 0 has
       }
       std::vector<Step> fills;
@@ -436,18 +447,18 @@ int synth_div_dev(const SdJob* jobs, const size_t* rounds, int nrounds, hipStrea
         steps.push_back({EVAL, first, count, nch, off});
         if (fill) fills.push_back({FILL, first, count, nch, off + nch});
         // one level up: each job's chunk values at u^SD_K; its quotient (b at chunks 1, 2, ..) is this level's carries
-        std::vector<uint64_t> uk(4 * count);
+        std::vector<uint64_t> uk((size_t)nl * count);
         for (size_t k = 0; k < count; k++) {
           const SdRec b = tab[first + k];
           SdRec x = {};
-          x.src = D ? D + 8 * (off + b.chunk0) : nullptr;
-          x.q = (D && b.q) ? D + 8 * (off + nch + b.chunk0) : nullptr;
+          x.src = D ? D + P::NW * (off + b.chunk0) : nullptr;
+          x.q = (D && b.q) ? D + P::NW * (off + nch + b.chunk0) : nullptr;
           x.y = b.y;
           x.len = (b.len + SD_K - 1) >> SD_K_LOG;
           if (D) {                                          // host powers are the call's set-up latency: once per run of equal points
-            if (k > 0 && !memcmp(&us[4 * k], &us[4 * k - 4], 32)) memcpy(&uk[4 * k], &uk[4 * k - 4], 32);
-            else h_powmod_u64(fr, &uk[4 * k], &us[4 * k], SD_K);
-            sd_words(&uk[4 * k], x.u);
+            if (k > 0 && !memcmp(&us[nl * k], &us[nl * (k - 1)], ub)) memcpy(&uk[nl * k], &uk[nl * (k - 1)], ub);
+            else h_powmod_u64(hf, &uk[nl * k], &us[nl * k], SD_K);
+            sd_words(&uk[nl * k], nl, x.u);
           }
           tab.push_back(x);
         }
@@ -463,7 +474,7 @@ int synth_div_dev(const SdJob* jobs, const size_t* rounds, int nrounds, hipStrea
   u32* D = nullptr;
   const size_t need = walk(nullptr);
   if (need) {
-    MZK_TRY(ws_get(WS_MISC_D, need * 32, (void**)&D));
+    MZK_TRY(ws_get(WS_MISC_D, need * field_bytes(fid), (void**)&D));
     walk(D);
   }
   if (tab.empty()) return MZK_OK;
@@ -473,14 +484,90 @@ int synth_div_dev(const SdJob* jobs, const size_t* rounds, int nrounds, hipStrea
   for (const Step& st : steps) {
     const SdRec* jt = d_tab + st.first;
     const unsigned grid = (unsigned)((st.nchunks + 63) / 64);
-    if (st.kind == BLOCK) hipLaunchKernelGGL(k_sd_block, dim3((unsigned)st.count), dim3(SD_THREADS), 0, s, jt);
-    else if (st.kind == EVAL) hipLaunchKernelGGL(k_sd_eval, dim3(grid), dim3(64), 0, s, jt, (int)st.count, st.nchunks, D + 8 * st.arr);
-    else hipLaunchKernelGGL(k_sd_fill, dim3(grid), dim3(64), 0, s, jt, (int)st.count, st.nchunks, (const u32*)D + 8 * st.arr);
+    if (st.kind == BLOCK) hipLaunchKernelGGL((k_sd_block<P>), dim3((unsigned)st.count), dim3(SD_THREADS), 0, s, jt);
+    else if (st.kind == EVAL) hipLaunchKernelGGL((k_sd_eval<P>), dim3(grid), dim3(64), 0, s, jt, (int)st.count, st.nchunks, D + P::NW * st.arr);
+    else hipLaunchKernelGGL((k_sd_fill<P>), dim3(grid), dim3(64), 0, s, jt, (int)st.count, st.nchunks, (const u32*)D + P::NW * st.arr);
   }
   MZK_HIP(hipGetLastError());
   return MZK_OK;
 }
+int synth_div_field_dev(int fid, const SdJob* jobs, const size_t* rounds, int nrounds, hipStream_t s) {
+  return fid == MZK_FIELD_M128 ? synth_div_impl<M128Params>(fid, jobs, rounds, nrounds, s) : synth_div_impl<FrParams>(MZK_FIELD_FR, jobs, rounds, nrounds, s);
+}
+int synth_div_dev(const SdJob* jobs, const size_t* rounds, int nrounds, hipStream_t s) { return synth_div_field_dev(MZK_FIELD_FR, jobs, rounds, nrounds, s); }
 
+// ---- division by a product of linear factors, many rows at once (the boundary quotients of FastStark::prove, fast_stark.rs:217-224) ----
+// floor(f / prod_j (X - r_j)) is one synthetic division per root with each remainder b_0 dropped (what kzg_batch_open_dev does for one
+// polynomial), and it equals (f - I) / Z of polynomial.rs:371-405 for ANY I of lower degree than Z: the interpolant never comes here.
+// Round r divides every row that has more than r roots; a row's rounds ping-pong between WS_MISC_A and WS_MISC_B and its last round
+// writes the out row.  The division runs over the lens[i] coefficients as given: leading zeros only give leading zeros in the quotient
+// (division with remainder is unique), so the reference's trim is one pass at the end (rows_trimmed_len_dev), which also clears the rows' tails.
+int poly_div_roots_check(int fid, const void* polys, size_t stride, const size_t* lens, size_t count, const uint64_t* roots, const size_t* root_offsets,
+                         const void* out, const size_t* out_lens) {
+  if (fid != MZK_FIELD_FR && fid != MZK_FIELD_M128) { set_error("poly_div_roots: bad field id %d", fid); return MZK_E_ARG; }
+  if (count == 0) return MZK_OK;
+  if (!lens || !root_offsets || !out_lens || (stride && (!polys || !out))) { set_error("poly_div_roots: null pointer"); return MZK_E_ARG; }
+  const HostField* hf = host_field(fid);
+  for (size_t i = 0; i < count; i++) {
+    if (root_offsets[i + 1] < root_offsets[i]) {
+      set_error("poly_div_roots: root_offsets[%zu] = %zu is below root_offsets[%zu] = %zu", i + 1, root_offsets[i + 1], i, root_offsets[i]);
+      return MZK_E_LENGTH;
+    }
+    if (lens[i] > stride) { set_error("poly_div_roots: row %zu has %zu coefficients, stride is %zu", i, lens[i], stride); return MZK_E_LENGTH; }
+  }
+  if (root_offsets[count] > root_offsets[0] && !roots) { set_error("poly_div_roots: null pointer"); return MZK_E_ARG; }
+  for (size_t j = root_offsets[0]; j < root_offsets[count]; j++)
+    if (!h_is_canonical(hf, roots + j * hf->nl)) { set_error("poly_div_roots: roots[%zu] not canonical", j); return MZK_E_RANGE; }
+  const size_t bpr = (stride + 255) / 256;
+  if (stride > ((size_t)1 << 32) || count > ((size_t)1 << 40) / (stride ? stride : 1) || (bpr && count > (((size_t)1 << 31) - 1) / bpr)) {
+    set_error("poly_div_roots: %zu rows of %zu elements are too many", count, stride);
+    return MZK_E_LENGTH;
+  }
+  return MZK_OK;
+}
+// validated arguments (poly_div_roots_check); d_out must not overlap d_polys.  Workspace: WS_MISC_A, B (the rounds in between), C, D (synth_div),
+// E (lengths).  Returns when d_out and out_lens are complete.
+int poly_div_roots_dev_impl(int fid, const void* d_polys, size_t stride, const size_t* lens, size_t count, const uint64_t* roots, const size_t* root_offsets,
+                            void* d_out, size_t* out_lens, hipStream_t s) {
+  if (count == 0) return MZK_OK;
+  const size_t esz = field_bytes(fid);
+  const int nl = host_field(fid)->nl;
+  size_t maxk = 0;
+  std::vector<unsigned long long> meta(count, 0);          // quotient lengths before the trim
+  for (size_t i = 0; i < count; i++) {
+    const size_t k = root_offsets[i + 1] - root_offsets[i];
+    meta[i] = lens[i] > k ? lens[i] - k : (k ? 0 : lens[i]);       // self.degree() < other.degree(): the zero polynomial (polynomial.rs:372)
+    if (meta[i] && k > maxk) maxk = k;
+    out_lens[i] = 0;
+  }
+  if (stride == 0) return MZK_OK;
+  char *bA = nullptr, *bB = nullptr;
+  if (maxk >= 2) MZK_TRY(ws_get(WS_MISC_A, count * stride * esz, (void**)&bA));
+  if (maxk >= 3) MZK_TRY(ws_get(WS_MISC_B, count * stride * esz, (void**)&bB));
+  std::vector<SdJob> jobs;
+  std::vector<size_t> rounds(maxk, 0);
+  for (size_t r = 0; r < maxk; r++)
+    for (size_t i = 0; i < count; i++) {
+      const size_t k = root_offsets[i + 1] - root_offsets[i];
+      if (k <= r || !meta[i]) continue;
+      const char* src = r == 0 ? (const char*)d_polys + i * stride * esz : ((r & 1) ? bA : bB) + i * stride * esz;
+      char* dst = r == k - 1 ? (char*)d_out + i * stride * esz : ((r & 1) ? bB : bA) + i * stride * esz;
+      jobs.push_back({src, lens[i] - r, roots + (root_offsets[i] + r) * nl, nullptr, nullptr, dst});
+      rounds[r]++;
+    }
+  auto fail = [&](int rc) { (void)hipStreamSynchronize(s); return rc; };
+  for (size_t i = 0; i < count; i++)                        // no roots: the row itself
+    if (root_offsets[i + 1] == root_offsets[i] && lens[i] &&
+        hipMemcpyAsync((char*)d_out + i * stride * esz, (const char*)d_polys + i * stride * esz, lens[i] * esz, hipMemcpyDeviceToDevice, s) != hipSuccess)
+      return fail(MZK_E_HIP);
+  int rc = synth_div_field_dev(fid, jobs.data(), rounds.data(), (int)maxk, s);
+  if (rc != MZK_OK) return fail(rc);
+  std::vector<size_t> qlens(count);
+  for (size_t i = 0; i < count; i++) qlens[i] = (size_t)meta[i];
+  rc = rows_trimmed_len_dev(fid, d_out, stride, qlens.data(), count, stride, nullptr, 0, WS_MISC_E, out_lens, s);
+  if (rc != MZK_OK) return fail(rc);
+  return MZK_OK;
+}
 // batch_open_kzg (kzg.rs:74-88).  y_i = f(u_i) is b_0 of the division of f by (X - u_i).  The quotient of f by prod (X - u_i) --
 // which equals (f - I)/Z because I = f mod Z -- is k successive divisions (each drops the remainder b_0): one round of k
 // evaluations, then one round per quotient.  d_ys: k * 8 words, d_w_xy: 16 words.
@@ -565,3 +652,38 @@ int kzg_open_many_dev(const mzk_srs* srs, const void* d_coefs, size_t n, size_t 
 }
 
 }  // namespace mzk
+
+using namespace mzk;
+
+extern "C" {
+
+int mzk_poly_div_roots_dev(int field_id, const void* d_polys, size_t stride, const size_t* lens, size_t count, const uint64_t* roots,
+                           const size_t* root_offsets, void* d_out, size_t* out_lens, void* stream) {
+  MZK_ENTER();
+  MZK_TRY(poly_div_roots_check(field_id, d_polys, stride, lens, count, roots, root_offsets, d_out, out_lens));
+  WsGuard wsg((hipStream_t)stream);
+  return poly_div_roots_dev_impl(field_id, d_polys, stride, lens, count, roots, root_offsets, d_out, out_lens, (hipStream_t)stream);
+}
+
+int mzk_poly_div_roots(int field_id, const uint64_t* polys, size_t stride, const size_t* lens, size_t count, const uint64_t* roots,
+                       const size_t* root_offsets, uint64_t* out, size_t* out_lens) {
+  MZK_ENTER();
+  MZK_TRY(poly_div_roots_check(field_id, polys, stride, lens, count, roots, root_offsets, out, out_lens));
+  if (count == 0) return MZK_OK;
+  const HostField* hf = host_field(field_id);
+  for (size_t i = 0; i < count; i++)
+    for (size_t j = 0; j < lens[i]; j++)
+      if (!h_is_canonical(hf, polys + (i * stride + j) * hf->nl)) { set_error("poly_div_roots: row %zu, coefficient %zu not canonical", i, j); return MZK_E_RANGE; }
+  const size_t bytes = count * stride * field_bytes(field_id);
+  hipStream_t s = ctx().stream;
+  WsGuard wsg(s);
+  char* d;
+  MZK_TRY(ws_get(WS_MISC_F, 2 * bytes + 16, (void**)&d));
+  if (bytes) MZK_HIP(hipMemcpyAsync(d, polys, bytes, hipMemcpyHostToDevice, s));
+  const int rc = poly_div_roots_dev_impl(field_id, d, stride, lens, count, roots, root_offsets, d + bytes, out_lens, s);
+  if (rc != MZK_OK) { (void)hipStreamSynchronize(s); return rc; }
+  if (bytes == 0) return MZK_OK;
+  return d2h_sync(out, d + bytes, bytes, s);
+}
+
+}  // extern "C"

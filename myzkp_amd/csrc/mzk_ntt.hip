@@ -817,23 +817,16 @@ __global__ void k_gen_inter_table(Words8 root_plain, uint64_t emul, int lgn, int
 }
 // Polynomial::scale (polynomial.rs:167-174) + zero padding (ntt.rs:264-267): out[i] = coef[i] * offset^i
 // for i < n_coef, 0 for n_coef <= i < order.
+// one lane's chunk of a scale-and-pad: out[j] = coef[j] * factor^j for j < n_coef, 0 for n_coef <= j < width, j in [j0, j0 + GEN_CHUNK)
 template <class P>
-__global__ void k_coset_scale_pad(const u32* __restrict__ coef, size_t n_coef, Words8 offset_plain,
-                                  u32* __restrict__ out, size_t order, size_t chunks_per, size_t batch) {
-  const size_t chunk = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const size_t o = chunk / chunks_per;                 // transform of the batch (vectors back to back: n_coef in, order out)
-  if (o >= batch) return;
-  const size_t j0 = (chunk - o * chunks_per) * GEN_CHUNK;
-  if (j0 >= order) return;
-  coef += o * n_coef * P::NW;
-  out += o * order * P::NW;
+__device__ __forceinline__ void scale_pad_chunk(const u32* __restrict__ coef, size_t n_coef, const Words8& factor_plain, u32* __restrict__ out, size_t width, size_t j0) {
   if (j0 >= n_coef) {
-    for (int i = 0; i < GEN_CHUNK && j0 + i < order; i++) gstore<P>(out, j0 + i, fe_zero<P>());
+    for (int i = 0; i < GEN_CHUNK && j0 + i < width; i++) gstore<P>(out, j0 + i, fe_zero<P>());
     return;
   }
-  Fe<P> g = fe_to_mont<P>(fe_unpack<P>(offset_plain.w));
+  Fe<P> g = fe_to_mont<P>(fe_unpack<P>(factor_plain.w));
   Fe<P> cur = fe_pow_u64<P>(g, j0);
-  for (int i = 0; i < GEN_CHUNK && j0 + i < order; i++) {
+  for (int i = 0; i < GEN_CHUNK && j0 + i < width; i++) {
     if (j0 + i < n_coef) {
       Fe<P> c = gload<P>(coef, j0 + i);
       gstore<P>(out, j0 + i, fe_reduce<P>(FeAsm<P>::mul(c, cur)));
@@ -842,6 +835,16 @@ __global__ void k_coset_scale_pad(const u32* __restrict__ coef, size_t n_coef, W
       gstore<P>(out, j0 + i, fe_zero<P>());
     }
   }
+}
+template <class P>
+__global__ void k_coset_scale_pad(const u32* __restrict__ coef, size_t n_coef, Words8 offset_plain,
+                                  u32* __restrict__ out, size_t order, size_t chunks_per, size_t batch) {
+  const size_t chunk = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const size_t o = chunk / chunks_per;                 // transform of the batch (vectors back to back: n_coef in, order out)
+  if (o >= batch) return;
+  const size_t j0 = (chunk - o * chunks_per) * GEN_CHUNK;
+  if (j0 >= order) return;
+  scale_pad_chunk<P>(coef + o * n_coef * P::NW, n_coef, offset_plain, out + o * order * P::NW, order, j0);
 }
 // Polynomial::scale (polynomial.rs:167-174) with a leading constant: out[i] = lead * in[i] * ratio^i, plain in and out,
 // in place allowed.  The twiddle step of the sharded transforms (myzkp_amd/sharded.py) and their n^-1.
@@ -1528,6 +1531,118 @@ int coset_divide_dev_impl(int fid, const void* d_lhs, size_t tl, const void* d_r
     hipLaunchKernelGGL((k_coset_scale_pad<M128Params>), dim3(sblocks), dim3(256), 0, s, (const u32*)eb, ql, ow, (u32*)d_out, ql, chunks, (size_t)1);
   else
     hipLaunchKernelGGL((k_coset_scale_pad<FrParams>), dim3(sblocks), dim3(256), 0, s, (const u32*)eb, ql, ow, (u32*)d_out, ql, chunks, (size_t)1);
+  MZK_HIP(hipGetLastError());
+  return MZK_OK;
+}
+
+// ---- fast_coset_divide for many numerators over one denominator (fast_stark.rs:261-273) ----------------------------------------------
+// dst row R.dst_row (dst_stride apart) = src row R.src_row (src_stride apart) scaled: element j times factor^j for j < R.len, zero for
+// R.len <= j < width.  k_coset_scale_pad with a row table (both run scale_pad_chunk): the scale-and-pad before the forward transforms (src = the numerators,
+// width = dst_stride = order) and the scale-back after the inverse ones (src = the quotient transforms, factor = offset^-1).
+struct ScaleRow { unsigned long long src_row, dst_row, len; };
+template <class P>
+__global__ __launch_bounds__(256) void k_scale_rows(const u32* __restrict__ src, size_t src_stride, u32* __restrict__ dst, size_t dst_stride,
+                                                    const ScaleRow* __restrict__ rows, size_t nrows, Words8 factor_plain, size_t width, size_t chunks_per) {
+  const size_t chunk = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const size_t o = chunk / chunks_per;
+  if (o >= nrows) return;
+  const size_t j0 = (chunk - o * chunks_per) * GEN_CHUNK;
+  if (j0 >= width) return;
+  const ScaleRow R = rows[o];
+  scale_pad_chunk<P>(src + R.src_row * src_stride * P::NW, R.len, factor_plain, dst + R.dst_row * dst_stride * P::NW, width, j0);
+}
+// out[a] = max(out[a], 1 + index of the last non-zero element among the first lens[a] of row a) -- out zeroed before the launch.  Row a <
+// count is rows + a * stride; row `count`, when there is one, is `extra` (a vector elsewhere: the denominator of a division).
+// clear_to != 0: the elements [lens[a], clear_to) of every row of `rows` are set to zero in the same pass.
+// The grid is rows x blocks-of-the-LONGEST-row: sized for a STARK's two or three rows of equal length.  A batch of one long and many
+// short rows launches mostly idle blocks (each still runs the LDS reduction); that shape works but is not a tuned path.
+template <class P>
+__global__ __launch_bounds__(256) void k_rows_trim(u32* __restrict__ rows, size_t stride, size_t count, const u32* __restrict__ extra, unsigned bpr,
+                                                   const unsigned long long* __restrict__ lens, unsigned long long* __restrict__ out, size_t clear_to) {
+  __shared__ unsigned long long sh[256];
+  const size_t a = blockIdx.x / bpr;
+  const size_t j = (size_t)(blockIdx.x % bpr) * 256 + threadIdx.x;
+  unsigned long long best = 0;
+  if (j < lens[a]) {
+    const uint4* v = reinterpret_cast<const uint4*>(a < count ? rows + (a * stride + j) * P::NW : extra + j * P::NW);
+    u32 nz = 0;
+#pragma unroll
+    for (int q = 0; q < P::NW / 4; q++) { const uint4 w = v[q]; nz |= w.x | w.y | w.z | w.w; }
+    if (nz) best = j + 1;
+  } else if (a < count && j < clear_to) {
+    uint4* o = reinterpret_cast<uint4*>(rows + (a * stride + j) * P::NW);
+#pragma unroll
+    for (int q = 0; q < P::NW / 4; q++) o[q] = make_uint4(0, 0, 0, 0);
+  }
+  sh[threadIdx.x] = best;
+  __syncthreads();
+  for (int off = 128; off >= 1; off >>= 1) {
+    if ((int)threadIdx.x < off && sh[threadIdx.x + off] > sh[threadIdx.x]) sh[threadIdx.x] = sh[threadIdx.x + off];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0 && sh[0]) atomicMax(&out[a], sh[0]);
+}
+int rows_trimmed_len_dev(int fid, void* d_rows, size_t stride, const size_t* lens, size_t count, size_t clear_to, const void* d_extra, size_t extra_len,
+                         WsSlot slot, size_t* out_lens, hipStream_t s) {
+  const size_t total = count + (d_extra ? 1 : 0);
+  if (total == 0) return MZK_OK;
+  size_t longest = clear_to;
+  std::vector<unsigned long long> meta(2 * total, 0);
+  for (size_t i = 0; i < total; i++) { meta[i] = i < count ? lens[i] : extra_len; longest = meta[i] > longest ? meta[i] : longest; out_lens[i] = 0; }
+  if (longest == 0) return MZK_OK;
+  const size_t bpr = (longest + 255) / 256;
+  if (total > (((size_t)1 << 31) - 1) / bpr) { set_error("trimmed lengths: %zu rows of %zu elements are too many", total, longest); return MZK_E_LENGTH; }
+  unsigned long long* d_meta;
+  MZK_TRY(ws_get(slot, 2 * total * sizeof(unsigned long long), (void**)&d_meta));
+  MZK_HIP(hipMemcpyAsync(d_meta, meta.data(), 2 * total * sizeof(unsigned long long), hipMemcpyHostToDevice, s));
+  if (fid == MZK_FIELD_M128)
+    hipLaunchKernelGGL((k_rows_trim<M128Params>), dim3((unsigned)(total * bpr)), dim3(256), 0, s, (u32*)d_rows, stride, count, (const u32*)d_extra, (unsigned)bpr, (const unsigned long long*)d_meta, d_meta + total, clear_to);
+  else
+    hipLaunchKernelGGL((k_rows_trim<FrParams>), dim3((unsigned)(total * bpr)), dim3(256), 0, s, (u32*)d_rows, stride, count, (const u32*)d_extra, (unsigned)bpr, (const unsigned long long*)d_meta, d_meta + total, clear_to);
+  if (hipGetLastError() != hipSuccess) { (void)hipStreamSynchronize(s); set_error("trimmed lengths: launch failed"); return MZK_E_HIP; }
+  const int rc = d2h_sync(meta.data(), d_meta + total, total * sizeof(unsigned long long), s);
+  if (rc != MZK_OK) { (void)hipStreamSynchronize(s); return rc; }
+  for (size_t i = 0; i < total; i++) out_lens[i] = (size_t)meta[i];
+  return MZK_OK;
+}
+template <class P>
+static void launch_scale_rows(const void* src, size_t src_stride, void* dst, size_t dst_stride, const ScaleRow* d_rows, size_t nrows, const Words8& f, size_t width,
+                              hipStream_t s) {
+  const size_t chunks_per = (width + GEN_CHUNK - 1) / GEN_CHUNK;
+  hipLaunchKernelGGL((k_scale_rows<P>), dim3((unsigned)((chunks_per * nrows + 255) / 256)), dim3(256), 0, s, (const u32*)src, src_stride, (u32*)dst, dst_stride,
+                     d_rows, nrows, f, width, chunks_per);
+}
+int coset_divide_rows_dev_impl(int fid, const void* d_lhs, size_t lhs_stride, const CdRow* rows, size_t nrows, const void* d_rhs, size_t tr,
+                               const uint64_t* offset_host, const uint64_t* root_host, size_t order, void* d_out, size_t out_stride, hipStream_t s) {
+  if (nrows == 0) return MZK_OK;
+  const HostField* hf = host_field(fid);
+  const size_t esz = field_bytes(fid);
+  if (nrows > ((size_t)1 << 40) / order) { set_error("fast_coset_divide: %zu rows of order %zu are too many", nrows, order); return MZK_E_LENGTH; }
+  void *ea, *eb;
+  ScaleRow* d_tab;
+  MZK_TRY(ws_get(WS_MISC_A, nrows * order * esz, &ea));
+  MZK_TRY(ws_get(WS_MISC_B, order * esz, &eb));
+  MZK_TRY(ws_get(WS_MISC_F, 2 * nrows * sizeof(ScaleRow), (void**)&d_tab));
+  std::vector<ScaleRow> tab(2 * nrows);
+  for (size_t k = 0; k < nrows; k++) {
+    tab[k] = {rows[k].row, k, rows[k].tl};                                // numerator row -> transform k
+    tab[nrows + k] = {k, rows[k].row, rows[k].tl - tr + 1};               // transform k -> quotient row
+  }
+  MZK_HIP(hipMemcpyAsync(d_tab, tab.data(), 2 * nrows * sizeof(ScaleRow), hipMemcpyHostToDevice, s));
+  Words8 fw, bw;
+  uint64_t oinv[4];
+  h_invmod(hf, oinv, offset_host);
+  to_words(offset_host, hf->nl, &fw);
+  to_words(oinv, hf->nl, &bw);
+  if (fid == MZK_FIELD_M128) launch_scale_rows<M128Params>(d_lhs, lhs_stride, ea, order, d_tab, nrows, fw, order, s);
+  else launch_scale_rows<FrParams>(d_lhs, lhs_stride, ea, order, d_tab, nrows, fw, order, s);
+  MZK_HIP(hipGetLastError());
+  MZK_TRY(ntt_batch_dev_impl(fid, root_host, ea, ea, order, nrows, 0, s));
+  MZK_TRY(coset_lde_dev_impl(fid, d_rhs, tr, offset_host, root_host, eb, order, s));
+  MZK_TRY(pointwise_div_shared_dev(fid, ea, order, eb, ea, order, order, nrows, s));      // one inversion chain serves every row
+  MZK_TRY(ntt_batch_dev_impl(fid, root_host, ea, ea, order, nrows, 1, s));
+  if (fid == MZK_FIELD_M128) launch_scale_rows<M128Params>(ea, order, d_out, out_stride, d_tab + nrows, nrows, bw, out_stride, s);
+  else launch_scale_rows<FrParams>(ea, order, d_out, out_stride, d_tab + nrows, nrows, bw, out_stride, s);
   MZK_HIP(hipGetLastError());
   return MZK_OK;
 }

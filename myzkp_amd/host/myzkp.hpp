@@ -19,17 +19,21 @@
 //   Merkle::commit / open, commit_codeword   algebra/merkle.rs:15-46, zkstark/fri.rs:160-166
 //   fri_split_and_fold, fri_commit           zkstark/fri.rs:144-209
 //   FriProof, fri_prove                      zkstark/fri.rs:71-143      -> mzk_fri_prove
+//   boundary_quotients, fast_stark_dims      zkstark/fast_stark.rs:217-224, :573-616 -> mzk_poly_div_roots, mzk_stark_plan
+//   FastStark (preprocess, prove), FastStarkProof   zkstark/fast_stark.rs:22-75, :177-396 -> mzk_stark_new, mzk_stark_prove
 //   batch::split_and_fold / commit_gemini / open_gemini / prove_sumcheck   algebra/gemini.rs:51-144, algebra/sumcheck.rs:128-167
 //
 // Values are held canonical (u64 limbs) -- the ABI wire format; arithmetic on single elements that the
 // reference does on the host (a handful of scalar ops in tests) is not offered here: this header only
 // marshals the bulk operations to the GPU.  Rust panics become C++ exceptions carrying the same text.
 #pragma once
+#include <algorithm>
 #include <array>
 #include <cstdint>
 #include <cstring>
 #include <stdexcept>
 #include <string>
+#include <tuple>
 #include <type_traits>
 #include <utility>
 #include <map>
@@ -346,6 +350,158 @@ Polynomial<F> weighted_combination(const std::vector<Polynomial<F>>& terms, cons
   expect(mzk_poly_lincomb(Polynomial<F>::field_id(), flat.data(), off.data(), terms.size(), w.data(), shifts.data(), out.data(), cap, &len));
   return Polynomial<F>{from_wire<F>(out, len)};
 }
+
+// the boundary quotients of FastStark::prove (fast_stark.rs:217-224): (trace_polynomials[s] - interpolant_s) / zerofier_s with zerofier_s =
+// from_monomials(zerofier_roots[s]).  The interpolant has a lower degree than the zerofier, so the quotient of the long division
+// (polynomial.rs:371-405) does not depend on it and it is not an argument; an inexact division drops its remainder as the reference does.
+template <class F>
+std::vector<Polynomial<F>> boundary_quotients(const std::vector<Polynomial<F>>& trace_polynomials, const std::vector<std::vector<F>>& zerofier_roots) {
+  if (zerofier_roots.size() != trace_polynomials.size()) throw Panic(MZK_E_LENGTH, "index out of bounds: one list of zerofier roots per trace polynomial");
+  const size_t nl = F().value.size(), m = trace_polynomials.size();
+  size_t stride = 0;
+  for (const auto& q : trace_polynomials) stride = std::max(stride, q.coef.size());
+  std::vector<uint64_t> flat(std::max<size_t>(m * stride, 1) * nl, 0), out(flat.size(), 0), roots;
+  std::vector<size_t> lens(m + 1, 0), off(1, 0), out_lens(m + 1, 0);
+  for (size_t s = 0; s < m; s++) {
+    auto w = to_wire(trace_polynomials[s].coef);
+    std::copy(w.begin(), w.end(), flat.begin() + s * stride * nl);
+    lens[s] = trace_polynomials[s].coef.size();
+    auto r = to_wire(zerofier_roots[s]);
+    roots.insert(roots.end(), r.begin(), r.end());
+    off.push_back(roots.size() / nl);
+  }
+  roots.resize(roots.size() + nl);      // never an empty pointer
+  expect(mzk_poly_div_roots(Polynomial<F>::field_id(), flat.data(), stride, lens.data(), m, roots.data(), off.data(), out.data(), out_lens.data()));
+  std::vector<Polynomial<F>> res(m);
+  for (size_t s = 0; s < m; s++) {
+    std::vector<uint64_t> row(out.begin() + s * stride * nl, out.begin() + (s * stride + out_lens[s]) * nl);
+    res[s].coef = from_wire<F>(row, out_lens[s]);
+  }
+  return res;
+}
+// initialize_fast_stark_m128 and the degree helpers of FastStark (fast_stark.rs:573-616, :77-111, :150-160) as numbers: mzk_stark_plan.
+// boundary: (cycle, register) pairs -- the values do not enter the sizes.
+template <class F>
+mzk_stark_dims fast_stark_dims(size_t expansion_factor, size_t num_colinearity_checks, size_t num_registers, size_t num_cycles,
+                               size_t transition_constraints_degree, const std::vector<MPolynomial<F>>& transition_constraints,
+                               const std::vector<std::pair<size_t, size_t>>& boundary) {
+  std::vector<uint64_t> coefs;
+  std::vector<uint32_t> exps;
+  std::vector<size_t> toff, cyc(boundary.size() + 1, 0), reg(boundary.size() + 1, 0);
+  MPolynomial<F>::term_table(transition_constraints, 1 + 2 * num_registers, coefs, exps, toff);
+  exps.push_back(0);                    // never an empty pointer
+  for (size_t i = 0; i < boundary.size(); i++) { cyc[i] = boundary[i].first; reg[i] = boundary[i].second; }
+  mzk_stark_dims d;
+  expect(mzk_stark_plan(Polynomial<F>::field_id(), expansion_factor, num_colinearity_checks, num_registers, num_cycles, transition_constraints_degree,
+                        exps.data(), toff.data(), transition_constraints.size(), cyc.data(), reg.data(), boundary.size(), &d));
+  return d;
+}
+
+// FastStarkProof (fast_stark.rs:22-32).  fri_proof is the packed proof of mzk_fri_prove (mzk_fri_proof_layout) with the top-level
+// indices sorted; a Merkle path is its entries bottom-up (the sibling leaf's bytes, then digests).
+using StarkPath = std::vector<std::vector<uint8_t>>;
+template <class F> struct FastStarkProof {
+  std::vector<uint8_t> fri_proof;
+  std::vector<std::array<uint8_t, 32>> bqc_roots;
+  std::vector<F> bqc_points;
+  std::vector<StarkPath> bqc_paths;
+  std::array<uint8_t, 32> rdc_root;
+  std::vector<F> rdc_points, tzc_points;
+  std::vector<StarkPath> rdc_paths, tzc_paths;
+  std::vector<size_t> duplicated_indices;      // not in the reference's struct: the verifier recomputes them
+};
+// FastStark (fast_stark.rs:34-50) over mzk_stark_new / mzk_stark_prove.  preprocess() returns the transition zerofier's Merkle root (the
+// zerofier and its codeword stay on the device); prove() takes the trace WITH its random rows appended and the randomizer polynomial's
+// max_degree + 1 coefficients -- the reference draws both itself (fast_stark.rs:187-195, :275-282), here the caller does.
+template <class F> struct FastStark {
+  using Boundary = std::vector<std::tuple<size_t, size_t, F>>;       // (cycle, register, value), stark.rs
+  size_t expansion_factor, num_colinearity_checks, num_registers, original_trace_length, transition_constraints_degree;
+  std::vector<MPolynomial<F>> transition_constraints;
+  mzk_stark* handle = nullptr;
+  FastStark(size_t expansion, size_t checks, size_t registers, size_t cycles, size_t degree, const F& generator, const std::vector<MPolynomial<F>>& air)
+      : expansion_factor(expansion), num_colinearity_checks(checks), num_registers(registers), original_trace_length(cycles),
+        transition_constraints_degree(degree), transition_constraints(air) {
+    std::vector<uint64_t> coefs;
+    std::vector<uint32_t> exps;
+    std::vector<size_t> toff;
+    MPolynomial<F>::term_table(air, 1 + 2 * registers, coefs, exps, toff);
+    coefs.resize(coefs.size() + 4);
+    exps.push_back(0);
+    expect(mzk_stark_new(Polynomial<F>::field_id(), expansion, checks, registers, cycles, degree, generator.value.data(), coefs.data(), exps.data(), toff.data(),
+                         air.size(), &handle));
+  }
+  FastStark(const FastStark&) = delete;
+  FastStark& operator=(const FastStark&) = delete;
+  ~FastStark() { if (handle) mzk_stark_free(handle); }
+  std::array<uint8_t, 32> preprocess() const {
+    std::array<uint8_t, 32> root;
+    expect(mzk_stark_transition_zerofier_root(handle, root.data()));
+    return root;
+  }
+  mzk_stark_dims dims(const Boundary& boundary) const {
+    std::vector<std::pair<size_t, size_t>> b;
+    for (const auto& e : boundary) b.push_back({std::get<0>(e), std::get<1>(e)});
+    return fast_stark_dims<F>(expansion_factor, num_colinearity_checks, num_registers, original_trace_length, transition_constraints_degree,
+                              transition_constraints, b);
+  }
+  FastStarkProof<F> prove(const std::vector<std::vector<F>>& trace, const Boundary& boundary, const Polynomial<F>& randomizer_polynomial) const {
+    const size_t nl = F().value.size(), m = num_registers;
+    const mzk_stark_dims d = dims(boundary);
+    uint64_t off[MZK_STARK_SECTIONS], size[MZK_STARK_SECTIONS], total = 0;
+    expect(mzk_stark_proof_layout(&d, Polynomial<F>::field_id(), off, size, &total));
+    std::vector<uint64_t> t;
+    for (const auto& row : trace) {
+      if (row.size() != m) throw Panic(MZK_E_LENGTH, "index out of bounds: a trace row has " + std::to_string(row.size()) + " registers");
+      auto w = to_wire(row);
+      t.insert(t.end(), w.begin(), w.end());
+    }
+    t.resize(t.size() + nl);
+    std::vector<size_t> bc(boundary.size() + 1, 0), br(boundary.size() + 1, 0);
+    std::vector<uint64_t> bv((boundary.size() + 1) * nl, 0);
+    for (size_t i = 0; i < boundary.size(); i++) {
+      bc[i] = std::get<0>(boundary[i]); br[i] = std::get<1>(boundary[i]);
+      std::memcpy(&bv[i * nl], std::get<2>(boundary[i]).value.data(), 8 * nl);
+    }
+    auto r = to_wire(randomizer_polynomial.coef);
+    r.resize(r.size() + nl);
+    std::vector<uint8_t> raw(total);
+    expect(mzk_stark_prove(handle, t.data(), trace.size(), bc.data(), br.data(), bv.data(), boundary.size(), r.data(), raw.data(), raw.size()));
+    FastStarkProof<F> p;
+    const size_t k = d.num_indices, esz = 8 * nl;
+    size_t depth = 0;
+    while (((size_t)1 << depth) < d.fri_domain_length) depth++;
+    p.fri_proof.assign(raw.begin() + off[MZK_STARK_FRI], raw.begin() + off[MZK_STARK_FRI] + size[MZK_STARK_FRI]);
+    p.duplicated_indices.resize(k);
+    for (size_t i = 0; i < k; i++) { uint64_t v; std::memcpy(&v, &raw[off[MZK_STARK_INDICES] + 8 * i], 8); p.duplicated_indices[i] = (size_t)v; }
+    p.bqc_roots.resize(m);
+    for (size_t s = 0; s < m; s++) std::memcpy(p.bqc_roots[s].data(), &raw[off[MZK_STARK_BQC_ROOTS] + 32 * s], 32);
+    std::memcpy(p.rdc_root.data(), &raw[off[MZK_STARK_RDC_ROOT]], 32);
+    auto points = [&](int sec, size_t count) {
+      std::vector<F> v(count);
+      for (size_t i = 0; i < count; i++) std::memcpy(v[i].value.data(), &raw[off[sec] + i * esz], esz);
+      return v;
+    };
+    p.bqc_points = points(MZK_STARK_BQC_POINTS, m * k);
+    p.rdc_points = points(MZK_STARK_RDC_POINTS, k);
+    p.tzc_points = points(MZK_STARK_TZC_POINTS, k);
+    size_t entry = 0;
+    auto paths = [&](int sec, size_t count) {
+      std::vector<StarkPath> v(count);
+      for (size_t q = 0; q < count; q++)
+        for (size_t j = 0; j < depth; j++, entry++) {
+          uint64_t len;
+          std::memcpy(&len, &raw[off[MZK_STARK_PATH_LENS] + 8 * entry], 8);
+          const uint8_t* e = &raw[off[sec] + (q * depth + j) * MZK_FRI_PATH_STRIDE];
+          v[q].emplace_back(e, e + len);
+        }
+      return v;
+    };
+    p.bqc_paths = paths(MZK_STARK_BQC_PATHS, m * k);
+    p.rdc_paths = paths(MZK_STARK_RDC_PATHS, k);
+    p.tzc_paths = paths(MZK_STARK_TZC_PATHS, k);
+    return p;
+  }
+};
 
 
 // ---- G2 (bn128.rs:33-49): Fq2 = Fq[u]/(u^2 + 1), G2Point = EllipticCurvePoint<Fq2, BN128Curve> ----------

@@ -14,7 +14,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HDR = os.path.join(ROOT, "include", "mzk.h")
 OUT = os.path.join(ROOT, "include", "mzk_ffi.rs")
 
-HANDLES = ("mzk_srs_multi", "mzk_srs", "mzk_merkle")
+HANDLES = ("mzk_srs_multi", "mzk_srs", "mzk_merkle", "mzk_stark")
+STRUCTS = ("mzk_stark_dims",)      # plain structs of uint64_t fields, passed by pointer: emitted as #[repr(C)] (c_structs)
 SCALARS = {"int": "c_int", "unsigned": "c_uint", "unsigned int": "c_uint", "size_t": "usize", "uint64_t": "u64", "uint32_t": "u32",
            "uint8_t": "u8", "double": "f64", "char": "c_char", "void": "c_void"}
 CHALLENGE = 'extern "C" fn(*mut c_void, c_int, c_int, *const u8, usize, *mut u64) -> c_int'
@@ -42,6 +43,28 @@ def c_prototypes(path=HDR):
                 params.append((pname, ptype))
         protos.append((name, None if ret == "void" else c_type(ret), params))
     return protos
+
+
+def c_structs(path=HDR):
+    """[(name, [(field, array length or None)])] for the STRUCTS of the header: `typedef struct X { uint64_t a, b[N], ...; ... } X;` with
+    array lengths given as numbers or as the header's enum constants"""
+    txt = strip_comments(open(path).read())
+    consts = {k: int(v) for body in re.findall(r"enum\s*\{([^}]*)\}", txt) for k, v in re.findall(r"([A-Z][A-Z0-9_]*)\s*=\s*(\d+)", body)}
+    out = []
+    for name in STRUCTS:
+        body = re.search(r"typedef struct %s \{(.*?)\} %s;" % (name, name), txt, flags=re.S).group(1)
+        fields = []
+        for decl in body.split(";"):
+            decl = " ".join(decl.split())
+            if not decl:
+                continue
+            assert decl.startswith("uint64_t "), decl
+            for f in decl[len("uint64_t "):].split(","):
+                m = re.match(r"\s*([a-z_0-9]+)\s*(?:\[([A-Za-z0-9_]+)\])?\s*$", f)
+                n = m.group(2)
+                fields.append((m.group(1), None if n is None else (int(n) if n.isdigit() else consts[n])))
+        out.append((name, fields))
+    return out
 
 
 def split_args(args):
@@ -85,6 +108,8 @@ def c_type(t):
     bname = " ".join(base)
     if bname in HANDLES or bname.startswith("struct "):
         rust = "c_void"
+    elif bname in STRUCTS:
+        rust = bname
     elif bname in SCALARS:
         rust = SCALARS[bname]
     else:
@@ -111,7 +136,8 @@ def emit():
     lines = ['// GENERATED by tools/gen_rust_ffi.py from include/mzk.h -- do not edit; `python tools/gen_rust_ffi.py` rewrites it.',
              '// The complete `extern "C"` surface of libmzk_hip.so (%d functions) for the Rust shim of INTEGRATION.md section 2:' % len(protos),
              '//     #[cfg(feature = "mi355x")] #[path = "../../../../include/mzk_ffi.rs"] pub mod ffi;',
-             '// Handles (mzk_srs, mzk_srs_multi, mzk_merkle) are opaque: `c_void` behind the pointer.  Status codes: include/mzk.h.',
+             '// Handles (mzk_srs, mzk_srs_multi, mzk_merkle, mzk_stark) are opaque: `c_void` behind the pointer.  Plain structs (%s) are #[repr(C)] below.' % ", ".join(STRUCTS),
+             '// Status codes: include/mzk.h.',
              '#![allow(non_camel_case_types, dead_code)]',
              'use std::os::raw::{c_char, c_int, c_uint, c_void};',
              '',
@@ -122,6 +148,8 @@ def emit():
              'pub const MZK_LAYOUT_CONTIGUOUS: c_int = 0;',
              'pub const MZK_LAYOUT_CYCLIC: c_int = 1;',
              '',
+             ] + ['#[repr(C)]\n#[derive(Clone, Copy, Debug)]\npub struct %s {\n%s}\n' % (n, "".join("    pub %s: %s,\n" % (f, "u64" if k is None else "[u64; %d]" % k) for f, k in fs))
+                  for n, fs in c_structs()] + [
              '#[link(name = "mzk_hip")]',
              'extern "C" {']
     for name, ret, params in protos:
