@@ -740,8 +740,10 @@ int mzk_host_field_op(int field_id, int op, const uint64_t* a, const uint64_t* b
 
 /* Device self-check: the throughput kernels compute their Montgomery products with hand-scheduled inline-asm blocks
  * (myzkp_amd/csrc/mzk_field_asm.h); this runs both forms (asm and portable C++) over n operand sets per field -- random,
- * all-ones, zero and the widest lazy limbs -- and returns the number of differing results (must be 0).
- * field_id may also be MZK_FIELD_FQ. */
+ * all-ones, zero and the widest lazy limbs; for M128 also the signed sparse product of the transform's butterflies on i32 limbs of
+ * either sign -- and returns the number of differing results (must be 0).  field_id may also be MZK_FIELD_FQ.
+ * These three are self-comparisons (two device forms of one function, a count back); the arithmetic probe below is what compares
+ * each form with integers. */
 int mzk_selftest_field_asm(int field_id, uint64_t seed, size_t n, uint64_t* mismatches);
 /* Device self-check of the ROW-cooperative group operations behind the MSM tails (myzkp_amd/csrc/mzk_row.h: one point
  * operation per wave, field elements spread over DPP rows): n pairs of XYZZ points -- independent points, P + P, P + (-P),
@@ -754,6 +756,34 @@ int mzk_selftest_row_ec(uint64_t seed, size_t n, int dbl_reps, uint64_t* mismatc
  * ones -- against the single-lane safegcd (which the host build pins on the oracle) and against a * a^-1 == 1.  Returns the
  * number of values that differ (must be 0). */
 int mzk_selftest_inv_wave(uint64_t seed, size_t n, uint64_t* mismatches);
+/* The arithmetic probe (myzkp_amd/csrc/mzk_probe.h, mzk_probe.hip): where the three self-checks above compare one device form with
+ * another and return a count, the probe runs ONE device function per call on operands the host supplies as raw 29-bit limbs and
+ * hands the raw result limbs back -- no reduction, packing or comparison on the way -- so that the test-suite can judge every limb
+ * against integer arithmetic (tests/arith_model.py, tests/test_gpu_arith_probe.py; the same table runs through the host build of
+ * the headers in tests/test_hostcheck_probe.py).  n <= 2^20 cases per call; host pointers; unknown field / op / form, a form the
+ * op does not have, null pointers or a larger n: MZK_E_ARG with nothing launched.
+ *   mzk_selftest_field_probe: in = n x arity x L limbs (L = 9 for Fr / Fq, 5 for M128; arity 1 .. 4, operands in the order of the
+ *     function's parameters), out = n x L limbs (the zero tests: limb 0 = 0 / 1).  MZK_PROBE_SHOUP_MUL takes (x, w, wq) and reads
+ *     w, wq from the first case of each wave of 64 (scalar registers, as the transform holds them).  form: MZK_PROBE_FORM_CPP
+ *     everywhere; _ASM for MUL, SQR, MUL_ADD2, SHOUP_MUL (Fr), SMUL (M128); _WAVE for INV over Fq (invw::inv, one case per wave).
+ *   mzk_selftest_g1_probe: a, b = XYZZ operands as raw slots (4 x 9 limbs, coordinate-major, Montgomery form, all-zero = infinity)
+ *     or affine operands (2 x 9 limbs, Montgomery form, canonical): MADD_SIGNED(a slot, b affine, neg[i]), MADD(a slot, b affine),
+ *     ADD(a slot, b slot), DBL(a slot), DBL_AFFINE(a affine), TO_AFFINE(a slot); out = one slot per case holding the limbs the
+ *     function returned (infinity all-zero; TO_AFFINE: 16 plain ABI words x || y, then zeros).  form: _CPP / _ASM (the product
+ *     routines of the single-lane group law), _QUAD (xyzz_add_quad / xyzz_dbl_quad, one case per DPP quad), _ROW (rowop::add /
+ *     rowop::dbl, one case per wave through the packed records of rowop::load / rowop::store), _WAVE (TO_AFFINE: wave_store_affine).
+ *     b may be NULL where the op takes no second operand, neg where it takes no sign. */
+enum { MZK_PROBE_MUL = 0, MZK_PROBE_SQR = 1, MZK_PROBE_MUL_ADD2 = 2, MZK_PROBE_SHOUP_MUL = 3, MZK_PROBE_SMUL = 4, MZK_PROBE_SMUL_C1 = 5,
+       MZK_PROBE_SADD = 6, MZK_PROBE_SSUB = 7, MZK_PROBE_SCARRY = 8, MZK_PROBE_SBIAS = 9, MZK_PROBE_SREDUCE = 10,
+       MZK_PROBE_ADD = 11, MZK_PROBE_SUB4 = 12, MZK_PROBE_SUB8 = 13, MZK_PROBE_NEG_LAZY4 = 14, MZK_PROBE_NEG_LAZY8 = 15,
+       MZK_PROBE_DBL = 16, MZK_PROBE_CARRY = 17, MZK_PROBE_WEAK_REDUCE = 18, MZK_PROBE_REDUCE = 19, MZK_PROBE_COND_SUB_P = 20,
+       MZK_PROBE_NEG_CANON = 21, MZK_PROBE_IS_ZERO_MOD6 = 22, MZK_PROBE_IS_ZERO_MOD10 = 23, MZK_PROBE_IS_ZERO_MOD12 = 24,
+       MZK_PROBE_INV = 25 };
+enum { MZK_PROBE_FORM_CPP = 0, MZK_PROBE_FORM_ASM = 1, MZK_PROBE_FORM_QUAD = 2, MZK_PROBE_FORM_ROW = 3, MZK_PROBE_FORM_WAVE = 4 };
+enum { MZK_PROBE_G1_MADD_SIGNED = 0, MZK_PROBE_G1_MADD = 1, MZK_PROBE_G1_ADD = 2, MZK_PROBE_G1_DBL = 3, MZK_PROBE_G1_DBL_AFFINE = 4,
+       MZK_PROBE_G1_TO_AFFINE = 5 };
+int mzk_selftest_field_probe(int field_id, int op, int form, size_t n, const uint32_t* in, uint32_t* out);
+int mzk_selftest_g1_probe(int op, int form, size_t n, const uint32_t* a, const uint32_t* b, const uint8_t* neg, uint32_t* out);
 
 /* Deterministic synthetic inputs (bench + tests): bit-identical to the oracle's orc_synth_*. */
 int mzk_synth_field_dev(int field_id, uint64_t seed, size_t n, void* d_out, void* stream);

@@ -1669,6 +1669,25 @@ int mzk_selftest_inv_wave(uint64_t seed, size_t n, uint64_t* mismatches) {
   WsGuard wsg(ctx().stream);
   return selftest_inv_wave_impl(seed, n, mismatches, ctx().stream);
 }
+int mzk_selftest_field_probe(int field_id, int op, int form, size_t n, const uint32_t* in, uint32_t* out) {
+  MZK_ENTER();
+  int limbs = 0;
+  if (selftest_field_probe_arity(field_id, op, form, &limbs) == 0) { set_error("field_probe: no field %d / op %d / form %d", field_id, op, form); return MZK_E_ARG; }
+  if (!in || !out || n > ((size_t)1 << 20)) { set_error("field_probe: null pointer or more than 2^20 cases"); return MZK_E_ARG; }
+  WsGuard wsg(ctx().stream);
+  return selftest_field_probe_impl(field_id, op, form, n, in, out, ctx().stream);
+}
+int mzk_selftest_g1_probe(int op, int form, size_t n, const uint32_t* a, const uint32_t* b, const uint8_t* neg, uint32_t* out) {
+  MZK_ENTER();
+  int aw = 0, bw = 0;
+  if (selftest_g1_probe_check(op, form, &aw, &bw) != MZK_OK) { set_error("g1_probe: no op %d / form %d", op, form); return MZK_E_ARG; }
+  if (!a || !out || (bw && !b) || (op == MZK_PROBE_G1_MADD_SIGNED && !neg) || n > ((size_t)1 << 20)) {
+    set_error("g1_probe: null pointer or more than 2^20 cases");
+    return MZK_E_ARG;
+  }
+  WsGuard wsg(ctx().stream);
+  return selftest_g1_probe_impl(op, form, n, a, b, neg, out, ctx().stream);
+}
 int mzk_synth_g1_points_dev(uint64_t seed, size_t n, void* d_out_xy, void* stream) {
   MZK_ENTER();
   WsGuard wsg((hipStream_t)stream);

@@ -262,6 +262,12 @@ int selftest_inv_wave_impl(uint64_t seed, size_t n, uint64_t* mismatches_host, h
 int selftest_row_ec_impl(uint64_t seed, size_t n, int dbl_reps, uint64_t* mismatches_host, hipStream_t s);
 int selftest_field_asm_impl(int fid, uint64_t seed, size_t n, uint64_t* mismatches_host, hipStream_t s);
 int selftest_copy_impl(const void* d_src, void* d_dst, size_t bytes, hipStream_t s);
+// the arithmetic probe (mzk_probe.hip): _arity / _check validate without launching (0 / MZK_E_ARG: no such field, op or form)
+int selftest_field_probe_arity(int fid, int op, int form, int* limbs);
+int selftest_field_probe_impl(int fid, int op, int form, size_t n, const uint32_t* in_host, uint32_t* out_host, hipStream_t s);
+int selftest_g1_probe_check(int op, int form, int* a_words, int* b_words);
+int selftest_g1_probe_impl(int op, int form, size_t n, const uint32_t* a_host, const uint32_t* b_host, const uint8_t* neg_host, uint32_t* out_host,
+                           hipStream_t s);
 int kzg_setup_g1_dev(const uint64_t* alpha_host, const uint64_t* g1_host, size_t first, size_t count, void* d_powers_xy, hipStream_t s);
 int kzg_open_dev(const void* d_coef, size_t n, const uint64_t* u_host, const void* d_points, int point_kind, size_t table_stride,
                  void* d_y, void* d_w_xy, void* d_q, hipStream_t s);

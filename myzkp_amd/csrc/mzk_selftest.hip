@@ -3,6 +3,7 @@
 // (tests/hostcheck) cannot reach them; this kernel feeds both forms the same operands -- random limbs, all-ones limbs,
 // zeros, and the widest lazy operands the callers produce (limbs up to 2^30.6 against normalised ones) -- and counts
 // the lanes whose results differ in any limb.  Called by tests/test_gpu_field_asm.py through mzk_selftest_field_asm.
+// A self-comparison: what pins both forms on integers is the arithmetic probe (mzk_probe.hip, tests/test_gpu_arith_probe.py).
 #include <type_traits>
 #include "mzk_common.h"
 #include "mzk_field_asm.h"
@@ -64,6 +65,18 @@ __global__ void k_selftest_field_asm(u64 seed, size_t n, unsigned long long* __r
     Fe<P> x = a;
     x.l[P::L - 1] &= 0x07ffffffu;            // value below 2^261: the quotient must fit its nine limbs
     bad += !st_same<P>(fe_shoup_mul<P>(x, w, wq), FeAsm<P>::shoup_mul(x, w, wq));
+  }
+  if constexpr (SparseMod<P>::value) {
+    // the signed product of the lazily accumulated butterflies: i32 limbs of either sign (kinds by case: full-range, the
+    // 3 (2^29 - 1) limbs a stage pair leaves, negated normalised limbs, mixed signs) against a normalised b
+    Fe<P> sa;
+    const int ks = (int)((i / 3) % 4);
+    for (int k = 0; k < P::L; k++) {
+      const u32 v = (u32)st_mix(s);
+      const i32 mag = ks == 0 ? (i32)(v & 0x7fffffffu) : ks == 1 ? (i32)(3u * MASK29) : (i32)(v & MASK29);
+      sa.l[k] = (u32)((ks == 2 || ((v >> 31) && ks != 1) || (ks == 1 && (i & 1))) ? -mag : mag);
+    }
+    bad += !st_same<P>(fe_mul_sparse<P, true, 0>(sa, b), FeAsm<P>::smul(sa, b));
   }
   if (bad) atomicAdd(mismatches, (unsigned long long)bad);
 }

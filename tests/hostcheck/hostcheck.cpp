@@ -7,7 +7,30 @@
 #include "../../myzkp_amd/csrc/mzk_ec.h"
 #include "../../myzkp_amd/csrc/mzk_g2.h"
 #include "../../myzkp_amd/csrc/mzk_glv.h"
+#include "../../myzkp_amd/csrc/mzk_probe.h"
 using namespace mzk;
+
+// The arithmetic probe on the host: the portable per-lane forms of mzk_probe.h (the text the device kernels of mzk_probe.hip
+// compile), raw limbs in, raw limbs out, every bounds assertion of the headers armed.
+template <class P, int OP = 0> static int run_field_probe(int op, size_t n, const u32* in, u32* out) {
+  if constexpr (OP == PR_FIELD_OPS) {
+    return -1;
+  } else {
+    if (op != OP) return run_field_probe<P, OP + 1>(op, n, in, out);
+    if constexpr (!probe_field_has<P>(OP)) {
+      return -1;
+    } else {
+      constexpr int AR = probe_field_arity(OP);
+      for (size_t i = 0; i < n; i++) probe_field_cpp<P, OP>(in + i * AR * P::L, out + i * P::L);
+      return 0;
+    }
+  }
+}
+template <int OP> static void run_g1_probe(size_t n, const u32* a, const u32* b, const uint8_t* neg, u32* out) {
+  constexpr int AW = OP == PR_G1_DBL_AFFINE ? PR_AFF : PR_SLOT;
+  constexpr int BW = OP == PR_G1_ADD ? PR_SLOT : (OP == PR_G1_MADD || OP == PR_G1_MADD_SIGNED) ? PR_AFF : 0;
+  for (size_t i = 0; i < n; i++) probe_g1_lane<OP, FeCpp>(a + i * AW, BW ? b + i * BW : nullptr, OP == PR_G1_MADD_SIGNED && neg[i] != 0, out + i * PR_SLOT);
+}
 
 template <class P> static void run_field(int op, const u32* a, const u32* b, u32* out) {
   Fe<P> x = fe_to_mont<P>(fe_unpack<P>(a));
@@ -141,6 +164,24 @@ int hc_field_op(int fid, int op, const u32* a, const u32* b, u32* out) {
   else if (fid == 2) run_field<FqParams>(op, a, b, out);
   else return -1;
   return 0;
+}
+// mzk_selftest_field_probe / mzk_selftest_g1_probe of include/mzk.h, portable form, on the host (same op codes, same layouts)
+int hc_field_probe(int fid, int op, size_t n, const u32* in, u32* out) {
+  if (fid == 0) return run_field_probe<FrParams>(op, n, in, out);
+  if (fid == 1) return run_field_probe<M128Params>(op, n, in, out);
+  if (fid == 2) return run_field_probe<FqParams>(op, n, in, out);
+  return -1;
+}
+int hc_g1_probe(int op, size_t n, const u32* a, const u32* b, const uint8_t* neg, u32* out) {
+  switch (op) {
+    case PR_G1_MADD_SIGNED: run_g1_probe<PR_G1_MADD_SIGNED>(n, a, b, neg, out); return 0;
+    case PR_G1_MADD: run_g1_probe<PR_G1_MADD>(n, a, b, neg, out); return 0;
+    case PR_G1_ADD: run_g1_probe<PR_G1_ADD>(n, a, b, neg, out); return 0;
+    case PR_G1_DBL: run_g1_probe<PR_G1_DBL>(n, a, b, neg, out); return 0;
+    case PR_G1_DBL_AFFINE: run_g1_probe<PR_G1_DBL_AFFINE>(n, a, b, neg, out); return 0;
+    case PR_G1_TO_AFFINE: run_g1_probe<PR_G1_TO_AFFINE>(n, a, b, neg, out); return 0;
+  }
+  return -1;
 }
 // one in-tile transform of 2^lgn points by the kernels' stage schedule (bounds asserted along the way)
 int hc_ntt_tile(int fid, const u32* words, int lgn, const u32* tw_words, u32* out) {

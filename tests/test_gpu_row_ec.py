@@ -1,6 +1,10 @@
 """Row-cooperative group operations (myzkp_amd/csrc/mzk_row.h: one XYZZ addition / doubling per wave, field elements spread over
 DPP rows) against the plain exception-complete formulas of mzk_ec.h, which the host build pins on the oracle's affine group law
-(curve.rs:44-161; tests/test_hostcheck_arith.py).  Pairs cover independent points, P + P, P + (-P) and infinity on either side;
+(curve.rs:44-161; tests/test_hostcheck_arith.py).  Both sides of this comparison run on the device and only a count comes back;
+what pins the "plain" side -- and the row, quad and wave forms themselves -- ON THE DEVICE is tests/test_gpu_arith_probe.py
+(mzk_selftest_g1_probe: raw slots from the host, the result judged against the affine law in Python integers, with the accumulator
+representations chosen so that every multiple of p the zero tests can meet occurs).  This file stays as the volume run.
+Pairs cover independent points, P + P, P + (-P) and infinity on either side;
 the MSM parity tests then exercise the same code inside the bucket-reduction tails, the window Horner and the partial fold.
 The integer model of the row product's column / carry bounds is tests/test_row_product_model.py (CPU)."""
 import ctypes
