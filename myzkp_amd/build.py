@@ -3,8 +3,8 @@
     python -m myzkp_amd.build [--force] [--tuning]
 
 hipcc cross-compiles without a GPU; the .so is git-ignored but travels to the GPU box with gpurun.
---tuning builds myzkp_amd/libmzk_hip_tuning.so instead (-DMZK_TUNING): the A/B switches of tools/timing (MZK_* environment
-variables) and the superseded kernels only they can reach exist there and nowhere else; load it with MZK_HIP_LIB=<that file>."""
+--tuning builds myzkp_amd/libmzk_hip_tuning.so instead (-DMZK_TUNING): the re-tuning parameters and forced choices that tools/timing
+sets (MZK_* environment variables) are read there and nowhere else; load it with MZK_HIP_LIB=<that file>."""
 import os, subprocess, sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -13,7 +13,6 @@ CSRC = os.path.join(HERE, "csrc")
 OUT = os.path.join(HERE, "libmzk_hip.so")
 OUT_TUNING = os.path.join(HERE, "libmzk_hip_tuning.so")
 SOURCES = ["mzk_api.hip", "mzk_multi.hip", "mzk_io.hip", "mzk_poly.hip", "mzk_ntt.hip", "mzk_msm.hip", "mzk_msm_row.hip", "mzk_kzg.hip", "mzk_gemini.hip", "mzk_mpoly.hip", "mzk_stark.hip", "mzk_merkle.hip", "mzk_g2.hip", "mzk_selftest.hip", "mzk_probe.hip"]
-TUNING_ONLY_SOURCES = ["mzk_msm_tail.hip"]      # the DPP-quad tails of round 2 (MZK_ROW_TAILS=0)
 import glob
 # every header of csrc/ plus the ABI header: a hand-kept list went stale once (mzk_glv.h)
 HEADERS = sorted(glob.glob(os.path.join(CSRC, "*.h"))) + [os.path.join(ROOT, "include", "mzk.h")]
@@ -44,7 +43,7 @@ def build(force=False, verbose=False, tuning=False):
     out = OUT_TUNING if tuning else OUT
     flags = FLAGS + (["-DMZK_TUNING"] if tuning else [])
     objs, procs = [], []
-    for s in SOURCES + (TUNING_ONLY_SOURCES if tuning else []):
+    for s in SOURCES:
         src = os.path.join(CSRC, s)
         if not os.path.exists(src):
             continue

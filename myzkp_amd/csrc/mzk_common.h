@@ -16,10 +16,9 @@
 namespace mzk {
 
 // ---- tuning switches --------------------------------------------------------------------------------
-// The SHIPPED library reads no environment variable: a caller's environment must not be able to change the code path.  The
-// A/B switches of tools/timing and tools/gpu_jobs exist only in the tuning build (python -m myzkp_amd.build --tuning ->
-// myzkp_amd/libmzk_hip_tuning.so, compiled with -DMZK_TUNING, loaded through MZK_HIP_LIB); there tune_int reads MZK_<NAME>, here it
-// is the constant default, and the kernels only a non-default switch can reach are not compiled at all.
+// The SHIPPED library reads no environment variable: a caller's environment must not be able to change the code path.  The switches of
+// tools/timing exist only in the tuning build (python -m myzkp_amd.build --tuning -> myzkp_amd/libmzk_hip_tuning.so, compiled with
+// -DMZK_TUNING, loaded through MZK_HIP_LIB); there tune_int reads MZK_<NAME>, here it is the constant default.
 #ifdef MZK_TUNING
 #include <stdlib.h>
 static inline int tune_int(const char* name, int dflt) { const char* v = getenv(name); return v ? atoi(v) : dflt; } static inline const char* tune_str(const char* name) { return getenv(name); }
@@ -215,7 +214,7 @@ int kzg_batch_open_dev(const void* d_coef, size_t n, const uint64_t* us_host, si
 // floor of a small generic MSM), so they get narrow windows: 8 bits = 32 tables x 128 buckets up to 1024 points, 10 bits =
 // 26 tables x 512 buckets up to 2^14 (where the sortless path still beats the general pipeline: profiles/r03v_*), then 16 and,
 // from 2^19 points on, 17 bits, from 2^22 on 20 bits through the general pipeline (tools/timing/window_sweep.py).
-// Round 4 (tools/gpu_jobs/r04_window_sweep.sh, profiles/round4_window_sweep.txt; one box, c = 16 / 17 / 20 / 22):
+// Round 4 (profiles/round4_window_sweep.txt, tools/timing/window_sweep.py; one box, c = 16 / 17 / 20 / 22):
 //   2^22   6.09 /  5.75 /  5.62 / 12.97      2^23  11.97 / 11.27 / 10.89 / 20.26      2^24  23.56 / 22.05 / 20.89 / 30.18
 // 20 bits (13 tables, 2^19 buckets) win from 2^22 points on: two accumulations fewer per pair outweigh the wider sort and the
 // longer reduction; 22 bits (12 tables) lose everything to the sort (2^21 buckets: 8192 per coarse bin, past the staged fine

@@ -84,8 +84,7 @@ __device__ __forceinline__ void xyzz_gstore_quad(u32* __restrict__ g, size_t idx
   p4[1] = make_uint4(w[4], w[5], w[6], w[7]);
 }
 
-// p replicated in the quad -> 2p replicated (dbl-2008-s-1; same schedule as the wave-wide variant in
-// mzk_msm_tail.hip).  Infinity in -> infinity out via the final select.
+// p replicated in the quad -> 2p replicated (dbl-2008-s-1).  Infinity in -> infinity out via the final select.
 __device__ __forceinline__ Xyzz xyzz_dbl_quad(const Xyzz& p, int lane) {
   typedef FqParams P;
   const bool was_inf = xyzz_is_inf(p);

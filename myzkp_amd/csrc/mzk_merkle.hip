@@ -22,7 +22,7 @@ template <int R> __device__ __forceinline__ u64 rotl64(u64 x) {
   if constexpr (R == 0) return x;
   else return (x << R) | (x >> (64 - R));
 }
-__constant__ u64 KECCAK_RC[32] = {      // 24 round constants (+ 8 pad words: keccak_f_pair fetches one round ahead)
+__constant__ u64 KECCAK_RC[24] = {
     0x0000000000000001ULL, 0x0000000000008082ULL, 0x800000000000808aULL, 0x8000000080008000ULL, 0x000000000000808bULL,
     0x0000000080000001ULL, 0x8000000080008081ULL, 0x8000000000008009ULL, 0x000000000000008aULL, 0x0000000000000088ULL,
     0x0000000080008009ULL, 0x000000008000000aULL, 0x000000008000808bULL, 0x800000000000008bULL, 0x8000000000008089ULL,
@@ -90,42 +90,16 @@ __device__ __forceinline__ void keccak_f(u64 (&st)[25]) {
 // a rotation needs the partner's half of the same word: one quad_perm DPP move + one v_alignbit_b32, the same formula
 // on both lanes.  ~125 instructions per round and lane instead of 190 (1.3 x the total work: only used where the level
 // is latency-bound).  Both lanes of a pair must be active (a DPP read of a disabled lane returns 0).
-__device__ __forceinline__ u32 pair_swap(u32 v) {
-  u32 r = (u32)__builtin_amdgcn_update_dpp(0, (int)v, 0xB1, 0xF, 0xF, true);     // quad_perm [1,0,3,2]
-  asm("" : "+v"(r));       // opaque to the DPP-combine pass (see mzk_coop.h)
-  return r;
-}
-template <int R> __device__ __forceinline__ u32 pair_rot(u32 mine) {
-  if constexpr (R == 0) return mine;
-  else {
-    const u32 other = pair_swap(mine);
-    if constexpr (R == 32) return other;
-    else if constexpr (R < 32) return __builtin_amdgcn_alignbit(mine, other, 32 - R);
-    else return __builtin_amdgcn_alignbit(other, mine, 64 - R);
-  }
-}
-__device__ __forceinline__ u32 x3(u32 a, u32 b, u32 c) { return (u32)__builtin_amdgcn_bitop3_b32((int)a, (int)b, (int)c, 0x96); }
-__device__ __forceinline__ u32 chi32(u32 a, u32 b, u32 c) { return a ^ (~b & c); }
-#ifndef MZK_KECCAK_PAIR_ASM
-#define MZK_KECCAK_PAIR_ASM 1       // 0: the compiler-scheduled round below (A/B builds)
-#endif
 __device__ __forceinline__ void keccak_f_pair(u32 (&a)[25], int parity) {
-#if MZK_KECCAK_PAIR_ASM
   // One scheduled asm block per round (mzk_keccak_asm.h, generated): hipcc emitted the round word by word -- xor, s_nop 1,
   // v_mov_b32_dpp, s_nop 0, v_alignbit: 49 wait-state instructions per round, 7.6 cycles per instruction on the lone wave of a
   // tree's upper levels; batched (all xors, all lane exchanges, all funnel shifts) every hazard distance is covered by independent work.
-  // the round constant of round r + 1 is fetched while round r runs: loaded at the top of the round it belongs to, the scalar load and
-  // its wait (~100 cycles on the lone wave of a tree's upper levels, a fifth of the round) sat in front of every round
   // Where the round constant comes from (same-box A/B, profiles/round6_keccak_round_constant_ab.txt; FRI round at 2^14 / Merkle commit of 2^16 leaves):
-  //   0  `KECCAK_RC[rnd]` inside its round: s_getpc + address arithmetic + s_load_dwordx2 + s_waitcnt in front of EVERY round of the lone wave
+  //   `KECCAK_RC[rnd]` inside its round: s_getpc + address arithmetic + s_load_dwordx2 + s_waitcnt in front of EVERY round of the lone wave
   //      of a tree's upper levels -- a fifth of the round                                                             114 - 116 us / 0.153 ms
-  //   1  the constant of round r + 1 fetched while round r runs (the wait finds it there)                           106 - 108 us / 0.147 ms
-  //   2  all 24 rounds unrolled, the constants literals of the instruction stream (49 KB of code in k_merkle_tail)  104 - 105 us / 0.139 ms
-#ifndef MZK_KECCAK_RC_AHEAD
-#define MZK_KECCAK_RC_AHEAD 2
-#endif
-#if MZK_KECCAK_RC_AHEAD == 2
-  // all 24 rounds unrolled, the constants literals of the instruction stream: no scalar load, no address arithmetic per round
+  //   the constant of round r + 1 fetched while round r runs (the wait finds it there)                              106 - 108 us / 0.147 ms
+  //   all 24 rounds unrolled, the constants literals of the instruction stream (49 KB of code in k_merkle_tail)     104 - 105 us / 0.139 ms
+  // The last is the form here: no scalar load, no address arithmetic per round.
   constexpr u64 K[24] = {
       0x0000000000000001ULL, 0x0000000000008082ULL, 0x800000000000808aULL, 0x8000000080008000ULL, 0x000000000000808bULL, 0x0000000080000001ULL,
       0x8000000080008081ULL, 0x8000000000008009ULL, 0x000000000000008aULL, 0x0000000000000088ULL, 0x0000000080008009ULL, 0x000000008000000aULL,
@@ -133,44 +107,6 @@ __device__ __forceinline__ void keccak_f_pair(u32 (&a)[25], int parity) {
       0x000000000000800aULL, 0x800000008000000aULL, 0x8000000080008081ULL, 0x8000000000008080ULL, 0x0000000080000001ULL, 0x8000000080008008ULL};
 #pragma unroll
   for (int rnd = 0; rnd < 24; rnd++) keccak_round_pair_asm(a, parity ? (u32)(K[rnd] >> 32) : (u32)K[rnd]);
-#elif MZK_KECCAK_RC_AHEAD
-  u64 rc = KECCAK_RC[0];
-#pragma unroll 1
-  for (int rnd = 0; rnd < 24; rnd++) {
-    const u64 nxt = KECCAK_RC[(rnd + 1) & 31];          // (the table has 32 entries: the last fetch reads a pad word)
-    keccak_round_pair_asm(a, parity ? (u32)(rc >> 32) : (u32)rc);
-    rc = nxt;
-  }
-#else
-#pragma unroll 1
-  for (int rnd = 0; rnd < 24; rnd++) {
-    const u64 rc = KECCAK_RC[rnd];
-    keccak_round_pair_asm(a, parity ? (u32)(rc >> 32) : (u32)rc);
-  }
-#endif
-  return;
-#endif
-#pragma unroll 1
-  for (int rnd = 0; rnd < 24; rnd++) {
-    const u32 c0 = x3(x3(a[0], a[5], a[10]), a[15], a[20]);
-    const u32 c1 = x3(x3(a[1], a[6], a[11]), a[16], a[21]);
-    const u32 c2 = x3(x3(a[2], a[7], a[12]), a[17], a[22]);
-    const u32 c3 = x3(x3(a[3], a[8], a[13]), a[18], a[23]);
-    const u32 c4 = x3(x3(a[4], a[9], a[14]), a[19], a[24]);
-    const u32 d0 = c4 ^ pair_rot<1>(c1), d1 = c0 ^ pair_rot<1>(c2), d2 = c1 ^ pair_rot<1>(c3), d3 = c2 ^ pair_rot<1>(c4), d4 = c3 ^ pair_rot<1>(c0);
-    const u32 b0 = pair_rot<0>(a[0] ^ d0), b16 = pair_rot<36>(a[5] ^ d0), b7 = pair_rot<3>(a[10] ^ d0), b23 = pair_rot<41>(a[15] ^ d0), b14 = pair_rot<18>(a[20] ^ d0);
-    const u32 b10 = pair_rot<1>(a[1] ^ d1), b1 = pair_rot<44>(a[6] ^ d1), b17 = pair_rot<10>(a[11] ^ d1), b8 = pair_rot<45>(a[16] ^ d1), b24 = pair_rot<2>(a[21] ^ d1);
-    const u32 b20 = pair_rot<62>(a[2] ^ d2), b11 = pair_rot<6>(a[7] ^ d2), b2 = pair_rot<43>(a[12] ^ d2), b18 = pair_rot<15>(a[17] ^ d2), b9 = pair_rot<61>(a[22] ^ d2);
-    const u32 b5 = pair_rot<28>(a[3] ^ d3), b21 = pair_rot<55>(a[8] ^ d3), b12 = pair_rot<25>(a[13] ^ d3), b3 = pair_rot<21>(a[18] ^ d3), b19 = pair_rot<56>(a[23] ^ d3);
-    const u32 b15 = pair_rot<27>(a[4] ^ d4), b6 = pair_rot<20>(a[9] ^ d4), b22 = pair_rot<39>(a[14] ^ d4), b13 = pair_rot<8>(a[19] ^ d4), b4 = pair_rot<14>(a[24] ^ d4);
-    a[0] = chi32(b0, b1, b2); a[1] = chi32(b1, b2, b3); a[2] = chi32(b2, b3, b4); a[3] = chi32(b3, b4, b0); a[4] = chi32(b4, b0, b1);
-    a[5] = chi32(b5, b6, b7); a[6] = chi32(b6, b7, b8); a[7] = chi32(b7, b8, b9); a[8] = chi32(b8, b9, b5); a[9] = chi32(b9, b5, b6);
-    a[10] = chi32(b10, b11, b12); a[11] = chi32(b11, b12, b13); a[12] = chi32(b12, b13, b14); a[13] = chi32(b13, b14, b10); a[14] = chi32(b14, b10, b11);
-    a[15] = chi32(b15, b16, b17); a[16] = chi32(b16, b17, b18); a[17] = chi32(b17, b18, b19); a[18] = chi32(b18, b19, b15); a[19] = chi32(b19, b15, b16);
-    a[20] = chi32(b20, b21, b22); a[21] = chi32(b21, b22, b23); a[22] = chi32(b22, b23, b24); a[23] = chi32(b23, b24, b20); a[24] = chi32(b24, b20, b21);
-    const u64 rc = KECCAK_RC[rnd];
-    a[0] ^= parity ? (u32)(rc >> 32) : (u32)rc;
-  }
 }
 // hash of two child digests by a lane pair: lane `parity` reads and writes its halves of the 64-bit words
 __device__ __forceinline__ void sha3_of_two_digests_pair(const u64* __restrict__ children, u64* __restrict__ out, int parity) {

@@ -16,8 +16,8 @@
 //   3. k_digits_scatter[_lds] counting-sort placement of (point reference, sign), no atomics
 //   4. k_seg_accumulate    one lane per fixed-size segment of the sorted entries, XYZZ += affine
 //                          (madd-2008-s), exception-complete; k_seg_combine sums a bucket's partials
-//   5. k_halve_step / k_reduce_tail   sum_b (b+1) B_b per bucket set by in-place halving
-//   6. k_window_combine (mzk_msm_tail.hip)  Horner over the bucket sets, XYZZ -> affine (one inversion)
+//   5. k_halve_step* / k_halve_multi / k_reduce_tail_row   sum_b (b+1) B_b per bucket set by in-place halving
+//   6. k_window_combine_row (mzk_msm_row.hip)  Horner over the bucket sets, XYZZ -> affine (one inversion)
 #include <stdlib.h>
 #include <type_traits>
 #include "mzk_common.h"
@@ -36,7 +36,7 @@ static const MsmKnobs& msm_knobs() {
     return MsmKnobs{tune_int("MZK_GLV_C", d.glv_c), tune_int("MZK_SMALL_SCAN", d.small_scan), tune_int("MZK_SCAN_MAX_LOG", d.scan_max_log),
                     tune_int("MZK_ACC_PREFETCH", d.acc_prefetch), tune_int("MZK_ACC_SEG", d.acc_seg), tune_int("MZK_COARSE_LOG_20", d.coarse_log_20),
                     tune_int("MZK_COARSE_LOG_17", d.coarse_log_17), tune_int("MZK_PER_FINE", d.per_fine), tune_int("MZK_SORT_SCAN_FREE", d.sort_scan_free),
-                    tune_int("MZK_COARSE_STAGED", d.coarse_staged), tune_int("MZK_COMBINE_WIDE_MIN_LOG", d.combine_wide_min_log)};
+                    tune_int("MZK_COMBINE_WIDE_MIN_LOG", d.combine_wide_min_log)};
   }();
   return k;
 }
@@ -1052,46 +1052,24 @@ __global__ __launch_bounds__(128) void k_seg_combine_wide(const u32* __restrict_
   }
   xyzz_gstore(buckets, b, acc);
 }
-// the same point held by the lane `dist` lanes away (every lane of a quad holds its quad's whole point)
-__device__ __forceinline__ Xyzz xyzz_from_lane_xor(const Xyzz& p, int dist) {
-  Xyzz r;
-#pragma unroll
-  for (int i = 0; i < FqParams::L; i++) {
-    r.X.l[i] = (u32)__shfl_xor((int)p.X.l[i], dist, 64); r.Y.l[i] = (u32)__shfl_xor((int)p.Y.l[i], dist, 64);
-    r.ZZ.l[i] = (u32)__shfl_xor((int)p.ZZ.l[i], dist, 64); r.ZZZ.l[i] = (u32)__shfl_xor((int)p.ZZZ.l[i], dist, 64);
-  }
-  return r;
-}
-// One DPP quad per bucket (QPB = 1: the shipped form).  A bucket's partials form a serial chain of additions, so the quad-cooperative
-// addition cuts the kernel's latency (the quad also splits the 128-byte records).  QPB = 2 / 4 -- adjacent quads take every QPB-th
-// partial each and fold their sums through shuffles, chain of 9 -> 5 + 1 / 3 + 2 in a grid-batched pass of 64 x 2^12 coefficients --
-// exist in the tuning build only: measured slower everywhere (see msm_many_dev_impl), the kernel is bound by its instruction count.
-template <int QPB>
+// One DPP quad per bucket.  A bucket's partials form a serial chain of additions, so the quad-cooperative addition cuts the kernel's
+// latency (the quad also splits the 128-byte records).  Two / four adjacent quads per bucket, each taking every 2nd / 4th partial and
+// folding their sums through shuffles, were measured slower everywhere (see msm_many_dev_impl): the kernel is bound by its instruction count.
 __global__ __launch_bounds__(128) void k_seg_combine(const u32* __restrict__ slots, const u32* __restrict__ offsets, u32* __restrict__ buckets,
                                                       size_t nbuckets, u32 seg_host, u32* __restrict__ heavy, const u32* __restrict__ tails, int lg_nb, u32 t_max) {
   const size_t tid = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const size_t b = tid / (4 * QPB);
-  const int lane = (int)(tid & 3), q = (int)((tid >> 2) % QPB);
-  if (b >= nbuckets) return;                         // (a bucket's QPB quads are adjacent lanes of one wave: uniform for the shuffles below)
+  const size_t b = tid / 4;
+  const int lane = (int)(tid & 3);
+  if (b >= nbuckets) return;
   const u32 seg = segment_length(seg_host, t_max, offsets[nbuckets]);
   if (tid == 0) heavy[1] = seg;                      // k_seg_combine_heavy reads it there
   const u32 o0 = offsets[b], o1 = bucket_end(offsets, tails, lg_nb, b);
   Xyzz acc = xyzz_inf();
   if (o1 > o0) {
     const size_t s0 = (size_t)(o0 / seg) + b, s1 = (size_t)((o1 - 1) / seg) + b;
-    if (defer_heavy(b, s0, s1, o1, heavy, lane == 0 && q == 0, tails ? HEAVY_SLOTS_SORT1 : HEAVY_SLOTS)) return;       // uniform over the bucket's quads
-    if (QPB == 1) {
-      acc = xyzz_gload_raw_quad(slots, s0, lane);
-      for (size_t sl = s0 + 1; sl <= s1; sl++) acc = xyzz_add_quad(acc, xyzz_gload_raw_quad(slots, sl, lane), lane);
-    } else {
-      for (size_t sl = s0 + q; sl <= s1; sl += QPB) acc = xyzz_add_quad(acc, xyzz_gload_raw_quad(slots, sl, lane), lane);
-    }
-  }
-  if (QPB > 1) {
-    // (all lanes of the bucket's quads are here, empty buckets included: the shuffles see active partners)
-    acc = xyzz_add_quad(acc, xyzz_from_lane_xor(acc, 4), lane);
-    if (QPB > 2) acc = xyzz_add_quad(acc, xyzz_from_lane_xor(acc, 8), lane);
-    if (q != 0) return;
+    if (defer_heavy(b, s0, s1, o1, heavy, lane == 0, tails ? HEAVY_SLOTS_SORT1 : HEAVY_SLOTS)) return;       // uniform over the bucket's quad
+    acc = xyzz_gload_raw_quad(slots, s0, lane);
+    for (size_t sl = s0 + 1; sl <= s1; sl++) acc = xyzz_add_quad(acc, xyzz_gload_raw_quad(slots, sl, lane), lane);
   }
   xyzz_gstore_quad(buckets, b, acc, lane);
 }
@@ -1246,53 +1224,6 @@ __global__ __launch_bounds__(HMULTI_THREADS) void k_halve_multi(u32* __restrict_
     g4[(base + ((size_t)k << lgs)) * 8 + (i & 7)] = l4[k * 8 + (i & 7)];
   }
 }
-#ifdef MZK_TUNING      // the DPP-quad tail of round 2: reachable only through MZK_ROW_TAILS=0 (A/B timing), not in the shipped library
-constexpr int TAIL_THREADS = 512;
-constexpr int TAIL_QUADS = TAIL_THREADS / 4;
-// Remaining steps t_start..lgB-1 inside one workgroup per bucket set, then the weighted sum
-// buf[0] + sum_j 2^j buf[2^j] (quad j doubles j times, LDS tree sum).  out[w] = XYZZ result of set w.
-// finish_affine (single bucket set only): convert the sum to the canonical affine point here (one safegcd inversion on
-// lane 0) instead of handing a 128-byte record to k_window_combine -- one dependent launch less on the merged path.
-__global__ __launch_bounds__(TAIL_THREADS) void k_reduce_tail(u32* __restrict__ buckets, int lgB, int t_start, u32* __restrict__ out, int finish_affine) {
-  __shared__ __attribute__((aligned(16))) u32 sh[32 * 32];
-  u32* buf = buckets + ((size_t)blockIdx.x << lgB) * 32;
-  const int lane = threadIdx.x & 3, quad = threadIdx.x >> 2;
-  for (int t = t_start; t < lgB; t++) {
-    const size_t total = (size_t)(t + 1) << (lgB - t - 1);
-    for (size_t id = quad; id < total; id += TAIL_QUADS) halve_op(buf, lgB, t, id, lane);
-    __syncthreads();
-  }
-  if (quad < 32) {
-    Xyzz v = xyzz_inf();
-    if (quad < lgB) {
-      v = xyzz_gload_quad(buf, (size_t)1 << quad, lane);
-      for (int d = 0; d < quad; d++) v = xyzz_dbl_quad(v, lane);
-    } else if (quad == lgB) {
-      v = xyzz_gload_quad(buf, 0, lane);
-    }
-    xyzz_gstore_quad(sh, quad, v, lane);
-  }
-  __syncthreads();
-  for (int off = 16; off >= 1; off >>= 1) {
-    if (quad < off) {
-      const Xyzz a = xyzz_gload_quad(sh, quad, lane), b = xyzz_gload_quad(sh, quad + off, lane);
-      xyzz_gstore_quad(sh, quad, xyzz_add_quad(a, b, lane), lane);
-    }
-    __syncthreads();
-  }
-  if (finish_affine) {
-    if (threadIdx.x == 0) {
-      u32 wds[16];
-      Affine af;
-      if (xyzz_to_affine<true>(xyzz_load(sh), &af)) affine_store_plain(af, wds);
-      else for (int i = 0; i < 16; i++) wds[i] = 0;
-      for (int i = 0; i < 16; i++) out[i] = wds[i];
-    }
-    return;
-  }
-  if (threadIdx.x < 32) out[(size_t)blockIdx.x * 32 + threadIdx.x] = sh[threadIdx.x];
-}
-#endif
 
 // ---- small inputs (n < 4096): three launches instead of twenty-five ---------------------------------------------
 // The reference's real callers commit to polynomials of at most a few thousand coefficients (das/avail.rs:96,
@@ -1301,7 +1232,7 @@ __global__ __launch_bounds__(TAIL_THREADS) void k_reduce_tail(u32* __restrict__ 
 //   k_small_sort        ONE workgroup: digits -> LDS histogram -> scan -> LDS cursors -> sorted entries (global)
 //   k_small_accumulate  one WAVE per bucket: lanes stride over the bucket's entries (madd), then the 64 partials are
 //                       summed by a quad-cooperative tree through LDS (seven rounds of ~2 us instead of a serial chain)
-//   k_reduce_tail       all halving steps of a bucket set inside one workgroup (t_start = 0), then k_window_combine.
+//   k_reduce_tail_row   all halving steps of a bucket set inside one workgroup (t_start = 0), then k_window_combine_row.
 constexpr int SMALL_SORT_THREADS = 1024;
 __global__ __launch_bounds__(SMALL_SORT_THREADS) void k_small_sort(const u32* __restrict__ scalars, size_t n, DigitLayout L, int NB,
                                                                     u32* __restrict__ offsets, u32* __restrict__ entries) {
@@ -1454,24 +1385,10 @@ __global__ __launch_bounds__(T) void k_small_accumulate_scan(const u32* __restri
 }
 static_assert(254 / 8 + 1 <= 32, "window hit masks are 32 bits");
 
-#ifdef MZK_TUNING
-// k_window_combine / k_fold_partials (DPP-quad forms, round 2) live in mzk_msm_tail.hip: tuning build only
-int launch_window_combine(const u32* wsum, int nwin, int c, int out_xyzz, u32* out, hipStream_t s);
-int launch_fold_partials(const u32* partials, int count, u32* out, hipStream_t s);
-#endif
-// mzk_msm_row.hip: the same tails on row-cooperative group operations (one point operation per wave)
+// mzk_msm_row.hip: the tails on row-cooperative group operations (one point operation per wave)
 int launch_reduce_tail_row(u32* buckets, int lgB, int t_start, int sets, u32* out, int finish_affine, hipStream_t s);
 int launch_window_combine_row(const u32* wsum, int nwin, int c, int out_xyzz, u32* out, hipStream_t s);
 int launch_fold_partials_row(const u32* partials, int count, u32* out, hipStream_t s);
-// tuning build: MZK_ROW_TAILS=0 selects the DPP-quad tails of round 2 (A/B timing: tools/timing/small_latency.py, time_msm.py)
-#ifdef MZK_TUNING
-static bool row_tails() {
-  static const int v = tune_int("MZK_ROW_TAILS", 1);
-  return v != 0;
-}
-#else
-static constexpr bool row_tails() { return true; }
-#endif
 // The single-workgroup tail takes over once a halving step is at most this wide: a dependent launch costs ~6 us whatever runs in
 // it (measured: a step of 1024 additions as one wave each 6.0 us, as DPP quads 6.4 us -- the launch, not the addition), a round
 // of 256 quad additions inside the tail's workgroup 3.6 us, a round of 16 row additions ~1.8 us.
@@ -1483,9 +1400,7 @@ static size_t row_tail_max_ops() {
 // The halving steps that run as launches of their own, in front of the single-workgroup tail: one lane per addition while a step is
 // throughput-bound (>= 2^16 additions over all sets), then k_halve_multi, up to eight steps per launch, until a step is at most
 // `tail_max` additions wide.  *t_next = the first step left to the tail (lgB: all done, the tail only forms the weighted sum).
-// MZK_HALVE_MULTI=0 (tuning build): one launch per step, the form of rounds 2-5.
 static int launch_halving_steps(u32* buckets, int lgB, int sets, size_t tail_max, int* t_next, hipStream_t s) {
-  static const int env_multi = tune_int("MZK_HALVE_MULTI", 1);
   int t = 0;
   while (t < lgB && ((size_t)(t + 1) << (lgB - t - 1)) > tail_max) {
     const size_t total = (size_t)(t + 1) << (lgB - t - 1);
@@ -1500,7 +1415,7 @@ static int launch_halving_steps(u32* buckets, int lgB, int sets, size_t tail_max
     // 256 x 2^10 at 11 bits 0.196 -> 0.270; profiles/round6_halving_multi_and_rec4_ab.txt)
     const int st = (lgB - t < HMULTI_MAX_S) ? lgB - t : HMULTI_MAX_S;
     const size_t multi_wgs = ((size_t)(t + 1) << (lgB - t - st)) * (size_t)sets;
-    if (env_multi == 0 || multi_wgs > (size_t)ctx().num_cu) {
+    if (multi_wgs > (size_t)ctx().num_cu) {
       hipLaunchKernelGGL(k_halve_step, dim3((unsigned)((4 * total + 127) / 128), (unsigned)sets), dim3(128), 0, s, buckets, lgB, t);
       t++;
     } else {
@@ -1518,37 +1433,18 @@ static int launch_halving_steps(u32* buckets, int lgB, int sets, size_t tail_max
 // tail writes the result itself (affine point, or the XYZZ partial record).
 static int reduce_bucket_sets(u32* buckets, int lgB, int sets, bool merged, int horner_c, u32* wsum, u32* d_out, bool out_partial_xyzz, hipStream_t s) {
   prof_begin(s, MZK_PH_MSM_REDUCE);
-  const bool rows = row_tails();
-  (void)rows;
   int t_start = 0;
-#ifdef MZK_TUNING
-  const size_t tail_max = rows ? row_tail_max_ops() : (size_t)4 * TAIL_QUADS;
-#else
-  const size_t tail_max = row_tail_max_ops();
-#endif
-  MZK_TRY(launch_halving_steps(buckets, lgB, sets, tail_max, &t_start, s));
+  MZK_TRY(launch_halving_steps(buckets, lgB, sets, row_tail_max_ops(), &t_start, s));
   if (merged) {
-#ifdef MZK_TUNING
-    if (!rows) hipLaunchKernelGGL(k_reduce_tail, dim3(1), dim3(TAIL_THREADS), 0, s, buckets, lgB, t_start, d_out, out_partial_xyzz ? 0 : 1);
-    else
-#endif
     MZK_TRY(launch_reduce_tail_row(buckets, lgB, t_start, 1, d_out, out_partial_xyzz ? 0 : 1, s));
     MZK_HIP(hipGetLastError());
     prof_end(s, MZK_PH_MSM_REDUCE);
     return MZK_OK;
   }
-#ifdef MZK_TUNING
-  if (!rows) hipLaunchKernelGGL(k_reduce_tail, dim3((unsigned)sets), dim3(TAIL_THREADS), 0, s, buckets, lgB, t_start, wsum, 0);
-  else
-#endif
   MZK_TRY(launch_reduce_tail_row(buckets, lgB, t_start, sets, wsum, 0, s));
   MZK_HIP(hipGetLastError());
   prof_end(s, MZK_PH_MSM_REDUCE);
   prof_begin(s, MZK_PH_MSM_COMBINE);
-#ifdef MZK_TUNING
-  if (!rows) MZK_TRY(launch_window_combine((const u32*)wsum, sets, horner_c, out_partial_xyzz ? 1 : 0, d_out, s));
-  else
-#endif
   MZK_TRY(launch_window_combine_row((const u32*)wsum, sets, horner_c, out_partial_xyzz ? 1 : 0, d_out, s));
   prof_end(s, MZK_PH_MSM_COMBINE);
   return MZK_OK;
@@ -1643,11 +1539,6 @@ static int sort_records(const MsmPlan& P, const SortBufs& a, hipStream_t s) {
     else if (P.coarse_c == 17) MZK_STAGED(17, COARSE_LOG);
     else MZK_STAGED(16, COARSE_LOG);
   }
-#ifdef MZK_TUNING
-  else if (P.coarse_c == 20) MZK_DIRECT(20, COARSE_LOG);
-  else if (P.coarse_c == 17) MZK_DIRECT(17, COARSE_LOG);
-  else if (P.coarse_c == 16) MZK_DIRECT(16, COARSE_LOG);
-#endif
   else if (P.cl == 10) MZK_DIRECT(0, 10);
   else MZK_DIRECT(0, COARSE_LOG);
 #undef MZK_STAGED
@@ -1794,7 +1685,7 @@ int msm_dev_impl(const void* d_scalars, const void* d_points, size_t n, int poin
     if (P.combine_wide)
       hipLaunchKernelGGL(k_seg_combine_wide, dim3((unsigned)((P.NB + 127) / 128)), dim3(128), 0, s, slots, offsets, buckets, P.NB, P.seg, heavy, P.t_max);
     else
-      hipLaunchKernelGGL(k_seg_combine<1>, dim3((unsigned)((4 * P.NB + 127) / 128)), dim3(128), 0, s, slots, offsets, buckets, P.NB, P.seg, heavy, (const u32*)nullptr, 0, P.t_max);
+      hipLaunchKernelGGL(k_seg_combine, dim3((unsigned)((4 * P.NB + 127) / 128)), dim3(128), 0, s, slots, offsets, buckets, P.NB, P.seg, heavy, (const u32*)nullptr, 0, P.t_max);
     hipLaunchKernelGGL(k_seg_combine_heavy, dim3(HEAVY_GRID), dim3(HEAVY_THREADS), 0, s, (const u32*)slots, (const u32*)offsets, buckets, heavy, P.max_heavy);
     MZK_HIP(hipGetLastError());
     prof_end(s, MZK_PH_MSM_SEG_COMBINE);
@@ -2082,15 +1973,7 @@ int msm_many_dev_impl(const void* d_scalars, size_t n, size_t stride_elems, size
     // 0.149 / 0.167 ms, 16 x 2^14 0.112 -> 0.130 / 0.168, 256 x 2^10 0.073 -> 0.092 / 0.135 (profiles/round6_seg_combine_quads_per_bucket_ab.txt):
     // the kernel is bound by the instructions of its additions, not by the length of a bucket's chain, and the fold adds some.
     const unsigned cgrid = (unsigned)((4 * NBtot + 127) / 128);
-#ifdef MZK_TUNING
-    static const int env_qpb = tune_int("MZK_COMBINE_QPB", 1);          // tuning build: 2 / 4 = the measured-and-dropped forms
-    if (env_qpb == 4)
-      hipLaunchKernelGGL(k_seg_combine<4>, dim3(4 * cgrid), dim3(128), 0, s, slots, (const u32*)compact, buckets, NBtot, seg, heavy, (const u32*)tails, lgB, t_max);
-    else if (env_qpb == 2)
-      hipLaunchKernelGGL(k_seg_combine<2>, dim3(2 * cgrid), dim3(128), 0, s, slots, (const u32*)compact, buckets, NBtot, seg, heavy, (const u32*)tails, lgB, t_max);
-    else
-#endif
-      hipLaunchKernelGGL(k_seg_combine<1>, dim3(cgrid), dim3(128), 0, s, slots, (const u32*)compact, buckets, NBtot, seg, heavy, (const u32*)tails, lgB, t_max);
+    hipLaunchKernelGGL(k_seg_combine, dim3(cgrid), dim3(128), 0, s, slots, (const u32*)compact, buckets, NBtot, seg, heavy, (const u32*)tails, lgB, t_max);
     hipLaunchKernelGGL(k_seg_combine_heavy, dim3(HEAVY_GRID), dim3(HEAVY_THREADS), 0, s, (const u32*)slots, (const u32*)compact, buckets, heavy, max_heavy);
     MZK_HIP(hipGetLastError());
     prof_end(s, MZK_PH_MSM_SEG_COMBINE);
@@ -2318,9 +2201,6 @@ int msm_many_srs(const mzk_srs* srs, const void* d_scalars, size_t n, size_t str
 
 int msm_fold_partials_impl(const void* d_partials, int count, void* d_out_xy, hipStream_t s) {
   if (!d_partials || !d_out_xy || count < 0) { set_error("fold_partials: bad argument"); return MZK_E_ARG; }
-#ifdef MZK_TUNING
-  if (!row_tails()) return launch_fold_partials((const u32*)d_partials, count, (u32*)d_out_xy, s);
-#endif
   MZK_TRY(launch_fold_partials_row((const u32*)d_partials, count, (u32*)d_out_xy, s));
   return MZK_OK;
 }

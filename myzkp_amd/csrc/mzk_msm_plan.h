@@ -112,7 +112,6 @@ struct MsmKnobs {
   int coarse_log_17 = 9;          // MZK_COARSE_LOG_17: 8 = the 256-bin form with 8-byte records
   int per_fine = 0;               // MZK_PER_FINE: records per fine workgroup (tools/timing/window_sweep.py)
   int sort_scan_free = 3;         // MZK_SORT_SCAN_FREE: bit 0 = coarse level, bit 1 = fine level
-  int coarse_staged = 1;          // MZK_COARSE_STAGED: 0 = A/B against the direct stores
   int combine_wide_min_log = 17;  // MZK_COMBINE_WIDE_MIN_LOG
 };
 
@@ -287,7 +286,7 @@ static inline MsmPlan msm_plan(size_t n, size_t n_shape, size_t n_alloc, int poi
   P.coarse_free = (kn.sort_scan_free & 1) != 0 && cbins <= (size_t)SORT_CTR_BINS;
   P.fine_free = (kn.sort_scan_free & 2) != 0 && P.F <= STAGE_F_MAX;
   P.coarse_c = (plain_merged && (L.c == 16 || L.c == 17 || L.c == 20)) ? L.c : 0;     // the default widths by SRS size
-  P.scatter_staged = P.coarse_c != 0 && (kn.coarse_staged != 0 || P.cl != COARSE_LOG);
+  P.scatter_staged = P.coarse_c != 0;
   return msm_sized(P, regions);
 }
 

@@ -40,9 +40,6 @@ constexpr int MAX_LEVEL_LOG = MZK_NTT_MAX_LEVEL_LOG;
 #define MZK_NTT_LAZY_FIRST 1       // 0: A/B builds of the carry-everywhere butterflies (tools/timing/time_ntt.py with MZK_HIP_LIB)
 #endif
 constexpr bool NTT_LAZY_FIRST = MZK_NTT_LAZY_FIRST != 0;
-#ifndef MZK_NTT_EARLY_TW
-#define MZK_NTT_EARLY_TW 0         // 1: A/B builds with the inter-pass twiddles requested at the top of the strided pass (measured slower, see k_ntt_strided)
-#endif
 // Tile geometry.  Small (1024 elements, 256 lanes, levels of <= 2^8): every size below 2^20.  Large (4096 elements,
 // 1024 lanes = one workgroup per CU, levels of <= 2^10): from 2^20 points on, where 256+ workgroups exist -- a 2^20
 // transform is TWO passes of 2^10 levels instead of three (one global round trip and one inter-pass twiddle product
@@ -110,17 +107,12 @@ struct LevelInfo {
 };
 
 // ---- global memory <-> limbs ----------------------------------------------------------------------
-// The streaming accesses of the transform passes -- the data (read once, written once per pass) and the inter-pass twiddles -- can
-// carry the non-temporal hint (MZK_NTT_NT = 1).  A plain copy gains 25 % from it on MI355X (profiles/round5_copy_kernel_variants.txt);
-// the transforms LOSE: M128 2^20 0.0407 -> 0.0433 ms, 2^22 0.151 -> 0.180 (same box, profiles/round5_ntt_nontemporal_ab.txt) -- what
-// one pass writes, the next one reads back out of L2 / the 256-MiB Infinity Cache, and so it does the twiddle tables of the
-// previous transform; the hint takes that away.  Off.
-#ifndef MZK_NTT_NT
-#define MZK_NTT_NT 0
-#endif
+// The streaming accesses of the transform passes -- the data (read once, written once per pass) and the inter-pass twiddles -- do NOT
+// carry the non-temporal hint.  A plain copy gains 25 % from it on MI355X (profiles/round5_copy_kernel_variants.txt); the transforms
+// LOSE: M128 2^20 0.0407 -> 0.0433 ms, 2^22 0.151 -> 0.180 (same box, profiles/round5_ntt_nontemporal_ab.txt) -- what one pass writes,
+// the next one reads back out of L2 / the 256-MiB Infinity Cache, and so it does the twiddle tables of the previous transform.
 typedef unsigned int u32x4_t __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ u32x4_t stream_load16(const u32* p) {
-  if (MZK_NTT_NT) return __builtin_nontemporal_load(reinterpret_cast<const u32x4_t*>(p));
   return *reinterpret_cast<const u32x4_t*>(p);
 }
 // wt: the store goes out write-through at agent scope (`sc1`), so what a pass writes reaches the fabric while the other waves
@@ -128,8 +120,7 @@ __device__ __forceinline__ u32x4_t stream_load16(const u32* p) {
 // kernels (a run-time branch around the store cost the 128-VGPR instantiations two to four spilled registers), chosen per transform
 // size by run_plan_geo.
 __device__ __forceinline__ void stream_store16(u32* p, u32x4_t v, bool wt) {
-  if (MZK_NTT_NT) __builtin_nontemporal_store(v, reinterpret_cast<u32x4_t*>(p));
-  else if (wt) asm volatile("global_store_dwordx4 %0, %1, off sc1" : : "v"(p), "v"(v) : "memory");
+  if (wt) asm volatile("global_store_dwordx4 %0, %1, off sc1" : : "v"(p), "v"(v) : "memory");
   else *reinterpret_cast<u32x4_t*>(p) = v;
 }
 template <class P> __device__ __forceinline__ void gload_words_stream(const u32* __restrict__ g, size_t idx, u32 (&w)[P::NW]) {
@@ -504,13 +495,9 @@ __global__ __launch_bounds__(G::NT, G::WPE) void k_ntt_strided(const u32* __rest
   static_assert(UNR == 4 * GQ, "whole radix-4 groups per lane");
   constexpr bool wt = WT;
   const bool fused = fuse_edges<G>(lgn, lgc, fuse);   // first (plain loads only) and last stage pair on registers, next to the global accesses
-  // EARLY_TW (M128, one 1024-lane workgroup per CU: 44 of 128 VGPRs in use): the inter-pass twiddles of the lane's four elements are
-  // requested right behind its data, at the top of the kernel, and wait in 16 registers.  A 2^20 transform is one tile per CU with
-  // all CUs in lock-step, so the request after the stage loop met an idle HBM and every wave waited out the whole 16-MiB burst
-  // (~4 us of a 24-us pass); now that burst streams in under the butterflies.
-  constexpr bool EARLY_OK = SparseMod<P>::value && G::NT == 1024 && !G::TWG;
-  constexpr bool EARLY_TW = MZK_NTT_EARLY_TW == 1 && EARLY_OK;          // at the top, behind the data loads
-  constexpr bool MID_TW = MZK_NTT_EARLY_TW == 2 && EARLY_OK;            // behind the first barrier: the data has arrived, HBM is idle
+  // The inter-pass twiddles are requested behind the stage loop.  The 1024-lane M128 tile has the registers to request them earlier: at the
+  // top of the kernel, behind the data loads, 2^20 went 0.0413 -> 0.0450 ms (the 16-MiB twiddle burst competes with the data's); behind the
+  // first barrier 0.0420-0.0426 -> 0.0430-0.0432 (profiles/round5_ntt_m128_sparse_signed_lazy_ab.txt).
   u32 tw[UNR][P::NW];
   auto tw_load_at = [&](int t, int u) {
     const int e = t + u * G::NT;
@@ -522,10 +509,6 @@ __global__ __launch_bounds__(G::NT, G::WPE) void k_ntt_strided(const u32* __rest
     for (int u = 0; u < UNR; u++) {
       const int e = tid + u * G::NT;
       gload_words_stream<P>(in, base + ((size_t)(e >> lgc) << lgM) + (e & cmask), w[u]);
-    }
-    if constexpr (EARLY_TW) {
-#pragma unroll
-      for (int u = 0; u < UNR; u++) tw_load_at(tid, u);
     }
     if (fused) {       // first stage pair next to the loads: the data of a wave starts computing when IT has arrived
 #pragma unroll
@@ -550,10 +533,6 @@ __global__ __launch_bounds__(G::NT, G::WPE) void k_ntt_strided(const u32* __rest
       lds_store<P, G>(lds, (k << lgc) | c, fe_unpack<P>(w[u]));
     }
   } else {
-  if constexpr (EARLY_TW) {      // the coefficient vector is a fraction of the tile (the rest is the zero padding): the twiddles may as well go first
-#pragma unroll
-    for (int u = 0; u < UNR; u++) tw_load_at(tid, u);
-  }
   for (int e = tid; e < tile_elems; e += G::NT) {
     const int j1 = e >> lgc, c = e & cmask;
     Fe<P> v;
@@ -576,10 +555,6 @@ __global__ __launch_bounds__(G::NT, G::WPE) void k_ntt_strided(const u32* __rest
   }
   }
   __syncthreads();
-  if constexpr (MID_TW) {
-#pragma unroll
-    for (int u = 0; u < UNR; u++) tw_load_at(tid, u);
-  }
   tile_stages<P, G>(lds, twl, lgn, lgc, (fused && !PRE) ? 3 - (lgn & 1) : 1, fused ? lgn - 2 : lgn, tw_shoup);
   {
     // The inter-pass twiddles of all the lane's elements, requested before the first product.  The epilogue's addresses are
@@ -588,10 +563,8 @@ __global__ __launch_bounds__(G::NT, G::WPE) void k_ntt_strided(const u32* __rest
     // keeps every hot kernel at zero).
     int tid = threadIdx.x;
     asm volatile("" : "+v"(tid));
-    if constexpr (!EARLY_TW && !MID_TW) {
 #pragma unroll
-      for (int u = 0; u < UNR; u++) tw_load_at(tid, u);
-    }
+    for (int u = 0; u < UNR; u++) tw_load_at(tid, u);
     if (fused) {       // last stage pair on registers: the lane's group q is rows j1 + v 2^(lgn-2), exactly the elements it stores
 #pragma unroll
       for (int q = 0; q < GQ; q++) {

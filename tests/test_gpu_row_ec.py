@@ -36,10 +36,10 @@ def test_wave_inversion_equals_the_single_lane_safegcd(seed, n):
 
 
 def test_tuning_build_switches_give_the_same_commitments_and_transforms():
-    """The shipped library reads no environment variable (tests/test_abi_load.py).  The A/B switches live in the tuning build
-    (python -m myzkp_amd.build --tuning, loaded through MZK_HIP_LIB): every non-default path they select -- the DPP-quad tails
-    of round 2, the sorted small path, direct-store coarse scatter, the prefetching accumulate, un-fused NTT edges, Montgomery-only
-    twiddles -- must still give the shipped library's results, which are the oracle's."""
+    """The shipped library reads no environment variable (tests/test_abi_load.py).  The switches live in the tuning build
+    (python -m myzkp_amd.build --tuning, loaded through MZK_HIP_LIB): every non-default path they select -- the sorted small
+    path, the prefetching accumulate, un-fused NTT edges, Montgomery-only twiddles -- must still give the shipped library's
+    results, which are the oracle's."""
     import os, subprocess, sys
     import myzkp_amd.build as b
     tuning = b.build(tuning=True)
@@ -62,8 +62,8 @@ print(repr(out))
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     res = {}
     variants = {"shipped": {},
-                "quad_tails": {"MZK_ROW_TAILS": "0"},
-                "sorted_small_direct_scatter_prefetch": {"MZK_SMALL_SCAN": "0", "MZK_COARSE_STAGED": "0", "MZK_ACC_PREFETCH": "1"},
+                "sorted_small": {"MZK_SMALL_SCAN": "0"},
+                "prefetch": {"MZK_ACC_PREFETCH": "1"},
                 "ntt_unfused_montgomery": {"MZK_NTT_FUSE_EDGES": "0", "MZK_NTT_SHOUP": "0"}}
     for name, extra in variants.items():
         env = dict(os.environ, **extra)
