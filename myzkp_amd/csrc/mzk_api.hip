@@ -238,9 +238,9 @@ int ensure_init() {
 }
 
 // ---- host parameter math --------------------------------------------------------------------------
-static const HostField HF_FR = {4, {0x43e1f593f0000001ULL, 0x2833e84879b97091ULL, 0xb85045b68181585dULL, 0x30644e72e131a029ULL}};
-static const HostField HF_FQ = {4, {0x3c208c16d87cfd47ULL, 0x97816a916871ca8dULL, 0xb85045b68181585dULL, 0x30644e72e131a029ULL}};
-static const HostField HF_M128 = {2, {1ULL, 407ULL << 55, 0, 0}};
+static const HostField HF_FR = {4, {0x43e1f593f0000001ULL, 0x2833e84879b97091ULL, 0xb85045b68181585dULL, 0x30644e72e131a029ULL}, 29 * FrParams::L};
+static const HostField HF_FQ = {4, {0x3c208c16d87cfd47ULL, 0x97816a916871ca8dULL, 0xb85045b68181585dULL, 0x30644e72e131a029ULL}, 29 * FqParams::L};
+static const HostField HF_M128 = {2, {1ULL, 407ULL << 55, 0, 0}, 29 * M128Params::L};
 const HostField* host_field(int fid) {
   switch (fid) {
     case MZK_FIELD_FR: return &HF_FR;
@@ -248,6 +248,16 @@ const HostField* host_field(int fid) {
     case MZK_FIELD_FQ: return &HF_FQ;
     default: return nullptr;
   }
+}
+int field_check(int fid, const char* who, bool fq_too) {
+  if (fid == MZK_FIELD_FR || fid == MZK_FIELD_M128 || (fq_too && fid == MZK_FIELD_FQ)) return MZK_OK;
+  set_error("%s: bad field id %d", who, fid);
+  return MZK_E_ARG;
+}
+int field_check_ntt(int fid, const char* who) {
+  if (fid == MZK_FIELD_FR || fid == MZK_FIELD_M128) return MZK_OK;
+  set_error("%s: field id %d has no NTT on this path", who, fid);
+  return MZK_E_ARG;
 }
 static int h_cmp(const uint64_t* a, const uint64_t* b, int n) {
   for (int i = n - 1; i >= 0; i--) if (a[i] != b[i]) return a[i] > b[i] ? 1 : -1;
@@ -367,6 +377,10 @@ void h_ninv_pow2(const HostField* f, unsigned k, uint64_t* out) {
     unsigned __int128 d = (unsigned __int128)f->p[i] - q[i] - (uint64_t)br;
     out[i] = (uint64_t)d; br = (d >> 64) & 1;
   }
+}
+void h_rmod(const HostField* f, uint64_t* out) {
+  const uint64_t two[4] = {2, 0, 0, 0};
+  h_powmod_u64(f, out, two, (uint64_t)f->mont_bits);
 }
 
 }  // namespace mzk
@@ -572,8 +586,7 @@ int mzk_root_of_unity(int field_id, unsigned log2_n, uint64_t* out) {
     for (int i = 0; i < 4; i++) out[i] = r[i];
     return MZK_OK;
   }
-  set_error("root_of_unity: bad field id %d", field_id);
-  return MZK_E_ARG;
+  return field_check(field_id, "root_of_unity");
 }
 
 // ---- host-buffer NTT family ---------------------------------------------------------------------------
@@ -666,7 +679,7 @@ static int msm_host_chunked(const uint64_t* scalars, const uint64_t* points, voi
 
 int mzk_ntt(int field_id, const uint64_t* root, const uint64_t* in, uint64_t* out, size_t n, int inverse) {
   MZK_ENTER();
-  if (field_id != MZK_FIELD_FR && field_id != MZK_FIELD_M128) { set_error("ntt: bad field id %d", field_id); return MZK_E_ARG; }
+  MZK_TRY(field_check(field_id, "ntt"));
   if (n == 0) return MZK_OK;
   if (!in || !out) { set_error("ntt: null pointer"); return MZK_E_ARG; }
   hipStream_t s = ctx().stream;
@@ -695,7 +708,7 @@ int mzk_coset_lde_batch_dev(int field_id, const void* d_coefs, size_t n_coef, co
 int mzk_coset_lde_batch(int field_id, const uint64_t* coefs, size_t n_coef, const uint64_t* offset, const uint64_t* generator,
                         uint64_t* out, size_t order, size_t batch) {
   MZK_ENTER();
-  if (field_id != MZK_FIELD_FR && field_id != MZK_FIELD_M128) { set_error("coset_lde: bad field id %d", field_id); return MZK_E_ARG; }
+  MZK_TRY(field_check(field_id, "coset_lde"));
   if (n_coef > order) { set_error("attempt to subtract with overflow (order - polynomial.coef.len())"); return MZK_E_LENGTH; }
   if (order == 0 || batch == 0) return MZK_OK;
   if (!out || (!coefs && n_coef)) { set_error("coset_lde: null pointer"); return MZK_E_ARG; }
@@ -716,7 +729,7 @@ int mzk_ntt_batch_dev(int field_id, const uint64_t* root_host, const void* d_in,
 }
 int mzk_ntt_batch(int field_id, const uint64_t* root, const uint64_t* in, uint64_t* out, size_t n, size_t batch, int inverse) {
   MZK_ENTER();
-  if (field_id != MZK_FIELD_FR && field_id != MZK_FIELD_M128) { set_error("ntt: bad field id %d", field_id); return MZK_E_ARG; }
+  MZK_TRY(field_check(field_id, "ntt"));
   if (n == 0 || batch == 0) return MZK_OK;
   if (!in || !out) { set_error("ntt: null pointer"); return MZK_E_ARG; }
   hipStream_t s = ctx().stream;
@@ -732,7 +745,7 @@ int mzk_ntt_batch(int field_id, const uint64_t* root, const uint64_t* in, uint64
 int mzk_coset_lde(int field_id, const uint64_t* coef, size_t n_coef, const uint64_t* offset, const uint64_t* generator,
                   uint64_t* out, size_t order) {
   MZK_ENTER();
-  if (field_id != MZK_FIELD_FR && field_id != MZK_FIELD_M128) { set_error("coset_lde: bad field id %d", field_id); return MZK_E_ARG; }
+  MZK_TRY(field_check(field_id, "coset_lde"));
   if (n_coef > order) { set_error("attempt to subtract with overflow (order - polynomial.coef.len())"); return MZK_E_LENGTH; }
   if (order == 0) return MZK_OK;
   if (!out || (!coef && n_coef)) { set_error("coset_lde: null pointer"); return MZK_E_ARG; }
@@ -762,7 +775,7 @@ int mzk_poly_scale(int field_id, const uint64_t* coef, size_t n, const uint64_t*
   MZK_ENTER();
   if (n == 0) return MZK_OK;
   if (!coef || !out) { set_error("poly_scale: null pointer"); return MZK_E_ARG; }
-  if (field_id != MZK_FIELD_FR && field_id != MZK_FIELD_M128) { set_error("poly_scale: bad field id %d", field_id); return MZK_E_ARG; }
+  MZK_TRY(field_check(field_id, "poly_scale"));
   hipStream_t s = ctx().stream;
   WsGuard wsg(s);
   const size_t esz = field_bytes(field_id);
@@ -810,7 +823,7 @@ static int conv_on_device(int fid, const uint64_t* a, size_t la, const uint64_t*
 int mzk_fft_multiply(int field_id, const uint64_t* a, size_t la, const uint64_t* b, size_t lb, const uint64_t* omega,
                      uint64_t* out, size_t* out_len) {
   MZK_ENTER();
-  if (field_id != MZK_FIELD_FR && field_id != MZK_FIELD_M128) { set_error("fft_multiply: bad field id %d", field_id); return MZK_E_ARG; }
+  MZK_TRY(field_check(field_id, "fft_multiply"));
   if (!out_len || (!a && la) || (!b && lb)) { set_error("fft_multiply: null pointer"); return MZK_E_ARG; }
   if (la + lb == 0) { set_error("attempt to subtract with overflow (self.coef.len() + other.coef.len() - 1)"); return MZK_E_LENGTH; }
   const size_t m = la + lb - 1;
@@ -847,7 +860,7 @@ int mzk_fft_multiply(int field_id, const uint64_t* a, size_t la, const uint64_t*
 int mzk_fast_multiply(int field_id, const uint64_t* a, size_t la, const uint64_t* b, size_t lb, const uint64_t* root,
                       size_t root_order, uint64_t* out, size_t* out_len) {
   MZK_ENTER();
-  if (field_id != MZK_FIELD_FR && field_id != MZK_FIELD_M128) { set_error("fast_multiply: bad field id %d", field_id); return MZK_E_ARG; }
+  MZK_TRY(field_check(field_id, "fast_multiply"));
   if (!out_len || !root || (!a && la) || (!b && lb)) { set_error("fast_multiply: null pointer"); return MZK_E_ARG; }
   const HostField* hf = host_field(field_id);
   const int nl = hf->nl;
@@ -872,7 +885,7 @@ int mzk_fast_multiply(int field_id, const uint64_t* a, size_t la, const uint64_t
     // ntt.rs:86-88 `return lhs * rhs` (schoolbook, trimmed).  Same product through a 16-point cyclic
     // convolution (degree < 8 < 16, so no wrap-around), then trimmed like Polynomial::mul_ref.
     order = 16;
-    if (field_id == MZK_FIELD_M128) MZK_TRY(mzk_root_of_unity(field_id, 4, r)); else MZK_TRY(mzk_root_of_unity(field_id, 4, r));
+    MZK_TRY(mzk_root_of_unity(field_id, 4, r));
     trim = true;
     la = da; lb = db;
   } else {
@@ -926,7 +939,7 @@ static size_t small_poly_div(const HostField* hf, const uint64_t* lhs, size_t tl
 int mzk_fast_coset_divide(int field_id, const uint64_t* lhs, size_t ll, const uint64_t* rhs, size_t lr, const uint64_t* offset,
                           const uint64_t* root, size_t root_order, uint64_t* out, size_t* out_len) {
   MZK_ENTER();
-  if (field_id != MZK_FIELD_FR && field_id != MZK_FIELD_M128) { set_error("fast_coset_divide: bad field id %d", field_id); return MZK_E_ARG; }
+  MZK_TRY(field_check(field_id, "fast_coset_divide"));
   if (!out || !out_len || !root || !offset || (!lhs && ll) || (!rhs && lr)) { set_error("fast_coset_divide: null pointer"); return MZK_E_ARG; }
   const HostField* hf = host_field(field_id);
   const int nl = hf->nl;
@@ -975,7 +988,7 @@ int mzk_fast_coset_divide_batch_dev(int field_id, const void* d_lhs, size_t lhs_
                                     size_t rhs_len, const uint64_t* offset, const uint64_t* root, size_t root_order, void* d_out, size_t out_stride,
                                     size_t* out_lens, void* stream) {
   MZK_ENTER();
-  if (field_id != MZK_FIELD_FR && field_id != MZK_FIELD_M128) { set_error("fast_coset_divide: bad field id %d", field_id); return MZK_E_ARG; }
+  MZK_TRY(field_check(field_id, "fast_coset_divide"));
   if (!root || !offset || (!d_rhs && rhs_len) || (count && (!lhs_lens || !out_lens || (!d_lhs && lhs_stride) || (!d_out && out_stride)))) {
     set_error("fast_coset_divide: null pointer");
     return MZK_E_ARG;
@@ -1565,7 +1578,7 @@ int mzk_fri_fold_dev(int field_id, const void* d_codeword, size_t n, const uint6
 int mzk_fri_fold(int field_id, const uint64_t* codeword, size_t n, const uint64_t* alpha, const uint64_t* offset,
                  const uint64_t* omega, uint64_t* out) {
   MZK_ENTER();
-  if (field_id != MZK_FIELD_FR && field_id != MZK_FIELD_M128) { set_error("fri_fold: bad field id %d", field_id); return MZK_E_ARG; }
+  MZK_TRY(field_check(field_id, "fri_fold"));
   if (n / 2 == 0) return MZK_OK;
   if (!codeword || !out) { set_error("fri_fold: null pointer"); return MZK_E_ARG; }
   hipStream_t s = ctx().stream;

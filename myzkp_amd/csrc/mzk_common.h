@@ -144,6 +144,7 @@ struct ProfScope {
 struct HostField {
   int nl;            // u64 limbs
   uint64_t p[4];
+  int mont_bits;     // the device's Montgomery radix is R = 2^mont_bits (29 bits per limb: mzk_field.h)
 };
 const HostField* host_field(int fid);
 bool h_is_canonical(const HostField* f, const uint64_t* a);
@@ -152,10 +153,38 @@ void h_powmod_u64(const HostField* f, uint64_t* r, const uint64_t* a, uint64_t e
 void h_invmod(const HostField* f, uint64_t* r, const uint64_t* a);   // a^(p-2) on the host (parameters only)
 void h_ninv_pow2(const HostField* f, unsigned log2n, uint64_t* out);  // (2^log2n)^-1 mod p, needs 2^log2n | p-1
 bool h_is_one(const HostField* f, const uint64_t* a);
+void h_rmod(const HostField* f, uint64_t* out);                       // R mod p: x -> x R mod p is one h_mulmod with it
 
 static inline int field_words(int fid) { return fid == MZK_FIELD_M128 ? 4 : 8; }   // u32 words per element
 static inline int field_limbs64(int fid) { return fid == MZK_FIELD_M128 ? 2 : 4; }
 static inline size_t field_bytes(int fid) { return fid == MZK_FIELD_M128 ? 16 : 32; }
+static inline unsigned field_max_log(int fid) { return fid == MZK_FIELD_FR ? 28 : 32; }   // mzk.h "Size limits"
+
+// ---- field id -> template instantiation ---------------------------------------------------------------
+// The ONE place that knows which field id selects which parameter set.  field_check / field_check_ntt are the argument checks of
+// the Fr / M128 entry points (fq_too: Fq passes as well): MZK_OK, or MZK_E_ARG with "<who>: bad field id <id>" /
+// "<who>: field id <id> has no NTT on this path".
+int field_check(int fid, const char* who, bool fq_too = false);
+int field_check_ntt(int fid, const char* who);
+// with_field(fid, f) returns f(FieldTag<FrParams or M128Params>()); f is a generic lambda that names the parameter set as
+// `typename decltype(tag)::P` (word-count templates take P::NW) and returns int.  An id that is neither is an error here, never Fr's
+// kernels -- callers have validated theirs, so that is a bug's landing place, not a path.
+template <class P_> struct FieldTag { typedef P_ P; };
+template <class F> static inline int with_field(int fid, F&& f) {
+  if (fid == MZK_FIELD_M128) return f(FieldTag<M128Params>());
+  if (fid == MZK_FIELD_FR) return f(FieldTag<FrParams>());
+  return field_check(fid, "with_field");
+}
+// ... and Fq as well (synthetic data, self-tests, probes)
+template <class F> static inline int with_field3(int fid, F&& f) {
+  if (fid == MZK_FIELD_FR) return f(FieldTag<FrParams>());
+  if (fid == MZK_FIELD_FQ) return f(FieldTag<FqParams>());
+  if (fid == MZK_FIELD_M128) return f(FieldTag<M128Params>());
+  return field_check(fid, "with_field", true);
+}
+// One launch of kernel<P> (or kernel<P::NW>) for the field: the arguments after the kernel are hipLaunchKernelGGL's.
+#define MZK_FIELD_LAUNCH(fid, kernel, ...) \
+  mzk::with_field(fid, [&](auto tag_) { typedef typename decltype(tag_)::P P; hipLaunchKernelGGL((kernel), __VA_ARGS__); return MZK_OK; })
 
 // ---- entry points implemented per translation unit ------------------------------------------------
 int ntt_dev_impl(int fid, const uint64_t* root_host, const void* d_in, void* d_out, size_t n, int inverse,

@@ -49,8 +49,8 @@ static void gm_words(const uint64_t* v, GmW8* out) {
 // v R mod r (R = 2^(29 L) = 2^261), as 8 words
 static void gm_mont(const uint64_t* v, GmW8* out) {
   const HostField* fr = host_field(MZK_FIELD_FR);
-  uint64_t two[4] = {2, 0, 0, 0}, rmod[4], t[4];
-  h_powmod_u64(fr, rmod, two, 29 * GP::L);
+  uint64_t rmod[4], t[4];
+  h_rmod(fr, rmod);
   h_mulmod(fr, t, v, rmod);
   gm_words(t, out);
 }

@@ -492,7 +492,7 @@ static int synth_div_impl(int fid, const SdJob* jobs, const size_t* rounds, int 
   return MZK_OK;
 }
 int synth_div_field_dev(int fid, const SdJob* jobs, const size_t* rounds, int nrounds, hipStream_t s) {
-  return fid == MZK_FIELD_M128 ? synth_div_impl<M128Params>(fid, jobs, rounds, nrounds, s) : synth_div_impl<FrParams>(MZK_FIELD_FR, jobs, rounds, nrounds, s);
+  return with_field(fid, [&](auto tag) { return synth_div_impl<typename decltype(tag)::P>(fid, jobs, rounds, nrounds, s); });
 }
 int synth_div_dev(const SdJob* jobs, const size_t* rounds, int nrounds, hipStream_t s) { return synth_div_field_dev(MZK_FIELD_FR, jobs, rounds, nrounds, s); }
 
@@ -504,7 +504,7 @@ int synth_div_dev(const SdJob* jobs, const size_t* rounds, int nrounds, hipStrea
 // (division with remainder is unique), so the reference's trim is one pass at the end (rows_trimmed_len_dev), which also clears the rows' tails.
 int poly_div_roots_check(int fid, const void* polys, size_t stride, const size_t* lens, size_t count, const uint64_t* roots, const size_t* root_offsets,
                          const void* out, const size_t* out_lens) {
-  if (fid != MZK_FIELD_FR && fid != MZK_FIELD_M128) { set_error("poly_div_roots: bad field id %d", fid); return MZK_E_ARG; }
+  MZK_TRY(field_check(fid, "poly_div_roots"));
   if (count == 0) return MZK_OK;
   if (!lens || !root_offsets || !out_lens || (stride && (!polys || !out))) { set_error("poly_div_roots: null pointer"); return MZK_E_ARG; }
   const HostField* hf = host_field(fid);

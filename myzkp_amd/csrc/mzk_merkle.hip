@@ -312,6 +312,11 @@ __global__ __launch_bounds__(256) void k_canonicalize_signed(u32* __restrict__ e
     borrow = (u32)(d >> 32) & 1u;
   }
 }
+static int canonicalize_signed(int fid, void* d_elems, const void* d_neg, size_t n, hipStream_t s) {
+  MZK_TRY(MZK_FIELD_LAUNCH(fid, k_canonicalize_signed<P::NW>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, (u32*)d_elems, (const u8*)d_neg, n, fid));
+  MZK_HIP(hipGetLastError());
+  return MZK_OK;
+}
 
 // ---- ragged leaf counts (merkle.rs:15-25 accepts any non-empty slice: mid = len / 2) ----------------------------
 // The recursion splits k leaves into floor(k/2) | ceil(k/2), so at depth D = floor(log2 n) there are M = 2^D subtrees
@@ -575,13 +580,8 @@ static int merkle_hash_levels(int kind, int fid, const void* d_leaves, const u64
     static const int lp_on = tune_int("MZK_LEAF_LANE_PAIRS", 1);      // tuning build: 0 = one lane per leaf pair at every size (A/B)
     const bool lp = lp_on && pairs <= LEAF_PAIR_MAX;
     const unsigned lpb = (unsigned)((pairs + LEAF_THREADS / 2 - 1) / (LEAF_THREADS / 2));
-    if (fid == MZK_FIELD_M128) {
-      if (lp) hipLaunchKernelGGL((k_merkle_leaf_pairs_lp<4>), dim3(lpb), dim3(LEAF_THREADS), 0, s, (const u32*)d_leaves, pairs, d_nodes, d_neg);
-      else hipLaunchKernelGGL((k_merkle_leaf_pairs<4>), dim3(blocks), dim3(LEAF_THREADS), 0, s, (const u32*)d_leaves, pairs, d_nodes, d_neg);
-    } else {
-      if (lp) hipLaunchKernelGGL((k_merkle_leaf_pairs_lp<8>), dim3(lpb), dim3(LEAF_THREADS), 0, s, (const u32*)d_leaves, pairs, d_nodes, d_neg);
-      else hipLaunchKernelGGL((k_merkle_leaf_pairs<8>), dim3(blocks), dim3(LEAF_THREADS), 0, s, (const u32*)d_leaves, pairs, d_nodes, d_neg);
-    }
+    if (lp) MZK_TRY(MZK_FIELD_LAUNCH(fid, k_merkle_leaf_pairs_lp<P::NW>, dim3(lpb), dim3(LEAF_THREADS), 0, s, (const u32*)d_leaves, pairs, d_nodes, d_neg));
+    else MZK_TRY(MZK_FIELD_LAUNCH(fid, k_merkle_leaf_pairs<P::NW>, dim3(blocks), dim3(LEAF_THREADS), 0, s, (const u32*)d_leaves, pairs, d_nodes, d_neg));
   }
   u64* below = d_nodes;
   size_t count = pairs;
@@ -776,12 +776,12 @@ extern "C" {
 int mzk_merkle_build_field_dev(int field_id, const void* d_elems, size_t n, mzk_merkle** out, void* stream) {
   MZK_ENTER();
   WsGuard wsg((hipStream_t)stream);
-  if (field_id != MZK_FIELD_FR && field_id != MZK_FIELD_M128) { set_error("merkle: bad field id %d", field_id); return MZK_E_ARG; }
+  MZK_TRY(field_check(field_id, "merkle"));
   return merkle_build(0, field_id, d_elems, true, n * field_bytes(field_id), nullptr, n, out, (hipStream_t)stream);
 }
 static int build_field_host(int field_id, const uint64_t* elems, const uint8_t* negative, size_t n, mzk_merkle** out) {
   MZK_ENTER();
-  if (field_id != MZK_FIELD_FR && field_id != MZK_FIELD_M128) { set_error("merkle: bad field id %d", field_id); return MZK_E_ARG; }
+  MZK_TRY(field_check(field_id, "merkle"));
   if (elems) {
     const HostField* hf = host_field(field_id);
     for (size_t i = 0; i < n; i++)
@@ -1093,7 +1093,7 @@ void mzk_merkle_free(mzk_merkle* t) {
 int mzk_merkle_commit_field_dev(int field_id, const void* d_elems, size_t n, uint8_t* root, size_t cap, size_t* root_len, void* stream) {
   MZK_ENTER();
   WsGuard wsg((hipStream_t)stream);
-  if (field_id != MZK_FIELD_FR && field_id != MZK_FIELD_M128) { set_error("merkle: bad field id %d", field_id); return MZK_E_ARG; }
+  MZK_TRY(field_check(field_id, "merkle"));
   if (n == 0) { set_error("merkle: empty leaf set (Merkle::commit recurses forever on it, merkle.rs:20-22)"); return MZK_E_LENGTH; }
   if (!d_elems || !root || !root_len) { set_error("merkle: null pointer"); return MZK_E_ARG; }
   if (!is_pow2(n)) {      // ragged (merkle.rs:15-25 accepts it; no prover call site produces it): handle path
@@ -1130,7 +1130,7 @@ int mzk_merkle_commit_field_dev(int field_id, const void* d_elems, size_t n, uin
 int mzk_merkle_commit_field_batch_dev(int field_id, const void* d_elems, size_t n, size_t batch, uint8_t* roots, void* stream) {
   MZK_ENTER();
   WsGuard wsg((hipStream_t)stream);
-  if (field_id != MZK_FIELD_FR && field_id != MZK_FIELD_M128) { set_error("merkle: bad field id %d", field_id); return MZK_E_ARG; }
+  MZK_TRY(field_check(field_id, "merkle"));
   if (batch == 0) return MZK_OK;
   if (n == 0) { set_error("merkle: empty leaf set (Merkle::commit recurses forever on it, merkle.rs:20-22)"); return MZK_E_LENGTH; }
   if (!d_elems || !roots) { set_error("merkle: null pointer"); return MZK_E_ARG; }
@@ -1146,7 +1146,7 @@ int mzk_merkle_commit_field_batch_dev(int field_id, const void* d_elems, size_t 
 }
 int mzk_merkle_commit_field_batch(int field_id, const uint64_t* elems, size_t n, size_t batch, uint8_t* roots) {
   MZK_ENTER();
-  if (field_id != MZK_FIELD_FR && field_id != MZK_FIELD_M128) { set_error("merkle: bad field id %d", field_id); return MZK_E_ARG; }
+  MZK_TRY(field_check(field_id, "merkle"));
   if (batch == 0) return MZK_OK;
   if (!elems) { set_error("merkle: null pointer"); return MZK_E_ARG; }
   hipStream_t s = ctx().stream;
@@ -1200,7 +1200,7 @@ static int fri_commit_rounds(int field_id, const uint64_t* codeword, const uint8
                              int num_rounds, mzk_fri_challenge_fn challenge, void* user, uint8_t* roots, uint64_t* root_len, uint64_t* codewords_out,
                              mzk_merkle** trees_out, bool on_device) {
   MZK_ENTER();
-  if (field_id != MZK_FIELD_FR && field_id != MZK_FIELD_M128) { set_error("fri_commit: bad field id %d", field_id); return MZK_E_ARG; }
+  MZK_TRY(field_check(field_id, "fri_commit"));
   if (num_rounds <= 0) return MZK_OK;
   if (!codeword || !omega || !offset || !challenge || !roots || !root_len) { set_error("fri_commit: null pointer"); return MZK_E_ARG; }
   if (!codewords_out && !trees_out) { set_error("fri_commit: no codeword output and no trees kept"); return MZK_E_ARG; }
@@ -1287,9 +1287,7 @@ static int fri_commit_rounds(int field_id, const uint64_t* codeword, const uint8
       root_len[r] = 32;
     }
     if (r == 0 && d_neg) {      // from here on the codeword is its canonical representative: v -> p - |v| where Sign::Minus
-      if (field_id == MZK_FIELD_M128) hipLaunchKernelGGL((k_canonicalize_signed<4>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, (u32*)cur, (const u8*)d_neg, n, field_id);
-      else hipLaunchKernelGGL((k_canonicalize_signed<8>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, (u32*)cur, (const u8*)d_neg, n, field_id);
-      MZK_HIP(hipGetLastError());
+      MZK_TRY(canonicalize_signed(field_id, cur, d_neg, n, s));
     }
     const int last = (r == num_rounds - 1);
     memset(alpha, 0xff, sizeof alpha);     // a callback that forgets alpha leaves a non-canonical value, never a silent 0
@@ -1556,7 +1554,7 @@ __global__ __launch_bounds__(64) void k_fri_query(FriQueryArgs A) {
 
 // Validation shared by the three entry points; fills the layout.  Nothing is enqueued.
 static int fri_prove_check(int field_id, size_t n, size_t expansion_factor, size_t tests, mzk_tx::FriLayout* L) {
-  if (field_id != MZK_FIELD_FR && field_id != MZK_FIELD_M128) { set_error("fri_prove: bad field id %d", field_id); return MZK_E_ARG; }
+  MZK_TRY(field_check(field_id, "fri_prove"));
   if (n == 0) { set_error("fri_prove: empty codeword"); return MZK_E_LENGTH; }
   if (!is_pow2(n)) { set_error("fri_prove: codeword length must be a power of two"); return MZK_E_NOT_POW2; }
   mzk_tx::fri_layout(n, expansion_factor, tests, field_limbs64(field_id), L);
@@ -1621,33 +1619,25 @@ static int fri_prove_impl(int field_id, const void* src, const void* negative, b
   memcpy(of, offset, 8 * nl);
   FriFoldConsts fc;
   MZK_TRY(fri_fold_consts(field_id, of, om, &fc));
-  const mzk_tx::FriLayout& P = L;
   for (int r = 0; r < R; r++) {
     const size_t len = n >> r;
     const void* leaves = r == 0 ? (const void*)mag0 : (const void*)(cw + cw_off[r]);
     u64* nd = (u64*)(nodes + node_off[r]);
     MZK_TRY(merkle_hash_levels(0, field_id, leaves, nullptr, len, nd, s, r == 0 ? d_neg : nullptr));
     const bool last = r == R - 1;
-    hipLaunchKernelGGL(k_fri_tx_round, dim3(1), dim3(64), 0, s, tx, r, (const u64*)(nd + 4 * (len - 2)), (u64*)(proof + P.off[mzk_tx::SEC_ROOTS] + 32 * (size_t)r),
+    hipLaunchKernelGGL(k_fri_tx_round, dim3(1), dim3(64), 0, s, tx, r, (const u64*)(nd + 4 * (len - 2)), (u64*)(proof + L.off[mzk_tx::SEC_ROOTS] + 32 * (size_t)r),
                        alphas + 4 * r, last ? 0 : 1);
     MZK_HIP(hipGetLastError());
     if (r == 0 && negative) {
-      if (field_id == MZK_FIELD_M128) hipLaunchKernelGGL((k_canonicalize_signed<4>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, (u32*)cw, d_neg, n, field_id);
-      else hipLaunchKernelGGL((k_canonicalize_signed<8>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, (u32*)cw, d_neg, n, field_id);
-      MZK_HIP(hipGetLastError());
+      MZK_TRY(canonicalize_signed(field_id, cw, d_neg, n, s));
     }
     if (last) break;
     MZK_TRY(fri_fold_dev_alpha(field_id, cw + cw_off[r], len, alphas + 4 * r, fc, cw + cw_off[r + 1], s));
     fri_fold_consts_square(field_id, &fc);
   }
   const u32* last_cw = (const u32*)(cw + cw_off[R - 1]);
-  auto sec = [&](int k) { return proof + P.off[k]; };
-  if (field_id == MZK_FIELD_M128)
-    hipLaunchKernelGGL((k_fri_tx_last<4>), dim3(1), dim3(TX_LAST_THREADS), 0, s, (u8*)tx, R, last_cw, (size_t)L.last_len, n / 2, tests,
-                       (u32*)(blk + o_seen), (u64*)sec(mzk_tx::SEC_STATUS), (u64*)sec(mzk_tx::SEC_TOP_INDICES), (u32*)sec(mzk_tx::SEC_LAST_CODEWORD));
-  else
-    hipLaunchKernelGGL((k_fri_tx_last<8>), dim3(1), dim3(TX_LAST_THREADS), 0, s, (u8*)tx, R, last_cw, (size_t)L.last_len, n / 2, tests,
-                       (u32*)(blk + o_seen), (u64*)sec(mzk_tx::SEC_STATUS), (u64*)sec(mzk_tx::SEC_TOP_INDICES), (u32*)sec(mzk_tx::SEC_LAST_CODEWORD));
+  auto sec = [&](int k) { return proof + L.off[k]; };
+  MZK_TRY(MZK_FIELD_LAUNCH(field_id, k_fri_tx_last<P::NW>, dim3(1), dim3(TX_LAST_THREADS), 0, s, (u8*)tx, R, last_cw, (size_t)L.last_len, n / 2, tests, (u32*)(blk + o_seen), (u64*)sec(mzk_tx::SEC_STATUS), (u64*)sec(mzk_tx::SEC_TOP_INDICES), (u32*)sec(mzk_tx::SEC_LAST_CODEWORD)));
   MZK_HIP(hipGetLastError());
   const size_t queries = 3 * tests * (size_t)(R - 1);
   if (queries) {
@@ -1656,8 +1646,7 @@ static int fri_prove_impl(int field_id, const void* src, const void* negative, b
     A.values = sec(mzk_tx::SEC_VALUES); A.signs = sec(mzk_tx::SEC_SIGNS); A.paths = sec(mzk_tx::SEC_PATHS); A.lens = (u64*)sec(mzk_tx::SEC_PATH_LENS);
     A.n = n; A.tests = tests;
     for (int r = 0; r < 64; r++) { A.cw_off[r] = r < R ? cw_off[r] : 0; A.node_off[r] = r < R ? node_off[r] : 0; }
-    if (field_id == MZK_FIELD_M128) hipLaunchKernelGGL((k_fri_query<4>), dim3((unsigned)queries), dim3(64), 0, s, A);
-    else hipLaunchKernelGGL((k_fri_query<8>), dim3((unsigned)queries), dim3(64), 0, s, A);
+    MZK_TRY(MZK_FIELD_LAUNCH(field_id, k_fri_query<P::NW>, dim3((unsigned)queries), dim3(64), 0, s, A));
     MZK_HIP(hipGetLastError());
   }
   if (on_device) return MZK_OK;

@@ -199,8 +199,6 @@ __global__ __launch_bounds__(256) void k_mp_lincomb(const u32* __restrict__ poly
 }
 
 // ---- host plan -----------------------------------------------------------------------------------------------------------------------
-static bool mp_field_ok(int fid) { return fid == MZK_FIELD_FR || fid == MZK_FIELD_M128; }
-static unsigned mp_max_log(int fid) { return fid == MZK_FIELD_FR ? 28 : 32; }       // mzk.h "Size limits"
 struct MpPlan { size_t n = 0, stride_min = 0; std::vector<size_t> bounds; };
 
 static int mp_monotone(const size_t* off, size_t count, const char* what) {
@@ -225,7 +223,7 @@ static int mp_term_degree(const uint32_t* k, size_t nv, const size_t* point_offs
   return MZK_OK;
 }
 static int mp_plan(int fid, const uint32_t* term_exps, const size_t* term_offsets, size_t nc, size_t nv, const size_t* point_offsets, MpPlan* pl) {
-  if (!mp_field_ok(fid)) { set_error("mpoly_compose: bad field id %d", fid); return MZK_E_ARG; }
+  MZK_TRY(field_check(fid, "mpoly_compose"));
   if (nv > (size_t)MP_MAX_VARS) { set_error("mpoly_compose: %zu variables (at most %d)", nv, MP_MAX_VARS); return MZK_E_ARG; }
   if (nc == 0) return MZK_OK;
   if (!term_offsets || (nv && !point_offsets)) { set_error("mpoly_compose: null pointer"); return MZK_E_ARG; }
@@ -245,8 +243,8 @@ static int mp_plan(int fid, const uint32_t* term_exps, const size_t* term_offset
   pl->stride_min = *std::max_element(pl->bounds.begin(), pl->bounds.end());
   unsigned lg = 0;
   while (lg < 64 && ((size_t)1 << lg) < pl->stride_min) lg++;
-  if (lg > mp_max_log(fid)) {
-    set_error("mpoly_compose: degree bound %zu needs a transform of 2^%u points (at most 2^%u over this field)", pl->stride_min - 1, lg, mp_max_log(fid));
+  if (lg > field_max_log(fid)) {
+    set_error("mpoly_compose: degree bound %zu needs a transform of 2^%u points (at most 2^%u over this field)", pl->stride_min - 1, lg, field_max_log(fid));
     return MZK_E_LENGTH;
   }
   pl->n = (size_t)1 << lg;
@@ -397,15 +395,15 @@ static int mp_compose_dev(int fid, const uint64_t* term_coefs, const uint32_t* t
 // v R mod p, R = 2^(29 L), as 32-bit words
 static void mp_mont_words(int fid, const uint64_t* v, u32* out8) {
   const HostField* hf = host_field(fid);
-  uint64_t two[4] = {2, 0, 0, 0}, r[4] = {0, 0, 0, 0}, t[4] = {0, 0, 0, 0};
-  h_powmod_u64(hf, r, two, 29 * (fid == MZK_FIELD_M128 ? M128Params::L : FrParams::L));
+  uint64_t r[4] = {0, 0, 0, 0}, t[4] = {0, 0, 0, 0};
+  h_rmod(hf, r);
   h_mulmod(hf, t, v, r);
   for (int i = 0; i < 8; i++) out8[i] = i < 2 * hf->nl ? (u32)(t[i / 2] >> (32 * (i & 1))) : 0u;
 }
 
 static int mp_lincomb_check(int fid, const size_t* offsets, size_t count, const uint64_t* weights, const size_t* shifts, size_t out_cap, const void* out,
                             const size_t* out_len) {
-  if (!mp_field_ok(fid)) { set_error("poly_lincomb: bad field id %d", fid); return MZK_E_ARG; }
+  MZK_TRY(field_check(fid, "poly_lincomb"));
   if (!out_len || (out_cap && !out) || (count && (!offsets || !weights || !shifts))) { set_error("poly_lincomb: null pointer"); return MZK_E_ARG; }
   if (count >= ((size_t)1 << 31)) { set_error("poly_lincomb: %zu polynomials (at most 2^31 - 1)", count); return MZK_E_LENGTH; }
   const HostField* hf = host_field(fid);
@@ -472,11 +470,11 @@ int mzk_mpoly_compose_dev(int field_id, const uint64_t* term_coefs, const uint32
                           size_t n_vars, const void* d_point, const size_t* point_offsets, void* d_out, size_t out_stride, size_t* out_lens,
                           void* stream) {
   MZK_ENTER();
-  if (!mp_field_ok(field_id)) { set_error("mpoly_compose: bad field id %d", field_id); return MZK_E_ARG; }
+  MZK_TRY(field_check(field_id, "mpoly_compose"));
   WsGuard wsg((hipStream_t)stream);
-  return field_id == MZK_FIELD_M128
-             ? mp_compose_dev<M128Params>(field_id, term_coefs, term_exps, term_offsets, n_constraints, n_vars, d_point, point_offsets, d_out, out_stride, out_lens, (hipStream_t)stream)
-             : mp_compose_dev<FrParams>(field_id, term_coefs, term_exps, term_offsets, n_constraints, n_vars, d_point, point_offsets, d_out, out_stride, out_lens, (hipStream_t)stream);
+  return with_field(field_id, [&](auto tag) {
+    return mp_compose_dev<typename decltype(tag)::P>(field_id, term_coefs, term_exps, term_offsets, n_constraints, n_vars, d_point, point_offsets, d_out, out_stride, out_lens, (hipStream_t)stream);
+  });
 }
 
 int mzk_mpoly_compose(int field_id, const uint64_t* term_coefs, const uint32_t* term_exps, const size_t* term_offsets, size_t n_constraints,
@@ -501,9 +499,9 @@ int mzk_mpoly_compose(int field_id, const uint64_t* term_coefs, const uint32_t* 
   std::vector<size_t> rel(n_vars + 1, 0);
   for (size_t i = 0; i <= n_vars && n_vars; i++) rel[i] = point_offsets[i] - p0;
   if (np) MZK_HIP(hipMemcpyAsync(d_p, point + p0 * hf->nl, np * esz, hipMemcpyHostToDevice, s));
-  const int rc = field_id == MZK_FIELD_M128
-                     ? mp_compose_dev<M128Params>(field_id, term_coefs, term_exps, term_offsets, n_constraints, n_vars, d_p, rel.data(), d_o, out_stride, out_lens, s)
-                     : mp_compose_dev<FrParams>(field_id, term_coefs, term_exps, term_offsets, n_constraints, n_vars, d_p, rel.data(), d_o, out_stride, out_lens, s);
+  const int rc = with_field(field_id, [&](auto tag) {
+    return mp_compose_dev<typename decltype(tag)::P>(field_id, term_coefs, term_exps, term_offsets, n_constraints, n_vars, d_p, rel.data(), d_o, out_stride, out_lens, s);
+  });
   if (rc != MZK_OK) { (void)hipStreamSynchronize(s); return rc; }
   if (out_stride == 0) return MZK_OK;
   return d2h_sync(out, d_o, n_constraints * out_stride * esz, s);
@@ -515,8 +513,7 @@ int mzk_poly_lincomb_dev(int field_id, const void* d_polys, const size_t* offset
   MZK_TRY(mp_lincomb_check(field_id, offsets, count, weights, shifts, out_cap, d_out, out_len));
   if (count && offsets[count] > offsets[0] && !d_polys) { set_error("poly_lincomb: null pointer"); return MZK_E_ARG; }
   WsGuard wsg((hipStream_t)stream);
-  return field_id == MZK_FIELD_M128 ? mp_lincomb_dev<M128Params>(field_id, d_polys, offsets, count, weights, shifts, d_out, out_cap, out_len, (hipStream_t)stream)
-                                    : mp_lincomb_dev<FrParams>(field_id, d_polys, offsets, count, weights, shifts, d_out, out_cap, out_len, (hipStream_t)stream);
+  return with_field(field_id, [&](auto tag) { return mp_lincomb_dev<typename decltype(tag)::P>(field_id, d_polys, offsets, count, weights, shifts, d_out, out_cap, out_len, (hipStream_t)stream); });
 }
 
 int mzk_poly_lincomb(int field_id, const uint64_t* polys, const size_t* offsets, size_t count, const uint64_t* weights, const size_t* shifts,
@@ -536,8 +533,7 @@ int mzk_poly_lincomb(int field_id, const uint64_t* polys, const size_t* offsets,
   std::vector<size_t> rel(count + 1, 0);
   for (size_t i = 0; i <= count; i++) rel[i] = count ? offsets[i] - p0 : 0;
   if (np) MZK_HIP(hipMemcpyAsync(d_p, polys + p0 * hf->nl, np * esz, hipMemcpyHostToDevice, s));
-  const int rc = field_id == MZK_FIELD_M128 ? mp_lincomb_dev<M128Params>(field_id, d_p, rel.data(), count, weights, shifts, d_o, out_cap, out_len, s)
-                                            : mp_lincomb_dev<FrParams>(field_id, d_p, rel.data(), count, weights, shifts, d_o, out_cap, out_len, s);
+  const int rc = with_field(field_id, [&](auto tag) { return mp_lincomb_dev<typename decltype(tag)::P>(field_id, d_p, rel.data(), count, weights, shifts, d_o, out_cap, out_len, s); });
   if (rc != MZK_OK) { (void)hipStreamSynchronize(s); return rc; }
   if (out_cap == 0) return MZK_OK;
   return d2h_sync(out, d_o, out_cap * esz, s);

@@ -2294,12 +2294,12 @@ __global__ void k_synth_g1(u64 seed, size_t n, u32* __restrict__ out) {
 int synth_field_impl(int fid, u64 seed, size_t n, void* d_out, hipStream_t s) {
   if (n == 0) return MZK_OK;
   const unsigned blocks = (unsigned)((n + 255) / 256);
-  if (fid == MZK_FIELD_FR) hipLaunchKernelGGL((k_synth_field<FrParams>), dim3(blocks), dim3(256), 0, s, seed, n, (u32*)d_out);
-  else if (fid == MZK_FIELD_FQ) hipLaunchKernelGGL((k_synth_field<FqParams>), dim3(blocks), dim3(256), 0, s, seed, n, (u32*)d_out);
-  else if (fid == MZK_FIELD_M128) hipLaunchKernelGGL((k_synth_field<M128Params>), dim3(blocks), dim3(256), 0, s, seed, n, (u32*)d_out);
-  else { set_error("synth: bad field id %d", fid); return MZK_E_ARG; }
-  MZK_HIP(hipGetLastError());
-  return MZK_OK;
+  MZK_TRY(field_check(fid, "synth", true));
+  return with_field3(fid, [&](auto tag) -> int {
+    hipLaunchKernelGGL((k_synth_field<typename decltype(tag)::P>), dim3(blocks), dim3(256), 0, s, seed, n, (u32*)d_out);
+    MZK_HIP(hipGetLastError());
+    return MZK_OK;
+  });
 }
 int synth_g1_impl(u64 seed, size_t n, void* d_out, hipStream_t s) {
   if (n == 0) return MZK_OK;

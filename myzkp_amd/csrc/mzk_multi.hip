@@ -115,7 +115,7 @@ static int exchange(Exchange& x, void* const* src, void* const* dst, bool wait_e
   return MZK_OK;
 }
 static int ntt_multi_impl(int fid, const uint64_t* root, const void* const* in, void* const* out, size_t n, int inverse, int layout_in, int layout_out) {
-  if (fid != MZK_FIELD_FR && fid != MZK_FIELD_M128) { set_error("ntt_multi: field id %d has no NTT on this path", fid); return MZK_E_ARG; }
+  MZK_TRY(field_check_ntt(fid, "ntt_multi"));
   if (n == 0) return MZK_OK;
   if (n & (n - 1)) { set_error("cannot compute ntt of non-power-of-two sequence"); return MZK_E_NOT_POW2; }
   if (!root || !in || !out) { set_error("ntt_multi: null pointer"); return MZK_E_ARG; }
@@ -367,7 +367,7 @@ int mzk_ntt_multi(int field_id, const uint64_t* root, const uint64_t* in, uint64
   MZK_ENTER();
   if (n == 0) return MZK_OK;
   if (!in || !out) { set_error("ntt_multi: null pointer"); return MZK_E_ARG; }
-  if (field_id != MZK_FIELD_FR && field_id != MZK_FIELD_M128) { set_error("ntt_multi: field id %d has no NTT on this path", field_id); return MZK_E_ARG; }
+  MZK_TRY(field_check_ntt(field_id, "ntt_multi"));
   const int W = ctx_count();
   if (n % (size_t)W) { set_error("ntt_multi: %d contexts do not divide n", W); return MZK_E_ARG; }
   const size_t esz = field_bytes(field_id), m = n / (size_t)W;

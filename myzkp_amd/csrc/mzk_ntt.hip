@@ -1032,16 +1032,14 @@ static int get_plan(int fid, unsigned logn, bool inverse, const uint64_t* root, 
   if (pl->li.nlev == 1 && !fold_is_one) {
     // single pass: no inter-pass table to fold into -> explicit scale in the last pass (Montgomery form
     // computed on the host: fold * R mod p via mulmod with R mod p)
-    uint64_t r_mod_p[4] = {0, 0, 0, 0}, two[4] = {2, 0, 0, 0};
-    // R = 2^(29 L): square-and-multiply on the host
-    h_powmod_u64(hf, r_mod_p, two, (uint64_t)(29 * (fid == MZK_FIELD_M128 ? 5 : 9)));
+    uint64_t r_mod_p[4] = {0, 0, 0, 0};
+    h_rmod(hf, r_mod_p);
     uint64_t m[4];
     h_mulmod(hf, m, fold, r_mod_p);
     to_words(m, hf->nl, &pl->last_scale);
     pl->has_last_scale = 1;
   }
-  int rc = (fid == MZK_FIELD_M128) ? build_tables<M128Params>(pl, eff_root, fold, s)
-                                   : build_tables<FrParams>(pl, eff_root, fold, s);
+  const int rc = with_field(fid, [&](auto tag) { return build_tables<typename decltype(tag)::P>(pl, eff_root, fold, s); });
   if (rc != MZK_OK) { free_plan(pl); return rc; }
   if (g_plans.size() >= MAX_PLANS) {
     size_t victim = 0;
@@ -1135,7 +1133,7 @@ static unsigned ilog2(size_t n) { unsigned l = 0; while (((size_t)1 << l) < n) l
 // products to fold constants); nullptr = 1.
 int ntt_dev_impl(int fid, const uint64_t* root_host, const void* d_in, void* d_out, size_t n, int inverse,
                  const uint64_t* extra_scale_host, hipStream_t s) {
-  if (fid != MZK_FIELD_FR && fid != MZK_FIELD_M128) { set_error("ntt: field id %d has no NTT on this path", fid); return MZK_E_ARG; }
+  MZK_TRY(field_check_ntt(fid, "ntt"));
   if (n == 0) return MZK_OK;  // empty Vec in, empty Vec out (ntt.rs:12-14 `len <= 1`; len-1 underflow aside)
   if (!is_pow2(n)) { set_error("cannot compute ntt of non-power-of-two sequence"); return MZK_E_NOT_POW2; }
   if (!d_in || !d_out || (!root_host && n > 1)) { set_error("ntt: null pointer"); return MZK_E_ARG; }
@@ -1149,15 +1147,14 @@ int ntt_dev_impl(int fid, const uint64_t* root_host, const void* d_in, void* d_o
   if (ilog2(n) > 32) { set_error("ntt: n too large"); return MZK_E_ARG; }
   NttPlan* pl = nullptr;
   MZK_TRY(get_plan(fid, ilog2(n), inverse != 0, root_host, extra_scale_host, s, &pl));
-  if (fid == MZK_FIELD_M128) return run_plan<M128Params>(pl, (const u32*)d_in, (u32*)d_out, s);
-  return run_plan<FrParams>(pl, (const u32*)d_in, (u32*)d_out, s);
+  return with_field(fid, [&](auto tag) { return run_plan<typename decltype(tag)::P>(pl, (const u32*)d_in, (u32*)d_out, s); });
 }
 
 // `batch` transforms of n points each, stored back to back (in place allowed); same root for all
 int ntt_batch_dev_impl(int fid, const uint64_t* root_host, const void* d_in, void* d_out, size_t n, size_t batch, int inverse, hipStream_t s) {
   if (batch == 0 || n == 0) return MZK_OK;
   if (batch == 1) return ntt_dev_impl(fid, root_host, d_in, d_out, n, inverse, nullptr, s);
-  if (fid != MZK_FIELD_FR && fid != MZK_FIELD_M128) { set_error("ntt: field id %d has no NTT on this path", fid); return MZK_E_ARG; }
+  MZK_TRY(field_check_ntt(fid, "ntt"));
   if (!is_pow2(n)) { set_error("cannot compute ntt of non-power-of-two sequence"); return MZK_E_NOT_POW2; }
   if (!d_in || !d_out || (!root_host && n > 1)) { set_error("ntt: null pointer"); return MZK_E_ARG; }
   if (n > 1 && !h_is_canonical(host_field(fid), root_host)) { set_error("ntt: root not canonical"); return MZK_E_RANGE; }
@@ -1168,8 +1165,7 @@ int ntt_batch_dev_impl(int fid, const uint64_t* root_host, const void* d_in, voi
   }
   NttPlan* pl = nullptr;
   MZK_TRY(get_plan(fid, ilog2(n), inverse != 0, root_host, nullptr, s, &pl, batch));
-  if (fid == MZK_FIELD_M128) return run_plan<M128Params>(pl, (const u32*)d_in, (u32*)d_out, s, nullptr, batch);
-  return run_plan<FrParams>(pl, (const u32*)d_in, (u32*)d_out, s, nullptr, batch);
+  return with_field(fid, [&](auto tag) { return run_plan<typename decltype(tag)::P>(pl, (const u32*)d_in, (u32*)d_out, s, nullptr, batch); });
 }
 
 template <class P, int LGW>
@@ -1191,7 +1187,7 @@ static int columns_dispatch(const NttPlan* pl, unsigned lgw, const void* d_in, v
 }
 // cols transforms of n_points (2, 4, 8 or 16) each, column-major; the same root checks and inverse convention as ntt_dev_impl
 int ntt_columns_dev_impl(int fid, const uint64_t* root_host, const void* d_in, void* d_out, size_t n_points, size_t cols, int inverse, hipStream_t s) {
-  if (fid != MZK_FIELD_FR && fid != MZK_FIELD_M128) { set_error("ntt_columns: field id %d has no NTT on this path", fid); return MZK_E_ARG; }
+  MZK_TRY(field_check_ntt(fid, "ntt_columns"));
   if (cols == 0 || n_points == 0) return MZK_OK;
   if (!is_pow2(n_points)) { set_error("cannot compute ntt of non-power-of-two sequence"); return MZK_E_NOT_POW2; }
   if (n_points < 2 || n_points > 16) { set_error("ntt_columns: 2..16 points per transform"); return MZK_E_ARG; }
@@ -1200,22 +1196,20 @@ int ntt_columns_dev_impl(int fid, const uint64_t* root_host, const void* d_in, v
   if (!h_is_canonical(host_field(fid), root_host)) { set_error("ntt: root not canonical"); return MZK_E_RANGE; }
   NttPlan* pl = nullptr;
   MZK_TRY(get_plan(fid, ilog2(n_points), inverse != 0, root_host, nullptr, s, &pl));
-  if (fid == MZK_FIELD_M128) return columns_dispatch<M128Params>(pl, ilog2(n_points), d_in, d_out, cols, s);
-  return columns_dispatch<FrParams>(pl, ilog2(n_points), d_in, d_out, cols, s);
+  return with_field(fid, [&](auto tag) { return columns_dispatch<typename decltype(tag)::P>(pl, ilog2(n_points), d_in, d_out, cols, s); });
 }
 
 int transpose_elems_dev_impl(int fid, const void* d_in, void* d_out, size_t rows, size_t cols, hipStream_t s) {
   const size_t total = rows * cols;
   if (total == 0) return MZK_OK;
   const unsigned blocks = (unsigned)((total + 255) / 256);
-  if (fid == MZK_FIELD_M128) hipLaunchKernelGGL((k_transpose_elems<4>), dim3(blocks), dim3(256), 0, s, (const u32*)d_in, (u32*)d_out, rows, cols);
-  else hipLaunchKernelGGL((k_transpose_elems<8>), dim3(blocks), dim3(256), 0, s, (const u32*)d_in, (u32*)d_out, rows, cols);
+  MZK_TRY(MZK_FIELD_LAUNCH(fid, k_transpose_elems<P::NW>, dim3(blocks), dim3(256), 0, s, (const u32*)d_in, (u32*)d_out, rows, cols));
   MZK_HIP(hipGetLastError());
   return MZK_OK;
 }
 
 int poly_scale_dev_impl(int fid, const void* d_in, size_t n, const uint64_t* ratio_host, const uint64_t* lead_host, void* d_out, hipStream_t s) {
-  if (fid != MZK_FIELD_FR && fid != MZK_FIELD_M128) { set_error("poly_scale: bad field id %d", fid); return MZK_E_ARG; }
+  MZK_TRY(field_check(fid, "poly_scale"));
   if (n == 0) return MZK_OK;
   if (!d_in || !d_out || !ratio_host) { set_error("poly_scale: null pointer"); return MZK_E_ARG; }
   const HostField* hf = host_field(fid);
@@ -1226,10 +1220,7 @@ int poly_scale_dev_impl(int fid, const void* d_in, size_t n, const uint64_t* rat
   to_words(lead_host ? lead_host : one, hf->nl, &lw);
   const size_t chunks = (n + GEN_CHUNK - 1) / GEN_CHUNK;
   const unsigned blocks = (unsigned)((chunks + 255) / 256);
-  if (fid == MZK_FIELD_M128)
-    hipLaunchKernelGGL((k_poly_scale<M128Params>), dim3(blocks), dim3(256), 0, s, (const u32*)d_in, n, rw, lw, (u32*)d_out);
-  else
-    hipLaunchKernelGGL((k_poly_scale<FrParams>), dim3(blocks), dim3(256), 0, s, (const u32*)d_in, n, rw, lw, (u32*)d_out);
+  MZK_TRY(MZK_FIELD_LAUNCH(fid, k_poly_scale<P>, dim3(blocks), dim3(256), 0, s, (const u32*)d_in, n, rw, lw, (u32*)d_out));
   MZK_HIP(hipGetLastError());
   return MZK_OK;
 }
@@ -1237,7 +1228,7 @@ int poly_scale_dev_impl(int fid, const void* d_in, size_t n, const uint64_t* rat
 int coset_lde_dev_impl(int fid, const void* d_coef, size_t n_coef, const uint64_t* offset_host,
                        const uint64_t* generator_host, void* d_out, size_t order, hipStream_t s, size_t batch) {
   if (batch == 0) return MZK_OK;
-  if (fid != MZK_FIELD_FR && fid != MZK_FIELD_M128) { set_error("coset_lde: bad field id %d", fid); return MZK_E_ARG; }
+  MZK_TRY(field_check(fid, "coset_lde"));
   if (n_coef > order) { set_error("attempt to subtract with overflow (order - polynomial.coef.len())"); return MZK_E_LENGTH; }
   if (order == 0) return MZK_OK;
   if (!is_pow2(order)) { set_error("cannot compute ntt of non-power-of-two sequence"); return MZK_E_NOT_POW2; }
@@ -1269,13 +1260,8 @@ int coset_lde_dev_impl(int fid, const void* d_coef, size_t n_coef, const uint64_
       // a regrown slot or another size invalidates the pointers: wait for earlier users of the old contents
       prof_begin(s, MZK_PH_NTT_PRESCALE);
       const unsigned bc = (unsigned)((ncol + GEN_CHUNK * 64 - 1) / (GEN_CHUNK * 64)), br = (unsigned)((nrow + GEN_CHUNK * 64 - 1) / (GEN_CHUNK * 64));
-      if (fid == MZK_FIELD_M128) {
-        hipLaunchKernelGGL((k_gen_pow_table<M128Params>), dim3(bc), dim3(64), 0, s, offw, (uint64_t)1, ncol, pre_col);
-        hipLaunchKernelGGL((k_gen_pow_table<M128Params>), dim3(br), dim3(64), 0, s, offw, (uint64_t)ncol, nrow, pre_row);
-      } else {
-        hipLaunchKernelGGL((k_gen_pow_table<FrParams>), dim3(bc), dim3(64), 0, s, offw, (uint64_t)1, ncol, pre_col);
-        hipLaunchKernelGGL((k_gen_pow_table<FrParams>), dim3(br), dim3(64), 0, s, offw, (uint64_t)ncol, nrow, pre_row);
-      }
+      MZK_TRY(MZK_FIELD_LAUNCH(fid, k_gen_pow_table<P>, dim3(bc), dim3(64), 0, s, offw, (uint64_t)1, ncol, pre_col));
+      MZK_TRY(MZK_FIELD_LAUNCH(fid, k_gen_pow_table<P>, dim3(br), dim3(64), 0, s, offw, (uint64_t)ncol, nrow, pre_row));
       MZK_HIP(hipGetLastError());
       prof_end(s, MZK_PH_NTT_PRESCALE);
       memset(ce.off, 0, sizeof ce.off);
@@ -1286,18 +1272,14 @@ int coset_lde_dev_impl(int fid, const void* d_coef, size_t n_coef, const uint64_
       MZK_HIP(hipStreamWaitEvent(s, ce.ready, 0));
     }
     const PreArgs pre{(const u32*)d_coef, n_coef, pre_row, pre_col};
-    if (fid == MZK_FIELD_M128) return run_plan<M128Params>(pl, (const u32*)d_coef, (u32*)d_out, s, &pre, batch);
-    return run_plan<FrParams>(pl, (const u32*)d_coef, (u32*)d_out, s, &pre, batch);
+    return with_field(fid, [&](auto tag) { return run_plan<typename decltype(tag)::P>(pl, (const u32*)d_coef, (u32*)d_out, s, &pre, batch); });
   }
   void* scaled = nullptr;
   MZK_TRY(ws_get(WS_NTT_IO_A, batch * order * field_bytes(fid), &scaled));
   const size_t chunks_per = (order + GEN_CHUNK - 1) / GEN_CHUNK;
   const unsigned blocks = (unsigned)((chunks_per * batch + 255) / 256);
   prof_begin(s, MZK_PH_NTT_PRESCALE);
-  if (fid == MZK_FIELD_M128)
-    hipLaunchKernelGGL((k_coset_scale_pad<M128Params>), dim3(blocks), dim3(256), 0, s, (const u32*)d_coef, n_coef, offw, (u32*)scaled, order, chunks_per, batch);
-  else
-    hipLaunchKernelGGL((k_coset_scale_pad<FrParams>), dim3(blocks), dim3(256), 0, s, (const u32*)d_coef, n_coef, offw, (u32*)scaled, order, chunks_per, batch);
+  MZK_TRY(MZK_FIELD_LAUNCH(fid, k_coset_scale_pad<P>, dim3(blocks), dim3(256), 0, s, (const u32*)d_coef, n_coef, offw, (u32*)scaled, order, chunks_per, batch));
   MZK_HIP(hipGetLastError());
   prof_end(s, MZK_PH_NTT_PRESCALE);
   return ntt_batch_dev_impl(fid, generator_host, scaled, d_out, order, batch, 0, s);
@@ -1331,7 +1313,7 @@ int fri_fold_consts(int fid, const uint64_t* offset, const uint64_t* omega, FriF
   h_invmod(hf, fc->half, two);
   h_invmod(hf, fc->oinv, offset);
   h_invmod(hf, fc->winv, omega);
-  h_powmod_u64(hf, fc->rmod, two, (uint64_t)(29 * (fid == MZK_FIELD_M128 ? 5 : 9)));
+  h_rmod(hf, fc->rmod);
   return MZK_OK;
 }
 void fri_fold_consts_square(int fid, FriFoldConsts* fc) {
@@ -1339,23 +1321,32 @@ void fri_fold_consts_square(int fid, FriFoldConsts* fc) {
   h_mulmod(hf, fc->oinv, fc->oinv, fc->oinv);
   h_mulmod(hf, fc->winv, fc->winv, fc->winv);
 }
+// What both fold kernels take besides r_0: omega^-1 and 2^-1 in Montgomery form (x R mod p), and the launch geometry.
+// Consecutive i per lane: a long walk amortises the lane's omega^-i0 power where there are lanes to spare; the late rounds
+// of a FRI commit are short codewords on an empty GPU, where the walk itself is the latency (16 steps: 18 us; one: 6 us)
+struct FoldLaunch { Words8 winvw, halfw; int per_lane; unsigned blocks; };
+static FoldLaunch fold_launch(const HostField* hf, const FriFoldConsts& fc, size_t h) {
+  FoldLaunch fl;
+  uint64_t winv[4], halfv[4];
+  h_mulmod(hf, winv, fc.winv, fc.rmod); h_mulmod(hf, halfv, fc.half, fc.rmod);
+  to_words(winv, hf->nl, &fl.winvw); to_words(halfv, hf->nl, &fl.halfw);
+  fl.per_lane = h >= ((size_t)1 << 20) ? GEN_CHUNK : (h >= ((size_t)1 << 16) ? 4 : 1);
+  const size_t chunks = (h + (size_t)fl.per_lane - 1) / (size_t)fl.per_lane;
+  fl.blocks = (unsigned)((chunks + 127) / 128);
+  return fl;
+}
 int fri_fold_dev_consts(int fid, const void* d_cw, size_t n, const uint64_t* alpha, const FriFoldConsts& fc, void* d_out, hipStream_t s) {
   const size_t h = n / 2;
   if (h == 0) return MZK_OK;
   const HostField* hf = host_field(fid);
-  uint64_t r0[4], winv[4], halfv[4];
+  uint64_t r0[4];
   h_mulmod(hf, r0, fc.half, alpha);
   h_mulmod(hf, r0, r0, fc.oinv);
-  h_mulmod(hf, r0, r0, fc.rmod); h_mulmod(hf, winv, fc.winv, fc.rmod); h_mulmod(hf, halfv, fc.half, fc.rmod);
-  Words8 r0w, winvw, halfw;
-  to_words(r0, hf->nl, &r0w); to_words(winv, hf->nl, &winvw); to_words(halfv, hf->nl, &halfw);
-  const int per_lane = h >= ((size_t)1 << 20) ? GEN_CHUNK : (h >= ((size_t)1 << 16) ? 4 : 1);
-  const size_t chunks = (h + (size_t)per_lane - 1) / (size_t)per_lane;
-  const unsigned blocks = (unsigned)((chunks + 127) / 128);
-  if (fid == MZK_FIELD_M128)
-    hipLaunchKernelGGL((k_fri_fold<M128Params>), dim3(blocks), dim3(128), 0, s, (const u32*)d_cw, h, r0w, winvw, halfw, (u32*)d_out, per_lane);
-  else
-    hipLaunchKernelGGL((k_fri_fold<FrParams>), dim3(blocks), dim3(128), 0, s, (const u32*)d_cw, h, r0w, winvw, halfw, (u32*)d_out, per_lane);
+  h_mulmod(hf, r0, r0, fc.rmod);
+  Words8 r0w;
+  to_words(r0, hf->nl, &r0w);
+  const FoldLaunch fl = fold_launch(hf, fc, h);
+  MZK_TRY(MZK_FIELD_LAUNCH(fid, k_fri_fold<P>, dim3(fl.blocks), dim3(128), 0, s, (const u32*)d_cw, h, r0w, fl.winvw, fl.halfw, (u32*)d_out, fl.per_lane));
   MZK_HIP(hipGetLastError());
   return MZK_OK;
 }
@@ -1383,52 +1374,26 @@ int fri_fold_dev_alpha(int fid, const void* d_cw, size_t n, const uint64_t* d_al
   const size_t h = n / 2;
   if (h == 0) return MZK_OK;
   const HostField* hf = host_field(fid);
-  uint64_t kv[4], winv[4], halfv[4];
+  uint64_t kv[4];
   h_mulmod(hf, kv, fc.half, fc.oinv);
   h_mulmod(hf, kv, kv, fc.rmod); h_mulmod(hf, kv, kv, fc.rmod);
-  h_mulmod(hf, winv, fc.winv, fc.rmod); h_mulmod(hf, halfv, fc.half, fc.rmod);
-  Words8 kw, winvw, halfw;
-  to_words(kv, hf->nl, &kw); to_words(winv, hf->nl, &winvw); to_words(halfv, hf->nl, &halfw);
-  const int per_lane = h >= ((size_t)1 << 20) ? GEN_CHUNK : (h >= ((size_t)1 << 16) ? 4 : 1);
-  const size_t chunks = (h + (size_t)per_lane - 1) / (size_t)per_lane;
-  const unsigned blocks = (unsigned)((chunks + 127) / 128);
-  if (fid == MZK_FIELD_M128)
-    hipLaunchKernelGGL((k_fri_fold_dev_alpha<M128Params>), dim3(blocks), dim3(128), 0, s, (const u32*)d_cw, h, (const u32*)d_alpha, kw, winvw, halfw, (u32*)d_out, per_lane);
-  else
-    hipLaunchKernelGGL((k_fri_fold_dev_alpha<FrParams>), dim3(blocks), dim3(128), 0, s, (const u32*)d_cw, h, (const u32*)d_alpha, kw, winvw, halfw, (u32*)d_out, per_lane);
+  Words8 kw;
+  to_words(kv, hf->nl, &kw);
+  const FoldLaunch fl = fold_launch(hf, fc, h);
+  MZK_TRY(MZK_FIELD_LAUNCH(fid, k_fri_fold_dev_alpha<P>, dim3(fl.blocks), dim3(128), 0, s, (const u32*)d_cw, h, (const u32*)d_alpha, kw, fl.winvw, fl.halfw, (u32*)d_out, fl.per_lane));
   MZK_HIP(hipGetLastError());
   return MZK_OK;
 }
 int fri_fold_dev_impl(int fid, const void* d_cw, size_t n, const uint64_t* alpha, const uint64_t* offset, const uint64_t* omega,
                       void* d_out, hipStream_t s) {
-  if (fid != MZK_FIELD_FR && fid != MZK_FIELD_M128) { set_error("fri_fold: bad field id %d", fid); return MZK_E_ARG; }
-  const size_t h = n / 2;
-  if (h == 0) return MZK_OK;
+  MZK_TRY(field_check(fid, "fri_fold"));
+  if (n / 2 == 0) return MZK_OK;
   if (!d_cw || !d_out || !alpha || !offset || !omega) { set_error("fri_fold: null pointer"); return MZK_E_ARG; }
   const HostField* hf = host_field(fid);
   if (!h_is_canonical(hf, alpha) || !h_is_canonical(hf, offset) || !h_is_canonical(hf, omega)) { set_error("fri_fold: parameter not canonical"); return MZK_E_RANGE; }
-  // host parameter math: 2^-1, offset^-1, omega^-1, all to Montgomery form (x * R mod p)
-  uint64_t two[4] = {2, 0, 0, 0}, halfv[4], oinv[4], winv[4], r0[4], rmod[4];
-  h_invmod(hf, halfv, two);
-  h_invmod(hf, oinv, offset);
-  h_invmod(hf, winv, omega);
-  h_mulmod(hf, r0, halfv, alpha);
-  h_mulmod(hf, r0, r0, oinv);
-  h_powmod_u64(hf, rmod, two, (uint64_t)(29 * (fid == MZK_FIELD_M128 ? 5 : 9)));
-  h_mulmod(hf, r0, r0, rmod); h_mulmod(hf, winv, winv, rmod); h_mulmod(hf, halfv, halfv, rmod);
-  Words8 r0w, winvw, halfw;
-  to_words(r0, hf->nl, &r0w); to_words(winv, hf->nl, &winvw); to_words(halfv, hf->nl, &halfw);
-  // consecutive i per lane: a long walk amortises the lane's omega^-i0 power where there are lanes to spare; the late rounds
-  // of a FRI commit are short codewords on an empty GPU, where the walk itself is the latency (16 steps: 18 us; one: 6 us)
-  const int per_lane = h >= ((size_t)1 << 20) ? GEN_CHUNK : (h >= ((size_t)1 << 16) ? 4 : 1);
-  const size_t chunks = (h + (size_t)per_lane - 1) / (size_t)per_lane;
-  const unsigned blocks = (unsigned)((chunks + 127) / 128);
-  if (fid == MZK_FIELD_M128)
-    hipLaunchKernelGGL((k_fri_fold<M128Params>), dim3(blocks), dim3(128), 0, s, (const u32*)d_cw, h, r0w, winvw, halfw, (u32*)d_out, per_lane);
-  else
-    hipLaunchKernelGGL((k_fri_fold<FrParams>), dim3(blocks), dim3(128), 0, s, (const u32*)d_cw, h, r0w, winvw, halfw, (u32*)d_out, per_lane);
-  MZK_HIP(hipGetLastError());
-  return MZK_OK;
+  FriFoldConsts fc;
+  MZK_TRY(fri_fold_consts(fid, offset, omega, &fc));
+  return fri_fold_dev_consts(fid, d_cw, n, alpha, fc, d_out, s);
 }
 
 // out[i] = a[i] * b[i]^-1 with inverse(0) = 0 (field.rs:209-232: the extended Euclid returns t = 0 for 0), plain
@@ -1485,13 +1450,7 @@ int coset_divide_dev_impl(int fid, const void* d_lhs, size_t tl, const void* d_r
   MZK_TRY(ws_get(WS_MISC_B, order * esz, &eb));
   MZK_TRY(coset_lde_dev_impl(fid, d_lhs, tl, offset_host, root_host, ea, order, s));
   MZK_TRY(coset_lde_dev_impl(fid, d_rhs, tr, offset_host, root_host, eb, order, s));
-  const size_t lanes = (order + DIV_BATCH - 1) / DIV_BATCH;
-  const unsigned blocks = (unsigned)((lanes + 127) / 128);
-  if (fid == MZK_FIELD_M128)
-    hipLaunchKernelGGL((k_pointwise_div<M128Params>), dim3(blocks), dim3(128), 0, s, (const u32*)ea, (const u32*)eb, (u32*)ea, order);
-  else
-    hipLaunchKernelGGL((k_pointwise_div<FrParams>), dim3(blocks), dim3(128), 0, s, (const u32*)ea, (const u32*)eb, (u32*)ea, order);
-  MZK_HIP(hipGetLastError());
+  MZK_TRY(pointwise_div_dev(fid, ea, eb, ea, order, s));
   MZK_TRY(ntt_dev_impl(fid, root_host, ea, eb, order, 1, nullptr, s));
   uint64_t oinv[4];
   h_invmod(hf, oinv, offset_host);
@@ -1500,10 +1459,7 @@ int coset_divide_dev_impl(int fid, const void* d_lhs, size_t tl, const void* d_r
   const size_t ql = tl - tr + 1;
   const size_t chunks = (ql + GEN_CHUNK - 1) / GEN_CHUNK;
   const unsigned sblocks = (unsigned)((chunks + 255) / 256);
-  if (fid == MZK_FIELD_M128)
-    hipLaunchKernelGGL((k_coset_scale_pad<M128Params>), dim3(sblocks), dim3(256), 0, s, (const u32*)eb, ql, ow, (u32*)d_out, ql, chunks, (size_t)1);
-  else
-    hipLaunchKernelGGL((k_coset_scale_pad<FrParams>), dim3(sblocks), dim3(256), 0, s, (const u32*)eb, ql, ow, (u32*)d_out, ql, chunks, (size_t)1);
+  MZK_TRY(MZK_FIELD_LAUNCH(fid, k_coset_scale_pad<P>, dim3(sblocks), dim3(256), 0, s, (const u32*)eb, ql, ow, (u32*)d_out, ql, chunks, (size_t)1));
   MZK_HIP(hipGetLastError());
   return MZK_OK;
 }
@@ -1568,22 +1524,19 @@ int rows_trimmed_len_dev(int fid, void* d_rows, size_t stride, const size_t* len
   unsigned long long* d_meta;
   MZK_TRY(ws_get(slot, 2 * total * sizeof(unsigned long long), (void**)&d_meta));
   MZK_HIP(hipMemcpyAsync(d_meta, meta.data(), 2 * total * sizeof(unsigned long long), hipMemcpyHostToDevice, s));
-  if (fid == MZK_FIELD_M128)
-    hipLaunchKernelGGL((k_rows_trim<M128Params>), dim3((unsigned)(total * bpr)), dim3(256), 0, s, (u32*)d_rows, stride, count, (const u32*)d_extra, (unsigned)bpr, (const unsigned long long*)d_meta, d_meta + total, clear_to);
-  else
-    hipLaunchKernelGGL((k_rows_trim<FrParams>), dim3((unsigned)(total * bpr)), dim3(256), 0, s, (u32*)d_rows, stride, count, (const u32*)d_extra, (unsigned)bpr, (const unsigned long long*)d_meta, d_meta + total, clear_to);
+  MZK_TRY(MZK_FIELD_LAUNCH(fid, k_rows_trim<P>, dim3((unsigned)(total * bpr)), dim3(256), 0, s, (u32*)d_rows, stride, count, (const u32*)d_extra, (unsigned)bpr, (const unsigned long long*)d_meta, d_meta + total, clear_to));
   if (hipGetLastError() != hipSuccess) { (void)hipStreamSynchronize(s); set_error("trimmed lengths: launch failed"); return MZK_E_HIP; }
   const int rc = d2h_sync(meta.data(), d_meta + total, total * sizeof(unsigned long long), s);
   if (rc != MZK_OK) { (void)hipStreamSynchronize(s); return rc; }
   for (size_t i = 0; i < total; i++) out_lens[i] = (size_t)meta[i];
   return MZK_OK;
 }
-template <class P>
-static void launch_scale_rows(const void* src, size_t src_stride, void* dst, size_t dst_stride, const ScaleRow* d_rows, size_t nrows, const Words8& f, size_t width,
-                              hipStream_t s) {
+static int launch_scale_rows(int fid, const void* src, size_t src_stride, void* dst, size_t dst_stride, const ScaleRow* d_rows, size_t nrows, const Words8& f,
+                             size_t width, hipStream_t s) {
   const size_t chunks_per = (width + GEN_CHUNK - 1) / GEN_CHUNK;
-  hipLaunchKernelGGL((k_scale_rows<P>), dim3((unsigned)((chunks_per * nrows + 255) / 256)), dim3(256), 0, s, (const u32*)src, src_stride, (u32*)dst, dst_stride,
-                     d_rows, nrows, f, width, chunks_per);
+  MZK_TRY(MZK_FIELD_LAUNCH(fid, k_scale_rows<P>, dim3((unsigned)((chunks_per * nrows + 255) / 256)), dim3(256), 0, s, (const u32*)src, src_stride, (u32*)dst, dst_stride, d_rows, nrows, f, width, chunks_per));
+  MZK_HIP(hipGetLastError());
+  return MZK_OK;
 }
 int coset_divide_rows_dev_impl(int fid, const void* d_lhs, size_t lhs_stride, const CdRow* rows, size_t nrows, const void* d_rhs, size_t tr,
                                const uint64_t* offset_host, const uint64_t* root_host, size_t order, void* d_out, size_t out_stride, hipStream_t s) {
@@ -1607,27 +1560,17 @@ int coset_divide_rows_dev_impl(int fid, const void* d_lhs, size_t lhs_stride, co
   h_invmod(hf, oinv, offset_host);
   to_words(offset_host, hf->nl, &fw);
   to_words(oinv, hf->nl, &bw);
-  if (fid == MZK_FIELD_M128) launch_scale_rows<M128Params>(d_lhs, lhs_stride, ea, order, d_tab, nrows, fw, order, s);
-  else launch_scale_rows<FrParams>(d_lhs, lhs_stride, ea, order, d_tab, nrows, fw, order, s);
-  MZK_HIP(hipGetLastError());
+  MZK_TRY(launch_scale_rows(fid, d_lhs, lhs_stride, ea, order, d_tab, nrows, fw, order, s));
   MZK_TRY(ntt_batch_dev_impl(fid, root_host, ea, ea, order, nrows, 0, s));
   MZK_TRY(coset_lde_dev_impl(fid, d_rhs, tr, offset_host, root_host, eb, order, s));
   MZK_TRY(pointwise_div_shared_dev(fid, ea, order, eb, ea, order, order, nrows, s));      // one inversion chain serves every row
   MZK_TRY(ntt_batch_dev_impl(fid, root_host, ea, ea, order, nrows, 1, s));
-  if (fid == MZK_FIELD_M128) launch_scale_rows<M128Params>(ea, order, d_out, out_stride, d_tab + nrows, nrows, bw, out_stride, s);
-  else launch_scale_rows<FrParams>(ea, order, d_out, out_stride, d_tab + nrows, nrows, bw, out_stride, s);
-  MZK_HIP(hipGetLastError());
-  return MZK_OK;
+  return launch_scale_rows(fid, ea, order, d_out, out_stride, d_tab + nrows, nrows, bw, out_stride, s);
 }
 
 // out[i] = a[i] / b[i] with inverse(0) = 0 (field.rs:209-232)
 int pointwise_div_dev(int fid, const void* d_a, const void* d_b, void* d_out, size_t n, hipStream_t s) {
-  if (n == 0) return MZK_OK;
-  const unsigned blocks = (unsigned)(((n + DIV_BATCH - 1) / DIV_BATCH + 127) / 128);
-  if (fid == MZK_FIELD_M128) hipLaunchKernelGGL((k_pointwise_div<M128Params>), dim3(blocks), dim3(128), 0, s, (const u32*)d_a, (const u32*)d_b, (u32*)d_out, n);
-  else hipLaunchKernelGGL((k_pointwise_div<FrParams>), dim3(blocks), dim3(128), 0, s, (const u32*)d_a, (const u32*)d_b, (u32*)d_out, n);
-  MZK_HIP(hipGetLastError());
-  return MZK_OK;
+  return pointwise_div_shared_dev(fid, d_a, 0, d_b, d_out, 0, n, 1, s);
 }
 // out[r * out_stride + i] = a[r * a_stride + i] * b[i]: `regs` vectors times ONE vector (the interpolation plan keeps 1 / Z'(d_i), so a
 // call multiplies where it used to divide: the shared inversion chain was 0.18 ms of a 1.5-ms interpolation)
@@ -1642,8 +1585,7 @@ __global__ __launch_bounds__(256) void k_pointwise_mul_shared(const u32* __restr
 int pointwise_mul_shared_dev(int fid, const void* d_a, size_t a_stride, const void* d_b, void* d_out, size_t out_stride, size_t n, size_t regs, hipStream_t s) {
   if (n == 0 || regs == 0) return MZK_OK;
   const unsigned blocks = (unsigned)((n + 255) / 256);
-  if (fid == MZK_FIELD_M128) hipLaunchKernelGGL((k_pointwise_mul_shared<M128Params>), dim3(blocks), dim3(256), 0, s, (const u32*)d_a, (const u32*)d_b, (u32*)d_out, n, regs, a_stride, out_stride);
-  else hipLaunchKernelGGL((k_pointwise_mul_shared<FrParams>), dim3(blocks), dim3(256), 0, s, (const u32*)d_a, (const u32*)d_b, (u32*)d_out, n, regs, a_stride, out_stride);
+  MZK_TRY(MZK_FIELD_LAUNCH(fid, k_pointwise_mul_shared<P>, dim3(blocks), dim3(256), 0, s, (const u32*)d_a, (const u32*)d_b, (u32*)d_out, n, regs, a_stride, out_stride));
   MZK_HIP(hipGetLastError());
   return MZK_OK;
 }
@@ -1651,18 +1593,14 @@ int pointwise_mul_shared_dev(int fid, const void* d_a, size_t a_stride, const vo
 int pointwise_div_shared_dev(int fid, const void* d_a, size_t a_stride, const void* d_b, void* d_out, size_t out_stride, size_t n, size_t regs, hipStream_t s) {
   if (n == 0 || regs == 0) return MZK_OK;
   const unsigned blocks = (unsigned)(((n + DIV_BATCH - 1) / DIV_BATCH + 127) / 128);
-  if (fid == MZK_FIELD_M128) hipLaunchKernelGGL((k_pointwise_div<M128Params>), dim3(blocks), dim3(128), 0, s, (const u32*)d_a, (const u32*)d_b, (u32*)d_out, n, regs, a_stride, out_stride);
-  else hipLaunchKernelGGL((k_pointwise_div<FrParams>), dim3(blocks), dim3(128), 0, s, (const u32*)d_a, (const u32*)d_b, (u32*)d_out, n, regs, a_stride, out_stride);
+  MZK_TRY(MZK_FIELD_LAUNCH(fid, k_pointwise_div<P>, dim3(blocks), dim3(128), 0, s, (const u32*)d_a, (const u32*)d_b, (u32*)d_out, n, regs, a_stride, out_stride));
   MZK_HIP(hipGetLastError());
   return MZK_OK;
 }
 int pointwise_mul_dev(int fid, const void* d_a, const void* d_b, void* d_out, size_t n, hipStream_t s) {
   if (n == 0) return MZK_OK;
   const unsigned blocks = (unsigned)((n + 255) / 256);
-  if (fid == MZK_FIELD_M128)
-    hipLaunchKernelGGL((k_pointwise_mul<M128Params>), dim3(blocks), dim3(256), 0, s, (const u32*)d_a, (const u32*)d_b, (u32*)d_out, n);
-  else
-    hipLaunchKernelGGL((k_pointwise_mul<FrParams>), dim3(blocks), dim3(256), 0, s, (const u32*)d_a, (const u32*)d_b, (u32*)d_out, n);
+  MZK_TRY(MZK_FIELD_LAUNCH(fid, k_pointwise_mul<P>, dim3(blocks), dim3(256), 0, s, (const u32*)d_a, (const u32*)d_b, (u32*)d_out, n));
   MZK_HIP(hipGetLastError());
   return MZK_OK;
 }

@@ -1133,62 +1133,57 @@ extern "C" {
 
 int mzk_fast_zerofier(int field_id, const uint64_t* domain, size_t n, const uint64_t* root, size_t root_order, uint64_t* out, size_t* out_len) {
   MZK_ENTER();
-  if (field_id != MZK_FIELD_FR && field_id != MZK_FIELD_M128) { set_error("fast_zerofier: bad field id %d", field_id); return MZK_E_ARG; }
+  MZK_TRY(field_check(field_id, "fast_zerofier"));
   if (!root || !out_len || (n && (!domain || !out))) { set_error("fast_zerofier: null pointer"); return MZK_E_ARG; }
   const HostField* hf = host_field(field_id);
   MZK_TRY(check_root(hf, root, root_order));
   MZK_TRY(check_canonical(hf, domain, n, "domain"));
-  return field_id == MZK_FIELD_M128 ? zerofier_impl<M128Params>(field_id, domain, n, root, root_order, out, out_len)
-                                    : zerofier_impl<FrParams>(field_id, domain, n, root, root_order, out, out_len);
+  return with_field(field_id, [&](auto tag) { return zerofier_impl<typename decltype(tag)::P>(field_id, domain, n, root, root_order, out, out_len); });
 }
 int mzk_fast_evaluate(int field_id, const uint64_t* coef, size_t m, const uint64_t* domain, size_t n, const uint64_t* root, size_t root_order, uint64_t* out) {
   MZK_ENTER();
-  if (field_id != MZK_FIELD_FR && field_id != MZK_FIELD_M128) { set_error("fast_evaluate: bad field id %d", field_id); return MZK_E_ARG; }
+  MZK_TRY(field_check(field_id, "fast_evaluate"));
   if (!root || (m && !coef) || (n && (!domain || !out))) { set_error("fast_evaluate: null pointer"); return MZK_E_ARG; }
   const HostField* hf = host_field(field_id);
   MZK_TRY(check_root(hf, root, root_order));
   MZK_TRY(check_canonical(hf, domain, n, "domain"));
   MZK_TRY(check_canonical(hf, coef, m, "coef"));
-  return field_id == MZK_FIELD_M128 ? evaluate_impl<M128Params>(field_id, coef, m, domain, n, root, root_order, out)
-                                    : evaluate_impl<FrParams>(field_id, coef, m, domain, n, root, root_order, out);
+  return with_field(field_id, [&](auto tag) { return evaluate_impl<typename decltype(tag)::P>(field_id, coef, m, domain, n, root, root_order, out); });
 }
 int mzk_fast_interpolate(int field_id, const uint64_t* domain, const uint64_t* values, size_t n, const uint64_t* root, size_t root_order, uint64_t* out,
                          size_t* out_len) {
   MZK_ENTER();
-  if (field_id != MZK_FIELD_FR && field_id != MZK_FIELD_M128) { set_error("fast_interpolate: bad field id %d", field_id); return MZK_E_ARG; }
+  MZK_TRY(field_check(field_id, "fast_interpolate"));
   if (!root || !out_len || (n && (!domain || !values || !out))) { set_error("fast_interpolate: null pointer"); return MZK_E_ARG; }
   const HostField* hf = host_field(field_id);
   MZK_TRY(check_root(hf, root, root_order));
   MZK_TRY(interp_check_domain(field_id, hf, domain, n));
   MZK_TRY(check_canonical(hf, values, n, "values"));
-  return field_id == MZK_FIELD_M128 ? interpolate_impl<M128Params>(field_id, domain, values, n, 1, root, root_order, out, out_len)
-                                    : interpolate_impl<FrParams>(field_id, domain, values, n, 1, root, root_order, out, out_len);
+  return with_field(field_id, [&](auto tag) { return interpolate_impl<typename decltype(tag)::P>(field_id, domain, values, n, 1, root, root_order, out, out_len); });
 }
 int mzk_fast_interpolate_batch(int field_id, const uint64_t* domain, const uint64_t* values, size_t n, size_t batch, const uint64_t* root,
                                size_t root_order, uint64_t* out, size_t* out_lens) {
   MZK_ENTER();
-  if (field_id != MZK_FIELD_FR && field_id != MZK_FIELD_M128) { set_error("fast_interpolate: bad field id %d", field_id); return MZK_E_ARG; }
+  MZK_TRY(field_check(field_id, "fast_interpolate"));
   if (batch == 0) return MZK_OK;
   if (!root || !out_lens || (n && (!domain || !values || !out))) { set_error("fast_interpolate: null pointer"); return MZK_E_ARG; }
   const HostField* hf = host_field(field_id);
   MZK_TRY(check_root(hf, root, root_order));
   MZK_TRY(interp_check_domain(field_id, hf, domain, n));
   MZK_TRY(check_canonical(hf, values, n * batch, "values"));
-  return field_id == MZK_FIELD_M128 ? interpolate_impl<M128Params>(field_id, domain, values, n, batch, root, root_order, out, out_lens)
-                                    : interpolate_impl<FrParams>(field_id, domain, values, n, batch, root, root_order, out, out_lens);
+  return with_field(field_id, [&](auto tag) { return interpolate_impl<typename decltype(tag)::P>(field_id, domain, values, n, batch, root, root_order, out, out_lens); });
 }
 
 int mzk_fast_interpolate_batch_dev(int field_id, const uint64_t* domain, const void* d_values, size_t n, size_t batch, const uint64_t* root,
                                    size_t root_order, void* d_out, size_t* out_lens, void* stream) {
   MZK_ENTER();
-  if (field_id != MZK_FIELD_FR && field_id != MZK_FIELD_M128) { set_error("fast_interpolate: bad field id %d", field_id); return MZK_E_ARG; }
+  MZK_TRY(field_check(field_id, "fast_interpolate"));
   if (batch == 0) return MZK_OK;
   if (!root || !out_lens || (n && (!domain || !d_values || !d_out))) { set_error("fast_interpolate: null pointer"); return MZK_E_ARG; }
   const HostField* hf = host_field(field_id);
   MZK_TRY(check_root(hf, root, root_order));
   MZK_TRY(interp_check_domain(field_id, hf, domain, n));
-  return field_id == MZK_FIELD_M128 ? interpolate_impl<M128Params>(field_id, domain, nullptr, n, batch, root, root_order, nullptr, out_lens, d_values, d_out, (hipStream_t)stream)
-                                    : interpolate_impl<FrParams>(field_id, domain, nullptr, n, batch, root, root_order, nullptr, out_lens, d_values, d_out, (hipStream_t)stream);
+  return with_field(field_id, [&](auto tag) { return interpolate_impl<typename decltype(tag)::P>(field_id, domain, nullptr, n, batch, root, root_order, nullptr, out_lens, d_values, d_out, (hipStream_t)stream); });
 }
 
 }  // extern "C"

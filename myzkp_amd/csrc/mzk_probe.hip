@@ -89,11 +89,14 @@ template <class P> static int probe_field_forms(int op, int form, size_t n, cons
 }
 
 int selftest_field_probe_arity(int fid, int op, int form, int* limbs) {
-  bool ok = false;
-  if (fid == MZK_FIELD_FR) { ok = probe_field_form_ok<FrParams>(op, form); *limbs = FrParams::L; }
-  else if (fid == MZK_FIELD_FQ) { ok = probe_field_form_ok<FqParams>(op, form); *limbs = FqParams::L; }
-  else if (fid == MZK_FIELD_M128) { ok = probe_field_form_ok<M128Params>(op, form); *limbs = M128Params::L; }
-  return ok ? probe_field_arity(op) : 0;
+  int arity = 0;      // stays 0 for an unknown id: both callers report that in their own words
+  (void)with_field3(fid, [&](auto tag) -> int {
+    typedef typename decltype(tag)::P P;
+    *limbs = P::L;
+    if (probe_field_form_ok<P>(op, form)) arity = probe_field_arity(op);
+    return MZK_OK;
+  });
+  return arity;
 }
 int selftest_field_probe_impl(int fid, int op, int form, size_t n, const uint32_t* in_host, uint32_t* out_host, hipStream_t s) {
   int L = 0;
@@ -106,11 +109,7 @@ int selftest_field_probe_impl(int fid, int op, int form, size_t n, const uint32_
   MZK_TRY(ws_get(WS_MISC_B, out_bytes, &dout));
   MZK_HIP(hipMemcpyAsync(din, in_host, in_bytes, hipMemcpyHostToDevice, s));
   MZK_HIP(hipMemsetAsync(dout, 0, out_bytes, s));
-  int rc = MZK_E_ARG;
-  if (fid == MZK_FIELD_FR) rc = probe_field_forms<FrParams>(op, form, n, (const u32*)din, (u32*)dout, s);
-  else if (fid == MZK_FIELD_FQ) rc = probe_field_forms<FqParams>(op, form, n, (const u32*)din, (u32*)dout, s);
-  else if (fid == MZK_FIELD_M128) rc = probe_field_forms<M128Params>(op, form, n, (const u32*)din, (u32*)dout, s);
-  MZK_TRY(rc);
+  MZK_TRY(with_field3(fid, [&](auto tag) { return probe_field_forms<typename decltype(tag)::P>(op, form, n, (const u32*)din, (u32*)dout, s); }));
   MZK_HIP(hipGetLastError());
   MZK_HIP(hipMemcpyAsync(out_host, dout, out_bytes, hipMemcpyDeviceToHost, s));
   MZK_HIP(hipStreamSynchronize(s));

@@ -119,11 +119,12 @@ int selftest_field_asm_impl(int fid, uint64_t seed, size_t n, uint64_t* mismatch
   MZK_HIP(hipMemsetAsync(d, 0, 8, s));
   const unsigned blocks = (unsigned)((n + 255) / 256);
   if (n) {
-    if (fid == MZK_FIELD_FR) hipLaunchKernelGGL(k_selftest_field_asm<FrParams>, dim3(blocks), dim3(256), 0, s, seed, n, d);
-    else if (fid == MZK_FIELD_FQ) hipLaunchKernelGGL(k_selftest_field_asm<FqParams>, dim3(blocks), dim3(256), 0, s, seed, n, d);
-    else if (fid == MZK_FIELD_M128) hipLaunchKernelGGL(k_selftest_field_asm<M128Params>, dim3(blocks), dim3(256), 0, s, seed, n, d);
-    else { set_error("selftest: unknown field id %d", fid); return MZK_E_ARG; }
-    MZK_HIP(hipGetLastError());
+    if (!host_field(fid)) { set_error("selftest: unknown field id %d", fid); return MZK_E_ARG; }
+    MZK_TRY(with_field3(fid, [&](auto tag) -> int {
+      hipLaunchKernelGGL(k_selftest_field_asm<typename decltype(tag)::P>, dim3(blocks), dim3(256), 0, s, seed, n, d);
+      MZK_HIP(hipGetLastError());
+      return MZK_OK;
+    }));
   }
   unsigned long long h = 0;
   MZK_HIP(hipMemcpyAsync(&h, d, 8, hipMemcpyDeviceToHost, s));

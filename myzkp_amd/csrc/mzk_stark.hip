@@ -16,7 +16,7 @@ static unsigned bit_length(uint64_t v) { return v ? 64u - (unsigned)__builtin_cl
 
 static int stark_plan(int fid, size_t expansion, size_t checks, size_t m, size_t cycles, size_t degree, const uint32_t* term_exps,
                       const size_t* term_offsets, size_t nc, const size_t* b_cycles, const size_t* b_regs, size_t nb, mzk_stark_dims* d, bool with_boundary = true) {
-  if (fid != MZK_FIELD_FR && fid != MZK_FIELD_M128) { set_error("stark_plan: bad field id %d", fid); return MZK_E_ARG; }
+  MZK_TRY(field_check(fid, "stark_plan"));
   if (!d || (nc && !term_offsets) || (nb && (!b_cycles || !b_regs))) { set_error("stark_plan: null pointer"); return MZK_E_ARG; }
   if (m > MZK_STARK_MAX_REGISTERS) {
     set_error("stark_plan: %zu registers need %zu variables, mzk_mpoly_compose takes %d (at most %d registers)", m, 1 + 2 * m, (int)MZK_MPOLY_MAX_VARS,
@@ -35,7 +35,7 @@ static int stark_plan(int fid, size_t expansion, size_t checks, size_t m, size_t
     return MZK_E_LENGTH;
   }
   if (cycles == 0) { set_error("stark_plan: num_cycles = 0 (original_trace_length - 1, fast_stark.rs:54)"); return MZK_E_LENGTH; }
-  const unsigned max_log = fid == MZK_FIELD_FR ? 28 : 32;           // mzk.h "Size limits"
+  const unsigned max_log = field_max_log(fid);
   const unsigned olog = bit_length(prod), elog = bit_length(expansion) - 1;
   if (olog + elog > max_log) {
     set_error("stark_plan: FRI domain of 2^%u elements (omicron domain 2^%u, expansion 2^%u), transforms go up to 2^%u", olog + elog, olog, elog, max_log);
@@ -117,7 +117,7 @@ static int stark_plan(int fid, size_t expansion, size_t checks, size_t m, size_t
 
 // ---- the proof layout -----------------------------------------------------------------------------------------------------------------
 static int stark_layout(const mzk_stark_dims* d, int fid, uint64_t* off, uint64_t* size, uint64_t* total) {
-  if (fid != MZK_FIELD_FR && fid != MZK_FIELD_M128) { set_error("stark_proof_layout: bad field id %d", fid); return MZK_E_ARG; }
+  MZK_TRY(field_check(fid, "stark_proof_layout"));
   if (!d) { set_error("stark_proof_layout: null pointer"); return MZK_E_ARG; }
   if (d->num_indices == 0 || d->fri_domain_length < 2 || (d->fri_domain_length & (d->fri_domain_length - 1)) || d->num_registers > MZK_STARK_MAX_REGISTERS ||
       d->fri_num_rounds < 2) {
