@@ -31,7 +31,29 @@ extern "C" {
 
 enum { MZK_FIELD_FR = 0,   /* ModEIP197 / FqOrder: algebra/field.rs:428-431, curve/bn128.rs:30 */
        MZK_FIELD_M128 = 1, /* M128 = 1 + 407*2^119: zkstark/fri.rs:408 */
-       MZK_FIELD_FQ = 2    /* BN128Modulus: curve/bn128.rs:19-22 (point coordinates only) */ };
+       MZK_FIELD_FQ = 2,   /* BN128Modulus: curve/bn128.rs:19-22 (point coordinates only) */
+       MZK_FIELD_M64 = 3,  /* Goldilocks, p = 2^64 - 2^32 + 1: zkstark/fri.rs:409 */
+       MZK_FIELD_M64X3 = 4 /* ExtendedFieldElement<M64, Ip3>, Ip3 = x^3 - x + 1: zkstark/fri.rs:410-421 */ };
+/* The Goldilocks ids (the second instantiation of the reference's FRI, test_fri_efield, fri.rs:546-594).
+ *   Wire format: M64 = one canonical uint64_t (< p) per element; M64X3 = three consecutive canonical uint64_t c0, c1, c2 of
+ *   c0 + c1 x + c2 x^2 (24 bytes, array of structures).  A scalar parameter of id 4 (root, offset, alpha) has the same three words.
+ *   Served by: mzk_root_of_unity, mzk_ntt / _dev / _batch / _batch_dev, mzk_coset_lde / _dev / _batch / _batch_dev, mzk_fri_fold / _dev,
+ *   mzk_merkle_build_field / _dev, mzk_merkle_commit_field / _dev and every call on a built tree (root, open, open_batch, open_multi,
+ *   leaves, free), mzk_fri_commit, mzk_fri_commit_keep_trees / _dev.  Every other call refuses them with MZK_E_ARG like any id it
+ *   does not serve (mzk_fri_prove*, mzk_stark_*, mzk_fast_*, mzk_fft_multiply, mzk_mpoly_*, mzk_poly_*, the *_signed Merkle and FRI
+ *   forms, mzk_merkle_commit_field_batch*, mzk_ntt_multi*, mzk_ntt_columns_dev, the synth / selftest / probe calls).
+ *   Restriction for id 4: omega, generator and offset must lie in the base field (c1 = c2 = 0), MZK_E_ARG otherwise -- every element
+ *   of 2-power order does, and the reference's only instantiation passes base values for all three; a transform root with c1 or
+ *   c2 != 0 fails the root-order check (MZK_E_ROOT_ORDER).  alpha and the data are unrestricted.
+ *   Leaves: the library's restatement of bincode, unpinned against Rust like the leaves of the other fields.  Base element v: sign
+ *   byte (0 for zero, else 1), u64 LE digit count, u32 LE digits (9 .. 17 bytes).  Extension element, as
+ *   ExtendedFieldElement{poly: Polynomial{coef}}: u64 LE count k of coefficients after trimming trailing zero coefficients
+ *   (0 <= k <= 3), then k base leaves (8 .. 59 bytes; a zero coefficient below a non-zero one is its 9-byte leaf).
+ *   mzk_merkle_leaves returns 1 or 3 words per element, flags 0.  A path stride below the longest possible leaf is accepted, as for
+ *   Fr: MZK_E_LENGTH only when a sibling leaf that is actually opened does not fit (64 holds every leaf of every field).
+ *   mzk_fri_commit*: alpha_out takes 1 or 3 words; `negative` must be NULL (MZK_E_ARG): elements are canonical, the signs the
+ *   reference's BigInt coefficients may carry are not represented; an id-4 round of ONE element is MZK_E_LENGTH (its 59-byte leaf
+ *   does not fit the 48-byte root slot). */
 
 enum { MZK_OK = 0,
        MZK_E_ARG = -1,        /* null pointer / bad field id */
@@ -79,7 +101,9 @@ int mzk_abi_version(void);
  *                                       SRS handle with 16-bit window tables holds 16 n points = 128 GiB at 2^27 -- pass
  *                                       with_tables = 0 to mzk_srs_from_device_ex to keep only the prepared points)
  *   transforms                          n <= 2^28 over Fr (its 2-adicity); over M128 up to 2^32 nominally, memory-bound in
- *                                       practice: in + out + (passes - 1) twiddle tables of n elements each
+ *                                       practice: in + out + (passes - 1) twiddle tables of n elements each; over M64 / M64X3
+ *                                       up to 2^32 (the 2-adicity), in + out + one scratch copy (no n-sized twiddle table)
+ *   Merkle leaves / path entries        at most 41 bytes over Fr, 59 over M64X3: a stride of 64 holds every leaf; FRI root slots are 48
  *   subproduct trees (mzk_fast_*)       n <= 2^27 points (the internal products are transforms of 2 n <= 2^28 points) */
 /* ---- NTT family ------------------------------------------------------------------------------- */
 /* ntt::ntt (algebra/ntt.rs:7-48) when inverse == 0: out[k] = sum_j in[j] * root^(j k), natural order

@@ -7,12 +7,22 @@ ROOT = os.path.dirname(HERE)
 SO = os.environ.get("MZK_HIP_LIB") or os.path.join(HERE, "libmzk_hip.so")   # MZK_HIP_LIB: experimental builds (tools/)
 
 FIELD_FR, FIELD_M128, FIELD_FQ = 0, 1, 2
-LIMBS = {FIELD_FR: 4, FIELD_M128: 2, FIELD_FQ: 4}
+# Goldilocks (p = 2^64 - 2^32 + 1) and its cubic extension F_p[x] / (x^3 - x + 1): one / three canonical u64 per element.  A scalar
+# extension element is an int packed as c0 + c1 * 2^64 + c2 * 2^128 (what to_limbs / from_limbs do with three limbs).
+FIELD_M64, FIELD_M64X3 = 3, 4
+LIMBS = {FIELD_FR: 4, FIELD_M128: 2, FIELD_FQ: 4, FIELD_M64: 1, FIELD_M64X3: 3}
 MODULUS = {
     FIELD_FR: 21888242871839275222246405745257275088548364400416034343698204186575808495617,
     FIELD_M128: 270497897142230380135924736767050121217,
     FIELD_FQ: 21888242871839275222246405745257275088696311157297823662689037894645226208583,
+    FIELD_M64: (1 << 64) - (1 << 32) + 1,
+    FIELD_M64X3: (1 << 64) - (1 << 32) + 1,        # of every coefficient
 }
+
+
+def _leaf_stride(fid):
+    """bytes that hold any leaf of the field: 41 for Fr, 59 for an M64X3 element"""
+    return 64 if fid == FIELD_M64X3 else 48
 ERRORS = {0: "MZK_OK", -1: "MZK_E_ARG", -2: "MZK_E_NOT_POW2", -3: "MZK_E_ROOT_ORDER", -4: "MZK_E_ROOT_PRIM",
           -5: "MZK_E_LENGTH", -6: "MZK_E_RANGE", -7: "MZK_E_HIP", -8: "MZK_E_NOGPU", -9: "MZK_E_CALLBACK", -10: "MZK_E_IO",
           -11: "MZK_E_BUSY", -12: "MZK_E_NOMEM"}
@@ -511,11 +521,11 @@ class MerkleTree:
         else:
             e = _arr(fid, elems)
             self.n = e.shape[0]
-            self.stride = 48
+            self.stride = _leaf_stride(fid)
             _check(lib().mzk_merkle_build_field(fid, _p(e), ctypes.c_size_t(self.n), ctypes.byref(self._h)))
 
     def root(self):
-        buf = (ctypes.c_uint8 * max(self.stride, 48))()
+        buf = (ctypes.c_uint8 * max(self.stride, 64))()
         ln = ctypes.c_size_t()
         _check(lib().mzk_merkle_root(self._h, buf, ctypes.c_size_t(len(buf)), ctypes.byref(ln)))
         return bytes(buf[:ln.value])
@@ -574,7 +584,7 @@ def merkle_open_multi(trees, index_lists):
     cnt = (ctypes.c_size_t * max(T, 1))(*counts)
     depths = (ctypes.c_size_t * max(T, 1))()
     entries = sum(c * max(t.n.bit_length(), 1) for t, c in zip(trees, counts) if t is not None)
-    stride = 48
+    stride = max([48] + [t.stride for t, c in zip(trees, counts) if t is not None and c])
     buf = (ctypes.c_uint8 * max(stride * entries, 1))()
     lens = (ctypes.c_uint64 * max(entries, 1))()
     _check(lib().mzk_merkle_open_multi(handles, ctypes.c_size_t(T), _p(flat) if flat.size else None, cnt, buf, ctypes.c_size_t(stride), lens, depths))
@@ -591,9 +601,9 @@ def merkle_open_multi(trees, index_lists):
 def merkle_commit_field(fid, elems):
     """Merkle::commit(&codeword.map(bincode::serialize)) (fri.rs:160-166)."""
     e = _arr(fid, elems)
-    buf = (ctypes.c_uint8 * 48)()
+    buf = (ctypes.c_uint8 * 64)()
     ln = ctypes.c_size_t()
-    _check(lib().mzk_merkle_commit_field(fid, _p(e), ctypes.c_size_t(e.shape[0]), buf, ctypes.c_size_t(48), ctypes.byref(ln)))
+    _check(lib().mzk_merkle_commit_field(fid, _p(e), ctypes.c_size_t(e.shape[0]), buf, ctypes.c_size_t(64), ctypes.byref(ln)))
     return bytes(buf[:ln.value])
 
 
@@ -783,7 +793,7 @@ def fri_commit(fid, codeword, omega, offset, num_rounds, challenge, negative=Non
             t = MerkleTree.__new__(MerkleTree)
             t._h = ctypes.c_void_p(handles[r])
             t.n = n >> r
-            t.stride = 48
+            t.stride = _leaf_stride(fid)
             t.fid = fid
             trees.append(t)
         return (cws if codewords else None), rts, trees

@@ -5,6 +5,7 @@
 #include <stdlib.h>
 #include <atomic>
 #include "mzk_common.h"
+#include "mzk_gl.h"
 
 namespace mzk {
 
@@ -586,6 +587,15 @@ int mzk_root_of_unity(int field_id, unsigned log2_n, uint64_t* out) {
     for (int i = 0; i < 4; i++) out[i] = r[i];
     return MZK_OK;
   }
+  if (field_is_gl(field_id)) {
+    // get_nth_root_of_m64, zkstark/fri.rs:449-473; for the extension the same value, embedded (c1 = c2 = 0)
+    if (log2_n > gl::TWO_ADICITY) { set_error("Field does not have nth root of unity where n > 2^32 or not power of two."); return MZK_E_ARG; }
+    uint64_t r = gl::ROOT_2_32;
+    for (unsigned o = gl::TWO_ADICITY; o > log2_n; o--) r = gl::sqr(r);
+    out[0] = r;
+    for (int i = 1; i < field_gl_comps(field_id); i++) out[i] = 0;
+    return MZK_OK;
+  }
   return field_check(field_id, "root_of_unity");
 }
 
@@ -679,7 +689,7 @@ static int msm_host_chunked(const uint64_t* scalars, const uint64_t* points, voi
 
 int mzk_ntt(int field_id, const uint64_t* root, const uint64_t* in, uint64_t* out, size_t n, int inverse) {
   MZK_ENTER();
-  MZK_TRY(field_check(field_id, "ntt"));
+  MZK_TRY(field_check_gl(field_id, "ntt"));
   if (n == 0) return MZK_OK;
   if (!in || !out) { set_error("ntt: null pointer"); return MZK_E_ARG; }
   hipStream_t s = ctx().stream;
@@ -708,7 +718,7 @@ int mzk_coset_lde_batch_dev(int field_id, const void* d_coefs, size_t n_coef, co
 int mzk_coset_lde_batch(int field_id, const uint64_t* coefs, size_t n_coef, const uint64_t* offset, const uint64_t* generator,
                         uint64_t* out, size_t order, size_t batch) {
   MZK_ENTER();
-  MZK_TRY(field_check(field_id, "coset_lde"));
+  MZK_TRY(field_check_gl(field_id, "coset_lde"));
   if (n_coef > order) { set_error("attempt to subtract with overflow (order - polynomial.coef.len())"); return MZK_E_LENGTH; }
   if (order == 0 || batch == 0) return MZK_OK;
   if (!out || (!coefs && n_coef)) { set_error("coset_lde: null pointer"); return MZK_E_ARG; }
@@ -729,7 +739,7 @@ int mzk_ntt_batch_dev(int field_id, const uint64_t* root_host, const void* d_in,
 }
 int mzk_ntt_batch(int field_id, const uint64_t* root, const uint64_t* in, uint64_t* out, size_t n, size_t batch, int inverse) {
   MZK_ENTER();
-  MZK_TRY(field_check(field_id, "ntt"));
+  MZK_TRY(field_check_gl(field_id, "ntt"));
   if (n == 0 || batch == 0) return MZK_OK;
   if (!in || !out) { set_error("ntt: null pointer"); return MZK_E_ARG; }
   hipStream_t s = ctx().stream;
@@ -745,7 +755,7 @@ int mzk_ntt_batch(int field_id, const uint64_t* root, const uint64_t* in, uint64
 int mzk_coset_lde(int field_id, const uint64_t* coef, size_t n_coef, const uint64_t* offset, const uint64_t* generator,
                   uint64_t* out, size_t order) {
   MZK_ENTER();
-  MZK_TRY(field_check(field_id, "coset_lde"));
+  MZK_TRY(field_check_gl(field_id, "coset_lde"));
   if (n_coef > order) { set_error("attempt to subtract with overflow (order - polynomial.coef.len())"); return MZK_E_LENGTH; }
   if (order == 0) return MZK_OK;
   if (!out || (!coef && n_coef)) { set_error("coset_lde: null pointer"); return MZK_E_ARG; }
@@ -1578,7 +1588,7 @@ int mzk_fri_fold_dev(int field_id, const void* d_codeword, size_t n, const uint6
 int mzk_fri_fold(int field_id, const uint64_t* codeword, size_t n, const uint64_t* alpha, const uint64_t* offset,
                  const uint64_t* omega, uint64_t* out) {
   MZK_ENTER();
-  MZK_TRY(field_check(field_id, "fri_fold"));
+  MZK_TRY(field_check_gl(field_id, "fri_fold"));
   if (n / 2 == 0) return MZK_OK;
   if (!codeword || !out) { set_error("fri_fold: null pointer"); return MZK_E_ARG; }
   hipStream_t s = ctx().stream;

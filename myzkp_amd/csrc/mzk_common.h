@@ -155,9 +155,12 @@ void h_ninv_pow2(const HostField* f, unsigned log2n, uint64_t* out);  // (2^log2
 bool h_is_one(const HostField* f, const uint64_t* a);
 void h_rmod(const HostField* f, uint64_t* out);                       // R mod p: x -> x R mod p is one h_mulmod with it
 
-static inline int field_words(int fid) { return fid == MZK_FIELD_M128 ? 4 : 8; }   // u32 words per element
-static inline int field_limbs64(int fid) { return fid == MZK_FIELD_M128 ? 2 : 4; }
-static inline size_t field_bytes(int fid) { return fid == MZK_FIELD_M128 ? 16 : 32; }
+// Goldilocks ids (mzk_gl.h): one or three canonical u64 per element, no Montgomery parameter set -- a kernel family of their own
+static inline bool field_is_gl(int fid) { return fid == MZK_FIELD_M64 || fid == MZK_FIELD_M64X3; }
+static inline int field_gl_comps(int fid) { return fid == MZK_FIELD_M64X3 ? 3 : 1; }
+static inline int field_words(int fid) { return field_is_gl(fid) ? 2 * field_gl_comps(fid) : (fid == MZK_FIELD_M128 ? 4 : 8); }   // u32 words per element
+static inline int field_limbs64(int fid) { return field_is_gl(fid) ? field_gl_comps(fid) : (fid == MZK_FIELD_M128 ? 2 : 4); }
+static inline size_t field_bytes(int fid) { return 8 * (size_t)field_limbs64(fid); }
 static inline unsigned field_max_log(int fid) { return fid == MZK_FIELD_FR ? 28 : 32; }   // mzk.h "Size limits"
 
 // ---- field id -> template instantiation ---------------------------------------------------------------
@@ -175,6 +178,17 @@ template <class F> static inline int with_field(int fid, F&& f) {
   if (fid == MZK_FIELD_FR) return f(FieldTag<FrParams>());
   return field_check(fid, "with_field");
 }
+// The Goldilocks ids select no parameter set but a coefficient count: with_gl(fid, f) returns f(GlTag<1>()) for MZK_FIELD_M64 and
+// f(GlTag<3>()) for MZK_FIELD_M64X3 (kernels take decltype(tag)::NC).  field_check_gl is the argument check of the entry points
+// that serve the Goldilocks ids next to Fr / M128 (transforms, coset LDE, fold, the unsigned Merkle and FRI commit calls); every
+// other call keeps field_check and so keeps refusing them in its present words.
+template <int NC_> struct GlTag { static constexpr int NC = NC_; };
+template <class F> static inline int with_gl(int fid, F&& f) {
+  if (fid == MZK_FIELD_M64) return f(GlTag<1>());
+  if (fid == MZK_FIELD_M64X3) return f(GlTag<3>());
+  return field_check(fid, "with_gl");
+}
+static inline int field_check_gl(int fid, const char* who) { return field_is_gl(fid) ? MZK_OK : field_check(fid, who); }
 // ... and Fq as well (synthetic data, self-tests, probes)
 template <class F> static inline int with_field3(int fid, F&& f) {
   if (fid == MZK_FIELD_FR) return f(FieldTag<FrParams>());
@@ -214,6 +228,15 @@ int pointwise_div_shared_dev(int fid, const void* d_a, size_t a_stride, const vo
 int pointwise_mul_shared_dev(int fid, const void* d_a, size_t a_stride, const void* d_b, void* d_out, size_t out_stride, size_t n, size_t regs, hipStream_t s);
 int pointwise_mul_dev(int fid, const void* d_a, const void* d_b, void* d_out, size_t n, hipStream_t s);
 void ntt_release_plans();
+// ---- Goldilocks family (mzk_gl.hip); same contracts as the calls above, parameters as canonical u64 (id 4: three of them, c0 c1 c2)
+// gl_param_check: every word of x[0 .. comps) canonical (MZK_E_RANGE otherwise); base_only: an id-4 parameter must have c1 = c2 = 0
+// (MZK_E_ARG: omega, generator and offset lie in the base field, mzk.h)
+int gl_param_check(int fid, const uint64_t* x, const char* who, const char* what, bool base_only);
+int gl_ntt_dev_impl(int fid, const uint64_t* root_host, const void* d_in, void* d_out, size_t n, size_t batch, int inverse, hipStream_t s);
+int gl_coset_lde_dev_impl(int fid, const void* d_coef, size_t n_coef, const uint64_t* offset_host, const uint64_t* generator_host, void* d_out,
+                          size_t order, hipStream_t s, size_t batch);
+int gl_fri_fold_dev(int fid, const void* d_cw, size_t n, const uint64_t* alpha, uint64_t half, uint64_t oinv, uint64_t winv, void* d_out, hipStream_t s);
+void gl_release_plans();
 void kzg_release_cache();       // mzk_kzg.hip: fixed-base tables of the current context
 void poly_release_pool();       // mzk_poly.hip: parked scratch blocks of the current context
 int fri_fold_dev_impl(int fid, const void* d_cw, size_t n, const uint64_t* alpha, const uint64_t* offset, const uint64_t* omega,

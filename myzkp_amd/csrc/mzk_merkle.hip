@@ -12,6 +12,7 @@
 #include <atomic>
 #include "mzk_common.h"
 #include "mzk_keccak_asm.h"
+#include "mzk_gl.h"
 
 namespace mzk {
 
@@ -256,6 +257,38 @@ __global__ __launch_bounds__(LEAF_THREADS) void k_merkle_leaf_pairs_lp(const u32
   u32* o32 = reinterpret_cast<u32*>(nodes + 4 * i);
 #pragma unroll
   for (int l = 0; l < 4; l++) o32[2 * l + parity] = a[l];
+}
+
+// The same level over Goldilocks elements (NC = 1: M64, 3: M64X3; leaf bytes: mzk_gl.h leaf_bytes).  A pair is at most 2 * 59 = 118 bytes:
+// still one block.  One lane per leaf pair at every size.
+template <int NC>
+__global__ __launch_bounds__(LEAF_THREADS) void k_merkle_leaf_pairs_gl(const u64* __restrict__ elems, size_t pairs, u64* __restrict__ nodes) {
+  __shared__ u32 blk[SHA3_RATE / 4][LEAF_THREADS];
+  const int tid = threadIdx.x;
+  const size_t i = (size_t)blockIdx.x * LEAF_THREADS + tid;
+  if (i >= pairs) return;
+#pragma unroll
+  for (int w = 0; w < SHA3_RATE / 4; w++) blk[w][tid] = 0;
+  auto put = [&](int pos, u32 byte) { reinterpret_cast<u8*>(&blk[pos >> 2][tid])[pos & 3] = (u8)byte; };
+  int pos = 0;
+#pragma unroll
+  for (int e = 0; e < 2; e++) {
+    u64 c[NC];
+#pragma unroll
+    for (int q = 0; q < NC; q++) c[q] = elems[(2 * i + e) * NC + q];
+    pos = gl::leaf_bytes<NC>(c, pos, put);
+  }
+  put(pos, 0x06u);
+  reinterpret_cast<u8*>(&blk[(SHA3_RATE - 1) >> 2][tid])[3] |= 0x80u;
+  u64 a[25];
+#pragma unroll
+  for (int l = 0; l < SHA3_RATE / 8; l++) a[l] = (u64)blk[2 * l][tid] | ((u64)blk[2 * l + 1][tid] << 32);
+#pragma unroll
+  for (int l = SHA3_RATE / 8; l < 25; l++) a[l] = 0;
+  keccak_f(a);
+  ulonglong2* o2 = reinterpret_cast<ulonglong2*>(nodes + 4 * i);
+  o2[0] = make_ulonglong2(a[0], a[1]);
+  o2[1] = make_ulonglong2(a[2], a[3]);
 }
 
 // ---- level 1 from arbitrary byte leaves: leaf 2i || leaf 2i+1 is the contiguous range off[2i] .. off[2i+2) ---
@@ -576,7 +609,12 @@ static int merkle_hash_levels(int kind, int fid, const void* d_leaves, const u64
   const unsigned blocks = (unsigned)((pairs + 127) / 128);
   if (kind == 1)
     hipLaunchKernelGGL(k_merkle_leaf_pairs_bytes, dim3(blocks), dim3(128), 0, s, (const u8*)d_leaves, d_off, pairs, d_nodes);
-  else {
+  else if (field_is_gl(fid)) {
+    MZK_TRY(with_gl(fid, [&](auto tag) {
+      hipLaunchKernelGGL((k_merkle_leaf_pairs_gl<decltype(tag)::NC>), dim3(blocks), dim3(LEAF_THREADS), 0, s, (const u64*)d_leaves, pairs, d_nodes);
+      return MZK_OK;
+    }));
+  } else {
     static const int lp_on = tune_int("MZK_LEAF_LANE_PAIRS", 1);      // tuning build: 0 = one lane per leaf pair at every size (A/B)
     const bool lp = lp_on && pairs <= LEAF_PAIR_MAX;
     const unsigned lpb = (unsigned)((pairs + LEAF_THREADS / 2 - 1) / (LEAF_THREADS / 2));
@@ -657,6 +695,27 @@ static size_t host_bincode_field(const uint64_t* limbs, int nl, uint8_t* out, bo
   return 9 + 4 * (size_t)k;
 }
 
+// The leaf bytes of one element of field `fid` on the host (at most HOST_LEAF_MAX: a 59-byte M64X3 leaf is the longest)
+constexpr size_t HOST_LEAF_MAX = 64;
+static size_t host_leaf(int fid, const uint64_t* limbs, uint8_t* out, bool negative = false) {
+  if (!field_is_gl(fid)) return host_bincode_field(limbs, field_limbs64(fid), out, negative);
+  auto put = [&](int pos, uint32_t byte) { out[pos] = (uint8_t)byte; };
+  return (size_t)(fid == MZK_FIELD_M64X3 ? gl::leaf_bytes<3>(limbs, 0, put) : gl::leaf_bytes<1>(limbs, 0, put));
+}
+// canonical elements of a host array: every limb group below the modulus (Goldilocks: every word below p)
+static int host_elems_canonical(int fid, const uint64_t* elems, size_t n) {
+  if (field_is_gl(fid)) {
+    const size_t words = n * (size_t)field_gl_comps(fid);
+    for (size_t i = 0; i < words; i++)
+      if (!gl::is_canonical(elems[i])) { set_error("merkle: element %zu not canonical", i / (size_t)field_gl_comps(fid)); return MZK_E_RANGE; }
+    return MZK_OK;
+  }
+  const HostField* hf = host_field(fid);
+  for (size_t i = 0; i < n; i++)
+    if (!h_is_canonical(hf, elems + (size_t)hf->nl * i)) { set_error("merkle: element %zu not canonical", i); return MZK_E_RANGE; }
+  return MZK_OK;
+}
+
 static int merkle_build(int kind, int fid, const void* src, bool src_on_device, size_t leaf_bytes, const uint64_t* offsets, size_t n,
                         mzk_merkle** out, hipStream_t s, const uint8_t* neg_host = nullptr);
 
@@ -731,10 +790,10 @@ static int merkle_build(int kind, int fid, const void* src, bool src_on_device, 
     } else {
       memcpy(host.data(), src, leaf_bytes);
     }
-    std::vector<uint8_t> blob(n * (size_t)(9 + 8 * nl));
+    std::vector<uint8_t> blob(n * HOST_LEAF_MAX);
     std::vector<uint64_t> off(n + 1);
     uint64_t o = 0;
-    for (size_t i = 0; i < n; i++) { off[i] = o; o += host_bincode_field(host.data() + i * nl, nl, blob.data() + o, neg_host && neg_host[i]); }
+    for (size_t i = 0; i < n; i++) { off[i] = o; o += host_leaf(fid, host.data() + i * nl, blob.data() + o, neg_host && neg_host[i]); }
     off[n] = o;
     return merkle_build_ragged(blob.data(), off.data(), n, out, s);
   }
@@ -776,30 +835,27 @@ extern "C" {
 int mzk_merkle_build_field_dev(int field_id, const void* d_elems, size_t n, mzk_merkle** out, void* stream) {
   MZK_ENTER();
   WsGuard wsg((hipStream_t)stream);
-  MZK_TRY(field_check(field_id, "merkle"));
+  MZK_TRY(field_check_gl(field_id, "merkle"));
   return merkle_build(0, field_id, d_elems, true, n * field_bytes(field_id), nullptr, n, out, (hipStream_t)stream);
 }
-static int build_field_host(int field_id, const uint64_t* elems, const uint8_t* negative, size_t n, mzk_merkle** out) {
+// signed_form: the (magnitude, sign) calls serve Fr and M128 only
+static int build_field_host(int field_id, const uint64_t* elems, const uint8_t* negative, size_t n, mzk_merkle** out, bool signed_form) {
   MZK_ENTER();
-  MZK_TRY(field_check(field_id, "merkle"));
-  if (elems) {
-    const HostField* hf = host_field(field_id);
-    for (size_t i = 0; i < n; i++)
-      if (!h_is_canonical(hf, elems + (size_t)hf->nl * i)) { set_error("merkle: element %zu not canonical", i); return MZK_E_RANGE; }
-  }
+  MZK_TRY(signed_form ? field_check(field_id, "merkle") : field_check_gl(field_id, "merkle"));
+  if (elems) MZK_TRY(host_elems_canonical(field_id, elems, n));
   WsGuard wsg(ctx().stream);
   MZK_TRY(merkle_build(0, field_id, elems, false, n * field_bytes(field_id), nullptr, n, out, ctx().stream, negative));
   MZK_HIP(hipStreamSynchronize(ctx().stream));
   return MZK_OK;
 }
-int mzk_merkle_build_field(int field_id, const uint64_t* elems, size_t n, mzk_merkle** out) { return build_field_host(field_id, elems, nullptr, n, out); }
+int mzk_merkle_build_field(int field_id, const uint64_t* elems, size_t n, mzk_merkle** out) { return build_field_host(field_id, elems, nullptr, n, out, false); }
 int mzk_merkle_build_field_signed(int field_id, const uint64_t* magnitudes, const uint8_t* negative, size_t n, mzk_merkle** out) {
-  return build_field_host(field_id, magnitudes, negative, n, out);
+  return build_field_host(field_id, magnitudes, negative, n, out, true);
 }
 int mzk_merkle_commit_field_signed(int field_id, const uint64_t* magnitudes, const uint8_t* negative, size_t n, uint8_t* root, size_t cap,
                                    size_t* root_len) {
   mzk_merkle* t = nullptr;
-  MZK_TRY(build_field_host(field_id, magnitudes, negative, n, &t));
+  MZK_TRY(build_field_host(field_id, magnitudes, negative, n, &t, true));
   const int rc = mzk_merkle_root(t, root, cap, root_len);
   mzk_merkle_free(t);
   return rc;
@@ -825,12 +881,12 @@ int mzk_merkle_root(const mzk_merkle* t, uint8_t* root, size_t cap, size_t* root
   MerkleScope ms(t);
   MZK_TRY(ms.rc);
   if (t->n == 1) {   // merkle.rs:17-19: the single leaf itself
-    uint8_t buf[48];
+    uint8_t buf[HOST_LEAF_MAX];
     size_t len;
     if (t->kind == 0) {
       uint64_t limbs[4];
       MZK_TRY(d2h_sync(limbs, t->d_leaves, field_bytes(t->field), ms.s));
-      len = host_bincode_field(limbs, field_limbs64(t->field), buf, !t->neg.empty() && t->neg[0]);
+      len = host_leaf(t->field, limbs, buf, !t->neg.empty() && t->neg[0]);
       if (cap < len) { set_error("merkle_root: buffer too small (%zu < %zu)", cap, len); return MZK_E_LENGTH; }
       memcpy(root, buf, len);
     } else {
@@ -948,7 +1004,7 @@ int mzk_merkle_open_batch(const mzk_merkle* t, const uint64_t* indices, size_t c
   MZK_TRY(ms.rc);
   hipStream_t s = ms.s;
   WsGuard wsg(s);
-  const int lw = (int)field_words(t->field), nl = field_limbs64(t->field);
+  const int lw = (int)field_words(t->field);
   const size_t node_words64 = count * (size_t)(t->depth - 1) * 4;
   u64 *d_idx, *d_on;
   u32* d_ol;
@@ -966,9 +1022,9 @@ int mzk_merkle_open_batch(const mzk_merkle* t, const uint64_t* indices, size_t c
   for (size_t q = 0; q < count; q++) {
     uint64_t limbs[4] = {0, 0, 0, 0};
     memcpy(limbs, hl.data() + q * lw, (size_t)lw * 4);
-    uint8_t buf[48];
+    uint8_t buf[HOST_LEAF_MAX];
     const size_t sib = (size_t)indices[q] ^ 1;
-    const size_t len = host_bincode_field(limbs, nl, buf, !t->neg.empty() && t->neg[sib]);
+    const size_t len = host_leaf(t->field, limbs, buf, !t->neg.empty() && t->neg[sib]);
     if (stride < len) { set_error("merkle_open: stride %zu < leaf length %zu", stride, len); return MZK_E_LENGTH; }
     uint8_t* pq = paths + q * (size_t)t->depth * stride;
     memcpy(pq, buf, len);
@@ -1050,13 +1106,13 @@ int mzk_merkle_open_multi(const mzk_merkle* const* trees, size_t n_trees, const 
   for (size_t t = 0; t < n_trees; t++) {
     if (counts[t] == 0) continue;
     const mzk_merkle* tr = trees[t];
-    const int lw = (int)field_words(tr->field), nl = field_limbs64(tr->field);
+    const int lw = (int)field_words(tr->field);
     for (size_t q = 0; q < counts[t]; q++) {
       uint64_t limbs[4] = {0, 0, 0, 0};
       memcpy(limbs, hl.data() + at_leaf + q * lw, (size_t)lw * 4);
-      uint8_t buf[48];
+      uint8_t buf[HOST_LEAF_MAX];
       const size_t sib = (size_t)indices[at + q] ^ 1;
-      const size_t len = host_bincode_field(limbs, nl, buf, !tr->neg.empty() && tr->neg[sib]);
+      const size_t len = host_leaf(tr->field, limbs, buf, !tr->neg.empty() && tr->neg[sib]);
       if (stride < len) { set_error("merkle_open: stride %zu < leaf length %zu", stride, len); return MZK_E_LENGTH; }
       uint8_t* pq = paths + (at_entry + q * (size_t)tr->depth) * stride;
       memcpy(pq, buf, len);
@@ -1093,7 +1149,7 @@ void mzk_merkle_free(mzk_merkle* t) {
 int mzk_merkle_commit_field_dev(int field_id, const void* d_elems, size_t n, uint8_t* root, size_t cap, size_t* root_len, void* stream) {
   MZK_ENTER();
   WsGuard wsg((hipStream_t)stream);
-  MZK_TRY(field_check(field_id, "merkle"));
+  MZK_TRY(field_check_gl(field_id, "merkle"));
   if (n == 0) { set_error("merkle: empty leaf set (Merkle::commit recurses forever on it, merkle.rs:20-22)"); return MZK_E_LENGTH; }
   if (!d_elems || !root || !root_len) { set_error("merkle: null pointer"); return MZK_E_ARG; }
   if (!is_pow2(n)) {      // ragged (merkle.rs:15-25 accepts it; no prover call site produces it): handle path
@@ -1106,9 +1162,9 @@ int mzk_merkle_commit_field_dev(int field_id, const void* d_elems, size_t n, uin
   hipStream_t s = (hipStream_t)stream;
   if (n == 1) {
     uint64_t limbs[4];
-    uint8_t buf[48];
+    uint8_t buf[HOST_LEAF_MAX];
     MZK_TRY(d2h_sync(limbs, d_elems, field_bytes(field_id), s));
-    const size_t len = host_bincode_field(limbs, field_limbs64(field_id), buf);
+    const size_t len = host_leaf(field_id, limbs, buf);
     if (cap < len) { set_error("merkle: root buffer too small"); return MZK_E_LENGTH; }
     memcpy(root, buf, len);
     *root_len = len;
@@ -1183,36 +1239,46 @@ int mzk_merkle_commit_bytes(const uint8_t* leaves, const uint64_t* offsets, size
 // return value `(codewords, roots)`; sending the last codeword (fri.rs:198-206) is the caller's transcript work.
 static int fri_commit_rounds(int field_id, const uint64_t* codeword, const uint8_t* negative, size_t n, const uint64_t* omega, const uint64_t* offset,
                              int num_rounds, mzk_fri_challenge_fn challenge, void* user, uint8_t* roots, uint64_t* root_len, uint64_t* codewords_out,
-                             mzk_merkle** trees_out, bool on_device);
+                             mzk_merkle** trees_out, bool on_device, bool signed_form);
 // trees_out (optional, num_rounds entries): the Merkle tree of every round's codeword stays on the device as a handle for the
 // query phase (mzk_merkle_open_batch; fri.rs:211-260 opens from exactly these codewords); a one-element round gets NULL.
 // On failure every handle made so far is released.
 static int fri_commit_impl(int field_id, const uint64_t* codeword, const uint8_t* negative, size_t n, const uint64_t* omega, const uint64_t* offset,
                            int num_rounds, mzk_fri_challenge_fn challenge, void* user, uint8_t* roots, uint64_t* root_len, uint64_t* codewords_out,
-                           mzk_merkle** trees_out = nullptr, bool on_device = false) {
+                           mzk_merkle** trees_out = nullptr, bool on_device = false, bool signed_form = false) {
   if (trees_out) for (int r = 0; r < num_rounds; r++) trees_out[r] = nullptr;
-  const int rc = fri_commit_rounds(field_id, codeword, negative, n, omega, offset, num_rounds, challenge, user, roots, root_len, codewords_out, trees_out, on_device);
+  const int rc = fri_commit_rounds(field_id, codeword, negative, n, omega, offset, num_rounds, challenge, user, roots, root_len, codewords_out, trees_out, on_device,
+                                   signed_form);
   if (rc != MZK_OK && trees_out)
     for (int r = 0; r < num_rounds; r++) { if (trees_out[r]) mzk_merkle_free(trees_out[r]); trees_out[r] = nullptr; }
   return rc;
 }
 static int fri_commit_rounds(int field_id, const uint64_t* codeword, const uint8_t* negative, size_t n, const uint64_t* omega, const uint64_t* offset,
                              int num_rounds, mzk_fri_challenge_fn challenge, void* user, uint8_t* roots, uint64_t* root_len, uint64_t* codewords_out,
-                             mzk_merkle** trees_out, bool on_device) {
+                             mzk_merkle** trees_out, bool on_device, bool signed_form) {
   MZK_ENTER();
-  MZK_TRY(field_check(field_id, "fri_commit"));
+  // the Goldilocks ids: every form but mzk_fri_commit_signed, and without signs (an extension element's coefficients carry their own
+  // signs in the reference; parity is defined on canonical coefficients only -- DESIGN.md section 9e)
+  MZK_TRY(signed_form ? field_check(field_id, "fri_commit") : field_check_gl(field_id, "fri_commit"));
+  const bool is_gl = field_is_gl(field_id);
+  if (is_gl && negative) { set_error("fri_commit: field id %d takes canonical elements only (negative must be NULL)", field_id); return MZK_E_ARG; }
   if (num_rounds <= 0) return MZK_OK;
   if (!codeword || !omega || !offset || !challenge || !roots || !root_len) { set_error("fri_commit: null pointer"); return MZK_E_ARG; }
   if (!codewords_out && !trees_out) { set_error("fri_commit: no codeword output and no trees kept"); return MZK_E_ARG; }
   if (n == 0) { set_error("fri_commit: empty codeword"); return MZK_E_LENGTH; }
   if (!is_pow2(n)) { set_error("fri_commit: codeword length must be a power of two"); return MZK_E_NOT_POW2; }
   if ((n >> (num_rounds - 1)) == 0) { set_error("fri_commit: %d rounds halve a length-%zu codeword away", num_rounds, n); return MZK_E_LENGTH; }
-  const HostField* hf = host_field(field_id);
-  if (!h_is_canonical(hf, omega) || !h_is_canonical(hf, offset)) { set_error("fri_commit: parameter not canonical"); return MZK_E_RANGE; }
+  const HostField* hf = host_field(field_id);      // null for the Goldilocks ids
+  if (is_gl) {
+    MZK_TRY(gl_param_check(field_id, omega, "fri_commit", "parameter", true));
+    MZK_TRY(gl_param_check(field_id, offset, "fri_commit", "parameter", true));
+    // a one-element round's "root" is the leaf itself: up to 59 bytes for M64X3, and a root slot holds 48
+    if (field_id == MZK_FIELD_M64X3 && (n >> (num_rounds - 1)) == 1) { set_error("fri_commit: a one-element round of field id %d does not fit the 48-byte root slot", field_id); return MZK_E_LENGTH; }
+  } else if (!h_is_canonical(hf, omega) || !h_is_canonical(hf, offset)) { set_error("fri_commit: parameter not canonical"); return MZK_E_RANGE; }
   hipStream_t s = ctx().stream;
   WsGuard wsg(s);
   const size_t esz = field_bytes(field_id);
-  const int nl = hf->nl;
+  const int nl = field_limbs64(field_id);
   size_t total = 0;
   for (int r = 0; r < num_rounds; r++) total += n >> r;
   uint8_t* d_all;
@@ -1244,13 +1310,11 @@ static int fri_commit_rounds(int field_id, const uint64_t* codeword, const uint8
     MZK_TRY(ws_get(WS_MISC_E, n, (void**)&d_neg));
     MZK_HIP(hipMemcpyAsync(d_neg, negative, n, hipMemcpyHostToDevice, s));
   }
-  uint64_t om[4], of[4], alpha[4];
-  memcpy(om, omega, 8 * nl);
-  memcpy(of, offset, 8 * nl);
+  uint64_t alpha[4];
   // the fold's constants 2^-1, offset^-1, omega^-1: inverted ONCE here and squared along with omega and offset (three host
   // inversions per round before)
   FriFoldConsts fc;
-  MZK_TRY(fri_fold_consts(field_id, of, om, &fc));
+  MZK_TRY(fri_fold_consts(field_id, offset, omega, &fc));
   uint8_t* cur = d_all;
   size_t len = n;
   for (int r = 0; r < num_rounds; r++) {
@@ -1258,7 +1322,7 @@ static int fri_commit_rounds(int field_id, const uint64_t* codeword, const uint8
     if (len == 1) {
       uint64_t limbs[4];
       MZK_TRY(d2h_sync(limbs, cur, esz, s));
-      root_len[r] = host_bincode_field(limbs, nl, root, r == 0 && negative && negative[0]);
+      root_len[r] = host_leaf(field_id, limbs, root, r == 0 && negative && negative[0]);
     } else {
       RootMailbox mb;
       bool mailed = false;
@@ -1294,11 +1358,11 @@ static int fri_commit_rounds(int field_id, const uint64_t* codeword, const uint8
     const int crc = challenge(user, r, last, root, (size_t)root_len[r], alpha);
     if (crc != 0) { set_error("fri_commit: challenge callback failed in round %d (status %d)", r, crc); return MZK_E_CALLBACK; }
     if (last) break;
-    if (!h_is_canonical(hf, alpha)) { set_error("fri_commit: challenge of round %d not canonical", r); return MZK_E_RANGE; }
+    bool alpha_ok = true;
+    if (is_gl) { for (int i = 0; i < nl; i++) alpha_ok = alpha_ok && gl::is_canonical(alpha[i]); } else alpha_ok = h_is_canonical(hf, alpha);
+    if (!alpha_ok) { set_error("fri_commit: challenge of round %d not canonical", r); return MZK_E_RANGE; }
     uint8_t* next = cur + len * esz;
     MZK_TRY(fri_fold_dev_consts(field_id, cur, len, alpha, fc, next, s));
-    h_mulmod(hf, om, om, om);
-    h_mulmod(hf, of, of, of);
     fri_fold_consts_square(field_id, &fc);
     if (trees_out && len >= 2) d_nodes += 4 * (len - 1);        // the next round's digests follow this round's
     cur = next;
@@ -1313,7 +1377,7 @@ int mzk_fri_commit(int field_id, const uint64_t* codeword, size_t n, const uint6
 }
 int mzk_fri_commit_signed(int field_id, const uint64_t* magnitudes, const uint8_t* negative, size_t n, const uint64_t* omega, const uint64_t* offset,
                           int num_rounds, mzk_fri_challenge_fn challenge, void* user, uint8_t* roots, uint64_t* root_len, uint64_t* codewords_out) {
-  return fri_commit_impl(field_id, magnitudes, negative, n, omega, offset, num_rounds, challenge, user, roots, root_len, codewords_out);
+  return fri_commit_impl(field_id, magnitudes, negative, n, omega, offset, num_rounds, challenge, user, roots, root_len, codewords_out, nullptr, false, true);
 }
 int mzk_fri_commit_keep_trees(int field_id, const uint64_t* magnitudes, const uint8_t* negative, size_t n, const uint64_t* omega, const uint64_t* offset,
                               int num_rounds, mzk_fri_challenge_fn challenge, void* user, uint8_t* roots, uint64_t* root_len, uint64_t* codewords_out,

@@ -24,6 +24,7 @@
 #include <stdlib.h>
 #include "mzk_common.h"
 #include "mzk_field_asm.h"
+#include "mzk_gl.h"
 
 namespace mzk {
 
@@ -874,6 +875,7 @@ static void free_plan(NttPlan* p) {
 // offset-power tables of the fused coset LDE, per (context, field); see coset_lde_dev_impl
 static struct { uint64_t off[4]; unsigned logn; int lgn0; uint64_t gen; bool valid; hipEvent_t ready; } g_lde_cache[MZK_MAX_CTX][2] = {};
 void ntt_release_plans() {
+  gl_release_plans();
   for (auto* p : g_plans) free_plan(p);
   g_plans.clear();
   for (auto& ce : g_lde_cache[ctx().index]) {      // mzk_shutdown walks the contexts: drop this one's entries and their events
@@ -1133,6 +1135,7 @@ static unsigned ilog2(size_t n) { unsigned l = 0; while (((size_t)1 << l) < n) l
 // products to fold constants); nullptr = 1.
 int ntt_dev_impl(int fid, const uint64_t* root_host, const void* d_in, void* d_out, size_t n, int inverse,
                  const uint64_t* extra_scale_host, hipStream_t s) {
+  if (field_is_gl(fid) && !extra_scale_host) return gl_ntt_dev_impl(fid, root_host, d_in, d_out, n, 1, inverse, s);
   MZK_TRY(field_check_ntt(fid, "ntt"));
   if (n == 0) return MZK_OK;  // empty Vec in, empty Vec out (ntt.rs:12-14 `len <= 1`; len-1 underflow aside)
   if (!is_pow2(n)) { set_error("cannot compute ntt of non-power-of-two sequence"); return MZK_E_NOT_POW2; }
@@ -1153,6 +1156,7 @@ int ntt_dev_impl(int fid, const uint64_t* root_host, const void* d_in, void* d_o
 // `batch` transforms of n points each, stored back to back (in place allowed); same root for all
 int ntt_batch_dev_impl(int fid, const uint64_t* root_host, const void* d_in, void* d_out, size_t n, size_t batch, int inverse, hipStream_t s) {
   if (batch == 0 || n == 0) return MZK_OK;
+  if (field_is_gl(fid)) return gl_ntt_dev_impl(fid, root_host, d_in, d_out, n, batch, inverse, s);
   if (batch == 1) return ntt_dev_impl(fid, root_host, d_in, d_out, n, inverse, nullptr, s);
   MZK_TRY(field_check_ntt(fid, "ntt"));
   if (!is_pow2(n)) { set_error("cannot compute ntt of non-power-of-two sequence"); return MZK_E_NOT_POW2; }
@@ -1228,6 +1232,7 @@ int poly_scale_dev_impl(int fid, const void* d_in, size_t n, const uint64_t* rat
 int coset_lde_dev_impl(int fid, const void* d_coef, size_t n_coef, const uint64_t* offset_host,
                        const uint64_t* generator_host, void* d_out, size_t order, hipStream_t s, size_t batch) {
   if (batch == 0) return MZK_OK;
+  if (field_is_gl(fid)) return gl_coset_lde_dev_impl(fid, d_coef, n_coef, offset_host, generator_host, d_out, order, s, batch);
   MZK_TRY(field_check(fid, "coset_lde"));
   if (n_coef > order) { set_error("attempt to subtract with overflow (order - polynomial.coef.len())"); return MZK_E_LENGTH; }
   if (order == 0) return MZK_OK;
@@ -1308,6 +1313,11 @@ __global__ void k_fri_fold(const u32* __restrict__ cw, size_t h, Words8 r0_mont,
 // The fold's host-side constants for (offset, omega): 2^-1, offset^-1, omega^-1 (plain) and R mod p.  FRI::commit squares offset and
 // omega from round to round (fri.rs:186-187), and so it may their inverses: one set of inversions per commit instead of per round.
 int fri_fold_consts(int fid, const uint64_t* offset, const uint64_t* omega, FriFoldConsts* fc) {
+  if (field_is_gl(fid)) {       // base values (mzk.h: offset and omega of an id-4 call lie in the base field); no Montgomery form
+    memset(fc, 0, sizeof *fc);
+    fc->half[0] = gl::inv(2); fc->oinv[0] = gl::inv(offset[0]); fc->winv[0] = gl::inv(omega[0]); fc->rmod[0] = 1;
+    return MZK_OK;
+  }
   const HostField* hf = host_field(fid);
   uint64_t two[4] = {2, 0, 0, 0};
   h_invmod(hf, fc->half, two);
@@ -1317,6 +1327,7 @@ int fri_fold_consts(int fid, const uint64_t* offset, const uint64_t* omega, FriF
   return MZK_OK;
 }
 void fri_fold_consts_square(int fid, FriFoldConsts* fc) {
+  if (field_is_gl(fid)) { fc->oinv[0] = gl::sqr(fc->oinv[0]); fc->winv[0] = gl::sqr(fc->winv[0]); return; }
   const HostField* hf = host_field(fid);
   h_mulmod(hf, fc->oinv, fc->oinv, fc->oinv);
   h_mulmod(hf, fc->winv, fc->winv, fc->winv);
@@ -1338,6 +1349,7 @@ static FoldLaunch fold_launch(const HostField* hf, const FriFoldConsts& fc, size
 int fri_fold_dev_consts(int fid, const void* d_cw, size_t n, const uint64_t* alpha, const FriFoldConsts& fc, void* d_out, hipStream_t s) {
   const size_t h = n / 2;
   if (h == 0) return MZK_OK;
+  if (field_is_gl(fid)) return gl_fri_fold_dev(fid, d_cw, n, alpha, fc.half[0], fc.oinv[0], fc.winv[0], d_out, s);
   const HostField* hf = host_field(fid);
   uint64_t r0[4];
   h_mulmod(hf, r0, fc.half, alpha);
@@ -1386,9 +1398,17 @@ int fri_fold_dev_alpha(int fid, const void* d_cw, size_t n, const uint64_t* d_al
 }
 int fri_fold_dev_impl(int fid, const void* d_cw, size_t n, const uint64_t* alpha, const uint64_t* offset, const uint64_t* omega,
                       void* d_out, hipStream_t s) {
-  MZK_TRY(field_check(fid, "fri_fold"));
+  MZK_TRY(field_check_gl(fid, "fri_fold"));
   if (n / 2 == 0) return MZK_OK;
   if (!d_cw || !d_out || !alpha || !offset || !omega) { set_error("fri_fold: null pointer"); return MZK_E_ARG; }
+  if (field_is_gl(fid)) {
+    MZK_TRY(gl_param_check(fid, alpha, "fri_fold", "parameter", false));
+    MZK_TRY(gl_param_check(fid, offset, "fri_fold", "parameter", true));
+    MZK_TRY(gl_param_check(fid, omega, "fri_fold", "parameter", true));
+    FriFoldConsts gfc;
+    MZK_TRY(fri_fold_consts(fid, offset, omega, &gfc));
+    return fri_fold_dev_consts(fid, d_cw, n, alpha, gfc, d_out, s);
+  }
   const HostField* hf = host_field(fid);
   if (!h_is_canonical(hf, alpha) || !h_is_canonical(hf, offset) || !h_is_canonical(hf, omega)) { set_error("fri_fold: parameter not canonical"); return MZK_E_RANGE; }
   FriFoldConsts fc;

@@ -59,8 +59,11 @@ inline size_t trim_workspace() { size_t r = 0; expect(mzk_trim_workspace(&r)); r
 struct ModEIP197 { static constexpr int FIELD_ID = MZK_FIELD_FR; static constexpr int LIMBS = 4; };
 struct BN128Modulus { static constexpr int FIELD_ID = MZK_FIELD_FQ; static constexpr int LIMBS = 4; };
 struct M128 { static constexpr int FIELD_ID = MZK_FIELD_M128; static constexpr int LIMBS = 2; };
+struct M64 { static constexpr int FIELD_ID = MZK_FIELD_M64; static constexpr int LIMBS = 1; };     // Goldilocks, fri.rs:409
+struct Ip3 { static constexpr int FIELD_ID = MZK_FIELD_M64X3; static constexpr int LIMBS = 3; };   // x^3 - x + 1 over M64, fri.rs:410-421
 
 template <class M> struct FiniteFieldElement {
+  static constexpr int FIELD_ID = M::FIELD_ID;
   std::array<uint64_t, M::LIMBS> value{};  // canonical little-endian limbs (sanitize()d, field.rs:260-270)
   FiniteFieldElement() = default;
   static FiniteFieldElement from_value(uint64_t v) {  // Ring::from_value for small values
@@ -81,6 +84,31 @@ template <class M> struct FiniteFieldElement {
   }
   bool operator==(const FiniteFieldElement& o) const { return value == o.value; }
   bool operator!=(const FiniteFieldElement& o) const { return !(*this == o); }
+};
+// ExtendedFieldElement<M, P> (efield.rs) for the one extension on the FRI path, <M64, Ip3>: value = the canonical coefficients c0, c1, c2
+// of c0 + c1 x + c2 x^2 (each sanitize()d, trailing zeros kept: the wire format always has three)
+template <class M, class P> struct ExtendedFieldElement {
+  static constexpr int FIELD_ID = P::FIELD_ID;
+  std::array<uint64_t, P::LIMBS> value{};
+  ExtendedFieldElement() = default;
+  static ExtendedFieldElement from_value(uint64_t v) {  // the base value v, embedded
+    ExtendedFieldElement e;
+    e.value[0] = v;
+    return e;
+  }
+  static ExtendedFieldElement from_limbs(const uint64_t* l) {
+    ExtendedFieldElement e;
+    std::memcpy(e.value.data(), l, 8 * P::LIMBS);
+    return e;
+  }
+  static ExtendedFieldElement zero() { return ExtendedFieldElement(); }
+  static ExtendedFieldElement one() { return from_value(1); }
+  bool is_zero() const {
+    for (auto x : value) if (x) return false;
+    return true;
+  }
+  bool operator==(const ExtendedFieldElement& o) const { return value == o.value; }
+  bool operator!=(const ExtendedFieldElement& o) const { return !(*this == o); }
 };
 using FqOrder = FiniteFieldElement<ModEIP197>;  // bn128.rs:30
 using Fq = FiniteFieldElement<BN128Modulus>;    // bn128.rs:29
@@ -161,7 +189,7 @@ template <class F> struct Polynomial {
     expect(mzk_poly_scale(field_id(), a.data(), coef.size(), offset.value.data(), nullptr, out.data()));
     return Polynomial{from_wire<F>(out, coef.size())};
   }
-  static int field_id() { return F().value.size() == 2 ? MZK_FIELD_M128 : MZK_FIELD_FR; }
+  static int field_id() { return F::FIELD_ID; }      // from the element type's modulus tag
 };
 
 // ---- algebra/ntt.rs ---------------------------------------------------------------------------------------
@@ -199,6 +227,12 @@ std::vector<F> fast_coset_evaluate(const Polynomial<F>& polynomial, const F& off
 inline FiniteFieldElement<M128> get_nth_root_of_m128(unsigned log2_n) {
   FiniteFieldElement<M128> r;
   expect(mzk_root_of_unity(MZK_FIELD_M128, log2_n, r.value.data()));
+  return r;
+}
+// zkstark/fri.rs:449-473: a base value (every root of 2-power order is), embedded in the extension
+inline ExtendedFieldElement<M64, Ip3> get_nth_root_of_m64(unsigned log2_n) {
+  ExtendedFieldElement<M64, Ip3> r;
+  expect(mzk_root_of_unity(MZK_FIELD_M64X3, log2_n, r.value.data()));
   return r;
 }
 inline FqOrder get_nth_root_of_fr(unsigned log2_n) {  // the reference ships none

@@ -144,6 +144,8 @@ def emit():
              'pub const MZK_FIELD_FR: c_int = 0;',
              'pub const MZK_FIELD_M128: c_int = 1;',
              'pub const MZK_FIELD_FQ: c_int = 2;',
+             'pub const MZK_FIELD_M64: c_int = 3;',
+             'pub const MZK_FIELD_M64X3: c_int = 4;',
              'pub const MZK_OK: c_int = 0;',
              'pub const MZK_LAYOUT_CONTIGUOUS: c_int = 0;',
              'pub const MZK_LAYOUT_CYCLIC: c_int = 1;',
