@@ -577,6 +577,59 @@ typedef int (*mzk_sumcheck_challenge_fn)(void* user, int round, const uint64_t g
 int mzk_sumcheck_prove_srs(const mzk_srs* srs, const uint64_t* coef, size_t n, mzk_sumcheck_challenge_fn challenge, void* user, uint64_t* gs,
                            uint64_t* rs, uint64_t beta[4], uint64_t* commits_xy, uint64_t* ys, uint64_t* ws_xy, uint64_t* deg_xy);
 
+/* ---- the product sum-check over evaluation tables (examples/sumcheck: SumCheckProverGPU::prove, prover.rs:98-247) -----
+ * num_factors = k multilinear factors as tables of n = 2^num_vars canonical Fr values, back to back: factor f at
+ * tables[4 (f n + x)].  Index bits are variables in BitCombinationsDictOrder: variable 0 is the most significant bit.  Claimed sum
+ * C = sum_x prod_f T_f[x].  Round j (m = n >> j live entries per factor, h = m / 2): s_j(c) = sum_{i<h} prod_f (T_f[i] + c (T_f[i+h] -
+ * T_f[i])) for c = 0..=d (d = max_degree, an input of its own: the demo uses d = k), each pushed as its own object
+ * vec![bincode(s_j(c))]; r_j = F::sample(SHAKE256(stream)[0..32]) (the last 8 digest bytes big-endian, so r_j < 2^64); every factor
+ * folds, T_f[i] <- T_f[i] + r_j (T_f[i+h] - T_f[i]).  Everything runs in one enqueue, the transcript included: no host round trip.
+ * Values are canonical representatives in [0, p), which is what the reference's GPU prover pushes (it rebuilds them from bytes with
+ * Sign::Plus); its CPU twin can push negative BigInts after sub_ref, which is not reproduced.  bincode(F) is the library's
+ * restatement (sign byte 0 / 1, u64 digit count, u32 digits without a leading zero digit: see the Merkle section), not pinned
+ * against a Rust vector.  The sums follow the mathematical definition and the *_cpu twins of utils.rs, not the reference's `sum`
+ * kernel (several blocks reduce one buffer in place there).
+ *
+ * header: what the reference pushes before round 0 (prover.rs:108-122: max_degree, num_factors, num_variables, bincode of every
+ * factor -- an MPolynomial is a HashMap, so only the caller has those bytes), as header_objects objects already in stream form and
+ * concatenated: per object its u64 LE string count, then u64 LE length + bytes per string, i.e. the reference's serialization after
+ * the leading object count (the library writes that count).  header_len = 0 with header_objects = 0 is legal.  header is HOST memory in
+ * both forms.  Cost: the leading count changes with every push, so no hash state can be kept and the WHOLE stream is hashed again in
+ * every round -- the reference's format.  A header costs num_vars times its length in SHAKE256 blocks on one lane pair: a caller at
+ * scale should push a digest of its factors, not their bincode.
+ *
+ * Packed proof (mzk_sumcheck_product_layout; offsets 8-byte aligned; el = num_vars):
+ *   MZK_SCP_STATUS          u64: 0
+ *   MZK_SCP_SUM             4 u64: C
+ *   MZK_SCP_EVALS           el (d+1) x 4 u64: s_j(c), canonical, round-major
+ *   MZK_SCP_CHALLENGES      el x 4 u64: r_j
+ *   MZK_SCP_FINALS          k x 4 u64: each factor's single remaining value after the last fold, T_f(r_0 .. r_(el-1)) -- what the
+ *                           verifier's last check compares the product of against (verifier.rs:68-73)
+ *   MZK_SCP_TRANSCRIPT_LEN  u64: bytes of the serialized proof stream
+ *   MZK_SCP_TRANSCRIPT      transcript.serialize() after the last round; capacity 8 + header_len + el (d+1) (16 + 41)
+ * The input tables are not modified; folded halves live in the context's workspace (k n/2 elements for round 1's tables, k n/4 for
+ * round 2's, then ping-pong).  Errors, all before anything is enqueued: null pointer, num_factors or max_degree outside 1..8, a header
+ * that does not parse to exactly header_objects objects over header_len bytes (MZK_E_ARG); num_vars == 0 (the reference has no round
+ * to run), num_vars > 30, header_len above 2^40 (the layout's sizes must not wrap), proof_cap below the layout's total (MZK_E_LENGTH); a table value that is not canonical (MZK_E_RANGE; host
+ * form only -- the _dev form ASSUMES canonical tables, 16-byte aligned, and an 8-byte aligned proof buffer, and only enqueues). */
+enum { MZK_SCP_STATUS = 0, MZK_SCP_SUM = 1, MZK_SCP_EVALS = 2, MZK_SCP_CHALLENGES = 3, MZK_SCP_FINALS = 4, MZK_SCP_TRANSCRIPT_LEN = 5,
+       MZK_SCP_TRANSCRIPT = 6, MZK_SCP_SECTIONS = 7 };
+/* host only, no device work: offsets / sizes have MZK_SCP_SECTIONS entries (each may be NULL) */
+int mzk_sumcheck_product_layout(size_t num_vars, size_t num_factors, size_t max_degree, size_t header_len, uint64_t* offsets, uint64_t* sizes,
+                                uint64_t* total_bytes);
+/* host memory in and out; returns when proof_out is complete */
+int mzk_sumcheck_product_prove(const uint64_t* tables, size_t num_vars, size_t num_factors, size_t max_degree, const uint8_t* header,
+                               size_t header_len, size_t header_objects, uint8_t* proof_out, size_t proof_cap);
+/* device tables and proof; only enqueues on `stream` */
+int mzk_sumcheck_product_prove_dev(const void* d_tables, size_t num_vars, size_t num_factors, size_t max_degree, const uint8_t* header,
+                                   size_t header_len, size_t header_objects, void* d_proof, size_t proof_cap, void* stream);
+/* evals_over_boolean_hypercube (examples/sumcheck/src/utils.rs) for a DENSE multilinear polynomial: coef[t] is the coefficient of
+ * prod_{i: bit (el-1-i) of t set} x_i (the tables' MSB-first order), evals[b] = sum over t subset of b of coef[t]: el stages of one
+ * modular addition each (the subset-sum butterfly).  n = 2^num_vars values in and out, canonical; num_vars <= 30 (MZK_E_LENGTH),
+ * a coefficient that is not canonical MZK_E_RANGE (host form).  d_evals may equal d_coef. */
+int mzk_mle_evals_from_coeffs(const uint64_t* coef, size_t num_vars, uint64_t* evals);
+int mzk_mle_evals_from_coeffs_dev(const void* d_coef, size_t num_vars, void* d_evals, void* stream);
+
 /* ---- symbolic evaluation of multivariate constraints and the combination of the quotients (FastStark::prove) ----------
  * MPolynomial::evaluate_symbolic (algebra/mpolynomials.rs:125-141; zkstark/fast_stark.rs:246-259 composes every transition
  * constraint with the trace polynomials, zkstark/stark.rs:214 does the same) for n_constraints sparse multivariate polynomials over
@@ -819,7 +872,11 @@ enum { MZK_PH_MSM_PREPARE = 0, MZK_PH_MSM_SORT = 1, MZK_PH_MSM_ACCUMULATE = 2, M
        MZK_PH_NTT_PASS3 = 8, MZK_PH_NTT_PRESCALE = 9, MZK_PH_MERKLE = 10,
        MZK_PH_MSM_SEG_COMBINE = 11,   /* k_seg_combine (+ heavy): sums a bucket's segment partials; MSM_ACCUMULATE is k_seg_accumulate alone */
        MZK_PH_NTT_TOTAL = 12,         /* one pair around all passes of a transform */
-       MZK_PH_COUNT = 13 };
+       MZK_PH_SCP_ROUND0 = 13,        /* mzk_sumcheck_product_prove: round 0's kernel (no fold: one read of the tables) */
+       MZK_PH_SCP_ROUND = 14,         /* ... the fold-and-sum kernels of the later grid rounds */
+       MZK_PH_SCP_ROUND_END = 15,     /* ... the one-workgroup transcript steps between them */
+       MZK_PH_SCP_TAIL = 16,          /* ... every round from 2^7 entries per factor down, one launch */
+       MZK_PH_COUNT = 17 };
 int mzk_prof_enable(int on);
 /* bit p set = phase p gets its event pair while profiling is on (default: all).  An event pair costs a few
  * microseconds of stream time, so a timed region instruments only the kernel it prices. */

@@ -651,6 +651,103 @@ def sumcheck_sum(coef):
     return from_limbs(h)[0]
 
 
+SCP_SECTIONS = ("status", "sum", "evals", "challenges", "finals", "transcript_len", "transcript")
+
+
+def sumcheck_product_layout(num_vars, num_factors, max_degree, header_len=0):
+    """mzk_sumcheck_product_layout: ({section: (byte offset, byte size)}, total bytes) of the packed proof (host only)."""
+    off = (ctypes.c_uint64 * len(SCP_SECTIONS))()
+    size = (ctypes.c_uint64 * len(SCP_SECTIONS))()
+    total = ctypes.c_uint64()
+    _check(lib().mzk_sumcheck_product_layout(ctypes.c_size_t(num_vars), ctypes.c_size_t(num_factors), ctypes.c_size_t(max_degree),
+                                             ctypes.c_size_t(header_len), off, size, ctypes.byref(total)))
+    return {k: (off[i], size[i]) for i, k in enumerate(SCP_SECTIONS)}, total.value
+
+
+def sumcheck_frame_header(objects):
+    """Objects of the proof stream (each a list of byte strings) in the form mzk_sumcheck_product_prove takes as `header`: per object
+    its u64 LE string count, then u64 LE length + bytes per string.  The reference's header (prover.rs:108-122) is
+    [[bincode(max_degree)], [bincode(num_factors)], [bincode(num_variables)]] + [[bincode(factor)] for every factor]."""
+    out = []
+    for obj in objects:
+        out.append(len(obj).to_bytes(8, "little"))
+        for s in obj:
+            out.append(len(s).to_bytes(8, "little") + bytes(s))
+    return b"".join(out)
+
+
+def sumcheck_product_unpack(num_vars, num_factors, max_degree, header_len, raw):
+    """The packed proof as a dict: sum (int), evals (num_vars lists of max_degree + 1 ints), challenges, finals, transcript (bytes)."""
+    raw = bytes(raw)
+    sec, _ = sumcheck_product_layout(num_vars, num_factors, max_degree, header_len)
+
+    def part(k):
+        o, s = sec[k]
+        return raw[o:o + s]
+
+    def vals(k):
+        return from_limbs(np.frombuffer(part(k), dtype=np.uint64).reshape(-1, 4))
+    status = int.from_bytes(part("status"), "little")
+    if status != 0:
+        raise MzkError(-6, "sumcheck_product_prove: status %d" % status)
+    ev = vals("evals")
+    tlen = int.from_bytes(part("transcript_len"), "little")
+    return {"sum": vals("sum")[0], "evals": [ev[j * (max_degree + 1):(j + 1) * (max_degree + 1)] for j in range(num_vars)],
+            "challenges": vals("challenges"), "finals": vals("finals"), "transcript": part("transcript")[:tlen]}
+
+
+def sumcheck_product_prove(tables, max_degree, header_objects=(), device_ptr=None, num_vars=None, num_factors=None, raw=False):
+    """SumCheckProverGPU::prove (examples/sumcheck/src/prover.rs:98-247) over evaluation tables in one call, the transcript on the
+    device (mzk_sumcheck_product_prove).  tables: (k, 2^el, 4) limbs, factor by factor, variable 0 the most significant index bit.
+    header_objects: the objects pushed before round 0 (sumcheck_frame_header's input).  device_ptr / num_vars / num_factors: the
+    tables are already in HBM (mzk_sumcheck_product_prove_dev on torch's current stream); `tables` is ignored.  Returns
+    sumcheck_product_unpack's dict, or the packed bytes with raw=True."""
+    header = sumcheck_frame_header(header_objects)
+    hbuf = (ctypes.c_uint8 * max(len(header), 1)).from_buffer_copy(header or b"\0")
+    if device_ptr is None:
+        t = np.ascontiguousarray(tables, dtype=np.uint64)
+        if t.ndim != 3 or t.shape[2] != 4:
+            raise ValueError("tables: (factors, 2^num_vars, 4) limbs")
+        num_factors, n = t.shape[0], t.shape[1]
+        num_vars = max(n.bit_length() - 1, 0)
+        if n != 1 << num_vars:
+            raise ValueError("tables: 2^num_vars values per factor")
+    _, total = sumcheck_product_layout(num_vars, num_factors, max_degree, len(header))
+    args = (ctypes.c_size_t(num_vars), ctypes.c_size_t(num_factors), ctypes.c_size_t(max_degree), hbuf, ctypes.c_size_t(len(header)),
+            ctypes.c_size_t(len(header_objects)))
+    if device_ptr is None:
+        buf = (ctypes.c_uint8 * total)()
+        _check(lib().mzk_sumcheck_product_prove(_p(t), *args, buf, ctypes.c_size_t(total)))
+        packed = bytes(buf)
+    else:
+        import torch
+        proof = torch.empty(total, dtype=torch.uint8, device="cuda")
+        stream = torch.cuda.current_stream()
+        _check(lib().mzk_sumcheck_product_prove_dev(ctypes.c_void_p(int(device_ptr)), *args, ctypes.c_void_p(proof.data_ptr()), ctypes.c_size_t(total),
+                                                    ctypes.c_void_p(stream.cuda_stream)))
+        stream.synchronize()
+        packed = proof.cpu().numpy().tobytes()
+    return packed if raw else sumcheck_product_unpack(num_vars, num_factors, max_degree, len(header), packed)
+
+
+def mle_evals_from_coeffs(coef, device_ptr=None, num_vars=None, out_ptr=None, stream=None):
+    """evals_over_boolean_hypercube (examples/sumcheck/src/utils.rs) of a dense multilinear polynomial (mzk_mle_evals_from_coeffs):
+    coef[t] multiplies the x_i whose bit (el-1-i) of t is set; returns the (2^el, 4) table.  device_ptr / num_vars / out_ptr: device
+    buffers (out_ptr may equal device_ptr), only enqueues on `stream`."""
+    if device_ptr is not None:
+        _check(lib().mzk_mle_evals_from_coeffs_dev(ctypes.c_void_p(int(device_ptr)), ctypes.c_size_t(num_vars), ctypes.c_void_p(int(out_ptr)),
+                                                   ctypes.c_void_p(stream)))
+        return None
+    c = np.ascontiguousarray(coef, dtype=np.uint64).reshape(-1, 4)
+    n = c.shape[0]
+    num_vars = max(n.bit_length() - 1, 0)
+    if n != 1 << num_vars:
+        raise ValueError("coef: 2^num_vars values")
+    out = np.empty_like(c)
+    _check(lib().mzk_mle_evals_from_coeffs(_p(c), ctypes.c_size_t(num_vars), _p(out)))
+    return out
+
+
 _SUMCHECK_CB = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64))
 
 

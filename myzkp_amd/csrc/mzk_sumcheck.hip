@@ -1,0 +1,514 @@
+// mzk_sumcheck.hip -- the product sum-check prover over evaluation tables (examples/sumcheck/src/prover.rs:98-247, the
+// `*_cpu` twins of examples/sumcheck/src/utils.rs) with its Fiat-Shamir transcript on the device, and the subset-sum butterfly that
+// turns dense multilinear coefficients into such a table (evals_over_boolean_hypercube).
+//
+// k factors as tables of n = 2^el canonical Fr values, variable 0 the most significant index bit.  Round j (m = n >> j live entries,
+// h = m / 2):  s_j(c) = sum_{i<h} prod_f (T_f[i] + c (T_f[i+h] - T_f[i])), c = 0..=d, pushed as d + 1 objects vec![bincode(s_j(c))];
+// r_j = F::sample(SHAKE256(stream)[0..32)); T_f[i] <- T_f[i] + r_j (T_f[i+h] - T_f[i]).  The reference's `sum` kernel reduces one
+// buffer in place from several blocks; here the mathematical definition is followed.
+// bincode(FiniteFieldElement) is the library's restatement (mzk_sumcheck_tx.h), not pinned against a Rust vector.
+//
+// Form of the tables: canonical, standard form, everywhere ("Product sum-check").  A product of k standard-form values by
+// k - 1 Montgomery products is prod / R^(k-1); the factor R^(k-1) is put back ONCE per round and point, on the reduced sum (one
+// product by R^k mod p in the round-end step), so no table is ever converted and the inner loop has exactly (k-1)(d+1) products.
+//
+// Kernels:
+//   k_sc_round<K>     one pass per round: folds round j-1's tables with r_(j-1) (read from the proof's CHALLENGES section, where the
+//                     transcript step left it), writes the folded tables and accumulates s_j(0..=d) of them in the same pass
+//                     (four inputs per factor and output pair); round 0 has no fold and writes nothing.  Per-workgroup partials.
+//   k_sc_round_end    one workgroup: reduces the partials, writes s_j(c) to the proof, appends the d + 1 objects to the stream,
+//                     rehashes the whole stream (the leading object count changed: no hash state can be kept) and writes r_j.
+//   k_sc_tail         one wave: every round from SC_TAIL_M live entries per factor down, the tables in LDS, the transcript step
+//                     between the rounds inside the kernel; FINALS, TRANSCRIPT_LEN and STATUS at the end.
+//   k_mle_pass        the subset-sum butterfly, up to MLE_TILE_LOG index bits per pass in LDS.
+#include <utility>
+#include "mzk_common.h"
+#include "mzk_keccak_pair.h"
+#include "mzk_sumcheck_tx.h"
+
+namespace mzk {
+
+typedef FrParams SP;
+typedef Fe<SP> SE;
+struct ScW8 { u32 w[8]; };
+
+__device__ __forceinline__ SE sc_load(const u32* __restrict__ g, size_t i) {
+  const uint4* p = reinterpret_cast<const uint4*>(g + 8 * i);
+  const uint4 a = p[0], b = p[1];
+  const u32 w[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
+  return fe_unpack<SP>(w);
+}
+// v canonical
+__device__ __forceinline__ void sc_store(u32* __restrict__ g, size_t i, const SE& v) {
+  u32 w[8];
+  fe_pack<SP>(v, w);
+  uint4* p = reinterpret_cast<uint4*>(g + 8 * i);
+  p[0] = make_uint4(w[0], w[1], w[2], w[3]);
+  p[1] = make_uint4(w[4], w[5], w[6], w[7]);
+}
+// a + r (b - a), canonical; a, b canonical, r_mont = r R normalised
+__device__ __forceinline__ SE sc_fold1(const SE& a, const SE& b, const SE& r_mont) {
+  return fe_reduce<SP>(fe_add<SP>(a, fe_mul<SP>(fe_sub_carry<SP, 2>(b, a), r_mont)));
+}
+// x + y for normalised x, y below 3 p each: normalised, below 3 p
+__device__ __forceinline__ SE sc_add(const SE& x, const SE& y) { return fe_weak_reduce<SP>(fe_add<SP>(x, y)); }
+// the sum of v over the 64 lanes of the wave, in every lane (all lanes active).  Modular addition is exact: any order, same residue.
+__device__ __forceinline__ SE sc_wave_sum(SE v) {
+#pragma unroll
+  for (int d = 32; d > 0; d >>= 1) {
+    SE o;
+#pragma unroll
+    for (int i = 0; i < SP::L; i++) o.l[i] = (u32)__shfl_xor((int)v.l[i], d, 64);
+    v = sc_add(v, o);
+  }
+  return v;
+}
+// the challenge as the folds use it: r R mod p from the canonical r
+__device__ __forceinline__ SE sc_challenge_mont(const u64* __restrict__ r) {
+  u32 w[8];
+#pragma unroll
+  for (int i = 0; i < 4; i++) { w[2 * i] = (u32)r[i]; w[2 * i + 1] = (u32)(r[i] >> 32); }
+  return fe_to_mont<SP>(fe_unpack<SP>(w));
+}
+
+// f(integral_constant<int, 0>) ... f(integral_constant<int, N - 1>): unrolled by the front end.  `#pragma unroll` gives up above the
+// optimizer's size limit for pragma-unrolled loops (about ten field products), and an array indexed by a loop counter then lives in scratch.
+template <int... Is, class F> __device__ __forceinline__ void sc_static_for_seq(std::integer_sequence<int, Is...>, F&& f) {
+  (f(std::integral_constant<int, Is>()), ...);
+}
+template <int N, class F> __device__ __forceinline__ void sc_static_for(F&& f) { sc_static_for_seq(std::make_integer_sequence<int, N>(), f); }
+
+// ---- the grid rounds --------------------------------------------------------------------------------------------------------
+constexpr int SC_THREADS = 128;
+constexpr int SC_WAVES = SC_THREADS / 64;
+constexpr int SC_MAX_WG = 2048;
+constexpr int SC_END_THREADS = 256;
+constexpr int SC_END_WAVES = SC_END_THREADS / 64;
+// src: factor f at src + f * src_stride elements.  chal == null (round 0): the live table is src itself, m = 2 h entries.
+// Otherwise src holds 4 h entries per factor and out[i] = fold(src[i], src[i + 2 h]) for i < 2 h goes to dst (stride 2 h).
+// partials: (D + 1) canonical values per workgroup, prod / R^(K-1) summed.
+// K is a template parameter: the 2 K operands (point and difference per factor, 9 limbs each) stay in registers through the loop over
+// the points.  D is not: the D + 1 accumulators are a column of LDS per lane (dynamic, (D + 1) * 9 * SC_THREADS words), read and
+// written once per point and index -- 18 LDS words against K - 1 field products -- so that the loop over c stays a loop.  With both as
+// template parameters and everything unrolled the 64 kernels took over ten minutes to compile and k = d = 8 needed 81 more registers.
+template <int K>
+__global__ __launch_bounds__(SC_THREADS) void k_sc_round(const u32* __restrict__ src, size_t src_stride, size_t h, const u64* __restrict__ chal,
+                                                          u32* __restrict__ dst, u32* __restrict__ partials, int D) {
+  extern __shared__ u32 sc_acc[];                       // [D + 1][L][SC_THREADS]
+  __shared__ u32 S[SC_WAVES][mzk_tx::SCP_MAX_DEGREE + 1][SP::L];
+  const int tid = threadIdx.x;
+  for (int q = 0; q < (D + 1) * SP::L; q++) sc_acc[q * SC_THREADS + tid] = 0;
+  SE rm = fe_zero<SP>();
+  if (chal) rm = sc_challenge_mont(chal);
+  for (size_t i = (size_t)blockIdx.x * SC_THREADS + tid; i < h; i += (size_t)gridDim.x * SC_THREADS) {
+    SE pt[K], df[K];
+    sc_static_for<K>([&](auto fc) __attribute__((always_inline)) {
+      constexpr int f = decltype(fc)::value;
+      const u32* t = src + 8 * (size_t)f * src_stride;
+      SE a, b;
+      if (chal) {
+        a = sc_fold1(sc_load(t, i), sc_load(t, i + 2 * h), rm);
+        b = sc_fold1(sc_load(t, i + h), sc_load(t, i + 3 * h), rm);
+        u32* o = dst + 8 * (size_t)f * 2 * h;
+        sc_store(o, i, a);
+        sc_store(o, i + h, b);
+      } else {
+        a = sc_load(t, i);
+        b = sc_load(t, i + h);
+      }
+      pt[f] = a;
+      df[f] = fe_sub_carry<SP, 2>(b, a);          // b - a + 2 p: the c-points are a, a + df, a + 2 df, ... by repeated addition
+    });
+#pragma unroll 1
+    for (int c = 0; c <= D; c++) {
+      SE prod = pt[0];
+      sc_static_for<K - 1>([&](auto fc) __attribute__((always_inline)) { prod = fe_mul<SP>(prod, pt[decltype(fc)::value + 1]); });
+      u32* col = sc_acc + (size_t)c * SP::L * SC_THREADS + tid;
+      SE a;
+#pragma unroll
+      for (int q = 0; q < SP::L; q++) a.l[q] = col[q * SC_THREADS];
+      a = sc_add(a, prod);
+#pragma unroll
+      for (int q = 0; q < SP::L; q++) col[q * SC_THREADS] = a.l[q];
+      if (c < D) sc_static_for<K>([&](auto fc) __attribute__((always_inline)) { pt[decltype(fc)::value] = sc_add(pt[decltype(fc)::value], df[decltype(fc)::value]); });
+    }
+  }
+  const int wave = tid >> 6, lane = tid & 63;
+  for (int c = 0; c <= D; c++) {
+    const u32* col = sc_acc + (size_t)c * SP::L * SC_THREADS + tid;
+    SE a;
+#pragma unroll
+    for (int q = 0; q < SP::L; q++) a.l[q] = col[q * SC_THREADS];
+    const SE v = sc_wave_sum(a);
+    if (lane == 0) {
+#pragma unroll
+      for (int q = 0; q < SP::L; q++) S[wave][c][q] = v.l[q];
+    }
+  }
+  __syncthreads();
+  if (tid <= D) {
+    SE v;
+#pragma unroll
+    for (int q = 0; q < SP::L; q++) v.l[q] = S[0][tid][q];
+    for (int w = 1; w < SC_WAVES; w++) {
+      SE o;
+#pragma unroll
+      for (int q = 0; q < SP::L; q++) o.l[q] = S[w][tid][q];
+      v = sc_add(v, o);
+    }
+    sc_store(partials, (size_t)blockIdx.x * (D + 1) + tid, fe_reduce<SP>(v));
+  }
+}
+
+// ---- the transcript step ----------------------------------------------------------------------------------------------------
+struct ScProof {
+  u8* base;                      // the packed proof (device)
+  u64 off[mzk_tx::SCP_COUNT];
+  u64 header_objects, pos0;      // objects of the caller's header; stream bytes before round 0 (8 + header_len)
+  int el, D;
+  ScW8 rk;                       // R^k mod p, standard form: sum / R^(k-1) times it, Montgomery-reduced, is the sum
+};
+// Every thread of the workgroup calls.  sw: the d + 1 canonical values of round j (LDS, 8 words each); pos: stream bytes so far.
+// Writes s_j to EVALS (and C = s_0(0) + s_0(1) to SUM), appends the d + 1 objects, sets the object count, hashes the stream and
+// writes r_j to CHALLENGES.  Returns the new stream length.  dig, s_len: LDS scratch.
+__device__ u64 sc_tx_step(const ScProof& P, int j, u64 pos, const u32 (*sw)[8], u32* dig, u64* s_len) {
+  const int tid = threadIdx.x, nt = blockDim.x;
+  const int D = P.D;
+  u8* tx = P.base + P.off[mzk_tx::SCP_TRANSCRIPT];
+  u32* evals = reinterpret_cast<u32*>(P.base + P.off[mzk_tx::SCP_EVALS]) + 8 * (size_t)j * (D + 1);
+  for (int q = tid; q < 8 * (D + 1); q += nt) evals[q] = sw[q >> 3][q & 7];
+  if (tid == 0) {
+    if (j == 0) {
+      const SE c = fe_reduce<SP>(fe_add<SP>(fe_unpack<SP>(sw[0]), fe_unpack<SP>(sw[1])));
+      u32 w[8];
+      fe_pack<SP>(c, w);
+      u32* sum = reinterpret_cast<u32*>(P.base + P.off[mzk_tx::SCP_SUM]);
+      for (int q = 0; q < 8; q++) sum[q] = w[q];
+    }
+    u64 at = pos;
+    for (int c = 0; c <= D; c++) at += mzk_tx::scp_write_record(tx + at, sw[c]);
+    *reinterpret_cast<u64*>(tx) = P.header_objects + (u64)(j + 1) * (u64)(D + 1);
+    *s_len = at;
+  }
+  __syncthreads();
+  const u64 len = *s_len;
+  if (tid < 2) fri_shake256_pair(tx, len, tid, dig);
+  __syncthreads();
+  if (tid < 4) {
+    u64* chal = reinterpret_cast<u64*>(P.base + P.off[mzk_tx::SCP_CHALLENGES]) + 4 * (size_t)j;
+    chal[tid] = tid == 0 ? mzk_tx::sample_digest_word3(((u64)dig[7] << 32) | dig[6]) : 0;
+  }
+  __syncthreads();
+  return len;
+}
+
+// One workgroup: partials of round j -> s_j -> transcript -> r_j.  state[0]: stream bytes so far (written here; read unless j == 0).
+__global__ __launch_bounds__(SC_END_THREADS) void k_sc_round_end(const u32* __restrict__ partials, int nparts, int j, ScProof P, u64* __restrict__ state) {
+  __shared__ u32 S[SC_END_WAVES][SP::L];
+  __shared__ u32 sw[mzk_tx::SCP_MAX_DEGREE + 1][8];
+  __shared__ u32 dig[8];
+  __shared__ u64 s_len;
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  const int D = P.D;
+  for (int c = 0; c <= D; c++) {
+    SE acc = fe_zero<SP>();
+    for (int p = tid; p < nparts; p += SC_END_THREADS) acc = sc_add(acc, sc_load(partials, (size_t)p * (D + 1) + c));
+    acc = sc_wave_sum(acc);
+    if (lane == 0) {
+#pragma unroll
+      for (int i = 0; i < SP::L; i++) S[wave][i] = acc.l[i];
+    }
+    __syncthreads();
+    if (tid == 0) {
+      SE v = acc;
+      for (int w = 1; w < SC_END_WAVES; w++) {
+        SE o;
+#pragma unroll
+        for (int i = 0; i < SP::L; i++) o.l[i] = S[w][i];
+        v = sc_add(v, o);
+      }
+      fe_pack<SP>(fe_reduce<SP>(fe_mul<SP>(v, fe_unpack<SP>(P.rk.w))), sw[c]);
+    }
+    __syncthreads();
+  }
+  const u64 pos = j == 0 ? P.pos0 : state[0];
+  const u64 len = sc_tx_step(P, j, pos, sw, dig, &s_len);
+  if (tid == 0) state[0] = len;
+}
+
+// ---- the tail ---------------------------------------------------------------------------------------------------------------
+// LDS holds K tables of at most SC_TAIL_M entries: 8 x 128 x 32 bytes = 32 KiB at the largest K, half of what a workgroup may
+// declare statically.  One wave: h <= 64, one lane per index pair, and every reduction is a wave reduction.
+constexpr int SC_TAIL_M = 128;
+constexpr int SC_TAIL_LOG = 7;
+// Rounds j0 .. el-1.  fold == 0 (j0 == 0): src is the input, m entries per factor.  fold != 0: src holds 2 m entries per factor, to be
+// folded with r_(j0-1) on the way in.
+__global__ __launch_bounds__(64) void k_sc_tail(const u32* __restrict__ src, size_t src_stride, int fold, int m, int j0, int K, ScProof P,
+                                                 const u64* __restrict__ state) {
+  __shared__ u32 T[mzk_tx::SCP_MAX_FACTORS][SC_TAIL_M][8];
+  __shared__ u32 sw[mzk_tx::SCP_MAX_DEGREE + 1][8];
+  __shared__ u32 dig[8];
+  __shared__ u64 s_len;
+  const int tid = threadIdx.x;
+  const int D = P.D;
+  const u64* chal = reinterpret_cast<const u64*>(P.base + P.off[mzk_tx::SCP_CHALLENGES]);
+  {
+    SE rm = fe_zero<SP>();
+    if (fold) rm = sc_challenge_mont(chal + 4 * (size_t)(j0 - 1));
+    for (int f = 0; f < K; f++) {
+      const u32* t = src + 8 * (size_t)f * src_stride;
+      for (int i = tid; i < m; i += 64) {
+        const SE v = fold ? sc_fold1(sc_load(t, i), sc_load(t, (size_t)i + m), rm) : sc_load(t, i);
+        fe_pack<SP>(v, T[f][i]);
+      }
+    }
+  }
+  __syncthreads();
+  u64 pos = j0 == 0 ? P.pos0 : state[0];
+  const SE rk = fe_unpack<SP>(P.rk.w);
+  for (int j = j0; j < P.el; j++) {
+    const int h = m >> 1;
+    for (int c = 0; c <= D; c++) {
+      SE prod = fe_zero<SP>();
+      if (tid < h) {
+        for (int f = 0; f < K; f++) {
+          const SE a = fe_unpack<SP>(T[f][tid]);
+          const SE df = fe_sub_carry<SP, 2>(fe_unpack<SP>(T[f][tid + h]), a);
+          SE pt = a;
+          for (int t = 0; t < c; t++) pt = sc_add(pt, df);
+          prod = f == 0 ? pt : fe_mul<SP>(prod, pt);
+        }
+      }
+      const SE total = sc_wave_sum(prod);
+      if (tid == 0) fe_pack<SP>(fe_reduce<SP>(fe_mul<SP>(total, rk)), sw[c]);
+    }
+    __syncthreads();
+    pos = sc_tx_step(P, j, pos, sw, dig, &s_len);
+    const SE rm = sc_challenge_mont(chal + 4 * (size_t)j);
+    if (tid < h) {
+      for (int f = 0; f < K; f++) {
+        const SE v = sc_fold1(fe_unpack<SP>(T[f][tid]), fe_unpack<SP>(T[f][tid + h]), rm);
+        fe_pack<SP>(v, T[f][tid]);                 // in place: entry i is read by lane i alone, entry i + h is never written
+      }
+    }
+    __syncthreads();
+    m = h;
+  }
+  u32* fin = reinterpret_cast<u32*>(P.base + P.off[mzk_tx::SCP_FINALS]);
+  for (int q = tid; q < 8 * K; q += 64) fin[q] = T[q >> 3][0][q & 7];
+  if (tid == 0) {
+    *reinterpret_cast<u64*>(P.base + P.off[mzk_tx::SCP_TRANSCRIPT_LEN]) = pos;
+    *reinterpret_cast<u64*>(P.base + P.off[mzk_tx::SCP_STATUS]) = 0;
+  }
+}
+
+// ---- host side --------------------------------------------------------------------------------------------------------------
+typedef void (*ScRoundFn)(const u32*, size_t, size_t, const u64*, u32*, u32*, int);
+template <int... Ks> static ScRoundFn sc_round_pick(int k, std::integer_sequence<int, Ks...>) {
+  static const ScRoundFn col[] = {k_sc_round<Ks + 1>...};
+  return col[k - 1];
+}
+static ScRoundFn sc_round_kernel(int k) { return sc_round_pick(k, std::make_integer_sequence<int, mzk_tx::SCP_MAX_FACTORS>()); }
+
+static int scp_check(size_t el, size_t k, size_t d, size_t header_len, mzk_tx::ScpLayout* L) {
+  if (k < 1 || k > (size_t)mzk_tx::SCP_MAX_FACTORS) { set_error("sumcheck_product: %zu factors (1 to %d)", k, mzk_tx::SCP_MAX_FACTORS); return MZK_E_ARG; }
+  if (d < 1 || d > (size_t)mzk_tx::SCP_MAX_DEGREE) { set_error("sumcheck_product: max_degree %zu (1 to %d)", d, mzk_tx::SCP_MAX_DEGREE); return MZK_E_ARG; }
+  if (el == 0) { set_error("sumcheck_product: no variable, the prover has no round to run"); return MZK_E_LENGTH; }
+  if (el > (size_t)mzk_tx::SCP_MAX_VARS) { set_error("sumcheck_product: %zu variables (at most %d)", el, mzk_tx::SCP_MAX_VARS); return MZK_E_LENGTH; }
+  // the layout's sizes are sums over header_len: keep them far from wrapping (no stream this long is hashed el times anyway)
+  if (header_len > ((size_t)1 << 40)) { set_error("sumcheck_product: header of %zu bytes (at most 2^40)", header_len); return MZK_E_LENGTH; }
+  mzk_tx::scp_layout(el, k, d, header_len, L);
+  return MZK_OK;
+}
+
+static int scp_prove_impl(const void* tables, bool on_device, size_t el, size_t k, size_t d, const uint8_t* header, size_t header_len,
+                          size_t header_objects, void* proof_out, size_t proof_cap, hipStream_t s_in) {
+  if (!tables || !proof_out || (header_len && !header)) { set_error("sumcheck_product_prove: null pointer"); return MZK_E_ARG; }
+  mzk_tx::ScpLayout L;
+  MZK_TRY(scp_check(el, k, d, header_len, &L));
+  if (proof_cap < L.total) { set_error("sumcheck_product_prove: proof buffer of %zu bytes, the layout needs %llu", proof_cap, (unsigned long long)L.total); return MZK_E_LENGTH; }
+  if (!mzk_tx::scp_header_ok(header, header_len, header_objects)) {
+    set_error("sumcheck_product_prove: the header does not parse to %zu objects over %zu bytes", header_objects, header_len);
+    return MZK_E_ARG;
+  }
+  if (on_device && (((uintptr_t)tables & 15) || ((uintptr_t)proof_out & 7))) { set_error("sumcheck_product_prove: tables need 16-byte, the proof 8-byte alignment"); return MZK_E_ARG; }
+  const size_t n = (size_t)1 << el;
+  const HostField* fr = host_field(MZK_FIELD_FR);
+  if (!on_device) {
+    const uint64_t* t = (const uint64_t*)tables;
+    for (size_t i = 0; i < k * n; i++)
+      if (!h_is_canonical(fr, t + 4 * i)) { set_error("sumcheck_product_prove: table value %zu of factor %zu not canonical", i % n, i / n); return MZK_E_RANGE; }
+  }
+  MZK_ENTER();
+  hipStream_t s = on_device ? s_in : ctx().stream;
+  WsGuard wsg(s);
+  auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
+  // rounds 0 .. j0-1 on the grid, the tail from j0 on: its first live size n >> j0 is at most SC_TAIL_M
+  const int j0 = el > (size_t)SC_TAIL_LOG ? (int)el - SC_TAIL_LOG : 0;
+  // one workspace block: the tables (host form) | folded tables of odd rounds | of even rounds | partials | state | the proof (host form)
+  const size_t o_a = on_device ? 0 : al(k * n * 32), o_b = o_a + (j0 > 1 ? al(k * (n / 2) * 32) : 0), o_part = o_b + (j0 > 2 ? al(k * (n / 4) * 32) : 0);
+  const size_t o_state = o_part + al((size_t)SC_MAX_WG * (d + 1) * 32), o_proof = o_state + 256, total = o_proof + (on_device ? 0 : al(L.total));
+  uint8_t* blk;
+  MZK_TRY(ws_get(WS_MISC_F, total, (void**)&blk));
+  const u32* d_tab = (const u32*)tables;
+  if (!on_device) {
+    MZK_HIP(hipMemcpyAsync(blk, tables, k * n * 32, hipMemcpyHostToDevice, s));
+    d_tab = (const u32*)blk;
+  }
+  ScProof P;
+  P.base = on_device ? (u8*)proof_out : blk + o_proof;
+  for (int q = 0; q < mzk_tx::SCP_COUNT; q++) P.off[q] = L.off[q];
+  P.header_objects = header_objects;
+  P.pos0 = 8 + header_len;
+  P.el = (int)el;
+  P.D = (int)d;
+  {
+    uint64_t rmod[4], rk[4];
+    h_rmod(fr, rmod);
+    memcpy(rk, rmod, 32);
+    for (size_t q = 1; q < k; q++) { uint64_t t[4]; h_mulmod(fr, t, rk, rmod); memcpy(rk, t, 32); }
+    for (int i = 0; i < 4; i++) { P.rk.w[2 * i] = (u32)rk[i]; P.rk.w[2 * i + 1] = (u32)(rk[i] >> 32); }
+  }
+  if (header_len) MZK_HIP(hipMemcpyAsync(P.base + L.off[mzk_tx::SCP_TRANSCRIPT] + 8, header, header_len, hipMemcpyHostToDevice, s));
+  u32* partials = (u32*)(blk + o_part);
+  u64* state = (u64*)(blk + o_state);
+  const u64* chal = (const u64*)(P.base + L.off[mzk_tx::SCP_CHALLENGES]);
+  const ScRoundFn round = sc_round_kernel((int)k);
+  const size_t acc_bytes = (d + 1) * SP::L * SC_THREADS * sizeof(u32);
+  const u32* cur = d_tab;            // round j-1's tables, stride n >> (j-1) (round 0: the input)
+  size_t cur_stride = n;
+  for (int j = 0; j < j0; j++) {
+    const size_t h = n >> (j + 1);
+    const size_t need = (h + SC_THREADS - 1) / SC_THREADS;
+    const int nwg = (int)(need < (size_t)SC_MAX_WG ? need : SC_MAX_WG);
+    u32* dst = j == 0 ? nullptr : (u32*)(blk + ((j & 1) ? o_a : o_b));
+    prof_begin(s, j == 0 ? MZK_PH_SCP_ROUND0 : MZK_PH_SCP_ROUND);
+    hipLaunchKernelGGL(round, dim3(nwg), dim3(SC_THREADS), acc_bytes, s, cur, cur_stride, h, j == 0 ? (const u64*)nullptr : chal + 4 * (size_t)(j - 1), dst, partials, (int)d);
+    prof_end(s, j == 0 ? MZK_PH_SCP_ROUND0 : MZK_PH_SCP_ROUND);
+    ProfScope pe(s, MZK_PH_SCP_ROUND_END);
+    hipLaunchKernelGGL(k_sc_round_end, dim3(1), dim3(SC_END_THREADS), 0, s, (const u32*)partials, nwg, j, P, state);
+    if (j > 0) { cur = dst; cur_stride = 2 * h; }
+  }
+  prof_begin(s, MZK_PH_SCP_TAIL);
+  hipLaunchKernelGGL(k_sc_tail, dim3(1), dim3(64), 0, s, cur, cur_stride, j0 > 0 ? 1 : 0, (int)(n >> j0), j0, (int)k, P, (const u64*)state);
+  prof_end(s, MZK_PH_SCP_TAIL);
+  MZK_HIP(hipGetLastError());
+  if (on_device) return MZK_OK;
+  MZK_TRY(d2h_sync(proof_out, P.base, L.total, s));
+  uint64_t status;
+  memcpy(&status, (const uint8_t*)proof_out + L.off[mzk_tx::SCP_STATUS], 8);
+  if (status != 0) { set_error("sumcheck_product_prove: status word %llu", (unsigned long long)status); return MZK_E_RANGE; }
+  return MZK_OK;
+}
+
+// ---- dense multilinear coefficients -> evaluation table ---------------------------------------------------------------------
+// evals[b] = sum over t subset of b of coef[t]: for every index bit, x[i | bit] += x[i].  One pass handles the g bits
+// [lo, lo + g) of a tile of 2^(g + cb) elements in LDS: 2^g rows 2^lo apart, 2^cb consecutive elements (cb = min(lo, 2): 128-byte
+// runs) per row.  The first pass takes bits [0, MLE_TILE_LOG) of consecutive tiles; every tile is read and written by one workgroup,
+// so a pass may run in place.
+constexpr int MLE_TILE_LOG = 10;
+constexpr int MLE_THREADS = 256;
+__global__ __launch_bounds__(MLE_THREADS) void k_mle_pass(const u32* in, u32* out, int lo, int g, int cb) {
+  __shared__ u32 X[1 << MLE_TILE_LOG][8];
+  const int tid = threadIdx.x;
+  const int elems = 1 << (g + cb);
+  const size_t tile = blockIdx.x;
+  const size_t t_low = tile & (((size_t)1 << (lo - cb)) - 1), t_high = tile >> (lo - cb);
+  const size_t base = (t_high << (lo + g)) | (t_low << cb);
+  for (int e = tid; e < elems; e += MLE_THREADS) {
+    const size_t idx = base | ((size_t)(e >> cb) << lo) | (size_t)(e & ((1 << cb) - 1));
+    const uint4* p = reinterpret_cast<const uint4*>(in + 8 * idx);
+    const uint4 a = p[0], b = p[1];
+    X[e][0] = a.x; X[e][1] = a.y; X[e][2] = a.z; X[e][3] = a.w; X[e][4] = b.x; X[e][5] = b.y; X[e][6] = b.z; X[e][7] = b.w;
+  }
+  for (int st = 0; st < g; st++) {
+    __syncthreads();
+    const int bit = 1 << (cb + st);
+    for (int q = tid; q < elems / 2; q += MLE_THREADS) {
+      const int e0 = ((q & ~(bit - 1)) << 1) | (q & (bit - 1)), e1 = e0 | bit;
+      const SE v = fe_reduce<SP>(fe_add<SP>(fe_unpack<SP>(X[e0]), fe_unpack<SP>(X[e1])));
+      fe_pack<SP>(v, X[e1]);
+    }
+  }
+  __syncthreads();
+  for (int e = tid; e < elems; e += MLE_THREADS) {
+    const size_t idx = base | ((size_t)(e >> cb) << lo) | (size_t)(e & ((1 << cb) - 1));
+    uint4* p = reinterpret_cast<uint4*>(out + 8 * idx);
+    p[0] = make_uint4(X[e][0], X[e][1], X[e][2], X[e][3]);
+    p[1] = make_uint4(X[e][4], X[e][5], X[e][6], X[e][7]);
+  }
+}
+
+static int mle_check(size_t el) {
+  if (el > (size_t)mzk_tx::SCP_MAX_VARS) { set_error("mle_evals_from_coeffs: %zu variables (at most %d)", el, mzk_tx::SCP_MAX_VARS); return MZK_E_LENGTH; }
+  return MZK_OK;
+}
+static int mle_dev_impl(const void* d_coef, size_t el, void* d_evals, hipStream_t s) {
+  const size_t n = (size_t)1 << el;
+  if (el == 0) {
+    if (d_coef != d_evals) MZK_HIP(hipMemcpyAsync(d_evals, d_coef, 32, hipMemcpyDeviceToDevice, s));
+    return MZK_OK;
+  }
+  const u32* in = (const u32*)d_coef;
+  for (int lo = 0; lo < (int)el;) {
+    const int cb = lo < 2 ? lo : 2;
+    const int g = (int)el - lo < MLE_TILE_LOG - cb ? (int)el - lo : MLE_TILE_LOG - cb;
+    hipLaunchKernelGGL(k_mle_pass, dim3((unsigned)(n >> (g + cb))), dim3(MLE_THREADS), 0, s, in, (u32*)d_evals, lo, g, cb);
+    in = (const u32*)d_evals;
+    lo += g;
+  }
+  MZK_HIP(hipGetLastError());
+  return MZK_OK;
+}
+
+}  // namespace mzk
+
+extern "C" {
+
+int mzk_sumcheck_product_layout(size_t num_vars, size_t num_factors, size_t max_degree, size_t header_len, uint64_t* offsets, uint64_t* sizes,
+                                uint64_t* total_bytes) {
+  mzk_tx::ScpLayout L;
+  MZK_TRY(mzk::scp_check(num_vars, num_factors, max_degree, header_len, &L));
+  for (int q = 0; q < mzk_tx::SCP_COUNT; q++) {
+    if (offsets) offsets[q] = L.off[q];
+    if (sizes) sizes[q] = L.size[q];
+  }
+  if (total_bytes) *total_bytes = L.total;
+  return MZK_OK;
+}
+int mzk_sumcheck_product_prove(const uint64_t* tables, size_t num_vars, size_t num_factors, size_t max_degree, const uint8_t* header, size_t header_len,
+                               size_t header_objects, uint8_t* proof_out, size_t proof_cap) {
+  return mzk::scp_prove_impl(tables, false, num_vars, num_factors, max_degree, header, header_len, header_objects, proof_out, proof_cap, nullptr);
+}
+int mzk_sumcheck_product_prove_dev(const void* d_tables, size_t num_vars, size_t num_factors, size_t max_degree, const uint8_t* header, size_t header_len,
+                                   size_t header_objects, void* d_proof, size_t proof_cap, void* stream) {
+  return mzk::scp_prove_impl(d_tables, true, num_vars, num_factors, max_degree, header, header_len, header_objects, d_proof, proof_cap,
+                             (hipStream_t)stream);
+}
+int mzk_mle_evals_from_coeffs(const uint64_t* coef, size_t num_vars, uint64_t* evals) {
+  using namespace mzk;
+  if (!coef || !evals) { set_error("mle_evals_from_coeffs: null pointer"); return MZK_E_ARG; }
+  MZK_TRY(mle_check(num_vars));
+  const size_t n = (size_t)1 << num_vars;
+  const HostField* fr = host_field(MZK_FIELD_FR);
+  for (size_t i = 0; i < n; i++)
+    if (!h_is_canonical(fr, coef + 4 * i)) { set_error("mle_evals_from_coeffs: coefficient %zu not canonical", i); return MZK_E_RANGE; }
+  MZK_ENTER();
+  hipStream_t s = ctx().stream;
+  WsGuard wsg(s);
+  void* buf;
+  MZK_TRY(ws_get(WS_MISC_F, n * 32, &buf));
+  MZK_HIP(hipMemcpyAsync(buf, coef, n * 32, hipMemcpyHostToDevice, s));
+  MZK_TRY(mle_dev_impl(buf, num_vars, buf, s));
+  return d2h_sync(evals, buf, n * 32, s);
+}
+int mzk_mle_evals_from_coeffs_dev(const void* d_coef, size_t num_vars, void* d_evals, void* stream) {
+  using namespace mzk;
+  if (!d_coef || !d_evals) { set_error("mle_evals_from_coeffs: null pointer"); return MZK_E_ARG; }
+  MZK_TRY(mle_check(num_vars));
+  if (((uintptr_t)d_coef & 15) || ((uintptr_t)d_evals & 15)) { set_error("mle_evals_from_coeffs: buffers need 16-byte alignment"); return MZK_E_ARG; }
+  MZK_ENTER();
+  return mle_dev_impl(d_coef, num_vars, d_evals, (hipStream_t)stream);
+}
+
+}  // extern "C"

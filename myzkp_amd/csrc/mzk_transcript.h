@@ -8,7 +8,7 @@
 //   F::sample / sample_index  acc = (acc << 8) ^ b over the bytes with a wrapping usize: the LAST 8 bytes read big-endian.
 //   sample_indices    Blake2b-256 (unkeyed, 12 rounds) of seed || counter as u64 LE.
 //
-// The Keccak permutation is not here: the kernels use mzk_merkle.hip's lane-pair permutation, the host the plain one below.
+// The Keccak permutation is not here: the kernels use the lane-pair permutation of mzk_keccak_pair.h, the host tests a plain one.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>

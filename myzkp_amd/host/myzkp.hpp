@@ -1004,4 +1004,66 @@ SumCheckProof prove_sumcheck(const std::vector<FqOrder>& coefs, const FqOrder& h
 
 }  // namespace batch
 
+// ---- examples/sumcheck: SumCheckProverGPU::prove (prover.rs:79-247) over evaluation tables -----------------------------------
+// The reference turns its MPolynomial factors into tables itself and pushes their bincode into the proof stream first; that bincode
+// is a HashMap in the iteration order of one process, so here the caller brings both: every factor's table over {0,1}^el (variable
+// 0 the most significant index bit) and the objects pushed before round 0.  The rounds, the transcript and the challenges run on the
+// device in one call (mzk_sumcheck_product_prove).
+typedef std::vector<std::vector<uint8_t>> StreamObject;     // one FiatShamirTransformer::push: a Vec<Vec<u8>>
+struct SumCheckProverGPU {
+  static std::vector<uint8_t> bincode_usize(size_t v) {
+    std::vector<uint8_t> b(8);
+    for (int i = 0; i < 8; i++) b[i] = (uint8_t)((uint64_t)v >> (8 * i));
+    return b;
+  }
+  // prover.rs:108-122: max_degree, num_factors, num_variables, then bincode(factor) of every factor (the caller's bytes)
+  static std::vector<StreamObject> reference_header(size_t max_degree, size_t num_variables, const std::vector<std::vector<uint8_t>>& factor_bytes) {
+    std::vector<StreamObject> h = {{bincode_usize(max_degree)}, {bincode_usize(factor_bytes.size())}, {bincode_usize(num_variables)}};
+    for (const auto& f : factor_bytes) h.push_back({f});
+    return h;
+  }
+  // the objects in stream form: per object its u64 string count, then u64 length + bytes per string
+  static std::vector<uint8_t> frame_header(const std::vector<StreamObject>& objects) {
+    std::vector<uint8_t> out;
+    auto put = [&](uint64_t v) { for (int i = 0; i < 8; i++) out.push_back((uint8_t)(v >> (8 * i))); };
+    for (const auto& obj : objects) {
+      put(obj.size());
+      for (const auto& s : obj) { put(s.size()); out.insert(out.end(), s.begin(), s.end()); }
+    }
+    return out;
+  }
+  // evals_over_boolean_hypercube (utils.rs) of a dense multilinear polynomial: coef[t] multiplies the x_i whose bit (el-1-i) of t is set
+  static std::vector<FqOrder> evals_over_boolean_hypercube(const std::vector<FqOrder>& coef) {
+    size_t el = 0;
+    while (((size_t)1 << el) < coef.size()) el++;
+    if (coef.size() != (size_t)1 << el) throw Panic(MZK_E_NOT_POW2, "evals_over_boolean_hypercube: 2^num_vars coefficients");
+    auto c = to_wire(coef);
+    std::vector<uint64_t> out(c.size() + 4);
+    expect(mzk_mle_evals_from_coeffs(c.data(), el, out.data()));
+    return from_wire<FqOrder>(out, coef.size());
+  }
+  // (claimed_sum, transcript.serialize()); tables[f] = factor f's 2^el values
+  std::pair<FqOrder, std::vector<uint8_t>> prove(size_t max_degree, const std::vector<std::vector<FqOrder>>& tables, const std::vector<StreamObject>& header) const {
+    const size_t k = tables.size(), n = k ? tables[0].size() : 0;
+    size_t el = 0;
+    while (((size_t)1 << el) < n) el++;
+    std::vector<uint64_t> flat;
+    for (const auto& t : tables) {
+      if (t.size() != n || n != (size_t)1 << el) throw Panic(MZK_E_LENGTH, "SumCheckProverGPU::prove: every factor needs 2^num_vars values");
+      for (const auto& v : t) flat.insert(flat.end(), v.value.begin(), v.value.end());
+    }
+    const std::vector<uint8_t> h = frame_header(header);
+    uint64_t off[MZK_SCP_SECTIONS], size[MZK_SCP_SECTIONS], total = 0;
+    expect(mzk_sumcheck_product_layout(el, k, max_degree, h.size(), off, size, &total));
+    std::vector<uint8_t> proof(total);
+    expect(mzk_sumcheck_product_prove(flat.data(), el, k, max_degree, h.data(), h.size(), header.size(), proof.data(), proof.size()));
+    FqOrder sum;
+    std::memcpy(sum.value.data(), &proof[off[MZK_SCP_SUM]], 32);
+    uint64_t len = 0;
+    std::memcpy(&len, &proof[off[MZK_SCP_TRANSCRIPT_LEN]], 8);
+    const uint8_t* tx = &proof[off[MZK_SCP_TRANSCRIPT]];
+    return {sum, std::vector<uint8_t>(tx, tx + len)};
+  }
+};
+
 }  // namespace myzkp
