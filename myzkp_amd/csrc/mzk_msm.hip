@@ -34,7 +34,7 @@ static const MsmKnobs& msm_knobs() {
   static const MsmKnobs k = [] {
     const MsmKnobs d;
     return MsmKnobs{tune_int("MZK_GLV_C", d.glv_c), tune_int("MZK_SMALL_SCAN", d.small_scan), tune_int("MZK_SCAN_MAX_LOG", d.scan_max_log),
-                    tune_int("MZK_ACC_PREFETCH", d.acc_prefetch), tune_int("MZK_ACC_SEG", d.acc_seg), tune_int("MZK_COARSE_LOG_20", d.coarse_log_20),
+                    tune_int("MZK_ACC_SEG", d.acc_seg), tune_int("MZK_COARSE_LOG_20", d.coarse_log_20),
                     tune_int("MZK_COARSE_LOG_17", d.coarse_log_17), tune_int("MZK_PER_FINE", d.per_fine), tune_int("MZK_SORT_SCAN_FREE", d.sort_scan_free),
                     tune_int("MZK_COMBINE_WIDE_MIN_LOG", d.combine_wide_min_log)};
   }();
@@ -931,14 +931,16 @@ static int launch_exclusive_scan(const u32* in, u32* out, size_t n, u32* scratch
 // slots are unique, and all partials of bucket b sit in the contiguous slot range
 // [offsets[b] / seg + b, (offsets[b+1] - 1) / seg + b] -- pass 2 sums that range (every slot of that range is
 // written: segment t overlaps bucket b exactly when slot t + b lies in it).
-// `seg` is chosen by the host so that the grid is ONE full round of resident waves (see accumulate_segment): the
-// kernel is a long dependent loop per lane, so a partial second round would run at a fraction of the occupancy.
+// `seg` is chosen by the host (msm_plan, mzk_msm_plan.h: what the grid is sized for and how many waves are resident).
 //
-// PREFETCH = true keeps the next entry's point in 16 extra registers (139 VGPRs -> 3 waves per SIMD); false loads the
-// point where it is used (123 VGPRs -> 4 waves per SIMD) and leaves the latency to the other three waves.
+// The loop is a two-deep software pipeline (seg_walk, mzk_msm_plan.h: the index logic, which the host checks on its own): while entry e
+// is added, the 64-byte table row of entry e + 1 and entries[e + 2] are on their way, each issued one whole mixed addition (~2200
+// instructions) before it is needed, and the end of the next bucket is loaded when a bucket begins.  Practically every row comes
+// from beyond L2, and a wave that is alone on its SIMD -- the launch's second round of workgroups -- has nothing else to cover that
+// latency with.  The row buffer is free for the next row as soon as the current row is converted into the point that is added, so
+// there is one buffer and no copy.
 // SENT (the one-kernel sort of the grid-batched commitments): a polynomial's entry region has a fixed capacity and its unused tail
 // is filled with MANY_SENTINEL entries, which are skipped without touching the table.
-constexpr u32 MANY_SENTINEL = 0xffffffffu;
 // Segment length as the kernels see it.  The host sizes `seg` for the MOST entries the scalars can have (every digit non-zero); short
 // or sparse scalars -- bits, bytes, 64-bit values, half of them zero -- emit a fraction of that, and with the host's length the
 // entries would fill the first few workgroups' lanes with full-length chains while the other CUs idle (2^20 16-bit scalars: 1/15 of
@@ -951,64 +953,41 @@ __device__ __forceinline__ u32 segment_length(u32 seg_host, u32 t_max, u32 total
   const u32 v = (total_entries + t_max - 1) / t_max;
   return v < SEG_MIN ? SEG_MIN : v;
 }
-template <bool PREFETCH, bool SENT = false>
-__global__ __launch_bounds__(256) void k_seg_accumulate(const u32* __restrict__ points_mont, const u32* __restrict__ offsets,
+template <bool SENT = false>
+__global__ __launch_bounds__(256, 3) void k_seg_accumulate(const u32* __restrict__ points_mont, const u32* __restrict__ offsets,
                                                          const u32* __restrict__ entries, u32* __restrict__ slots, size_t nbuckets,
                                                          u32 seg_host, u32 t_max) {
   const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   const u32 total_entries = offsets[nbuckets];
-  const u32 seg = segment_length(seg_host, t_max, total_entries);
-  const u64 e0w = (u64)t * seg;
-  if (e0w >= total_entries) return;
-  const u32 e0 = (u32)e0w;
-  const u32 e1 = (e0w + seg < total_entries) ? e0 + seg : total_entries;
-  // bucket of entry e0: last b with offsets[b] <= e0
-  size_t lo = 0, hi = nbuckets;  // invariant: offsets[lo] <= e0 < offsets[hi] (offsets[nbuckets] = total)
-  while (hi - lo > 1) {
-    const size_t mid = (lo + hi) >> 1;
-    if (offsets[mid] <= e0) lo = mid; else hi = mid;
-  }
-  size_t b = lo;
-  u32 bend = offsets[b + 1];
+  u32 e0, e1;
+  if (!seg_span(t, segment_length(seg_host, t_max, total_entries), total_entries, &e0, &e1)) return;
+  const auto offset_at = [&](size_t b) __attribute__((always_inline)) { return offsets[b]; };
   Xyzz acc = xyzz_inf();
-  u32 ent_next = entries[e0];
-  u32 wn[16];
-  if (PREFETCH) {
-    // software pipeline: the point of entry e+1 is requested before the ~3000-instruction madd of entry e,
-    // so the dependent entries[] -> points[] gather is in flight behind arithmetic instead of in front of it
-    const size_t idx = ent_next & 0x7fffffffu;
-    load_words8(points_mont + idx * 16, wn);
-    load_words8(points_mont + idx * 16 + 8, wn + 8);
-  }
-  for (u32 e = e0; e < e1; e++) {
-    const u32 ent = ent_next;
-    u32 w[16];
-    if (PREFETCH) {
+  u32 w[16];                // the row buffer
+  Affine pt;                // the current entry's point, taken out of the buffer
+  bool skip = false;
+  seg_walk<SENT>(
+      e0, e1, seg_first_bucket(offset_at, nbuckets, e0), nbuckets, [&](u32 e) __attribute__((always_inline)) { return entries[e]; }, offset_at,
+      [&](u32 ref) __attribute__((always_inline)) {
+        const size_t idx = ref & 0x7fffffffu;
+        load_words8(points_mont + idx * 16, w);
+        load_words8(points_mont + idx * 16 + 8, w + 8);
+      },
+      [&](u32 ent) __attribute__((always_inline)) {
+        // the wait for the row belongs HERE, in front of the next request and of the flush (an empty statement that reads the words
+        // pins it: the conversion below could sink behind the flush's stores, and the wait with it)
 #pragma unroll
-      for (int k = 0; k < 16; k++) w[k] = wn[k];
-    } else {
-      const size_t idx = (SENT && ent == MANY_SENTINEL) ? 0 : (ent & 0x7fffffffu);
-      load_words8(points_mont + idx * 16, w);
-      load_words8(points_mont + idx * 16 + 8, w + 8);
-    }
-    if (e + 1 < e1) {
-      ent_next = entries[e + 1];
-      if (PREFETCH) {
-        const size_t idx = ent_next & 0x7fffffffu;
-        load_words8(points_mont + idx * 16, wn);
-        load_words8(points_mont + idx * 16 + 8, wn + 8);
-      }
-    }
-    if (e >= bend) {
-      xyzz_gstore_raw(slots, t + b, acc);
-      acc = xyzz_inf();
-      do { b++; bend = offsets[b + 1]; } while (e >= bend);
-    }
-    if (affine_words_is_inf(w)) continue;  // infinity contributes nothing (curve.rs:107-109)
-    if (SENT && ent == MANY_SENTINEL) continue;
-    acc = xyzz_madd_signed_with<FeAsm>(acc, affine_load_mont(w), (ent >> 31) != 0);
-  }
-  xyzz_gstore_raw(slots, t + b, acc);
+        for (int k = 0; k < 16; k++) asm volatile("" : "+v"(w[k]));
+        skip = affine_words_is_inf(w) || (SENT && ent == MANY_SENTINEL);      // infinity contributes nothing (curve.rs:107-109)
+        pt = affine_load_mont(w);
+      },
+      [&](size_t b) __attribute__((always_inline)) {
+        xyzz_gstore_raw(slots, t + b, acc);
+        acc = xyzz_inf();
+      },
+      [&](u32, u32 ent, size_t) __attribute__((always_inline)) {
+        if (!skip) acc = xyzz_madd_signed_with<FeAsm>(acc, pt, (ent >> 31) != 0);
+      });
 }
 // pass 2: buckets[b] = sum of slots [offsets[b] / seg + b, (offsets[b+1] - 1) / seg + b]   (inclusive end:
 // the last entry of bucket b is offsets[b+1]-1)
@@ -1674,12 +1653,7 @@ int msm_dev_impl(const void* d_scalars, const void* d_points, size_t n, int poin
     MZK_TRY(prepare());
     prof_begin(s, MZK_PH_MSM_ACCUMULATE);
     // the true entry count lives in offsets[NB] on the device; lanes past it exit (E_max bounds it)
-#ifdef MZK_TUNING
-    if (P.prefetch)
-      hipLaunchKernelGGL(k_seg_accumulate<true>, dim3((unsigned)((P.T + 255) / 256)), dim3(256), 0, s, pts, offsets, entries, slots, P.NB, P.seg, P.t_max);
-    else
-#endif
-      hipLaunchKernelGGL(k_seg_accumulate<false>, dim3((unsigned)((P.T + 255) / 256)), dim3(256), 0, s, pts, offsets, entries, slots, P.NB, P.seg, P.t_max);
+    hipLaunchKernelGGL(k_seg_accumulate<false>, dim3((unsigned)((P.T + 255) / 256)), dim3(256), 0, s, pts, offsets, entries, slots, P.NB, P.seg, P.t_max);
     prof_end(s, MZK_PH_MSM_ACCUMULATE);
     prof_begin(s, MZK_PH_MSM_SEG_COMBINE);
     if (P.combine_wide)
@@ -1823,7 +1797,7 @@ __global__ __launch_bounds__(MANY_THREADS) void k_many_scatter(const u32* __rest
 // Polynomials of at most MANY_CHUNK coefficients: count, scan and scatter in ONE launch.  Workgroup j owns polynomial j and the entry
 // region [j CAP, (j + 1) CAP), CAP = n NWIN: LDS histogram (first walk), exclusive scan inside the workgroup, bucket offsets
 // j CAP + prefix (no global scan: the regions have a fixed size), placement through LDS cursors (second walk), and the unused tail
-// of the region -- zero digits emit nothing -- filled with sentinels, which k_seg_accumulate<.., SENT> skips and bucket_end (tails[j]) keeps
+// of the region -- zero digits emit nothing -- filled with sentinels, which k_seg_accumulate<SENT> skips and bucket_end (tails[j]) keeps
 // out of the last bucket's sum.  One coefficient per lane (1024 lanes: at 256 polynomials the kernel is one workgroup per CU, i.e.
 // latency) and the sorted region staged in LDS (<= 128 KiB) and copied out as one stream: **19 us** at 256 x 2^10 against 17 + 10 +
 // 35 us and three more launch gaps for the count / scan / scatter form (placed directly into global memory it was 42 us: 32
@@ -1961,7 +1935,7 @@ int msm_many_dev_impl(const void* d_scalars, size_t n, size_t stride_elems, size
     // (the one-kernel sort's regions have a fixed capacity, sentinels included: the host's segment length stands there)
     const u32 t_max = one_kernel_sort ? 0u : (u32)T;
     if (one_kernel_sort)
-      hipLaunchKernelGGL((k_seg_accumulate<false, true>), dim3((unsigned)((T + 255) / 256)), dim3(256), 0, s, (const u32*)d_tables, (const u32*)compact, (const u32*)entries,
+      hipLaunchKernelGGL(k_seg_accumulate<true>, dim3((unsigned)((T + 255) / 256)), dim3(256), 0, s, (const u32*)d_tables, (const u32*)compact, (const u32*)entries,
                          slots, NBtot, seg, t_max);
     else
       hipLaunchKernelGGL(k_seg_accumulate<false>, dim3((unsigned)((T + 255) / 256)), dim3(256), 0, s, (const u32*)d_tables, (const u32*)compact, (const u32*)entries,

@@ -21,6 +21,7 @@ constexpr int SCALAR_BITS = 254;
 constexpr int MAX_WINDOWS = 32;
 constexpr int GLV_MAG_BITS = 126;      // |k1|, |k2| < 2^126 (mzk_glv.h)
 constexpr int SLOT_WORDS = 36;         // a segment partial: 4 x 9 raw limbs (mzk_msm.hip)
+constexpr int ACC_RESIDENT_WAVES = 3;  // waves per SIMD the accumulate's grid is sized for (msm_plan); k_seg_accumulate's __launch_bounds__(256, 3) keeps them resident
 
 // Bucket layout.  Generic MSM: bucket = window * 2^(c-1) + |digit| - 1, entry = point index.
 // Fixed-base MSM over precomputed tables T[w][i] = 2^(c w) P_i: every window shares ONE bucket set,
@@ -106,8 +107,7 @@ struct MsmKnobs {
   int glv_c = 0;                  // MZK_GLV_C: force the generic layout's width
   int small_scan = 1;             // MZK_SMALL_SCAN: 0 = A/B against the sorted path
   int scan_max_log = 14;          // MZK_SCAN_MAX_LOG
-  int acc_prefetch = -1;          // MZK_ACC_PREFETCH (tools/timing/acc_sweep.py sweeps it and MZK_ACC_SEG)
-  int acc_seg = 0;                // MZK_ACC_SEG: a fixed segment length
+  int acc_seg = 0;                // MZK_ACC_SEG: a fixed segment length (tools/timing/acc_sweep.py sweeps it)
   int coarse_log_20 = 10;         // MZK_COARSE_LOG_20: 8 = the 256-bin form at 20 bits too
   int coarse_log_17 = 9;          // MZK_COARSE_LOG_17: 8 = the 256-bin form with 8-byte records
   int per_fine = 0;               // MZK_PER_FINE: records per fine workgroup (tools/timing/window_sweep.py)
@@ -139,7 +139,7 @@ struct MsmPlan {
   // accumulate
   uint32_t seg = 0, t_max = 0;
   size_t T = 0, nslots = 0, max_heavy = 0, slot_region_words = 0;    // (one chunk's slots + heavy list)
-  bool prefetch = false, combine_wide = false;
+  bool combine_wide = false;
   MsmSizing own{}, alloc{};                    // what this call touches; what its buffers are sized for (the largest chunk in chunk mode)
   MsmWsBytes ws{}, ws_used{};                  // requests; the same formula over `own` (no chunk outgrows its region)
   MsmPlan& fail(const char* fmt, size_t a = 0, size_t b = 0, size_t c = 0) { err = MZK_E_ARG; snprintf(msg, sizeof msg, fmt, a, b, c); return *this; }
@@ -214,13 +214,14 @@ static inline MsmPlan msm_plan(size_t n, size_t n_shape, size_t n_alloc, int poi
   if (ref_max > ((size_t)1 << 31) || E_max >= ((size_t)1 << 32))
     return P.fail("msm: %zu pairs x %zu windows (table stride %zu) exceed the 31-bit point references / 32-bit entry offsets", n, (size_t)L.nwin, table_stride);
 
-  // Segment length: one lane per segment, sized as if four waves per SIMD were resident (E / (CUs * 4 * 4 * 64), >= 16).  Round 2's
-  // kernel had 123 VGPRs and the grid was exactly one round of resident waves; with the signed mixed addition of round 3 the
-  // compiler takes 140 VGPRs (three waves per SIMD), and the same segment length is still the fastest of the variants measured
-  // (profiles/r03o_accumulate_occupancy_ab.txt: shipped 1.05-1.06 ms at 2^20; __launch_bounds__(256, 4) = 128 VGPRs + 64 B of
-  // scratch 1.07-1.10; segments sized for three waves 1.07 with a cheaper segment combine: equal in total).
-  P.prefetch = kn.acc_prefetch > 0;
-  const size_t resident_lanes = (size_t)num_cu * 4 * (P.prefetch ? 3 : 4) * 64;
+  // Segment length: one lane per segment, the grid ONE round of the waves that are resident: three per SIMD at the kernel's 159 VGPRs
+  // (E / (CUs * 4 * 3 * 64), >= 16).  Until round 7 the grid was sized for four -- three quarters of the workgroups at once, then the
+  // last quarter one wave per SIMD -- and measured equal to this form twice: with the loop that exposed a load per iteration
+  // (profiles/r03o_accumulate_occupancy_ab.txt) and with the pipelined one (profiles/round7_accumulate_pipeline_ab.txt: 1.3643 against
+  // 1.3622 ms per 2^20 commit, 2^24 and the generic MSM equal too).  The accumulate alone is ~10 us faster with the second round (its
+  // workgroups fill the first round's ragged end), the segment combine ~10 us faster without it (a quarter fewer partials): of two
+  // equal forms the one with the cheaper combine ships.
+  const size_t resident_lanes = (size_t)num_cu * 4 * ACC_RESIDENT_WAVES * 64;
   size_t seg = (E_max + resident_lanes - 1) / resident_lanes;
   seg = kn.acc_seg > 0 ? (size_t)kn.acc_seg : seg < 16 ? 16 : seg;
   P.seg = (uint32_t)seg;
@@ -288,6 +289,95 @@ static inline MsmPlan msm_plan(size_t n, size_t n_shape, size_t n_alloc, int poi
   P.coarse_c = (plain_merged && (L.c == 16 || L.c == 17 || L.c == 20)) ? L.c : 0;     // the default widths by SRS size
   P.scatter_staged = P.coarse_c != 0;
   return msm_sized(P, regions);
+}
+
+// ---- the segment walk of k_seg_accumulate ------------------------------------------------------------------------------------------
+// Which entry a lane adds, which loads it has in flight meanwhile and where it stops -- the index logic of the kernel's loop, templated
+// over its loads so that the host runs the same code over arrays of exactly the kernel's sizes (tests/hostcheck/seg_walk_shim.cpp).
+#if defined(__HIPCC__)
+#define MZK_HD __host__ __device__ __forceinline__
+#else
+#define MZK_HD inline
+#endif
+constexpr uint32_t MANY_SENTINEL = 0xffffffffu;      // filler behind a polynomial's real entries (k_many_sort1): never a table row
+
+// The segment of lane t: entries [e0, e1) of `total`; false when the lane has none (it must not load anything then).
+MZK_HD bool seg_span(uint64_t t, uint32_t seg, uint32_t total, uint32_t* e0, uint32_t* e1) {
+  const uint64_t e0w = t * seg;
+  if (e0w >= total) return false;
+  *e0 = (uint32_t)e0w;
+  *e1 = (e0w + seg < total) ? (uint32_t)e0w + seg : total;
+  return true;
+}
+
+// Bucket of entry e: the b with offsets[b] <= e < offsets[b + 1] (offsets[0] = 0 <= e < offsets[nbuckets]: the caller's contract).
+// K-ary: the K - 1 pivots of a level do not depend on one another, so a level costs ONE load latency -- four levels for 2^16 buckets
+// and five up to 2^20 with K = 16, five up to 2^25 with K = 32 (seg_first_bucket), where the binary search had 16 to 25 in a row.
+// A pivot past hi is clamped to hi, which is above e by the invariant: no branch, and no load outside [lo, hi].
+template <int K, class Offset>
+MZK_HD size_t seg_bucket_search(Offset offset_at, size_t nbuckets, uint32_t e) {
+  size_t lo = 0, hi = nbuckets;      // invariant: offsets[lo] <= e < offsets[hi]
+  while (hi - lo > 1) {
+    const size_t step = (hi - lo + K - 1) / K;
+    uint32_t v[K];
+#if defined(__HIPCC__)
+#pragma unroll
+#endif
+    for (int j = 1; j < K; j++) v[j] = offset_at(lo + j * step < hi ? lo + j * step : hi);
+    size_t below = 0;                // the pivots at or below e are a prefix: offsets is sorted
+#if defined(__HIPCC__)
+#pragma unroll
+#endif
+    for (int j = 1; j < K; j++) below += v[j] <= e ? 1 : 0;
+    lo += below * step;
+    if (lo + step < hi) hi = lo + step;
+  }
+  return lo;
+}
+template <class Offset>
+MZK_HD size_t seg_first_bucket(Offset offset_at, size_t nbuckets, uint32_t e) {
+  return nbuckets <= ((size_t)1 << 20) ? seg_bucket_search<16>(offset_at, nbuckets, e) : seg_bucket_search<32>(offset_at, nbuckets, e);
+}
+
+// The walk of one lane over entries [e0, e1), e0 < e1 <= offsets[nbuckets], starting in bucket b (seg_first_bucket(e0)), two deep:
+// while entry e is added, the table row of entry e + 1 and entries[e + 2] are on their way.  Every load is issued one whole addition
+// before its value is needed; the entry goes first because the memory counter retires in order and the next row's address is formed
+// from it.  Likewise the end of the NEXT bucket is loaded when a bucket begins, so a bucket change waits for memory only across an
+// empty bucket.  There is ONE row buffer and nothing is copied: a step first takes the current row out of the buffer -- the caller
+// converts it into the point it adds, which it has to do anyway -- and only then asks for the next row into the same buffer.
+// The look-ahead is unconditional -- a branch around a load would make the compiler wait for the memory counter as if the load had
+// not been issued, which drains the pipeline -- and clamped instead: near the end of the segment it reads the segment's LAST entry
+// and that entry's row again, never an entry at or past e1 and never a bucket end past offsets[nbuckets]; with SENT a MANY_SENTINEL
+// entry asks for row 0 in its place, which every table has, and what the buffer then holds is not used.
+//   entry_at(e), offset_at(b)    the loads
+//   take_row(ent)                the buffer holds the row of the current entry `ent` (unless that is a sentinel): take it out.  This
+//                                is the step's only wait for memory, and everything it can wait for was issued an addition ago
+//   issue_row(ref)               request the table row of entry word `ref` into the buffer
+//   flush(b)                     bucket b is complete as far as this segment goes: store the accumulator, start a new one
+//   add(e, ent, b)               entry e (word `ent`, the row just taken) belongs to bucket b
+template <bool SENT, class Entry, class Offset, class IssueRow, class TakeRow, class Flush, class Add>
+MZK_HD void seg_walk(uint32_t e0, uint32_t e1, size_t b, size_t nbuckets, Entry entry_at, Offset offset_at, IssueRow issue_row, TakeRow take_row,
+                     Flush flush, Add add) {
+  const auto row_ref = [](uint32_t ent) { return (SENT && ent == MANY_SENTINEL) ? 0u : ent; };
+  const auto end_after_next = [&](size_t bb) { return offset_at(bb + 2 <= nbuckets ? bb + 2 : nbuckets); };
+  uint32_t ent = entry_at(e0);
+  uint32_t ent1 = entry_at(e1 - e0 > 1 ? e0 + 1 : e0);
+  issue_row(row_ref(ent));
+  uint32_t bend = offset_at(b + 1), bend1 = end_after_next(b);
+  for (uint32_t e = e0; e < e1; e++) {
+    take_row(ent);
+    const uint32_t ent2 = entry_at(e1 - e > 2 ? e + 2 : e1 - 1);      // (e < e1: the difference cannot wrap)
+    issue_row(row_ref(ent1));
+    if (e >= bend) {
+      flush(b);
+      b++, bend = bend1;
+      while (e >= bend) b++, bend = offset_at(b + 1);     // across empty buckets only: these loads are waited for
+      bend1 = end_after_next(b);                          // (one load, outside the loop: nothing in this step waits for it)
+    }
+    add(e, ent, b);
+    ent = ent1, ent1 = ent2;
+  }
+  flush(b);
 }
 
 // Chunk mode (msm_chunked_impl) covers the problems whose every chunk takes the two-level sort with one bucket set: the generic layout

@@ -1,6 +1,8 @@
-"""A/B of k_seg_accumulate variants on one box: PREFETCH on/off x segment length, merged (SRS tables) and generic MSM at
-2^LOG pairs.  Each configuration runs in its own process (the knobs are read once): python tools/timing/acc_sweep.py [LOG]
-    child: python tools/timing/acc_sweep.py --child LOG   (MZK_ACC_PREFETCH / MZK_ACC_SEG in the environment)"""
+"""A/B of k_seg_accumulate's segment length on one box, merged (SRS tables) and generic MSM at 2^LOG pairs: the shipped sizing, fixed
+segments for four and for three resident waves per SIMD (one round of workgroups at the kernel's register count) and two off-size
+ones, ROUNDS times over, interleaved.  Needs the tuning build (MZK_HIP_LIB = libmzk_hip_tuning.so); each configuration runs in its own
+process (the knobs are read once): python tools/timing/acc_sweep.py [LOG] [ROUNDS] [SEGS = comma list, 0 = the shipped sizing]
+    child: python tools/timing/acc_sweep.py --child LOG   (MZK_ACC_SEG in the environment)"""
 import ctypes, os, subprocess, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT)
@@ -35,8 +37,8 @@ def child(lg):
         ms, cnt = ctypes.c_double(), ctypes.c_uint64()
         L.mzk_prof_read(2, ctypes.byref(ms), ctypes.byref(cnt))
         res[name] = (dt, ms.value / max(cnt.value, 1))
-    print("RESULT prefetch=%s seg=%s merged %.3f ms (accumulate+combine %.3f) generic %.3f ms (accumulate+combine %.3f) result %s" % (
-        os.environ.get("MZK_ACC_PREFETCH", "-"), os.environ.get("MZK_ACC_SEG", "auto"), res["merged"][0], res["merged"][1],
+    print("RESULT seg=%s merged %.3f ms (accumulate+combine %.3f) generic %.3f ms (accumulate+combine %.3f) result %s" % (
+        os.environ.get("MZK_ACC_SEG", "auto"), res["merged"][0], res["merged"][1],
         res["generic"][0], res["generic"][1], hex(int(out[0].item()) & 0xffffffff)), flush=True)
 
 
@@ -45,13 +47,16 @@ if __name__ == "__main__":
         child(int(sys.argv[2]))
     else:
         lg = int(sys.argv[1]) if len(sys.argv) > 1 else 20
-        E = 16 << lg
-        segs = {0: ["0"] + [str(-(-E // (256 * 4 * 4 * 64 * k))) for k in (2,)] + ["48", "96"],
-                1: ["0"] + [str(-(-E // (256 * 4 * 3 * 64 * k))) for k in (2,)] + ["64"]}
-        for pf in (0, 1):
-            for seg in segs[pf]:
-                env = dict(os.environ, MZK_ACC_PREFETCH=str(pf))
+        rounds = int(sys.argv[2]) if len(sys.argv) > 2 else 1
+        E = 15 << lg                  # entries of the merged layout at 17-bit windows (the generic layout has 16 per pair)
+        segs = sys.argv[3].split(",") if len(sys.argv) > 3 else ["0"] + [str(-(-E // (256 * 4 * w * 64))) for w in (4, 3)] + ["48", "96"]
+        for _ in range(rounds):
+            for seg in segs:
+                env = dict(os.environ)
+                env.pop("MZK_ACC_SEG", None)
                 if seg != "0":
                     env["MZK_ACC_SEG"] = seg
                 r = subprocess.run([sys.executable, os.path.abspath(__file__), "--child", str(lg)], env=env, capture_output=True, text=True, timeout=600)
                 print((r.stdout.strip().splitlines() or ["(no output) " + r.stderr[-300:]])[-1], flush=True)
+                if r.returncode != 0:          # nothing more is started on a device a child has failed on
+                    sys.exit("seg %s: child exit status %d" % (seg, r.returncode))
