@@ -4,6 +4,7 @@ recursive ntt / intt (ntt.rs:7-64), fast_coset_evaluate (ntt.rs:254-269), the le
 (fri.rs:99-400) over either field.  bincode, the transcript, Merkle and sample_indices come from fri_prove_model.  No GPU, no library.
 
 A base element is an int in [0, p); an extension element is a tuple (c0, c1, c2) of such ints for c0 + c1 x + c2 x^2."""
+import numpy as np
 import fri_prove_model as fpm
 
 P = (1 << 64) - (1 << 32) + 1
@@ -296,3 +297,92 @@ def verify(F, proof, omega, offset, domain_length, expansion_factor, tests, poin
                 return False
         omega, offset = F.mul(omega, omega), F.mul(offset, offset)
     return True
+
+
+# ---- the same field on numpy uint64 arrays ------------------------------------------------------------------------------------------
+# For transforms too large for Python integers.  Canonical values (< p) in and out; the operands broadcast.  Checked against Python
+# integers in test_goldilocks_model.py.  A transform of M64X3 data with a base-field root is the M64 transform of each of its three
+# coefficient columns, so np_ntt over an (n, 3) array serves the extension as well.
+_U = np.uint64
+_P, _EPS, _M32, _S32 = _U(P), _U((1 << 32) - 1), _U((1 << 32) - 1), _U(32)
+
+
+def _operands(a, b):
+    """at least one dimension: array arithmetic wraps silently, numpy scalars warn"""
+    return np.atleast_1d(np.asarray(a, dtype=_U)), np.atleast_1d(np.asarray(b, dtype=_U))
+
+
+def np_add(a, b):
+    a, b = _operands(a, b)
+    s = a + b                                             # wraps; a + b < 2 p
+    s = s + (s < a).astype(_U) * _EPS                     # 2^64 = 2^32 - 1: the wrapped sum is below 2 p - 2^64, no second carry
+    return s - (s >= _P).astype(_U) * _P
+
+
+def np_sub(a, b):
+    a, b = _operands(a, b)
+    return (a - b) - (a < b).astype(_U) * _EPS            # a - b + 2^64 - (2^32 - 1) = a - b + p
+
+
+def np_mul(a, b):
+    """four 32 x 32 partial products -> (hi, lo) of the 128-bit product -> lo + hi_lo (2^32 - 1) - hi_hi, by 2^64 = 2^32 - 1 and 2^96 = -1"""
+    a, b = _operands(a, b)
+    a0, a1, b0, b1 = a & _M32, a >> _S32, b & _M32, b >> _S32
+    ll, lh, hl, hh = a0 * b0, a0 * b1, a1 * b0, a1 * b1
+    m1 = lh + (ll >> _S32)                                # < 2^64: (2^32 - 1)^2 + 2^32 - 1
+    m2 = hl + (m1 & _M32)
+    lo = (m2 << _S32) | (ll & _M32)
+    hi = hh + (m1 >> _S32) + (m2 >> _S32)
+    hi_lo, hi_hi = hi & _M32, hi >> _S32
+    t = lo - hi_hi
+    t = t - (lo < hi_hi).astype(_U) * _EPS                # borrowed 2^64: the wrapped value is at least 2^64 - 2^32, no second borrow
+    u = hi_lo * _EPS
+    r = t + u
+    r = r + (r < u).astype(_U) * _EPS                     # carried 2^64: the wrapped sum is below 2^64 - 2^32, no second carry
+    return r - (r >= _P).astype(_U) * _P
+
+
+def np_powers(a, n):
+    """a^0 .. a^(n-1) by doubling: the first k powers times a^k are the next k"""
+    out = np.ones(max(n, 1), dtype=_U)
+    k, ak = 1, int(a) % P
+    while k < n:
+        m = min(k, n - k)
+        out[k:k + m] = np_mul(out[:m], _U(ak))
+        ak = ak * ak % P
+        k *= 2
+    return out[:n]
+
+
+def np_ntt(x, w):
+    """X[k] = sum_j x[j] w^(j k), w of order n = len(x): iterative radix 2 (bit-reversal, then decimation-in-time stages), natural
+    order in and out, over an (n,) array or column by column over an (n, c) one"""
+    x = np.asarray(x, dtype=_U)
+    n = x.shape[0]
+    assert n and n & (n - 1) == 0, "cannot compute ntt of non-power-of-two sequence"
+    if n == 1:
+        return x.copy()
+    lg = n.bit_length() - 1
+    assert pow(int(w), n, P) == 1 and pow(int(w), n // 2, P) == P - 1
+    rev = np.zeros(n, dtype=np.int64)
+    for b in range(lg):
+        rev |= ((np.arange(n, dtype=np.int64) >> b) & 1) << (lg - 1 - b)
+    y = x[rev].reshape(n, -1)
+    c = y.shape[1]
+    pw = np_powers(w, n // 2)
+    m = 1
+    while m < n:                                          # blocks of 2 m: (u, v) -> (u + t v, u - t v), t = w_{2m}^j
+        y = y.reshape(n // (2 * m), 2, m, c)
+        tv = np_mul(y[:, 1], pw[::n // (2 * m)][None, :, None])
+        u = y[:, 0]
+        y = np.stack([np_add(u, tv), np_sub(u, tv)], axis=1)
+        m *= 2
+    return y.reshape(x.shape)
+
+
+def np_intt(x, w):
+    """n^-1 times the transform with w^-1 (ntt.rs:50-64)"""
+    n = np.asarray(x).shape[0]
+    if n == 1:
+        return np.asarray(x, dtype=_U).copy()
+    return np_mul(np_ntt(x, pow(int(w), P - 2, P)), _U(pow(n, P - 2, P)))

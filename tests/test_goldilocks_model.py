@@ -1,6 +1,7 @@
 """tests/goldilocks_model.py against facts checked here with plain integers, and its own FRI::prove / FRI::verify at the parameters of
 the reference's test_fri_efield (zkstark/fri.rs:546-594).  CPU only."""
 import random
+import numpy as np
 import pytest
 import fri_prove_model as fpm
 import goldilocks_model as gm
@@ -124,3 +125,53 @@ def test_verify_rejects_the_corrupted_codeword(efield_case):
     n, omega, offset, coef, cw = efield_case
     bad = [X3.one] * 21 + cw[21:]
     assert not gm.verify(X3, gm.prove(X3, bad, omega, offset, 16, 17), omega, offset, n, 16, 17, [])
+
+
+# ---- the numpy form of the field ------------------------------------------------------------------------------------------------
+EDGES = [0, 1, P - 1, P - 2, (1 << 32) - 1, 1 << 32, (1 << 32) + 1, P - (1 << 32), 1 << 63, (1 << 64) - (1 << 32)]
+
+
+def _check_ops(a, b):
+    A, B = np.array(a, dtype=np.uint64), np.array(b, dtype=np.uint64)
+    assert gm.np_mul(A, B).tolist() == [x * y % P for x, y in zip(a, b)]
+    assert gm.np_add(A, B).tolist() == [(x + y) % P for x, y in zip(a, b)]
+    assert gm.np_sub(A, B).tolist() == [(x - y) % P for x, y in zip(a, b)]
+
+
+def test_numpy_field_ops_on_random_pairs():
+    rng = random.Random(11)
+    n = 20000
+    _check_ops([rng.randrange(P) for _ in range(n)], [rng.randrange(P) for _ in range(n)])
+    # operands with a half of all ones or all zeros: the carries between the partial products
+    halves = [0, 1, (1 << 32) - 1, (1 << 32) - 2]
+    pick = lambda: ((rng.choice(halves) << 32) | rng.randrange(1 << 32) if rng.random() < 0.5 else (rng.randrange(1 << 32) << 32) | rng.choice(halves)) % P
+    _check_ops([pick() for _ in range(n)], [pick() for _ in range(n)])
+
+
+def test_numpy_field_ops_on_the_edge_values():
+    assert all(e < P for e in EDGES)
+    _check_ops([x for x in EDGES for _ in EDGES], [y for _ in EDGES for y in EDGES])
+    assert gm.np_mul(P - 1, np.uint64(P - 1)).tolist() == [1]               # scalars come back as one-element arrays
+
+
+def test_numpy_powers():
+    for a in (0, 1, 7, P - 1, gm.ROOT_2_32):
+        for n in (1, 2, 3, 8, 1000):
+            assert gm.np_powers(a, n).tolist() == [pow(a, i, P) for i in range(n)]
+
+
+@pytest.mark.parametrize("n", [2, 4, 32, 1024])
+def test_numpy_ntt_equals_the_literal_recursion(n):
+    rng = random.Random(n)
+    lg = n.bit_length() - 1
+    for F in (gm.M64, X3):
+        w = gm.root_of_unity(F, lg)
+        v = [F.from_words([rng.randrange(P) for _ in range(F.limbs)]) for _ in range(n)]
+        v[0], v[-1] = F.zero, F.from_words([P - 1] * F.limbs)
+        a = np.array([F.words(e) for e in v], dtype=np.uint64)              # (n, limbs)
+        w0 = F.words(w)[0]
+        assert [F.from_words(r) for r in gm.np_ntt(a, w0).tolist()] == gm.ntt(F, w, v)
+        assert [F.from_words(r) for r in gm.np_intt(a, w0).tolist()] == gm.intt(F, w, v)
+        if F.limbs == 1:                                                    # the (n,) form
+            assert gm.np_ntt(a[:, 0], w0).tolist() == gm.ntt(F, w, v)
+    assert gm.np_ntt(np.array([5], dtype=np.uint64), 1).tolist() == [5]

@@ -80,7 +80,8 @@ def test_large_sizes_vs_fast_oracle(mz, fid, lg):
 def test_noncanonical_edge_values(mz):
     # all p-1 / zeros / ones inputs; p - 2 and 2^116 - 1: every 29-bit limb of an M128 element at its maximum -- the worst case of the
     # signed lazy butterflies (limb sums up to 4 (2^29 - 1)) and, through X[0] = n x, of the borrow path of the final reduction --
-    # in every tile geometry (one pass, two small-tile passes, the 2^10-level tiles of 2^20)
+    # in every tile geometry (one pass, two small-tile passes, the 2^10-level tiles of 2^20).  A constant vector transforms to zero
+    # outside index 0, so these fills exercise no twiddle and no index: 2^15 gets its real-data check in test_gpu_ntt_splits.py
     for fid in (FR, M128):
         p = orc.MOD[fid]
         for lg in (4, 9, 12, 15, 20):
