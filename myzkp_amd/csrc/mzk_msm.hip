@@ -176,19 +176,10 @@ __device__ __forceinline__ void load_scalar_canonical(const u32* __restrict__ sc
     fe_pack<FrParams>(x, w);
   }
 }
-// digit of window `win` before carry handling: bits [c win, c win + c)
-__device__ __forceinline__ u32 raw_window(const u32* w, int win, int c) {
-  const int bit = win * c;
-  if (bit >= 256) return 0;
-  const int k = bit >> 5, s = bit & 31;
-  u64 v = w[k];
-  if (k + 1 < 8) v |= (u64)w[k + 1] << 32;
-  return (u32)(v >> s) & ((1u << c) - 1u);
-}
 // Calls emit(slot, key, payload) for every non-zero signed digit of scalar i (canonical words w).  `slot` numbers
 // the (half, window) positions of a scalar: 0 .. slots_per_scalar-1.  key = bucket index; payload = point reference
 // with the sign in bit 31.
-//   merged : windows of the full scalar, key = |d| - 1, reference = window * table_stride + i
+//   merged : windows of the full scalar, key = |d| - 1, reference = window * table_stride + i (walk_digits_whole, mzk_msm_plan.h)
 //   generic: k = k1 + k2 lambda (mzk_glv.h); windows of |k1| address point i, windows of |k2| its phi image
 //            phi_offset + i; key = window * 2^(c-1) + |d| - 1; the sign of the part flips the digit's sign
 __device__ __forceinline__ int slots_per_scalar(const DigitLayout& L) { return L.glv ? 2 * L.nwin : L.nwin; }
@@ -196,21 +187,7 @@ template <class Emit>
 __device__ __forceinline__ void walk_digits(const u32* w, const DigitLayout& L, size_t i, Emit emit) {
   const int c = L.c;
   const u32 half = 1u << (c - 1);
-  if (!L.glv) {
-    u32 carry = 0;
-    for (int win = 0; win < L.nwin; win++) {
-      u32 raw = raw_window(w, win, c) + carry;
-      u32 neg = 0, mag = raw;
-      carry = 0;
-      if (raw > half) { mag = (1u << c) - raw; neg = 1; carry = 1; }
-      if (mag != 0) {
-        const u32 key = (L.merged ? ((u32)(win % L.sets) << (c - 1)) : ((u32)win << (c - 1))) + (mag - 1);
-        const u32 payload = (L.merged ? (u32)((size_t)(win / L.sets) * L.table_stride + i) : (u32)i) | (neg << 31);
-        emit(win, key, payload);
-      }
-    }
-    return;
-  }
+  if (!L.glv) { walk_digits_whole(w, L, i, emit); return; }      // (mzk_msm_plan.h: the host runs it too)
   u32 m[2][8], sg[2];
 #pragma unroll
   for (int h = 0; h < 2; h++)
@@ -234,43 +211,7 @@ __device__ __forceinline__ void walk_digits(const u32* w, const DigitLayout& L, 
   }
 }
 
-// Signed c-bit digits without the serial carry walk: with t = k + sum_w (2^(c-1) - 1) 2^(c w) the digit of window w is
-// window_w(t) - (2^(c-1) - 1) (the carries of that ONE long addition are exactly the recoding's carries: window w overflows iff
-// raw_w + carry > 2^(c-1)), same digits as walk_digits.  Word k of the constant, C a compile-time width:
-constexpr u32 digit_bias_word(int C, int k) {
-  const int nwin = 254 / C + 1;
-  const unsigned long long hm1 = (1ull << (C - 1)) - 1;
-  unsigned long long acc = 0;
-  for (int w = 0; w < nwin; w++) {
-    const int sh = w * C - 32 * k;
-    if (sh >= 0 && sh < 32) acc |= (hm1 << sh) & 0xffffffffull;
-    else if (sh < 0 && sh > -32) acc |= hm1 >> (-sh);
-  }
-  return (u32)acc;
-}
-// walk_digits for the merged layout with a compile-time window width: the same (window, key, payload) triples in the same order,
-// from ONE long addition and NWIN independent extractions with static word indices (walk_digits' runtime window index makes
-// every word access a select chain).  Used by the coarse passes of the two-level sort and by the sortless small path.
-template <int C, class Emit>
-__device__ __forceinline__ void walk_digits_merged(const u32* w, size_t table_stride, size_t i, Emit emit) {
-  constexpr int NWIN = 254 / C + 1;
-  constexpr u32 HALF = 1u << (C - 1), MASKC = (1u << C) - 1u;
-  u32 t[9];
-  u64 cy = 0;
-#pragma unroll
-  for (int k = 0; k < 8; k++) { cy += (u64)w[k] + digit_bias_word(C, k); t[k] = (u32)cy; cy >>= 32; }
-  t[8] = (u32)cy + digit_bias_word(C, 8);
-#pragma unroll
-  for (int win = 0; win < NWIN; win++) {
-    const int bit = win * C, k = bit >> 5, sft = bit & 31;
-    const u64 pair = (u64)t[k] | ((k + 1 < 9) ? ((u64)t[k + 1] << 32) : 0ull);
-    const u32 v = (u32)(pair >> sft) & MASKC;            // digit + HALF - 1
-    if (v == HALF - 1u) continue;                        // digit 0
-    const bool neg = v < HALF - 1u;
-    const u32 mag = neg ? (HALF - 1u) - v : v - (HALF - 1u);
-    emit(win, mag - 1u, (u32)((size_t)win * table_stride + i) | ((u32)neg << 31));
-  }
-}
+// digit_bias_word and walk_digits_merged<C>, the compile-time-width walk of the merged layout: mzk_msm_plan.h
 
 // Exclusive prefix of one value per lane over a workgroup of NT lanes, and the workgroup's total: shuffles inside the waves, the
 // NT / 64 wave totals by the first wave -- two barriers (the Hillis-Steele form over LDS this replaces took 2 log2(NT) = 20 at 1024
@@ -340,15 +281,15 @@ __global__ __launch_bounds__(256) void k_digits_scatter(const u32* __restrict__ 
   walk_digits(w, L, i, [&](int slot, u32 key, u32 payload) { entries[offsets[key] + ranks[(size_t)slot * n + i]] = payload; });
 }
 
-// Merged (fixed-base) layout: one bucket set of 2^(c-1) = 32768 counters = 128 KiB fits the 160 KiB LDS of
-// a CU, so the histogram runs on LDS atomics (the returned value is the entry's rank inside this
+// Merged (fixed-base) layout: its bucket sets, 2^15 counters at the most (msm_plan: one set at 16 bits, four at 14) = 128 KiB, fit
+// the 160 KiB LDS of a CU, so the histogram runs on LDS atomics (the returned value is the entry's rank inside this
 // workgroup's share of the bucket) and no global atomic is issued at all.  Workgroup g owns scalars
 // [g * per_wg, (g+1) * per_wg); wg_hist[g][b] receives its counts.
 constexpr int LDS_SORT_THREADS = 1024;
 __global__ __launch_bounds__(LDS_SORT_THREADS) void k_digits_count_lds(const u32* __restrict__ scalars, size_t n, size_t per_wg, DigitLayout L,
                                                                       u32* __restrict__ wg_hist, u32* __restrict__ ranks) {
   extern __shared__ u32 hist[];
-  const int NBK = 1 << (L.c - 1);
+  const int NBK = L.sets << (L.c - 1);
   for (int b = threadIdx.x; b < NBK; b += LDS_SORT_THREADS) hist[b] = 0;
   __syncthreads();
   const size_t lo = (size_t)blockIdx.x * per_wg;
@@ -359,14 +300,16 @@ __global__ __launch_bounds__(LDS_SORT_THREADS) void k_digits_count_lds(const u32
     u32 w[8];
     load_scalar_canonical(scalars, i, w);
     u32 carry = 0;
+    int set = 0;                            // win % L.sets: the bucket set of the window (walk_digits_whole)
     for (int win = 0; win < L.nwin; win++) {
       u32 raw = raw_window(w, win, c) + carry;
       u32 mag = raw;
       carry = 0;
       if (raw > half) { mag = (1u << c) - raw; carry = 1; }
       u32 rank = NO_RANK;
-      if (mag != 0) rank = atomicAdd(&hist[mag - 1], 1u);
+      if (mag != 0) rank = atomicAdd(&hist[((u32)set << (c - 1)) + mag - 1], 1u);
       ranks[(size_t)win * n + i] = rank;
+      if (++set == L.sets) set = 0;
     }
   }
   __syncthreads();
@@ -390,7 +333,7 @@ __global__ __launch_bounds__(LDS_SORT_THREADS) void k_digits_scatter_lds(const u
                                                                         const u32* __restrict__ offsets, const u32* __restrict__ wg_hist,
                                                                         const u32* __restrict__ ranks, u32* __restrict__ entries) {
   extern __shared__ u32 base[];   // offsets[b] + this workgroup's prefix inside bucket b
-  const int NBK = 1 << (L.c - 1);
+  const int NBK = L.sets << (L.c - 1);
   const u32* row = wg_hist + (size_t)blockIdx.x * NBK;
   for (int b = threadIdx.x; b < NBK; b += LDS_SORT_THREADS) base[b] = offsets[b] + row[b];
   __syncthreads();
@@ -402,6 +345,7 @@ __global__ __launch_bounds__(LDS_SORT_THREADS) void k_digits_scatter_lds(const u
     u32 w[8];
     load_scalar_canonical(scalars, i, w);
     u32 carry = 0;
+    int set = 0, trow = 0;                  // win % L.sets, win / L.sets: the window's bucket set and its row of the tables
     for (int win = 0; win < L.nwin; win++) {
       u32 raw = raw_window(w, win, c) + carry;
       u32 neg = 0, mag = raw;
@@ -409,9 +353,10 @@ __global__ __launch_bounds__(LDS_SORT_THREADS) void k_digits_scatter_lds(const u
       if (raw > half) { mag = (1u << c) - raw; neg = 1; carry = 1; }
       if (mag != 0) {
         const u32 rank = ranks[(size_t)win * n + i];
-        const u32 ref = (u32)((size_t)win * L.table_stride + i);
-        entries[base[mag - 1] + rank] = ref | (neg << 31);
+        const u32 ref = (u32)((size_t)trow * L.table_stride + i);
+        entries[base[((u32)set << (c - 1)) + mag - 1] + rank] = ref | (neg << 31);
       }
+      if (++set == L.sets) set = 0, trow++;
     }
   }
 }

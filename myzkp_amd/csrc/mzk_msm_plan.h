@@ -380,6 +380,85 @@ MZK_HD void seg_walk(uint32_t e0, uint32_t e1, size_t b, size_t nbuckets, Entry 
   flush(b);
 }
 
+// ---- the digit walk of the window-table layouts ----------------------------------------------------------------------------------------
+// Which bucket and which table row every window of a scalar goes to: the sort's kernels (mzk_msm.hip) and the host
+// (tests/hostcheck/digit_walk_shim.cpp) run the same code.  The GLV half of walk_digits stays in mzk_msm.hip (it needs mzk_glv.h).
+// (u32 / u64 as in mzk_field.h, which this header must not include: the same typedefs again, a legal redeclaration in the library's
+// build and the only declaration in the stand-alone host builds -- keep both)
+typedef uint32_t u32;
+typedef uint64_t u64;
+// digit of window `win` before carry handling: bits [c win, c win + c)
+MZK_HD u32 raw_window(const u32* w, int win, int c) {
+  const int bit = win * c;
+  if (bit >= 256) return 0;
+  const int k = bit >> 5, s = bit & 31;
+  u64 v = w[k];
+  if (k + 1 < 8) v |= (u64)w[k + 1] << 32;
+  return (u32)(v >> s) & ((1u << c) - 1u);
+}
+// walk_digits (mzk_msm.hip) without the GLV split: the windows of the full scalar (canonical words w).  emit(window, key, payload) for
+// every non-zero signed digit d: key = |d| - 1 in bucket set window % sets (merged), payload = the point reference -- row window / sets
+// of the tables -- with the sign in bit 31.
+template <class Emit>
+MZK_HD void walk_digits_whole(const u32* w, const DigitLayout& L, size_t i, Emit emit) {
+  const int c = L.c;
+  const u32 half = 1u << (c - 1);
+  u32 carry = 0;
+  for (int win = 0; win < L.nwin; win++) {
+    u32 raw = raw_window(w, win, c) + carry;
+    u32 neg = 0, mag = raw;
+    carry = 0;
+    if (raw > half) { mag = (1u << c) - raw; neg = 1; carry = 1; }
+    if (mag != 0) {
+      const u32 key = (L.merged ? ((u32)(win % L.sets) << (c - 1)) : ((u32)win << (c - 1))) + (mag - 1);
+      const u32 payload = (L.merged ? (u32)((size_t)(win / L.sets) * L.table_stride + i) : (u32)i) | (neg << 31);
+      emit(win, key, payload);
+    }
+  }
+}
+
+// Signed c-bit digits without the serial carry walk: with t = k + sum_w (2^(c-1) - 1) 2^(c w) the digit of window w is
+// window_w(t) - (2^(c-1) - 1) (the carries of that ONE long addition are exactly the recoding's carries: window w overflows iff
+// raw_w + carry > 2^(c-1)), same digits as walk_digits.  Word k of the constant, C a compile-time width:
+constexpr u32 digit_bias_word(int C, int k) {
+  const int nwin = 254 / C + 1;
+  const unsigned long long hm1 = (1ull << (C - 1)) - 1;
+  unsigned long long acc = 0;
+  for (int w = 0; w < nwin; w++) {
+    const int sh = w * C - 32 * k;
+    if (sh >= 0 && sh < 32) acc |= (hm1 << sh) & 0xffffffffull;
+    else if (sh < 0 && sh > -32) acc |= hm1 >> (-sh);
+  }
+  return (u32)acc;
+}
+// walk_digits for the merged layout with a compile-time window width: the same (window, key, payload) triples in the same order,
+// from ONE long addition and NWIN independent extractions with static word indices (walk_digits' runtime window index makes
+// every word access a select chain).  Used by the coarse passes of the two-level sort and by the sortless small path.
+template <int C, class Emit>
+MZK_HD void walk_digits_merged(const u32* w, size_t table_stride, size_t i, Emit emit) {
+  constexpr int NWIN = 254 / C + 1;
+  constexpr u32 HALF = 1u << (C - 1), MASKC = (1u << C) - 1u;
+  u32 t[9];
+  u64 cy = 0;
+#if defined(__HIPCC__)
+#pragma unroll
+#endif
+  for (int k = 0; k < 8; k++) { cy += (u64)w[k] + digit_bias_word(C, k); t[k] = (u32)cy; cy >>= 32; }
+  t[8] = (u32)cy + digit_bias_word(C, 8);
+#if defined(__HIPCC__)
+#pragma unroll
+#endif
+  for (int win = 0; win < NWIN; win++) {
+    const int bit = win * C, k = bit >> 5, sft = bit & 31;
+    const u64 pair = (u64)t[k] | ((k + 1 < 9) ? ((u64)t[k + 1] << 32) : 0ull);
+    const u32 v = (u32)(pair >> sft) & MASKC;            // digit + HALF - 1
+    if (v == HALF - 1u) continue;                        // digit 0
+    const bool neg = v < HALF - 1u;
+    const u32 mag = neg ? (HALF - 1u) - v : v - (HALF - 1u);
+    emit(win, mag - 1u, (u32)((size_t)win * table_stride + i) | ((u32)neg << 31));
+  }
+}
+
 // Chunk mode (msm_chunked_impl) covers the problems whose every chunk takes the two-level sort with one bucket set: the generic layout
 // and window tables of 13 bits and more, from 2^18 pairs on (every chunk must keep the accumulate's lanes busy).  The path does not
 // depend on the CU count.

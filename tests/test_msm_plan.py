@@ -2,6 +2,7 @@
 (tests/hostcheck/msm_plan_shim.cpp): which path a call takes, which layout, and what it asks of the workspace.  CPU only."""
 import ctypes, os, random, subprocess
 import pytest
+import msm_layouts
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 PLAIN, MONT, TABLES = 0, 1, 2
@@ -23,9 +24,9 @@ def lib(tmp_path_factory):
     return L
 
 
-def plan(L, n, kind, stride, n_shape=None, n_alloc=None, chunks=0):
+def plan(L, n, kind, stride, n_shape=None, n_alloc=None, chunks=0, num_cu=256):
     out = (ctypes.c_uint64 * len(L.names))()
-    assert L.plan(n, n_shape or n, n_alloc or n, kind, stride, 256, chunks, out) == len(L.names)
+    assert L.plan(n, n_shape or n, n_alloc or n, kind, stride, num_cu, chunks, out) == len(L.names)
     return dict(zip(L.names, out))
 
 
@@ -159,3 +160,30 @@ def test_the_decisions_the_comments_promise(lib):
     assert plan(lib, (1 << 27) + 1, PLAIN, 0)["err"] != 0
     # chunk mode needs the two-level sort
     assert plan(lib, 1 << 18, tables(10), 1 << 18, chunks=2)["err"] != 0
+
+
+def test_every_layout_takes_the_tabled_path_at_every_prefix(lib):
+    """msm_layouts.EXPECTED_PATH, the literal table tests/test_gpu_msm_layouts.py commits through: 23 layouts x 8 prefixes of a 2^15-point
+    handle, at the CU count of an MI355X and at two others (the path, and the sort's shape, do not depend on it).  A changed threshold
+    has to change that table on purpose."""
+    assert set(msm_layouts.EXPECTED_PATH) == set(msm_layouts.LAYOUTS) and len(msm_layouts.LAYOUTS) == 23
+    ran = set()
+    for (c, sets), paths in msm_layouts.EXPECTED_PATH.items():
+        assert len(paths) == len(msm_layouts.PREFIXES)
+        for n, path in zip(msm_layouts.PREFIXES, paths):
+            for num_cu in (256, 64, 304):
+                p = plan(lib, n, tables(c, sets), msm_layouts.N_SRS, num_cu=num_cu)
+                where = (c, sets, n, num_cu)
+                assert p["err"] == 0 and p["path"] == msm_layouts.PATH_ID[path], where
+                assert (p["c"], p["sets"], p["nwin"], p["NB"]) == (c, sets, 254 // c + 1, sets << (c - 1)), where
+                assert (p["one_set"], p["red_windows"], p["horner_c"]) == (int(sets == 1), sets, 0 if sets == 1 else c), where
+                if path != msm_layouts.TWO:
+                    continue
+                assert p["cl"] == msm_layouts.EXPECTED_CL.get((c, sets), 8), where
+                assert p["F"] == (sets << (c - 1)) >> p["cl"], where
+                if sets == 1:
+                    assert p["F"] == msm_layouts.EXPECTED_F[c], where
+                assert p["coarse_c"] == msm_layouts.EXPECTED_COARSE_C.get((c, sets), 0) and p["staged"] == int(p["coarse_c"] != 0), where
+                assert p["compact"] == int((c, sets) not in msm_layouts.EXPECTED_WIDE_RECORDS), where
+            ran.add(path)
+    assert ran == set(msm_layouts.PATH_ID)
