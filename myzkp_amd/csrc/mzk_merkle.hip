@@ -13,6 +13,7 @@
 #include "mzk_common.h"
 #include "mzk_keccak_pair.h"
 #include "mzk_gl.h"
+#include "mzk_merkle_plan.h"      // the level schedule and its thresholds (LEAF_PAIR_MAX, LEVEL_PAIR_MAX, TAIL_NODES)
 
 namespace mzk {
 
@@ -121,7 +122,6 @@ __device__ __forceinline__ void sha3_of_two_digests(const u64* __restrict__ chil
 // ---- level 1 from field elements -----------------------------------------------------------------------
 // One lane per leaf pair.  The pair's message (<= 2 * (9 + 4 NW) <= 82 bytes) is serialised bytewise into a
 // word-major LDS block buffer, padded, and absorbed as 17 lanes.
-constexpr int LEAF_THREADS = 128;
 template <int NW>
 __global__ __launch_bounds__(LEAF_THREADS) void k_merkle_leaf_pairs(const u32* __restrict__ elems, size_t pairs, u64* __restrict__ nodes,
                                                                      const u8* __restrict__ neg) {
@@ -172,7 +172,6 @@ __global__ __launch_bounds__(LEAF_THREADS) void k_merkle_leaf_pairs(const u32* _
 // wave per SIMD at two lanes each): lane e of a pair serialises element e of its message -- the odd lane starts behind the even lane's
 // element, whose digit count it recounts --, the halves of the 17 rate words come back from LDS and the permutation is the lane-pair one
 // (~127 instructions per round and lane instead of 190).  Same bytes, same digests as k_merkle_leaf_pairs.
-constexpr size_t LEAF_PAIR_MAX = (size_t)1 << 15;      // pairs
 template <int NW>
 __global__ __launch_bounds__(LEAF_THREADS) void k_merkle_leaf_pairs_lp(const u32* __restrict__ elems, size_t pairs, u64* __restrict__ nodes,
                                                                         const u8* __restrict__ neg) {
@@ -378,7 +377,6 @@ __global__ __launch_bounds__(128) void k_merkle_level(const u64* __restrict__ be
   sha3_of_two_digests(below + 8 * i, above + 4 * i);
 }
 // small levels (latency-bound: fewer hashes than the GPU has lanes to spare): one lane PAIR per hash
-constexpr size_t LEVEL_PAIR_MAX = 16384;      // hashes
 __global__ __launch_bounds__(128) void k_merkle_level_pair(const u64* __restrict__ below, size_t count, u64* __restrict__ above) {
   const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   const size_t i = t >> 1;
@@ -419,7 +417,6 @@ __global__ __launch_bounds__(64 << LV) void k_merkle_level_pair_multi(const u64*
   }
 }
 // the last levels (<= TAIL_NODES nodes each) in one workgroup: no launch per level; one lane pair per hash
-constexpr int TAIL_NODES = 512;
 __global__ __launch_bounds__(TAIL_NODES) void k_merkle_tail(u64* __restrict__ level, size_t count, size_t stop, u32* __restrict__ mailbox, u32 seq) {
   // `level` holds `count` nodes; the levels above follow contiguously (count/2, count/4, ... stop); stop = 1 for one tree,
   // the number of trees for a batch (their roots are the last level).
@@ -580,49 +577,50 @@ static int merkle_hash_levels(int kind, int fid, const void* d_leaves, const u64
   if (mailed) *mailed = false;
   if (n < 2) return MZK_OK;
   ProfScope ps(s, MZK_PH_MERKLE);
-  const size_t pairs = n / 2;
-  const unsigned blocks = (unsigned)((pairs + 127) / 128);
-  if (kind == 1)
-    hipLaunchKernelGGL(k_merkle_leaf_pairs_bytes, dim3(blocks), dim3(128), 0, s, (const u8*)d_leaves, d_off, pairs, d_nodes);
-  else if (field_is_gl(fid)) {
-    MZK_TRY(with_gl(fid, [&](auto tag) {
-      hipLaunchKernelGGL((k_merkle_leaf_pairs_gl<decltype(tag)::NC>), dim3(blocks), dim3(LEAF_THREADS), 0, s, (const u64*)d_leaves, pairs, d_nodes);
-      return MZK_OK;
-    }));
-  } else {
-    static const int lp_on = tune_int("MZK_LEAF_LANE_PAIRS", 1);      // tuning build: 0 = one lane per leaf pair at every size (A/B)
-    const bool lp = lp_on && pairs <= LEAF_PAIR_MAX;
-    const unsigned lpb = (unsigned)((pairs + LEAF_THREADS / 2 - 1) / (LEAF_THREADS / 2));
-    if (lp) MZK_TRY(MZK_FIELD_LAUNCH(fid, k_merkle_leaf_pairs_lp<P::NW>, dim3(lpb), dim3(LEAF_THREADS), 0, s, (const u32*)d_leaves, pairs, d_nodes, d_neg));
-    else MZK_TRY(MZK_FIELD_LAUNCH(fid, k_merkle_leaf_pairs<P::NW>, dim3(blocks), dim3(LEAF_THREADS), 0, s, (const u32*)d_leaves, pairs, d_nodes, d_neg));
-  }
-  u64* below = d_nodes;
-  size_t count = pairs;
-  while (count > (size_t)TAIL_NODES && count > trees) {
-    u64* above = below + 4 * count;
-    if (count / 2 <= LEVEL_PAIR_MAX && (count >> 3) >= (size_t)TAIL_NODES && (count >> 3) >= trees) {          // three levels in one launch
-      hipLaunchKernelGGL((k_merkle_level_pair_multi<3>), dim3((unsigned)((count / 2 + 255) / 256)), dim3(512), 0, s, (const u64*)below, count / 2, above);
-      below = above + 4 * (count / 2) + 4 * (count / 4);
-      count >>= 3;
-      continue;
+  static const int lp_on = tune_int("MZK_LEAF_LANE_PAIRS", 1);      // tuning build: 0 = one lane per leaf pair at every size (A/B)
+  const int leaf_kind = kind == 1 ? MERKLE_LEAVES_BYTES : field_is_gl(fid) ? MERKLE_LEAVES_GL : lp_on ? MERKLE_LEAVES_FIELD : MERKLE_LEAVES_FIELD_PLAIN;
+  const MerklePlan plan = merkle_plan(n, trees, leaf_kind);
+  for (int i = 0; i < plan.nsteps; i++) {
+    const MerkleStep& st = plan.steps[i];
+    const dim3 grid((unsigned)st.grid), block(st.block);
+    u64* above = d_nodes + 4 * st.out_offset;
+    // inner steps: the level below ends where this step's output begins (a leaf step reads the leaves: no digests below it)
+    u64* below = st.kernel >= MK_LEVEL ? above - 4 * st.nodes_in : nullptr;
+    switch (st.kernel) {
+      case MK_LEAF_BYTES:
+        hipLaunchKernelGGL(k_merkle_leaf_pairs_bytes, grid, block, 0, s, (const u8*)d_leaves, d_off, st.parents, above);
+        break;
+      case MK_LEAF_GL:
+        MZK_TRY(with_gl(fid, [&](auto tag) {
+          hipLaunchKernelGGL((k_merkle_leaf_pairs_gl<decltype(tag)::NC>), grid, block, 0, s, (const u64*)d_leaves, st.parents, above);
+          return MZK_OK;
+        }));
+        break;
+      case MK_LEAF_LP:
+        MZK_TRY(MZK_FIELD_LAUNCH(fid, k_merkle_leaf_pairs_lp<P::NW>, grid, block, 0, s, (const u32*)d_leaves, st.parents, above, d_neg));
+        break;
+      case MK_LEAF_PLAIN:
+        MZK_TRY(MZK_FIELD_LAUNCH(fid, k_merkle_leaf_pairs<P::NW>, grid, block, 0, s, (const u32*)d_leaves, st.parents, above, d_neg));
+        break;
+      case MK_LEVEL:
+        hipLaunchKernelGGL(k_merkle_level, grid, block, 0, s, (const u64*)below, st.parents, above);
+        break;
+      case MK_LEVEL_PAIR:
+        hipLaunchKernelGGL(k_merkle_level_pair, grid, block, 0, s, (const u64*)below, st.parents, above);
+        break;
+      case MK_MULTI2:
+        hipLaunchKernelGGL((k_merkle_level_pair_multi<2>), grid, block, 0, s, (const u64*)below, st.parents, above);
+        break;
+      case MK_MULTI3:
+        hipLaunchKernelGGL((k_merkle_level_pair_multi<3>), grid, block, 0, s, (const u64*)below, st.parents, above);
+        break;
+      case MK_TAIL: {
+        const bool mail = mailbox != nullptr && trees == 1;
+        hipLaunchKernelGGL(k_merkle_tail, grid, block, 0, s, below, st.nodes_in, trees, mail ? mailbox : (u32*)nullptr, seq);
+        if (mail && mailed) *mailed = true;
+        break;
+      }
     }
-    if (count / 2 <= LEVEL_PAIR_MAX && (count >> 2) >= (size_t)TAIL_NODES && (count >> 2) >= trees) {          // two
-      hipLaunchKernelGGL((k_merkle_level_pair_multi<2>), dim3((unsigned)((count / 2 + 127) / 128)), dim3(256), 0, s, (const u64*)below, count / 2, above);
-      below = above + 4 * (count / 2);
-      count >>= 2;
-      continue;
-    }
-    if (count / 2 <= LEVEL_PAIR_MAX)
-      hipLaunchKernelGGL(k_merkle_level_pair, dim3((unsigned)((count + 127) / 128)), dim3(128), 0, s, (const u64*)below, count / 2, above);
-    else
-      hipLaunchKernelGGL(k_merkle_level, dim3((unsigned)((count / 2 + 127) / 128)), dim3(128), 0, s, (const u64*)below, count / 2, above);
-    below = above;
-    count /= 2;
-  }
-  if (count > trees) {
-    const bool mail = mailbox != nullptr && trees == 1;
-    hipLaunchKernelGGL(k_merkle_tail, dim3(1), dim3(TAIL_NODES), 0, s, below, count, trees, mail ? mailbox : (u32*)nullptr, seq);
-    if (mail && mailed) *mailed = true;
   }
   MZK_HIP(hipGetLastError());
   return MZK_OK;
