@@ -39,9 +39,10 @@ enum { MZK_FIELD_FR = 0,   /* ModEIP197 / FqOrder: algebra/field.rs:428-431, cur
  *   c0 + c1 x + c2 x^2 (24 bytes, array of structures).  A scalar parameter of id 4 (root, offset, alpha) has the same three words.
  *   Served by: mzk_root_of_unity, mzk_ntt / _dev / _batch / _batch_dev, mzk_coset_lde / _dev / _batch / _batch_dev, mzk_fri_fold / _dev,
  *   mzk_merkle_build_field / _dev, mzk_merkle_commit_field / _dev and every call on a built tree (root, open, open_batch, open_multi,
- *   leaves, free), mzk_fri_commit, mzk_fri_commit_keep_trees / _dev.  Every other call refuses them with MZK_E_ARG like any id it
- *   does not serve (mzk_fri_prove*, mzk_stark_*, mzk_fast_*, mzk_fft_multiply, mzk_mpoly_*, mzk_poly_*, the *_signed Merkle and FRI
- *   forms, mzk_merkle_commit_field_batch*, mzk_ntt_multi*, mzk_ntt_columns_dev, the synth / selftest / probe calls).
+ *   leaves, free), mzk_fri_commit, mzk_fri_commit_keep_trees / _dev, and mzk_fri_proof_layout_gl, mzk_fri_prove_gl / _dev, which
+ *   serve no other id.  Every other call refuses them with MZK_E_ARG like any id it does not serve (mzk_fri_prove,
+ *   mzk_fri_prove_dev, mzk_fri_proof_layout, mzk_stark_*, mzk_fast_*, mzk_fft_multiply, mzk_mpoly_*, mzk_poly_*, the *_signed Merkle
+ *   and FRI forms, mzk_merkle_commit_field_batch*, mzk_ntt_multi*, mzk_ntt_columns_dev, the synth / selftest / probe calls).
  *   Restriction for id 4: omega, generator and offset must lie in the base field (c1 = c2 = 0), MZK_E_ARG otherwise -- every element
  *   of 2-power order does, and the reference's only instantiation passes base values for all three; a transform root with c1 or
  *   c2 != 0 fails the root-order check (MZK_E_ROOT_ORDER).  alpha and the data are unrestricted.
@@ -354,6 +355,31 @@ int mzk_fri_prove(int field_id, const uint64_t* magnitudes, const uint8_t* negat
 /* device memory in and out (d_negative: device flags or NULL); only enqueues on `stream`: read MZK_FRI_STATUS after synchronizing */
 int mzk_fri_prove_dev(int field_id, const void* d_magnitudes, const void* d_negative, size_t n, const uint64_t* omega, const uint64_t* offset,
                       size_t expansion_factor, size_t num_colinearity_tests, void* d_proof, size_t proof_cap, void* stream);
+
+/* FRI::prove over the Goldilocks ids (MZK_FIELD_M64, MZK_FIELD_M64X3; the reference's test_fri_efield, fri.rs:546-594, calls
+ * fri.prove): the same one-enqueue prover with entry points of its own, because the packed layout differs.  Field ids 0 .. 2 get
+ * MZK_E_ARG ("fri_prove_gl: bad field id N").  There is no `negative` argument: these fields take canonical elements only.
+ *
+ * alpha_r = F::sample(SHAKE256(stream)[0..32]) is the wrapping accumulator (the last 8 digest bytes big-endian) reduced mod p --
+ * it can exceed p --, embedded as (v, 0, 0) for id 4 (efield.rs:180-186).  The last codeword is pushed as one object of m strings,
+ * each the element's leaf bytes (9 .. 17 bytes for M64, 8 .. 59 for M64X3; see the Goldilocks note at the top).
+ *
+ * Packed proof: the eight sections of mzk_fri_proof_layout in the same order, with NL = 1 or 3 words per element; MZK_FRI_SIGNS is
+ * present and all zero (unpackers are shared); a path entry takes MZK_FRI_PATH_STRIDE_GL bytes, zero padded (an M64X3 sibling leaf
+ * is up to 59 bytes).  Errors, before anything is enqueued: those of mzk_fri_prove, with the parameter rules of the Goldilocks
+ * ids -- omega / offset not canonical MZK_E_RANGE, outside the base field for id 4 MZK_E_ARG.  With num_rounds >= 2 and an
+ * expansion factor >= 1 the last codeword has at least two elements; expansion factor 0 without tests would halve down to one:
+ * MZK_E_LENGTH. */
+enum { MZK_FRI_PATH_STRIDE_GL = 64 };
+/* gl_field_id: MZK_FIELD_M64 or MZK_FIELD_M64X3.  host only */
+int mzk_fri_proof_layout_gl(int gl_field_id, size_t n, size_t expansion_factor, size_t num_colinearity_tests, int* num_rounds, uint64_t* offsets,
+                            uint64_t* sizes, uint64_t* total_bytes);
+/* host memory in and out; returns when proof_out is complete (MZK_E_RANGE when the sampler gave up, as mzk_fri_prove) */
+int mzk_fri_prove_gl(int gl_field_id, const uint64_t* codeword, size_t n, const uint64_t* omega, const uint64_t* offset, size_t expansion_factor,
+                     size_t num_colinearity_tests, uint8_t* proof_out, size_t proof_cap);
+/* device memory in and out; only enqueues on `stream`: read MZK_FRI_STATUS after synchronizing */
+int mzk_fri_prove_gl_dev(int gl_field_id, const void* d_codeword, size_t n, const uint64_t* omega, const uint64_t* offset, size_t expansion_factor,
+                         size_t num_colinearity_tests, void* d_proof, size_t proof_cap, void* stream);
 
 /* ---- G2 (BN254 twist over Fq2 = Fq[u]/(u^2+1); bn128.rs:33-49) ------------------------------------------------
  * A G2 point is 16 limbs: x.c0 | x.c1 | y.c0 | y.c1 (4 limbs each, canonical); all-zero = infinity.

@@ -912,14 +912,11 @@ def fri_proof_layout(fid, n, expansion_factor, num_colinearity_tests):
     return rounds.value, {k: (off[i], size[i]) for i, k in enumerate(FRI_SECTIONS)}, total.value
 
 
-def fri_unpack_proof(fid, n, expansion_factor, num_colinearity_tests, raw):
-    """The packed proof of mzk_fri_prove as the reference's FriProof (fri.rs:71-82): top_level_indices, last_codeword ((m, limbs)
-    array), merkle_roots (bytes), revealed_layers ([{"a": (values, paths), "b": ..., "c": ...}]).  A value with Sign::Minus is the
-    negative int -magnitude.  Raises MzkError when the status word is set."""
+def _fri_unpack(layout, nl, stride, n, T, raw, rows):
+    """the sections of a packed FRI proof (mzk_fri_proof_layout or _gl) as fri_unpack_proof's dict; rows: a layer's values stay a
+    (T, nl) array (no signs) instead of becoming ints"""
     raw = bytes(raw)
-    nl = LIMBS[fid]
-    R, sec, _ = fri_proof_layout(fid, n, expansion_factor, num_colinearity_tests)
-    T = num_colinearity_tests
+    R, sec, _ = layout
 
     def part(k):
         o, s = sec[k]
@@ -930,7 +927,8 @@ def fri_unpack_proof(fid, n, expansion_factor, num_colinearity_tests, raw):
     top = [int(x) for x in np.frombuffer(part("top_indices"), dtype=np.uint64)]
     roots = [part("roots")[32 * r:32 * r + 32] for r in range(R)]
     last = np.frombuffer(part("last_codeword"), dtype=np.uint64).reshape(-1, nl).copy()
-    vals = from_limbs(np.frombuffer(part("values"), dtype=np.uint64).reshape(-1, nl)) if T else []
+    words = np.frombuffer(part("values"), dtype=np.uint64).reshape(-1, nl)
+    vals = words if rows else (from_limbs(words) if T else [])
     signs = part("signs")
     paths, lens = part("paths"), np.frombuffer(part("path_lens"), dtype=np.uint64)
     layers, q, e = [], 0, 0
@@ -940,13 +938,22 @@ def fri_unpack_proof(fid, n, expansion_factor, num_colinearity_tests, raw):
             d = (n >> (i + (kind == "c"))).bit_length() - 1
             v, ps = [], []
             for _ in range(T):
-                v.append(-vals[q] if signs[q] else vals[q])
-                ps.append([paths[(e + k) * FRI_PATH_STRIDE:(e + k) * FRI_PATH_STRIDE + int(lens[e + k])] for k in range(d)])
+                if not rows:
+                    v.append(-vals[q] if signs[q] else vals[q])
+                ps.append([paths[(e + k) * stride:(e + k) * stride + int(lens[e + k])] for k in range(d)])
                 q += 1
                 e += d
-            layer[kind] = (v, ps)
+            layer[kind] = (vals[q - T:q].copy() if rows else v, ps)
         layers.append(layer)
     return {"top_level_indices": top, "last_codeword": last, "merkle_roots": roots, "revealed_layers": layers}
+
+
+def fri_unpack_proof(fid, n, expansion_factor, num_colinearity_tests, raw):
+    """The packed proof of mzk_fri_prove as the reference's FriProof (fri.rs:71-82): top_level_indices, last_codeword ((m, limbs)
+    array), merkle_roots (bytes), revealed_layers ([{"a": (values, paths), "b": ..., "c": ...}]).  A value with Sign::Minus is the
+    negative int -magnitude.  Raises MzkError when the status word is set."""
+    return _fri_unpack(fri_proof_layout(fid, n, expansion_factor, num_colinearity_tests), LIMBS[fid], FRI_PATH_STRIDE, n, num_colinearity_tests,
+                       raw, False)
 
 
 def fri_prove(fid, codeword, omega, offset, expansion_factor, num_colinearity_tests, negative=None, device_ptr=None, n=None):
@@ -974,6 +981,53 @@ def fri_prove(fid, codeword, omega, offset, expansion_factor, num_colinearity_te
         stream.synchronize()
         raw = proof.cpu().numpy().tobytes()
     return fri_unpack_proof(fid, n, expansion_factor, num_colinearity_tests, raw)
+
+
+FRI_PATH_STRIDE_GL = 64
+
+
+def fri_proof_layout_gl(fid, n, expansion_factor, num_colinearity_tests):
+    """mzk_fri_proof_layout_gl: fri_proof_layout's triple for the Goldilocks ids (1 or 3 words per element, 64-byte path entries)."""
+    rounds = ctypes.c_int()
+    off = (ctypes.c_uint64 * len(FRI_SECTIONS))()
+    size = (ctypes.c_uint64 * len(FRI_SECTIONS))()
+    total = ctypes.c_uint64()
+    _check(lib().mzk_fri_proof_layout_gl(int(fid), ctypes.c_size_t(n), ctypes.c_size_t(expansion_factor), ctypes.c_size_t(num_colinearity_tests),
+                                         ctypes.byref(rounds), off, size, ctypes.byref(total)))
+    return rounds.value, {k: (off[i], size[i]) for i, k in enumerate(FRI_SECTIONS)}, total.value
+
+
+def fri_unpack_proof_gl(fid, n, expansion_factor, num_colinearity_tests, raw):
+    """The packed proof of mzk_fri_prove_gl in fri_unpack_proof's shape; last_codeword and every layer's values are rows of 1 or 3
+    words ((count, limbs) arrays), as the other Goldilocks wrappers return elements."""
+    return _fri_unpack(fri_proof_layout_gl(fid, n, expansion_factor, num_colinearity_tests), LIMBS[fid], FRI_PATH_STRIDE_GL, n,
+                       num_colinearity_tests, raw, True)
+
+
+def fri_prove_gl(fid, codeword, omega, offset, expansion_factor, num_colinearity_tests, device_ptr=None, n=None):
+    """FRI::prove over MZK_FIELD_M64 / MZK_FIELD_M64X3 in one call (mzk_fri_prove_gl), the transcript on the device.  Returns
+    fri_unpack_proof_gl's dict.  device_ptr / n: the codeword is already in HBM (mzk_fri_prove_gl_dev on torch's current stream);
+    `codeword` is ignored."""
+    if device_ptr is None:
+        c = _arr(fid, codeword)
+        n = c.shape[0]
+    _, _, total = fri_proof_layout_gl(fid, n, expansion_factor, num_colinearity_tests)
+    w, o = _one(fid, omega), _one(fid, offset)
+    if device_ptr is None:
+        buf = (ctypes.c_uint8 * total)()
+        _check(lib().mzk_fri_prove_gl(int(fid), _p(c), ctypes.c_size_t(n), _p(w), _p(o), ctypes.c_size_t(expansion_factor),
+                                      ctypes.c_size_t(num_colinearity_tests), buf, ctypes.c_size_t(total)))
+        raw = bytes(buf)
+    else:
+        import torch
+        proof = torch.empty(total, dtype=torch.uint8, device="cuda")
+        stream = torch.cuda.current_stream()
+        _check(lib().mzk_fri_prove_gl_dev(int(fid), ctypes.c_void_p(int(device_ptr)), ctypes.c_size_t(n), _p(w), _p(o), ctypes.c_size_t(expansion_factor),
+                                          ctypes.c_size_t(num_colinearity_tests), ctypes.c_void_p(proof.data_ptr()), ctypes.c_size_t(total),
+                                          ctypes.c_void_p(stream.cuda_stream)))
+        stream.synchronize()
+        raw = proof.cpu().numpy().tobytes()
+    return fri_unpack_proof_gl(fid, n, expansion_factor, num_colinearity_tests, raw)
 
 
 def fast_coset_divide(fid, lhs, rhs, offset, root, root_order):

@@ -236,6 +236,8 @@ int gl_ntt_dev_impl(int fid, const uint64_t* root_host, const void* d_in, void* 
 int gl_coset_lde_dev_impl(int fid, const void* d_coef, size_t n_coef, const uint64_t* offset_host, const uint64_t* generator_host, void* d_out,
                           size_t order, hipStream_t s, size_t batch);
 int gl_fri_fold_dev(int fid, const void* d_cw, size_t n, const uint64_t* alpha, uint64_t half, uint64_t oinv, uint64_t winv, void* d_out, hipStream_t s);
+int gl_fri_fold_dev_alpha(int fid, const void* d_cw, size_t n, const uint64_t* d_alpha, uint64_t half, uint64_t oinv, uint64_t winv, void* d_out,
+                          hipStream_t s);       // alpha: NC canonical words in device memory
 void gl_release_plans();
 void kzg_release_cache();       // mzk_kzg.hip: fixed-base tables of the current context
 void poly_release_pool();       // mzk_poly.hip: parked scratch blocks of the current context

@@ -227,6 +227,27 @@ __global__ __launch_bounds__(GL_NT) void k_gl_fri_fold(const u64* __restrict__ c
     q = gl::mul(q, winv_step);
   }
 }
+// The same fold with alpha in device memory (mzk_fri_prove_gl: the round's transcript kernel wrote it there, NC canonical words);
+// 2^-1 alpha is formed here as gl_fri_fold_dev forms it on the host, everything else is k_gl_fri_fold.
+template <int NC>
+__global__ __launch_bounds__(GL_NT) void k_gl_fri_fold_dev_alpha(const u64* __restrict__ cw, size_t h, const u64* __restrict__ alpha, u64 half, u64 oinv, u64 winv,
+                                                                 u64 winv_step, u64* __restrict__ out) {
+  size_t i = (size_t)blockIdx.x * GL_FOLD_BLOCK + threadIdx.x;
+  if (i >= h) return;
+  gl::El<NC> alpha_half;
+#pragma unroll
+  for (int c = 0; c < NC; c++) alpha_half.c[c] = gl::mul(alpha[c], half);
+  u64 q = gl::mul(oinv, gl::pow(winv, (u64)i));
+  for (int t = 0; t < GL_FOLD_PER_LANE && i < h; t++, i += GL_NT) {
+    gl::El<NC> a, b;
+#pragma unroll
+    for (int c = 0; c < NC; c++) { a.c[c] = cw[i * NC + c]; b.c[c] = cw[(h + i) * NC + c]; }
+    const gl::El<NC> o = gl::el_add<NC>(gl::el_scale<NC>(gl::el_add<NC>(a, b), half), gl::el_mul(gl::el_scale<NC>(alpha_half, q), gl::el_sub<NC>(a, b)));
+#pragma unroll
+    for (int c = 0; c < NC; c++) out[i * NC + c] = o.c[c];
+    q = gl::mul(q, winv_step);
+  }
+}
 
 // ---- plans ------------------------------------------------------------------------------------------------------------------
 // Per (context, log2 n, direction, root): the level split and ONE device table [w_{2^tl}^j, j < 2048 | lo | mid | hi] of the effective
@@ -447,6 +468,21 @@ int gl_fri_fold_dev(int fid, const void* d_cw, size_t n, const uint64_t* alpha, 
     gl::El<NC> ah;
     for (int c = 0; c < NC; c++) ah.c[c] = gl::mul(alpha[c], half);
     hipLaunchKernelGGL((k_gl_fri_fold<NC>), dim3((unsigned)blocks), dim3(GL_NT), 0, s, (const u64*)d_cw, h, ah, half, oinv, winv, step, (u64*)d_out);
+    return MZK_OK;
+  }));
+  MZK_HIP(hipGetLastError());
+  return MZK_OK;
+}
+
+int gl_fri_fold_dev_alpha(int fid, const void* d_cw, size_t n, const uint64_t* d_alpha, uint64_t half, uint64_t oinv, uint64_t winv, void* d_out, hipStream_t s) {
+  const size_t h = n / 2;
+  if (h == 0) return MZK_OK;
+  const size_t blocks = (h + GL_FOLD_BLOCK - 1) / GL_FOLD_BLOCK;
+  if (blocks > 0x7fffffffu) { set_error("fri_fold: codeword too long"); return MZK_E_ARG; }
+  const u64 step = gl::pow(winv, GL_NT);
+  MZK_TRY(with_gl(fid, [&](auto tag) {
+    hipLaunchKernelGGL((k_gl_fri_fold_dev_alpha<decltype(tag)::NC>), dim3((unsigned)blocks), dim3(GL_NT), 0, s, (const u64*)d_cw, h, d_alpha, half, oinv, winv, step,
+                       (u64*)d_out);
     return MZK_OK;
   }));
   MZK_HIP(hipGetLastError());

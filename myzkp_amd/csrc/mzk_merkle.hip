@@ -1401,6 +1401,7 @@ int mzk_merkle_leaves(const mzk_merkle* t, const uint64_t* indices, size_t count
 // vec![root_r] to the device transcript, rehashes the whole serialization with SHAKE256 and writes alpha_r; the fold reads it
 // from there.  After the last root k_fri_tx_last pushes the last codeword, squeezes the index seed and samples the top-level
 // indices; k_fri_query gathers every layer's values and paths into the packed proof.  No host round trip inside.
+// mzk_fri_prove_gl runs the same driver over the Goldilocks ids with the *_gl forms of the three kernels (mzk.h: 64-byte path entries).
 #include "mzk_transcript.h"
 namespace mzk {
 
@@ -1570,37 +1571,190 @@ __global__ __launch_bounds__(64) void k_fri_query(FriQueryArgs A) {
   }
 }
 
-// Validation shared by the three entry points; fills the layout.  Nothing is enqueued.
-static int fri_prove_check(int field_id, size_t n, size_t expansion_factor, size_t tests, mzk_tx::FriLayout* L) {
-  MZK_TRY(field_check(field_id, "fri_prove"));
-  if (n == 0) { set_error("fri_prove: empty codeword"); return MZK_E_LENGTH; }
-  if (!is_pow2(n)) { set_error("fri_prove: codeword length must be a power of two"); return MZK_E_NOT_POW2; }
-  mzk_tx::fri_layout(n, expansion_factor, tests, field_limbs64(field_id), L);
+// ---- the same three kernels over the Goldilocks ids (mzk_fri_prove_gl; NC = 1: M64, 3: M64X3) ------------------------------------------
+// Round r: as k_fri_tx_round, with alpha_r = F::sample taken mod p (mzk_tx::sample_gl) -- the base value, which id 4 embeds as
+// (v, 0, 0): `alpha` takes the same four words, the fold reads the first NC.
+__global__ __launch_bounds__(64) void k_fri_tx_round_gl(u64* __restrict__ tx, int r, const u64* __restrict__ root, u64* __restrict__ proof_root,
+                                                        u64* __restrict__ alpha, int squeeze) {
+  __shared__ u32 dig[8];
+  const int tid = threadIdx.x;
+  if (tid < 6) {
+    const u64 v = tid == 0 ? 1 : (tid == 1 ? 32 : root[tid - 2]);
+    tx[1 + 6 * (size_t)r + tid] = v;
+    if (tid >= 2) proof_root[tid - 2] = v;
+  }
+  if (tid == 0) tx[0] = (u64)r + 1;
+  __syncthreads();
+  if (!squeeze) return;
+  if (tid < 2) fri_shake256_pair(reinterpret_cast<const u8*>(tx), 8 + 48 * ((size_t)r + 1), tid, dig);
+  __syncthreads();
+  if (tid < 4) alpha[tid] = tid == 0 ? mzk_tx::sample_gl(((u64)dig[7] << 32) | dig[6]) : 0;
+}
+
+// After the last root: as k_fri_tx_last, the strings being gl::leaf_bytes<NC> of the elements (8 .. 59 bytes, mzk_tx::fri_gl_record_put);
+// a string's position is the prefix sum of the record lengths before it, a workgroup's worth of strings per step.  The stream is
+// then rehashed by one lane pair (about 65 SHAKE blocks at m = 128 over M64X3).
+template <int NC>
+__global__ __launch_bounds__(TX_LAST_THREADS) void k_fri_tx_last_gl(u8* __restrict__ tx, int rounds, const u64* __restrict__ cw, size_t m, size_t size,
+                                                                     size_t number, u32* __restrict__ seen, u64* __restrict__ p_status,
+                                                                     u64* __restrict__ p_top, u64* __restrict__ p_last) {
+  __shared__ u64 scan[TX_LAST_THREADS];
+  __shared__ u64 cand[TX_LAST_THREADS];
+  __shared__ u32 seed32[8];
+  __shared__ u64 s_count, s_done;
+  const int tid = threadIdx.x;
+  u64* tw = reinterpret_cast<u64*>(tx);
+  const size_t obj = 8 + 48 * (size_t)rounds;
+  if (tid == 0) { tw[0] = (u64)rounds + 1; tw[obj / 8] = (u64)m; }
+  size_t at = obj + 8;
+  for (size_t base = 0; base < m; base += TX_LAST_THREADS) {
+    const size_t j = base + tid;
+    u64 c[NC];
+#pragma unroll
+    for (int q = 0; q < NC; q++) c[q] = 0;
+    if (j < m) {
+#pragma unroll
+      for (int q = 0; q < NC; q++) { c[q] = cw[j * NC + q]; p_last[j * NC + q] = c[q]; }
+    }
+    const u64 rec = j < m ? mzk_tx::fri_gl_record_len<NC>(c) : 0;
+    scan[tid] = rec;
+    __syncthreads();
+    for (int d = 1; d < TX_LAST_THREADS; d <<= 1) {          // inclusive scan of the record lengths
+      const u64 add = tid >= d ? scan[tid - d] : 0;
+      __syncthreads();
+      scan[tid] += add;
+      __syncthreads();
+    }
+    if (j < m) mzk_tx::fri_gl_record_put<NC>(c, tx + at + scan[tid] - rec);
+    at += scan[TX_LAST_THREADS - 1];
+    __syncthreads();
+  }
+  if (tid < 2) fri_shake256_pair(tx, at, tid, seed32);
+  for (size_t i = tid; i < (m + 31) / 32; i += TX_LAST_THREADS) seen[i] = 0;
+  if (tid == 0) { s_count = 0; s_done = 0; }
+  __syncthreads();
+  u64 seed[4];
+#pragma unroll
+  for (int i = 0; i < 4; i++) seed[i] = ((u64)seed32[2 * i + 1] << 32) | seed32[2 * i];
+  // sample_indices exactly as k_fri_tx_last: batches of 256 counters, accepted in counter order, bounded
+  for (u64 c0 = 0; c0 < mzk_tx::SAMPLE_COUNTER_LIMIT && !s_done; c0 += TX_LAST_THREADS) {
+    u64 h[4];
+    mzk_tx::blake2b256_seed_counter(seed, c0 + tid, h);
+    cand[tid] = mzk_tx::sample_digest_word3(h[3]) & (u64)(size - 1);
+    __syncthreads();
+    if (tid == 0) {
+      u64 cnt = s_count;
+      for (int t = 0; t < TX_LAST_THREADS && cnt < number; t++) {
+        const u64 idx = cand[t], red = idx & (u64)(m - 1);
+        const u32 bit = 1u << (red & 31);
+        if (!(seen[red >> 5] & bit)) {
+          seen[red >> 5] |= bit;
+          p_top[cnt++] = idx;
+        }
+      }
+      s_count = cnt;
+      s_done = cnt >= number;
+    }
+    __syncthreads();
+  }
+  if (tid == 0) {
+    for (u64 q = s_count; q < number; q++) p_top[q] = 0;
+    *p_status = s_count >= number ? 0 : 1;
+  }
+}
+
+// The query phase: the blocks of k_fri_query.  A value is NC words and its sign byte 0; a path entry is a PATH_STRIDE_GL-byte slot, zero
+// padded: entry 0 the sibling's leaf bytes, serialised in LDS as k_merkle_leaf_pairs_gl does, entries 1 .. depth-1 the digests.
+template <int NC>
+__global__ __launch_bounds__(64) void k_fri_query_gl(FriQueryArgs A) {
+  constexpr int SLOT_WORDS = mzk_tx::PATH_STRIDE_GL / 8;
+  __shared__ u64 slot[SLOT_WORDS];
+  __shared__ int leaf_len;
+  const u64 T = A.tests, q = blockIdx.x;
+  const int layer = (int)(q / (3 * T)), kind = (int)((q / T) % 3);
+  const u64 s = q % T;
+  const u64 half = (A.n >> layer) / 2;
+  const u64 a = A.top[s] & (half - 1);
+  const u64 idx = kind == 1 ? a + half : a;
+  const int rnd = layer + (kind == 2);
+  const u64 len = A.n >> rnd;
+  const int depth = mzk_tx::log2_pow2(len);
+  const u64* leaves = reinterpret_cast<const u64*>(A.cw + A.cw_off[rnd]);
+  const u64* nodes = reinterpret_cast<const u64*>(A.nodes + A.node_off[rnd]);
+  const int tid = threadIdx.x;
+  if (tid < NC) reinterpret_cast<u64*>(A.values)[q * NC + tid] = leaves[idx * NC + tid];
+  if (tid == 0) A.signs[q] = 0;
+  const u64 e0 = mzk_tx::fri_entry_base(A.n, T, layer, kind) + s * (u64)depth;
+  const int l = tid;
+  if (l >= 1 && l < depth) {
+    const u64 start = len - (len >> (l - 1));
+    const u64* src = nodes + 4 * (start + ((idx >> l) ^ 1));
+    u64* dst = reinterpret_cast<u64*>(A.paths + (e0 + l) * mzk_tx::PATH_STRIDE_GL);
+#pragma unroll
+    for (int k = 0; k < 4; k++) dst[k] = src[k];
+#pragma unroll
+    for (int k = 4; k < SLOT_WORDS; k++) dst[k] = 0;
+    A.lens[e0 + l] = 32;
+  }
+  if (tid < SLOT_WORDS) slot[tid] = 0;
+  __syncthreads();
+  if (tid == 0) {
+    const u64 sib = idx ^ 1;
+    u64 c[NC];
+#pragma unroll
+    for (int k = 0; k < NC; k++) c[k] = leaves[sib * NC + k];
+    u8* bytes = reinterpret_cast<u8*>(slot);
+    leaf_len = gl::leaf_bytes<NC>(c, 0, [&](int pos, u32 byte) { bytes[pos] = (u8)byte; });
+  }
+  __syncthreads();
+  if (tid < SLOT_WORDS) reinterpret_cast<u64*>(A.paths + e0 * mzk_tx::PATH_STRIDE_GL)[tid] = slot[tid];
+  if (tid == 0) A.lens[e0] = (u64)leaf_len;
+}
+
+// Validation shared by the entry points; fills the layout.  Nothing is enqueued.  gl: the mzk_fri_*_gl entry points (field ids 3 and 4
+// only, 64-byte path entries); otherwise ids 0 and 1 only.
+static int fri_prove_check(int field_id, size_t n, size_t expansion_factor, size_t tests, mzk_tx::FriLayout* L, bool gl = false) {
+  const char* who = gl ? "fri_prove_gl" : "fri_prove";
+  if (gl) {
+    if (!field_is_gl(field_id)) { set_error("fri_prove_gl: bad field id %d", field_id); return MZK_E_ARG; }
+  } else MZK_TRY(field_check(field_id, "fri_prove"));
+  if (n == 0) { set_error("%s: empty codeword", who); return MZK_E_LENGTH; }
+  if (!is_pow2(n)) { set_error("%s: codeword length must be a power of two", who); return MZK_E_NOT_POW2; }
+  if (gl) mzk_tx::fri_layout_gl(n, expansion_factor, tests, field_limbs64(field_id), L);
+  else mzk_tx::fri_layout(n, expansion_factor, tests, field_limbs64(field_id), L);
   if (L->rounds < 2) {
-    set_error("fri_prove: num_rounds = %d for domain length %zu, expansion factor %zu, %zu colinearity tests; FRI::prove reads codewords[1] (fri.rs:117-121)",
-              L->rounds, n, expansion_factor, tests);
+    set_error("%s: num_rounds = %d for domain length %zu, expansion factor %zu, %zu colinearity tests; FRI::prove reads codewords[1] (fri.rs:117-121)",
+              who, L->rounds, n, expansion_factor, tests);
     return MZK_E_LENGTH;
   }
   if (tests > L->last_len) {
     set_error("cannot sample more indices than available in last codeword; requested: %zu, available: %llu", tests, (unsigned long long)L->last_len);
     return MZK_E_ARG;
   }
-  if (L->rounds > 63) { set_error("fri_prove: too many rounds"); return MZK_E_LENGTH; }
+  if (L->rounds > 63) { set_error("%s: too many rounds", who); return MZK_E_LENGTH; }
+  // expansion factor 0 with no tests halves down to ONE element, which has no tree (and an id-4 leaf no room in a root record)
+  if (gl && L->last_len < 2) { set_error("fri_prove_gl: a one-element last round"); return MZK_E_LENGTH; }
   return MZK_OK;
 }
 
 static int fri_prove_impl(int field_id, const void* src, const void* negative, bool on_device, size_t n, const uint64_t* omega, const uint64_t* offset,
-                          size_t expansion_factor, size_t tests, void* proof_out, size_t proof_cap, hipStream_t s_in) {
+                          size_t expansion_factor, size_t tests, void* proof_out, size_t proof_cap, hipStream_t s_in, bool gl = false) {
   mzk_tx::FriLayout L;
-  MZK_TRY(fri_prove_check(field_id, n, expansion_factor, tests, &L));
-  if (!src || !omega || !offset || !proof_out) { set_error("fri_prove: null pointer"); return MZK_E_ARG; }
-  if (proof_cap < L.total) { set_error("fri_prove: proof buffer of %zu bytes, the layout needs %llu", proof_cap, (unsigned long long)L.total); return MZK_E_LENGTH; }
-  const HostField* hf = host_field(field_id);
-  if (!h_is_canonical(hf, omega) || !h_is_canonical(hf, offset)) { set_error("fri_prove: parameter not canonical"); return MZK_E_RANGE; }
+  const char* who = gl ? "fri_prove_gl" : "fri_prove";
+  MZK_TRY(fri_prove_check(field_id, n, expansion_factor, tests, &L, gl));
+  if (!src || !omega || !offset || !proof_out) { set_error("%s: null pointer", who); return MZK_E_ARG; }
+  if (proof_cap < L.total) { set_error("%s: proof buffer of %zu bytes, the layout needs %llu", who, proof_cap, (unsigned long long)L.total); return MZK_E_LENGTH; }
+  if (gl) {      // canonical words; omega and offset of id 4 in the base field, as everywhere (mzk.h)
+    MZK_TRY(gl_param_check(field_id, omega, who, "parameter", true));
+    MZK_TRY(gl_param_check(field_id, offset, who, "parameter", true));
+  } else if (!h_is_canonical(host_field(field_id), omega) || !h_is_canonical(host_field(field_id), offset)) {
+    set_error("fri_prove: parameter not canonical");
+    return MZK_E_RANGE;
+  }
   MZK_ENTER();
   hipStream_t s = on_device ? s_in : ctx().stream;
   WsGuard wsg(s);
-  const int R = L.rounds, nl = hf->nl;
+  const int R = L.rounds, nl = field_limbs64(field_id);
   const size_t esz = field_bytes(field_id);
   auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
   // one workspace block: codewords of all rounds | digests of all rounds | round-0 magnitudes and signs | transcript | alphas | seen
@@ -1610,7 +1764,7 @@ static int fri_prove_impl(int field_id, const void* src, const void* negative, b
   for (int r = 0; r < R; r++) { cw_off[r] = cw_total; node_off[r] = node_total; cw_total += (n >> r) * esz; node_total += ((n >> r) - 1) * 32; }
   const size_t o_nodes = al(cw_total), o_mag = o_nodes + al(node_total), o_neg = o_mag + (negative ? al(n * esz) : 0);
   const size_t o_tx = o_neg + (negative && !on_device ? al(n) : 0);
-  const size_t o_alpha = o_tx + al(mzk_tx::fri_transcript_cap(L, nl) + 16), o_seen = o_alpha + al(32 * (size_t)R);
+  const size_t o_alpha = o_tx + al((gl ? mzk_tx::fri_transcript_cap_gl(L, nl) : mzk_tx::fri_transcript_cap(L, nl)) + 16), o_seen = o_alpha + al(32 * (size_t)R);
   const size_t o_proof = o_seen + al((L.last_len + 31) / 32 * 4), total = o_proof + (on_device ? 0 : al(L.total));
   uint8_t* blk;
   MZK_TRY(ws_get(WS_MISC_F, total, (void**)&blk));
@@ -1643,8 +1797,8 @@ static int fri_prove_impl(int field_id, const void* src, const void* negative, b
     u64* nd = (u64*)(nodes + node_off[r]);
     MZK_TRY(merkle_hash_levels(0, field_id, leaves, nullptr, len, nd, s, r == 0 ? d_neg : nullptr));
     const bool last = r == R - 1;
-    hipLaunchKernelGGL(k_fri_tx_round, dim3(1), dim3(64), 0, s, tx, r, (const u64*)(nd + 4 * (len - 2)), (u64*)(proof + L.off[mzk_tx::SEC_ROOTS] + 32 * (size_t)r),
-                       alphas + 4 * r, last ? 0 : 1);
+    hipLaunchKernelGGL(gl ? k_fri_tx_round_gl : k_fri_tx_round, dim3(1), dim3(64), 0, s, tx, r, (const u64*)(nd + 4 * (len - 2)),
+                       (u64*)(proof + L.off[mzk_tx::SEC_ROOTS] + 32 * (size_t)r), alphas + 4 * r, last ? 0 : 1);
     MZK_HIP(hipGetLastError());
     if (r == 0 && negative) {
       MZK_TRY(canonicalize_signed(field_id, cw, d_neg, n, s));
@@ -1655,7 +1809,15 @@ static int fri_prove_impl(int field_id, const void* src, const void* negative, b
   }
   const u32* last_cw = (const u32*)(cw + cw_off[R - 1]);
   auto sec = [&](int k) { return proof + L.off[k]; };
-  MZK_TRY(MZK_FIELD_LAUNCH(field_id, k_fri_tx_last<P::NW>, dim3(1), dim3(TX_LAST_THREADS), 0, s, (u8*)tx, R, last_cw, (size_t)L.last_len, n / 2, tests, (u32*)(blk + o_seen), (u64*)sec(mzk_tx::SEC_STATUS), (u64*)sec(mzk_tx::SEC_TOP_INDICES), (u32*)sec(mzk_tx::SEC_LAST_CODEWORD)));
+  if (gl) {
+    MZK_TRY(with_gl(field_id, [&](auto tag) {
+      hipLaunchKernelGGL((k_fri_tx_last_gl<decltype(tag)::NC>), dim3(1), dim3(TX_LAST_THREADS), 0, s, (u8*)tx, R, (const u64*)last_cw, (size_t)L.last_len, n / 2, tests,
+                         (u32*)(blk + o_seen), (u64*)sec(mzk_tx::SEC_STATUS), (u64*)sec(mzk_tx::SEC_TOP_INDICES), (u64*)sec(mzk_tx::SEC_LAST_CODEWORD));
+      return MZK_OK;
+    }));
+  } else {
+    MZK_TRY(MZK_FIELD_LAUNCH(field_id, k_fri_tx_last<P::NW>, dim3(1), dim3(TX_LAST_THREADS), 0, s, (u8*)tx, R, last_cw, (size_t)L.last_len, n / 2, tests, (u32*)(blk + o_seen), (u64*)sec(mzk_tx::SEC_STATUS), (u64*)sec(mzk_tx::SEC_TOP_INDICES), (u32*)sec(mzk_tx::SEC_LAST_CODEWORD)));
+  }
   MZK_HIP(hipGetLastError());
   const size_t queries = 3 * tests * (size_t)(R - 1);
   if (queries) {
@@ -1664,7 +1826,14 @@ static int fri_prove_impl(int field_id, const void* src, const void* negative, b
     A.values = sec(mzk_tx::SEC_VALUES); A.signs = sec(mzk_tx::SEC_SIGNS); A.paths = sec(mzk_tx::SEC_PATHS); A.lens = (u64*)sec(mzk_tx::SEC_PATH_LENS);
     A.n = n; A.tests = tests;
     for (int r = 0; r < 64; r++) { A.cw_off[r] = r < R ? cw_off[r] : 0; A.node_off[r] = r < R ? node_off[r] : 0; }
-    MZK_TRY(MZK_FIELD_LAUNCH(field_id, k_fri_query<P::NW>, dim3((unsigned)queries), dim3(64), 0, s, A));
+    if (gl) {
+      MZK_TRY(with_gl(field_id, [&](auto tag) {
+        hipLaunchKernelGGL((k_fri_query_gl<decltype(tag)::NC>), dim3((unsigned)queries), dim3(64), 0, s, A);
+        return MZK_OK;
+      }));
+    } else {
+      MZK_TRY(MZK_FIELD_LAUNCH(field_id, k_fri_query<P::NW>, dim3((unsigned)queries), dim3(64), 0, s, A));
+    }
     MZK_HIP(hipGetLastError());
   }
   if (on_device) return MZK_OK;
@@ -1672,9 +1841,23 @@ static int fri_prove_impl(int field_id, const void* src, const void* negative, b
   uint64_t status;
   memcpy(&status, proof_out, 8);
   if (status != 0) {
-    set_error("fri_prove: sample_indices found %zu distinct reduced indices in %llu counters", tests, (unsigned long long)mzk_tx::SAMPLE_COUNTER_LIMIT);
+    set_error("%s: sample_indices found %zu distinct reduced indices in %llu counters", who, tests, (unsigned long long)mzk_tx::SAMPLE_COUNTER_LIMIT);
     return MZK_E_RANGE;
   }
+  return MZK_OK;
+}
+
+// mzk_fri_proof_layout / _gl: host only
+static int fri_proof_layout_impl(int field_id, size_t n, size_t expansion_factor, size_t num_colinearity_tests, int* num_rounds, uint64_t* offsets,
+                                 uint64_t* sizes, uint64_t* total_bytes, bool gl) {
+  mzk_tx::FriLayout L;
+  MZK_TRY(fri_prove_check(field_id, n, expansion_factor, num_colinearity_tests, &L, gl));
+  if (num_rounds) *num_rounds = L.rounds;
+  for (int k = 0; k < mzk_tx::SEC_COUNT; k++) {
+    if (offsets) offsets[k] = L.off[k];
+    if (sizes) sizes[k] = L.size[k];
+  }
+  if (total_bytes) *total_bytes = L.total;
   return MZK_OK;
 }
 
@@ -1684,15 +1867,11 @@ extern "C" {
 
 int mzk_fri_proof_layout(int field_id, size_t n, size_t expansion_factor, size_t num_colinearity_tests, int* num_rounds, uint64_t* offsets,
                          uint64_t* sizes, uint64_t* total_bytes) {
-  mzk_tx::FriLayout L;
-  MZK_TRY(fri_prove_check(field_id, n, expansion_factor, num_colinearity_tests, &L));
-  if (num_rounds) *num_rounds = L.rounds;
-  for (int k = 0; k < mzk_tx::SEC_COUNT; k++) {
-    if (offsets) offsets[k] = L.off[k];
-    if (sizes) sizes[k] = L.size[k];
-  }
-  if (total_bytes) *total_bytes = L.total;
-  return MZK_OK;
+  return fri_proof_layout_impl(field_id, n, expansion_factor, num_colinearity_tests, num_rounds, offsets, sizes, total_bytes, false);
+}
+int mzk_fri_proof_layout_gl(int gl_field_id, size_t n, size_t expansion_factor, size_t num_colinearity_tests, int* num_rounds, uint64_t* offsets,
+                            uint64_t* sizes, uint64_t* total_bytes) {
+  return fri_proof_layout_impl(gl_field_id, n, expansion_factor, num_colinearity_tests, num_rounds, offsets, sizes, total_bytes, true);
 }
 int mzk_fri_prove(int field_id, const uint64_t* magnitudes, const uint8_t* negative, size_t n, const uint64_t* omega, const uint64_t* offset,
                   size_t expansion_factor, size_t num_colinearity_tests, uint8_t* proof_out, size_t proof_cap) {
@@ -1702,6 +1881,16 @@ int mzk_fri_prove_dev(int field_id, const void* d_magnitudes, const void* d_nega
                       size_t expansion_factor, size_t num_colinearity_tests, void* d_proof, size_t proof_cap, void* stream) {
   return fri_prove_impl(field_id, d_magnitudes, d_negative, true, n, omega, offset, expansion_factor, num_colinearity_tests, d_proof, proof_cap,
                         (hipStream_t)stream);
+}
+// FRI::prove over the Goldilocks ids: canonical elements only (no signs), 64-byte path entries
+int mzk_fri_prove_gl(int gl_field_id, const uint64_t* codeword, size_t n, const uint64_t* omega, const uint64_t* offset, size_t expansion_factor,
+                     size_t num_colinearity_tests, uint8_t* proof_out, size_t proof_cap) {
+  return fri_prove_impl(gl_field_id, codeword, nullptr, false, n, omega, offset, expansion_factor, num_colinearity_tests, proof_out, proof_cap, nullptr, true);
+}
+int mzk_fri_prove_gl_dev(int gl_field_id, const void* d_codeword, size_t n, const uint64_t* omega, const uint64_t* offset, size_t expansion_factor,
+                         size_t num_colinearity_tests, void* d_proof, size_t proof_cap, void* stream) {
+  return fri_prove_impl(gl_field_id, d_codeword, nullptr, true, n, omega, offset, expansion_factor, num_colinearity_tests, d_proof, proof_cap, (hipStream_t)stream,
+                        true);
 }
 
 }  // extern "C"

@@ -1363,7 +1363,7 @@ int fri_fold_dev_consts(int fid, const void* d_cw, size_t n, const uint64_t* alp
   return MZK_OK;
 }
 // The same fold with alpha in device memory (mzk_fri_prove: the transcript kernel of the round wrote it there; alpha < 2^64, canonical
-// limbs).  k_mont = 2^-1 offset^-1 R^2: one product with the plain alpha gives r_0 in Montgomery form, as the host forms it above.
+// limbs; the Goldilocks ids of mzk_fri_prove_gl go to their own kernel, as in fri_fold_dev_consts).  k_mont = 2^-1 offset^-1 R^2: one product with the plain alpha gives r_0 in Montgomery form, as the host forms it above.
 template <class P>
 __global__ void k_fri_fold_dev_alpha(const u32* __restrict__ cw, size_t h, const u32* __restrict__ alpha, Words8 k_mont, Words8 winv_mont,
                                      Words8 half_mont, u32* __restrict__ out, int per_lane) {
@@ -1385,6 +1385,7 @@ __global__ void k_fri_fold_dev_alpha(const u32* __restrict__ cw, size_t h, const
 int fri_fold_dev_alpha(int fid, const void* d_cw, size_t n, const uint64_t* d_alpha, const FriFoldConsts& fc, void* d_out, hipStream_t s) {
   const size_t h = n / 2;
   if (h == 0) return MZK_OK;
+  if (field_is_gl(fid)) return gl_fri_fold_dev_alpha(fid, d_cw, n, d_alpha, fc.half[0], fc.oinv[0], fc.winv[0], d_out, s);
   const HostField* hf = host_field(fid);
   uint64_t kv[4];
   h_mulmod(hf, kv, fc.half, fc.oinv);

@@ -12,6 +12,7 @@
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
+#include "mzk_gl.h"
 
 #if defined(__HIPCC__)
 #define MZK_TX_HD __host__ __device__ __forceinline__
@@ -26,6 +27,7 @@ typedef uint8_t u8;
 
 constexpr int SHAKE_RATE = 136;
 constexpr int PATH_STRIDE = 48;          // bytes per authentication-path entry in a packed proof (a leaf is at most 41 bytes)
+constexpr int PATH_STRIDE_GL = 64;       // the same in a packed proof of mzk_fri_prove_gl (an M64X3 leaf is up to 59 bytes)
 constexpr u64 SAMPLE_COUNTER_LIMIT = (u64)1 << 20;      // sample_indices gives up (status word 1) after this many counters
 
 // ---- SHAKE256 framing ---------------------------------------------------------------------------------------------
@@ -55,6 +57,12 @@ MZK_TX_HD u64 sample_digest_word3(u64 w3) {
   u64 r = 0;
   for (int i = 0; i < 8; i++) r = (r << 8) | ((w3 >> (8 * i)) & 0xFF);
   return r;
+}
+// F::sample over Goldilocks: that accumulator taken mod p = 2^64 - 2^32 + 1 (the base value; id 4 embeds it as (v, 0, 0),
+// efield.rs:180-186).  The accumulator can be >= p -- with probability 2^-32 -- and is below 2 p: one conditional subtraction.
+MZK_TX_HD u64 sample_gl(u64 w3) {
+  const u64 acc = sample_digest_word3(w3);
+  return acc >= mzk::gl::P ? acc - mzk::gl::P : acc;
 }
 
 // ---- Blake2b-256 (RFC 7693; no key, digest length 32) -----------------------------------------------------------------
@@ -154,8 +162,9 @@ MZK_TX_HD u64 fri_entry_base(u64 n, u64 tests, int layer, int kind) {
   const u64 di = (u64)log2_pow2(n >> layer);
   return e + (u64)kind * tests * di;
 }
-// n a power of two, rounds >= 2 and tests <= the last codeword's length (the caller checks); limbs = 2 (M128) or 4 (Fr)
-MZK_TX_HD void fri_layout(u64 n, u64 expansion_factor, u64 tests, int limbs, FriLayout* L) {
+// n a power of two, rounds >= 2 and tests <= the last codeword's length (the caller checks); limbs = 2 (M128) or 4 (Fr) with
+// PATH_STRIDE, 1 (M64) or 3 (M64X3) with PATH_STRIDE_GL
+MZK_TX_HD void fri_layout_stride(u64 n, u64 expansion_factor, u64 tests, int limbs, int stride, FriLayout* L) {
   L->rounds = fri_num_rounds(n, expansion_factor, tests);
   L->tests = tests;
   L->last_len = L->rounds > 0 ? n >> (L->rounds - 1) : n;
@@ -167,7 +176,7 @@ MZK_TX_HD void fri_layout(u64 n, u64 expansion_factor, u64 tests, int limbs, Fri
   L->size[SEC_LAST_CODEWORD] = 8 * (u64)limbs * L->last_len;
   L->size[SEC_VALUES] = 8 * (u64)limbs * 3 * tests * layers;
   L->size[SEC_SIGNS] = 3 * tests * layers;
-  L->size[SEC_PATHS] = (u64)PATH_STRIDE * L->entries;
+  L->size[SEC_PATHS] = (u64)stride * L->entries;
   L->size[SEC_PATH_LENS] = 8 * L->entries;
   u64 at = 0;
   for (int s = 0; s < SEC_COUNT; s++) {
@@ -176,8 +185,35 @@ MZK_TX_HD void fri_layout(u64 n, u64 expansion_factor, u64 tests, int limbs, Fri
   }
   L->total = at;
 }
+MZK_TX_HD void fri_layout(u64 n, u64 expansion_factor, u64 tests, int limbs, FriLayout* L) { fri_layout_stride(n, expansion_factor, tests, limbs, PATH_STRIDE, L); }
+// the packed proof of mzk_fri_prove_gl: the same sections, nc = 1 or 3 words per element, 64-byte path entries, signs all zero
+MZK_TX_HD void fri_layout_gl(u64 n, u64 expansion_factor, u64 tests, int nc, FriLayout* L) { fri_layout_stride(n, expansion_factor, tests, nc, PATH_STRIDE_GL, L); }
 // bytes of the proof stream after the last push: count | one record per root | the last codeword as one object of
 // `last_len` leaves, each u64 length + bincode(FiniteFieldElement) (at most 9 + 4 * 2 * limbs bytes)
 MZK_TX_HD u64 fri_transcript_cap(const FriLayout& L, int limbs) { return 8 + 48 * (u64)L.rounds + 8 + L.last_len * (8 + 9 + 8 * (u64)limbs); }
+
+// ---- the last codeword of a Goldilocks proof stream (mzk_fri_prove_gl) -------------------------------------------------
+// One object of m strings, string j = u64 LE length | gl::leaf_bytes<NC>(element j): 9 .. 17 bytes for M64, 8 .. 59 (nested) for M64X3.
+MZK_TX_HD u64 fri_transcript_cap_gl(const FriLayout& L, int nc) {
+  return 8 + 48 * (u64)L.rounds + 8 + L.last_len * (8 + (u64)(nc == 1 ? mzk::gl::LEAF_MAX_BASE : mzk::gl::LEAF_MAX_EXT));
+}
+// bytes of string j's record (length word included)
+template <int NC> MZK_TX_HD u64 fri_gl_record_len(const u64* c) { return 8 + (u64)mzk::gl::leaf_bytes<NC>(c, 0, [](int, uint32_t) {}); }
+// writes the record at dst (any alignment) and returns its length
+template <int NC> MZK_TX_HD u64 fri_gl_record_put(const u64* c, u8* dst) {
+  const u64 len = (u64)mzk::gl::leaf_bytes<NC>(c, 8, [&](int pos, uint32_t byte) { dst[pos] = (u8)byte; }) - 8;
+  for (int b = 0; b < 8; b++) dst[b] = (u8)(len >> (8 * b));
+  return 8 + len;
+}
+// The whole push, one record after the other: behind the `rounds` root records of tx the object's string count m, then the records;
+// the object count becomes rounds + 1.  Returns the stream's length.  (k_fri_tx_last_gl places the same records by a prefix sum over
+// fri_gl_record_len, a workgroup's worth at a time; this serial form is the host's, and the check of both record functions.)
+template <int NC> MZK_TX_HD u64 fri_gl_push_last(u8* tx, int rounds, const u64* cw, u64 m) {
+  u64 at = 8 + 48 * (u64)rounds;
+  for (int b = 0; b < 8; b++) { tx[b] = (u8)(((u64)rounds + 1) >> (8 * b)); tx[at + b] = (u8)(m >> (8 * b)); }
+  at += 8;
+  for (u64 j = 0; j < m; j++) at += fri_gl_record_put<NC>(cw + j * NC, tx + at);
+  return at;
+}
 
 }  // namespace mzk_tx

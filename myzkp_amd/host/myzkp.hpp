@@ -18,7 +18,7 @@
 //   accumulate_curve_points (G1 and G2)     zksnark/utils.rs:83-92
 //   Merkle::commit / open, commit_codeword   algebra/merkle.rs:15-46, zkstark/fri.rs:160-166
 //   fri_split_and_fold, fri_commit           zkstark/fri.rs:144-209
-//   FriProof, fri_prove                      zkstark/fri.rs:71-143      -> mzk_fri_prove
+//   FriProof, fri_prove                      zkstark/fri.rs:71-143      -> mzk_fri_prove (M64, <M64, Ip3>: mzk_fri_prove_gl)
 //   boundary_quotients, fast_stark_dims      zkstark/fast_stark.rs:217-224, :573-616 -> mzk_poly_div_roots, mzk_stark_plan
 //   FastStark (preprocess, prove), FastStarkProof   zkstark/fast_stark.rs:22-75, :177-396 -> mzk_stark_new, mzk_stark_prove
 //   batch::split_and_fold / commit_gemini / open_gemini / prove_sumcheck   algebra/gemini.rs:51-144, algebra/sumcheck.rs:128-167
@@ -681,7 +681,7 @@ FriCommitment<F> fri_commit(const std::vector<F>& initial_codeword, const F& ome
   }
   return out;
 }
-// FRI::prove (fri.rs:99-143) in one call (mzk_fri_prove): commit, the proof stream (started empty, as FRI::prove starts it),
+// FRI::prove (fri.rs:99-143) in one call (mzk_fri_prove; mzk_fri_prove_gl for the Goldilocks tags): commit, the proof stream (started empty, as FRI::prove starts it),
 // sample_indices and reveal on the device.  FriProof / FriQueryLayer as fri.rs:71-82; the codeword's elements are canonical here.
 template <class F> struct FriQueryLayer {
   std::pair<std::vector<F>, std::vector<MerklePath>> a, b, c;
@@ -698,10 +698,15 @@ FriProof<F> fri_prove(const std::vector<F>& initial_codeword, const F& omega, co
   const size_t n = initial_codeword.size(), nl = F().value.size(), T = num_colinearity_tests;
   int rounds = 0;
   uint64_t off[MZK_FRI_SECTIONS], size[MZK_FRI_SECTIONS], total = 0;
-  expect(mzk_fri_proof_layout(fid, n, expansion_factor, T, &rounds, off, size, &total));
+  // the Goldilocks tags have entry points and a path stride of their own (mzk_fri_prove_gl: no signs, 64-byte path entries)
+  constexpr bool GL = F::FIELD_ID == MZK_FIELD_M64 || F::FIELD_ID == MZK_FIELD_M64X3;
+  constexpr uint64_t STRIDE = GL ? MZK_FRI_PATH_STRIDE_GL : MZK_FRI_PATH_STRIDE;
+  if constexpr (GL) expect(mzk_fri_proof_layout_gl(fid, n, expansion_factor, T, &rounds, off, size, &total));
+  else expect(mzk_fri_proof_layout(fid, n, expansion_factor, T, &rounds, off, size, &total));
   std::vector<uint8_t> buf(total);
   auto c = to_wire(initial_codeword);
-  expect(mzk_fri_prove(fid, c.data(), nullptr, n, omega.value.data(), offset.value.data(), expansion_factor, T, buf.data(), buf.size()));
+  if constexpr (GL) expect(mzk_fri_prove_gl(fid, c.data(), n, omega.value.data(), offset.value.data(), expansion_factor, T, buf.data(), buf.size()));
+  else expect(mzk_fri_prove(fid, c.data(), nullptr, n, omega.value.data(), offset.value.data(), expansion_factor, T, buf.data(), buf.size()));
   auto u64_at = [&](uint64_t byte) { uint64_t v; std::memcpy(&v, buf.data() + byte, 8); return v; };
   auto elems = [&](uint64_t byte, size_t count) {
     std::vector<uint64_t> w(count * nl);
@@ -723,7 +728,7 @@ FriProof<F> fri_prove(const std::vector<F>& initial_codeword, const F& omega, co
       for (size_t s = 0; s < T; s++, e += depth) {
         MerklePath path;
         for (size_t l = 0; l < depth; l++) {
-          const uint64_t at = off[MZK_FRI_PATHS] + (uint64_t)MZK_FRI_PATH_STRIDE * (e + l);
+          const uint64_t at = off[MZK_FRI_PATHS] + STRIDE * (e + l);
           path.emplace_back(buf.begin() + at, buf.begin() + at + u64_at(off[MZK_FRI_PATH_LENS] + 8 * (e + l)));
         }
         parts[k]->second.push_back(std::move(path));

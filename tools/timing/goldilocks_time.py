@@ -7,10 +7,12 @@ One GPU visit, two steps, each a child process under its own time limit, the sec
   1. tools/microbench/copy_bw (prebuilt): the copy rate of this box, the yardstick of the transform rows;
   2. this file with --measure: in ONE process, device-resident (hipEvent pairs around single calls, warm-up, median of --reps):
        forward NTT over M64, M64X3 and M128 at 2^16, 2^20, 2^24; coset LDE 2^18 -> 2^20, fold at 2^20, Merkle commit at 2^20 and the
-       FRI commit loop (host callback included) at 2^16 for the two Goldilocks ids.
+       FRI commit loop (host callback included) at 2^16 for the two Goldilocks ids; FRI::prove at 2^16 and 2^20 (expansion 4, 17 tests)
+       as one call (mzk_fri_prove_gl_dev) and as the composition it replaces (commit with a host callback, leaves, open_multi).
 A transform row reports (bytes in + bytes out) / time as a fraction of the copy rate -- the HBM-roofline figure of a kernel that would
 read and write the data once; the transform makes two to three passes, which is what the fraction shows.
-Gate (exit status 1 when missed): the M64 transform is not slower than the M128 transform at 2^20 and at 2^24 in this run.
+Gates (exit status 1 when missed): the M64 transform is not slower than the M128 transform at 2^20 and at 2^24 in this run; the
+one-call prover is not slower than the composed form (the same kernels minus one host round trip per round).
 The M64X3 : M64 ratio is reported against the 3 that the work count predicts, without a threshold."""
 import argparse, ctypes, os, re, statistics, subprocess, sys
 
@@ -64,7 +66,77 @@ def measure(reps, warmup, copy_gbs):
     def limbs(fid, v):
         return mz.to_limbs([v], mz.LIMBS[fid])
 
-    lines, ntt_ms = [], {}
+    lines, ntt_ms, prove_ms = [], {}, {}
+    EXPANSION, TESTS = 4, 17
+
+    def prove_rows(fid, lg, cw):
+        """mzk_fri_prove_gl_dev, and today's composition of the same proof: the commit loop with the transcript in a host callback (one
+        round trip per round), the last codeword, the indices sampled on the host, then merkle_open_multi and the revealed leaves"""
+        import hashlib
+        n, nl = 1 << lg, mz.LIMBS[fid]
+        w, off = mz.root_of_unity(fid, lg), 7
+        wl, ol = limbs(fid, w), limbs(fid, off)
+        R, _, total = mz.fri_proof_layout_gl(fid, n, EXPANSION, TESTS)
+        proof = torch.empty(total, dtype=torch.uint8, device=dev)
+
+        def one_call():
+            check(L.mzk_fri_prove_gl_dev(fid, vp(cw.data_ptr()), SZ(n), vp(wl.ctypes.data), vp(ol.ctypes.data), SZ(EXPANSION), SZ(TESTS), vp(proof.data_ptr()),
+                                         SZ(total), st))
+
+        def u64le(x):
+            return int(x).to_bytes(8, "little")
+
+        def leaf(v):        # the base leaf of mzk.h: sign byte, digit count, u32 digits
+            d = [v & 0xFFFFFFFF, v >> 32] if v >> 32 else ([v] if v else [])
+            return bytes([1 if v else 0]) + u64le(len(d)) + b"".join(x.to_bytes(4, "little") for x in d)
+
+        def elem_leaf(row):
+            if nl == 1:
+                return leaf(int(row[0]))
+            k = 3
+            while k and int(row[k - 1]) == 0:
+                k -= 1
+            return u64le(k) + b"".join(leaf(int(c)) for c in row[:k])
+
+        def composed():
+            stream = [b""]
+
+            def challenge(rnd, last, root):
+                stream[0] += u64le(1) + u64le(32) + root
+                if last:
+                    return None
+                d = hashlib.shake_256(u64le(rnd + 1) + stream[0]).digest(32)
+                return int.from_bytes(d[24:], "big") % P64
+            _, _, trees = mz.fri_commit(fid, None, w, off, R, challenge, keep_trees=True, codewords=False, device_ptr=cw.data_ptr(), n=n)
+            m = n >> (R - 1)
+            last = trees[-1].leaves(list(range(m)))
+            body = u64le(m) + b"".join(u64le(len(x)) + x for x in (elem_leaf(row) for row in last))
+            seed = hashlib.shake_256(u64le(R + 1) + stream[0] + body).digest(32)
+            top, seen, counter = [], set(), 0
+            while len(top) < TESTS:
+                h = hashlib.blake2b(seed + u64le(counter), digest_size=32).digest()
+                idx = int.from_bytes(h[24:], "big") % (n // 2)
+                counter += 1
+                if idx % m not in seen:
+                    seen.add(idx % m)
+                    top.append(idx)
+            lists = [[] for _ in range(R)]
+            for i in range(R - 1):
+                half_len = (n >> i) // 2
+                a = [t % half_len for t in top]
+                lists[i] += a + [x + half_len for x in a]
+                lists[i + 1] += a
+            mz.merkle_open_multi(trees, lists)
+            for r in range(R):
+                trees[r].leaves(lists[r])
+            for t in trees:
+                t.close()
+        one, one_best = timed(one_call)
+        comp, comp_best = timed(composed)
+        lines.append("prove  %-5s 2^%-2d fri_prove_gl_dev, %d rounds            median %8.4f ms  best %8.4f ms" % (NAMES[fid], lg, R, one, one_best))
+        lines.append("prove  %-5s 2^%-2d composed: commit (host callback), leaves, open_multi  median %8.4f ms  best %8.4f ms" %
+                     (NAMES[fid], lg, comp, comp_best))
+        return one, comp
     for lg in (16, 20, 24):
         n = 1 << lg
         for fid in (M64, M64X3, M128):
@@ -103,8 +175,16 @@ def measure(reps, warmup, copy_gbs):
         med, best = timed(commit)
         lines.append("fri    %-5s 2^16 commit loop, 10 rounds, trees kept  median %8.4f ms  best %8.4f ms  (host callback and handle release included)" %
                      (NAMES[fid], med, best))
+        # FRI::prove in one enqueue next to the composed form it replaces, timed in the same run on the same codeword (the LDE above)
+        for lg in (16, 20):
+            n = 1 << lg
+            prove_ms[(fid, lg)] = prove_rows(fid, lg, out[:n * nl])
         del coef, out, half
     ok = True
+    for (fid, lg), (one, composed) in sorted(prove_ms.items()):
+        verdict = "ok" if one <= composed else "MISSED"
+        ok = ok and one <= composed
+        lines.append("gate   prove %-5s 2^%d: one call %.4f ms <= composed %.4f ms: %s" % (NAMES[fid], lg, one, composed, verdict))
     for lg in (20, 24):
         a, b = ntt_ms[(M64, lg)], ntt_ms[(M128, lg)]
         verdict = "ok" if a <= b else "MISSED"
