@@ -20,13 +20,13 @@
 // offset^i pre-scale uses tables of the same form and is fused into the first pass's loads (zero padding included).
 #include "mzk_common.h"
 #include "mzk_gl.h"
+#include "mzk_ntt_plan.h"
 
 namespace mzk {
 
 typedef uint64_t u64;
 
-constexpr int GL_TL = 12, GL_TILE = 1 << GL_TL, GL_NT = 256, GL_EPL = GL_TILE / GL_NT;      // 16 elements per lane
-constexpr int GL_MAX_LEVEL = 8;                    // widest level of a multi-pass plan
+constexpr int GL_TL = NTT_GEOS[NTT_GEO_GL].tl, GL_TILE = 1 << GL_TL, GL_NT = NTT_GEOS[NTT_GEO_GL].nt, GL_EPL = GL_TILE / GL_NT;      // 16 elements per lane
 constexpr int GL_TW = GL_TILE / 2;                 // in-tile twiddles w_4096^j
 constexpr int GL_POW_LO = 4096, GL_POW_MID = 4096, GL_POW_HI = 256, GL_POW = GL_POW_LO + GL_POW_MID + GL_POW_HI;
 // tile position -> LDS slot: one slot of padding per 16 and per 256 elements, so that neither the bit-reversed scatter of the loads
@@ -95,7 +95,6 @@ __device__ __forceinline__ void gl_stage_twiddles(u64* tw, const u64* __restrict
 
 // coset LDE: element idx of transform o is coef[o * n_coef + idx] * offset^idx below n_coef and zero beyond (ntt.rs:254-269)
 struct GlPre { const u64* coef; size_t n_coef; const u64* otab; int obig; };
-struct GlLevels { int nlev; int lg[4]; };
 
 // Pass t < last: in place on the strided columns of block o (2^(lgn + lgM) elements), then the inter-pass twiddle
 // w^(escale * column * k), escale = n / block size.  lgn + lgc = 12.
@@ -147,7 +146,7 @@ __global__ __launch_bounds__(GL_NT) void k_gl_ntt_strided(const u64* __restrict_
 // grid may cover a batch (row r belongs to transform r >> lg_rows).  Logical row r is the digit reversal of its memory row
 // (row_base, as in k_ntt_last).
 template <int NC, bool PRE>
-__global__ __launch_bounds__(GL_NT) void k_gl_ntt_last(const u64* __restrict__ in, u64* __restrict__ out, const u64* __restrict__ tab, GlLevels li, int lgn,
+__global__ __launch_bounds__(GL_NT) void k_gl_ntt_last(const u64* __restrict__ in, u64* __restrict__ out, const u64* __restrict__ tab, NttLevels li, int lgn,
                                                        int lgr, int lg_rows, u64 scale, int has_scale, size_t total_rows, int tl, GlPre pre) {
   __shared__ u64 lds[GL_LDS_DATA + GL_TW];
   u64* tw = lds + GL_LDS_DATA;
@@ -250,9 +249,9 @@ __global__ __launch_bounds__(GL_NT) void k_gl_fri_fold_dev_alpha(const u64* __re
 }
 
 // ---- plans ------------------------------------------------------------------------------------------------------------------
-// Per (context, log2 n, direction, root): the level split and ONE device table [w_{2^tl}^j, j < 2048 | lo | mid | hi] of the effective
+// Per (context, log2 n, direction, root): ONE device table [w_{2^tl}^j, j < 2048 | lo | mid | hi] of the effective
 // root (root^-1 for the inverse).  Offset tables of the LDE: [lo | mid | hi] of the offset, kept per (context, offset).
-struct GlPlan { unsigned logn; bool inverse; u64 root; GlLevels li; int tl; u64* d_tab; u64 scale; int has_scale; uint64_t stamp; };
+struct GlPlan { unsigned logn; bool inverse; u64 root; int tl; u64* d_tab; u64 scale; int has_scale; uint64_t stamp; };
 struct GlOffTab { u64 offset; u64* d_tab; uint64_t stamp; };
 static std::vector<GlPlan*> g_gl_plans[MZK_MAX_CTX];
 static std::vector<GlOffTab*> g_gl_offs[MZK_MAX_CTX];
@@ -266,16 +265,6 @@ void gl_release_plans() {
   g_gl_offs[ctx().index].clear();
 }
 
-static GlLevels gl_choose_levels(unsigned logn) {
-  GlLevels li{};
-  if (logn <= (unsigned)GL_TL) { li.nlev = 1; li.lg[0] = (int)logn; return li; }
-  const int k = (int)((logn + GL_MAX_LEVEL - 1) / GL_MAX_LEVEL);
-  li.nlev = k;
-  // the wider levels last: a strided pass works on whole tiles, so the block it splits -- at the second to last pass the last two
-  // levels together -- must hold at least one (2^13 = 7 + 6, 2^17 = 5 + 6 + 6)
-  for (int i = 0; i < k; i++) li.lg[i] = (int)logn / k + (i >= k - (int)logn % k ? 1 : 0);
-  return li;
-}
 static void gl_fill_pow(u64 g, u64* t) {        // [lo | mid | hi] of g
   u64 x = 1;
   for (int i = 0; i < GL_POW_LO; i++) { t[i] = x; x = gl::mul(x, g); }
@@ -315,7 +304,7 @@ static int gl_get_plan(unsigned logn, bool inverse, u64 root, hipStream_t s, GlP
   if (gl::pow(root, n / 2) == 1) { set_error("primitive root is not primitive nth root of unity, where n is len(values)"); return MZK_E_ROOT_PRIM; }
   MZK_TRY(gl_evict(plans, GL_MAX_PLANS, s));
   GlPlan* pl = new GlPlan();
-  pl->logn = logn; pl->inverse = inverse; pl->root = root; pl->li = gl_choose_levels(logn);
+  pl->logn = logn; pl->inverse = inverse; pl->root = root;
   pl->tl = logn < (unsigned)GL_TL ? (int)logn : GL_TL;
   pl->stamp = ++g_gl_stamp;
   const u64 w = inverse ? gl::pow(root, n - 1) : root;          // root^-1 = root^(n-1)                      (ntt.rs:59)
@@ -347,44 +336,30 @@ static int gl_get_offtab(u64 offset, hipStream_t s, const u64** out) {
   return MZK_OK;
 }
 
+// Walks the steps of ntt_plan (mzk_ntt_plan.h) over the tables of `pl`.
 template <int NC>
 static int gl_run_plan(const GlPlan* pl, const u64* d_in, u64* d_out, size_t batch, const GlPre* pre, hipStream_t s) {
-  const GlLevels& li = pl->li;
   const unsigned logn = pl->logn;
+  const NttSchedule sc = ntt_plan(NC == 3 ? MZK_FIELD_M64X3 : MZK_FIELD_M64, logn, batch, NttKnobs());
+  if (sc.err != MZK_OK) { set_error("%s", sc.msg); return sc.err; }
   const int big = logn > 24 ? 1 : 0;
   const GlPre none{nullptr, 0, nullptr, 0};
   ProfScope whole(s, MZK_PH_NTT_TOTAL);
   const u64* src = d_in;
   u64* tmp = nullptr;
-  if (li.nlev > 1) MZK_TRY(ws_get(WS_NTT_TMP, (batch << logn) * 8 * NC, (void**)&tmp));
-  int lg_after = (int)logn;
-  for (int t = 0; t < li.nlev - 1; t++) {
-    const int lgn = li.lg[t], lgM = lg_after - lgn, lgc = GL_TL - lgn;
-    const size_t blocks = (batch << (logn - GL_TL)) * NC;
-    if (blocks > 0x7fffffffu) { set_error("ntt: too many tiles for one launch"); return MZK_E_ARG; }
-    if (lgM < lgc) { set_error("ntt: level split leaves a block smaller than a tile"); return MZK_E_ARG; }      // (gl_choose_levels never does)
-    const u64 escale = (u64)1 << (logn - (unsigned)(lgn + lgM));
-    if (t == 0 && pre)
-      hipLaunchKernelGGL((k_gl_ntt_strided<NC, true>), dim3((unsigned)blocks), dim3(GL_NT), 0, s, src, tmp, (const u64*)pl->d_tab, lgn, lgM, lgc, pl->tl, big, escale, *pre);
-    else
-      hipLaunchKernelGGL((k_gl_ntt_strided<NC, false>), dim3((unsigned)blocks), dim3(GL_NT), 0, s, src, tmp, (const u64*)pl->d_tab, lgn, lgM, lgc, pl->tl, big, escale, none);
-    src = tmp;
-    lg_after = lgM;
-  }
-  {
-    const int lgn = li.lg[li.nlev - 1];
-    const int lg_rows = (int)logn - lgn;
-    const size_t total_rows = batch << lg_rows;
-    int lgr = GL_TL - lgn;
-    while (lgr > 0 && ((size_t)1 << lgr) > total_rows) lgr--;
-    const size_t blocks = ((total_rows + ((size_t)1 << lgr) - 1) >> lgr) * NC;
-    if (blocks > 0x7fffffffu) { set_error("ntt: too many tiles for one launch"); return MZK_E_ARG; }
-    if (li.nlev == 1 && pre)
-      hipLaunchKernelGGL((k_gl_ntt_last<NC, true>), dim3((unsigned)blocks), dim3(GL_NT), 0, s, src, d_out, (const u64*)pl->d_tab, li, lgn, lgr, lg_rows, pl->scale,
-                         pl->has_scale, total_rows, pl->tl, *pre);
-    else
-      hipLaunchKernelGGL((k_gl_ntt_last<NC, false>), dim3((unsigned)blocks), dim3(GL_NT), 0, s, src, d_out, (const u64*)pl->d_tab, li, lgn, lgr, lg_rows, pl->scale,
-                         pl->has_scale, total_rows, pl->tl, none);
+  if (sc.tmp_bytes) MZK_TRY(ws_get(WS_NTT_TMP, sc.tmp_bytes, (void**)&tmp));
+  for (int t = 0; t < sc.nsteps; t++) {
+    const NttStep& st = sc.steps[t];
+    const bool with_pre = t == 0 && pre;
+    if (st.kind == NTT_STEP_STRIDED) {
+      const u64 escale = (u64)1 << (logn - (unsigned)(st.lgn + st.lgM));
+      hipLaunchKernelGGL((with_pre ? k_gl_ntt_strided<NC, true> : k_gl_ntt_strided<NC, false>), dim3(st.grid), dim3(st.block), 0, s, src, tmp, (const u64*)pl->d_tab,
+                         st.lgn, st.lgM, st.lgc, pl->tl, big, escale, with_pre ? *pre : none);
+      src = tmp;
+    } else {
+      hipLaunchKernelGGL((with_pre ? k_gl_ntt_last<NC, true> : k_gl_ntt_last<NC, false>), dim3(st.grid), dim3(st.block), 0, s, src, d_out, (const u64*)pl->d_tab, sc.li,
+                         st.lgn, st.lgr, st.lg_rows, pl->scale, pl->has_scale, st.total_rows, pl->tl, with_pre ? *pre : none);
+    }
   }
   MZK_HIP(hipGetLastError());
   return MZK_OK;
@@ -438,7 +413,7 @@ int gl_coset_lde_dev_impl(int fid, const void* d_coef, size_t n_coef, const uint
   MZK_TRY(gl_get_offtab(offset_host[0], s, &otab));
   if (order == 1) {      // one point: the constant coefficient (or zero), no root involved
     const GlPre pre{(const u64*)d_coef, n_coef, otab, 0};
-    const GlLevels li{1, {0, 0, 0, 0}};
+    const NttLevels li{1, {0, 0, 0, 0}};
     const int nc = field_gl_comps(fid);
     const size_t blocks = batch * nc;
     if (blocks > 0x7fffffffu) { set_error("coset_lde: order * batch too large"); return MZK_E_ARG; }

@@ -25,32 +25,18 @@
 #include "mzk_common.h"
 #include "mzk_field_asm.h"
 #include "mzk_gl.h"
+#include "mzk_ntt_plan.h"
 
 namespace mzk {
 
-constexpr int TILE_LOG = 10;
-#ifndef MZK_NTT_THREADS
-#define MZK_NTT_THREADS 256
-#endif
-constexpr int NTHREADS = MZK_NTT_THREADS;
-#ifndef MZK_NTT_MAX_LEVEL_LOG
-#define MZK_NTT_MAX_LEVEL_LOG 8
-#endif
-constexpr int MAX_LEVEL_LOG = MZK_NTT_MAX_LEVEL_LOG;
+constexpr int TILE_LOG = NTT_GEOS[NTT_GEO_S].tl;
 #ifndef MZK_NTT_LAZY_FIRST
 #define MZK_NTT_LAZY_FIRST 1       // 0: A/B builds of the carry-everywhere butterflies (tools/timing/time_ntt.py with MZK_HIP_LIB)
 #endif
 constexpr bool NTT_LAZY_FIRST = MZK_NTT_LAZY_FIRST != 0;
-// Tile geometry.  Small (1024 elements, 256 lanes, levels of <= 2^8): every size below 2^20.  Large (4096 elements,
-// 1024 lanes = one workgroup per CU, levels of <= 2^10): from 2^20 points on, where 256+ workgroups exist -- a 2^20
-// transform is TWO passes of 2^10 levels instead of three (one global round trip and one inter-pass twiddle product
-// per element less), each tile still 4+ adjacent columns wide (>= 128-byte runs).  The Fr tile is 144 KiB of limbs, so
-// its in-tile twiddles are staged as packed words (16 KiB: 160 KiB exactly) and unpacked at use.
-// TWG_ (M128 large tiles): the in-tile twiddles are NOT staged in LDS -- a 4096-element M128 tile is 80 KiB, so without its
-// 10 KiB of twiddles TWO workgroups of 512 lanes share a CU and one's loads / stores run under the other's butterflies (the
-// single 1024-lane workgroup per CU had nothing to overlap its ~22 us of global traffic with).  A twiddle is 16 packed bytes:
-// stage pairs in which a wave shares its twiddles read them by scalar loads, the others by one dwordx4 per twiddle from L1.
-// WPE_: waves per SIMD the register budget must allow (4 = two 512-lane workgroups per CU).
+// Tile geometry (the numbers and what each is for: NttGeo / NTT_GEOS, mzk_ntt_plan.h).  TWG_: the in-tile twiddles are NOT staged in
+// LDS.  A twiddle is 16 packed bytes: stage pairs in which a wave shares its twiddles read them by scalar loads, the others by one
+// dwordx4 per twiddle from L1.  WPE_: waves per SIMD the register budget must allow (4 = two 512-lane workgroups per CU).
 template <int TL_, int NT_, int MAXLV_, bool TWG_ = false, int WPE_ = 1> struct Geo {
   static constexpr int TL = TL_, TILE = 1 << TL_, NT = NT_, MAXLV = MAXLV_, WPE = WPE_;
   static constexpr bool TWG = TWG_;
@@ -70,42 +56,30 @@ template <int TL_, int NT_, int MAXLV_, bool TWG_ = false, int WPE_ = 1> struct 
     const int x = (TL_ == 10) ? (h ^ (h << 2) ^ (h << 3)) : ((h >> 2) ^ (h << 1) ^ (h << 3));
     return pos ^ (x & 31);
   }
-  template <class P> static constexpr bool twpack() { return !TWG_ && (size_t)4 * P::L * (TILE + (1 << (MAXLV_ - 1))) > (size_t)160 * 1024; }
-  template <class P> static constexpr size_t lds_bytes(int lgn) {
-    if (TWG_) return sizeof(u32) * (size_t)P::L * TILE;
-    return sizeof(u32) * ((size_t)P::L * TILE + (size_t)(twpack<P>() ? P::NW : P::L) * TWS);
-  }
+  template <class P> static constexpr bool twpack() { return ntt_twpack(NttGeo{TL_, NT_, MAXLV_, TWG_, WPE_}, P::L); }
 };
-typedef Geo<TILE_LOG, NTHREADS, MAX_LEVEL_LOG> GeoS;
-typedef Geo<TILE_LOG, NTHREADS, TILE_LOG> GeoS1;   // the one-pass transforms of 2^9 and 2^10 points: their level is wider than GeoS's twiddle rows
-typedef Geo<12, 1024, 10> GeoL;
-typedef Geo<12, 512, 10, true, 4> GeoM;        // M128 large tiles: two workgroups per CU
+template <int ID> using GeoOf = Geo<NTT_GEOS[ID].tl, NTT_GEOS[ID].nt, NTT_GEOS[ID].maxlv, NTT_GEOS[ID].twg, NTT_GEOS[ID].wpe>;
+typedef GeoOf<NTT_GEO_S> GeoS;
+typedef GeoOf<NTT_GEO_S1> GeoS1;
+typedef GeoOf<NTT_GEO_L> GeoL;
+typedef GeoOf<NTT_GEO_M> GeoM;
 template <class P> struct LargeGeo { typedef GeoL type; };
-template <> struct LargeGeo<M128Params> { typedef GeoM type; };
-// The large geometry is used exactly where it saves a whole pass: 2^20 (two passes of 2^10 instead of 7/7/6: measured
-// Fr 0.147 -> 0.137 ms, M128 0.063 -> 0.056 ms) and 2^25 .. 2^30.  Where both geometries need three passes the small
-// tiles win (2^21 .. 2^24: Fr +8 %, M128 +16 % with large tiles; tools/timing/time_ntt.py with MZK_NTT_LARGE_FR /
-// MZK_NTT_LARGE_M128 = smallest log2 size forced onto the large geometry, 99 = never).
-// A BATCH of transforms gives the small tiles what a single 2^20 transform lacks: several rounds of workgroups per CU,
-// so the loads and stores of one tile run under the butterflies of its neighbours (four small-tile workgroups share a
-// CU; the large tile owns it) -- from three Fr / two M128 transforms of 2^20 on, three overlapped passes beat two
-// exposed ones (tools/timing/ntt_batch.py: Fr 0.1045 vs 0.1131 ms per transform at batch 16, M128 0.041 vs 0.048).
-static bool large_geo(int fid, unsigned logn, size_t batch = 1) {
-  static const int env_fr = tune_int("MZK_NTT_LARGE_FR", -1);
-  static const int env_m = tune_int("MZK_NTT_LARGE_M128", -1);
-  const int env = fid == MZK_FIELD_M128 ? env_m : env_fr;
-  if (env >= 0) return logn >= (unsigned)env && logn >= 14;
-  if (logn < 20) return false;
-  if (batch > (fid == MZK_FIELD_M128 ? 1u : 2u)) return false;
-  return (logn + 9) / 10 < (logn + MAX_LEVEL_LOG - 1) / MAX_LEVEL_LOG;
+template <> struct LargeGeo<M128Params> { typedef GeoM type; };      // the only field ntt_plan puts on NTT_GEO_M
+static_assert(ntt_limbs(MZK_FIELD_FR) == FrParams::L && ntt_words(MZK_FIELD_FR) == FrParams::NW && ntt_limbs(MZK_FIELD_M128) == M128Params::L &&
+              ntt_words(MZK_FIELD_M128) == M128Params::NW, "mzk_ntt_plan.h sizes the LDS for these limb and word counts");
+
+// the launch-shape switches: read once; in the shipped library tune_int is the constant default
+static const NttKnobs& ntt_knobs() {
+  static const NttKnobs k = [] {
+    const NttKnobs d;
+    return NttKnobs{tune_int("MZK_NTT_LARGE_FR", d.large_fr), tune_int("MZK_NTT_LARGE_M128", d.large_m128), tune_int("MZK_NTT_M128_TWO_WG", d.m128_two_wg),
+                    tune_int("MZK_NTT_WT_LO", d.wt_lo), tune_int("MZK_NTT_WT_HI", d.wt_hi_fr), tune_int("MZK_NTT_WT_HI", d.wt_hi_m128),
+                    tune_int("MZK_NTT_WT_MASK", d.wt_mask)};
+  }();
+  return k;
 }
 
 struct Words8 { u32 w[8]; };
-
-struct LevelInfo {
-  int nlev;
-  int lg[4];
-};
 
 // ---- global memory <-> limbs ----------------------------------------------------------------------
 // The streaming accesses of the transform passes -- the data (read once, written once per pass) and the inter-pass twiddles -- do NOT
@@ -119,7 +93,7 @@ __device__ __forceinline__ u32x4_t stream_load16(const u32* p) {
 // wt: the store goes out write-through at agent scope (`sc1`), so what a pass writes reaches the fabric while the other waves
 // still compute instead of sitting dirty in the XCDs' L2s until the end-of-kernel release flushes it.  A template flag of the pass
 // kernels (a run-time branch around the store cost the 128-VGPR instantiations two to four spilled registers), chosen per transform
-// size by run_plan_geo.
+// size by ntt_plan.
 __device__ __forceinline__ void stream_store16(u32* p, u32x4_t v, bool wt) {
   if (wt) asm volatile("global_store_dwordx4 %0, %1, off sc1" : : "v"(p), "v"(v) : "memory");
   else *reinterpret_cast<u32x4_t*>(p) = v;
@@ -600,7 +574,7 @@ __global__ __launch_bounds__(G::NT, G::WPE) void k_ntt_strided(const u32* __rest
 // of small polynomials per launch.
 template <class P, class G, bool WT>
 __global__ __launch_bounds__(G::NT, G::WPE) void k_ntt_last(const u32* __restrict__ in, u32* __restrict__ out,
-                                                        const u32* __restrict__ tw_tile, LevelInfo li, int lgn, int lgr,
+                                                        const u32* __restrict__ tw_tile, NttLevels li, int lgn, int lgr,
                                                         int lg_rows, Words8 scale, int has_scale, size_t total_rows, int fuse, const u32* __restrict__ tw_shoup) {
   extern __shared__ __attribute__((aligned(16))) u32 lds[];
   const int tid = threadIdx.x;
@@ -850,10 +824,9 @@ struct NttPlan {
   int fid = -1;
   unsigned logn = 0;
   bool inverse = false;
-  bool large = false;                  // tile geometry the level split and the tables were built for (large_geo)
+  bool large = false;                  // the level split the tables were built for (NttSchedule::large)
   uint64_t root[4] = {0, 0, 0, 0};     // forward root as passed by the caller
   uint64_t scale[4] = {0, 0, 0, 0};    // extra plain scale folded into the tables (1 if none)
-  LevelInfo li{};
   u32* tw_tile[4] = {nullptr, nullptr, nullptr, nullptr};
   u32* tw_inter[3] = {nullptr, nullptr, nullptr};
   u32* tw_shoup[4] = {nullptr, nullptr, nullptr, nullptr};   // Fr: per level, the in-tile twiddles again as (plain w, floor(w 2^261 / p)) limb entries
@@ -882,21 +855,6 @@ void ntt_release_plans() {
     if (ce.ready) (void)hipEventDestroy(ce.ready);
     memset(&ce, 0, sizeof ce);
   }
-}
-
-static LevelInfo choose_levels(unsigned logn, bool large) {
-  LevelInfo li{};
-  if (logn <= TILE_LOG) {
-    li.nlev = 1;
-    li.lg[0] = (int)logn;
-    return li;
-  }
-  const int maxlv = large ? GeoL::MAXLV : MAX_LEVEL_LOG;
-  int k = (int)((logn + maxlv - 1) / maxlv);
-  li.nlev = k;
-  int base = (int)logn / k, extra = (int)logn % k;
-  for (int i = 0; i < k; i++) li.lg[i] = base + (i < extra ? 1 : 0);
-  return li;
 }
 
 static void to_words(const uint64_t* limbs, int nl, Words8* w) {
@@ -953,7 +911,7 @@ static int build_shoup_table(const HostField* hf, const uint64_t* root, uint64_t
 }
 
 template <class P>
-static int build_tables(NttPlan* pl, const uint64_t* eff_root, const uint64_t* fold_scale, hipStream_t s) {
+static int build_tables(NttPlan* pl, const NttLevels& li, const uint64_t* eff_root, const uint64_t* fold_scale, hipStream_t s) {
   const HostField* hf = host_field(pl->fid);
   Words8 rootw, scalew;
   to_words(eff_root, hf->nl, &rootw);
@@ -961,7 +919,6 @@ static int build_tables(NttPlan* pl, const uint64_t* eff_root, const uint64_t* f
   uint64_t one[4] = {1, 0, 0, 0};
   Words8 onew;
   to_words(one, hf->nl, &onew);
-  const LevelInfo& li = pl->li;
   const size_t esz = sizeof(u32) * P::NW;
   int lg_after = (int)pl->logn;  // log of (n_t * M_t) while walking levels
   for (int t = 0; t < li.nlev; t++) {
@@ -992,9 +949,11 @@ static int build_tables(NttPlan* pl, const uint64_t* eff_root, const uint64_t* f
   return MZK_OK;
 }
 
-static int get_plan(int fid, unsigned logn, bool inverse, const uint64_t* root, const uint64_t* extra_scale,
-                    hipStream_t s, NttPlan** out, size_t batch = 1) {
-  const bool large = large_geo(fid, logn, batch);
+// the cached tables of the transform that `sched` schedules
+static int get_plan(const NttSchedule& sched, bool inverse, const uint64_t* root, const uint64_t* extra_scale, hipStream_t s, NttPlan** out) {
+  const int fid = sched.fid;
+  const unsigned logn = sched.logn;
+  const bool large = sched.large;
   const HostField* hf = host_field(fid);
   uint64_t one[4] = {1, 0, 0, 0};
   const uint64_t* sc = extra_scale ? extra_scale : one;
@@ -1018,7 +977,6 @@ static int get_plan(int fid, unsigned logn, bool inverse, const uint64_t* root, 
   pl->fid = fid; pl->logn = logn; pl->inverse = inverse; pl->large = large;
   memcpy(pl->root, root, 8 * hf->nl);
   memcpy(pl->scale, sc, 8 * hf->nl);
-  pl->li = choose_levels(logn, large);
   pl->stamp = ++g_stamp;
   uint64_t eff_root[4] = {0, 0, 0, 0}, fold[4] = {0, 0, 0, 0};
   memcpy(fold, sc, 8 * hf->nl);
@@ -1031,7 +989,7 @@ static int get_plan(int fid, unsigned logn, bool inverse, const uint64_t* root, 
     memcpy(eff_root, root, 8 * hf->nl);
   }
   bool fold_is_one = h_is_one(hf, fold);
-  if (pl->li.nlev == 1 && !fold_is_one) {
+  if (sched.li.nlev == 1 && !fold_is_one) {
     // single pass: no inter-pass table to fold into -> explicit scale in the last pass (Montgomery form
     // computed on the host: fold * R mod p via mulmod with R mod p)
     uint64_t r_mod_p[4] = {0, 0, 0, 0};
@@ -1041,7 +999,7 @@ static int get_plan(int fid, unsigned logn, bool inverse, const uint64_t* root, 
     to_words(m, hf->nl, &pl->last_scale);
     pl->has_last_scale = 1;
   }
-  const int rc = with_field(fid, [&](auto tag) { return build_tables<typename decltype(tag)::P>(pl, eff_root, fold, s); });
+  const int rc = with_field(fid, [&](auto tag) { return build_tables<typename decltype(tag)::P>(pl, sched.li, eff_root, fold, s); });
   if (rc != MZK_OK) { free_plan(pl); return rc; }
   if (g_plans.size() >= MAX_PLANS) {
     size_t victim = 0;
@@ -1055,77 +1013,53 @@ static int get_plan(int fid, unsigned logn, bool inverse, const uint64_t* root, 
   return MZK_OK;
 }
 
-template <class P, class G>
-static int run_plan_geo(const NttPlan* pl, const u32* d_in, u32* d_out, hipStream_t s, const PreArgs* pre, size_t batch) {
-  const LevelInfo& li = pl->li;
-  const unsigned logn = pl->logn;
-
-  ProfScope whole(s, MZK_PH_NTT_TOTAL);
+// Walks the steps of `sc` (ntt_plan) over the tables of `pl` (get_plan of the same schedule).
+template <class P>
+static int run_plan(const NttPlan* pl, const NttSchedule& sc, const u32* d_in, u32* d_out, hipStream_t s, const PreArgs* pre = nullptr) {
+  if (sc.err != MZK_OK) { set_error("%s", sc.msg); return sc.err; }
   static const int fuse = tune_int("MZK_NTT_FUSE_EDGES", 1);     // 0: A/B (tools/timing/time_ntt.py)
   static const int shoup = tune_int("MZK_NTT_SHOUP", 1);
-  // write-through stores (stream_store16) for multi-pass transforms whose data is between 2^WT_LO and 2^WT_HI bytes; mask bit 0:
-  // the strided passes, bit 1: the last pass
-  // (same-box map, profiles/round5_ntt_write_through_ab.txt: Fr 2^17..2^19 -1..-13 %, M128 2^17..2^22 -2..-16 %; below 2 MiB and
-  // from 32 MiB (Fr) / 128 MiB (M128) up it gains nothing or costs 3-9 %: the working set no longer sits in the Infinity Cache)
-  static const int wt_lo = tune_int("MZK_NTT_WT_LO", 21), wt_hi = tune_int("MZK_NTT_WT_HI", P::NW == 4 ? 26 : 24), wt_mask = tune_int("MZK_NTT_WT_MASK", 3);
-  const size_t bytes = (batch << logn) * sizeof(u32) * P::NW;
-  const bool wt_on = li.nlev > 1 && bytes >= ((size_t)1 << wt_lo) && bytes <= ((size_t)1 << wt_hi);
-  const bool wt_s = wt_on && (wt_mask & 1), wt_l = wt_on && (wt_mask & 2);
-  if constexpr (G::TL != TILE_LOG) {        // tiles above 64 KiB of LDS need the attribute, once per context and instantiation
-    bool& done = ctx().attr_done[P::NW == 4 ? (G::TWG ? ATTR_NTT_LARGE_M128_2WG : ATTR_NTT_LARGE_M128) : ATTR_NTT_LARGE_FR];
-    if (!done) {
-      const void* fns[] = {(const void*)k_ntt_strided<P, true, G, false>, (const void*)k_ntt_strided<P, false, G, false>, (const void*)k_ntt_last<P, G, false>,
-                           (const void*)k_ntt_strided<P, true, G, true>,  (const void*)k_ntt_strided<P, false, G, true>,  (const void*)k_ntt_last<P, G, true>};
-      for (const void* f : fns) MZK_HIP(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-      done = true;
+  auto walk = [&](auto geo) -> int {
+    typedef decltype(geo) G;
+    ProfScope whole(s, MZK_PH_NTT_TOTAL);
+    if constexpr (G::TL != TILE_LOG) {        // the geometries above 64 KiB of LDS: the attribute, once per context and instantiation
+      bool& done = ctx().attr_done[P::NW == 4 ? (G::TWG ? ATTR_NTT_LARGE_M128_2WG : ATTR_NTT_LARGE_M128) : ATTR_NTT_LARGE_FR];
+      if (sc.lds_attr && !done) {
+        const void* fns[] = {(const void*)k_ntt_strided<P, true, G, false>, (const void*)k_ntt_strided<P, false, G, false>, (const void*)k_ntt_last<P, G, false>,
+                             (const void*)k_ntt_strided<P, true, G, true>,  (const void*)k_ntt_strided<P, false, G, true>,  (const void*)k_ntt_last<P, G, true>};
+        for (const void* f : fns) MZK_HIP(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)NTT_LDS_MAX));
+        done = true;
+      }
     }
-  }
-  const u32* src = d_in;
-  u32* tmp = nullptr;
-  if (li.nlev > 1) MZK_TRY(ws_get(WS_NTT_TMP, (batch << logn) * sizeof(u32) * P::NW, (void**)&tmp));
-  int lg_after = (int)logn;
-  if constexpr (G::MAXLV < G::TL || G::TL != TILE_LOG)      // (GeoS1 serves single-pass plans only: no strided kernels of its own)
-  for (int t = 0; t < li.nlev - 1; t++) {
-    const int lgn = li.lg[t], lgM = lg_after - lgn;
-    const int lgc = G::TL - lgn;
-    const unsigned blocks = (unsigned)(batch << (logn - G::TL));      // `o` in the kernel runs over the batch too
-    {
+    const u32* src = d_in;
+    u32* tmp = nullptr;
+    if (sc.tmp_bytes) MZK_TRY(ws_get(WS_NTT_TMP, sc.tmp_bytes, (void**)&tmp));
+    for (int t = 0; t < sc.nsteps; t++) {
+      const NttStep& st = sc.steps[t];
       ProfScope ps(s, MZK_PH_NTT_PASS0 + t);
-      const bool with_pre = t == 0 && pre;
-      auto* k = with_pre ? (wt_s ? k_ntt_strided<P, true, G, true> : k_ntt_strided<P, true, G, false>)
-                         : (wt_s ? k_ntt_strided<P, false, G, true> : k_ntt_strided<P, false, G, false>);
-      hipLaunchKernelGGL(k, dim3(blocks), dim3(G::NT), G::template lds_bytes<P>(lgn), s, src, tmp, pl->tw_tile[t], pl->tw_inter[t], lgn, lgM, lgc,
-                         with_pre ? *pre : PreArgs{nullptr, 0, nullptr, nullptr}, fuse, shoup ? pl->tw_shoup[t] : nullptr);
+      if (st.kind == NTT_STEP_STRIDED) {
+        if constexpr (G::MAXLV < G::TL || G::TL != TILE_LOG) {      // (GeoS1 serves single-pass plans only: no strided kernels of its own)
+          const bool with_pre = t == 0 && pre;
+          auto* k = with_pre ? (st.wt ? k_ntt_strided<P, true, G, true> : k_ntt_strided<P, true, G, false>)
+                             : (st.wt ? k_ntt_strided<P, false, G, true> : k_ntt_strided<P, false, G, false>);
+          hipLaunchKernelGGL(k, dim3(st.grid), dim3(st.block), st.lds, s, src, tmp, pl->tw_tile[t], pl->tw_inter[t], st.lgn, st.lgM, st.lgc,
+                             with_pre ? *pre : PreArgs{nullptr, 0, nullptr, nullptr}, fuse, shoup ? pl->tw_shoup[t] : nullptr);
+          src = tmp;
+        }
+      } else {
+        hipLaunchKernelGGL((st.wt ? k_ntt_last<P, G, true> : k_ntt_last<P, G, false>), dim3(st.grid), dim3(st.block), st.lds, s, src, d_out, pl->tw_tile[t], sc.li,
+                           st.lgn, st.lgr, st.lg_rows, pl->last_scale, pl->has_last_scale, st.total_rows, fuse, shoup ? pl->tw_shoup[t] : nullptr);
+      }
     }
-    src = tmp;
-    lg_after = lgM;
+    MZK_HIP(hipGetLastError());
+    return MZK_OK;
+  };
+  switch (sc.geo) {
+    case NTT_GEO_M: return walk(typename LargeGeo<P>::type());
+    case NTT_GEO_L: return walk(GeoL());
+    case NTT_GEO_S1: return walk(GeoS1());
+    default: return walk(GeoS());
   }
-  {
-    const int lgn = li.lg[li.nlev - 1];
-    const int lg_rows = (int)logn - lgn;
-    const size_t total_rows = batch << lg_rows;
-    int lgr = G::TL - lgn;
-    while (lgr > 0 && ((size_t)1 << lgr) > total_rows) lgr--;
-    const unsigned blocks = (unsigned)((total_rows + ((size_t)1 << lgr) - 1) >> lgr);
-    ProfScope ps(s, MZK_PH_NTT_PASS0 + li.nlev - 1);
-    hipLaunchKernelGGL((wt_l ? k_ntt_last<P, G, true> : k_ntt_last<P, G, false>), dim3(blocks), dim3(G::NT), G::template lds_bytes<P>(lgn), s, src, d_out,
-                       pl->tw_tile[li.nlev - 1], li, lgn, lgr, lg_rows, pl->last_scale, pl->has_last_scale, total_rows, fuse,
-                       shoup ? pl->tw_shoup[li.nlev - 1] : nullptr);
-  }
-  MZK_HIP(hipGetLastError());
-  return MZK_OK;
-}
-template <class P>
-static int run_plan(const NttPlan* pl, const u32* d_in, u32* d_out, hipStream_t s, const PreArgs* pre = nullptr, size_t batch = 1) {
-  // M128 large tiles: two 512-lane workgroups per CU (GeoM) once there are at least two tiles per CU -- 2^25 and up: 1.69 instead of
-  // 1.83 - 1.85 ms at 2^25 (same box A/B, profiles/round4_ntt_m128_two_workgroups_ab.txt).  A 2^20 transform is exactly 256 tiles, ONE per CU whatever the
-  // workgroup size, and the 512-lane form only halves the lanes working on it (0.057 against 0.047 ms): it keeps round 3's
-  // single 1024-lane workgroup.  Tuning build: MZK_NTT_M128_TWO_WG = smallest log2 size on GeoM (99 = never).
-  static const int two_wg_from = tune_int("MZK_NTT_M128_TWO_WG", 21);
-  if (pl->large && P::NW == 4 && (int)pl->logn >= two_wg_from) return run_plan_geo<P, typename LargeGeo<P>::type>(pl, d_in, d_out, s, pre, batch);
-  if (pl->large) return run_plan_geo<P, GeoL>(pl, d_in, d_out, s, pre, batch);
-  if (pl->li.nlev == 1 && pl->li.lg[0] > GeoS::MAXLV) return run_plan_geo<P, GeoS1>(pl, d_in, d_out, s, pre, batch);
-  return run_plan_geo<P, GeoS>(pl, d_in, d_out, s, pre, batch);
 }
 
 static bool is_pow2(size_t n) { return n && !(n & (n - 1)); }
@@ -1149,8 +1083,9 @@ int ntt_dev_impl(int fid, const uint64_t* root_host, const void* d_in, void* d_o
   if (!h_is_canonical(hf, root_host)) { set_error("ntt: root not canonical"); return MZK_E_RANGE; }
   if (ilog2(n) > 32) { set_error("ntt: n too large"); return MZK_E_ARG; }
   NttPlan* pl = nullptr;
-  MZK_TRY(get_plan(fid, ilog2(n), inverse != 0, root_host, extra_scale_host, s, &pl));
-  return with_field(fid, [&](auto tag) { return run_plan<typename decltype(tag)::P>(pl, (const u32*)d_in, (u32*)d_out, s); });
+  const NttSchedule sc = ntt_plan(fid, ilog2(n), 1, ntt_knobs());
+  MZK_TRY(get_plan(sc, inverse != 0, root_host, extra_scale_host, s, &pl));
+  return with_field(fid, [&](auto tag) { return run_plan<typename decltype(tag)::P>(pl, sc, (const u32*)d_in, (u32*)d_out, s); });
 }
 
 // `batch` transforms of n points each, stored back to back (in place allowed); same root for all
@@ -1168,8 +1103,9 @@ int ntt_batch_dev_impl(int fid, const uint64_t* root_host, const void* d_in, voi
     return MZK_OK;
   }
   NttPlan* pl = nullptr;
-  MZK_TRY(get_plan(fid, ilog2(n), inverse != 0, root_host, nullptr, s, &pl, batch));
-  return with_field(fid, [&](auto tag) { return run_plan<typename decltype(tag)::P>(pl, (const u32*)d_in, (u32*)d_out, s, nullptr, batch); });
+  const NttSchedule sc = ntt_plan(fid, ilog2(n), batch, ntt_knobs());
+  MZK_TRY(get_plan(sc, inverse != 0, root_host, nullptr, s, &pl));
+  return with_field(fid, [&](auto tag) { return run_plan<typename decltype(tag)::P>(pl, sc, (const u32*)d_in, (u32*)d_out, s); });
 }
 
 template <class P, int LGW>
@@ -1199,7 +1135,7 @@ int ntt_columns_dev_impl(int fid, const uint64_t* root_host, const void* d_in, v
   if (d_in == d_out) { set_error("ntt_columns: in place is not supported"); return MZK_E_ARG; }
   if (!h_is_canonical(host_field(fid), root_host)) { set_error("ntt: root not canonical"); return MZK_E_RANGE; }
   NttPlan* pl = nullptr;
-  MZK_TRY(get_plan(fid, ilog2(n_points), inverse != 0, root_host, nullptr, s, &pl));
+  MZK_TRY(get_plan(ntt_plan(fid, ilog2(n_points), 1, ntt_knobs()), inverse != 0, root_host, nullptr, s, &pl));
   return with_field(fid, [&](auto tag) { return columns_dispatch<typename decltype(tag)::P>(pl, ilog2(n_points), d_in, d_out, cols, s); });
 }
 
@@ -1244,12 +1180,13 @@ int coset_lde_dev_impl(int fid, const void* d_coef, size_t n_coef, const uint64_
   to_words(offset_host, hf->nl, &offw);
   const unsigned logn = ilog2(order);
   if (logn > 32 || batch > ((size_t)1 << 40) / order) { set_error("coset_lde: order * batch too large"); return MZK_E_ARG; }
-  if (order > 1 && choose_levels(logn, large_geo(fid, logn, batch)).nlev > 1) {
+  const NttSchedule sc = ntt_plan(fid, logn, batch, ntt_knobs());
+  if (order > 1 && sc.li.nlev > 1) {
     // multi-pass transform: Polynomial::scale + padding fused into the first pass (PreArgs)
     if (!h_is_canonical(hf, generator_host)) { set_error("coset_lde: parameter not canonical"); return MZK_E_RANGE; }
     NttPlan* pl = nullptr;
-    MZK_TRY(get_plan(fid, logn, false, generator_host, nullptr, s, &pl, batch));
-    const int lgn0 = pl->li.lg[0], lgM0 = (int)logn - lgn0;
+    MZK_TRY(get_plan(sc, false, generator_host, nullptr, s, &pl));
+    const int lgn0 = sc.li.lg[0], lgM0 = (int)logn - lgn0;
     const size_t nrow = (size_t)1 << lgn0, ncol = (size_t)1 << lgM0;
     // offset^(j M) and offset^col tables: like the plan's twiddles they depend only on (field, offset, size) -- a STARK
     // prover evaluates every polynomial on ONE coset -- so the last pair per field is kept (workspace generation and
@@ -1277,7 +1214,7 @@ int coset_lde_dev_impl(int fid, const void* d_coef, size_t n_coef, const uint64_
       MZK_HIP(hipStreamWaitEvent(s, ce.ready, 0));
     }
     const PreArgs pre{(const u32*)d_coef, n_coef, pre_row, pre_col};
-    return with_field(fid, [&](auto tag) { return run_plan<typename decltype(tag)::P>(pl, (const u32*)d_coef, (u32*)d_out, s, &pre, batch); });
+    return with_field(fid, [&](auto tag) { return run_plan<typename decltype(tag)::P>(pl, sc, (const u32*)d_coef, (u32*)d_out, s, &pre); });
   }
   void* scaled = nullptr;
   MZK_TRY(ws_get(WS_NTT_IO_A, batch * order * field_bytes(fid), &scaled));

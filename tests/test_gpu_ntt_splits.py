@@ -7,7 +7,7 @@ the in-place device call.
 
 2^20 runs on the large tiles as a single transform and on (7,7,6) as a batch of three.  The write-through stores are on for
 Fr 2^16 .. 2^21 and M128 2^17 .. 2^20 and off on both sides.  test_pass_counts reads the launch counts of the library's own phase
-timers, so a change of large_geo or choose_levels that moves a size to another pass count fails here instead of leaving a split
+timers, so a change of ntt_plan (mzk_ntt_plan.h) that moves a size to another pass count fails here instead of leaving a split
 untested.  test_gpu_ntt.py covers 2^0 .. 2^14, test_gpu_full_size.py 2^24."""
 import ctypes
 import numpy as np
