@@ -19,7 +19,7 @@
  *     records its own), so results are correct on any stream; work on one context never overlaps.  Calls must
  *     still come from one host thread at a time: a call that arrives while another thread is inside the library returns
  *     MZK_E_BUSY without touching any state (calls nested on ONE thread -- the challenge callback of mzk_fri_commit calling back
- *     in -- are fine).
+ *     in -- are fine; a nested call that needs scratch the running call holds is refused with MZK_E_ARG).
  */
 #ifndef MZK_H
 #define MZK_H

@@ -26,8 +26,6 @@ int hip_fail(hipError_t e, const char* what, const char* file, int line) {
 static std::atomic<uint64_t> g_owner{0};
 static thread_local int t_depth = 0;
 static thread_local char t_marker;            // its address is this thread's id
-static uint64_t g_call_epoch = 1;              // one per outermost API call: which workspace slots the running call has asked for
-static size_t g_ws_budget = 0;                 // mzk_set_workspace_budget: bytes of workspace a context may keep (0 = no limit)
 EntryGuard::EntryGuard() : ok(true), nested(false) {
   if (t_depth > 0) { t_depth++; nested = true; return; }
   uint64_t expected = 0;
@@ -37,7 +35,7 @@ EntryGuard::EntryGuard() : ok(true), nested(false) {
     return;
   }
   t_depth = 1;
-  g_call_epoch++;
+  g_ws_epoch++;
 }
 EntryGuard::~EntryGuard() {
   if (!ok) return;
@@ -49,7 +47,6 @@ static int g_nctx = 0, g_cur = 0;
 static int g_last_ordinal = 0;                   // what ensure_init() re-initialises on after a shutdown
 static signed char g_peer[MZK_MAX_CTX][MZK_MAX_CTX];
 int ctx_peer_enabled(int a, int b) { return (a >= 0 && b >= 0 && a < g_nctx && b < g_nctx) ? g_peer[a][b] : 0; }
-static uint64_t g_gen_counter = 1;
 Context& ctx() { return g_ctxs[g_cur]; }
 int ctx_count() { return g_nctx; }
 // What mzk_init's unguarded fast path may look at, and nothing else: the ordinal context 0 drives WHILE it is ready and current, -1
@@ -77,72 +74,20 @@ CtxScope::~CtxScope() {
   if (prev_dev >= 0) (void)hipSetDevice(prev_dev);
 }
 
-// Workspace memory gives itself back (round 5).  The slots only ever grew, so a 2^27-pair MSM left gigabytes in them for good, a
-// later call could fail in here with a bare HIP error, and a new SRS handle degraded its tables although idle scratch was in the
-// way -- where commit_kzg(&poly, &pk) cannot fail for memory at all (kzg.rs:57-59).  Now: a slot remembers the outermost call
-// that last asked for it; when an allocation would exceed the caller's budget (mzk_set_workspace_budget) or the device refuses
-// it, every slot the RUNNING call has not asked for is freed and the allocation tried again; what is still refused is
-// MZK_E_NOMEM, not MZK_E_HIP.  mzk_trim_workspace() does the same on request, for every context, cached transform plans included.
-size_t ws_bytes_held() {
-  size_t t = poly_bytes_held();        // the polynomial routines' pool and cached plans count as workspace
-  for (const auto& b : ctx().ws) t += b.cap;
-  return t;
-}
-size_t ws_trim_idle() {
-  Context& c = ctx();
-  const size_t poly_idle = poly_trim_idle();
-  size_t idle = 0;
-  for (const auto& b : c.ws) if (b.p && b.epoch != g_call_epoch) idle += b.cap;
-  if (!idle) return poly_idle;
-  (void)hipDeviceSynchronize();
-  bool table_slot_freed = false;
-  for (int k = 0; k < WS_COUNT; k++) {
-    WsBuf& b = c.ws[k];
-    if (b.p && b.epoch != g_call_epoch) {
-      (void)hipFree(b.p);
-      b.p = nullptr; b.cap = 0;
-      table_slot_freed = table_slot_freed || k == WS_FB_TABLE16 || k == WS_FB_TABLE8 || k == WS_NTT_PRE || k == WS_NTT_PRE_M128;
-    }
-  }
-  // device tables cached inside slots (fixed-base tables of g, offset powers) are gone with THEIR slots only: a trim in the middle of a
-  // call that holds them leaves the caches valid (a budgeted loop that alternates call kinds rebuilt them on every call otherwise)
-  if (table_slot_freed) c.ws_gen = ++g_gen_counter;
-  return idle + poly_idle;
-}
-int dev_alloc(void** out, size_t bytes, const char* what) {
-  *out = nullptr;
-  hipError_t e = hipMalloc(out, bytes);
-  if (e == hipErrorOutOfMemory || e == hipErrorMemoryAllocation) {
-    (void)hipGetLastError();
-    if (ws_trim_idle()) e = hipMalloc(out, bytes);
-  }
+// The workspace's bookkeeping is mzk_ws.h; here it meets the device.  A refused hipMalloc is MZK_E_NOMEM (dev_alloc trims the idle
+// slots and tries once more before it says so), not MZK_E_HIP.
+int ws_hook_alloc(void** out, size_t bytes, const char* what) {
+  const hipError_t e = hipMalloc(out, bytes);
   if (e == hipSuccess) return MZK_OK;
   (void)hipGetLastError();
   *out = nullptr;
-  if (e == hipErrorOutOfMemory || e == hipErrorMemoryAllocation) {
-    set_error("%s: the device has no %zu bytes left (idle workspace already released)", what, bytes);
-    return MZK_E_NOMEM;
-  }
+  if (e == hipErrorOutOfMemory || e == hipErrorMemoryAllocation) return MZK_E_NOMEM;
   return hip_fail(e, what, __FILE__, __LINE__);
 }
-int ws_get(WsSlot slot, size_t bytes, void** out) {
-  WsBuf& b = ctx().ws[slot];
-  b.epoch = g_call_epoch;
-  if (bytes > b.cap) {
-    if (b.p) {
-      MZK_HIP(hipDeviceSynchronize());
-      MZK_HIP(hipFree(b.p));
-      b.p = nullptr; b.cap = 0;
-    }
-    size_t cap = bytes < 4096 ? 4096 : bytes;
-    if (g_ws_budget && ws_bytes_held() + cap > g_ws_budget) (void)ws_trim_idle();
-    MZK_TRY(dev_alloc(&b.p, cap, "workspace"));
-    b.cap = cap;
-  }
-  *out = b.p;
-  return MZK_OK;
-}
-uint64_t ws_generation() { return ctx().ws_gen; }
+int ws_hook_free(void* p) { MZK_HIP(hipFree(p)); return MZK_OK; }
+int ws_hook_sync() { MZK_HIP(hipDeviceSynchronize()); return MZK_OK; }
+WsTable* ws_table_of(int ctx_index) { return &g_ctxs[ctx_index].ws; }
+int ws_current_ctx() { return g_cur; }
 int d2h_sync(void* host, const void* dev, size_t bytes, hipStream_t s) {
   if (bytes == 0 || bytes > SMALL_D2H_MAX) {
     if (bytes) MZK_HIP(hipMemcpyAsync(host, dev, bytes, hipMemcpyDeviceToHost, s));
@@ -155,14 +100,6 @@ int d2h_sync(void* host, const void* dev, size_t bytes, hipStream_t s) {
   MZK_HIP(hipStreamSynchronize(s));
   memcpy(host, c.bounce, bytes);
   return MZK_OK;
-}
-void ws_release_all() {
-  Context& c = ctx();
-  c.ws_gen = ++g_gen_counter;
-  for (auto& b : c.ws) {
-    if (b.p) (void)hipFree(b.p);
-    b.p = nullptr; b.cap = 0;
-  }
 }
 // The workspace slots are shared by every entry point of a context.  *_dev calls only enqueue work, so a call on
 // stream B could overwrite slots that kernels of an earlier call on stream A are still reading: the guard orders B
@@ -428,7 +365,7 @@ int mzk_init_devices(const int* device_ordinals, int n_devices) {
     c.index = i;
     c.device = device_ordinals[i];
     c.num_cu = ncu[i];
-    c.ws_gen = ++g_gen_counter;
+    ws_new_generation(c.ws);
     MZK_HIP(hipSetDevice(c.device));
     // Contexts that share a GPU are there to keep several calls in flight: give each its own stream PRIORITY level, which
     // also puts them on different hardware queues (streams of one priority may share a queue and then serialise).
@@ -600,12 +537,12 @@ int mzk_root_of_unity(int field_id, unsigned log2_n, uint64_t* out) {
 }
 
 // ---- host-buffer NTT family ---------------------------------------------------------------------------
-// host buffer -> workspace slot.  A plain hipMemcpyAsync from pageable memory: on this runtime (ROCm 7.2) it already moves 56 GB/s
+// host buffer -> workspace slot, leased from the caller's frame (the caller uses the pointer).  A plain hipMemcpyAsync from pageable memory: on this runtime (ROCm 7.2) it already moves 56 GB/s
 // in either direction, the same as a DMA from pinned memory (tools/timing/pcie_probe.py, profiles/r03h_pcie_probe.txt); a pinned
 // staging ring with copy threads was built in round 3 and measured SLOWER (generic MSM 4.5 vs 3.7 ms, NTT 4.8 vs 3.6 ms), so
 // what the host-buffer entry points can gain is overlap, not a faster copy (see mzk_msm_g1_bn254).
-static int stage_in(WsSlot slot, const void* host, size_t bytes, void** dev, hipStream_t s) {
-  MZK_TRY(ws_get(slot, bytes ? bytes : 16, dev));
+static int stage_in(WsFrame& ws, WsSlot slot, const void* host, size_t bytes, void** dev, hipStream_t s) {
+  MZK_TRY(ws.get(slot, bytes ? bytes : 16, dev));
   if (bytes) MZK_HIP(hipMemcpyAsync(*dev, host, bytes, hipMemcpyHostToDevice, s));
   return MZK_OK;
 }
@@ -689,6 +626,7 @@ static int msm_host_chunked(const uint64_t* scalars, const uint64_t* points, voi
 
 int mzk_ntt(int field_id, const uint64_t* root, const uint64_t* in, uint64_t* out, size_t n, int inverse) {
   MZK_ENTER();
+  WsFrame ws("mzk_ntt");
   MZK_TRY(field_check_gl(field_id, "ntt"));
   if (n == 0) return MZK_OK;
   if (!in || !out) { set_error("ntt: null pointer"); return MZK_E_ARG; }
@@ -696,8 +634,8 @@ int mzk_ntt(int field_id, const uint64_t* root, const uint64_t* in, uint64_t* ou
   WsGuard wsg(s);
   const size_t bytes = n * field_bytes(field_id);
   void *d_in, *d_out;
-  MZK_TRY(stage_in(WS_NTT_IO_A, in, bytes, &d_in, s));
-  MZK_TRY(ws_get(WS_NTT_IO_B, bytes, &d_out));
+  MZK_TRY(stage_in(ws, WS_NTT_IO_A, in, bytes, &d_in, s));
+  MZK_TRY(ws.get(WS_NTT_IO_B, bytes, &d_out));
   MZK_TRY(ntt_dev_impl(field_id, root, d_in, d_out, n, inverse, nullptr, s));
   MZK_TRY(stage_out(out, d_out, bytes, s));
   return MZK_OK;
@@ -718,6 +656,7 @@ int mzk_coset_lde_batch_dev(int field_id, const void* d_coefs, size_t n_coef, co
 int mzk_coset_lde_batch(int field_id, const uint64_t* coefs, size_t n_coef, const uint64_t* offset, const uint64_t* generator,
                         uint64_t* out, size_t order, size_t batch) {
   MZK_ENTER();
+  WsFrame ws("mzk_coset_lde_batch");
   MZK_TRY(field_check_gl(field_id, "coset_lde"));
   if (n_coef > order) { set_error("attempt to subtract with overflow (order - polynomial.coef.len())"); return MZK_E_LENGTH; }
   if (order == 0 || batch == 0) return MZK_OK;
@@ -726,8 +665,8 @@ int mzk_coset_lde_batch(int field_id, const uint64_t* coefs, size_t n_coef, cons
   WsGuard wsg(s);
   const size_t esz = field_bytes(field_id);
   void *d_coef, *d_out;
-  MZK_TRY(stage_in(WS_MISC_A, coefs, batch * n_coef * esz, &d_coef, s));
-  MZK_TRY(ws_get(WS_NTT_IO_B, batch * order * esz, &d_out));
+  MZK_TRY(stage_in(ws, WS_MISC_A, coefs, batch * n_coef * esz, &d_coef, s));
+  MZK_TRY(ws.get(WS_NTT_IO_B, batch * order * esz, &d_out));
   MZK_TRY(coset_lde_dev_impl(field_id, d_coef, n_coef, offset, generator, d_out, order, s, batch));
   MZK_TRY(stage_out(out, d_out, batch * order * esz, s));
   return MZK_OK;
@@ -739,6 +678,7 @@ int mzk_ntt_batch_dev(int field_id, const uint64_t* root_host, const void* d_in,
 }
 int mzk_ntt_batch(int field_id, const uint64_t* root, const uint64_t* in, uint64_t* out, size_t n, size_t batch, int inverse) {
   MZK_ENTER();
+  WsFrame ws("mzk_ntt_batch");
   MZK_TRY(field_check_gl(field_id, "ntt"));
   if (n == 0 || batch == 0) return MZK_OK;
   if (!in || !out) { set_error("ntt: null pointer"); return MZK_E_ARG; }
@@ -746,7 +686,7 @@ int mzk_ntt_batch(int field_id, const uint64_t* root, const uint64_t* in, uint64
   WsGuard wsg(s);
   const size_t bytes = batch * n * field_bytes(field_id);
   void* d;
-  MZK_TRY(stage_in(WS_NTT_IO_A, in, bytes, &d, s));
+  MZK_TRY(stage_in(ws, WS_NTT_IO_A, in, bytes, &d, s));
   MZK_TRY(ntt_batch_dev_impl(field_id, root, d, d, n, batch, inverse, s));
   MZK_TRY(stage_out(out, d, bytes, s));
   return MZK_OK;
@@ -755,6 +695,7 @@ int mzk_ntt_batch(int field_id, const uint64_t* root, const uint64_t* in, uint64
 int mzk_coset_lde(int field_id, const uint64_t* coef, size_t n_coef, const uint64_t* offset, const uint64_t* generator,
                   uint64_t* out, size_t order) {
   MZK_ENTER();
+  WsFrame ws("mzk_coset_lde");
   MZK_TRY(field_check_gl(field_id, "coset_lde"));
   if (n_coef > order) { set_error("attempt to subtract with overflow (order - polynomial.coef.len())"); return MZK_E_LENGTH; }
   if (order == 0) return MZK_OK;
@@ -763,8 +704,8 @@ int mzk_coset_lde(int field_id, const uint64_t* coef, size_t n_coef, const uint6
   WsGuard wsg(s);
   const size_t esz = field_bytes(field_id);
   void *d_coef, *d_out;
-  MZK_TRY(stage_in(WS_MISC_A, coef, n_coef * esz, &d_coef, s));
-  MZK_TRY(ws_get(WS_NTT_IO_B, order * esz, &d_out));
+  MZK_TRY(stage_in(ws, WS_MISC_A, coef, n_coef * esz, &d_coef, s));
+  MZK_TRY(ws.get(WS_NTT_IO_B, order * esz, &d_out));
   MZK_TRY(coset_lde_dev_impl(field_id, d_coef, n_coef, offset, generator, d_out, order, s));
   MZK_TRY(stage_out(out, d_out, order * esz, s));
   return MZK_OK;
@@ -783,6 +724,7 @@ int mzk_ntt_columns_dev(int field_id, const uint64_t* root, const void* d_in, vo
 }
 int mzk_poly_scale(int field_id, const uint64_t* coef, size_t n, const uint64_t* ratio, const uint64_t* lead, uint64_t* out) {
   MZK_ENTER();
+  WsFrame ws("mzk_poly_scale");
   if (n == 0) return MZK_OK;
   if (!coef || !out) { set_error("poly_scale: null pointer"); return MZK_E_ARG; }
   MZK_TRY(field_check(field_id, "poly_scale"));
@@ -790,7 +732,7 @@ int mzk_poly_scale(int field_id, const uint64_t* coef, size_t n, const uint64_t*
   WsGuard wsg(s);
   const size_t esz = field_bytes(field_id);
   void* d;
-  MZK_TRY(stage_in(WS_MISC_A, coef, n * esz, &d, s));
+  MZK_TRY(stage_in(ws, WS_MISC_A, coef, n * esz, &d, s));
   MZK_TRY(poly_scale_dev_impl(field_id, d, n, ratio, lead, d, s));
   MZK_TRY(stage_out(out, d, n * esz, s));
   return MZK_OK;
@@ -810,14 +752,15 @@ static size_t trimmed_len(const uint64_t* c, size_t n, int nl) {
   return n;
 }
 
-// zero-pad two host polynomials to `order` on the device, forward-transform both, Hadamard, inverse.
-static int conv_on_device(int fid, const uint64_t* a, size_t la, const uint64_t* b, size_t lb, const uint64_t* root,
+// zero-pad two host polynomials to `order` on the device, forward-transform both, Hadamard, inverse.  The result stays in the
+// caller's lease (WS_MISC_C of its frame).
+static int conv_on_device(WsFrame& ws, int fid, const uint64_t* a, size_t la, const uint64_t* b, size_t lb, const uint64_t* root,
                           size_t order, void** d_result, hipStream_t s) {
   const size_t esz = field_bytes(fid);
   void *da, *db, *dc;
-  MZK_TRY(ws_get(WS_MISC_A, order * esz, &da));
-  MZK_TRY(ws_get(WS_MISC_B, order * esz, &db));
-  MZK_TRY(ws_get(WS_MISC_C, order * esz, &dc));
+  MZK_TRY(ws.get(WS_MISC_A, order * esz, &da));
+  MZK_TRY(ws.get(WS_MISC_B, order * esz, &db));
+  MZK_TRY(ws.get(WS_MISC_C, order * esz, &dc));
   MZK_HIP(hipMemsetAsync(da, 0, order * esz, s));
   MZK_HIP(hipMemsetAsync(db, 0, order * esz, s));
   if (la) MZK_HIP(hipMemcpyAsync(da, a, la * esz, hipMemcpyHostToDevice, s));
@@ -833,6 +776,7 @@ static int conv_on_device(int fid, const uint64_t* a, size_t la, const uint64_t*
 int mzk_fft_multiply(int field_id, const uint64_t* a, size_t la, const uint64_t* b, size_t lb, const uint64_t* omega,
                      uint64_t* out, size_t* out_len) {
   MZK_ENTER();
+  WsFrame ws("mzk_fft_multiply");
   MZK_TRY(field_check(field_id, "fft_multiply"));
   if (!out_len || (!a && la) || (!b && lb)) { set_error("fft_multiply: null pointer"); return MZK_E_ARG; }
   if (la + lb == 0) { set_error("attempt to subtract with overflow (self.coef.len() + other.coef.len() - 1)"); return MZK_E_LENGTH; }
@@ -849,16 +793,16 @@ int mzk_fft_multiply(int field_id, const uint64_t* a, size_t la, const uint64_t*
   if (n == 1) {
     // 1x1 product: the reference's fft() of length 1 is the identity; c[0] = a[0] * b[0] * 1^-1
     void *da, *db, *dc;
-    MZK_TRY(stage_in(WS_MISC_A, a, la * esz, &da, s));
-    MZK_TRY(stage_in(WS_MISC_B, b, lb * esz, &db, s));
-    MZK_TRY(ws_get(WS_MISC_C, esz, &dc));
+    MZK_TRY(stage_in(ws, WS_MISC_A, a, la * esz, &da, s));
+    MZK_TRY(stage_in(ws, WS_MISC_B, b, lb * esz, &db, s));
+    MZK_TRY(ws.get(WS_MISC_C, esz, &dc));
     if (la == 0 || lb == 0) { *out_len = 0; return MZK_OK; }
     MZK_TRY(pointwise_mul_dev(field_id, da, db, dc, 1, s));
     MZK_TRY(d2h_sync(res.data(), dc, esz, s));
   } else {
     if (!omega) { set_error("fft_multiply: null omega"); return MZK_E_ARG; }
     void* dc;
-    MZK_TRY(conv_on_device(field_id, a, la, b, lb, omega, n, &dc, s));
+    MZK_TRY(conv_on_device(ws, field_id, a, la, b, lb, omega, n, &dc, s));
     MZK_TRY(d2h_sync(res.data(), dc, n * esz, s));
   }
   size_t lo = trimmed_len(res.data(), m, nl);  // truncate(m) then trim_trailing_zeros, polynomial.rs:271-275
@@ -870,6 +814,7 @@ int mzk_fft_multiply(int field_id, const uint64_t* a, size_t la, const uint64_t*
 int mzk_fast_multiply(int field_id, const uint64_t* a, size_t la, const uint64_t* b, size_t lb, const uint64_t* root,
                       size_t root_order, uint64_t* out, size_t* out_len) {
   MZK_ENTER();
+  WsFrame ws("mzk_fast_multiply");
   MZK_TRY(field_check(field_id, "fast_multiply"));
   if (!out_len || !root || (!a && la) || (!b && lb)) { set_error("fast_multiply: null pointer"); return MZK_E_ARG; }
   const HostField* hf = host_field(field_id);
@@ -905,7 +850,7 @@ int mzk_fast_multiply(int field_id, const uint64_t* a, size_t la, const uint64_t
     trim = false;
   }
   void* dc;
-  MZK_TRY(conv_on_device(field_id, a, la, b, lb, r, order, &dc, s));
+  MZK_TRY(conv_on_device(ws, field_id, a, la, b, lb, r, order, &dc, s));
   std::vector<uint64_t> res(order * nl);
   MZK_TRY(d2h_sync(res.data(), dc, order * esz, s));
   size_t lo = trim ? trimmed_len(res.data(), da + db - 1, nl) : order;
@@ -949,6 +894,7 @@ static size_t small_poly_div(const HostField* hf, const uint64_t* lhs, size_t tl
 int mzk_fast_coset_divide(int field_id, const uint64_t* lhs, size_t ll, const uint64_t* rhs, size_t lr, const uint64_t* offset,
                           const uint64_t* root, size_t root_order, uint64_t* out, size_t* out_len) {
   MZK_ENTER();
+  WsFrame ws("mzk_fast_coset_divide");
   MZK_TRY(field_check(field_id, "fast_coset_divide"));
   if (!out || !out_len || !root || !offset || (!lhs && ll) || (!rhs && lr)) { set_error("fast_coset_divide: null pointer"); return MZK_E_ARG; }
   const HostField* hf = host_field(field_id);
@@ -981,9 +927,9 @@ int mzk_fast_coset_divide(int field_id, const uint64_t* lhs, size_t ll, const ui
   WsGuard wsg(s);
   const size_t esz = field_bytes(field_id);
   void *d_l, *d_r, *d_o;
-  MZK_TRY(stage_in(WS_MISC_C, lhs, tl * esz, &d_l, s));
-  MZK_TRY(stage_in(WS_MISC_D, rhs, tr * esz, &d_r, s));
-  MZK_TRY(ws_get(WS_NTT_IO_B, ql * esz, &d_o));
+  MZK_TRY(stage_in(ws, WS_MISC_C, lhs, tl * esz, &d_l, s));
+  MZK_TRY(stage_in(ws, WS_MISC_D, rhs, tr * esz, &d_r, s));
+  MZK_TRY(ws.get(WS_NTT_IO_B, ql * esz, &d_o));
   MZK_TRY(coset_divide_dev_impl(field_id, d_l, tl, d_r, tr, offset, r, order, d_o, s));
   MZK_TRY(stage_out(out, d_o, ql * esz, s));
   *out_len = ql;
@@ -1023,7 +969,10 @@ int mzk_fast_coset_divide_batch_dev(int field_id, const void* d_lhs, size_t lhs_
   const size_t esz = field_bytes(field_id);
   if (rhs_len == 0) { set_error("assertion failed: !rhs.is_zero()"); return MZK_E_ARG; }                    // ntt.rs:284: no launch for an empty denominator
   std::vector<size_t> tl(count + 1);
-  MZK_TRY(rows_trimmed_len_dev(field_id, const_cast<void*>(d_lhs), lhs_stride, lhs_lens, count, 0, d_rhs, rhs_len, WS_MISC_F, tl.data(), s));
+  {   // the lengths are on the host when this returns: the lease ends here, coset_divide_rows_dev_impl takes WS_MISC_F itself
+    WsFrame ws("mzk_fast_coset_divide_batch_dev (lengths)");
+    MZK_TRY(rows_trimmed_len_dev(field_id, const_cast<void*>(d_lhs), lhs_stride, lhs_lens, count, 0, d_rhs, rhs_len, ws, WS_MISC_F, tl.data(), s));
+  }
   const size_t tr = tl[count];
   if (tr == 0) { set_error("assertion failed: !rhs.is_zero()"); return MZK_E_ARG; }                           // ntt.rs:284
   struct Group { size_t order; uint64_t root[4]; std::vector<CdRow> rows; };
@@ -1096,6 +1045,7 @@ static int srs_check_ctx(const mzk_srs* srs) {
 
 int mzk_msm_g1_bn254(const uint64_t* scalars, const uint64_t* points_xy, size_t n, uint64_t out_xy[8]) {
   MZK_ENTER();
+  WsFrame ws("mzk_msm_g1_bn254");
   if (!out_xy || ((!scalars || !points_xy) && n)) { set_error("msm: null pointer"); return MZK_E_ARG; }
   hipStream_t s = ctx().stream;
   WsGuard wsg(s);
@@ -1106,14 +1056,14 @@ int mzk_msm_g1_bn254(const uint64_t* scalars, const uint64_t* points_xy, size_t 
   hipStream_t side;
   hipEvent_t fork, join;
   MZK_TRY(side_stream(&side, &fork, &join));
-  MZK_TRY(ws_get(WS_MISC_A, n ? n * 64 : 16, &d_p));
-  MZK_TRY(ws_get(WS_MISC_B, 256, &d_o));
+  MZK_TRY(ws.get(WS_MISC_A, n ? n * 64 : 16, &d_p));
+  MZK_TRY(ws.get(WS_MISC_B, 256, &d_o));
   if (msm_chunkable(n, MSM_PTS_PLAIN, 0) && host_chunks_enabled()) {
     // four equal pieces of scalars + points: the transfers (96 bytes per pair: 1.7 ms at 2^20) run under the pieces' kernels but for
     // the first piece's (profiles/round6_host_buffer_chunks.txt)
     static const int quarters[4] = {64, 128, 192, 256};
     MsmChunk ch[8];
-    MZK_TRY(ws_get(WS_MSM_SCALARS, n * 32, &d_s));
+    MZK_TRY(ws.get(WS_MSM_SCALARS, n * 32, &d_s));
     const int K = host_chunk_plan(n, "MZK_HOST_CHUNKS_MSM", quarters, 4, ch);
     MZK_TRY(msm_host_chunked(scalars, points_xy, d_s, d_p, d_p, n, MSM_PTS_PLAIN, 0, d_o, s, ch, K));
     MZK_TRY(d2h_sync(out_xy, d_o, 64, s));
@@ -1121,7 +1071,7 @@ int mzk_msm_g1_bn254(const uint64_t* scalars, const uint64_t* points_xy, size_t 
   }
   MZK_HIP(hipEventRecord(fork, s));
   MZK_HIP(hipStreamWaitEvent(side, fork, 0));
-  MZK_TRY(stage_in(WS_MSM_SCALARS, scalars, n * 32, &d_s, s));
+  MZK_TRY(stage_in(ws, WS_MSM_SCALARS, scalars, n * 32, &d_s, s));
   const std::function<int()> points_ready = [&]() -> int {
     if (n) MZK_HIP(hipMemcpyAsync(d_p, points_xy, n * 64, hipMemcpyHostToDevice, side));
     MZK_HIP(hipEventRecord(join, side));
@@ -1195,11 +1145,12 @@ int srs_alloc_layout(mzk_srs* h, int with_tables) {
 }
 // fills a freshly laid-out handle from n affine canonical points in device memory
 int srs_fill(mzk_srs* h, const void* d_plain, hipStream_t s) {
+  WsFrame ws("srs_fill");
   const size_t n = h->n;
   if (n == 0) return MZK_OK;
   if (!h->has_tables) return msm_prepare_points(d_plain, n, h->d_points_mont, (uint8_t*)h->d_points_mont + n * 64, s);
   void* d_mont;
-  MZK_TRY(ws_get(WS_MSM_POINTS, n * 64, &d_mont));
+  MZK_TRY(ws.get(WS_MSM_POINTS, n * 64, &d_mont));
   MZK_TRY(msm_prepare_points(d_plain, n, d_mont, nullptr, s));
   return msm_build_tables(d_mont, n, h->d_points_mont, h->window_bits * h->sets, s);     // every sets-th window: rows 2^(c sets q) P_i
 }
@@ -1248,6 +1199,7 @@ int mzk_srs_bucket_sets(const mzk_srs* srs) { return (srs && srs->has_tables) ? 
 
 int mzk_srs_upload(const uint64_t* powers_xy, size_t n, mzk_srs** out) {
   MZK_ENTER();
+  WsFrame ws("mzk_srs_upload");
   if (!out || (!powers_xy && n)) { set_error("srs_upload: null pointer"); return MZK_E_ARG; }
   hipStream_t s = ctx().stream;
   WsGuard wsg(s);
@@ -1256,7 +1208,7 @@ int mzk_srs_upload(const uint64_t* powers_xy, size_t n, mzk_srs** out) {
   if (rc != MZK_OK) { delete h; return rc; }
   if (n) {
     void* d_plain;
-    rc = stage_in(WS_MISC_A, powers_xy, n * 64, &d_plain, s);
+    rc = stage_in(ws, WS_MISC_A, powers_xy, n * 64, &d_plain, s);
     if (rc == MZK_OK) rc = srs_fill(h, d_plain, s);
     if (rc == MZK_OK && hipStreamSynchronize(s) != hipSuccess) rc = MZK_E_HIP;
     if (rc != MZK_OK) { (void)hipFree(h->d_points_mont); delete h; return rc; }
@@ -1273,24 +1225,25 @@ void mzk_srs_free(mzk_srs* srs) {
 }
 int mzk_kzg_commit_srs(const mzk_srs* srs, const uint64_t* coef, size_t n, uint64_t out_xy[8]) {
   MZK_ENTER();
+  WsFrame ws("mzk_kzg_commit_srs");
   if (!srs || !out_xy || (!coef && n)) { set_error("commit_srs: null pointer"); return MZK_E_ARG; }
   MZK_TRY(srs_check_ctx(srs));
   if (n > srs->n) { set_error("index out of bounds: the len is %zu but the index is %zu", srs->n, srs->n); return MZK_E_LENGTH; }  // powers[i], polynomial.rs:162
   hipStream_t s = ctx().stream;
   WsGuard wsg(s);
   void *d_s, *d_o;
-  MZK_TRY(ws_get(WS_MISC_B, 256, &d_o));
+  MZK_TRY(ws.get(WS_MISC_B, 256, &d_o));
   if (msm_chunkable(n, srs->kind(), srs->n) && host_chunks_enabled()) {
     // a quarter of the coefficients first, the rest under its kernels (two pieces: every piece costs a segment combine of its own)
     static const int quarter_then_rest[2] = {64, 256};
     MsmChunk ch[8];
-    MZK_TRY(ws_get(WS_MSM_SCALARS, n * 32, &d_s));
+    MZK_TRY(ws.get(WS_MSM_SCALARS, n * 32, &d_s));
     const int K = host_chunk_plan(n, "MZK_HOST_CHUNKS_COMMIT", quarter_then_rest, 2, ch);
     MZK_TRY(msm_host_chunked(coef, nullptr, d_s, nullptr, srs->d_points_mont, n, srs->kind(), srs->n, d_o, s, ch, K));
     MZK_TRY(d2h_sync(out_xy, d_o, 64, s));
     return MZK_OK;
   }
-  MZK_TRY(stage_in(WS_MSM_SCALARS, coef, n * 32, &d_s, s));
+  MZK_TRY(stage_in(ws, WS_MSM_SCALARS, coef, n * 32, &d_s, s));
   MZK_TRY(msm_dev_impl(d_s, srs->d_points_mont, n, srs->kind(), srs->n, d_o, false, s));
   MZK_TRY(d2h_sync(out_xy, d_o, 64, s));
   return MZK_OK;
@@ -1478,14 +1431,15 @@ int mzk_kzg_open_srs_batch_dev(const mzk_srs* srs, const void* d_coefs, size_t n
 // open_kzg of `count` polynomials with everything in host memory: ys = count * 4 limbs, ws_xy = count * 8 limbs
 int mzk_kzg_open_srs_batch(const mzk_srs* srs, const uint64_t* coefs, size_t n, size_t count, const uint64_t* us, uint64_t* ys, uint64_t* ws_xy) {
   MZK_ENTER();
+  WsFrame ws("mzk_kzg_open_srs_batch");
   if (!srs || ((!coefs || !us || !ys || !ws_xy) && count)) { set_error("open_srs_batch: null pointer"); return MZK_E_ARG; }
   if (count == 0) return MZK_OK;
   hipStream_t s = ctx().stream;
   void *d_c, *d_o;
   {
     WsGuard wsg(s);
-    MZK_TRY(stage_in(WS_MISC_E, coefs, count * n * 32, &d_c, s));
-    MZK_TRY(ws_get(WS_MISC_F, count * 96, &d_o));
+    MZK_TRY(stage_in(ws, WS_MISC_E, coefs, count * n * 32, &d_c, s));
+    MZK_TRY(ws.get(WS_MISC_F, count * 96, &d_o));
   }
   char* d_y = (char*)d_o;
   char* d_w = d_y + count * 32;
@@ -1496,14 +1450,15 @@ int mzk_kzg_open_srs_batch(const mzk_srs* srs, const uint64_t* coefs, size_t n, 
 }
 int mzk_kzg_commit_srs_batch(const mzk_srs* srs, const uint64_t* coefs, size_t n, size_t count, uint64_t* out_xy) {
   MZK_ENTER();
+  WsFrame ws("mzk_kzg_commit_srs_batch");
   if (!srs || ((!coefs || !out_xy) && count)) { set_error("commit_srs_batch: null pointer"); return MZK_E_ARG; }
   if (count == 0) return MZK_OK;
   hipStream_t s = ctx().stream;
   void *d_c, *d_o;
   {
     WsGuard wsg(s);
-    MZK_TRY(stage_in(WS_MISC_E, coefs, count * n * 32, &d_c, s));
-    MZK_TRY(ws_get(WS_MISC_F, count * 64, &d_o));
+    MZK_TRY(stage_in(ws, WS_MISC_E, coefs, count * n * 32, &d_c, s));
+    MZK_TRY(ws.get(WS_MISC_F, count * 64, &d_o));
   }
   MZK_TRY(mzk_kzg_commit_srs_batch_dev(srs, d_c, n, count, d_o, 0, s));
   MZK_TRY(d2h_sync(out_xy, d_o, count * 64, s));
@@ -1588,6 +1543,7 @@ int mzk_fri_fold_dev(int field_id, const void* d_codeword, size_t n, const uint6
 int mzk_fri_fold(int field_id, const uint64_t* codeword, size_t n, const uint64_t* alpha, const uint64_t* offset,
                  const uint64_t* omega, uint64_t* out) {
   MZK_ENTER();
+  WsFrame ws("mzk_fri_fold");
   MZK_TRY(field_check_gl(field_id, "fri_fold"));
   if (n / 2 == 0) return MZK_OK;
   if (!codeword || !out) { set_error("fri_fold: null pointer"); return MZK_E_ARG; }
@@ -1595,8 +1551,8 @@ int mzk_fri_fold(int field_id, const uint64_t* codeword, size_t n, const uint64_
   WsGuard wsg(s);
   const size_t esz = field_bytes(field_id);
   void *d_in, *d_out;
-  MZK_TRY(stage_in(WS_NTT_IO_A, codeword, n * esz, &d_in, s));
-  MZK_TRY(ws_get(WS_NTT_IO_B, (n / 2) * esz, &d_out));
+  MZK_TRY(stage_in(ws, WS_NTT_IO_A, codeword, n * esz, &d_in, s));
+  MZK_TRY(ws.get(WS_NTT_IO_B, (n / 2) * esz, &d_out));
   MZK_TRY(fri_fold_dev_impl(field_id, d_in, n, alpha, offset, omega, d_out, s));
   MZK_TRY(stage_out(out, d_out, (n / 2) * esz, s));
   return MZK_OK;
@@ -1605,14 +1561,15 @@ int mzk_fri_fold(int field_id, const uint64_t* codeword, size_t n, const uint64_
 int mzk_kzg_batch_open(const uint64_t* coef, size_t n, const uint64_t* us, size_t k, const uint64_t* powers_xy, uint64_t* ys,
                        uint64_t w_xy[8]) {
   MZK_ENTER();
+  WsFrame ws("mzk_kzg_batch_open");
   if (!w_xy || (!coef && n) || ((!us || !ys) && k) || (!powers_xy && n > k)) { set_error("batch_open: null pointer"); return MZK_E_ARG; }
   hipStream_t s = ctx().stream;
   WsGuard wsg(s);
   const size_t nq = n > k ? n - k : 0;
   void *d_c, *d_p, *d_o;
-  MZK_TRY(stage_in(WS_MSM_SCALARS, coef, n * 32, &d_c, s));
-  MZK_TRY(stage_in(WS_NTT_IO_A, powers_xy, nq * 64, &d_p, s));
-  MZK_TRY(ws_get(WS_NTT_IO_B, 64 + k * 32 + 64, &d_o));
+  MZK_TRY(stage_in(ws, WS_MSM_SCALARS, coef, n * 32, &d_c, s));
+  MZK_TRY(stage_in(ws, WS_NTT_IO_A, powers_xy, nq * 64, &d_p, s));
+  MZK_TRY(ws.get(WS_NTT_IO_B, 64 + k * 32 + 64, &d_o));
   MZK_TRY(kzg_batch_open_dev(d_c, n, us, k, d_p, MSM_PTS_PLAIN, 0, (char*)d_o + 64, d_o, s));
   std::vector<uint64_t> tmp(8 + 4 * k + 8);
   MZK_TRY(d2h_sync(tmp.data(), d_o, 64 + k * 32, s));
@@ -1635,12 +1592,13 @@ int mzk_kzg_prove_degree_bound(const uint64_t* coef, size_t n, const uint64_t* p
 
 int mzk_kzg_setup_g1(const uint64_t alpha[4], const uint64_t g1_xy[8], size_t max_d, uint64_t* powers_xy) {
   MZK_ENTER();
+  WsFrame ws("mzk_kzg_setup_g1");
   if (!alpha || !g1_xy || !powers_xy) { set_error("kzg_setup: null pointer"); return MZK_E_ARG; }
   hipStream_t s = ctx().stream;
   WsGuard wsg(s);
   const size_t count = max_d + 1;  // `for _ in 0..1 + max_d`, kzg.rs:32
   void* d_p;
-  MZK_TRY(ws_get(WS_MSM_POINTS, count * 64, &d_p));
+  MZK_TRY(ws.get(WS_MSM_POINTS, count * 64, &d_p));
   MZK_TRY(kzg_setup_g1_dev(alpha, g1_xy, 0, count, d_p, s));
   MZK_TRY(stage_out(powers_xy, d_p, count * 64, s));
   return MZK_OK;
@@ -1648,13 +1606,14 @@ int mzk_kzg_setup_g1(const uint64_t alpha[4], const uint64_t g1_xy[8], size_t ma
 
 int mzk_kzg_open(const uint64_t* coef, size_t n, const uint64_t u[4], const uint64_t* powers_xy, uint64_t y[4], uint64_t w_xy[8]) {
   MZK_ENTER();
+  WsFrame ws("mzk_kzg_open");
   if (!u || !y || !w_xy || (!coef && n) || (!powers_xy && n > 1)) { set_error("kzg_open: null pointer"); return MZK_E_ARG; }
   hipStream_t s = ctx().stream;
   WsGuard wsg(s);
   void *d_c, *d_p, *d_o;
-  MZK_TRY(stage_in(WS_MSM_SCALARS, coef, n * 32, &d_c, s));
-  MZK_TRY(stage_in(WS_NTT_IO_A, powers_xy, (n > 1 ? n - 1 : 0) * 64, &d_p, s));
-  MZK_TRY(ws_get(WS_NTT_IO_B, 256, &d_o));
+  MZK_TRY(stage_in(ws, WS_MSM_SCALARS, coef, n * 32, &d_c, s));
+  MZK_TRY(stage_in(ws, WS_NTT_IO_A, powers_xy, (n > 1 ? n - 1 : 0) * 64, &d_p, s));
+  MZK_TRY(ws.get(WS_NTT_IO_B, 256, &d_o));
   MZK_TRY(kzg_open_dev(d_c, n, u, d_p, MSM_PTS_PLAIN, 0, d_o, (char*)d_o + 64, nullptr, s));
   uint64_t tmp[16];
   MZK_TRY(d2h_sync(tmp, d_o, 128, s));

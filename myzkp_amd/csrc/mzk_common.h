@@ -12,6 +12,7 @@
 #include "../../include/mzk.h"
 #include "mzk_field.h"
 #include "mzk_msm_plan.h"
+#include "mzk_ws.h"
 
 namespace mzk {
 
@@ -48,11 +49,6 @@ int hip_fail(hipError_t e, const char* what, const char* file, int line);
 // mzk_init_devices creates one per listed ordinal (duplicates allowed: several contexts may share one GPU, which is
 // how the multi-GPU path is exercised on a one-GPU box).  Every entry point works on the CURRENT context
 // (mzk_ctx_select; context 0 after init); the *_multi entry points walk all of them.
-constexpr int MZK_MAX_CTX = 16;
-struct WsBuf { void* p = nullptr; size_t cap = 0; uint64_t epoch = 0; };      // epoch: the outermost API call that last asked for the slot
-enum WsSlot { WS_NTT_TMP = 0, WS_NTT_IO_A, WS_NTT_IO_B, WS_MSM_POINTS, WS_MSM_SCALARS, WS_MSM_COUNTS, WS_MSM_OFFSETS,
-              WS_MSM_CURSOR, WS_MSM_ENTRIES, WS_MSM_BUCKETS, WS_MSM_RED_A, WS_MSM_RED_B, WS_MSM_SCAN, WS_MSM_OUT, WS_MSM_SLOTS, WS_MSM_WGHIST, WS_BATCHINV, WS_XYZZ_TMP, WS_MERKLE_NODES, WS_FB_TABLE16, WS_FB_TABLE8, WS_NTT_PRE, WS_NTT_PRE_M128,
-              WS_MISC_A, WS_MISC_B, WS_MISC_C, WS_MISC_D, WS_MISC_E, WS_MISC_F, WS_COUNT };
 enum AttrFlag { ATTR_FINE_SCATTER4 = 0, ATTR_FINE_SCATTER8, ATTR_DIGITS_LDS, ATTR_SMALL_MSM, ATTR_NTT_LARGE_FR, ATTR_NTT_LARGE_M128, ATTR_NTT_LARGE_M128_2WG, ATTR_MANY_SORT1, ATTR_TAIL_ROW, ATTR_COARSE_STAGED4, ATTR_COARSE_STAGED8, ATTR_COUNT };
 struct Context {
   bool ready = false;
@@ -60,8 +56,7 @@ struct Context {
   int device = -1;
   int num_cu = 256;
   hipStream_t stream = nullptr;  // library-owned stream for the host-buffer entry points
-  WsBuf ws[WS_COUNT];
-  uint64_t ws_gen = 1;           // bumps whenever every workspace buffer has been released (cached device tables die with it)
+  WsTable ws;                    // scratch slots, cache slots and their generation (mzk_ws.h)
   // Stream-order guard of the shared workspace: ws_last = stream of the last entry point; an entry point on another
   // stream records ws_event on ws_last and waits for it before touching the slots (WsGuard).
   hipEvent_t ws_event = nullptr;
@@ -112,18 +107,7 @@ struct CtxScope {
   ~CtxScope();
 };
 
-// Grow-only device scratch buffers of the current context, keyed by slot, so steady-state calls never hipMalloc.
-int ws_get(WsSlot slot, size_t bytes, void** out);
-void ws_release_all();
-// Frees the slots of the current context that the running outermost call has not asked for (all of them between calls); waits for
-// the device first (earlier *_dev calls may still be reading them).  Returns the bytes given back.
-size_t ws_trim_idle();
-size_t ws_bytes_held();
-// hipMalloc that tries again after ws_trim_idle() when the device is out of memory; MZK_E_NOMEM if it still is.
-int dev_alloc(void** out, size_t bytes, const char* what);
-size_t poly_bytes_held();                      // mzk_poly.hip: pool blocks + cached interpolation plans of the current context
-size_t poly_trim_idle();                       // ... released but for what the running call uses; bytes given back
-uint64_t ws_generation();
+// Device scratch of the current context: WsFrame leases, ws_cache_get, ws_trim_idle, dev_alloc -- all in mzk_ws.h.
 // Put one at the top of every entry point that enqueues work using workspace slots on stream s.
 struct WsGuard {
   hipStream_t s;
@@ -214,9 +198,9 @@ int coset_divide_dev_impl(int fid, const void* d_lhs, size_t tl, const void* d_r
 // Trimmed length (1 + index of the last non-zero coefficient among the lens[i] given) of `count` rows `stride` elements apart, plus --
 // when d_extra is not null -- of one more vector of extra_len elements elsewhere (out_lens[count]), into host memory, in ONE launch and
 // one wait.  clear_to != 0: elements [lens[i], clear_to) of every row are zeroed in the same pass (d_rows is written only then).
-// Workspace: `slot` alone.
+// Workspace: `slot` alone, leased from the caller's frame (the caller reads nothing of it, but it is the caller that names it).
 int rows_trimmed_len_dev(int fid, void* d_rows, size_t stride, const size_t* lens, size_t count, size_t clear_to, const void* d_extra, size_t extra_len,
-                         WsSlot slot, size_t* out_lens, hipStream_t s);
+                         WsFrame& ws, WsSlot slot, size_t* out_lens, hipStream_t s);
 // coset_divide_dev_impl for several numerators of ONE squared-down order over one denominator: rows[k] = (row index in d_lhs / d_out,
 // trimmed length); quotient row = tl - tr + 1 coefficients, zeros behind them up to out_stride.  Workspace: WS_MISC_A, B, F and the
 // transform slots.
@@ -280,7 +264,10 @@ static inline bool msm_srs_default_tables(size_t n) { return n > 0; }
 // One MSM computed in CHUNKS of consecutive pairs (msm_chunked_impl): every chunk is sorted and accumulated on its own -- as soon as
 // ITS scalars (and points) are on the device -- into its own bucket array, the chunks' bucket arrays are summed and reduced once.
 // msm_dev_impl in chunk mode (cc != null) takes the chunk's scalars, the WHOLE point array, and stops after the segment combine.
+// the MSM's scratch, one pointer per slot that msm_plan sizes (null where the plan asks for nothing)
+struct MsmWs { uint32_t *points, *counts, *offsets, *cursor, *entries, *scan, *buckets, *slots, *wghist, *out; };
 struct MsmChunkCtx {
+  const MsmWs* ws;       // the slots, taken ONCE by msm_chunked_impl for all chunks: K regions in the per-chunk ones, chunk k works in the k-th
   int k, K;              // this chunk, number of chunks
   size_t i0;             // index of the chunk's first pair in the whole problem
   size_t n_total;        // pairs of the whole problem: decides the window width / bucket layout of every chunk

@@ -75,10 +75,11 @@ __global__ __launch_bounds__(64) void k_g2_powers(Words8k alpha_plain, const u32
 }
 
 int g2_msm_dev_impl(const void* d_scalars, const void* d_points, size_t n, void* d_out, hipStream_t s) {
+  WsFrame ws("g2_msm_dev_impl");
   if (!d_out || ((!d_scalars || !d_points) && n)) { set_error("msm_g2: null pointer"); return MZK_E_ARG; }
   if (n == 0) { MZK_HIP(hipMemsetAsync(d_out, 0, 128, s)); return MZK_OK; }     // empty polynomial -> infinity (polynomial.rs:160)
   u32* recs;
-  MZK_TRY(ws_get(WS_XYZZ_TMP, n * 256, (void**)&recs));
+  MZK_TRY(ws.get(WS_XYZZ_TMP, n * 256, (void**)&recs));
   hipLaunchKernelGGL(k_g2_pair_mul, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, s, (const u32*)d_scalars, (const u32*)d_points, n, recs);
   hipLaunchKernelGGL(k_g2_sum, dim3(1), dim3(G2_SUM_THREADS), 0, s, (const u32*)recs, n, (u32*)d_out);
   MZK_HIP(hipGetLastError());
@@ -96,6 +97,7 @@ int mzk_msm_g2_bn254_dev(const void* d_scalars, const void* d_points_xy, size_t 
 }
 int mzk_msm_g2_bn254(const uint64_t* scalars, const uint64_t* points_xy, size_t n, uint64_t out_xy[16]) {
   MZK_ENTER();
+  WsFrame ws("mzk_msm_g2_bn254");
   if (!out_xy || ((!scalars || !points_xy) && n)) { set_error("msm_g2: null pointer"); return MZK_E_ARG; }
   const HostField* fq = host_field(MZK_FIELD_FQ);
   for (size_t i = 0; i < 4 * n; i++)
@@ -103,9 +105,9 @@ int mzk_msm_g2_bn254(const uint64_t* scalars, const uint64_t* points_xy, size_t 
   hipStream_t s = ctx().stream;
   WsGuard wsg(s);
   void *d_s, *d_p, *d_o;
-  MZK_TRY(ws_get(WS_MSM_SCALARS, n ? n * 32 : 16, &d_s));
-  MZK_TRY(ws_get(WS_MSM_POINTS, n ? n * 128 : 16, &d_p));
-  MZK_TRY(ws_get(WS_MSM_OUT, 4096, &d_o));
+  MZK_TRY(ws.get(WS_MSM_SCALARS, n ? n * 32 : 16, &d_s));
+  MZK_TRY(ws.get(WS_MSM_POINTS, n ? n * 128 : 16, &d_p));
+  MZK_TRY(ws.get(WS_MSM_OUT, 4096, &d_o));
   if (n) {
     MZK_HIP(hipMemcpyAsync(d_s, scalars, n * 32, hipMemcpyHostToDevice, s));
     MZK_HIP(hipMemcpyAsync(d_p, points_xy, n * 128, hipMemcpyHostToDevice, s));
@@ -116,6 +118,7 @@ int mzk_msm_g2_bn254(const uint64_t* scalars, const uint64_t* points_xy, size_t 
 }
 int mzk_kzg_setup_g2(const uint64_t alpha[4], const uint64_t g2_xy[16], size_t max_d, uint64_t* powers2_xy) {
   MZK_ENTER();
+  WsFrame ws("mzk_kzg_setup_g2");
   if (!alpha || !g2_xy || !powers2_xy) { set_error("kzg_setup_g2: null pointer"); return MZK_E_ARG; }
   const HostField* fq = host_field(MZK_FIELD_FQ);
   if (!h_is_canonical(host_field(MZK_FIELD_FR), alpha)) { set_error("kzg_setup_g2: alpha not canonical"); return MZK_E_RANGE; }
@@ -124,8 +127,8 @@ int mzk_kzg_setup_g2(const uint64_t alpha[4], const uint64_t g2_xy[16], size_t m
   hipStream_t s = ctx().stream;
   WsGuard wsg(s);
   void *d_g, *d_o;
-  MZK_TRY(ws_get(WS_MSM_OUT, 4096, &d_g));
-  MZK_TRY(ws_get(WS_MSM_POINTS, count * 128, &d_o));
+  MZK_TRY(ws.get(WS_MSM_OUT, 4096, &d_g));
+  MZK_TRY(ws.get(WS_MSM_POINTS, count * 128, &d_o));
   MZK_HIP(hipMemcpyAsync(d_g, g2_xy, 128, hipMemcpyHostToDevice, s));
   Words8k aw;
   for (int i = 0; i < 4; i++) { aw.w[2 * i] = (u32)alpha[i]; aw.w[2 * i + 1] = (u32)(alpha[i] >> 32); }

@@ -240,13 +240,14 @@ __global__ __launch_bounds__(SUM_THREADS) void k_gm_sums_final(const u32* __rest
 }
 // d_out2: 2 elements (slot 0, slot 1).  Workspace: WS_NTT_IO_A (partials).
 static int gm_sums(const void* d_f, size_t count, const uint64_t* r_host, void* d_fold_out, int base, int shift, int split, void* d_out2, hipStream_t s) {
+  WsFrame ws("gm_sums");
   static const GmPow2 pw = gm_pow2();
   GmW8 r = {};
   if (r_host) gm_mont(r_host, &r);
   const size_t wg_need = (count + SUM_THREADS - 1) / SUM_THREADS;
   const int nwg = (int)(wg_need < (size_t)SUM_MAX_WG ? (wg_need ? wg_need : 1) : SUM_MAX_WG);
   u32* partials = nullptr;
-  MZK_TRY(ws_get(WS_NTT_IO_A, (size_t)nwg * 64, (void**)&partials));
+  MZK_TRY(ws.get(WS_NTT_IO_A, (size_t)nwg * 64, (void**)&partials));
   if (d_fold_out)
     hipLaunchKernelGGL(k_gm_sums<true>, dim3(nwg), dim3(SUM_THREADS), 0, s, (const u32*)d_f, count, r, (u32*)d_fold_out, base, shift, split, pw, partials);
   else
@@ -286,6 +287,7 @@ struct GmMsm { const void* src; size_t len; size_t shift; };
 // out[k] (64 bytes each) = MSM(items[k].src, points [shift_k, shift_k + len_k)).  Items i0.. (the small ones) may go as one pass:
 // then `front` pads at the front (all windows end at the same point, base = that end - width) instead of at the back.
 static int gm_msms(const mzk_srs* srs, const GmMsm* items, int count, int i0, bool front, u32* d_out, hipStream_t s) {
+  WsFrame ws("gm_msms");
   const bool capable = srs_many_capable(srs);
   const bool many = capable && count - i0 >= 2;
   const int single_to = many ? i0 : count;
@@ -293,7 +295,7 @@ static int gm_msms(const mzk_srs* srs, const GmMsm* items, int count, int i0, bo
   for (int k = 0; k < single_to && !capable; k++)
     if (items[k].len <= GM_PLAIN_MAX && items[k].len > plain_max) plain_max = items[k].len;
   u32* plain = nullptr;
-  if (plain_max) MZK_TRY(ws_get(WS_NTT_TMP, plain_max * 64, (void**)&plain));
+  if (plain_max) MZK_TRY(ws.get(WS_NTT_TMP, plain_max * 64, (void**)&plain));
   for (int k = 0; k < single_to; k++) {
     const char* pts = (const char*)srs->d_points_mont + items[k].shift * 64;
     if (plain && items[k].len <= plain_max && items[k].len > 0) {
@@ -315,7 +317,7 @@ static int gm_msms(const mzk_srs* srs, const GmMsm* items, int count, int i0, bo
     R.pad[r] = front ? (u32)(w - items[i0 + r].len) : 0;
   }
   u32* mat;
-  MZK_TRY(ws_get(WS_MISC_F, (size_t)rows * w * 32, (void**)&mat));
+  MZK_TRY(ws.get(WS_MISC_F, (size_t)rows * w * 32, (void**)&mat));
   hipLaunchKernelGGL(k_gm_pack, dim3((unsigned)((w + 255) / 256), (unsigned)rows), dim3(256), 0, s, R, (u32)w, mat);
   MZK_HIP(hipGetLastError());
   // front-padded rows: every window ends at shift_k + len_k = the same point; the padded row starts w earlier
@@ -350,6 +352,7 @@ static int gemini_commit_impl(const mzk_srs* srs, const void* d_levels, size_t n
 
 // open_gemini (gemini.rs:116-144).  d_ys: el * 3 values (f_i(beta), f_i(-beta), f_i(beta^2)); d_ws: el points; d_deg: el + 1 points.
 static int gemini_open_impl(const mzk_srs* srs, const void* d_levels, size_t n, const uint64_t* beta, void* d_ys, void* d_ws, void* d_deg, hipStream_t s) {
+  WsFrame ws("gemini_open_impl");
   if (!srs || !d_levels || !beta || !d_deg || ((!d_ys || !d_ws) && n > 1)) { set_error("gemini_open: null pointer"); return MZK_E_ARG; }
   int el;
   MZK_TRY(gm_srs_ok(srs, n, &el, "gemini_open"));
@@ -377,8 +380,8 @@ static int gemini_open_impl(const mzk_srs* srs, const void* d_levels, size_t n, 
   for (int i = 0; i < el; i++) qtot += n >> i;
   u32 *qa = nullptr, *qb = nullptr;
   if (el > 0) {
-    MZK_TRY(ws_get(WS_MISC_A, qtot * 32, (void**)&qa));
-    MZK_TRY(ws_get(WS_MISC_B, qtot * 32, (void**)&qb));
+    MZK_TRY(ws.get(WS_MISC_A, qtot * 32, (void**)&qa));
+    MZK_TRY(ws.get(WS_MISC_B, qtot * 32, (void**)&qb));
     // round A: every level at beta (quotient q1 kept), at -beta and at beta^2 (values); round B: q2 = q1 / (X + beta); round C:
     // q3 = q2 / (X - beta^2), len - 3 elements.  Grouped by point: the engine's host powers of u are per run of equal points.
     std::vector<SdJob> jobs;
@@ -437,6 +440,7 @@ int mzk_gemini_split_fold_dev(const void* d_coef, size_t n, const uint64_t* rhos
 
 int mzk_gemini_split_fold(const uint64_t* coef, size_t n, const uint64_t* rhos, size_t n_rhos, uint64_t* out) {
   MZK_ENTER();
+  WsFrame ws("mzk_gemini_split_fold");
   if (!out || (!coef && n)) { set_error("split_fold: null pointer"); return MZK_E_ARG; }
   int el;
   MZK_TRY(gm_check_n(n, &el, "split_fold"));
@@ -447,7 +451,7 @@ int mzk_gemini_split_fold(const uint64_t* coef, size_t n, const uint64_t* rhos, 
   hipStream_t s = ctx().stream;
   WsGuard wsg(s);
   void* d;
-  MZK_TRY(ws_get(WS_MISC_E, (2 * n - 1) * 32, &d));
+  MZK_TRY(ws.get(WS_MISC_E, (2 * n - 1) * 32, &d));
   MZK_HIP(hipMemcpyAsync(d, coef, n * 32, hipMemcpyHostToDevice, s));
   MZK_TRY(split_fold_impl(d, n, rhos, n_rhos, d, s));
   return d2h_sync(out, d, (2 * n - 1) * 32, s);
@@ -461,14 +465,15 @@ int mzk_gemini_commit_srs_dev(const mzk_srs* srs, const void* d_levels, size_t n
 
 int mzk_gemini_commit_srs(const mzk_srs* srs, const uint64_t* levels, size_t n, uint64_t* out_xy) {
   MZK_ENTER();
+  WsFrame ws("mzk_gemini_commit_srs");
   if (!srs || !levels || !out_xy) { set_error("gemini_commit: null pointer"); return MZK_E_ARG; }
   int el;
   MZK_TRY(gm_srs_ok(srs, n, &el, "gemini_commit"));
   hipStream_t s = ctx().stream;
   WsGuard wsg(s);
   void *d, *d_o;
-  MZK_TRY(ws_get(WS_MISC_E, (2 * n - 1) * 32, &d));
-  MZK_TRY(ws_get(WS_NTT_IO_B, (size_t)(el + 1) * 64, &d_o));
+  MZK_TRY(ws.get(WS_MISC_E, (2 * n - 1) * 32, &d));
+  MZK_TRY(ws.get(WS_NTT_IO_B, (size_t)(el + 1) * 64, &d_o));
   MZK_HIP(hipMemcpyAsync(d, levels, (2 * n - 1) * 32, hipMemcpyHostToDevice, s));
   const int rc = gemini_commit_impl(srs, d, n, d_o, s);
   if (rc != MZK_OK) { (void)hipStreamSynchronize(s); return rc; }
@@ -485,9 +490,10 @@ int mzk_gemini_open_srs_dev(const mzk_srs* srs, const void* d_levels, size_t n, 
 // results of the host forms in one device block: ys (el * 3 * 32 B), ws (el * 64 B), deg ((el + 1) * 64 B)
 static int gm_open_host(const mzk_srs* srs, const void* d_levels, size_t n, int el, const uint64_t* beta, uint64_t* ys, uint64_t* ws_xy, uint64_t* deg_xy,
                         hipStream_t s) {
+  WsFrame ws("gm_open_host");
   const size_t by = (size_t)el * 96, bw = (size_t)el * 64, bd = (size_t)(el + 1) * 64;
   char* d_o;
-  MZK_TRY(ws_get(WS_NTT_IO_B, by + bw + bd, (void**)&d_o));
+  MZK_TRY(ws.get(WS_NTT_IO_B, by + bw + bd, (void**)&d_o));
   const int rc = gemini_open_impl(srs, d_levels, n, beta, d_o, d_o + by, d_o + by + bw, s);
   if (rc != MZK_OK) { (void)hipStreamSynchronize(s); return rc; }
   std::vector<uint64_t> tmp((by + bw + bd) / 8);
@@ -499,27 +505,29 @@ static int gm_open_host(const mzk_srs* srs, const void* d_levels, size_t n, int 
 
 int mzk_gemini_open_srs(const mzk_srs* srs, const uint64_t* levels, size_t n, const uint64_t beta[4], uint64_t* ys, uint64_t* ws_xy, uint64_t* deg_xy) {
   MZK_ENTER();
+  WsFrame ws("mzk_gemini_open_srs");
   if (!srs || !levels || !beta || !deg_xy || ((!ys || !ws_xy) && n > 1)) { set_error("gemini_open: null pointer"); return MZK_E_ARG; }
   int el;
   MZK_TRY(gm_srs_ok(srs, n, &el, "gemini_open"));
   hipStream_t s = ctx().stream;
   WsGuard wsg(s);
   void* d;
-  MZK_TRY(ws_get(WS_MISC_E, (2 * n - 1) * 32, &d));
+  MZK_TRY(ws.get(WS_MISC_E, (2 * n - 1) * 32, &d));
   MZK_HIP(hipMemcpyAsync(d, levels, (2 * n - 1) * 32, hipMemcpyHostToDevice, s));
   return gm_open_host(srs, d, n, el, beta, ys, ws_xy, deg_xy, s);
 }
 
 int mzk_sumcheck_sum(const uint64_t* coef, size_t n, uint64_t h[4]) {
   MZK_ENTER();
+  WsFrame ws("mzk_sumcheck_sum");
   if (!h || (!coef && n)) { set_error("sumcheck_sum: null pointer"); return MZK_E_ARG; }
   int el;
   MZK_TRY(gm_check_n(n, &el, "sumcheck_sum"));
   hipStream_t s = ctx().stream;
   WsGuard wsg(s);
   void *d, *d_o;
-  MZK_TRY(ws_get(WS_MISC_E, n * 32, &d));
-  MZK_TRY(ws_get(WS_NTT_IO_B, 64, &d_o));
+  MZK_TRY(ws.get(WS_MISC_E, n * 32, &d));
+  MZK_TRY(ws.get(WS_NTT_IO_B, 64, &d_o));
   MZK_HIP(hipMemcpyAsync(d, coef, n * 32, hipMemcpyHostToDevice, s));
   // h = sum_t c[t] 2^(el - popcount t): variable i contributes g(..0..) + g(..1..), a factor 2 where its exponent is 0
   MZK_TRY(gm_sums(d, n, nullptr, nullptr, el, 0, 0, d_o, s));
@@ -532,6 +540,7 @@ int mzk_sumcheck_sum(const uint64_t* coef, size_t n, uint64_t h[4]) {
 int mzk_sumcheck_prove_srs(const mzk_srs* srs, const uint64_t* coef, size_t n, mzk_sumcheck_challenge_fn cb, void* user, uint64_t* gs, uint64_t* rs,
                            uint64_t beta[4], uint64_t* commits_xy, uint64_t* ys, uint64_t* ws_xy, uint64_t* deg_xy) {
   MZK_ENTER();
+  WsFrame ws("mzk_sumcheck_prove_srs");
   if (!srs || !coef || !cb || !gs || !rs || !beta || !commits_xy || !ys || !ws_xy || !deg_xy) { set_error("sumcheck_prove: null pointer"); return MZK_E_ARG; }
   int el;
   MZK_TRY(gm_srs_ok(srs, n, &el, "sumcheck_prove"));
@@ -540,28 +549,32 @@ int mzk_sumcheck_prove_srs(const mzk_srs* srs, const uint64_t* coef, size_t n, m
   const HostField* fr = host_field(MZK_FIELD_FR);
   hipStream_t s = ctx().stream;
   WsGuard wsg(s);
-  char *d, *d_g;
-  MZK_TRY(ws_get(WS_MISC_E, (2 * n - 1) * 32, (void**)&d));
-  MZK_TRY(ws_get(WS_NTT_IO_B, 64, (void**)&d_g));
-  MZK_HIP(hipMemcpyAsync(d, coef, n * 32, hipMemcpyHostToDevice, s));
-  // round 0: g_0 = A_0 + B_0 X from f_0 (m = el - 1)
-  MZK_TRY(gm_sums(d, n, nullptr, nullptr, el - 1, 1, 1, d_g, s));
-  for (int j = 0; j < el; j++) {
-    MZK_TRY(d2h_sync(gs + 8 * j, d_g, 64, s));
-    uint64_t r[4] = {0, 0, 0, 0};
-    if (cb(user, j, gs + 8 * j, r) != 0) { set_error("sumcheck_prove: the challenge callback failed in round %d", j); return MZK_E_CALLBACK; }
-    if (!h_is_canonical(fr, r)) { set_error("sumcheck_prove: r_%d not canonical", j); return MZK_E_RANGE; }
-    memcpy(rs + 4 * j, r, 32);
-    // f_{j+1} = fold(f_j, r_j), and in the same pass g_{j+1}'s sums (m = el - 2 - j; none after the last round)
-    const size_t len = n >> j;
-    MZK_TRY(gm_sums(d + gm_level_off(n, j) * 32, len / 2, r, d + gm_level_off(n, j + 1) * 32, el - 2 - j, 1, 1, d_g, s));
+  char* d;
+  MZK_TRY(ws.get(WS_MISC_E, (2 * n - 1) * 32, (void**)&d));
+  {   // the rounds' sums land in WS_NTT_IO_B; the lease ends with the rounds, gm_open_host below takes the slot for its results
+    WsFrame rounds("mzk_sumcheck_prove_srs (rounds)");
+    char* d_g;
+    MZK_TRY(rounds.get(WS_NTT_IO_B, 64, (void**)&d_g));
+    MZK_HIP(hipMemcpyAsync(d, coef, n * 32, hipMemcpyHostToDevice, s));
+    // round 0: g_0 = A_0 + B_0 X from f_0 (m = el - 1)
+    MZK_TRY(gm_sums(d, n, nullptr, nullptr, el - 1, 1, 1, d_g, s));
+    for (int j = 0; j < el; j++) {
+      MZK_TRY(d2h_sync(gs + 8 * j, d_g, 64, s));
+      uint64_t r[4] = {0, 0, 0, 0};
+      if (cb(user, j, gs + 8 * j, r) != 0) { set_error("sumcheck_prove: the challenge callback failed in round %d", j); return MZK_E_CALLBACK; }
+      if (!h_is_canonical(fr, r)) { set_error("sumcheck_prove: r_%d not canonical", j); return MZK_E_RANGE; }
+      memcpy(rs + 4 * j, r, 32);
+      // f_{j+1} = fold(f_j, r_j), and in the same pass g_{j+1}'s sums (m = el - 2 - j; none after the last round)
+      const size_t len = n >> j;
+      MZK_TRY(gm_sums(d + gm_level_off(n, j) * 32, len / 2, r, d + gm_level_off(n, j + 1) * 32, el - 2 - j, 1, 1, d_g, s));
+    }
   }
   uint64_t b[4] = {0, 0, 0, 0};
   if (cb(user, el, nullptr, b) != 0) { (void)hipStreamSynchronize(s); set_error("sumcheck_prove: the challenge callback failed for beta"); return MZK_E_CALLBACK; }
   if (!h_is_canonical(fr, b)) { (void)hipStreamSynchronize(s); set_error("sumcheck_prove: beta not canonical"); return MZK_E_RANGE; }
   memcpy(beta, b, 32);
   char* d_c;
-  MZK_TRY(ws_get(WS_NTT_IO_A, (size_t)(el + 1) * 64, (void**)&d_c));
+  MZK_TRY(ws.get(WS_NTT_IO_A, (size_t)(el + 1) * 64, (void**)&d_c));
   int rc = gemini_commit_impl(srs, d, n, d_c, s);
   if (rc == MZK_OK) rc = d2h_sync(commits_xy, d_c, (size_t)(el + 1) * 64, s);
   if (rc != MZK_OK) { (void)hipStreamSynchronize(s); return rc; }

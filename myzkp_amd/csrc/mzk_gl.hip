@@ -339,6 +339,7 @@ static int gl_get_offtab(u64 offset, hipStream_t s, const u64** out) {
 // Walks the steps of ntt_plan (mzk_ntt_plan.h) over the tables of `pl`.
 template <int NC>
 static int gl_run_plan(const GlPlan* pl, const u64* d_in, u64* d_out, size_t batch, const GlPre* pre, hipStream_t s) {
+  WsFrame ws("gl_run_plan");
   const unsigned logn = pl->logn;
   const NttSchedule sc = ntt_plan(NC == 3 ? MZK_FIELD_M64X3 : MZK_FIELD_M64, logn, batch, NttKnobs());
   if (sc.err != MZK_OK) { set_error("%s", sc.msg); return sc.err; }
@@ -347,7 +348,7 @@ static int gl_run_plan(const GlPlan* pl, const u64* d_in, u64* d_out, size_t bat
   ProfScope whole(s, MZK_PH_NTT_TOTAL);
   const u64* src = d_in;
   u64* tmp = nullptr;
-  if (sc.tmp_bytes) MZK_TRY(ws_get(WS_NTT_TMP, sc.tmp_bytes, (void**)&tmp));
+  if (sc.tmp_bytes) MZK_TRY(ws.get(WS_NTT_TMP, sc.tmp_bytes, (void**)&tmp));
   for (int t = 0; t < sc.nsteps; t++) {
     const NttStep& st = sc.steps[t];
     const bool with_pre = t == 0 && pre;

@@ -55,6 +55,7 @@ extern "C" {
 
 int mzk_srs_save(const mzk_srs* srs, const char* path, int with_tables) {
   MZK_ENTER();
+  WsFrame ws("mzk_srs_save");
   if (!srs || !path) { set_error("srs_save: null pointer"); return MZK_E_ARG; }
   if (srs->ctx_index != ctx().index) { set_error("SRS handle lives on context %d, the current context is %d", srs->ctx_index, ctx().index); return MZK_E_ARG; }
   hipStream_t s = ctx().stream;
@@ -71,7 +72,7 @@ int mzk_srs_save(const mzk_srs* srs, const char* path, int with_tables) {
   if (fwrite(&h, sizeof h, 1, fc.f) != 1) { set_error("srs_save: write failed"); return MZK_E_IO; }
   std::vector<uint8_t> host(IO_CHUNK_POINTS * 64);
   void* d_plain;
-  MZK_TRY(ws_get(WS_MISC_A, IO_CHUNK_POINTS * 64, &d_plain));
+  MZK_TRY(ws.get(WS_MISC_A, IO_CHUNK_POINTS * 64, &d_plain));
   uint64_t hash = 0xcbf29ce484222325ULL;
   for (size_t at = 0; at < srs->n; at += IO_CHUNK_POINTS) {
     const size_t m = srs->n - at < IO_CHUNK_POINTS ? srs->n - at : IO_CHUNK_POINTS;
@@ -159,13 +160,14 @@ int mzk_srs_load(const char* path, int with_tables, mzk_srs** out) {
 // the points of a handle back at the ABI (affine canonical, n * 8 limbs): PublicKeyKZG.powers_1 as the reference holds it
 int mzk_srs_download(const mzk_srs* srs, uint64_t* powers_xy, size_t cap_points) {
   MZK_ENTER();
+  WsFrame ws("mzk_srs_download");
   if (!srs || (!powers_xy && srs->n)) { set_error("srs_download: null pointer"); return MZK_E_ARG; }
   if (cap_points < srs->n) { set_error("srs_download: buffer holds %zu points, the SRS has %zu", cap_points, srs->n); return MZK_E_LENGTH; }
   if (srs->ctx_index != ctx().index) { set_error("SRS handle lives on context %d, the current context is %d", srs->ctx_index, ctx().index); return MZK_E_ARG; }
   hipStream_t s = ctx().stream;
   WsGuard wsg(s);
   void* d_plain;
-  MZK_TRY(ws_get(WS_MISC_A, IO_CHUNK_POINTS * 64, &d_plain));
+  MZK_TRY(ws.get(WS_MISC_A, IO_CHUNK_POINTS * 64, &d_plain));
   for (size_t at = 0; at < srs->n; at += IO_CHUNK_POINTS) {
     const size_t m = srs->n - at < IO_CHUNK_POINTS ? srs->n - at : IO_CHUNK_POINTS;
     MZK_TRY(msm_points_to_plain((const uint8_t*)srs->d_points_mont + at * 64, m, d_plain, s));

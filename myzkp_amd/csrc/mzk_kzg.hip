@@ -204,9 +204,10 @@ __global__ __launch_bounds__(128) void k_xyzz_batch_to_affine(const u32* __restr
   }
 }
 int xyzz_batch_to_affine(const void* d_xyzz, size_t count, void* d_out, bool out_mont, hipStream_t s) {
+  WsFrame ws("xyzz_batch_to_affine");
   if (count == 0) return MZK_OK;
   u32* scratch;
-  MZK_TRY(ws_get(WS_BATCHINV, count * FqParams::L * sizeof(u32), (void**)&scratch));
+  MZK_TRY(ws.get(WS_BATCHINV, count * FqParams::L * sizeof(u32), (void**)&scratch));
   const size_t threads = (count + BATCH_INV - 1) / BATCH_INV;
   hipLaunchKernelGGL(k_xyzz_batch_to_affine, dim3((unsigned)((threads + 127) / 128)), dim3(128), 0, s, (const u32*)d_xyzz, count, scratch,
                      (u32*)d_out, out_mont ? 1 : 0);
@@ -215,6 +216,7 @@ int xyzz_batch_to_affine(const void* d_xyzz, size_t count, void* d_out, bool out
 }
 
 int kzg_setup_g1_dev(const uint64_t* alpha_host, const uint64_t* g1_host, size_t first, size_t count, void* d_powers_xy, hipStream_t s) {
+  WsFrame ws("kzg_setup_g1_dev");
   if (!alpha_host || !g1_host || (!d_powers_xy && count)) { set_error("kzg_setup: null pointer"); return MZK_E_ARG; }
   if (count == 0) return MZK_OK;
   if (!h_is_canonical(host_field(MZK_FIELD_FR), alpha_host) || !h_is_canonical(host_field(MZK_FIELD_FQ), g1_host) ||
@@ -224,14 +226,14 @@ int kzg_setup_g1_dev(const uint64_t* alpha_host, const uint64_t* g1_host, size_t
   for (int i = 0; i < 4; i++) { aw.w[2 * i] = (u32)alpha_host[i]; aw.w[2 * i + 1] = (u32)(alpha_host[i] >> 32); }
   for (int i = 0; i < 8; i++) { gw.w[2 * i] = (u32)g1_host[i]; gw.w[2 * i + 1] = (u32)(g1_host[i] >> 32); }
   u32 *bases, *table, *acc, *atab;
-  MZK_TRY(ws_get(WS_MISC_C, (size_t)(3 << ATAB_BITS) * 32, (void**)&atab));
-  MZK_TRY(ws_get(WS_FB_TABLE8, 32 * 64 + 32 * 256 * 64, (void**)&bases));
+  MZK_TRY(ws.get(WS_MISC_C, (size_t)(3 << ATAB_BITS) * 32, (void**)&atab));
+  MZK_TRY(ws_cache_get(WS_FB_TABLE8, 32 * 64 + 32 * 256 * 64, (void**)&bases));
   table = bases + 32 * 16;
   const bool wide = count >= ((size_t)1 << 16);      // the 64 MiB table pays for itself from ~2^16 powers on
   const size_t t16 = (size_t)16 << 16;
-  MZK_TRY(ws_get(WS_XYZZ_TMP, (wide && t16 > count ? t16 : count) * 128, (void**)&acc));
+  MZK_TRY(ws.get(WS_XYZZ_TMP, (wide && t16 > count ? t16 : count) * 128, (void**)&acc));
   u32* table16 = nullptr;
-  if (wide) MZK_TRY(ws_get(WS_FB_TABLE16, t16 * 64, (void**)&table16));
+  if (wide) MZK_TRY(ws_cache_get(WS_FB_TABLE16, t16 * 64, (void**)&table16));
   // The fixed-base tables depend only on g1 (in practice always BN128::generator_g1()) and their construction is a
   // latency chain (248 serial doublings for the window bases + two inversions: ~1.4 ms, more than a whole 2^16-power
   // setup), so they are kept across calls, keyed by g1 and by the workspace generation.
@@ -405,6 +407,7 @@ static void sd_words(const uint64_t* v, int nl, u32* w) {
 }
 template <class P>
 static int synth_div_impl(int fid, const SdJob* jobs, const size_t* rounds, int nrounds, hipStream_t s) {
+  WsFrame ws("synth_div_impl");
   const HostField* hf = host_field(fid);
   const int nl = hf->nl;
   const size_t ub = 8 * (size_t)nl;                        // bytes of one host element
@@ -474,12 +477,12 @@ static int synth_div_impl(int fid, const SdJob* jobs, const size_t* rounds, int 
   u32* D = nullptr;
   const size_t need = walk(nullptr);
   if (need) {
-    MZK_TRY(ws_get(WS_MISC_D, need * field_bytes(fid), (void**)&D));
+    MZK_TRY(ws.get(WS_MISC_D, need * field_bytes(fid), (void**)&D));
     walk(D);
   }
   if (tab.empty()) return MZK_OK;
   SdRec* d_tab;
-  MZK_TRY(ws_get(WS_MISC_C, tab.size() * sizeof(SdRec), (void**)&d_tab));
+  MZK_TRY(ws.get(WS_MISC_C, tab.size() * sizeof(SdRec), (void**)&d_tab));
   MZK_HIP(hipMemcpyAsync(d_tab, tab.data(), tab.size() * sizeof(SdRec), hipMemcpyHostToDevice, s));
   for (const Step& st : steps) {
     const SdRec* jt = d_tab + st.first;
@@ -529,6 +532,7 @@ int poly_div_roots_check(int fid, const void* polys, size_t stride, const size_t
 // E (lengths).  Returns when d_out and out_lens are complete.
 int poly_div_roots_dev_impl(int fid, const void* d_polys, size_t stride, const size_t* lens, size_t count, const uint64_t* roots, const size_t* root_offsets,
                             void* d_out, size_t* out_lens, hipStream_t s) {
+  WsFrame ws("poly_div_roots_dev_impl");
   if (count == 0) return MZK_OK;
   const size_t esz = field_bytes(fid);
   const int nl = host_field(fid)->nl;
@@ -542,8 +546,8 @@ int poly_div_roots_dev_impl(int fid, const void* d_polys, size_t stride, const s
   }
   if (stride == 0) return MZK_OK;
   char *bA = nullptr, *bB = nullptr;
-  if (maxk >= 2) MZK_TRY(ws_get(WS_MISC_A, count * stride * esz, (void**)&bA));
-  if (maxk >= 3) MZK_TRY(ws_get(WS_MISC_B, count * stride * esz, (void**)&bB));
+  if (maxk >= 2) MZK_TRY(ws.get(WS_MISC_A, count * stride * esz, (void**)&bA));
+  if (maxk >= 3) MZK_TRY(ws.get(WS_MISC_B, count * stride * esz, (void**)&bB));
   std::vector<SdJob> jobs;
   std::vector<size_t> rounds(maxk, 0);
   for (size_t r = 0; r < maxk; r++)
@@ -564,7 +568,7 @@ int poly_div_roots_dev_impl(int fid, const void* d_polys, size_t stride, const s
   if (rc != MZK_OK) return fail(rc);
   std::vector<size_t> qlens(count);
   for (size_t i = 0; i < count; i++) qlens[i] = (size_t)meta[i];
-  rc = rows_trimmed_len_dev(fid, d_out, stride, qlens.data(), count, stride, nullptr, 0, WS_MISC_E, out_lens, s);
+  rc = rows_trimmed_len_dev(fid, d_out, stride, qlens.data(), count, stride, nullptr, 0, ws, WS_MISC_E, out_lens, s);
   if (rc != MZK_OK) return fail(rc);
   return MZK_OK;
 }
@@ -573,6 +577,7 @@ int poly_div_roots_dev_impl(int fid, const void* d_polys, size_t stride, const s
 // evaluations, then one round per quotient.  d_ys: k * 8 words, d_w_xy: 16 words.
 int kzg_batch_open_dev(const void* d_coef, size_t n, const uint64_t* us_host, size_t k, const void* d_points, int point_kind,
                        size_t table_stride, void* d_ys, void* d_w_xy, hipStream_t s) {
+  WsFrame ws("kzg_batch_open_dev");
   if (!d_w_xy || (!d_coef && n) || ((!us_host || !d_ys) && k)) { set_error("batch_open: null pointer"); return MZK_E_ARG; }
   const HostField* fr = host_field(MZK_FIELD_FR);
   for (size_t i = 0; i < k; i++) if (!h_is_canonical(fr, us_host + 4 * i)) { set_error("batch_open: u not canonical"); return MZK_E_RANGE; }
@@ -582,8 +587,8 @@ int kzg_batch_open_dev(const void* d_coef, size_t n, const uint64_t* us_host, si
     return MZK_OK;
   }
   u32 *bA, *bB;
-  MZK_TRY(ws_get(WS_MISC_A, n * 32, (void**)&bA));
-  MZK_TRY(ws_get(WS_MISC_B, n * 32, (void**)&bB));
+  MZK_TRY(ws.get(WS_MISC_A, n * 32, (void**)&bA));
+  MZK_TRY(ws.get(WS_MISC_B, n * 32, (void**)&bB));
   std::vector<SdJob> jobs;
   std::vector<size_t> rounds;
   for (size_t i = 0; i < k; i++) jobs.push_back({d_coef, n, us_host + 4 * i, nullptr, (char*)d_ys + 32 * i, nullptr});
@@ -604,6 +609,7 @@ int kzg_batch_open_dev(const void* d_coef, size_t n, const uint64_t* us_host, si
 // witness w = MSM(q, points) into d_w_xy (16 words) when given, q then in workspace unless d_q holds it.
 int kzg_open_dev(const void* d_coef, size_t n, const uint64_t* u_host, const void* d_points, int point_kind, size_t table_stride,
                  void* d_y, void* d_w_xy, void* d_q, hipStream_t s) {
+  WsFrame ws("kzg_open_dev");
   if (!u_host || !d_y || (!d_coef && n) || (d_w_xy && !d_points && n > 1)) { set_error("kzg_open: null pointer"); return MZK_E_ARG; }
   if (!h_is_canonical(host_field(MZK_FIELD_FR), u_host)) { set_error("kzg_open: u not canonical"); return MZK_E_RANGE; }
   if (n == 0) {  // empty polynomial: y = 0, quotient empty -> infinity
@@ -611,7 +617,7 @@ int kzg_open_dev(const void* d_coef, size_t n, const uint64_t* u_host, const voi
     if (d_w_xy) MZK_HIP(hipMemsetAsync(d_w_xy, 0, 64, s));
     return MZK_OK;
   }
-  if (d_w_xy && !d_q) MZK_TRY(ws_get(WS_MISC_A, n * 32, &d_q));
+  if (d_w_xy && !d_q) MZK_TRY(ws.get(WS_MISC_A, n * 32, &d_q));
   const SdJob job = {d_coef, n, u_host, nullptr, d_y, d_q};
   const size_t one = 1;
   MZK_TRY(synth_div_dev(&job, &one, 1, s));
@@ -626,6 +632,7 @@ constexpr size_t OPEN_MANY_MAX_N = (size_t)1 << 14;      // the witness pass's r
 bool kzg_open_many_supported(const mzk_srs* srs, size_t n) { return n <= OPEN_MANY_MAX_N && srs_many_capable(srs); }
 // d_ys: count * 8 words, d_ws_xy: count * 16 words.
 int kzg_open_many_dev(const mzk_srs* srs, const void* d_coefs, size_t n, size_t count, const uint64_t* us_host, void* d_ys, void* d_ws_xy, hipStream_t s) {
+  WsFrame ws("kzg_open_many_dev");
   if (count == 0) return MZK_OK;
   if (!srs || !us_host || !d_ys || !d_ws_xy || (!d_coefs && n)) { set_error("kzg_open_many: null pointer"); return MZK_E_ARG; }
   const HostField* fr = host_field(MZK_FIELD_FR);
@@ -637,7 +644,7 @@ int kzg_open_many_dev(const mzk_srs* srs, const void* d_coefs, size_t n, size_t 
   }
   const size_t per_pass = (((size_t)1 << 22) + n - 1) / n;
   char* d_q;
-  MZK_TRY(ws_get(WS_MISC_A, (count < per_pass ? count : per_pass) * n * 32, (void**)&d_q));
+  MZK_TRY(ws.get(WS_MISC_A, (count < per_pass ? count : per_pass) * n * 32, (void**)&d_q));
   std::vector<SdJob> jobs;
   for (size_t first = 0; first < count; first += per_pass) {
     const size_t cnt = (count - first < per_pass) ? count - first : per_pass;
@@ -668,6 +675,7 @@ int mzk_poly_div_roots_dev(int field_id, const void* d_polys, size_t stride, con
 int mzk_poly_div_roots(int field_id, const uint64_t* polys, size_t stride, const size_t* lens, size_t count, const uint64_t* roots,
                        const size_t* root_offsets, uint64_t* out, size_t* out_lens) {
   MZK_ENTER();
+  WsFrame ws("mzk_poly_div_roots");
   MZK_TRY(poly_div_roots_check(field_id, polys, stride, lens, count, roots, root_offsets, out, out_lens));
   if (count == 0) return MZK_OK;
   const HostField* hf = host_field(field_id);
@@ -678,7 +686,7 @@ int mzk_poly_div_roots(int field_id, const uint64_t* polys, size_t stride, const
   hipStream_t s = ctx().stream;
   WsGuard wsg(s);
   char* d;
-  MZK_TRY(ws_get(WS_MISC_F, 2 * bytes + 16, (void**)&d));
+  MZK_TRY(ws.get(WS_MISC_F, 2 * bytes + 16, (void**)&d));
   if (bytes) MZK_HIP(hipMemcpyAsync(d, polys, bytes, hipMemcpyHostToDevice, s));
   const int rc = poly_div_roots_dev_impl(field_id, d, stride, lens, count, roots, root_offsets, d + bytes, out_lens, s);
   if (rc != MZK_OK) { (void)hipStreamSynchronize(s); return rc; }

@@ -694,6 +694,7 @@ static int merkle_build(int kind, int fid, const void* src, bool src_on_device, 
 
 // Any leaf count that is not a power of two (never produced by the provers, but accepted by merkle.rs:15-25).
 static int merkle_build_ragged(const uint8_t* leaves, const uint64_t* offsets, size_t n, mzk_merkle** out, hipStream_t s) {
+  WsFrame ws("merkle_build_ragged");
   if (n > ((size_t)1 << 31)) { set_error("merkle: ragged trees support up to 2^31 leaves"); return MZK_E_ARG; }
   mzk_merkle* t = new mzk_merkle();
   t->kind = 1; t->field = -1; t->n = n; t->stream = s; t->d_nodes = nullptr; t->d_leaves = nullptr; t->ragged = true;
@@ -728,9 +729,9 @@ static int merkle_build_ragged(const uint8_t* leaves, const uint64_t* offsets, s
   do {
     if (hipMalloc(&t->d_leaves, leaf_bytes ? leaf_bytes : 16) != hipSuccess || hipMalloc(&t->d_items, io ? io : 16) != hipSuccess ||
         hipMalloc((void**)&t->d_nodes, (m - 1) * 32) != hipSuccess) { set_error("merkle: hipMalloc failed"); rc = MZK_E_HIP; break; }
-    if ((rc = ws_get(WS_MISC_D, (n + 1) * 8, (void**)&d_off)) != MZK_OK) break;
-    if ((rc = ws_get(WS_MISC_E, (m + 1) * 8, (void**)&d_ioff)) != MZK_OK) break;
-    if ((rc = ws_get(WS_MISC_F, (m + 1) * 4, (void**)&d_ns)) != MZK_OK) break;
+    if ((rc = ws.get(WS_MISC_D, (n + 1) * 8, (void**)&d_off)) != MZK_OK) break;
+    if ((rc = ws.get(WS_MISC_E, (m + 1) * 8, (void**)&d_ioff)) != MZK_OK) break;
+    if ((rc = ws.get(WS_MISC_F, (m + 1) * 4, (void**)&d_ns)) != MZK_OK) break;
     if ((leaf_bytes && hipMemcpyAsync(t->d_leaves, leaves, leaf_bytes, hipMemcpyHostToDevice, s) != hipSuccess) ||
         hipMemcpyAsync(d_off, offsets, (n + 1) * 8, hipMemcpyHostToDevice, s) != hipSuccess ||
         hipMemcpyAsync(d_ioff, t->item_off.data(), (m + 1) * 8, hipMemcpyHostToDevice, s) != hipSuccess ||
@@ -748,6 +749,7 @@ static int merkle_build_ragged(const uint8_t* leaves, const uint64_t* offsets, s
 
 static int merkle_build(int kind, int fid, const void* src, bool src_on_device, size_t leaf_bytes, const uint64_t* offsets, size_t n,
                         mzk_merkle** out, hipStream_t s, const uint8_t* neg_host) {
+  WsFrame ws("merkle_build");
   if (!out) { set_error("merkle: null output handle"); return MZK_E_ARG; }
   *out = nullptr;
   if (n == 0) { set_error("merkle: empty leaf set (Merkle::commit recurses forever on it, merkle.rs:20-22)"); return MZK_E_LENGTH; }
@@ -784,13 +786,13 @@ static int merkle_build(int kind, int fid, const void* src, bool src_on_device, 
     if (n > 1 && hipMalloc((void**)&t->d_nodes, (n - 1) * 32) != hipSuccess) { set_error("merkle: hipMalloc failed"); rc = MZK_E_HIP; break; }
     if (kind == 1) {
       t->offsets.assign(offsets, offsets + n + 1);
-      if ((rc = ws_get(WS_MISC_D, (n + 1) * 8, (void**)&d_off)) != MZK_OK) break;
+      if ((rc = ws.get(WS_MISC_D, (n + 1) * 8, (void**)&d_off)) != MZK_OK) break;
       if (hipMemcpyAsync(d_off, offsets, (n + 1) * 8, hipMemcpyHostToDevice, s) != hipSuccess) { set_error("merkle: offset copy failed"); rc = MZK_E_HIP; break; }
     }
     u8* d_neg = nullptr;
     if (kind == 0 && neg_host) {
       t->neg.assign(neg_host, neg_host + n);
-      if ((rc = ws_get(WS_MISC_E, n, (void**)&d_neg)) != MZK_OK) break;
+      if ((rc = ws.get(WS_MISC_E, n, (void**)&d_neg)) != MZK_OK) break;
       if (hipMemcpyAsync(d_neg, neg_host, n, hipMemcpyHostToDevice, s) != hipSuccess) { set_error("merkle: sign copy failed"); rc = MZK_E_HIP; break; }
     }
     rc = merkle_hash_levels(kind, fid, t->d_leaves, d_off, n, t->d_nodes, s, d_neg);
@@ -888,6 +890,7 @@ int mzk_merkle_open(const mzk_merkle* t, size_t index, uint8_t* path, size_t str
     return mzk_merkle_open_batch(t, &idx64, 1, path, stride, path_len, depth);
   }
   MZK_ENTER();
+  WsFrame ws("mzk_merkle_open");
   MerkleScope ms(t);
   MZK_TRY(ms.rc);
   hipStream_t s = ms.s;
@@ -920,7 +923,7 @@ int mzk_merkle_open(const mzk_merkle* t, size_t index, uint8_t* path, size_t str
     path_len[k] = l1;
     if (t->depth > 1) {
       u64* d_out;
-      MZK_TRY(ws_get(WS_MISC_C, (size_t)t->depth * 32, (void**)&d_out));
+      MZK_TRY(ws.get(WS_MISC_C, (size_t)t->depth * 32, (void**)&d_out));
       hipLaunchKernelGGL(k_merkle_gather, dim3(1), dim3(64), 0, s, (const u64*)t->d_nodes, t->m, p, t->depth, d_out);
       MZK_HIP(hipGetLastError());
       uint8_t tmp[64 * 32];
@@ -942,7 +945,7 @@ int mzk_merkle_open(const mzk_merkle* t, size_t index, uint8_t* path, size_t str
   }
   if (t->depth > 1) {
     u64* d_out;
-    MZK_TRY(ws_get(WS_MISC_C, (size_t)t->depth * 32, (void**)&d_out));
+    MZK_TRY(ws.get(WS_MISC_C, (size_t)t->depth * 32, (void**)&d_out));
     hipLaunchKernelGGL(k_merkle_gather, dim3(1), dim3(64), 0, s, (const u64*)t->d_nodes, t->n, index, t->depth, d_out);
     MZK_HIP(hipGetLastError());
     uint8_t tmp[64 * 32];
@@ -973,6 +976,7 @@ int mzk_merkle_open_batch(const mzk_merkle* t, const uint64_t* indices, size_t c
   for (size_t q = 0; q < count; q++)
     if (indices[q] >= t->n) { set_error("merkle_open: index %llu out of range", (unsigned long long)indices[q]); return MZK_E_LENGTH; }
   MZK_ENTER();
+  WsFrame ws("mzk_merkle_open_batch");
   MerkleScope ms(t);
   MZK_TRY(ms.rc);
   hipStream_t s = ms.s;
@@ -981,7 +985,7 @@ int mzk_merkle_open_batch(const mzk_merkle* t, const uint64_t* indices, size_t c
   const size_t node_words64 = count * (size_t)(t->depth - 1) * 4;
   u64 *d_idx, *d_on;
   u32* d_ol;
-  MZK_TRY(ws_get(WS_MISC_C, count * 8 + node_words64 * 8 + count * (size_t)lw * 4 + 64, (void**)&d_idx));
+  MZK_TRY(ws.get(WS_MISC_C, count * 8 + node_words64 * 8 + count * (size_t)lw * 4 + 64, (void**)&d_idx));
   d_on = d_idx + count;
   d_ol = (u32*)(d_on + node_words64);
   MZK_HIP(hipMemcpyAsync(d_idx, indices, count * 8, hipMemcpyHostToDevice, s));
@@ -1045,6 +1049,7 @@ int mzk_merkle_open_multi(const mzk_merkle* const* trees, size_t n_trees, const 
   if (total == 0) return MZK_OK;
   if (stride < 32) { set_error("merkle_open: stride < 32"); return MZK_E_LENGTH; }
   MZK_ENTER();
+  WsFrame ws("mzk_merkle_open_multi");
   MerkleScope ms(first);
   MZK_TRY(ms.rc);
   hipStream_t s = ms.s;
@@ -1053,7 +1058,7 @@ int mzk_merkle_open_multi(const mzk_merkle* const* trees, size_t n_trees, const 
   WsGuard wsg(s);
   u64 *d_idx, *d_on;
   u32* d_ol;
-  MZK_TRY(ws_get(WS_MISC_C, total * 8 + total_nodes * 8 + total_leaf_words * 4 + 64, (void**)&d_idx));
+  MZK_TRY(ws.get(WS_MISC_C, total * 8 + total_nodes * 8 + total_leaf_words * 4 + 64, (void**)&d_idx));
   d_on = d_idx + total;
   d_ol = (u32*)(d_on + total_nodes);
   MZK_HIP(hipMemcpyAsync(d_idx, indices, total * 8, hipMemcpyHostToDevice, s));
@@ -1121,6 +1126,7 @@ void mzk_merkle_free(mzk_merkle* t) {
 // retained, the node levels live in workspace.  root: 32 bytes (n >= 2) or the leaf bytes (n == 1; cap >= 41).
 int mzk_merkle_commit_field_dev(int field_id, const void* d_elems, size_t n, uint8_t* root, size_t cap, size_t* root_len, void* stream) {
   MZK_ENTER();
+  WsFrame ws("mzk_merkle_commit_field_dev");
   WsGuard wsg((hipStream_t)stream);
   MZK_TRY(field_check_gl(field_id, "merkle"));
   if (n == 0) { set_error("merkle: empty leaf set (Merkle::commit recurses forever on it, merkle.rs:20-22)"); return MZK_E_LENGTH; }
@@ -1145,7 +1151,7 @@ int mzk_merkle_commit_field_dev(int field_id, const void* d_elems, size_t n, uin
   }
   if (cap < 32) { set_error("merkle: root buffer too small"); return MZK_E_LENGTH; }
   u64* d_nodes;
-  MZK_TRY(ws_get(WS_MERKLE_NODES, (n - 1) * 32, (void**)&d_nodes));
+  MZK_TRY(ws.get(WS_MERKLE_NODES, (n - 1) * 32, (void**)&d_nodes));
   RootMailbox mb;
   bool mailed = false;
   MZK_TRY(merkle_mailbox(&mb));
@@ -1158,6 +1164,7 @@ int mzk_merkle_commit_field_dev(int field_id, const void* d_elems, size_t n, uin
 // trees, so the latency-bound upper levels of the trees run side by side.
 int mzk_merkle_commit_field_batch_dev(int field_id, const void* d_elems, size_t n, size_t batch, uint8_t* roots, void* stream) {
   MZK_ENTER();
+  WsFrame ws("mzk_merkle_commit_field_batch_dev");
   WsGuard wsg((hipStream_t)stream);
   MZK_TRY(field_check(field_id, "merkle"));
   if (batch == 0) return MZK_OK;
@@ -1168,13 +1175,14 @@ int mzk_merkle_commit_field_batch_dev(int field_id, const void* d_elems, size_t 
   hipStream_t s = (hipStream_t)stream;
   const size_t total = n * batch;
   u64* d_nodes;
-  MZK_TRY(ws_get(WS_MERKLE_NODES, (total - batch) * 32, (void**)&d_nodes));
+  MZK_TRY(ws.get(WS_MERKLE_NODES, (total - batch) * 32, (void**)&d_nodes));
   MZK_TRY(merkle_hash_levels(0, field_id, d_elems, nullptr, total, d_nodes, s, nullptr, batch));
   MZK_TRY(d2h_sync(roots, d_nodes + 4 * (total - 2 * batch), batch * 32, s));
   return MZK_OK;
 }
 int mzk_merkle_commit_field_batch(int field_id, const uint64_t* elems, size_t n, size_t batch, uint8_t* roots) {
   MZK_ENTER();
+  WsFrame ws("mzk_merkle_commit_field_batch");
   MZK_TRY(field_check(field_id, "merkle"));
   if (batch == 0) return MZK_OK;
   if (!elems) { set_error("merkle: null pointer"); return MZK_E_ARG; }
@@ -1182,7 +1190,7 @@ int mzk_merkle_commit_field_batch(int field_id, const uint64_t* elems, size_t n,
   void* d;
   {
     WsGuard wsg(s);
-    MZK_TRY(ws_get(WS_MISC_D, n * batch * field_bytes(field_id) + 16, &d));
+    MZK_TRY(ws.get(WS_MISC_D, n * batch * field_bytes(field_id) + 16, &d));
     MZK_HIP(hipMemcpyAsync(d, elems, n * batch * field_bytes(field_id), hipMemcpyHostToDevice, s));
   }
   return mzk_merkle_commit_field_batch_dev(field_id, d, n, batch, roots, s);
@@ -1230,6 +1238,7 @@ static int fri_commit_rounds(int field_id, const uint64_t* codeword, const uint8
                              int num_rounds, mzk_fri_challenge_fn challenge, void* user, uint8_t* roots, uint64_t* root_len, uint64_t* codewords_out,
                              mzk_merkle** trees_out, bool on_device, bool signed_form) {
   MZK_ENTER();
+  WsFrame ws("fri_commit_rounds");
   // the Goldilocks ids: every form but mzk_fri_commit_signed, and without signs (an extension element's coefficients carry their own
   // signs in the reference; parity is defined on canonical coefficients only -- DESIGN.md section 9e)
   MZK_TRY(signed_form ? field_check(field_id, "fri_commit") : field_check_gl(field_id, "fri_commit"));
@@ -1270,8 +1279,8 @@ static int fri_commit_rounds(int field_id, const uint64_t* codeword, const uint8
     d_all = (uint8_t*)blk;
     d_nodes = (u64*)((uint8_t*)blk + cw_bytes);
   } else {
-    MZK_TRY(ws_get(WS_NTT_IO_A, total * esz, (void**)&d_all));
-    MZK_TRY(ws_get(WS_MERKLE_NODES, n * 32, (void**)&d_nodes));
+    MZK_TRY(ws.get(WS_NTT_IO_A, total * esz, (void**)&d_all));
+    MZK_TRY(ws.get(WS_MERKLE_NODES, n * 32, (void**)&d_nodes));
   }
   struct DropRef {        // every exit path: the handles already handed out keep the block alive, otherwise it goes
     mzk_merkle::SharedBlock* b;
@@ -1280,7 +1289,7 @@ static int fri_commit_rounds(int field_id, const uint64_t* codeword, const uint8
   MZK_HIP(hipMemcpyAsync(d_all, codeword, n * esz, on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s));
   u8* d_neg = nullptr;
   if (negative) {     // round 0 hashes bincode of the UNSANITIZED elements (fri.rs:160-166); the fold sanitizes (fri.rs:190)
-    MZK_TRY(ws_get(WS_MISC_E, n, (void**)&d_neg));
+    MZK_TRY(ws.get(WS_MISC_E, n, (void**)&d_neg));
     MZK_HIP(hipMemcpyAsync(d_neg, negative, n, hipMemcpyHostToDevice, s));
   }
   uint64_t alpha[4];
@@ -1375,6 +1384,7 @@ int mzk_merkle_leaves(const mzk_merkle* t, const uint64_t* indices, size_t count
     if (indices[q] >= t->n) { set_error("merkle_leaves: index %llu out of range", (unsigned long long)indices[q]); return MZK_E_LENGTH; }
   if (count == 0) return MZK_OK;
   MZK_ENTER();
+  WsFrame ws("mzk_merkle_leaves");
   MerkleScope ms(t);
   MZK_TRY(ms.rc);
   hipStream_t s = ms.s;
@@ -1382,7 +1392,7 @@ int mzk_merkle_leaves(const mzk_merkle* t, const uint64_t* indices, size_t count
   const size_t esz = field_bytes(t->field);
   const int lw = (int)field_words(t->field);
   u64* d_idx;
-  MZK_TRY(ws_get(WS_MISC_C, count * 8 + count * esz + 64, (void**)&d_idx));
+  MZK_TRY(ws.get(WS_MISC_C, count * 8 + count * esz + 64, (void**)&d_idx));
   u32* d_out = (u32*)(d_idx + count);
   MZK_HIP(hipMemcpyAsync(d_idx, indices, count * 8, hipMemcpyHostToDevice, s));
   hipLaunchKernelGGL(k_gather_leaves, dim3((unsigned)((count * lw + 255) / 256)), dim3(256), 0, s, (const u32*)t->d_leaves, lw, (const u64*)d_idx, count, d_out);
@@ -1752,6 +1762,7 @@ static int fri_prove_impl(int field_id, const void* src, const void* negative, b
     return MZK_E_RANGE;
   }
   MZK_ENTER();
+  WsFrame ws("fri_prove_impl");
   hipStream_t s = on_device ? s_in : ctx().stream;
   WsGuard wsg(s);
   const int R = L.rounds, nl = field_limbs64(field_id);
@@ -1767,7 +1778,7 @@ static int fri_prove_impl(int field_id, const void* src, const void* negative, b
   const size_t o_alpha = o_tx + al((gl ? mzk_tx::fri_transcript_cap_gl(L, nl) : mzk_tx::fri_transcript_cap(L, nl)) + 16), o_seen = o_alpha + al(32 * (size_t)R);
   const size_t o_proof = o_seen + al((L.last_len + 31) / 32 * 4), total = o_proof + (on_device ? 0 : al(L.total));
   uint8_t* blk;
-  MZK_TRY(ws_get(WS_MISC_F, total, (void**)&blk));
+  MZK_TRY(ws.get(WS_MISC_F, total, (void**)&blk));
   uint8_t* cw = blk;
   uint8_t* nodes = blk + o_nodes;
   uint8_t* proof = on_device ? (uint8_t*)proof_out : blk + o_proof;

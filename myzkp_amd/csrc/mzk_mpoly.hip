@@ -332,6 +332,7 @@ static inline unsigned mp_grid(size_t n, unsigned per) { return (unsigned)((n + 
 template <class P>
 static int mp_compose_dev(int fid, const uint64_t* term_coefs, const uint32_t* term_exps, const size_t* term_offsets, size_t nc, size_t nv,
                           const void* d_point, const size_t* point_offsets, void* d_out, size_t out_stride, size_t* out_lens, hipStream_t s) {
+  WsFrame ws("mp_compose_dev");
   MpPlan pl;
   MZK_TRY(mp_plan(fid, term_exps, term_offsets, nc, nv, point_offsets, &pl));
   if (nc == 0) return MZK_OK;
@@ -358,10 +359,10 @@ static int mp_compose_dev(int fid, const uint64_t* term_coefs, const uint32_t* t
   const size_t b_tab = b_ops + b_off + b_coef;
   char *d_tab, *d_E, *d_V;
   unsigned long long* d_lens;
-  MZK_TRY(ws_get(WS_MISC_C, b_tab ? b_tab : 16, (void**)&d_tab));
-  MZK_TRY(ws_get(WS_MISC_D, nc * 8, (void**)&d_lens));
-  MZK_TRY(ws_get(WS_MISC_A, (nv ? nv : 1) * N * esz, (void**)&d_E));
-  MZK_TRY(ws_get(WS_MISC_B, nc * N * esz, (void**)&d_V));
+  MZK_TRY(ws.get(WS_MISC_C, b_tab ? b_tab : 16, (void**)&d_tab));
+  MZK_TRY(ws.get(WS_MISC_D, nc * 8, (void**)&d_lens));
+  MZK_TRY(ws.get(WS_MISC_A, (nv ? nv : 1) * N * esz, (void**)&d_E));
+  MZK_TRY(ws.get(WS_MISC_B, nc * N * esz, (void**)&d_V));
   std::vector<char> tab(b_tab);
   if (!pg.ops.empty()) memcpy(tab.data(), pg.ops.data(), pg.ops.size() * sizeof(MpOp));
   memcpy(tab.data() + b_ops, pg.off.data(), pg.off.size() * 4);
@@ -422,6 +423,7 @@ static int mp_lincomb_check(int fid, const size_t* offsets, size_t count, const 
 template <class P>
 static int mp_lincomb_dev(int fid, const void* d_polys, const size_t* offsets, size_t count, const uint64_t* weights, const size_t* shifts, void* d_out,
                           size_t out_cap, size_t* out_len, hipStream_t s) {
+  WsFrame ws("mp_lincomb_dev");
   *out_len = 0;
   if (out_cap == 0) return MZK_OK;
   std::vector<MpLcItem> items(count);
@@ -432,7 +434,7 @@ static int mp_lincomb_dev(int fid, const void* d_polys, const size_t* offsets, s
     items[i].pad[0] = items[i].pad[1] = 0;
   }
   char* d_tab;
-  MZK_TRY(ws_get(WS_MISC_C, (count ? count : 1) * sizeof(MpLcItem) + 16, (void**)&d_tab));
+  MZK_TRY(ws.get(WS_MISC_C, (count ? count : 1) * sizeof(MpLcItem) + 16, (void**)&d_tab));
   unsigned long long* d_len = (unsigned long long*)d_tab;
   MpLcItem* d_items = (MpLcItem*)(d_tab + 16);
   auto fail = [&](int rc) { (void)hipStreamSynchronize(s); return rc; };
@@ -480,6 +482,7 @@ int mzk_mpoly_compose_dev(int field_id, const uint64_t* term_coefs, const uint32
 int mzk_mpoly_compose(int field_id, const uint64_t* term_coefs, const uint32_t* term_exps, const size_t* term_offsets, size_t n_constraints,
                       size_t n_vars, const uint64_t* point, const size_t* point_offsets, uint64_t* out, size_t out_stride, size_t* out_lens) {
   MZK_ENTER();
+  WsFrame ws("mzk_mpoly_compose");
   MpPlan pl;
   MZK_TRY(mp_plan(field_id, term_exps, term_offsets, n_constraints, n_vars, point_offsets, &pl));
   if (n_constraints == 0) return MZK_OK;
@@ -493,8 +496,8 @@ int mzk_mpoly_compose(int field_id, const uint64_t* term_coefs, const uint32_t* 
   hipStream_t s = ctx().stream;
   WsGuard wsg(s);
   char *d_p, *d_o;
-  MZK_TRY(ws_get(WS_MISC_E, (np ? np : 1) * esz, (void**)&d_p));
-  MZK_TRY(ws_get(WS_MISC_F, (n_constraints * out_stride + 1) * esz, (void**)&d_o));
+  MZK_TRY(ws.get(WS_MISC_E, (np ? np : 1) * esz, (void**)&d_p));
+  MZK_TRY(ws.get(WS_MISC_F, (n_constraints * out_stride + 1) * esz, (void**)&d_o));
   // offsets relative to the staged copy
   std::vector<size_t> rel(n_vars + 1, 0);
   for (size_t i = 0; i <= n_vars && n_vars; i++) rel[i] = point_offsets[i] - p0;
@@ -519,6 +522,7 @@ int mzk_poly_lincomb_dev(int field_id, const void* d_polys, const size_t* offset
 int mzk_poly_lincomb(int field_id, const uint64_t* polys, const size_t* offsets, size_t count, const uint64_t* weights, const size_t* shifts,
                      uint64_t* out, size_t out_cap, size_t* out_len) {
   MZK_ENTER();
+  WsFrame ws("mzk_poly_lincomb");
   MZK_TRY(mp_lincomb_check(field_id, offsets, count, weights, shifts, out_cap, out, out_len));
   const HostField* hf = host_field(field_id);
   const size_t esz = field_bytes(field_id), p0 = count ? offsets[0] : 0, np = count ? offsets[count] - p0 : 0;
@@ -528,8 +532,8 @@ int mzk_poly_lincomb(int field_id, const uint64_t* polys, const size_t* offsets,
   hipStream_t s = ctx().stream;
   WsGuard wsg(s);
   char *d_p, *d_o;
-  MZK_TRY(ws_get(WS_MISC_E, (np ? np : 1) * esz, (void**)&d_p));
-  MZK_TRY(ws_get(WS_MISC_F, (out_cap ? out_cap : 1) * esz, (void**)&d_o));
+  MZK_TRY(ws.get(WS_MISC_E, (np ? np : 1) * esz, (void**)&d_p));
+  MZK_TRY(ws.get(WS_MISC_F, (out_cap ? out_cap : 1) * esz, (void**)&d_o));
   std::vector<size_t> rel(count + 1, 0);
   for (size_t i = 0; i <= count; i++) rel[i] = count ? offsets[i] - p0 : 0;
   if (np) MZK_HIP(hipMemcpyAsync(d_p, polys + p0 * hf->nl, np * esz, hipMemcpyHostToDevice, s));

@@ -1417,9 +1417,10 @@ __global__ __launch_bounds__(128) void k_srs_window_step(u32* __restrict__ state
   xyzz_gstore(state, i, p);
 }
 int msm_build_tables(const void* d_points_mont, size_t n, void* d_tables, int window_bits, hipStream_t s) {
+  WsFrame ws("msm_build_tables");
   if (n == 0) return MZK_OK;
   u32* state;
-  MZK_TRY(ws_get(WS_XYZZ_TMP, n * 128, (void**)&state));
+  MZK_TRY(ws.get(WS_XYZZ_TMP, n * 128, (void**)&state));
   const unsigned blocks = (unsigned)((n + 127) / 128);
   MZK_HIP(hipMemcpyAsync(d_tables, d_points_mont, n * 64, hipMemcpyDeviceToDevice, s));   // window 0
   hipLaunchKernelGGL(k_srs_state_init, dim3(blocks), dim3(128), 0, s, (const u32*)d_points_mont, n, state);
@@ -1490,12 +1491,23 @@ static int sort_records(const MsmPlan& P, const SortBufs& a, hipStream_t s) {
   return MZK_OK;
 }
 
+// one request per slot that the plan sizes
+static int msm_take_ws(WsFrame& ws, const MsmWsBytes& b, MsmWs* w) {
+  const struct { WsSlot slot; size_t bytes; u32** p; } req[] = {
+      {WS_MSM_POINTS, b.points, &w->points}, {WS_MSM_COUNTS, b.counts, &w->counts}, {WS_MSM_OFFSETS, b.offsets, &w->offsets},
+      {WS_MSM_CURSOR, b.cursor, &w->cursor}, {WS_MSM_ENTRIES, b.entries, &w->entries}, {WS_MSM_SCAN, b.scan, &w->scan},
+      {WS_MSM_BUCKETS, b.buckets, &w->buckets}, {WS_MSM_SLOTS, b.slots, &w->slots}, {WS_MSM_WGHIST, b.wghist, &w->wghist}, {WS_MSM_OUT, b.out, &w->out}};
+  for (const auto& r : req)
+    if (r.bytes) MZK_TRY(ws.get(r.slot, r.bytes, (void**)r.p));
+  return MZK_OK;
+}
 // Executes msm_plan (mzk_msm_plan.h: point_kind, layout, path, workspace).
 // points_ready (optional, plain points only): called once, after the digit sort has been enqueued and before the first kernel
 // that reads the points -- the host-buffer entry point stages the points onto the device there, so that the transfer of the
 // 64 n bytes of points runs under the sort of the scalars instead of in front of it.
 int msm_dev_impl(const void* d_scalars, const void* d_points, size_t n, int point_kind, size_t table_stride, void* d_out,
                  bool out_partial_xyzz, hipStream_t s, const std::function<int()>* points_ready, const MsmChunkCtx* cc) {
+  WsFrame ws("msm_dev_impl");
   if (!d_out || ((!d_scalars || !d_points) && n)) { set_error("msm: null pointer"); return MZK_E_ARG; }
   // chunk mode (msm_chunked_impl): the pairs [i0, i0 + n) of a problem of n_total pairs; layout by the whole problem, per-chunk buffers
   // sized for the largest chunk, returns with the chunk's buckets summed (no reduction)
@@ -1508,16 +1520,14 @@ int msm_dev_impl(const void* d_scalars, const void* d_points, size_t n, int poin
   const size_t n_shape = cc ? cc->n_total : n, i0 = cc ? cc->i0 : 0;
   const MsmPlan P = msm_plan(n, n_shape, cc ? cc->n_alloc : n, point_kind, table_stride, ctx().num_cu, cc ? cc->K : 0, msm_knobs());
   if (P.err != MZK_OK) { set_error("%s", P.msg); return P.err; }
-  u32 *pm = nullptr, *counts = nullptr, *offsets = nullptr, *ranks = nullptr, *entries = nullptr, *scan = nullptr, *buckets = nullptr,
-      *slots = nullptr, *wghist = nullptr, *wsum = nullptr;
-  // one request per slot; in chunk mode the per-chunk slots hold one region (of `words`) per chunk, this chunk's is the k-th
-  const struct { WsSlot slot; size_t bytes; u32** p; size_t words; } req[] = {
-      {WS_MSM_POINTS, P.ws.points, &pm, 0}, {WS_MSM_COUNTS, P.ws.counts, &counts, 0}, {WS_MSM_OFFSETS, P.ws.offsets, &offsets, P.NBtot + 1},
-      {WS_MSM_CURSOR, P.ws.cursor, &ranks, 0}, {WS_MSM_ENTRIES, P.ws.entries, &entries, P.alloc.E}, {WS_MSM_SCAN, P.ws.scan, &scan, 0},
-      {WS_MSM_BUCKETS, P.ws.buckets, &buckets, P.NB * 32}, {WS_MSM_SLOTS, P.ws.slots, &slots, P.slot_region_words},
-      {WS_MSM_WGHIST, P.ws.wghist, &wghist, 0}, {WS_MSM_OUT, P.ws.out, &wsum, 0}};
-  for (const auto& r : req)
-    if (r.bytes) { MZK_TRY(ws_get(r.slot, r.bytes, (void**)r.p)); *r.p += (cc ? cc->k : 0) * r.words; }
+  // the caller's slots in chunk mode (every chunk's plan asks for the same bytes), this call's own otherwise
+  MsmWs w = {};
+  if (cc) w = *cc->ws;
+  else MZK_TRY(msm_take_ws(ws, P.ws, &w));
+  // in chunk mode the per-chunk slots hold one region per chunk, this chunk's is the k-th
+  const size_t k = cc ? cc->k : 0;
+  u32 *pm = w.points, *counts = w.counts, *offsets = w.offsets + k * (P.NBtot + 1), *ranks = w.cursor, *entries = w.entries + k * P.alloc.E, *scan = w.scan,
+      *buckets = w.buckets + k * P.NB * 32, *slots = w.slots + k * P.slot_region_words, *wghist = w.wghist, *wsum = w.out;
   // (a chunk's entries count from its first pair: every table row / the endomorphism images sit at the same distance behind it)
   const u32* pts = (pm ? pm : (const u32*)d_points) + i0 * 16;
   bool prepared = false;
@@ -1631,6 +1641,7 @@ bool msm_chunkable(size_t n_total, int point_kind, size_t table_stride) { return
 // affine point as the one-piece call.
 int msm_chunked_impl(const MsmChunk* chunks, int K, const void* d_points, size_t n_total, int point_kind, size_t table_stride, void* d_out,
                      bool out_partial_xyzz, hipStream_t s, const std::function<int(int)>* before_chunk) {
+  WsFrame ws("msm_chunked_impl");
   if (!chunks || K < 1 || K > 8 || !d_out || !d_points) { set_error("msm_chunked: bad argument"); return MZK_E_ARG; }
   size_t n_alloc = 0, covered = 0;
   for (int k = 0; k < K; k++) {
@@ -1639,19 +1650,22 @@ int msm_chunked_impl(const MsmChunk* chunks, int K, const void* d_points, size_t
     n_alloc = chunks[k].n > n_alloc ? chunks[k].n : n_alloc;
   }
   if (covered != n_total || !msm_chunkable(n_total, point_kind, table_stride)) { set_error("msm_chunked: chunks do not cover a chunkable problem"); return MZK_E_ARG; }
+  // the plan every chunk follows (its largest chunk's): layout, bucket array.  Its slots are taken here, once, and lent to the chunks:
+  // K regions in the per-chunk ones, and the bucket array they leave behind is the one summed below.
+  const MsmPlan P = msm_plan(n_alloc, n_total, n_alloc, point_kind, table_stride, ctx().num_cu, K, msm_knobs());
+  if (P.err != MZK_OK) { set_error("%s", P.msg); return P.err; }
+  MsmWs w = {};
+  MZK_TRY(msm_take_ws(ws, P.ws, &w));
+  MZK_TRY(ws.get(WS_MSM_OUT, (size_t)MAX_WINDOWS * 128, (void**)&w.out));
   for (int k = 0; k < K; k++) {
     // before_chunk(k): the caller brings chunk k's inputs onto the device (a host-buffer entry point copies them here, blocking the
     // host while the GPU works on chunk k - 1) and records chunks[k].ready
     if (before_chunk) MZK_TRY((*before_chunk)(k));
     if (chunks[k].ready) MZK_HIP(hipStreamWaitEvent(s, chunks[k].ready, 0));
-    const MsmChunkCtx cc{k, K, chunks[k].i0, n_total, n_alloc};
+    const MsmChunkCtx cc{&w, k, K, chunks[k].i0, n_total, n_alloc};
     MZK_TRY(msm_dev_impl(chunks[k].d_scalars, d_points, chunks[k].n, point_kind, table_stride, d_out, out_partial_xyzz, s, nullptr, &cc));
   }
-  // the plan every chunk followed (its largest chunk's): layout, bucket array
-  const MsmPlan P = msm_plan(n_alloc, n_total, n_alloc, point_kind, table_stride, ctx().num_cu, K, msm_knobs());
-  u32 *buckets, *wsum;
-  MZK_TRY(ws_get(WS_MSM_BUCKETS, P.ws.buckets, (void**)&buckets));       // (the chunks' request: same size, same buffer)
-  MZK_TRY(ws_get(WS_MSM_OUT, (size_t)MAX_WINDOWS * 128, (void**)&wsum));
+  u32 *buckets = w.buckets, *wsum = w.out;
   if (K > 1) {
     prof_begin(s, MZK_PH_MSM_SEG_COMBINE);
     hipLaunchKernelGGL(k_fold_bucket_sets, dim3((unsigned)((P.NB + 127) / 128)), dim3(128), 0, s, buckets, P.NB, K);
@@ -1822,6 +1836,7 @@ int msm_many_dev_impl(const void* d_scalars, size_t n, size_t stride_elems, size
   if (by_coefs < per_pass) per_pass = by_coefs;
   if (per_pass < 1) per_pass = 1;
   for (size_t first = 0; first < count; first += per_pass) {
+    WsFrame ws("msm_many_dev_impl");      // one lease per pass: every pass asks again, none for more than the first
     const size_t cnt = (count - first < per_pass) ? count - first : per_pass;
     const u32* sc = (const u32*)d_scalars + first * stride_elems * 8;
     u32* out = (u32*)d_out + first * 16;
@@ -1836,15 +1851,15 @@ int msm_many_dev_impl(const void* d_scalars, size_t n, size_t stride_elems, size
     const size_t max_heavy = (T + NBtot) / HEAVY_SLOTS_SORT1 + 1;
     const size_t heavy_words = heavy_total_words(max_heavy);
     u32 *offs, *compact, *entries, *scan_tmp, *buckets, *slots;
-    MZK_TRY(ws_get(WS_MSM_COUNTS, (ncnt + 1) * 4, (void**)&offs));
-    MZK_TRY(ws_get(WS_MSM_ENTRIES, E_max * 4, (void**)&entries));
-    MZK_TRY(ws_get(WS_MSM_SCAN, scan_scratch_words(ncnt) * 4, (void**)&scan_tmp));
-    MZK_TRY(ws_get(WS_MSM_BUCKETS, NBtot * 128, (void**)&buckets));
-    MZK_TRY(ws_get(WS_MSM_SLOTS, nslots * SLOT_WORDS * 4 + heavy_words * 4, (void**)&slots));
+    MZK_TRY(ws.get(WS_MSM_COUNTS, (ncnt + 1) * 4, (void**)&offs));
+    MZK_TRY(ws.get(WS_MSM_ENTRIES, E_max * 4, (void**)&entries));
+    MZK_TRY(ws.get(WS_MSM_SCAN, scan_scratch_words(ncnt) * 4, (void**)&scan_tmp));
+    MZK_TRY(ws.get(WS_MSM_BUCKETS, NBtot * 128, (void**)&buckets));
+    MZK_TRY(ws.get(WS_MSM_SLOTS, nslots * SLOT_WORDS * 4 + heavy_words * 4, (void**)&slots));
     compact = offs;
     u32* tails = nullptr;                   // one-kernel sort only: end of every polynomial's real entries (bucket_end)
-    if (nch > 1) MZK_TRY(ws_get(WS_MSM_OFFSETS, (NBtot + 1) * 4, (void**)&compact));
-    else MZK_TRY(ws_get(WS_MSM_OFFSETS, cnt * 4, (void**)&tails));
+    if (nch > 1) MZK_TRY(ws.get(WS_MSM_OFFSETS, (NBtot + 1) * 4, (void**)&compact));
+    else MZK_TRY(ws.get(WS_MSM_OFFSETS, cnt * 4, (void**)&tails));
     u32* heavy = slots + nslots * SLOT_WORDS;
     prof_begin(s, MZK_PH_MSM_SORT);
     MZK_HIP(hipMemsetAsync(heavy, 0, (size_t)HEAVY_HDR * 4, s));
@@ -1934,17 +1949,18 @@ __global__ __launch_bounds__(64) void k_direct_chain(const u32* __restrict__ row
   }
 }
 int msm_build_direct(const void* d_points_mont, size_t n, int c, void* d_direct, hipStream_t s) {
+  WsFrame ws("msm_build_direct");
   if (n == 0) return MZK_OK;
   const int nwin = msm_table_windows(c), M = 1 << (c - 1);
   const size_t rows = (size_t)nwin * n;
   // window tables T[w][i] = 2^(c w) P_i of this width (scratch), then the multiples of every row in slices of <= 2^21 records
   u32 *tables, *tmp;
-  MZK_TRY(ws_get(WS_MISC_C, rows * 64, (void**)&tables));
+  MZK_TRY(ws.get(WS_MISC_C, rows * 64, (void**)&tables));
   MZK_TRY(msm_build_tables(d_points_mont, n, tables, c, s));
   size_t slice = ((size_t)1 << 21) / (size_t)M;
   if (slice < 64) slice = 64;
   if (slice > rows) slice = rows;
-  MZK_TRY(ws_get(WS_MISC_D, slice * (size_t)M * 128, (void**)&tmp));
+  MZK_TRY(ws.get(WS_MISC_D, slice * (size_t)M * 128, (void**)&tmp));
   for (size_t r0 = 0; r0 < rows; r0 += slice) {
     const size_t cnt = (rows - r0 < slice) ? rows - r0 : slice;
     hipLaunchKernelGGL(k_direct_chain, dim3((unsigned)((cnt + 63) / 64)), dim3(64), 0, s, (const u32*)tables + r0 * 16, cnt, M, tmp);
@@ -2046,6 +2062,7 @@ int msm_direct_many_dev_impl(const void* d_scalars, size_t n, size_t stride_elem
   const size_t items = n * (size_t)msm_table_windows(c);
   const size_t per_pass = (size_t)1 << 12;                           // polynomials per pass: cnt x parts <= ~4096 workgroups of lane partials (36 KiB each: <= 150 MiB)
   for (size_t first = 0; first < count; first += per_pass) {
+    WsFrame ws("msm_direct_many_dev_impl");      // one lease per pass: every pass asks again, none for more than the first
     const size_t cnt = (count - first < per_pass) ? count - first : per_pass;
     // workgroups per polynomial: one round of resident workgroups over the batch (three 256-lane workgroups per CU at the
     // kernel's VGPR count), at least one, at most one per 256 items, and at most 64 (k_direct_fold / k_direct_finish add them)
@@ -2059,8 +2076,8 @@ int msm_direct_many_dev_impl(const void* d_scalars, size_t n, size_t stride_elem
     size_t groups = 0;
     if (parts > (size_t)DIRECT_FINISH_PARTS) for (groups = 2; groups * groups < parts; groups++) {}
     u32 *slots, *scratch;
-    MZK_TRY(ws_get(WS_MSM_SLOTS, cnt * (parts + groups) * DIRECT_THREADS * SLOT_WORDS * 4, (void**)&slots));
-    MZK_TRY(ws_get(WS_MSM_BUCKETS, cnt * 128, (void**)&scratch));
+    MZK_TRY(ws.get(WS_MSM_SLOTS, cnt * (parts + groups) * DIRECT_THREADS * SLOT_WORDS * 4, (void**)&slots));
+    MZK_TRY(ws.get(WS_MSM_BUCKETS, cnt * 128, (void**)&scratch));
     const u32* sc = (const u32*)d_scalars + first * stride_elems * 8;
     const unsigned nwg = (unsigned)(cnt * parts);
     prof_begin(s, MZK_PH_MSM_ACCUMULATE);

@@ -338,8 +338,9 @@ __global__ __launch_bounds__(256) void k_invtest(u64 seed, size_t n, unsigned lo
   if (!ok && (threadIdx.x & 63) == 0) atomicAdd(mismatches, 1ull);
 }
 int selftest_inv_wave_impl(uint64_t seed, size_t n, uint64_t* mismatches_host, hipStream_t s) {
+  WsFrame ws("selftest_inv_wave_impl");
   unsigned long long* cnt;
-  MZK_TRY(ws_get(WS_MISC_A, 64, (void**)&cnt));
+  MZK_TRY(ws.get(WS_MISC_A, 64, (void**)&cnt));
   MZK_HIP(hipMemsetAsync(cnt, 0, 8, s));
   if (n) hipLaunchKernelGGL(k_invtest, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, s, (u64)seed, n, cnt);
   MZK_HIP(hipGetLastError());
@@ -351,14 +352,15 @@ int selftest_inv_wave_impl(uint64_t seed, size_t n, uint64_t* mismatches_host, h
 }
 int synth_g1_impl(uint64_t seed, size_t n, void* d_out, hipStream_t s);
 int selftest_row_ec_impl(uint64_t seed, size_t n, int dbl_reps, uint64_t* mismatches_host, hipStream_t s) {
+  WsFrame ws("selftest_row_ec_impl");
   if (n == 0) { *mismatches_host = 0; return MZK_OK; }
   void *plain, *mont, *a, *b, *so, *dd, *cnt;
-  MZK_TRY(ws_get(WS_MISC_A, n * 64, &plain));
-  MZK_TRY(ws_get(WS_MISC_B, n * 64, &mont));
-  MZK_TRY(ws_get(WS_MISC_C, n * 128, &a));
-  MZK_TRY(ws_get(WS_MISC_D, n * 128, &b));
-  MZK_TRY(ws_get(WS_MISC_E, n * 128, &so));
-  MZK_TRY(ws_get(WS_MISC_F, n * 128 + 64, &dd));
+  MZK_TRY(ws.get(WS_MISC_A, n * 64, &plain));
+  MZK_TRY(ws.get(WS_MISC_B, n * 64, &mont));
+  MZK_TRY(ws.get(WS_MISC_C, n * 128, &a));
+  MZK_TRY(ws.get(WS_MISC_D, n * 128, &b));
+  MZK_TRY(ws.get(WS_MISC_E, n * 128, &so));
+  MZK_TRY(ws.get(WS_MISC_F, n * 128 + 64, &dd));
   cnt = (char*)dd + n * 128;
   MZK_TRY(synth_g1_impl(seed, n, plain, s));
   MZK_TRY(msm_prepare_points(plain, n, mont, nullptr, s));

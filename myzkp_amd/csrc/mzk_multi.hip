@@ -40,6 +40,7 @@ static int pinned_records(uint64_t** out) {
 
 // wait for every context's stream, then fold the W records on context 0 and return the affine point
 static int gather_and_fold(int world, const uint64_t* h_records, uint64_t out_xy[8]) {
+  WsFrame ws("gather_and_fold");
   for (int r = 0; r < world; r++) {
     CtxScope sc(r);
     if (!sc.ok) return MZK_E_ARG;
@@ -50,7 +51,7 @@ static int gather_and_fold(int world, const uint64_t* h_records, uint64_t out_xy
   hipStream_t s = ctx().stream;
   WsGuard wsg(s);
   void* d_rec;
-  MZK_TRY(ws_get(WS_MISC_E, (size_t)world * 128 + 64, &d_rec));
+  MZK_TRY(ws.get(WS_MISC_E, (size_t)world * 128 + 64, &d_rec));
   MZK_HIP(hipMemcpyAsync(d_rec, h_records, (size_t)world * 128, hipMemcpyHostToDevice, s));
   void* d_out = (char*)d_rec + (size_t)world * 128;
   MZK_TRY(msm_fold_partials_impl(d_rec, world, d_out, s));
@@ -115,6 +116,7 @@ static int exchange(Exchange& x, void* const* src, void* const* dst, bool wait_e
   return MZK_OK;
 }
 static int ntt_multi_impl(int fid, const uint64_t* root, const void* const* in, void* const* out, size_t n, int inverse, int layout_in, int layout_out) {
+  WsFrame ws("ntt_multi_impl");
   MZK_TRY(field_check_ntt(fid, "ntt_multi"));
   if (n == 0) return MZK_OK;
   if (n & (n - 1)) { set_error("cannot compute ntt of non-power-of-two sequence"); return MZK_E_NOT_POW2; }
@@ -157,9 +159,9 @@ static int ntt_multi_impl(int fid, const uint64_t* root, const void* const* in, 
     if (hipEventCreateWithFlags(&x.ev[r], hipEventDisableTiming) != hipSuccess) { set_error("ntt_multi: hipEventCreate failed"); rc = MZK_E_HIP; break; }
     made = r + 1;
     WsGuard wsg(ctx().stream);      // the exchanges below write these slots on the context's stream: order them behind whoever used them last
-    rc = ws_get(WS_MISC_D, m * esz, &A[r]);
-    if (rc == MZK_OK) rc = ws_get(WS_MISC_E, m * esz, &B[r]);
-    if (rc == MZK_OK) rc = ws_get(WS_MISC_F, m * esz, &C[r]);
+    rc = ws.get(WS_MISC_D, m * esz, &A[r]);
+    if (rc == MZK_OK) rc = ws.get(WS_MISC_E, m * esz, &B[r]);
+    if (rc == MZK_OK) rc = ws.get(WS_MISC_F, m * esz, &C[r]);
   }
   // a local step on every context: fn(r, stream)
   auto each = [&](auto fn) -> int {
@@ -227,6 +229,7 @@ void mzk_shard_range(size_t n, int rank, int world, size_t* lo, size_t* hi) {
 
 int mzk_msm_g1_bn254_multi(const uint64_t* scalars, const uint64_t* points_xy, size_t n, uint64_t out_xy[8]) {
   MZK_ENTER();
+  WsFrame ws("mzk_msm_g1_bn254_multi");
   if (!out_xy || ((!scalars || !points_xy) && n)) { set_error("msm_multi: null pointer"); return MZK_E_ARG; }
   const int world = ctx_count();
   uint64_t* h_rec;
@@ -240,9 +243,9 @@ int mzk_msm_g1_bn254_multi(const uint64_t* scalars, const uint64_t* points_xy, s
     WsGuard wsg(s);
     void *d_s, *d_p, *d_o;
     const size_t m = hi - lo;
-    MZK_TRY(ws_get(WS_MSM_SCALARS, m ? m * 32 : 16, &d_s));
-    MZK_TRY(ws_get(WS_MISC_A, m ? m * 64 : 16, &d_p));
-    MZK_TRY(ws_get(WS_MISC_B, 256, &d_o));
+    MZK_TRY(ws.get(WS_MSM_SCALARS, m ? m * 32 : 16, &d_s));
+    MZK_TRY(ws.get(WS_MISC_A, m ? m * 64 : 16, &d_p));
+    MZK_TRY(ws.get(WS_MISC_B, 256, &d_o));
     if (m) {
       MZK_HIP(hipMemcpyAsync(d_s, scalars + 4 * lo, m * 32, hipMemcpyHostToDevice, s));
       MZK_HIP(hipMemcpyAsync(d_p, points_xy + 8 * lo, m * 64, hipMemcpyHostToDevice, s));
@@ -321,6 +324,7 @@ int mzk_srs_multi_world(const mzk_srs_multi* h) { return h ? h->world : 0; }
 // [lo_r, min(hi_r, n)) -- already complete when the call is made (the call does not know the producer's stream).
 static int commit_multi(const mzk_srs_multi* h, const uint64_t* host_coef, const void* const* d_coef_shards, size_t n, uint64_t out_xy[8]) {
   MZK_ENTER();
+  WsFrame ws("commit_multi");
   if (!h || !out_xy || (n && !host_coef && !d_coef_shards)) { set_error("commit_srs_multi: null pointer"); return MZK_E_ARG; }
   if (h->world != ctx_count()) { set_error("commit_srs_multi: handle was built for %d contexts, %d are initialised", h->world, ctx_count()); return MZK_E_ARG; }
   if (n > h->n) { set_error("index out of bounds: the len is %zu but the index is %zu", h->n, h->n); return MZK_E_LENGTH; }   // powers[i], polynomial.rs:162
@@ -334,9 +338,9 @@ static int commit_multi(const mzk_srs_multi* h, const uint64_t* host_coef, const
     hipStream_t s = ctx().stream;
     WsGuard wsg(s);
     void *d_s = nullptr, *d_o;
-    MZK_TRY(ws_get(WS_MISC_B, 256, &d_o));
+    MZK_TRY(ws.get(WS_MISC_B, 256, &d_o));
     if (host_coef) {
-      MZK_TRY(ws_get(WS_MSM_SCALARS, m ? m * 32 : 16, &d_s));
+      MZK_TRY(ws.get(WS_MSM_SCALARS, m ? m * 32 : 16, &d_s));
       if (m) MZK_HIP(hipMemcpyAsync(d_s, host_coef + 4 * lo, m * 32, hipMemcpyHostToDevice, s));
     } else if (m) {
       d_s = (void*)d_coef_shards[r];
@@ -365,6 +369,7 @@ int mzk_ntt_multi_dev(int field_id, const uint64_t* root, const void* const* d_i
 // host vector in natural order: context r gets x[r n/W, (r+1) n/W) and returns the same slice of the result
 int mzk_ntt_multi(int field_id, const uint64_t* root, const uint64_t* in, uint64_t* out, size_t n, int inverse) {
   MZK_ENTER();
+  WsFrame ws("mzk_ntt_multi");
   if (n == 0) return MZK_OK;
   if (!in || !out) { set_error("ntt_multi: null pointer"); return MZK_E_ARG; }
   MZK_TRY(field_check_ntt(field_id, "ntt_multi"));
@@ -377,8 +382,8 @@ int mzk_ntt_multi(int field_id, const uint64_t* root, const uint64_t* in, uint64
     if (!sc.ok) return MZK_E_ARG;
     hipStream_t s = ctx().stream;
     WsGuard wsg(s);
-    MZK_TRY(ws_get(WS_NTT_IO_B, m * esz, &din[r]));
-    MZK_TRY(ws_get(WS_MISC_C, m * esz, &dout[r]));
+    MZK_TRY(ws.get(WS_NTT_IO_B, m * esz, &din[r]));
+    MZK_TRY(ws.get(WS_MISC_C, m * esz, &dout[r]));
     MZK_HIP(hipMemcpyAsync(din[r], (const char*)in + (size_t)r * m * esz, m * esz, hipMemcpyHostToDevice, s));
   }
   for (int r = 0; r < W; r++) { CtxScope sc(r); if (!sc.ok) return MZK_E_ARG; MZK_HIP(hipStreamSynchronize(ctx().stream)); }

@@ -1016,6 +1016,7 @@ static int get_plan(const NttSchedule& sched, bool inverse, const uint64_t* root
 // Walks the steps of `sc` (ntt_plan) over the tables of `pl` (get_plan of the same schedule).
 template <class P>
 static int run_plan(const NttPlan* pl, const NttSchedule& sc, const u32* d_in, u32* d_out, hipStream_t s, const PreArgs* pre = nullptr) {
+  WsFrame ws("run_plan");
   if (sc.err != MZK_OK) { set_error("%s", sc.msg); return sc.err; }
   static const int fuse = tune_int("MZK_NTT_FUSE_EDGES", 1);     // 0: A/B (tools/timing/time_ntt.py)
   static const int shoup = tune_int("MZK_NTT_SHOUP", 1);
@@ -1033,7 +1034,7 @@ static int run_plan(const NttPlan* pl, const NttSchedule& sc, const u32* d_in, u
     }
     const u32* src = d_in;
     u32* tmp = nullptr;
-    if (sc.tmp_bytes) MZK_TRY(ws_get(WS_NTT_TMP, sc.tmp_bytes, (void**)&tmp));
+    if (sc.tmp_bytes) MZK_TRY(ws.get(WS_NTT_TMP, sc.tmp_bytes, (void**)&tmp));
     for (int t = 0; t < sc.nsteps; t++) {
       const NttStep& st = sc.steps[t];
       ProfScope ps(s, MZK_PH_NTT_PASS0 + t);
@@ -1167,6 +1168,7 @@ int poly_scale_dev_impl(int fid, const void* d_in, size_t n, const uint64_t* rat
 
 int coset_lde_dev_impl(int fid, const void* d_coef, size_t n_coef, const uint64_t* offset_host,
                        const uint64_t* generator_host, void* d_out, size_t order, hipStream_t s, size_t batch) {
+  WsFrame ws("coset_lde_dev_impl");
   if (batch == 0) return MZK_OK;
   if (field_is_gl(fid)) return gl_coset_lde_dev_impl(fid, d_coef, n_coef, offset_host, generator_host, d_out, order, s, batch);
   MZK_TRY(field_check(fid, "coset_lde"));
@@ -1193,7 +1195,7 @@ int coset_lde_dev_impl(int fid, const void* d_coef, size_t n_coef, const uint64_
     // stream order checked like the fixed-base tables in mzk_kzg.hip).
     auto& ce = g_lde_cache[ctx().index][fid == MZK_FIELD_M128 ? 1 : 0];
     void* tabs = nullptr;
-    MZK_TRY(ws_get(fid == MZK_FIELD_M128 ? WS_NTT_PRE_M128 : WS_NTT_PRE, (nrow + ncol) * field_bytes(fid), &tabs));
+    MZK_TRY(ws_cache_get(fid == MZK_FIELD_M128 ? WS_NTT_PRE_M128 : WS_NTT_PRE, (nrow + ncol) * field_bytes(fid), &tabs));
     u32* pre_row = (u32*)tabs;
     u32* pre_col = pre_row + nrow * field_words(fid);
     if (!ce.ready) MZK_HIP(hipEventCreateWithFlags(&ce.ready, hipEventDisableTiming));
@@ -1217,7 +1219,7 @@ int coset_lde_dev_impl(int fid, const void* d_coef, size_t n_coef, const uint64_
     return with_field(fid, [&](auto tag) { return run_plan<typename decltype(tag)::P>(pl, sc, (const u32*)d_coef, (u32*)d_out, s, &pre); });
   }
   void* scaled = nullptr;
-  MZK_TRY(ws_get(WS_NTT_IO_A, batch * order * field_bytes(fid), &scaled));
+  MZK_TRY(ws.get(WS_NTT_IO_A, batch * order * field_bytes(fid), &scaled));
   const size_t chunks_per = (order + GEN_CHUNK - 1) / GEN_CHUNK;
   const unsigned blocks = (unsigned)((chunks_per * batch + 255) / 256);
   prof_begin(s, MZK_PH_NTT_PRESCALE);
@@ -1401,11 +1403,12 @@ __global__ __launch_bounds__(128) void k_pointwise_div(const u32* __restrict__ a
 // scaled by offset^-i.  root has order exactly `order` (the caller squared it down, ntt.rs:299-302).
 int coset_divide_dev_impl(int fid, const void* d_lhs, size_t tl, const void* d_rhs, size_t tr, const uint64_t* offset_host,
                           const uint64_t* root_host, size_t order, void* d_out, hipStream_t s) {
+  WsFrame ws("coset_divide_dev_impl");
   const HostField* hf = host_field(fid);
   const size_t esz = field_bytes(fid);
   void *ea, *eb;
-  MZK_TRY(ws_get(WS_MISC_A, order * esz, &ea));
-  MZK_TRY(ws_get(WS_MISC_B, order * esz, &eb));
+  MZK_TRY(ws.get(WS_MISC_A, order * esz, &ea));
+  MZK_TRY(ws.get(WS_MISC_B, order * esz, &eb));
   MZK_TRY(coset_lde_dev_impl(fid, d_lhs, tl, offset_host, root_host, ea, order, s));
   MZK_TRY(coset_lde_dev_impl(fid, d_rhs, tr, offset_host, root_host, eb, order, s));
   MZK_TRY(pointwise_div_dev(fid, ea, eb, ea, order, s));
@@ -1470,7 +1473,7 @@ __global__ __launch_bounds__(256) void k_rows_trim(u32* __restrict__ rows, size_
   if (threadIdx.x == 0 && sh[0]) atomicMax(&out[a], sh[0]);
 }
 int rows_trimmed_len_dev(int fid, void* d_rows, size_t stride, const size_t* lens, size_t count, size_t clear_to, const void* d_extra, size_t extra_len,
-                         WsSlot slot, size_t* out_lens, hipStream_t s) {
+                         WsFrame& ws, WsSlot slot, size_t* out_lens, hipStream_t s) {
   const size_t total = count + (d_extra ? 1 : 0);
   if (total == 0) return MZK_OK;
   size_t longest = clear_to;
@@ -1480,7 +1483,7 @@ int rows_trimmed_len_dev(int fid, void* d_rows, size_t stride, const size_t* len
   const size_t bpr = (longest + 255) / 256;
   if (total > (((size_t)1 << 31) - 1) / bpr) { set_error("trimmed lengths: %zu rows of %zu elements are too many", total, longest); return MZK_E_LENGTH; }
   unsigned long long* d_meta;
-  MZK_TRY(ws_get(slot, 2 * total * sizeof(unsigned long long), (void**)&d_meta));
+  MZK_TRY(ws.get(slot, 2 * total * sizeof(unsigned long long), (void**)&d_meta));
   MZK_HIP(hipMemcpyAsync(d_meta, meta.data(), 2 * total * sizeof(unsigned long long), hipMemcpyHostToDevice, s));
   MZK_TRY(MZK_FIELD_LAUNCH(fid, k_rows_trim<P>, dim3((unsigned)(total * bpr)), dim3(256), 0, s, (u32*)d_rows, stride, count, (const u32*)d_extra, (unsigned)bpr, (const unsigned long long*)d_meta, d_meta + total, clear_to));
   if (hipGetLastError() != hipSuccess) { (void)hipStreamSynchronize(s); set_error("trimmed lengths: launch failed"); return MZK_E_HIP; }
@@ -1498,15 +1501,16 @@ static int launch_scale_rows(int fid, const void* src, size_t src_stride, void* 
 }
 int coset_divide_rows_dev_impl(int fid, const void* d_lhs, size_t lhs_stride, const CdRow* rows, size_t nrows, const void* d_rhs, size_t tr,
                                const uint64_t* offset_host, const uint64_t* root_host, size_t order, void* d_out, size_t out_stride, hipStream_t s) {
+  WsFrame ws("coset_divide_rows_dev_impl");
   if (nrows == 0) return MZK_OK;
   const HostField* hf = host_field(fid);
   const size_t esz = field_bytes(fid);
   if (nrows > ((size_t)1 << 40) / order) { set_error("fast_coset_divide: %zu rows of order %zu are too many", nrows, order); return MZK_E_LENGTH; }
   void *ea, *eb;
   ScaleRow* d_tab;
-  MZK_TRY(ws_get(WS_MISC_A, nrows * order * esz, &ea));
-  MZK_TRY(ws_get(WS_MISC_B, order * esz, &eb));
-  MZK_TRY(ws_get(WS_MISC_F, 2 * nrows * sizeof(ScaleRow), (void**)&d_tab));
+  MZK_TRY(ws.get(WS_MISC_A, nrows * order * esz, &ea));
+  MZK_TRY(ws.get(WS_MISC_B, order * esz, &eb));
+  MZK_TRY(ws.get(WS_MISC_F, 2 * nrows * sizeof(ScaleRow), (void**)&d_tab));
   std::vector<ScaleRow> tab(2 * nrows);
   for (size_t k = 0; k < nrows; k++) {
     tab[k] = {rows[k].row, k, rows[k].tl};                                // numerator row -> transform k

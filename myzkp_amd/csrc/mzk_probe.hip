@@ -99,14 +99,15 @@ int selftest_field_probe_arity(int fid, int op, int form, int* limbs) {
   return arity;
 }
 int selftest_field_probe_impl(int fid, int op, int form, size_t n, const uint32_t* in_host, uint32_t* out_host, hipStream_t s) {
+  WsFrame ws("selftest_field_probe_impl");
   int L = 0;
   const int ar = selftest_field_probe_arity(fid, op, form, &L);
   if (ar == 0) { set_error("field_probe: no field %d / op %d / form %d", fid, op, form); return MZK_E_ARG; }
   if (n == 0) return MZK_OK;
   const size_t in_bytes = n * (size_t)ar * L * 4, out_bytes = n * (size_t)L * 4;
   void *din, *dout;
-  MZK_TRY(ws_get(WS_MISC_A, in_bytes, &din));
-  MZK_TRY(ws_get(WS_MISC_B, out_bytes, &dout));
+  MZK_TRY(ws.get(WS_MISC_A, in_bytes, &din));
+  MZK_TRY(ws.get(WS_MISC_B, out_bytes, &dout));
   MZK_HIP(hipMemcpyAsync(din, in_host, in_bytes, hipMemcpyHostToDevice, s));
   MZK_HIP(hipMemsetAsync(dout, 0, out_bytes, s));
   MZK_TRY(with_field3(fid, [&](auto tag) { return probe_field_forms<typename decltype(tag)::P>(op, form, n, (const u32*)din, (u32*)dout, s); }));
@@ -217,15 +218,16 @@ template <int OP> static void probe_g1_lane_launch(int form, size_t n, const u32
 }
 int selftest_g1_probe_impl(int op, int form, size_t n, const uint32_t* a_host, const uint32_t* b_host, const uint8_t* neg_host, uint32_t* out_host,
                            hipStream_t s) {
+  WsFrame ws("selftest_g1_probe_impl");
   int aw = 0, bw = 0;
   if (selftest_g1_probe_check(op, form, &aw, &bw) != MZK_OK) { set_error("g1_probe: no op %d / form %d", op, form); return MZK_E_ARG; }
   if (n == 0) return MZK_OK;
   void *da, *db, *dn, *dout;
   const size_t out_bytes = n * (size_t)PR_SLOT * 4;
-  MZK_TRY(ws_get(WS_MISC_A, n * (size_t)aw * 4, &da));
-  MZK_TRY(ws_get(WS_MISC_B, n * (size_t)(bw ? bw : 1) * 4, &db));
-  MZK_TRY(ws_get(WS_MISC_C, n, &dn));
-  MZK_TRY(ws_get(WS_MISC_D, out_bytes, &dout));
+  MZK_TRY(ws.get(WS_MISC_A, n * (size_t)aw * 4, &da));
+  MZK_TRY(ws.get(WS_MISC_B, n * (size_t)(bw ? bw : 1) * 4, &db));
+  MZK_TRY(ws.get(WS_MISC_C, n, &dn));
+  MZK_TRY(ws.get(WS_MISC_D, out_bytes, &dout));
   MZK_HIP(hipMemcpyAsync(da, a_host, n * (size_t)aw * 4, hipMemcpyHostToDevice, s));
   if (bw) MZK_HIP(hipMemcpyAsync(db, b_host, n * (size_t)bw * 4, hipMemcpyHostToDevice, s));
   if (op == PR_G1_MADD_SIGNED) MZK_HIP(hipMemcpyAsync(dn, neg_host, n, hipMemcpyHostToDevice, s));

@@ -114,8 +114,9 @@ int selftest_copy_impl(const void* d_src, void* d_dst, size_t bytes, hipStream_t
 }
 
 int selftest_field_asm_impl(int fid, uint64_t seed, size_t n, uint64_t* mismatches_host, hipStream_t s) {
+  WsFrame ws("selftest_field_asm_impl");
   unsigned long long* d;
-  MZK_TRY(ws_get(WS_MISC_A, 8, (void**)&d));
+  MZK_TRY(ws.get(WS_MISC_A, 8, (void**)&d));
   MZK_HIP(hipMemsetAsync(d, 0, 8, s));
   const unsigned blocks = (unsigned)((n + 255) / 256);
   if (n) {

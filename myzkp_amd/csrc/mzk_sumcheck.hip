@@ -340,6 +340,7 @@ static int scp_prove_impl(const void* tables, bool on_device, size_t el, size_t 
       if (!h_is_canonical(fr, t + 4 * i)) { set_error("sumcheck_product_prove: table value %zu of factor %zu not canonical", i % n, i / n); return MZK_E_RANGE; }
   }
   MZK_ENTER();
+  WsFrame ws("scp_prove_impl");
   hipStream_t s = on_device ? s_in : ctx().stream;
   WsGuard wsg(s);
   auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
@@ -349,7 +350,7 @@ static int scp_prove_impl(const void* tables, bool on_device, size_t el, size_t 
   const size_t o_a = on_device ? 0 : al(k * n * 32), o_b = o_a + (j0 > 1 ? al(k * (n / 2) * 32) : 0), o_part = o_b + (j0 > 2 ? al(k * (n / 4) * 32) : 0);
   const size_t o_state = o_part + al((size_t)SC_MAX_WG * (d + 1) * 32), o_proof = o_state + 256, total = o_proof + (on_device ? 0 : al(L.total));
   uint8_t* blk;
-  MZK_TRY(ws_get(WS_MISC_F, total, (void**)&blk));
+  MZK_TRY(ws.get(WS_MISC_F, total, (void**)&blk));
   const u32* d_tab = (const u32*)tables;
   if (!on_device) {
     MZK_HIP(hipMemcpyAsync(blk, tables, k * n * 32, hipMemcpyHostToDevice, s));
@@ -494,10 +495,11 @@ int mzk_mle_evals_from_coeffs(const uint64_t* coef, size_t num_vars, uint64_t* e
   for (size_t i = 0; i < n; i++)
     if (!h_is_canonical(fr, coef + 4 * i)) { set_error("mle_evals_from_coeffs: coefficient %zu not canonical", i); return MZK_E_RANGE; }
   MZK_ENTER();
+  WsFrame ws("mzk_mle_evals_from_coeffs");
   hipStream_t s = ctx().stream;
   WsGuard wsg(s);
   void* buf;
-  MZK_TRY(ws_get(WS_MISC_F, n * 32, &buf));
+  MZK_TRY(ws.get(WS_MISC_F, n * 32, &buf));
   MZK_HIP(hipMemcpyAsync(buf, coef, n * 32, hipMemcpyHostToDevice, s));
   MZK_TRY(mle_dev_impl(buf, num_vars, buf, s));
   return d2h_sync(evals, buf, n * 32, s);
