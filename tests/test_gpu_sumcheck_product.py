@@ -7,7 +7,11 @@ tables in one enqueue, transcript included, against tests/sumcheck_product_model
   framing   no header; the reference-shaped header; filler lengths that put a hashed stream length on both SHAKE256 padding edges
   forms     _dev == host form, inputs untouched, two proofs back to back on one stream
   el = 20   the model's verifier accepts the library's proof; SUM and FINALS against linear-time Python
-  mle       the subset-sum butterfly in and out of place, and coefficients -> tables -> proof end to end"""
+  mle       the subset-sum butterfly in and out of place, and coefficients -> tables -> proof end to end
+
+These are the spot shapes of the change that introduced the prover.  The sweep -- all 64 (k, d), every el from 1 to 13 with the
+launches counted, el = 21 where a lane of k_sc_round strides, values at the field's edges, three passes of k_mle_pass and the error
+paths -- is test_gpu_sumcheck_product_matrix.py, over the shapes and tables of sumcheck_product_cases.py."""
 import ctypes, functools, random
 import numpy as np
 import pytest
