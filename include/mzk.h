@@ -823,8 +823,8 @@ int mzk_srs_bucket_sets(const mzk_srs* srs);
  *   mzk_set_workspace_budget(bytes): the workspace a context may KEEP (0 = no limit, the default).  A call takes what it needs;
  *     whenever a buffer has to grow while the context holds more than the budget, every buffer the running call has not asked for
  *     is released first (the device is waited for).  Setting a budget below what is held releases the idle buffers at once.
- *   Whatever the budget: an allocation the device refuses -- workspace, SRS tables, prepared points -- is tried again after the idle
- *     workspace has been released, and a new SRS handle does that BEFORE it degrades its table layout; what is still refused is
+ *   Whatever the budget: an allocation the device refuses -- workspace, SRS tables, prepared points, the buffers of a Merkle tree
+ *     handle, the tables of a transform plan -- is tried again after the idle workspace has been released, and a new SRS handle does that BEFORE it degrades its table layout; what is still refused is
  *     MZK_E_NOMEM (never a bare MZK_E_HIP), with nothing enqueued.
  *   mzk_trim_workspace(&released): releases every workspace buffer of every context and the tables of the cached transform plans
  *     (rebuilt on demand); waits for the devices.  released may be NULL.

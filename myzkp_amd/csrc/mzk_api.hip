@@ -86,6 +86,7 @@ int ws_hook_alloc(void** out, size_t bytes, const char* what) {
 }
 int ws_hook_free(void* p) { MZK_HIP(hipFree(p)); return MZK_OK; }
 int ws_hook_sync() { MZK_HIP(hipDeviceSynchronize()); return MZK_OK; }
+int ws_hook_wait(void* stream) { MZK_HIP(hipStreamSynchronize((hipStream_t)stream)); return MZK_OK; }
 WsTable* ws_table_of(int ctx_index) { return &g_ctxs[ctx_index].ws; }
 int ws_current_ctx() { return g_cur; }
 int d2h_sync(void* host, const void* dev, size_t bytes, hipStream_t s) {
@@ -451,7 +452,7 @@ void mzk_shutdown(void) {
     (void)hipDeviceSynchronize();
     ntt_release_plans();
     kzg_release_cache();
-    poly_release_pool();
+    poly_release_plans();          // their blocks park in the pool, which goes next
     ws_release_all();
     if (c.ws_event) (void)hipEventDestroy(c.ws_event);
     if (c.fork_event) (void)hipEventDestroy(c.fork_event);
@@ -1179,7 +1180,6 @@ int mzk_trim_workspace(size_t* bytes_released) {
     total += ws_trim_idle();
     (void)hipDeviceSynchronize();
     ntt_release_plans();           // tables of the cached transform plans: rebuilt on the next call that needs them
-    poly_release_pool();
   }
   if (bytes_released) *bytes_released = total;
   return MZK_OK;
@@ -1211,16 +1211,16 @@ int mzk_srs_upload(const uint64_t* powers_xy, size_t n, mzk_srs** out) {
     rc = stage_in(ws, WS_MISC_A, powers_xy, n * 64, &d_plain, s);
     if (rc == MZK_OK) rc = srs_fill(h, d_plain, s);
     if (rc == MZK_OK && hipStreamSynchronize(s) != hipSuccess) rc = MZK_E_HIP;
-    if (rc != MZK_OK) { (void)hipFree(h->d_points_mont); delete h; return rc; }
+    if (rc != MZK_OK) { (void)ws_hook_free(h->d_points_mont); delete h; return rc; }
   }
   *out = h;
   return MZK_OK;
 }
 void mzk_srs_free(mzk_srs* srs) {
   if (!srs) return;
-  if (srs->d_points_mont) (void)hipFree(srs->d_points_mont);
-  if (srs->d_direct) (void)hipFree(srs->d_direct);
-  if (srs->d_tables_wide) (void)hipFree(srs->d_tables_wide);
+  if (srs->d_points_mont) (void)ws_hook_free(srs->d_points_mont);
+  if (srs->d_direct) (void)ws_hook_free(srs->d_direct);
+  if (srs->d_tables_wide) (void)ws_hook_free(srs->d_tables_wide);
   delete srs;
 }
 int mzk_kzg_commit_srs(const mzk_srs* srs, const uint64_t* coef, size_t n, uint64_t out_xy[8]) {
@@ -1342,15 +1342,15 @@ int mzk_srs_build_direct(mzk_srs* srs, int window_bits, size_t max_bytes, void* 
   if (bytes > budget) { set_error("srs_build_direct: %d-bit direct tables of %zu points take %zu bytes, the budget is %zu", c, srs->n, bytes, budget); return MZK_E_ARG; }
   if (srs->d_direct && srs->direct_bits == c) return MZK_OK;
   void* d = nullptr;
-  if (hipMalloc(&d, bytes) != hipSuccess) { (void)hipGetLastError(); set_error("srs_build_direct: hipMalloc of %zu bytes failed", bytes); return MZK_E_HIP; }
+  MZK_TRY(dev_alloc(&d, bytes, "srs_build_direct: direct tables"));
   int rc = msm_build_direct(srs->d_points_mont, srs->n, c, d, (hipStream_t)stream);
   if (rc == MZK_OK && hipStreamSynchronize((hipStream_t)stream) != hipSuccess) rc = MZK_E_HIP;
-  if (rc != MZK_OK) { (void)hipFree(d); return rc; }
+  if (rc != MZK_OK) { (void)ws_hook_free(d); return rc; }
   if (srs->d_direct) {
     // the old tables may still be read by work enqueued on OTHER streams of the handle's device (the in-flight lanes of the batch
     // entry points, a caller's second stream): wait for the whole device -- srs_check_ctx above made it the current one -- before freeing
     (void)hipDeviceSynchronize();
-    (void)hipFree(srs->d_direct);
+    (void)ws_hook_free(srs->d_direct);
   }
   srs->d_direct = d; srs->direct_bits = c; srs->direct_bytes = bytes;
   return MZK_OK;
@@ -1362,7 +1362,7 @@ void mzk_srs_drop_direct(mzk_srs* srs) {
   CtxScope sc(srs->ctx_index);    // the handle's own context and device, whatever is current: synchronise THAT device
   if (!sc.ok) return;
   (void)hipDeviceSynchronize();
-  (void)hipFree(srs->d_direct);
+  (void)ws_hook_free(srs->d_direct);
   srs->d_direct = nullptr; srs->direct_bits = 0; srs->direct_bytes = 0;
 }
 int mzk_srs_window_bits(const mzk_srs* srs) { return (srs && srs->has_tables) ? srs->window_bits : 0; }
@@ -1528,7 +1528,7 @@ int mzk_srs_from_device_ex(const void* d_powers_xy, size_t n, int with_tables, m
   if (n) {
     rc = srs_fill(h, d_powers_xy, s);
     if (rc == MZK_OK && hipStreamSynchronize(s) != hipSuccess) rc = MZK_E_HIP;
-    if (rc != MZK_OK) { (void)hipFree(h->d_points_mont); delete h; return rc; }
+    if (rc != MZK_OK) { (void)ws_hook_free(h->d_points_mont); delete h; return rc; }
   }
   *out = h;
   return MZK_OK;

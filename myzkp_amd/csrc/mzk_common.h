@@ -224,7 +224,7 @@ int gl_fri_fold_dev_alpha(int fid, const void* d_cw, size_t n, const uint64_t* d
                           hipStream_t s);       // alpha: NC canonical words in device memory
 void gl_release_plans();
 void kzg_release_cache();       // mzk_kzg.hip: fixed-base tables of the current context
-void poly_release_pool();       // mzk_poly.hip: parked scratch blocks of the current context
+void poly_release_plans();      // mzk_poly.hip: cached interpolation plans of the current context
 int fri_fold_dev_impl(int fid, const void* d_cw, size_t n, const uint64_t* alpha, const uint64_t* offset, const uint64_t* omega,
                       void* d_out, hipStream_t s);
 struct FriFoldConsts { uint64_t half[4], oinv[4], winv[4], rmod[4]; };

@@ -251,17 +251,14 @@ __global__ __launch_bounds__(GL_NT) void k_gl_fri_fold_dev_alpha(const u64* __re
 // ---- plans ------------------------------------------------------------------------------------------------------------------
 // Per (context, log2 n, direction, root): ONE device table [w_{2^tl}^j, j < 2048 | lo | mid | hi] of the effective
 // root (root^-1 for the inverse).  Offset tables of the LDE: [lo | mid | hi] of the offset, kept per (context, offset).
-struct GlPlan { unsigned logn; bool inverse; u64 root; int tl; u64* d_tab; u64 scale; int has_scale; uint64_t stamp; };
-struct GlOffTab { u64 offset; u64* d_tab; uint64_t stamp; };
-static std::vector<GlPlan*> g_gl_plans[MZK_MAX_CTX];
-static std::vector<GlOffTab*> g_gl_offs[MZK_MAX_CTX];
-static uint64_t g_gl_stamp = 0;
+struct GlPlan { unsigned logn; bool inverse; u64 root; int tl; DevMem d_tab; u64 scale; int has_scale; uint64_t stamp; };
+struct GlOffTab { u64 offset; DevMem d_tab; uint64_t stamp; };
+static std::vector<std::unique_ptr<GlPlan>> g_gl_plans[MZK_MAX_CTX];
+static std::vector<std::unique_ptr<GlOffTab>> g_gl_offs[MZK_MAX_CTX];
 constexpr size_t GL_MAX_PLANS = 48, GL_MAX_OFFS = 8;
 
 void gl_release_plans() {
-  for (auto* p : g_gl_plans[ctx().index]) { (void)hipFree(p->d_tab); delete p; }
   g_gl_plans[ctx().index].clear();
-  for (auto* p : g_gl_offs[ctx().index]) { (void)hipFree(p->d_tab); delete p; }
   g_gl_offs[ctx().index].clear();
 }
 
@@ -275,38 +272,25 @@ static void gl_fill_pow(u64 g, u64* t) {        // [lo | mid | hi] of g
   x = 1;
   for (int i = 0; i < GL_POW_HI; i++) { t[GL_POW_LO + GL_POW_MID + i] = x; x = gl::mul(x, g24); }
 }
-template <class T> static int gl_evict(std::vector<T*>& v, size_t cap, hipStream_t s) {
-  if (v.size() < cap) return MZK_OK;
-  size_t victim = 0;
-  for (size_t i = 1; i < v.size(); i++) if (v[i]->stamp < v[victim]->stamp) victim = i;
-  MZK_HIP(hipStreamSynchronize(s));
-  (void)hipFree(v[victim]->d_tab);
-  delete v[victim];
-  v.erase(v.begin() + victim);
-  return MZK_OK;
-}
-static int gl_upload(const std::vector<u64>& host, u64** d_tab, hipStream_t s) {
-  MZK_TRY(dev_alloc((void**)d_tab, host.size() * 8, "goldilocks twiddle tables"));
+static int gl_upload(const std::vector<u64>& host, DevMem* d_tab, hipStream_t s) {
+  MZK_TRY(d_tab->alloc(host.size() * 8, "goldilocks twiddle tables"));
   // (pageable source: the copy is staged before the call returns, as everywhere in this library)
-  if (hipMemcpyAsync(*d_tab, host.data(), host.size() * 8, hipMemcpyHostToDevice, s) != hipSuccess) {
-    (void)hipFree(*d_tab);
-    return hip_fail(hipGetLastError(), "hipMemcpyAsync(twiddle tables)", __FILE__, __LINE__);
-  }
+  MZK_HIP(hipMemcpyAsync(d_tab->get(), host.data(), host.size() * 8, hipMemcpyHostToDevice, s));
   return MZK_OK;
 }
 static int gl_get_plan(unsigned logn, bool inverse, u64 root, hipStream_t s, GlPlan** out) {
   auto& plans = g_gl_plans[ctx().index];
-  for (auto* p : plans)
-    if (p->logn == logn && p->inverse == inverse && p->root == root) { p->stamp = ++g_gl_stamp; *out = p; return MZK_OK; }
+  for (auto& p : plans)
+    if (p->logn == logn && p->inverse == inverse && p->root == root) { p->stamp = lru_stamp(); *out = p.get(); return MZK_OK; }
   // reference assertions, ntt.rs:15-22
   const u64 n = (u64)1 << logn;
   if (gl::pow(root, n) != 1) { set_error("primitive root must be nth root of unity, where n is len(values)"); return MZK_E_ROOT_ORDER; }
   if (gl::pow(root, n / 2) == 1) { set_error("primitive root is not primitive nth root of unity, where n is len(values)"); return MZK_E_ROOT_PRIM; }
-  MZK_TRY(gl_evict(plans, GL_MAX_PLANS, s));
-  GlPlan* pl = new GlPlan();
+  MZK_TRY(lru_evict(plans, GL_MAX_PLANS, s));
+  std::unique_ptr<GlPlan> pl(new GlPlan());
   pl->logn = logn; pl->inverse = inverse; pl->root = root;
   pl->tl = logn < (unsigned)GL_TL ? (int)logn : GL_TL;
-  pl->stamp = ++g_gl_stamp;
+  pl->stamp = lru_stamp();
   const u64 w = inverse ? gl::pow(root, n - 1) : root;          // root^-1 = root^(n-1)                      (ntt.rs:59)
   pl->has_scale = inverse ? 1 : 0;
   pl->scale = inverse ? gl::inv(n % gl::P) : 1;                 // F::from_value(n).inverse()                (ntt.rs:58)
@@ -315,24 +299,22 @@ static int gl_get_plan(unsigned logn, bool inverse, u64 root, hipStream_t s, GlP
   u64 x = 1;
   for (int j = 0; j < (1 << pl->tl) / 2; j++) { host[j] = x; x = gl::mul(x, wt); }
   gl_fill_pow(w, host.data() + GL_TW);
-  const int rc = gl_upload(host, &pl->d_tab, s);
-  if (rc != MZK_OK) { delete pl; return rc; }
-  plans.push_back(pl);
-  *out = pl;
+  MZK_TRY(gl_upload(host, &pl->d_tab, s));
+  *out = pl.get();
+  plans.push_back(std::move(pl));
   return MZK_OK;
 }
 static int gl_get_offtab(u64 offset, hipStream_t s, const u64** out) {
   auto& offs = g_gl_offs[ctx().index];
-  for (auto* p : offs)
-    if (p->offset == offset) { p->stamp = ++g_gl_stamp; *out = p->d_tab; return MZK_OK; }
-  MZK_TRY(gl_evict(offs, GL_MAX_OFFS, s));
+  for (auto& p : offs)
+    if (p->offset == offset) { p->stamp = lru_stamp(); *out = p->d_tab.as<u64>(); return MZK_OK; }
+  MZK_TRY(lru_evict(offs, GL_MAX_OFFS, s));
   std::vector<u64> host(GL_POW);
   gl_fill_pow(offset, host.data());
-  GlOffTab* t = new GlOffTab{offset, nullptr, ++g_gl_stamp};
-  const int rc = gl_upload(host, &t->d_tab, s);
-  if (rc != MZK_OK) { delete t; return rc; }
-  offs.push_back(t);
-  *out = t->d_tab;
+  std::unique_ptr<GlOffTab> t(new GlOffTab{offset, DevMem(), lru_stamp()});
+  MZK_TRY(gl_upload(host, &t->d_tab, s));
+  *out = t->d_tab.as<u64>();
+  offs.push_back(std::move(t));
   return MZK_OK;
 }
 
@@ -354,11 +336,11 @@ static int gl_run_plan(const GlPlan* pl, const u64* d_in, u64* d_out, size_t bat
     const bool with_pre = t == 0 && pre;
     if (st.kind == NTT_STEP_STRIDED) {
       const u64 escale = (u64)1 << (logn - (unsigned)(st.lgn + st.lgM));
-      hipLaunchKernelGGL((with_pre ? k_gl_ntt_strided<NC, true> : k_gl_ntt_strided<NC, false>), dim3(st.grid), dim3(st.block), 0, s, src, tmp, (const u64*)pl->d_tab,
+      hipLaunchKernelGGL((with_pre ? k_gl_ntt_strided<NC, true> : k_gl_ntt_strided<NC, false>), dim3(st.grid), dim3(st.block), 0, s, src, tmp, pl->d_tab.as<u64>(),
                          st.lgn, st.lgM, st.lgc, pl->tl, big, escale, with_pre ? *pre : none);
       src = tmp;
     } else {
-      hipLaunchKernelGGL((with_pre ? k_gl_ntt_last<NC, true> : k_gl_ntt_last<NC, false>), dim3(st.grid), dim3(st.block), 0, s, src, d_out, (const u64*)pl->d_tab, sc.li,
+      hipLaunchKernelGGL((with_pre ? k_gl_ntt_last<NC, true> : k_gl_ntt_last<NC, false>), dim3(st.grid), dim3(st.block), 0, s, src, d_out, pl->d_tab.as<u64>(), sc.li,
                          st.lgn, st.lgr, st.lg_rows, pl->scale, pl->has_scale, st.total_rows, pl->tl, with_pre ? *pre : none);
     }
   }

@@ -112,9 +112,9 @@ int mzk_srs_load(const char* path, int with_tables, mzk_srs** out) {
   if (fread(&h, sizeof h, 1, fc.f) != 1 || memcmp(h.magic, SRS_MAGIC, 8) != 0 || (h.format != 1 && h.format != 2)) { set_error("srs_load: %s is not an SRS dump of this library", path); return MZK_E_IO; }
   if (h.n > ((uint64_t)1 << 27)) { set_error("srs_load: %llu points exceed the supported 2^27", (unsigned long long)h.n); return MZK_E_IO; }
   const size_t n = (size_t)h.n;
-  void* d_plain = nullptr;
-  if (hipMalloc(&d_plain, n ? n * 64 : 64) != hipSuccess) { set_error("srs_load: hipMalloc failed"); return MZK_E_HIP; }
-  struct DevFree { void* p; ~DevFree() { if (p) (void)hipFree(p); } } df{d_plain};
+  DevMem plain;
+  MZK_TRY(plain.alloc(n ? n * 64 : 64, "srs_load: staging"));
+  void* const d_plain = plain.get();
   std::vector<uint8_t> host(IO_CHUNK_POINTS * 64);
   uint64_t hash = 0xcbf29ce484222325ULL;
   for (size_t at = 0; at < n; at += IO_CHUNK_POINTS) {

@@ -510,7 +510,8 @@ struct mzk_merkle {
   size_t n;
   int depth;             // log2 n
   u64* d_nodes;          // n - 1 digests: level 1 (n/2), level 2 (n/4), ..., root
-  void* d_leaves;        // owned copy of the elements / the leaf bytes (needed by open and by n == 1)
+  void* d_leaves;        // copy of the elements / the leaf bytes (needed by open and by n == 1)
+  DevMem own_nodes, own_leaves, own_items;     // what d_nodes, d_leaves and d_items point to, where the handle owns it alone
   std::vector<uint64_t> offsets;   // byte leaves only
   std::vector<uint8_t> neg;        // field leaves given as (magnitude, sign): 1 = Sign::Minus; empty = all non-negative
   hipStream_t stream;    // the stream the tree was BUILT on (a caller stream for the *_dev builders); never used again
@@ -522,11 +523,10 @@ struct mzk_merkle {
   // ragged leaf counts: the tree is built over m = 2^floor(log2 n) items (see k_merkle_ragged_items); d_nodes, depth
   // and the gather kernel then refer to the item tree
   // FRI::commit with the trees kept: the codewords and digests of ALL rounds live in one device allocation shared by the rounds'
-  // handles (one hipMalloc per commit instead of two per round, and no copies: a round hashes and folds in place there);
-  // d_leaves / d_nodes then point into it and the last handle freed releases it.
-  struct SharedBlock { void* p; int refs; };
-  SharedBlock* shared = nullptr;
-  bool owns_leaves = false;        // with `shared`: d_leaves is nevertheless an allocation of its own (signed round-0 leaves)
+  // handles (one allocation per commit instead of two per round, and no copies: a round hashes and folds in place there);
+  // d_leaves / d_nodes then point into it -- but for signed round-0 leaves, a copy in own_leaves -- and the last handle freed
+  // releases it.
+  std::shared_ptr<DevMem> shared;
   bool ragged = false;
   size_t m = 0;
   void* d_items = nullptr;
@@ -727,8 +727,10 @@ static int merkle_build_ragged(const uint8_t* leaves, const uint64_t* offsets, s
   u32* d_ns = nullptr;
   int rc = MZK_OK;
   do {
-    if (hipMalloc(&t->d_leaves, leaf_bytes ? leaf_bytes : 16) != hipSuccess || hipMalloc(&t->d_items, io ? io : 16) != hipSuccess ||
-        hipMalloc((void**)&t->d_nodes, (m - 1) * 32) != hipSuccess) { set_error("merkle: hipMalloc failed"); rc = MZK_E_HIP; break; }
+    if ((rc = t->own_leaves.alloc(leaf_bytes ? leaf_bytes : 16, "merkle: leaves")) != MZK_OK) break;
+    if ((rc = t->own_items.alloc(io ? io : 16, "merkle: items")) != MZK_OK) break;
+    if ((rc = t->own_nodes.alloc((m - 1) * 32, "merkle: digests")) != MZK_OK) break;
+    t->d_leaves = t->own_leaves.get(); t->d_items = t->own_items.get(); t->d_nodes = t->own_nodes.as<u64>();
     if ((rc = ws.get(WS_MISC_D, (n + 1) * 8, (void**)&d_off)) != MZK_OK) break;
     if ((rc = ws.get(WS_MISC_E, (m + 1) * 8, (void**)&d_ioff)) != MZK_OK) break;
     if ((rc = ws.get(WS_MISC_F, (m + 1) * 4, (void**)&d_ns)) != MZK_OK) break;
@@ -779,11 +781,13 @@ static int merkle_build(int kind, int fid, const void* src, bool src_on_device, 
   u64* d_off = nullptr;
   int rc = MZK_OK;
   do {
-    if (hipMalloc(&t->d_leaves, leaf_bytes ? leaf_bytes : 16) != hipSuccess) { set_error("merkle: hipMalloc failed"); rc = MZK_E_HIP; break; }
+    if ((rc = t->own_leaves.alloc(leaf_bytes ? leaf_bytes : 16, "merkle: leaves")) != MZK_OK) break;
+    t->d_leaves = t->own_leaves.get();
     if (leaf_bytes && hipMemcpyAsync(t->d_leaves, src, leaf_bytes, src_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s) != hipSuccess) {
       set_error("merkle: leaf copy failed"); rc = MZK_E_HIP; break;
     }
-    if (n > 1 && hipMalloc((void**)&t->d_nodes, (n - 1) * 32) != hipSuccess) { set_error("merkle: hipMalloc failed"); rc = MZK_E_HIP; break; }
+    if (n > 1 && (rc = t->own_nodes.alloc((n - 1) * 32, "merkle: digests")) != MZK_OK) break;
+    t->d_nodes = t->own_nodes.as<u64>();
     if (kind == 1) {
       t->offsets.assign(offsets, offsets + n + 1);
       if ((rc = ws.get(WS_MISC_D, (n + 1) * 8, (void**)&d_off)) != MZK_OK) break;
@@ -1110,14 +1114,6 @@ int mzk_merkle_open_multi(const mzk_merkle* const* trees, size_t n_trees, const 
 
 void mzk_merkle_free(mzk_merkle* t) {
   if (!t) return;
-  if (t->shared) {
-    if (--t->shared->refs == 0) { (void)hipFree(t->shared->p); delete t->shared; }
-    if (!t->owns_leaves) t->d_leaves = nullptr;
-    t->d_nodes = nullptr;
-  }
-  if (t->d_leaves) (void)hipFree(t->d_leaves);
-  if (t->d_nodes) (void)hipFree(t->d_nodes);
-  if (t->d_items) (void)hipFree(t->d_items);
   if (t->built) (void)hipEventDestroy(t->built);
   delete t;
 }
@@ -1265,27 +1261,22 @@ static int fri_commit_rounds(int field_id, const uint64_t* codeword, const uint8
   for (int r = 0; r < num_rounds; r++) total += n >> r;
   uint8_t* d_all;
   u64* d_nodes;
-  mzk_merkle::SharedBlock* shared = nullptr;
+  std::shared_ptr<DevMem> shared;      // this function's own reference: the handles already handed out keep the block alive on every exit path
   if (trees_out) {
-    // trees kept: codewords and digests of every round in ONE allocation that the rounds' handles share (2 hipMalloc and two
+    // trees kept: codewords and digests of every round in ONE allocation that the rounds' handles share (two allocations and two
     // device copies per round before: ~25 us of a ~155-us round at 2^14); layout: [codewords of all rounds | digests of round 0 | 1 | ...]
     for (int r = 0; r < num_rounds; r++) trees_out[r] = nullptr;
     size_t node_bytes = 0;
     for (int r = 0; r < num_rounds; r++) if ((n >> r) >= 2) node_bytes += ((n >> r) - 1) * 32;
     const size_t cw_bytes = (total * esz + 255) & ~(size_t)255;
-    void* blk = nullptr;
-    MZK_TRY(dev_alloc(&blk, cw_bytes + node_bytes + 256, "fri_commit: kept trees"));
-    shared = new mzk_merkle::SharedBlock{blk, 1};        // this function's own reference, dropped at the end
-    d_all = (uint8_t*)blk;
-    d_nodes = (u64*)((uint8_t*)blk + cw_bytes);
+    shared = std::make_shared<DevMem>();
+    MZK_TRY(shared->alloc(cw_bytes + node_bytes + 256, "fri_commit: kept trees"));
+    d_all = shared->as<uint8_t>();
+    d_nodes = (u64*)(d_all + cw_bytes);
   } else {
     MZK_TRY(ws.get(WS_NTT_IO_A, total * esz, (void**)&d_all));
     MZK_TRY(ws.get(WS_MERKLE_NODES, n * 32, (void**)&d_nodes));
   }
-  struct DropRef {        // every exit path: the handles already handed out keep the block alive, otherwise it goes
-    mzk_merkle::SharedBlock* b;
-    ~DropRef() { if (b && --b->refs == 0) { (void)hipFree(b->p); delete b; } }
-  } drop{shared};
   MZK_HIP(hipMemcpyAsync(d_all, codeword, n * esz, on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s));
   u8* d_neg = nullptr;
   if (negative) {     // round 0 hashes bincode of the UNSANITIZED elements (fri.rs:160-166); the fold sanitizes (fri.rs:190)
@@ -1314,17 +1305,16 @@ static int fri_commit_rounds(int field_id, const uint64_t* codeword, const uint8
         mzk_merkle* t = new mzk_merkle();
         t->kind = 0; t->field = field_id; t->n = len; t->stream = s;
         t->d_nodes = d_nodes; t->d_leaves = cur;
-        t->shared = shared; shared->refs++;
+        t->shared = shared;
         t->depth = 0;
         while (((size_t)1 << t->depth) < len) t->depth++;
         trees_out[r] = t;
         if (r == 0 && negative) {
           // round 0 commits to the UNSANITIZED elements and the fold below canonicalises the codeword in place: the tree keeps
           // the magnitudes as they were given, in a copy of its own
-          void* own = nullptr;
-          MZK_TRY(dev_alloc(&own, len * esz, "fri_commit: round-0 leaves"));
-          MZK_HIP(hipMemcpyAsync(own, cur, len * esz, hipMemcpyDeviceToDevice, s));
-          t->d_leaves = own; t->owns_leaves = true;
+          MZK_TRY(t->own_leaves.alloc(len * esz, "fri_commit: round-0 leaves"));
+          MZK_HIP(hipMemcpyAsync(t->own_leaves.get(), cur, len * esz, hipMemcpyDeviceToDevice, s));
+          t->d_leaves = t->own_leaves.get();
           t->neg.assign(negative, negative + n);
         }
         MZK_TRY(merkle_stamp(t, s, true));

@@ -2122,7 +2122,7 @@ int msm_many_srs(const mzk_srs* srs, const void* d_scalars, size_t n, size_t str
       const bool within_budget = table_budget_bytes() == 0 || own + bytes <= table_budget_bytes();
       if (within_budget && dev_alloc(&t, bytes, "wide window tables of the grid-batched pass") == MZK_OK) {
         const int rc = msm_build_tables(srs->d_points_mont, srs->n, t, MANY_WIDE_BITS, s);
-        if (rc != MZK_OK) { (void)hipFree(t); return rc; }
+        if (rc != MZK_OK) { (void)ws_hook_free(t); return rc; }
         srs->d_tables_wide = t; srs->wide_bits = MANY_WIDE_BITS; srs->wide_bytes = bytes;
       } else {
         srs->wide_bits = -1;         // no memory (or no budget) for them: the handle's own tables serve (slower, same points)

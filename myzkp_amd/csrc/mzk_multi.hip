@@ -294,23 +294,23 @@ int mzk_kzg_setup_srs_multi(const uint64_t alpha[4], const uint64_t g1_xy[8], si
   MZK_ENTER();
   if (!out || !alpha || !g1_xy) { set_error("setup_srs_multi: null pointer"); return MZK_E_ARG; }
   mzk_srs_multi* h = new_multi(max_d + 1);
-  void* tmp[MZK_MAX_CTX] = {};
+  DevMem tmp[MZK_MAX_CTX];
   int rc = MZK_OK;
   // enqueue every context's setup first (they run concurrently), then build the handles (each synchronises its stream)
   for (int r = 0; r < h->world && rc == MZK_OK; r++) {
     CtxScope sc(r);
     if (!sc.ok) { rc = MZK_E_ARG; break; }
     const size_t cnt = h->lo[r + 1] - h->lo[r];
-    if (hipMalloc(&tmp[r], cnt ? cnt * 64 : 64) != hipSuccess) { set_error("setup_srs_multi: hipMalloc failed"); rc = MZK_E_HIP; break; }
+    if ((rc = tmp[r].alloc(cnt ? cnt * 64 : 64, "setup_srs_multi: powers")) != MZK_OK) break;
     WsGuard wsg(ctx().stream);
-    rc = kzg_setup_g1_dev(alpha, g1_xy, h->lo[r], cnt, tmp[r], ctx().stream);
+    rc = kzg_setup_g1_dev(alpha, g1_xy, h->lo[r], cnt, tmp[r].get(), ctx().stream);
   }
   for (int r = 0; r < h->world && rc == MZK_OK; r++) {
     CtxScope sc(r);
     if (!sc.ok) { rc = MZK_E_ARG; break; }
-    rc = mzk_srs_from_device_ex(tmp[r], h->lo[r + 1] - h->lo[r], with_tables, &h->shard[r], ctx().stream);
+    rc = mzk_srs_from_device_ex(tmp[r].get(), h->lo[r + 1] - h->lo[r], with_tables, &h->shard[r], ctx().stream);
   }
-  for (int r = 0; r < h->world; r++) if (tmp[r]) { CtxScope sc(r); (void)hipStreamSynchronize(ctx().stream); (void)hipFree(tmp[r]); }
+  for (int r = 0; r < h->world; r++) if (tmp[r]) { CtxScope sc(r); (void)hipStreamSynchronize(ctx().stream); tmp[r].reset(); }
   if (rc != MZK_OK) { mzk_srs_multi_free(h); return rc; }
   *out = h;
   return MZK_OK;

@@ -827,29 +827,19 @@ struct NttPlan {
   bool large = false;                  // the level split the tables were built for (NttSchedule::large)
   uint64_t root[4] = {0, 0, 0, 0};     // forward root as passed by the caller
   uint64_t scale[4] = {0, 0, 0, 0};    // extra plain scale folded into the tables (1 if none)
-  u32* tw_tile[4] = {nullptr, nullptr, nullptr, nullptr};
-  u32* tw_inter[3] = {nullptr, nullptr, nullptr};
-  u32* tw_shoup[4] = {nullptr, nullptr, nullptr, nullptr};   // Fr: per level, the in-tile twiddles again as (plain w, floor(w 2^261 / p)) limb entries
+  DevMem tw_tile[4], tw_inter[3];
+  DevMem tw_shoup[4];                  // Fr: per level, the in-tile twiddles again as (plain w, floor(w 2^261 / p)) limb entries
   Words8 last_scale{};                 // single-pass inverse: n^-1 (* scale), Montgomery
   int has_last_scale = 0;
   uint64_t stamp = 0;
 };
-static std::vector<NttPlan*> g_plans_all[MZK_MAX_CTX];      // per context (device)
+static std::vector<std::unique_ptr<NttPlan>> g_plans_all[MZK_MAX_CTX];      // per context (device)
 #define g_plans g_plans_all[ctx().index]
-static uint64_t g_stamp = 0;
 constexpr size_t MAX_PLANS = 96;      // the polynomial trees of mzk_poly.hip use every size from 2^7 up, both directions
-
-static void free_plan(NttPlan* p) {
-  for (auto& t : p->tw_tile) if (t) (void)hipFree(t);
-  for (auto& t : p->tw_inter) if (t) (void)hipFree(t);
-  for (auto& t : p->tw_shoup) if (t) (void)hipFree(t);
-  delete p;
-}
 // offset-power tables of the fused coset LDE, per (context, field); see coset_lde_dev_impl
 static struct { uint64_t off[4]; unsigned logn; int lgn0; uint64_t gen; bool valid; hipEvent_t ready; } g_lde_cache[MZK_MAX_CTX][2] = {};
 void ntt_release_plans() {
   gl_release_plans();
-  for (auto* p : g_plans) free_plan(p);
   g_plans.clear();
   for (auto& ce : g_lde_cache[ctx().index]) {      // mzk_shutdown walks the contexts: drop this one's entries and their events
     if (ce.ready) (void)hipEventDestroy(ce.ready);
@@ -867,7 +857,7 @@ static void to_words(const uint64_t* limbs, int nl, Words8* w) {
 
 // Shoup entries of the in-tile twiddles w^j, j < cnt, w = root^emul: limbs (29 bits) of w^j at words [0, 9), of
 // floor(w^j 2^261 / p) at [16, 25) of a 32-word entry.  Host arithmetic (a few hundred 256-bit products and divisions per plan).
-static int build_shoup_table(const HostField* hf, const uint64_t* root, uint64_t emul, size_t cnt, u32** out, hipStream_t s) {
+static int build_shoup_table(const HostField* hf, const uint64_t* root, uint64_t emul, size_t cnt, DevMem* out, hipStream_t s) {
   std::vector<u32> tab(cnt * SHOUP_ENTRY_WORDS, 0u);
   uint64_t w[4], cur[4] = {1, 0, 0, 0};
   h_powmod_u64(hf, w, root, emul);
@@ -904,8 +894,8 @@ static int build_shoup_table(const HostField* hf, const uint64_t* root, uint64_t
     limbs_of(q, &tab[j * SHOUP_ENTRY_WORDS + 16]);
     h_mulmod(hf, cur, cur, w);
   }
-  MZK_HIP(hipMalloc((void**)out, tab.size() * sizeof(u32)));
-  MZK_HIP(hipMemcpyAsync(*out, tab.data(), tab.size() * sizeof(u32), hipMemcpyHostToDevice, s));
+  MZK_TRY(out->alloc(tab.size() * sizeof(u32), "transform plan tables"));
+  MZK_HIP(hipMemcpyAsync(out->get(), tab.data(), tab.size() * sizeof(u32), hipMemcpyHostToDevice, s));
   MZK_HIP(hipStreamSynchronize(s));          // `tab` is a local
   return MZK_OK;
 }
@@ -927,21 +917,21 @@ static int build_tables(NttPlan* pl, const NttLevels& li, const uint64_t* eff_ro
     // in-tile twiddles: w_{n_t}^j = root^(j * n / n_t), j < n_t / 2
     if (lgn >= 2) {
       size_t cnt = (size_t)1 << (lgn - 1);
-      MZK_HIP(hipMalloc((void**)&pl->tw_tile[t], cnt * esz));
+      MZK_TRY(pl->tw_tile[t].alloc(cnt * esz, "transform plan tables"));
       unsigned blocks = (unsigned)((cnt + GEN_CHUNK * 64 - 1) / (GEN_CHUNK * 64));
       hipLaunchKernelGGL((k_gen_pow_table<P>), dim3(blocks), dim3(64), 0, s, rootw, (uint64_t)1 << (pl->logn - lgn), cnt,
-                         pl->tw_tile[t]);
+                         pl->tw_tile[t].as<u32>());
       if (HasShoup<P>::value) MZK_TRY(build_shoup_table(hf, eff_root, (uint64_t)1 << (pl->logn - lgn), cnt, &pl->tw_shoup[t], s));
     }
     if (t < li.nlev - 1) {
       // inter-pass twiddles for the block of size n_t * M_t: primitive root = root^(n / (n_t M_t))
       size_t cnt = (size_t)1 << lg_after;
-      MZK_HIP(hipMalloc((void**)&pl->tw_inter[t], cnt * esz));
+      MZK_TRY(pl->tw_inter[t].alloc(cnt * esz, "transform plan tables"));
       size_t clen = ((size_t)1 << lgM) < (size_t)GEN_CHUNK ? ((size_t)1 << lgM) : (size_t)GEN_CHUNK;
       size_t chunks = cnt / clen;
       unsigned blocks = (unsigned)((chunks + 255) / 256);
       hipLaunchKernelGGL((k_gen_inter_table<P>), dim3(blocks), dim3(256), 0, s, rootw,
-                         (uint64_t)1 << (pl->logn - lg_after), lgn, lgM, (t == 0) ? scalew : onew, pl->tw_inter[t]);
+                         (uint64_t)1 << (pl->logn - lg_after), lgn, lgM, (t == 0) ? scalew : onew, pl->tw_inter[t].as<u32>());
     }
     lg_after = lgM;
   }
@@ -957,11 +947,11 @@ static int get_plan(const NttSchedule& sched, bool inverse, const uint64_t* root
   const HostField* hf = host_field(fid);
   uint64_t one[4] = {1, 0, 0, 0};
   const uint64_t* sc = extra_scale ? extra_scale : one;
-  for (auto* p : g_plans) {
+  for (auto& p : g_plans) {
     if (p->fid == fid && p->logn == logn && p->inverse == inverse && p->large == large && !memcmp(p->root, root, 8 * hf->nl) &&
         !memcmp(p->scale, sc, 8 * hf->nl)) {
-      p->stamp = ++g_stamp;
-      *out = p;
+      p->stamp = lru_stamp();
+      *out = p.get();
       return MZK_OK;
     }
   }
@@ -973,11 +963,11 @@ static int get_plan(const NttSchedule& sched, bool inverse, const uint64_t* root
   h_powmod_u64(hf, t, root, n / 2);
   if (h_is_one(hf, t)) { set_error("primitive root is not primitive nth root of unity, where n is len(values)"); return MZK_E_ROOT_PRIM; }
 
-  NttPlan* pl = new NttPlan();
+  std::unique_ptr<NttPlan> pl(new NttPlan());
   pl->fid = fid; pl->logn = logn; pl->inverse = inverse; pl->large = large;
   memcpy(pl->root, root, 8 * hf->nl);
   memcpy(pl->scale, sc, 8 * hf->nl);
-  pl->stamp = ++g_stamp;
+  pl->stamp = lru_stamp();
   uint64_t eff_root[4] = {0, 0, 0, 0}, fold[4] = {0, 0, 0, 0};
   memcpy(fold, sc, 8 * hf->nl);
   if (inverse) {
@@ -999,17 +989,10 @@ static int get_plan(const NttSchedule& sched, bool inverse, const uint64_t* root
     to_words(m, hf->nl, &pl->last_scale);
     pl->has_last_scale = 1;
   }
-  const int rc = with_field(fid, [&](auto tag) { return build_tables<typename decltype(tag)::P>(pl, sched.li, eff_root, fold, s); });
-  if (rc != MZK_OK) { free_plan(pl); return rc; }
-  if (g_plans.size() >= MAX_PLANS) {
-    size_t victim = 0;
-    for (size_t i = 1; i < g_plans.size(); i++) if (g_plans[i]->stamp < g_plans[victim]->stamp) victim = i;
-    MZK_HIP(hipStreamSynchronize(s));
-    free_plan(g_plans[victim]);
-    g_plans.erase(g_plans.begin() + victim);
-  }
-  g_plans.push_back(pl);
-  *out = pl;
+  MZK_TRY(with_field(fid, [&](auto tag) { return build_tables<typename decltype(tag)::P>(pl.get(), sched.li, eff_root, fold, s); }));
+  MZK_TRY(lru_evict(g_plans, MAX_PLANS, s));
+  *out = pl.get();
+  g_plans.push_back(std::move(pl));
   return MZK_OK;
 }
 
@@ -1043,13 +1026,13 @@ static int run_plan(const NttPlan* pl, const NttSchedule& sc, const u32* d_in, u
           const bool with_pre = t == 0 && pre;
           auto* k = with_pre ? (st.wt ? k_ntt_strided<P, true, G, true> : k_ntt_strided<P, true, G, false>)
                              : (st.wt ? k_ntt_strided<P, false, G, true> : k_ntt_strided<P, false, G, false>);
-          hipLaunchKernelGGL(k, dim3(st.grid), dim3(st.block), st.lds, s, src, tmp, pl->tw_tile[t], pl->tw_inter[t], st.lgn, st.lgM, st.lgc,
-                             with_pre ? *pre : PreArgs{nullptr, 0, nullptr, nullptr}, fuse, shoup ? pl->tw_shoup[t] : nullptr);
+          hipLaunchKernelGGL(k, dim3(st.grid), dim3(st.block), st.lds, s, src, tmp, pl->tw_tile[t].as<u32>(), pl->tw_inter[t].as<u32>(), st.lgn, st.lgM, st.lgc,
+                             with_pre ? *pre : PreArgs{nullptr, 0, nullptr, nullptr}, fuse, shoup ? pl->tw_shoup[t].as<u32>() : nullptr);
           src = tmp;
         }
       } else {
-        hipLaunchKernelGGL((st.wt ? k_ntt_last<P, G, true> : k_ntt_last<P, G, false>), dim3(st.grid), dim3(st.block), st.lds, s, src, d_out, pl->tw_tile[t], sc.li,
-                           st.lgn, st.lgr, st.lg_rows, pl->last_scale, pl->has_last_scale, st.total_rows, fuse, shoup ? pl->tw_shoup[t] : nullptr);
+        hipLaunchKernelGGL((st.wt ? k_ntt_last<P, G, true> : k_ntt_last<P, G, false>), dim3(st.grid), dim3(st.block), st.lds, s, src, d_out, pl->tw_tile[t].as<u32>(), sc.li,
+                           st.lgn, st.lgr, st.lg_rows, pl->last_scale, pl->has_last_scale, st.total_rows, fuse, shoup ? pl->tw_shoup[t].as<u32>() : nullptr);
       }
     }
     MZK_HIP(hipGetLastError());
@@ -1112,7 +1095,7 @@ int ntt_batch_dev_impl(int fid, const uint64_t* root_host, const void* d_in, voi
 template <class P, int LGW>
 static void launch_columns(const NttPlan* pl, const void* d_in, void* d_out, size_t cols, hipStream_t s) {
   hipLaunchKernelGGL((k_ntt_columns<P, LGW>), dim3((unsigned)((cols + 255) / 256)), dim3(256), 0, s, (const u32*)d_in, (u32*)d_out, cols,
-                     (const u32*)pl->tw_tile[0], pl->last_scale, pl->has_last_scale ? 1 : 0);
+                     pl->tw_tile[0].as<u32>(), pl->last_scale, pl->has_last_scale ? 1 : 0);
 }
 template <class P>
 static int columns_dispatch(const NttPlan* pl, unsigned lgw, const void* d_in, void* d_out, size_t cols, hipStream_t s) {

@@ -313,64 +313,7 @@ __global__ __launch_bounds__(256) void k_up_mul(const u32* __restrict__ Phat, co
 }
 
 // ---- host orchestration ----------------------------------------------------------------------------------------
-// Device scratch of the tree routines.  A call makes a dozen buffers whose sizes repeat from call to call; hipMalloc /
-// hipFree cost more than the kernels of a small tree (and hipFree synchronises the device), so released blocks wait in a
-// per-context pool and are handed out again (everything here runs on the context's own stream, so reuse is stream-ordered).
-struct PolyPool {
-  struct Block { void* p; size_t cap; };
-  std::vector<Block> free_blocks;
-  size_t bytes = 0;
-};
-static PolyPool g_poly_pool[MZK_MAX_CTX];
-constexpr size_t POLY_POOL_MAX_BYTES = (size_t)2 << 30;
-void poly_release_plans();
-size_t poly_trim_idle();
-static void poly_release_free_blocks() {
-  PolyPool& pool = g_poly_pool[ctx().index];
-  for (auto& b : pool.free_blocks) (void)hipFree(b.p);
-  pool.free_blocks.clear();
-  pool.bytes = 0;
-}
-void poly_release_pool() {         // shutdown / mzk_trim_workspace: nothing of this file is in use
-  poly_release_plans();            // the cached interpolation plans: their buffers go back into the pool first
-  poly_release_free_blocks();
-}
-struct DevBuf {
-  void* p = nullptr;
-  size_t cap = 0;
-  ~DevBuf() {
-    if (!p) return;
-    PolyPool& pool = g_poly_pool[ctx().index];
-    if (pool.bytes + cap > POLY_POOL_MAX_BYTES) { (void)hipFree(p); return; }
-    pool.free_blocks.push_back({p, cap});
-    pool.bytes += cap;
-  }
-  int alloc(size_t bytes) {
-    size_t want = 4096;
-    while (want < bytes) want <<= 1;                 // sizes are N * element size: powers of two anyway
-    PolyPool& pool = g_poly_pool[ctx().index];
-    for (size_t i = pool.free_blocks.size(); i-- > 0;) {
-      if (pool.free_blocks[i].cap == want) {
-        p = pool.free_blocks[i].p; cap = want;
-        pool.bytes -= want;
-        pool.free_blocks.erase(pool.free_blocks.begin() + (long)i);
-        return MZK_OK;
-      }
-    }
-    if (hipMalloc(&p, want) != hipSuccess) {
-      // the ABI's out-of-memory contract (mzk.h): give back what the running call does not use -- the blocks parked in this pool, the
-      // cached interpolation plans but the one in use, then (dev_alloc) the idle workspace slots -- retry, and what is still refused is
-      // MZK_E_NOMEM, never a bare HIP error
-      (void)hipGetLastError();
-      p = nullptr;
-      (void)poly_trim_idle();
-      MZK_TRY(dev_alloc(&p, want, "polynomial scratch"));
-    }
-    cap = want;
-    return MZK_OK;
-  }
-  u32* w() const { return (u32*)p; }
-};
+// Device scratch of the tree routines: WsBlock (mzk_ws.h), out of the context's pool.
 static inline unsigned grid256(size_t total) { return (unsigned)((total + 255) / 256); }
 
 template <class P> struct PolyTree {
@@ -380,9 +323,9 @@ template <class P> struct PolyTree {
   const HostField* hf;
   uint64_t root[4]; size_t root_order;
   hipStream_t s;
-  std::vector<DevBuf> low;          // low[l]: N elements, polynomials of degree 64 << l
-  std::vector<DevBuf> Zhat;         // Zhat[l] (l < levels): 2N elements, NTT_{2D}(low part) of every level-l polynomial
-  DevBuf U;                         // N scratch
+  std::vector<WsBlock> low;         // low[l]: N elements, polynomials of degree 64 << l
+  std::vector<WsBlock> Zhat;        // Zhat[l] (l < levels): 2N elements, NTT_{2D}(low part) of every level-l polynomial
+  WsBlock U;                        // N scratch
 
   void sub_root(size_t size, uint64_t* out) const {     // primitive `size`-th root from the caller's root
     uint64_t r[4] = {0, 0, 0, 0};
@@ -403,7 +346,7 @@ template <class P> struct PolyTree {
     MZK_TRY(low[0].alloc(N * esz));
     hipLaunchKernelGGL((k_chunk_zerofier<P>), dim3((unsigned)(N / CHUNK)), dim3(64), 0, s, (const u32*)d_domain, n, low[0].w());
     if (levels) MZK_TRY(U.alloc(N * esz));
-    DevBuf shared_T;
+    WsBlock shared_T;
     if (levels && !keep_hats) MZK_TRY(shared_T.alloc(2 * N * esz));
     for (int l = 0; l < levels; l++) {
       const int lgD = 6 + l;
@@ -423,7 +366,7 @@ template <class P> struct PolyTree {
   // values of f (m <= N coefficients, device) at the N padded points -> d_out[0 .. out_n)
   int evaluate(const void* d_f, size_t m, const void* d_domain, void* d_out, size_t out_n) {
     const size_t esz = field_bytes(fid);
-    DevBuf g, inv, A, B, t, V;
+    WsBlock g, inv, A, B, t, V;
     MZK_TRY(g.alloc(N * esz)); MZK_TRY(inv.alloc(N * esz)); MZK_TRY(A.alloc(2 * N * esz)); MZK_TRY(B.alloc(2 * N * esz));
     MZK_TRY(t.alloc(N * esz)); MZK_TRY(V.alloc(2 * N * esz));
     // 1 / rev(Z_pad) mod X^N
@@ -468,7 +411,7 @@ template <class P> struct PolyTree {
   int combine(const void* d_domain, const void* d_w, void* d_out, size_t regs = 1) {
     const size_t esz = field_bytes(fid);
     const size_t M = N * regs;
-    DevBuf cur, nxt, Ph, W;
+    WsBlock cur, nxt, Ph, W;
     MZK_TRY(cur.alloc(M * esz)); MZK_TRY(nxt.alloc(M * esz)); MZK_TRY(Ph.alloc(2 * M * esz)); MZK_TRY(W.alloc(M * esz));
     hipLaunchKernelGGL((k_chunk_combine<P>), dim3((unsigned)(M / CHUNK)), dim3(64), 0, s, (const u32*)d_domain, (const u32*)d_w, n, (const u32*)low[0].w(), cur.w(),
                        N / CHUNK);
@@ -555,7 +498,7 @@ static int zerofier_impl(int fid, const uint64_t* domain, size_t n, const uint64
   }
   PolyTree<P> T;
   MZK_TRY(tree_init(&T, fid, n, root, root_order, s));
-  DevBuf d_dom;
+  WsBlock d_dom;
   MZK_TRY(d_dom.alloc(n * esz));
   MZK_HIP(hipMemcpyAsync(d_dom.p, domain, n * esz, hipMemcpyHostToDevice, s));
   MZK_TRY(T.build(d_dom.p, false));
@@ -579,7 +522,7 @@ static int evaluate_impl(int fid, const uint64_t* coef, size_t m, const uint64_t
   PolyTree<P> T;
   MZK_TRY(check_order_for(n - n / 2, root_order, "fast_evaluate"));           // the larger half's zerofier (ntt.rs:167-168)
   MZK_TRY(tree_init(&T, fid, n, root, root_order, s));
-  DevBuf d_dom, d_f, d_vals;
+  WsBlock d_dom, d_f, d_vals;
   MZK_TRY(d_dom.alloc(n * esz)); MZK_TRY(d_f.alloc((m ? m : 1) * esz)); MZK_TRY(d_vals.alloc(T.N * esz));
   MZK_HIP(hipMemcpyAsync(d_dom.p, domain, n * esz, hipMemcpyHostToDevice, s));
   if (m) MZK_HIP(hipMemcpyAsync(d_f.p, coef, m * esz, hipMemcpyHostToDevice, s));
@@ -851,7 +794,7 @@ static int zerofier_of_prefix(int fid, const uint64_t* domain, size_t n, size_t 
   if (m && !prefix_zerofier_params(hf, domain + nl, n, N, &params)) return MZK_OK;
   // every point is compared on the device; the coefficients are computed behind the comparison without waiting for its answer and
   // thrown away if it says no (one synchronize for both)
-  DevBuf d_dom, d_flag, d_params, d_z;
+  WsBlock d_dom, d_flag, d_params, d_z;
   u32 flag = 1;
   MZK_TRY(d_dom.alloc(n * esz)); MZK_TRY(d_flag.alloc(4));
   std::vector<uint64_t> z;
@@ -895,53 +838,37 @@ struct InterpPlanBase {
 };
 template <class P> struct InterpPlan : InterpPlanBase {
   PolyTree<P> T;
-  DevBuf d_dom, d_zp;        // the domain; 1 / Z'(d_i)
+  WsBlock d_dom, d_zp;       // the domain; 1 / Z'(d_i)
   // a prefix of a power-of-two subgroup (see k_prefix_weights): no tree; the generator, the subgroup's order, the number of its points
   // that are missing and the weights that give the interpolant's values there
   bool prefix = false;
   uint64_t g[4] = {0, 0, 0, 0};
   size_t pN = 0, pm = 0;
-  DevBuf d_C;
+  WsBlock d_C;
 };
-static std::vector<InterpPlanBase*> g_interp_plans[MZK_MAX_CTX];
+static std::vector<std::unique_ptr<InterpPlanBase>> g_interp_plans[MZK_MAX_CTX];
 static InterpPlanBase* g_interp_busy[MZK_MAX_CTX];     // the cached plan the running call works with: never evicted under it
-static uint64_t g_interp_stamp = 0;
 constexpr size_t INTERP_MAX_PLANS = 4;
 constexpr size_t INTERP_MAX_BYTES = (size_t)1 << 30;
 void poly_release_plans() {
-  auto& v = g_interp_plans[ctx().index];
-  for (auto* p : v) delete p;
-  v.clear();
+  g_interp_plans[ctx().index].clear();
   g_interp_busy[ctx().index] = nullptr;
 }
-// Device bytes this file holds on the current context outside any call: blocks parked in the pool + the cached plans (their own
-// estimate).  Part of mzk_workspace_bytes and of the workspace budget.
-size_t poly_bytes_held() {
-  size_t t = g_poly_pool[ctx().index].bytes;
-  for (auto* b : g_interp_plans[ctx().index]) t += b->bytes;
-  return t;
-}
-// Everything here the RUNNING call does not use goes back to the device: the cached plans but the busy one (their buffers pass
-// through the pool), then the parked blocks.  Returns the bytes released.  Called when an allocation was refused or would exceed
-// the budget (ws_trim_idle) and by mzk_trim_workspace.
-size_t poly_trim_idle() {
-  const size_t before = poly_bytes_held();
+// The cached plans but the busy one go, their buffers into the pool, from where ws_trim_idle frees them: when an allocation was
+// refused or would exceed the budget, and in mzk_trim_workspace.
+void poly_drop_idle_plans() {
   auto& v = g_interp_plans[ctx().index];
   InterpPlanBase* busy = g_interp_busy[ctx().index];
   bool any = false;
   for (size_t i = v.size(); i-- > 0;) {
-    if (v[i] == busy) continue;
+    if (v[i].get() == busy) continue;
     if (!any) { (void)hipDeviceSynchronize(); any = true; }      // a plan's buffers may still be read by enqueued work of an earlier call
-    delete v[i];
     v.erase(v.begin() + (long)i);
   }
-  poly_release_free_blocks();
-  const size_t after = poly_bytes_held();
-  return before > after ? before - after : 0;
 }
 // the domain of an interpolation is canonical if a cached plan was built from exactly these limbs (it was checked then); otherwise check it now
 static int interp_check_domain(int fid, const HostField* hf, const uint64_t* domain, size_t n) {
-  for (auto* b : g_interp_plans[ctx().index])
+  for (auto& b : g_interp_plans[ctx().index])
     if (b->fid == fid && b->n == n && n && !memcmp(b->domain.data(), domain, n * (size_t)hf->nl * 8)) return MZK_OK;
   return check_canonical(hf, domain, n, "domain");
 }
@@ -950,24 +877,24 @@ static int interp_plan_get(int fid, const uint64_t* domain, size_t n, const uint
   *transient = false;
   auto& v = g_interp_plans[ctx().index];
   const size_t nl = (size_t)host_field(fid)->nl;
-  for (auto* b : v) {
+  for (auto& b : v) {
     if (b->fid == fid && b->n == n && !memcmp(b->domain.data(), domain, n * nl * 8)) {
-      b->stamp = ++g_interp_stamp;
-      *out = static_cast<InterpPlan<P>*>(b);
+      b->stamp = lru_stamp();
+      *out = static_cast<InterpPlan<P>*>(b.get());
       return MZK_OK;
     }
   }
   const size_t esz = field_bytes(fid);
   const HostField* hf = host_field(fid);
-  InterpPlan<P>* pl = new InterpPlan<P>();
+  std::unique_ptr<InterpPlan<P>> pl(new InterpPlan<P>());
   pl->fid = fid; pl->n = n;
   int rc = tree_init(&pl->T, fid, n, root, root_order, s);
-  DevBuf d_dz, d_zpv;
+  WsBlock d_dz, d_zpv;
   if (rc == MZK_OK) rc = pl->d_dom.alloc(n * esz);
   if (rc == MZK_OK && hipMemcpyAsync(pl->d_dom.p, domain, n * esz, hipMemcpyHostToDevice, s) != hipSuccess) rc = hip_fail(hipGetLastError(), "hipMemcpyAsync", __FILE__, __LINE__);
   std::vector<uint64_t> ainv;
   if (rc == MZK_OK && prefix_candidate(hf, domain, n, &pl->pN)) {
-    DevBuf d_flag;
+    WsBlock d_flag;
     u32 flag = 1;
     rc = d_flag.alloc(4);
     if (rc == MZK_OK) rc = prefix_check_launch<P>(pl->d_dom.p, n, (u32*)d_flag.p, s);
@@ -980,7 +907,7 @@ static int interp_plan_get(int fid, const uint64_t* domain, size_t n, const uint
   }
   if (rc == MZK_OK && pl->prefix && pl->pm) {
     const size_t m = pl->pm;
-    DevBuf d_ainv;
+    WsBlock d_ainv;
     rc = d_ainv.alloc(m * m * esz);
     if (rc == MZK_OK) rc = pl->d_C.alloc(m * n * esz);
     if (rc == MZK_OK && hipMemcpyAsync(d_ainv.p, ainv.data(), m * m * esz, hipMemcpyHostToDevice, s) != hipSuccess) rc = hip_fail(hipGetLastError(), "hipMemcpyAsync", __FILE__, __LINE__);
@@ -1007,23 +934,22 @@ static int interp_plan_get(int fid, const uint64_t* domain, size_t n, const uint
     if (rc == MZK_OK) rc = pointwise_div_shared_dev(fid, d_dz.p, n, d_zpv.p, pl->d_zp.p, n, n, 1, s);
     if (hipStreamSynchronize(s) != hipSuccess && rc == MZK_OK) rc = hip_fail(hipGetLastError(), "hipStreamSynchronize", __FILE__, __LINE__);      // `ones` is read until here
   }
-  if (rc != MZK_OK) { (void)hipStreamSynchronize(s); delete pl; return rc; }
+  if (rc != MZK_OK) { (void)hipStreamSynchronize(s); return rc; }
   pl->domain.assign(domain, domain + n * nl);
-  pl->stamp = ++g_interp_stamp;
+  pl->stamp = lru_stamp();
   pl->bytes = pl->prefix ? (pl->pm + 1) * n * esz : (size_t)(3 * pl->T.levels + 4) * pl->T.N * esz;
   size_t total = pl->bytes;
-  for (auto* b : v) total += b->bytes;
-  while (pl->bytes <= INTERP_MAX_BYTES && !v.empty() && (v.size() >= INTERP_MAX_PLANS || total > INTERP_MAX_BYTES)) {      // least recently used first; their buffers return to the pool
-    size_t victim = 0;
-    for (size_t i = 1; i < v.size(); i++) if (v[i]->stamp < v[victim]->stamp) victim = i;
-    (void)hipStreamSynchronize(s);
-    total -= v[victim]->bytes;
-    delete v[victim];
-    v.erase(v.begin() + (long)victim);
+  for (auto& b : v) total += b->bytes;
+  const bool keep = pl->bytes <= INTERP_MAX_BYTES;      // larger (2^22 points and up): the caller deletes it after use
+  while (keep && !v.empty() && (v.size() >= INTERP_MAX_PLANS || total > INTERP_MAX_BYTES)) {      // least recently used first; their buffers return to the pool
+    MZK_TRY(lru_evict(v, v.size(), s));
+    total = pl->bytes;
+    for (auto& b : v) total += b->bytes;
   }
-  if (pl->bytes <= INTERP_MAX_BYTES) v.push_back(pl);
-  else *transient = true;           // too large to keep (2^22 points and up): the caller deletes it after use, as before round 5
-  *out = pl;
+  *transient = !keep;
+  *out = pl.get();
+  if (keep) v.push_back(std::move(pl));
+  else (void)pl.release();
   return MZK_OK;
 }
 
@@ -1073,7 +999,7 @@ static int interpolate_impl(int fid, const uint64_t* domain, const uint64_t* val
     int lgN = 0;
     while (((size_t)1 << lgN) < N) lgN++;
     const size_t group = std::max<size_t>(1, std::min<size_t>(std::min<size_t>(batch, ((size_t)1 << 24) / N), 65535));      // (65535: the register index is a grid's y)
-    DevBuf d_vals, d_ext, d_lens;
+    WsBlock d_vals, d_ext, d_lens;
     if (!on_device) MZK_TRY(d_vals.alloc(group * n * esz));
     MZK_TRY(d_ext.alloc(group * N * esz)); MZK_TRY(d_lens.alloc(group * 4 + 64));
     std::vector<u32> lens(group);
@@ -1095,11 +1021,11 @@ static int interpolate_impl(int fid, const uint64_t* domain, const uint64_t* val
     return MZK_OK;
   }
   PolyTree<P>& T = plan->T;
-  DevBuf& d_dom = plan->d_dom;
-  DevBuf& d_zp = plan->d_zp;
+  WsBlock& d_dom = plan->d_dom;
+  WsBlock& d_zp = plan->d_zp;
   // registers go through the up-sweep in groups (at most 2^24 elements per buffer)
   const size_t group = std::max<size_t>(1, std::min<size_t>(batch, ((size_t)1 << 24) / T.N));
-  DevBuf d_vals, d_ws, d_ress, d_lens;
+  WsBlock d_vals, d_ws, d_ress, d_lens;
   if (!on_device) MZK_TRY(d_vals.alloc(group * n * esz));
   MZK_TRY(d_ws.alloc(group * T.N * esz)); MZK_TRY(d_ress.alloc(group * T.N * esz)); MZK_TRY(d_lens.alloc(group * 4 + 64));
   std::vector<u32> lens(group);

@@ -228,7 +228,7 @@ namespace mzk {
 static void stark_release(mzk_stark* h) {
   if (!h) return;
   for (char* p : {h->d_tz, h->d_tz_cw, h->d_vals, h->d_point, h->d_bq, h->d_cw, h->d_tpoly, h->d_tq, h->d_lin, h->d_comb, h->d_comb_cw, h->d_fri, h->d_stage})
-    if (p) (void)hipFree(p);
+    if (p) (void)ws_hook_free(p);
   if (h->tz_tree) mzk_merkle_free(h->tz_tree);
   delete h;
 }
@@ -487,7 +487,7 @@ int mzk_stark_prove(mzk_stark* h, const uint64_t* trace, size_t n_rows, const si
   for (size_t i = 0; i < n_boundary; i++) if (!h_is_canonical(hf, boundary_values + i * nl)) { set_error("stark_prove: boundary value %zu not canonical", i); return MZK_E_RANGE; }
   const size_t need = (nt + nr + 2) * esz + total + 64;
   if (need > h->stage_bytes) {
-    if (h->d_stage) { (void)hipDeviceSynchronize(); (void)hipFree(h->d_stage); h->d_stage = nullptr; h->stage_bytes = 0; }
+    if (h->d_stage) { (void)hipDeviceSynchronize(); (void)ws_hook_free(h->d_stage); h->d_stage = nullptr; h->stage_bytes = 0; }
     MZK_TRY(dev_alloc((void**)&h->d_stage, need, "stark staging"));
     h->stage_bytes = need;
   }

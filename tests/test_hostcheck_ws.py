@@ -1,6 +1,6 @@
 """The workspace's bookkeeping (myzkp_amd/csrc/mzk_ws.h: leased scratch slots, the refusal of a held slot, growth, the trim after a
-refused allocation, the budget, the cache generation) run on the host by tests/hostcheck/ws_shim.cpp, a stand-alone program built with
--fsanitize=address,undefined whose device hooks are malloc, free and a counter.  The program asserts the rules one by one and prints
+refused allocation, the budget, the cache generation, the pool of size classes, the plan caches' eviction) run on the host by tests/hostcheck/ws_shim.cpp, a stand-alone program built with
+-fsanitize=address,undefined whose device hooks are malloc, free and two counters.  The program asserts the rules one by one and prints
 "ok <letter>" for each; a block freed under a live lease or left behind at exit is the sanitizer's report.  CPU only."""
 import os, subprocess
 import pytest
@@ -15,7 +15,18 @@ RULES = {
     "f": "the same slot on two contexts does not collide",
     "g": "a frame that took nothing, and one destroyed after an early error return, leave no holder behind",
     "h": "everything is given back at shutdown: no leak at exit",
+    "i": "a pool request is rounded to a power of two, 4096 at least; a released block of that class is handed out again with no hook "
+         "call; another class allocates",
+    "j": "with the pool's cap lowered, a release that would pass it frees the block instead of parking it",
+    "k": "a refused pool allocation releases the parked blocks and the idle slots and is retried; refused twice it is MZK_E_NOMEM, the "
+         "message naming the request",
+    "l": "ws_bytes_held counts parked and lent bytes; ws_trim_idle returns exactly what it freed and leaves lent blocks live",
+    "m": "a block taken on context 0 and destroyed while context 1 is current returns to context 0's pool",
+    "n": "lru_evict removes the entry with the oldest stamp once the cap is reached, frees its memory exactly once, and removes "
+         "nothing below the cap",
+    "o": "ws_release_all on both contexts leaves nothing live, parked blocks included",
 }
+CSRC = os.path.join(os.path.dirname(HERE), "myzkp_amd", "csrc")
 
 
 @pytest.fixture(scope="module")
@@ -37,3 +48,14 @@ def test_the_program_ends_clean_under_the_sanitizers(run):
 @pytest.mark.parametrize("rule", sorted(RULES))
 def test_rule(run, rule):
     assert "ok " + rule in run.stdout.splitlines(), RULES[rule] + "\n" + run.stdout[-2000:] + run.stderr[-2000:]
+
+
+@pytest.mark.parametrize("call", ["hipMalloc(", "hipFree("])
+def test_device_memory_has_one_way_in_and_one_way_out(call):
+    """every allocation passes ws_hook_alloc and every release ws_hook_free, both in mzk_api.hip, where mzk_ws.h meets the device"""
+    hits = []
+    for name in sorted(os.listdir(CSRC)):
+        if name.endswith((".hip", ".h")):
+            with open(os.path.join(CSRC, name)) as f:
+                hits += [(name, no) for no, line in enumerate(f, 1) for _ in range(line.count(call))]
+    assert [name for name, _ in hits] == ["mzk_api.hip"], hits
