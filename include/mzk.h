@@ -888,6 +888,57 @@ enum { MZK_PROBE_G1_MADD_SIGNED = 0, MZK_PROBE_G1_MADD = 1, MZK_PROBE_G1_ADD = 2
 int mzk_selftest_field_probe(int field_id, int op, int form, size_t n, const uint32_t* in, uint32_t* out);
 int mzk_selftest_g1_probe(int op, int form, size_t n, const uint32_t* a, const uint32_t* b, const uint8_t* neg, uint32_t* out);
 
+/* ---- Reed-Solomon over GF(2^8) (algebra/reedsolomon.rs) ------------------------------------------------------------ */
+/* The codec every data-availability system of das/ starts with (das/avail.rs, das/eigenda.rs, das/celestia.rs), batched: every chunk,
+ * row and column is an independent codeword.  The field is ExtendedFieldElement<Mod2, Ip0x11D> (reedsolomon.rs:352-371): a byte is a
+ * polynomial over GF(2), bit i the coefficient of x^i, modulo x^8 + x^4 + x^3 + x^2 + 1; the generator of every code is x = 0x02
+ * (setup_rs1d / setup_rs2d, :396-416).  A symbol is one byte on both sides of the boundary; no call takes a field id.
+ *   (n, k): 1 <= k <= n <= 255, d = n - k parity symbols, t = d / 2 correctable errors; d = 0 makes encode and decode copies.  Anything
+ *   else is MZK_E_ARG: 2 has order 255, so from n = 256 on the reference's evaluation points repeat and its own decoder stops
+ *   correcting.  batch: 1 .. 2^31 codewords (MZK_E_ARG outside).
+ *   Messages are exactly k bytes.  The reference accepts a shorter message (reedsolomon.rs:54-78): that is the same call with the message
+ *   zero-padded at the top.  Codewords are exactly n bytes: (m(x) x^d mod g) in positions 0 .. d-1, the message in d .. n-1.  The
+ *   reference's vector is this one with its trailing zero symbols trimmed (its Polynomial subtraction trims, :76-77): shorter than n
+ *   whenever the top message bytes are zero, empty for the zero message.
+ *   status, one byte per codeword: 0 = all syndromes zero, the word is returned as it came; 1 .. = the number of symbols corrected
+ *   (the degree of the error locator, all of whose roots were found); 255 = the reference's None (root count != degree, or a zero
+ *   derivative in Forney's formula, :225-245) -- corrected / messages then hold the received word unchanged.  Beyond t errors the
+ *   reference either gives up or miscorrects to another codeword; the status says which, the call itself returns MZK_OK.
+ * Host forms take host pointers and return MZK_E_NOGPU without a device; the _dev forms take device pointers and only enqueue. */
+/* generator_polynomial (:34-37) = prod_{i<d} (x - 2^i), n - k + 1 coefficients from the constant term up.  Host arithmetic: works without a GPU. */
+int mzk_rs_generator_poly(size_t n, size_t k, uint8_t* g);
+/* encode (:54-78) of `batch` messages, k bytes each, into `batch` codewords, n bytes each.
+ * d_columns_fr (may be NULL): the codewords once more as BN254 Fr elements (4 x uint64_t, value = the byte), symbol-major: element
+ * i * batch + b is symbol i of codeword b -- n polynomials of `batch` coefficients, the layout
+ * mzk_kzg_commit_srs_many_dev(srs, d_columns_fr, batch, n, ...) takes, so that Avail's commit (das/avail.rs:87-98) follows its encode
+ * with no host step in between.
+ * _view_dev: both sides as views -- symbol s of item b at base + b * stride + s * symbol_stride (bytes) -- so that columns of a
+ * row-major matrix are encoded where they lie.  In place is allowed in exactly one form: the message already sits in positions
+ * d .. n-1 of its codeword (d_messages = d_codewords + d * cw_symbol_stride, equal strides); any other overlap is undefined. */
+int mzk_rs_encode(size_t n, size_t k, const uint8_t* messages, size_t batch, uint8_t* codewords);
+int mzk_rs_encode_dev(size_t n, size_t k, const void* d_messages, size_t batch, void* d_codewords, void* d_columns_fr, void* stream);
+int mzk_rs_encode_view_dev(size_t n, size_t k, const void* d_messages, size_t msg_symbol_stride, size_t msg_stride, size_t batch, void* d_codewords,
+                           size_t cw_symbol_stride, size_t cw_stride, void* d_columns_fr, void* stream);
+/* compute_syndromes (:90-102): S_j = sum_i r_i 2^(i j), j < d; d bytes per word (nothing is written when d = 0). */
+int mzk_rs_syndromes(size_t n, size_t k, const uint8_t* words, size_t batch, uint8_t* syndromes);
+int mzk_rs_syndromes_dev(size_t n, size_t k, const void* d_words, size_t batch, void* d_syndromes, void* stream);
+/* correct_errors (:206-253) and decode (:80-86): corrected = n bytes per word, messages = corrected[d ..] = k bytes per word; either
+ * may be NULL.  status: see above. */
+int mzk_rs_decode(size_t n, size_t k, const uint8_t* received, size_t batch, uint8_t* corrected, uint8_t* messages, uint8_t* status);
+int mzk_rs_decode_dev(size_t n, size_t k, const void* d_received, size_t batch, void* d_corrected, void* d_messages, void* d_status, void* stream);
+/* ReedSolomon2D (:256-350): size = ceil(sqrt(message_len)), rows coded (row_n, size), columns (col_n, size); message_len >= 1 and
+ * size <= min(col_n, row_n) (MZK_E_ARG otherwise, in the words of the 1D code).  code = col_n rows of row_n bytes, row-major, the data at
+ * [col_n - size + i][row_n - size + j].  The reference's transposes mis-handle rows that its encode trimmed (they truncate, or panic
+ * when the first row is the shortest); these calls work on fixed-length rows: the reference's result wherever it does neither.
+ * decode: every column, then every one of the `size` rows; *ok = 0 is the reference's None (a column or a row with status 255; data is
+ * then not meaningful).  col_status (row_n bytes) / row_status (size bytes) may be NULL; the row statuses mean nothing when a
+ * column failed (the reference returns before it decodes a row).  _dev: d_ok is a device int. */
+int mzk_rs2d_encode(size_t col_n, size_t row_n, const uint8_t* data, size_t message_len, uint8_t* code);
+int mzk_rs2d_encode_dev(size_t col_n, size_t row_n, const void* d_data, size_t message_len, void* d_code, void* stream);
+int mzk_rs2d_decode(size_t col_n, size_t row_n, const uint8_t* code, size_t message_len, uint8_t* data, int* ok, uint8_t* col_status, uint8_t* row_status);
+int mzk_rs2d_decode_dev(size_t col_n, size_t row_n, const void* d_code, size_t message_len, void* d_data, int* d_ok, void* d_col_status, void* d_row_status,
+                        void* stream);
+
 /* Deterministic synthetic inputs (bench + tests): bit-identical to the oracle's orc_synth_*. */
 int mzk_synth_field_dev(int field_id, uint64_t seed, size_t n, void* d_out, void* stream);
 int mzk_synth_g1_points_dev(uint64_t seed, size_t n, void* d_out_xy, void* stream);

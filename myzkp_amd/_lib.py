@@ -1436,3 +1436,116 @@ def kzg_setup_g2(alpha, max_d, g2):
     out = np.zeros((max_d + 1, 16), dtype=np.uint64)
     _check(lib().mzk_kzg_setup_g2(_p(a), _p(g), ctypes.c_size_t(max_d), _p(out)))
     return out
+
+
+# ---- Reed-Solomon over GF(2^8) (algebra/reedsolomon.rs): symbols are bytes, arrays numpy uint8 ---------------------------------------
+RS_NONE = 255      # the status of a word the reference's decoder returns None for
+
+
+def _sz(v):
+    return ctypes.c_size_t(int(v))
+
+
+def _bytes2d(a, width, what):
+    a = np.ascontiguousarray(a, dtype=np.uint8)
+    if a.ndim == 1:
+        a = a.reshape(1, -1)
+    if a.ndim != 2 or a.shape[1] != width:
+        raise MzkError(-5, "%s: expected rows of %d bytes, got shape %s" % (what, width, a.shape))
+    return a
+
+
+def rs_generator_poly(n, k):
+    """generator_polynomial (reedsolomon.rs:34-37): n - k + 1 coefficients from the constant term up.  Host arithmetic: no GPU needed."""
+    g = np.zeros(max(int(n) - int(k), 0) + 1, dtype=np.uint8)
+    _check(lib().mzk_rs_generator_poly(_sz(n), _sz(k), _p(g)))
+    return g
+
+
+def rs_encode(n, k, messages):
+    """encode (reedsolomon.rs:54-78) of every row of `messages` (batch x k bytes): batch x n bytes, fixed length (the reference's
+    vector is this one without its trailing zeros)."""
+    m = _bytes2d(messages, k, "rs_encode")
+    out = np.empty((m.shape[0], n), dtype=np.uint8)
+    _check(lib().mzk_rs_encode(_sz(n), _sz(k), _p(m), _sz(m.shape[0]), _p(out)))
+    return out
+
+
+def rs_encode_dev(n, k, d_messages, batch, d_codewords, d_columns_fr=None, stream=None):
+    """mzk_rs_encode_dev: device pointers (ints); d_columns_fr (optional): n x batch Fr elements, symbol-major.  Only enqueues."""
+    _check(lib().mzk_rs_encode_dev(_sz(n), _sz(k), ctypes.c_void_p(int(d_messages)), _sz(batch), ctypes.c_void_p(int(d_codewords)),
+                                   ctypes.c_void_p(int(d_columns_fr)) if d_columns_fr else None, ctypes.c_void_p(stream)))
+
+
+def rs_encode_view_dev(n, k, d_messages, msg_symbol_stride, msg_stride, batch, d_codewords, cw_symbol_stride, cw_stride, d_columns_fr=None, stream=None):
+    """mzk_rs_encode_view_dev: symbol s of item b at base + b * stride + s * symbol_stride on both sides.  Only enqueues."""
+    _check(lib().mzk_rs_encode_view_dev(_sz(n), _sz(k), ctypes.c_void_p(int(d_messages)), _sz(msg_symbol_stride), _sz(msg_stride), _sz(batch),
+                                        ctypes.c_void_p(int(d_codewords)), _sz(cw_symbol_stride), _sz(cw_stride),
+                                        ctypes.c_void_p(int(d_columns_fr)) if d_columns_fr else None, ctypes.c_void_p(stream)))
+
+
+def rs_syndromes(n, k, words):
+    """compute_syndromes (reedsolomon.rs:90-102) of every row of `words` (batch x n bytes): batch x (n - k) bytes."""
+    w = _bytes2d(words, n, "rs_syndromes")
+    out = np.zeros((w.shape[0], n - k), dtype=np.uint8)
+    _check(lib().mzk_rs_syndromes(_sz(n), _sz(k), _p(w), _sz(w.shape[0]), _p(out)))
+    return out
+
+
+def rs_syndromes_dev(n, k, d_words, batch, d_syndromes, stream=None):
+    _check(lib().mzk_rs_syndromes_dev(_sz(n), _sz(k), ctypes.c_void_p(int(d_words)), _sz(batch), ctypes.c_void_p(int(d_syndromes)), ctypes.c_void_p(stream)))
+
+
+def rs_decode(n, k, received, with_corrected=False):
+    """decode (reedsolomon.rs:80-86) of every row of `received` (batch x n bytes): (messages batch x k, status batch) -- status 0
+    clean, else the number of corrected symbols, RS_NONE (255) where the reference returns None (that row of messages is then the
+    received one).  with_corrected: (corrected batch x n, messages, status)."""
+    r = _bytes2d(received, n, "rs_decode")
+    batch = r.shape[0]
+    msgs = np.empty((batch, k), dtype=np.uint8)
+    status = np.empty(batch, dtype=np.uint8)
+    corr = np.empty((batch, n), dtype=np.uint8) if with_corrected else None
+    _check(lib().mzk_rs_decode(_sz(n), _sz(k), _p(r), _sz(batch), _p(corr) if with_corrected else None, _p(msgs), _p(status)))
+    return (corr, msgs, status) if with_corrected else (msgs, status)
+
+
+def rs_decode_dev(n, k, d_received, batch, d_corrected, d_messages, d_status, stream=None):
+    """mzk_rs_decode_dev: device pointers (ints); d_corrected or d_messages may be None.  Only enqueues."""
+    opt = lambda p: ctypes.c_void_p(int(p)) if p else None
+    _check(lib().mzk_rs_decode_dev(_sz(n), _sz(k), ctypes.c_void_p(int(d_received)), _sz(batch), opt(d_corrected), opt(d_messages),
+                                   ctypes.c_void_p(int(d_status)), ctypes.c_void_p(stream)))
+
+
+def rs2d_encode(col_n, row_n, data):
+    """ReedSolomon2D::encode (reedsolomon.rs:274-295) of `data` (message_len bytes): col_n x row_n bytes."""
+    d = np.ascontiguousarray(data, dtype=np.uint8).reshape(-1)
+    out = np.empty((col_n, row_n), dtype=np.uint8)
+    _check(lib().mzk_rs2d_encode(_sz(col_n), _sz(row_n), _p(d), _sz(d.shape[0]), _p(out)))
+    return out
+
+
+def rs2d_encode_dev(col_n, row_n, d_data, message_len, d_code, stream=None):
+    _check(lib().mzk_rs2d_encode_dev(_sz(col_n), _sz(row_n), ctypes.c_void_p(int(d_data)), _sz(message_len), ctypes.c_void_p(int(d_code)), ctypes.c_void_p(stream)))
+
+
+def rs2d_decode(col_n, row_n, code, message_len, with_status=False):
+    """ReedSolomon2D::decode (reedsolomon.rs:297-324) of `code` (col_n x row_n bytes): message_len bytes, or None where the reference
+    returns None.  with_status: (data or None, column statuses, row statuses)."""
+    c = _bytes2d(code, row_n, "rs2d_decode")
+    if c.shape[0] != col_n:
+        raise MzkError(-5, "rs2d_decode: expected %d rows, got %d" % (col_n, c.shape[0]))
+    size = 0
+    while size * size < message_len:
+        size += 1
+    data = np.empty(message_len, dtype=np.uint8)
+    ok = ctypes.c_int(0)
+    cs, rs = np.empty(row_n, dtype=np.uint8), np.empty(size, dtype=np.uint8)
+    _check(lib().mzk_rs2d_decode(_sz(col_n), _sz(row_n), _p(c), _sz(message_len), _p(data), ctypes.byref(ok), _p(cs), _p(rs)))
+    res = data if ok.value else None
+    return (res, cs, rs) if with_status else res
+
+
+def rs2d_decode_dev(col_n, row_n, d_code, message_len, d_data, d_ok, d_col_status=None, d_row_status=None, stream=None):
+    opt = lambda p: ctypes.c_void_p(int(p)) if p else None
+    _check(lib().mzk_rs2d_decode_dev(_sz(col_n), _sz(row_n), ctypes.c_void_p(int(d_code)), _sz(message_len), ctypes.c_void_p(int(d_data)),
+                                     ctypes.c_void_p(int(d_ok)), opt(d_col_status), opt(d_row_status), ctypes.c_void_p(stream)))

@@ -451,6 +451,7 @@ void mzk_shutdown(void) {
     (void)hipSetDevice(c.device);
     (void)hipDeviceSynchronize();
     ntt_release_plans();
+    rs_release_plans();
     kzg_release_cache();
     poly_release_plans();          // their blocks park in the pool, which goes next
     ws_release_all();

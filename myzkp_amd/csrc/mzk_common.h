@@ -223,6 +223,7 @@ int gl_fri_fold_dev(int fid, const void* d_cw, size_t n, const uint64_t* alpha, 
 int gl_fri_fold_dev_alpha(int fid, const void* d_cw, size_t n, const uint64_t* d_alpha, uint64_t half, uint64_t oinv, uint64_t winv, void* d_out,
                           hipStream_t s);       // alpha: NC canonical words in device memory
 void gl_release_plans();
+void rs_release_plans();        // mzk_rs.hip: Reed-Solomon tables of the current context
 void kzg_release_cache();       // mzk_kzg.hip: fixed-base tables of the current context
 void poly_release_plans();      // mzk_poly.hip: cached interpolation plans of the current context
 int fri_fold_dev_impl(int fid, const void* d_cw, size_t n, const uint64_t* alpha, const uint64_t* offset, const uint64_t* omega,

@@ -22,6 +22,8 @@
 //   boundary_quotients, fast_stark_dims      zkstark/fast_stark.rs:217-224, :573-616 -> mzk_poly_div_roots, mzk_stark_plan
 //   FastStark (preprocess, prove), FastStarkProof   zkstark/fast_stark.rs:22-75, :177-396 -> mzk_stark_new, mzk_stark_prove
 //   batch::split_and_fold / commit_gemini / open_gemini / prove_sumcheck   algebra/gemini.rs:51-144, algebra/sumcheck.rs:128-167
+//   ReedSolomon, ReedSolomon2D, setup_rs1d / encode_rs1d / decode_rs1d, setup_rs2d / encode_rs2d / decode_rs2d
+//                                            algebra/reedsolomon.rs:20-350, :396-455 -> mzk_rs_*, mzk_rs2d_*
 //
 // Values are held canonical (u64 limbs) -- the ABI wire format; arithmetic on single elements that the
 // reference does on the host (a handful of scalar ops in tests) is not offered here: this header only
@@ -37,6 +39,7 @@
 #include <type_traits>
 #include <utility>
 #include <map>
+#include <optional>
 #include <vector>
 #include <exception>
 #include "../../include/mzk.h"
@@ -1070,5 +1073,73 @@ struct SumCheckProverGPU {
     return {sum, std::vector<uint8_t>(tx, tx + len)};
   }
 };
+
+// ---- Reed-Solomon over GF(2^8) (algebra/reedsolomon.rs) ----------------------------------------------------------------------------
+// ReedSolomon<GF2to8> / ReedSolomon2D<GF2to8> with g = x (setup_rs1d / setup_rs2d, :396-416); symbols are bytes.  The library works on
+// fixed lengths (n symbols per codeword, k per message); encode_rs1d gives the reference's vector -- trailing zero symbols trimmed,
+// reedsolomon.rs:76-77 -- and encode_rs1d_fixed, beside it, all n symbols.  A received word shorter than n is the same word with zeros at
+// the top, which is what the reference's sums make of it.
+struct ReedSolomon {
+  size_t n, k, d;
+  ReedSolomon(size_t n_, size_t k_) : n(n_), k(k_), d(n_ - k_) {
+    if (n_ < k_) throw Panic(MZK_E_ARG, "n must be at least k");                                   // :29
+  }
+  std::vector<uint8_t> generator_polynomial() const {                                               // :34-37
+    std::vector<uint8_t> g(d + 1);
+    expect(mzk_rs_generator_poly(n, k, g.data()));
+    return g;
+  }
+};
+struct ReedSolomon2D {
+  size_t col_n, row_n, message_len;
+  ReedSolomon2D(size_t c, size_t r, size_t len) : col_n(c), row_n(r), message_len(len) {}
+};
+inline ReedSolomon setup_rs1d(size_t codeword_len, size_t message_len) { return ReedSolomon(codeword_len, message_len); }
+inline ReedSolomon2D setup_rs2d(size_t col_codeword_len, size_t row_codeword_len, size_t message_len) {
+  return ReedSolomon2D(col_codeword_len, row_codeword_len, message_len);
+}
+inline std::vector<uint8_t> encode_rs1d_fixed(const std::vector<uint8_t>& message, const ReedSolomon& rs) {
+  if (message.size() > rs.k) throw Panic(MZK_E_LENGTH, "Received message must be less than or equal to k");      // :55-60
+  std::vector<uint8_t> m(message), code(rs.n);
+  m.resize(rs.k, 0);
+  expect(mzk_rs_encode(rs.n, rs.k, m.data(), 1, code.data()));
+  return code;
+}
+inline std::vector<uint8_t> encode_rs1d(const std::vector<uint8_t>& message, const ReedSolomon& rs) {             // :418-428
+  std::vector<uint8_t> code = encode_rs1d_fixed(message, rs);
+  while (!code.empty() && code.back() == 0) code.pop_back();
+  return code;
+}
+inline std::optional<std::vector<uint8_t>> decode_rs1d(const std::vector<uint8_t>& code, const ReedSolomon& rs) {  // :430-433
+  if (code.size() > rs.n) throw Panic(MZK_E_LENGTH, "Received codeword must have length n");                       // :207-212
+  if (code.size() < rs.d) return std::nullopt;                                                                    // :82-84
+  std::vector<uint8_t> r(code), message(rs.k);
+  r.resize(rs.n, 0);
+  uint8_t status = 0;
+  expect(mzk_rs_decode(rs.n, rs.k, r.data(), 1, nullptr, message.data(), &status));
+  if (status == 255) return std::nullopt;
+  message.resize(code.size() - rs.d);                                                                             // corrected[d..] of a word of code.size() symbols
+  return message;
+}
+inline std::vector<std::vector<uint8_t>> encode_rs2d(const std::vector<uint8_t>& message, const ReedSolomon2D& rs) {      // :435-445
+  std::vector<uint8_t> flat(rs.col_n * rs.row_n);
+  expect(mzk_rs2d_encode(rs.col_n, rs.row_n, message.data(), message.size(), flat.data()));
+  std::vector<std::vector<uint8_t>> code(rs.col_n);
+  for (size_t r = 0; r < rs.col_n; r++) code[r].assign(flat.begin() + r * rs.row_n, flat.begin() + (r + 1) * rs.row_n);
+  return code;
+}
+inline std::optional<std::vector<uint8_t>> decode_rs2d(const std::vector<std::vector<uint8_t>>& code, const ReedSolomon2D& rs) {      // :447-455
+  if (code.size() != rs.col_n) throw Panic(MZK_E_LENGTH, "decode_rs2d: the code must have col_codeword_len rows");
+  std::vector<uint8_t> flat;
+  for (const auto& row : code) {
+    if (row.size() != rs.row_n) throw Panic(MZK_E_LENGTH, "decode_rs2d: every row must have row_codeword_len symbols");
+    flat.insert(flat.end(), row.begin(), row.end());
+  }
+  std::vector<uint8_t> data(rs.message_len);
+  int ok = 0;
+  expect(mzk_rs2d_decode(rs.col_n, rs.row_n, flat.data(), rs.message_len, data.data(), &ok, nullptr, nullptr));
+  if (!ok) return std::nullopt;
+  return data;
+}
 
 }  // namespace myzkp
