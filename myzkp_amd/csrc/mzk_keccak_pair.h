@@ -1,6 +1,6 @@
 // mzk_keccak_pair.h -- Keccak-f[1600] on a pair of lanes and SHAKE256 over a byte stream on top of it, shared by the translation
-// units that hash on a nearly empty GPU: the upper levels of a Merkle tree and the proof stream of FRI::prove (mzk_merkle.hip), the
-// proof stream of the product sum-check (mzk_sumcheck.hip).  Device code only; the library is built without relocatable device code,
+// units that hash on a nearly empty GPU: the upper levels of a Merkle tree (mzk_merkle.hip), the proof stream of FRI::prove
+// (mzk_fri.hip), the proof stream of the product sum-check (mzk_sumcheck.hip).  Device code only; the library is built without relocatable device code,
 // so every user compiles its own copy.
 #pragma once
 #include "mzk_field.h"

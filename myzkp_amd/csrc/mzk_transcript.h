@@ -1,5 +1,5 @@
 // mzk_transcript.h -- the byte-level pieces of FRI::prove's transcript and query sampling (zkstark/fri.rs:19-62, 86-143;
-// algebra/fiat_shamir.rs), written once for the device kernels of mzk_merkle.hip and for the host (mzk_fri_proof_layout, and
+// algebra/fiat_shamir.rs), written once for the device kernels of mzk_fri.hip and for the host (mzk_fri_proof_layout, and
 // tests/hostcheck/transcript_shim.cpp, which checks them against hashlib without a GPU).
 //
 //   proof stream      Vec<Vec<Vec<u8>>> in bincode 1.x default form: u64 LE object count | per object: u64 LE count of byte
@@ -188,32 +188,78 @@ MZK_TX_HD void fri_layout_stride(u64 n, u64 expansion_factor, u64 tests, int lim
 MZK_TX_HD void fri_layout(u64 n, u64 expansion_factor, u64 tests, int limbs, FriLayout* L) { fri_layout_stride(n, expansion_factor, tests, limbs, PATH_STRIDE, L); }
 // the packed proof of mzk_fri_prove_gl: the same sections, nc = 1 or 3 words per element, 64-byte path entries, signs all zero
 MZK_TX_HD void fri_layout_gl(u64 n, u64 expansion_factor, u64 tests, int nc, FriLayout* L) { fri_layout_stride(n, expansion_factor, tests, nc, PATH_STRIDE_GL, L); }
-// bytes of the proof stream after the last push: count | one record per root | the last codeword as one object of
-// `last_len` leaves, each u64 length + bincode(FiniteFieldElement) (at most 9 + 4 * 2 * limbs bytes)
-MZK_TX_HD u64 fri_transcript_cap(const FriLayout& L, int limbs) { return 8 + 48 * (u64)L.rounds + 8 + L.last_len * (8 + 9 + 8 * (u64)limbs); }
 
-// ---- the last codeword of a Goldilocks proof stream (mzk_fri_prove_gl) -------------------------------------------------
-// One object of m strings, string j = u64 LE length | gl::leaf_bytes<NC>(element j): 9 .. 17 bytes for M64, 8 .. 59 (nested) for M64X3.
-MZK_TX_HD u64 fri_transcript_cap_gl(const FriLayout& L, int nc) {
-  return 8 + 48 * (u64)L.rounds + 8 + L.last_len * (8 + (u64)(nc == 1 ? mzk::gl::LEAF_MAX_BASE : mzk::gl::LEAF_MAX_EXT));
+// ---- the leaf of one codeword element: bincode(FiniteFieldElement) ----------------------------------------------------------
+// The proof stream holds a leaf as a record (u64 LE length | leaf), an authentication path holds the sibling's leaf bare.
+// Fr, Fq (NW = 8) and M128 (NW = 4): a magnitude of NW 32-bit words w and its Sign::Minus flag.  The leaf is the sign byte | u64 LE k |
+// the first k words, k = the index past the last non-zero word; the sign byte is 0 (NoSign) when k = 0, else 0xff if negative, else 1.
+template <int NW> MZK_TX_HD int fri_leaf_digits(const uint32_t* w) {
+  int k = 0;
+  for (int q = 0; q < NW; q++) if (w[q]) k = q + 1;
+  return k;
 }
-// bytes of string j's record (length word included)
+// writes the leaf at dst (any alignment) and returns its length, 9 .. 9 + 4 NW
+template <int NW> MZK_TX_HD u64 fri_leaf_put(const uint32_t* w, bool negative, u8* dst) {
+  const int k = fri_leaf_digits<NW>(w);
+  dst[0] = k ? (negative ? 0xff : 1) : 0;
+  for (int b = 0; b < 8; b++) dst[1 + b] = b == 0 ? (u8)k : 0;
+  for (int q = 0; q < NW; q++)
+    if (q < k)
+      for (int b = 0; b < 4; b++) dst[9 + 4 * q + b] = (u8)(w[q] >> (8 * b));
+  return 9 + 4 * (u64)k;
+}
+// bytes of the element's record (length word included), and the record itself at dst (any alignment; returns its length)
+template <int NW> MZK_TX_HD u64 fri_record_len(const uint32_t* w) { return 8 + 9 + 4 * (u64)fri_leaf_digits<NW>(w); }
+template <int NW> MZK_TX_HD u64 fri_record_put(const uint32_t* w, bool negative, u8* dst) {
+  const u64 len = fri_leaf_put<NW>(w, negative, dst + 8);
+  for (int b = 0; b < 8; b++) dst[b] = (u8)(len >> (8 * b));
+  return 8 + len;
+}
+// M64 (NC = 1) and M64X3 (NC = 3): gl::leaf_bytes<NC> of NC canonical words, 9 .. 17 bytes for M64, 8 .. 59 (nested) for M64X3; no signs.
 template <int NC> MZK_TX_HD u64 fri_gl_record_len(const u64* c) { return 8 + (u64)mzk::gl::leaf_bytes<NC>(c, 0, [](int, uint32_t) {}); }
-// writes the record at dst (any alignment) and returns its length
 template <int NC> MZK_TX_HD u64 fri_gl_record_put(const u64* c, u8* dst) {
   const u64 len = (u64)mzk::gl::leaf_bytes<NC>(c, 8, [&](int pos, uint32_t byte) { dst[pos] = (u8)byte; }) - 8;
   for (int b = 0; b < 8; b++) dst[b] = (u8)(len >> (8 * b));
   return 8 + len;
 }
-// The whole push, one record after the other: behind the `rounds` root records of tx the object's string count m, then the records;
-// the object count becomes rounds + 1.  Returns the stream's length.  (k_fri_tx_last_gl places the same records by a prefix sum over
-// fri_gl_record_len, a workgroup's worth at a time; this serial form is the host's, and the check of both record functions.)
-template <int NC> MZK_TX_HD u64 fri_gl_push_last(u8* tx, int rounds, const u64* cw, u64 m) {
+
+// The two families under one set of names, for the kernels of mzk_fri.hip and their host checks: an element is WORDS words of type
+// `word`, a path entry a zero-padded slot of STRIDE bytes, RECORD_MAX the longest record, and GL says that F::sample reduces mod
+// the Goldilocks prime (sample_gl).  `negative` is ignored by the Goldilocks form.
+template <int NW> struct FriLeafLimbs {
+  typedef uint32_t word;
+  static constexpr int WORDS = NW, STRIDE = PATH_STRIDE, RECORD_MAX = 8 + 9 + 4 * NW;
+  static constexpr bool GL = false;
+  static MZK_TX_HD u64 record_len(const word* w) { return fri_record_len<NW>(w); }
+  static MZK_TX_HD u64 record_put(const word* w, bool negative, u8* dst) { return fri_record_put<NW>(w, negative, dst); }
+  static MZK_TX_HD u64 leaf_put(const word* w, bool negative, u8* dst) { return fri_leaf_put<NW>(w, negative, dst); }
+};
+template <int NC> struct FriLeafGl {
+  typedef u64 word;
+  static constexpr int WORDS = NC, STRIDE = PATH_STRIDE_GL, RECORD_MAX = 8 + (NC == 1 ? mzk::gl::LEAF_MAX_BASE : mzk::gl::LEAF_MAX_EXT);
+  static constexpr bool GL = true;
+  static MZK_TX_HD u64 record_len(const word* c) { return fri_gl_record_len<NC>(c); }
+  static MZK_TX_HD u64 record_put(const word* c, bool, u8* dst) { return fri_gl_record_put<NC>(c, dst); }
+  static MZK_TX_HD u64 leaf_put(const word* c, bool, u8* dst) {
+    return (u64)mzk::gl::leaf_bytes<NC>(c, 0, [&](int pos, uint32_t byte) { dst[pos] = (u8)byte; });
+  }
+};
+
+// bytes of the proof stream after the last push: count | one record per root | the last codeword as one object of `last_len` records
+template <class LEAF> MZK_TX_HD u64 fri_transcript_cap(const FriLayout& L) { return 8 + 48 * (u64)L.rounds + 8 + L.last_len * (u64)LEAF::RECORD_MAX; }
+// The whole push, one record after the other: behind the `rounds` root records of tx the object's string count m, then the records
+// of the (canonical, unsigned) elements; the object count becomes rounds + 1.  Returns the stream's length.  (k_fri_tx_last places
+// the same records by a prefix sum over record_len, a workgroup's worth at a time; this serial form is the host's, and the check of
+// both record functions.)
+template <class LEAF> MZK_TX_HD u64 fri_push_last(u8* tx, int rounds, const typename LEAF::word* cw, u64 m) {
   u64 at = 8 + 48 * (u64)rounds;
   for (int b = 0; b < 8; b++) { tx[b] = (u8)(((u64)rounds + 1) >> (8 * b)); tx[at + b] = (u8)(m >> (8 * b)); }
   at += 8;
-  for (u64 j = 0; j < m; j++) at += fri_gl_record_put<NC>(cw + j * NC, tx + at);
+  for (u64 j = 0; j < m; j++) at += LEAF::record_put(cw + j * LEAF::WORDS, false, tx + at);
   return at;
 }
+// the two above by a coefficient count, as the host check of the Goldilocks ids (tests/hostcheck/transcript_gl_shim.cpp) names them
+MZK_TX_HD u64 fri_transcript_cap_gl(const FriLayout& L, int nc) { return nc == 1 ? fri_transcript_cap<FriLeafGl<1>>(L) : fri_transcript_cap<FriLeafGl<3>>(L); }
+template <int NC> MZK_TX_HD u64 fri_gl_push_last(u8* tx, int rounds, const u64* cw, u64 m) { return fri_push_last<FriLeafGl<NC>>(tx, rounds, cw, m); }
 
 }  // namespace mzk_tx

@@ -1,5 +1,5 @@
 // Host build of the Goldilocks pieces of myzkp_amd/csrc/mzk_transcript.h (TEST INFRASTRUCTURE, never shipped): F::sample mod p, the
-// packed-proof layout of mzk_fri_prove_gl, the transcript capacity and the last-codeword writer that k_fri_tx_last_gl places its
+// packed-proof layout of mzk_fri_prove_gl, the transcript capacity and the last-codeword writer that k_fri_tx_last places its
 // records with, checked against tests/goldilocks_model.py and tests/fri_prove_model.py by tests/test_fri_prove_gl_model.py.
 #include "../../myzkp_amd/csrc/mzk_transcript.h"
 using namespace mzk_tx;

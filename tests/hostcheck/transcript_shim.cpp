@@ -1,11 +1,12 @@
 // Host build of myzkp_amd/csrc/mzk_transcript.h (TEST INFRASTRUCTURE, never shipped): the SHAKE256 framing, Blake2b-256,
-// F::sample and the packed-proof layout that the FRI prove kernels run, checked against hashlib by tests/test_fri_transcript_model.py.
+// F::sample, the packed-proof layout and the leaf records of M128 and Fr that the FRI prove kernels run, checked against hashlib and
+// tests/fri_prove_model.py by tests/test_fri_transcript_model.py.
 #include <string.h>
 #include <vector>
 #include "../../myzkp_amd/csrc/mzk_transcript.h"
 using namespace mzk_tx;
 
-// Keccak-f[1600] (FIPS 202), plain 64-bit lanes: the kernels use mzk_merkle.hip's lane-pair form of the same permutation
+// Keccak-f[1600] (FIPS 202), plain 64-bit lanes: the kernels use mzk_keccak_pair.h's lane-pair form of the same permutation
 static void keccak_f(u64 (&a)[25]) {
   static const u64 RC[24] = {0x0000000000000001ULL, 0x0000000000008082ULL, 0x800000000000808aULL, 0x8000000080008000ULL, 0x000000000000808bULL,
                              0x0000000080000001ULL, 0x8000000080008081ULL, 0x8000000000008009ULL, 0x000000000000008aULL, 0x0000000000000088ULL,
@@ -67,4 +68,53 @@ void tx_layout(u64 n, u64 e, u64 t, int limbs, u64* out) {
   for (int k = 0; k < SEC_COUNT; k++) { out[1 + k] = L.off[k]; out[9 + k] = L.size[k]; }
   out[17] = L.total;
 }
+// the leaf form of M128 (nw = 4) and of Fr and Fq (nw = 8): one element's record, and the whole last-codeword push
+u64 tx_transcript_cap(u64 n, u64 e, u64 t, int nw) {
+  FriLayout L;
+  fri_layout(n, e, t, nw / 2, &L);
+  return nw == 4 ? fri_transcript_cap<FriLeafLimbs<4>>(L) : fri_transcript_cap<FriLeafLimbs<8>>(L);
+}
+u64 tx_record_len(int nw, const uint32_t* w) { return nw == 4 ? fri_record_len<4>(w) : fri_record_len<8>(w); }
+u64 tx_record_put(int nw, const uint32_t* w, int negative, u8* dst) {
+  return nw == 4 ? fri_record_put<4>(w, negative != 0, dst) : fri_record_put<8>(w, negative != 0, dst);
+}
+// tx holds the `rounds` root records already; returns the stream's length
+u64 tx_push_last(int nw, u8* tx, int rounds, const uint32_t* cw, u64 m) {
+  return nw == 4 ? fri_push_last<FriLeafLimbs<4>>(tx, rounds, cw, m) : fri_push_last<FriLeafLimbs<8>>(tx, rounds, cw, m);
+}
+}
+
+// The stand-alone form (built with -fsanitize=address,undefined): every record and every stream is written into a heap block of exactly
+// its length, so a byte too many is a report.  Input: lines "nw rounds m <m * nw words in hex>"; per line the output is one
+// "R <plus record> <minus record>" per element, then "S <stream>" with all-zero roots, in hex; then "ok <lines>".
+#include <stdio.h>
+static void hex(const u8* p, size_t n) { for (size_t i = 0; i < n; i++) printf("%02x", p[i]); }
+int main(int argc, char** argv) {
+  if (argc != 2) return 2;
+  FILE* f = fopen(argv[1], "r");
+  if (!f) return 2;
+  int nw, rounds, lines = 0;
+  unsigned long long m;
+  while (fscanf(f, "%d %d %llu", &nw, &rounds, &m) == 3) {
+    std::vector<uint32_t> cw(m * (size_t)nw);
+    for (uint32_t& w : cw) if (fscanf(f, "%x", &w) != 1) return 3;
+    u64 sum = 0;
+    for (u64 j = 0; j < m; j++) {
+      const uint32_t* w = cw.data() + j * nw;
+      const u64 len = tx_record_len(nw, w);
+      std::vector<u8> plus(len), minus(len);
+      if (tx_record_put(nw, w, 0, plus.data()) != len || tx_record_put(nw, w, 1, minus.data()) != len) return 4;
+      printf("R "); hex(plus.data(), len); printf(" "); hex(minus.data(), len); printf("\n");
+      sum += len;
+    }
+    const u64 head = 8 + 48 * (u64)rounds, total = head + 8 + sum;
+    std::vector<u8> tx(total, 0);
+    for (int r = 0; r < rounds; r++) { tx[8 + 48 * r] = 1; tx[16 + 48 * r] = 32; }
+    if (tx_push_last(nw, tx.data(), rounds, cw.data(), m) != total) return 5;
+    printf("S "); hex(tx.data(), total); printf("\n");
+    lines++;
+  }
+  fclose(f);
+  printf("ok %d\n", lines);
+  return 0;
 }

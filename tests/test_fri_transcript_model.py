@@ -1,10 +1,14 @@
 """The deterministic pieces of FRI::prove (zkstark/fri.rs:19-143, algebra/fiat_shamir.rs) on the CPU: the Python model of
 tests/fri_prove_model.py against hand-built bincode bytes and literal restatements, and the device header
 myzkp_amd/csrc/mzk_transcript.h compiled for the host (tests/hostcheck/transcript_shim.cpp) against hashlib -- the SHAKE256
-framing, Blake2b-256, F::sample and the packed proof layout that the kernels of mzk_fri_prove run.  CPU only."""
+framing, Blake2b-256, F::sample and the packed proof layout that the kernels of mzk_fri_prove run -- and against the model's leaves
+the record writers of M128 and Fr (fri_record_len, fri_record_put, the serial last-codeword push), once more as a stand-alone
+program under the sanitizers.  CPU only."""
 import ctypes, hashlib, json, os, random, subprocess
+import numpy as np
 import pytest
 import fri_prove_model as fm
+import fri_prove_cases as fc
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
@@ -23,6 +27,14 @@ def tx(tmp_path_factory):
     L.tx_num_rounds.argtypes = [ctypes.c_uint64] * 3
     L.tx_blake2b256_seed_counter.argtypes = [ctypes.c_char_p, ctypes.c_uint64, ctypes.c_char_p]
     L.tx_layout.argtypes = [ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_int, ctypes.POINTER(ctypes.c_uint64)]
+    L.tx_transcript_cap.restype = ctypes.c_uint64
+    L.tx_transcript_cap.argtypes = [ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_int]
+    L.tx_record_len.restype = ctypes.c_uint64
+    L.tx_record_len.argtypes = [ctypes.c_int, ctypes.c_void_p]
+    L.tx_record_put.restype = ctypes.c_uint64
+    L.tx_record_put.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_char_p]
+    L.tx_push_last.restype = ctypes.c_uint64
+    L.tx_push_last.argtypes = [ctypes.c_int, ctypes.c_char_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_uint64]
     return L
 
 
@@ -115,6 +127,80 @@ def test_layout_matches_python(tx, n, e, t, limbs):
     R, sec, total = want
     assert sec["paths"][1] == fm.PATH_STRIDE * sec["path_lens"][1] // 8
     assert all(o % 8 == 0 for o, _ in sec.values()) and total >= sum(s for _, s in sec.values())
+
+
+FIELD_WORDS = [(4, fm.P_M128), (8, fm.P_FR)]              # 32-bit words per element: M128, and Fr (Fq has Fr's form)
+LAST_SHAPES = [(2, 2), (16, 3), (128, 4), (512, 4)]        # (last codeword's length m, rounds)
+
+
+def _u32(vals, nw):
+    return np.array([fc.words(v, nw) for v in vals], dtype=np.uint32).reshape(len(vals), nw)
+
+
+def _record(v):
+    return fm.u64le(len(fm.leaf(v))) + fm.leaf(v)
+
+
+@pytest.mark.parametrize("nw,p", FIELD_WORDS, ids=["M128", "Fr"])
+def test_leaf_records_against_the_model(tx, nw, p):
+    """fri_record_len / fri_record_put over the edge values with both signs: every trimmed word count 0 .. nw, the zero element
+    (NoSign whatever the flag says) and Sign::Minus; nothing written past the record"""
+    edge = fc.edge_values(p, nw)
+    assert {len(fm.leaf(v)) for v in edge} == {9 + 4 * k for k in range(nw + 1)}
+    for v in edge + [-v for v in edge]:
+        for negative in ((1,) if v < 0 else (0, 1) if v == 0 else (0,)):
+            w = _u32([v], nw)
+            want = _record(v)
+            assert tx.tx_record_len(nw, w.ctypes.data) == len(want), v
+            buf = ctypes.create_string_buffer(b"\xA5" * (len(want) + 16), len(want) + 16)
+            assert tx.tx_record_put(nw, w.ctypes.data, negative, buf) == len(want), v
+            assert buf.raw == want + b"\xA5" * 16, v
+
+
+@pytest.mark.parametrize("nw,p", FIELD_WORDS, ids=["M128", "Fr"])
+@pytest.mark.parametrize("m,rounds", LAST_SHAPES)
+def test_last_codeword_writer_against_the_stream_model(tx, nw, p, m, rounds):
+    """the serial writer of mzk_transcript.h over the edge vector: byte for byte fm.serialize_stream, and the capacity the driver
+    reserves"""
+    v = fc.edge_vector(p, nw, m)
+    roots = [hashlib.sha3_256(bytes([r, m & 255])).digest() for r in range(rounds)]
+    want = fm.serialize_stream([[r] for r in roots] + [[fm.leaf(e) for e in v]])
+    n, expansion, tests = m << (rounds - 1), m // 2, 0                 # a shape with this many rounds and this last length
+    assert fm.num_rounds(n, expansion, tests) == rounds
+    cap = tx.tx_transcript_cap(n, expansion, tests, nw)
+    assert cap == 8 + 48 * rounds + 8 + m * (8 + 9 + 4 * nw) and len(want) <= cap
+    buf = ctypes.create_string_buffer(b"\xA5" * (cap + 16), cap + 16)
+    head = fm.serialize_stream([[r] for r in roots])
+    ctypes.memmove(buf, head, len(head))
+    assert tx.tx_push_last(nw, buf, rounds, _u32(v, nw).ctypes.data, m) == len(want)
+    assert buf.raw[:len(want)] == want
+    assert buf.raw[len(want):] == b"\xA5" * (cap + 16 - len(want))
+    # all-maximal leaves fill the capacity exactly
+    assert tx.tx_push_last(nw, buf, rounds, _u32([p - 1] * m, nw).ctypes.data, m) == cap
+
+
+def test_record_writers_stand_alone_under_the_sanitizers(tmp_path):
+    """the same writers in a program of their own, built with -fsanitize=address,undefined: every record and every stream goes into a
+    heap block of exactly its length"""
+    exe, inp = str(tmp_path / "transcript_shim_san"), str(tmp_path / "cases.txt")
+    subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-Wall", "-Wextra", "-Werror", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+                           "-o", exe, os.path.join(HERE, "hostcheck", "transcript_shim.cpp")])
+    cases = [(nw, rounds, fc.edge_vector(p, nw, m)) for nw, p in FIELD_WORDS for m, rounds in LAST_SHAPES]
+    with open(inp, "w") as f:
+        for nw, rounds, v in cases:
+            f.write("%d %d %d %s\n" % (nw, rounds, len(v), " ".join("%x" % w for e in v for w in fc.words(e, nw))))
+    r = subprocess.run([exe, inp], capture_output=True, text=True, env=dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0"))
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
+    assert "AddressSanitizer" not in r.stderr and "runtime error" not in r.stderr, r.stderr[-4000:]
+    lines = r.stdout.splitlines()
+    assert lines.pop() == "ok %d" % len(cases)
+    for nw, rounds, v in cases:
+        for e in v:
+            kind, plus, minus = lines.pop(0).split()
+            assert kind == "R" and bytes.fromhex(plus) == _record(e) and bytes.fromhex(minus) == _record(-e), (nw, e)
+        kind, stream = lines.pop(0).split()
+        assert kind == "S" and bytes.fromhex(stream) == fm.serialize_stream([[bytes(32)]] * rounds + [[fm.leaf(e) for e in v]]), (nw, len(v))
+    assert not lines
 
 
 def test_library_layout_entry_point():

@@ -6,6 +6,8 @@ device (FiatShamirTransformer = SHAKE256 over the bincode of Vec<Vec<Vec<u8>>>, 
             the corrupted codeword of fri.rs:531-538 and a proof with one revealed value changed
   composed  the same proof built from the callback entry points: mzk_fri_commit_keep_trees with a Python challenge running the real
             transcript, mzk_merkle_open_multi and mzk_merkle_leaves -- field for field
+  model     the packed bytes section by section and the unpacked fields against tests/fri_prove_model.py: periodic codewords that put
+            every leaf length into every tree (with and without signs on round 0), and a last codeword of 512 elements
   _dev      from a torch tensor, and two proofs enqueued back to back before one synchronize
   errors    every validation failure returns before anything is enqueued"""
 import ctypes, json, os
@@ -13,6 +15,7 @@ import numpy as np
 import pytest
 import orc
 import fri_prove_model as fm
+import fri_prove_cases as fc
 from orc import FR, M128
 
 pytestmark = pytest.mark.gpu
@@ -155,6 +158,90 @@ def test_signed_round_zero(mz, fid):
     model, _ = fm.prove(p, [-v if s else v for v, s in zip(orc.from_limbs(cw), neg)], w, 3, 4, 17)
     assert one == model
     assert any(v < 0 for v in one["revealed_layers"][0]["a"][0] + one["revealed_layers"][0]["b"][0])
+
+
+# ---- against the model, packed bytes and fields: every leaf length in every tree, and a last codeword of two scan batches ----------------
+def pack(fid, proof, tests):
+    """the model's proof in mzk_fri_prove's packed form: {section: bytes}; a negative value is a magnitude and a sign byte of 1"""
+    limbs = lambda vs: orc.to_limbs([abs(v) for v in vs], orc.LIMBS[fid]).tobytes()
+    out = {"status": bytes(8), "top_indices": np.array(proof["top_level_indices"], dtype=np.uint64).tobytes(),
+           "roots": b"".join(proof["merkle_roots"]), "last_codeword": limbs(proof["last_codeword"])}
+    values, signs, paths, lens = [], [], [], []
+    for layer in proof["revealed_layers"]:
+        for k in "abc":
+            values.append(limbs(layer[k][0]))
+            signs += [1 if v < 0 else 0 for v in layer[k][0]]
+            for path in layer[k][1]:
+                for entry in path:
+                    assert len(entry) <= fm.PATH_STRIDE
+                    paths.append(entry + bytes(fm.PATH_STRIDE - len(entry)))
+                    lens.append(len(entry))
+    out.update(values=b"".join(values), signs=bytes(signs), paths=b"".join(paths), path_lens=np.array(lens, dtype=np.uint64).tobytes())
+    return out
+
+
+def prove_and_compare(mz, fid, cw, lg, expansion, tests, flags=None):
+    """one proof of the codeword `cw` (ints; a negative one is given as magnitude and Sign::Minus flag, `flags` may flag zeros as well)
+    through the C entry point against the model: the packed sections byte for byte (zero padding of every path slot included; not
+    the alignment gaps between sections), then the unpacked fields; returns the model's proof"""
+    n, nl = len(cw), orc.LIMBS[fid]
+    omega, offset = root(fid, lg), 7
+    want, _ = fm.prove(PRIME[fid], cw, omega, offset, expansion, tests)
+    neg = np.array([1 if v < 0 else 0 for v in cw] if flags is None else flags, dtype=np.uint8)
+    assert all(f for v, f in zip(cw, neg) if v < 0) and not any(f for v, f in zip(cw, neg) if v > 0)
+    mags, w, o = orc.to_limbs([abs(v) for v in cw], nl), orc.to_limbs([omega], nl), orc.to_limbs([offset], nl)
+    R, sec, total = fm.layout(nl, n, expansion, tests)
+    buf = (ctypes.c_uint8 * total)()
+    rc = mz.lib().mzk_fri_prove(fid, orc.ptr(mags), orc.ptr(neg) if neg.any() else None, ctypes.c_size_t(n), orc.ptr(w), orc.ptr(o),
+                                ctypes.c_size_t(expansion), ctypes.c_size_t(tests), buf, ctypes.c_size_t(total))
+    assert rc == 0, mz.lib().mzk_last_error()
+    raw = bytes(buf)
+    packed = pack(fid, want, tests)
+    for k in fm.SECTIONS:
+        off, size = sec[k]
+        assert len(packed[k]) == size, k
+        assert raw[off:off + size] == packed[k], k
+    got = as_model(mz.fri_unpack_proof(fid, n, expansion, tests, raw))
+    for k in ("top_level_indices", "last_codeword", "merkle_roots", "revealed_layers"):
+        assert got[k] == want[k], k
+    return want
+
+
+@pytest.mark.parametrize("fid", [M128, FR])
+@pytest.mark.parametrize("n,expansion,tests,rounds,m", [(64, 4, 4, 2, 32), (64, 2, 3, 3, 16), (1024, 16, 17, 4, 128)])
+def test_edge_vectors_through_a_periodic_codeword(mz, fid, n, expansion, tests, rounds, m):
+    """cw[i] = v[i mod m]: every fold has a = b, so the edge values -- the zero element and every trimmed word count -- are every round's
+    leaves, every revealed sibling's candidates and the last codeword"""
+    assert fm.num_rounds(n, expansion, tests) == rounds and n >> (rounds - 1) == m
+    v = fc.edge_vector(PRIME[fid], 2 * orc.LIMBS[fid], m)
+    want = prove_and_compare(mz, fid, fc.periodic(v, n), n.bit_length() - 1, expansion, tests)
+    assert want["last_codeword"] == v
+
+
+@pytest.mark.parametrize("fid", [M128, FR])
+def test_edge_vectors_with_signs_on_round_zero(mz, fid):
+    """the m = 32 periodic case with Sign::Minus flags on round 0 (periodic as well, so that a = b still holds after the fold has
+    canonicalised them), the zero element flagged too: its leaf stays NoSign"""
+    n, expansion, tests, rounds, m = 64, 4, 4, 2, 32
+    assert fm.num_rounds(n, expansion, tests) == rounds and n >> (rounds - 1) == m
+    p = PRIME[fid]
+    flags = [1 if j % 3 != 2 else 0 for j in range(m)]
+    v = [-x if f else x for x, f in zip(fc.edge_vector(p, 2 * orc.LIMBS[fid], m), flags)]
+    assert v[0] == 0 and flags[0] and v[1] == -1
+    want = prove_and_compare(mz, fid, fc.periodic(v, n), 6, expansion, tests, flags=fc.periodic(flags, n))
+    assert want["last_codeword"] == [x % p for x in v]
+    L0 = want["revealed_layers"][0]
+    assert any(x < 0 for x in L0["a"][0] + L0["b"][0]) and all(x >= 0 for x in L0["c"][0])
+
+
+@pytest.mark.parametrize("fid", [M128, FR])
+def test_last_codeword_of_two_scan_batches(mz, fid):
+    """m = 512: the second batch of records starts where the first one's prefix sum ended"""
+    n, expansion, tests, rounds, m = 4096, 4, 100, 4, 512
+    assert fm.num_rounds(n, expansion, tests) == rounds and n >> (rounds - 1) == m
+    cw = orc.from_limbs(codeword_of(fid, n, 61 + fid))
+    cw[n // 2], cw[n - 1] = 0, PRIME[fid] - 1
+    prove_and_compare(mz, fid, cw, 12, expansion, tests)
 
 
 def test_dev_form_and_back_to_back(mz):
