@@ -1,7 +1,10 @@
 """Reed-Solomon over GF(2^8) on the device (myzkp_amd/csrc/mzk_rs.hip: encode in both forms, the Fr columns, syndromes, decode, the 2D
 code) against tests/rs_model.py, the Python restatement of algebra/reedsolomon.rs -- every comparison bit for bit.  Shapes are the
 smallest at which each path can go wrong: every parity-register count and the boundaries between them, the lane and the wave encoder,
-every decode group width, batches around the workgroup and wave sizes, strided and in-place views."""
+batches around the workgroup and wave sizes, strided and in-place encoder views.  Decoding is covered at the group widths 8 (d = 1, 4,
+5, 8), 32 (d = 32) and 64 (d = 128), the syndromes at d = 4, 8, 32 and 254, the 2D code up to 9 x 8.  Width 16, d at the boundaries
+of every width, errors placed after the lane ownership, miscorrection, the 2D code beyond one stride per lane, the wave encoder's
+64-byte chunk boundaries and the lane encoder's two read paths side by side are in test_gpu_rs_matrix.py."""
 import ctypes, random
 import numpy as np
 import pytest
