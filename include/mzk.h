@@ -838,7 +838,9 @@ int mzk_selftest_copy_dev(const void* d_src, void* d_dst, size_t bytes, void* st
 
 /* Host-side parameter arithmetic of the library (roots, inverses, offsets: O(log n) scalar work per call, never on the
  * data path), exposed for checking without a GPU: op 0 = a * b, 1 = a^-1 (0 -> 0), 2 = a^(b[0]), 3 = a * b by the
- * bit-serial reference implementation.  field_id may also be MZK_FIELD_FQ. */
+ * bit-serial reference implementation, 4 = a * R mod p with R = 2^(29 L) the device's Montgomery radix (L = 9 limbs for
+ * Fr / Fq, 5 for M128), as the eight 32-bit words of a kernel argument: out receives four uint64 for every field, the upper
+ * two zero for M128.  b is not read by ops 1 and 4 and may be null there.  field_id may also be MZK_FIELD_FQ. */
 int mzk_host_field_op(int field_id, int op, const uint64_t* a, const uint64_t* b, uint64_t* out);
 
 /* Device self-check: the throughput kernels compute their Montgomery products with hand-scheduled inline-asm blocks

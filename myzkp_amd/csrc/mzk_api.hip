@@ -321,6 +321,15 @@ void h_rmod(const HostField* f, uint64_t* out) {
   const uint64_t two[4] = {2, 0, 0, 0};
   h_powmod_u64(f, out, two, (uint64_t)f->mont_bits);
 }
+void h_words(const uint64_t* v, int nl, u32 out8[8]) {
+  for (int i = 0; i < 8; i++) out8[i] = i < 2 * nl ? (u32)(v[i / 2] >> (32 * (i & 1))) : 0u;
+}
+void h_mont_words(const HostField* f, const uint64_t* v, u32 out8[8]) {
+  uint64_t r[4], t[4];
+  h_rmod(f, r);
+  h_mulmod(f, t, v, r);
+  h_words(t, f->nl, out8);
+}
 
 }  // namespace mzk
 
@@ -493,16 +502,23 @@ const char* mzk_prof_name(int phase) {
 }
 
 // Host parameter arithmetic, exposed so that it can be checked without a GPU (tests/test_abi_load.py): op 0 = a * b,
-// 1 = a^-1 (0 -> 0), 2 = a^b[0], 3 = a * b by the bit-serial reference implementation.
+// 1 = a^-1 (0 -> 0), 2 = a^b[0], 3 = a * b by the bit-serial reference implementation, 4 = h_mont_words(a): a R mod p as the eight
+// 32-bit words of a kernel argument, in four uint64 whatever the field (M128: the upper two are zero).  b is not read by 1 and 4.
 int mzk_host_field_op(int field_id, int op, const uint64_t* a, const uint64_t* b, uint64_t* out) {
   const HostField* f = host_field(field_id);
-  if (!f || !a || !out || (!b && op != 1)) { set_error("host_field_op: bad argument"); return MZK_E_ARG; }
+  if (!f || !a || !out || (!b && op != 1 && op != 4)) { set_error("host_field_op: bad argument"); return MZK_E_ARG; }
   if (!h_is_canonical(f, a) || ((op == 0 || op == 3) && !h_is_canonical(f, b))) { set_error("host_field_op: operand not canonical"); return MZK_E_RANGE; }
   switch (op) {
     case 0: h_mulmod(f, out, a, b); return MZK_OK;
     case 1: h_invmod(f, out, a); return MZK_OK;
     case 2: h_powmod_u64(f, out, a, b[0]); return MZK_OK;
     case 3: h_mulmod_slow(f, out, a, b); return MZK_OK;
+    case 4: {
+      u32 w[8];
+      h_mont_words(f, a, w);
+      for (int i = 0; i < 4; i++) out[i] = (uint64_t)w[2 * i] | ((uint64_t)w[2 * i + 1] << 32);
+      return MZK_OK;
+    }
     default: set_error("host_field_op: bad op %d", op); return MZK_E_ARG;
   }
 }

@@ -138,6 +138,12 @@ void h_invmod(const HostField* f, uint64_t* r, const uint64_t* a);   // a^(p-2) 
 void h_ninv_pow2(const HostField* f, unsigned log2n, uint64_t* out);  // (2^log2n)^-1 mod p, needs 2^log2n | p-1
 bool h_is_one(const HostField* f, const uint64_t* a);
 void h_rmod(const HostField* f, uint64_t* out);                       // R mod p: x -> x R mod p is one h_mulmod with it
+// One element as a kernel argument (Words8, mzk_elem.h), words [2 nl, 8) zero:
+void h_words(const uint64_t* v, int nl, u32 out8[8]);                   // limbs -> words
+void h_mont_words(const HostField* f, const uint64_t* v, u32 out8[8]);  // (v R mod p) -> words
+
+static inline bool is_pow2(size_t n) { return n && !(n & (n - 1)); }
+static inline unsigned ilog2(size_t n) { unsigned l = 0; while (((size_t)1 << l) < n) l++; return l; }   // ceil(log2 n); 0 for n <= 1
 
 // Goldilocks ids (mzk_gl.h): one or three canonical u64 per element, no Montgomery parameter set -- a kernel family of their own
 static inline bool field_is_gl(int fid) { return fid == MZK_FIELD_M64 || fid == MZK_FIELD_M64X3; }

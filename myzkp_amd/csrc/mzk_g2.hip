@@ -3,11 +3,11 @@
 // Sizes in the reference are tiny, so the shape is the simple one: one lane per (scalar, point) pair does a
 // double-and-add on an XYZZ accumulator over Fq2 (mzk_g2.h), one workgroup sums the partial results.
 #include "mzk_common.h"
+#include "mzk_elem.h"
 #include "mzk_g2.h"
 
 namespace mzk {
 
-struct Words8k { u32 w[8]; };
 __device__ __forceinline__ void ldw(const u32* __restrict__ g, u32* w, int n) { for (int i = 0; i < n; i++) w[i] = g[i]; }
 
 // out[i] = scalars[i] * points[i] as a 64-word XYZZ record; scalars canonicalised like polynomial.rs:162 (sanitize)
@@ -60,7 +60,7 @@ __global__ __launch_bounds__(G2_SUM_THREADS) void k_g2_sum(const u32* __restrict
   }
 }
 // powers[i] = alpha^(first + i) * g2, affine wire points
-__global__ __launch_bounds__(64) void k_g2_powers(Words8k alpha_plain, const u32* __restrict__ g2_words, size_t first, size_t count, u32* __restrict__ out) {
+__global__ __launch_bounds__(64) void k_g2_powers(Words8 alpha_plain, const u32* __restrict__ g2_words, size_t first, size_t count, u32* __restrict__ out) {
   const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= count) return;
   typedef FrParams R;
@@ -130,8 +130,8 @@ int mzk_kzg_setup_g2(const uint64_t alpha[4], const uint64_t g2_xy[16], size_t m
   MZK_TRY(ws.get(WS_MSM_OUT, 4096, &d_g));
   MZK_TRY(ws.get(WS_MSM_POINTS, count * 128, &d_o));
   MZK_HIP(hipMemcpyAsync(d_g, g2_xy, 128, hipMemcpyHostToDevice, s));
-  Words8k aw;
-  for (int i = 0; i < 4; i++) { aw.w[2 * i] = (u32)alpha[i]; aw.w[2 * i + 1] = (u32)(alpha[i] >> 32); }
+  Words8 aw;
+  h_words(alpha, 4, aw.w);
   hipLaunchKernelGGL(k_g2_powers, dim3((unsigned)((count + 63) / 64)), dim3(64), 0, s, aw, (const u32*)d_g, (size_t)0, count, (u32*)d_o);
   MZK_HIP(hipGetLastError());
   MZK_TRY(d2h_sync(powers2_xy, d_o, count * 128, s));

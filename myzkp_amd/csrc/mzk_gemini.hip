@@ -16,54 +16,23 @@
 // The MSMs run on the SRS handle's tables (mzk_msm.hip); the degree-bound MSMs of prove_degree_bound (kzg.rs:121-134) on the
 // handle entered max_d - d rows further on (see gemini_open_impl).
 #include "mzk_common.h"
+#include "mzk_elem.h"
 
 namespace mzk {
 
 typedef FrParams GP;
 typedef Fe<GP> GE;
-struct GmW8 { u32 w[8]; };
 
-__device__ __forceinline__ GE gm_load(const u32* __restrict__ g, size_t i) {
-  const uint4* p = reinterpret_cast<const uint4*>(g + 8 * i);
-  const uint4 a = p[0], b = p[1];
-  const u32 w[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
-  return fe_unpack<GP>(w);
-}
-// v canonical
-__device__ __forceinline__ void gm_store(u32* __restrict__ g, size_t i, const GE& v) {
-  u32 w[8];
-  fe_pack<GP>(v, w);
-  uint4* p = reinterpret_cast<uint4*>(g + 8 * i);
-  p[0] = make_uint4(w[0], w[1], w[2], w[3]);
-  p[1] = make_uint4(w[4], w[5], w[6], w[7]);
-}
 // canonical a + b * (r R) / R = a + b r
 __device__ __forceinline__ GE gm_fold1(const GE& a, const GE& b, const GE& r_mont) {
   return fe_reduce<GP>(fe_add<GP>(a, fe_mul<GP>(b, r_mont)));
 }
 
 // ---- host parameter math ------------------------------------------------------------------------------------------
-static void gm_words(const uint64_t* v, GmW8* out) {
-  for (int i = 0; i < 4; i++) { out->w[2 * i] = (u32)v[i]; out->w[2 * i + 1] = (u32)(v[i] >> 32); }
-}
-// v R mod r (R = 2^(29 L) = 2^261), as 8 words
-static void gm_mont(const uint64_t* v, GmW8* out) {
-  const HostField* fr = host_field(MZK_FIELD_FR);
-  uint64_t rmod[4], t[4];
-  h_rmod(fr, rmod);
-  h_mulmod(fr, t, v, rmod);
-  gm_words(t, out);
-}
-static bool gm_log2(size_t n, int* el) {
-  if (n == 0 || (n & (n - 1))) return false;
-  int e = 0;
-  while (((size_t)1 << e) < n) e++;
-  *el = e;
-  return true;
-}
 constexpr int GM_MAX_LOG = 30;
 static int gm_check_n(size_t n, int* el, const char* who) {
-  if (!gm_log2(n, el)) { set_error("%s: coefs.len() must be a power of two, but got %zu", who, n); return MZK_E_NOT_POW2; }
+  if (!is_pow2(n)) { set_error("%s: coefs.len() must be a power of two, but got %zu", who, n); return MZK_E_NOT_POW2; }
+  *el = (int)ilog2(n);
   if (*el > GM_MAX_LOG) { set_error("%s: 2^%d coefficients (at most 2^%d)", who, *el, GM_MAX_LOG); return MZK_E_ARG; }
   return MZK_OK;
 }
@@ -73,9 +42,7 @@ static GmPow2 gm_pow2() {
   GmPow2 p;
   for (int k = 0; k < 32; k++) {
     uint64_t v[4] = {(uint64_t)1 << k, 0, 0, 0};
-    GmW8 m;
-    gm_mont(v, &m);
-    memcpy(p.w[k], m.w, 32);
+    h_mont_words(host_field(MZK_FIELD_FR), v, p.w[k]);
   }
   return p;
 }
@@ -85,10 +52,10 @@ constexpr size_t FOLD_LDS_IN = 2048;       // levels of at most this many elemen
 constexpr int FOLD_THREADS = 256;
 struct GmRho16 { u32 w[16][8]; };
 
-__global__ __launch_bounds__(FOLD_THREADS) void k_gm_fold(const u32* __restrict__ in, size_t n_out, GmW8 rho, u32* __restrict__ out) {
+__global__ __launch_bounds__(FOLD_THREADS) void k_gm_fold(const u32* __restrict__ in, size_t n_out, Words8 rho, u32* __restrict__ out) {
   const size_t k = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (k >= n_out) return;
-  gm_store(out, k, gm_fold1(gm_load(in, 2 * k), gm_load(in, 2 * k + 1), fe_unpack<GP>(rho.w)));
+  fe_gstore<GP>(out, k, gm_fold1(fe_gload<GP>(in, 2 * k), fe_gload<GP>(in, 2 * k + 1), fe_unpack<GP>(rho.w)));
 }
 // in: one level of len0 <= FOLD_LDS_IN elements (global); writes the nfold levels below it back to back from `out`
 __global__ __launch_bounds__(FOLD_THREADS) void k_gm_fold_lds(const u32* __restrict__ in, int len0, GmRho16 rho, int nfold, u32* __restrict__ out) {
@@ -99,9 +66,9 @@ __global__ __launch_bounds__(FOLD_THREADS) void k_gm_fold_lds(const u32* __restr
   {
     const GE r = fe_unpack<GP>(rho.w[0]);
     for (int k = tid; k < len; k += FOLD_THREADS) {
-      const GE v = gm_fold1(gm_load(in, 2 * k), gm_load(in, 2 * k + 1), r);
+      const GE v = gm_fold1(fe_gload<GP>(in, 2 * k), fe_gload<GP>(in, 2 * k + 1), r);
       fe_pack<GP>(v, A[k]);
-      gm_store(out, k, v);
+      fe_gstore<GP>(out, k, v);
     }
   }
   u32* o = out + 8 * (size_t)len;
@@ -114,7 +81,7 @@ __global__ __launch_bounds__(FOLD_THREADS) void k_gm_fold_lds(const u32* __restr
     for (int k = tid; k < nl; k += FOLD_THREADS) {
       const GE v = gm_fold1(fe_unpack<GP>(src[2 * k]), fe_unpack<GP>(src[2 * k + 1]), r);
       fe_pack<GP>(v, dst[k]);
-      gm_store(o, k, v);
+      fe_gstore<GP>(o, k, v);
     }
     o += 8 * (size_t)nl;
     len = nl;
@@ -135,8 +102,8 @@ static int split_fold_impl(const void* d_coef, size_t n, const uint64_t* rhos, s
   size_t len = n;
   int i = 0;
   while (len > FOLD_LDS_IN) {
-    GmW8 r;
-    gm_mont(rhos + 4 * i, &r);
+    Words8 r;
+    h_mont_words(fr, rhos + 4 * i, r.w);
     u32* next = (u32*)cur + 8 * len;
     const size_t nout = len / 2;
     hipLaunchKernelGGL(k_gm_fold, dim3((unsigned)((nout + FOLD_THREADS - 1) / FOLD_THREADS)), dim3(FOLD_THREADS), 0, s, cur, nout, r, next);
@@ -144,7 +111,7 @@ static int split_fold_impl(const void* d_coef, size_t n, const uint64_t* rhos, s
   }
   if (len > 1) {
     GmRho16 rr;
-    for (int f = 0; f < el - i; f++) { GmW8 r; gm_mont(rhos + 4 * (i + f), &r); memcpy(rr.w[f], r.w, 32); }
+    for (int f = 0; f < el - i; f++) h_mont_words(fr, rhos + 4 * (i + f), rr.w[f]);
     hipLaunchKernelGGL(k_gm_fold_lds, dim3(1), dim3(FOLD_THREADS), 0, s, cur, (int)len, rr, el - i, (u32*)cur + 8 * len);
   }
   MZK_HIP(hipGetLastError());
@@ -157,7 +124,7 @@ static int split_fold_impl(const void* d_coef, size_t n, const uint64_t* rhos, s
 constexpr int SUM_THREADS = 256;
 constexpr int SUM_MAX_WG = 1024;
 template <bool FOLD>
-__global__ __launch_bounds__(SUM_THREADS) void k_gm_sums(const u32* __restrict__ f, size_t count, GmW8 r, u32* __restrict__ out, int base, int shift,
+__global__ __launch_bounds__(SUM_THREADS) void k_gm_sums(const u32* __restrict__ f, size_t count, Words8 r, u32* __restrict__ out, int base, int shift,
                                                           int split, GmPow2 pw, u32* __restrict__ partials) {
   __shared__ u32 S[2][SUM_THREADS][GP::L];
   const int tid = threadIdx.x;
@@ -166,10 +133,10 @@ __global__ __launch_bounds__(SUM_THREADS) void k_gm_sums(const u32* __restrict__
   for (size_t t = (size_t)blockIdx.x * SUM_THREADS + tid; t < count; t += (size_t)gridDim.x * SUM_THREADS) {
     GE v;
     if (FOLD) {
-      v = gm_fold1(gm_load(f, 2 * t), gm_load(f, 2 * t + 1), rm);
-      gm_store(out, t, v);
+      v = gm_fold1(fe_gload<GP>(f, 2 * t), fe_gload<GP>(f, 2 * t + 1), rm);
+      fe_gstore<GP>(out, t, v);
     } else {
-      v = gm_load(f, t);
+      v = fe_gload<GP>(f, t);
     }
     if (base < 0) continue;
     const int e = base - __popcll((unsigned long long)(t >> shift));
@@ -201,7 +168,7 @@ __global__ __launch_bounds__(SUM_THREADS) void k_gm_sums(const u32* __restrict__
     GE a;
 #pragma unroll
     for (int i = 0; i < GP::L; i++) a.l[i] = S[tid][0][i];
-    gm_store(partials, 2 * (size_t)blockIdx.x + tid, a);
+    fe_gstore<GP>(partials, 2 * (size_t)blockIdx.x + tid, a);
   }
 }
 // out[0..2) = the two slots summed over nparts workgroups
@@ -211,7 +178,7 @@ __global__ __launch_bounds__(SUM_THREADS) void k_gm_sums_final(const u32* __rest
   GE acc[2] = {fe_zero<GP>(), fe_zero<GP>()};
   for (int p = tid; p < nparts; p += SUM_THREADS)
 #pragma unroll
-    for (int q = 0; q < 2; q++) acc[q] = fe_reduce<GP>(fe_add<GP>(acc[q], gm_load(partials, 2 * (size_t)p + q)));
+    for (int q = 0; q < 2; q++) acc[q] = fe_reduce<GP>(fe_add<GP>(acc[q], fe_gload<GP>(partials, 2 * (size_t)p + q)));
 #pragma unroll
   for (int q = 0; q < 2; q++)
 #pragma unroll
@@ -235,15 +202,15 @@ __global__ __launch_bounds__(SUM_THREADS) void k_gm_sums_final(const u32* __rest
     GE a;
 #pragma unroll
     for (int i = 0; i < GP::L; i++) a.l[i] = S[tid][0][i];
-    gm_store(out, tid, a);
+    fe_gstore<GP>(out, tid, a);
   }
 }
 // d_out2: 2 elements (slot 0, slot 1).  Workspace: WS_NTT_IO_A (partials).
 static int gm_sums(const void* d_f, size_t count, const uint64_t* r_host, void* d_fold_out, int base, int shift, int split, void* d_out2, hipStream_t s) {
   WsFrame ws("gm_sums");
   static const GmPow2 pw = gm_pow2();
-  GmW8 r = {};
-  if (r_host) gm_mont(r_host, &r);
+  Words8 r = {};
+  if (r_host) h_mont_words(host_field(MZK_FIELD_FR), r_host, r.w);
   const size_t wg_need = (count + SUM_THREADS - 1) / SUM_THREADS;
   const int nwg = (int)(wg_need < (size_t)SUM_MAX_WG ? (wg_need ? wg_need : 1) : SUM_MAX_WG);
   u32* partials = nullptr;

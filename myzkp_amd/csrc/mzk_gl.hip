@@ -348,9 +348,6 @@ static int gl_run_plan(const GlPlan* pl, const u64* d_in, u64* d_out, size_t bat
   return MZK_OK;
 }
 
-static bool gl_is_pow2(size_t n) { return n && !(n & (n - 1)); }
-static unsigned gl_ilog2(size_t n) { unsigned l = 0; while (((size_t)1 << l) < n) l++; return l; }
-
 int gl_param_check(int fid, const uint64_t* x, const char* who, const char* what, bool base_only) {
   const int nc = field_gl_comps(fid);
   for (int i = 0; i < nc; i++)
@@ -364,11 +361,11 @@ int gl_param_check(int fid, const uint64_t* x, const char* who, const char* what
 // `batch` transforms of n points each, back to back, in place allowed; the argument checks of ntt_dev_impl / ntt_batch_dev_impl
 int gl_ntt_dev_impl(int fid, const uint64_t* root_host, const void* d_in, void* d_out, size_t n, size_t batch, int inverse, hipStream_t s) {
   if (n == 0 || batch == 0) return MZK_OK;
-  if (!gl_is_pow2(n)) { set_error("cannot compute ntt of non-power-of-two sequence"); return MZK_E_NOT_POW2; }
+  if (!is_pow2(n)) { set_error("cannot compute ntt of non-power-of-two sequence"); return MZK_E_NOT_POW2; }
   if (!d_in || !d_out || (!root_host && n > 1)) { set_error("ntt: null pointer"); return MZK_E_ARG; }
   const size_t esz = field_bytes(fid);
   if (n > 1) MZK_TRY(gl_param_check(fid, root_host, "ntt", "root", false));
-  if (gl_ilog2(n) > gl::TWO_ADICITY || batch > ((size_t)1 << 40) / n) { set_error(batch == 1 ? "ntt: n too large" : "ntt: batch too large"); return MZK_E_ARG; }
+  if (ilog2(n) > gl::TWO_ADICITY || batch > ((size_t)1 << 40) / n) { set_error(batch == 1 ? "ntt: n too large" : "ntt: batch too large"); return MZK_E_ARG; }
   if (n == 1) {      // ntt.rs:12-14 / :54-56: returned unchanged
     if (d_in != d_out) MZK_HIP(hipMemcpyAsync(d_out, d_in, batch * esz, hipMemcpyDeviceToDevice, s));
     return MZK_OK;
@@ -376,7 +373,7 @@ int gl_ntt_dev_impl(int fid, const uint64_t* root_host, const void* d_in, void* 
   for (int i = 1; i < field_gl_comps(fid); i++)      // an element outside the base field has no 2-power order
     if (root_host[i]) { set_error("primitive root must be nth root of unity, where n is len(values)"); return MZK_E_ROOT_ORDER; }
   GlPlan* pl = nullptr;
-  MZK_TRY(gl_get_plan(gl_ilog2(n), inverse != 0, root_host[0], s, &pl));
+  MZK_TRY(gl_get_plan(ilog2(n), inverse != 0, root_host[0], s, &pl));
   return with_gl(fid, [&](auto tag) { return gl_run_plan<decltype(tag)::NC>(pl, (const u64*)d_in, (u64*)d_out, batch, nullptr, s); });
 }
 
@@ -386,11 +383,11 @@ int gl_coset_lde_dev_impl(int fid, const void* d_coef, size_t n_coef, const uint
   if (batch == 0) return MZK_OK;
   if (n_coef > order) { set_error("attempt to subtract with overflow (order - polynomial.coef.len())"); return MZK_E_LENGTH; }
   if (order == 0) return MZK_OK;
-  if (!gl_is_pow2(order)) { set_error("cannot compute ntt of non-power-of-two sequence"); return MZK_E_NOT_POW2; }
+  if (!is_pow2(order)) { set_error("cannot compute ntt of non-power-of-two sequence"); return MZK_E_NOT_POW2; }
   if (!d_out || (!d_coef && n_coef) || !offset_host || !generator_host) { set_error("coset_lde: null pointer"); return MZK_E_ARG; }
   MZK_TRY(gl_param_check(fid, offset_host, "coset_lde", "parameter", true));
   MZK_TRY(gl_param_check(fid, generator_host, "coset_lde", "parameter", true));
-  const unsigned logn = gl_ilog2(order);
+  const unsigned logn = ilog2(order);
   if (logn > gl::TWO_ADICITY || batch > ((size_t)1 << 40) / order) { set_error("coset_lde: order * batch too large"); return MZK_E_ARG; }
   const u64* otab = nullptr;
   MZK_TRY(gl_get_offtab(offset_host[0], s, &otab));

@@ -11,6 +11,7 @@
 // the chunk values with base u^K), so it is parallel at every level.  The witness MSM then runs in
 // mzk_msm.hip on q.
 #include "mzk_common.h"
+#include "mzk_elem.h"
 #include "mzk_ec.h"
 
 namespace mzk {
@@ -24,23 +25,9 @@ void kzg_release_cache() {
   memset(&c, 0, sizeof c);
 }
 
-struct Words8k { u32 w[8]; };
-struct Words16k { u32 w[16]; };
-
-__device__ __forceinline__ void ld8(const u32* __restrict__ g, u32* w) {
-  const uint4* p4 = reinterpret_cast<const uint4*>(g);
-  uint4 a = p4[0], b = p4[1];
-  w[0] = a.x; w[1] = a.y; w[2] = a.z; w[3] = a.w; w[4] = b.x; w[5] = b.y; w[6] = b.z; w[7] = b.w;
-}
-__device__ __forceinline__ void st8(u32* __restrict__ g, const u32* w) {
-  uint4* p4 = reinterpret_cast<uint4*>(g);
-  p4[0] = make_uint4(w[0], w[1], w[2], w[3]);
-  p4[1] = make_uint4(w[4], w[5], w[6], w[7]);
-}
-
 // ---- fixed-base table ---------------------------------------------------------------------------------
 // bases[w] = 2^(8 w) * g1, affine Montgomery (16 words); infinity base -> zeros
-__global__ void k_fb_bases(Words16k g1_plain, u32* __restrict__ bases) {
+__global__ void k_fb_bases(Words16 g1_plain, u32* __restrict__ bases) {
   const int w = blockIdx.x * blockDim.x + threadIdx.x;
   if (w >= 32) return;
   u32 o[16];
@@ -51,8 +38,8 @@ __global__ void k_fb_bases(Words16k g1_plain, u32* __restrict__ bases) {
     Affine a;
     if (xyzz_to_affine(p, &a)) affine_store_mont(a, o);
   }
-  st8(bases + 16 * w, o);
-  st8(bases + 16 * w + 8, o + 8);
+  store_words8(bases + 16 * w, o);
+  store_words8(bases + 16 * w + 8, o + 8);
 }
 // table[w][d] = d * bases[w], d = 0..255 (d = 0 and infinity -> zeros), affine Montgomery
 __global__ void k_fb_table(const u32* __restrict__ bases, u32* __restrict__ table) {
@@ -60,8 +47,8 @@ __global__ void k_fb_table(const u32* __restrict__ bases, u32* __restrict__ tabl
   if (t >= 32 * 256) return;
   const int w = t >> 8, d = t & 255;
   u32 bw[16], o[16];
-  ld8(bases + 16 * w, bw);
-  ld8(bases + 16 * w + 8, bw + 8);
+  load_words8(bases + 16 * w, bw);
+  load_words8(bases + 16 * w + 8, bw + 8);
   for (int i = 0; i < 16; i++) o[i] = 0;
   if (d != 0 && !affine_words_is_inf(bw)) {
     Affine b = affine_load_mont(bw);
@@ -73,8 +60,8 @@ __global__ void k_fb_table(const u32* __restrict__ bases, u32* __restrict__ tabl
     Affine a;
     if (xyzz_to_affine(acc, &a)) affine_store_mont(a, o);
   }
-  st8(table + 16 * t, o);
-  st8(table + 16 * t + 8, o + 8);
+  store_words8(table + 16 * t, o);
+  store_words8(table + 16 * t + 8, o + 8);
 }
 // table16[w][d] = d * 2^(16 w) * g1 for d < 65536 from the 8-bit table: T8[2w][d & 255] + T8[2w+1][d >> 8], written
 // as XYZZ records (converted to affine in one batched pass afterwards).  Halves the additions per SRS power.
@@ -84,22 +71,22 @@ __global__ __launch_bounds__(128) void k_fb_table16(const u32* __restrict__ tabl
   const int w = (int)(t >> 16);
   const u32 d = (u32)t & 65535u, lo = d & 255u, hi = d >> 8;
   u32 a[16], b[16];
-  ld8(table8 + 16 * ((size_t)(2 * w) * 256 + lo), a);
-  ld8(table8 + 16 * ((size_t)(2 * w) * 256 + lo) + 8, a + 8);
-  ld8(table8 + 16 * ((size_t)(2 * w + 1) * 256 + hi), b);
-  ld8(table8 + 16 * ((size_t)(2 * w + 1) * 256 + hi) + 8, b + 8);
+  load_words8(table8 + 16 * ((size_t)(2 * w) * 256 + lo), a);
+  load_words8(table8 + 16 * ((size_t)(2 * w) * 256 + lo) + 8, a + 8);
+  load_words8(table8 + 16 * ((size_t)(2 * w + 1) * 256 + hi), b);
+  load_words8(table8 + 16 * ((size_t)(2 * w + 1) * 256 + hi) + 8, b + 8);
   Xyzz acc = xyzz_inf();
   if (!affine_words_is_inf(a)) acc = xyzz_from_affine(affine_load_mont(a));
   if (!affine_words_is_inf(b)) acc = xyzz_madd(acc, affine_load_mont(b));
   u32 o[32];
   xyzz_store(acc, o);
 #pragma unroll
-  for (int q = 0; q < 4; q++) st8(out_xyzz + 32 * t + 8 * q, o + 8 * q);
+  for (int q = 0; q < 4; q++) store_words8(out_xyzz + 32 * t + 8 * q, o + 8 * q);
 }
 // atab[l][j] = alpha^(j * 2^(11 l)), l < 3, j < 2048, canonical Montgomery: alpha^e for e < 2^33 is then two
 // products instead of a ~96-product square-and-multiply per SRS power.
 constexpr int ATAB_BITS = 11;
-__global__ void k_alpha_table(Words8k alpha_plain, u32* __restrict__ atab) {
+__global__ void k_alpha_table(Words8 alpha_plain, u32* __restrict__ atab) {
   typedef FrParams R;
   const int t = blockIdx.x * blockDim.x + threadIdx.x;
   if (t >= 3 << ATAB_BITS) return;
@@ -108,11 +95,11 @@ __global__ void k_alpha_table(Words8k alpha_plain, u32* __restrict__ atab) {
   Fe<R> v = fe_reduce<R>(fe_pow_u64<R>(a, (u64)j << (ATAB_BITS * l)));
   u32 o[8];
   fe_pack<R>(v, o);
-  st8(atab + 8 * t, o);
+  store_words8(atab + 8 * t, o);
 }
 // acc[i] = alpha^(first+i) * g1 as XYZZ (32 words); the affine conversion is batched afterwards.
 template <int WB>   // window bits of the fixed-base table: 8 (32 windows, 512 KiB) or 16 (16 windows, 64 MiB)
-__global__ __launch_bounds__(128) void k_fb_powers(Words8k alpha_plain, const u32* __restrict__ atab, const u32* __restrict__ table,
+__global__ __launch_bounds__(128) void k_fb_powers(Words8 alpha_plain, const u32* __restrict__ atab, const u32* __restrict__ table,
                                                    size_t first, size_t count, u32* __restrict__ out_xyzz) {
   typedef FrParams R;
   const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -124,9 +111,9 @@ __global__ __launch_bounds__(128) void k_fb_powers(Words8k alpha_plain, const u3
   } else {
     const u32 m = (1u << ATAB_BITS) - 1;
     u32 w0[8], w1[8], w2[8];
-    ld8(atab + 8 * (size_t)(e & m), w0);
-    ld8(atab + 8 * (size_t)((1u << ATAB_BITS) + ((e >> ATAB_BITS) & m)), w1);
-    ld8(atab + 8 * (size_t)((2u << ATAB_BITS) + ((e >> (2 * ATAB_BITS)) & m)), w2);
+    load_words8(atab + 8 * (size_t)(e & m), w0);
+    load_words8(atab + 8 * (size_t)((1u << ATAB_BITS) + ((e >> ATAB_BITS) & m)), w1);
+    load_words8(atab + 8 * (size_t)((2u << ATAB_BITS) + ((e >> (2 * ATAB_BITS)) & m)), w2);
     km = fe_mul<R>(fe_mul<R>(fe_unpack<R>(w0), fe_unpack<R>(w1)), fe_unpack<R>(w2));
   }
   Fe<R> k = fe_from_mont<R>(km);   // canonical alpha^(first+i)   (kzg.rs:33-36)
@@ -139,15 +126,15 @@ __global__ __launch_bounds__(128) void k_fb_powers(Words8k alpha_plain, const u3
     if (d == 0) continue;
     u32 tw[16];
     const size_t idx = ((size_t)w << WB) + d;
-    ld8(table + 16 * idx, tw);
-    ld8(table + 16 * idx + 8, tw + 8);
+    load_words8(table + 16 * idx, tw);
+    load_words8(table + 16 * idx + 8, tw + 8);
     if (affine_words_is_inf(tw)) continue;
     acc = xyzz_madd_with<FeAsm>(acc, affine_load_mont(tw));
   }
   u32 o[32];
   xyzz_store(acc, o);
 #pragma unroll
-  for (int q = 0; q < 4; q++) st8(out_xyzz + 32 * i + 8 * q, o + 8 * q);
+  for (int q = 0; q < 4; q++) store_words8(out_xyzz + 32 * i + 8 * q, o + 8 * q);
 }
 
 // XYZZ -> affine for a whole array with Montgomery's batch-inversion trick: one lane owns BATCH consecutive
@@ -165,8 +152,8 @@ __global__ __launch_bounds__(128) void k_xyzz_batch_to_affine(const u32* __restr
   Fq run = fe_one<P>();
   for (int j = 0; j < len; j++) {
     u32 w[16];
-    ld8(xyzz + 32 * (i0 + j) + 16, w);       // ZZ
-    ld8(xyzz + 32 * (i0 + j) + 24, w + 8);   // ZZZ
+    load_words8(xyzz + 32 * (i0 + j) + 16, w);       // ZZ
+    load_words8(xyzz + 32 * (i0 + j) + 24, w + 8);   // ZZZ
     const bool inf = affine_words_is_inf(w);
     Fq d = FeAsm<P>::mul(fe_unpack<P>(w), fe_unpack<P>(w + 8));
     if (inf) d = fe_one<P>();
@@ -179,7 +166,7 @@ __global__ __launch_bounds__(128) void k_xyzz_batch_to_affine(const u32* __restr
   for (int j = len - 1; j >= 0; j--) {
     u32 w[32];
 #pragma unroll
-    for (int q = 0; q < 4; q++) ld8(xyzz + 32 * (i0 + j) + 8 * q, w + 8 * q);
+    for (int q = 0; q < 4; q++) load_words8(xyzz + 32 * (i0 + j) + 8 * q, w + 8 * q);
     const bool inf = affine_words_is_inf(w + 16);
     const Fq X = fe_unpack<P>(w), Y = fe_unpack<P>(w + 8), ZZ = fe_unpack<P>(w + 16), ZZZ = fe_unpack<P>(w + 24);
     Fq pre;
@@ -199,8 +186,8 @@ __global__ __launch_bounds__(128) void k_xyzz_batch_to_affine(const u32* __restr
       a.y = fe_reduce<P>(FeAsm<P>::mul(Y, FeAsm<P>::mul(dinv, ZZ)));    // Y / ZZZ
       if (out_mont) affine_store_mont(a, o); else affine_store_plain(a, o);
     }
-    st8(out + 16 * (i0 + j), o);
-    st8(out + 16 * (i0 + j) + 8, o + 8);
+    store_words8(out + 16 * (i0 + j), o);
+    store_words8(out + 16 * (i0 + j) + 8, o + 8);
   }
 }
 int xyzz_batch_to_affine(const void* d_xyzz, size_t count, void* d_out, bool out_mont, hipStream_t s) {
@@ -221,10 +208,11 @@ int kzg_setup_g1_dev(const uint64_t* alpha_host, const uint64_t* g1_host, size_t
   if (count == 0) return MZK_OK;
   if (!h_is_canonical(host_field(MZK_FIELD_FR), alpha_host) || !h_is_canonical(host_field(MZK_FIELD_FQ), g1_host) ||
       !h_is_canonical(host_field(MZK_FIELD_FQ), g1_host + 4)) { set_error("kzg_setup: operand not canonical"); return MZK_E_RANGE; }
-  Words8k aw;
-  Words16k gw;
-  for (int i = 0; i < 4; i++) { aw.w[2 * i] = (u32)alpha_host[i]; aw.w[2 * i + 1] = (u32)(alpha_host[i] >> 32); }
-  for (int i = 0; i < 8; i++) { gw.w[2 * i] = (u32)g1_host[i]; gw.w[2 * i + 1] = (u32)(g1_host[i] >> 32); }
+  Words8 aw;
+  Words16 gw;
+  h_words(alpha_host, 4, aw.w);
+  h_words(g1_host, 4, gw.w);          // x
+  h_words(g1_host + 4, 4, gw.w + 8);  // y
   u32 *bases, *table, *acc, *atab;
   MZK_TRY(ws.get(WS_MISC_C, (size_t)(3 << ATAB_BITS) * 32, (void**)&atab));
   MZK_TRY(ws_cache_get(WS_FB_TABLE8, 32 * 64 + 32 * 256 * 64, (void**)&bases));
@@ -291,31 +279,17 @@ struct SdRec {          // one job of one level, as the kernels read it; u / end
   u32 end[8];           // b_len, canonical
   u32 has_end;          // q also gets b_len
 };
-template <class P> __device__ __forceinline__ Fe<P> sd_gload(const u32* __restrict__ g, size_t i) {
-  u32 w[P::NW];
-  const uint4* p4 = reinterpret_cast<const uint4*>(g + i * P::NW);
-#pragma unroll
-  for (int k = 0; k < P::NW / 4; k++) { const uint4 v = p4[k]; w[4 * k] = v.x; w[4 * k + 1] = v.y; w[4 * k + 2] = v.z; w[4 * k + 3] = v.w; }
-  return fe_unpack<P>(w);
-}
-template <class P> __device__ __forceinline__ void sd_gstore(u32* __restrict__ g, size_t i, const Fe<P>& v) {   // v canonical
-  u32 w[P::NW];
-  fe_pack<P>(v, w);
-  uint4* p4 = reinterpret_cast<uint4*>(g + i * P::NW);
-#pragma unroll
-  for (int k = 0; k < P::NW / 4; k++) p4[k] = make_uint4(w[4 * k], w[4 * k + 1], w[4 * k + 2], w[4 * k + 3]);
-}
 // b_lo from b_hi = acc over the coefficients [lo, hi); u in Montgomery form (fe_mul(x, u R) = x u)
 template <class P> __device__ __forceinline__ Fe<P> sd_horner(const u32* __restrict__ c, u64 lo, u64 hi, const Fe<P>& u, Fe<P> acc) {
-  for (u64 t = hi; t-- > lo;) acc = fe_add<P>(fe_mul<P>(acc, u), sd_gload<P>(c, t));
+  for (u64 t = hi; t-- > lo;) acc = fe_add<P>(fe_mul<P>(acc, u), fe_gload<P>(c, t));
   return fe_reduce<P>(acc);
 }
 // b_hi-1 .. b_lo from b_hi = acc into q (b_t at q[t - 1]; b_0 is y's)
 template <class P> __device__ __forceinline__ void sd_fill(const SdRec& J, u64 lo, u64 hi, const Fe<P>& u, Fe<P> acc) {
-  if (hi == J.len && J.has_end) sd_gstore<P>(J.q, hi - 1, acc);
+  if (hi == J.len && J.has_end) fe_gstore<P>(J.q, hi - 1, acc);
   for (u64 t = hi; t-- > lo;) {
-    acc = fe_reduce<P>(fe_add<P>(fe_mul<P>(acc, u), sd_gload<P>(J.src, t)));
-    if (t > 0) sd_gstore<P>(J.q, t - 1, acc);
+    acc = fe_reduce<P>(fe_add<P>(fe_mul<P>(acc, u), fe_gload<P>(J.src, t)));
+    if (t > 0) fe_gstore<P>(J.q, t - 1, acc);
   }
 }
 // a job's values are wave-uniform: held in VGPRs, the powers of u of the scan below do not overflow the scalar registers
@@ -359,7 +333,7 @@ __global__ __launch_bounds__(SD_THREADS) void k_sd_block(const SdRec* __restrict
     for (int i = 0; i < P::L; i++) S[L][i] = mine.l[i];
     pw = fe_sqr<P>(pw);
   }
-  if (L == 0 && J.y) sd_gstore<P>(J.y, 0, mine);
+  if (L == 0 && J.y) fe_gstore<P>(J.y, 0, mine);
   __syncthreads();
   if (!J.q || lo >= n) return;
   E acc = end;                                              // b_hi
@@ -386,7 +360,7 @@ __global__ __launch_bounds__(64) void k_sd_eval(const SdRec* __restrict__ jobs, 
   const u64 lo = (g - J.chunk0) << SD_K_LOG;
   const u64 hi = (lo + SD_K < J.len) ? lo + SD_K : J.len;
   const Fe<P> u = fe_to_mont<P>(fe_unpack<P>(J.u));
-  sd_gstore<P>(h, g, sd_horner<P>(J.src, lo, hi, u, hi == J.len ? fe_unpack<P>(J.end) : fe_zero<P>()));
+  fe_gstore<P>(h, g, sd_horner<P>(J.src, lo, hi, u, hi == J.len ? fe_unpack<P>(J.end) : fe_zero<P>()));
 }
 // chunk g from b at the start of the next chunk, carry[g] (the level above wrote it as its quotient), or from the end
 template <class P>
@@ -398,13 +372,9 @@ __global__ __launch_bounds__(64) void k_sd_fill(const SdRec* __restrict__ jobs, 
   const u64 lo = (g - J.chunk0) << SD_K_LOG;
   const u64 hi = (lo + SD_K < J.len) ? lo + SD_K : J.len;
   const Fe<P> u = fe_to_mont<P>(fe_unpack<P>(J.u));
-  sd_fill<P>(J, lo, hi, u, hi == J.len ? fe_unpack<P>(J.end) : sd_gload<P>(carry, g));
+  sd_fill<P>(J, lo, hi, u, hi == J.len ? fe_unpack<P>(J.end) : fe_gload<P>(carry, g));
 }
 
-// nl 64-bit limbs -> 2 nl words
-static void sd_words(const uint64_t* v, int nl, u32* w) {
-  for (int i = 0; i < nl; i++) { w[2 * i] = (u32)v[i]; w[2 * i + 1] = (u32)(v[i] >> 32); }
-}
 template <class P>
 static int synth_div_impl(int fid, const SdJob* jobs, const size_t* rounds, int nrounds, hipStream_t s) {
   WsFrame ws("synth_div_impl");
@@ -430,8 +400,8 @@ static int synth_div_impl(int fid, const SdJob* jobs, const size_t* rounds, int 
         if (J.len == 0) continue;
         SdRec x = {};
         x.src = (const u32*)J.src; x.q = (u32*)J.q; x.y = (u32*)J.y; x.len = J.len;
-        sd_words(J.u, nl, x.u);
-        if (J.end) { sd_words(J.end, nl, x.end); x.has_end = 1; }
+        h_words(J.u, nl, x.u);
+        if (J.end) { h_words(J.end, nl, x.end); x.has_end = 1; }
         tab.push_back(x);
         us.insert(us.end(), J.u, J.u + nl);
         fill |= J.q != nullptr;                            // every level above has q where level 0 has
@@ -461,7 +431,7 @@ static int synth_div_impl(int fid, const SdJob* jobs, const size_t* rounds, int 
           if (D) {                                          // host powers are the call's set-up latency: once per run of equal points
             if (k > 0 && !memcmp(&us[nl * k], &us[nl * (k - 1)], ub)) memcpy(&uk[nl * k], &uk[nl * (k - 1)], ub);
             else h_powmod_u64(hf, &uk[nl * k], &us[nl * k], SD_K);
-            sd_words(&uk[nl * k], nl, x.u);
+            h_words(&uk[nl * k], nl, x.u);
           }
           tab.push_back(x);
         }

@@ -35,7 +35,6 @@ struct mzk_merkle {
 
 namespace mzk {
 
-bool is_pow2(size_t n);
 int canonicalize_signed(int fid, void* d_elems, const void* d_neg, size_t n, hipStream_t s);
 int merkle_stamp(mzk_merkle* t, hipStream_t s, bool complete_on_return = false);
 int merkle_hash_levels(int kind, int fid, const void* d_leaves, const u64* d_off, size_t n, u64* d_nodes, hipStream_t s,

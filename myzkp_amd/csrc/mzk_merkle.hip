@@ -11,6 +11,7 @@
 #include <algorithm>
 #include <atomic>
 #include "mzk_common.h"
+#include "mzk_elem.h"
 #include "mzk_merkle.h"           // the handle type and what mzk_fri.hip calls of this file
 #include "mzk_keccak_pair.h"
 #include "mzk_gl.h"
@@ -137,9 +138,7 @@ __global__ __launch_bounds__(LEAF_THREADS) void k_merkle_leaf_pairs(const u32* _
 #pragma unroll
   for (int e = 0; e < 2; e++) {
     u32 w[NW];
-    const uint4* p4 = reinterpret_cast<const uint4*>(elems + (2 * i + e) * NW);
-#pragma unroll
-    for (int q = 0; q < NW / 4; q++) { uint4 v = p4[q]; w[4 * q] = v.x; w[4 * q + 1] = v.y; w[4 * q + 2] = v.z; w[4 * q + 3] = v.w; }
+    gload_words<NW>(elems, 2 * i + e, w);
     int k = 0;                                    // significant u32 digits (BigUint keeps no leading zero digit)
 #pragma unroll
     for (int j = 0; j < NW; j++) if (w[j]) k = j + 1;
@@ -186,18 +185,12 @@ __global__ __launch_bounds__(LEAF_THREADS) void k_merkle_leaf_pairs_lp(const u32
   if (live) {
     auto put = [&](int pos, u32 byte) { atomicOr(&blk[pos >> 2][col], (byte & 255u) << (8 * (pos & 3))); };     // the two lanes may meet in one word
     u32 w0[NW], w[NW];
-    {
-      const uint4* p4 = reinterpret_cast<const uint4*>(elems + (2 * i) * NW);
-#pragma unroll
-      for (int q = 0; q < NW / 4; q++) { uint4 v = p4[q]; w0[4 * q] = v.x; w0[4 * q + 1] = v.y; w0[4 * q + 2] = v.z; w0[4 * q + 3] = v.w; }
-    }
+    gload_words<NW>(elems, 2 * i, w0);
     int k0 = 0;
 #pragma unroll
     for (int j = 0; j < NW; j++) if (w0[j]) k0 = j + 1;
     if (parity) {
-      const uint4* p4 = reinterpret_cast<const uint4*>(elems + (2 * i + 1) * NW);
-#pragma unroll
-      for (int q = 0; q < NW / 4; q++) { uint4 v = p4[q]; w[4 * q] = v.x; w[4 * q + 1] = v.y; w[4 * q + 2] = v.z; w[4 * q + 3] = v.w; }
+      gload_words<NW>(elems, 2 * i + 1, w);
     } else {
 #pragma unroll
       for (int j = 0; j < NW; j++) w[j] = w0[j];
@@ -506,7 +499,6 @@ __global__ void k_gather_leaves(const u32* __restrict__ leaves, int leaf_words, 
 using namespace mzk;
 
 namespace mzk {
-bool is_pow2(size_t n) { return n && !(n & (n - 1)); }
 
 // end of a successful build on stream s of the current context
 // complete_on_return: the caller synchronizes the stream before it hands the tree out (mzk_fri_commit does once, after its last round --

@@ -30,6 +30,7 @@
 #include <algorithm>
 #include <vector>
 #include "mzk_common.h"
+#include "mzk_elem.h"
 #include "mzk_field_asm.h"
 
 namespace mzk {
@@ -44,20 +45,6 @@ struct MpOp { u32 op, arg; };
 struct MpVars { u32 first_slot[MP_MAX_VARS]; u32 depth[MP_MAX_VARS]; };
 struct MpRows { size_t off[MP_MAX_VARS + 1]; };
 
-template <class P> __device__ __forceinline__ Fe<P> mp_gload(const u32* __restrict__ g, size_t idx) {
-  u32 w[P::NW];
-  const uint4* p4 = reinterpret_cast<const uint4*>(g + idx * P::NW);
-#pragma unroll
-  for (int q = 0; q < P::NW / 4; q++) { const uint4 v = p4[q]; w[4 * q] = v.x; w[4 * q + 1] = v.y; w[4 * q + 2] = v.z; w[4 * q + 3] = v.w; }
-  return fe_unpack<P>(w);
-}
-template <class P> __device__ __forceinline__ void mp_gstore(u32* __restrict__ g, size_t idx, const Fe<P>& v) {   // v canonical
-  u32 w[P::NW];
-  fe_pack<P>(v, w);
-  uint4* p4 = reinterpret_cast<uint4*>(g + idx * P::NW);
-#pragma unroll
-  for (int q = 0; q < P::NW / 4; q++) p4[q] = make_uint4(w[4 * q], w[4 * q + 1], w[4 * q + 2], w[4 * q + 3]);
-}
 // the same element for every lane: word loads at a wave-uniform address
 template <class P> __device__ __forceinline__ Fe<P> mp_uload(const u32* __restrict__ g, u32 idx) {
   u32 w[P::NW];
@@ -100,7 +87,7 @@ __global__ __launch_bounds__(MP_LANES) void k_mp_terms(const u32* __restrict__ E
   for (int i = 0; i < n_vars; i++) {
     const u32 depth = vars.depth[i], s0 = vars.first_slot[i];
     if (depth == 0) continue;
-    const Fe<P> x = FeAsm<P>::mul(mp_gload<P>(E, (size_t)i * n + jj), fe_r2<P>());
+    const Fe<P> x = FeAsm<P>::mul(fe_gload<P>(E, (size_t)i * n + jj), fe_r2<P>());
     mp_lds_store<P>(mp_lds, s0, lane, x);
     if (depth > 1) {
       const Fe<P> x2 = FeAsm<P>::sqr(x);
@@ -136,7 +123,7 @@ __global__ __launch_bounds__(MP_LANES) void k_mp_terms(const u32* __restrict__ E
     }
     if (w & MP_FLUSH) sum = fe_reduce<P>(fe_add<P>(sum, acc));
   }
-  if (j < n) mp_gstore<P>(V, (size_t)a * n + j, sum);
+  if (j < n) fe_gstore<P>(V, (size_t)a * n + j, sum);
 }
 
 // out row a (stride elements) = the first min(n, stride) elements of V's row a, zeros behind them; lens[a] = max(lens[a], 1 + index of the
@@ -182,11 +169,11 @@ __global__ __launch_bounds__(256) void k_mp_lincomb(const u32* __restrict__ poly
     u32 w[P::NW];
 #pragma unroll
     for (int k = 0; k < P::NW; k++) w[k] = items[i].w[k];
-    acc = fe_reduce<P>(fe_add<P>(acc, FeAsm<P>::mul(mp_gload<P>(polys, off + (j - sft)), fe_unpack<P>(w))));
+    acc = fe_reduce<P>(fe_add<P>(acc, FeAsm<P>::mul(fe_gload<P>(polys, off + (j - sft)), fe_unpack<P>(w))));
   }
   unsigned long long best = 0;
   if (j < cap) {
-    mp_gstore<P>(out, j, acc);
+    fe_gstore<P>(out, j, acc);
     if (!fe_is_zero_canon<P>(acc)) best = j + 1;
   }
   sh[threadIdx.x] = best;
@@ -393,15 +380,6 @@ static int mp_compose_dev(int fid, const uint64_t* term_coefs, const uint32_t* t
   return MZK_OK;
 }
 
-// v R mod p, R = 2^(29 L), as 32-bit words
-static void mp_mont_words(int fid, const uint64_t* v, u32* out8) {
-  const HostField* hf = host_field(fid);
-  uint64_t r[4] = {0, 0, 0, 0}, t[4] = {0, 0, 0, 0};
-  h_rmod(hf, r);
-  h_mulmod(hf, t, v, r);
-  for (int i = 0; i < 8; i++) out8[i] = i < 2 * hf->nl ? (u32)(t[i / 2] >> (32 * (i & 1))) : 0u;
-}
-
 static int mp_lincomb_check(int fid, const size_t* offsets, size_t count, const uint64_t* weights, const size_t* shifts, size_t out_cap, const void* out,
                             const size_t* out_len) {
   MZK_TRY(field_check(fid, "poly_lincomb"));
@@ -427,10 +405,10 @@ static int mp_lincomb_dev(int fid, const void* d_polys, const size_t* offsets, s
   *out_len = 0;
   if (out_cap == 0) return MZK_OK;
   std::vector<MpLcItem> items(count);
-  const int nl = host_field(fid)->nl;
+  const HostField* hf = host_field(fid);
   for (size_t i = 0; i < count; i++) {
     items[i].off = offsets[i] - offsets[0]; items[i].len = offsets[i + 1] - offsets[i]; items[i].shift = shifts[i];
-    mp_mont_words(fid, weights + i * nl, items[i].w);
+    h_mont_words(hf, weights + i * hf->nl, items[i].w);
     items[i].pad[0] = items[i].pad[1] = 0;
   }
   char* d_tab;

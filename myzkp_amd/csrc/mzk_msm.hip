@@ -21,6 +21,7 @@
 #include <stdlib.h>
 #include <type_traits>
 #include "mzk_common.h"
+#include "mzk_elem.h"
 #include "mzk_ec.h"
 #include "mzk_coop.h"
 #include "mzk_row.h"
@@ -43,17 +44,7 @@ static const MsmKnobs& msm_knobs() {
 
 int msm_generic_window_bits(size_t n) { return choose_shape_glv(n ? n : 1, msm_knobs().glv_c).c; }
 
-// ---- global loads of packed 256-bit values -----------------------------------------------------------
-__device__ __forceinline__ void load_words8(const u32* __restrict__ g, u32* w) {
-  const uint4* p4 = reinterpret_cast<const uint4*>(g);
-  uint4 a = p4[0], b = p4[1];
-  w[0] = a.x; w[1] = a.y; w[2] = a.z; w[3] = a.w; w[4] = b.x; w[5] = b.y; w[6] = b.z; w[7] = b.w;
-}
-__device__ __forceinline__ void store_words8(u32* __restrict__ g, const u32* w) {
-  uint4* p4 = reinterpret_cast<uint4*>(g);
-  p4[0] = make_uint4(w[0], w[1], w[2], w[3]);
-  p4[1] = make_uint4(w[4], w[5], w[6], w[7]);
-}
+// ---- global loads of packed 256-bit values (load_words8 / store_words8: mzk_elem.h) --------------------
 __device__ __forceinline__ Xyzz xyzz_gload(const u32* __restrict__ g, size_t idx) {
   u32 w[32];
 #pragma unroll

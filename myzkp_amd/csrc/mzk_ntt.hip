@@ -23,6 +23,7 @@
 // load phase nor the strided stage accesses serialise on a bank.
 #include <stdlib.h>
 #include "mzk_common.h"
+#include "mzk_elem.h"
 #include "mzk_field_asm.h"
 #include "mzk_gl.h"
 #include "mzk_ntt_plan.h"
@@ -79,8 +80,6 @@ static const NttKnobs& ntt_knobs() {
   return k;
 }
 
-struct Words8 { u32 w[8]; };
-
 // ---- global memory <-> limbs ----------------------------------------------------------------------
 // The streaming accesses of the transform passes -- the data (read once, written once per pass) and the inter-pass twiddles -- do NOT
 // carry the non-temporal hint.  A plain copy gains 25 % from it on MI355X (profiles/round5_copy_kernel_variants.txt); the transforms
@@ -114,33 +113,6 @@ template <class P> __device__ __forceinline__ void gstore_stream(u32* __restrict
     t.x = w[4 * q]; t.y = w[4 * q + 1]; t.z = w[4 * q + 2]; t.w = w[4 * q + 3];
     stream_store16(g + idx * P::NW + 4 * q, t, wt);
   }
-}
-template <class P> __device__ __forceinline__ Fe<P> gload(const u32* __restrict__ g, size_t idx) {
-  u32 w[P::NW];
-  const uint4* p4 = reinterpret_cast<const uint4*>(g + idx * P::NW);
-#pragma unroll
-  for (int q = 0; q < P::NW / 4; q++) {
-    uint4 v = p4[q];
-    w[4 * q] = v.x; w[4 * q + 1] = v.y; w[4 * q + 2] = v.z; w[4 * q + 3] = v.w;
-  }
-  return fe_unpack<P>(w);
-}
-// the packed words only: the tile loops issue the loads of ALL their elements first and unpack afterwards, so a lane has
-// several 32-byte requests in flight instead of one per loop trip (load, wait, store to LDS, next)
-template <class P> __device__ __forceinline__ void gload_words(const u32* __restrict__ g, size_t idx, u32 (&w)[P::NW]) {
-  const uint4* p4 = reinterpret_cast<const uint4*>(g + idx * P::NW);
-#pragma unroll
-  for (int q = 0; q < P::NW / 4; q++) {
-    uint4 v = p4[q];
-    w[4 * q] = v.x; w[4 * q + 1] = v.y; w[4 * q + 2] = v.z; w[4 * q + 3] = v.w;
-  }
-}
-template <class P> __device__ __forceinline__ void gstore(u32* __restrict__ g, size_t idx, const Fe<P>& v) {
-  u32 w[P::NW];
-  fe_pack<P>(v, w);
-  uint4* p4 = reinterpret_cast<uint4*>(g + idx * P::NW);
-#pragma unroll
-  for (int q = 0; q < P::NW / 4; q++) p4[q] = make_uint4(w[4 * q], w[4 * q + 1], w[4 * q + 2], w[4 * q + 3]);
 }
 // value < 2p, normalised -> something fe_pack can hold (value < 2^(32 NW)).
 template <class P> __device__ __forceinline__ Fe<P> fe_fit(const Fe<P>& v) {
@@ -204,7 +176,7 @@ __device__ __forceinline__ void stage_twiddles(u32* twl, const u32* __restrict__
 #pragma unroll
       for (int i = 0; i < P::NW; i++) twl[i * G::TWS + j] = tw[(size_t)j * P::NW + i];
     } else {
-      Fe<P> w = gload<P>(tw, j);
+      Fe<P> w = fe_gload<P>(tw, j);
 #pragma unroll
       for (int i = 0; i < P::L; i++) twl[i * G::TWS + j] = w.l[i];
     }
@@ -230,7 +202,7 @@ template <class P, class G>
 __device__ __forceinline__ Fe<P> tw_fetch(const u32* twl, int tws, int ti) {
   Fe<P> w;
   if constexpr (G::TWG) {
-    w = gload<P>(twl, (size_t)ti);         // twl = the plan's table in global memory (16 bytes per M128 twiddle; L1 / scalar cache)
+    w = fe_gload<P>(twl, (size_t)ti);         // twl = the plan's table in global memory (16 bytes per M128 twiddle; L1 / scalar cache)
   } else if constexpr (G::template twpack<P>()) {
     u32 ww[P::NW];
 #pragma unroll
@@ -365,7 +337,7 @@ __device__ __forceinline__ void first_pair_regs(Fe<P>& x0, Fe<P>& x1, Fe<P>& x2,
   if constexpr (HasShoup<P>::value) {
     if (tw_shoup) { radix4_shoup<P>(x0, x1, x2, x3, tw_shoup, lgn, 1, 0); return; }
   }
-  const Fe<P> zeta = gload<P>(tw_tile, (size_t)1 << (lgn - 2));
+  const Fe<P> zeta = fe_gload<P>(tw_tile, (size_t)1 << (lgn - 2));
   bfly<P, G, NTT_LAZY_FIRST>(x0, x1, nullptr, 0, 0, true, true);
   bfly<P, G, NTT_LAZY_FIRST>(x2, x3, nullptr, 0, 0, true, true);
   bfly<P, G>(x0, x2, nullptr, 0, 0, true, false);
@@ -516,14 +488,14 @@ __global__ __launch_bounds__(G::NT, G::WPE) void k_ntt_strided(const u32* __rest
       // the coefficient vectors back to back, n_coef apart
       const size_t idx = ((size_t)j1 << lgM) + (ct << lgc) + c;
       if (idx < pre.n_coef) {
-        const Fe<P> x = gload<P>(pre.coef, o * pre.n_coef + idx);
-        const Fe<P> wc = gload<P>(pre.pre_col, (ct << lgc) + c), wr = gload<P>(pre.pre_row, (size_t)j1);
+        const Fe<P> x = fe_gload<P>(pre.coef, o * pre.n_coef + idx);
+        const Fe<P> wc = fe_gload<P>(pre.pre_col, (ct << lgc) + c), wr = fe_gload<P>(pre.pre_row, (size_t)j1);
         v = fe_fit<P>(FeAsm<P>::mul(FeAsm<P>::mul(x, wc), wr));    // plain * Montgomery * Montgomery = plain
       } else {
         v = fe_zero<P>();
       }
     } else {
-      v = gload<P>(in, base + ((size_t)j1 << lgM) + c);
+      v = fe_gload<P>(in, base + ((size_t)j1 << lgM) + c);
     }
     const int k = (int)(__brev((unsigned)j1) >> (32 - lgn));
     lds_store<P, G>(lds, (k << lgc) | c, v);
@@ -692,7 +664,7 @@ __global__ __launch_bounds__(256) void k_ntt_columns(const u32* __restrict__ in,
   if (c >= cols) return;
   Fe<P> x[W];
 #pragma unroll
-  for (int i = 0; i < W; i++) x[(int)(__brev((unsigned)i) >> (32 - LGW))] = gload<P>(in, (size_t)i * cols + c);
+  for (int i = 0; i < W; i++) x[(int)(__brev((unsigned)i) >> (32 - LGW))] = fe_gload<P>(in, (size_t)i * cols + c);
 #pragma unroll
   for (int s = 1; s <= LGW; s++) {
     const int half = 1 << (s - 1);
@@ -701,7 +673,7 @@ __global__ __launch_bounds__(256) void k_ntt_columns(const u32* __restrict__ in,
       const int j = b & (half - 1), g = b >> (s - 1);
       const int lo = (g << s) | j, hi = lo + half;
       Fe<P> t = x[hi];
-      if (j != 0) t = FeAsm<P>::mul(t, gload<P>(tw, (size_t)(j << (LGW - s))));
+      if (j != 0) t = FeAsm<P>::mul(t, fe_gload<P>(tw, (size_t)(j << (LGW - s))));
       else if (s != 1) t = fe_weak_reduce<P>(t);
       x[hi] = fe_sub_carry<P, 8>(x[lo], t);
       x[lo] = fe_add_carry<P>(x[lo], t);
@@ -713,7 +685,7 @@ __global__ __launch_bounds__(256) void k_ntt_columns(const u32* __restrict__ in,
   for (int k = 0; k < W; k++) {
     Fe<P> v = x[k];
     if (has_scale) v = FeAsm<P>::mul(v, sc);
-    gstore<P>(out, (size_t)k * cols + c, fe_reduce<P>(v));
+    fe_gstore<P>(out, (size_t)k * cols + c, fe_reduce<P>(v));
   }
 }
 
@@ -741,7 +713,7 @@ __global__ void k_gen_pow_table(Words8 root_plain, uint64_t emul, size_t count, 
   Fe<P> g = fe_pow_u64<P>(fe_to_mont<P>(fe_unpack<P>(root_plain.w)), emul);
   Fe<P> cur = fe_pow_u64<P>(g, j0);
   for (int i = 0; i < GEN_CHUNK && j0 + i < count; i++) {
-    gstore<P>(out, j0 + i, fe_reduce<P>(cur));
+    fe_gstore<P>(out, j0 + i, fe_reduce<P>(cur));
     cur = fe_mul<P>(cur, g);
   }
 }
@@ -759,7 +731,7 @@ __global__ void k_gen_inter_table(Words8 root_plain, uint64_t emul, int lgn, int
   Fe<P> gk = fe_pow_u64<P>(g, k);
   Fe<P> cur = fe_mul<P>(fe_pow_u64<P>(gk, j0), fe_to_mont<P>(fe_unpack<P>(scale_plain.w)));
   for (size_t i = 0; i < clen; i++) {
-    gstore<P>(out, k * M + j0 + i, fe_reduce<P>(cur));
+    fe_gstore<P>(out, k * M + j0 + i, fe_reduce<P>(cur));
     cur = fe_mul<P>(cur, gk);
   }
 }
@@ -769,18 +741,18 @@ __global__ void k_gen_inter_table(Words8 root_plain, uint64_t emul, int lgn, int
 template <class P>
 __device__ __forceinline__ void scale_pad_chunk(const u32* __restrict__ coef, size_t n_coef, const Words8& factor_plain, u32* __restrict__ out, size_t width, size_t j0) {
   if (j0 >= n_coef) {
-    for (int i = 0; i < GEN_CHUNK && j0 + i < width; i++) gstore<P>(out, j0 + i, fe_zero<P>());
+    for (int i = 0; i < GEN_CHUNK && j0 + i < width; i++) fe_gstore<P>(out, j0 + i, fe_zero<P>());
     return;
   }
   Fe<P> g = fe_to_mont<P>(fe_unpack<P>(factor_plain.w));
   Fe<P> cur = fe_pow_u64<P>(g, j0);
   for (int i = 0; i < GEN_CHUNK && j0 + i < width; i++) {
     if (j0 + i < n_coef) {
-      Fe<P> c = gload<P>(coef, j0 + i);
-      gstore<P>(out, j0 + i, fe_reduce<P>(FeAsm<P>::mul(c, cur)));
+      Fe<P> c = fe_gload<P>(coef, j0 + i);
+      fe_gstore<P>(out, j0 + i, fe_reduce<P>(FeAsm<P>::mul(c, cur)));
       cur = FeAsm<P>::mul(cur, g);
     } else {
-      gstore<P>(out, j0 + i, fe_zero<P>());
+      fe_gstore<P>(out, j0 + i, fe_zero<P>());
     }
   }
 }
@@ -804,8 +776,8 @@ __global__ void k_poly_scale(const u32* __restrict__ in, size_t n, Words8 ratio_
   const Fe<P> g = fe_to_mont<P>(fe_unpack<P>(ratio_plain.w));
   Fe<P> cur = FeAsm<P>::mul(fe_pow_u64<P>(g, j0), fe_to_mont<P>(fe_unpack<P>(lead_plain.w)));
   for (int i = 0; i < GEN_CHUNK && j0 + i < n; i++) {
-    const Fe<P> c = gload<P>(in, j0 + i);
-    gstore<P>(out, j0 + i, fe_reduce<P>(FeAsm<P>::mul(c, cur)));
+    const Fe<P> c = fe_gload<P>(in, j0 + i);
+    fe_gstore<P>(out, j0 + i, fe_reduce<P>(FeAsm<P>::mul(c, cur)));
     cur = FeAsm<P>::mul(cur, g);
   }
 }
@@ -814,9 +786,9 @@ template <class P>
 __global__ void k_pointwise_mul(const u32* __restrict__ a, const u32* __restrict__ b, u32* __restrict__ out, size_t n) {
   const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
-  Fe<P> x = gload<P>(a, i), y = gload<P>(b, i);
+  Fe<P> x = fe_gload<P>(a, i), y = fe_gload<P>(b, i);
   Fe<P> t = FeAsm<P>::mul(FeAsm<P>::mul(x, y), fe_r2<P>());
-  gstore<P>(out, i, fe_reduce<P>(t));
+  fe_gstore<P>(out, i, fe_reduce<P>(t));
 }
 
 // ---- plans -------------------------------------------------------------------------------------------
@@ -844,14 +816,6 @@ void ntt_release_plans() {
   for (auto& ce : g_lde_cache[ctx().index]) {      // mzk_shutdown walks the contexts: drop this one's entries and their events
     if (ce.ready) (void)hipEventDestroy(ce.ready);
     memset(&ce, 0, sizeof ce);
-  }
-}
-
-static void to_words(const uint64_t* limbs, int nl, Words8* w) {
-  memset(w, 0, sizeof *w);
-  for (int i = 0; i < nl; i++) {
-    w->w[2 * i] = (u32)limbs[i];
-    w->w[2 * i + 1] = (u32)(limbs[i] >> 32);
   }
 }
 
@@ -904,11 +868,11 @@ template <class P>
 static int build_tables(NttPlan* pl, const NttLevels& li, const uint64_t* eff_root, const uint64_t* fold_scale, hipStream_t s) {
   const HostField* hf = host_field(pl->fid);
   Words8 rootw, scalew;
-  to_words(eff_root, hf->nl, &rootw);
-  to_words(fold_scale, hf->nl, &scalew);
+  h_words(eff_root, hf->nl, rootw.w);
+  h_words(fold_scale, hf->nl, scalew.w);
   uint64_t one[4] = {1, 0, 0, 0};
   Words8 onew;
-  to_words(one, hf->nl, &onew);
+  h_words(one, hf->nl, onew.w);
   const size_t esz = sizeof(u32) * P::NW;
   int lg_after = (int)pl->logn;  // log of (n_t * M_t) while walking levels
   for (int t = 0; t < li.nlev; t++) {
@@ -980,13 +944,8 @@ static int get_plan(const NttSchedule& sched, bool inverse, const uint64_t* root
   }
   bool fold_is_one = h_is_one(hf, fold);
   if (sched.li.nlev == 1 && !fold_is_one) {
-    // single pass: no inter-pass table to fold into -> explicit scale in the last pass (Montgomery form
-    // computed on the host: fold * R mod p via mulmod with R mod p)
-    uint64_t r_mod_p[4] = {0, 0, 0, 0};
-    h_rmod(hf, r_mod_p);
-    uint64_t m[4];
-    h_mulmod(hf, m, fold, r_mod_p);
-    to_words(m, hf->nl, &pl->last_scale);
+    // single pass: no inter-pass table to fold into -> explicit scale in the last pass (Montgomery form computed on the host)
+    h_mont_words(hf, fold, pl->last_scale.w);
     pl->has_last_scale = 1;
   }
   MZK_TRY(with_field(fid, [&](auto tag) { return build_tables<typename decltype(tag)::P>(pl.get(), sched.li, eff_root, fold, s); }));
@@ -1045,9 +1004,6 @@ static int run_plan(const NttPlan* pl, const NttSchedule& sc, const u32* d_in, u
     default: return walk(GeoS());
   }
 }
-
-static bool is_pow2(size_t n) { return n && !(n & (n - 1)); }
-static unsigned ilog2(size_t n) { unsigned l = 0; while (((size_t)1 << l) < n) l++; return l; }
 
 // extra_scale_host: optional plain constant multiplied into every output (used by the polynomial
 // products to fold constants); nullptr = 1.
@@ -1140,8 +1096,8 @@ int poly_scale_dev_impl(int fid, const void* d_in, size_t n, const uint64_t* rat
   if (!h_is_canonical(hf, ratio_host) || (lead_host && !h_is_canonical(hf, lead_host))) { set_error("poly_scale: parameter not canonical"); return MZK_E_RANGE; }
   const uint64_t one[4] = {1, 0, 0, 0};
   Words8 rw, lw;
-  to_words(ratio_host, hf->nl, &rw);
-  to_words(lead_host ? lead_host : one, hf->nl, &lw);
+  h_words(ratio_host, hf->nl, rw.w);
+  h_words(lead_host ? lead_host : one, hf->nl, lw.w);
   const size_t chunks = (n + GEN_CHUNK - 1) / GEN_CHUNK;
   const unsigned blocks = (unsigned)((chunks + 255) / 256);
   MZK_TRY(MZK_FIELD_LAUNCH(fid, k_poly_scale<P>, dim3(blocks), dim3(256), 0, s, (const u32*)d_in, n, rw, lw, (u32*)d_out));
@@ -1162,7 +1118,7 @@ int coset_lde_dev_impl(int fid, const void* d_coef, size_t n_coef, const uint64_
   const HostField* hf = host_field(fid);
   if (!h_is_canonical(hf, offset_host) || !h_is_canonical(hf, generator_host)) { set_error("coset_lde: parameter not canonical"); return MZK_E_RANGE; }
   Words8 offw;
-  to_words(offset_host, hf->nl, &offw);
+  h_words(offset_host, hf->nl, offw.w);
   const unsigned logn = ilog2(order);
   if (logn > 32 || batch > ((size_t)1 << 40) / order) { set_error("coset_lde: order * batch too large"); return MZK_E_ARG; }
   const NttSchedule sc = ntt_plan(fid, logn, batch, ntt_knobs());
@@ -1224,11 +1180,11 @@ __global__ void k_fri_fold(const u32* __restrict__ cw, size_t h, Words8 r0_mont,
   const Fe<P> winv = fe_unpack<P>(winv_mont.w), half = fe_unpack<P>(half_mont.w);
   Fe<P> r = FeAsm<P>::mul(fe_unpack<P>(r0_mont.w), fe_pow_u64<P>(winv, i0));   // r_{i0}, Montgomery form
   for (int t = 0; t < per_lane && i0 + t < h; t++) {
-    const Fe<P> a = gload<P>(cw, i0 + t), b = gload<P>(cw, h + i0 + t);     // canonical, plain domain
+    const Fe<P> a = fe_gload<P>(cw, i0 + t), b = fe_gload<P>(cw, h + i0 + t);     // canonical, plain domain
     const Fe<P> sum = fe_add<P>(a, b);                                       // < 2p, limbs < 2^30
     const Fe<P> dif = fe_carry<P>(fe_sub<P, 4>(a, b));                       // a - b + 4p
     const Fe<P> o = fe_add<P>(FeAsm<P>::mul(sum, half), FeAsm<P>::mul(dif, r));      // plain * Montgomery constant = plain
-    gstore<P>(out, i0 + t, fe_reduce<P>(o));                                 // .sanitize()
+    fe_gstore<P>(out, i0 + t, fe_reduce<P>(o));                                 // .sanitize()
     r = FeAsm<P>::mul(r, winv);
   }
 }
@@ -1262,7 +1218,7 @@ static FoldLaunch fold_launch(const HostField* hf, const FriFoldConsts& fc, size
   FoldLaunch fl;
   uint64_t winv[4], halfv[4];
   h_mulmod(hf, winv, fc.winv, fc.rmod); h_mulmod(hf, halfv, fc.half, fc.rmod);
-  to_words(winv, hf->nl, &fl.winvw); to_words(halfv, hf->nl, &fl.halfw);
+  h_words(winv, hf->nl, fl.winvw.w); h_words(halfv, hf->nl, fl.halfw.w);
   fl.per_lane = h >= ((size_t)1 << 20) ? GEN_CHUNK : (h >= ((size_t)1 << 16) ? 4 : 1);
   const size_t chunks = (h + (size_t)fl.per_lane - 1) / (size_t)fl.per_lane;
   fl.blocks = (unsigned)((chunks + 127) / 128);
@@ -1278,7 +1234,7 @@ int fri_fold_dev_consts(int fid, const void* d_cw, size_t n, const uint64_t* alp
   h_mulmod(hf, r0, r0, fc.oinv);
   h_mulmod(hf, r0, r0, fc.rmod);
   Words8 r0w;
-  to_words(r0, hf->nl, &r0w);
+  h_words(r0, hf->nl, r0w.w);
   const FoldLaunch fl = fold_launch(hf, fc, h);
   MZK_TRY(MZK_FIELD_LAUNCH(fid, k_fri_fold<P>, dim3(fl.blocks), dim3(128), 0, s, (const u32*)d_cw, h, r0w, fl.winvw, fl.halfw, (u32*)d_out, fl.per_lane));
   MZK_HIP(hipGetLastError());
@@ -1293,14 +1249,14 @@ __global__ void k_fri_fold_dev_alpha(const u32* __restrict__ cw, size_t h, const
   const size_t i0 = chunk * (size_t)per_lane;
   if (i0 >= h) return;
   const Fe<P> winv = fe_unpack<P>(winv_mont.w), half = fe_unpack<P>(half_mont.w);
-  const Fe<P> r0 = FeAsm<P>::mul(gload<P>(alpha, 0), fe_unpack<P>(k_mont.w));
+  const Fe<P> r0 = FeAsm<P>::mul(fe_gload<P>(alpha, 0), fe_unpack<P>(k_mont.w));
   Fe<P> r = FeAsm<P>::mul(r0, fe_pow_u64<P>(winv, i0));
   for (int t = 0; t < per_lane && i0 + t < h; t++) {
-    const Fe<P> a = gload<P>(cw, i0 + t), b = gload<P>(cw, h + i0 + t);
+    const Fe<P> a = fe_gload<P>(cw, i0 + t), b = fe_gload<P>(cw, h + i0 + t);
     const Fe<P> sum = fe_add<P>(a, b);
     const Fe<P> dif = fe_carry<P>(fe_sub<P, 4>(a, b));
     const Fe<P> o = fe_add<P>(FeAsm<P>::mul(sum, half), FeAsm<P>::mul(dif, r));
-    gstore<P>(out, i0 + t, fe_reduce<P>(o));
+    fe_gstore<P>(out, i0 + t, fe_reduce<P>(o));
     r = FeAsm<P>::mul(r, winv);
   }
 }
@@ -1313,7 +1269,7 @@ int fri_fold_dev_alpha(int fid, const void* d_cw, size_t n, const uint64_t* d_al
   h_mulmod(hf, kv, fc.half, fc.oinv);
   h_mulmod(hf, kv, kv, fc.rmod); h_mulmod(hf, kv, kv, fc.rmod);
   Words8 kw;
-  to_words(kv, hf->nl, &kw);
+  h_words(kv, hf->nl, kw.w);
   const FoldLaunch fl = fold_launch(hf, fc, h);
   MZK_TRY(MZK_FIELD_LAUNCH(fid, k_fri_fold_dev_alpha<P>, dim3(fl.blocks), dim3(128), 0, s, (const u32*)d_cw, h, (const u32*)d_alpha, kw, fl.winvw, fl.halfw, (u32*)d_out, fl.per_lane));
   MZK_HIP(hipGetLastError());
@@ -1356,7 +1312,7 @@ __global__ __launch_bounds__(128) void k_pointwise_div(const u32* __restrict__ a
   Fe<P> run = fe_one<P>();
   for (int j = 0; j < len; j++) {
     {
-      const Fe<P> y = gload<P>(b, i0 + j);                   // canonical
+      const Fe<P> y = fe_gload<P>(b, i0 + j);                   // canonical
       pre[j] = run;                                          // product of the earlier non-zero denominators (Montgomery)
       Fe<P> ym = fe_to_mont<P>(y);
       if (fe_is_zero_canon<P>(y)) ym = fe_one<P>();
@@ -1366,16 +1322,16 @@ __global__ __launch_bounds__(128) void k_pointwise_div(const u32* __restrict__ a
   Fe<P> inv = fe_inv<P>(run);
   for (int j = len - 1; j >= 0; j--) {
     {
-      const Fe<P> y = gload<P>(b, i0 + j);
+      const Fe<P> y = fe_gload<P>(b, i0 + j);
       const bool zero = fe_is_zero_canon<P>(y);
       const Fe<P> yinv = FeAsm<P>::mul(inv, pre[j]);             // Montgomery form of 1 / y_j
       Fe<P> ym = fe_to_mont<P>(y);
       if (zero) ym = fe_one<P>();
       inv = FeAsm<P>::mul(inv, ym);
       for (size_t r = 0; r < regs; r++) {
-        const Fe<P> x = gload<P>(a, r * a_stride + i0 + j);
+        const Fe<P> x = fe_gload<P>(a, r * a_stride + i0 + j);
         const Fe<P> q = fe_reduce<P>(FeAsm<P>::mul(x, yinv));       // plain * Montgomery = plain
-        gstore<P>(out, r * out_stride + i0 + j, zero ? fe_zero<P>() : q);
+        fe_gstore<P>(out, r * out_stride + i0 + j, zero ? fe_zero<P>() : q);
       }
     }
   }
@@ -1399,7 +1355,7 @@ int coset_divide_dev_impl(int fid, const void* d_lhs, size_t tl, const void* d_r
   uint64_t oinv[4];
   h_invmod(hf, oinv, offset_host);
   Words8 ow;
-  to_words(oinv, hf->nl, &ow);
+  h_words(oinv, hf->nl, ow.w);
   const size_t ql = tl - tr + 1;
   const size_t chunks = (ql + GEN_CHUNK - 1) / GEN_CHUNK;
   const unsigned sblocks = (unsigned)((chunks + 255) / 256);
@@ -1503,8 +1459,8 @@ int coset_divide_rows_dev_impl(int fid, const void* d_lhs, size_t lhs_stride, co
   Words8 fw, bw;
   uint64_t oinv[4];
   h_invmod(hf, oinv, offset_host);
-  to_words(offset_host, hf->nl, &fw);
-  to_words(oinv, hf->nl, &bw);
+  h_words(offset_host, hf->nl, fw.w);
+  h_words(oinv, hf->nl, bw.w);
   MZK_TRY(launch_scale_rows(fid, d_lhs, lhs_stride, ea, order, d_tab, nrows, fw, order, s));
   MZK_TRY(ntt_batch_dev_impl(fid, root_host, ea, ea, order, nrows, 0, s));
   MZK_TRY(coset_lde_dev_impl(fid, d_rhs, tr, offset_host, root_host, eb, order, s));
@@ -1524,8 +1480,8 @@ __global__ __launch_bounds__(256) void k_pointwise_mul_shared(const u32* __restr
                                                               size_t a_stride, size_t out_stride) {
   const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
-  const Fe<P> ym = fe_to_mont<P>(gload<P>(b, i));
-  for (size_t r = 0; r < regs; r++) gstore<P>(out, r * out_stride + i, fe_reduce<P>(FeAsm<P>::mul(gload<P>(a, r * a_stride + i), ym)));      // plain * Montgomery = plain
+  const Fe<P> ym = fe_to_mont<P>(fe_gload<P>(b, i));
+  for (size_t r = 0; r < regs; r++) fe_gstore<P>(out, r * out_stride + i, fe_reduce<P>(FeAsm<P>::mul(fe_gload<P>(a, r * a_stride + i), ym)));      // plain * Montgomery = plain
 }
 int pointwise_mul_shared_dev(int fid, const void* d_a, size_t a_stride, const void* d_b, void* d_out, size_t out_stride, size_t n, size_t regs, hipStream_t s) {
   if (n == 0 || regs == 0) return MZK_OK;

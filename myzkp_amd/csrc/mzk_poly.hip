@@ -25,26 +25,13 @@
 #include <algorithm>
 #include <vector>
 #include "mzk_common.h"
+#include "mzk_elem.h"
 #include "mzk_field_asm.h"
 
 namespace mzk {
 
 constexpr int CHUNK = 64;        // points per level-0 polynomial = one wave
 
-template <class P> __device__ __forceinline__ Fe<P> pl_load(const u32* __restrict__ g, size_t idx) {
-  u32 w[P::NW];
-  const uint4* p4 = reinterpret_cast<const uint4*>(g + idx * P::NW);
-#pragma unroll
-  for (int q = 0; q < P::NW / 4; q++) { uint4 v = p4[q]; w[4 * q] = v.x; w[4 * q + 1] = v.y; w[4 * q + 2] = v.z; w[4 * q + 3] = v.w; }
-  return fe_unpack<P>(w);
-}
-template <class P> __device__ __forceinline__ void pl_store(u32* __restrict__ g, size_t idx, const Fe<P>& v) {   // v canonical
-  u32 w[P::NW];
-  fe_pack<P>(v, w);
-  uint4* p4 = reinterpret_cast<uint4*>(g + idx * P::NW);
-#pragma unroll
-  for (int q = 0; q < P::NW / 4; q++) p4[q] = make_uint4(w[4 * q], w[4 * q + 1], w[4 * q + 2], w[4 * q + 3]);
-}
 // plain-domain helpers: canonical in, canonical out
 template <class P> __device__ __forceinline__ Fe<P> pl_mul(const Fe<P>& x, const Fe<P>& y) { return fe_reduce<P>(FeAsm<P>::mul(FeAsm<P>::mul(x, y), fe_r2<P>())); }
 template <class P> __device__ __forceinline__ Fe<P> pl_add(const Fe<P>& x, const Fe<P>& y) { return fe_reduce<P>(fe_carry<P>(fe_add<P>(x, y))); }
@@ -78,7 +65,7 @@ __global__ __launch_bounds__(64) void k_chunk_zerofier(const u32* __restrict__ d
   const size_t chunk = blockIdx.x;
   const size_t idx = chunk * CHUNK + lane;
   Fe<P> d = fe_zero<P>();
-  if (idx < n) d = fe_reduce<P>(fe_to_mont<P>(pl_load<P>(domain, idx)));     // Montgomery form: fe_mul(c, dM) = c d in the plain domain
+  if (idx < n) d = fe_reduce<P>(fe_to_mont<P>(fe_gload<P>(domain, idx)));     // Montgomery form: fe_mul(c, dM) = c d in the plain domain
   Fe<P> c = fe_zero<P>();
   if (lane == 0) c = pl_one<P>();
   for (int i = 0; i < CHUNK; i++) {
@@ -87,7 +74,7 @@ __global__ __launch_bounds__(64) void k_chunk_zerofier(const u32* __restrict__ d
     if (lane == 0) up = fe_zero<P>();
     c = pl_sub<P>(up, fe_reduce<P>(FeAsm<P>::mul(c, di)));
   }
-  pl_store<P>(low, idx, c);
+  fe_gstore<P>(low, idx, c);
 }
 
 // ---- level step kernels -------------------------------------------------------------------------------------
@@ -98,8 +85,8 @@ __global__ __launch_bounds__(256) void k_pad_double(const u32* __restrict__ src,
   if (e >= total2) return;
   const size_t p = e >> (lgD + 1), i = e & (((size_t)2 << lgD) - 1);
   Fe<P> v = fe_zero<P>();
-  if (i < ((size_t)1 << lgD)) v = pl_load<P>(src, (p << lgD) + i);
-  pl_store<P>(T, e, v);
+  if (i < ((size_t)1 << lgD)) v = fe_gload<P>(src, (p << lgD) + i);
+  fe_gstore<P>(T, e, v);
 }
 // U[q * 2D + k] = T[(2q) * 2D + k] * T[(2q + 1) * 2D + k]
 template <class P>
@@ -108,7 +95,7 @@ __global__ __launch_bounds__(256) void k_pair_mul(const u32* __restrict__ T, int
   if (e >= total) return;
   const size_t q = e >> (lgD + 1), k = e & (((size_t)2 << lgD) - 1);
   const size_t a = ((2 * q) << (lgD + 1)) + k;
-  pl_store<P>(U, e, pl_mul<P>(pl_load<P>(T, a), pl_load<P>(T, a + ((size_t)2 << lgD))));
+  fe_gstore<P>(U, e, pl_mul<P>(fe_gload<P>(T, a), fe_gload<P>(T, a + ((size_t)2 << lgD))));
 }
 // next[q * 2D + i] = U[q * 2D + i] + (i >= D ? cur[2q D + i - D] + cur[(2q + 1) D + i - D] : 0)
 template <class P>
@@ -117,12 +104,12 @@ __global__ __launch_bounds__(256) void k_monic_fixup(const u32* __restrict__ U, 
   if (e >= total) return;
   const size_t D = (size_t)1 << lgD;
   const size_t q = e >> (lgD + 1), i = e & (2 * D - 1);
-  Fe<P> v = pl_load<P>(U, e);
+  Fe<P> v = fe_gload<P>(U, e);
   if (i >= D) {
     const size_t a = ((2 * q) << lgD) + (i - D);
-    v = pl_add<P>(v, pl_add<P>(pl_load<P>(cur, a), pl_load<P>(cur, a + D)));
+    v = pl_add<P>(v, pl_add<P>(fe_gload<P>(cur, a), fe_gload<P>(cur, a + D)));
   }
-  pl_store<P>(next, e, v);
+  fe_gstore<P>(next, e, v);
 }
 
 // ---- power-series inverse of g = rev(Z_pad) (g[0] = 1, g[k] = Zpad[N - k]) ----------------------------------------
@@ -131,7 +118,7 @@ template <class P>
 __global__ __launch_bounds__(256) void k_reverse_monic(const u32* __restrict__ low_top, size_t N, u32* __restrict__ g) {
   const size_t k = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (k >= N) return;
-  pl_store<P>(g, k, k == 0 ? pl_one<P>() : pl_load<P>(low_top, N - k));
+  fe_gstore<P>(g, k, k == 0 ? pl_one<P>() : fe_gload<P>(low_top, N - k));
 }
 // inv[0 .. 64) of 1 / g, one wave: inv_k = - sum_{j=1..k} g_j inv_{k-j}; lane j holds g_j, the partial sums are
 // wave-reduced (64 steps)
@@ -139,45 +126,45 @@ template <class P>
 __global__ __launch_bounds__(64) void k_series_inverse_64(const u32* __restrict__ g, u32* __restrict__ inv) {
   __shared__ u32 sh[CHUNK * P::NW];
   const int lane = threadIdx.x;
-  const Fe<P> gj = pl_load<P>(g, lane);
-  if (lane == 0) pl_store<P>(sh, 0, pl_one<P>());
+  const Fe<P> gj = fe_gload<P>(g, lane);
+  if (lane == 0) fe_gstore<P>(sh, 0, pl_one<P>());
   __syncthreads();
   for (int k = 1; k < CHUNK; k++) {
     Fe<P> term = fe_zero<P>();
-    if (lane >= 1 && lane <= k) term = pl_mul<P>(gj, pl_load<P>(sh, k - lane));
+    if (lane >= 1 && lane <= k) term = pl_mul<P>(gj, fe_gload<P>(sh, k - lane));
     for (int m = 1; m < 64; m <<= 1) term = pl_add<P>(term, shfl_xor_fe<P>(term, m));
-    if (lane == 0) pl_store<P>(sh, k, fe_reduce<P>(fe_neg_canon<P>(term)));
+    if (lane == 0) fe_gstore<P>(sh, k, fe_reduce<P>(fe_neg_canon<P>(term)));
     __syncthreads();
   }
-  pl_store<P>(inv, lane, pl_load<P>(sh, lane));
+  fe_gstore<P>(inv, lane, fe_gload<P>(sh, lane));
 }
 // A[i] = i < m_in ? src[i] : 0 for i < 2m   (src may be longer than m_in)
 template <class P>
 __global__ __launch_bounds__(256) void k_copy_pad(const u32* __restrict__ src, size_t m_in, size_t total, u32* __restrict__ dst) {
   const size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (e >= total) return;
-  pl_store<P>(dst, e, e < m_in ? pl_load<P>(src, e) : fe_zero<P>());
+  fe_gstore<P>(dst, e, e < m_in ? fe_gload<P>(src, e) : fe_zero<P>());
 }
 // dst[i] = a[i] * b[i]
 template <class P>
 __global__ __launch_bounds__(256) void k_mul_vec(const u32* __restrict__ a, const u32* __restrict__ b, size_t total, u32* __restrict__ dst) {
   const size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (e >= total) return;
-  pl_store<P>(dst, e, pl_mul<P>(pl_load<P>(a, e), pl_load<P>(b, e)));
+  fe_gstore<P>(dst, e, pl_mul<P>(fe_gload<P>(a, e), fe_gload<P>(b, e)));
 }
 // dst[i] = i < m ? src[m + i] : 0 for i < 2m  (the error term e of g inv = 1 + X^m e)
 template <class P>
 __global__ __launch_bounds__(256) void k_upper_half_pad(const u32* __restrict__ src, size_t m, u32* __restrict__ dst) {
   const size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (e >= 2 * m) return;
-  pl_store<P>(dst, e, e < m ? pl_load<P>(src, m + e) : fe_zero<P>());
+  fe_gstore<P>(dst, e, e < m ? fe_gload<P>(src, m + e) : fe_zero<P>());
 }
 // inv[m + i] = - prod[i], i < m
 template <class P>
 __global__ __launch_bounds__(256) void k_newton_store(const u32* __restrict__ prod, size_t m, u32* __restrict__ inv) {
   const size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (e >= m) return;
-  pl_store<P>(inv, m + e, fe_reduce<P>(fe_neg_canon<P>(pl_load<P>(prod, e))));
+  fe_gstore<P>(inv, m + e, fe_reduce<P>(fe_neg_canon<P>(fe_gload<P>(prod, e))));
 }
 
 // ---- transposed evaluation ------------------------------------------------------------------------------------
@@ -190,18 +177,18 @@ __global__ __launch_bounds__(256) void k_eval_prepare(const u32* __restrict__ f,
   Fe<P> a = fe_zero<P>(), b = fe_zero<P>();
   if (e < N) {
     const size_t src = N - 1 - e;
-    if (src < m) a = pl_load<P>(f, src);
-    b = pl_load<P>(inv, e);
+    if (src < m) a = fe_gload<P>(f, src);
+    b = fe_gload<P>(inv, e);
   }
-  pl_store<P>(A, e, a);
-  pl_store<P>(B, e, b);
+  fe_gstore<P>(A, e, a);
+  fe_gstore<P>(B, e, b);
 }
 // t[i] = prod[N - 1 - i], i < N
 template <class P>
 __global__ __launch_bounds__(256) void k_reverse_low(const u32* __restrict__ prod, size_t N, u32* __restrict__ t) {
   const size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (e >= N) return;
-  pl_store<P>(t, e, pl_load<P>(prod, N - 1 - e));
+  fe_gstore<P>(t, e, fe_gload<P>(prod, N - 1 - e));
 }
 // down step, children of degree D: V[c * 2D + k] = That_node[(c >> 1) * 2D + k] * (Zhat[(c ^ 1) * 2D + k] + (-1)^k)
 template <class P>
@@ -209,10 +196,10 @@ __global__ __launch_bounds__(256) void k_down_mul(const u32* __restrict__ That, 
   const size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (e >= total2) return;
   const size_t c = e >> (lgD + 1), k = e & (((size_t)2 << lgD) - 1);
-  const Fe<P> t = pl_load<P>(That, ((c >> 1) << (lgD + 1)) + k);
-  Fe<P> z = pl_load<P>(Zhat, ((c ^ 1) << (lgD + 1)) + k);
+  const Fe<P> t = fe_gload<P>(That, ((c >> 1) << (lgD + 1)) + k);
+  Fe<P> z = fe_gload<P>(Zhat, ((c ^ 1) << (lgD + 1)) + k);
   z = (k & 1) ? pl_sub<P>(z, pl_one<P>()) : pl_add<P>(z, pl_one<P>());       // + NTT(X^D)[k] = w^(D k) = (-1)^k
-  pl_store<P>(V, e, pl_mul<P>(t, z));
+  fe_gstore<P>(V, e, pl_mul<P>(t, z));
 }
 // t_child[c * D + i] = V[c * 2D + D + i]
 template <class P>
@@ -220,7 +207,7 @@ __global__ __launch_bounds__(256) void k_take_upper(const u32* __restrict__ V, i
   const size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (e >= total) return;
   const size_t c = e >> lgD, i = e & (((size_t)1 << lgD) - 1);
-  pl_store<P>(t, e, pl_load<P>(V, (c << (lgD + 1)) + ((size_t)1 << lgD) + i));
+  fe_gstore<P>(t, e, fe_gload<P>(V, (c << (lgD + 1)) + ((size_t)1 << lgD) + i));
 }
 // 64-point finish: f(x_i) = sum_k t[k] q_k, q_0 = 1, q_k = g_k + x_i q_{k-1}, g_k = Zc[64 - k] (g_64 unused)
 template <class P>
@@ -229,18 +216,18 @@ __global__ __launch_bounds__(64) void k_chunk_eval(const u32* __restrict__ domai
   __shared__ u32 sh_t[CHUNK * P::NW], sh_z[CHUNK * P::NW];
   const int lane = threadIdx.x;
   const size_t idx = (size_t)blockIdx.x * CHUNK + lane;
-  pl_store<P>(sh_t, lane, pl_load<P>(t, idx));
-  pl_store<P>(sh_z, lane, pl_load<P>(low0, idx));
+  fe_gstore<P>(sh_t, lane, fe_gload<P>(t, idx));
+  fe_gstore<P>(sh_z, lane, fe_gload<P>(low0, idx));
   __syncthreads();
   Fe<P> x = fe_zero<P>();
-  if (idx < n) x = fe_reduce<P>(fe_to_mont<P>(pl_load<P>(domain, idx)));
+  if (idx < n) x = fe_reduce<P>(fe_to_mont<P>(fe_gload<P>(domain, idx)));
   Fe<P> q = pl_one<P>();
-  Fe<P> acc = pl_load<P>(sh_t, 0);
+  Fe<P> acc = fe_gload<P>(sh_t, 0);
   for (int k = 1; k < CHUNK; k++) {
-    q = pl_add<P>(pl_load<P>(sh_z, CHUNK - k), fe_reduce<P>(FeAsm<P>::mul(q, x)));
-    acc = pl_add<P>(acc, pl_mul<P>(pl_load<P>(sh_t, k), q));
+    q = pl_add<P>(fe_gload<P>(sh_z, CHUNK - k), fe_reduce<P>(FeAsm<P>::mul(q, x)));
+    acc = pl_add<P>(acc, pl_mul<P>(fe_gload<P>(sh_t, k), q));
   }
-  if (idx < out_n) pl_store<P>(out, idx, acc);
+  if (idx < out_n) fe_gstore<P>(out, idx, acc);
 }
 
 // ---- interpolation ------------------------------------------------------------------------------------------------
@@ -250,11 +237,11 @@ __global__ __launch_bounds__(256) void k_derivative(const u32* __restrict__ low_
   const size_t j = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (j >= n) return;
   const size_t src = j + 1 + pad;
-  const Fe<P> z = src < N ? pl_load<P>(low_top, src) : pl_one<P>();
+  const Fe<P> z = src < N ? fe_gload<P>(low_top, src) : pl_one<P>();
   Fe<P> m = fe_zero<P>();
   const u64 jj = (u64)j + 1;
   m.l[0] = (u32)(jj & MASK29); m.l[1] = (u32)((jj >> 29) & MASK29); m.l[2] = (u32)(jj >> 58);
-  pl_store<P>(dz, j, pl_mul<P>(z, m));
+  fe_gstore<P>(dz, j, pl_mul<P>(z, m));
 }
 // P_chunk = sum_i w_i Zc / (X - x_i): lane i divides synthetically (q_63 = 1, q_{k-1} = zc_k + x_i q_k), the scaled
 // coefficients are summed over the wave; out0[chunk * 64 + k] = coefficient k.
@@ -277,28 +264,28 @@ __global__ __launch_bounds__(64) void k_chunk_combine(const u32* __restrict__ do
   const size_t idx = ((size_t)blockIdx.x - reg * chunks) * CHUNK + lane;
   w += reg * chunks * CHUNK * P::NW;
   out0 += reg * chunks * CHUNK * P::NW;
-  pl_store<P>(sh_z, lane, pl_load<P>(low0, idx));
+  fe_gstore<P>(sh_z, lane, fe_gload<P>(low0, idx));
   __syncthreads();
   Fe<P> x = fe_zero<P>(), wi = fe_zero<P>();
-  if (idx < n) { x = fe_reduce<P>(fe_to_mont<P>(pl_load<P>(domain, idx))); wi = fe_reduce<P>(fe_to_mont<P>(pl_load<P>(w, idx))); }
+  if (idx < n) { x = fe_reduce<P>(fe_to_mont<P>(fe_gload<P>(domain, idx))); wi = fe_reduce<P>(fe_to_mont<P>(fe_gload<P>(w, idx))); }
   Fe<P> q = pl_one<P>();
   const int col = lane >> 3, sub = lane & 7;
   for (int kb = CHUNK - COMBINE_BLOCK; kb >= 0; kb -= COMBINE_BLOCK) {
 #pragma unroll 1
     for (int kk = COMBINE_BLOCK - 1; kk >= 0; kk--) {
       const int k = kb + kk;
-      pl_store<P>(sh_t, kk * CHUNK + lane, fe_reduce<P>(FeAsm<P>::mul(q, wi)));
-      if (k > 0) q = pl_add<P>(pl_load<P>(sh_z, k), fe_reduce<P>(FeAsm<P>::mul(q, x)));
+      fe_gstore<P>(sh_t, kk * CHUNK + lane, fe_reduce<P>(FeAsm<P>::mul(q, wi)));
+      if (k > 0) q = pl_add<P>(fe_gload<P>(sh_z, k), fe_reduce<P>(FeAsm<P>::mul(q, x)));
     }
     __syncthreads();
-    Fe<P> sum = pl_load<P>(sh_t, col * CHUNK + sub);
+    Fe<P> sum = fe_gload<P>(sh_t, col * CHUNK + sub);
 #pragma unroll 1
-    for (int j = 1; j < COMBINE_BLOCK; j++) sum = pl_add<P>(sum, pl_load<P>(sh_t, col * CHUNK + j * COMBINE_BLOCK + sub));
+    for (int j = 1; j < COMBINE_BLOCK; j++) sum = pl_add<P>(sum, fe_gload<P>(sh_t, col * CHUNK + j * COMBINE_BLOCK + sub));
     for (int m = 1; m < COMBINE_BLOCK; m <<= 1) sum = pl_add<P>(sum, shfl_xor_fe<P>(sum, m));
-    if (sub == 0) pl_store<P>(sh_o, kb + col, sum);
+    if (sub == 0) fe_gstore<P>(sh_o, kb + col, sum);
     __syncthreads();
   }
-  pl_store<P>(out0, idx, pl_load<P>(sh_o, lane));
+  fe_gstore<P>(out0, idx, fe_gload<P>(sh_o, lane));
 }
 // W[q * 2D + k] = Pl[k] Zr[k] + Pr[k] Zl[k]   (all transformed, children q*2, q*2+1 of degree D)
 template <class P>
@@ -309,7 +296,7 @@ __global__ __launch_bounds__(256) void k_up_mul(const u32* __restrict__ Phat, co
   if (e >= total) return;
   const size_t q = e >> (lgD + 1), k = e & (((size_t)2 << lgD) - 1);
   const size_t a = ((2 * q) << (lgD + 1)) + k, b = a + ((size_t)2 << lgD);
-  pl_store<P>(W, e, pl_add<P>(pl_mul<P>(pl_load<P>(Phat, a), pl_load<P>(Zhat, b & zmask)), pl_mul<P>(pl_load<P>(Phat, b), pl_load<P>(Zhat, a & zmask))));
+  fe_gstore<P>(W, e, pl_add<P>(pl_mul<P>(fe_gload<P>(Phat, a), fe_gload<P>(Zhat, b & zmask)), pl_mul<P>(fe_gload<P>(Phat, b), fe_gload<P>(Zhat, a & zmask))));
 }
 
 // ---- host orchestration ----------------------------------------------------------------------------------------
@@ -602,11 +589,11 @@ __global__ __launch_bounds__(256) void k_prefix_weights(const u32* __restrict__ 
   const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   const size_t j = blockIdx.y;
   if (i >= n) return;
-  const Fe<P> x = fe_reduce<P>(fe_to_mont<P>(pl_load<P>(domain, i)));       // Montgomery form: mul(acc, x) is the plain product
+  const Fe<P> x = fe_reduce<P>(fe_to_mont<P>(fe_gload<P>(domain, i)));       // Montgomery form: mul(acc, x) is the plain product
   Fe<P> acc = fe_zero<P>();
-  for (int t = m - 1; t >= 0; t--) acc = pl_add<P>(fe_reduce<P>(FeAsm<P>::mul(acc, x)), pl_load<P>(ainv, j * (size_t)m + t));
+  for (int t = m - 1; t >= 0; t--) acc = pl_add<P>(fe_reduce<P>(FeAsm<P>::mul(acc, x)), fe_gload<P>(ainv, j * (size_t)m + t));
   acc = fe_reduce<P>(fe_neg_canon<P>(fe_reduce<P>(FeAsm<P>::mul(acc, x))));
-  pl_store<P>(C, j * n + i, fe_reduce<P>(fe_to_mont<P>(acc)));
+  fe_gstore<P>(C, j * n + i, fe_reduce<P>(fe_to_mont<P>(acc)));
 }
 // ext[r * N + i] = i < n ? v[r * n + i] : 0, N = 2^lgN  (the m missing values are written by k_prefix_missing afterwards)
 template <class P>
@@ -614,7 +601,7 @@ __global__ __launch_bounds__(256) void k_prefix_pad(const u32* __restrict__ v, s
   const size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (e >= total) return;
   const size_t r = e >> lgN, i = e & (((size_t)1 << lgN) - 1);
-  pl_store<P>(ext, e, i < n ? pl_load<P>(v, r * n + i) : fe_zero<P>());
+  fe_gstore<P>(ext, e, i < n ? fe_gload<P>(v, r * n + i) : fe_zero<P>());
 }
 // ext[r * N + n + j] = sum_i v[r * n + i] C[j * n + i]: one workgroup per (missing point j = blockIdx.x, register r = blockIdx.y)
 constexpr int PREFIX_NT = 1024;
@@ -625,14 +612,14 @@ __global__ __launch_bounds__(PREFIX_NT) void k_prefix_missing(const u32* __restr
   const u32* row = v + r * n * P::NW;
   const u32* cj = C + j * n * P::NW;
   Fe<P> acc = fe_zero<P>();
-  for (size_t i = threadIdx.x; i < n; i += PREFIX_NT) acc = pl_add<P>(acc, fe_reduce<P>(FeAsm<P>::mul(pl_load<P>(row, i), pl_load<P>(cj, i))));
+  for (size_t i = threadIdx.x; i < n; i += PREFIX_NT) acc = pl_add<P>(acc, fe_reduce<P>(FeAsm<P>::mul(fe_gload<P>(row, i), fe_gload<P>(cj, i))));
   for (int k = 1; k < 64; k <<= 1) acc = pl_add<P>(acc, shfl_xor_fe<P>(acc, k));
-  if ((threadIdx.x & 63) == 0) pl_store<P>(sh, threadIdx.x >> 6, acc);
+  if ((threadIdx.x & 63) == 0) fe_gstore<P>(sh, threadIdx.x >> 6, acc);
   __syncthreads();
   if (threadIdx.x < 64) {
-    Fe<P> t = threadIdx.x < PREFIX_NT / 64 ? pl_load<P>(sh, threadIdx.x) : fe_zero<P>();
+    Fe<P> t = threadIdx.x < PREFIX_NT / 64 ? fe_gload<P>(sh, threadIdx.x) : fe_zero<P>();
     for (int k = 1; k < PREFIX_NT / 64; k <<= 1) t = pl_add<P>(t, shfl_xor_fe<P>(t, k));
-    if (threadIdx.x == 0) pl_store<P>(ext, r * N + n + j, t);
+    if (threadIdx.x == 0) fe_gstore<P>(ext, r * N + n + j, t);
   }
 }
 
@@ -683,11 +670,11 @@ template <class P>
 __global__ __launch_bounds__(256) void k_prefix_check(const u32* __restrict__ domain, size_t n, u32* __restrict__ flag) {
   const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
-  const Fe<P> g = fe_reduce<P>(fe_to_mont<P>(pl_load<P>(domain, 1)));
+  const Fe<P> g = fe_reduce<P>(fe_to_mont<P>(fe_gload<P>(domain, 1)));
   Fe<P> one = fe_zero<P>();
   one.l[0] = 1;
   const Fe<P> want = fe_reduce<P>(FeAsm<P>::mul(fe_reduce<P>(fe_pow_u64<P>(g, (u64)i)), one));      // g^i, plain and canonical
-  const Fe<P> have = pl_load<P>(domain, i);
+  const Fe<P> have = fe_gload<P>(domain, i);
   u32 diff = 0;
 #pragma unroll
   for (int k = 0; k < P::L; k++) diff |= want.l[k] ^ have.l[k];
@@ -747,8 +734,8 @@ __global__ __launch_bounds__(256) void k_prefix_zerofier(const u32* __restrict__
 #pragma unroll
   for (int c = 0; c < ZERO_CHUNK; c++) acc[c] = fe_zero<P>();
   for (int j = 0; j < m; j++) {
-    const Fe<P> w = fe_reduce<P>(fe_to_mont<P>(pl_load<P>(params, 2 * (size_t)j + 1)));         // Montgomery form: mul(t, w) is the plain product
-    Fe<P> t = fe_reduce<P>(FeAsm<P>::mul(pl_load<P>(params, 2 * (size_t)j), fe_reduce<P>(fe_pow_u64<P>(w, (u64)k0 + 1))));      // rho_j w_j^(k0+1), plain
+    const Fe<P> w = fe_reduce<P>(fe_to_mont<P>(fe_gload<P>(params, 2 * (size_t)j + 1)));         // Montgomery form: mul(t, w) is the plain product
+    Fe<P> t = fe_reduce<P>(FeAsm<P>::mul(fe_gload<P>(params, 2 * (size_t)j), fe_reduce<P>(fe_pow_u64<P>(w, (u64)k0 + 1))));      // rho_j w_j^(k0+1), plain
 #pragma unroll
     for (int c = 0; c < ZERO_CHUNK; c++) {
       acc[c] = pl_add<P>(acc[c], t);
@@ -756,7 +743,7 @@ __global__ __launch_bounds__(256) void k_prefix_zerofier(const u32* __restrict__
     }
   }
 #pragma unroll
-  for (int c = 0; c < ZERO_CHUNK; c++) if (k0 + c < count) pl_store<P>(out, k0 + c, acc[c]);
+  for (int c = 0; c < ZERO_CHUNK; c++) if (k0 + c < count) fe_gstore<P>(out, k0 + c, acc[c]);
 }
 // (rho_j, w_j) for j < m, canonical, interleaved; false if two missing points coincide (cannot happen in a subgroup)
 static bool prefix_zerofier_params(const HostField* hf, const uint64_t* g, size_t n, size_t N, std::vector<uint64_t>* out) {

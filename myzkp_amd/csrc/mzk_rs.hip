@@ -369,7 +369,6 @@ static int rs_plan_checked(size_t n, size_t k, size_t batch, RsPlan* P) {
   if (P->err != MZK_OK) { set_error("%s", P->msg); return P->err; }
   return MZK_OK;
 }
-static int ilog2(int w) { int lg = 0; while ((1 << lg) < w) lg++; return lg; }
 
 template <int PW>
 static void rs_launch_lane(const RsPlan& P, const RsEntry* e, RsView m, RsView o, size_t batch, hipStream_t s) {
@@ -410,7 +409,7 @@ static int rs_syndromes_views(size_t n, size_t k, RsView in, size_t batch, uint8
   if (P.d == 0) return MZK_OK;
   RsEntry* e;
   MZK_TRY(rs_get_entry(P, s, &e));
-  hipLaunchKernelGGL(k_rs_syndromes, dim3(P.syn.grid), dim3(P.syn.block), 0, s, in.p, in.sym, in.cw, d_syndromes, rs_dev_pts(e), P.n, P.d, ilog2(P.dec_w), batch, P.syn.iters);
+  hipLaunchKernelGGL(k_rs_syndromes, dim3(P.syn.grid), dim3(P.syn.block), 0, s, in.p, in.sym, in.cw, d_syndromes, rs_dev_pts(e), P.n, P.d, (int)ilog2((size_t)P.dec_w), batch, P.syn.iters);
   MZK_HIP(hipGetLastError());
   return MZK_OK;
 }
@@ -422,7 +421,7 @@ static int rs_decode_views(size_t n, size_t k, RsView in, size_t batch, RsView c
   RsEntry* e;
   MZK_TRY(rs_get_entry(P, s, &e));
   hipLaunchKernelGGL(k_rs_decode, dim3(P.dec.grid), dim3(P.dec.block), P.dec.lds, s, in.p, in.sym, in.cw, corr.p, corr.sym, corr.cw, msgs.p, msgs.sym, msgs.cw, d_status,
-                     rs_dev_pts(e), rs_dev_inv(e), P.n, P.d, ilog2(P.dec_w), P.dec_npad, P.dec_dpad, batch, P.dec.iters);
+                     rs_dev_pts(e), rs_dev_inv(e), P.n, P.d, (int)ilog2((size_t)P.dec_w), P.dec_npad, P.dec_dpad, batch, P.dec.iters);
   MZK_HIP(hipGetLastError());
   return MZK_OK;
 }

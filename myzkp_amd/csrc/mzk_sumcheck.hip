@@ -23,6 +23,7 @@
 //   k_mle_pass        the subset-sum butterfly, up to MLE_TILE_LOG index bits per pass in LDS.
 #include <utility>
 #include "mzk_common.h"
+#include "mzk_elem.h"
 #include "mzk_keccak_pair.h"
 #include "mzk_sumcheck_tx.h"
 
@@ -30,22 +31,7 @@ namespace mzk {
 
 typedef FrParams SP;
 typedef Fe<SP> SE;
-struct ScW8 { u32 w[8]; };
 
-__device__ __forceinline__ SE sc_load(const u32* __restrict__ g, size_t i) {
-  const uint4* p = reinterpret_cast<const uint4*>(g + 8 * i);
-  const uint4 a = p[0], b = p[1];
-  const u32 w[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
-  return fe_unpack<SP>(w);
-}
-// v canonical
-__device__ __forceinline__ void sc_store(u32* __restrict__ g, size_t i, const SE& v) {
-  u32 w[8];
-  fe_pack<SP>(v, w);
-  uint4* p = reinterpret_cast<uint4*>(g + 8 * i);
-  p[0] = make_uint4(w[0], w[1], w[2], w[3]);
-  p[1] = make_uint4(w[4], w[5], w[6], w[7]);
-}
 // a + r (b - a), canonical; a, b canonical, r_mont = r R normalised
 __device__ __forceinline__ SE sc_fold1(const SE& a, const SE& b, const SE& r_mont) {
   return fe_reduce<SP>(fe_add<SP>(a, fe_mul<SP>(fe_sub_carry<SP, 2>(b, a), r_mont)));
@@ -107,14 +93,14 @@ __global__ __launch_bounds__(SC_THREADS) void k_sc_round(const u32* __restrict__
       const u32* t = src + 8 * (size_t)f * src_stride;
       SE a, b;
       if (chal) {
-        a = sc_fold1(sc_load(t, i), sc_load(t, i + 2 * h), rm);
-        b = sc_fold1(sc_load(t, i + h), sc_load(t, i + 3 * h), rm);
+        a = sc_fold1(fe_gload<SP>(t, i), fe_gload<SP>(t, i + 2 * h), rm);
+        b = sc_fold1(fe_gload<SP>(t, i + h), fe_gload<SP>(t, i + 3 * h), rm);
         u32* o = dst + 8 * (size_t)f * 2 * h;
-        sc_store(o, i, a);
-        sc_store(o, i + h, b);
+        fe_gstore<SP>(o, i, a);
+        fe_gstore<SP>(o, i + h, b);
       } else {
-        a = sc_load(t, i);
-        b = sc_load(t, i + h);
+        a = fe_gload<SP>(t, i);
+        b = fe_gload<SP>(t, i + h);
       }
       pt[f] = a;
       df[f] = fe_sub_carry<SP, 2>(b, a);          // b - a + 2 p: the c-points are a, a + df, a + 2 df, ... by repeated addition
@@ -156,7 +142,7 @@ __global__ __launch_bounds__(SC_THREADS) void k_sc_round(const u32* __restrict__
       for (int q = 0; q < SP::L; q++) o.l[q] = S[w][tid][q];
       v = sc_add(v, o);
     }
-    sc_store(partials, (size_t)blockIdx.x * (D + 1) + tid, fe_reduce<SP>(v));
+    fe_gstore<SP>(partials, (size_t)blockIdx.x * (D + 1) + tid, fe_reduce<SP>(v));
   }
 }
 
@@ -166,7 +152,7 @@ struct ScProof {
   u64 off[mzk_tx::SCP_COUNT];
   u64 header_objects, pos0;      // objects of the caller's header; stream bytes before round 0 (8 + header_len)
   int el, D;
-  ScW8 rk;                       // R^k mod p, standard form: sum / R^(k-1) times it, Montgomery-reduced, is the sum
+  Words8 rk;                     // R^k mod p, standard form: sum / R^(k-1) times it, Montgomery-reduced, is the sum
 };
 // Every thread of the workgroup calls.  sw: the d + 1 canonical values of round j (LDS, 8 words each); pos: stream bytes so far.
 // Writes s_j to EVALS (and C = s_0(0) + s_0(1) to SUM), appends the d + 1 objects, sets the object count, hashes the stream and
@@ -212,7 +198,7 @@ __global__ __launch_bounds__(SC_END_THREADS) void k_sc_round_end(const u32* __re
   const int D = P.D;
   for (int c = 0; c <= D; c++) {
     SE acc = fe_zero<SP>();
-    for (int p = tid; p < nparts; p += SC_END_THREADS) acc = sc_add(acc, sc_load(partials, (size_t)p * (D + 1) + c));
+    for (int p = tid; p < nparts; p += SC_END_THREADS) acc = sc_add(acc, fe_gload<SP>(partials, (size_t)p * (D + 1) + c));
     acc = sc_wave_sum(acc);
     if (lane == 0) {
 #pragma unroll
@@ -258,7 +244,7 @@ __global__ __launch_bounds__(64) void k_sc_tail(const u32* __restrict__ src, siz
     for (int f = 0; f < K; f++) {
       const u32* t = src + 8 * (size_t)f * src_stride;
       for (int i = tid; i < m; i += 64) {
-        const SE v = fold ? sc_fold1(sc_load(t, i), sc_load(t, (size_t)i + m), rm) : sc_load(t, i);
+        const SE v = fold ? sc_fold1(fe_gload<SP>(t, i), fe_gload<SP>(t, (size_t)i + m), rm) : fe_gload<SP>(t, i);
         fe_pack<SP>(v, T[f][i]);
       }
     }
@@ -368,7 +354,7 @@ static int scp_prove_impl(const void* tables, bool on_device, size_t el, size_t 
     h_rmod(fr, rmod);
     memcpy(rk, rmod, 32);
     for (size_t q = 1; q < k; q++) { uint64_t t[4]; h_mulmod(fr, t, rk, rmod); memcpy(rk, t, 32); }
-    for (int i = 0; i < 4; i++) { P.rk.w[2 * i] = (u32)rk[i]; P.rk.w[2 * i + 1] = (u32)(rk[i] >> 32); }
+    h_words(rk, 4, P.rk.w);
   }
   if (header_len) MZK_HIP(hipMemcpyAsync(P.base + L.off[mzk_tx::SCP_TRANSCRIPT] + 8, header, header_len, hipMemcpyHostToDevice, s));
   u32* partials = (u32*)(blk + o_part);
@@ -418,9 +404,7 @@ __global__ __launch_bounds__(MLE_THREADS) void k_mle_pass(const u32* in, u32* ou
   const size_t base = (t_high << (lo + g)) | (t_low << cb);
   for (int e = tid; e < elems; e += MLE_THREADS) {
     const size_t idx = base | ((size_t)(e >> cb) << lo) | (size_t)(e & ((1 << cb) - 1));
-    const uint4* p = reinterpret_cast<const uint4*>(in + 8 * idx);
-    const uint4 a = p[0], b = p[1];
-    X[e][0] = a.x; X[e][1] = a.y; X[e][2] = a.z; X[e][3] = a.w; X[e][4] = b.x; X[e][5] = b.y; X[e][6] = b.z; X[e][7] = b.w;
+    gload_words<8>(in, idx, X[e]);
   }
   for (int st = 0; st < g; st++) {
     __syncthreads();

@@ -75,6 +75,20 @@ def test_host_parameter_arithmetic_without_a_gpu(mz):
                 e = rnd.getrandbits(64)
                 assert op(fid, 2, a, e) == pow(a, e, p)
 
+    # op 4 = h_mont_words: a * R mod p with R = 2^(29 L), L the device's 29-bit limbs, as the eight words of a kernel argument
+    # (four uint64 whatever the field; b may be null)
+    rnd4 = random.Random(45)
+    for fid, limbs29 in ((mz.FIELD_FR, 9), (mz.FIELD_FQ, 9), (mz.FIELD_M128, 5)):
+        p = mz.MODULUS[fid]
+        nl = 2 if fid == mz.FIELD_M128 else 4
+        for a in [0, 1, 2, p - 1, p - 2, (1 << 64) - 1, 1 << 64] + [rnd4.randrange(p) for _ in range(30)]:
+            out = np.full(4, 0xdeadbeefdeadbeef, dtype=np.uint64)
+            assert L.mzk_host_field_op(fid, 4, orc.ptr(orc.to_limbs([a], nl)), None, orc.ptr(out)) == 0
+            words = [(int(out[i // 2]) >> (32 * (i & 1))) & 0xffffffff for i in range(8)]
+            assert sum(w << (32 * i) for i, w in enumerate(words)) == a * (1 << (29 * limbs29)) % p, (fid, a)
+            if fid == mz.FIELD_M128:
+                assert words[4:] == [0, 0, 0, 0], (a, words)
+
 
 def test_shipped_library_reads_no_environment_variable():
     """a caller's environment must not be able to change the code path.  The shipped .so does not import

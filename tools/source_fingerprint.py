@@ -13,9 +13,9 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "myzkp_amd", "csrc")
 FAMILIES = {
     # what the accumulate / sort kernels of the MSM are compiled from
-    "msm": ["mzk_msm.hip", "mzk_ec.h", "mzk_field.h", "mzk_field_asm.h", "mzk_coop.h", "mzk_glv.h", "mzk_common.h"],
+    "msm": ["mzk_msm.hip", "mzk_ec.h", "mzk_field.h", "mzk_field_asm.h", "mzk_coop.h", "mzk_glv.h", "mzk_common.h", "mzk_elem.h"],
     # the transform passes
-    "ntt": ["mzk_ntt.hip", "mzk_field.h", "mzk_field_asm.h", "mzk_common.h"],
+    "ntt": ["mzk_ntt.hip", "mzk_field.h", "mzk_field_asm.h", "mzk_common.h", "mzk_elem.h"],
 }
 
 
