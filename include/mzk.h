@@ -941,6 +941,64 @@ int mzk_rs2d_decode(size_t col_n, size_t row_n, const uint8_t* code, size_t mess
 int mzk_rs2d_decode_dev(size_t col_n, size_t row_n, const void* d_code, size_t message_len, void* d_data, int* d_ok, void* d_col_status, void* d_row_status,
                         void* stream);
 
+/* ---- Celestia's commitment (das/celestia.rs:73-169 over algebra/merkle.rs) ---------------------------------------------- */
+/* Row roots, column roots and the data root of a batch of byte squares in one call, and a handle that keeps every node and serves
+ * sample proofs as gathers.  A square is rows x cols symbols; symbol (r, c) of square q is at
+ *     base + q * square_stride + r * row_stride + c
+ * which is what mzk_rs2d_encode_dev writes, with rows = col_n, cols = row_n (dense: row_stride = cols, square_stride = rows * cols).
+ *   Trees: a leaf is one symbol, one byte, not hashed itself; Merkle::commit splits a slice at mid = len / 2 and hashes
+ *   SHA3-256(left || right); a one-leaf slice commits to the leaf.  row_roots[r] = commit of row r (cols leaves), col_roots[c] =
+ *   commit of column c (rows leaves), data_root = commit of the rows + cols roots, rows first, as 32-byte leaves.
+ *   Admitted: 2 <= rows, cols <= 255; row_stride >= cols; square_stride >= (rows - 1) * row_stride + cols when squares > 1;
+ *   1 <= squares, squares * (rows + cols) <= 2^31.  Anything else: MZK_E_ARG, the text names the parameter, nothing is enqueued.
+ *   Outputs per square: rows x 32, cols x 32 and 32 bytes, dense, square-major.
+ * Host forms take host pointers and dense squares and return MZK_E_NOGPU without a device; the _dev forms take device pointers and
+ * only enqueue. */
+enum { MZK_DAS_PATH_MAX = 8 };      /* floor(log2 255) + 1: the most entries of a path */
+/* What the calls below launch for (rows, cols, squares): host only, works without a GPU.  plan: MZK_DAS_PLAN_WORDS values, indexed by
+ * the constants below (the form of mzk_stark_proof_layout's sections).  *_ITEMS / *_DEPTH: M = 2^D bottom subtrees of one or two leaves
+ * and D = floor(log2 n) levels above them, of a row tree (cols leaves), a column tree (rows leaves) and the data-root tree (rows + cols
+ * leaves).  The tree launch takes ROW_WGS + COL_WGS workgroups' worth of work (*_TREES_PER_WG trees each) with TREE_GRID workgroups in
+ * TREE_ITERS rounds; the data-root launch one workgroup per square.  NODE_BYTES: what a handle keeps in device memory (every item
+ * and node of every row and column tree, the roots, a copy of the symbols). */
+enum { MZK_DAS_PLAN_ROWS = 0, MZK_DAS_PLAN_COLS = 1, MZK_DAS_PLAN_SQUARES = 2,
+       MZK_DAS_PLAN_ROW_ITEMS = 3, MZK_DAS_PLAN_ROW_DEPTH = 4, MZK_DAS_PLAN_COL_ITEMS = 5, MZK_DAS_PLAN_COL_DEPTH = 6,
+       MZK_DAS_PLAN_ROOT_ITEMS = 7, MZK_DAS_PLAN_ROOT_DEPTH = 8,
+       MZK_DAS_PLAN_ROW_TREES_PER_WG = 9, MZK_DAS_PLAN_COL_TREES_PER_WG = 10, MZK_DAS_PLAN_ROW_WGS = 11, MZK_DAS_PLAN_COL_WGS = 12,
+       MZK_DAS_PLAN_TREE_GRID = 13, MZK_DAS_PLAN_TREE_ITERS = 14, MZK_DAS_PLAN_TREE_BLOCK = 15, MZK_DAS_PLAN_TREE_LDS = 16,
+       MZK_DAS_PLAN_ROOT_GRID = 17, MZK_DAS_PLAN_ROOT_ITERS = 18, MZK_DAS_PLAN_ROOT_BLOCK = 19, MZK_DAS_PLAN_ROOT_LDS = 20,
+       MZK_DAS_PLAN_NODE_BYTES = 21, MZK_DAS_PLAN_PATH_MAX = 22, MZK_DAS_PLAN_WORDS = 23 };
+int mzk_das_plan_get(size_t rows, size_t cols, size_t squares, uint64_t* plan);
+/* Celestia::commit (:73-113) of `squares` squares: two launches, no host step.  d_row_roots / d_col_roots may be NULL when only the
+ * data roots are wanted (they are then scratch of the workspace).  The three outputs must be 16-byte aligned (MZK_E_ARG otherwise); the
+ * input needs no alignment. */
+int mzk_das_commit_dev(const void* d_code, size_t rows, size_t cols, size_t row_stride, size_t square_stride, size_t squares, void* d_row_roots,
+                       void* d_col_roots, void* d_data_roots, void* stream);
+int mzk_das_commit(const uint8_t* code, size_t rows, size_t cols, size_t squares, uint8_t* row_roots, uint8_t* col_roots, uint8_t* data_roots);
+/* The same hashing with every item and node level of every row and column tree kept in device memory, plus a copy of the symbols.
+ * The handle belongs to the context that built it, as a mzk_merkle does: later calls enter that context and run behind the build. */
+typedef struct mzk_das_grid mzk_das_grid;
+int mzk_das_grid_build_dev(const void* d_code, size_t rows, size_t cols, size_t row_stride, size_t square_stride, size_t squares, mzk_das_grid** out,
+                           void* stream);
+int mzk_das_grid_build(const uint8_t* code, size_t rows, size_t cols, size_t squares, mzk_das_grid** out);
+/* host outputs, any of them may be NULL */
+int mzk_das_grid_roots(const mzk_das_grid* grid, uint8_t* row_roots, uint8_t* col_roots, uint8_t* data_roots);
+/* Merkle::open as Celestia::verify calls it (:124-135), `count` samples in one gather launch.  positions: count x 4 uint64_t
+ * (square, row, col, is_row), SamplePosition plus the square: is_row = 1 opens index col of row `row`'s tree, is_row = 0 index row of
+ * column `col`'s tree.  For sample s: entry k at paths[(s * 8 + k) * 32 ..], zero-filled behind its length; its length (1 or 32) in
+ * entry_lens[s * 8 + k] (0 from depths[s] on); depths[s] = the number of entries; leaves[s] = the opened symbol.  Entry 0 is the
+ * sibling leaf, higher entries the sibling subtree's commitment: 1 byte where that is a one-leaf item, else 32.
+ * depths[s] = 0 is the reference's non-termination (a leaf that is the one-leaf half of a three-leaf slice): nothing else of that
+ * sample is meaningful and the call still returns MZK_OK, as the status byte of mzk_rs_decode.
+ * A position out of range (or is_row > 1): MZK_E_ARG for the whole call in the host form; the _dev form (device pointers, only
+ * enqueues on `stream` behind the build; d_paths 16-byte aligned, d_positions 8-byte aligned) writes depths[s] = 255 and nothing else of
+ * that sample. */
+int mzk_das_grid_open(const mzk_das_grid* grid, const uint64_t* positions, size_t count, uint8_t* paths, uint8_t* entry_lens, uint8_t* depths,
+                      uint8_t* leaves);
+int mzk_das_grid_open_dev(const mzk_das_grid* grid, const void* d_positions, size_t count, void* d_paths, void* d_entry_lens, void* d_depths,
+                          void* d_leaves, void* stream);
+void mzk_das_grid_free(mzk_das_grid* grid);
+
 /* Deterministic synthetic inputs (bench + tests): bit-identical to the oracle's orc_synth_*. */
 int mzk_synth_field_dev(int field_id, uint64_t seed, size_t n, void* d_out, void* stream);
 int mzk_synth_g1_points_dev(uint64_t seed, size_t n, void* d_out_xy, void* stream);

@@ -1549,3 +1549,100 @@ def rs2d_decode_dev(col_n, row_n, d_code, message_len, d_data, d_ok, d_col_statu
     opt = lambda p: ctypes.c_void_p(int(p)) if p else None
     _check(lib().mzk_rs2d_decode_dev(_sz(col_n), _sz(row_n), ctypes.c_void_p(int(d_code)), _sz(message_len), ctypes.c_void_p(int(d_data)),
                                      ctypes.c_void_p(int(d_ok)), opt(d_col_status), opt(d_row_status), ctypes.c_void_p(stream)))
+
+
+# ---- Celestia's commitment (das/celestia.rs over algebra/merkle.rs): squares are numpy uint8, roots 32 bytes ---------------------------
+DAS_PATH_MAX = 8           # entries a path can have: floor(log2 255) + 1
+DAS_OUT_OF_RANGE = 255     # depths[s] of a position outside the grid (open_dev)
+
+
+DAS_PLAN_FIELDS = ("rows", "cols", "squares", "row_items", "row_depth", "col_items", "col_depth", "root_items", "root_depth", "row_trees_per_wg", "col_trees_per_wg",
+                   "row_wgs", "col_wgs", "tree_grid", "tree_iters", "tree_block", "tree_lds", "root_grid", "root_iters", "root_block", "root_lds", "node_bytes", "path_max")
+
+
+def das_plan(rows, cols, squares=1):
+    """What the commitment of `squares` squares of rows x cols symbols launches, as a dict keyed after the MZK_DAS_PLAN_* constants
+    (mzk_das_plan_get).  Host only: no GPU needed."""
+    p = np.zeros(len(DAS_PLAN_FIELDS), dtype=np.uint64)
+    _check(lib().mzk_das_plan_get(_sz(rows), _sz(cols), _sz(squares), _p(p)))
+    return {n: int(v) for n, v in zip(DAS_PLAN_FIELDS, p)}
+
+
+def _squares3d(code, what):
+    a = np.ascontiguousarray(code, dtype=np.uint8)
+    if a.ndim == 2:
+        a = a.reshape((1,) + a.shape)
+    if a.ndim != 3:
+        raise MzkError(-5, "%s: expected squares x rows x cols bytes, got shape %s" % (what, a.shape))
+    return a
+
+
+def das_commit(code):
+    """Celestia::commit (das/celestia.rs:73-113) of every square of `code` (squares x rows x cols bytes, or one rows x cols square):
+    (row_roots squares x rows x 32, col_roots squares x cols x 32, data_roots squares x 32)."""
+    a = _squares3d(code, "das_commit")
+    q, r, c = a.shape
+    rr, cr, dr = np.empty((q, r, 32), dtype=np.uint8), np.empty((q, c, 32), dtype=np.uint8), np.empty((q, 32), dtype=np.uint8)
+    _check(lib().mzk_das_commit(_p(a), _sz(r), _sz(c), _sz(q), _p(rr), _p(cr), _p(dr)))
+    return rr, cr, dr
+
+
+def das_commit_dev(d_code, rows, cols, row_stride, square_stride, squares, d_row_roots, d_col_roots, d_data_roots, stream=None):
+    """mzk_das_commit_dev: device pointers (ints); d_row_roots / d_col_roots may be None.  Only enqueues."""
+    opt = lambda p: ctypes.c_void_p(int(p)) if p else None
+    _check(lib().mzk_das_commit_dev(ctypes.c_void_p(int(d_code)), _sz(rows), _sz(cols), _sz(row_stride), _sz(square_stride), _sz(squares), opt(d_row_roots),
+                                    opt(d_col_roots), ctypes.c_void_p(int(d_data_roots)), ctypes.c_void_p(stream)))
+
+
+class DasGrid:
+    """mzk_das_grid: the row and column trees of a batch of squares kept on the device.  DasGrid(code) builds from host bytes;
+    DasGrid.from_device(...) from a view in device memory on a caller stream (only enqueues)."""
+
+    def __init__(self, code=None, _handle=None, _shape=None):
+        if _handle is not None:
+            self._h, self.shape = _handle, _shape
+            return
+        a = _squares3d(code, "DasGrid")
+        h = ctypes.c_void_p()
+        _check(lib().mzk_das_grid_build(_p(a), _sz(a.shape[1]), _sz(a.shape[2]), _sz(a.shape[0]), ctypes.byref(h)))
+        self._h, self.shape = h, a.shape
+
+    @classmethod
+    def from_device(cls, d_code, rows, cols, row_stride, square_stride, squares, stream=None):
+        h = ctypes.c_void_p()
+        _check(lib().mzk_das_grid_build_dev(ctypes.c_void_p(int(d_code)), _sz(rows), _sz(cols), _sz(row_stride), _sz(square_stride), _sz(squares), ctypes.byref(h),
+                                            ctypes.c_void_p(stream)))
+        return cls(_handle=h, _shape=(int(squares), int(rows), int(cols)))
+
+    def roots(self):
+        """(row_roots, col_roots, data_roots) as das_commit returns them"""
+        q, r, c = self.shape
+        rr, cr, dr = np.empty((q, r, 32), dtype=np.uint8), np.empty((q, c, 32), dtype=np.uint8), np.empty((q, 32), dtype=np.uint8)
+        _check(lib().mzk_das_grid_roots(self._h, _p(rr), _p(cr), _p(dr)))
+        return rr, cr, dr
+
+    def open(self, positions):
+        """Merkle::open of every (square, row, col, is_row) of `positions` (count x 4): (paths count x 8 x 32, entry_lens count x 8,
+        depths count, leaves count).  depths[s] = 0: the reference does not terminate on that sample."""
+        pos = np.ascontiguousarray(positions, dtype=np.uint64).reshape(-1, 4)
+        n = pos.shape[0]
+        paths, lens = np.zeros((n, DAS_PATH_MAX, 32), dtype=np.uint8), np.zeros((n, DAS_PATH_MAX), dtype=np.uint8)
+        depths, leaves = np.zeros(n, dtype=np.uint8), np.zeros(n, dtype=np.uint8)
+        _check(lib().mzk_das_grid_open(self._h, _p(pos), _sz(n), _p(paths), _p(lens), _p(depths), _p(leaves)))
+        return paths, lens, depths, leaves
+
+    def open_dev(self, d_positions, count, d_paths, d_entry_lens, d_depths, d_leaves, stream=None):
+        """mzk_das_grid_open_dev: device pointers (ints).  Only enqueues, behind the build."""
+        _check(lib().mzk_das_grid_open_dev(self._h, ctypes.c_void_p(int(d_positions)), _sz(count), ctypes.c_void_p(int(d_paths)), ctypes.c_void_p(int(d_entry_lens)),
+                                           ctypes.c_void_p(int(d_depths)), ctypes.c_void_p(int(d_leaves)), ctypes.c_void_p(stream)))
+
+    def close(self):
+        if self._h:
+            lib().mzk_das_grid_free(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass

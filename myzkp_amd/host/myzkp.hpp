@@ -39,6 +39,7 @@
 #include <type_traits>
 #include <utility>
 #include <map>
+#include <memory>
 #include <optional>
 #include <vector>
 #include <exception>
@@ -605,7 +606,69 @@ inline std::vector<G2Point> setup_kzg_powers_2_with_alpha(const G2Point& g2, con
 // ---- Merkle (algebra/merkle.rs) and the FRI commit phase (zkstark/fri.rs:144-209) ------------------------
 typedef std::vector<uint8_t> MerkleRoot;               // merkle.rs:4
 typedef std::vector<std::vector<uint8_t>> MerklePath;  // merkle.rs:5
+// SHA3-256 (FIPS 202) on the host, portable and byte-order independent: what Merkle::hash and Merkle::verify run on.  Verification stays
+// on the host by design: a verifier hashes a handful of nodes.
+inline std::array<uint8_t, 32> sha3_256(const uint8_t* data, size_t len) {
+  static const uint64_t RC[24] = {
+      0x0000000000000001ULL, 0x0000000000008082ULL, 0x800000000000808aULL, 0x8000000080008000ULL, 0x000000000000808bULL, 0x0000000080000001ULL,
+      0x8000000080008081ULL, 0x8000000000008009ULL, 0x000000000000008aULL, 0x0000000000000088ULL, 0x0000000080008009ULL, 0x000000008000000aULL,
+      0x000000008000808bULL, 0x800000000000008bULL, 0x8000000000008089ULL, 0x8000000000008003ULL, 0x8000000000008002ULL, 0x8000000000000080ULL,
+      0x000000000000800aULL, 0x800000008000000aULL, 0x8000000080008081ULL, 0x8000000000008080ULL, 0x0000000080000001ULL, 0x8000000080008008ULL};
+  static const int ROT[25] = {0, 1, 62, 28, 27, 36, 44, 6, 55, 20, 3, 10, 43, 25, 39, 41, 45, 15, 21, 8, 18, 2, 61, 56, 14};      // lane x + 5y
+  constexpr size_t RATE = 136;
+  uint64_t a[25] = {0};
+  const auto permute = [&]() {
+    for (int rnd = 0; rnd < 24; rnd++) {
+      uint64_t c[5], b[25];
+      for (int x = 0; x < 5; x++) c[x] = a[x] ^ a[x + 5] ^ a[x + 10] ^ a[x + 15] ^ a[x + 20];
+      for (int x = 0; x < 5; x++) {
+        const uint64_t r = c[(x + 1) % 5], d = c[(x + 4) % 5] ^ ((r << 1) | (r >> 63));
+        for (int y = 0; y < 25; y += 5) a[x + y] ^= d;
+      }
+      for (int x = 0; x < 5; x++)
+        for (int y = 0; y < 5; y++) {
+          const uint64_t v = a[x + 5 * y];
+          const int s = ROT[x + 5 * y];
+          b[y + 5 * ((2 * x + 3 * y) % 5)] = s ? (v << s) | (v >> (64 - s)) : v;
+        }
+      for (int y = 0; y < 25; y += 5)
+        for (int x = 0; x < 5; x++) a[x + y] = b[x + y] ^ (~b[(x + 1) % 5 + y] & b[(x + 2) % 5 + y]);
+      a[0] ^= RC[rnd];
+    }
+  };
+  const auto absorb = [&](size_t pos, uint8_t byte) { a[pos / 8] ^= (uint64_t)byte << (8 * (pos % 8)); };
+  size_t pos = 0;
+  for (size_t i = 0; i < len; i++) {
+    absorb(pos, data[i]);
+    if (++pos == RATE) { permute(); pos = 0; }
+  }
+  absorb(pos, 0x06);
+  absorb(RATE - 1, 0x80);
+  permute();
+  std::array<uint8_t, 32> out;
+  for (size_t i = 0; i < 32; i++) out[i] = (uint8_t)(a[i / 8] >> (8 * (i % 8)));
+  return out;
+}
 struct Merkle {
+  static std::vector<uint8_t> hash(const std::vector<uint8_t>& data) {          // merkle.rs:8-12
+    const auto h = sha3_256(data.data(), data.size());
+    return std::vector<uint8_t>(h.begin(), h.end());
+  }
+  // merkle.rs:49-66, as written: left / right are read off the bits of the index, which is the tree's shape when every split is even
+  static bool verify(const MerkleRoot& root, size_t index, const MerklePath& path, const std::vector<uint8_t>& leaf) {
+    if (path.empty()) throw Panic(MZK_E_LENGTH, "Merkle::verify: empty path (the reference indexes path[0])");
+    std::vector<uint8_t> acc(leaf);
+    for (size_t k = 0; k < path.size(); k++) {
+      const bool last = k + 1 == path.size();
+      const bool leaf_first = last ? index == 0 : index % 2 == 0;
+      std::vector<uint8_t> msg(leaf_first ? acc : path[k]);
+      const std::vector<uint8_t>& second = leaf_first ? path[k] : acc;
+      msg.insert(msg.end(), second.begin(), second.end());
+      acc = hash(msg);
+      index >>= 1;
+    }
+    return acc == root;
+  }
   static void flatten(const std::vector<std::vector<uint8_t>>& leafs, std::vector<uint8_t>& blob, std::vector<uint64_t>& off, size_t& stride) {
     off.assign(1, 0);
     stride = 32;
@@ -1141,5 +1204,110 @@ inline std::optional<std::vector<uint8_t>> decode_rs2d(const std::vector<std::ve
   if (!ok) return std::nullopt;
   return data;
 }
+
+// ---- Celestia (das/celestia.rs) ------------------------------------------------------------------------------------------------------
+// The reference's surface: setup, encode, commit, verify, reconstruct.  encode is the 2D code (mzk_rs2d_encode); commit is ONE call that
+// hashes every row tree, every column tree and the tree over their roots (mzk_das_grid_build) and keeps the handle, so that verify's
+// Merkle::open (:124-135) is a gather from the stored nodes (mzk_das_grid_open) where the reference re-hashes a whole row or column;
+// the check itself is Merkle::verify on the host.  Where Merkle::open does not terminate in the reference (a leaf that is the one-leaf
+// half of a three-leaf slice: ragged sides only) verify throws Panic(MZK_E_LENGTH), as Merkle::open of this mirror does.
+struct SamplePosition { size_t row, col; bool is_row; };          // das/utils.rs
+struct PublicParamsCelestia { size_t codeword_size, chunk_size; };
+struct EncodedDataCelestia {
+  std::vector<std::vector<std::vector<uint8_t>>> codewords;       // codewords[row][col] = vec![symbol]
+  size_t data_size;
+};
+struct DasGridHandle {                                            // the device-resident trees of one commitment
+  mzk_das_grid* h = nullptr;
+  DasGridHandle() = default;
+  explicit DasGridHandle(mzk_das_grid* g) : h(g) {}
+  DasGridHandle(const DasGridHandle&) = delete;
+  DasGridHandle& operator=(const DasGridHandle&) = delete;
+  ~DasGridHandle() { mzk_das_grid_free(h); }
+};
+struct CommitmentCelestia {
+  std::vector<std::vector<uint8_t>> row_roots, col_roots;
+  std::vector<uint8_t> data_root;
+  std::shared_ptr<DasGridHandle> grid;                            // not part of the commitment: what verify opens through
+};
+struct ProofCelestia { MerklePath proof; bool is_row; };
+struct Celestia {
+  typedef EncodedDataCelestia EncodedData;
+  typedef CommitmentCelestia Commitment;
+  typedef PublicParamsCelestia PublicParams;
+  static PublicParams setup(size_t chunk_size, double expansion_factor, size_t /*data_size*/) {                  // :34-41
+    size_t up = (size_t)expansion_factor;
+    if ((double)up < expansion_factor) up++;                                                                     // expansion_factor.ceil()
+    return PublicParams{chunk_size * up, chunk_size};
+  }
+  static EncodedData encode(const std::vector<uint8_t>& data, const PublicParams& params) {                      // :43-71
+    const auto rows = encode_rs2d(data, setup_rs2d(params.codeword_size, params.codeword_size, data.size()));
+    EncodedData e;
+    e.data_size = data.size();
+    for (const auto& row : rows) {
+      e.codewords.emplace_back();
+      for (uint8_t s : row) e.codewords.back().push_back(std::vector<uint8_t>(1, s));
+    }
+    return e;
+  }
+  static std::vector<uint8_t> flat(const EncodedData& encoded, size_t* rows, size_t* cols) {
+    *rows = encoded.codewords.size();
+    *cols = *rows ? encoded.codewords[0].size() : 0;
+    std::vector<uint8_t> m;
+    for (const auto& row : encoded.codewords) {
+      if (row.size() != *cols) throw Panic(MZK_E_LENGTH, "Celestia: every row must have the same number of symbols");
+      for (const auto& leaf : row) {
+        if (leaf.size() != 1) throw Panic(MZK_E_LENGTH, "Celestia: a leaf is one symbol");
+        m.push_back(leaf[0]);
+      }
+    }
+    return m;
+  }
+  static Commitment commit(const EncodedData& encoded, const PublicParams& /*params*/) {                         // :73-113
+    size_t rows, cols;
+    const std::vector<uint8_t> m = flat(encoded, &rows, &cols);
+    mzk_das_grid* g = nullptr;
+    expect(mzk_das_grid_build(m.data(), rows, cols, 1, &g));
+    Commitment c;
+    c.grid = std::make_shared<DasGridHandle>(g);
+    std::vector<uint8_t> rr(rows * 32), cr(cols * 32);
+    c.data_root.resize(32);
+    expect(mzk_das_grid_roots(g, rr.data(), cr.data(), c.data_root.data()));
+    for (size_t r = 0; r < rows; r++) c.row_roots.emplace_back(rr.begin() + 32 * r, rr.begin() + 32 * (r + 1));
+    for (size_t k = 0; k < cols; k++) c.col_roots.emplace_back(cr.begin() + 32 * k, cr.begin() + 32 * (k + 1));
+    return c;
+  }
+  // Merkle::open(position) of the COMMITTED square, from the handle
+  static ProofCelestia open(const SamplePosition& position, const Commitment& commitment, uint8_t* leaf = nullptr) {
+    if (!commitment.grid || !commitment.grid->h) throw Panic(MZK_E_ARG, "Celestia: the commitment holds no grid handle");
+    const uint64_t pos[4] = {0, position.row, position.col, position.is_row ? 1u : 0u};
+    uint8_t paths[MZK_DAS_PATH_MAX * 32], lens[MZK_DAS_PATH_MAX], depth = 0, symbol = 0;
+    expect(mzk_das_grid_open(commitment.grid->h, pos, 1, paths, lens, &depth, &symbol));
+    if (depth == 0) throw Panic(MZK_E_LENGTH, "Merkle::open recurses forever on the one-leaf half of a three-leaf slice (merkle.rs:36-45)");
+    ProofCelestia p;
+    p.is_row = position.is_row;
+    for (size_t k = 0; k < depth; k++) p.proof.emplace_back(paths + 32 * k, paths + 32 * k + lens[k]);
+    if (leaf) *leaf = symbol;
+    return p;
+  }
+  // :115-169.  The path is the committed square's (the reference opens `encoded`, which is the committed square in every honest call);
+  // the leaf is encoded's, so a square that differs from the commitment at the sampled position fails as it does there.
+  static bool verify(const SamplePosition& position, const EncodedData& encoded, const Commitment& commitment, const PublicParams& /*params*/) {
+    const ProofCelestia proof = open(position, commitment);
+    const std::vector<uint8_t>& leaf = encoded.codewords.at(position.row).at(position.col);
+    if (proof.is_row) return Merkle::verify(commitment.row_roots.at(position.row), position.col, proof.proof, leaf);
+    return Merkle::verify(commitment.col_roots.at(position.col), position.row, proof.proof, leaf);
+  }
+  static std::vector<uint8_t> reconstruct(const EncodedData& encoded, const PublicParams& params) {              // :171-185
+    std::vector<std::vector<uint8_t>> reshaped;
+    for (const auto& row : encoded.codewords) {
+      reshaped.emplace_back();
+      for (const auto& v : row) reshaped.back().push_back(v.at(0));
+    }
+    auto out = decode_rs2d(reshaped, setup_rs2d(params.codeword_size, params.codeword_size, encoded.data_size));
+    if (!out) throw Panic(MZK_E_ARG, "called `Option::unwrap()` on a `None` value");                            // :184
+    return *out;
+  }
+};
 
 }  // namespace myzkp

@@ -65,7 +65,7 @@ def kernel_resources(so):
 # `python tools/kernel_resources.py --priced` prints their table (profiles/r05final_kernel_resources.txt)
 PRICED = ("k_seg_accumulate", "k_seg_combine", "k_ntt_strided", "k_ntt_last", "k_direct_accumulate", "k_direct_finish", "k_many_sort1", "k_many_count",
           "k_many_scatter", "k_sd_block", "k_fine_scatter", "k_fine_count", "k_coarse_scatter", "k_coarse_count", "k_merkle", "k_fri_fold", "k_reduce_tail_row",
-          "k_prepare_points", "k_window_combine_row")
+          "k_prepare_points", "k_window_combine_row", "k_das_trees")
 
 
 if __name__ == "__main__":
