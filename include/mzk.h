@@ -877,7 +877,16 @@ int mzk_selftest_inv_wave(uint64_t seed, size_t n, uint64_t* mismatches);
  *     function returned (infinity all-zero; TO_AFFINE: 16 plain ABI words x || y, then zeros).  form: _CPP / _ASM (the product
  *     routines of the single-lane group law), _QUAD (xyzz_add_quad / xyzz_dbl_quad, one case per DPP quad), _ROW (rowop::add /
  *     rowop::dbl, one case per wave through the packed records of rowop::load / rowop::store), _WAVE (TO_AFFINE: wave_store_affine).
- *     b may be NULL where the op takes no second operand, neg where it takes no sign. */
+ *     b may be NULL where the op takes no second operand, neg where it takes no sign.
+ *   mzk_selftest_g2_probe: ONE function of myzkp_amd/csrc/mzk_g2.h per call (tests/g2_model.py, tests/test_gpu_g2_probe.py; the host
+ *     build runs the same tables in tests/test_hostcheck_g2_probe.py).  An Fq2 value is 2 x 9 limbs (c0 then c1, Montgomery form), an
+ *     XYZZ slot over Fq2 4 x 2 x 9 limbs (X, Y, ZZ, ZZZ; all-zero = infinity), an affine operand 2 x 2 x 9 limbs (x, y; canonical).
+ *     F2_ADD / F2_SUB / F2_MUL(a, b), F2_DBL / F2_SQR / F2_INV / F2_IS_ZERO(a): out = one Fq2 per case (IS_ZERO: limb 0 = 0 / 1).
+ *     MADD(a slot, b affine), ADD(a slot, b slot), DBL(a slot), DBL_AFFINE(a affine), TO_AFFINE(a slot), SCALAR_MUL(a affine, k = 8
+ *     canonical scalar words), STORE_LOAD(a slot: x2_store then x2_load): out = one slot per case holding the limbs the function
+ *     returned (TO_AFFINE: the 32 plain wire words x.c0 | x.c1 | y.c0 | y.c1, then zeros).  G2 has the portable form only, so there
+ *     is no form argument.  b and k may be NULL where the op does not take them; an unknown op, a null pointer the op needs or
+ *     n > 2^20: MZK_E_ARG with nothing launched; n = 0 is MZK_OK. */
 enum { MZK_PROBE_MUL = 0, MZK_PROBE_SQR = 1, MZK_PROBE_MUL_ADD2 = 2, MZK_PROBE_SHOUP_MUL = 3, MZK_PROBE_SMUL = 4, MZK_PROBE_SMUL_C1 = 5,
        MZK_PROBE_SADD = 6, MZK_PROBE_SSUB = 7, MZK_PROBE_SCARRY = 8, MZK_PROBE_SBIAS = 9, MZK_PROBE_SREDUCE = 10,
        MZK_PROBE_ADD = 11, MZK_PROBE_SUB4 = 12, MZK_PROBE_SUB8 = 13, MZK_PROBE_NEG_LAZY4 = 14, MZK_PROBE_NEG_LAZY8 = 15,
@@ -887,8 +896,12 @@ enum { MZK_PROBE_MUL = 0, MZK_PROBE_SQR = 1, MZK_PROBE_MUL_ADD2 = 2, MZK_PROBE_S
 enum { MZK_PROBE_FORM_CPP = 0, MZK_PROBE_FORM_ASM = 1, MZK_PROBE_FORM_QUAD = 2, MZK_PROBE_FORM_ROW = 3, MZK_PROBE_FORM_WAVE = 4 };
 enum { MZK_PROBE_G1_MADD_SIGNED = 0, MZK_PROBE_G1_MADD = 1, MZK_PROBE_G1_ADD = 2, MZK_PROBE_G1_DBL = 3, MZK_PROBE_G1_DBL_AFFINE = 4,
        MZK_PROBE_G1_TO_AFFINE = 5 };
+enum { MZK_PROBE_G2_F2_ADD = 0, MZK_PROBE_G2_F2_SUB = 1, MZK_PROBE_G2_F2_DBL = 2, MZK_PROBE_G2_F2_MUL = 3, MZK_PROBE_G2_F2_SQR = 4,
+       MZK_PROBE_G2_F2_INV = 5, MZK_PROBE_G2_F2_IS_ZERO = 6, MZK_PROBE_G2_MADD = 7, MZK_PROBE_G2_ADD = 8, MZK_PROBE_G2_DBL = 9,
+       MZK_PROBE_G2_DBL_AFFINE = 10, MZK_PROBE_G2_TO_AFFINE = 11, MZK_PROBE_G2_SCALAR_MUL = 12, MZK_PROBE_G2_STORE_LOAD = 13 };
 int mzk_selftest_field_probe(int field_id, int op, int form, size_t n, const uint32_t* in, uint32_t* out);
 int mzk_selftest_g1_probe(int op, int form, size_t n, const uint32_t* a, const uint32_t* b, const uint8_t* neg, uint32_t* out);
+int mzk_selftest_g2_probe(int op, size_t n, const uint32_t* a, const uint32_t* b, const uint32_t* k, uint32_t* out);
 
 /* ---- Reed-Solomon over GF(2^8) (algebra/reedsolomon.rs) ------------------------------------------------------------ */
 /* The codec every data-availability system of das/ starts with (das/avail.rs, das/eigenda.rs, das/celestia.rs), batched: every chunk,

@@ -3,11 +3,12 @@
 // TEST SURFACE.  Operands arrive as raw u32 limbs (P::L per field element, whatever representation the caller chose: lazy,
 // signed, un-normalised), the result leaves as the raw limbs the function returned -- no reduction, packing or comparison on the
 // way; the judgement is made in Python integers (tests/arith_model.py).  The per-lane forms below are plain C++ over
-// mzk_field.h / mzk_ec.h, so the SAME text is compiled by hipcc for the device (mzk_probe.hip, mzk_selftest_field_probe /
-// mzk_selftest_g1_probe) and by g++ for the bounds-checked host build (tests/hostcheck: hc_field_probe / hc_g1_probe), and both
-// sides read the same case table.  The asm, quad, row and wave forms exist only on the device and live in mzk_probe.hip.
+// mzk_field.h / mzk_ec.h / mzk_g2.h, so the SAME text is compiled by hipcc for the device (mzk_probe.hip, mzk_selftest_field_probe /
+// mzk_selftest_g1_probe / mzk_selftest_g2_probe) and by g++ for the bounds-checked host build (tests/hostcheck: hc_field_probe /
+// hc_g1_probe / hc_g2_probe), and both sides read the same case table (G2: tests/g2_model.py).  The asm, quad, row and wave forms exist only on the device and live in mzk_probe.hip.
 #pragma once
 #include "mzk_ec.h"
+#include "mzk_g2.h"
 
 namespace mzk {
 
@@ -118,6 +119,66 @@ template <int OP, template <class> class A> MZK_HD void probe_g1_lane(const u32*
 #pragma unroll
     for (int i = 0; i < PR_SLOT; i++) out[i] = 0;
     if (xyzz_to_affine<true>(probe_ld_slot(a), &af)) affine_store_plain(af, out);
+  }
+}
+
+// ---- G2 (mzk_g2.h): Fq2 and the XYZZ group law over it.  Portable form only: G2 has no asm, quad or row variant. ----------------
+enum {
+  PR_G2_F2_ADD = 0, PR_G2_F2_SUB = 1, PR_G2_F2_DBL = 2, PR_G2_F2_MUL = 3, PR_G2_F2_SQR = 4, PR_G2_F2_INV = 5, PR_G2_F2_IS_ZERO = 6,
+  PR_G2_MADD = 7, PR_G2_ADD = 8, PR_G2_DBL = 9, PR_G2_DBL_AFFINE = 10, PR_G2_TO_AFFINE = 11, PR_G2_SCALAR_MUL = 12, PR_G2_STORE_LOAD = 13,
+  PR_G2_OPS = 14
+};
+constexpr int PR_F2 = 2 * FqParams::L;        // an Fq2 operand / result: c0 then c1, 9 raw limbs each
+constexpr int PR_SLOT2 = 4 * PR_F2;           // an XYZZ operand / result over Fq2: X, Y, ZZ, ZZZ, coordinate-major, all-zero = infinity
+constexpr int PR_AFF2 = 2 * PR_F2;            // an affine operand: x, y, Montgomery form, canonical
+// limbs of operand a / operand b / the result, scalar words, per case
+MZK_HD constexpr int probe_g2_a_words(int op) { return op <= PR_G2_F2_IS_ZERO ? PR_F2 : (op == PR_G2_DBL_AFFINE || op == PR_G2_SCALAR_MUL) ? PR_AFF2 : PR_SLOT2; }
+MZK_HD constexpr int probe_g2_b_words(int op) {
+  return (op == PR_G2_F2_ADD || op == PR_G2_F2_SUB || op == PR_G2_F2_MUL) ? PR_F2 : op == PR_G2_MADD ? PR_AFF2 : op == PR_G2_ADD ? PR_SLOT2 : 0;
+}
+MZK_HD constexpr int probe_g2_k_words(int op) { return op == PR_G2_SCALAR_MUL ? 8 : 0; }
+MZK_HD constexpr int probe_g2_out_words(int op) { return op <= PR_G2_F2_IS_ZERO ? PR_F2 : PR_SLOT2; }
+
+MZK_HD Fq2 probe_ld_f2(const u32* w) { Fq2 r; r.c0 = probe_ld<FqParams>(w); r.c1 = probe_ld<FqParams>(w + 9); return r; }
+MZK_HD void probe_st_f2(const Fq2& a, u32* w) { probe_st<FqParams>(a.c0, w); probe_st<FqParams>(a.c1, w + 9); }
+MZK_HD Xyzz2 probe_ld_slot2(const u32* w) {
+  Xyzz2 p;
+  p.X = probe_ld_f2(w); p.Y = probe_ld_f2(w + PR_F2); p.ZZ = probe_ld_f2(w + 2 * PR_F2); p.ZZZ = probe_ld_f2(w + 3 * PR_F2);
+  return p;
+}
+MZK_HD Affine2 probe_ld_affine2(const u32* w) { Affine2 a; a.x = probe_ld_f2(w); a.y = probe_ld_f2(w + PR_F2); return a; }
+// the limbs the function returned, as they are: infinity has to come back as the all-zero slot by itself
+MZK_HD void probe_st_slot2(const Xyzz2& p, u32* w) {
+  probe_st_f2(p.X, w); probe_st_f2(p.Y, w + PR_F2); probe_st_f2(p.ZZ, w + 2 * PR_F2); probe_st_f2(p.ZZZ, w + 3 * PR_F2);
+}
+// G2 op OP on one case.  Fq2 ops: a, b, out = Fq2 (is_zero: out[0] = 0 / 1, rest 0).  Group ops: a = slot (dbl_affine, scalar_mul:
+// affine), b = affine (madd) or slot (add), k = 8 canonical scalar words (scalar_mul); out = one slot.  to_affine: the 32 plain wire
+// words of g2_store_plain (all-zero = infinity), rest 0.  store_load: the slot x2_load reads back from what x2_store wrote.
+template <int OP> MZK_HD void probe_g2_lane(const u32* a, const u32* b, const u32* k, u32* out) {
+  if constexpr (OP == PR_G2_F2_ADD) probe_st_f2(f2_add(probe_ld_f2(a), probe_ld_f2(b)), out);
+  else if constexpr (OP == PR_G2_F2_SUB) probe_st_f2(f2_sub(probe_ld_f2(a), probe_ld_f2(b)), out);
+  else if constexpr (OP == PR_G2_F2_DBL) probe_st_f2(f2_dbl(probe_ld_f2(a)), out);
+  else if constexpr (OP == PR_G2_F2_MUL) probe_st_f2(f2_mul(probe_ld_f2(a), probe_ld_f2(b)), out);
+  else if constexpr (OP == PR_G2_F2_SQR) probe_st_f2(f2_sqr(probe_ld_f2(a)), out);
+  else if constexpr (OP == PR_G2_F2_INV) probe_st_f2(f2_inv(probe_ld_f2(a)), out);
+  else if constexpr (OP == PR_G2_F2_IS_ZERO) {
+    const bool z = f2_is_zero(probe_ld_f2(a));
+    for (int i = 0; i < PR_F2; i++) out[i] = 0;
+    out[0] = z ? 1u : 0u;
+  }
+  else if constexpr (OP == PR_G2_MADD) probe_st_slot2(x2_madd(probe_ld_slot2(a), probe_ld_affine2(b)), out);
+  else if constexpr (OP == PR_G2_ADD) probe_st_slot2(x2_add(probe_ld_slot2(a), probe_ld_slot2(b)), out);
+  else if constexpr (OP == PR_G2_DBL) probe_st_slot2(x2_dbl(probe_ld_slot2(a)), out);
+  else if constexpr (OP == PR_G2_DBL_AFFINE) probe_st_slot2(x2_dbl_affine(probe_ld_affine2(a)), out);
+  else if constexpr (OP == PR_G2_TO_AFFINE) {
+    for (int i = 0; i < PR_SLOT2; i++) out[i] = 0;
+    g2_store_plain(probe_ld_slot2(a), out);
+  }
+  else if constexpr (OP == PR_G2_SCALAR_MUL) probe_st_slot2(x2_scalar_mul(probe_ld_affine2(a), k), out);
+  else if constexpr (OP == PR_G2_STORE_LOAD) {
+    u32 rec[64];
+    x2_store(probe_ld_slot2(a), rec);
+    probe_st_slot2(x2_load(rec), out);
   }
 }
 

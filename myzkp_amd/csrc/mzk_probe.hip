@@ -1,4 +1,5 @@
-// mzk_probe.hip -- the device side of the arithmetic probe (mzk_probe.h): mzk_selftest_field_probe / mzk_selftest_g1_probe.
+// mzk_probe.hip -- the device side of the arithmetic probe (mzk_probe.h): mzk_selftest_field_probe / mzk_selftest_g1_probe /
+// mzk_selftest_g2_probe.
 // One kernel per (field, op, form): a probe kernel holds one device function and its loads and stores, so what it compiles to is
 // that function under no other register pressure, and a failure names the operation and the form.  Operands come from the host as
 // raw limbs and go back as raw limbs; tests/test_gpu_arith_probe.py judges them against the integer model of tests/arith_model.py.
@@ -260,4 +261,57 @@ int selftest_g1_probe_impl(int op, int form, size_t n, const uint32_t* a_host, c
   return MZK_OK;
 }
 
+// ---- G2 (mzk_g2.h) -------------------------------------------------------------------------------------------------------------
+// one thread per case, 64 per workgroup like the G2 kernels of mzk_g2.hip (the group law over Fq2 wants the whole register file)
+template <int OP>
+__global__ __launch_bounds__(64) void k_probe_g2_lane(size_t n, const u32* __restrict__ a, const u32* __restrict__ b, const u32* __restrict__ k,
+                                                       u32* __restrict__ out) {
+  constexpr int AW = probe_g2_a_words(OP), BW = probe_g2_b_words(OP), KW = probe_g2_k_words(OP), OW = probe_g2_out_words(OP);
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  u32 x[AW], y[BW ? BW : 1], kk[KW ? KW : 1], r[OW];
+  for (int j = 0; j < AW; j++) x[j] = a[i * AW + j];
+  for (int j = 0; j < BW; j++) y[j] = b[i * BW + j];
+  for (int j = 0; j < KW; j++) kk[j] = k[i * KW + j];
+  probe_g2_lane<OP>(x, y, kk, r);
+  for (int j = 0; j < OW; j++) out[i * OW + j] = r[j];
+}
+template <int OP = 0> static void probe_g2_launch(int op, size_t n, const u32* a, const u32* b, const u32* k, u32* out, hipStream_t s) {
+  if constexpr (OP < PR_G2_OPS) {
+    if (op != OP) return probe_g2_launch<OP + 1>(op, n, a, b, k, out, s);
+    hipLaunchKernelGGL(k_probe_g2_lane<OP>, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, s, n, a, b, k, out);
+  }
+}
+static int selftest_g2_probe_impl(int op, size_t n, const uint32_t* a_host, const uint32_t* b_host, const uint32_t* k_host, uint32_t* out_host, hipStream_t s) {
+  WsFrame ws("selftest_g2_probe_impl");
+  const size_t aw = probe_g2_a_words(op), bw = probe_g2_b_words(op), kw = probe_g2_k_words(op), ow = probe_g2_out_words(op);
+  void *da, *db, *dk, *dout;
+  MZK_TRY(ws.get(WS_MISC_A, n * aw * 4, &da));
+  MZK_TRY(ws.get(WS_MISC_B, n * (bw ? bw : 1) * 4, &db));
+  MZK_TRY(ws.get(WS_MISC_C, n * (kw ? kw : 1) * 4, &dk));
+  MZK_TRY(ws.get(WS_MISC_D, n * ow * 4, &dout));
+  MZK_HIP(hipMemcpyAsync(da, a_host, n * aw * 4, hipMemcpyHostToDevice, s));
+  if (bw) MZK_HIP(hipMemcpyAsync(db, b_host, n * bw * 4, hipMemcpyHostToDevice, s));
+  if (kw) MZK_HIP(hipMemcpyAsync(dk, k_host, n * kw * 4, hipMemcpyHostToDevice, s));
+  MZK_HIP(hipMemsetAsync(dout, 0, n * ow * 4, s));
+  probe_g2_launch(op, n, (const u32*)da, (const u32*)db, (const u32*)dk, (u32*)dout, s);
+  MZK_HIP(hipGetLastError());
+  MZK_HIP(hipMemcpyAsync(out_host, dout, n * ow * 4, hipMemcpyDeviceToHost, s));
+  MZK_HIP(hipStreamSynchronize(s));
+  return MZK_OK;
+}
+
 }  // namespace mzk
+
+using namespace mzk;
+extern "C" int mzk_selftest_g2_probe(int op, size_t n, const uint32_t* a, const uint32_t* b, const uint32_t* k, uint32_t* out) {
+  MZK_ENTER();
+  if (op < 0 || op >= PR_G2_OPS) { set_error("g2_probe: no op %d", op); return MZK_E_ARG; }
+  if (!a || !out || (probe_g2_b_words(op) && !b) || (probe_g2_k_words(op) && !k) || n > ((size_t)1 << 20)) {
+    set_error("g2_probe: null pointer or more than 2^20 cases");
+    return MZK_E_ARG;
+  }
+  if (n == 0) return MZK_OK;
+  WsGuard wsg(ctx().stream);
+  return selftest_g2_probe_impl(op, n, a, b, k, out, ctx().stream);
+}

@@ -31,6 +31,16 @@ template <int OP> static void run_g1_probe(size_t n, const u32* a, const u32* b,
   constexpr int BW = OP == PR_G1_ADD ? PR_SLOT : (OP == PR_G1_MADD || OP == PR_G1_MADD_SIGNED) ? PR_AFF : 0;
   for (size_t i = 0; i < n; i++) probe_g1_lane<OP, FeCpp>(a + i * AW, BW ? b + i * BW : nullptr, OP == PR_G1_MADD_SIGNED && neg[i] != 0, out + i * PR_SLOT);
 }
+template <int OP = 0> static int run_g2_probe(int op, size_t n, const u32* a, const u32* b, const u32* k, u32* out) {
+  if constexpr (OP == PR_G2_OPS) {
+    return -1;
+  } else {
+    if (op != OP) return run_g2_probe<OP + 1>(op, n, a, b, k, out);
+    constexpr int AW = probe_g2_a_words(OP), BW = probe_g2_b_words(OP), KW = probe_g2_k_words(OP), OW = probe_g2_out_words(OP);
+    for (size_t i = 0; i < n; i++) probe_g2_lane<OP>(a + i * AW, BW ? b + i * BW : nullptr, KW ? k + i * KW : nullptr, out + i * OW);
+    return 0;
+  }
+}
 
 template <class P> static void run_field(int op, const u32* a, const u32* b, u32* out) {
   Fe<P> x = fe_to_mont<P>(fe_unpack<P>(a));
@@ -183,6 +193,8 @@ int hc_g1_probe(int op, size_t n, const u32* a, const u32* b, const uint8_t* neg
   }
   return -1;
 }
+// mzk_selftest_g2_probe on the host: one function of mzk_g2.h per call, raw limbs in, raw limbs out (tests/g2_model.py)
+int hc_g2_probe(int op, size_t n, const u32* a, const u32* b, const u32* k, u32* out) { return op < 0 ? -1 : run_g2_probe<>(op, n, a, b, k, out); }
 // one in-tile transform of 2^lgn points by the kernels' stage schedule (bounds asserted along the way)
 int hc_ntt_tile(int fid, const u32* words, int lgn, const u32* tw_words, u32* out) {
   if (fid == 0) run_ntt_tile<FrParams>(words, lgn, tw_words, out);
