@@ -145,11 +145,16 @@ def _interpolate_degree(p, xs, ys):
     """degree of the Lagrange interpolant through (xs, ys) -- the last codeword's low-degree check (fri.rs:300-318)"""
     n = len(xs)
     coef = [0] * n
+    full = [1]                                                                   # prod_j (X - x_j), ascending
+    for x in xs:
+        full = [(a - x * b) % p for a, b in zip([0] + full, full + [0])]
     for i in range(n):
-        num, den = [1], 1
+        num, carry, den = [0] * n, 0, 1                                          # full / (X - x_i) by synthetic division (quadratic in all)
+        for k in range(n, 0, -1):
+            carry = (full[k] + carry * xs[i]) % p
+            num[k - 1] = carry
         for j in range(n):
             if j != i:
-                num = [(a - xs[j] * b) % p for a, b in zip([0] + num, num + [0])]
                 den = den * (xs[i] - xs[j]) % p
         s = ys[i] * pow(den, -1, p) % p
         coef = [(c + s * t) % p for c, t in zip(coef, num)]

@@ -4,7 +4,11 @@
   * scale: the two-register AIR of tests/test_gpu_stark_stages.py at T = 2000, 30000, 120000 with 17 colinearity checks and once over Fr:
     the model's verifier (O(T) per query) accepts and rejects the false boundary; the proof equals the one assembled stage by stage
     (whose roots that file rebuilds from Python long division and the oracle); two calls give identical bytes; host and _dev forms agree;
-  * workspace hygiene: a prove between unrelated calls changes none of their results, nor they its own; the workspace can be released."""
+  * workspace hygiene: a prove between unrelated calls changes none of their results, nor they its own; the workspace can be released.
+Every case here has two registers, degree 2, expansion 4 and two constraints with equal shifts, and every refusal happens before the
+first launch.  Other register counts, degrees, expansion factors, constraint counts and shifts, boundaries that leave a register
+without an entry, the prefix interpolation and zerofier, the small coset division, a constant register, a refusal after work is
+enqueued and one handle over several boundaries are tests/test_gpu_stark_shapes.py, bit for bit against the model's prover."""
 import json, os, random, sys
 import numpy as np
 import pytest
@@ -48,8 +52,8 @@ def prove_both(env, st, fid, trace, boundary, randomizer):
     return raw, proof
 
 
-def tampered(proof):
-    """one changed value / path byte / root in every section of the FastStarkProof"""
+def tampered(proof, P=P):
+    """one changed value / path byte / root in every section of the FastStarkProof (P: the field's modulus)"""
     for key in ("bqc_points", "rdc_points", "tzc_points"):
         bad = dict(proof)
         bad[key] = [(proof[key][0] + 1) % P] + list(proof[key][1:])

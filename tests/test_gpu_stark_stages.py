@@ -47,9 +47,11 @@ def rescue():
     return rp, model, rp.transition_constraints(omicron)
 
 
-def prove_staged(env, fid, p, g, omega, omicron, e, checks, m, cycles, degree, cons, trace, boundary, randomizer, dbg=None):
+def prove_staged(env, fid, p, g, omega, omicron, e, checks, m, cycles, degree, cons, trace, boundary, randomizer, dbg=None, exact=True):
     """fast_stark.rs:177-396 over the library's entry points; returns the proof in the model's shape.  dbg: the model's intermediates to
-    compare with on the way (reference parameters only)."""
+    compare with on the way.  exact: every quotient meets its degree bound (False for a trace with a constant register, whose
+    polynomials are shorter: the bounds then hold as bounds)."""
+    meets = (lambda degrees, bounds: degrees == bounds) if exact else (lambda degrees, bounds: all(a <= b for a, b in zip(degrees, bounds)))
     torch, mz, dev, st = env
     nl = orc.LIMBS[fid]
     Lf = lambda vals: orc.to_limbs([int(v) for v in vals], nl)
@@ -62,7 +64,7 @@ def prove_staged(env, fid, p, g, omega, omicron, e, checks, m, cycles, degree, c
     # boundary quotients (:217-224): no interpolant, the roots alone
     roots = [[pow(omicron, c, p) for c, r, _ in boundary if r == s] for s in range(m)]
     bqs = mz.poly_div_roots(fid, tps, roots)
-    assert [q.shape[0] - 1 for q in bqs] == d["boundary_quotient_degree_bounds"]
+    assert meets([q.shape[0] - 1 for q in bqs], d["boundary_quotient_degree_bounds"])
     # extend and commit (:228-244)
     codewords = [mz.coset_lde(fid, q, g, omega, flen) for q in bqs]
     trees = [mz.MerkleTree(fid, cw) for cw in codewords]
@@ -87,7 +89,7 @@ def prove_staged(env, fid, p, g, omega, omicron, e, checks, m, cycles, degree, c
     torch.cuda.synchronize()
     out = d_tq.cpu().numpy().view(np.uint64).reshape(len(tpolys), stride, nl)
     tqs = [out[a, :qlens[a]].copy() for a in range(len(tpolys))]
-    assert [n - 1 for n in qlens] == d["transition_quotient_degree_bounds"]
+    assert meets([n - 1 for n in qlens], d["transition_quotient_degree_bounds"])
     # the randomizer codeword and its root (:275-299), the weights over the library's roots
     r_cw = mz.coset_lde(fid, Lf(randomizer), g, omega, flen)
     proof["rdc_root"] = bytes(mz.merkle_commit_field(fid, r_cw))
