@@ -1012,6 +1012,57 @@ int mzk_das_grid_open_dev(const mzk_das_grid* grid, const void* d_positions, siz
                           void* d_leaves, void* stream);
 void mzk_das_grid_free(mzk_das_grid* grid);
 
+/* ---- Rescue-Prime (zkstark/rescueprime.rs) -------------------------------------------------------------------------------- */
+/* Batched hashes, hash chains and their traces, one chain per lane: the witness of mzk_stark_prove_dev made where it is read.
+ *   A hash (rescueprime.rs:401-452) absorbs one element, state = [x, 0, .., 0] of m elements, runs n_rounds rounds of two half-rounds
+ *   -- every element raised to alpha (first half) or alphainv (second half), then state = mds * state + round constants, the constant
+ *   of (round r, half h, element i) at index 2 r m + h m + i -- and returns state[0].  A chain of `links` hashes feeds the output of
+ *   link l into link l + 1.  The trace of a hash is the state before round 0 and after every round: n_rounds + 1 rows of m elements.
+ *   Admitted: rescue_field_id MZK_FIELD_M128 or MZK_FIELD_FR (any other id, MZK_FIELD_FQ and the Goldilocks ids included, is refused in this
+ *   section's own words: "rescue: field id N is neither MZK_FIELD_M128 nor MZK_FIELD_FR"); 1 <= m <= MZK_RESCUE_MAX_M; 1 <= n_rounds <= MZK_RESCUE_MAX_ROUNDS; alpha any
+ *   uint64_t; alphainv any exponent below 2^256, four little-endian uint64_t for both fields.  x^0 = 1 for every x, 0 included (utils.rs
+ *   pow).  That the two exponents are inverse to each other is not checked, as the reference does not check it.
+ *   Elements are canonical little-endian limbs, 2 uint64_t (M128) or 4 (Fr).  mds is m x m, row-major; round_constants 2 n_rounds m.
+ *   Layout: outputs[b * links + l] = the output of link l of chain b.  The trace of (chain b, link l) starts at element
+ *   (b * links + l) * trace_stride of `traces`, row r at r * m behind that; trace_stride >= (n_rounds + 1) m, in elements.  Elements of a
+ *   slot past the last row are NOT written: a caller that keeps the random rows of mzk_stark_prove_dev there passes
+ *   d_traces + slot * trace_stride (elements) on as d_trace as it stands.  The boundary values do not enter a proof, so a prove can be
+ *   enqueued behind mzk_rescue_trace_dev before the host knows the output.
+ *   Errors, all before anything is enqueued: MZK_E_ARG (null pointer, bad field, m or n_rounds outside the limits, a _dev pointer that
+ *   is not 16-byte aligned), MZK_E_RANGE (a constant, or in the host forms an input, that is not canonical), MZK_E_LENGTH (trace_stride
+ *   too small, batch beyond 2^40, an overflowing size product), MZK_E_NOMEM.  batch = 0 or links = 0: MZK_OK, nothing done.
+ * Host forms take host pointers and return MZK_E_NOGPU without a device.  The _dev forms take device pointers holding canonical inputs
+ * (not checked) and only enqueue on `stream`.  A handle belongs to the context that made it, as a mzk_stark and a mzk_das_grid do: later
+ * calls enter that context; its constants are complete when mzk_rescue_new returns. */
+enum { MZK_RESCUE_MAX_M = 4, MZK_RESCUE_MAX_ROUNDS = 64 };
+typedef struct mzk_rescue mzk_rescue;
+/* What the calls below run for these parameters and `batch` chains (mzk_rescue_plan.h): host only, works without a GPU.  plan:
+ * MZK_RESCUE_PLAN_WORDS values indexed by the constants below.  For each exponent, from *_WINDOW on: the window width kept (3, 2 or 1;
+ * 0 for exponent 0), the slots read (x, x^3, x^5, x^7: at most 4), the steps of the program, its squarings, its products by a slot, the
+ * products that build the table, their sum, and what the binary method would take.  PRODUCTS_PER_HASH = n_rounds (m (both sums) + 2 m^2)
+ * + 2.  ROWS = n_rounds + 1, MIN_STRIDE = ROWS m.  A launch takes WGS = ceil(batch / BLOCK) workgroups' worth of chains with GRID <=
+ * GRID_CAP workgroups in ITERS rounds.  CONST_BYTES: what a handle keeps in device memory. */
+enum { MZK_RESCUE_PLAN_FIELD = 0, MZK_RESCUE_PLAN_M = 1, MZK_RESCUE_PLAN_ROUNDS = 2, MZK_RESCUE_PLAN_BATCH = 3,
+       MZK_RESCUE_PLAN_ALPHA_WINDOW = 4, MZK_RESCUE_PLAN_ALPHA_SLOTS = 5, MZK_RESCUE_PLAN_ALPHA_STEPS = 6, MZK_RESCUE_PLAN_ALPHA_SQUARINGS = 7,
+       MZK_RESCUE_PLAN_ALPHA_MULTIPLIES = 8, MZK_RESCUE_PLAN_ALPHA_TABLE = 9, MZK_RESCUE_PLAN_ALPHA_PRODUCTS = 10, MZK_RESCUE_PLAN_ALPHA_BINARY = 11,
+       MZK_RESCUE_PLAN_ALPHAINV_WINDOW = 12, MZK_RESCUE_PLAN_ALPHAINV_SLOTS = 13, MZK_RESCUE_PLAN_ALPHAINV_STEPS = 14, MZK_RESCUE_PLAN_ALPHAINV_SQUARINGS = 15,
+       MZK_RESCUE_PLAN_ALPHAINV_MULTIPLIES = 16, MZK_RESCUE_PLAN_ALPHAINV_TABLE = 17, MZK_RESCUE_PLAN_ALPHAINV_PRODUCTS = 18, MZK_RESCUE_PLAN_ALPHAINV_BINARY = 19,
+       MZK_RESCUE_PLAN_PRODUCTS_PER_HASH = 20, MZK_RESCUE_PLAN_ROWS = 21, MZK_RESCUE_PLAN_MIN_STRIDE = 22,
+       MZK_RESCUE_PLAN_BLOCK = 23, MZK_RESCUE_PLAN_WGS = 24, MZK_RESCUE_PLAN_GRID = 25, MZK_RESCUE_PLAN_ITERS = 26, MZK_RESCUE_PLAN_GRID_CAP = 27,
+       MZK_RESCUE_PLAN_CONST_BYTES = 28, MZK_RESCUE_PLAN_WORDS = 29 };
+int mzk_rescue_plan_get(int rescue_field_id, size_t m, size_t n_rounds, uint64_t alpha, const uint64_t alphainv[4], size_t batch, uint64_t* plan);
+/* The parameters as a handle: both exponents as programs, the MDS matrix and the round constants in Montgomery form, in device memory. */
+int mzk_rescue_new(int rescue_field_id, size_t m, size_t n_rounds, uint64_t alpha, const uint64_t alphainv[4], const uint64_t* mds,
+                   const uint64_t* round_constants, mzk_rescue** out);
+void mzk_rescue_free(mzk_rescue* h);
+/* `batch` chains of `links` hashes: batch inputs, batch * links outputs. */
+int mzk_rescue_hash(mzk_rescue* h, const uint64_t* inputs, size_t batch, size_t links, uint64_t* outputs);
+int mzk_rescue_hash_dev(mzk_rescue* h, const void* d_inputs, size_t batch, size_t links, void* d_outputs, void* stream);
+/* The same with the trace of every hash; outputs / d_outputs may be NULL. */
+int mzk_rescue_trace(mzk_rescue* h, const uint64_t* inputs, size_t batch, size_t links, uint64_t* traces, size_t trace_stride, uint64_t* outputs);
+int mzk_rescue_trace_dev(mzk_rescue* h, const void* d_inputs, size_t batch, size_t links, void* d_traces, size_t trace_stride, void* d_outputs,
+                         void* stream);
+
 /* Deterministic synthetic inputs (bench + tests): bit-identical to the oracle's orc_synth_*. */
 int mzk_synth_field_dev(int field_id, uint64_t seed, size_t n, void* d_out, void* stream);
 int mzk_synth_g1_points_dev(uint64_t seed, size_t n, void* d_out_xy, void* stream);

@@ -1646,3 +1646,88 @@ class DasGrid:
             self.close()
         except Exception:
             pass
+
+
+# ---- Rescue-Prime (zkstark/rescueprime.rs): batched hashes, chains and traces, one chain per lane ----------------------------------------
+RESCUE_MAX_M, RESCUE_MAX_ROUNDS = 4, 64
+RESCUE_PLAN_FIELDS = ("field", "m", "rounds", "batch",
+                      "alpha_window", "alpha_slots", "alpha_steps", "alpha_squarings", "alpha_multiplies", "alpha_table", "alpha_products", "alpha_binary",
+                      "alphainv_window", "alphainv_slots", "alphainv_steps", "alphainv_squarings", "alphainv_multiplies", "alphainv_table", "alphainv_products",
+                      "alphainv_binary", "products_per_hash", "rows", "min_stride", "block", "wgs", "grid", "iters", "grid_cap", "const_bytes")
+
+
+def _exp4(e):
+    e = int(e)
+    if e < 0 or e >> 256:
+        raise MzkError(-1, "rescue: alphainv = %d is outside 0 .. 2^256 - 1" % e)
+    return to_limbs([e], 4)
+
+
+def rescue_plan(fid, m, n, alpha, alphainv, batch=0):
+    """What a handle of these parameters runs for `batch` chains, as a dict keyed after the MZK_RESCUE_PLAN_* constants
+    (mzk_rescue_plan_get).  Host only: no GPU needed."""
+    p = np.zeros(len(RESCUE_PLAN_FIELDS), dtype=np.uint64)
+    _check(lib().mzk_rescue_plan_get(int(fid), _sz(m), _sz(n), ctypes.c_uint64(int(alpha)), _p(_exp4(alphainv)), _sz(batch), _p(p)))
+    return {k: int(v) for k, v in zip(RESCUE_PLAN_FIELDS, p)}
+
+
+class RescuePrime:
+    """mzk_rescue: Rescue-Prime over field `fid` with state width m and n rounds; mds m x m (nested or flat, row-major) and 2 n m round
+    constants as ints.  Elements travel as numpy uint64 (count x limbs); the _dev forms take device pointers (ints) and only enqueue."""
+
+    def __init__(self, fid, m, n, alpha, alphainv, mds, round_constants):
+        self.fid, self.m, self.n, self.alpha, self.alphainv = int(fid), int(m), int(n), int(alpha), int(alphainv)
+        self.rows = self.n + 1
+        flat = [int(v) for row in mds for v in (row if isinstance(row, (list, tuple)) else [row])]
+        self._h = ctypes.c_void_p()
+        _check(lib().mzk_rescue_new(self.fid, _sz(m), _sz(n), ctypes.c_uint64(self.alpha), _p(_exp4(alphainv)), _p(to_limbs(flat, LIMBS[self.fid])),
+                                    _p(to_limbs([int(v) for v in round_constants], LIMBS[self.fid])), ctypes.byref(self._h)))
+
+    def _inputs(self, inputs):
+        if isinstance(inputs, np.ndarray):
+            return _arr(self.fid, inputs)
+        return to_limbs([int(v) for v in inputs], LIMBS[self.fid])
+
+    def hash(self, inputs, links=1):
+        """outputs (batch * links x limbs): row b * links + l is the output of link l of the chain from inputs[b]"""
+        x = self._inputs(inputs)
+        out = np.zeros((x.shape[0] * int(links), LIMBS[self.fid]), dtype=np.uint64)
+        _check(lib().mzk_rescue_hash(self._h, _p(x), _sz(x.shape[0]), _sz(links), _p(out)))
+        return out
+
+    def trace(self, inputs, links=1, trace_stride=None, traces=None, with_outputs=True):
+        """(traces (batch * links x trace_stride x limbs), outputs or None).  traces: an array to write into -- elements of a slot past
+        the last row keep what they hold."""
+        x = self._inputs(inputs)
+        stride = self.rows * self.m if trace_stride is None else int(trace_stride)
+        slots = x.shape[0] * int(links)
+        if traces is None:
+            traces = np.zeros((slots, stride, LIMBS[self.fid]), dtype=np.uint64)
+        assert traces.dtype == np.uint64 and traces.flags["C_CONTIGUOUS"] and traces.size >= slots * stride * LIMBS[self.fid]
+        out = np.zeros((slots, LIMBS[self.fid]), dtype=np.uint64) if with_outputs else None
+        _check(lib().mzk_rescue_trace(self._h, _p(x), _sz(x.shape[0]), _sz(links), _p(traces), _sz(stride), _p(out) if with_outputs else None))
+        return traces, out
+
+    def hash_dev(self, d_inputs, batch, links, d_outputs, stream=None):
+        _check(lib().mzk_rescue_hash_dev(self._h, ctypes.c_void_p(int(d_inputs)), _sz(batch), _sz(links), ctypes.c_void_p(int(d_outputs)), ctypes.c_void_p(stream)))
+
+    def trace_dev(self, d_inputs, batch, links, d_traces, trace_stride, d_outputs=None, stream=None):
+        _check(lib().mzk_rescue_trace_dev(self._h, ctypes.c_void_p(int(d_inputs)), _sz(batch), _sz(links), ctypes.c_void_p(int(d_traces)), _sz(trace_stride),
+                                          ctypes.c_void_p(int(d_outputs)) if d_outputs else None, ctypes.c_void_p(stream)))
+
+    def close(self):
+        if self._h:
+            lib().mzk_rescue_free(self._h)
+            self._h = ctypes.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass

@@ -1310,4 +1310,63 @@ struct Celestia {
   }
 };
 
+// ---- RescuePrime (zkstark/rescueprime.rs) ----------------------------------------------------------------------------------------------
+// Built from the caller's parameters: the mirror holds no constants (the reference's own are data, tests/golden/rescue_prime_m128.json).
+// hash (:401-452) and trace (:531-591) go over the host forms of mzk_rescue_*; boundary_constraints (:521-529) is host arithmetic.
+// transition_constraints (:486-519) stays with the caller: symbolic MPolynomial arithmetic and Lagrange interpolation on the host; the
+// AIR enters FastStark as a term table.
+struct RescueHandle {
+  mzk_rescue* h = nullptr;
+  RescueHandle() = default;
+  explicit RescueHandle(mzk_rescue* r) : h(r) {}
+  RescueHandle(const RescueHandle&) = delete;
+  RescueHandle& operator=(const RescueHandle&) = delete;
+  ~RescueHandle() { mzk_rescue_free(h); }
+};
+template <class F> struct RescuePrime {
+  typedef std::vector<std::vector<F>> Trace;                          // stark.rs
+  typedef std::vector<std::tuple<size_t, size_t, F>> Boundary;
+  size_t m, n;
+  uint64_t alpha;
+  std::array<uint64_t, 4> alphainv;                                   // little-endian, below 2^256
+  std::vector<std::vector<F>> mds;
+  std::vector<F> round_constants;
+  std::shared_ptr<RescueHandle> handle;
+  RescuePrime(size_t m_, size_t n_, uint64_t alpha_, const std::array<uint64_t, 4>& alphainv_, const std::vector<std::vector<F>>& mds_,
+              const std::vector<F>& round_constants_)
+      : m(m_), n(n_), alpha(alpha_), alphainv(alphainv_), mds(mds_), round_constants(round_constants_) {
+    if (mds.size() != m || round_constants.size() != 2 * n * m) throw Panic(MZK_E_LENGTH, "RescuePrime: mds is m x m, round_constants 2 * n * m");
+    std::vector<F> flat;
+    for (const auto& row : mds) {
+      if (row.size() != m) throw Panic(MZK_E_LENGTH, "RescuePrime: mds is m x m, round_constants 2 * n * m");
+      flat.insert(flat.end(), row.begin(), row.end());
+    }
+    mzk_rescue* r = nullptr;
+    expect(mzk_rescue_new(F::FIELD_ID, m, n, alpha, alphainv.data(), to_wire(flat).data(), to_wire(round_constants).data(), &r));
+    handle = std::make_shared<RescueHandle>(r);
+  }
+  F hash(const F& input_element) const { return chain(input_element, 1).at(0); }                                  // :401-452
+  // the outputs of `links` hashes, link l + 1 absorbing the output of link l
+  std::vector<F> chain(const F& input_element, size_t links) const {
+    std::vector<uint64_t> out(links * F().value.size());
+    expect(mzk_rescue_hash(handle->h, input_element.value.data(), 1, links, out.data()));
+    return from_wire<F>(out, links);
+  }
+  Trace trace(const F& input_element) const {                                                                     // :531-591
+    const size_t nl = F().value.size();
+    std::vector<uint64_t> w((n + 1) * m * nl);
+    expect(mzk_rescue_trace(handle->h, input_element.value.data(), 1, 1, w.data(), (n + 1) * m, nullptr));
+    const std::vector<F> flat = from_wire<F>(w, (n + 1) * m);
+    Trace t;
+    for (size_t r = 0; r <= n; r++) t.emplace_back(flat.begin() + r * m, flat.begin() + (r + 1) * m);
+    return t;
+  }
+  Boundary boundary_constraints(const F& output_element) const {                                                  // :521-529
+    Boundary b;
+    b.emplace_back((size_t)0, (size_t)1, F::zero());
+    b.emplace_back(n, (size_t)0, output_element);
+    return b;
+  }
+};
+
 }  // namespace myzkp

@@ -14,7 +14,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HDR = os.path.join(ROOT, "include", "mzk.h")
 OUT = os.path.join(ROOT, "include", "mzk_ffi.rs")
 
-HANDLES = ("mzk_srs_multi", "mzk_srs", "mzk_merkle", "mzk_stark", "mzk_das_grid")
+HANDLES = ("mzk_srs_multi", "mzk_srs", "mzk_merkle", "mzk_stark", "mzk_das_grid", "mzk_rescue")
 STRUCTS = ("mzk_stark_dims",)      # plain structs of uint64_t fields, passed by pointer: emitted as #[repr(C)] (c_structs)
 SCALARS = {"int": "c_int", "unsigned": "c_uint", "unsigned int": "c_uint", "size_t": "usize", "uint64_t": "u64", "uint32_t": "u32",
            "uint8_t": "u8", "double": "f64", "char": "c_char", "void": "c_void"}
@@ -136,7 +136,7 @@ def emit():
     lines = ['// GENERATED by tools/gen_rust_ffi.py from include/mzk.h -- do not edit; `python tools/gen_rust_ffi.py` rewrites it.',
              '// The complete `extern "C"` surface of libmzk_hip.so (%d functions) for the Rust shim of INTEGRATION.md section 2:' % len(protos),
              '//     #[cfg(feature = "mi355x")] #[path = "../../../../include/mzk_ffi.rs"] pub mod ffi;',
-             '// Handles (mzk_srs, mzk_srs_multi, mzk_merkle, mzk_stark, mzk_das_grid) are opaque: `c_void` behind the pointer.  Plain structs (%s) are #[repr(C)] below.' % ", ".join(STRUCTS),
+             '// Handles (mzk_srs, mzk_srs_multi, mzk_merkle, mzk_stark, mzk_das_grid, mzk_rescue) are opaque: `c_void` behind the pointer.  Plain structs (%s) are #[repr(C)] below.' % ", ".join(STRUCTS),
              '// Status codes: include/mzk.h.',
              '#![allow(non_camel_case_types, dead_code)]',
              'use std::os::raw::{c_char, c_int, c_uint, c_void};',
