@@ -37,7 +37,8 @@ static const MsmKnobs& msm_knobs() {
     return MsmKnobs{tune_int("MZK_GLV_C", d.glv_c), tune_int("MZK_SMALL_SCAN", d.small_scan), tune_int("MZK_SCAN_MAX_LOG", d.scan_max_log),
                     tune_int("MZK_ACC_SEG", d.acc_seg), tune_int("MZK_COARSE_LOG_20", d.coarse_log_20),
                     tune_int("MZK_COARSE_LOG_17", d.coarse_log_17), tune_int("MZK_PER_FINE", d.per_fine), tune_int("MZK_SORT_SCAN_FREE", d.sort_scan_free),
-                    tune_int("MZK_COMBINE_WIDE_MIN_LOG", d.combine_wide_min_log)};
+                    tune_int("MZK_COMBINE_WIDE_MIN_LOG", d.combine_wide_min_log), tune_int("MZK_COMBINE_FORM", d.combine_form),
+                    tune_int("MZK_COMBINE_LANE_TPB", d.combine_lane_tpb)};
   }();
   return k;
 }
@@ -950,10 +951,32 @@ __device__ __forceinline__ bool defer_heavy(size_t b, size_t s0, size_t s1, u32 
   if (leader) { const u32 i = atomicAdd(&heavy[0], 1u); heavy[HEAVY_HDR + 2 * i] = (u32)b; heavy[HEAVY_HDR + 2 * i + 1] = o1; }
   return true;
 }
-// one lane per bucket: with 2^19 buckets of one or two partials each (generic layout) the kernel is bound by
-// the record traffic, not by a dependent chain
-__global__ __launch_bounds__(128) void k_seg_combine_wide(const u32* __restrict__ slots, const u32* __restrict__ offsets,
-                                                           u32* __restrict__ buckets, size_t nbuckets, u32 seg_host, u32* __restrict__ heavy, u32 t_max) {
+// One lane per bucket, wherever that puts at least one wave on every SIMD (msm_plan): the 2^19 buckets of one or two partials each of
+// the generic layout, and the 2^16 buckets of the 17-bit commit -- exactly one wave per SIMD, each lane a chain of 3 - 5 additions.
+// The kernel is bound by the instructions it issues either way, and the plain addition is a third of the quad form's per addition.
+// AHEAD (msm_plan: below 2^17 buckets, a wave or two per SIMD): the record of partial sl + 1 is requested before
+// partial sl is added (one buffer, taken out before the next request, as in k_seg_accumulate), so that a wave that is alone on its
+// SIMD waits for arithmetic only; the look-ahead is unconditional and clamped to the bucket's last partial, never a slot outside
+// [s0, s1].  The buffer costs registers (two waves per SIMD still fit: __launch_bounds__), which the wide grids of one or two
+// partials per bucket have no use for: they keep the plain loop and their three waves.  The look-ahead form runs in workgroups of
+// four waves (msm_plan: combine_tpb), one per SIMD of a CU; in workgroups of two the 2^16 lanes used half the SIMDs, two waves each.
+__device__ __forceinline__ void slot_request(const u32* __restrict__ g, size_t idx, u32* w) {
+  const uint4* p4 = reinterpret_cast<const uint4*>(g + idx * SLOT_WORDS);
+#pragma unroll
+  for (int q = 0; q < SLOT_WORDS / 4; q++) { const uint4 v = p4[q]; w[4 * q] = v.x; w[4 * q + 1] = v.y; w[4 * q + 2] = v.z; w[4 * q + 3] = v.w; }
+}
+__device__ __forceinline__ Xyzz slot_take(u32* w) {
+  // the wait for the record belongs HERE, in front of the next request (k_seg_accumulate's take_row)
+#pragma unroll
+  for (int k = 0; k < SLOT_WORDS; k++) asm volatile("" : "+v"(w[k]));
+  Xyzz p;
+#pragma unroll
+  for (int i = 0; i < FqParams::L; i++) { p.X.l[i] = w[i]; p.Y.l[i] = w[9 + i]; p.ZZ.l[i] = w[18 + i]; p.ZZZ.l[i] = w[27 + i]; }
+  return p;
+}
+template <bool AHEAD>
+__global__ __launch_bounds__(AHEAD ? 256 : 128, AHEAD ? 2 : 1) void k_seg_combine_wide(const u32* __restrict__ slots, const u32* __restrict__ offsets,
+                                                              u32* __restrict__ buckets, size_t nbuckets, u32 seg_host, u32* __restrict__ heavy, u32 t_max) {
   const size_t b = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (b >= nbuckets) return;
   const u32 seg = segment_length(seg_host, t_max, offsets[nbuckets]);
@@ -963,13 +986,28 @@ __global__ __launch_bounds__(128) void k_seg_combine_wide(const u32* __restrict_
   if (o1 > o0) {
     const size_t s0 = (size_t)(o0 / seg) + b, s1 = (size_t)((o1 - 1) / seg) + b;
     if (defer_heavy(b, s0, s1, o1, heavy, true)) return;
-    for (size_t sl = s0; sl <= s1; sl++) acc = xyzz_add_with<FeAsm>(acc, xyzz_gload_raw(slots, sl));
+    if constexpr (AHEAD) {
+      u32 w[SLOT_WORDS];                             // the record buffer
+      slot_request(slots, s0, w);
+      acc = slot_take(w);                            // (all-zero limbs are infinity in both forms)
+      slot_request(slots, s0 < s1 ? s0 + 1 : s1, w);
+      for (size_t sl = s0 + 1; sl <= s1; sl++) {
+        const Xyzz p = slot_take(w);
+        slot_request(slots, sl < s1 ? sl + 1 : s1, w);
+        acc = xyzz_add_with<FeAsm>(acc, p);
+      }
+    } else {
+      for (size_t sl = s0; sl <= s1; sl++) acc = xyzz_add_with<FeAsm>(acc, xyzz_gload_raw(slots, sl));
+    }
   }
   xyzz_gstore(buckets, b, acc);
 }
 // One DPP quad per bucket.  A bucket's partials form a serial chain of additions, so the quad-cooperative addition cuts the kernel's
 // latency (the quad also splits the 128-byte records).  Two / four adjacent quads per bucket, each taking every 2nd / 4th partial and
 // folding their sums through shuffles, were measured slower everywhere (see msm_many_dev_impl): the kernel is bound by its instruction count.
+// That is also where the quad stops paying: once a lane per bucket fills every SIMD with a wave (msm_plan: 64 x 4 x CUs buckets in the
+// one merged set, 2^17 elsewhere) k_seg_combine_wide takes over, a third of the instructions per addition.  The grid-batched
+// commitments (tails != null: few buckets per polynomial, HEAVY_SLOTS_SORT1) always come here.
 __global__ __launch_bounds__(128) void k_seg_combine(const u32* __restrict__ slots, const u32* __restrict__ offsets, u32* __restrict__ buckets,
                                                       size_t nbuckets, u32 seg_host, u32* __restrict__ heavy, const u32* __restrict__ tails, int lg_nb, u32 t_max) {
   const size_t tid = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -1602,8 +1640,11 @@ int msm_dev_impl(const void* d_scalars, const void* d_points, size_t n, int poin
     hipLaunchKernelGGL(k_seg_accumulate<false>, dim3((unsigned)((P.T + 255) / 256)), dim3(256), 0, s, pts, offsets, entries, slots, P.NB, P.seg, P.t_max);
     prof_end(s, MZK_PH_MSM_ACCUMULATE);
     prof_begin(s, MZK_PH_MSM_SEG_COMBINE);
-    if (P.combine_wide)
-      hipLaunchKernelGGL(k_seg_combine_wide, dim3((unsigned)((P.NB + 127) / 128)), dim3(128), 0, s, slots, offsets, buckets, P.NB, P.seg, heavy, P.t_max);
+    if (P.combine_wide && P.combine_ahead)
+      hipLaunchKernelGGL(k_seg_combine_wide<true>, dim3((unsigned)((P.NB + P.combine_tpb - 1) / P.combine_tpb)), dim3(P.combine_tpb), 0, s, slots, offsets, buckets,
+                         P.NB, P.seg, heavy, P.t_max);
+    else if (P.combine_wide)
+      hipLaunchKernelGGL(k_seg_combine_wide<false>, dim3((unsigned)((P.NB + 127) / 128)), dim3(128), 0, s, slots, offsets, buckets, P.NB, P.seg, heavy, P.t_max);
     else
       hipLaunchKernelGGL(k_seg_combine, dim3((unsigned)((4 * P.NB + 127) / 128)), dim3(128), 0, s, slots, offsets, buckets, P.NB, P.seg, heavy, (const u32*)nullptr, 0, P.t_max);
     hipLaunchKernelGGL(k_seg_combine_heavy, dim3(HEAVY_GRID), dim3(HEAVY_THREADS), 0, s, (const u32*)slots, (const u32*)offsets, buckets, heavy, P.max_heavy);

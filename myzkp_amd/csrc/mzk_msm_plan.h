@@ -113,6 +113,8 @@ struct MsmKnobs {
   int per_fine = 0;               // MZK_PER_FINE: records per fine workgroup (tools/timing/window_sweep.py)
   int sort_scan_free = 3;         // MZK_SORT_SCAN_FREE: bit 0 = coarse level, bit 1 = fine level
   int combine_wide_min_log = 17;  // MZK_COMBINE_WIDE_MIN_LOG
+  int combine_form = 0;           // MZK_COMBINE_FORM: 1 = a DPP quad per bucket, 2 = a lane per bucket, whatever the plan would pick
+  int combine_lane_tpb = 256;     // MZK_COMBINE_LANE_TPB: lanes per workgroup of the look-ahead lane form (64, 128: the measurement behind 256)
 };
 
 enum class MsmPath { SmallScan, SmallSort, TwoLevel, LdsOnePass, Atomic };
@@ -139,7 +141,8 @@ struct MsmPlan {
   // accumulate
   uint32_t seg = 0, t_max = 0;
   size_t T = 0, nslots = 0, max_heavy = 0, slot_region_words = 0;    // (one chunk's slots + heavy list)
-  bool combine_wide = false;
+  bool combine_wide = false, combine_ahead = false;    // segment combine: a lane per bucket (not a DPP quad); ... with the next record on its way
+  int combine_tpb = 256;                               // ... in workgroups of so many lanes
   MsmSizing own{}, alloc{};                    // what this call touches; what its buffers are sized for (the largest chunk in chunk mode)
   MsmWsBytes ws{}, ws_used{};                  // requests; the same formula over `own` (no chunk outgrows its region)
   MsmPlan& fail(const char* fmt, size_t a = 0, size_t b = 0, size_t c = 0) { err = MZK_E_ARG; snprintf(msg, sizeof msg, fmt, a, b, c); return *this; }
@@ -229,7 +232,19 @@ static inline MsmPlan msm_plan(size_t n, size_t n_shape, size_t n_alloc, int poi
   P.t_max = kn.acc_seg > 0 ? 0u : (uint32_t)P.T;       // the kernels shorten the segments when the scalars emit fewer entries (segment_length)
   P.nslots = P.T + P.NB + 1;
   P.max_heavy = (P.T + P.NB) / HEAVY_SLOTS + 1;        // at most (T + NB) / 33 buckets hold more than 32 partials
-  P.combine_wide = P.NB >= ((size_t)1 << kn.combine_wide_min_log);
+  // Segment combine: a lane per bucket from 2^17 buckets on, and for the one merged bucket set as soon as a lane per bucket puts a wave
+  // on every SIMD (64 lanes x 4 SIMDs x CUs: 2^16 buckets on 256 CUs, the 17-bit commit).  From there on the kernel is bound by the
+  // instructions it issues, and the plain addition issues a third of the quad form's per addition; below, lanes would leave SIMDs
+  // empty and the quad's shorter chain is what counts (k_seg_combine, mzk_msm.hip).
+  const size_t lanes_fill_chip = (size_t)64 * 4 * (size_t)(num_cu > 0 ? num_cu : 1);
+  P.combine_wide = kn.combine_form ? kn.combine_form == 2
+                                   : P.NB >= ((size_t)1 << kn.combine_wide_min_log) || (P.one_set && P.NB >= lanes_fill_chip);
+  // below 2^17 buckets the lanes are a wave or two per SIMD with nothing else to cover a record's latency: they load one record ahead
+  P.combine_ahead = P.combine_wide && P.NB < ((size_t)1 << kn.combine_wide_min_log);
+  // ... in workgroups of FOUR waves, which the dispatcher spreads over a CU's four SIMDs: 2^16 lanes are then one workgroup per CU and
+  // one wave per SIMD.  Workgroups of one or two waves came to lie two waves to a SIMD with half the SIMDs idle (55 - 56 us against
+  // 37.6 at the 2^20 commit, profiles/combine_lane_form_ab.txt); an LDS request that admits one workgroup per CU changed nothing.
+  P.combine_tpb = (kn.combine_lane_tpb == 64 || kn.combine_lane_tpb == 128) ? kn.combine_lane_tpb : 256;
   // (a chunk never has more segments than resident lanes, nor than entries / 16 -- entries / MZK_ACC_SEG with a fixed length: the
   // slot region of every chunk is sized for that)
   const size_t T_seg = E_alloc / (kn.acc_seg > 0 ? (size_t)kn.acc_seg : 16) + 1;
