@@ -49,7 +49,7 @@ int hip_fail(hipError_t e, const char* what, const char* file, int line);
 // mzk_init_devices creates one per listed ordinal (duplicates allowed: several contexts may share one GPU, which is
 // how the multi-GPU path is exercised on a one-GPU box).  Every entry point works on the CURRENT context
 // (mzk_ctx_select; context 0 after init); the *_multi entry points walk all of them.
-enum AttrFlag { ATTR_FINE_SCATTER4 = 0, ATTR_FINE_SCATTER8, ATTR_DIGITS_LDS, ATTR_SMALL_MSM, ATTR_NTT_LARGE_FR, ATTR_NTT_LARGE_M128, ATTR_NTT_LARGE_M128_2WG, ATTR_MANY_SORT1, ATTR_TAIL_ROW, ATTR_COARSE_STAGED4, ATTR_COARSE_STAGED8, ATTR_COUNT };
+enum AttrFlag { ATTR_FINE_SCATTER4 = 0, ATTR_FINE_SCATTER8, ATTR_DIGITS_LDS, ATTR_SMALL_MSM, ATTR_NTT_LARGE_FR, ATTR_NTT_LARGE_M128, ATTR_NTT_LARGE_M128_2WG, ATTR_MANY_SORT1, ATTR_TAIL_ROW, ATTR_COARSE_STAGED4, ATTR_COARSE_STAGED8, ATTR_FINE_SORT, ATTR_COUNT };
 struct Context {
   bool ready = false;
   int index = 0;                 // position in the context table (keys the per-context caches of the other translation units)

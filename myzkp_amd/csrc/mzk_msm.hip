@@ -38,7 +38,7 @@ static const MsmKnobs& msm_knobs() {
                     tune_int("MZK_ACC_SEG", d.acc_seg), tune_int("MZK_COARSE_LOG_20", d.coarse_log_20),
                     tune_int("MZK_COARSE_LOG_17", d.coarse_log_17), tune_int("MZK_PER_FINE", d.per_fine), tune_int("MZK_SORT_SCAN_FREE", d.sort_scan_free),
                     tune_int("MZK_COMBINE_WIDE_MIN_LOG", d.combine_wide_min_log), tune_int("MZK_COMBINE_FORM", d.combine_form),
-                    tune_int("MZK_COMBINE_LANE_TPB", d.combine_lane_tpb)};
+                    tune_int("MZK_COMBINE_LANE_TPB", d.combine_lane_tpb), tune_int("MZK_FINE_FUSED", d.fine_fused)};
   }();
   return k;
 }
@@ -592,7 +592,7 @@ __global__ __launch_bounds__(SORT2_THREADS) void k_coarse_scatter_staged(const u
 // plan from the bin boundaries (one load per lane and a block scan of two barriers): workgroup w -> (bin, slice); the histogram of bin b sits at
 // finehist[F P_b + f S_b + s] (P_b = slices before bin b), one flat exclusive scan as before; workgroups past the last slice zero
 // their block of the histogram, so the scan runs over the host's bound F * gridDim.
-struct FineSlice { int bin, s, Sb; u32 lo, hi, start; bool active; };
+// (FineSlice: mzk_msm_plan.h)
 // (sc, res: LDS scratch of the caller, SORT2_THREADS and 6 words -- no static LDS here: k_fine_scatter asks for all 160 KiB as dynamic)
 __device__ __forceinline__ FineSlice fine_plan(const u32* __restrict__ binbase, int nwg, int bins, int S, u32 cap, u32* sc, u32* res) {
   const int tid = threadIdx.x;
@@ -628,6 +628,27 @@ __device__ __forceinline__ FineSlice fine_plan(const u32* __restrict__ binbase, 
   r.start = res[3];
   r.lo = res[3] + (u32)(L * (u64)r.s / (u64)r.Sb);
   r.hi = res[3] + (u32)(L * (u64)(r.s + 1) / (u64)r.Sb);
+  return r;
+}
+// The same for the extra workgroups of the fused form (fine_slice_of_bin, mzk_msm_plan.h): extra workgroup j -> the slice of an
+// over-full bin, or nothing.  bound: the bins + 1 bin starts.  sc: SORT2_THREADS / 64 + 1 words, res: 7.
+__device__ __forceinline__ FineSlice fine_fused_slice(const u32* __restrict__ bound, int bins, u32 cap, u32 j, u32* sc, u32* res) {
+  const int tid = threadIdx.x;
+  u32 start = 0, len = 0;
+  if (tid < bins) {
+    start = bound[tid];
+    len = bound[tid + 1] - start;
+  }
+  if (tid == 0) res[0] = 0u;
+  const u32 excl = block_excl_scan<SORT2_THREADS>(fine_bin_slices(len, cap), sc, nullptr);      // (its barriers also order res[0])
+  FineSlice mine;
+  if (tid < bins && fine_slice_of_bin(j, tid, start, len, excl, cap, &mine)) {
+    res[0] = 1u; res[1] = (u32)mine.bin; res[2] = (u32)mine.s; res[3] = (u32)mine.Sb; res[4] = mine.lo; res[5] = mine.hi; res[6] = mine.start;
+  }
+  __syncthreads();
+  FineSlice r;
+  r.active = res[0] != 0u;
+  r.bin = (int)res[1]; r.s = (int)res[2]; r.Sb = (int)res[3]; r.lo = res[4]; r.hi = res[5]; r.start = res[6];
   return r;
 }
 constexpr int FINE_UNROLL = 8;
@@ -711,7 +732,7 @@ template <class REC>
 __global__ __launch_bounds__(SORT2_THREADS) void k_fine_scatter(const typename REC::T* __restrict__ tmp, const u32* __restrict__ binbase, int nwg, int F,
                                                                  int S, int fb, const u32* __restrict__ finebase, u32* __restrict__ offsets,
                                                                  u32* __restrict__ entries, size_t nbuckets, int bins, u32 cap, const u32* __restrict__ bucket_tot,
-                                                                 u32* __restrict__ bucket_cur) {
+                                                                 u32* __restrict__ bucket_cur, int fused) {
   extern __shared__ u32 lds_fs[];
   u32* gbase = lds_fs;                 // [F]   global position of the next entry of bucket f written by this workgroup
   u32* cnt = gbase + F;                // [F]   records of bucket f in the current round
@@ -720,9 +741,11 @@ __global__ __launch_bounds__(SORT2_THREADS) void k_fine_scatter(const typename R
   u32* spay = scan + SORT2_THREADS;    // [STAGE_CAP] staged payloads, bucket-sorted
   unsigned short* skey = reinterpret_cast<unsigned short*>(spay + STAGE_CAP);   // [STAGE_CAP] their buckets
   const int tid = threadIdx.x;
-  const FineSlice p = fine_plan(binbase, nwg, bins, S, cap, scan, gbase);
+  // fused: the second launch behind k_fine_sort -- workgroup j is extra workgroup j of that launch, a slice of an over-full bin which it
+  // counted there; on uniform scalars there is none and every workgroup returns here
+  const FineSlice p = fused ? fine_fused_slice(binbase, bins, cap, blockIdx.x, scan, gbase) : fine_plan(binbase, nwg, bins, S, cap, scan, gbase);
   __syncthreads();                     // (gbase is the plan's scratch until here)
-  if (blockIdx.x == 0 && tid == 0) offsets[nbuckets] = bucket_tot ? binbase[(size_t)bins * nwg] : finebase[(size_t)F * gridDim.x];   // total entries
+  if (!fused && blockIdx.x == 0 && tid == 0) offsets[nbuckets] = bucket_tot ? binbase[(size_t)bins * nwg] : finebase[(size_t)F * gridDim.x];   // total entries
   if (!p.active) return;
   const size_t hbase = (size_t)F * (blockIdx.x - (u32)p.s);
   if (bucket_tot) {
@@ -792,6 +815,119 @@ __global__ __launch_bounds__(SORT2_THREADS) void k_fine_scatter(const typename R
     }
     __syncthreads();
     for (int f = tid; f < F; f += SORT2_THREADS) gbase[f] += cnt[f];
+    __syncthreads();
+  }
+}
+
+// The fine level in ONE pass over the coarse-sorted records (4-byte records; the plan: mzk_msm_plan.h, "the fused fine level").
+// k_fine_count read a bin only to tell k_fine_scatter where the bin's buckets begin, because a bin was cut into slices that needed each
+// other's counts.  Here workgroup b < bins owns bin b whole: its lanes load all records at once, FINE_REGS each, count them into cnt[F]
+// and keep the rank every atomic returns; the exclusive prefix of the counts is the bin's bucket offsets, and prefix + rank is a
+// record's place in the bin -- 16 bits, two to a register beside the records.  The records then leave through an LDS window of
+// 2^FINE_WIN_LOG places per round: every lane drops the records whose place falls into the round's window, and the window is copied
+// out whole, consecutive lanes to consecutive entries.  Nothing is read twice, no counter outside the workgroup is touched.
+// A bin above FINE_BIN_CAP records is left alone by its workgroup; the extra workgroups in front of the bins' count its slices as
+// k_fine_count does (finehist, bucket_tot), and the k_fine_scatter launch that follows places them.  No workgroup waits for another.
+// __launch_bounds__(.., 8): 64 registers, two workgroups per CU -- 512 bins are one round of 256 CUs.
+static_assert(FINE_LANES == SORT2_THREADS && FINE_SORT_F_MAX <= STAGE_F_MAX, "k_fine_sort shares the fine kernels' workgroup and bucket range");
+constexpr size_t fine_sort_lds_bytes(int F) { return ((size_t)F + SORT2_THREADS / 64 + 1 + 7 + ((size_t)1 << FINE_WIN_LOG)) * 4; }
+__global__ __launch_bounds__(SORT2_THREADS, 8) void k_fine_sort(const u32* __restrict__ tmp, const u32* __restrict__ bound, int F, int fb, int bins, u32 cap,
+                                                                 u32* __restrict__ offsets, u32* __restrict__ entries, size_t nbuckets,
+                                                                 u32* __restrict__ finehist, u32* __restrict__ bucket_tot) {
+  extern __shared__ u32 lds_fine[];
+  u32* cnt = lds_fine;                       // [F] records per bucket, then their exclusive prefix
+  u32* sc = cnt + F;                         // [SORT2_THREADS / 64 + 1] block-scan scratch
+  u32* res = sc + SORT2_THREADS / 64 + 1;    // [7] an extra workgroup's slice
+  u32* win = res + 7;                        // [1 << FINE_WIN_LOG] the round's entries, in place
+  constexpr u32 WIN = 1u << FINE_WIN_LOG, NOWHERE = 0xffffu, NO_RECORD = 0xffffffffu;      // (no record: the plan keeps the references below 2^(31 - fb) - 1)
+  constexpr int NPOS = (FINE_REGS + 1) / 2;
+  const u32 tid = threadIdx.x, fmask = (u32)F - 1u;
+  u32 bin;                                   // (or the extra workgroup's index; they come first: the slices of a skewed input start at once, as in k_fine_count)
+  if (fine_wg_is_extra(blockIdx.x, gridDim.x - (u32)bins, &bin)) {      // a slice of an over-full bin: count it for the launch that follows
+    const FineSlice p = fine_fused_slice(bound, bins, cap, bin, sc, res);
+    if (!p.active) return;
+    for (u32 f = tid; f < (u32)F; f += SORT2_THREADS) cnt[f] = 0;
+    __syncthreads();
+    for (u32 base = p.lo + tid; base < p.hi; base += FINE_UNROLL * SORT2_THREADS) {
+      u32 f[FINE_UNROLL];
+#pragma unroll
+      for (int k = 0; k < FINE_UNROLL; k++) {
+        const u32 e = base + k * SORT2_THREADS;
+        f[k] = (e < p.hi) ? Rec4::fine(tmp[e], fmask, fb) : 0xffffffffu;
+      }
+#pragma unroll
+      for (int k = 0; k < FINE_UNROLL; k++) if (f[k] != 0xffffffffu) counter_inc_agg(cnt, f[k]);
+    }
+    __syncthreads();
+    const size_t hbase = (size_t)F * (blockIdx.x - (u32)p.s);        // F x the bin's first slice, as k_fine_scatter indexes it
+    for (u32 f = tid; f < (u32)F; f += SORT2_THREADS) {
+      const u32 v = cnt[f];
+      finehist[hbase + (size_t)f * p.Sb + p.s] = v;
+      if (v) atomicAdd(&bucket_tot[(size_t)p.bin * F + f], v);
+    }
+    return;
+  }
+  const u32 start = bound[bin], len = bound[bin + 1] - start;
+  if (bin == 0 && tid == 0) offsets[nbuckets] = bound[bins];      // total entries
+  if (len > FINE_BIN_CAP) return;
+  // (the records and their places fill 50 of the 64 registers: the pairs below are kept apart, sched_barrier, so that the results of
+  // no more than two LDS operations wait in registers of their own)
+  u32 r[FINE_REGS], pos[NPOS];
+  const u32* mine = tmp + start + tid;
+#pragma unroll
+  for (int k = 0; k < FINE_REGS; k++) {
+    r[k] = NO_RECORD;
+    if (fine_reg_record(k, tid) < len) r[k] = mine[k * FINE_LANES];
+  }
+  if (tid < (u32)F) cnt[tid] = 0;
+  __syncthreads();
+  const auto rank_of = [&](int k) { return r[k] != NO_RECORD ? counter_inc_agg(cnt, Rec4::fine(r[k], fmask, fb)) : NOWHERE; };
+#pragma unroll
+  for (int h = 0; h < NPOS; h++) {
+    const u32 even = rank_of(2 * h), odd = (2 * h + 1 < FINE_REGS) ? rank_of(2 * h + 1) : NOWHERE;
+    pos[h] = even | (odd << 16);
+    asm volatile("" : "+v"(pos[h]));      // (really packed: the compiler would otherwise carry both halves in registers of their own)
+    __builtin_amdgcn_sched_barrier(0);
+  }
+  __syncthreads();
+  // exclusive prefix of the counts in place (F <= SORT2_THREADS: a counter per lane): the bin's bucket offsets
+  {
+    const u32 v = tid < (u32)F ? cnt[tid] : 0u;
+    const u32 run = block_excl_scan<SORT2_THREADS>(v, sc, nullptr);
+    if (tid < (u32)F) {
+      cnt[tid] = run;
+      offsets[(size_t)bin * F + tid] = start + run;
+    }
+  }
+  __syncthreads();
+  const auto place_of = [&](int k, u32 rank) {
+    asm volatile("" : "+v"(r[k]));      // (the bucket is extracted again: kept from the count it would be a register more per record)
+    const u32 first = cnt[Rec4::fine(r[k], fmask, fb)];      // (an empty slot reads the last bucket's: no branch)
+    return rank == NOWHERE ? NOWHERE : first + rank;
+  };
+#pragma unroll
+  for (int h = 0; h < NPOS; h++) {
+    const u32 even = place_of(2 * h, pos[h] & 0xffffu), odd = (2 * h + 1 < FINE_REGS) ? place_of(2 * h + 1, pos[h] >> 16) : NOWHERE;
+    pos[h] = even | (odd << 16);
+    asm volatile("" : "+v"(pos[h]));
+    __builtin_amdgcn_sched_barrier(0);
+  }
+#pragma unroll
+  for (int k = 0; k < FINE_REGS; k++) r[k] = Rec4::payload(r[k], fb);      // (the bucket is in the place now)
+  for (u32 w0 = 0; w0 < len; w0 += WIN) {
+    const u32 q = w0 >> FINE_WIN_LOG;
+#pragma unroll
+    for (int h = 0; h < NPOS; h++) {
+      u32 both = pos[h];
+      asm volatile("" : "+v"(both));      // unpacked per round: hoisted out of the loop the 33 places would take registers of their own
+      const u32 even = both & 0xffffu, odd = both >> 16;
+      if ((even >> FINE_WIN_LOG) == q) win[even & (WIN - 1u)] = r[2 * h];
+      if (2 * h + 1 < FINE_REGS && (odd >> FINE_WIN_LOG) == q) win[odd & (WIN - 1u)] = r[2 * h + 1];
+    }
+    __syncthreads();
+    const u32 m = (len - w0 < WIN) ? len - w0 : WIN;
+#pragma unroll 2
+    for (u32 j = tid; j < m; j += SORT2_THREADS) entries[start + w0 + j] = win[j];
     __syncthreads();
   }
 }
@@ -1500,18 +1636,34 @@ static int sort_records(const MsmPlan& P, const SortBufs& a, hipStream_t s) {
   // bin boundaries as the fine kernels index them: the coarse scan's [bin][workgroup] prefix, or the scan-free form's bins + 1 starts
   const u32* bounds = a.bin_tot ? (const u32*)a.bin_start : (const u32*)a.binhist;
   const int bstride = a.bin_tot ? 1 : P.nwg;
+  const size_t scatter_lds = ((size_t)3 * P.F + SORT2_THREADS + STAGE_CAP) * 4 + (size_t)STAGE_CAP * 2;
+  bool& staged_attr = ctx().attr_done[sizeof(R) == 4 ? ATTR_FINE_SCATTER4 : ATTR_FINE_SCATTER8];     // per instantiation and context
+  if (P.F <= STAGE_F_MAX && !staged_attr) {
+    MZK_HIP(hipFuncSetAttribute((const void*)k_fine_scatter<REC>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    staged_attr = true;
+  }
+  if constexpr (sizeof(R) == 4) {
+    if (P.fine_fused) {      // one launch finishes every bin of ordinary size; the second places the slices of over-full bins (none: it is empty)
+      bool& attr = ctx().attr_done[ATTR_FINE_SORT];
+      if (!attr) {
+        MZK_HIP(hipFuncSetAttribute((const void*)k_fine_sort, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+        attr = true;
+      }
+      hipLaunchKernelGGL(k_fine_sort, dim3(P.fine_wgs), dim3(SORT2_THREADS), fine_sort_lds_bytes(P.F), s, (const u32*)a.tmp, (const u32*)a.bin_start, P.F, P.fb,
+                         (int)bins, P.slice_cap, a.offsets, a.entries, P.NBtot, a.finehist, a.bucket_tot);
+      if (P.fine_wgs > bins)
+        hipLaunchKernelGGL((k_fine_scatter<REC>), dim3(P.fine_wgs - bins), dim3(SORT2_THREADS), scatter_lds, s, (const R*)a.tmp, (const u32*)a.bin_start, 1, P.F,
+                           P.S, P.fb, (const u32*)a.finehist, a.offsets, a.entries, P.NBtot, (int)bins, P.slice_cap, (const u32*)a.bucket_tot, a.bucket_cur, 1);
+      MZK_HIP(hipGetLastError());
+      return MZK_OK;
+    }
+  }
   hipLaunchKernelGGL((k_fine_count<REC>), dim3(P.fine_wgs), dim3(SORT2_THREADS), 0, s, (const R*)a.tmp, bounds, bstride, P.F, P.S,
                      P.fb, a.finehist, (int)bins, P.slice_cap, a.bucket_tot);
   if (!P.fine_free) MZK_TRY(launch_exclusive_scan((const u32*)a.finehist, a.finehist, P.own.n_fine, a.scan3, s));
   if (P.F <= STAGE_F_MAX) {
-    const size_t lds = ((size_t)3 * P.F + SORT2_THREADS + STAGE_CAP) * 4 + (size_t)STAGE_CAP * 2;
-    bool& staged_attr = ctx().attr_done[sizeof(R) == 4 ? ATTR_FINE_SCATTER4 : ATTR_FINE_SCATTER8];     // per instantiation and context
-    if (!staged_attr) {
-      MZK_HIP(hipFuncSetAttribute((const void*)k_fine_scatter<REC>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-      staged_attr = true;
-    }
-    hipLaunchKernelGGL((k_fine_scatter<REC>), dim3(P.fine_wgs), dim3(SORT2_THREADS), lds, s, (const R*)a.tmp, bounds, bstride, P.F,
-                       P.S, P.fb, (const u32*)a.finehist, a.offsets, a.entries, P.NBtot, (int)bins, P.slice_cap, (const u32*)a.bucket_tot, a.bucket_cur);
+    hipLaunchKernelGGL((k_fine_scatter<REC>), dim3(P.fine_wgs), dim3(SORT2_THREADS), scatter_lds, s, (const R*)a.tmp, bounds, bstride, P.F,
+                       P.S, P.fb, (const u32*)a.finehist, a.offsets, a.entries, P.NBtot, (int)bins, P.slice_cap, (const u32*)a.bucket_tot, a.bucket_cur, 0);
   } else {
     hipLaunchKernelGGL((k_fine_scatter_direct<REC>), dim3(P.fine_wgs), dim3(SORT2_THREADS), 0, s, (const R*)a.tmp, bounds, bstride,
                        P.F, P.S, P.fb, (const u32*)a.finehist, a.offsets, a.entries, P.NBtot, (int)bins, P.slice_cap);

@@ -100,6 +100,93 @@ constexpr int HEAVY_HDR = SORT_CTR_AT + 2 * SORT_CTR_BINS;
 // (a multiple of four words: the scratch records behind the list are read and written as uint4)
 constexpr size_t heavy_list_words(size_t max_heavy) { return (HEAVY_HDR + 2 * max_heavy + 2 + 3) & ~(size_t)3; }
 constexpr size_t heavy_total_words(size_t max_heavy) { return heavy_list_words(max_heavy) + (size_t)HEAVY_GRID * 32 + 8; }
+// One fine kernel per bin (k_fine_sort, mzk_msm.hip): a workgroup of FINE_LANES lanes holds a whole bin in registers, FINE_REGS records
+// per lane.  The capacity is sized for the fullest bin of a uniform 2^20-pair commit against 17-bit tables, not for the mean: 512 bins of
+// 128 buckets hold 28 672 records of the fourteen full windows, and the bins of the top window's digits (they stop at 49 554: bins
+// 0 - 387) another ~2 708 -- 31 380 with a standard deviation of 177.  Eight deviations above that are 32 797: 33 records per lane
+// (33 792); 32 (32 768) are 7.8.  33 records and their 17 words of packed places still leave the kernel inside the 64 registers that
+// keep two workgroups on a CU (tools/kernel_resources.py: 64 VGPRs, no scratch).
+constexpr int FINE_LANES = 1024;
+constexpr int FINE_REGS = 33;
+constexpr uint32_t FINE_BIN_CAP = (uint32_t)FINE_REGS * FINE_LANES;
+constexpr int FINE_SORT_F_MAX = 1024;      // the most buckets per bin k_fine_sort takes: its counters + a 16 Ki-record window, twice per CU
+constexpr int FINE_WIN_LOG = 14;           // log2 of the records it stages per round
+static_assert(FINE_BIN_CAP + (1u << FINE_WIN_LOG) <= 0xffffu, "a record's position in its bin packs into 16 bits, 0xffff falls into no round");
+
+// code the kernels and the host run alike (the host: tests/hostcheck/*_shim.cpp)
+#if defined(__HIPCC__)
+#define MZK_HD __host__ __device__ __forceinline__
+#else
+#define MZK_HD inline
+#endif
+
+// ---- the fused fine level: which workgroup of k_fine_sort does what --------------------------------------------------------------------
+// The last `bins` workgroups own a bin each, the records [bound[b], bound[b + 1]) of the coarse sort: up to FINE_BIN_CAP of them a
+// workgroup sorts alone, from registers.  A fuller bin (skewed scalars: bytes, repeated values, short coefficients) it leaves to SLICES,
+// cut as fine_plan cuts them: ceil(len / cap) equal parts, one extra workgroup each.  The extra workgroups stand in front of the bins',
+// in bin order -- extra workgroup j is slice j - X_b of the bin b with X_b <= j < X_b + slices(b), X the exclusive prefix of the slice
+// counts -- and only count in k_fine_sort; the second launch (k_fine_scatter over the extra workgroups alone) places their records.
+// Lane b of an extra workgroup evaluates bin b.
+struct FineSlice { int bin, s, Sb; uint32_t lo, hi, start; bool active; };
+// register k of lane `lane` of a whole-bin workgroup holds record k FINE_LANES + lane of the bin, if the bin has that many
+MZK_HD uint32_t fine_reg_record(int k, uint32_t lane) { return (uint32_t)k * FINE_LANES + lane; }
+// workgroup w of a grid of bins + extra: true = extra workgroup *idx, false = the workgroup of bin *idx
+MZK_HD bool fine_wg_is_extra(uint32_t w, uint32_t extra, uint32_t* idx) { *idx = w < extra ? w : w - extra; return w < extra; }
+MZK_HD uint32_t fine_bin_slices(uint32_t len, uint32_t cap) { return len > FINE_BIN_CAP ? (uint32_t)(((uint64_t)len + cap - 1) / cap) : 0u; }
+// records [lo, hi) of slice s of Sb: the slices of a bin tile it exactly
+MZK_HD void fine_slice_bounds(uint32_t start, uint32_t len, uint32_t s, uint32_t Sb, uint32_t* lo, uint32_t* hi) {
+  *lo = start + (uint32_t)((uint64_t)len * s / Sb);
+  *hi = start + (uint32_t)((uint64_t)len * (s + 1) / Sb);
+}
+// lane `bin`'s answer for extra workgroup j: true, and the slice, when j is one of this bin's (excl = X_bin)
+MZK_HD bool fine_slice_of_bin(uint32_t j, int bin, uint32_t start, uint32_t len, uint32_t excl, uint32_t cap, FineSlice* out) {
+  const uint32_t Sb = fine_bin_slices(len, cap);
+  if (j < excl || j - excl >= Sb) return false;
+  out->bin = bin, out->s = (int)(j - excl), out->Sb = (int)Sb, out->start = start, out->active = true;
+  fine_slice_bounds(start, len, j - excl, Sb, &out->lo, &out->hi);
+  return true;
+}
+// The most slices the over-full bins of E records in `bins` bins can need -- the extra workgroups the launch provides.  A bin opens at
+// FINE_BIN_CAP + 1 records with a = ceil((CAP + 1) / cap) slices, its next slice comes a cap - CAP records later and every further one
+// cap records later; with m bins open the rest of the records buys slices at those two prices.  The best m is found by trying all.
+static inline size_t fine_max_slices(size_t E, size_t bins, uint32_t cap) {
+  const size_t open = (size_t)FINE_BIN_CAP + 1, a = (open + cap - 1) / cap, first = a * cap - FINE_BIN_CAP;
+  size_t best = 0;
+  for (size_t m = 1; m <= bins && m * open <= E; m++) {
+    const size_t rest = E - m * open, cheap = rest / first < m ? rest / first : m;
+    const size_t v = m * a + cheap + (rest - cheap * first) / cap;
+    if (v > best) best = v;
+  }
+  return best;
+}
+// The fullest bin that uniform scalars make, and whether it stays eight standard deviations (of a count: its root) below the capacity.
+// Window w spreads its entries evenly over the digit magnitudes it can take -- 2^(c-1), fewer in the top window, whose digits stop at
+// the top bits of the modulus (of 2^126 after the GLV split) -- so the bin of the smallest magnitudes is the fullest of its bucket set.
+constexpr uint64_t FR_TOP64 = 0x30644e72e131a029ull;      // bits 192 .. 255 of the scalar field's modulus
+static inline size_t fine_uniform_max_bin(const DigitLayout& L, size_t n, size_t F) {
+  const int nsets = L.merged ? L.sets : L.nwin;
+  double best = 0;
+  for (int set = 0; set < nsets; set++) {
+    double sum = 0;
+    for (int w = 0; w < L.nwin; w++) {
+      if ((L.merged ? w % L.sets : w) != set) continue;
+      double range = (double)((uint64_t)1 << (L.c - 1));
+      if (w == L.nwin - 1) {
+        const int low = L.c * w, top = (L.glv ? GLV_MAG_BITS : 256) - low;      // bits of the scalar above the window's lowest
+        const double r = L.glv ? (double)((uint64_t)1 << (top > 0 ? top : 0)) : (double)(FR_TOP64 >> (64 - top)) + 1;
+        if (r < range) range = r;
+      }
+      sum += (double)(L.glv ? 2 * n : n) * (range > (double)F ? (double)F / range : 1.0);
+    }
+    if (sum > best) best = sum;
+  }
+  return (size_t)best + 1;
+}
+static inline bool fine_bins_fit(size_t fullest) {
+  if (fullest >= FINE_BIN_CAP) return false;
+  const size_t margin = FINE_BIN_CAP - fullest;
+  return margin * margin >= 64 * fullest;
+}
 
 // ---- the plan ----------------------------------------------------------------------------------------------------------------------
 // The MSM's tuning switches: the shipped values here; the tuning build reads MZK_<NAME> over them, in this order (mzk_msm.hip).
@@ -115,6 +202,7 @@ struct MsmKnobs {
   int combine_wide_min_log = 17;  // MZK_COMBINE_WIDE_MIN_LOG
   int combine_form = 0;           // MZK_COMBINE_FORM: 1 = a DPP quad per bucket, 2 = a lane per bucket, whatever the plan would pick
   int combine_lane_tpb = 256;     // MZK_COMBINE_LANE_TPB: lanes per workgroup of the look-ahead lane form (64, 128: the measurement behind 256)
+  int fine_fused = -1;            // MZK_FINE_FUSED: 0 = k_fine_count + k_fine_scatter, 1 = k_fine_sort wherever its records and counters fit, however full the bins
 };
 
 enum class MsmPath { SmallScan, SmallSort, TwoLevel, LdsOnePass, Atomic };
@@ -135,6 +223,7 @@ struct MsmPlan {
   int cl = 0, F = 0, fb = 0, key_shift = 0, S = 0, nwg = 0;
   uint32_t fine_mask = 0, slice_cap = 0;
   unsigned fine_wgs = 0;
+  bool fine_fused = false;                     // fine level: k_fine_sort, one workgroup per bin (+ fine_wgs - bins for the slices of over-full bins)
   size_t per_wg = 0;                           // LDS path: pairs per workgroup
   bool compact = false, coarse_free = false, fine_free = false, scatter_staged = false;   // 4-byte records, scan-free levels, staged scatter
   int coarse_c = 0;                            // the compile-time merged width of the coarse count / scatter kernels (0: any layout)
@@ -303,17 +392,23 @@ static inline MsmPlan msm_plan(size_t n, size_t n_shape, size_t n_alloc, int poi
   P.fine_free = (kn.sort_scan_free & 2) != 0 && P.F <= STAGE_F_MAX;
   P.coarse_c = (plain_merged && (L.c == 16 || L.c == 17 || L.c == 20)) ? L.c : 0;     // the default widths by SRS size
   P.scatter_staged = P.coarse_c != 0;
+  // Fine level in one kernel per bin (k_fine_sort) where a workgroup holds a bin: 4-byte records, both levels scan-free, counters and a
+  // round's window in half a CU's LDS, and the fullest bin of uniform scalars eight deviations inside the capacity.  Bins far above it keep
+  // the two launches (2^24 pairs at 20 bits: ~213 000 records per bin), and so does chunk mode, whose buffers are sized once for chunks
+  // of several lengths.  The grid: a workgroup per bin and one per slice that over-full bins can need (fine_max_slices).
+  // (references strictly below 2^(31 - fb) - 1: the all-ones word is no record, it marks a register that holds none)
+  const bool fused_can = !chunks && P.compact && ref_max < ((size_t)1 << (31 - P.fb)) && P.coarse_free && P.fine_free && P.F <= FINE_SORT_F_MAX;
+  P.fine_fused = fused_can && kn.fine_fused != 0 && (kn.fine_fused > 0 || fine_bins_fit(fine_uniform_max_bin(L, n, (size_t)P.F)));
+  if (P.fine_fused) {
+    P.fine_wgs = (unsigned)(cbins + fine_max_slices(E_max, cbins, P.slice_cap));
+    P.own.n_fine = P.alloc.n_fine = (size_t)P.F * P.fine_wgs;
+  }
   return msm_sized(P, regions);
 }
 
 // ---- the segment walk of k_seg_accumulate ------------------------------------------------------------------------------------------
 // Which entry a lane adds, which loads it has in flight meanwhile and where it stops -- the index logic of the kernel's loop, templated
 // over its loads so that the host runs the same code over arrays of exactly the kernel's sizes (tests/hostcheck/seg_walk_shim.cpp).
-#if defined(__HIPCC__)
-#define MZK_HD __host__ __device__ __forceinline__
-#else
-#define MZK_HD inline
-#endif
 constexpr uint32_t MANY_SENTINEL = 0xffffffffu;      // filler behind a polynomial's real entries (k_many_sort1): never a table row
 
 // The segment of lane t: entries [e0, e1) of `total`; false when the lane has none (it must not load anything then).
