@@ -1315,7 +1315,9 @@ static int run_in_flight(size_t count, int max_in_flight, hipStream_t caller, JO
     if (!scope.ok) { rc = MZK_E_ARG; break; }
     hipStream_t ls = k == 0 ? caller : ctx().stream;
     WsGuard wsg(ls);
+    ctx().lanes_in_flight = K;       // the job's launches are chosen for a chip that other jobs occupy (launch_halving_steps)
     rc = job(i, ls);
+    ctx().lanes_in_flight = 1;
   }
   // join: the caller's stream continues after every lane's last job (also after a failure: nothing may be left running
   // behind the caller's back)

@@ -61,6 +61,7 @@ struct Context {
   // stream records ws_event on ws_last and waits for it before touching the slots (WsGuard).
   hipEvent_t ws_event = nullptr;
   hipEvent_t fork_event = nullptr, join_event = nullptr;     // mzk_kzg_commit_srs_batch_dev: caller stream -> lanes -> caller stream
+  int lanes_in_flight = 1;       // > 1 while run_in_flight (mzk_api.hip) enqueues a job here that runs beside the other lanes' jobs
   hipStream_t ws_last = nullptr;
   bool ws_used = false;
   bool attr_done[ATTR_COUNT] = {};   // hipFuncSetAttribute(MaxDynamicSharedMemorySize) applied on this context's device

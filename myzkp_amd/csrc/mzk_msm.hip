@@ -16,7 +16,7 @@
 //   3. k_digits_scatter[_lds] counting-sort placement of (point reference, sign), no atomics
 //   4. k_seg_accumulate    one lane per fixed-size segment of the sorted entries, XYZZ += affine
 //                          (madd-2008-s), exception-complete; k_seg_combine sums a bucket's partials
-//   5. k_halve_step* / k_halve_multi / k_reduce_tail_row   sum_b (b+1) B_b per bucket set by in-place halving
+//   5. k_halve_step* / k_halve_multi / k_halve_multi_row / k_reduce_tail_row   sum_b (b+1) B_b per bucket set by in-place halving
 //   6. k_window_combine_row (mzk_msm_row.hip)  Horner over the bucket sets, XYZZ -> affine (one inversion)
 #include <stdlib.h>
 #include <type_traits>
@@ -38,7 +38,8 @@ static const MsmKnobs& msm_knobs() {
                     tune_int("MZK_ACC_SEG", d.acc_seg), tune_int("MZK_COARSE_LOG_20", d.coarse_log_20),
                     tune_int("MZK_COARSE_LOG_17", d.coarse_log_17), tune_int("MZK_PER_FINE", d.per_fine), tune_int("MZK_SORT_SCAN_FREE", d.sort_scan_free),
                     tune_int("MZK_COMBINE_WIDE_MIN_LOG", d.combine_wide_min_log), tune_int("MZK_COMBINE_FORM", d.combine_form),
-                    tune_int("MZK_COMBINE_LANE_TPB", d.combine_lane_tpb), tune_int("MZK_FINE_FUSED", d.fine_fused)};
+                    tune_int("MZK_COMBINE_LANE_TPB", d.combine_lane_tpb), tune_int("MZK_FINE_FUSED", d.fine_fused),
+                    tune_int("MZK_HALVE_ROW", d.halve_row)};
   }();
   return k;
 }
@@ -1280,10 +1281,12 @@ __global__ __launch_bounds__(128) void k_halve_step(u32* __restrict__ buckets, i
 // step leaves its upper half behind as a new block; the others only fold).  One workgroup loads its 2^s records (<= 32 KiB)
 // into LDS, runs the s steps between barriers (DPP-quad additions, 128 quads) and stores back the s + 1 (or one) records
 // that are still live -- instead of s dependent launches at ~6-10 us each whatever they hold (the 2^16 buckets of the
-// 17-bit commit: thirteen launches, 91 us; now two launches of eight steps each).
+// 17-bit commit: thirteen launches, 91 us; then two launches of eight steps each; now the second of them is two row-form launches of
+// four steps, k_halve_multi_row in mzk_msm_row.hip, which runs the same cut through the templates of mzk_msm_plan.h).
 constexpr int HMULTI_THREADS = 512;
 constexpr int HMULTI_QUADS = HMULTI_THREADS / 4;
-constexpr int HMULTI_MAX_S = 8;
+constexpr int HMULTI_MAX_S = HALVE_MULTI_MAX_S;
+static_assert(((size_t)128 << HMULTI_MAX_S) <= 64 * 1024, "a workgroup's records fit its dynamic LDS without an attribute");
 __global__ __launch_bounds__(HMULTI_THREADS) void k_halve_multi(u32* __restrict__ buckets, int lgB, int t0, int s) {
   extern __shared__ __attribute__((aligned(16))) u32 lds_hm[];
   const int lgs = lgB - t0 - s;                    // log2 of the stride
@@ -1476,6 +1479,7 @@ static_assert(254 / 8 + 1 <= 32, "window hit masks are 32 bits");
 
 // mzk_msm_row.hip: the tails on row-cooperative group operations (one point operation per wave)
 int launch_reduce_tail_row(u32* buckets, int lgB, int t_start, int sets, u32* out, int finish_affine, hipStream_t s);
+int launch_halve_multi_row(u32* buckets, int lgB, int t0, int steps, size_t grid, int sets, hipStream_t s);
 int launch_window_combine_row(const u32* wsum, int nwin, int c, int out_xyzz, u32* out, hipStream_t s);
 int launch_fold_partials_row(const u32* partials, int count, u32* out, hipStream_t s);
 // The single-workgroup tail takes over once a halving step is at most this wide: a dependent launch costs ~6 us whatever runs in
@@ -1486,34 +1490,28 @@ static size_t row_tail_max_ops() {
   return v < 1 ? 1 : v;
 }
 
-// The halving steps that run as launches of their own, in front of the single-workgroup tail: one lane per addition while a step is
-// throughput-bound (>= 2^16 additions over all sets), then k_halve_multi, up to eight steps per launch, until a step is at most
-// `tail_max` additions wide.  *t_next = the first step left to the tail (lgB: all done, the tail only forms the weighted sum).
+// The halving steps that run as launches of their own, in front of the single-workgroup tail: the list is halve_plan's
+// (mzk_msm_plan.h), a function of the layout, the CU count and the switches alone.  *t_next = the first step left to the tail
+// (lgB: all done, the tail only forms the weighted sum).
 static int launch_halving_steps(u32* buckets, int lgB, int sets, size_t tail_max, int* t_next, hipStream_t s) {
-  int t = 0;
-  while (t < lgB && ((size_t)(t + 1) << (lgB - t - 1)) > tail_max) {
-    const size_t total = (size_t)(t + 1) << (lgB - t - 1);
-    if (total * (size_t)sets >= ((size_t)1 << 16)) {
-      hipLaunchKernelGGL(k_halve_step_wide, dim3((unsigned)((total + 127) / 128), (unsigned)sets), dim3(128), 0, s, buckets, lgB, t);
-      t++;
-      continue;
-    }
-    // several steps per launch only in the latency regime -- at most one workgroup per CU.  Its workgroups are unequal (region 0 carries
-    // t + 1 times the additions of the others) and stay where they were placed, so with more of them than CUs the launches of ONE step,
-    // which spread every step's additions over the whole chip, are faster (generic 2^20, 384 workgroups: bucket reduction 0.204 -> 0.222 ms;
-    // 256 x 2^10 at 11 bits 0.196 -> 0.270; profiles/round6_halving_multi_and_rec4_ab.txt)
-    const int st = (lgB - t < HMULTI_MAX_S) ? lgB - t : HMULTI_MAX_S;
-    const size_t multi_wgs = ((size_t)(t + 1) << (lgB - t - st)) * (size_t)sets;
-    if (multi_wgs > (size_t)ctx().num_cu) {
-      hipLaunchKernelGGL(k_halve_step, dim3((unsigned)((4 * total + 127) / 128), (unsigned)sets), dim3(128), 0, s, buckets, lgB, t);
-      t++;
-    } else {
-      hipLaunchKernelGGL(k_halve_multi, dim3((unsigned)((size_t)(t + 1) << (lgB - t - st)), (unsigned)sets), dim3(HMULTI_THREADS), ((size_t)128 << st), s, buckets, lgB, t, st);
-      t += st;
+  // The row launches shorten the chain by spreading it over many CUs (144 workgroups of eight waves at 2^16 buckets), which pays on an
+  // idle chip.  With several commits in flight the reduction runs under another commit's accumulate, whose waves own every SIMD until
+  // they retire: there the nine workgroups of the quad form find room sooner (profiles/halve_row_ab.txt), so a job enqueued by
+  // run_in_flight keeps them.  MZK_HALVE_ROW = 2 of the tuning build takes the row launches there too.
+  const int row = msm_knobs().halve_row;
+  const HalvePlan H = halve_plan(lgB, sets, ctx().num_cu, tail_max, row == 2 || (row == 1 && ctx().lanes_in_flight <= 1));
+  for (int i = 0; i < H.count; i++) {
+    const HalveLaunch& l = H.l[i];
+    const dim3 grid((unsigned)l.grid, (unsigned)sets);
+    switch (l.kind) {
+      case HALVE_STEP_WIDE: hipLaunchKernelGGL(k_halve_step_wide, grid, dim3(128), 0, s, buckets, lgB, l.t); break;
+      case HALVE_STEP_QUAD: hipLaunchKernelGGL(k_halve_step, grid, dim3(128), 0, s, buckets, lgB, l.t); break;
+      case HALVE_MULTI_QUAD: hipLaunchKernelGGL(k_halve_multi, grid, dim3(HMULTI_THREADS), ((size_t)128 << l.steps), s, buckets, lgB, l.t, l.steps); break;
+      default: MZK_TRY(launch_halve_multi_row(buckets, lgB, l.t, l.steps, l.grid, sets, s)); break;
     }
   }
   MZK_HIP(hipGetLastError());
-  *t_next = t;
+  *t_next = H.t_next;
   return MZK_OK;
 }
 

@@ -203,6 +203,7 @@ struct MsmKnobs {
   int combine_form = 0;           // MZK_COMBINE_FORM: 1 = a DPP quad per bucket, 2 = a lane per bucket, whatever the plan would pick
   int combine_lane_tpb = 256;     // MZK_COMBINE_LANE_TPB: lanes per workgroup of the look-ahead lane form (64, 128: the measurement behind 256)
   int fine_fused = -1;            // MZK_FINE_FUSED: 0 = k_fine_count + k_fine_scatter, 1 = k_fine_sort wherever its records and counters fit, however full the bins
+  int halve_row = 1;              // MZK_HALVE_ROW: 0 = the late halving steps stay DPP-quad launches (k_halve_multi), no k_halve_multi_row; 1 = row launches unless commits are in flight; 2 = always
 };
 
 enum class MsmPath { SmallScan, SmallSort, TwoLevel, LdsOnePass, Atomic };
@@ -567,6 +568,88 @@ MZK_HD void walk_digits_merged(const u32* w, size_t table_stride, size_t i, Emit
     const u32 mag = neg ? (HALF - 1u) - v : v - (HALF - 1u);
     emit(win, mag - 1u, (u32)((size_t)win * table_stride + i) | ((u32)neg << 31));
   }
+}
+
+// ---- the halving steps of the bucket reduction: which records a step adds, which launches run the steps ------------------------------------
+// (the recursion: mzk_msm.hip, section 5).  Step t of a set of 2^lgB buckets has (t + 1) << (lgB - t - 1) additions; addition `id`
+// is buf[*lo] += buf[*hi]: region a = id >> lgh folds its upper half onto its lower half, region 0 at 0, region a >= 1 at 2^(lgB - a).
+MZK_HD void halve_indices(int lgB, int t, size_t id, size_t* lo, size_t* hi) {
+  const int lgh = lgB - t - 1;
+  const size_t a = id >> lgh, j = id & (((size_t)1 << lgh) - 1);
+  *lo = ((a == 0) ? 0 : ((size_t)1 << (lgB - a))) + j;
+  *hi = *lo + ((size_t)1 << lgh);
+}
+// SEVERAL steps per launch (k_halve_multi, k_halve_multi_row): steps t0 .. t0 + s - 1 pair no two indices closer than 2^lgs,
+// lgs = lgB - t0 - s, so region 0 = [0, 2^(lgB - t0)) and the regions a = 1 .. t0 fall apart into 2^lgs problems of 2^s records
+// each, one workgroup per problem: local record k is buf[base + (k << lgs)].  Region 0's problems leave every step's upper half
+// behind as a new block (local block aa >= 1 at 2^(s - aa): the global region t0 + aa), the others only fold.
+constexpr int HALVE_MULTI_MAX_S = 8;      // k_halve_multi: 2^8 records = 32 KiB of LDS, DPP-quad additions
+constexpr int HALVE_ROW_MAX_S = 4;        // k_halve_multi_row: at most 8 additions per step, one per wave
+struct HalveWg { int region, lgs; size_t base; };
+MZK_HD size_t halve_multi_grid(int lgB, int t0, int s) { return (size_t)(t0 + 1) << (lgB - t0 - s); }      // workgroups per bucket set
+MZK_HD HalveWg halve_multi_wg(int lgB, int t0, int s, size_t wg) {
+  HalveWg g;
+  g.lgs = lgB - t0 - s;
+  g.region = (int)(wg >> g.lgs);
+  g.base = ((g.region == 0) ? 0 : ((size_t)1 << (lgB - g.region))) + (wg & (((size_t)1 << g.lgs) - 1));
+  return g;
+}
+// additions of local step tl = 0 .. s - 1, and the local records of addition `id`: the single-step rule on 2^s records
+MZK_HD int halve_multi_ops(int region, int s, int tl) { return ((region == 0) ? tl + 1 : 1) << (s - tl - 1); }
+MZK_HD void halve_multi_pair(int s, int tl, int id, int* lo, int* hi) {
+  const int lgh = s - tl - 1, aa = id >> lgh;
+  *lo = ((aa == 0) ? 0 : (1 << (s - aa))) + (id & ((1 << lgh) - 1));
+  *hi = *lo + (1 << lgh);
+}
+// what later steps and the tail still read: local 0 and, in region 0, the heads 2^(e - 1) of the blocks the steps left behind
+MZK_HD int halve_multi_live(int region, int s) { return (region == 0) ? s + 1 : 1; }
+MZK_HD int halve_multi_live_at(int e) { return (e == 0) ? 0 : (1 << (e - 1)); }
+
+// The launches in front of the single-workgroup tail (launch_halving_steps, mzk_msm.hip): one lane per addition while a step is
+// throughput-bound (>= 2^16 additions over all sets), then DPP-quad additions -- k_halve_multi, up to eight steps per launch, in the
+// latency regime of at most one workgroup per CU, launches of one step above it -- until a step is at most `tail_max` additions wide.
+// Once a k_halve_multi launch has left at most eight steps and launches of up to four steps need at most one workgroup per CU, the
+// rest runs on row operations (k_halve_multi_row): ceil(steps / 4) launches, four steps each and the remainder last; such a
+// workgroup has at most eight additions per step, one per wave, and a row addition is a third of the quad form's chain.
+enum { HALVE_STEP_WIDE = 0, HALVE_STEP_QUAD = 1, HALVE_MULTI_QUAD = 2, HALVE_MULTI_ROW = 3 };
+struct HalveLaunch { int kind, t, steps; size_t grid; };      // grid: workgroups per bucket set (x sets)
+struct HalvePlan {
+  int count = 0, t_next = 0;                                  // t_next: the first step left to the tail (lgB: the tail only forms the weighted sum)
+  HalveLaunch l[32];                                          // (a launch takes at least one of the lgB < 32 steps)
+};
+static inline HalvePlan halve_plan(int lgB, int sets, int num_cu, size_t tail_max, int halve_row) {
+  HalvePlan H;
+  if (lgB < 0 || lgB >= 32) return H;
+  auto put = [&H](int kind, int t, int steps, size_t grid) { H.l[H.count++] = HalveLaunch{kind, t, steps, grid}; };
+  int t = 0;
+  bool multi_ran = false;
+  while (t < lgB && ((size_t)(t + 1) << (lgB - t - 1)) > tail_max) {
+    const size_t total = (size_t)(t + 1) << (lgB - t - 1);
+    if (total * (size_t)sets >= ((size_t)1 << 16)) { put(HALVE_STEP_WIDE, t, 1, (total + 127) / 128); t++; continue; }
+    // several steps per launch only with at most one workgroup per CU.  Its workgroups are unequal (region 0 carries t + 1 times the
+    // additions of the others) and stay where they were placed, so with more of them than CUs the launches of ONE step, which spread every
+    // step's additions over the whole chip, are faster (generic 2^20, 384 workgroups: bucket reduction 0.204 -> 0.222 ms; 256 x 2^10 at
+    // 11 bits 0.196 -> 0.270; profiles/round6_halving_multi_and_rec4_ab.txt)
+    const int left = lgB - t, st = left < HALVE_MULTI_MAX_S ? left : HALVE_MULTI_MAX_S;
+    if (halve_multi_grid(lgB, t, st) * (size_t)sets > (size_t)num_cu) { put(HALVE_STEP_QUAD, t, 1, (4 * total + 127) / 128); t++; continue; }
+    bool row = halve_row != 0 && multi_ran && left <= 2 * HALVE_ROW_MAX_S;
+    for (int tt = t; row && tt < lgB; tt += HALVE_ROW_MAX_S) {
+      const int s = lgB - tt < HALVE_ROW_MAX_S ? lgB - tt : HALVE_ROW_MAX_S;
+      row = halve_multi_grid(lgB, tt, s) * (size_t)sets <= (size_t)num_cu;
+    }
+    if (row) {
+      for (; t < lgB; t += HALVE_ROW_MAX_S) {
+        const int s = lgB - t < HALVE_ROW_MAX_S ? lgB - t : HALVE_ROW_MAX_S;
+        put(HALVE_MULTI_ROW, t, s, halve_multi_grid(lgB, t, s));
+      }
+      t = lgB;
+      break;
+    }
+    put(HALVE_MULTI_QUAD, t, st, halve_multi_grid(lgB, t, st));
+    t += st, multi_ran = true;
+  }
+  H.t_next = t;
+  return H;
 }
 
 // Chunk mode (msm_chunked_impl) covers the problems whose every chunk takes the two-level sort with one bucket set: the generic layout

@@ -16,12 +16,6 @@ namespace mzk {
 using rowop::Lane;
 using rowop::Pt;
 
-__device__ __forceinline__ void halve_indices(int lgB, int t, size_t id, size_t* lo, size_t* hi) {
-  const int lgh = lgB - t - 1;
-  const size_t a = id >> lgh, j = id & (((size_t)1 << lgh) - 1);
-  *lo = ((a == 0) ? 0 : ((size_t)1 << (lgB - a))) + j;
-  *hi = *lo + ((size_t)1 << lgh);
-}
 __device__ __noinline__ void halve_op_quad(u32* __restrict__ buf, int lgB, int t, size_t id, int lane) {
   size_t lo, hi;
   halve_indices(lgB, t, id, &lo, &hi);
@@ -56,6 +50,40 @@ __device__ __noinline__ void quad_add_lds(int lo, int hi, int ql) {
   extern __shared__ __attribute__((aligned(16))) u32 lds[];
   const Xyzz x = xyzz_gload_quad(lds, (size_t)lo, ql), y = xyzz_gload_quad(lds, (size_t)hi, ql);
   xyzz_gstore_quad(lds, (size_t)lo, xyzz_add_quad(x, y, ql), ql);
+}
+
+// Up to four late halving steps per launch on row operations: k_halve_multi's cut (halve_multi_wg, mzk_msm_plan.h) with problems of
+// at most 2^4 records, whose steps have 8, 8, 6, 4 additions in region 0 and 8, 4, 2, 1 in the regions that only fold -- one addition
+// per wave, eight waves, two to a SIMD, where a row addition is ~1.3 - 1.9 us against the ~3.5 - 5.4 us of a round of DPP quads.
+// The 2^s packed records move into LDS, wave w takes additions w, w + 8, ... of every step between barriers, and the records that are
+// still live (halve_multi_live) go back to where they came from.
+constexpr int HROW_THREADS = 512;
+constexpr int HROW_WAVES = HROW_THREADS / 64;
+__global__ __launch_bounds__(HROW_THREADS) void k_halve_multi_row(u32* __restrict__ buckets, int lgB, int t0, int s) {
+  __shared__ __attribute__((aligned(16))) u32 rec[(1 << HALVE_ROW_MAX_S) * 32];
+  const HalveWg g = halve_multi_wg(lgB, t0, s, blockIdx.x);
+  uint4* g4 = reinterpret_cast<uint4*>(buckets + ((size_t)blockIdx.y << lgB) * 32);
+  uint4* l4 = reinterpret_cast<uint4*>(rec);
+  for (int i = threadIdx.x; i < (8 << s); i += HROW_THREADS) l4[i] = g4[(g.base + ((size_t)(i >> 3) << g.lgs)) * 8 + (i & 7)];
+  __syncthreads();
+  const Lane ln = rowop::lane_init();
+  const int wave = threadIdx.x >> 6;
+#pragma unroll 1
+  for (int tl = 0; tl < s; tl++) {
+    const int total = halve_multi_ops(g.region, s, tl);
+#pragma unroll 1
+    for (int id = wave; id < total; id += HROW_WAVES) {          // wave-uniform; the kernel's ONE addition, inlined: nothing to save around a call
+      int lo, hi;
+      halve_multi_pair(s, tl, id, &lo, &hi);
+      const Pt x = rowop::load(rec + lo * 32, ln), y = rowop::load(rec + hi * 32, ln);
+      rowop::store(rec + lo * 32, rowop::add(x, y, ln), ln);
+    }
+    __syncthreads();
+  }
+  for (int i = threadIdx.x; i < 8 * halve_multi_live(g.region, s); i += HROW_THREADS) {
+    const int k = halve_multi_live_at(i >> 3);
+    g4[(g.base + ((size_t)k << g.lgs)) * 8 + (i & 7)] = l4[k * 8 + (i & 7)];
+  }
 }
 
 // Remaining steps t_start .. lgB-1 of a bucket set inside one workgroup, then  buf[0] + sum_q 2^q buf[2^q]  and, for a single
@@ -217,6 +245,12 @@ int launch_reduce_tail_row(u32* buckets, int lgB, int t_start, int sets, u32* ou
   }
   hipLaunchKernelGGL(k_reduce_tail_row, dim3((unsigned)sets), dim3(RTAIL_THREADS), LDS_BYTES, s, buckets, lgB, t_start, out, finish_affine, tail_row_max(),
                      tail_plan(lgB));
+  return MZK_OK;
+}
+// steps t0 .. t0 + steps - 1 of `sets` bucket sets: grid = halve_multi_grid(lgB, t0, steps) workgroups per set
+int launch_halve_multi_row(u32* buckets, int lgB, int t0, int steps, size_t grid, int sets, hipStream_t s) {
+  if (steps < 1 || steps > HALVE_ROW_MAX_S || t0 < 0 || t0 + steps > lgB || grid != halve_multi_grid(lgB, t0, steps)) return MZK_E_ARG;
+  hipLaunchKernelGGL(k_halve_multi_row, dim3((unsigned)grid, (unsigned)sets), dim3(HROW_THREADS), 0, s, buckets, lgB, t0, steps);
   return MZK_OK;
 }
 int launch_window_combine_row(const u32* wsum, int nwin, int c, int out_xyzz, u32* out, hipStream_t s) {
