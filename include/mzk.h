@@ -119,14 +119,25 @@ int mzk_ntt(int field_id, const uint64_t* root, const uint64_t* in, uint64_t* ou
 int mzk_coset_lde(int field_id, const uint64_t* coef, size_t n_coef, const uint64_t* offset,
                   const uint64_t* generator, uint64_t* out, size_t order);
 
-/* Polynomial::fft_multiply (polynomial.rs:242-276): omega must have order next_pow2(la+lb-1) (the
- * reference does not check it; neither do we).  out holds la+lb-1 elements; *out_len = length after
- * the reference's trailing-zero trim. */
+/* Polynomial::fft_multiply (polynomial.rs:242-276): m = la+lb-1 and n = next_pow2(m) come from the stored lengths,
+ * trailing zeros included.  omega must be a primitive n-th root of unity.  The reference's private fft takes any
+ * omega unchecked; the transforms here check theirs like ntt::ntt: MZK_E_ROOT_ORDER when omega^n != 1,
+ * MZK_E_ROOT_PRIM when omega^(n/2) == 1, MZK_E_RANGE when it is not canonical, MZK_E_ARG when it is NULL.  omega is
+ * not read when n == 1 (1 x 1) or when an operand is empty.  An empty operand (la == 0 or lb == 0, not both) gives the
+ * empty product, *out_len = 0, as the reference's resize(n) and trim do; la == lb == 0 is its usize underflow,
+ * MZK_E_LENGTH.  out holds la+lb-1 elements; *out_len = length after the reference's truncate(m) and
+ * trailing-zero trim (0 for an all-zero operand). */
 int mzk_fft_multiply(int field_id, const uint64_t* a, size_t la, const uint64_t* b, size_t lb,
                      const uint64_t* omega, uint64_t* out, size_t* out_len);
 
-/* ntt::fast_multiply (ntt.rs:66-116): root of order root_order; picks the sub-root itself; schoolbook
- * below degree 8; result NOT trimmed on the NTT path (length = chosen order).  out must hold
+/* ntt::fast_multiply (ntt.rs:66-116): root must be canonical (MZK_E_RANGE) and primitive of order root_order
+ * (MZK_E_ROOT_ORDER / MZK_E_ROOT_PRIM, the assertions :75-76, made before anything else).  A zero operand (empty or
+ * all zero coefficients) gives *out_len = 0.  With degree = the sum of the operands' degrees after trimming: below 8
+ * the trimmed schoolbook product (`lhs * rhs`), whatever root_order is; else order = root_order halved while
+ * degree < order / 2, the sub-root picked here, and the result is the `order` coefficients of the cyclic convolution,
+ * NOT trimmed (*out_len = order; it wraps around when degree >= order, i.e. when nothing could be halved).  The stored
+ * lengths, trailing zeros included, must not exceed `order`: the reference hands a longer operand to ntt as it is and
+ * panics there, MZK_E_LENGTH; an order that is no power of two is MZK_E_NOT_POW2.  out must hold
  * max(root_order, la+lb) elements. */
 int mzk_fast_multiply(int field_id, const uint64_t* a, size_t la, const uint64_t* b, size_t lb,
                       const uint64_t* root, size_t root_order, uint64_t* out, size_t* out_len);

@@ -6,6 +6,7 @@
 #include <atomic>
 #include "mzk_common.h"
 #include "mzk_gl.h"
+#include "mzk_mul_plan.h"
 
 namespace mzk {
 
@@ -770,24 +771,31 @@ static size_t trimmed_len(const uint64_t* c, size_t n, int nl) {
   return n;
 }
 
-// zero-pad two host polynomials to `order` on the device, forward-transform both, Hadamard, inverse.  The result stays in the
-// caller's lease (WS_MISC_C of its frame).
-static int conv_on_device(WsFrame& ws, int fid, const uint64_t* a, size_t la, const uint64_t* b, size_t lb, const uint64_t* root,
-                          size_t order, void** d_result, hipStream_t s) {
-  const size_t esz = field_bytes(fid);
+// The product a plan admits (mzk_mul_plan.h): the leading copy_a / copy_b elements of the host polynomials zero-padded to `order` on the
+// device, both forward-transformed, Hadamard, inverse; then the first `keep` elements, trimmed or not, to the caller.  The three
+// buffers are leases of the caller's frame, `order` elements each: the plan keeps every copy within them.
+static int conv_on_device(WsFrame& ws, int fid, const MulPlan& P, const uint64_t* a, const uint64_t* b, const uint64_t* root, uint64_t* out,
+                          size_t* out_len, hipStream_t s) {
+  const size_t esz = field_bytes(fid), order = P.order;
+  if (P.copy_a > order || P.copy_b > order || P.keep > order) { set_error("polynomial product: plan outside its buffers"); return MZK_E_ARG; }
   void *da, *db, *dc;
   MZK_TRY(ws.get(WS_MISC_A, order * esz, &da));
   MZK_TRY(ws.get(WS_MISC_B, order * esz, &db));
   MZK_TRY(ws.get(WS_MISC_C, order * esz, &dc));
   MZK_HIP(hipMemsetAsync(da, 0, order * esz, s));
   MZK_HIP(hipMemsetAsync(db, 0, order * esz, s));
-  if (la) MZK_HIP(hipMemcpyAsync(da, a, la * esz, hipMemcpyHostToDevice, s));
-  if (lb) MZK_HIP(hipMemcpyAsync(db, b, lb * esz, hipMemcpyHostToDevice, s));
-  MZK_TRY(ntt_dev_impl(fid, root, da, da, order, 0, nullptr, s));
+  MZK_HIP(hipMemcpyAsync(da, a, P.copy_a * esz, hipMemcpyHostToDevice, s));
+  MZK_HIP(hipMemcpyAsync(db, b, P.copy_b * esz, hipMemcpyHostToDevice, s));
+  MZK_TRY(ntt_dev_impl(fid, root, da, da, order, 0, nullptr, s));      // order 1: the identity, the root is not looked at
   MZK_TRY(ntt_dev_impl(fid, root, db, db, order, 0, nullptr, s));
   MZK_TRY(pointwise_mul_dev(fid, da, db, dc, order, s));
   MZK_TRY(ntt_dev_impl(fid, root, dc, dc, order, 1, nullptr, s));
-  *d_result = dc;
+  const int nl = field_limbs64(fid);
+  std::vector<uint64_t> res(order * nl);
+  MZK_TRY(d2h_sync(res.data(), dc, order * esz, s));
+  const size_t lo = P.trim ? trimmed_len(res.data(), P.keep, nl) : P.keep;
+  memcpy(out, res.data(), lo * esz);
+  *out_len = lo;
   return MZK_OK;
 }
 
@@ -797,36 +805,15 @@ int mzk_fft_multiply(int field_id, const uint64_t* a, size_t la, const uint64_t*
   WsFrame ws("mzk_fft_multiply");
   MZK_TRY(field_check(field_id, "fft_multiply"));
   if (!out_len || (!a && la) || (!b && lb)) { set_error("fft_multiply: null pointer"); return MZK_E_ARG; }
-  if (la + lb == 0) { set_error("attempt to subtract with overflow (self.coef.len() + other.coef.len() - 1)"); return MZK_E_LENGTH; }
-  const size_t m = la + lb - 1;
-  size_t n = 1;
-  while (n < m) n <<= 1;
-  const int nl = field_limbs64(field_id);
+  const MulPlan P = fft_mul_plan(la, lb);
+  if (P.err) { set_error(P.msg); return P.err; }
+  if (P.empty) { *out_len = 0; return MZK_OK; }
+  if (!out) { set_error("fft_multiply: null pointer"); return MZK_E_ARG; }
+  // 1 x 1: the reference's fft() of length 1 is the identity (polynomial.rs:280-282) and omega is not used
+  if (P.order > 1 && !omega) { set_error("fft_multiply: null omega"); return MZK_E_ARG; }
   hipStream_t s = ctx().stream;
   WsGuard wsg(s);
-  const size_t esz = field_bytes(field_id);
-  if (m == 0) { *out_len = 0; return MZK_OK; }
-  if (!out) { set_error("fft_multiply: null pointer"); return MZK_E_ARG; }
-  std::vector<uint64_t> res(n * nl);
-  if (n == 1) {
-    // 1x1 product: the reference's fft() of length 1 is the identity; c[0] = a[0] * b[0] * 1^-1
-    void *da, *db, *dc;
-    MZK_TRY(stage_in(ws, WS_MISC_A, a, la * esz, &da, s));
-    MZK_TRY(stage_in(ws, WS_MISC_B, b, lb * esz, &db, s));
-    MZK_TRY(ws.get(WS_MISC_C, esz, &dc));
-    if (la == 0 || lb == 0) { *out_len = 0; return MZK_OK; }
-    MZK_TRY(pointwise_mul_dev(field_id, da, db, dc, 1, s));
-    MZK_TRY(d2h_sync(res.data(), dc, esz, s));
-  } else {
-    if (!omega) { set_error("fft_multiply: null omega"); return MZK_E_ARG; }
-    void* dc;
-    MZK_TRY(conv_on_device(ws, field_id, a, la, b, lb, omega, n, &dc, s));
-    MZK_TRY(d2h_sync(res.data(), dc, n * esz, s));
-  }
-  size_t lo = trimmed_len(res.data(), m, nl);  // truncate(m) then trim_trailing_zeros, polynomial.rs:271-275
-  memcpy(out, res.data(), lo * esz);
-  *out_len = lo;
-  return MZK_OK;
+  return conv_on_device(ws, field_id, P, a, b, omega, out, out_len, s);
 }
 
 int mzk_fast_multiply(int field_id, const uint64_t* a, size_t la, const uint64_t* b, size_t lb, const uint64_t* root,
@@ -843,38 +830,17 @@ int mzk_fast_multiply(int field_id, const uint64_t* a, size_t la, const uint64_t
   if (!h_is_one(hf, t)) { set_error("assertion failed: primitive_root.pow(root_order).is_one()"); return MZK_E_ROOT_ORDER; }
   h_powmod_u64(hf, t, root, root_order / 2);
   if (h_is_one(hf, t)) { set_error("assertion failed: !primitive_root.pow(root_order / 2).is_one()"); return MZK_E_ROOT_PRIM; }
-  const size_t da = trimmed_len(a, la, nl), db = trimmed_len(b, lb, nl);
-  if (da == 0 || db == 0) { *out_len = 0; return MZK_OK; }  // ntt.rs:78-80
-  const size_t degree = (da - 1) + (db - 1);
-  hipStream_t s = ctx().stream;
-  WsGuard wsg(s);
-  const size_t esz = field_bytes(field_id);
+  const MulPlan P = fast_mul_plan(la, lb, trimmed_len(a, la, nl), trimmed_len(b, lb, nl), root_order);
+  if (P.err) { set_error(P.msg); return P.err; }
+  if (P.empty) { *out_len = 0; return MZK_OK; }  // ntt.rs:78-80
   if (!out) { set_error("fast_multiply: null pointer"); return MZK_E_ARG; }
   uint64_t r[4] = {0, 0, 0, 0};
   memcpy(r, root, 8 * nl);
-  size_t order;
-  bool trim;
-  if (degree < 8) {
-    // ntt.rs:86-88 `return lhs * rhs` (schoolbook, trimmed).  Same product through a 16-point cyclic
-    // convolution (degree < 8 < 16, so no wrap-around), then trimmed like Polynomial::mul_ref.
-    order = 16;
-    MZK_TRY(mzk_root_of_unity(field_id, 4, r));
-    trim = true;
-    la = da; lb = db;
-  } else {
-    order = root_order;
-    while (degree < order / 2) { h_mulmod(hf, r, r, r); order /= 2; }  // ntt.rs:90-93
-    if (la > order || lb > order) { set_error("fast_multiply: operand longer than the transform order"); return MZK_E_LENGTH; }
-    trim = false;
-  }
-  void* dc;
-  MZK_TRY(conv_on_device(ws, field_id, a, la, b, lb, r, order, &dc, s));
-  std::vector<uint64_t> res(order * nl);
-  MZK_TRY(d2h_sync(res.data(), dc, order * esz, s));
-  size_t lo = trim ? trimmed_len(res.data(), da + db - 1, nl) : order;
-  memcpy(out, res.data(), lo * esz);
-  *out_len = lo;
-  return MZK_OK;
+  if (P.small) MZK_TRY(mzk_root_of_unity(field_id, MUL_SMALL_LOG, r));       // ntt.rs:86-88 `return lhs * rhs`: not the caller's root
+  for (int i = 0; i < P.squarings; i++) h_mulmod(hf, r, r, r);               // ntt.rs:90-93
+  hipStream_t s = ctx().stream;
+  WsGuard wsg(s);
+  return conv_on_device(ws, field_id, P, a, b, r, out, out_len, s);
 }
 
 // lhs / rhs of at most 8 coefficients (trimmed lengths tl <= 8, 0 < tr <= tl): the trimmed quotient into out, its length returned

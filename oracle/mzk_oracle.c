@@ -505,7 +505,8 @@ int orc_fft_multiply_ref(int fid, const u64* a, size_t la, const u64* b, size_t 
   while (n < m) n <<= 1;
   if (m == 0) n = 1; /* usize::next_power_of_two(0) == 1 */
   u64* x = calloc(n, 8 * L), *y = calloc(n, 8 * L);
-  to_mont_vec(f, x, a, la); to_mont_vec(f, y, b, lb);
+  /* resize(n) (:248-251) cuts the longer operand when the other one is empty: m = lb - 1 < lb */
+  to_mont_vec(f, x, a, la < n ? la : n); to_mont_vec(f, y, b, lb < n ? lb : n);
   u64 wm[MAXN], winv[MAXN], nn[MAXN] = {0}, ninv[MAXN];
   f_tomont(f, wm, omega);
   fft_ref_rec(f, x, n, wm);

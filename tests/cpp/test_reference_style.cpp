@@ -130,6 +130,34 @@ static void test_fast_multiply() {
   for (size_t i = p1.coef.size(); i < p2.coef.size(); i++) CHECK(p2.coef[i].is_zero());
   // spot check coefficient 1: a0 b1 + a1 b0 = 1*3 + 4*2
   CHECK(p1.coef[1] == FqOrder::from_value(11));
+  // the result fills the whole root_order: nothing is halved (63 >= 64 / 2), out_len == root_order
+  auto p3 = fast_multiply(a, b, get_nth_root_of_fr(6), 64);
+  CHECK(p3.coef.size() == 64);
+  for (size_t i = 0; i < 64 && i < p3.coef.size(); i++) CHECK(p3.coef[i] == p1.coef[i]);
+  // one coefficient more: m = 65 takes the next order in both (fft_multiply trims to 65, fast_multiply keeps 128)
+  b.coef.push_back(FqOrder::from_value(7));
+  auto q1 = a.fft_multiply(b, get_nth_root_of_fr(7));
+  auto q2 = fast_multiply(a, b, get_nth_root_of_fr(10), 1024);
+  CHECK(q1.coef.size() == 65);
+  CHECK(q2.coef.size() == 128);
+  for (size_t i = 0; i < q1.coef.size() && i < q2.coef.size(); i++) CHECK(q1.coef[i] == q2.coef[i]);
+  for (size_t i = q1.coef.size(); i < q2.coef.size(); i++) CHECK(q2.coef[i].is_zero());
+  CHECK(q1.coef.size() == 65 && q1.coef[64] == FqOrder::from_value((3 * 39 + 1) * 7));   // a39 b25
+  for (size_t i = 0; i < 25; i++) CHECK(q1.coef[i] == p1.coef[i]);                         // below X^25 the new coefficient adds nothing
+  // an empty operand: the empty polynomial from both, whichever side it is on (polynomial.rs:248-251 resize cuts the other operand;
+  // ntt.rs:78-80): a against nothing has m = 39, n = 64; nothing against the 26 coefficients of b has m = 25, n = 32
+  Polynomial<FqOrder> e;
+  CHECK(a.fft_multiply(e, get_nth_root_of_fr(6)).coef.empty());
+  CHECK(e.fft_multiply(b, get_nth_root_of_fr(5)).coef.empty());
+  CHECK(fast_multiply(a, e, get_nth_root_of_fr(10), 1024).coef.empty());
+  CHECK(fast_multiply(e, b, get_nth_root_of_fr(10), 1024).coef.empty());
+  Polynomial<FqOrder> b17;                                                                // la = 0, lb = 2^4 + 1: m = n = 16 < lb
+  for (uint64_t i = 0; i < 17; i++) b17.coef.push_back(FqOrder::from_value(i + 1));
+  CHECK(e.fft_multiply(b17, get_nth_root_of_fr(4)).coef.empty());
+  CHECK(b17.fft_multiply(e, get_nth_root_of_fr(4)).coef.empty());
+  auto p4 = a.fft_multiply(b, get_nth_root_of_fr(7));                                     // and the next product is the same as before
+  CHECK(p4.coef.size() == q1.coef.size());
+  for (size_t i = 0; i < p4.coef.size() && i < q1.coef.size(); i++) CHECK(p4.coef[i] == q1.coef[i]);
 }
 
 static void test_panics() {
