@@ -13,7 +13,7 @@
 //   k_mp_rows     rows copied to the caller's stride (zeros behind them) and every row's trimmed length (polynomial.rs:214-228 trims
 //                 after every + and *), so that only the lengths travel to the host.
 //
-// k_mp_terms runs a TERM PROGRAM the host compiles per constraint (mp_compile).  The terms are sorted so that those sharing the monomial of
+// k_mp_terms runs a TERM PROGRAM the host compiles per constraint (mp_compile, mzk_mpoly_plan.h).  The terms are sorted so that those sharing the monomial of
 // every variable but one (the Horner variable h: the one with the largest exponent in the constraint) form a run -- the shape
 // MPolynomial::lift produces (rescueprime.rs:454-484: a univariate in the cycle variable times a monomial of the state variables) -- and a
 // run sum_j c_j x_h^(d_j) m, d_0 > d_1 > ..., is evaluated as (((c_0 x_h^(d_0-d_1) + c_1) x_h^(d_1-d_2) + ...) x_h^(d_k)) m: about one
@@ -32,17 +32,10 @@
 #include "mzk_common.h"
 #include "mzk_elem.h"
 #include "mzk_field_asm.h"
+#include "mzk_mpoly_plan.h"
 
 namespace mzk {
 
-constexpr int MP_MAX_VARS = MZK_MPOLY_MAX_VARS;
-constexpr int MP_TABLE = 3;              // deepest power kept per variable
-constexpr int MP_LANES = 64;
-enum { MP_LOADC = 1, MP_ADDC = 2, MP_MULT = 3, MP_HORNER = 4, MP_POW = 5 };
-constexpr u32 MP_FLUSH = 1u << 31;       // after the op: sum += acc
-// op word: op | slot << 8 | flush; arg word: coefficient index (LOADC, ADDC, HORNER) or exponent (POW; slot = the variable's first slot)
-struct MpOp { u32 op, arg; };
-struct MpVars { u32 first_slot[MP_MAX_VARS]; u32 depth[MP_MAX_VARS]; };
 struct MpRows { size_t off[MP_MAX_VARS + 1]; };
 
 // the same element for every lane: word loads at a wave-uniform address
@@ -80,6 +73,7 @@ __global__ __launch_bounds__(256) void k_mp_pad(const u32* __restrict__ point, M
 template <class P>
 __global__ __launch_bounds__(MP_LANES) void k_mp_terms(const u32* __restrict__ E, size_t n, int n_vars, MpVars vars, const MpOp* __restrict__ prog,
                                                        const u32* __restrict__ prog_off, const u32* __restrict__ coefs, u32* __restrict__ V) {
+  static_assert(P::L <= MP_MAX_LIMBS, "the LDS bound of mzk_mpoly_plan.h is stated for at most MP_MAX_LIMBS limbs");
   extern __shared__ u32 mp_lds[];
   const int lane = threadIdx.x;
   const size_t j = (size_t)blockIdx.x * MP_LANES + lane;
@@ -185,133 +179,12 @@ __global__ __launch_bounds__(256) void k_mp_lincomb(const u32* __restrict__ poly
   if (threadIdx.x == 0 && sh[0]) atomicMax(len, sh[0]);
 }
 
-// ---- host plan -----------------------------------------------------------------------------------------------------------------------
-struct MpPlan { size_t n = 0, stride_min = 0; std::vector<size_t> bounds; };
-
-static int mp_monotone(const size_t* off, size_t count, const char* what) {
-  for (size_t i = 0; i < count; i++) if (off[i + 1] < off[i]) { set_error("mpoly_compose: %s[%zu] = %zu is below %s[%zu] = %zu", what, i + 1, off[i + 1], what, i, off[i]); return MZK_E_LENGTH; }
-  return MZK_OK;
-}
-// term t vanishes (a positive exponent on an empty polynomial) ?  *deg = sum_i k_i (len_i - 1)
-static int mp_term_degree(const uint32_t* k, size_t nv, const size_t* point_offsets, bool* vanishes, size_t* deg) {
-  size_t d = 0;
-  *vanishes = false;
-  for (size_t i = 0; i < nv; i++) {
-    if (k[i] == 0) continue;
-    const size_t len = point_offsets[i + 1] - point_offsets[i];
-    if (len == 0) { *vanishes = true; return MZK_OK; }
-    size_t m;
-    if (__builtin_mul_overflow((size_t)k[i], len - 1, &m) || __builtin_add_overflow(d, m, &d)) {
-      set_error("mpoly_compose: the degree bound of a term overflows 64 bits");
-      return MZK_E_LENGTH;
-    }
-  }
-  *deg = d;
-  return MZK_OK;
-}
-static int mp_plan(int fid, const uint32_t* term_exps, const size_t* term_offsets, size_t nc, size_t nv, const size_t* point_offsets, MpPlan* pl) {
+// ---- host plan and term programs: mzk_mpoly_plan.h (mp_plan, mp_compile) -------------------------------------------------------------
+static int mp_plan_of(int fid, const uint32_t* term_exps, const size_t* term_offsets, size_t nc, size_t nv, const size_t* point_offsets, MpPlan* pl) {
   MZK_TRY(field_check(fid, "mpoly_compose"));
-  if (nv > (size_t)MP_MAX_VARS) { set_error("mpoly_compose: %zu variables (at most %d)", nv, MP_MAX_VARS); return MZK_E_ARG; }
-  if (nc == 0) return MZK_OK;
-  if (!term_offsets || (nv && !point_offsets)) { set_error("mpoly_compose: null pointer"); return MZK_E_ARG; }
-  MZK_TRY(mp_monotone(term_offsets, nc, "term_offsets"));
-  if (nv) MZK_TRY(mp_monotone(point_offsets, nv, "point_offsets"));
-  if (term_offsets[nc] > term_offsets[0] && nv && !term_exps) { set_error("mpoly_compose: null pointer"); return MZK_E_ARG; }
-  pl->bounds.assign(nc, 0);
-  for (size_t a = 0; a < nc; a++)
-    for (size_t t = term_offsets[a]; t < term_offsets[a + 1]; t++) {
-      bool vanishes;
-      size_t d = 0;
-      MZK_TRY(mp_term_degree(nv ? term_exps + t * nv : nullptr, nv, point_offsets, &vanishes, &d));
-      if (vanishes) continue;
-      if (d == SIZE_MAX) { set_error("mpoly_compose: the degree bound of a term overflows 64 bits"); return MZK_E_LENGTH; }
-      pl->bounds[a] = std::max(pl->bounds[a], d + 1);
-    }
-  pl->stride_min = *std::max_element(pl->bounds.begin(), pl->bounds.end());
-  unsigned lg = 0;
-  while (lg < 64 && ((size_t)1 << lg) < pl->stride_min) lg++;
-  if (lg > field_max_log(fid)) {
-    set_error("mpoly_compose: degree bound %zu needs a transform of 2^%u points (at most 2^%u over this field)", pl->stride_min - 1, lg, field_max_log(fid));
-    return MZK_E_LENGTH;
-  }
-  pl->n = (size_t)1 << lg;
-  return MZK_OK;
-}
-
-// ---- term programs -------------------------------------------------------------------------------------------------------------------
-struct MpProgram { std::vector<MpOp> ops; std::vector<u32> off; MpVars vars; u32 slots = 0; };
-
-static void mp_emit_pow(std::vector<MpOp>& ops, const MpVars& v, u32 var, u32 e) {
-  const u32 s0 = v.first_slot[var];
-  if (e == 0) return;
-  if (e <= (u32)MP_TABLE) ops.push_back({MP_MULT | (s0 + e - 1) << 8, 0});
-  else if (e <= 2u * MP_TABLE) { ops.push_back({MP_MULT | (s0 + MP_TABLE - 1) << 8, 0}); ops.push_back({MP_MULT | (s0 + e - MP_TABLE - 1) << 8, 0}); }
-  else ops.push_back({MP_POW | s0 << 8, e});
-}
-// term_exps / term_offsets as at the ABI; coefficient index = term index - term_offsets[0]
-static void mp_compile(const uint32_t* term_exps, const size_t* term_offsets, size_t nc, size_t nv, const size_t* point_offsets, MpProgram* pg) {
-  // table depth per variable: the largest exponent any term asks for, at most MP_TABLE (gaps and tails of a Horner run are no larger)
-  u32 maxe[MP_MAX_VARS] = {};
-  for (size_t t = term_offsets[0]; t < term_offsets[nc]; t++)
-    for (size_t i = 0; i < nv; i++) maxe[i] = std::max(maxe[i], term_exps[t * nv + i]);
-  pg->slots = 0;
-  for (size_t i = 0; i < (size_t)MP_MAX_VARS; i++) {
-    const u32 e = i < nv ? maxe[i] : 0;
-    pg->vars.depth[i] = e > (u32)MP_TABLE ? (u32)MP_TABLE : e;
-    pg->vars.first_slot[i] = pg->slots;
-    pg->slots += pg->vars.depth[i];
-  }
-  pg->off.assign(1, 0);
-  for (size_t a = 0; a < nc; a++) {
-    std::vector<size_t> terms;
-    u32 cmax[MP_MAX_VARS] = {};
-    for (size_t t = term_offsets[a]; t < term_offsets[a + 1]; t++) {
-      bool vanishes = false;
-      for (size_t i = 0; i < nv; i++) {
-        const u32 e = term_exps[t * nv + i];
-        if (e && point_offsets[i + 1] == point_offsets[i]) vanishes = true;
-        cmax[i] = std::max(cmax[i], e);
-      }
-      if (!vanishes) terms.push_back(t);
-    }
-    size_t h = 0;                                        // the Horner variable
-    for (size_t i = 1; i < nv; i++) if (cmax[i] > cmax[h]) h = i;
-    auto rest_less = [&](size_t x, size_t y) {           // by the monomial of the other variables, then by falling exponent of h
-      for (size_t i = 0; i < nv; i++) {
-        if (i == h) continue;
-        const u32 ex = term_exps[x * nv + i], ey = term_exps[y * nv + i];
-        if (ex != ey) return ex < ey;
-      }
-      if (nv && term_exps[x * nv + h] != term_exps[y * nv + h]) return term_exps[x * nv + h] > term_exps[y * nv + h];
-      return x < y;
-    };
-    std::sort(terms.begin(), terms.end(), rest_less);
-    auto same_rest = [&](size_t x, size_t y) {
-      for (size_t i = 0; i < nv; i++) if (i != h && term_exps[x * nv + i] != term_exps[y * nv + i]) return false;
-      return true;
-    };
-    for (size_t r0 = 0; r0 < terms.size();) {
-      size_t r1 = r0 + 1;
-      while (r1 < terms.size() && same_rest(terms[r0], terms[r1])) r1++;
-      pg->ops.push_back({MP_LOADC, (u32)(terms[r0] - term_offsets[0])});
-      for (size_t q = r0 + 1; q < r1; q++) {
-        const u32 gap = nv ? term_exps[terms[q - 1] * nv + h] - term_exps[terms[q] * nv + h] : 0u;
-        const u32 ci = (u32)(terms[q] - term_offsets[0]);
-        if (gap == 0) pg->ops.push_back({MP_ADDC, ci});
-        else if (gap <= (u32)MP_TABLE) pg->ops.push_back({MP_HORNER | (pg->vars.first_slot[h] + gap - 1) << 8, ci});
-        else {
-          mp_emit_pow(pg->ops, pg->vars, (u32)h, gap);
-          // the product is below p + 1: the sum with a canonical coefficient is what HORNER leaves, one reduction more is harmless
-          pg->ops.push_back({MP_ADDC, ci});
-        }
-      }
-      if (nv) mp_emit_pow(pg->ops, pg->vars, (u32)h, term_exps[terms[r1 - 1] * nv + h]);
-      for (size_t i = 0; i < nv; i++) if (i != h) mp_emit_pow(pg->ops, pg->vars, (u32)i, term_exps[terms[r0] * nv + i]);
-      pg->ops.back().op |= MP_FLUSH;
-      r0 = r1;
-    }
-    pg->off.push_back((u32)pg->ops.size());
-  }
+  const int rc = mp_plan(field_max_log(fid), term_exps, term_offsets, nc, nv, point_offsets, pl);
+  if (rc != MZK_OK) set_error("%s", pl->msg);
+  return rc;
 }
 
 static inline unsigned mp_grid(size_t n, unsigned per) { return (unsigned)((n + per - 1) / per); }
@@ -321,7 +194,7 @@ static int mp_compose_dev(int fid, const uint64_t* term_coefs, const uint32_t* t
                           const void* d_point, const size_t* point_offsets, void* d_out, size_t out_stride, size_t* out_lens, hipStream_t s) {
   WsFrame ws("mp_compose_dev");
   MpPlan pl;
-  MZK_TRY(mp_plan(fid, term_exps, term_offsets, nc, nv, point_offsets, &pl));
+  MZK_TRY(mp_plan_of(fid, term_exps, term_offsets, nc, nv, point_offsets, &pl));
   if (nc == 0) return MZK_OK;
   if (!out_lens || (out_stride && !d_out)) { set_error("mpoly_compose: null pointer"); return MZK_E_ARG; }
   const size_t t0 = term_offsets[0], nt = term_offsets[nc] - t0;
@@ -439,7 +312,7 @@ int mzk_mpoly_compose_plan(int field_id, const uint32_t* term_exps, const size_t
                            const size_t* point_offsets, size_t* n_transform, size_t* out_stride_min, size_t* bounds) {
   if (!n_transform || !out_stride_min) { set_error("mpoly_compose_plan: null pointer"); return MZK_E_ARG; }
   MpPlan pl;
-  MZK_TRY(mp_plan(field_id, term_exps, term_offsets, n_constraints, n_vars, point_offsets, &pl));
+  MZK_TRY(mp_plan_of(field_id, term_exps, term_offsets, n_constraints, n_vars, point_offsets, &pl));
   *n_transform = pl.n;
   *out_stride_min = pl.stride_min;
   if (bounds) for (size_t a = 0; a < n_constraints; a++) bounds[a] = pl.bounds[a];
@@ -462,7 +335,7 @@ int mzk_mpoly_compose(int field_id, const uint64_t* term_coefs, const uint32_t* 
   MZK_ENTER();
   WsFrame ws("mzk_mpoly_compose");
   MpPlan pl;
-  MZK_TRY(mp_plan(field_id, term_exps, term_offsets, n_constraints, n_vars, point_offsets, &pl));
+  MZK_TRY(mp_plan_of(field_id, term_exps, term_offsets, n_constraints, n_vars, point_offsets, &pl));
   if (n_constraints == 0) return MZK_OK;
   if (!out_lens || (out_stride && !out)) { set_error("mpoly_compose: null pointer"); return MZK_E_ARG; }
   const HostField* hf = host_field(field_id);

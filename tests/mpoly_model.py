@@ -55,6 +55,8 @@ def ppow(a, e, p):
         return [1]
     if e == 1:
         return list(a)
+    if len(a) == 1:
+        return [pow(a[0], e, p)]                # a constant: the same value without e's bits of polynomial products
     acc = [1]
     for bit in bin(e)[2:]:
         acc = pmul(acc, acc, p)
