@@ -1,10 +1,11 @@
-// mzk_api.hip -- process context, host-side parameter math, and the host-buffer entry points of
+// mzk_api.hip -- process context and the host-buffer entry points of
 // include/mzk.h (H2D copy -> device implementation -> D2H copy, as the reference's only device
 // boundary does: examples/sumcheck/src/prover.rs:149-170).
 #include <stdarg.h>
 #include <stdlib.h>
 #include <atomic>
 #include "mzk_common.h"
+#include "mzk_divide_plan.h"
 #include "mzk_gl.h"
 #include "mzk_mul_plan.h"
 
@@ -177,18 +178,8 @@ int ensure_init() {
   return mzk_init(g_last_ordinal);
 }
 
-// ---- host parameter math --------------------------------------------------------------------------
-static const HostField HF_FR = {4, {0x43e1f593f0000001ULL, 0x2833e84879b97091ULL, 0xb85045b68181585dULL, 0x30644e72e131a029ULL}, 29 * FrParams::L};
-static const HostField HF_FQ = {4, {0x3c208c16d87cfd47ULL, 0x97816a916871ca8dULL, 0xb85045b68181585dULL, 0x30644e72e131a029ULL}, 29 * FqParams::L};
-static const HostField HF_M128 = {2, {1ULL, 407ULL << 55, 0, 0}, 29 * M128Params::L};
-const HostField* host_field(int fid) {
-  switch (fid) {
-    case MZK_FIELD_FR: return &HF_FR;
-    case MZK_FIELD_M128: return &HF_M128;
-    case MZK_FIELD_FQ: return &HF_FQ;
-    default: return nullptr;
-  }
-}
+static_assert(HOST_LIMBS29_FR == FrParams::L && HOST_LIMBS29_FQ == FqParams::L && HOST_LIMBS29_M128 == M128Params::L,
+              "mzk_hostfield.h states the device's limb counts");
 int field_check(int fid, const char* who, bool fq_too) {
   if (fid == MZK_FIELD_FR || fid == MZK_FIELD_M128 || (fq_too && fid == MZK_FIELD_FQ)) return MZK_OK;
   set_error("%s: bad field id %d", who, fid);
@@ -198,138 +189,6 @@ int field_check_ntt(int fid, const char* who) {
   if (fid == MZK_FIELD_FR || fid == MZK_FIELD_M128) return MZK_OK;
   set_error("%s: field id %d has no NTT on this path", who, fid);
   return MZK_E_ARG;
-}
-static int h_cmp(const uint64_t* a, const uint64_t* b, int n) {
-  for (int i = n - 1; i >= 0; i--) if (a[i] != b[i]) return a[i] > b[i] ? 1 : -1;
-  return 0;
-}
-bool h_is_canonical(const HostField* f, const uint64_t* a) { return h_cmp(a, f->p, f->nl) < 0; }
-bool h_is_one(const HostField* f, const uint64_t* a) {
-  if (a[0] != 1) return false;
-  for (int i = 1; i < f->nl; i++) if (a[i]) return false;
-  return true;
-}
-static void h_addmod(const HostField* f, uint64_t* r, const uint64_t* a, const uint64_t* b) {
-  uint64_t t[4] = {0, 0, 0, 0};
-  unsigned __int128 c = 0;
-  for (int i = 0; i < f->nl; i++) { c += (unsigned __int128)a[i] + b[i]; t[i] = (uint64_t)c; c >>= 64; }
-  if (c || h_cmp(t, f->p, f->nl) >= 0) {
-    unsigned __int128 br = 0;
-    for (int i = 0; i < f->nl; i++) {
-      unsigned __int128 d = (unsigned __int128)t[i] - f->p[i] - (uint64_t)br;
-      t[i] = (uint64_t)d; br = (d >> 64) & 1;
-    }
-  }
-  for (int i = 0; i < f->nl; i++) r[i] = t[i];
-}
-// double-and-add product: O(bits) modular additions.  Only used once per field, to derive the Montgomery constant
-// of the fast product below (and as its cross-check in tests through the same entry point).
-static void h_mulmod_slow(const HostField* f, uint64_t* r, const uint64_t* a, const uint64_t* b) {
-  uint64_t acc[4] = {0, 0, 0, 0}, aa[4] = {0, 0, 0, 0}, bb[4] = {0, 0, 0, 0};
-  for (int i = 0; i < f->nl; i++) { aa[i] = a[i]; bb[i] = b[i]; }
-  for (int bit = 64 * f->nl - 1; bit >= 0; bit--) {
-    h_addmod(f, acc, acc, acc);
-    if ((bb[bit / 64] >> (bit % 64)) & 1) h_addmod(f, acc, acc, aa);
-  }
-  for (int i = 0; i < f->nl; i++) r[i] = acc[i];
-}
-// Montgomery constants per host field (64-bit limbs): n0 = -p^-1 mod 2^64, r2 = 2^(128 nl) mod p
-struct HostMont { bool ready; uint64_t n0; uint64_t r2[4]; };
-static HostMont g_hmont[3];
-static const HostMont* host_mont(const HostField* f) {
-  HostMont* m = &g_hmont[f == &HF_FR ? 0 : (f == &HF_FQ ? 1 : 2)];
-  if (!m->ready) {
-    uint64_t inv = f->p[0];                              // Newton: p0 * p0 == 1 mod 8
-    for (int i = 0; i < 6; i++) inv *= 2 - f->p[0] * inv;
-    m->n0 = (uint64_t)0 - inv;
-    uint64_t x[4] = {1, 0, 0, 0};                        // 2^(128 nl) mod p by 128 nl modular doublings
-    for (int i = 0; i < 128 * f->nl; i++) h_addmod(f, x, x, x);
-    for (int i = 0; i < 4; i++) m->r2[i] = x[i];
-    m->ready = true;
-  }
-  return m;
-}
-// a * b / 2^(64 nl) mod p (CIOS), inputs < p
-static void h_montmul(const HostField* f, const HostMont* m, uint64_t* r, const uint64_t* a, const uint64_t* b) {
-  const int n = f->nl;
-  uint64_t t[6] = {0, 0, 0, 0, 0, 0};
-  for (int i = 0; i < n; i++) {
-    unsigned __int128 c = 0;
-    for (int j = 0; j < n; j++) { c += (unsigned __int128)a[j] * b[i] + t[j]; t[j] = (uint64_t)c; c >>= 64; }
-    c += t[n]; t[n] = (uint64_t)c; t[n + 1] = (uint64_t)(c >> 64);
-    const uint64_t q = t[0] * m->n0;
-    c = (unsigned __int128)q * f->p[0] + t[0];
-    c >>= 64;
-    for (int j = 1; j < n; j++) { c += (unsigned __int128)q * f->p[j] + t[j]; t[j - 1] = (uint64_t)c; c >>= 64; }
-    c += t[n]; t[n - 1] = (uint64_t)c;
-    t[n] = t[n + 1] + (uint64_t)(c >> 64);
-  }
-  if (t[n] || h_cmp(t, f->p, n) >= 0) {
-    unsigned __int128 br = 0;
-    for (int i = 0; i < n; i++) { unsigned __int128 d = (unsigned __int128)t[i] - f->p[i] - (uint64_t)br; t[i] = (uint64_t)d; br = (d >> 64) & 1; }
-  }
-  for (int i = 0; i < n; i++) r[i] = t[i];
-}
-// a * b mod p for canonical a, b: mont(mont(a, b), R^2)
-void h_mulmod(const HostField* f, uint64_t* r, const uint64_t* a, const uint64_t* b) {
-  const HostMont* m = host_mont(f);
-  uint64_t t[4] = {0, 0, 0, 0};
-  h_montmul(f, m, t, a, b);
-  h_montmul(f, m, r, t, m->r2);
-}
-void h_powmod_u64(const HostField* f, uint64_t* r, const uint64_t* a, uint64_t e) {
-  uint64_t res[4] = {1, 0, 0, 0}, base[4] = {0, 0, 0, 0};
-  for (int i = 0; i < f->nl; i++) base[i] = a[i];
-  while (e) {
-    if (e & 1) h_mulmod(f, res, res, base);
-    h_mulmod(f, base, base, base);
-    e >>= 1;
-  }
-  for (int i = 0; i < f->nl; i++) r[i] = res[i];
-}
-void h_invmod(const HostField* f, uint64_t* r, const uint64_t* a) {
-  uint64_t e[4] = {0, 0, 0, 0}, res[4] = {1, 0, 0, 0}, base[4] = {0, 0, 0, 0};
-  for (int i = 0; i < f->nl; i++) { e[i] = f->p[i]; base[i] = a[i]; }
-  {  // e = p - 2 with borrow propagation (M128's low limb is 1)
-    uint64_t borrow = 2;
-    for (int i = 0; i < f->nl && borrow; i++) {
-      const uint64_t old = e[i];
-      e[i] = old - borrow;
-      borrow = (old < borrow) ? 1 : 0;
-    }
-  }
-  for (int bit = 0; bit < 64 * f->nl; bit++) {
-    if ((e[bit / 64] >> (bit % 64)) & 1) h_mulmod(f, res, res, base);
-    h_mulmod(f, base, base, base);
-  }
-  for (int i = 0; i < f->nl; i++) r[i] = res[i];
-}
-// n = 2^k divides p - 1:  n * ((p-1)/n) = -1 (mod p)  =>  n^-1 = p - (p-1)/n
-void h_ninv_pow2(const HostField* f, unsigned k, uint64_t* out) {
-  uint64_t q[4] = {0, 0, 0, 0};
-  for (int i = 0; i < f->nl; i++) q[i] = f->p[i];
-  q[0] -= 1;  // p is odd
-  for (unsigned s = 0; s < k; s++) {
-    for (int i = 0; i < f->nl; i++) q[i] = (q[i] >> 1) | ((i + 1 < f->nl) ? (q[i + 1] << 63) : 0);
-  }
-  unsigned __int128 br = 0;
-  for (int i = 0; i < f->nl; i++) {
-    unsigned __int128 d = (unsigned __int128)f->p[i] - q[i] - (uint64_t)br;
-    out[i] = (uint64_t)d; br = (d >> 64) & 1;
-  }
-}
-void h_rmod(const HostField* f, uint64_t* out) {
-  const uint64_t two[4] = {2, 0, 0, 0};
-  h_powmod_u64(f, out, two, (uint64_t)f->mont_bits);
-}
-void h_words(const uint64_t* v, int nl, u32 out8[8]) {
-  for (int i = 0; i < 8; i++) out8[i] = i < 2 * nl ? (u32)(v[i / 2] >> (32 * (i & 1))) : 0u;
-}
-void h_mont_words(const HostField* f, const uint64_t* v, u32 out8[8]) {
-  uint64_t r[4], t[4];
-  h_rmod(f, r);
-  h_mulmod(f, t, v, r);
-  h_words(t, f->nl, out8);
 }
 
 }  // namespace mzk
@@ -502,7 +361,7 @@ const char* mzk_prof_name(int phase) {
   return (phase >= 0 && phase < MZK_PH_COUNT) ? names[phase] : "?";
 }
 
-// Host parameter arithmetic, exposed so that it can be checked without a GPU (tests/test_abi_load.py): op 0 = a * b,
+// Host parameter arithmetic (mzk_hostfield.h) as the library carries it, checked without a GPU (tests/test_abi_load.py): op 0 = a * b,
 // 1 = a^-1 (0 -> 0), 2 = a^b[0], 3 = a * b by the bit-serial reference implementation, 4 = h_mont_words(a): a R mod p as the eight
 // 32-bit words of a kernel argument, in four uint64 whatever the field (M128: the upper two are zero).  b is not read by 1 and 4.
 int mzk_host_field_op(int field_id, int op, const uint64_t* a, const uint64_t* b, uint64_t* out) {
@@ -825,11 +684,7 @@ int mzk_fast_multiply(int field_id, const uint64_t* a, size_t la, const uint64_t
   const HostField* hf = host_field(field_id);
   const int nl = hf->nl;
   if (!h_is_canonical(hf, root)) { set_error("fast_multiply: root not canonical"); return MZK_E_RANGE; }
-  uint64_t t[4];
-  h_powmod_u64(hf, t, root, root_order);  // ntt.rs:75-76
-  if (!h_is_one(hf, t)) { set_error("assertion failed: primitive_root.pow(root_order).is_one()"); return MZK_E_ROOT_ORDER; }
-  h_powmod_u64(hf, t, root, root_order / 2);
-  if (h_is_one(hf, t)) { set_error("assertion failed: !primitive_root.pow(root_order / 2).is_one()"); return MZK_E_ROOT_PRIM; }
+  MZK_TRY(root_check(hf, root, root_order));  // ntt.rs:75-76
   const MulPlan P = fast_mul_plan(la, lb, trimmed_len(a, la, nl), trimmed_len(b, lb, nl), root_order);
   if (P.err) { set_error(P.msg); return P.err; }
   if (P.empty) { *out_len = 0; return MZK_OK; }  // ntt.rs:78-80
@@ -860,17 +715,12 @@ static size_t small_poly_div(const HostField* hf, const uint64_t* lhs, size_t tl
     memcpy(quo[dd], lead, 8 * nl);
     for (size_t i = 0; i < tr; i++) {
       h_mulmod(hf, prod, lead, rhs + i * nl);
-      // rem - prod mod p = rem + (p - prod)
-      uint64_t neg[4] = {0, 0, 0, 0};
-      bool z = true;
-      for (int k = 0; k < nl; k++) z = z && prod[k] == 0;
-      if (!z) { unsigned __int128 br = 0; for (int k = 0; k < nl; k++) { unsigned __int128 d = (unsigned __int128)hf->p[k] - prod[k] - br; neg[k] = (uint64_t)d; br = (d >> 64) & 1; } }
-      h_addmod(hf, rem[dd + i], rem[dd + i], neg);
+      h_submod(hf, rem[dd + i], rem[dd + i], prod);
     }
-    while (rl > 0) { bool z = true; for (int k = 0; k < nl; k++) z = z && rem[rl - 1][k] == 0; if (!z) break; rl--; }
+    while (rl > 0 && h_is_zero(hf, rem[rl - 1])) rl--;
   }
   size_t qt = ql;
-  while (qt > 0) { bool z = true; for (int k = 0; k < nl; k++) z = z && quo[qt - 1][k] == 0; if (!z) break; qt--; }
+  while (qt > 0 && h_is_zero(hf, quo[qt - 1])) qt--;
   for (size_t i = 0; i < qt; i++) memcpy(out + i * nl, quo[i], 8 * nl);
   return qt;
 }
@@ -884,39 +734,29 @@ int mzk_fast_coset_divide(int field_id, const uint64_t* lhs, size_t ll, const ui
   const HostField* hf = host_field(field_id);
   const int nl = hf->nl;
   if (!h_is_canonical(hf, root) || !h_is_canonical(hf, offset)) { set_error("fast_coset_divide: parameter not canonical"); return MZK_E_RANGE; }
-  uint64_t t[4];
-  h_powmod_u64(hf, t, root, root_order);       // ntt.rs:282-283
-  if (!h_is_one(hf, t)) { set_error("assertion failed: primitive_root.pow(root_order).is_one()"); return MZK_E_ROOT_ORDER; }
-  h_powmod_u64(hf, t, root, root_order / 2);
-  if (h_is_one(hf, t)) { set_error("assertion failed: !primitive_root.pow(root_order / 2).is_one()"); return MZK_E_ROOT_PRIM; }
+  MZK_TRY(root_check(hf, root, root_order));       // ntt.rs:281-282
   for (size_t i = 0; i < ll; i++) if (!h_is_canonical(hf, lhs + i * nl)) { set_error("fast_coset_divide: lhs[%zu] not canonical", i); return MZK_E_RANGE; }
   for (size_t i = 0; i < lr; i++) if (!h_is_canonical(hf, rhs + i * nl)) { set_error("fast_coset_divide: rhs[%zu] not canonical", i); return MZK_E_RANGE; }
   const size_t tl = trimmed_len(lhs, ll, nl), tr = trimmed_len(rhs, lr, nl);
-  if (tr == 0) { set_error("assertion failed: !rhs.is_zero()"); return MZK_E_ARG; }                           // ntt.rs:284
-  if (!(tr < tl)) { set_error("assertion failed: rhs.degree() < lhs.degree()"); return MZK_E_LENGTH; }      // ntt.rs:285 (a zero lhs has degree -1)
-  const size_t degree = tl - 1, ql = tl - tr + 1;
-  if (degree < 8) {
+  const DividePlan D = coset_divide_plan(tl, tr, root_order);
+  if (D.err) { set_error("%s", D.msg); return D.err; }
+  if (D.small) {
     *out_len = small_poly_div(hf, lhs, tl, rhs, tr, out);
     return MZK_OK;
   }
   uint64_t r[4] = {0, 0, 0, 0};
   memcpy(r, root, 8 * nl);
-  size_t order = root_order;
-  while (degree < order / 2) { h_mulmod(hf, r, r, r); order /= 2; }   // ntt.rs:299-302
-  if (tl > order) {   // the inner ntt call's own assertions (ntt.rs:8-18)
-    if (tl & (tl - 1)) { set_error("cannot compute ntt of non-power-of-two sequence"); return MZK_E_NOT_POW2; }
-    set_error("primitive root must be nth root of unity, where n is len(values)"); return MZK_E_ROOT_ORDER;
-  }
+  for (int i = 0; i < D.squarings; i++) h_mulmod(hf, r, r, r);        // ntt.rs:298-302
   hipStream_t s = ctx().stream;
   WsGuard wsg(s);
   const size_t esz = field_bytes(field_id);
   void *d_l, *d_r, *d_o;
   MZK_TRY(stage_in(ws, WS_MISC_C, lhs, tl * esz, &d_l, s));
   MZK_TRY(stage_in(ws, WS_MISC_D, rhs, tr * esz, &d_r, s));
-  MZK_TRY(ws.get(WS_NTT_IO_B, ql * esz, &d_o));
-  MZK_TRY(coset_divide_dev_impl(field_id, d_l, tl, d_r, tr, offset, r, order, d_o, s));
-  MZK_TRY(stage_out(out, d_o, ql * esz, s));
-  *out_len = ql;
+  MZK_TRY(ws.get(WS_NTT_IO_B, D.ql * esz, &d_o));
+  MZK_TRY(coset_divide_dev_impl(field_id, d_l, tl, d_r, tr, offset, r, D.order, d_o, s));
+  MZK_TRY(stage_out(out, d_o, D.ql * esz, s));
+  *out_len = D.ql;
   return MZK_OK;
 }
 
@@ -936,11 +776,7 @@ int mzk_fast_coset_divide_batch_dev(int field_id, const void* d_lhs, size_t lhs_
   const HostField* hf = host_field(field_id);
   const int nl = hf->nl;
   if (!h_is_canonical(hf, root) || !h_is_canonical(hf, offset)) { set_error("fast_coset_divide: parameter not canonical"); return MZK_E_RANGE; }
-  uint64_t t[4];
-  h_powmod_u64(hf, t, root, root_order);       // ntt.rs:282-283
-  if (!h_is_one(hf, t)) { set_error("assertion failed: primitive_root.pow(root_order).is_one()"); return MZK_E_ROOT_ORDER; }
-  h_powmod_u64(hf, t, root, root_order / 2);
-  if (h_is_one(hf, t)) { set_error("assertion failed: !primitive_root.pow(root_order / 2).is_one()"); return MZK_E_ROOT_PRIM; }
+  MZK_TRY(root_check(hf, root, root_order));       // ntt.rs:281-282
   for (size_t i = 0; i < count; i++)
     if (lhs_lens[i] > lhs_stride) { set_error("fast_coset_divide: row %zu has %zu coefficients, lhs_stride is %zu", i, lhs_lens[i], lhs_stride); return MZK_E_LENGTH; }
   if (count > ((size_t)1 << 20) || (lhs_stride && count > ((size_t)1 << 40) / lhs_stride) || (out_stride && count > ((size_t)1 << 40) / out_stride)) {
@@ -958,32 +794,28 @@ int mzk_fast_coset_divide_batch_dev(int field_id, const void* d_lhs, size_t lhs_
     MZK_TRY(rows_trimmed_len_dev(field_id, const_cast<void*>(d_lhs), lhs_stride, lhs_lens, count, 0, d_rhs, rhs_len, ws, WS_MISC_F, tl.data(), s));
   }
   const size_t tr = tl[count];
-  if (tr == 0) { set_error("assertion failed: !rhs.is_zero()"); return MZK_E_ARG; }                           // ntt.rs:284
   struct Group { size_t order; uint64_t root[4]; std::vector<CdRow> rows; };
   std::vector<Group> groups;
   std::vector<size_t> small;
   for (size_t i = 0; i < count; i++) {
-    if (!(tr < tl[i])) { set_error("assertion failed: rhs.degree() < lhs.degree() (row %zu)", i); return MZK_E_LENGTH; }   // ntt.rs:285
-    const size_t degree = tl[i] - 1, ql = tl[i] - tr + 1;
-    if (ql > out_stride) { set_error("fast_coset_divide: row %zu has a quotient of %zu coefficients, out_stride is %zu", i, ql, out_stride); return MZK_E_LENGTH; }
-    if (degree < 8) { small.push_back(i); continue; }
-    size_t order = root_order;
-    while (degree < order / 2) order /= 2;       // ntt.rs:299-302
-    if (tl[i] > order) {   // the inner ntt call's own assertions (ntt.rs:8-18)
-      if (tl[i] & (tl[i] - 1)) { set_error("cannot compute ntt of non-power-of-two sequence"); return MZK_E_NOT_POW2; }
-      set_error("primitive root must be nth root of unity, where n is len(values)"); return MZK_E_ROOT_ORDER;
-    }
+    // a row's refusals in order: the assertion on the degrees, this call's own check of the quotient against out_stride, then the
+    // inner transform's assertions (a zero denominator, ntt.rs:283, has no quotient length and refuses row 0 in the last line)
+    const DividePlan D = coset_divide_plan(tl[i], tr, root_order);
+    if (D.err == MZK_E_LENGTH) { set_error("%s (row %zu)", D.msg, i); return D.err; }
+    if (D.ql > out_stride) { set_error("fast_coset_divide: row %zu has a quotient of %zu coefficients, out_stride is %zu", i, D.ql, out_stride); return MZK_E_LENGTH; }
+    if (D.err) { set_error("%s", D.msg); return D.err; }
+    if (D.small) { small.push_back(i); continue; }
     size_t g = 0;
-    while (g < groups.size() && groups[g].order != order) g++;
+    while (g < groups.size() && groups[g].order != D.order) g++;
     if (g == groups.size()) {
       groups.push_back(Group());
-      groups[g].order = order;
+      groups[g].order = D.order;
       memset(groups[g].root, 0, sizeof groups[g].root);
       memcpy(groups[g].root, root, 8 * nl);
-      for (size_t o = root_order; o > order; o /= 2) h_mulmod(hf, groups[g].root, groups[g].root, groups[g].root);
+      for (int k = 0; k < D.squarings; k++) h_mulmod(hf, groups[g].root, groups[g].root, groups[g].root);      // ntt.rs:298-302
     }
     groups[g].rows.push_back({i, tl[i]});
-    out_lens[i] = ql;
+    out_lens[i] = D.ql;
   }
   auto fail = [&](int rc) { (void)hipStreamSynchronize(s); return rc; };
   if (!small.empty()) {      // ntt.rs:295-297 `return lhs / rhs`: at most 8 coefficients of a row visit the host; one wait in, one out for all

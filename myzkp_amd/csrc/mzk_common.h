@@ -11,6 +11,7 @@
 #include <vector>
 #include "../../include/mzk.h"
 #include "mzk_field.h"
+#include "mzk_hostfield.h"
 #include "mzk_msm_plan.h"
 #include "mzk_ws.h"
 
@@ -125,23 +126,13 @@ struct ProfScope {
   ~ProfScope() { prof_end(s, ph); }
 };
 
-// ---- host parameter math (O(log n) scalar work: roots, n^-1, canonical checks; never on the data path)
-struct HostField {
-  int nl;            // u64 limbs
-  uint64_t p[4];
-  int mont_bits;     // the device's Montgomery radix is R = 2^mont_bits (29 bits per limb: mzk_field.h)
-};
-const HostField* host_field(int fid);
-bool h_is_canonical(const HostField* f, const uint64_t* a);
-void h_mulmod(const HostField* f, uint64_t* r, const uint64_t* a, const uint64_t* b);
-void h_powmod_u64(const HostField* f, uint64_t* r, const uint64_t* a, uint64_t e);
-void h_invmod(const HostField* f, uint64_t* r, const uint64_t* a);   // a^(p-2) on the host (parameters only)
-void h_ninv_pow2(const HostField* f, unsigned log2n, uint64_t* out);  // (2^log2n)^-1 mod p, needs 2^log2n | p-1
-bool h_is_one(const HostField* f, const uint64_t* a);
-void h_rmod(const HostField* f, uint64_t* out);                       // R mod p: x -> x R mod p is one h_mulmod with it
-// One element as a kernel argument (Words8, mzk_elem.h), words [2 nl, 8) zero:
-void h_words(const uint64_t* v, int nl, u32 out8[8]);                   // limbs -> words
-void h_mont_words(const HostField* f, const uint64_t* v, u32 out8[8]);  // (v R mod p) -> words
+// ---- host parameter math: mzk_hostfield.h.  The reference's two assertions on a root and its order as an entry point's refusal:
+static inline int root_check(const HostField* f, const uint64_t* root, size_t root_order) {
+  const char* msg;
+  const int rc = h_root_check(f, root, root_order, &msg);
+  if (rc != MZK_OK) set_error("%s", msg);
+  return rc;
+}
 
 static inline bool is_pow2(size_t n) { return n && !(n & (n - 1)); }
 static inline unsigned ilog2(size_t n) { unsigned l = 0; while (((size_t)1 << l) < n) l++; return l; }   // ceil(log2 n); 0 for n <= 1

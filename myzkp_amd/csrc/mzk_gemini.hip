@@ -329,14 +329,7 @@ static int gemini_open_impl(const mzk_srs* srs, const void* d_levels, size_t n, 
   const size_t max_d = srs->n - 1;
   if (srs->n == 0 || max_d < n) { set_error("attempt to subtract with overflow (max_d %zu - d %zu): the SRS needs n + 1 powers", srs->n ? max_d : 0, n); return MZK_E_LENGTH; }
   uint64_t nb[4] = {0, 0, 0, 0}, b2[4];
-  if (beta[0] | beta[1] | beta[2] | beta[3]) {            // (0 - beta).sanitize()
-    unsigned __int128 br = 0;
-    for (int i = 0; i < 4; i++) {
-      const unsigned __int128 d = (unsigned __int128)fr->p[i] - beta[i] - (uint64_t)br;
-      nb[i] = (uint64_t)d;
-      br = (d >> 64) ? 1 : 0;
-    }
-  }
+  h_negmod(fr, nb, beta);                                 // (0 - beta).sanitize()
   h_mulmod(fr, b2, beta, beta);
   if (el > 0 && (!memcmp(beta, nb, 32) || !memcmp(beta, b2, 32) || !memcmp(nb, b2, 32))) {
     set_error("gemini_open: beta, -beta and beta^2 must be distinct (beta in {0, 1, -1}: interpolate divides by zero)");

@@ -283,10 +283,9 @@ __device__ __forceinline__ void radix4_wave(Fe<P>& x0, Fe<P>& x1, Fe<P>& x2, Fe<
 }
 // Stage pairs whose twiddles are the same for a whole wave (groups are enumerated twiddle-major: 2^lgrest consecutive groups
 // share j1, so from lgrest >= 6 on a wave has ONE j1) take them from the plan's Shoup table by scalar loads -- entry ti =
-// 32 words: limbs of the plain w^ti at [0, 9), of floor(w^ti 2^261 / p) at [16, 25) -- and multiply by the precomputed-quotient
+// SHOUP_ENTRY_WORDS = 32 words (h_shoup_entry, mzk_hostfield.h): limbs of the plain w^ti at [0, 9), of floor(w^ti 2^261 / p) at [16, 25) -- and multiply by the precomputed-quotient
 // product (fe_shoup_mul: 143 multiply-adds, the constant in scalar registers) instead of the Montgomery one (162 + the twiddle's
 // eight LDS reads and its unpacking).  BN254 Fr only (M128's sparse modulus makes its Montgomery reduction cheaper than that).
-constexpr int SHOUP_ENTRY_WORDS = 32;
 template <class P> struct HasShoup { static constexpr bool value = false; };
 template <> struct HasShoup<FrParams> { static constexpr bool value = true; };
 template <class P, bool LAZY>
@@ -825,37 +824,8 @@ static int build_shoup_table(const HostField* hf, const uint64_t* root, uint64_t
   std::vector<u32> tab(cnt * SHOUP_ENTRY_WORDS, 0u);
   uint64_t w[4], cur[4] = {1, 0, 0, 0};
   h_powmod_u64(hf, w, root, emul);
-  auto limbs_of = [](const uint64_t* v5, u32* dst) {      // 9 limbs of 29 bits from a 5 x 64-bit number
-    for (int i = 0; i < 9; i++) {
-      const int bit = 29 * i, k = bit >> 6, sft = bit & 63;
-      uint64_t x = v5[k] >> sft;
-      if (sft > 35 && k + 1 < 5) x |= v5[k + 1] << (64 - sft);
-      dst[i] = (u32)(x & 0x1fffffffu);
-    }
-  };
   for (size_t j = 0; j < cnt; j++) {
-    uint64_t v5[5] = {cur[0], cur[1], cur[2], cur[3], 0};
-    limbs_of(v5, &tab[j * SHOUP_ENTRY_WORDS]);
-    // q = floor(cur 2^261 / p): restoring division, one quotient bit per step (cur < p < 2^254, so the remainder stays below 2^255)
-    uint64_t rem[4] = {cur[0], cur[1], cur[2], cur[3]}, q[5] = {0, 0, 0, 0, 0};
-    for (int step = 0; step < 261; step++) {
-      for (int i = 4; i > 0; i--) q[i] = (q[i] << 1) | (q[i - 1] >> 63);
-      q[0] <<= 1;
-      for (int i = 3; i > 0; i--) rem[i] = (rem[i] << 1) | (rem[i - 1] >> 63);
-      rem[0] <<= 1;
-      bool ge = true;
-      for (int i = 3; i >= 0; i--) if (rem[i] != hf->p[i]) { ge = rem[i] > hf->p[i]; break; }
-      if (ge) {
-        unsigned __int128 br = 0;
-        for (int i = 0; i < 4; i++) {
-          const unsigned __int128 d = (unsigned __int128)rem[i] - hf->p[i] - (uint64_t)br;
-          rem[i] = (uint64_t)d;
-          br = (d >> 64) & 1;
-        }
-        q[0] |= 1;
-      }
-    }
-    limbs_of(q, &tab[j * SHOUP_ENTRY_WORDS + 16]);
+    h_shoup_entry(hf, cur, &tab[j * SHOUP_ENTRY_WORDS]);
     h_mulmod(hf, cur, cur, w);
   }
   MZK_TRY(out->alloc(tab.size() * sizeof(u32), "transform plan tables"));

@@ -27,10 +27,11 @@
 #include "mzk_common.h"
 #include "mzk_elem.h"
 #include "mzk_field_asm.h"
+#include "mzk_prefix_plan.h"
 
 namespace mzk {
 
-constexpr int CHUNK = 64;        // points per level-0 polynomial = one wave
+constexpr int CHUNK = 64;       // points per level-0 polynomial = one wave
 
 // plain-domain helpers: canonical in, canonical out
 template <class P> __device__ __forceinline__ Fe<P> pl_mul(const Fe<P>& x, const Fe<P>& y) { return fe_reduce<P>(FeAsm<P>::mul(FeAsm<P>::mul(x, y), fe_r2<P>())); }
@@ -418,17 +419,10 @@ template <class P> struct PolyTree {
   }
 };
 
-static size_t next_pow2(size_t x) { size_t p = 1; while (p < x) p <<= 1; return p; }
-
 // shared argument checks: the reference's two assertions (ntt.rs:122-123 etc.) and canonical inputs
 static int check_root(const HostField* hf, const uint64_t* root, size_t root_order) {
   if (!h_is_canonical(hf, root)) { set_error("poly: root not canonical"); return MZK_E_RANGE; }
-  uint64_t t[4];
-  h_powmod_u64(hf, t, root, root_order);
-  if (!h_is_one(hf, t)) { set_error("assertion failed: primitive_root.pow(root_order).is_one()"); return MZK_E_ROOT_ORDER; }
-  h_powmod_u64(hf, t, root, root_order / 2);
-  if (h_is_one(hf, t)) { set_error("assertion failed: !primitive_root.pow(root_order / 2).is_one()"); return MZK_E_ROOT_PRIM; }
-  return MZK_OK;
+  return root_check(hf, root, root_order);
 }
 static int check_canonical(const HostField* hf, const uint64_t* v, size_t n, const char* what) {
   for (size_t i = 0; i < n; i++) if (!h_is_canonical(hf, v + i * hf->nl)) { set_error("poly: %s[%zu] not canonical", what, i); return MZK_E_RANGE; }
@@ -531,14 +525,7 @@ static int evaluate_impl(int fid, const uint64_t* coef, size_t m, const uint64_t
     for (size_t i = 0; i < n; i++) {       // acc = acc * x^N + f_b(x)   (n host products per block: parameter-sized next to the tree work)
       uint64_t t[4];
       h_mulmod(hf, t, acc.data() + i * nl, xn.data() + i * nl);
-      // t + blk mod p
-      unsigned __int128 c = 0;
-      uint64_t r[4] = {0, 0, 0, 0};
-      for (int k = 0; k < nl; k++) { c += (unsigned __int128)t[k] + blk[i * nl + k]; r[k] = (uint64_t)c; c >>= 64; }
-      bool ge = c != 0;
-      if (!ge) { ge = true; for (int k = nl - 1; k >= 0; k--) if (r[k] != hf->p[k]) { ge = r[k] > hf->p[k]; break; } }
-      if (ge) { unsigned __int128 br = 0; for (int k = 0; k < nl; k++) { unsigned __int128 d = (unsigned __int128)r[k] - hf->p[k] - (uint64_t)br; r[k] = (uint64_t)d; br = (d >> 64) & 1; } }
-      memcpy(acc.data() + i * nl, r, 8 * nl);
+      h_addmod(hf, acc.data() + i * nl, t, blk.data() + i * nl);
     }
   }
   memcpy(out, acc.data(), n * esz);
@@ -581,8 +568,9 @@ __global__ __launch_bounds__(256) void k_row_len(const u32* __restrict__ rows, s
 // C[j][i] = - sum_t Ainv[j][t] x_i^(1+t) is part of the plan: a call costs m dot products of length n per register and ONE batched
 // inverse transform of N points -- O(n log n + m n) where the subproduct tree is O(n log^2 n) with ~50 launches.  The coefficients are
 // those of the same polynomial the reference's recursion returns (ntt.rs:203-252), trimmed the same way; any other domain (and a prefix
-// with more than PREFIX_MAX_MISSING points missing) goes through the tree below.
-constexpr size_t PREFIX_MAX_MISSING = 64;
+// with more than PREFIX_MAX_MISSING points missing) goes through the tree below.  What the host derives from the domain alone
+// (prefix_candidate, prefix_system_inverse, prefix_zerofier_params) is mzk_prefix_plan.h.
+static bool prefix_enabled() { return tune_int("MZK_INTERP_PREFIX", 1) != 0; }      // tuning build: 0 = every domain through the tree (A/B, tests of the tree)
 // C[j * n + i] = Montgomery form of  - x_i sum_t ainv[j * m + t] x_i^t  (Horner in x_i); blockIdx.y = j
 template <class P>
 __global__ __launch_bounds__(256) void k_prefix_weights(const u32* __restrict__ domain, size_t n, const u32* __restrict__ ainv, int m, u32* __restrict__ C) {
@@ -623,49 +611,8 @@ __global__ __launch_bounds__(PREFIX_NT) void k_prefix_missing(const u32* __restr
   }
 }
 
-// host side (parameters only): a + b, a - b mod p for canonical a, b
-static void hp_add(const HostField* f, uint64_t* r, const uint64_t* a, const uint64_t* b) {
-  uint64_t t[4] = {0, 0, 0, 0};
-  unsigned __int128 c = 0;
-  for (int i = 0; i < f->nl; i++) { c += (unsigned __int128)a[i] + b[i]; t[i] = (uint64_t)c; c >>= 64; }
-  bool ge = c != 0;
-  if (!ge) { ge = true; for (int k = f->nl - 1; k >= 0; k--) if (t[k] != f->p[k]) { ge = t[k] > f->p[k]; break; } }
-  if (ge) { unsigned __int128 br = 0; for (int k = 0; k < f->nl; k++) { unsigned __int128 d = (unsigned __int128)t[k] - f->p[k] - (uint64_t)br; t[k] = (uint64_t)d; br = (d >> 64) & 1; } }
-  for (int i = 0; i < f->nl; i++) r[i] = t[i];
-}
-static void hp_sub(const HostField* f, uint64_t* r, const uint64_t* a, const uint64_t* b) {
-  uint64_t nb[4] = {0, 0, 0, 0};
-  bool zero = true;
-  for (int i = 0; i < f->nl; i++) zero = zero && b[i] == 0;
-  if (!zero) { unsigned __int128 br = 0; for (int k = 0; k < f->nl; k++) { unsigned __int128 d = (unsigned __int128)f->p[k] - b[k] - (uint64_t)br; nb[k] = (uint64_t)d; br = (d >> 64) & 1; } }
-  hp_add(f, r, a, nb);
-}
-// domain[i] == g^i for i < n with g = domain[1] of order exactly N = next_pow2(n), at most PREFIX_MAX_MISSING points of the subgroup
-// missing.  Two steps: the host looks at the order of g and at three points (an arbitrary domain leaves here after a few short
-// exponentiations), then a kernel compares EVERY point with its power of g (n host products were 0.3 ms at 2^14 points -- more than the
-// zerofier below takes) and raises a flag on the first difference.
-static bool prefix_candidate(const HostField* hf, const uint64_t* domain, size_t n, size_t* N_out) {
-  static const int enabled = tune_int("MZK_INTERP_PREFIX", 1);      // tuning build: 0 = every domain through the tree (A/B, tests of the tree)
-  if (!enabled || n < 2) return false;
-  const int nl = hf->nl;
-  const size_t N = next_pow2(n);
-  if (N - n > PREFIX_MAX_MISSING || (N - n) * n * (size_t)nl * 8 > ((size_t)1 << 30)) return false;
-  if (!h_is_one(hf, domain)) return false;
-  const uint64_t* g = domain + nl;
-  uint64_t t[4] = {0, 0, 0, 0};
-  h_powmod_u64(hf, t, g, N);
-  if (!h_is_one(hf, t)) return false;
-  h_powmod_u64(hf, t, g, N / 2);
-  if (h_is_one(hf, t)) return false;
-  if (n > 2) {
-    h_mulmod(hf, t, g, g);
-    if (memcmp(t, domain + 2 * nl, 8 * (size_t)nl)) return false;
-    h_powmod_u64(hf, t, g, (uint64_t)(n - 1));
-    if (memcmp(t, domain + (n - 1) * nl, 8 * (size_t)nl)) return false;
-  }
-  *N_out = N;
-  return true;
-}
+// After prefix_candidate's look at three points, EVERY point is compared with its power of g = domain[1]; a flag is raised on the
+// first difference.
 template <class P>
 __global__ __launch_bounds__(256) void k_prefix_check(const u32* __restrict__ domain, size_t n, u32* __restrict__ flag) {
   const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -687,43 +634,9 @@ template <class P> static int prefix_check_launch(const void* d_domain, size_t n
   MZK_HIP(hipGetLastError());
   return MZK_OK;
 }
-// Ainv (m x m, row-major, canonical) of A[t][j] = x_(n+j)^(1+t) by Gauss-Jordan on the host; false if a pivot is missing (cannot
-// happen for distinct non-zero x: every leading minor is a Vandermonde determinant times a product of x's)
-static bool prefix_system_inverse(const HostField* hf, const uint64_t* g, size_t n, size_t m, std::vector<uint64_t>* out) {
-  const size_t nl = (size_t)hf->nl;
-  std::vector<uint64_t> a(m * 2 * m * 4, 0);                  // [A | I], four limbs per entry
-  auto at = [&](size_t row, size_t col) { return a.data() + (row * 2 * m + col) * 4; };
-  for (size_t j = 0; j < m; j++) {
-    uint64_t x[4] = {0, 0, 0, 0}, pw[4] = {0, 0, 0, 0};
-    h_powmod_u64(hf, x, g, (uint64_t)(n + j));
-    memcpy(pw, x, 8 * nl);
-    for (size_t t = 0; t < m; t++) { memcpy(at(t, j), pw, 8 * nl); h_mulmod(hf, pw, pw, x); }
-    at(j, m + j)[0] = 1;
-  }
-  auto is_zero = [&](const uint64_t* v) { for (size_t k = 0; k < nl; k++) if (v[k]) return false; return true; };
-  for (size_t col = 0; col < m; col++) {
-    size_t piv = col;
-    while (piv < m && is_zero(at(piv, col))) piv++;
-    if (piv == m) return false;
-    if (piv != col) for (size_t k = 0; k < 2 * m * 4; k++) std::swap(a[col * 2 * m * 4 + k], a[piv * 2 * m * 4 + k]);
-    uint64_t inv[4] = {0, 0, 0, 0};
-    h_invmod(hf, inv, at(col, col));
-    for (size_t k = 0; k < 2 * m; k++) h_mulmod(hf, at(col, k), at(col, k), inv);
-    for (size_t row = 0; row < m; row++) {
-      if (row == col || is_zero(at(row, col))) continue;
-      uint64_t f[4] = {0, 0, 0, 0}, prod[4] = {0, 0, 0, 0};
-      memcpy(f, at(row, col), 8 * nl);
-      for (size_t k = 0; k < 2 * m; k++) { h_mulmod(hf, prod, at(col, k), f); hp_sub(hf, at(row, k), at(row, k), prod); }
-    }
-  }
-  out->assign(m * m * nl, 0);
-  for (size_t j = 0; j < m; j++) for (size_t t = 0; t < m; t++) memcpy(out->data() + (j * m + t) * nl, at(j, m + t), 8 * nl);
-  return true;
-}
 
-// The zerofier of such a prefix (FastStark's transition zerofier, fast_stark.rs:53-57: omicron^i for i < cycles - 1): Z D = X^N - 1 with
-// D = prod_j (X - x_(n+j)) over the m missing points, so the coefficients of Z are minus those of the power series 1 / D, and by partial
-// fractions  z_k = sum_j rho_j w_j^(k+1),  k <= n,  w_j = 1 / x_(n+j),  rho_j = 1 / prod_(l != j) (x_(n+j) - x_(n+l))  (host, m^2 products).
+// The zerofier of such a prefix (FastStark's transition zerofier, fast_stark.rs:53-57: omicron^i for i < cycles - 1):
+// z_k = sum_j rho_j w_j^(k+1),  k <= n, over the m missing points (prefix_zerofier_params).
 // One launch: a lane owns ZERO_CHUNK consecutive coefficients, one exponentiation per missing point and lane.  params: m pairs (rho_j, w_j).
 constexpr int ZERO_CHUNK = 8;
 template <class P>
@@ -745,29 +658,6 @@ __global__ __launch_bounds__(256) void k_prefix_zerofier(const u32* __restrict__
 #pragma unroll
   for (int c = 0; c < ZERO_CHUNK; c++) if (k0 + c < count) fe_gstore<P>(out, k0 + c, acc[c]);
 }
-// (rho_j, w_j) for j < m, canonical, interleaved; false if two missing points coincide (cannot happen in a subgroup)
-static bool prefix_zerofier_params(const HostField* hf, const uint64_t* g, size_t n, size_t N, std::vector<uint64_t>* out) {
-  const size_t nl = (size_t)hf->nl, m = N - n;
-  std::vector<uint64_t> x(m * 4, 0);
-  for (size_t j = 0; j < m; j++) h_powmod_u64(hf, x.data() + 4 * j, g, (uint64_t)(n + j));
-  out->assign(2 * m * nl, 0);
-  for (size_t j = 0; j < m; j++) {
-    uint64_t prod[4] = {1, 0, 0, 0}, d[4] = {0, 0, 0, 0}, inv[4] = {0, 0, 0, 0}, w[4] = {0, 0, 0, 0};
-    for (size_t l = 0; l < m; l++) {
-      if (l == j) continue;
-      hp_sub(hf, d, x.data() + 4 * j, x.data() + 4 * l);
-      bool zero = true;
-      for (size_t k = 0; k < nl; k++) zero = zero && d[k] == 0;
-      if (zero) return false;
-      h_mulmod(hf, prod, prod, d);
-    }
-    h_invmod(hf, inv, prod);
-    h_powmod_u64(hf, w, g, (uint64_t)(N - (n + j)));           // 1 / x_(n+j) = g^(N - n - j)
-    memcpy(out->data() + (2 * j) * nl, inv, 8 * nl);
-    memcpy(out->data() + (2 * j + 1) * nl, w, 8 * nl);
-  }
-  return true;
-}
 
 template <class P>
 static int zerofier_of_prefix(int fid, const uint64_t* domain, size_t n, size_t len, uint64_t* out, hipStream_t s, bool* done) {
@@ -775,7 +665,7 @@ static int zerofier_of_prefix(int fid, const uint64_t* domain, size_t n, size_t 
   const size_t nl = (size_t)hf->nl, esz = field_bytes(fid);
   size_t N = 0;
   *done = false;
-  if (!prefix_candidate(hf, domain, n, &N)) return MZK_OK;
+  if (!prefix_enabled() || !prefix_candidate(hf, domain, n, &N)) return MZK_OK;
   const size_t m = N - n;
   std::vector<uint64_t> params;
   if (m && !prefix_zerofier_params(hf, domain + nl, n, N, &params)) return MZK_OK;
@@ -805,9 +695,8 @@ static int zerofier_of_prefix(int fid, const uint64_t* domain, size_t n, size_t 
   if (flag) return MZK_OK;                                    // not a prefix after all: the caller runs the tree
   memset(out, 0, len * esz);
   if (m == 0) {                                               // the whole subgroup: X^N - 1
-    uint64_t one[4] = {1, 0, 0, 0}, zero[4] = {0, 0, 0, 0}, neg[4] = {0, 0, 0, 0};
-    hp_sub(hf, neg, zero, one);
-    memcpy(out, neg, 8 * nl);
+    const uint64_t one[4] = {1, 0, 0, 0};
+    h_negmod(hf, out, one);
     out[N * nl] = 1;
   } else memcpy(out, z.data(), (n + 1) * esz);
   *done = true;
@@ -880,7 +769,7 @@ static int interp_plan_get(int fid, const uint64_t* domain, size_t n, const uint
   if (rc == MZK_OK) rc = pl->d_dom.alloc(n * esz);
   if (rc == MZK_OK && hipMemcpyAsync(pl->d_dom.p, domain, n * esz, hipMemcpyHostToDevice, s) != hipSuccess) rc = hip_fail(hipGetLastError(), "hipMemcpyAsync", __FILE__, __LINE__);
   std::vector<uint64_t> ainv;
-  if (rc == MZK_OK && prefix_candidate(hf, domain, n, &pl->pN)) {
+  if (rc == MZK_OK && prefix_enabled() && prefix_candidate(hf, domain, n, &pl->pN)) {
     WsBlock d_flag;
     u32 flag = 1;
     rc = d_flag.alloc(4);

@@ -1,4 +1,5 @@
-"""The two closed forms behind the subgroup-prefix routines of mzk_poly.hip (round 6), checked with Python integers on the CPU -- no GPU, no
+"""The two closed forms behind the subgroup-prefix routines (host parameters: myzkp_amd/csrc/mzk_prefix_plan.h, whose C++ is run against
+these forms by test_hostcheck_prefix_plan.py; kernels: mzk_poly.hip), checked with Python integers on the CPU -- no GPU, no
 library: (1) the interpolant through the first n points of a subgroup of order N is the inverse transform of the values extended by
 u_j = sum_i v_i C[j][i], C[j][i] = - sum_t Ainv[j][t] x_i^(1+t), A[t][j] = x_(n+j)^(1+t); (2) the zerofier of those points has the
 coefficients z_k = sum_j rho_j w_j^(k+1), w_j = 1 / x_(n+j), rho_j = 1 / prod_(l != j) (x_(n+j) - x_(n+l)).  References: ntt.rs:118-143 (fast_zerofier),
