@@ -666,6 +666,54 @@ int mzk_sumcheck_product_prove_dev(const void* d_tables, size_t num_vars, size_t
  * a coefficient that is not canonical MZK_E_RANGE (host form).  d_evals may equal d_coef. */
 int mzk_mle_evals_from_coeffs(const uint64_t* coef, size_t num_vars, uint64_t* evals);
 int mzk_mle_evals_from_coeffs_dev(const void* d_coef, size_t num_vars, void* d_evals, void* stream);
+/* evals_over_boolean_hypercube for SPARSE factors -- the reference prover's first kernel (eval_all_binary_combinations over
+ * convert_mpoly_to_kernel_format, prover.rs:124-187) -- and the prover from the reference's own inputs.  n_factors MPolynomials as the
+ * flat term table of mzk_mpoly_compose over Fr: factor f = terms [term_offsets[f], term_offsets[f+1]), term t = term_coefs[t] (canonical)
+ * and the exponents term_exps[t * num_vars .. (t+1) * num_vars); a HashMap key shorter than num_vars is padded with zeros by the
+ * caller, num_vars is the maximum over the factors (prover.rs:99).  Table of factor f at tables[4 (f 2^num_vars + b)]:
+ *   evals[b] = sum_t c_t prod_i b_i^(e_t[i]),  b_i = bit (num_vars-1-i) of b (BitCombinationsDictOrder),  0^0 = 1.
+ * Only the support of a term matters on {0,1}: with mask_t = OR over {i: e_t[i] > 0} of 1 << (num_vars-1-i), evals[b] is the sum of
+ * c_t over the terms with mask_t & ~b == 0 -- a factor that is not multilinear gives the table of its multilinearisation, as the
+ * reference's kernel does.  Rows with equal masks add up (duplicate rows and rows such as x0^2, x0^5 included); zero coefficients are
+ * allowed; a factor without terms is the zero table.  Coefficients of equal masks are added on the host.
+ *   MZK_HYPER_TILE     one launch for all factors: a workgroup builds 2^min(num_vars,10) consecutive entries in LDS from the masks whose
+ *                      high bits fit its own and writes them once; nothing of size 2^num_vars is read, uploaded or zero-filled.
+ *   MZK_HYPER_SCATTER  hipMemsetAsync of the tables, one kernel writes every merged coefficient to table[mask], then the butterfly of
+ *                      mzk_mle_evals_from_coeffs_dev in place per factor: the form for term counts near 2^num_vars.
+ *   MZK_HYPER_AUTO     TILE while no factor has more than 256 groups (distinct values of mask >> 10) or more than 4096 distinct
+ *                      masks, else SCATTER.
+ * mzk_mpoly_hypercube_plan (host only, needs no device) reports what a call with these arguments does: the form that runs, tile_log =
+ * min(num_vars, 10), the totals over the factors of terms, distinct masks and groups and the largest per-factor counts, per factor the
+ * distinct masks and groups (the first MZK_HYPER_PLAN_FACTORS factors), kernel launches and memsets, the grid of the form's own kernel,
+ * the butterfly passes per factor, the bytes uploaded, the workspace bytes of the _dev form and the bytes of the tables.
+ * The term table is HOST memory in every form.  The _dev forms return once it has been uploaded (that waits for earlier work on
+ * `stream`); the kernels are only enqueued.  d_tables: n_factors * 2^num_vars * 32 bytes, 16-byte aligned, laid out as
+ * mzk_sumcheck_product_prove_dev reads them.  mzk_sumcheck_product_prove_terms* builds the tables in the context's workspace
+ * (MZK_HYPER_AUTO) and runs mzk_sumcheck_product_prove_dev on them: same packed proof, same header convention.
+ * Errors, all before anything is enqueued: null pointer, a form other than the three, misaligned d_tables / d_proof: MZK_E_ARG;
+ * num_vars > 30, decreasing term_offsets, 2^28 terms or more, 65536 factors or more: MZK_E_LENGTH; a coefficient that is not
+ * canonical: MZK_E_RANGE; prove_terms: every refusal of mzk_sumcheck_product_prove with its code.  num_vars == 0 (evals): one value
+ * per factor, the sum of its coefficients.  n_factors == 0 (evals): MZK_OK, nothing written. */
+enum { MZK_HYPER_AUTO = 0, MZK_HYPER_TILE = 1, MZK_HYPER_SCATTER = 2 };
+enum { MZK_HYPER_PLAN_FACTORS = 8 };
+typedef struct mzk_hypercube_plan {
+  uint64_t form, tile_log, terms, masks, groups, max_masks, max_groups;
+  uint64_t launches, memsets, grid_x, grid_y, mle_passes;
+  uint64_t upload_bytes, workspace_bytes, table_bytes;
+  uint64_t factor_masks[MZK_HYPER_PLAN_FACTORS], factor_groups[MZK_HYPER_PLAN_FACTORS];
+} mzk_hypercube_plan;
+int mzk_mpoly_hypercube_plan(const uint32_t* term_exps, const size_t* term_offsets, size_t n_factors, size_t num_vars, int form,
+                             mzk_hypercube_plan* out);
+int mzk_mpoly_hypercube_evals(const uint64_t* term_coefs, const uint32_t* term_exps, const size_t* term_offsets, size_t n_factors, size_t num_vars,
+                              int form, uint64_t* tables);
+int mzk_mpoly_hypercube_evals_dev(const uint64_t* term_coefs, const uint32_t* term_exps, const size_t* term_offsets, size_t n_factors,
+                                  size_t num_vars, int form, void* d_tables, void* stream);
+int mzk_sumcheck_product_prove_terms(const uint64_t* term_coefs, const uint32_t* term_exps, const size_t* term_offsets, size_t n_factors,
+                                     size_t num_vars, size_t max_degree, const uint8_t* header, size_t header_len, size_t header_objects,
+                                     uint8_t* proof_out, size_t proof_cap);
+int mzk_sumcheck_product_prove_terms_dev(const uint64_t* term_coefs, const uint32_t* term_exps, const size_t* term_offsets, size_t n_factors,
+                                         size_t num_vars, size_t max_degree, const uint8_t* header, size_t header_len, size_t header_objects,
+                                         void* d_proof, size_t proof_cap, void* stream);
 
 /* ---- symbolic evaluation of multivariate constraints and the combination of the quotients (FastStark::prove) ----------
  * MPolynomial::evaluate_symbolic (algebra/mpolynomials.rs:125-141; zkstark/fast_stark.rs:246-259 composes every transition
@@ -1088,7 +1136,8 @@ enum { MZK_PH_MSM_PREPARE = 0, MZK_PH_MSM_SORT = 1, MZK_PH_MSM_ACCUMULATE = 2, M
        MZK_PH_SCP_ROUND = 14,         /* ... the fold-and-sum kernels of the later grid rounds */
        MZK_PH_SCP_ROUND_END = 15,     /* ... the one-workgroup transcript steps between them */
        MZK_PH_SCP_TAIL = 16,          /* ... every round from 2^7 entries per factor down, one launch */
-       MZK_PH_COUNT = 17 };
+       MZK_PH_HYPERCUBE = 17,         /* mzk_mpoly_hypercube_evals: the device work behind the upload (tile kernel, or memset, scatter and butterfly) */
+       MZK_PH_COUNT = 18 };
 int mzk_prof_enable(int on);
 /* bit p set = phase p gets its event pair while profiling is on (default: all).  An event pair costs a few
  * microseconds of stream time, so a timed region instruments only the kernel it prices. */

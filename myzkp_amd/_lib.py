@@ -748,6 +748,102 @@ def mle_evals_from_coeffs(coef, device_ptr=None, num_vars=None, out_ptr=None, st
     return out
 
 
+HYPER_AUTO, HYPER_TILE, HYPER_SCATTER = 0, 1, 2
+HYPER_PLAN_FACTORS = 8
+_HYPER_PLAN_SCALARS = ("form", "tile_log", "terms", "masks", "groups", "max_masks", "max_groups", "launches", "memsets", "grid_x", "grid_y",
+                       "mle_passes", "upload_bytes", "workspace_bytes", "table_bytes")
+
+
+class _HypercubePlan(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_uint64) for n in _HYPER_PLAN_SCALARS] + [("factor_masks", ctypes.c_uint64 * HYPER_PLAN_FACTORS),
+                                                                      ("factor_groups", ctypes.c_uint64 * HYPER_PLAN_FACTORS)]
+
+
+def hypercube_term_table(factors, num_vars=None):
+    """Sparse Fr factors -> the flat term table of mzk_mpoly_hypercube_evals: (coefficients (T, 4) limbs, exponents (T, num_vars)
+    uint32, offsets (size_t), num_vars).  A factor is an MPolynomial's dictionary {exponent tuple: int} or a pair of arrays
+    (coefs (T, 4) limbs, exps (T, n) uint32); num_vars defaults to the longest key, shorter keys are padded with zeros."""
+    parts = []
+    for f in factors:
+        if isinstance(f, dict):
+            keys = list(f)
+            width = max([len(k) for k in keys], default=0)
+            e = np.zeros((len(keys), width), dtype=np.uint32)
+            for t, key in enumerate(keys):
+                e[t, :len(key)] = [int(x) for x in key]
+            c = to_limbs([f[key] for key in keys], 4)
+        else:
+            c = np.ascontiguousarray(f[0], dtype=np.uint64).reshape(-1, 4)
+            e = np.ascontiguousarray(f[1], dtype=np.uint32)
+            if e.ndim != 2 or e.shape[0] != c.shape[0]:
+                e = e.reshape(c.shape[0], e.size // c.shape[0]) if c.shape[0] else np.zeros((0, 0), dtype=np.uint32)
+        parts.append((c, e))
+    widest = max([e.shape[1] for _, e in parts], default=0)
+    nv = widest if num_vars is None else int(num_vars)
+    if nv < widest:
+        raise MzkError(-5, "a term has %d exponents, num_vars is %d" % (widest, nv))
+    total = sum(c.shape[0] for c, _ in parts)
+    tc, te, offs = np.zeros((total, 4), dtype=np.uint64), np.zeros((total, nv), dtype=np.uint32), [0]
+    for c, e in parts:
+        at = offs[-1]
+        tc[at:at + c.shape[0]] = c
+        te[at:at + c.shape[0], :e.shape[1]] = e
+        offs.append(at + c.shape[0])
+    return tc, te, (ctypes.c_size_t * len(offs))(*offs), nv
+
+
+def mpoly_hypercube_plan(factors, num_vars=None, form=HYPER_AUTO):
+    """mzk_mpoly_hypercube_plan (host only): what mpoly_hypercube_evals does for these factors, as a dict -- the form that runs, the
+    distinct masks and groups (totals, maxima and per factor), launches, grid, bytes uploaded, workspace and table bytes."""
+    _, te, toff, nv = hypercube_term_table(factors, num_vars)
+    out = _HypercubePlan()
+    _check(lib().mzk_mpoly_hypercube_plan(_p(te), toff, ctypes.c_size_t(len(factors)), ctypes.c_size_t(nv), int(form), ctypes.byref(out)))
+    d = {n: int(getattr(out, n)) for n in _HYPER_PLAN_SCALARS}
+    shown = min(len(factors), HYPER_PLAN_FACTORS)
+    d["factor_masks"] = [int(out.factor_masks[f]) for f in range(shown)]
+    d["factor_groups"] = [int(out.factor_groups[f]) for f in range(shown)]
+    return d
+
+
+def mpoly_hypercube_evals(factors, num_vars=None, form=HYPER_AUTO, out_ptr=None, stream=None):
+    """evals_over_boolean_hypercube of sparse factors (mzk_mpoly_hypercube_evals): the (k, 2^num_vars, 4) tables, variable 0 the most
+    significant index bit, as sumcheck_product_prove takes them.  out_ptr: the tables are written to that device buffer
+    (mzk_mpoly_hypercube_evals_dev, enqueued on `stream`) and None is returned."""
+    tc, te, toff, nv = hypercube_term_table(factors, num_vars)
+    args = (_p(tc), _p(te), toff, ctypes.c_size_t(len(factors)), ctypes.c_size_t(nv), int(form))
+    if out_ptr is not None:
+        _check(lib().mzk_mpoly_hypercube_evals_dev(*args, ctypes.c_void_p(int(out_ptr)), ctypes.c_void_p(stream)))
+        return None
+    out = np.empty((len(factors), 1 << nv, 4), dtype=np.uint64)
+    _check(lib().mzk_mpoly_hypercube_evals(*args, _p(out)))
+    return out
+
+
+def sumcheck_product_prove_terms(factors, max_degree, header_objects=(), num_vars=None, device=False, raw=False):
+    """SumCheckProverGPU::prove from the reference's own inputs (mzk_sumcheck_product_prove_terms): sparse factors as in
+    hypercube_term_table, their tables built on the device and never seen by the host.  device=True: the proof is written to a torch
+    buffer on torch's current stream (the _dev form).  Returns what sumcheck_product_prove returns."""
+    tc, te, toff, nv = hypercube_term_table(factors, num_vars)
+    k = len(factors)
+    header = sumcheck_frame_header(header_objects)
+    hbuf = (ctypes.c_uint8 * max(len(header), 1)).from_buffer_copy(header or b"\0")
+    _, total = sumcheck_product_layout(nv, k, max_degree, len(header))
+    args = (_p(tc), _p(te), toff, ctypes.c_size_t(k), ctypes.c_size_t(nv), ctypes.c_size_t(max_degree), hbuf, ctypes.c_size_t(len(header)),
+            ctypes.c_size_t(len(header_objects)))
+    if not device:
+        buf = (ctypes.c_uint8 * total)()
+        _check(lib().mzk_sumcheck_product_prove_terms(*args, buf, ctypes.c_size_t(total)))
+        packed = bytes(buf)
+    else:
+        import torch
+        proof = torch.empty(total, dtype=torch.uint8, device="cuda")
+        stream = torch.cuda.current_stream()
+        _check(lib().mzk_sumcheck_product_prove_terms_dev(*args, ctypes.c_void_p(proof.data_ptr()), ctypes.c_size_t(total), ctypes.c_void_p(stream.cuda_stream)))
+        stream.synchronize()
+        packed = proof.cpu().numpy().tobytes()
+    return packed if raw else sumcheck_product_unpack(nv, k, max_degree, len(header), packed)
+
+
 _SUMCHECK_CB = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64))
 
 

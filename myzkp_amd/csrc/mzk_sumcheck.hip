@@ -1,6 +1,7 @@
 // mzk_sumcheck.hip -- the product sum-check prover over evaluation tables (examples/sumcheck/src/prover.rs:98-247, the
-// `*_cpu` twins of examples/sumcheck/src/utils.rs) with its Fiat-Shamir transcript on the device, and the subset-sum butterfly that
-// turns dense multilinear coefficients into such a table (evals_over_boolean_hypercube).
+// `*_cpu` twins of examples/sumcheck/src/utils.rs) with its Fiat-Shamir transcript on the device, the subset-sum butterfly that
+// turns dense multilinear coefficients into such a table (evals_over_boolean_hypercube), and the tables of sparse MPolynomial factors
+// from their term table (the reference prover's eval_all_binary_combinations), with the prover behind them in one call.
 //
 // k factors as tables of n = 2^el canonical Fr values, variable 0 the most significant index bit.  Round j (m = n >> j live entries,
 // h = m / 2):  s_j(c) = sum_{i<h} prod_f (T_f[i] + c (T_f[i+h] - T_f[i])), c = 0..=d, pushed as d + 1 objects vec![bincode(s_j(c))];
@@ -21,11 +22,15 @@
 //   k_sc_tail         one wave: every round from SC_TAIL_M live entries per factor down, the tables in LDS, the transcript step
 //                     between the rounds inside the kernel; FINALS, TRANSCRIPT_LEN and STATUS at the end.
 //   k_mle_pass        the subset-sum butterfly, up to MLE_TILE_LOG index bits per pass in LDS.
+//   k_hyper_tile      a sparse factor's evaluation table tile by tile: the support masks that fit a tile's high bits go into LDS, the
+//                     butterfly's stages run there, the tile is written once (eval_all_binary_combinations, MZK_HYPER_TILE).
+//   k_hyper_scatter   merged coefficients to table[mask] of zero-filled tables, k_mle_pass after it (MZK_HYPER_SCATTER).
 #include <utility>
 #include "mzk_common.h"
 #include "mzk_elem.h"
 #include "mzk_keccak_pair.h"
 #include "mzk_sumcheck_tx.h"
+#include "mzk_hypercube_plan.h"
 
 namespace mzk {
 
@@ -307,10 +312,11 @@ static int scp_check(size_t el, size_t k, size_t d, size_t header_len, mzk_tx::S
   return MZK_OK;
 }
 
-static int scp_prove_impl(const void* tables, bool on_device, size_t el, size_t k, size_t d, const uint8_t* header, size_t header_len,
-                          size_t header_objects, void* proof_out, size_t proof_cap, hipStream_t s_in) {
+// every refusal of the prover that does not read a table value, in the prover's order; sets the layout
+static int scp_args_check(const void* tables, bool on_device, size_t el, size_t k, size_t d, const uint8_t* header, size_t header_len,
+                          size_t header_objects, const void* proof_out, size_t proof_cap, mzk_tx::ScpLayout* Lp) {
   if (!tables || !proof_out || (header_len && !header)) { set_error("sumcheck_product_prove: null pointer"); return MZK_E_ARG; }
-  mzk_tx::ScpLayout L;
+  mzk_tx::ScpLayout& L = *Lp;
   MZK_TRY(scp_check(el, k, d, header_len, &L));
   if (proof_cap < L.total) { set_error("sumcheck_product_prove: proof buffer of %zu bytes, the layout needs %llu", proof_cap, (unsigned long long)L.total); return MZK_E_LENGTH; }
   if (!mzk_tx::scp_header_ok(header, header_len, header_objects)) {
@@ -318,6 +324,13 @@ static int scp_prove_impl(const void* tables, bool on_device, size_t el, size_t 
     return MZK_E_ARG;
   }
   if (on_device && (((uintptr_t)tables & 15) || ((uintptr_t)proof_out & 7))) { set_error("sumcheck_product_prove: tables need 16-byte, the proof 8-byte alignment"); return MZK_E_ARG; }
+  return MZK_OK;
+}
+
+static int scp_prove_impl(const void* tables, bool on_device, size_t el, size_t k, size_t d, const uint8_t* header, size_t header_len,
+                          size_t header_objects, void* proof_out, size_t proof_cap, hipStream_t s_in) {
+  mzk_tx::ScpLayout L;
+  MZK_TRY(scp_args_check(tables, on_device, el, k, d, header, header_len, header_objects, proof_out, proof_cap, &L));
   const size_t n = (size_t)1 << el;
   const HostField* fr = host_field(MZK_FIELD_FR);
   if (!on_device) {
@@ -395,6 +408,45 @@ static int scp_prove_impl(const void* tables, bool on_device, size_t el, size_t 
 // so a pass may run in place.
 constexpr int MLE_TILE_LOG = 10;
 constexpr int MLE_THREADS = 256;
+// x <- x + y mod p on canonical 32-bit words, BOTH operands below p: one carry chain, one borrow chain, one select -- the words that
+// fe_pack(fe_reduce(fe_add(fe_unpack(x), fe_unpack(y)))) leaves, at a tenth of its instructions.  An operand of p or more is outside
+// its contract (the limb form reduces any value), so only code whose operands are canonical by construction may use it.
+__device__ __forceinline__ void mle_addmod_words(u32* x, const u32* y) {
+  u32 s[8], t[8];
+  u64 c = 0;
+#pragma unroll
+  for (int i = 0; i < 8; i++) { c += (u64)x[i] + y[i]; s[i] = (u32)c; c >>= 32; }          // x + y < 2 p < 2^255: nothing is carried out
+  int64_t b = 0;
+#pragma unroll
+  for (int i = 0; i < 8; i++) { b += (int64_t)s[i] - (int64_t)SP::PW[i]; t[i] = (u32)b; b >>= 32; }
+  const bool below = b < 0;                                                                  // the borrow out: x + y < p
+#pragma unroll
+  for (int i = 0; i < 8; i++) x[i] = below ? s[i] : t[i];
+}
+// The g subset-sum stages over the element-index bits [cb, cb + g) of a tile of `elems` canonical values in LDS; every stage starts
+// with a barrier, none follows the last.  Shared by k_mle_pass (WORDS = false: the limb form it always had, which also reduces a caller's
+// value that is not canonical) and k_hyper_tile (WORDS = true: its tile holds sums of host-checked coefficients only).
+template <bool WORDS> __device__ __forceinline__ void mle_tile_stages(u32 (*X)[8], int tid, int elems, int cb, int g) {
+  for (int st = 0; st < g; st++) {
+    __syncthreads();
+    const int bit = 1 << (cb + st);
+    for (int q = tid; q < elems / 2; q += MLE_THREADS) {
+      const int e0 = ((q & ~(bit - 1)) << 1) | (q & (bit - 1)), e1 = e0 | bit;
+      if constexpr (WORDS) {
+        mle_addmod_words(X[e1], X[e0]);
+      } else {
+        const SE v = fe_reduce<SP>(fe_add<SP>(fe_unpack<SP>(X[e0]), fe_unpack<SP>(X[e1])));
+        fe_pack<SP>(v, X[e1]);
+      }
+    }
+  }
+}
+// one 32-byte element as two 16-byte stores: four neighbouring lanes fill a 128-byte row
+__device__ __forceinline__ void mle_store32(u32* out, size_t idx, const u32* x) {
+  uint4* p = reinterpret_cast<uint4*>(out + 8 * idx);
+  p[0] = make_uint4(x[0], x[1], x[2], x[3]);
+  p[1] = make_uint4(x[4], x[5], x[6], x[7]);
+}
 __global__ __launch_bounds__(MLE_THREADS) void k_mle_pass(const u32* in, u32* out, int lo, int g, int cb) {
   __shared__ u32 X[1 << MLE_TILE_LOG][8];
   const int tid = threadIdx.x;
@@ -406,21 +458,11 @@ __global__ __launch_bounds__(MLE_THREADS) void k_mle_pass(const u32* in, u32* ou
     const size_t idx = base | ((size_t)(e >> cb) << lo) | (size_t)(e & ((1 << cb) - 1));
     gload_words<8>(in, idx, X[e]);
   }
-  for (int st = 0; st < g; st++) {
-    __syncthreads();
-    const int bit = 1 << (cb + st);
-    for (int q = tid; q < elems / 2; q += MLE_THREADS) {
-      const int e0 = ((q & ~(bit - 1)) << 1) | (q & (bit - 1)), e1 = e0 | bit;
-      const SE v = fe_reduce<SP>(fe_add<SP>(fe_unpack<SP>(X[e0]), fe_unpack<SP>(X[e1])));
-      fe_pack<SP>(v, X[e1]);
-    }
-  }
+  mle_tile_stages<false>(X, tid, elems, cb, g);
   __syncthreads();
   for (int e = tid; e < elems; e += MLE_THREADS) {
     const size_t idx = base | ((size_t)(e >> cb) << lo) | (size_t)(e & ((1 << cb) - 1));
-    uint4* p = reinterpret_cast<uint4*>(out + 8 * idx);
-    p[0] = make_uint4(X[e][0], X[e][1], X[e][2], X[e][3]);
-    p[1] = make_uint4(X[e][4], X[e][5], X[e][6], X[e][7]);
+    mle_store32(out, idx, X[e]);
   }
 }
 
@@ -443,6 +485,141 @@ static int mle_dev_impl(const void* d_coef, size_t el, void* d_evals, hipStream_
     lo += g;
   }
   MZK_HIP(hipGetLastError());
+  return MZK_OK;
+}
+
+// ---- sparse MPolynomial factors -> evaluation tables (eval_all_binary_combinations of the reference's prover) ------------------
+// The host plan (mzk_hypercube_plan.h) leaves, per factor, the distinct support masks in ascending order with the coefficients of
+// equal masks already added (on the host), and the groups of masks with one high part mask >> g.  evals[b] = sum of the
+// coefficients whose mask is a subset of b.
+//
+// k_hyper_tile: workgroup (x, f) owns the 2^g consecutive entries of factor f whose high index bits are x.  A mask contributes to the
+// tile iff its high part is a subset of x -- one test per GROUP, the same for every lane (group heads and ranges are read at uniform
+// addresses) -- and then lands on slot (mask & (2^g - 1)) of the tile.  Low masks within a group are distinct, so the lanes of one
+// group write different slots; a barrier orders the groups.  The g subset-sum stages in LDS then finish the tile, which is written
+// once.  Nothing of size 2^el is read.
+__global__ __launch_bounds__(HC_THREADS) void k_hyper_tile(const u32* __restrict__ grp_off, const u32* __restrict__ grp_hi, const u32* __restrict__ grp_begin,
+                                                           const u32* __restrict__ mask, const u32* __restrict__ coef, int g, size_t n,
+                                                           u32* __restrict__ tables) {
+  __shared__ u32 X[1 << MLE_TILE_LOG][8];
+  static_assert(HC_TILE_LOG == MLE_TILE_LOG && HC_THREADS == MLE_THREADS, "the tile of k_hyper_tile is the tile of k_mle_pass");
+  const int tid = threadIdx.x;
+  const int elems = 1 << g;
+  const u32 hi = blockIdx.x, f = blockIdx.y;
+  for (int e = tid; e < elems; e += HC_THREADS) {
+    uint4* x = reinterpret_cast<uint4*>(X[e]);
+    x[0] = make_uint4(0, 0, 0, 0);
+    x[1] = make_uint4(0, 0, 0, 0);
+  }
+  __syncthreads();
+  const u32 j1 = grp_off[f + 1];
+  for (u32 j = grp_off[f]; j < j1; j++) {
+    if (grp_hi[j] & ~hi) continue;
+    const u32 q1 = grp_begin[j + 1];
+    for (u32 q = grp_begin[j] + tid; q < q1; q += HC_THREADS) {
+      u32 w[8];
+      gload_words<8>(coef, q, w);
+      mle_addmod_words(X[mask[q] & (u32)(elems - 1)], w);
+    }
+    __syncthreads();
+  }
+  mle_tile_stages<true>(X, tid, elems, 0, g);
+  __syncthreads();
+  u32* out = tables + 8 * ((size_t)f * n + ((size_t)hi << g));
+  // the loop vectoriser would turn this into word-by-word stores 32 bytes apart per lane: keep one element, two 16-byte stores, per trip
+#pragma clang loop vectorize(disable) interleave(disable)
+  for (int e = tid; e < elems; e += HC_THREADS) mle_store32(out, e, X[e]);
+}
+// k_hyper_scatter: entry q of factor f -> table_f[mask[q]] of the zero-filled tables; masks within a factor are distinct and below n
+__global__ __launch_bounds__(HC_THREADS) void k_hyper_scatter(const u32* __restrict__ ent_off, const u32* __restrict__ mask, const u32* __restrict__ coef, size_t n,
+                                                              u32* __restrict__ tables) {
+  const u32 f = blockIdx.y;
+  const u32 q = ent_off[f] + blockIdx.x * HC_THREADS + threadIdx.x;
+  if (q >= ent_off[f + 1]) return;
+  u32 w[8];
+  gload_words<8>(coef, q, w);
+  mle_store32(tables, (size_t)f * n + mask[q], w);
+}
+
+// the plan and the words that go to the device: head (hc_plan's order) | merged coefficients
+struct HcStaged { HcPlan pl; std::vector<u32> blob; };
+// every refusal of mzk_mpoly_hypercube_evals* that needs no device, then the host merge
+static int hc_prepare(const uint64_t* term_coefs, const uint32_t* term_exps, const size_t* term_offsets, size_t k, size_t el, int form, HcStaged* st) {
+  HcPlan& pl = st->pl;
+  const int rc = hc_plan(term_exps, term_offsets, k, el, form, &pl);
+  if (rc != MZK_OK) { set_error("%s", pl.msg); return rc; }
+  if (pl.terms && !term_coefs) { set_error("mpoly_hypercube: null pointer"); return MZK_E_ARG; }
+  const HostField* fr = host_field(MZK_FIELD_FR);
+  const size_t t0 = k ? term_offsets[0] : 0;
+  for (size_t t = 0; t < pl.terms; t++)
+    if (!h_is_canonical(fr, term_coefs + 4 * (t0 + t))) { set_error("mpoly_hypercube: term_coefs[%zu] not canonical", t0 + t); return MZK_E_RANGE; }
+  if (k == 0) return MZK_OK;
+  st->blob.assign(pl.upload_bytes / 4, 0);
+  u32* w = st->blob.data();
+  if (pl.form == MZK_HYPER_TILE) {
+    w = std::copy(pl.grp_off.begin(), pl.grp_off.end(), w);
+    w = std::copy(pl.grp_hi.begin(), pl.grp_hi.end(), w);
+    w = std::copy(pl.grp_begin.begin(), pl.grp_begin.end(), w);
+  } else {
+    w = std::copy(pl.ent_off.begin(), pl.ent_off.end(), w);
+  }
+  std::copy(pl.mask.begin(), pl.mask.end(), w);
+  hc_merge_coefs(pl, term_coefs, t0, st->blob.data() + pl.upload_words_head);
+  return MZK_OK;
+}
+// Uploads the staged words and enqueues the form.  The words are host memory of the caller's frame: the stream is waited for right
+// behind the copy (it has only earlier work and the copy on it), so the kernels below are enqueued and not waited for.
+static int hc_enqueue(const HcStaged& st, WsFrame& ws, void* d_tables, hipStream_t s) {
+  const HcPlan& pl = st.pl;
+  if (pl.k == 0) return MZK_OK;
+  const size_t n = (size_t)1 << pl.el, E = pl.mask.size(), G = pl.grp_hi.size(), k = pl.k;
+  u32* d_blob;
+  MZK_TRY(ws.get(WS_MISC_C, pl.workspace_bytes, (void**)&d_blob));
+  MZK_HIP(hipMemcpyAsync(d_blob, st.blob.data(), pl.upload_bytes, hipMemcpyHostToDevice, s));
+  MZK_HIP(hipStreamSynchronize(s));
+  const u32* d_coef = d_blob + pl.upload_words_head;
+  ProfScope ph(s, MZK_PH_HYPERCUBE);
+  if (pl.form == MZK_HYPER_TILE) {
+    const u32 *d_goff = d_blob, *d_ghi = d_goff + (k + 1), *d_gbeg = d_ghi + G, *d_mask = d_gbeg + (G + 1);
+    hipLaunchKernelGGL(k_hyper_tile, dim3((unsigned)pl.grid_x, (unsigned)pl.grid_y), dim3(HC_THREADS), 0, s, d_goff, d_ghi, d_gbeg, d_mask, d_coef, pl.g, n,
+                       (u32*)d_tables);
+    MZK_HIP(hipGetLastError());
+    return MZK_OK;
+  }
+  MZK_HIP(hipMemsetAsync(d_tables, 0, pl.table_bytes, s));
+  if (E == 0) return MZK_OK;
+  const u32 *d_eoff = d_blob, *d_mask = d_eoff + (k + 1);
+  hipLaunchKernelGGL(k_hyper_scatter, dim3((unsigned)pl.grid_x, (unsigned)pl.grid_y), dim3(HC_THREADS), 0, s, d_eoff, d_mask, d_coef, n, (u32*)d_tables);
+  MZK_HIP(hipGetLastError());
+  for (size_t f = 0; f < k; f++) {
+    void* t = (char*)d_tables + f * n * 32;
+    MZK_TRY(mle_dev_impl(t, pl.el, t, s));
+  }
+  return MZK_OK;
+}
+
+static int hc_prove_terms_impl(const uint64_t* term_coefs, const uint32_t* term_exps, const size_t* term_offsets, size_t k, size_t el, size_t d,
+                               const uint8_t* header, size_t header_len, size_t header_objects, void* proof_out, size_t proof_cap, bool on_device,
+                               hipStream_t s_in) {
+  mzk_tx::ScpLayout L;
+  // the prover's refusals first (the tables are this call's own: any aligned non-null value stands in for them)
+  MZK_TRY(scp_args_check((const void*)(uintptr_t)16, on_device, el, k, d, header, header_len, header_objects, proof_out, proof_cap, &L));
+  HcStaged st;
+  MZK_TRY(hc_prepare(term_coefs, term_exps, term_offsets, k, el, MZK_HYPER_AUTO, &st));
+  MZK_ENTER();
+  WsFrame ws("mzk_sumcheck_product_prove_terms");
+  hipStream_t s = on_device ? s_in : ctx().stream;
+  WsGuard wsg(s);
+  void *d_tab, *d_proof = proof_out;
+  MZK_TRY(ws.get(WS_MISC_E, st.pl.table_bytes, &d_tab));
+  if (!on_device) MZK_TRY(ws.get(WS_MISC_D, L.total, &d_proof));
+  MZK_TRY(hc_enqueue(st, ws, d_tab, s));
+  MZK_TRY(scp_prove_impl(d_tab, true, el, k, d, header, header_len, header_objects, d_proof, L.total, s));
+  if (on_device) return MZK_OK;
+  MZK_TRY(d2h_sync(proof_out, d_proof, L.total, s));
+  uint64_t status;
+  memcpy(&status, (const uint8_t*)proof_out + L.off[mzk_tx::SCP_STATUS], 8);
+  if (status != 0) { set_error("sumcheck_product_prove_terms: status word %llu", (unsigned long long)status); return MZK_E_RANGE; }
   return MZK_OK;
 }
 
@@ -495,6 +672,65 @@ int mzk_mle_evals_from_coeffs_dev(const void* d_coef, size_t num_vars, void* d_e
   if (((uintptr_t)d_coef & 15) || ((uintptr_t)d_evals & 15)) { set_error("mle_evals_from_coeffs: buffers need 16-byte alignment"); return MZK_E_ARG; }
   MZK_ENTER();
   return mle_dev_impl(d_coef, num_vars, d_evals, (hipStream_t)stream);
+}
+
+int mzk_mpoly_hypercube_plan(const uint32_t* term_exps, const size_t* term_offsets, size_t n_factors, size_t num_vars, int form, mzk_hypercube_plan* out) {
+  using namespace mzk;
+  if (!out) { set_error("mpoly_hypercube_plan: null pointer"); return MZK_E_ARG; }
+  HcPlan pl;
+  const int rc = hc_plan(term_exps, term_offsets, n_factors, num_vars, form, &pl);
+  if (rc != MZK_OK) { set_error("%s", pl.msg); return rc; }
+  memset(out, 0, sizeof *out);
+  out->form = (uint64_t)pl.form; out->tile_log = (uint64_t)pl.g; out->terms = pl.terms; out->masks = pl.mask.size(); out->groups = pl.grp_hi.size();
+  out->max_masks = pl.max_masks; out->max_groups = pl.max_groups;
+  out->launches = pl.launches; out->memsets = pl.memsets; out->grid_x = pl.grid_x; out->grid_y = pl.grid_y; out->mle_passes = pl.mle_passes;
+  out->upload_bytes = pl.upload_bytes; out->workspace_bytes = pl.workspace_bytes; out->table_bytes = pl.table_bytes;
+  for (size_t f = 0; f < n_factors && f < (size_t)MZK_HYPER_PLAN_FACTORS; f++) {
+    out->factor_masks[f] = pl.ent_off[f + 1] - pl.ent_off[f];
+    out->factor_groups[f] = pl.grp_off[f + 1] - pl.grp_off[f];
+  }
+  return MZK_OK;
+}
+int mzk_mpoly_hypercube_evals(const uint64_t* term_coefs, const uint32_t* term_exps, const size_t* term_offsets, size_t n_factors, size_t num_vars, int form,
+                              uint64_t* tables) {
+  using namespace mzk;
+  if (n_factors && !tables) { set_error("mpoly_hypercube_evals: null pointer"); return MZK_E_ARG; }
+  HcStaged st;
+  MZK_TRY(hc_prepare(term_coefs, term_exps, term_offsets, n_factors, num_vars, form, &st));
+  if (n_factors == 0) return MZK_OK;
+  MZK_ENTER();
+  WsFrame ws("mzk_mpoly_hypercube_evals");
+  hipStream_t s = ctx().stream;
+  WsGuard wsg(s);
+  void* d_tab;
+  MZK_TRY(ws.get(WS_MISC_E, st.pl.table_bytes, &d_tab));
+  MZK_TRY(hc_enqueue(st, ws, d_tab, s));
+  return d2h_sync(tables, d_tab, st.pl.table_bytes, s);
+}
+int mzk_mpoly_hypercube_evals_dev(const uint64_t* term_coefs, const uint32_t* term_exps, const size_t* term_offsets, size_t n_factors, size_t num_vars,
+                                  int form, void* d_tables, void* stream) {
+  using namespace mzk;
+  if (n_factors && !d_tables) { set_error("mpoly_hypercube_evals: null pointer"); return MZK_E_ARG; }
+  if ((uintptr_t)d_tables & 15) { set_error("mpoly_hypercube_evals: the tables need 16-byte alignment"); return MZK_E_ARG; }
+  HcStaged st;
+  MZK_TRY(hc_prepare(term_coefs, term_exps, term_offsets, n_factors, num_vars, form, &st));
+  if (n_factors == 0) return MZK_OK;
+  MZK_ENTER();
+  WsFrame ws("mzk_mpoly_hypercube_evals_dev");
+  WsGuard wsg((hipStream_t)stream);
+  return hc_enqueue(st, ws, d_tables, (hipStream_t)stream);
+}
+int mzk_sumcheck_product_prove_terms(const uint64_t* term_coefs, const uint32_t* term_exps, const size_t* term_offsets, size_t n_factors, size_t num_vars,
+                                     size_t max_degree, const uint8_t* header, size_t header_len, size_t header_objects, uint8_t* proof_out,
+                                     size_t proof_cap) {
+  return mzk::hc_prove_terms_impl(term_coefs, term_exps, term_offsets, n_factors, num_vars, max_degree, header, header_len, header_objects, proof_out,
+                                  proof_cap, false, nullptr);
+}
+int mzk_sumcheck_product_prove_terms_dev(const uint64_t* term_coefs, const uint32_t* term_exps, const size_t* term_offsets, size_t n_factors, size_t num_vars,
+                                         size_t max_degree, const uint8_t* header, size_t header_len, size_t header_objects, void* d_proof,
+                                         size_t proof_cap, void* stream) {
+  return mzk::hc_prove_terms_impl(term_coefs, term_exps, term_offsets, n_factors, num_vars, max_degree, header, header_len, header_objects, d_proof, proof_cap,
+                                  true, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -1076,10 +1076,12 @@ SumCheckProof prove_sumcheck(const std::vector<FqOrder>& coefs, const FqOrder& h
 }  // namespace batch
 
 // ---- examples/sumcheck: SumCheckProverGPU::prove (prover.rs:79-247) over evaluation tables -----------------------------------
-// The reference turns its MPolynomial factors into tables itself and pushes their bincode into the proof stream first; that bincode
-// is a HashMap in the iteration order of one process, so here the caller brings both: every factor's table over {0,1}^el (variable
-// 0 the most significant index bit) and the objects pushed before round 0.  The rounds, the transcript and the challenges run on the
-// device in one call (mzk_sumcheck_product_prove).
+// prove(max_degree, factors, header) takes the reference's MPolynomial factors: their tables over {0,1}^el (variable 0 the most
+// significant index bit) are built on the device (mzk_mpoly_hypercube_evals, the reference's eval_all_binary_combinations) and the
+// rounds, the transcript and the challenges run behind them in the same call (mzk_sumcheck_product_prove_terms); the tables never
+// exist on the host.  The table overload takes tables the caller already has.  The reference pushes the bincode of its factors into
+// the proof stream first; that bincode is a HashMap in the iteration order of one process, so the objects pushed before round 0 stay
+// the caller's bytes in both overloads.
 typedef std::vector<std::vector<uint8_t>> StreamObject;     // one FiatShamirTransformer::push: a Vec<Vec<u8>>
 struct SumCheckProverGPU {
   static std::vector<uint8_t> bincode_usize(size_t v) {
@@ -1113,6 +1115,50 @@ struct SumCheckProverGPU {
     expect(mzk_mle_evals_from_coeffs(c.data(), el, out.data()));
     return from_wire<FqOrder>(out, coef.size());
   }
+  // a factor without terms, or el = 0, leaves an empty vector whose data() may be null, which the ABI refuses: one spare element each
+  static void pad_term_table(std::vector<uint64_t>& coefs, std::vector<uint32_t>& exps) {
+    coefs.resize(coefs.size() + 4);
+    exps.resize(exps.size() + 1);
+  }
+  // evals_over_boolean_hypercube (utils.rs) of a sparse factor over el variables: what eval_all_binary_combinations leaves in its
+  // row of the reference's device buffer.  A factor that is not multilinear gives the table of its multilinearisation.
+  static std::vector<FqOrder> evals_over_boolean_hypercube(const MPolynomial<FqOrder>& f, size_t el) {
+    if (el > 30) throw Panic(MZK_E_LENGTH, "evals_over_boolean_hypercube: at most 30 variables");
+    std::vector<uint64_t> coefs;
+    std::vector<uint32_t> exps;
+    std::vector<size_t> toff;
+    MPolynomial<FqOrder>::term_table({f}, el, coefs, exps, toff);
+    std::vector<uint64_t> out(4 * ((size_t)1 << el) + 4);
+    pad_term_table(coefs, exps);
+    expect(mzk_mpoly_hypercube_evals(coefs.data(), exps.data(), toff.data(), 1, el, MZK_HYPER_AUTO, out.data()));
+    return from_wire<FqOrder>(out, (size_t)1 << el);
+  }
+  static std::pair<FqOrder, std::vector<uint8_t>> unpack(const std::vector<uint8_t>& proof, const uint64_t* off) {
+    FqOrder sum;
+    std::memcpy(sum.value.data(), &proof[off[MZK_SCP_SUM]], 32);
+    uint64_t len = 0;
+    std::memcpy(&len, &proof[off[MZK_SCP_TRANSCRIPT_LEN]], 8);
+    const uint8_t* tx = &proof[off[MZK_SCP_TRANSCRIPT]];
+    return {sum, std::vector<uint8_t>(tx, tx + len)};
+  }
+  // prover.rs:98: (claimed_sum, transcript.serialize()) from the factors themselves; num_variables is the maximum over the factors
+  std::pair<FqOrder, std::vector<uint8_t>> prove(size_t max_degree, const std::vector<MPolynomial<FqOrder>>& factors, const std::vector<StreamObject>& header) const {
+    size_t el = 0;
+    for (const auto& f : factors)
+      for (const auto& kv : f.dictionary) el = std::max(el, kv.first.size());
+    std::vector<uint64_t> coefs;
+    std::vector<uint32_t> exps;
+    std::vector<size_t> toff;
+    MPolynomial<FqOrder>::term_table(factors, el, coefs, exps, toff);
+    pad_term_table(coefs, exps);
+    const std::vector<uint8_t> h = frame_header(header);
+    uint64_t off[MZK_SCP_SECTIONS], size[MZK_SCP_SECTIONS], total = 0;
+    expect(mzk_sumcheck_product_layout(el, factors.size(), max_degree, h.size(), off, size, &total));
+    std::vector<uint8_t> proof(total);
+    expect(mzk_sumcheck_product_prove_terms(coefs.data(), exps.data(), toff.data(), factors.size(), el, max_degree, h.data(), h.size(), header.size(),
+                                            proof.data(), proof.size()));
+    return unpack(proof, off);
+  }
   // (claimed_sum, transcript.serialize()); tables[f] = factor f's 2^el values
   std::pair<FqOrder, std::vector<uint8_t>> prove(size_t max_degree, const std::vector<std::vector<FqOrder>>& tables, const std::vector<StreamObject>& header) const {
     const size_t k = tables.size(), n = k ? tables[0].size() : 0;
@@ -1128,12 +1174,7 @@ struct SumCheckProverGPU {
     expect(mzk_sumcheck_product_layout(el, k, max_degree, h.size(), off, size, &total));
     std::vector<uint8_t> proof(total);
     expect(mzk_sumcheck_product_prove(flat.data(), el, k, max_degree, h.data(), h.size(), header.size(), proof.data(), proof.size()));
-    FqOrder sum;
-    std::memcpy(sum.value.data(), &proof[off[MZK_SCP_SUM]], 32);
-    uint64_t len = 0;
-    std::memcpy(&len, &proof[off[MZK_SCP_TRANSCRIPT_LEN]], 8);
-    const uint8_t* tx = &proof[off[MZK_SCP_TRANSCRIPT]];
-    return {sum, std::vector<uint8_t>(tx, tx + len)};
+    return unpack(proof, off);
   }
 };
 

@@ -15,7 +15,8 @@ HDR = os.path.join(ROOT, "include", "mzk.h")
 OUT = os.path.join(ROOT, "include", "mzk_ffi.rs")
 
 HANDLES = ("mzk_srs_multi", "mzk_srs", "mzk_merkle", "mzk_stark", "mzk_das_grid", "mzk_rescue")
-STRUCTS = ("mzk_stark_dims",)      # plain structs of uint64_t fields, passed by pointer: emitted as #[repr(C)] (c_structs)
+STRUCTS = ("mzk_stark_dims",)           # plain structs of uint64_t fields, passed by pointer: emitted as #[repr(C)] (c_structs)
+PLAN_STRUCTS = ("mzk_hypercube_plan",)   # the same kind of struct, added later: c_structs() keeps answering for STRUCTS alone
 SCALARS = {"int": "c_int", "unsigned": "c_uint", "unsigned int": "c_uint", "size_t": "usize", "uint64_t": "u64", "uint32_t": "u32",
            "uint8_t": "u8", "double": "f64", "char": "c_char", "void": "c_void"}
 CHALLENGE = 'extern "C" fn(*mut c_void, c_int, c_int, *const u8, usize, *mut u64) -> c_int'
@@ -45,13 +46,13 @@ def c_prototypes(path=HDR):
     return protos
 
 
-def c_structs(path=HDR):
-    """[(name, [(field, array length or None)])] for the STRUCTS of the header: `typedef struct X { uint64_t a, b[N], ...; ... } X;` with
+def c_structs(path=HDR, names=STRUCTS):
+    """[(name, [(field, array length or None)])] for the STRUCTS (or `names`) of the header: `typedef struct X { uint64_t a, b[N], ...; ... } X;` with
     array lengths given as numbers or as the header's enum constants"""
     txt = strip_comments(open(path).read())
     consts = {k: int(v) for body in re.findall(r"enum\s*\{([^}]*)\}", txt) for k, v in re.findall(r"([A-Z][A-Z0-9_]*)\s*=\s*(\d+)", body)}
     out = []
-    for name in STRUCTS:
+    for name in names:
         body = re.search(r"typedef struct %s \{(.*?)\} %s;" % (name, name), txt, flags=re.S).group(1)
         fields = []
         for decl in body.split(";"):
@@ -108,7 +109,7 @@ def c_type(t):
     bname = " ".join(base)
     if bname in HANDLES or bname.startswith("struct "):
         rust = "c_void"
-    elif bname in STRUCTS:
+    elif bname in STRUCTS or bname in PLAN_STRUCTS:
         rust = bname
     elif bname in SCALARS:
         rust = SCALARS[bname]
@@ -136,7 +137,7 @@ def emit():
     lines = ['// GENERATED by tools/gen_rust_ffi.py from include/mzk.h -- do not edit; `python tools/gen_rust_ffi.py` rewrites it.',
              '// The complete `extern "C"` surface of libmzk_hip.so (%d functions) for the Rust shim of INTEGRATION.md section 2:' % len(protos),
              '//     #[cfg(feature = "mi355x")] #[path = "../../../../include/mzk_ffi.rs"] pub mod ffi;',
-             '// Handles (mzk_srs, mzk_srs_multi, mzk_merkle, mzk_stark, mzk_das_grid, mzk_rescue) are opaque: `c_void` behind the pointer.  Plain structs (%s) are #[repr(C)] below.' % ", ".join(STRUCTS),
+             '// Handles (mzk_srs, mzk_srs_multi, mzk_merkle, mzk_stark, mzk_das_grid, mzk_rescue) are opaque: `c_void` behind the pointer.  Plain structs (%s) are #[repr(C)] below.' % ", ".join(STRUCTS + PLAN_STRUCTS),
              '// Status codes: include/mzk.h.',
              '#![allow(non_camel_case_types, dead_code)]',
              'use std::os::raw::{c_char, c_int, c_uint, c_void};',
@@ -151,7 +152,7 @@ def emit():
              'pub const MZK_LAYOUT_CYCLIC: c_int = 1;',
              '',
              ] + ['#[repr(C)]\n#[derive(Clone, Copy, Debug)]\npub struct %s {\n%s}\n' % (n, "".join("    pub %s: %s,\n" % (f, "u64" if k is None else "[u64; %d]" % k) for f, k in fs))
-                  for n, fs in c_structs()] + [
+                  for n, fs in c_structs(names=STRUCTS + PLAN_STRUCTS)] + [
              '#[link(name = "mzk_hip")]',
              'extern "C" {']
     for name, ret, params in protos:
