@@ -1,15 +1,17 @@
 """ctypes loader + thin wrappers for include/mzk.h.  Arrays are numpy uint64, shape (n, limbs)."""
-import ctypes, os, re
+import ctypes, os
 import numpy as np
+from . import _abi
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 SO = os.environ.get("MZK_HIP_LIB") or os.path.join(HERE, "libmzk_hip.so")   # MZK_HIP_LIB: experimental builds (tools/)
 
-FIELD_FR, FIELD_M128, FIELD_FQ = 0, 1, 2
+_C = _abi.constants()        # every NAME = integer of the header's enums
+FIELD_FR, FIELD_M128, FIELD_FQ = _C["MZK_FIELD_FR"], _C["MZK_FIELD_M128"], _C["MZK_FIELD_FQ"]
 # Goldilocks (p = 2^64 - 2^32 + 1) and its cubic extension F_p[x] / (x^3 - x + 1): one / three canonical u64 per element.  A scalar
 # extension element is an int packed as c0 + c1 * 2^64 + c2 * 2^128 (what to_limbs / from_limbs do with three limbs).
-FIELD_M64, FIELD_M64X3 = 3, 4
+FIELD_M64, FIELD_M64X3 = _C["MZK_FIELD_M64"], _C["MZK_FIELD_M64X3"]
 LIMBS = {FIELD_FR: 4, FIELD_M128: 2, FIELD_FQ: 4, FIELD_M64: 1, FIELD_M64X3: 3}
 MODULUS = {
     FIELD_FR: 21888242871839275222246405745257275088548364400416034343698204186575808495617,
@@ -23,9 +25,7 @@ MODULUS = {
 def _leaf_stride(fid):
     """bytes that hold any leaf of the field: 41 for Fr, 59 for an M64X3 element"""
     return 64 if fid == FIELD_M64X3 else 48
-ERRORS = {0: "MZK_OK", -1: "MZK_E_ARG", -2: "MZK_E_NOT_POW2", -3: "MZK_E_ROOT_ORDER", -4: "MZK_E_ROOT_PRIM",
-          -5: "MZK_E_LENGTH", -6: "MZK_E_RANGE", -7: "MZK_E_HIP", -8: "MZK_E_NOGPU", -9: "MZK_E_CALLBACK", -10: "MZK_E_IO",
-          -11: "MZK_E_BUSY", -12: "MZK_E_NOMEM"}
+ERRORS = {v: k for k, v in _C.items() if k == "MZK_OK" or k.startswith("MZK_E_")}
 
 
 class MzkError(RuntimeError):
@@ -38,14 +38,7 @@ class MzkError(RuntimeError):
 _lib = None
 
 
-def _declared_symbols():
-    hdr = os.path.join(ROOT, "include", "mzk.h")
-    txt = open(hdr).read()
-    txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
-    return sorted(set(re.findall(r"\b(mzk_[a-z0-9_]+)\s*\(", txt)))
-
-
-DECLARED_SYMBOLS = _declared_symbols()
+DECLARED_SYMBOLS = sorted(name for name, _, _ in _abi.c_prototypes())
 
 
 def lib():
@@ -62,8 +55,7 @@ def lib():
             import torch  # noqa: F401
         except Exception:
             pass
-        _lib = ctypes.CDLL(SO)
-        _lib.mzk_last_error.restype = ctypes.c_char_p
+        _lib = _abi.bind(ctypes.CDLL(SO))       # argtypes and restype of every entry point, from the header: callers pass plain values
     return _lib
 
 
@@ -83,7 +75,7 @@ def init(device=0):
 
 def set_workspace_budget(nbytes):
     """bytes of scratch a context may keep between calls (0 = no limit); idle buffers above it are released at once"""
-    _check(lib().mzk_set_workspace_budget(ctypes.c_size_t(int(nbytes))))
+    _check(lib().mzk_set_workspace_budget(int(nbytes)))
 
 
 def trim_workspace():
@@ -119,7 +111,7 @@ def ctx_select(index):
 
 def shard_range(n, rank, world):
     lo, hi = ctypes.c_size_t(), ctypes.c_size_t()
-    lib().mzk_shard_range(ctypes.c_size_t(n), int(rank), int(world), ctypes.byref(lo), ctypes.byref(hi))
+    lib().mzk_shard_range(n, int(rank), int(world), ctypes.byref(lo), ctypes.byref(hi))
     return lo.value, hi.value
 
 
@@ -169,7 +161,7 @@ def ntt(fid, root, values, inverse=False):
     v = _arr(fid, values)
     out = np.empty_like(v)
     r = _one(fid, root)
-    _check(lib().mzk_ntt(fid, _p(r), _p(v), _p(out), ctypes.c_size_t(v.shape[0]), int(bool(inverse))))
+    _check(lib().mzk_ntt(fid, _p(r), _p(v), _p(out), v.shape[0], int(bool(inverse))))
     return out
 
 
@@ -185,7 +177,7 @@ def merkle_commit_field_batch(fid, codewords):
         return []
     c = c.reshape(batch, -1, LIMBS[fid])
     roots = (ctypes.c_uint8 * (32 * batch))()
-    _check(lib().mzk_merkle_commit_field_batch(fid, _p(c), ctypes.c_size_t(c.shape[1]), ctypes.c_size_t(batch), roots))
+    _check(lib().mzk_merkle_commit_field_batch(fid, _p(c), c.shape[1], batch, roots))
     raw = bytes(roots)
     return [raw[32 * k: 32 * k + 32] for k in range(batch)]
 
@@ -196,8 +188,7 @@ def coset_lde_batch(fid, coefs, offset, generator, order):
     batch = c.shape[0]
     c = c.reshape(batch, -1, LIMBS[fid]) if batch else c.reshape(0, 0, LIMBS[fid])
     out = np.empty((batch, order, LIMBS[fid]), dtype=np.uint64)
-    _check(lib().mzk_coset_lde_batch(fid, _p(c), ctypes.c_size_t(c.shape[1]), _p(_one(fid, offset)), _p(_one(fid, generator)), _p(out),
-                                     ctypes.c_size_t(order), ctypes.c_size_t(batch)))
+    _check(lib().mzk_coset_lde_batch(fid, _p(c), c.shape[1], _p(_one(fid, offset)), _p(_one(fid, generator)), _p(out), order, batch))
     return out
 
 
@@ -210,7 +201,7 @@ def ntt_batch(fid, root, columns, inverse=False):
     v = v.reshape(batch, -1, LIMBS[fid])
     out = np.empty_like(v)
     r = _one(fid, root)
-    _check(lib().mzk_ntt_batch(fid, _p(r), _p(v), _p(out), ctypes.c_size_t(v.shape[1]), ctypes.c_size_t(batch), int(bool(inverse))))
+    _check(lib().mzk_ntt_batch(fid, _p(r), _p(v), _p(out), v.shape[1], batch, int(bool(inverse))))
     return out
 
 
@@ -219,7 +210,7 @@ def coset_lde(fid, coef, offset, generator, order):
     c = _arr(fid, coef)
     out = np.empty((order, LIMBS[fid]), dtype=np.uint64)
     o, g = _one(fid, offset), _one(fid, generator)
-    _check(lib().mzk_coset_lde(fid, _p(c), ctypes.c_size_t(c.shape[0]), _p(o), _p(g), _p(out), ctypes.c_size_t(order)))
+    _check(lib().mzk_coset_lde(fid, _p(c), c.shape[0], _p(o), _p(g), _p(out), order))
     return out
 
 
@@ -227,7 +218,7 @@ def poly_scale(fid, coef, ratio, lead=None):
     """Polynomial::scale (algebra/polynomial.rs:167-174), optionally times a leading constant: lead * coef[i] * ratio^i."""
     c = _arr(fid, coef)
     out = np.empty_like(c)
-    _check(lib().mzk_poly_scale(fid, _p(c), ctypes.c_size_t(c.shape[0]), _p(_one(fid, ratio)), _p(_one(fid, lead)) if lead is not None else None, _p(out)))
+    _check(lib().mzk_poly_scale(fid, _p(c), c.shape[0], _p(_one(fid, ratio)), _p(_one(fid, lead)) if lead is not None else None, _p(out)))
     return out
 
 
@@ -237,7 +228,7 @@ def fft_multiply(fid, a, b, omega):
     out = np.zeros((max(a.shape[0] + b.shape[0], 1), LIMBS[fid]), dtype=np.uint64)
     n = ctypes.c_size_t(0)
     w = _one(fid, omega)
-    _check(lib().mzk_fft_multiply(fid, _p(a), ctypes.c_size_t(a.shape[0]), _p(b), ctypes.c_size_t(b.shape[0]), _p(w), _p(out), ctypes.byref(n)))
+    _check(lib().mzk_fft_multiply(fid, _p(a), a.shape[0], _p(b), b.shape[0], _p(w), _p(out), ctypes.byref(n)))
     return out[:n.value]
 
 
@@ -247,8 +238,7 @@ def fast_multiply(fid, a, b, root, root_order):
     out = np.zeros((max(root_order, a.shape[0] + b.shape[0], 1), LIMBS[fid]), dtype=np.uint64)
     n = ctypes.c_size_t(0)
     w = _one(fid, root)
-    _check(lib().mzk_fast_multiply(fid, _p(a), ctypes.c_size_t(a.shape[0]), _p(b), ctypes.c_size_t(b.shape[0]), _p(w),
-                                   ctypes.c_size_t(root_order), _p(out), ctypes.byref(n)))
+    _check(lib().mzk_fast_multiply(fid, _p(a), a.shape[0], _p(b), b.shape[0], _p(w), root_order, _p(out), ctypes.byref(n)))
     return out[:n.value]
 
 
@@ -265,7 +255,7 @@ def msm_g1(scalars, points):
     if p.shape[0] < s.shape[0]:
         raise MzkError(-5, "index out of bounds: the len is %d but the index is %d" % (p.shape[0], p.shape[0]))
     out = np.zeros((1, 8), dtype=np.uint64)
-    _check(lib().mzk_msm_g1_bn254(_p(s), _p(p), ctypes.c_size_t(s.shape[0]), _p(out)))
+    _check(lib().mzk_msm_g1_bn254(_p(s), _p(p), s.shape[0], _p(out)))
     return array_to_points(out)[0]
 
 
@@ -279,27 +269,27 @@ def msm_g1_multi(scalars, points):
     if p.shape[0] < s.shape[0]:
         raise MzkError(-5, "index out of bounds: the len is %d but the index is %d" % (p.shape[0], p.shape[0]))
     out = np.zeros((1, 8), dtype=np.uint64)
-    _check(lib().mzk_msm_g1_bn254_multi(_p(s), _p(p), ctypes.c_size_t(s.shape[0]), _p(out)))
+    _check(lib().mzk_msm_g1_bn254_multi(_p(s), _p(p), s.shape[0], _p(out)))
     return array_to_points(out)[0]
 
 
-LAYOUT_CONTIGUOUS, LAYOUT_CYCLIC = 0, 1
+LAYOUT_CONTIGUOUS, LAYOUT_CYCLIC = _C["MZK_LAYOUT_CONTIGUOUS"], _C["MZK_LAYOUT_CYCLIC"]
 
 
 def ntt_multi(fid, root, values, inverse=False):
     """ntt::ntt / ntt::intt of ONE vector spread over every context of init_devices (four-step layout, mzk_ntt_multi)."""
     v = _arr(fid, values)
     out = np.empty_like(v)
-    _check(lib().mzk_ntt_multi(fid, _p(_one(fid, root)), _p(v), _p(out), ctypes.c_size_t(v.shape[0]), int(bool(inverse))))
+    _check(lib().mzk_ntt_multi(fid, _p(_one(fid, root)), _p(v), _p(out), v.shape[0], int(bool(inverse))))
     return out
 
 
 def ntt_multi_dev(fid, root, in_ptrs, out_ptrs, n, inverse=False, layout_in=LAYOUT_CONTIGUOUS, layout_out=LAYOUT_CONTIGUOUS):
     """The same with the parts resident in HBM: in_ptrs[r] / out_ptrs[r] = device pointers (ints) on context r's GPU."""
     W = len(in_ptrs)
-    ins = (ctypes.c_void_p * W)(*[ctypes.c_void_p(int(p)) for p in in_ptrs])
-    outs = (ctypes.c_void_p * W)(*[ctypes.c_void_p(int(p)) for p in out_ptrs])
-    _check(lib().mzk_ntt_multi_dev(fid, _p(_one(fid, root)), ins, outs, ctypes.c_size_t(n), int(bool(inverse)), int(layout_in), int(layout_out)))
+    ins = (ctypes.c_void_p * W)(*[int(p) for p in in_ptrs])
+    outs = (ctypes.c_void_p * W)(*[int(p) for p in out_ptrs])
+    _check(lib().mzk_ntt_multi_dev(fid, _p(_one(fid, root)), ins, outs, n, int(bool(inverse)), int(layout_in), int(layout_out)))
 
 
 class SrsMulti:
@@ -311,26 +301,25 @@ class SrsMulti:
         if powers is not None:
             p = np.ascontiguousarray(powers, dtype=np.uint64).reshape(-1, 8)
             self.n = p.shape[0]
-            _check(lib().mzk_srs_upload_multi(_p(p), ctypes.c_size_t(self.n), ctypes.byref(self._h)))
+            _check(lib().mzk_srs_upload_multi(_p(p), self.n, ctypes.byref(self._h)))
         else:
             a, g = _one(FIELD_FR, alpha), points_to_array([g1])
             self.n = max_d + 1
-            _check(lib().mzk_kzg_setup_srs_multi(_p(a), _p(g), ctypes.c_size_t(max_d), int(with_tables), ctypes.byref(self._h)))
-        lib().mzk_srs_multi_shard_lo.restype = ctypes.c_size_t
+            _check(lib().mzk_kzg_setup_srs_multi(_p(a), _p(g), max_d, int(with_tables), ctypes.byref(self._h)))
         self.world = int(lib().mzk_srs_multi_world(self._h))
         self.lo = [int(lib().mzk_srs_multi_shard_lo(self._h, r)) for r in range(self.world + 1)]
 
     def commit(self, coef):
         c = np.ascontiguousarray(coef, dtype=np.uint64).reshape(-1, 4)
         out = np.zeros((1, 8), dtype=np.uint64)
-        _check(lib().mzk_kzg_commit_srs_multi(self._h, _p(c), ctypes.c_size_t(c.shape[0]), _p(out)))
+        _check(lib().mzk_kzg_commit_srs_multi(self._h, _p(c), c.shape[0], _p(out)))
         return array_to_points(out)[0]
 
     def commit_dev(self, shard_ptrs, n):
         """shard_ptrs[r]: device pointer (int) on context r's GPU to coefficients [lo[r], min(lo[r+1], n))."""
-        arr = (ctypes.c_void_p * self.world)(*[ctypes.c_void_p(int(x)) for x in shard_ptrs])
+        arr = (ctypes.c_void_p * self.world)(*[int(x) for x in shard_ptrs])
         out = np.zeros((1, 8), dtype=np.uint64)
-        _check(lib().mzk_kzg_commit_srs_multi_dev(self._h, arr, ctypes.c_size_t(n), _p(out)))
+        _check(lib().mzk_kzg_commit_srs_multi_dev(self._h, arr, n, _p(out)))
         return array_to_points(out)[0]
 
     def close(self):
@@ -349,7 +338,7 @@ def kzg_setup_g1(alpha, max_d, g1=(1, 2)):
     """setup_kzg (algebra/kzg.rs:27-40), G1 powers for a caller-supplied trapdoor."""
     out = np.zeros((max_d + 1, 8), dtype=np.uint64)
     a, g = _one(FIELD_FR, alpha), points_to_array([g1])
-    _check(lib().mzk_kzg_setup_g1(_p(a), _p(g), ctypes.c_size_t(max_d), _p(out)))
+    _check(lib().mzk_kzg_setup_g1(_p(a), _p(g), max_d, _p(out)))
     return out
 
 
@@ -362,7 +351,7 @@ def kzg_open(coef, u, powers):
     y = np.zeros((1, 4), dtype=np.uint64)
     w = np.zeros((1, 8), dtype=np.uint64)
     uu = _one(FIELD_FR, u)
-    _check(lib().mzk_kzg_open(_p(c), ctypes.c_size_t(c.shape[0]), _p(uu), _p(p), _p(y), _p(w)))
+    _check(lib().mzk_kzg_open(_p(c), c.shape[0], _p(uu), _p(p), _p(y), _p(w)))
     return from_limbs(y)[0], array_to_points(w)[0]
 
 
@@ -377,7 +366,7 @@ def kzg_batch_open(coef, us, powers):
         raise MzkError(-5, "index out of bounds: the len is %d but the index is %d" % (p.shape[0], p.shape[0]))
     ys = np.zeros((max(k, 1), 4), dtype=np.uint64)
     w = np.zeros((1, 8), dtype=np.uint64)
-    _check(lib().mzk_kzg_batch_open(_p(c), ctypes.c_size_t(c.shape[0]), _p(u), ctypes.c_size_t(k), _p(p), _p(ys), _p(w)))
+    _check(lib().mzk_kzg_batch_open(_p(c), c.shape[0], _p(u), k, _p(p), _p(ys), _p(w)))
     return from_limbs(ys[:k]), array_to_points(w)[0]
 
 
@@ -386,7 +375,7 @@ def kzg_prove_degree_bound(coef, powers, d):
     c = np.ascontiguousarray(coef, dtype=np.uint64).reshape(-1, 4)
     p = np.ascontiguousarray(powers, dtype=np.uint64).reshape(-1, 8)
     out = np.zeros((1, 8), dtype=np.uint64)
-    _check(lib().mzk_kzg_prove_degree_bound(_p(c), ctypes.c_size_t(c.shape[0]), _p(p), ctypes.c_size_t(p.shape[0]), ctypes.c_size_t(d), _p(out)))
+    _check(lib().mzk_kzg_prove_degree_bound(_p(c), c.shape[0], _p(p), p.shape[0], d, _p(out)))
     return array_to_points(out)[0]
 
 
@@ -395,7 +384,7 @@ def fri_fold(fid, codeword, alpha, offset, omega):
     c = _arr(fid, codeword)
     out = np.zeros((max(c.shape[0] // 2, 1), LIMBS[fid]), dtype=np.uint64)
     a, o, w = _one(fid, alpha), _one(fid, offset), _one(fid, omega)
-    _check(lib().mzk_fri_fold(fid, _p(c), ctypes.c_size_t(c.shape[0]), _p(a), _p(o), _p(w), _p(out)))
+    _check(lib().mzk_fri_fold(fid, _p(c), c.shape[0], _p(a), _p(o), _p(w), _p(out)))
     return out[:c.shape[0] // 2]
 
 
@@ -406,12 +395,12 @@ class Srs:
         p = np.ascontiguousarray(powers, dtype=np.uint64).reshape(-1, 8)
         self._h = ctypes.c_void_p()
         self.n = p.shape[0]
-        _check(lib().mzk_srs_upload(_p(p), ctypes.c_size_t(self.n), ctypes.byref(self._h)))
+        _check(lib().mzk_srs_upload(_p(p), self.n, ctypes.byref(self._h)))
 
     def commit(self, coef):
         c = np.ascontiguousarray(coef, dtype=np.uint64).reshape(-1, 4)
         out = np.zeros((1, 8), dtype=np.uint64)
-        _check(lib().mzk_kzg_commit_srs(self._h, _p(c), ctypes.c_size_t(c.shape[0]), _p(out)))
+        _check(lib().mzk_kzg_commit_srs(self._h, _p(c), c.shape[0], _p(out)))
         return array_to_points(out)[0]
 
     def commit_batch(self, coefs):
@@ -423,7 +412,7 @@ class Srs:
             return []
         c = c.reshape(count, -1, 4)
         out = np.zeros((max(count, 1), 8), dtype=np.uint64)
-        _check(lib().mzk_kzg_commit_srs_batch(self._h, _p(c), ctypes.c_size_t(c.shape[1]), ctypes.c_size_t(count), _p(out)))
+        _check(lib().mzk_kzg_commit_srs_batch(self._h, _p(c), c.shape[1], count, _p(out)))
         return array_to_points(out[:count])
 
     def commit_many(self, coefs):
@@ -435,11 +424,10 @@ class Srs:
         if count == 0:
             return []
         c = c.reshape(count, -1, 4)
-        st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+        st = torch.cuda.current_stream().cuda_stream
         d_c = torch.from_numpy(c.view(np.int64).reshape(-1).copy()).cuda() if c.size else torch.zeros(4, dtype=torch.int64, device="cuda")
         d_o = torch.zeros(count * 8, dtype=torch.int64, device="cuda")
-        _check(lib().mzk_kzg_commit_srs_many_dev(self._h, ctypes.c_void_p(d_c.data_ptr()), ctypes.c_size_t(c.shape[1]), ctypes.c_size_t(count),
-                                                 ctypes.c_void_p(d_o.data_ptr()), st))
+        _check(lib().mzk_kzg_commit_srs_many_dev(self._h, d_c.data_ptr(), c.shape[1], count, d_o.data_ptr(), st))
         torch.cuda.synchronize()
         return array_to_points(d_o.cpu().numpy().view(np.uint64).reshape(count, 8))
 
@@ -459,7 +447,7 @@ class Srs:
 
     def build_direct(self, window_bits=0, max_bytes=0):
         """Direct tables for batches of short polynomials (mzk_srs_build_direct); returns the width built."""
-        _check(lib().mzk_srs_build_direct(self._h, int(window_bits), ctypes.c_size_t(max_bytes), None))
+        _check(lib().mzk_srs_build_direct(self._h, int(window_bits), max_bytes, None))
         return int(lib().mzk_srs_direct_bits(self._h))
 
     def drop_direct(self):
@@ -474,14 +462,13 @@ class Srs:
         self = cls.__new__(cls)
         self._h = ctypes.c_void_p()
         _check(lib().mzk_srs_load(os.fsencode(path), int(with_tables), ctypes.byref(self._h)))
-        lib().mzk_srs_len.restype = ctypes.c_size_t
         self.n = int(lib().mzk_srs_len(self._h))
         return self
 
     def download(self):
         """powers_1 back as an (n, 8) limb array."""
         out = np.zeros((max(self.n, 1), 8), dtype=np.uint64)
-        _check(lib().mzk_srs_download(self._h, _p(out), ctypes.c_size_t(self.n)))
+        _check(lib().mzk_srs_download(self._h, _p(out), self.n))
         return out[:self.n]
 
     def close(self):
@@ -509,7 +496,7 @@ class MerkleTree:
             ng = np.ascontiguousarray(negative, dtype=np.uint8)
             self.n = e.shape[0]
             self.stride = 48
-            _check(lib().mzk_merkle_build_field_signed(fid, _p(e), _p(ng), ctypes.c_size_t(self.n), ctypes.byref(self._h)))
+            _check(lib().mzk_merkle_build_field_signed(fid, _p(e), _p(ng), self.n, ctypes.byref(self._h)))
         elif leaves is not None:
             blob = b"".join(leaves)
             off = np.zeros(len(leaves) + 1, dtype=np.uint64)
@@ -517,17 +504,17 @@ class MerkleTree:
             buf = (ctypes.c_uint8 * max(len(blob), 1)).from_buffer_copy(blob or b"\0")
             self.n = len(leaves)
             self.stride = max([32] + [len(x) for x in leaves])
-            _check(lib().mzk_merkle_build_bytes(buf, _p(off), ctypes.c_size_t(self.n), ctypes.byref(self._h)))
+            _check(lib().mzk_merkle_build_bytes(buf, _p(off), self.n, ctypes.byref(self._h)))
         else:
             e = _arr(fid, elems)
             self.n = e.shape[0]
             self.stride = _leaf_stride(fid)
-            _check(lib().mzk_merkle_build_field(fid, _p(e), ctypes.c_size_t(self.n), ctypes.byref(self._h)))
+            _check(lib().mzk_merkle_build_field(fid, _p(e), self.n, ctypes.byref(self._h)))
 
     def root(self):
         buf = (ctypes.c_uint8 * max(self.stride, 64))()
         ln = ctypes.c_size_t()
-        _check(lib().mzk_merkle_root(self._h, buf, ctypes.c_size_t(len(buf)), ctypes.byref(ln)))
+        _check(lib().mzk_merkle_root(self._h, buf, len(buf), ctypes.byref(ln)))
         return bytes(buf[:ln.value])
 
     def open(self, index):
@@ -535,7 +522,7 @@ class MerkleTree:
         buf = (ctypes.c_uint8 * (self.stride * depth_cap))()
         lens = (ctypes.c_uint64 * depth_cap)()
         depth = ctypes.c_size_t()
-        _check(lib().mzk_merkle_open(self._h, ctypes.c_size_t(index), buf, ctypes.c_size_t(self.stride), lens, ctypes.byref(depth)))
+        _check(lib().mzk_merkle_open(self._h, index, buf, self.stride, lens, ctypes.byref(depth)))
         raw = bytes(buf)
         return [raw[k * self.stride:k * self.stride + lens[k]] for k in range(depth.value)]
 
@@ -547,7 +534,7 @@ class MerkleTree:
         buf = (ctypes.c_uint8 * max(self.stride * depth_cap * count, 1))()
         lens = (ctypes.c_uint64 * max(depth_cap * count, 1))()
         depth = ctypes.c_size_t()
-        _check(lib().mzk_merkle_open_batch(self._h, _p(idx), ctypes.c_size_t(count), buf, ctypes.c_size_t(self.stride), lens, ctypes.byref(depth)))
+        _check(lib().mzk_merkle_open_batch(self._h, _p(idx), count, buf, self.stride, lens, ctypes.byref(depth)))
         raw, d = bytes(buf), depth.value
         return [[raw[(q * d + k) * self.stride:(q * d + k) * self.stride + lens[q * d + k]] for k in range(d)] for q in range(count)]
 
@@ -559,7 +546,7 @@ class MerkleTree:
             raise MzkError(-1, "leaves: field-element trees only")
         out = np.zeros((idx.shape[0], nl), dtype=np.uint64)
         neg = np.zeros(idx.shape[0], dtype=np.uint8)
-        _check(lib().mzk_merkle_leaves(self._h, _p(idx), ctypes.c_size_t(idx.shape[0]), _p(out), _p(neg) if with_sign else None))
+        _check(lib().mzk_merkle_leaves(self._h, _p(idx), idx.shape[0], _p(out), _p(neg) if with_sign else None))
         return (out, neg) if with_sign else out
 
     def close(self):
@@ -587,7 +574,7 @@ def merkle_open_multi(trees, index_lists):
     stride = max([48] + [t.stride for t, c in zip(trees, counts) if t is not None and c])
     buf = (ctypes.c_uint8 * max(stride * entries, 1))()
     lens = (ctypes.c_uint64 * max(entries, 1))()
-    _check(lib().mzk_merkle_open_multi(handles, ctypes.c_size_t(T), _p(flat) if flat.size else None, cnt, buf, ctypes.c_size_t(stride), lens, depths))
+    _check(lib().mzk_merkle_open_multi(handles, T, _p(flat) if flat.size else None, cnt, buf, stride, lens, depths))
     raw, out, at = memoryview(buf), [], 0
     for t in range(T):
         d, paths = depths[t], []
@@ -603,7 +590,7 @@ def merkle_commit_field(fid, elems):
     e = _arr(fid, elems)
     buf = (ctypes.c_uint8 * 64)()
     ln = ctypes.c_size_t()
-    _check(lib().mzk_merkle_commit_field(fid, _p(e), ctypes.c_size_t(e.shape[0]), buf, ctypes.c_size_t(64), ctypes.byref(ln)))
+    _check(lib().mzk_merkle_commit_field(fid, _p(e), e.shape[0], buf, 64, ctypes.byref(ln)))
     return bytes(buf[:ln.value])
 
 
@@ -632,26 +619,25 @@ def gemini_split_fold(coef, rhos):
     n = c.shape[0]
     r = to_limbs(list(rhos), 4) if len(rhos) else np.zeros((1, 4), dtype=np.uint64)
     out = np.zeros((max(2 * n - 1, 1), 4), dtype=np.uint64)
-    _check(lib().mzk_gemini_split_fold(_p(c) if n else None, ctypes.c_size_t(n), _p(r), ctypes.c_size_t(len(rhos)), _p(out)))
+    _check(lib().mzk_gemini_split_fold(_p(c) if n else None, n, _p(r), len(rhos), _p(out)))
     return _levels_split(out, n)
 
 
 def gemini_split_fold_dev(d_coef, n, rhos, d_out, stream=None):
     """mzk_gemini_split_fold_dev: device pointers (ints), the 2n - 1 packed levels written at d_out; only enqueues."""
     r = to_limbs(list(rhos), 4) if len(rhos) else np.zeros((1, 4), dtype=np.uint64)
-    _check(lib().mzk_gemini_split_fold_dev(ctypes.c_void_p(int(d_coef)), ctypes.c_size_t(n), _p(r), ctypes.c_size_t(len(rhos)),
-                                           ctypes.c_void_p(int(d_out)), ctypes.c_void_p(stream)))
+    _check(lib().mzk_gemini_split_fold_dev(int(d_coef), n, _p(r), len(rhos), int(d_out), stream))
 
 
 def sumcheck_sum(coef):
     """sum_over_boolean_hypercube (algebra/sumcheck.rs:57-66) of the multilinear g with these coefficients (get_coefs_in_order)."""
     c = np.ascontiguousarray(coef, dtype=np.uint64).reshape(-1, 4)
     h = np.zeros((1, 4), dtype=np.uint64)
-    _check(lib().mzk_sumcheck_sum(_p(c) if c.shape[0] else None, ctypes.c_size_t(c.shape[0]), _p(h)))
+    _check(lib().mzk_sumcheck_sum(_p(c) if c.shape[0] else None, c.shape[0], _p(h)))
     return from_limbs(h)[0]
 
 
-SCP_SECTIONS = ("status", "sum", "evals", "challenges", "finals", "transcript_len", "transcript")
+SCP_SECTIONS = _abi.index_names("MZK_SCP_SECTIONS")
 
 
 def sumcheck_product_layout(num_vars, num_factors, max_degree, header_len=0):
@@ -659,8 +645,7 @@ def sumcheck_product_layout(num_vars, num_factors, max_degree, header_len=0):
     off = (ctypes.c_uint64 * len(SCP_SECTIONS))()
     size = (ctypes.c_uint64 * len(SCP_SECTIONS))()
     total = ctypes.c_uint64()
-    _check(lib().mzk_sumcheck_product_layout(ctypes.c_size_t(num_vars), ctypes.c_size_t(num_factors), ctypes.c_size_t(max_degree),
-                                             ctypes.c_size_t(header_len), off, size, ctypes.byref(total)))
+    _check(lib().mzk_sumcheck_product_layout(num_vars, num_factors, max_degree, header_len, off, size, ctypes.byref(total)))
     return {k: (off[i], size[i]) for i, k in enumerate(SCP_SECTIONS)}, total.value
 
 
@@ -713,18 +698,16 @@ def sumcheck_product_prove(tables, max_degree, header_objects=(), device_ptr=Non
         if n != 1 << num_vars:
             raise ValueError("tables: 2^num_vars values per factor")
     _, total = sumcheck_product_layout(num_vars, num_factors, max_degree, len(header))
-    args = (ctypes.c_size_t(num_vars), ctypes.c_size_t(num_factors), ctypes.c_size_t(max_degree), hbuf, ctypes.c_size_t(len(header)),
-            ctypes.c_size_t(len(header_objects)))
+    args = (num_vars, num_factors, max_degree, hbuf, len(header), len(header_objects))
     if device_ptr is None:
         buf = (ctypes.c_uint8 * total)()
-        _check(lib().mzk_sumcheck_product_prove(_p(t), *args, buf, ctypes.c_size_t(total)))
+        _check(lib().mzk_sumcheck_product_prove(_p(t), *args, buf, total))
         packed = bytes(buf)
     else:
         import torch
         proof = torch.empty(total, dtype=torch.uint8, device="cuda")
         stream = torch.cuda.current_stream()
-        _check(lib().mzk_sumcheck_product_prove_dev(ctypes.c_void_p(int(device_ptr)), *args, ctypes.c_void_p(proof.data_ptr()), ctypes.c_size_t(total),
-                                                    ctypes.c_void_p(stream.cuda_stream)))
+        _check(lib().mzk_sumcheck_product_prove_dev(int(device_ptr), *args, proof.data_ptr(), total, stream.cuda_stream))
         stream.synchronize()
         packed = proof.cpu().numpy().tobytes()
     return packed if raw else sumcheck_product_unpack(num_vars, num_factors, max_degree, len(header), packed)
@@ -735,8 +718,7 @@ def mle_evals_from_coeffs(coef, device_ptr=None, num_vars=None, out_ptr=None, st
     coef[t] multiplies the x_i whose bit (el-1-i) of t is set; returns the (2^el, 4) table.  device_ptr / num_vars / out_ptr: device
     buffers (out_ptr may equal device_ptr), only enqueues on `stream`."""
     if device_ptr is not None:
-        _check(lib().mzk_mle_evals_from_coeffs_dev(ctypes.c_void_p(int(device_ptr)), ctypes.c_size_t(num_vars), ctypes.c_void_p(int(out_ptr)),
-                                                   ctypes.c_void_p(stream)))
+        _check(lib().mzk_mle_evals_from_coeffs_dev(int(device_ptr), num_vars, int(out_ptr), stream))
         return None
     c = np.ascontiguousarray(coef, dtype=np.uint64).reshape(-1, 4)
     n = c.shape[0]
@@ -744,19 +726,25 @@ def mle_evals_from_coeffs(coef, device_ptr=None, num_vars=None, out_ptr=None, st
     if n != 1 << num_vars:
         raise ValueError("coef: 2^num_vars values")
     out = np.empty_like(c)
-    _check(lib().mzk_mle_evals_from_coeffs(_p(c), ctypes.c_size_t(num_vars), _p(out)))
+    _check(lib().mzk_mle_evals_from_coeffs(_p(c), num_vars, _p(out)))
     return out
 
 
-HYPER_AUTO, HYPER_TILE, HYPER_SCATTER = 0, 1, 2
-HYPER_PLAN_FACTORS = 8
-_HYPER_PLAN_SCALARS = ("form", "tile_log", "terms", "masks", "groups", "max_masks", "max_groups", "launches", "memsets", "grid_x", "grid_y",
-                       "mle_passes", "upload_bytes", "workspace_bytes", "table_bytes")
+HYPER_AUTO, HYPER_TILE, HYPER_SCATTER = _C["MZK_HYPER_AUTO"], _C["MZK_HYPER_TILE"], _C["MZK_HYPER_SCATTER"]
+HYPER_PLAN_FACTORS = _C["MZK_HYPER_PLAN_FACTORS"]
+
+
+def _struct_fields(name):
+    """the header's struct `name` (uint64_t scalars and arrays) as ctypes _fields_"""
+    return [(f, ctypes.c_uint64 if k is None else ctypes.c_uint64 * k) for f, k in _abi.c_structs(names=(name,))[0][1]]
 
 
 class _HypercubePlan(ctypes.Structure):
-    _fields_ = [(n, ctypes.c_uint64) for n in _HYPER_PLAN_SCALARS] + [("factor_masks", ctypes.c_uint64 * HYPER_PLAN_FACTORS),
-                                                                      ("factor_groups", ctypes.c_uint64 * HYPER_PLAN_FACTORS)]
+    """mzk_hypercube_plan (include/mzk.h)"""
+    _fields_ = _struct_fields("mzk_hypercube_plan")
+
+
+_HYPER_PLAN_SCALARS = tuple(f for f, t in _HypercubePlan._fields_ if t is ctypes.c_uint64)
 
 
 def hypercube_term_table(factors, num_vars=None):
@@ -797,7 +785,7 @@ def mpoly_hypercube_plan(factors, num_vars=None, form=HYPER_AUTO):
     distinct masks and groups (totals, maxima and per factor), launches, grid, bytes uploaded, workspace and table bytes."""
     _, te, toff, nv = hypercube_term_table(factors, num_vars)
     out = _HypercubePlan()
-    _check(lib().mzk_mpoly_hypercube_plan(_p(te), toff, ctypes.c_size_t(len(factors)), ctypes.c_size_t(nv), int(form), ctypes.byref(out)))
+    _check(lib().mzk_mpoly_hypercube_plan(_p(te), toff, len(factors), nv, int(form), ctypes.byref(out)))
     d = {n: int(getattr(out, n)) for n in _HYPER_PLAN_SCALARS}
     shown = min(len(factors), HYPER_PLAN_FACTORS)
     d["factor_masks"] = [int(out.factor_masks[f]) for f in range(shown)]
@@ -810,9 +798,9 @@ def mpoly_hypercube_evals(factors, num_vars=None, form=HYPER_AUTO, out_ptr=None,
     significant index bit, as sumcheck_product_prove takes them.  out_ptr: the tables are written to that device buffer
     (mzk_mpoly_hypercube_evals_dev, enqueued on `stream`) and None is returned."""
     tc, te, toff, nv = hypercube_term_table(factors, num_vars)
-    args = (_p(tc), _p(te), toff, ctypes.c_size_t(len(factors)), ctypes.c_size_t(nv), int(form))
+    args = (_p(tc), _p(te), toff, len(factors), nv, int(form))
     if out_ptr is not None:
-        _check(lib().mzk_mpoly_hypercube_evals_dev(*args, ctypes.c_void_p(int(out_ptr)), ctypes.c_void_p(stream)))
+        _check(lib().mzk_mpoly_hypercube_evals_dev(*args, int(out_ptr), stream))
         return None
     out = np.empty((len(factors), 1 << nv, 4), dtype=np.uint64)
     _check(lib().mzk_mpoly_hypercube_evals(*args, _p(out)))
@@ -828,17 +816,16 @@ def sumcheck_product_prove_terms(factors, max_degree, header_objects=(), num_var
     header = sumcheck_frame_header(header_objects)
     hbuf = (ctypes.c_uint8 * max(len(header), 1)).from_buffer_copy(header or b"\0")
     _, total = sumcheck_product_layout(nv, k, max_degree, len(header))
-    args = (_p(tc), _p(te), toff, ctypes.c_size_t(k), ctypes.c_size_t(nv), ctypes.c_size_t(max_degree), hbuf, ctypes.c_size_t(len(header)),
-            ctypes.c_size_t(len(header_objects)))
+    args = (_p(tc), _p(te), toff, k, nv, max_degree, hbuf, len(header), len(header_objects))
     if not device:
         buf = (ctypes.c_uint8 * total)()
-        _check(lib().mzk_sumcheck_product_prove_terms(*args, buf, ctypes.c_size_t(total)))
+        _check(lib().mzk_sumcheck_product_prove_terms(*args, buf, total))
         packed = bytes(buf)
     else:
         import torch
         proof = torch.empty(total, dtype=torch.uint8, device="cuda")
         stream = torch.cuda.current_stream()
-        _check(lib().mzk_sumcheck_product_prove_terms_dev(*args, ctypes.c_void_p(proof.data_ptr()), ctypes.c_size_t(total), ctypes.c_void_p(stream.cuda_stream)))
+        _check(lib().mzk_sumcheck_product_prove_terms_dev(*args, proof.data_ptr(), total, stream.cuda_stream))
         stream.synchronize()
         packed = proof.cpu().numpy().tobytes()
     return packed if raw else sumcheck_product_unpack(nv, k, max_degree, len(header), packed)
@@ -851,7 +838,7 @@ def _gemini_commit(h, levels):
     arr, n = _levels_packed(levels)
     el = max(n.bit_length() - 1, 0)
     out = np.zeros((el + 1, 8), dtype=np.uint64)
-    _check(lib().mzk_gemini_commit_srs(h, _p(arr), ctypes.c_size_t(n), _p(out)))
+    _check(lib().mzk_gemini_commit_srs(h, _p(arr), n, _p(out)))
     return array_to_points(out)
 
 
@@ -862,7 +849,7 @@ def _gemini_open(h, levels, beta):
     ws = np.zeros((max(el, 1), 8), dtype=np.uint64)
     deg = np.zeros((el + 1, 8), dtype=np.uint64)
     b = to_limbs([beta], 4)
-    _check(lib().mzk_gemini_open_srs(h, _p(arr), ctypes.c_size_t(n), _p(b), _p(ys), _p(ws), _p(deg)))
+    _check(lib().mzk_gemini_open_srs(h, _p(arr), n, _p(b), _p(ys), _p(ws), _p(deg)))
     y = from_limbs(ys[:3 * el]) if el else []
     return [tuple(y[3 * i:3 * i + 3]) for i in range(el)], (array_to_points(ws[:el]) if el else []), array_to_points(deg)
 
@@ -897,8 +884,7 @@ def _sumcheck_prove(h, coef, challenge):
     commits, deg = np.zeros((el + 1, 8), dtype=np.uint64), np.zeros((el + 1, 8), dtype=np.uint64)
     ys, ws = np.zeros((3 * k, 4), dtype=np.uint64), np.zeros((k, 8), dtype=np.uint64)
     fn = _SUMCHECK_CB(cb)
-    rc = lib().mzk_sumcheck_prove_srs(h, _p(c) if n else None, ctypes.c_size_t(n), fn, None, _p(gs), _p(rs), _p(beta), _p(commits), _p(ys), _p(ws),
-                                      _p(deg))
+    rc = lib().mzk_sumcheck_prove_srs(h, _p(c) if n else None, n, fn, None, _p(gs), _p(rs), _p(beta), _p(commits), _p(ys), _p(ws), _p(deg))
     if failure:
         raise failure[0]
     _check(rc)
@@ -957,16 +943,15 @@ def fri_commit(fid, codeword, omega, offset, num_rounds, challenge, negative=Non
         ng = None if negative is None else np.ascontiguousarray(negative, dtype=np.uint8)
         cw_out = _p(allcw) if codewords else None
         if device_ptr is not None:
-            rc = lib().mzk_fri_commit_keep_trees_dev(fid, ctypes.c_void_p(int(device_ptr)), None if ng is None else _p(ng), ctypes.c_size_t(n), _p(w), _p(o),
+            rc = lib().mzk_fri_commit_keep_trees_dev(fid, int(device_ptr), None if ng is None else _p(ng), n, _p(w), _p(o),
                                                      int(num_rounds), fn, None, roots, lens, cw_out, handles)
         else:
-            rc = lib().mzk_fri_commit_keep_trees(fid, _p(c), None if ng is None else _p(ng), ctypes.c_size_t(n), _p(w), _p(o), int(num_rounds), fn, None,
-                                                 roots, lens, cw_out, handles)
+            rc = lib().mzk_fri_commit_keep_trees(fid, _p(c), None if ng is None else _p(ng), n, _p(w), _p(o), int(num_rounds), fn, None, roots, lens, cw_out, handles)
     elif negative is not None:
         ng = np.ascontiguousarray(negative, dtype=np.uint8)
-        rc = lib().mzk_fri_commit_signed(fid, _p(c), _p(ng), ctypes.c_size_t(n), _p(w), _p(o), int(num_rounds), fn, None, roots, lens, _p(allcw))
+        rc = lib().mzk_fri_commit_signed(fid, _p(c), _p(ng), n, _p(w), _p(o), int(num_rounds), fn, None, roots, lens, _p(allcw))
     else:
-        rc = lib().mzk_fri_commit(fid, _p(c), ctypes.c_size_t(n), _p(w), _p(o), int(num_rounds), fn, None, roots, lens, _p(allcw))
+        rc = lib().mzk_fri_commit(fid, _p(c), n, _p(w), _p(o), int(num_rounds), fn, None, roots, lens, _p(allcw))
     if failure:
         raise failure[0]
     _check(rc)
@@ -993,8 +978,8 @@ def fri_commit(fid, codeword, omega, offset, num_rounds, challenge, negative=Non
     return cws, rts
 
 
-FRI_SECTIONS = ("status", "top_indices", "roots", "last_codeword", "values", "signs", "paths", "path_lens")
-FRI_PATH_STRIDE = 48
+FRI_SECTIONS = _abi.index_names("MZK_FRI_SECTIONS")
+FRI_PATH_STRIDE = _C["MZK_FRI_PATH_STRIDE"]
 
 
 def fri_proof_layout(fid, n, expansion_factor, num_colinearity_tests):
@@ -1003,8 +988,7 @@ def fri_proof_layout(fid, n, expansion_factor, num_colinearity_tests):
     off = (ctypes.c_uint64 * len(FRI_SECTIONS))()
     size = (ctypes.c_uint64 * len(FRI_SECTIONS))()
     total = ctypes.c_uint64()
-    _check(lib().mzk_fri_proof_layout(int(fid), ctypes.c_size_t(n), ctypes.c_size_t(expansion_factor), ctypes.c_size_t(num_colinearity_tests),
-                                      ctypes.byref(rounds), off, size, ctypes.byref(total)))
+    _check(lib().mzk_fri_proof_layout(int(fid), n, expansion_factor, num_colinearity_tests, ctypes.byref(rounds), off, size, ctypes.byref(total)))
     return rounds.value, {k: (off[i], size[i]) for i, k in enumerate(FRI_SECTIONS)}, total.value
 
 
@@ -1064,22 +1048,20 @@ def fri_prove(fid, codeword, omega, offset, expansion_factor, num_colinearity_te
         n = c.shape[0]
         ng = None if negative is None else np.ascontiguousarray(negative, dtype=np.uint8)
         buf = (ctypes.c_uint8 * total)()
-        _check(lib().mzk_fri_prove(int(fid), _p(c), None if ng is None else _p(ng), ctypes.c_size_t(n), _p(w), _p(o), ctypes.c_size_t(expansion_factor),
-                                   ctypes.c_size_t(num_colinearity_tests), buf, ctypes.c_size_t(total)))
+        _check(lib().mzk_fri_prove(int(fid), _p(c), None if ng is None else _p(ng), n, _p(w), _p(o), expansion_factor, num_colinearity_tests, buf, total))
         raw = bytes(buf)
     else:
         import torch
         proof = torch.empty(total, dtype=torch.uint8, device="cuda")
         stream = torch.cuda.current_stream()
-        _check(lib().mzk_fri_prove_dev(int(fid), ctypes.c_void_p(int(device_ptr)), None if negative is None else ctypes.c_void_p(int(negative)),
-                                       ctypes.c_size_t(n), _p(w), _p(o), ctypes.c_size_t(expansion_factor), ctypes.c_size_t(num_colinearity_tests),
-                                       ctypes.c_void_p(proof.data_ptr()), ctypes.c_size_t(total), ctypes.c_void_p(stream.cuda_stream)))
+        _check(lib().mzk_fri_prove_dev(int(fid), int(device_ptr), None if negative is None else int(negative), n, _p(w), _p(o), expansion_factor, num_colinearity_tests,
+                                       proof.data_ptr(), total, stream.cuda_stream))
         stream.synchronize()
         raw = proof.cpu().numpy().tobytes()
     return fri_unpack_proof(fid, n, expansion_factor, num_colinearity_tests, raw)
 
 
-FRI_PATH_STRIDE_GL = 64
+FRI_PATH_STRIDE_GL = _C["MZK_FRI_PATH_STRIDE_GL"]
 
 
 def fri_proof_layout_gl(fid, n, expansion_factor, num_colinearity_tests):
@@ -1088,8 +1070,7 @@ def fri_proof_layout_gl(fid, n, expansion_factor, num_colinearity_tests):
     off = (ctypes.c_uint64 * len(FRI_SECTIONS))()
     size = (ctypes.c_uint64 * len(FRI_SECTIONS))()
     total = ctypes.c_uint64()
-    _check(lib().mzk_fri_proof_layout_gl(int(fid), ctypes.c_size_t(n), ctypes.c_size_t(expansion_factor), ctypes.c_size_t(num_colinearity_tests),
-                                         ctypes.byref(rounds), off, size, ctypes.byref(total)))
+    _check(lib().mzk_fri_proof_layout_gl(int(fid), n, expansion_factor, num_colinearity_tests, ctypes.byref(rounds), off, size, ctypes.byref(total)))
     return rounds.value, {k: (off[i], size[i]) for i, k in enumerate(FRI_SECTIONS)}, total.value
 
 
@@ -1111,16 +1092,14 @@ def fri_prove_gl(fid, codeword, omega, offset, expansion_factor, num_colinearity
     w, o = _one(fid, omega), _one(fid, offset)
     if device_ptr is None:
         buf = (ctypes.c_uint8 * total)()
-        _check(lib().mzk_fri_prove_gl(int(fid), _p(c), ctypes.c_size_t(n), _p(w), _p(o), ctypes.c_size_t(expansion_factor),
-                                      ctypes.c_size_t(num_colinearity_tests), buf, ctypes.c_size_t(total)))
+        _check(lib().mzk_fri_prove_gl(int(fid), _p(c), n, _p(w), _p(o), expansion_factor, num_colinearity_tests, buf, total))
         raw = bytes(buf)
     else:
         import torch
         proof = torch.empty(total, dtype=torch.uint8, device="cuda")
         stream = torch.cuda.current_stream()
-        _check(lib().mzk_fri_prove_gl_dev(int(fid), ctypes.c_void_p(int(device_ptr)), ctypes.c_size_t(n), _p(w), _p(o), ctypes.c_size_t(expansion_factor),
-                                          ctypes.c_size_t(num_colinearity_tests), ctypes.c_void_p(proof.data_ptr()), ctypes.c_size_t(total),
-                                          ctypes.c_void_p(stream.cuda_stream)))
+        _check(lib().mzk_fri_prove_gl_dev(int(fid), int(device_ptr), n, _p(w), _p(o), expansion_factor, num_colinearity_tests, proof.data_ptr(), total,
+                                          stream.cuda_stream))
         stream.synchronize()
         raw = proof.cpu().numpy().tobytes()
     return fri_unpack_proof_gl(fid, n, expansion_factor, num_colinearity_tests, raw)
@@ -1132,8 +1111,7 @@ def fast_coset_divide(fid, lhs, rhs, offset, root, root_order):
     out = np.zeros((max(a.shape[0], 1), LIMBS[fid]), dtype=np.uint64)
     ln = ctypes.c_size_t()
     o, r = _one(fid, offset), _one(fid, root)
-    _check(lib().mzk_fast_coset_divide(fid, _p(a), ctypes.c_size_t(a.shape[0]), _p(b), ctypes.c_size_t(b.shape[0]), _p(o), _p(r),
-                                       ctypes.c_size_t(root_order), _p(out), ctypes.byref(ln)))
+    _check(lib().mzk_fast_coset_divide(fid, _p(a), a.shape[0], _p(b), b.shape[0], _p(o), _p(r), root_order, _p(out), ctypes.byref(ln)))
     return out[:ln.value]
 
 
@@ -1151,9 +1129,8 @@ def fast_coset_divide_batch_dev(fid, d_lhs_ptr, lhs_stride, lhs_lens, d_rhs_ptr,
     ln = (ctypes.c_size_t * max(count, 1))(*[int(x) for x in lhs_lens])
     out_lens = (ctypes.c_size_t * max(count, 1))()
     o, r = _one(fid, offset), _one(fid, root)
-    _check(lib().mzk_fast_coset_divide_batch_dev(int(fid), ctypes.c_void_p(d_lhs_ptr), ctypes.c_size_t(lhs_stride), ln, ctypes.c_size_t(count),
-                                                 ctypes.c_void_p(d_rhs_ptr), ctypes.c_size_t(rhs_len), _p(o), _p(r), ctypes.c_size_t(root_order),
-                                                 ctypes.c_void_p(d_out_ptr), ctypes.c_size_t(out_stride), out_lens, ctypes.c_void_p(stream)))
+    _check(lib().mzk_fast_coset_divide_batch_dev(int(fid), d_lhs_ptr, lhs_stride, ln, count, d_rhs_ptr, rhs_len, _p(o), _p(r), root_order,
+                                                 d_out_ptr, out_stride, out_lens, stream))
     return [int(out_lens[i]) for i in range(count)]
 
 
@@ -1164,7 +1141,7 @@ def fast_zerofier(fid, domain, root, root_order):
     out = np.zeros((max(n + 1, _np2(n + 1)), LIMBS[fid]), dtype=np.uint64)
     ln = ctypes.c_size_t()
     r = _one(fid, root)
-    _check(lib().mzk_fast_zerofier(fid, _p(d), ctypes.c_size_t(n), _p(r), ctypes.c_size_t(root_order), _p(out), ctypes.byref(ln)))
+    _check(lib().mzk_fast_zerofier(fid, _p(d), n, _p(r), root_order, _p(out), ctypes.byref(ln)))
     return out[:ln.value]
 
 
@@ -1173,7 +1150,7 @@ def fast_evaluate(fid, coef, domain, root, root_order):
     c, d = _arr(fid, coef), _arr(fid, domain)
     out = np.zeros((max(d.shape[0], 1), LIMBS[fid]), dtype=np.uint64)
     r = _one(fid, root)
-    _check(lib().mzk_fast_evaluate(fid, _p(c), ctypes.c_size_t(c.shape[0]), _p(d), ctypes.c_size_t(d.shape[0]), _p(r), ctypes.c_size_t(root_order), _p(out)))
+    _check(lib().mzk_fast_evaluate(fid, _p(c), c.shape[0], _p(d), d.shape[0], _p(r), root_order, _p(out)))
     return out[:d.shape[0]]
 
 
@@ -1185,7 +1162,7 @@ def fast_interpolate(fid, domain, values, root, root_order):
     out = np.zeros((max(d.shape[0], 1), LIMBS[fid]), dtype=np.uint64)
     ln = ctypes.c_size_t()
     r = _one(fid, root)
-    _check(lib().mzk_fast_interpolate(fid, _p(d), _p(v), ctypes.c_size_t(d.shape[0]), _p(r), ctypes.c_size_t(root_order), _p(out), ctypes.byref(ln)))
+    _check(lib().mzk_fast_interpolate(fid, _p(d), _p(v), d.shape[0], _p(r), root_order, _p(out), ctypes.byref(ln)))
     return out[:ln.value]
 
 
@@ -1203,7 +1180,7 @@ def fast_interpolate_batch(fid, domain, values, root, root_order):
     out = np.zeros((batch, max(n, 1), LIMBS[fid]), dtype=np.uint64)
     lens = (ctypes.c_size_t * batch)()
     r = _one(fid, root)
-    _check(lib().mzk_fast_interpolate_batch(fid, _p(d), _p(v), ctypes.c_size_t(n), ctypes.c_size_t(batch), _p(r), ctypes.c_size_t(root_order), _p(out), lens))
+    _check(lib().mzk_fast_interpolate_batch(fid, _p(d), _p(v), n, batch, _p(r), root_order, _p(out), lens))
     return [out[k, :lens[k]] for k in range(batch)]
 
 
@@ -1214,8 +1191,7 @@ def fast_interpolate_batch_dev(fid, domain, d_values_ptr, batch, root, root_orde
     n = d.shape[0]
     lens = (ctypes.c_size_t * max(batch, 1))()
     r = _one(fid, root)
-    _check(lib().mzk_fast_interpolate_batch_dev(fid, _p(d), ctypes.c_void_p(d_values_ptr), ctypes.c_size_t(n), ctypes.c_size_t(batch), _p(r),
-                                                ctypes.c_size_t(root_order), ctypes.c_void_p(d_out_ptr), lens, ctypes.c_void_p(stream)))
+    _check(lib().mzk_fast_interpolate_batch_dev(fid, _p(d), d_values_ptr, n, batch, _p(r), root_order, d_out_ptr, lens, stream))
     return [int(lens[k]) for k in range(batch)]
 
 
@@ -1249,8 +1225,7 @@ def mpoly_compose_plan(fid, constraints, point_lens):
     _, te, toff = mpoly_term_table(fid, constraints, nv)
     n, smin = ctypes.c_size_t(0), ctypes.c_size_t(0)
     bounds = (ctypes.c_size_t * max(nc, 1))()
-    _check(lib().mzk_mpoly_compose_plan(int(fid), _p(te), toff, ctypes.c_size_t(nc), ctypes.c_size_t(nv), _offsets_of(point_lens),
-                                        ctypes.byref(n), ctypes.byref(smin), bounds))
+    _check(lib().mzk_mpoly_compose_plan(int(fid), _p(te), toff, nc, nv, _offsets_of(point_lens), ctypes.byref(n), ctypes.byref(smin), bounds))
     return n.value, smin.value, [int(bounds[a]) for a in range(nc)]
 
 
@@ -1266,8 +1241,7 @@ def mpoly_compose(fid, constraints, point, out_stride=None):
         out_stride = mpoly_compose_plan(fid, constraints, [q.shape[0] for q in pts])[1]
     out = np.zeros((max(nc, 1), max(out_stride, 1), LIMBS[fid]), dtype=np.uint64)
     lens = (ctypes.c_size_t * max(nc, 1))()
-    _check(lib().mzk_mpoly_compose(int(fid), _p(tc), _p(te), toff, ctypes.c_size_t(nc), ctypes.c_size_t(nv), _p(flat), poff, _p(out),
-                                   ctypes.c_size_t(out_stride), lens))
+    _check(lib().mzk_mpoly_compose(int(fid), _p(tc), _p(te), toff, nc, nv, _p(flat), poff, _p(out), out_stride, lens))
     return [out[a, :lens[a]].copy() for a in range(nc)]
 
 
@@ -1277,8 +1251,7 @@ def mpoly_compose_dev(fid, constraints, d_point_ptr, point_lens, d_out_ptr, out_
     nv, nc = len(point_lens), len(constraints)
     tc, te, toff = mpoly_term_table(fid, constraints, nv)
     lens = (ctypes.c_size_t * max(nc, 1))()
-    _check(lib().mzk_mpoly_compose_dev(int(fid), _p(tc), _p(te), toff, ctypes.c_size_t(nc), ctypes.c_size_t(nv), ctypes.c_void_p(d_point_ptr),
-                                       _offsets_of(point_lens), ctypes.c_void_p(d_out_ptr), ctypes.c_size_t(out_stride), lens, ctypes.c_void_p(stream)))
+    _check(lib().mzk_mpoly_compose_dev(int(fid), _p(tc), _p(te), toff, nc, nv, d_point_ptr, _offsets_of(point_lens), d_out_ptr, out_stride, lens, stream))
     return [int(lens[a]) for a in range(nc)]
 
 
@@ -1293,8 +1266,7 @@ def poly_lincomb(fid, polys, weights, shifts, out_cap=None):
     sh = (ctypes.c_size_t * max(count, 1))(*[int(x) for x in shifts])
     out = np.zeros((max(out_cap, 1), LIMBS[fid]), dtype=np.uint64)
     n = ctypes.c_size_t(0)
-    _check(lib().mzk_poly_lincomb(int(fid), _p(flat), _offsets_of([q.shape[0] for q in ps]), ctypes.c_size_t(count), _p(w), sh, _p(out),
-                                  ctypes.c_size_t(out_cap), ctypes.byref(n)))
+    _check(lib().mzk_poly_lincomb(int(fid), _p(flat), _offsets_of([q.shape[0] for q in ps]), count, _p(w), sh, _p(out), out_cap, ctypes.byref(n)))
     return out[:n.value].copy()
 
 
@@ -1304,8 +1276,7 @@ def poly_lincomb_dev(fid, d_polys_ptr, lens, weights, shifts, d_out_ptr, out_cap
     w = to_limbs([int(x) for x in weights], LIMBS[fid]) if count else np.zeros((0, LIMBS[fid]), dtype=np.uint64)
     sh = (ctypes.c_size_t * max(count, 1))(*[int(x) for x in shifts])
     n = ctypes.c_size_t(0)
-    _check(lib().mzk_poly_lincomb_dev(int(fid), ctypes.c_void_p(d_polys_ptr), _offsets_of(lens), ctypes.c_size_t(count), _p(w), sh,
-                                      ctypes.c_void_p(d_out_ptr), ctypes.c_size_t(out_cap), ctypes.byref(n), ctypes.c_void_p(stream)))
+    _check(lib().mzk_poly_lincomb_dev(int(fid), d_polys_ptr, _offsets_of(lens), count, _p(w), sh, d_out_ptr, out_cap, ctypes.byref(n), stream))
     return n.value
 
 
@@ -1327,8 +1298,7 @@ def poly_div_roots(fid, polys, roots, stride=None):
     r = to_limbs(rs, nl) if rs else np.zeros((1, nl), dtype=np.uint64)
     out = np.zeros_like(flat)
     out_lens = (ctypes.c_size_t * max(count, 1))()
-    _check(lib().mzk_poly_div_roots(int(fid), _p(flat), ctypes.c_size_t(stride), lens, ctypes.c_size_t(count), _p(r),
-                                    _offsets_of([len(row) for row in roots]), _p(out), out_lens))
+    _check(lib().mzk_poly_div_roots(int(fid), _p(flat), stride, lens, count, _p(r), _offsets_of([len(row) for row in roots]), _p(out), out_lens))
     return [out[i * stride:i * stride + int(out_lens[i])].copy() for i in range(count)]
 
 
@@ -1342,22 +1312,19 @@ def poly_div_roots_dev(fid, d_polys_ptr, stride, lens, roots, d_out_ptr, stream=
     r = to_limbs(rs, nl) if rs else np.zeros((1, nl), dtype=np.uint64)
     ln = (ctypes.c_size_t * max(count, 1))(*[int(x) for x in lens])
     out_lens = (ctypes.c_size_t * max(count, 1))()
-    _check(lib().mzk_poly_div_roots_dev(int(fid), ctypes.c_void_p(d_polys_ptr), ctypes.c_size_t(stride), ln, ctypes.c_size_t(count), _p(r),
-                                        _offsets_of([len(row) for row in roots]), ctypes.c_void_p(d_out_ptr), out_lens, ctypes.c_void_p(stream)))
+    _check(lib().mzk_poly_div_roots_dev(int(fid), d_polys_ptr, stride, ln, count, _p(r), _offsets_of([len(row) for row in roots]), d_out_ptr, out_lens, stream))
     return [int(out_lens[i]) for i in range(count)]
 
 
-STARK_MAX_REGISTERS, STARK_MAX_CONSTRAINTS = 3, 16
+STARK_MAX_REGISTERS, STARK_MAX_CONSTRAINTS = _C["MZK_STARK_MAX_REGISTERS"], _C["MZK_STARK_MAX_CONSTRAINTS"]
 
 
 class StarkDims(ctypes.Structure):
-    """mzk_stark_dims (include/mzk.h)"""
-    _scalars = ("num_randomizers", "randomized_trace_length", "omicron_domain_length", "fri_domain_length", "num_registers", "n_vars",
-                "n_constraints", "max_degree", "randomizer_length", "n_weights", "fri_num_rounds", "fri_last_length", "num_indices")
-    _per_constraint = ("transition_degree_bounds", "transition_quotient_degree_bounds", "transition_shifts")
-    _per_register = ("boundary_counts", "boundary_quotient_degree_bounds", "boundary_shifts")
-    _fields_ = ([(k, ctypes.c_uint64) for k in _scalars] + [(k, ctypes.c_uint64 * STARK_MAX_CONSTRAINTS) for k in _per_constraint] +
-                [(k, ctypes.c_uint64 * STARK_MAX_REGISTERS) for k in _per_register])
+    """mzk_stark_dims (include/mzk.h): scalars, then arrays per transition constraint and per register"""
+    _fields_ = _struct_fields("mzk_stark_dims")
+    _scalars = tuple(f for f, t in _fields_ if t is ctypes.c_uint64)
+    _per_constraint = tuple(f for f, t in _fields_ if f.startswith("transition_"))
+    _per_register = tuple(f for f, t in _fields_ if f.startswith("boundary_"))
 
 
 def stark_plan(fid, expansion_factor, num_colinearity_checks, num_registers, num_cycles, transition_constraints_degree, constraints, boundary):
@@ -1369,17 +1336,15 @@ def stark_plan(fid, expansion_factor, num_colinearity_checks, num_registers, num
     bc = (ctypes.c_size_t * max(nb, 1))(*[int(b[0]) for b in boundary])
     br = (ctypes.c_size_t * max(nb, 1))(*[int(b[1]) for b in boundary])
     d = StarkDims()
-    sz = ctypes.c_size_t
-    _check(lib().mzk_stark_plan(int(fid), sz(expansion_factor), sz(num_colinearity_checks), sz(num_registers), sz(num_cycles),
-                                sz(transition_constraints_degree), _p(te), toff, sz(len(constraints)), bc, br, sz(nb), ctypes.byref(d)))
+    _check(lib().mzk_stark_plan(int(fid), expansion_factor, num_colinearity_checks, num_registers, num_cycles, transition_constraints_degree, _p(te), toff,
+                                len(constraints), bc, br, nb, ctypes.byref(d)))
     out = {k: int(getattr(d, k)) for k in StarkDims._scalars}
     out.update({k: [int(v) for v in getattr(d, k)][:len(constraints)] for k in StarkDims._per_constraint})
     out.update({k: [int(v) for v in getattr(d, k)][:int(num_registers)] for k in StarkDims._per_register})
     return out
 
 
-STARK_SECTIONS = ("status", "fri", "indices", "bqc_roots", "rdc_root", "bqc_points", "rdc_points", "tzc_points", "bqc_paths", "rdc_paths",
-                  "tzc_paths", "path_lens")
+STARK_SECTIONS = _abi.index_names("MZK_STARK_SECTIONS")
 
 
 def _stark_dims_struct(dims):
@@ -1438,9 +1403,7 @@ class Stark:
         self.fid, self.constraints = int(fid), constraints
         self.params = (int(expansion_factor), int(num_colinearity_checks), int(num_registers), int(num_cycles), int(transition_constraints_degree))
         tc, te, toff = mpoly_term_table(fid, constraints, 1 + 2 * int(num_registers))
-        sz = ctypes.c_size_t
-        _check(lib().mzk_stark_new(self.fid, *[sz(v) for v in self.params], _p(_one(fid, generator)), _p(tc), _p(te), toff, sz(len(constraints)),
-                                   ctypes.byref(self._h)))
+        _check(lib().mzk_stark_new(self.fid, *self.params, _p(_one(fid, generator)), _p(tc), _p(te), toff, len(constraints), ctypes.byref(self._h)))
 
     def dims(self, boundary):
         """the sizes of a proof for this boundary (stark_plan)"""
@@ -1457,7 +1420,7 @@ class Stark:
         bc = (sz * max(nb, 1))(*[int(b[0]) for b in boundary])
         br = (sz * max(nb, 1))(*[int(b[1]) for b in boundary])
         bv = to_limbs([int(b[2]) for b in boundary], LIMBS[self.fid]) if nb else np.zeros((1, LIMBS[self.fid]), dtype=np.uint64)
-        return bc, br, bv, sz(nb)
+        return bc, br, bv, nb
 
     def prove_raw(self, trace, boundary, randomizer):
         """mzk_stark_prove: trace (rows x registers x limbs, the random rows appended), randomizer (max_degree + 1 coefficients) -> packed bytes"""
@@ -1467,7 +1430,7 @@ class Stark:
         r = _arr(self.fid, randomizer)
         bc, br, bv, nb = self._boundary(boundary)
         buf = (ctypes.c_uint8 * total)()
-        _check(lib().mzk_stark_prove(self._h, _p(t), ctypes.c_size_t(t.shape[0]), bc, br, _p(bv), nb, _p(r), buf, ctypes.c_size_t(total)))
+        _check(lib().mzk_stark_prove(self._h, _p(t), t.shape[0], bc, br, _p(bv), nb, _p(r), buf, total))
         return bytes(buf)
 
     def prove(self, trace, boundary, randomizer):
@@ -1476,8 +1439,7 @@ class Stark:
     def prove_dev(self, d_trace_ptr, n_rows, boundary, d_randomizer_ptr, d_proof_ptr, proof_cap, stream=0):
         """mzk_stark_prove_dev: raw device pointers; returns when the proof at d_proof_ptr is complete"""
         bc, br, bv, nb = self._boundary(boundary)
-        _check(lib().mzk_stark_prove_dev(self._h, ctypes.c_void_p(d_trace_ptr), ctypes.c_size_t(n_rows), bc, br, _p(bv), nb, ctypes.c_void_p(d_randomizer_ptr),
-                                         ctypes.c_void_p(d_proof_ptr), ctypes.c_size_t(proof_cap), ctypes.c_void_p(stream)))
+        _check(lib().mzk_stark_prove_dev(self._h, d_trace_ptr, n_rows, bc, br, _p(bv), nb, d_randomizer_ptr, d_proof_ptr, proof_cap, stream))
 
     def close(self):
         if self._h:
@@ -1521,7 +1483,7 @@ def msm_g2(scalars, points):
     if p.shape[0] < s.shape[0]:
         raise MzkError(-5, "index out of bounds: powers.len() < coef.len() (polynomial.rs:162)")
     out = np.zeros(16, dtype=np.uint64)
-    _check(lib().mzk_msm_g2_bn254(_p(s), _p(p), ctypes.c_size_t(s.shape[0]), _p(out)))
+    _check(lib().mzk_msm_g2_bn254(_p(s), _p(p), s.shape[0], _p(out)))
     return array_to_g2_points(out)[0]
 
 
@@ -1530,16 +1492,12 @@ def kzg_setup_g2(alpha, max_d, g2):
     a = to_limbs([alpha], 4)
     g = g2_points_to_array([g2])
     out = np.zeros((max_d + 1, 16), dtype=np.uint64)
-    _check(lib().mzk_kzg_setup_g2(_p(a), _p(g), ctypes.c_size_t(max_d), _p(out)))
+    _check(lib().mzk_kzg_setup_g2(_p(a), _p(g), max_d, _p(out)))
     return out
 
 
 # ---- Reed-Solomon over GF(2^8) (algebra/reedsolomon.rs): symbols are bytes, arrays numpy uint8 ---------------------------------------
 RS_NONE = 255      # the status of a word the reference's decoder returns None for
-
-
-def _sz(v):
-    return ctypes.c_size_t(int(v))
 
 
 def _bytes2d(a, width, what):
@@ -1554,7 +1512,7 @@ def _bytes2d(a, width, what):
 def rs_generator_poly(n, k):
     """generator_polynomial (reedsolomon.rs:34-37): n - k + 1 coefficients from the constant term up.  Host arithmetic: no GPU needed."""
     g = np.zeros(max(int(n) - int(k), 0) + 1, dtype=np.uint8)
-    _check(lib().mzk_rs_generator_poly(_sz(n), _sz(k), _p(g)))
+    _check(lib().mzk_rs_generator_poly(int(n), int(k), _p(g)))
     return g
 
 
@@ -1563,33 +1521,32 @@ def rs_encode(n, k, messages):
     vector is this one without its trailing zeros)."""
     m = _bytes2d(messages, k, "rs_encode")
     out = np.empty((m.shape[0], n), dtype=np.uint8)
-    _check(lib().mzk_rs_encode(_sz(n), _sz(k), _p(m), _sz(m.shape[0]), _p(out)))
+    _check(lib().mzk_rs_encode(int(n), int(k), _p(m), m.shape[0], _p(out)))
     return out
 
 
 def rs_encode_dev(n, k, d_messages, batch, d_codewords, d_columns_fr=None, stream=None):
     """mzk_rs_encode_dev: device pointers (ints); d_columns_fr (optional): n x batch Fr elements, symbol-major.  Only enqueues."""
-    _check(lib().mzk_rs_encode_dev(_sz(n), _sz(k), ctypes.c_void_p(int(d_messages)), _sz(batch), ctypes.c_void_p(int(d_codewords)),
-                                   ctypes.c_void_p(int(d_columns_fr)) if d_columns_fr else None, ctypes.c_void_p(stream)))
+    _check(lib().mzk_rs_encode_dev(int(n), int(k), int(d_messages), int(batch), int(d_codewords), int(d_columns_fr) if d_columns_fr else None, stream))
 
 
 def rs_encode_view_dev(n, k, d_messages, msg_symbol_stride, msg_stride, batch, d_codewords, cw_symbol_stride, cw_stride, d_columns_fr=None, stream=None):
     """mzk_rs_encode_view_dev: symbol s of item b at base + b * stride + s * symbol_stride on both sides.  Only enqueues."""
-    _check(lib().mzk_rs_encode_view_dev(_sz(n), _sz(k), ctypes.c_void_p(int(d_messages)), _sz(msg_symbol_stride), _sz(msg_stride), _sz(batch),
-                                        ctypes.c_void_p(int(d_codewords)), _sz(cw_symbol_stride), _sz(cw_stride),
-                                        ctypes.c_void_p(int(d_columns_fr)) if d_columns_fr else None, ctypes.c_void_p(stream)))
+    _check(lib().mzk_rs_encode_view_dev(int(n), int(k), int(d_messages), int(msg_symbol_stride), int(msg_stride), int(batch),
+                                        int(d_codewords), int(cw_symbol_stride), int(cw_stride),
+                                        int(d_columns_fr) if d_columns_fr else None, stream))
 
 
 def rs_syndromes(n, k, words):
     """compute_syndromes (reedsolomon.rs:90-102) of every row of `words` (batch x n bytes): batch x (n - k) bytes."""
     w = _bytes2d(words, n, "rs_syndromes")
     out = np.zeros((w.shape[0], n - k), dtype=np.uint8)
-    _check(lib().mzk_rs_syndromes(_sz(n), _sz(k), _p(w), _sz(w.shape[0]), _p(out)))
+    _check(lib().mzk_rs_syndromes(int(n), int(k), _p(w), w.shape[0], _p(out)))
     return out
 
 
 def rs_syndromes_dev(n, k, d_words, batch, d_syndromes, stream=None):
-    _check(lib().mzk_rs_syndromes_dev(_sz(n), _sz(k), ctypes.c_void_p(int(d_words)), _sz(batch), ctypes.c_void_p(int(d_syndromes)), ctypes.c_void_p(stream)))
+    _check(lib().mzk_rs_syndromes_dev(int(n), int(k), int(d_words), int(batch), int(d_syndromes), stream))
 
 
 def rs_decode(n, k, received, with_corrected=False):
@@ -1601,27 +1558,26 @@ def rs_decode(n, k, received, with_corrected=False):
     msgs = np.empty((batch, k), dtype=np.uint8)
     status = np.empty(batch, dtype=np.uint8)
     corr = np.empty((batch, n), dtype=np.uint8) if with_corrected else None
-    _check(lib().mzk_rs_decode(_sz(n), _sz(k), _p(r), _sz(batch), _p(corr) if with_corrected else None, _p(msgs), _p(status)))
+    _check(lib().mzk_rs_decode(int(n), int(k), _p(r), batch, _p(corr) if with_corrected else None, _p(msgs), _p(status)))
     return (corr, msgs, status) if with_corrected else (msgs, status)
 
 
 def rs_decode_dev(n, k, d_received, batch, d_corrected, d_messages, d_status, stream=None):
     """mzk_rs_decode_dev: device pointers (ints); d_corrected or d_messages may be None.  Only enqueues."""
-    opt = lambda p: ctypes.c_void_p(int(p)) if p else None
-    _check(lib().mzk_rs_decode_dev(_sz(n), _sz(k), ctypes.c_void_p(int(d_received)), _sz(batch), opt(d_corrected), opt(d_messages),
-                                   ctypes.c_void_p(int(d_status)), ctypes.c_void_p(stream)))
+    opt = lambda p: int(p) if p else None
+    _check(lib().mzk_rs_decode_dev(int(n), int(k), int(d_received), int(batch), opt(d_corrected), opt(d_messages), int(d_status), stream))
 
 
 def rs2d_encode(col_n, row_n, data):
     """ReedSolomon2D::encode (reedsolomon.rs:274-295) of `data` (message_len bytes): col_n x row_n bytes."""
     d = np.ascontiguousarray(data, dtype=np.uint8).reshape(-1)
     out = np.empty((col_n, row_n), dtype=np.uint8)
-    _check(lib().mzk_rs2d_encode(_sz(col_n), _sz(row_n), _p(d), _sz(d.shape[0]), _p(out)))
+    _check(lib().mzk_rs2d_encode(int(col_n), int(row_n), _p(d), d.shape[0], _p(out)))
     return out
 
 
 def rs2d_encode_dev(col_n, row_n, d_data, message_len, d_code, stream=None):
-    _check(lib().mzk_rs2d_encode_dev(_sz(col_n), _sz(row_n), ctypes.c_void_p(int(d_data)), _sz(message_len), ctypes.c_void_p(int(d_code)), ctypes.c_void_p(stream)))
+    _check(lib().mzk_rs2d_encode_dev(int(col_n), int(row_n), int(d_data), int(message_len), int(d_code), stream))
 
 
 def rs2d_decode(col_n, row_n, code, message_len, with_status=False):
@@ -1636,31 +1592,29 @@ def rs2d_decode(col_n, row_n, code, message_len, with_status=False):
     data = np.empty(message_len, dtype=np.uint8)
     ok = ctypes.c_int(0)
     cs, rs = np.empty(row_n, dtype=np.uint8), np.empty(size, dtype=np.uint8)
-    _check(lib().mzk_rs2d_decode(_sz(col_n), _sz(row_n), _p(c), _sz(message_len), _p(data), ctypes.byref(ok), _p(cs), _p(rs)))
+    _check(lib().mzk_rs2d_decode(int(col_n), int(row_n), _p(c), int(message_len), _p(data), ctypes.byref(ok), _p(cs), _p(rs)))
     res = data if ok.value else None
     return (res, cs, rs) if with_status else res
 
 
 def rs2d_decode_dev(col_n, row_n, d_code, message_len, d_data, d_ok, d_col_status=None, d_row_status=None, stream=None):
-    opt = lambda p: ctypes.c_void_p(int(p)) if p else None
-    _check(lib().mzk_rs2d_decode_dev(_sz(col_n), _sz(row_n), ctypes.c_void_p(int(d_code)), _sz(message_len), ctypes.c_void_p(int(d_data)),
-                                     ctypes.c_void_p(int(d_ok)), opt(d_col_status), opt(d_row_status), ctypes.c_void_p(stream)))
+    opt = lambda p: int(p) if p else None
+    _check(lib().mzk_rs2d_decode_dev(int(col_n), int(row_n), int(d_code), int(message_len), int(d_data), int(d_ok), opt(d_col_status), opt(d_row_status), stream))
 
 
 # ---- Celestia's commitment (das/celestia.rs over algebra/merkle.rs): squares are numpy uint8, roots 32 bytes ---------------------------
-DAS_PATH_MAX = 8           # entries a path can have: floor(log2 255) + 1
+DAS_PATH_MAX = _C["MZK_DAS_PATH_MAX"]      # entries a path can have: floor(log2 255) + 1
 DAS_OUT_OF_RANGE = 255     # depths[s] of a position outside the grid (open_dev)
 
 
-DAS_PLAN_FIELDS = ("rows", "cols", "squares", "row_items", "row_depth", "col_items", "col_depth", "root_items", "root_depth", "row_trees_per_wg", "col_trees_per_wg",
-                   "row_wgs", "col_wgs", "tree_grid", "tree_iters", "tree_block", "tree_lds", "root_grid", "root_iters", "root_block", "root_lds", "node_bytes", "path_max")
+DAS_PLAN_FIELDS = _abi.index_names("MZK_DAS_PLAN_WORDS")
 
 
 def das_plan(rows, cols, squares=1):
     """What the commitment of `squares` squares of rows x cols symbols launches, as a dict keyed after the MZK_DAS_PLAN_* constants
     (mzk_das_plan_get).  Host only: no GPU needed."""
     p = np.zeros(len(DAS_PLAN_FIELDS), dtype=np.uint64)
-    _check(lib().mzk_das_plan_get(_sz(rows), _sz(cols), _sz(squares), _p(p)))
+    _check(lib().mzk_das_plan_get(int(rows), int(cols), int(squares), _p(p)))
     return {n: int(v) for n, v in zip(DAS_PLAN_FIELDS, p)}
 
 
@@ -1679,15 +1633,15 @@ def das_commit(code):
     a = _squares3d(code, "das_commit")
     q, r, c = a.shape
     rr, cr, dr = np.empty((q, r, 32), dtype=np.uint8), np.empty((q, c, 32), dtype=np.uint8), np.empty((q, 32), dtype=np.uint8)
-    _check(lib().mzk_das_commit(_p(a), _sz(r), _sz(c), _sz(q), _p(rr), _p(cr), _p(dr)))
+    _check(lib().mzk_das_commit(_p(a), r, c, q, _p(rr), _p(cr), _p(dr)))
     return rr, cr, dr
 
 
 def das_commit_dev(d_code, rows, cols, row_stride, square_stride, squares, d_row_roots, d_col_roots, d_data_roots, stream=None):
     """mzk_das_commit_dev: device pointers (ints); d_row_roots / d_col_roots may be None.  Only enqueues."""
-    opt = lambda p: ctypes.c_void_p(int(p)) if p else None
-    _check(lib().mzk_das_commit_dev(ctypes.c_void_p(int(d_code)), _sz(rows), _sz(cols), _sz(row_stride), _sz(square_stride), _sz(squares), opt(d_row_roots),
-                                    opt(d_col_roots), ctypes.c_void_p(int(d_data_roots)), ctypes.c_void_p(stream)))
+    opt = lambda p: int(p) if p else None
+    _check(lib().mzk_das_commit_dev(int(d_code), int(rows), int(cols), int(row_stride), int(square_stride), int(squares), opt(d_row_roots),
+                                    opt(d_col_roots), int(d_data_roots), stream))
 
 
 class DasGrid:
@@ -1700,14 +1654,13 @@ class DasGrid:
             return
         a = _squares3d(code, "DasGrid")
         h = ctypes.c_void_p()
-        _check(lib().mzk_das_grid_build(_p(a), _sz(a.shape[1]), _sz(a.shape[2]), _sz(a.shape[0]), ctypes.byref(h)))
+        _check(lib().mzk_das_grid_build(_p(a), a.shape[1], a.shape[2], a.shape[0], ctypes.byref(h)))
         self._h, self.shape = h, a.shape
 
     @classmethod
     def from_device(cls, d_code, rows, cols, row_stride, square_stride, squares, stream=None):
         h = ctypes.c_void_p()
-        _check(lib().mzk_das_grid_build_dev(ctypes.c_void_p(int(d_code)), _sz(rows), _sz(cols), _sz(row_stride), _sz(square_stride), _sz(squares), ctypes.byref(h),
-                                            ctypes.c_void_p(stream)))
+        _check(lib().mzk_das_grid_build_dev(int(d_code), int(rows), int(cols), int(row_stride), int(square_stride), int(squares), ctypes.byref(h), stream))
         return cls(_handle=h, _shape=(int(squares), int(rows), int(cols)))
 
     def roots(self):
@@ -1724,13 +1677,12 @@ class DasGrid:
         n = pos.shape[0]
         paths, lens = np.zeros((n, DAS_PATH_MAX, 32), dtype=np.uint8), np.zeros((n, DAS_PATH_MAX), dtype=np.uint8)
         depths, leaves = np.zeros(n, dtype=np.uint8), np.zeros(n, dtype=np.uint8)
-        _check(lib().mzk_das_grid_open(self._h, _p(pos), _sz(n), _p(paths), _p(lens), _p(depths), _p(leaves)))
+        _check(lib().mzk_das_grid_open(self._h, _p(pos), n, _p(paths), _p(lens), _p(depths), _p(leaves)))
         return paths, lens, depths, leaves
 
     def open_dev(self, d_positions, count, d_paths, d_entry_lens, d_depths, d_leaves, stream=None):
         """mzk_das_grid_open_dev: device pointers (ints).  Only enqueues, behind the build."""
-        _check(lib().mzk_das_grid_open_dev(self._h, ctypes.c_void_p(int(d_positions)), _sz(count), ctypes.c_void_p(int(d_paths)), ctypes.c_void_p(int(d_entry_lens)),
-                                           ctypes.c_void_p(int(d_depths)), ctypes.c_void_p(int(d_leaves)), ctypes.c_void_p(stream)))
+        _check(lib().mzk_das_grid_open_dev(self._h, int(d_positions), int(count), int(d_paths), int(d_entry_lens), int(d_depths), int(d_leaves), stream))
 
     def close(self):
         if self._h:
@@ -1745,11 +1697,8 @@ class DasGrid:
 
 
 # ---- Rescue-Prime (zkstark/rescueprime.rs): batched hashes, chains and traces, one chain per lane ----------------------------------------
-RESCUE_MAX_M, RESCUE_MAX_ROUNDS = 4, 64
-RESCUE_PLAN_FIELDS = ("field", "m", "rounds", "batch",
-                      "alpha_window", "alpha_slots", "alpha_steps", "alpha_squarings", "alpha_multiplies", "alpha_table", "alpha_products", "alpha_binary",
-                      "alphainv_window", "alphainv_slots", "alphainv_steps", "alphainv_squarings", "alphainv_multiplies", "alphainv_table", "alphainv_products",
-                      "alphainv_binary", "products_per_hash", "rows", "min_stride", "block", "wgs", "grid", "iters", "grid_cap", "const_bytes")
+RESCUE_MAX_M, RESCUE_MAX_ROUNDS = _C["MZK_RESCUE_MAX_M"], _C["MZK_RESCUE_MAX_ROUNDS"]
+RESCUE_PLAN_FIELDS = _abi.index_names("MZK_RESCUE_PLAN_WORDS")
 
 
 def _exp4(e):
@@ -1763,7 +1712,7 @@ def rescue_plan(fid, m, n, alpha, alphainv, batch=0):
     """What a handle of these parameters runs for `batch` chains, as a dict keyed after the MZK_RESCUE_PLAN_* constants
     (mzk_rescue_plan_get).  Host only: no GPU needed."""
     p = np.zeros(len(RESCUE_PLAN_FIELDS), dtype=np.uint64)
-    _check(lib().mzk_rescue_plan_get(int(fid), _sz(m), _sz(n), ctypes.c_uint64(int(alpha)), _p(_exp4(alphainv)), _sz(batch), _p(p)))
+    _check(lib().mzk_rescue_plan_get(int(fid), int(m), int(n), int(alpha), _p(_exp4(alphainv)), int(batch), _p(p)))
     return {k: int(v) for k, v in zip(RESCUE_PLAN_FIELDS, p)}
 
 
@@ -1776,7 +1725,7 @@ class RescuePrime:
         self.rows = self.n + 1
         flat = [int(v) for row in mds for v in (row if isinstance(row, (list, tuple)) else [row])]
         self._h = ctypes.c_void_p()
-        _check(lib().mzk_rescue_new(self.fid, _sz(m), _sz(n), ctypes.c_uint64(self.alpha), _p(_exp4(alphainv)), _p(to_limbs(flat, LIMBS[self.fid])),
+        _check(lib().mzk_rescue_new(self.fid, int(m), int(n), self.alpha, _p(_exp4(alphainv)), _p(to_limbs(flat, LIMBS[self.fid])),
                                     _p(to_limbs([int(v) for v in round_constants], LIMBS[self.fid])), ctypes.byref(self._h)))
 
     def _inputs(self, inputs):
@@ -1788,7 +1737,7 @@ class RescuePrime:
         """outputs (batch * links x limbs): row b * links + l is the output of link l of the chain from inputs[b]"""
         x = self._inputs(inputs)
         out = np.zeros((x.shape[0] * int(links), LIMBS[self.fid]), dtype=np.uint64)
-        _check(lib().mzk_rescue_hash(self._h, _p(x), _sz(x.shape[0]), _sz(links), _p(out)))
+        _check(lib().mzk_rescue_hash(self._h, _p(x), x.shape[0], int(links), _p(out)))
         return out
 
     def trace(self, inputs, links=1, trace_stride=None, traces=None, with_outputs=True):
@@ -1801,15 +1750,15 @@ class RescuePrime:
             traces = np.zeros((slots, stride, LIMBS[self.fid]), dtype=np.uint64)
         assert traces.dtype == np.uint64 and traces.flags["C_CONTIGUOUS"] and traces.size >= slots * stride * LIMBS[self.fid]
         out = np.zeros((slots, LIMBS[self.fid]), dtype=np.uint64) if with_outputs else None
-        _check(lib().mzk_rescue_trace(self._h, _p(x), _sz(x.shape[0]), _sz(links), _p(traces), _sz(stride), _p(out) if with_outputs else None))
+        _check(lib().mzk_rescue_trace(self._h, _p(x), x.shape[0], int(links), _p(traces), int(stride), _p(out) if with_outputs else None))
         return traces, out
 
     def hash_dev(self, d_inputs, batch, links, d_outputs, stream=None):
-        _check(lib().mzk_rescue_hash_dev(self._h, ctypes.c_void_p(int(d_inputs)), _sz(batch), _sz(links), ctypes.c_void_p(int(d_outputs)), ctypes.c_void_p(stream)))
+        _check(lib().mzk_rescue_hash_dev(self._h, int(d_inputs), int(batch), int(links), int(d_outputs), stream))
 
     def trace_dev(self, d_inputs, batch, links, d_traces, trace_stride, d_outputs=None, stream=None):
-        _check(lib().mzk_rescue_trace_dev(self._h, ctypes.c_void_p(int(d_inputs)), _sz(batch), _sz(links), ctypes.c_void_p(int(d_traces)), _sz(trace_stride),
-                                          ctypes.c_void_p(int(d_outputs)) if d_outputs else None, ctypes.c_void_p(stream)))
+        _check(lib().mzk_rescue_trace_dev(self._h, int(d_inputs), int(batch), int(links), int(d_traces), int(trace_stride),
+                                          int(d_outputs) if d_outputs else None, stream))
 
     def close(self):
         if self._h:

@@ -99,13 +99,12 @@ class DeviceOpenOps:
         y = torch.zeros(4, dtype=torch.int64, device=coef.device)
         n = coef.numel() // 4
         q[-4:] = 0
-        self._ok(self.L.mzk_kzg_open_quotient_dev(self.ct.c_void_p(coef.data_ptr()), self.ct.c_size_t(n), ul.ctypes.data_as(self.ct.c_void_p),
-                                                  self.ct.c_void_p(y.data_ptr()), self.ct.c_void_p(q.data_ptr()), self._st()))
+        self._ok(self.L.mzk_kzg_open_quotient_dev(coef.data_ptr(), n, ul.ctypes.data_as(self.ct.c_void_p), y.data_ptr(), q.data_ptr(), self._st()))
         self._join()
         return self.mz.from_limbs(y.cpu().numpy().view(np.uint64).reshape(1, 4))[0], q
 
     def _st(self):
-        return self.ct.c_void_p(self.stream if self.stream is not None else torch.cuda.current_stream().cuda_stream)
+        return self.stream if self.stream is not None else torch.cuda.current_stream().cuda_stream
 
     def _join(self):
         if self.stream is not None:
@@ -118,8 +117,7 @@ class DeviceOpenOps:
     def slice_value(self, coef, u):
         ul = self.mz.to_limbs([u], 4)
         out = torch.zeros(4, dtype=torch.int64, device=coef.device)
-        self._ok(self.L.mzk_kzg_open_slice_value_dev(self.ct.c_void_p(coef.data_ptr()), self.ct.c_size_t(coef.numel() // 4), ul.ctypes.data_as(self.ct.c_void_p),
-                                                     self.ct.c_void_p(out.data_ptr()), self._st()))
+        self._ok(self.L.mzk_kzg_open_slice_value_dev(coef.data_ptr(), coef.numel() // 4, ul.ctypes.data_as(self.ct.c_void_p), out.data_ptr(), self._st()))
         self._join()
         return out                       # stays on the device: the gather takes it from there
 
@@ -131,8 +129,8 @@ class DeviceOpenOps:
     def slice_quotient(self, coef, u, carry):
         ul, cl = self.mz.to_limbs([u], 4), self.mz.to_limbs([carry], 4)
         q = self._q(coef)
-        self._ok(self.L.mzk_kzg_open_slice_quotient_dev(self.ct.c_void_p(coef.data_ptr()), self.ct.c_size_t(coef.numel() // 4), ul.ctypes.data_as(self.ct.c_void_p),
-                                                        cl.ctypes.data_as(self.ct.c_void_p), self.ct.c_void_p(q.data_ptr()), self._st()))
+        self._ok(self.L.mzk_kzg_open_slice_quotient_dev(coef.data_ptr(), coef.numel() // 4, ul.ctypes.data_as(self.ct.c_void_p),
+                                                        cl.ctypes.data_as(self.ct.c_void_p), q.data_ptr(), self._st()))
         return q
 
 
@@ -217,7 +215,7 @@ class DeviceOps:
         self.ct, self.mz, self.fid, self.nl, self.L = ctypes, mz, fid, mz.LIMBS[fid], mz.lib()
 
     def _st(self):
-        return self.ct.c_void_p(torch.cuda.current_stream().cuda_stream)
+        return torch.cuda.current_stream().cuda_stream
 
     def _one(self, v):
         a = self.mz.to_limbs([v], self.nl)
@@ -230,14 +228,13 @@ class DeviceOps:
     def ntt(self, b, m, root, inverse):        # out of place: the caller's part is never overwritten
         keep, r = self._one(root)
         out = torch.empty_like(b)
-        self._ok(self.L.mzk_ntt_dev(self.fid, r, self.ct.c_void_p(b.data_ptr()), self.ct.c_void_p(out.data_ptr()), self.ct.c_size_t(m),
-                                    int(bool(inverse)), self._st()))
+        self._ok(self.L.mzk_ntt_dev(self.fid, r, b.data_ptr(), out.data_ptr(), m, int(bool(inverse)), self._st()))
         return out
 
     def ntt_rows(self, b, rows, n, root, inverse):
         keep, r = self._one(root)
-        p = self.ct.c_void_p(b.data_ptr())
-        self._ok(self.L.mzk_ntt_batch_dev(self.fid, r, p, p, self.ct.c_size_t(n), self.ct.c_size_t(rows), int(bool(inverse)), self._st()))
+        p = b.data_ptr()
+        self._ok(self.L.mzk_ntt_batch_dev(self.fid, r, p, p, n, rows, int(bool(inverse)), self._st()))
         return b
 
     def ntt_columns(self, b, W, cols, root, inverse):
@@ -245,22 +242,20 @@ class DeviceOps:
             return None                      # the schedule falls back to transpose + row transforms + transpose
         keep, r = self._one(root)
         out = torch.empty_like(b)
-        self._ok(self.L.mzk_ntt_columns_dev(self.fid, r, self.ct.c_void_p(b.data_ptr()), self.ct.c_void_p(out.data_ptr()), self.ct.c_size_t(W),
-                                            self.ct.c_size_t(cols), int(bool(inverse)), self._st()))
+        self._ok(self.L.mzk_ntt_columns_dev(self.fid, r, b.data_ptr(), out.data_ptr(), W, cols, int(bool(inverse)), self._st()))
         return out
 
     def lde(self, b, m, offset, generator):
         k1, o = self._one(offset)
         k2, g = self._one(generator)
         out = torch.empty_like(b)
-        self._ok(self.L.mzk_coset_lde_dev(self.fid, self.ct.c_void_p(b.data_ptr()), self.ct.c_size_t(m), o, g, self.ct.c_void_p(out.data_ptr()),
-                                          self.ct.c_size_t(m), self._st()))
+        self._ok(self.L.mzk_coset_lde_dev(self.fid, b.data_ptr(), m, o, g, out.data_ptr(), m, self._st()))
         return out
 
     def scale(self, b, m, ratio):
         keep, r = self._one(ratio)
-        p = self.ct.c_void_p(b.data_ptr())
-        self._ok(self.L.mzk_poly_scale_dev(self.fid, p, self.ct.c_size_t(m), r, None, p, self._st()))
+        p = b.data_ptr()
+        self._ok(self.L.mzk_poly_scale_dev(self.fid, p, m, r, None, p, self._st()))
         return b
 
     def transpose(self, b, rows, cols):

@@ -189,7 +189,6 @@ def test_table_budget_degrades_the_layout_not_the_result(env):
     (mzk_set_table_budget, or a refused hipMalloc) degrades -- every 2nd table with two bucket sets, every 4th with four, the
     prepared points alone -- and every commitment, opening and saved/loaded handle stays bit-identical to the oracle's."""
     torch, mz, L, dev, st = env
-    L.mzk_srs_table_bytes.restype = ctypes.c_size_t
     n = (1 << 16) + 37
     p = orc.synth_points(601, n)
     p[11] = 0
@@ -248,7 +247,6 @@ def test_workspace_gives_itself_back(env):
     (oracle Pippenger on the same pairs); with the budget in force a later call of another kind trims what the MSM left instead of
     stacking on top of it; mzk_trim_workspace gives everything back and the next calls rebuild what they need."""
     torch, mz, L, dev, st = env
-    L.mzk_srs_table_bytes.restype = ctypes.c_size_t
     big, n = 1 << 24, 1 << 20
     try:
         pts = torch.empty(big * 8, dtype=torch.int64, device=dev)
@@ -321,8 +319,6 @@ def test_many_commit_wide_tables_respect_the_table_budget(env):
     mzk_set_table_budget like the handle's own tables; a refusal is remembered on the handle, leaves no error message behind on a call
     that succeeds, and the commitments are the same points (das/eigenda.rs:92-101 -> kzg.rs:57-59)."""
     torch, mz, L, dev, st = env
-    L.mzk_srs_table_bytes.restype = ctypes.c_size_t
-    L.mzk_last_error.restype = ctypes.c_char_p
     nn, count = 1 << 13, 4
     pt = torch.empty(nn * 8, dtype=torch.int64, device=dev)
     cf = torch.empty(count * nn * 4, dtype=torch.int64, device=dev)

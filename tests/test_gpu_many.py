@@ -100,7 +100,6 @@ def test_many_commits_equal_oracle_and_single_calls(mz, n, count, width):
         # the wide tables are the handle's (built once, counted by mzk_srs_table_bytes, used again by the next call; a SHORTER batch
         # against the same handle keeps to its own tables and a longer prefix than 2^13 takes the wide ones): same points either way
         L = mz.lib()
-        L.mzk_srs_table_bytes.restype = ctypes.c_size_t
         assert L.mzk_srs_table_bytes(h) == (26 + 22) * n * 64
         assert _commit_many(mz, h, coefs) == got
         flat = coefs.reshape(-1, 4)                  # a batch of SHORTER polynomials out of the same buffer: polynomial k = the k-th run of m coefficients

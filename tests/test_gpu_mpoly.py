@@ -20,7 +20,6 @@ E_ARG, E_LENGTH, E_RANGE = -1, -5, -6
 def mz():
     import myzkp_amd as mz
     mz.init(0)
-    mz.lib().mzk_ctx_stream.restype = ctypes.c_void_p
     return mz
 
 

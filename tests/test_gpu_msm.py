@@ -261,7 +261,6 @@ def test_host_buffer_calls_in_pieces_equal_the_resident_calls(mz, n):
     import ctypes
     import torch
     L, dev = mz.lib(), torch.device("cuda", 0)
-    L.mzk_last_error.restype = ctypes.c_char_p
     st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
     sc = torch.empty(n * 4, dtype=torch.int64, device=dev)
     pt = torch.empty(n * 8, dtype=torch.int64, device=dev)
@@ -298,7 +297,6 @@ def test_host_commit_on_narrow_tables_at_the_piece_threshold(mz, with_tables):
     import torch
     n = 1 << 18
     L, dev = mz.lib(), torch.device("cuda", 0)
-    L.mzk_last_error.restype = ctypes.c_char_p
     st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
     sc = torch.empty(n * 4, dtype=torch.int64, device=dev)
     pt = torch.empty(n * 8, dtype=torch.int64, device=dev)

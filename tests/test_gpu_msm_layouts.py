@@ -76,7 +76,6 @@ def phase_pairs(L, call):
 def test_commit_through_the_layout_at_every_prefix(mz, plan, data, c, sets):
     import torch
     L = mz.lib()
-    L.mzk_srs_table_bytes.restype = ctypes.c_size_t
     d_p, d_s, want = data
     st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
     ok = lambda rc: rc == 0 or pytest.fail(L.mzk_last_error().decode())

@@ -119,7 +119,6 @@ def test_dumps_and_loads_under_a_table_budget(mz, tmp_path):
     full tables loaded under a budget they do not fit degrades instead of failing -- commitments bit-identical all the way."""
     import ctypes
     L = mz.lib()
-    L.mzk_srs_table_bytes.restype = ctypes.c_size_t
     n = (1 << 15) + 5
     p = orc.synth_points(77, n)
     s = orc.synth_vector(FR, 78, n)

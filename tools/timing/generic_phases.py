@@ -4,7 +4,6 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspa
 import torch
 import myzkp_amd as mz
 mz.init(0); L = mz.lib()
-L.mzk_prof_name.restype = ctypes.c_char_p
 dev = torch.device("cuda", 0)
 st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
 for lg in ([int(a) for a in sys.argv[1:]] or [20]):

@@ -45,7 +45,6 @@ def run_el(el):
     mz.init(0)
     L = mz.lib()
     hip = hip_runtime()
-    L.mzk_prof_name.restype = ctypes.c_char_p
     PH_HYPERCUBE = next(ph for ph in range(64) if L.mzk_prof_name(ph) == b"hypercube_tables")       # by name: the enum may grow
     SZ, VP = ctypes.c_size_t, ctypes.c_void_p
     stream = torch.cuda.current_stream()

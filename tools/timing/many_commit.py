@@ -12,7 +12,6 @@ dev = torch.device("cuda", 0)
 st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
 PH = {}
 for i in range(32):
-    L.mzk_prof_name.restype = ctypes.c_char_p
     nm = L.mzk_prof_name(i)
     if nm: PH[i] = nm.decode()
 shapes = sys.argv[1] if len(sys.argv) > 1 else "10:256,12:64,8:1024,14:16,10:256:8,10:256:11"
@@ -30,7 +29,6 @@ for spec in shapes.split(','):
     assert L.mzk_srs_from_device_ex(ctypes.c_void_p(pt.data_ptr()), ctypes.c_size_t(n), width, ctypes.byref(h), st) == 0, L.mzk_last_error()
     note = ""
     if direct:
-        L.mzk_srs_table_bytes.restype = ctypes.c_size_t
         b0 = L.mzk_srs_table_bytes(h)
         torch.cuda.synchronize(); t0 = time.perf_counter()
         assert L.mzk_srs_build_direct(h, direct, ctypes.c_size_t(64 << 30), st) == 0, L.mzk_last_error()

@@ -6,7 +6,6 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspa
 import torch
 import myzkp_amd as mz
 L = mz.lib()
-L.mzk_ctx_stream.restype = ctypes.c_void_p
 dev = torch.device("cuda", 0)
 shapes = sys.argv[1] if len(sys.argv) > 1 else "10:256,10:256:10,12:64,14:16"
 for spec in shapes.split(','):

@@ -11,7 +11,6 @@ mz.init_devices([0, 0]); L = mz.lib()
 dev = torch.device("cuda", 0)
 # the contexts' own streams (distinct priorities = distinct hardware queues); PIPE_TORCH_STREAMS=1 uses two torch
 # streams instead, which overlap only when the runtime happens to put them on different queues
-mz.lib().mzk_ctx_stream.restype = ctypes.c_void_p
 st = [ctypes.c_void_p(mz.lib().mzk_ctx_stream(k)) for k in range(2)]
 if os.environ.get("PIPE_TORCH_STREAMS") == "1":
     streams = [torch.cuda.Stream(), torch.cuda.Stream()]

@@ -13,7 +13,6 @@ h = ctypes.c_void_p()
 assert L.mzk_srs_from_device(ctypes.c_void_p(pts.data_ptr()), ctypes.c_size_t(n), ctypes.byref(h), st) == 0
 out = torch.zeros(8, dtype=torch.int64, device=dev)
 PH = {}
-L.mzk_prof_name.restype = ctypes.c_char_p
 for i in range(32):
     nm = L.mzk_prof_name(i)
     if nm: PH[i] = nm.decode()

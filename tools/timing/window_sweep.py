@@ -1,7 +1,6 @@
 import sys, time, ctypes; sys.path.insert(0, "tests"); sys.path.insert(0, ".")
 import numpy as np, torch, myzkp_amd as mz
 mz.init(0); L = mz.lib(); dev = torch.device("cuda", 0)
-L.mzk_prof_name.restype = ctypes.c_char_p
 st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
 for lg in [int(x) for x in sys.argv[1].split(",")]:
     n = 1 << lg
