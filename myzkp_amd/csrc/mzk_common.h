@@ -137,12 +137,7 @@ static inline int root_check(const HostField* f, const uint64_t* root, size_t ro
 static inline bool is_pow2(size_t n) { return n && !(n & (n - 1)); }
 static inline unsigned ilog2(size_t n) { unsigned l = 0; while (((size_t)1 << l) < n) l++; return l; }   // ceil(log2 n); 0 for n <= 1
 
-// Goldilocks ids (mzk_gl.h): one or three canonical u64 per element, no Montgomery parameter set -- a kernel family of their own
-static inline bool field_is_gl(int fid) { return fid == MZK_FIELD_M64 || fid == MZK_FIELD_M64X3; }
-static inline int field_gl_comps(int fid) { return fid == MZK_FIELD_M64X3 ? 3 : 1; }
-static inline int field_words(int fid) { return field_is_gl(fid) ? 2 * field_gl_comps(fid) : (fid == MZK_FIELD_M128 ? 4 : 8); }   // u32 words per element
-static inline int field_limbs64(int fid) { return field_is_gl(fid) ? field_gl_comps(fid) : (fid == MZK_FIELD_M128 ? 2 : 4); }
-static inline size_t field_bytes(int fid) { return 8 * (size_t)field_limbs64(fid); }
+// field_is_gl, field_gl_comps, field_words, field_limbs64, field_bytes: the element shapes per field id, in mzk_hostfield.h
 static inline unsigned field_max_log(int fid) { return fid == MZK_FIELD_FR ? 28 : 32; }   // mzk.h "Size limits"
 
 // ---- field id -> template instantiation ---------------------------------------------------------------

@@ -97,22 +97,20 @@ static int fri_commit_rounds(int field_id, const uint64_t* codeword, const uint8
   for (int r = 0; r < num_rounds; r++) {
     uint8_t* root = roots + 48 * (size_t)r;
     if (len == 1) {
-      uint64_t limbs[4];
-      MZK_TRY(d2h_sync(limbs, cur, esz, s));
-      root_len[r] = host_leaf(field_id, limbs, root, r == 0 && negative && negative[0]);
+      size_t leaf_len = 0;
+      const int rc = merkle_single_leaf_root(field_id, cur, r == 0 && negative && negative[0], root, 48, &leaf_len, s);
+      if (rc == MZK_E_LENGTH) set_error("fri_commit: the one-element round %d does not fit the 48-byte root slot (%zu bytes)", r, leaf_len);
+      MZK_TRY(rc);
+      root_len[r] = leaf_len;
     } else {
       RootMailbox mb;
       bool mailed = false;
       MZK_TRY(merkle_mailbox(&mb));
       MZK_TRY(merkle_hash_levels(0, field_id, cur, nullptr, len, d_nodes, s, r == 0 ? d_neg : nullptr, 1, mb.p, mb.seq, &mailed));
       if (trees_out) {      // keep this round's tree: its leaves and digests stay where they were computed, in the shared block
-        mzk_merkle* t = new mzk_merkle();
-        t->kind = 0; t->field = field_id; t->n = len; t->stream = s;
+        mzk_merkle* t = (trees_out[r] = merkle_new(0, field_id, len, s).release());      // fri_commit_impl frees trees_out on failure
         t->d_nodes = d_nodes; t->d_leaves = cur;
         t->shared = shared;
-        t->depth = 0;
-        while (((size_t)1 << t->depth) < len) t->depth++;
-        trees_out[r] = t;
         if (r == 0 && negative) {
           // round 0 commits to the UNSANITIZED elements and the fold below canonicalises the codeword in place: the tree keeps
           // the magnitudes as they were given, in a copy of its own

@@ -10,6 +10,14 @@
 
 namespace mzk {
 
+// Element shapes per field id.  Goldilocks ids (mzk_gl.h): one or three canonical u64 per element, no Montgomery parameter set -- a
+// kernel family of their own
+static inline bool field_is_gl(int fid) { return fid == MZK_FIELD_M64 || fid == MZK_FIELD_M64X3; }
+static inline int field_gl_comps(int fid) { return fid == MZK_FIELD_M64X3 ? 3 : 1; }
+static inline int field_words(int fid) { return field_is_gl(fid) ? 2 * field_gl_comps(fid) : (fid == MZK_FIELD_M128 ? 4 : 8); }   // u32 words per element
+static inline int field_limbs64(int fid) { return field_is_gl(fid) ? field_gl_comps(fid) : (fid == MZK_FIELD_M128 ? 2 : 4); }
+static inline size_t field_bytes(int fid) { return 8 * (size_t)field_limbs64(fid); }
+
 // 29-bit limbs of the device's elements (FrParams::L, FqParams::L, M128Params::L: mzk_api.hip holds the static_assert)
 constexpr int HOST_LIMBS29_FR = 9, HOST_LIMBS29_FQ = 9, HOST_LIMBS29_M128 = 5;
 

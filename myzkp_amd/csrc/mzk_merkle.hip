@@ -17,6 +17,7 @@
 #include "mzk_keccak_pair.h"
 #include "mzk_gl.h"
 #include "mzk_merkle_plan.h"      // the level schedule and its thresholds (LEAF_PAIR_MAX, LEVEL_PAIR_MAX, TAIL_NODES)
+#include "mzk_merkle_open_plan.h" // openings: the scratch and output layout, host_leaf, the unpack
 
 namespace mzk {
 
@@ -554,20 +555,27 @@ int merkle_root_to_host(uint8_t* root, const u64* d_root, const RootMailbox& mb,
   return d2h_sync(root, d_root, 32, s);
 }
 
-// bincode(FiniteFieldElement) of ONE canonical element on the host: used for the n == 1 root and for the
-// sibling leaf of an authentication path (both are a copy of input bytes, not computation).
-static size_t host_bincode_field(const uint64_t* limbs, int nl, uint8_t* out, bool negative = false) {
-  uint32_t w[8];
-  memcpy(w, limbs, 8 * (size_t)nl);
-  return (size_t)(nl == 2 ? mzk_tx::fri_leaf_put<4>(w, negative, out) : mzk_tx::fri_leaf_put<8>(w, negative, out));
+// (the leaf bytes of one element on the host: host_leaf, mzk_merkle_open_plan.h)
+MerkleOwner merkle_new(int kind, int fid, size_t n, hipStream_t stream) {
+  MerkleOwner t(new mzk_merkle());
+  t->kind = kind; t->field = fid; t->n = n; t->stream = stream;
+  t->ragged = !is_pow2(n);
+  if (t->ragged) {      // the item tree: m = 2^floor(log2 n) items (k_merkle_ragged_items)
+    while (((size_t)2 << t->depth) <= n) t->depth++;
+    t->m = (size_t)1 << t->depth;
+  } else {
+    t->depth = (int)ilog2(n);
+  }
+  return t;
 }
-
-// The leaf bytes of one element of field `fid` on the host (at most HOST_LEAF_MAX: a 59-byte M64X3 leaf is the longest)
-constexpr size_t HOST_LEAF_MAX = 64;
-size_t host_leaf(int fid, const uint64_t* limbs, uint8_t* out, bool negative) {
-  if (!field_is_gl(fid)) return host_bincode_field(limbs, field_limbs64(fid), out, negative);
-  auto put = [&](int pos, uint32_t byte) { out[pos] = (uint8_t)byte; };
-  return (size_t)(fid == MZK_FIELD_M64X3 ? gl::leaf_bytes<3>(limbs, 0, put) : gl::leaf_bytes<1>(limbs, 0, put));
+int merkle_single_leaf_root(int fid, const void* d_leaf, bool negative, uint8_t* out, size_t cap, size_t* len, hipStream_t stream) {
+  uint64_t limbs[4];
+  uint8_t buf[HOST_LEAF_MAX];
+  MZK_TRY(d2h_sync(limbs, d_leaf, field_bytes(fid), stream));
+  *len = host_leaf(fid, limbs, buf, negative);
+  if (cap < *len) return MZK_E_LENGTH;
+  memcpy(out, buf, *len);
+  return MZK_OK;
 }
 // canonical elements of a host array: every limb group below the modulus (Goldilocks: every word below p)
 static int host_elems_canonical(int fid, const uint64_t* elems, size_t n) {
@@ -590,12 +598,9 @@ static int merkle_build(int kind, int fid, const void* src, bool src_on_device, 
 static int merkle_build_ragged(const uint8_t* leaves, const uint64_t* offsets, size_t n, mzk_merkle** out, hipStream_t s) {
   WsFrame ws("merkle_build_ragged");
   if (n > ((size_t)1 << 31)) { set_error("merkle: ragged trees support up to 2^31 leaves"); return MZK_E_ARG; }
-  mzk_merkle* t = new mzk_merkle();
-  t->kind = 1; t->field = -1; t->n = n; t->stream = s; t->d_nodes = nullptr; t->d_leaves = nullptr; t->ragged = true;
-  int D = 0;
-  while (((size_t)2 << D) <= n) D++;
-  const size_t m = (size_t)1 << D;
-  t->m = m; t->depth = D;
+  MerkleOwner t = merkle_new(1, -1, n, s);
+  const int D = t->depth;
+  const size_t m = t->m;
   t->offsets.assign(offsets, offsets + n + 1);
   // subtree p at depth D: walk the bits of p from the root (0 = left = floor half, 1 = right = ceil half)
   t->node_start.resize(m + 1);
@@ -617,29 +622,25 @@ static int merkle_build_ragged(const uint8_t* leaves, const uint64_t* offsets, s
   }
   t->item_off[m] = io;
   const size_t leaf_bytes = (size_t)(offsets[n] - offsets[0]);
-  u64 *d_off = nullptr, *d_ioff = nullptr;
-  u32* d_ns = nullptr;
-  int rc = MZK_OK;
-  do {
-    if ((rc = t->own_leaves.alloc(leaf_bytes ? leaf_bytes : 16, "merkle: leaves")) != MZK_OK) break;
-    if ((rc = t->own_items.alloc(io ? io : 16, "merkle: items")) != MZK_OK) break;
-    if ((rc = t->own_nodes.alloc((m - 1) * 32, "merkle: digests")) != MZK_OK) break;
-    t->d_leaves = t->own_leaves.get(); t->d_items = t->own_items.get(); t->d_nodes = t->own_nodes.as<u64>();
-    if ((rc = ws.get(WS_MISC_D, (n + 1) * 8, (void**)&d_off)) != MZK_OK) break;
-    if ((rc = ws.get(WS_MISC_E, (m + 1) * 8, (void**)&d_ioff)) != MZK_OK) break;
-    if ((rc = ws.get(WS_MISC_F, (m + 1) * 4, (void**)&d_ns)) != MZK_OK) break;
-    if ((leaf_bytes && hipMemcpyAsync(t->d_leaves, leaves, leaf_bytes, hipMemcpyHostToDevice, s) != hipSuccess) ||
-        hipMemcpyAsync(d_off, offsets, (n + 1) * 8, hipMemcpyHostToDevice, s) != hipSuccess ||
-        hipMemcpyAsync(d_ioff, t->item_off.data(), (m + 1) * 8, hipMemcpyHostToDevice, s) != hipSuccess ||
-        hipMemcpyAsync(d_ns, t->node_start.data(), (m + 1) * 4, hipMemcpyHostToDevice, s) != hipSuccess) { set_error("merkle: copy failed"); rc = MZK_E_HIP; break; }
-    hipLaunchKernelGGL(k_merkle_ragged_items, dim3((unsigned)((m + 127) / 128)), dim3(128), 0, s, (const u8*)t->d_leaves, (const u64*)d_off, (const u32*)d_ns, m,
-                       (const u64*)d_ioff, (u8*)t->d_items);
-    rc = merkle_hash_levels(1, -1, t->d_items, d_ioff, m, t->d_nodes, s);
-    if (rc == MZK_OK && hipStreamSynchronize(s) != hipSuccess) { set_error("merkle: sync failed"); rc = MZK_E_HIP; }
-    if (rc == MZK_OK) rc = merkle_stamp(t, s);
-  } while (0);
-  if (rc != MZK_OK) { mzk_merkle_free(t); return rc; }
-  *out = t;
+  u64 *d_off, *d_ioff;
+  u32* d_ns;
+  MZK_TRY(t->own_leaves.alloc(leaf_bytes ? leaf_bytes : 16, "merkle: leaves"));
+  MZK_TRY(t->own_items.alloc(io ? io : 16, "merkle: items"));
+  MZK_TRY(t->own_nodes.alloc((m - 1) * 32, "merkle: digests"));
+  t->d_leaves = t->own_leaves.get(); t->d_items = t->own_items.get(); t->d_nodes = t->own_nodes.as<u64>();
+  MZK_TRY(ws.get(WS_MISC_D, (n + 1) * 8, (void**)&d_off));
+  MZK_TRY(ws.get(WS_MISC_E, (m + 1) * 8, (void**)&d_ioff));
+  MZK_TRY(ws.get(WS_MISC_F, (m + 1) * 4, (void**)&d_ns));
+  if (leaf_bytes) MZK_HIP(hipMemcpyAsync(t->d_leaves, leaves, leaf_bytes, hipMemcpyHostToDevice, s));
+  MZK_HIP(hipMemcpyAsync(d_off, offsets, (n + 1) * 8, hipMemcpyHostToDevice, s));
+  MZK_HIP(hipMemcpyAsync(d_ioff, t->item_off.data(), (m + 1) * 8, hipMemcpyHostToDevice, s));
+  MZK_HIP(hipMemcpyAsync(d_ns, t->node_start.data(), (m + 1) * 4, hipMemcpyHostToDevice, s));
+  hipLaunchKernelGGL(k_merkle_ragged_items, dim3((unsigned)((m + 127) / 128)), dim3(128), 0, s, (const u8*)t->d_leaves, (const u64*)d_off, (const u32*)d_ns, m,
+                     (const u64*)d_ioff, (u8*)t->d_items);
+  MZK_TRY(merkle_hash_levels(1, -1, t->d_items, d_ioff, m, t->d_nodes, s));
+  MZK_HIP(hipStreamSynchronize(s));
+  MZK_TRY(merkle_stamp(t.get(), s));
+  *out = t.release();
   return MZK_OK;
 }
 
@@ -668,37 +669,28 @@ static int merkle_build(int kind, int fid, const void* src, bool src_on_device, 
     off[n] = o;
     return merkle_build_ragged(blob.data(), off.data(), n, out, s);
   }
-  mzk_merkle* t = new mzk_merkle();
-  t->kind = kind; t->field = fid; t->n = n; t->stream = s; t->d_nodes = nullptr; t->d_leaves = nullptr;
-  t->depth = 0;
-  while (((size_t)1 << t->depth) < n) t->depth++;
+  MerkleOwner t = merkle_new(kind, fid, n, s);
+  MZK_TRY(t->own_leaves.alloc(leaf_bytes ? leaf_bytes : 16, "merkle: leaves"));
+  t->d_leaves = t->own_leaves.get();
+  if (leaf_bytes) MZK_HIP(hipMemcpyAsync(t->d_leaves, src, leaf_bytes, src_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s));
+  if (n > 1) MZK_TRY(t->own_nodes.alloc((n - 1) * 32, "merkle: digests"));
+  t->d_nodes = t->own_nodes.as<u64>();
   u64* d_off = nullptr;
-  int rc = MZK_OK;
-  do {
-    if ((rc = t->own_leaves.alloc(leaf_bytes ? leaf_bytes : 16, "merkle: leaves")) != MZK_OK) break;
-    t->d_leaves = t->own_leaves.get();
-    if (leaf_bytes && hipMemcpyAsync(t->d_leaves, src, leaf_bytes, src_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s) != hipSuccess) {
-      set_error("merkle: leaf copy failed"); rc = MZK_E_HIP; break;
-    }
-    if (n > 1 && (rc = t->own_nodes.alloc((n - 1) * 32, "merkle: digests")) != MZK_OK) break;
-    t->d_nodes = t->own_nodes.as<u64>();
-    if (kind == 1) {
-      t->offsets.assign(offsets, offsets + n + 1);
-      if ((rc = ws.get(WS_MISC_D, (n + 1) * 8, (void**)&d_off)) != MZK_OK) break;
-      if (hipMemcpyAsync(d_off, offsets, (n + 1) * 8, hipMemcpyHostToDevice, s) != hipSuccess) { set_error("merkle: offset copy failed"); rc = MZK_E_HIP; break; }
-    }
-    u8* d_neg = nullptr;
-    if (kind == 0 && neg_host) {
-      t->neg.assign(neg_host, neg_host + n);
-      if ((rc = ws.get(WS_MISC_E, n, (void**)&d_neg)) != MZK_OK) break;
-      if (hipMemcpyAsync(d_neg, neg_host, n, hipMemcpyHostToDevice, s) != hipSuccess) { set_error("merkle: sign copy failed"); rc = MZK_E_HIP; break; }
-    }
-    rc = merkle_hash_levels(kind, fid, t->d_leaves, d_off, n, t->d_nodes, s, d_neg);
-    if (rc == MZK_OK && kind == 1 && hipStreamSynchronize(s) != hipSuccess) { set_error("merkle: sync failed"); rc = MZK_E_HIP; }
-    if (rc == MZK_OK) rc = merkle_stamp(t, s);
-  } while (0);
-  if (rc != MZK_OK) { mzk_merkle_free(t); return rc; }
-  *out = t;
+  if (kind == 1) {
+    t->offsets.assign(offsets, offsets + n + 1);
+    MZK_TRY(ws.get(WS_MISC_D, (n + 1) * 8, (void**)&d_off));
+    MZK_HIP(hipMemcpyAsync(d_off, offsets, (n + 1) * 8, hipMemcpyHostToDevice, s));
+  }
+  u8* d_neg = nullptr;
+  if (kind == 0 && neg_host) {
+    t->neg.assign(neg_host, neg_host + n);
+    MZK_TRY(ws.get(WS_MISC_E, n, (void**)&d_neg));
+    MZK_HIP(hipMemcpyAsync(d_neg, neg_host, n, hipMemcpyHostToDevice, s));
+  }
+  MZK_TRY(merkle_hash_levels(kind, fid, t->d_leaves, d_off, n, t->d_nodes, s, d_neg));
+  if (kind == 1) MZK_HIP(hipStreamSynchronize(s));
+  MZK_TRY(merkle_stamp(t.get(), s));
+  *out = t.release();
   return MZK_OK;
 }
 }  // namespace mzk
@@ -754,14 +746,11 @@ int mzk_merkle_root(const mzk_merkle* t, uint8_t* root, size_t cap, size_t* root
   MerkleScope ms(t);
   MZK_TRY(ms.rc);
   if (t->n == 1) {   // merkle.rs:17-19: the single leaf itself
-    uint8_t buf[HOST_LEAF_MAX];
-    size_t len;
+    size_t len = 0;
     if (t->kind == 0) {
-      uint64_t limbs[4];
-      MZK_TRY(d2h_sync(limbs, t->d_leaves, field_bytes(t->field), ms.s));
-      len = host_leaf(t->field, limbs, buf, !t->neg.empty() && t->neg[0]);
-      if (cap < len) { set_error("merkle_root: buffer too small (%zu < %zu)", cap, len); return MZK_E_LENGTH; }
-      memcpy(root, buf, len);
+      const int rc = merkle_single_leaf_root(t->field, t->d_leaves, !t->neg.empty() && t->neg[0], root, cap, &len, ms.s);
+      if (rc == MZK_E_LENGTH) set_error("merkle_root: buffer too small (%zu < %zu)", cap, len);
+      MZK_TRY(rc);
     } else {
       len = (size_t)(t->offsets[1] - t->offsets[0]);
       if (cap < len) { set_error("merkle_root: buffer too small (%zu < %zu)", cap, len); return MZK_E_LENGTH; }
@@ -793,10 +782,15 @@ int mzk_merkle_open(const mzk_merkle* t, size_t index, uint8_t* path, size_t str
   MZK_TRY(ms.rc);
   hipStream_t s = ms.s;
   WsGuard wsg(s);          // WS_MISC_C below is shared with every other entry point of the context
+  // Byte leaves.  Either form of tree names the entries that lead the path (device source, length), the size of the tree the digests
+  // are gathered from and the position in it; the digests follow the leading entries.
+  struct { const uint8_t* src; size_t len; } lead[2];
+  int n_lead = 0;
+  size_t size, pos;
   if (t->ragged) {
     // subtree p (depth D) that holds the leaf.  Merkle::open only terminates when its descent ends in a TWO-leaf
     // slice (merkle.rs:32-34); a one-leaf slice recurses forever (mid = 0), so those indices are an error here.
-    size_t p = (size_t)(std::upper_bound(t->node_start.begin(), t->node_start.end(), (uint32_t)index) - t->node_start.begin()) - 1;
+    const size_t p = (size_t)(std::upper_bound(t->node_start.begin(), t->node_start.end(), (uint32_t)index) - t->node_start.begin()) - 1;
     const uint32_t first = t->node_start[p], cnt = t->node_start[p + 1] - first;
     const size_t sibp = p ^ 1;
     const uint32_t sib_cnt = t->node_start[sibp + 1] - t->node_start[sibp];
@@ -806,110 +800,129 @@ int mzk_merkle_open(const mzk_merkle* t, size_t index, uint8_t* path, size_t str
     }
     // cnt == 2: the recursion ends inside subtree p (entry 0 = the other leaf), then climbs the item tree;
     // cnt == 1 with a one-leaf sibling: it ends one level higher, on the two-leaf slice {p, p ^ 1} -- the item path itself.
-    int k = 0;
     if (cnt == 2) {
       const size_t other = first + (1 - (index - first));
-      const size_t l0 = (size_t)(t->offsets[other + 1] - t->offsets[other]);
-      if (stride < l0) { set_error("merkle_open: stride %zu < entry length %zu", stride, l0); return MZK_E_LENGTH; }
-      if (l0) MZK_HIP(hipMemcpyAsync(path, (const uint8_t*)t->d_leaves + t->offsets[other], l0, hipMemcpyDeviceToHost, s));
-      path_len[0] = l0;
-      k = 1;
+      lead[n_lead++] = {(const uint8_t*)t->d_leaves + t->offsets[other], (size_t)(t->offsets[other + 1] - t->offsets[other])};
     }
-    const size_t l1 = (size_t)(t->item_off[sibp + 1] - t->item_off[sibp]);
-    if (stride < l1) { set_error("merkle_open: stride %zu < entry length %zu", stride, l1); return MZK_E_LENGTH; }
-    if (l1) MZK_HIP(hipMemcpyAsync(path + (size_t)k * stride, (const uint8_t*)t->d_items + t->item_off[sibp], l1, hipMemcpyDeviceToHost, s));   // sibling item: a leaf or a digest
-    path_len[k] = l1;
-    if (t->depth > 1) {
-      u64* d_out;
-      MZK_TRY(ws.get(WS_MISC_C, (size_t)t->depth * 32, (void**)&d_out));
-      hipLaunchKernelGGL(k_merkle_gather, dim3(1), dim3(64), 0, s, (const u64*)t->d_nodes, t->m, p, t->depth, d_out);
-      MZK_HIP(hipGetLastError());
-      uint8_t tmp[64 * 32];
-      MZK_TRY(d2h_sync(tmp, d_out, (size_t)(t->depth - 1) * 32, s));
-      for (int l = 1; l < t->depth; l++) { memcpy(path + (size_t)(l + k) * stride, tmp + 32 * (l - 1), 32); path_len[l + k] = 32; }
-    } else {
-      MZK_HIP(hipStreamSynchronize(s));
-    }
-    *depth = (size_t)t->depth + k;
-    return MZK_OK;
+    lead[n_lead++] = {(const uint8_t*)t->d_items + t->item_off[sibp], (size_t)(t->item_off[sibp + 1] - t->item_off[sibp])};   // sibling item: a leaf or a digest
+    size = t->m;
+    pos = p;
+  } else {
+    const size_t sib = index ^ 1;      // entry 0 is the sibling LEAF, verbatim
+    lead[n_lead++] = {(const uint8_t*)t->d_leaves + t->offsets[sib], (size_t)(t->offsets[sib + 1] - t->offsets[sib])};
+    size = t->n;
+    pos = index;
   }
-  const size_t sib = index ^ 1;
-  // byte leaves: entry 0 is the sibling LEAF, verbatim
-  {
-    const size_t len = (size_t)(t->offsets[sib + 1] - t->offsets[sib]);
-    if (stride < len) { set_error("merkle_open: stride %zu < leaf length %zu", stride, len); return MZK_E_LENGTH; }
-    if (len) MZK_HIP(hipMemcpyAsync(path, (const uint8_t*)t->d_leaves + t->offsets[sib], len, hipMemcpyDeviceToHost, s));
-    path_len[0] = len;
+  const int k = n_lead - 1;      // the digest of level l is entry l + k
+  for (int e = 0; e < n_lead; e++)
+    if (stride < lead[e].len) { set_error("merkle_open: stride %zu < %s length %zu", stride, t->ragged ? "entry" : "leaf", lead[e].len); return MZK_E_LENGTH; }
+  for (int e = 0; e < n_lead; e++) {
+    if (lead[e].len) MZK_HIP(hipMemcpyAsync(path + (size_t)e * stride, lead[e].src, lead[e].len, hipMemcpyDeviceToHost, s));
+    path_len[e] = lead[e].len;
   }
   if (t->depth > 1) {
     u64* d_out;
     MZK_TRY(ws.get(WS_MISC_C, (size_t)t->depth * 32, (void**)&d_out));
-    hipLaunchKernelGGL(k_merkle_gather, dim3(1), dim3(64), 0, s, (const u64*)t->d_nodes, t->n, index, t->depth, d_out);
+    hipLaunchKernelGGL(k_merkle_gather, dim3(1), dim3(64), 0, s, (const u64*)t->d_nodes, size, pos, t->depth, d_out);
     MZK_HIP(hipGetLastError());
     uint8_t tmp[64 * 32];
     MZK_TRY(d2h_sync(tmp, d_out, (size_t)(t->depth - 1) * 32, s));
-    for (int l = 1; l < t->depth; l++) { memcpy(path + (size_t)l * stride, tmp + 32 * (l - 1), 32); path_len[l] = 32; }
+    for (int l = 1; l < t->depth; l++) { memcpy(path + (size_t)(l + k) * stride, tmp + 32 * (l - 1), 32); path_len[l + k] = 32; }
   } else {
     MZK_HIP(hipStreamSynchronize(s));
   }
-  *depth = (size_t)t->depth;
+  *depth = (size_t)t->depth + k;
   return MZK_OK;
 }
+
+}  // extern "C"
+
+namespace mzk {
+// what the batched openings serve: field-element trees of two or more leaves, a power of two of them (`t`: the tree's place in the call)
+static int merkle_open_tree_check(const mzk_merkle* tr, size_t t, const char* who) {
+  if (tr->n < 2) { set_error("merkle_open: needs at least two leaves (merkle.rs:32)"); return MZK_E_LENGTH; }
+  if (tr->ragged || tr->kind != 0) {
+    set_error("%s: field-element trees with a power-of-two leaf count only (tree %zu: %s); open its paths one by one", who, t,
+              tr->kind != 0 ? "byte leaves" : "ragged");
+    return MZK_E_ARG;
+  }
+  return MZK_OK;
+}
+// Openings of SEVERAL field-element trees in one gather and one synchronisation: what mzk_merkle_open_multi documents.  Tree t takes the
+// next counts[t] entries of `indices`; the layout of the scratch and of paths / path_lens, and the unpack, are mzk_merkle_open_plan.h's.
+int merkle_open_trees(const mzk_merkle* const* trees, size_t n_trees, const uint64_t* indices, const size_t* counts, uint8_t* paths, size_t stride,
+                      uint64_t* path_lens, size_t* depths, const char* who) {
+  if (!trees || !counts || !depths) { set_error("%s: null pointer", who); return MZK_E_ARG; }
+  std::vector<MerkleOpenTree> plan(n_trees);
+  MerkleOpenAt total;
+  const mzk_merkle* first = nullptr;
+  for (size_t t = 0; t < n_trees; t++) {
+    const mzk_merkle* tr = trees[t];
+    depths[t] = tr ? (size_t)tr->depth : 0;
+    if (counts[t] == 0) continue;
+    if (!tr || !indices || !paths || !path_lens) { set_error("%s: null pointer", who); return MZK_E_ARG; }
+    MZK_TRY(merkle_open_tree_check(tr, t, who));
+    for (size_t q = 0; q < counts[t]; q++)
+      if (indices[total.index + q] >= tr->n) { set_error("merkle_open: index %llu out of range (tree %zu)", (unsigned long long)indices[total.index + q], t); return MZK_E_LENGTH; }
+    if (!first) first = tr;
+    if (tr->ctx_index != first->ctx_index || tr->device != first->device) {
+      set_error("%s: tree %zu lives on context %d, the first opened tree on context %d; one call opens trees of one context", who, t, tr->ctx_index,
+                first->ctx_index);
+      return MZK_E_ARG;
+    }
+    plan[t].field = tr->field; plan[t].depth = tr->depth; plan[t].count = counts[t];
+    plan[t].neg = tr->neg.empty() ? nullptr : tr->neg.data();
+    total.advance(plan[t]);
+  }
+  if (total.index == 0) return MZK_OK;
+  if (stride < 32) { set_error("merkle_open: stride < 32"); return MZK_E_LENGTH; }
+  MZK_ENTER();
+  WsFrame ws(who);
+  MerkleScope ms(first);
+  MZK_TRY(ms.rc);
+  hipStream_t s = ms.s;
+  for (size_t t = 0; t < n_trees; t++)      // every opened tree's build, not only the first one's (whose event MerkleScope has waited on)
+    if (counts[t] && trees[t] != first && trees[t]->built) MZK_HIP(hipStreamWaitEvent(s, trees[t]->built, 0));
+  WsGuard wsg(s);
+  u64* d_idx;
+  MZK_TRY(ws.get(WS_MISC_C, merkle_open_scratch_bytes(total), (void**)&d_idx));
+  u64* d_on = d_idx + total.index;
+  u32* d_ol = (u32*)(d_on + total.node);
+  MZK_HIP(hipMemcpyAsync(d_idx, indices, total.index * 8, hipMemcpyHostToDevice, s));
+  MerkleOpenAt at;
+  for (size_t t = 0; t < n_trees; t++) {
+    if (counts[t] == 0) continue;
+    const mzk_merkle* tr = trees[t];
+    hipLaunchKernelGGL(k_merkle_gather_batch, dim3((unsigned)counts[t]), dim3(64), 0, s, (const u64*)tr->d_nodes, (const u32*)tr->d_leaves, field_words(tr->field),
+                       tr->n, (const u64*)(d_idx + at.index), tr->depth, d_on + at.node, d_ol + at.leaf);
+    at.advance(plan[t]);
+  }
+  MZK_HIP(hipGetLastError());
+  std::vector<uint64_t> hn(total.node + 1);
+  std::vector<uint32_t> hl(total.leaf + 1);
+  if (total.node) MZK_HIP(hipMemcpyAsync(hn.data(), d_on, total.node * 8, hipMemcpyDeviceToHost, s));
+  MZK_TRY(d2h_sync(hl.data(), d_ol, total.leaf * 4, s));
+  size_t bad_entry = 0, bad_len = 0;
+  const int rc = merkle_open_unpack(plan.data(), n_trees, indices, hn.data(), hl.data(), paths, stride, path_lens, &bad_entry, &bad_len);
+  if (rc != MZK_OK) set_error("merkle_open: stride %zu < leaf length %zu (path entry %zu)", stride, bad_len, bad_entry);
+  return rc;
+}
+}  // namespace mzk
+
+extern "C" {
 
 // `count` openings of one tree: paths[(q * depth + l) * stride ..] / path_lens[q * depth + l] as mzk_merkle_open writes them
 // for index indices[q]; *depth entries per path.  Field-element trees with a power-of-two leaf count (every codeword of
 // the provers): ONE gather launch and ONE copy for all paths.  Byte-leaf and ragged trees: MZK_E_ARG (open one by one).
 int mzk_merkle_open_batch(const mzk_merkle* t, const uint64_t* indices, size_t count, uint8_t* paths, size_t stride, uint64_t* path_lens,
                           size_t* depth) {
-  if (!t || !depth || ((!indices || !paths || !path_lens) && count)) { set_error("merkle_open_batch: null pointer"); return MZK_E_ARG; }
-  if (t->n < 2) { set_error("merkle_open: needs at least two leaves (merkle.rs:32)"); return MZK_E_LENGTH; }
-  if (t->ragged || t->kind != 0) {
-    set_error("merkle_open_batch: field-element trees with a power-of-two leaf count only (this one: %s); open its paths one by one",
-              t->kind != 0 ? "byte leaves" : "ragged");
-    return MZK_E_ARG;
+  if (!t || !depth) { set_error("merkle_open_batch: null pointer"); return MZK_E_ARG; }
+  if (count == 0) {      // nothing to open: the tree is still refused if it could not be opened, and *depth is written; no context is entered
+    MZK_TRY(merkle_open_tree_check(t, 0, "merkle_open_batch"));
+    *depth = (size_t)t->depth;
+    return MZK_OK;
   }
-  *depth = (size_t)t->depth;
-  if (count == 0) return MZK_OK;
-  if (stride < 32) { set_error("merkle_open: stride < 32"); return MZK_E_LENGTH; }
-  for (size_t q = 0; q < count; q++)
-    if (indices[q] >= t->n) { set_error("merkle_open: index %llu out of range", (unsigned long long)indices[q]); return MZK_E_LENGTH; }
-  MZK_ENTER();
-  WsFrame ws("mzk_merkle_open_batch");
-  MerkleScope ms(t);
-  MZK_TRY(ms.rc);
-  hipStream_t s = ms.s;
-  WsGuard wsg(s);
-  const int lw = (int)field_words(t->field);
-  const size_t node_words64 = count * (size_t)(t->depth - 1) * 4;
-  u64 *d_idx, *d_on;
-  u32* d_ol;
-  MZK_TRY(ws.get(WS_MISC_C, count * 8 + node_words64 * 8 + count * (size_t)lw * 4 + 64, (void**)&d_idx));
-  d_on = d_idx + count;
-  d_ol = (u32*)(d_on + node_words64);
-  MZK_HIP(hipMemcpyAsync(d_idx, indices, count * 8, hipMemcpyHostToDevice, s));
-  hipLaunchKernelGGL(k_merkle_gather_batch, dim3((unsigned)count), dim3(64), 0, s, (const u64*)t->d_nodes, (const u32*)t->d_leaves, lw, t->n,
-                     (const u64*)d_idx, t->depth, d_on, d_ol);
-  MZK_HIP(hipGetLastError());
-  std::vector<uint64_t> hn(node_words64 + 1);
-  std::vector<uint32_t> hl(count * (size_t)lw);
-  if (node_words64) MZK_HIP(hipMemcpyAsync(hn.data(), d_on, node_words64 * 8, hipMemcpyDeviceToHost, s));
-  MZK_TRY(d2h_sync(hl.data(), d_ol, count * (size_t)lw * 4, s));
-  for (size_t q = 0; q < count; q++) {
-    uint64_t limbs[4] = {0, 0, 0, 0};
-    memcpy(limbs, hl.data() + q * lw, (size_t)lw * 4);
-    uint8_t buf[HOST_LEAF_MAX];
-    const size_t sib = (size_t)indices[q] ^ 1;
-    const size_t len = host_leaf(t->field, limbs, buf, !t->neg.empty() && t->neg[sib]);
-    if (stride < len) { set_error("merkle_open: stride %zu < leaf length %zu", stride, len); return MZK_E_LENGTH; }
-    uint8_t* pq = paths + q * (size_t)t->depth * stride;
-    memcpy(pq, buf, len);
-    path_lens[q * (size_t)t->depth] = len;
-    for (int l = 1; l < t->depth; l++) {
-      memcpy(pq + (size_t)l * stride, hn.data() + (q * (size_t)(t->depth - 1) + (l - 1)) * 4, 32);
-      path_lens[q * (size_t)t->depth + l] = 32;
-    }
-  }
-  return MZK_OK;
+  return merkle_open_trees(&t, 1, indices, &count, paths, stride, path_lens, depth, "merkle_open_batch");
 }
 
 // Openings of SEVERAL trees in one call: the query phase of FRI::prove (fri.rs:127-137, reveal :211-260) opens the a / b indices
@@ -919,91 +932,7 @@ int mzk_merkle_open_batch(const mzk_merkle* t, const uint64_t* indices, size_t c
 // lays them out with depths[t] entries per path.  counts[t] == 0 skips tree t (which may then be NULL).
 int mzk_merkle_open_multi(const mzk_merkle* const* trees, size_t n_trees, const uint64_t* indices, const size_t* counts, uint8_t* paths,
                           size_t stride, uint64_t* path_lens, size_t* depths) {
-  if (!trees || !counts || !depths) { set_error("merkle_open_multi: null pointer"); return MZK_E_ARG; }
-  size_t total = 0, total_nodes = 0, total_leaf_words = 0;
-  const mzk_merkle* first = nullptr;
-  for (size_t t = 0; t < n_trees; t++) {
-    depths[t] = trees[t] ? (size_t)trees[t]->depth : 0;
-    if (counts[t] == 0) continue;
-    const mzk_merkle* tr = trees[t];
-    if (!tr || !indices || !paths || !path_lens) { set_error("merkle_open_multi: null pointer"); return MZK_E_ARG; }
-    if (tr->n < 2) { set_error("merkle_open: needs at least two leaves (merkle.rs:32)"); return MZK_E_LENGTH; }
-    if (tr->ragged || tr->kind != 0) {
-      set_error("merkle_open_multi: field-element trees with a power-of-two leaf count only (tree %zu: %s)", t, tr->kind != 0 ? "byte leaves" : "ragged");
-      return MZK_E_ARG;
-    }
-    for (size_t q = 0; q < counts[t]; q++)
-      if (indices[total + q] >= tr->n) { set_error("merkle_open: index %llu out of range (tree %zu)", (unsigned long long)indices[total + q], t); return MZK_E_LENGTH; }
-    if (!first) first = tr;
-    if (tr->ctx_index != first->ctx_index || tr->device != first->device) {
-      set_error("merkle_open_multi: tree %zu lives on context %d, the first opened tree on context %d; one call opens trees of one context", t,
-                tr->ctx_index, first->ctx_index);
-      return MZK_E_ARG;
-    }
-    total += counts[t];
-    total_nodes += counts[t] * (size_t)(tr->depth - 1) * 4;
-    total_leaf_words += counts[t] * field_words(tr->field);
-  }
-  if (total == 0) return MZK_OK;
-  if (stride < 32) { set_error("merkle_open: stride < 32"); return MZK_E_LENGTH; }
-  MZK_ENTER();
-  WsFrame ws("mzk_merkle_open_multi");
-  MerkleScope ms(first);
-  MZK_TRY(ms.rc);
-  hipStream_t s = ms.s;
-  for (size_t t = 0; t < n_trees; t++)      // every opened tree's build, not only the first one's
-    if (counts[t] && trees[t]->built) MZK_HIP(hipStreamWaitEvent(s, trees[t]->built, 0));
-  WsGuard wsg(s);
-  u64 *d_idx, *d_on;
-  u32* d_ol;
-  MZK_TRY(ws.get(WS_MISC_C, total * 8 + total_nodes * 8 + total_leaf_words * 4 + 64, (void**)&d_idx));
-  d_on = d_idx + total;
-  d_ol = (u32*)(d_on + total_nodes);
-  MZK_HIP(hipMemcpyAsync(d_idx, indices, total * 8, hipMemcpyHostToDevice, s));
-  {
-    size_t at = 0, at_nodes = 0, at_leaf = 0;
-    for (size_t t = 0; t < n_trees; t++) {
-      if (counts[t] == 0) continue;
-      const mzk_merkle* tr = trees[t];
-      const int lw = (int)field_words(tr->field);
-      hipLaunchKernelGGL(k_merkle_gather_batch, dim3((unsigned)counts[t]), dim3(64), 0, s, (const u64*)tr->d_nodes, (const u32*)tr->d_leaves, lw, tr->n,
-                         (const u64*)(d_idx + at), tr->depth, d_on + at_nodes, d_ol + at_leaf);
-      at += counts[t];
-      at_nodes += counts[t] * (size_t)(tr->depth - 1) * 4;
-      at_leaf += counts[t] * (size_t)lw;
-    }
-  }
-  MZK_HIP(hipGetLastError());
-  std::vector<uint64_t> hn(total_nodes + 1);
-  std::vector<uint32_t> hl(total_leaf_words + 1);
-  if (total_nodes) MZK_HIP(hipMemcpyAsync(hn.data(), d_on, total_nodes * 8, hipMemcpyDeviceToHost, s));
-  MZK_TRY(d2h_sync(hl.data(), d_ol, total_leaf_words * 4, s));
-  size_t at = 0, at_nodes = 0, at_leaf = 0, at_entry = 0;
-  for (size_t t = 0; t < n_trees; t++) {
-    if (counts[t] == 0) continue;
-    const mzk_merkle* tr = trees[t];
-    const int lw = (int)field_words(tr->field);
-    for (size_t q = 0; q < counts[t]; q++) {
-      uint64_t limbs[4] = {0, 0, 0, 0};
-      memcpy(limbs, hl.data() + at_leaf + q * lw, (size_t)lw * 4);
-      uint8_t buf[HOST_LEAF_MAX];
-      const size_t sib = (size_t)indices[at + q] ^ 1;
-      const size_t len = host_leaf(tr->field, limbs, buf, !tr->neg.empty() && tr->neg[sib]);
-      if (stride < len) { set_error("merkle_open: stride %zu < leaf length %zu", stride, len); return MZK_E_LENGTH; }
-      uint8_t* pq = paths + (at_entry + q * (size_t)tr->depth) * stride;
-      memcpy(pq, buf, len);
-      path_lens[at_entry + q * (size_t)tr->depth] = len;
-      for (int l = 1; l < tr->depth; l++) {
-        memcpy(pq + (size_t)l * stride, hn.data() + at_nodes + (q * (size_t)(tr->depth - 1) + (l - 1)) * 4, 32);
-        path_lens[at_entry + q * (size_t)tr->depth + l] = 32;
-      }
-    }
-    at += counts[t];
-    at_nodes += counts[t] * (size_t)(tr->depth - 1) * 4;
-    at_leaf += counts[t] * (size_t)lw;
-    at_entry += counts[t] * (size_t)tr->depth;
-  }
-  return MZK_OK;
+  return merkle_open_trees(trees, n_trees, indices, counts, paths, stride, path_lens, depths, "merkle_open_multi");
 }
 
 void mzk_merkle_free(mzk_merkle* t) {
@@ -1030,14 +959,9 @@ int mzk_merkle_commit_field_dev(int field_id, const void* d_elems, size_t n, uin
   }
   hipStream_t s = (hipStream_t)stream;
   if (n == 1) {
-    uint64_t limbs[4];
-    uint8_t buf[HOST_LEAF_MAX];
-    MZK_TRY(d2h_sync(limbs, d_elems, field_bytes(field_id), s));
-    const size_t len = host_leaf(field_id, limbs, buf);
-    if (cap < len) { set_error("merkle: root buffer too small"); return MZK_E_LENGTH; }
-    memcpy(root, buf, len);
-    *root_len = len;
-    return MZK_OK;
+    const int rc = merkle_single_leaf_root(field_id, d_elems, false, root, cap, root_len, s);
+    if (rc == MZK_E_LENGTH) set_error("merkle: root buffer too small");
+    return rc;
   }
   if (cap < 32) { set_error("merkle: root buffer too small"); return MZK_E_LENGTH; }
   u64* d_nodes;
