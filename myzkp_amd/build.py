@@ -12,7 +12,7 @@ ROOT = os.path.dirname(HERE)
 CSRC = os.path.join(HERE, "csrc")
 OUT = os.path.join(HERE, "libmzk_hip.so")
 OUT_TUNING = os.path.join(HERE, "libmzk_hip_tuning.so")
-SOURCES = ["mzk_api.hip", "mzk_multi.hip", "mzk_io.hip", "mzk_poly.hip", "mzk_ntt.hip", "mzk_gl.hip", "mzk_msm.hip", "mzk_msm_row.hip", "mzk_kzg.hip", "mzk_gemini.hip", "mzk_sumcheck.hip", "mzk_mpoly.hip", "mzk_stark.hip", "mzk_merkle.hip", "mzk_fri.hip", "mzk_rs.hip", "mzk_das.hip", "mzk_rescue.hip", "mzk_g2.hip", "mzk_selftest.hip", "mzk_probe.hip"]
+SOURCES = ["mzk_api.hip", "mzk_multi.hip", "mzk_io.hip", "mzk_srs.hip", "mzk_poly.hip", "mzk_ntt.hip", "mzk_gl.hip", "mzk_msm.hip", "mzk_msm_row.hip", "mzk_kzg.hip", "mzk_gemini.hip", "mzk_sumcheck.hip", "mzk_mpoly.hip", "mzk_stark.hip", "mzk_merkle.hip", "mzk_fri.hip", "mzk_rs.hip", "mzk_das.hip", "mzk_rescue.hip", "mzk_g2.hip", "mzk_selftest.hip", "mzk_probe.hip"]
 import glob
 # every header of csrc/ plus the ABI header: a hand-kept list went stale once (mzk_glv.h)
 HEADERS = sorted(glob.glob(os.path.join(CSRC, "*.h"))) + [os.path.join(ROOT, "include", "mzk.h")]

@@ -8,6 +8,7 @@
 #include "mzk_divide_plan.h"
 #include "mzk_gl.h"
 #include "mzk_mul_plan.h"
+#include "mzk_srs.h"
 
 namespace mzk {
 
@@ -485,8 +486,8 @@ struct EventSet {          // a few events for the length of one call
   int make(int count) { for (int k = 0; k < count; k++) MZK_HIP(hipEventCreateWithFlags(&ev[k], hipEventDisableTiming)); return MZK_OK; }
   ~EventSet() { for (auto e : ev) if (e) (void)hipEventDestroy(e); }
 };
-static int msm_host_chunked(const uint64_t* scalars, const uint64_t* points, void* d_s, void* d_p, const void* d_points_for_msm, size_t n, int point_kind,
-                            size_t table_stride, void* d_o, hipStream_t s, mzk::MsmChunk* ch, int K) {
+static int msm_host_chunked(const uint64_t* scalars, const uint64_t* points, void* d_s, void* d_p, mzk::MsmPoints pts, size_t n, void* d_o, hipStream_t s,
+                            mzk::MsmChunk* ch, int K) {
   hipStream_t side;
   hipEvent_t fork, join;
   MZK_TRY(side_stream(&side, &fork, &join));
@@ -497,7 +498,7 @@ static int msm_host_chunked(const uint64_t* scalars, const uint64_t* points, voi
   for (int k = 0; k < K; k++) { ch[k].d_scalars = (const uint8_t*)d_s + ch[k].i0 * 32; ch[k].ready = es.ev[k]; }
   const HostChunkUpload up{scalars, points, d_s, d_p, ch, es.ev, side};
   const std::function<int(int)> before = [&](int k) -> int { return up(k); };
-  const int rc = msm_chunked_impl(ch, K, d_points_for_msm, n, point_kind, table_stride, d_o, false, s, &before);
+  const int rc = msm_chunked_impl(ch, K, pts, n, d_o, false, s, &before);
   if (rc != MZK_OK) (void)hipStreamSynchronize(side);      // no piece may still be reading the caller's host buffers on return
   return rc;
 }
@@ -846,19 +847,7 @@ int mzk_fast_coset_divide_batch_dev(int field_id, const void* d_lhs, size_t lhs_
 }
 
 // ---- MSM / KZG ---------------------------------------------------------------------------------------------
-// Every SRS handle gets window tables of the width msm_srs_window_bits picks for its size, unless the caller asks for
-// plain prepared points (mzk_srs_from_device_ex(with_tables = 0): the one-shot pipelines).
-// A handle is plain device memory: any context on the SAME GPU may commit against it (two contexts on one device
-// keep two commits in flight: the latency-bound tail of one overlaps the sort / accumulate of the next).
-static int srs_check_ctx(const mzk_srs* srs) {
-  if (srs->ctx_index != ctx().index && mzk_ctx_device(srs->ctx_index) != ctx().device) {
-    set_error("SRS handle lives on context %d (device %d), the current context %d drives device %d (mzk_ctx_select)", srs->ctx_index,
-              mzk_ctx_device(srs->ctx_index), ctx().index, ctx().device);
-    return MZK_E_ARG;
-  }
-  return MZK_OK;
-}
-
+// (the SRS handle, its constructors and its tables: mzk_srs.h, mzk_srs.hip)
 int mzk_msm_g1_bn254(const uint64_t* scalars, const uint64_t* points_xy, size_t n, uint64_t out_xy[8]) {
   MZK_ENTER();
   WsFrame ws("mzk_msm_g1_bn254");
@@ -874,14 +863,14 @@ int mzk_msm_g1_bn254(const uint64_t* scalars, const uint64_t* points_xy, size_t 
   MZK_TRY(side_stream(&side, &fork, &join));
   MZK_TRY(ws.get(WS_MISC_A, n ? n * 64 : 16, &d_p));
   MZK_TRY(ws.get(WS_MISC_B, 256, &d_o));
-  if (msm_chunkable(n, MSM_PTS_PLAIN, 0) && host_chunks_enabled()) {
+  if (msm_chunkable(n, MsmPoints::plain(d_p)) && host_chunks_enabled()) {
     // four equal pieces of scalars + points: the transfers (96 bytes per pair: 1.7 ms at 2^20) run under the pieces' kernels but for
     // the first piece's (profiles/round6_host_buffer_chunks.txt)
     static const int quarters[4] = {64, 128, 192, 256};
     MsmChunk ch[8];
     MZK_TRY(ws.get(WS_MSM_SCALARS, n * 32, &d_s));
     const int K = host_chunk_plan(n, "MZK_HOST_CHUNKS_MSM", quarters, 4, ch);
-    MZK_TRY(msm_host_chunked(scalars, points_xy, d_s, d_p, d_p, n, MSM_PTS_PLAIN, 0, d_o, s, ch, K));
+    MZK_TRY(msm_host_chunked(scalars, points_xy, d_s, d_p, MsmPoints::plain(d_p), n, d_o, s, ch, K));
     MZK_TRY(d2h_sync(out_xy, d_o, 64, s));
     return MZK_OK;
   }
@@ -894,19 +883,19 @@ int mzk_msm_g1_bn254(const uint64_t* scalars, const uint64_t* points_xy, size_t 
     MZK_HIP(hipStreamWaitEvent(s, join, 0));
     return MZK_OK;
   };
-  MZK_TRY(msm_dev_impl(d_s, d_p, n, MSM_PTS_PLAIN, 0, d_o, false, s, &points_ready));
+  MZK_TRY(msm_dev_impl(d_s, MsmPoints::plain(d_p), n, d_o, false, s, &points_ready));
   MZK_TRY(d2h_sync(out_xy, d_o, 64, s));
   return MZK_OK;
 }
 int mzk_msm_g1_bn254_dev(const void* d_scalars, const void* d_points_xy, size_t n, void* d_out_xy, void* stream) {
   MZK_ENTER();
   WsGuard wsg((hipStream_t)stream);
-  return msm_dev_impl(d_scalars, d_points_xy, n, MSM_PTS_PLAIN, 0, d_out_xy, false, (hipStream_t)stream);
+  return msm_dev_impl(d_scalars, MsmPoints::plain(d_points_xy), n, d_out_xy, false, (hipStream_t)stream);
 }
 int mzk_msm_g1_bn254_partial_dev(const void* d_scalars, const void* d_points_xy, size_t n, void* d_partial16, void* stream) {
   MZK_ENTER();
   WsGuard wsg((hipStream_t)stream);
-  return msm_dev_impl(d_scalars, d_points_xy, n, MSM_PTS_PLAIN, 0, d_partial16, true, (hipStream_t)stream);
+  return msm_dev_impl(d_scalars, MsmPoints::plain(d_points_xy), n, d_partial16, true, (hipStream_t)stream);
 }
 int mzk_g1_fold_partials_dev(const void* d_partials16, int count, void* d_out_xy, void* stream) {
   MZK_ENTER();
@@ -914,67 +903,6 @@ int mzk_g1_fold_partials_dev(const void* d_partials16, int count, void* d_out_xy
   return msm_fold_partials_impl(d_partials16, count, d_out_xy, (hipStream_t)stream);
 }
 
-}  // extern "C"
-
-// ---- layout of a new handle: what fits -------------------------------------------------------------------------------------
-// commit_kzg(&poly, &pk) never fails for lack of memory, so neither may the seam: the window tables are an accelerator, and a
-// handle takes the richest layout that fits the caller's budget (mzk_set_table_budget; 0 = no limit) AND the device --
-//   all tables of the wanted width (15 x n points at 17 bits: 0.94 GiB at 2^20, 13 x n at 20 bits: 13 GiB at 2^24)
-//   -> every 2nd table with two bucket sets -> every 4th with four (from 2^15 points on; at most 17-bit windows: the bucket
-//      sets multiply the bucket count, and beyond 2^19 buckets the sort leaves its staged path)
-//   -> the prepared points and their endomorphism images only (the generic GLV layout: 128 bytes per point).
-// The last step ignores the budget (it is what the library needs to work at all); only when even that allocation fails is
-// the error MZK_E_NOMEM.  mzk_srs_window_bits / mzk_srs_bucket_sets / mzk_srs_table_bytes report what a handle got.
-static size_t g_table_budget = 0;
-namespace mzk {
-size_t table_budget_bytes() { return g_table_budget; }
-int srs_alloc_layout(mzk_srs* h, int with_tables) {
-  const size_t n = h->n;
-  struct Cand { bool tables; int bits, sets; };
-  Cand cand[4];
-  int nc = 0;
-  const bool want = with_tables > 1 || (with_tables && msm_srs_default_tables(n));
-  const int bits = with_tables > 1 ? with_tables : msm_srs_window_bits(n);
-  if (want) {
-    cand[nc++] = {true, bits, 1};
-    if (n >= ((size_t)1 << 15) && bits >= 14) {
-      const int b2 = bits > 17 ? 17 : bits;
-      cand[nc++] = {true, b2, 2};
-      cand[nc++] = {true, b2, 4};
-    }
-  }
-  cand[nc++] = {false, bits, 1};
-  for (int k = 0; k < nc; k++) {
-    const size_t rows = cand[k].tables ? (size_t)msm_table_rows(cand[k].bits, cand[k].sets) : 2;
-    const size_t bytes = n * 64 * rows;
-    const bool last = k == nc - 1;
-    if (!last && g_table_budget && bytes > g_table_budget) continue;
-    void* p = nullptr;
-    // (dev_alloc: a refused allocation is tried again after the idle workspace has been released -- BEFORE the layout degrades)
-    if (n == 0 || dev_alloc(&p, bytes, "SRS handle") == MZK_OK) {
-      h->d_points_mont = p; h->has_tables = cand[k].tables; h->window_bits = cand[k].bits; h->sets = cand[k].sets;
-      return MZK_OK;
-    }
-  }
-  set_error("SRS handle: the device has no %zu bytes left for the prepared points alone (idle workspace already released)", n * 128);
-  return MZK_E_NOMEM;
-}
-// fills a freshly laid-out handle from n affine canonical points in device memory
-int srs_fill(mzk_srs* h, const void* d_plain, hipStream_t s) {
-  WsFrame ws("srs_fill");
-  const size_t n = h->n;
-  if (n == 0) return MZK_OK;
-  if (!h->has_tables) return msm_prepare_points(d_plain, n, h->d_points_mont, (uint8_t*)h->d_points_mont + n * 64, s);
-  void* d_mont;
-  MZK_TRY(ws.get(WS_MSM_POINTS, n * 64, &d_mont));
-  MZK_TRY(msm_prepare_points(d_plain, n, d_mont, nullptr, s));
-  return msm_build_tables(d_mont, n, h->d_points_mont, h->window_bits * h->sets, s);     // every sets-th window: rows 2^(c sets q) P_i
-}
-}  // namespace mzk
-
-extern "C" {
-
-int mzk_set_table_budget(size_t bytes) { g_table_budget = bytes; return MZK_OK; }
 int mzk_set_workspace_budget(size_t bytes) {
   MZK_ENTER();
   g_ws_budget = bytes;
@@ -1010,34 +938,6 @@ int mzk_workspace_bytes(size_t* bytes) {
   *bytes = total;
   return MZK_OK;
 }
-int mzk_srs_bucket_sets(const mzk_srs* srs) { return (srs && srs->has_tables) ? srs->sets : 0; }
-
-int mzk_srs_upload(const uint64_t* powers_xy, size_t n, mzk_srs** out) {
-  MZK_ENTER();
-  WsFrame ws("mzk_srs_upload");
-  if (!out || (!powers_xy && n)) { set_error("srs_upload: null pointer"); return MZK_E_ARG; }
-  hipStream_t s = ctx().stream;
-  WsGuard wsg(s);
-  mzk_srs* h = new mzk_srs{nullptr, n, false, 0, ctx().index};
-  int rc = srs_alloc_layout(h, 1);
-  if (rc != MZK_OK) { delete h; return rc; }
-  if (n) {
-    void* d_plain;
-    rc = stage_in(ws, WS_MISC_A, powers_xy, n * 64, &d_plain, s);
-    if (rc == MZK_OK) rc = srs_fill(h, d_plain, s);
-    if (rc == MZK_OK && hipStreamSynchronize(s) != hipSuccess) rc = MZK_E_HIP;
-    if (rc != MZK_OK) { (void)ws_hook_free(h->d_points_mont); delete h; return rc; }
-  }
-  *out = h;
-  return MZK_OK;
-}
-void mzk_srs_free(mzk_srs* srs) {
-  if (!srs) return;
-  if (srs->d_points_mont) (void)ws_hook_free(srs->d_points_mont);
-  if (srs->d_direct) (void)ws_hook_free(srs->d_direct);
-  if (srs->d_tables_wide) (void)ws_hook_free(srs->d_tables_wide);
-  delete srs;
-}
 int mzk_kzg_commit_srs(const mzk_srs* srs, const uint64_t* coef, size_t n, uint64_t out_xy[8]) {
   MZK_ENTER();
   WsFrame ws("mzk_kzg_commit_srs");
@@ -1048,18 +948,18 @@ int mzk_kzg_commit_srs(const mzk_srs* srs, const uint64_t* coef, size_t n, uint6
   WsGuard wsg(s);
   void *d_s, *d_o;
   MZK_TRY(ws.get(WS_MISC_B, 256, &d_o));
-  if (msm_chunkable(n, srs->kind(), srs->n) && host_chunks_enabled()) {
+  if (msm_chunkable(n, srs->points()) && host_chunks_enabled()) {
     // a quarter of the coefficients first, the rest under its kernels (two pieces: every piece costs a segment combine of its own)
     static const int quarter_then_rest[2] = {64, 256};
     MsmChunk ch[8];
     MZK_TRY(ws.get(WS_MSM_SCALARS, n * 32, &d_s));
     const int K = host_chunk_plan(n, "MZK_HOST_CHUNKS_COMMIT", quarter_then_rest, 2, ch);
-    MZK_TRY(msm_host_chunked(coef, nullptr, d_s, nullptr, srs->d_points_mont, n, srs->kind(), srs->n, d_o, s, ch, K));
+    MZK_TRY(msm_host_chunked(coef, nullptr, d_s, nullptr, srs->points(), n, d_o, s, ch, K));
     MZK_TRY(d2h_sync(out_xy, d_o, 64, s));
     return MZK_OK;
   }
   MZK_TRY(stage_in(ws, WS_MSM_SCALARS, coef, n * 32, &d_s, s));
-  MZK_TRY(msm_dev_impl(d_s, srs->d_points_mont, n, srs->kind(), srs->n, d_o, false, s));
+  MZK_TRY(msm_dev_impl(d_s, srs->points(), n, d_o, false, s));
   MZK_TRY(d2h_sync(out_xy, d_o, 64, s));
   return MZK_OK;
 }
@@ -1070,7 +970,7 @@ int mzk_kzg_commit_srs_dev(const mzk_srs* srs, const void* d_coef, size_t n, voi
   if (!srs || !d_out || (!d_coef && n)) { set_error("commit_srs_dev: null pointer"); return MZK_E_ARG; }
   MZK_TRY(srs_check_ctx(srs));
   if (n > srs->n) { set_error("index out of bounds: the len is %zu but the index is %zu", srs->n, srs->n); return MZK_E_LENGTH; }
-  return msm_dev_impl(d_coef, srs->d_points_mont, n, srs->kind(), srs->n, d_out, out_partial != 0, (hipStream_t)stream);
+  return msm_dev_impl(d_coef, srs->points(), n, d_out, out_partial != 0, (hipStream_t)stream);
 }
 
 }  // extern "C" (the lane scheduler is a template)
@@ -1135,61 +1035,7 @@ extern "C" {
 // Short polynomials against narrow window tables: the whole batch as ONE bucket problem (msm_many_dev_impl) instead of one
 // commit per lane -- every kernel of it runs over (polynomial x bucket), one tail workgroup per polynomial.
 
-// Direct tables (every multiple of every window-table row) for the grid-batched commitments of short polynomials.
-int mzk_srs_build_direct(mzk_srs* srs, int window_bits, size_t max_bytes, void* stream) {
-  MZK_ENTER();
-  WsGuard wsg((hipStream_t)stream);
-  if (!srs) { set_error("srs_build_direct: null handle"); return MZK_E_ARG; }
-  MZK_TRY(srs_check_ctx(srs));
-  if (srs->n == 0) return MZK_OK;
-  if (srs->n > MSM_DIRECT_MAX_N) { set_error("srs_build_direct: direct tables are for SRS of at most %zu points (this one has %zu)", MSM_DIRECT_MAX_N, srs->n); return MZK_E_ARG; }
-  if (window_bits != 0 && (window_bits < 8 || window_bits > 12)) { set_error("srs_build_direct: window_bits must be 0 (by budget) or 8..12"); return MZK_E_ARG; }
-  size_t budget = max_bytes;
-  if (budget == 0) {                       // default: a quarter of what is free now, at most 4 GiB
-    size_t free_b = 0, total_b = 0;
-    MZK_HIP(hipMemGetInfo(&free_b, &total_b));
-    budget = free_b / 4;
-    if (budget > ((size_t)4 << 30)) budget = (size_t)4 << 30;
-  }
-  int c = window_bits;
-  if (c == 0) {                            // the widest windows (fewest additions per coefficient) that fit
-    for (c = 12; c > 8 && msm_direct_bytes(srs->n, c) > budget; c--) {}
-  }
-  const size_t bytes = msm_direct_bytes(srs->n, c);
-  if (bytes > budget) { set_error("srs_build_direct: %d-bit direct tables of %zu points take %zu bytes, the budget is %zu", c, srs->n, bytes, budget); return MZK_E_ARG; }
-  if (srs->d_direct && srs->direct_bits == c) return MZK_OK;
-  void* d = nullptr;
-  MZK_TRY(dev_alloc(&d, bytes, "srs_build_direct: direct tables"));
-  int rc = msm_build_direct(srs->d_points_mont, srs->n, c, d, (hipStream_t)stream);
-  if (rc == MZK_OK && hipStreamSynchronize((hipStream_t)stream) != hipSuccess) rc = MZK_E_HIP;
-  if (rc != MZK_OK) { (void)ws_hook_free(d); return rc; }
-  if (srs->d_direct) {
-    // the old tables may still be read by work enqueued on OTHER streams of the handle's device (the in-flight lanes of the batch
-    // entry points, a caller's second stream): wait for the whole device -- srs_check_ctx above made it the current one -- before freeing
-    (void)hipDeviceSynchronize();
-    (void)ws_hook_free(srs->d_direct);
-  }
-  srs->d_direct = d; srs->direct_bits = c; srs->direct_bytes = bytes;
-  return MZK_OK;
-}
-void mzk_srs_drop_direct(mzk_srs* srs) {
-  mzk::EntryGuard entry;
-  if (!entry.ok) return;          // another thread is inside a call that may be reading the tables
-  if (!srs || !srs->d_direct) return;
-  CtxScope sc(srs->ctx_index);    // the handle's own context and device, whatever is current: synchronise THAT device
-  if (!sc.ok) return;
-  (void)hipDeviceSynchronize();
-  (void)ws_hook_free(srs->d_direct);
-  srs->d_direct = nullptr; srs->direct_bits = 0; srs->direct_bytes = 0;
-}
-int mzk_srs_window_bits(const mzk_srs* srs) { return (srs && srs->has_tables) ? srs->window_bits : 0; }
-int mzk_srs_direct_bits(const mzk_srs* srs) { return (srs && srs->d_direct) ? srs->direct_bits : 0; }
 int mzk_msm_generic_window_bits(size_t n) { return mzk::msm_generic_window_bits(n); }
-size_t mzk_srs_table_bytes(const mzk_srs* srs) {
-  if (!srs) return 0;
-  return srs->n * 64 * srs->table_rows() + srs->direct_bytes + srs->wide_bytes;
-}
-
 // The _many forms take the grid pass whenever the handle can (any count >= 1); the _batch forms from MANY_MIN_COUNT polynomials
 // on (two or three are served as well by the lanes: the pass has ~10 launches and an 80-us tail of its own).
 constexpr size_t MANY_MIN_COUNT = 4;
@@ -1205,7 +1051,7 @@ static int commit_batch_route(const mzk_srs* srs, const void* d_coefs, size_t n,
   const char* coefs = (const char*)d_coefs;
   char* outs = (char*)d_out_xy;
   return run_in_flight(count, max_in_flight, stream, [&](size_t i, hipStream_t ls) {
-    return msm_dev_impl(coefs + i * n * 32, srs->d_points_mont, n, srs->kind(), srs->n, outs + i * 64, false, ls);
+    return msm_dev_impl(coefs + i * n * 32, srs->points(), n, outs + i * 64, false, ls);
   });
 }
 // open_kzg (kzg.rs:61-72) of `count` polynomials, polynomial i at the point us[i]: y_i = f_i(u_i) and the witness
@@ -1223,7 +1069,7 @@ static int open_batch_route(const mzk_srs* srs, const void* d_coefs, size_t n, s
   const char* coefs = (const char*)d_coefs;
   char *ys = (char*)d_ys, *ws = (char*)d_ws_xy;
   return run_in_flight(count, max_in_flight, stream, [&](size_t i, hipStream_t ls) {
-    return kzg_open_dev(coefs + i * n * 32, n, us_host + 4 * i, srs->d_points_mont, srs->kind(), srs->n, ys + i * 32, ws + i * 64, nullptr, ls);
+    return kzg_open_dev(coefs + i * n * 32, n, us_host + 4 * i, srs->points(), ys + i * 32, ws + i * 64, nullptr, ls);
   });
 }
 int mzk_kzg_commit_srs_many_dev(const mzk_srs* srs, const void* d_coefs, size_t n, size_t count, void* d_out_xy, void* stream) {
@@ -1289,7 +1135,7 @@ int mzk_kzg_open_srs_dev(const mzk_srs* srs, const void* d_coef, size_t n, const
   MZK_TRY(srs_check_ctx(srs));
   if (n > 1 && n - 1 > srs->n) { set_error("index out of bounds: the len is %zu but the index is %zu", srs->n, srs->n); return MZK_E_LENGTH; }
   if (!d_w_xy) { set_error("kzg_open: null pointer"); return MZK_E_ARG; }
-  return kzg_open_dev(d_coef, n, u_host, srs->d_points_mont, srs->kind(), srs->n, d_y, d_w_xy, nullptr, (hipStream_t)stream);
+  return kzg_open_dev(d_coef, n, u_host, srs->points(), d_y, d_w_xy, nullptr, (hipStream_t)stream);
 }
 int mzk_kzg_setup_g1_dev(const uint64_t alpha_host[4], const uint64_t g1_xy_host[8], size_t max_d, void* d_powers_xy, void* stream) {
   MZK_ENTER();
@@ -1306,14 +1152,14 @@ int mzk_kzg_open_quotient_dev(const void* d_coef, size_t n, const uint64_t u_hos
   MZK_ENTER();
   WsGuard wsg((hipStream_t)stream);
   if (!d_q && n > 1) { set_error("open_quotient: null pointer"); return MZK_E_ARG; }
-  return kzg_open_dev(d_coef, n, u_host, nullptr, MSM_PTS_PLAIN, 0, d_y, nullptr, d_q, (hipStream_t)stream);
+  return kzg_open_dev(d_coef, n, u_host, MsmPoints::plain(nullptr), d_y, nullptr, d_q, (hipStream_t)stream);
 }
 int mzk_kzg_open_slice_value_dev(const void* d_coef_slice, size_t len, const uint64_t u_host[4], void* d_value, void* stream) {
   MZK_ENTER();
   WsGuard wsg((hipStream_t)stream);
   if (!d_value || !u_host || (!d_coef_slice && len)) { set_error("open_slice_value: null pointer"); return MZK_E_ARG; }
   // the slice's own recurrence with nothing behind it: b_lo = the slice as a polynomial, evaluated at u (kzg_open_dev's y)
-  return kzg_open_dev(d_coef_slice, len, u_host, nullptr, MSM_PTS_PLAIN, 0, d_value, nullptr, nullptr, (hipStream_t)stream);
+  return kzg_open_dev(d_coef_slice, len, u_host, MsmPoints::plain(nullptr), d_value, nullptr, nullptr, (hipStream_t)stream);
 }
 int mzk_kzg_open_slice_quotient_dev(const void* d_coef_slice, size_t len, const uint64_t u_host[4], const uint64_t carry_in[4], void* d_q_slice,
                                     void* stream) {
@@ -1330,27 +1176,6 @@ int mzk_kzg_open_slice_quotient_dev(const void* d_coef_slice, size_t len, const 
   const size_t one = 1;
   return synth_div_dev(&job, &one, 1, s);
 }
-int mzk_srs_from_device(const void* d_powers_xy, size_t n, mzk_srs** out, void* stream) {
-  return mzk_srs_from_device_ex(d_powers_xy, n, 1, out, stream);
-}
-int mzk_srs_from_device_ex(const void* d_powers_xy, size_t n, int with_tables, mzk_srs** out, void* stream) {
-  MZK_ENTER();
-  WsGuard wsg((hipStream_t)stream);
-  if (!out || (!d_powers_xy && n)) { set_error("srs_from_device: null pointer"); return MZK_E_ARG; }
-  hipStream_t s = (hipStream_t)stream;
-  if (with_tables < 0 || (with_tables > 1 && (with_tables < 8 || with_tables > 22))) { set_error("srs_from_device: with_tables must be 0, 1 or a window width 8..22"); return MZK_E_ARG; }
-  mzk_srs* h = new mzk_srs{nullptr, n, false, 0, ctx().index};
-  int rc = srs_alloc_layout(h, with_tables);
-  if (rc != MZK_OK) { delete h; return rc; }
-  if (n) {
-    rc = srs_fill(h, d_powers_xy, s);
-    if (rc == MZK_OK && hipStreamSynchronize(s) != hipSuccess) rc = MZK_E_HIP;
-    if (rc != MZK_OK) { (void)ws_hook_free(h->d_points_mont); delete h; return rc; }
-  }
-  *out = h;
-  return MZK_OK;
-}
-
 int mzk_fri_fold_dev(int field_id, const void* d_codeword, size_t n, const uint64_t* alpha_host, const uint64_t* offset_host,
                      const uint64_t* omega_host, void* d_out, void* stream) {
   MZK_ENTER();
@@ -1387,7 +1212,7 @@ int mzk_kzg_batch_open(const uint64_t* coef, size_t n, const uint64_t* us, size_
   MZK_TRY(stage_in(ws, WS_MSM_SCALARS, coef, n * 32, &d_c, s));
   MZK_TRY(stage_in(ws, WS_NTT_IO_A, powers_xy, nq * 64, &d_p, s));
   MZK_TRY(ws.get(WS_NTT_IO_B, 64 + k * 32 + 64, &d_o));
-  MZK_TRY(kzg_batch_open_dev(d_c, n, us, k, d_p, MSM_PTS_PLAIN, 0, (char*)d_o + 64, d_o, s));
+  MZK_TRY(kzg_batch_open_dev(d_c, n, us, k, MsmPoints::plain(d_p), (char*)d_o + 64, d_o, s));
   std::vector<uint64_t> tmp(8 + 4 * k + 8);
   MZK_TRY(d2h_sync(tmp.data(), d_o, 64 + k * 32, s));
   memcpy(w_xy, tmp.data(), 64);
@@ -1431,7 +1256,7 @@ int mzk_kzg_open(const uint64_t* coef, size_t n, const uint64_t u[4], const uint
   MZK_TRY(stage_in(ws, WS_MSM_SCALARS, coef, n * 32, &d_c, s));
   MZK_TRY(stage_in(ws, WS_NTT_IO_A, powers_xy, (n > 1 ? n - 1 : 0) * 64, &d_p, s));
   MZK_TRY(ws.get(WS_NTT_IO_B, 256, &d_o));
-  MZK_TRY(kzg_open_dev(d_c, n, u, d_p, MSM_PTS_PLAIN, 0, d_o, (char*)d_o + 64, nullptr, s));
+  MZK_TRY(kzg_open_dev(d_c, n, u, MsmPoints::plain(d_p), d_o, (char*)d_o + 64, nullptr, s));
   uint64_t tmp[16];
   MZK_TRY(d2h_sync(tmp, d_o, 128, s));
   memcpy(y, tmp, 32);

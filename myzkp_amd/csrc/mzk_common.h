@@ -13,6 +13,7 @@
 #include "mzk_field.h"
 #include "mzk_hostfield.h"
 #include "mzk_msm_plan.h"
+#include "mzk_srs_plan.h"
 #include "mzk_ws.h"
 
 namespace mzk {
@@ -31,8 +32,6 @@ static inline constexpr const char* tune_str(const char*) { return nullptr; }
 
 // ---- error plumbing ------------------------------------------------------------------------------
 void set_error(const char* fmt, ...);
-void clear_error();                            // a refused allocation that the call then does without leaves no message behind
-size_t table_budget_bytes();                   // mzk_set_table_budget (0 = no limit)
 int hip_fail(hipError_t e, const char* what, const char* file, int line);
 #define MZK_HIP(x)                                                        \
   do {                                                                    \
@@ -226,35 +225,9 @@ int fri_fold_consts(int fid, const uint64_t* offset, const uint64_t* omega, FriF
 void fri_fold_consts_square(int fid, FriFoldConsts* fc);
 int fri_fold_dev_consts(int fid, const void* d_cw, size_t n, const uint64_t* alpha, const FriFoldConsts& fc, void* d_out, hipStream_t s);
 int fri_fold_dev_alpha(int fid, const void* d_cw, size_t n, const uint64_t* d_alpha, const FriFoldConsts& fc, void* d_out, hipStream_t s);
-int kzg_batch_open_dev(const void* d_coef, size_t n, const uint64_t* us_host, size_t k, const void* d_points, int point_kind,
-                       size_t table_stride, void* d_ys, void* d_w_xy, hipStream_t s);
+int kzg_batch_open_dev(const void* d_coef, size_t n, const uint64_t* us_host, size_t k, MsmPoints pts, void* d_ys, void* d_w_xy, hipStream_t s);
 
-// point_kind, window tables: mzk_msm_plan.h.  Width by SRS size, from the sweep of round 3 (tools/timing/window_sweep.py,
-// profiles/r03b_window_sweep.txt; one box, ms per commit at c = 16 / 17 / 19 / 20):
-//   2^17  0.54 / 0.57 / 0.89 / 0.80      2^20  1.67 / 1.63 / 2.24 / 1.78      2^22   6.46 /  6.12 /  6.98 / 5.85
-//   2^18  0.73 / 0.74 / 1.00 / 0.93      2^21  3.28 / 2.94 / 3.83 / 3.20      2^24  24.38 / 23.00 / 25.01 /  --
-//   2^19  1.01 / 0.99 / 1.37 / 1.17
-// 17 bits = 15 tables (one accumulation fewer per pair, one table less to hold) with 2^16 buckets wins from 2^19 points on;
-// wider windows lose what they save in the accumulation to the sort and to the bucket reduction (2^19 buckets at c = 20:
-// reduce 0.42 instead of 0.25 ms) except at exactly 2^22.  Widths whose top window is nearly empty are pathological for the
-// merged layout: 254 = 14 * 18 + 2 = 18 * 14 + 2, so at c = 18 (and 14, 21) a quarter of all top-window digits land in each of
-// four buckets, 4096 segment partials apiece at 2^20 -- 0.45 ms of heavy-bucket combine at every size.
-// Other widths stay selectable through mzk_srs_from_device_ex for tuning and tests (BASELINE configs[2] names 16 bits:
-// bench.py reports that width as its own leg).
-// Small SRS (the reference's actual sizes: a few thousand powers at most) take the short paths of mzk_msm.hip (two launches:
-// k_small_accumulate_scan + the tail); with tables there is no window Horner either (its ~120 serial doublings are the latency
-// floor of a small generic MSM), so they get narrow windows: 8 bits = 32 tables x 128 buckets up to 1024 points, 10 bits =
-// 26 tables x 512 buckets up to 2^14 (where the sortless path still beats the general pipeline: profiles/r03v_*), then 16 and,
-// from 2^19 points on, 17 bits, from 2^22 on 20 bits through the general pipeline (tools/timing/window_sweep.py).
-// Round 4 (profiles/round4_window_sweep.txt, tools/timing/window_sweep.py; one box, c = 16 / 17 / 20 / 22):
-//   2^22   6.09 /  5.75 /  5.62 / 12.97      2^23  11.97 / 11.27 / 10.89 / 20.26      2^24  23.56 / 22.05 / 20.89 / 30.18
-// 20 bits (13 tables, 2^19 buckets) win from 2^22 points on: two accumulations fewer per pair outweigh the wider sort and the
-// longer reduction; 22 bits (12 tables) lose everything to the sort (2^21 buckets: 8192 per coarse bin, past the staged fine
-// scatter) and their accumulate is no faster (a longer bucket search per segment).
-static inline int msm_srs_window_bits(size_t n) {
-  return n <= 1024 ? 8 : (n <= ((size_t)1 << 14) ? 10 : (n < ((size_t)1 << 19) ? 16 : (n < ((size_t)1 << 22) ? 17 : 20)));
-}
-static inline bool msm_srs_default_tables(size_t n) { return n > 0; }
+// point_kind, window tables: mzk_msm_plan.h; MsmPoints, the one argument for a point set, and the width by SRS size: mzk_srs_plan.h.
 // One MSM computed in CHUNKS of consecutive pairs (msm_chunked_impl): every chunk is sorted and accumulated on its own -- as soon as
 // ITS scalars (and points) are on the device -- into its own bucket array, the chunks' bucket arrays are summed and reduced once.
 // msm_dev_impl in chunk mode (cc != null) takes the chunk's scalars, the WHOLE point array, and stops after the segment combine.
@@ -268,11 +241,11 @@ struct MsmChunkCtx {
   size_t n_alloc;        // the largest chunk: size of the per-chunk buffers (the same in every call, so that no workspace slot is regrown)
 };
 struct MsmChunk { const void* d_scalars; size_t i0, n; hipEvent_t ready; };    // ready (or null): recorded when the chunk's inputs are on the device
-int msm_chunked_impl(const MsmChunk* chunks, int K, const void* d_points, size_t n_total, int point_kind, size_t table_stride, void* d_out,
-                     bool out_partial_xyzz, hipStream_t s, const std::function<int(int)>* before_chunk = nullptr);
-bool msm_chunkable(size_t n_total, int point_kind, size_t table_stride);      // mzk_msm_plan.h, with the library's MsmKnobs
-int msm_dev_impl(const void* d_scalars, const void* d_points, size_t n, int point_kind, size_t table_stride, void* d_out,
-                 bool out_partial_xyzz, hipStream_t s, const std::function<int()>* points_ready = nullptr, const MsmChunkCtx* cc = nullptr);
+int msm_chunked_impl(const MsmChunk* chunks, int K, MsmPoints pts, size_t n_total, void* d_out, bool out_partial_xyzz, hipStream_t s,
+                     const std::function<int(int)>* before_chunk = nullptr);
+bool msm_chunkable(size_t n_total, MsmPoints pts);      // mzk_msm_plan.h, with the library's MsmKnobs
+int msm_dev_impl(const void* d_scalars, MsmPoints pts, size_t n, void* d_out, bool out_partial_xyzz, hipStream_t s,
+                 const std::function<int()>* points_ready = nullptr, const MsmChunkCtx* cc = nullptr);
 
 // Grid-batched form for many short polynomials against one set of narrow window tables (mzk_msm.hip, mzk_kzg.hip)
 bool msm_many_supported(int window_bits);
@@ -280,7 +253,6 @@ int msm_generic_window_bits(size_t n);        // window width of the generic (GL
 int msm_many_dev_impl(const void* d_scalars, size_t n, size_t stride_elems, size_t count, const void* d_tables, int c, size_t table_stride, void* d_out,
                       hipStream_t s);
 constexpr size_t MSM_DIRECT_MAX_N = (size_t)1 << 14;
-size_t msm_direct_bytes(size_t n, int c);
 int msm_build_direct(const void* d_points_mont, size_t n, int c, void* d_direct, hipStream_t s);
 int msm_direct_many_dev_impl(const void* d_scalars, size_t n, size_t stride_elems, size_t count, const void* d_direct, int c, size_t table_stride, void* d_out,
                              hipStream_t s);
@@ -303,8 +275,7 @@ int selftest_g1_probe_check(int op, int form, int* a_words, int* b_words);
 int selftest_g1_probe_impl(int op, int form, size_t n, const uint32_t* a_host, const uint32_t* b_host, const uint8_t* neg_host, uint32_t* out_host,
                            hipStream_t s);
 int kzg_setup_g1_dev(const uint64_t* alpha_host, const uint64_t* g1_host, size_t first, size_t count, void* d_powers_xy, hipStream_t s);
-int kzg_open_dev(const void* d_coef, size_t n, const uint64_t* u_host, const void* d_points, int point_kind, size_t table_stride,
-                 void* d_y, void* d_w_xy, void* d_q, hipStream_t s);
+int kzg_open_dev(const void* d_coef, size_t n, const uint64_t* u_host, MsmPoints pts, void* d_y, void* d_w_xy, void* d_q, hipStream_t s);
 // Synthetic division by (X - u) (mzk_kzg.hip): b_len = *end (0 when end is null),
 // b_t = src[t] + u b_{t+1}; y = b_0, q = b_1 .. b_{len-1}, or b_1 .. b_len with an end.  u and end are canonical host values;
 // y and q are device outputs or null; a job of length 0 writes nothing.
@@ -324,42 +295,17 @@ int poly_div_roots_dev_impl(int fid, const void* d_polys, size_t stride, const s
 
 }  // namespace mzk
 
-// Device-resident PublicKeyKZG.powers_1 (kzg.rs:8-11)
-struct mzk_srs {
-  void* d_points_mont;   // msm_table_windows(window_bits) x n window tables when has_tables, else n prepared points + their n phi images
-  size_t n;
-  bool has_tables;
-  int window_bits;
-  int ctx_index;         // the context (device) that owns d_points_mont
-  // Bucket sets of the table layout (1 = every window shares one set: the default).  With k sets the handle holds only every
-  // k-th window table, T[q][i] = 2^(c k q) P_i: window w = k q + r adds T[q][i] into bucket set r, and the result is
-  // sum_r 2^(c r) B_r (k - 1 times c doublings at the very end).  1/k of the table memory for the same additions -- what a
-  // handle degrades to when the full tables do not fit the budget / the device (srs_alloc_layout).
-  int sets = 1;
-  // optional (mzk_srs_build_direct): every multiple a window digit can ask for, D[(w n + i) 2^(direct_bits-1) + m] = (m + 1) 2^(direct_bits w) P_i,
-  // affine Montgomery -- commitments of many short polynomials then need no buckets at all (msm_many_srs)
-  void* d_direct = nullptr;
-  int direct_bits = 0;
-  size_t direct_bytes = 0;
-  // optional, built by the first grid-batched pass that wants them (msm_many_srs): a SECOND set of window tables, wider than the
-  // handle's own.  A handle of <= 2^14 points keeps 8- / 10-bit tables for the sortless single commit; a batch of LONG polynomials
-  // (>= 2^13 coefficients) is 20 % faster over 12-bit ones (shorter accumulate, and a bucket's partials are a chain a quarter as
-  // long in the segment combine: profiles/round5_many_commit_widths.txt).  22 x n points: 22 MiB at 2^14.
-  mutable void* d_tables_wide = nullptr;
-  mutable int wide_bits = 0;
-  mutable size_t wide_bytes = 0;
-  int kind() const { return has_tables ? (mzk::MSM_PTS_TABLES | (window_bits << 8) | (sets << 16)) : (int)mzk::MSM_PTS_MONT; }
-  size_t table_rows() const { return has_tables ? (size_t)mzk::msm_table_rows(window_bits, sets) : 2; }   // no tables: P_i, then phi(P_i) (GLV layout)
-};
-
+// ---- against an SRS handle (struct mzk_srs: mzk_srs.h) ------------------------------------------------------------------------------
 namespace mzk {
 // `count` commitments of n coefficients each (polynomial j at d_scalars + j * stride_elems * 32 bytes) against one handle, as ONE
 // pass: over the direct tables when the handle has them, over its narrow window tables otherwise (srs_many_capable).
 // shift != 0: against the points [shift, shift + n) of the handle (every layout keeps point i of a table at row offset i, so the
-// tables are entered `shift` rows further on with the row stride unchanged); shift + n <= srs->n.
-bool srs_many_capable(const mzk_srs* srs);
+// tables are entered `shift` rows further on with the row stride unchanged); shift + n <= srs->n.  mzk_srs.hip.
 int msm_many_srs(const mzk_srs* srs, const void* d_scalars, size_t n, size_t stride_elems, size_t count, void* d_out, hipStream_t s,
                  size_t shift = 0);
+// The one body of mzk_srs_upload, mzk_srs_from_device_ex and mzk_srs_load's rebuild: a handle of the layout that fits (srs_new), filled
+// from n affine canonical points in host memory (host_xy, staged through WS_MISC_A) or on the device (d_xy); the stream is idle on return.
+int srs_from_points(const uint64_t* host_xy, const void* d_xy, size_t n, int with_tables, mzk_srs** out, hipStream_t s);
 bool kzg_open_many_supported(const mzk_srs* srs, size_t n);
 int kzg_open_many_dev(const mzk_srs* srs, const void* d_coefs, size_t n, size_t count, const uint64_t* us_host, void* d_ys, void* d_ws_xy, hipStream_t s);
 }  // namespace mzk

@@ -16,6 +16,7 @@
 // The MSMs run on the SRS handle's tables (mzk_msm.hip); the degree-bound MSMs of prove_degree_bound (kzg.rs:121-134) on the
 // handle entered max_d - d rows further on (see gemini_open_impl).
 #include "mzk_common.h"
+#include "mzk_srs.h"
 #include "mzk_elem.h"
 
 namespace mzk {
@@ -264,12 +265,12 @@ static int gm_msms(const mzk_srs* srs, const GmMsm* items, int count, int i0, bo
   u32* plain = nullptr;
   if (plain_max) MZK_TRY(ws.get(WS_NTT_TMP, plain_max * 64, (void**)&plain));
   for (int k = 0; k < single_to; k++) {
-    const char* pts = (const char*)srs->d_points_mont + items[k].shift * 64;
+    const MsmPoints pts = srs->points(items[k].shift);
     if (plain && items[k].len <= plain_max && items[k].len > 0) {
-      MZK_TRY(msm_points_to_plain(pts, items[k].len, plain, s));
-      MZK_TRY(msm_dev_impl(items[k].src, plain, items[k].len, MSM_PTS_PLAIN, 0, d_out + 16 * k, false, s));
+      MZK_TRY(msm_points_to_plain(pts.d, items[k].len, plain, s));
+      MZK_TRY(msm_dev_impl(items[k].src, MsmPoints::plain(plain), items[k].len, d_out + 16 * k, false, s));
     } else {
-      MZK_TRY(msm_dev_impl(items[k].src, pts, items[k].len, srs->kind(), srs->n, d_out + 16 * k, false, s));
+      MZK_TRY(msm_dev_impl(items[k].src, pts, items[k].len, d_out + 16 * k, false, s));
     }
   }
   if (!many) return MZK_OK;
@@ -294,11 +295,7 @@ static int gm_msms(const mzk_srs* srs, const GmMsm* items, int count, int i0, bo
 
 static int gm_srs_ok(const mzk_srs* srs, size_t n, int* el, const char* who) {
   MZK_TRY(gm_check_n(n, el, who));
-  if (srs->ctx_index != ctx().index && mzk_ctx_device(srs->ctx_index) != ctx().device) {
-    set_error("SRS handle lives on context %d, the current context %d drives device %d (mzk_ctx_select)", srs->ctx_index, ctx().index, ctx().device);
-    return MZK_E_ARG;
-  }
-  return MZK_OK;
+  return srs_check_ctx(srs);
 }
 static inline size_t gm_level_off(size_t n, int i) { return 2 * n - (n >> i) * 2; }     // sum_{j < i} n / 2^j
 

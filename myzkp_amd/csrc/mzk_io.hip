@@ -16,11 +16,11 @@
 #include <stdio.h>
 #include <vector>
 #include "mzk_common.h"
+#include "mzk_srs.h"
 
 using namespace mzk;
 
 namespace mzk {
-int srs_alloc_layout(mzk_srs* h, int with_tables);     // mzk_api.hip
 struct SrsFileHeader {
   char magic[8];          // "MZKSRS\0\0"
   uint32_t format;        // 2 (1 = older dumps without tables_fnv1a)
@@ -57,7 +57,7 @@ int mzk_srs_save(const mzk_srs* srs, const char* path, int with_tables) {
   MZK_ENTER();
   WsFrame ws("mzk_srs_save");
   if (!srs || !path) { set_error("srs_save: null pointer"); return MZK_E_ARG; }
-  if (srs->ctx_index != ctx().index) { set_error("SRS handle lives on context %d, the current context is %d", srs->ctx_index, ctx().index); return MZK_E_ARG; }
+  MZK_TRY(srs_check_ctx(srs, true));
   hipStream_t s = ctx().stream;
   WsGuard wsg(s);
   FileCloser fc{fopen(path, "wb")};
@@ -67,8 +67,8 @@ int mzk_srs_save(const mzk_srs* srs, const char* path, int with_tables) {
   memset(&h, 0, sizeof h);
   memcpy(h.magic, SRS_MAGIC, 8);
   h.format = 2; h.flags = tables ? 1u : 0u; h.n = srs->n;
-  h.window_bits = tables ? (uint32_t)srs->window_bits : 0u;
-  h.table_rows = tables ? (uint32_t)(msm_table_windows(srs->window_bits) - 1) : 0u;
+  h.window_bits = tables ? (uint32_t)srs->own.bits : 0u;
+  h.table_rows = tables ? (uint32_t)(msm_table_windows(srs->own.bits) - 1) : 0u;
   if (fwrite(&h, sizeof h, 1, fc.f) != 1) { set_error("srs_save: write failed"); return MZK_E_IO; }
   std::vector<uint8_t> host(IO_CHUNK_POINTS * 64);
   void* d_plain;
@@ -76,7 +76,7 @@ int mzk_srs_save(const mzk_srs* srs, const char* path, int with_tables) {
   uint64_t hash = 0xcbf29ce484222325ULL;
   for (size_t at = 0; at < srs->n; at += IO_CHUNK_POINTS) {
     const size_t m = srs->n - at < IO_CHUNK_POINTS ? srs->n - at : IO_CHUNK_POINTS;
-    MZK_TRY(msm_points_to_plain((const uint8_t*)srs->d_points_mont + at * 64, m, d_plain, s));    // row 0 / the prepared points
+    MZK_TRY(msm_points_to_plain(srs->own.mem.as<uint8_t>() + at * 64, m, d_plain, s));    // row 0 / the prepared points
     MZK_HIP(hipMemcpyAsync(host.data(), d_plain, m * 64, hipMemcpyDeviceToHost, s));
     MZK_HIP(hipStreamSynchronize(s));
     hash = fnv1a(hash, host.data(), m * 64);
@@ -86,7 +86,7 @@ int mzk_srs_save(const mzk_srs* srs, const char* path, int with_tables) {
   for (uint32_t row = 1; tables && row <= h.table_rows; row++) {
     for (size_t at = 0; at < srs->n; at += IO_CHUNK_POINTS) {
       const size_t m = srs->n - at < IO_CHUNK_POINTS ? srs->n - at : IO_CHUNK_POINTS;
-      MZK_HIP(hipMemcpyAsync(host.data(), (const uint8_t*)srs->d_points_mont + ((size_t)row * srs->n + at) * 64, m * 64, hipMemcpyDeviceToHost, s));
+      MZK_HIP(hipMemcpyAsync(host.data(), srs->own.mem.as<uint8_t>() + ((size_t)row * srs->n + at) * 64, m * 64, hipMemcpyDeviceToHost, s));
       MZK_HIP(hipStreamSynchronize(s));
       thash = fnv1a_words(thash, host.data(), m * 64);
       if (fwrite(host.data(), 64, m, fc.f) != m) { set_error("srs_save: write failed"); return MZK_E_IO; }
@@ -125,35 +125,31 @@ int mzk_srs_load(const char* path, int with_tables, mzk_srs** out) {
     MZK_HIP(hipStreamSynchronize(s));     // `host` is reused
   }
   if (hash != h.points_fnv1a) { set_error("srs_load: checksum mismatch in %s (corrupted or truncated)", path); return MZK_E_IO; }
-  const int want_bits = with_tables > 1 ? with_tables : msm_srs_window_bits(n);
-  const bool use_stored = with_tables && h.format >= 2 && (h.flags & 1u) && (int)h.window_bits == want_bits &&
-                          h.table_rows == (uint32_t)(msm_table_windows(want_bits) - 1) && n > 0;
-  if (!use_stored) return mzk_srs_from_device_ex(d_plain, n, with_tables, out, s);
   WsGuard wsg(s);
-  mzk_srs* hd = new mzk_srs{nullptr, n, false, 0, ctx().index};
-  const size_t rows = (size_t)h.table_rows + 1;
-  int rc = srs_alloc_layout(hd, with_tables);
-  if (rc == MZK_OK && !(hd->has_tables && hd->sets == 1 && hd->window_bits == want_bits)) {
+  SrsOwner hd;
+  if (srs_use_stored(with_tables, h.format, h.flags, h.window_bits, h.table_rows, n)) {
+    MZK_TRY(srs_new(n, with_tables, &hd));
     // the stored tables do not fit the budget / the device as they are: take whatever layout does fit, built from the points
-    mzk_srs_free(hd);
-    return mzk_srs_from_device_ex(d_plain, n, with_tables, out, s);
+    if (!(hd->has_tables && hd->sets == 1 && (uint32_t)hd->own.bits == h.window_bits)) hd.reset();
   }
-  if (rc != MZK_OK) { delete hd; return rc; }
+  if (!hd) return srs_from_points(nullptr, d_plain, n, with_tables, out, s);
+  const size_t rows = (size_t)h.table_rows + 1;
+  uint8_t* const d_own = hd->own.mem.as<uint8_t>();
+  int rc = msm_prepare_points(d_plain, n, d_own, nullptr, s);      // row 0 = the points, Montgomery form
   uint64_t thash = hash;
-  if (rc == MZK_OK) rc = msm_prepare_points(d_plain, n, hd->d_points_mont, nullptr, s);      // row 0 = the points, Montgomery form
   for (size_t row = 1; rc == MZK_OK && row < rows; row++) {
     for (size_t at = 0; rc == MZK_OK && at < n; at += IO_CHUNK_POINTS) {
       const size_t m = n - at < IO_CHUNK_POINTS ? n - at : IO_CHUNK_POINTS;
       if (fread(host.data(), 64, m, fc.f) != m) { set_error("srs_load: %s is truncated (tables)", path); rc = MZK_E_IO; break; }
       thash = fnv1a_words(thash, host.data(), m * 64);
-      if (hipMemcpyAsync((uint8_t*)hd->d_points_mont + (row * n + at) * 64, host.data(), m * 64, hipMemcpyHostToDevice, s) != hipSuccess ||
+      if (hipMemcpyAsync(d_own + (row * n + at) * 64, host.data(), m * 64, hipMemcpyHostToDevice, s) != hipSuccess ||
           hipStreamSynchronize(s) != hipSuccess) { set_error("srs_load: copy failed"); rc = MZK_E_HIP; }
     }
   }
   if (rc == MZK_OK && hipStreamSynchronize(s) != hipSuccess) rc = MZK_E_HIP;
   if (rc == MZK_OK && thash != h.tables_fnv1a) { set_error("srs_load: checksum mismatch in the window tables of %s (corrupted or stale)", path); rc = MZK_E_IO; }
-  if (rc != MZK_OK) { mzk_srs_free(hd); return rc; }
-  *out = hd;
+  if (rc != MZK_OK) return rc;
+  *out = hd.release();
   return MZK_OK;
 }
 
@@ -163,14 +159,14 @@ int mzk_srs_download(const mzk_srs* srs, uint64_t* powers_xy, size_t cap_points)
   WsFrame ws("mzk_srs_download");
   if (!srs || (!powers_xy && srs->n)) { set_error("srs_download: null pointer"); return MZK_E_ARG; }
   if (cap_points < srs->n) { set_error("srs_download: buffer holds %zu points, the SRS has %zu", cap_points, srs->n); return MZK_E_LENGTH; }
-  if (srs->ctx_index != ctx().index) { set_error("SRS handle lives on context %d, the current context is %d", srs->ctx_index, ctx().index); return MZK_E_ARG; }
+  MZK_TRY(srs_check_ctx(srs, true));
   hipStream_t s = ctx().stream;
   WsGuard wsg(s);
   void* d_plain;
   MZK_TRY(ws.get(WS_MISC_A, IO_CHUNK_POINTS * 64, &d_plain));
   for (size_t at = 0; at < srs->n; at += IO_CHUNK_POINTS) {
     const size_t m = srs->n - at < IO_CHUNK_POINTS ? srs->n - at : IO_CHUNK_POINTS;
-    MZK_TRY(msm_points_to_plain((const uint8_t*)srs->d_points_mont + at * 64, m, d_plain, s));
+    MZK_TRY(msm_points_to_plain(srs->own.mem.as<uint8_t>() + at * 64, m, d_plain, s));
     MZK_HIP(hipMemcpyAsync(powers_xy + at * 8, d_plain, m * 64, hipMemcpyDeviceToHost, s));
     MZK_HIP(hipStreamSynchronize(s));
   }

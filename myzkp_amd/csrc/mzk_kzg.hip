@@ -11,6 +11,7 @@
 // the chunk values with base u^K), so it is parallel at every level.  The witness MSM then runs in
 // mzk_msm.hip on q.
 #include "mzk_common.h"
+#include "mzk_srs.h"
 #include "mzk_elem.h"
 #include "mzk_ec.h"
 
@@ -545,8 +546,7 @@ int poly_div_roots_dev_impl(int fid, const void* d_polys, size_t stride, const s
 // batch_open_kzg (kzg.rs:74-88).  y_i = f(u_i) is b_0 of the division of f by (X - u_i).  The quotient of f by prod (X - u_i) --
 // which equals (f - I)/Z because I = f mod Z -- is k successive divisions (each drops the remainder b_0): one round of k
 // evaluations, then one round per quotient.  d_ys: k * 8 words, d_w_xy: 16 words.
-int kzg_batch_open_dev(const void* d_coef, size_t n, const uint64_t* us_host, size_t k, const void* d_points, int point_kind,
-                       size_t table_stride, void* d_ys, void* d_w_xy, hipStream_t s) {
+int kzg_batch_open_dev(const void* d_coef, size_t n, const uint64_t* us_host, size_t k, MsmPoints pts, void* d_ys, void* d_w_xy, hipStream_t s) {
   WsFrame ws("kzg_batch_open_dev");
   if (!d_w_xy || (!d_coef && n) || ((!us_host || !d_ys) && k)) { set_error("batch_open: null pointer"); return MZK_E_ARG; }
   const HostField* fr = host_field(MZK_FIELD_FR);
@@ -572,15 +572,14 @@ int kzg_batch_open_dev(const void* d_coef, size_t n, const uint64_t* us_host, si
     cur = dst;
   }
   MZK_TRY(synth_div_dev(jobs.data(), rounds.data(), (int)rounds.size(), s));
-  return msm_dev_impl(cur, d_points, len, point_kind, table_stride, d_w_xy, false, s);
+  return msm_dev_impl(cur, pts, len, d_w_xy, false, s);
 }
 
 // open_kzg (kzg.rs:61-72) as one division: y = f(u) into d_y (8 words); the quotient q = b_1 .. b_{n-1} into d_q when given; the
 // witness w = MSM(q, points) into d_w_xy (16 words) when given, q then in workspace unless d_q holds it.
-int kzg_open_dev(const void* d_coef, size_t n, const uint64_t* u_host, const void* d_points, int point_kind, size_t table_stride,
-                 void* d_y, void* d_w_xy, void* d_q, hipStream_t s) {
+int kzg_open_dev(const void* d_coef, size_t n, const uint64_t* u_host, MsmPoints pts, void* d_y, void* d_w_xy, void* d_q, hipStream_t s) {
   WsFrame ws("kzg_open_dev");
-  if (!u_host || !d_y || (!d_coef && n) || (d_w_xy && !d_points && n > 1)) { set_error("kzg_open: null pointer"); return MZK_E_ARG; }
+  if (!u_host || !d_y || (!d_coef && n) || (d_w_xy && !pts.d && n > 1)) { set_error("kzg_open: null pointer"); return MZK_E_ARG; }
   if (!h_is_canonical(host_field(MZK_FIELD_FR), u_host)) { set_error("kzg_open: u not canonical"); return MZK_E_RANGE; }
   if (n == 0) {  // empty polynomial: y = 0, quotient empty -> infinity
     MZK_HIP(hipMemsetAsync(d_y, 0, 32, s));
@@ -592,7 +591,7 @@ int kzg_open_dev(const void* d_coef, size_t n, const uint64_t* u_host, const voi
   const size_t one = 1;
   MZK_TRY(synth_div_dev(&job, &one, 1, s));
   if (!d_w_xy) return MZK_OK;
-  return msm_dev_impl(d_q, d_points, n - 1, point_kind, table_stride, d_w_xy, false, s);   // w = MSM(q, powers)  (kzg.rs:70)
+  return msm_dev_impl(d_q, pts, n - 1, d_w_xy, false, s);   // w = MSM(q, powers)  (kzg.rs:70)
 }
 
 // ---- open_kzg of MANY short polynomials, polynomial j at its own point u_j (kzg.rs:61-72 once per polynomial, as das/avail.rs:132

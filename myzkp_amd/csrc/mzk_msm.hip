@@ -1684,10 +1684,10 @@ static int msm_take_ws(WsFrame& ws, const MsmWsBytes& b, MsmWs* w) {
 // points_ready (optional, plain points only): called once, after the digit sort has been enqueued and before the first kernel
 // that reads the points -- the host-buffer entry point stages the points onto the device there, so that the transfer of the
 // 64 n bytes of points runs under the sort of the scalars instead of in front of it.
-int msm_dev_impl(const void* d_scalars, const void* d_points, size_t n, int point_kind, size_t table_stride, void* d_out,
-                 bool out_partial_xyzz, hipStream_t s, const std::function<int()>* points_ready, const MsmChunkCtx* cc) {
+int msm_dev_impl(const void* d_scalars, MsmPoints points, size_t n, void* d_out, bool out_partial_xyzz, hipStream_t s,
+                 const std::function<int()>* points_ready, const MsmChunkCtx* cc) {
   WsFrame ws("msm_dev_impl");
-  if (!d_out || ((!d_scalars || !d_points) && n)) { set_error("msm: null pointer"); return MZK_E_ARG; }
+  if (!d_out || ((!d_scalars || !points.d) && n)) { set_error("msm: null pointer"); return MZK_E_ARG; }
   // chunk mode (msm_chunked_impl): the pairs [i0, i0 + n) of a problem of n_total pairs; layout by the whole problem, per-chunk buffers
   // sized for the largest chunk, returns with the chunk's buckets summed (no reduction)
   if (cc && (n < SMALL_MAX_N || n > cc->n_alloc)) { set_error("msm: chunk of %zu pairs (chunks hold 4097 .. %zu)", n, cc->n_alloc); return MZK_E_ARG; }
@@ -1697,7 +1697,7 @@ int msm_dev_impl(const void* d_scalars, const void* d_points, size_t n, int poin
     return MZK_OK;
   }
   const size_t n_shape = cc ? cc->n_total : n, i0 = cc ? cc->i0 : 0;
-  const MsmPlan P = msm_plan(n, n_shape, cc ? cc->n_alloc : n, point_kind, table_stride, ctx().num_cu, cc ? cc->K : 0, msm_knobs());
+  const MsmPlan P = msm_plan(n, n_shape, cc ? cc->n_alloc : n, points.kind, points.stride, ctx().num_cu, cc ? cc->K : 0, msm_knobs());
   if (P.err != MZK_OK) { set_error("%s", P.msg); return P.err; }
   // the caller's slots in chunk mode (every chunk's plan asks for the same bytes), this call's own otherwise
   MsmWs w = {};
@@ -1708,7 +1708,7 @@ int msm_dev_impl(const void* d_scalars, const void* d_points, size_t n, int poin
   u32 *pm = w.points, *counts = w.counts, *offsets = w.offsets + k * (P.NBtot + 1), *ranks = w.cursor, *entries = w.entries + k * P.alloc.E, *scan = w.scan,
       *buckets = w.buckets + k * P.NB * 32, *slots = w.slots + k * P.slot_region_words, *wghist = w.wghist, *wsum = w.out;
   // (a chunk's entries count from its first pair: every table row / the endomorphism images sit at the same distance behind it)
-  const u32* pts = (pm ? pm : (const u32*)d_points) + i0 * 16;
+  const u32* pts = (pm ? pm : (const u32*)points.d) + i0 * 16;
   bool prepared = false;
   auto prepare = [&]() -> int {          // Montgomery form + endomorphism images of plain points; once, before their first reader
     if (prepared) return MZK_OK;
@@ -1716,7 +1716,7 @@ int msm_dev_impl(const void* d_scalars, const void* d_points, size_t n, int poin
     if (points_ready) MZK_TRY((*points_ready)());
     if (!pm) return MZK_OK;
     prof_begin(s, MZK_PH_MSM_PREPARE);
-    MZK_TRY(msm_prepare_points((const u32*)d_points + i0 * 16, n, pm + i0 * 16, pm + (n_shape + i0) * 16, s));
+    MZK_TRY(msm_prepare_points((const u32*)points.d + i0 * 16, n, pm + i0 * 16, pm + (n_shape + i0) * 16, s));
     prof_end(s, MZK_PH_MSM_PREPARE);
     return MZK_OK;
   };
@@ -1816,25 +1816,25 @@ __global__ __launch_bounds__(128) void k_fold_bucket_sets(u32* __restrict__ buck
   for (int k = 1; k < K; k++) acc = xyzz_add_with<FeAsm>(acc, xyzz_gload(buckets, (size_t)k * NB + b));
   xyzz_gstore(buckets, b, acc);
 }
-bool msm_chunkable(size_t n_total, int point_kind, size_t table_stride) { return msm_chunkable(n_total, point_kind, table_stride, msm_knobs()); }
+bool msm_chunkable(size_t n_total, MsmPoints pts) { return msm_chunkable(n_total, pts.kind, pts.stride, msm_knobs()); }
 // Sum over the chunks' pairs = the MSM of all n_total pairs (polynomial.rs:156-165 is a sum over independent pairs; the bucket sums
-// are too).  chunks[k].d_scalars: that chunk's scalars on the device; d_points: the WHOLE point array / table set.  A chunk is sorted
+// are too).  chunks[k].d_scalars: that chunk's scalars on the device; pts: the WHOLE point array / table set.  A chunk is sorted
 // and accumulated as soon as its `ready` event has fired: the host-buffer entry points upload chunk k + 1 meanwhile.  Same canonical
 // affine point as the one-piece call.
-int msm_chunked_impl(const MsmChunk* chunks, int K, const void* d_points, size_t n_total, int point_kind, size_t table_stride, void* d_out,
-                     bool out_partial_xyzz, hipStream_t s, const std::function<int(int)>* before_chunk) {
+int msm_chunked_impl(const MsmChunk* chunks, int K, MsmPoints pts, size_t n_total, void* d_out, bool out_partial_xyzz, hipStream_t s,
+                     const std::function<int(int)>* before_chunk) {
   WsFrame ws("msm_chunked_impl");
-  if (!chunks || K < 1 || K > 8 || !d_out || !d_points) { set_error("msm_chunked: bad argument"); return MZK_E_ARG; }
+  if (!chunks || K < 1 || K > 8 || !d_out || !pts.d) { set_error("msm_chunked: bad argument"); return MZK_E_ARG; }
   size_t n_alloc = 0, covered = 0;
   for (int k = 0; k < K; k++) {
     if (chunks[k].i0 != covered) { set_error("msm_chunked: chunks must be consecutive"); return MZK_E_ARG; }
     covered += chunks[k].n;
     n_alloc = chunks[k].n > n_alloc ? chunks[k].n : n_alloc;
   }
-  if (covered != n_total || !msm_chunkable(n_total, point_kind, table_stride)) { set_error("msm_chunked: chunks do not cover a chunkable problem"); return MZK_E_ARG; }
+  if (covered != n_total || !msm_chunkable(n_total, pts)) { set_error("msm_chunked: chunks do not cover a chunkable problem"); return MZK_E_ARG; }
   // the plan every chunk follows (its largest chunk's): layout, bucket array.  Its slots are taken here, once, and lent to the chunks:
   // K regions in the per-chunk ones, and the bucket array they leave behind is the one summed below.
-  const MsmPlan P = msm_plan(n_alloc, n_total, n_alloc, point_kind, table_stride, ctx().num_cu, K, msm_knobs());
+  const MsmPlan P = msm_plan(n_alloc, n_total, n_alloc, pts.kind, pts.stride, ctx().num_cu, K, msm_knobs());
   if (P.err != MZK_OK) { set_error("%s", P.msg); return P.err; }
   MsmWs w = {};
   MZK_TRY(msm_take_ws(ws, P.ws, &w));
@@ -1845,7 +1845,7 @@ int msm_chunked_impl(const MsmChunk* chunks, int K, const void* d_points, size_t
     if (before_chunk) MZK_TRY((*before_chunk)(k));
     if (chunks[k].ready) MZK_HIP(hipStreamWaitEvent(s, chunks[k].ready, 0));
     const MsmChunkCtx cc{&w, k, K, chunks[k].i0, n_total, n_alloc};
-    MZK_TRY(msm_dev_impl(chunks[k].d_scalars, d_points, chunks[k].n, point_kind, table_stride, d_out, out_partial_xyzz, s, nullptr, &cc));
+    MZK_TRY(msm_dev_impl(chunks[k].d_scalars, pts, chunks[k].n, d_out, out_partial_xyzz, s, nullptr, &cc));
   }
   u32 *buckets = w.buckets, *wsum = w.out;
   if (K > 1) {
@@ -2114,7 +2114,6 @@ int msm_many_dev_impl(const void* d_scalars, size_t n, size_t stride_elems, size
 //                        then the 256 partials -> one by the tree of the small-commit path (quads, the last levels row additions)
 //   k_fold_partials_row  one wave per polynomial: its ceil(n / 256) partials, then the affine conversion (wave inversion)
 constexpr int DIRECT_THREADS = 256;
-size_t msm_direct_bytes(size_t n, int c) { return (size_t)msm_table_windows(c) * n * ((size_t)1 << (c - 1)) * 64; }
 // multiples 1 .. M of `rows` table rows (affine Montgomery) as XYZZ records, row-major: out[(r M + m)] = (m + 1) T[r]
 __global__ __launch_bounds__(64) void k_direct_chain(const u32* __restrict__ rows_mont, size_t rows, int M, u32* __restrict__ out_xyzz) {
   const size_t r = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -2282,41 +2281,6 @@ int msm_direct_many_dev_impl(const void* d_scalars, size_t n, size_t stride_elem
   }
   return MZK_OK;
 }
-bool srs_many_capable(const mzk_srs* srs) { return srs->d_direct != nullptr || (srs->has_tables && srs->sets == 1 && msm_many_supported(srs->window_bits)); }
-// Window width of the bucket pass by polynomial length (same-box sweep, profiles/round5_many_commit_widths.txt: 16 x 2^14 0.884 ms at
-// 10 bits, 0.707 at 12; 32 x 2^13 0.842 / 0.713; 64 x 2^12 0.730 / 0.752; 128 x 2^11 0.755 / 1.236): 12 bits from 2^13 coefficients on.
-constexpr size_t MANY_WIDE_FROM = (size_t)1 << 13;
-constexpr int MANY_WIDE_BITS = 12;
-int msm_many_srs(const mzk_srs* srs, const void* d_scalars, size_t n, size_t stride_elems, size_t count, void* d_out, hipStream_t s,
-                 size_t shift) {
-  if (shift && shift + n > srs->n) { set_error("msm_many: points [%zu, %zu) past the handle's %zu", shift, shift + n, srs->n); return MZK_E_LENGTH; }
-  if (srs->d_direct)      // D[(w n + i) 2^(c-1) + m]: point i's multiples are 2^(c-1) records of 64 bytes
-    return msm_direct_many_dev_impl(d_scalars, n, stride_elems, count, (const char*)srs->d_direct + shift * ((size_t)1 << (srs->direct_bits - 1)) * 64,
-                                    srs->direct_bits, srs->n, d_out, s);
-  if (n >= MANY_WIDE_FROM && srs->has_tables && srs->sets == 1 && srs->window_bits < MANY_WIDE_BITS) {
-    if (!srs->d_tables_wide && srs->wide_bits == 0) {       // once per handle: row 0 of its own tables are the prepared points
-      const size_t bytes = (size_t)msm_table_windows(MANY_WIDE_BITS) * srs->n * 64;
-      const size_t own = (size_t)srs->n * 64 * srs->table_rows() + srs->direct_bytes;
-      void* t = nullptr;
-      // the caller's table budget (mzk_set_table_budget) covers these tables too; a refusal -- budget or device -- is remembered on the
-      // handle (wide_bits = -1), so that later batches do not repeat a failing hipMalloc and the idle-workspace release it triggers,
-      // and the message of the refused allocation does not stay behind on a call that returns MZK_OK
-      const bool within_budget = table_budget_bytes() == 0 || own + bytes <= table_budget_bytes();
-      if (within_budget && dev_alloc(&t, bytes, "wide window tables of the grid-batched pass") == MZK_OK) {
-        const int rc = msm_build_tables(srs->d_points_mont, srs->n, t, MANY_WIDE_BITS, s);
-        if (rc != MZK_OK) { (void)ws_hook_free(t); return rc; }
-        srs->d_tables_wide = t; srs->wide_bits = MANY_WIDE_BITS; srs->wide_bytes = bytes;
-      } else {
-        srs->wide_bits = -1;         // no memory (or no budget) for them: the handle's own tables serve (slower, same points)
-        if (within_budget) clear_error();
-      }
-    }
-    if (srs->d_tables_wide)
-      return msm_many_dev_impl(d_scalars, n, stride_elems, count, (const char*)srs->d_tables_wide + shift * 64, srs->wide_bits, srs->n, d_out, s);
-  }
-  return msm_many_dev_impl(d_scalars, n, stride_elems, count, (const char*)srs->d_points_mont + shift * 64, srs->window_bits, srs->n, d_out, s);
-}
-
 int msm_fold_partials_impl(const void* d_partials, int count, void* d_out_xy, hipStream_t s) {
   if (!d_partials || !d_out_xy || count < 0) { set_error("fold_partials: bad argument"); return MZK_E_ARG; }
   MZK_TRY(launch_fold_partials_row((const u32*)d_partials, count, (u32*)d_out_xy, s));

@@ -11,6 +11,7 @@
 // Several contexts may name the same device ordinal, so the whole path -- W streams, W workspaces, gather, fold --
 // runs on a one-GPU box too (tests/cpp/test_multi_device.cpp, tests/test_gpu_multi.py).
 #include "mzk_common.h"
+#include "mzk_srs.h"
 
 using namespace mzk;
 
@@ -18,7 +19,7 @@ struct mzk_srs_multi {
   int world;
   size_t n;
   size_t lo[MZK_MAX_CTX + 1];
-  mzk_srs* shard[MZK_MAX_CTX];
+  mzk::SrsOwner shard[MZK_MAX_CTX];
 };
 
 namespace mzk {
@@ -250,23 +251,18 @@ int mzk_msm_g1_bn254_multi(const uint64_t* scalars, const uint64_t* points_xy, s
       MZK_HIP(hipMemcpyAsync(d_s, scalars + 4 * lo, m * 32, hipMemcpyHostToDevice, s));
       MZK_HIP(hipMemcpyAsync(d_p, points_xy + 8 * lo, m * 64, hipMemcpyHostToDevice, s));
     }
-    MZK_TRY(msm_dev_impl(d_s, d_p, m, MSM_PTS_PLAIN, 0, d_o, true, s));
+    MZK_TRY(msm_dev_impl(d_s, MsmPoints::plain(d_p), m, d_o, true, s));
     MZK_HIP(hipMemcpyAsync(h_rec + 16 * r, d_o, 128, hipMemcpyDeviceToHost, s));
   }
   return gather_and_fold(world, h_rec, out_xy);
 }
 
-void mzk_srs_multi_free(mzk_srs_multi* h) {
-  if (!h) return;
-  for (int r = 0; r < h->world; r++) mzk_srs_free(h->shard[r]);
-  delete h;
-}
+void mzk_srs_multi_free(mzk_srs_multi* h) { delete h; }
 
-static mzk_srs_multi* new_multi(size_t n) {
-  mzk_srs_multi* h = new mzk_srs_multi();
+static std::unique_ptr<mzk_srs_multi> new_multi(size_t n) {
+  auto h = std::make_unique<mzk_srs_multi>();
   h->world = ctx_count();
   h->n = n;
-  for (int r = 0; r < MZK_MAX_CTX; r++) h->shard[r] = nullptr;
   for (int r = 0; r < h->world; r++) {
     size_t hi;
     shard_range(n, r, h->world, &h->lo[r], &hi);
@@ -278,13 +274,15 @@ static mzk_srs_multi* new_multi(size_t n) {
 int mzk_srs_upload_multi(const uint64_t* powers_xy, size_t n, mzk_srs_multi** out) {
   MZK_ENTER();
   if (!out || (!powers_xy && n)) { set_error("srs_upload_multi: null pointer"); return MZK_E_ARG; }
-  mzk_srs_multi* h = new_multi(n);
+  std::unique_ptr<mzk_srs_multi> h = new_multi(n);
   for (int r = 0; r < h->world; r++) {
     CtxScope sc(r);
-    int rc = sc.ok ? mzk_srs_upload(powers_xy + 8 * h->lo[r], h->lo[r + 1] - h->lo[r], &h->shard[r]) : MZK_E_ARG;
-    if (rc != MZK_OK) { mzk_srs_multi_free(h); return rc; }
+    if (!sc.ok) return MZK_E_ARG;
+    mzk_srs* shard = nullptr;
+    MZK_TRY(mzk_srs_upload(powers_xy + 8 * h->lo[r], h->lo[r + 1] - h->lo[r], &shard));
+    h->shard[r].reset(shard);
   }
-  *out = h;
+  *out = h.release();
   return MZK_OK;
 }
 
@@ -293,7 +291,7 @@ int mzk_srs_upload_multi(const uint64_t* powers_xy, size_t n, mzk_srs_multi** ou
 int mzk_kzg_setup_srs_multi(const uint64_t alpha[4], const uint64_t g1_xy[8], size_t max_d, int with_tables, mzk_srs_multi** out) {
   MZK_ENTER();
   if (!out || !alpha || !g1_xy) { set_error("setup_srs_multi: null pointer"); return MZK_E_ARG; }
-  mzk_srs_multi* h = new_multi(max_d + 1);
+  std::unique_ptr<mzk_srs_multi> h = new_multi(max_d + 1);
   DevMem tmp[MZK_MAX_CTX];
   int rc = MZK_OK;
   // enqueue every context's setup first (they run concurrently), then build the handles (each synchronises its stream)
@@ -308,11 +306,13 @@ int mzk_kzg_setup_srs_multi(const uint64_t alpha[4], const uint64_t g1_xy[8], si
   for (int r = 0; r < h->world && rc == MZK_OK; r++) {
     CtxScope sc(r);
     if (!sc.ok) { rc = MZK_E_ARG; break; }
-    rc = mzk_srs_from_device_ex(tmp[r].get(), h->lo[r + 1] - h->lo[r], with_tables, &h->shard[r], ctx().stream);
+    mzk_srs* shard = nullptr;
+    rc = mzk_srs_from_device_ex(tmp[r].get(), h->lo[r + 1] - h->lo[r], with_tables, &shard, ctx().stream);
+    h->shard[r].reset(shard);
   }
   for (int r = 0; r < h->world; r++) if (tmp[r]) { CtxScope sc(r); (void)hipStreamSynchronize(ctx().stream); tmp[r].reset(); }
-  if (rc != MZK_OK) { mzk_srs_multi_free(h); return rc; }
-  *out = h;
+  if (rc != MZK_OK) return rc;
+  *out = h.release();
   return MZK_OK;
 }
 
@@ -346,8 +346,8 @@ static int commit_multi(const mzk_srs_multi* h, const uint64_t* host_coef, const
       d_s = (void*)d_coef_shards[r];
       if (!d_s) { set_error("commit_srs_multi_dev: null shard pointer for context %d", r); return MZK_E_ARG; }
     }
-    const mzk_srs* sh = h->shard[r];
-    MZK_TRY(msm_dev_impl(d_s ? d_s : d_o, sh->d_points_mont, m, sh->kind(), sh->n, d_o, true, s));
+    const mzk_srs* sh = h->shard[r].get();
+    MZK_TRY(msm_dev_impl(d_s ? d_s : d_o, sh->points(), m, d_o, true, s));
     MZK_HIP(hipMemcpyAsync(h_rec + 16 * r, d_o, 128, hipMemcpyDeviceToHost, s));
   }
   return gather_and_fold(h->world, h_rec, out_xy);

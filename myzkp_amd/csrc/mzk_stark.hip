@@ -217,21 +217,15 @@ struct mzk_stark {
   std::vector<uint32_t> exps;
   std::vector<size_t> toff;
   mzk_stark_dims dims;                   // without a boundary
-  char *d_tz = nullptr, *d_tz_cw = nullptr, *d_vals = nullptr, *d_point = nullptr, *d_bq = nullptr, *d_cw = nullptr, *d_tpoly = nullptr, *d_tq = nullptr,
-       *d_lin = nullptr, *d_comb = nullptr, *d_comb_cw = nullptr, *d_fri = nullptr, *d_stage = nullptr;
+  struct Buf : mzk::DevMem { operator char*() const { return as<char>(); } };       // read as the char* it owns
+  Buf d_tz, d_tz_cw, d_vals, d_point, d_bq, d_cw, d_tpoly, d_tq, d_lin, d_comb, d_comb_cw, d_fri, d_stage;
   size_t stage_bytes = 0;
   mzk_merkle* tz_tree = nullptr;
   uint8_t tz_root[32];
+  ~mzk_stark() { if (tz_tree) mzk_merkle_free(tz_tree); }
 };
 
 namespace mzk {
-static void stark_release(mzk_stark* h) {
-  if (!h) return;
-  for (char* p : {h->d_tz, h->d_tz_cw, h->d_vals, h->d_point, h->d_bq, h->d_cw, h->d_tpoly, h->d_tq, h->d_lin, h->d_comb, h->d_comb_cw, h->d_fri, h->d_stage})
-    if (p) (void)ws_hook_free(p);
-  if (h->tz_tree) mzk_merkle_free(h->tz_tree);
-  delete h;
-}
 #define STARK_TRY(x) do { int _rc = (x); if (_rc != MZK_OK) return fail(_rc); } while (0)
 #define STARK_HIP(x) do { if ((x) != hipSuccess) { set_error("stark_prove: %s failed", #x); return fail(MZK_E_HIP); } } while (0)
 
@@ -387,16 +381,15 @@ int mzk_stark_new(int field_id, size_t expansion_factor, size_t num_colinearity_
   if (nterms && !term_coefs) { set_error("stark_new: null pointer"); return MZK_E_ARG; }
   if (!h_is_canonical(hf, generator)) { set_error("stark_new: generator not canonical"); return MZK_E_RANGE; }
   if (num_cycles < 2) { set_error("stark_new: a trace of one cycle has no transition"); return MZK_E_LENGTH; }
-  mzk_stark* h = new mzk_stark();
-  auto fail = [&](int rc) { stark_release(h); return rc; };
+  std::unique_ptr<mzk_stark> h(new mzk_stark());
   h->fid = field_id; h->ctx_index = ctx().index;
   h->e = expansion_factor; h->checks = num_colinearity_checks; h->m = num_registers; h->cycles = num_cycles; h->degree = transition_constraints_degree;
   h->nc = n_constraints; h->nv = d.n_vars; h->rl = d.randomized_trace_length; h->olen = d.omicron_domain_length; h->flen = d.fri_domain_length;
   h->dims = d;
   memset(h->g, 0, sizeof h->g); memset(h->omega, 0, sizeof h->omega); memset(h->omicron, 0, sizeof h->omicron);
   memcpy(h->g, generator, 8 * nl);
-  STARK_TRY(mzk_root_of_unity(field_id, bit_length(h->flen) - 1, h->omega));
-  STARK_TRY(mzk_root_of_unity(field_id, bit_length(h->olen) - 1, h->omicron));
+  MZK_TRY(mzk_root_of_unity(field_id, bit_length(h->flen) - 1, h->omega));
+  MZK_TRY(mzk_root_of_unity(field_id, bit_length(h->olen) - 1, h->omicron));
   h->toff.assign(term_offsets, term_offsets + n_constraints + 1);
   for (size_t& o : h->toff) o -= term_offsets[0];
   h->coefs.assign(term_coefs + term_offsets[0] * nl, term_coefs + term_offsets[n_constraints] * nl);
@@ -410,16 +403,16 @@ int mzk_stark_new(int field_id, size_t expansion_factor, size_t num_colinearity_
   std::vector<size_t> poff(h->nv + 1, 0);
   for (size_t i = 1; i <= h->nv; i++) poff[i] = 2 + (i - 1) * h->rl;
   size_t ntr = 0;
-  STARK_TRY(mzk_mpoly_compose_plan(field_id, h->exps.data(), h->toff.data(), h->nc, h->nv, poff.data(), &ntr, &h->cstride, nullptr));
+  MZK_TRY(mzk_mpoly_compose_plan(field_id, h->exps.data(), h->toff.data(), h->nc, h->nv, poff.data(), &ntr, &h->cstride, nullptr));
   if (h->cstride == 0) h->cstride = 1;
   // preprocess (:52-75): fast_zerofier over omicron^0 .. omicron^(T-2), its codeword, its tree
   const size_t nz = h->cycles - 1;
   size_t cap = 1;
   while (cap < nz + 1) cap <<= 1;
   std::vector<uint64_t> tz((cap + 1) * nl, 0);
-  STARK_TRY(mzk_fast_zerofier(field_id, h->domain.data(), nz, h->omicron, h->olen, tz.data(), &h->tz_len));
+  MZK_TRY(mzk_fast_zerofier(field_id, h->domain.data(), nz, h->omicron, h->olen, tz.data(), &h->tz_len));
   const size_t lin = d.randomizer_length + 2 * h->nc * h->cstride + 2 * h->m * h->rl;
-  struct { char** p; size_t bytes; } bufs[] = {{&h->d_tz, (h->tz_len + 1) * esz}, {&h->d_tz_cw, h->flen * esz}, {&h->d_vals, (h->m * h->rl + 1) * esz},
+  struct { mzk_stark::Buf* p; size_t bytes; } bufs[] = {{&h->d_tz, (h->tz_len + 1) * esz}, {&h->d_tz_cw, h->flen * esz}, {&h->d_vals, (h->m * h->rl + 1) * esz},
                                                {&h->d_point, (2 + 2 * h->m * h->rl) * esz}, {&h->d_bq, (h->m * h->rl + 1) * esz},
                                                {&h->d_cw, (h->m + 1) * h->flen * esz}, {&h->d_tpoly, h->nc * h->cstride * esz},
                                                {&h->d_tq, h->nc * h->cstride * esz}, {&h->d_lin, lin * esz}, {&h->d_comb, (d.max_degree + 1) * esz},
@@ -429,7 +422,7 @@ int mzk_stark_new(int field_id, size_t expansion_factor, size_t num_colinearity_
     mzk_tx::fri_layout(h->flen, h->e, h->checks, (int)nl, &L);
     bufs[sizeof bufs / sizeof bufs[0] - 1].bytes = L.total + 64;
   }
-  for (auto& b : bufs) STARK_TRY(dev_alloc((void**)b.p, b.bytes, "stark handle"));
+  for (auto& b : bufs) MZK_TRY(b.p->alloc(b.bytes, "stark handle"));
   hipStream_t s = ctx().stream;
   WsGuard wsg(s);
   uint64_t x[8] = {0, 0, 0, 0, 0, 0, 0, 0};
@@ -437,16 +430,16 @@ int mzk_stark_new(int field_id, size_t expansion_factor, size_t num_colinearity_
   if (hipMemcpyAsync(h->d_point, x, 2 * esz, hipMemcpyHostToDevice, s) != hipSuccess ||
       hipMemcpyAsync(h->d_tz, tz.data(), h->tz_len * esz, hipMemcpyHostToDevice, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess) {
     set_error("stark_new: upload failed");
-    return fail(MZK_E_HIP);
+    return MZK_E_HIP;
   }
-  STARK_TRY(coset_lde_dev_impl(field_id, h->d_tz, h->tz_len, h->g, h->omega, h->d_tz_cw, h->flen, s));
-  STARK_TRY(mzk_merkle_build_field_dev(field_id, h->d_tz_cw, h->flen, &h->tz_tree, s));
+  MZK_TRY(coset_lde_dev_impl(field_id, h->d_tz, h->tz_len, h->g, h->omega, h->d_tz_cw, h->flen, s));
+  MZK_TRY(mzk_merkle_build_field_dev(field_id, h->d_tz_cw, h->flen, &h->tz_tree, s));
   size_t len = 0;
-  STARK_TRY(mzk_merkle_root(h->tz_tree, h->tz_root, 32, &len));
-  *out = h;
+  MZK_TRY(mzk_merkle_root(h->tz_tree, h->tz_root, 32, &len));
+  *out = h.release();
   return MZK_OK;
 }
-void mzk_stark_free(mzk_stark* h) { stark_release(h); }
+void mzk_stark_free(mzk_stark* h) { delete h; }
 int mzk_stark_transition_zerofier_root(const mzk_stark* h, uint8_t root[32]) {
   if (!h || !root) { set_error("stark: null pointer"); return MZK_E_ARG; }
   memcpy(root, h->tz_root, 32);
@@ -487,8 +480,9 @@ int mzk_stark_prove(mzk_stark* h, const uint64_t* trace, size_t n_rows, const si
   for (size_t i = 0; i < n_boundary; i++) if (!h_is_canonical(hf, boundary_values + i * nl)) { set_error("stark_prove: boundary value %zu not canonical", i); return MZK_E_RANGE; }
   const size_t need = (nt + nr + 2) * esz + total + 64;
   if (need > h->stage_bytes) {
-    if (h->d_stage) { (void)hipDeviceSynchronize(); (void)ws_hook_free(h->d_stage); h->d_stage = nullptr; h->stage_bytes = 0; }
-    MZK_TRY(dev_alloc((void**)&h->d_stage, need, "stark staging"));
+    if (h->d_stage) (void)hipDeviceSynchronize();      // an earlier call's enqueued work may still read the old buffer
+    h->stage_bytes = 0;
+    MZK_TRY(h->d_stage.alloc(need, "stark staging"));
     h->stage_bytes = need;
   }
   hipStream_t s = ctx().stream;

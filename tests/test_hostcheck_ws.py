@@ -50,12 +50,29 @@ def test_rule(run, rule):
     assert "ok " + rule in run.stdout.splitlines(), RULES[rule] + "\n" + run.stdout[-2000:] + run.stderr[-2000:]
 
 
-@pytest.mark.parametrize("call", ["hipMalloc(", "hipFree("])
-def test_device_memory_has_one_way_in_and_one_way_out(call):
-    """every allocation passes ws_hook_alloc and every release ws_hook_free, both in mzk_api.hip, where mzk_ws.h meets the device"""
+def occurrences(call):
     hits = []
     for name in sorted(os.listdir(CSRC)):
         if name.endswith((".hip", ".h")):
             with open(os.path.join(CSRC, name)) as f:
                 hits += [(name, no) for no, line in enumerate(f, 1) for _ in range(line.count(call))]
+    return hits
+
+
+@pytest.mark.parametrize("call", ["hipMalloc(", "hipFree("])
+def test_device_memory_has_one_way_in_and_one_way_out(call):
+    """every allocation passes ws_hook_alloc and every release ws_hook_free, both in mzk_api.hip, where mzk_ws.h meets the device"""
+    hits = occurrences(call)
     assert [name for name, _ in hits] == ["mzk_api.hip"], hits
+
+
+def test_only_the_owner_types_release_device_memory():
+    """ws_hook_free is defined in mzk_api.hip and called by mzk_ws.h (the workspace, WsBlock, DevMem) alone: no handle frees by hand"""
+    hits = occurrences("ws_hook_free(")
+    assert {name for name, _ in hits} == {"mzk_api.hip", "mzk_ws.h"}, hits
+    assert [name for name, _ in hits].count("mzk_api.hip") == 1, hits
+
+
+def test_an_srs_handle_is_made_in_one_place():
+    hits = occurrences("new mzk_srs")
+    assert [name for name, _ in hits] == ["mzk_srs.h"], hits
